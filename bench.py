@@ -870,6 +870,16 @@ def latency_leg(local_rank):
 
 
 # --------------------------------------------------------------------------------------------- launcher
+def dump_outputs(out_dir, res):
+    """The heaps of the headline's last timed step, as its caller receives them: keys [NQ][R] (uint32, kept exactly in float64),
+    int8 distance sums [NQ][R], heap sizes and status [NQ] (float32).  The inputs are seeded, so two builds compare array for
+    array."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in res.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype == np.uint32 else np.float32))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves — as CHILD processes, from a parent
     that never touches the GPU (no exec of a GPU-initialised process) — and relay rank 0's JSON line."""
@@ -883,6 +893,8 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", args.dump_outputs]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=None)
@@ -905,8 +917,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned (neighbour keys, int8 "
+                         "distance sums, heap sizes, status) as DIR/<name>.npy")
     ap.add_argument("--pmc-leg", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.pmc_leg:
         return pmc_leg_main()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1158,6 +1175,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     prof = idx.profile()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("keys", "values", "sizes"), last)) if use_dist else last)
 
     # ---- Recall@100 against the exact float-ADC nearest code, last batch, untimed ----
     tb = pool[(args.steps - 1) % len(pool)]

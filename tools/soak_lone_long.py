@@ -2,7 +2,7 @@
 lengths 2.5 x 10^5 ... 3 x 10^6, keep, R, table kinds; status, qmin, qmax, the int8 table and the heap against the oracle.
 python tools/soak_lone_long.py <stream>;  N=<configurations> (recorded in profiles/r06_fuzz_soak_final.txt)."""
 import os, sys, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "quick-adc_amd")); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import numpy as np
 import pyqadc, pyoracle as po

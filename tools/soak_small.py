@@ -2,7 +2,7 @@
 regrown, fresh index per configuration) against the oracle — the neighbourhood of the one unreproduced failure of the round-6 fuzz soak
 (profiles/r06_fuzz_soak_final.txt).  python tools/soak_small.py <stream> [lib tag];  N=<configurations>; run several streams at once."""
 import os, sys, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "quick-adc_amd")); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
 os.environ["QADC_TEST_HOOKS"] = "1"; os.environ["QADC_WGQ"] = os.environ.get("WGQ", "2"); os.environ["QADC_HEAD_LEVEL"] = "0"
 import numpy as np

@@ -276,8 +276,8 @@ int qadc_pq_encode_host_mode(int M, int dim, const float* codebooks, const float
 
 /* N4, the rest of the build path (host buffers in and out, any device).
  * qadc_ivf_encode_host = the compute of index_db::add_vectors (databases.hpp:270-298) / flat_db::add_vectors (136-156):
- *   nearest coarse centroid per vector (K > 0; find_k_neighbors with k = 1 on the expansion distances: first strict
- *   minimum), residual, optional OPQ rotation rotated[r] = sum_c x[c] * rotation[r][c] (quantizers.hpp:289-301; rotation
+ *   nearest coarse centroid per vector (K > 0; find_k_neighbors with k = 1 on the expansion distances: its compiled replace
+ *   test !(d >= kept), the first strict minimum after the last NaN), residual, optional OPQ rotation rotated[r] = sum_c x[c] * rotation[r][c] (quantizers.hpp:289-301; rotation
  *   [dim][dim] or NULL), PQ encode (quantizers.hpp:222-245; qadc_pq_encode above, _mode likewise).  assign_out [n]
  *   (nullable; untouched when K == 0), codes [n][M/2].  The caller dispatches (assign, code, label = index + offset) to its partitions in vector order
  *   like databases.hpp:291-297 (host/db_build.hpp does).
@@ -294,6 +294,12 @@ int qadc_ivf_encode_host_mode(int M, int dim, const float* codebooks, const floa
                               int sum_mode, int device_id);
 int qadc_kmeans_iterations_host(const float* vectors, uint64_t n, int dim, int K, float* centroids, int iters,
                                 int32_t* assign_out, int device_id);
+/* qadc_coarse_assign_host = find_k_neighbors (neighbors.cpp:30-76) with k = ma on the coarse centroids, as qadc_search's front
+ *   computes it (the expansion distances, then the reference's heap selection AS COMPILED, NaN and exact ties included):
+ *   queries [nq][dim], coarse [K][dim] -> assign_out [nq][ma], nearest first; 0 < ma <= K.  Every entry is in [0, K).
+ *   A query with a NaN distance and ma > 256 is refused (QADC_E_ARG): the exact replay keeps at most 256 entries. */
+int qadc_coarse_assign_host(const float* queries, int nq, const float* coarse, int K, int dim, int ma, int32_t* assign_out,
+                            int device_id);
 int qadc_kmeans_iterations_host_mode(const float* vectors, uint64_t n, int dim, int K, float* centroids, int iters,
                                      int32_t* assign_out, int div_mode, int device_id);
 

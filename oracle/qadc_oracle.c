@@ -243,6 +243,20 @@ void orc_sort_keys_i8(int size, const uint32_t* heap_keys, const int8_t* heap_va
  * as the int8 heap's), then kv_binheap::sort (118-127) writes keys and values in std::sort's order of the permutation.
  * The distances are GIVEN (the reference's come from cblas_sgemm).  Pinned to the reference's own text
  * (oracle/_ref/libqadc_ref_float.so: qadc_reff_select_k_neighbors) by tests/test_oracle_float_ref.py, exact ties included.
+ *
+ * Non-finite distances.  The reference is compiled with -ffast-math, so what it does on a NaN is decided by the
+ * instructions g++ chose, not by the source's operators.  Read off the reference build (objdump -d, x86-64, AT&T order;
+ * "vcomiss b,a" sets the flags of a ? b, and an unordered result sets ZF = PF = CF = 1):
+ *   sift-up     vcomiss parent,value ; ja  (swap)        -> swap iff value > parent            (IEEE '>', as written)
+ *   replace     vcomiss top,value    ; jae (skip)        -> replace iff !(value >= top)        (NOT '<': a NaN replaces
+ *                                                            the top, and any value replaces a NaN top)
+ *   sift-down   vcomiss left,right   ; jbe (keep left)   -> right child iff right > left       (IEEE '>', as written)
+ *               vcomiss largest,value; jb  (swap)        -> swap iff !(value >= largest)       (= the source's
+ *                                                            "largest <= value: break" under IEEE)
+ *   std::sort   kv_binheap<int, float>::comparator is out of line and every std::sort helper calls it indirectly:
+ *               vcomiss v[a],v[b]    ; seta              -> v[a] < v[b]                        (IEEE '<', as written)
+ * So the replace test is the one comparison whose compiled predicate differs from its source on a NaN; it is written out
+ * below as !(value >= top), which this file's strict-IEEE build (-ffp-contract=off, no fast-math) keeps as it stands.
  * ---------------------------------------------------------------------------------------- */
 void orc_select_k_neighbors(const float* dists, long count, int neighbor_count, int k, int32_t* assign, float* sorted) {
     float* hv = (float*)malloc(sizeof(float) * (size_t)(k > 0 ? k : 1));
@@ -263,7 +277,7 @@ void orc_select_k_neighbors(const float* dists, long count, int neighbor_count, 
                     index = parent;
                     parent = (index - 1) / 2;
                 }
-            } else if (value < hv[0]) {                                       /* 93-115 */
+            } else if (!(value >= hv[0])) {                                   /* 93-115: the compiled replace test */
                 int index = 0;
                 hv[0] = value; hk[0] = n;
                 for (;;) {
@@ -271,7 +285,7 @@ void orc_select_k_neighbors(const float* dists, long count, int neighbor_count, 
                     if (left >= size) break;
                     int largest = left;
                     if (right < size && hv[right] > hv[left]) largest = right;
-                    if (hv[largest] <= hv[index]) break;
+                    if (hv[index] >= hv[largest]) break;                      /* jb: swap iff !(value >= largest) */
                     const float tv = hv[index]; hv[index] = hv[largest]; hv[largest] = tv;
                     const int tk = hk[index]; hk[index] = hk[largest]; hk[largest] = tk;
                     index = largest;
@@ -724,8 +738,9 @@ void orc_tables_expansion(int dsq, int M, const float* centroids, const float* v
 /* ------------------------------------------------------------------------------------------
  * base_pq::encode_multiple_vectors — quantizers.hpp:222-245 (opq: rotate_multiple_vectors first, 289-301): per
  * sub-quantizer extract the sub-vectors (86-94), find_k_neighbors(count, 16, sq_dim, k = 1, ...) (neighbors.cpp:30-76:
- * the expansion distances of orc_cross_dists, pushed in centroid order into a capacity-1 kv_binheap — the first strict
- * minimum, the first centroid when its distance is NaN), multiple_set_bits_4 (49-68).
+ * the expansion distances of orc_cross_dists, pushed in centroid order into a capacity-1 kv_binheap — with the compiled
+ * replace test !(d >= kept): the first strict minimum after the last NaN, or the last centroid when its distance is NaN),
+ * multiple_set_bits_4 (49-68).
  *   form 1 = that (the reference's); form 0 = the direct form sum (x - c)^2 in one sequential loop, first minimum (this
  *   repository's encoder before round 6, kept as an option).
  * rotation (nullable) [dim][dim]: rotated[r] = sum_c x[c] * rotation[r][c], one sequential float sum (the reference's is

@@ -16,6 +16,7 @@ int qadc_pq_encode_mode(int M, int dim, const float* codebooks, const void* d_ve
                         int sum_mode, int device_id) {
     if ((M != 16 && M != 32) || dim <= 0 || dim % M != 0 || !codebooks || (n && (!d_vectors || !d_codes)))
         return fail(QADC_E_ARG, "bad arguments");
+    if (dim > kPqEncodeMaxDim) return fail(QADC_E_ARG, "dim must be <= 2048 (the encoder keeps the codebooks in LDS)");
     HIPCHECK(hipSetDevice(device_id));
     const size_t ncb = (size_t)M * 16 * (dim / M);
     float* d_cb = nullptr;
@@ -92,6 +93,7 @@ int qadc_ivf_encode_host_mode(int M, int dim, const float* codebooks, const floa
     if ((M != 16 && M != 32) || dim <= 0 || dim % M != 0 || !codebooks || K < 0 || (K > 0 && !coarse) ||
         (n && (!vectors || !codes)))
         return fail(QADC_E_ARG, "bad arguments");
+    if (dim > kPqEncodeMaxDim) return fail(QADC_E_ARG, "dim must be <= 2048 (the encoder keeps the codebooks in LDS)");
     HIPCHECK(hipSetDevice(device_id));
     ScratchFree mem;
     const size_t ncb = (size_t)M * 16 * (dim / M);
@@ -126,6 +128,34 @@ int qadc_ivf_encode_host_mode(int M, int dim, const float* codebooks, const floa
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(codes, d_codes, n * (size_t)(M / 2), hipMemcpyDeviceToHost));
     if (assign_out && K > 0) HIPCHECK(hipMemcpy(assign_out, d_assign, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return QADC_OK;
+}
+
+int qadc_coarse_assign_host(const float* queries, int nq, const float* coarse, int K, int dim, int ma, int32_t* assign_out,
+                            int device_id) {
+    if (!queries || !coarse || !assign_out || nq <= 0 || K <= 0 || dim <= 0 || ma <= 0 || ma > K || nq >= (1 << 24))
+        return fail(QADC_E_ARG, "bad arguments (need nq > 0, 0 < ma <= K)");
+    HIPCHECK(hipSetDevice(device_id));
+    ScratchFree mem;
+    float *d_q = nullptr, *d_c = nullptr, *d_dist = nullptr, *d_qnorm = nullptr, *d_cnorm = nullptr;
+    int32_t* d_assign = nullptr;
+    HIPCHECK(mem.alloc(&d_q, sizeof(float) * (size_t)nq * dim));
+    HIPCHECK(mem.alloc(&d_c, sizeof(float) * (size_t)K * dim));
+    HIPCHECK(mem.alloc(&d_dist, sizeof(float) * (size_t)nq * K));
+    HIPCHECK(mem.alloc(&d_qnorm, sizeof(float) * (size_t)nq));
+    HIPCHECK(mem.alloc(&d_cnorm, sizeof(float) * (size_t)K));
+    HIPCHECK(mem.alloc(&d_assign, sizeof(int32_t) * (size_t)nq * ma));
+    HIPCHECK(hipMemcpy(d_q, queries, sizeof(float) * (size_t)nq * dim, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(d_c, coarse, sizeof(float) * (size_t)K * dim, hipMemcpyHostToDevice));
+    HIPCHECK(coarse_nan_unreplayed_reset(nullptr));
+    launch_row_sqnorm(d_c, K, dim, 1, d_cnorm, nullptr);
+    launch_coarse_assign(d_q, d_c, nq, K, dim, ma, d_qnorm, d_cnorm, 1, d_dist, d_assign, nullptr);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    unsigned int unreplayed = 0;
+    HIPCHECK(coarse_nan_unreplayed_read(&unreplayed));
+    if (unreplayed) return fail(QADC_E_ARG, "a query has a NaN coarse distance and ma > 256: the reference's heap replay is not available");
+    HIPCHECK(hipMemcpy(assign_out, d_assign, sizeof(int32_t) * (size_t)nq * ma, hipMemcpyDeviceToHost));
     return QADC_OK;
 }
 

@@ -313,8 +313,13 @@ void launch_kmeans_update(const float* d_vectors, uint64_t n, int dim, int K, co
 // sequential dot) into d_dist [nq][K], then the ma nearest per query as its heaps select them (exact ties included) into
 // d_assign [nq][ma].  d_cnorm [K] = launch_row_sqnorm of the centroids (the caller's, once per centroid set); d_qnorm [nq] scratch.
 void launch_row_sqnorm(const float* d_rows, int n, int dim, int sum_mode, float* d_out, hipStream_t stream);
+// Requires ma <= K: every assign[] entry is then an index in [0, K), whatever the distances (NaN, +inf, FLT_MAX included).
+// A row with a NaN distance takes the reference's heap replay (its compiled predicates); with ma > 256 that replay is not
+// available and the row is counted instead: reset / read the count around the launch (coarse_nan_unreplayed_*) to refuse it.
 void launch_coarse_assign(const float* d_queries, const float* d_coarse, int nq, int K, int dim, int ma, float* d_qnorm,
                           const float* d_cnorm, int sum_mode, float* d_dist, int32_t* d_assign, hipStream_t stream);
+hipError_t coarse_nan_unreplayed_reset(hipStream_t stream);
+hipError_t coarse_nan_unreplayed_read(unsigned int* count);     // (synchronous)
 // Residual + per-query distance tables (compute_dists_single_simd_cg's result, distances.hpp:294-311):
 // tables[q][a][m][c] = sum_d ((x - centroid[assign])[m*ds+d] - codebook[m][c][d])^2; sum_mode 1: added like the
 // reference's fmanorm as compiled (AVX lanes + fused multiply-add + reduceadd tree: direct_sqdist in qadc_kernels.hip),
@@ -349,6 +354,9 @@ void launch_prescan_minmax(const float* d_vals, uint32_t nvals, int nq, QuerySta
 
 // PQ encode of device-resident vectors [n][dim] with codebooks [M][16][dim/M] -> codes [n][M/2].  form 1 = the reference's
 // (find_k_neighbors with k = 1 on the BLAS-expansion distances), 0 = direct sum (x - c)^2; sum_mode: the norms' grouping.
+// dim <= kPqEncodeMaxDim (the codebooks live in LDS).
+constexpr int kPqEncodeMaxDim = 2048;
+constexpr size_t kPqEncodeMaxLds = ((size_t)16 * kPqEncodeMaxDim + 32 * 16) * sizeof(float);
 void launch_pq_encode(const float* d_vectors, uint64_t n, int M, int dim, const float* d_codebooks, int form, int sum_mode,
                       uint8_t* d_codes, hipStream_t stream);
 

@@ -2113,15 +2113,43 @@ __device__ __forceinline__ float expansion_dist(const X& x, const C& c, int ds, 
     return (vn + cn) + (-2.0f * dot);
 }
 
-// called by every lane of wave 0 (lane = 0..63); dq = the query's K distances in global memory
+// Rows with a NaN distance (any query: one workgroup's barrier-wide OR; uniform result).  NaN breaks the (distance, index) order
+// the fast selections rest on — the reference's compiled heap lets a NaN replace the top (coarse_exact_select) — so such a row is
+// replayed exactly.  The replay's heap lives in LDS arrays of 256: a NaN row with ma > 256 is counted in g_coarse_nan_unreplayed
+// instead (its assign[] still holds indices in [0, K)), and the entry points that read the counter fail.
+__device__ unsigned int g_coarse_nan_unreplayed;
+
+__device__ __forceinline__ bool coarse_nan_row(int lane_nan, int ma) {
+    const bool row = __syncthreads_or(lane_nan) != 0;
+    if (row && ma > 256) {
+        if (threadIdx.x == 0) atomicAdd(&g_coarse_nan_unreplayed, 1u);
+        return false;
+    }
+    return row;
+}
+
+// Distances of either sign as unsigned keys that order like the values (positive: sign bit set; negative: all bits flipped; -0 does
+// not occur: a sum of a non-negative and a product rounds to +0); 0xffffffff stays above every finite key: the padding past K.
+__device__ __forceinline__ uint32_t coarse_key(float f) {
+    const uint32_t b = __float_as_uint(f);
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+// called by every lane of wave 0 (lane = 0..63); dq = the query's K distances in global memory.
+// The comparisons are the reference's AS COMPILED (-ffast-math; read off its build, oracle/qadc_oracle.c orc_select_k_neighbors):
+// sift-up v > parent, replace-top !(v >= top) — a NaN replaces the top and any value replaces a NaN top —, sift-down right > left
+// and stop iff value >= largest, std::sort's v[a] < v[b].  The ballot pre-filter drops the values the top rejects; that holds for
+// the rest of a 64-chunk only while the top cannot grow, i.e. until the first NaN of the row: from there on every value is pushed.
 __device__ __forceinline__ void coarse_exact_select(const float* __restrict__ dq, int K, int ma, int32_t* __restrict__ out,
                                                  float* hv, int* hk, int* perm, uint32_t lane) {
     const ExactSel x{hv, hk, perm};
     int size = 0;
+    bool seen_nan = false;
     for (int k0 = 0; k0 < K; k0 += 64) {
         const int k = k0 + (int)lane;
         const float v = k < K ? dq[k] : 0.0f;
-        uint64_t todo = __builtin_amdgcn_ballot_w64(k < K && (size < ma || v < hv[0]));
+        seen_nan = seen_nan || __builtin_amdgcn_ballot_w64(k < K && v != v) != 0;                  // (uniform)
+        uint64_t todo = __builtin_amdgcn_ballot_w64(k < K && (size < ma || seen_nan || !(v >= hv[0])));
         while (todo) {
             const int j = (int)__builtin_ctzll(todo);
             todo &= todo - 1;
@@ -2137,7 +2165,7 @@ __device__ __forceinline__ void coarse_exact_select(const float* __restrict__ dq
                         i = parent;
                         parent = (i - 1) / 2;
                     }
-                } else if (vj < hv[0]) {
+                } else if (!(vj >= hv[0])) {                                                      // (vcomiss + jae)
                     int i = 0;
                     hv[0] = vj; hk[0] = k0 + j;
                     for (;;) {
@@ -2145,7 +2173,7 @@ __device__ __forceinline__ void coarse_exact_select(const float* __restrict__ dq
                         if (l >= ma) break;
                         int c = l;
                         if (r < ma && hv[r] > hv[l]) c = r;
-                        if (hv[c] <= hv[i]) break;
+                        if (hv[i] >= hv[c]) break;                                                // (vcomiss + jb)
                         const float tv = hv[i]; hv[i] = hv[c]; hv[c] = tv;
                         const int tk = hk[i]; hk[i] = hk[c]; hk[c] = tk;
                         i = c;
@@ -2193,8 +2221,7 @@ __global__ __launch_bounds__(256) void coarse_assign_kernel(const float* __restr
                                                             float* __restrict__ dist, int32_t* __restrict__ assign) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     float* q = reinterpret_cast<float*>(dyn);                 // [QB][dim]
-    __shared__ float rv[4];
-    __shared__ int rk[4];
+    __shared__ uint32_t rv[4], rk[4];
     const int q0 = blockIdx.x * QB, tid = threadIdx.x;
     const int nqb = min(QB, nq - q0);
     for (int i = tid; i < QB * dim; i += 256) {
@@ -2204,6 +2231,9 @@ __global__ __launch_bounds__(256) void coarse_assign_kernel(const float* __restr
     __syncthreads();
     constexpr int NR = KPT > 0 ? KPT : 1;
     float mine[NR][QB];
+    int nan[QB];
+#pragma unroll
+    for (int b = 0; b < QB; ++b) nan[b] = 0;
 #pragma unroll
     for (int j = 0; j < NR; ++j)
 #pragma unroll
@@ -2228,6 +2258,8 @@ __global__ __launch_bounds__(256) void coarse_assign_kernel(const float* __restr
             const int k = j * 256 + tid;
             if (j < nblk && k < K) {
                 row_dist(k, mine[j]);
+#pragma unroll
+                for (int b = 0; b < QB; ++b) nan[b] |= mine[j][b] != mine[j][b];
                 if (dist)                                        // (the exact-tie path below reads the row from memory)
 #pragma unroll
                     for (int b = 0; b < QB; ++b)
@@ -2239,46 +2271,49 @@ __global__ __launch_bounds__(256) void coarse_assign_kernel(const float* __restr
             float s[QB];
             row_dist(k, s);
 #pragma unroll
-            for (int b = 0; b < QB; ++b)
+            for (int b = 0; b < QB; ++b) {
+                nan[b] |= s[b] != s[b];
                 if (b < nqb) dist[(size_t)(q0 + b) * K + k] = s[b];
+            }
         }
     }
     __syncthreads();
     __shared__ float x_hv[256];
     __shared__ int x_hk[256], x_perm[kExactSelInts];
-    // per query: ma rounds of "smallest (distance, index) strictly after the previous pick" (+ one more round that only looks
-    // for a value equal to the ma-th outside the picks: an exact tie, see coarse_exact_select)
+    // per query: ma rounds of "smallest (key, index) strictly after the previous pick" in coarse_key's order (+ one more round
+    // that only looks for a value equal to the ma-th outside the picks: an exact tie, see coarse_exact_select).  Keys, not
+    // floats: +inf and FLT_MAX are ordinary candidates, and (0xffffffff, 0xffffffff) is beaten by every (key, k < K), so
+    // with ma <= K every pick is an index in [0, K).  A row with a NaN is replayed exactly afterwards (coarse_nan_row).
 #pragma unroll
     for (int b = 0; b < QB; ++b) {
         if (b >= nqb) break;
         const float* __restrict__ dq = dist + (size_t)(q0 + b) * K;
-        float last_v = -FLT_MAX;
+        uint32_t last_v = 0;
         int last_k = -1;
         bool tie = false;
         const int rounds = (dist && ma > 1 && ma <= 256 && ma < K) ? ma + 1 : ma;
         for (int a = 0; a < rounds; ++a) {
-            float bv = FLT_MAX;
-            int bk = 0x7fffffff;
+            uint32_t bv = 0xffffffffu, bk = 0xffffffffu;
             if (KPT > 0) {
 #pragma unroll
                 for (int j = 0; j < NR; ++j) {
                     const int k = j * 256 + tid;
-                    const float v = mine[j][b];
+                    const uint32_t v = coarse_key(mine[j][b]);
                     const bool after = v > last_v || (v == last_v && k > last_k);
-                    if (k < K && after && (v < bv || (v == bv && k < bk))) { bv = v; bk = k; }
+                    if (k < K && after && (v < bv || (v == bv && (uint32_t)k < bk))) { bv = v; bk = (uint32_t)k; }
                 }
             } else {
                 for (int k = tid; k < K; k += 256) {
-                    const float v = dq[k];
+                    const uint32_t v = coarse_key(dq[k]);
                     const bool after = v > last_v || (v == last_v && k > last_k);
-                    if (after && (v < bv || (v == bv && k < bk))) { bv = v; bk = k; }
+                    if (after && (v < bv || (v == bv && (uint32_t)k < bk))) { bv = v; bk = (uint32_t)k; }
                 }
             }
             // wave-level reduction first (no barrier), then across the 4 waves through LDS
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) {
-                const float ov = __shfl_xor(bv, d, 64);
-                const int ok = __shfl_xor(bk, d, 64);
+                const uint32_t ov = __shfl_xor(bv, d, 64);
+                const uint32_t ok = __shfl_xor(bk, d, 64);
                 if (ov < bv || (ov == bv && ok < bk)) { bv = ov; bk = ok; }
             }
             if ((tid & 63) == 0) { rv[tid >> 6] = bv; rk[tid >> 6] = bk; }
@@ -2288,12 +2323,13 @@ __global__ __launch_bounds__(256) void coarse_assign_kernel(const float* __restr
 #pragma unroll
             for (int w = 1; w < 4; ++w)
                 if (rv[w] < bv || (rv[w] == bv && rk[w] < bk)) { bv = rv[w]; bk = rk[w]; }
-            tie = tie || (a > 0 && bv == last_v);
+            tie = tie || (a > 0 && bv == last_v && bk != 0xffffffffu);
             last_v = bv;
-            last_k = bk;
+            last_k = (int)bk;
             if (tid == 0 && a < ma) assign[(size_t)(q0 + b) * ma + a] = last_k;
             __syncthreads();
         }
+        if (dist && coarse_nan_row(nan[b], ma)) tie = true;      // (a NaN row: the exact replay, as for a tie)
         if (tie && dist && ma <= 256) {                          // (uniform: every thread saw the same picks)
             __threadfence_block();
             if (tid < 64) coarse_exact_select(dq, K, ma, assign + (size_t)(q0 + b) * ma, x_hv, x_hk, x_perm, (uint32_t)tid);
@@ -2395,13 +2431,6 @@ __global__ __launch_bounds__(256) void coarse_dist_kernel(const float* __restric
     }
 }
 
-// Distances of either sign as unsigned keys that order like the values (positive: sign bit set; negative: all bits flipped; -0 does
-// not occur: a sum of a non-negative and a product rounds to +0); 0xffffffff stays above every finite key: the padding past K.
-__device__ __forceinline__ uint32_t coarse_key(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-
 // ma rounds of "smallest (distance, index) strictly after the previous pick" over a query's K distances (as coarse_key);
 // one workgroup per query, KPT distances per lane in registers
 template <int KPT>
@@ -2409,13 +2438,20 @@ __global__ __launch_bounds__(256) void coarse_select_kernel(const float* __restr
     __shared__ uint32_t rv[2][4], rk[2][4];
     const int q = blockIdx.x, tid = threadIdx.x;
     uint32_t mine[KPT];
+    int nan = 0;
 #pragma unroll
     for (int j = 0; j < KPT; ++j) {
         const int k = j * 256 + tid;
-        mine[j] = k < K ? coarse_key(dist[(size_t)q * K + k]) : 0xffffffffu;
+        const float f = k < K ? dist[(size_t)q * K + k] : 0.0f;
+        nan |= f != f;
+        mine[j] = k < K ? coarse_key(f) : 0xffffffffu;
     }
     __shared__ float x_hv[256];
     __shared__ int x_hk[256], x_perm[kExactSelInts];
+    if (coarse_nan_row(nan, ma)) {                               // a NaN: the reference's heap history decides (uniform branch)
+        if (tid < 64) coarse_exact_select(dist + (size_t)q * K, K, ma, assign + (size_t)q * ma, x_hv, x_hk, x_perm, (uint32_t)tid);
+        return;
+    }
     uint32_t last_v = 0;
     int last_k = -1, par = 0;
     bool tie = false;
@@ -2463,11 +2499,20 @@ __global__ __launch_bounds__(256) void coarse_select_radix_kernel(const float* _
     __shared__ uint32_t ties[256];
     __shared__ uint32_t s_prefix, s_rank, s_nless, s_nties, s_kept, s_T0;
     const int q = blockIdx.x, tid = threadIdx.x;
+    __shared__ float x_hv[256];
+    __shared__ int x_hk[256], x_perm[kExactSelInts];
     uint32_t mine[KPT];
+    int nan = 0;
 #pragma unroll
     for (int j = 0; j < KPT; ++j) {
         const int k = j * 256 + tid;
-        mine[j] = k < K ? coarse_key(dist[(size_t)q * K + k]) : 0xffffffffu;
+        const float f = k < K ? dist[(size_t)q * K + k] : 0.0f;
+        nan |= f != f;
+        mine[j] = k < K ? coarse_key(f) : 0xffffffffu;
+    }
+    if (coarse_nan_row(nan, ma)) {                               // a NaN: the reference's heap history decides (uniform branch)
+        if (tid < 64) coarse_exact_select(dist + (size_t)q * K, K, ma, assign + (size_t)q * ma, x_hv, x_hk, x_perm, (uint32_t)tid);
+        return;
     }
     if (tid == 0) { s_prefix = 0; s_rank = (uint32_t)ma; s_nless = 0; s_nties = 0; s_kept = 0; s_T0 = 0xffffffffu; }
     __syncthreads();
@@ -2552,8 +2597,6 @@ __global__ __launch_bounds__(256) void coarse_select_radix_kernel(const float* _
     }
     __syncthreads();
     const uint32_t nless = s_nless, nties = s_nties;            // nless == ma - need_ties
-    __shared__ float x_hv[256];
-    __shared__ int x_hk[256], x_perm[kExactSelInts];
     __shared__ uint32_t s_tie;
     if (nties > need_ties) {                                     // a value equal to the ma-th outside the picks: an exact tie at the boundary —
         // the reference's heap history decides which of them stay and in which order (coarse_exact_select); uniform branch
@@ -2591,6 +2634,15 @@ __global__ __launch_bounds__(256) void coarse_select_radix_kernel(const float* _
     }
     __syncthreads();
     if (s_tie && tid < 64) coarse_exact_select(dist + (size_t)q * K, K, ma, assign + (size_t)q * ma, x_hv, x_hk, x_perm, (uint32_t)tid);
+}
+
+hipError_t coarse_nan_unreplayed_reset(hipStream_t stream) {
+    const unsigned int zero = 0;
+    return hipMemcpyToSymbolAsync(HIP_SYMBOL(g_coarse_nan_unreplayed), &zero, sizeof(zero), 0, hipMemcpyHostToDevice, stream);
+}
+
+hipError_t coarse_nan_unreplayed_read(unsigned int* count) {
+    return hipMemcpyFromSymbol(count, HIP_SYMBOL(g_coarse_nan_unreplayed), sizeof(*count), 0, hipMemcpyDeviceToHost);
 }
 
 void launch_row_sqnorm(const float* d_rows, int n, int dim, int sum_mode, float* d_out, hipStream_t stream) {
@@ -2750,7 +2802,10 @@ void launch_build_tables(const float* d_queries, const float* d_coarse, const in
 // find_k_neighbors(count, 16, sq_dim, k = 1, ...) (neighbors.cpp:30-76) — the BLAS-expansion distances of
 // compute_cross_dists_blas (expansion_dist above) pushed in centroid order into a kv_binheap of capacity 1
 // (add_candidates_heaps, 18-28; binheap.hpp:75-116): the first centroid is appended whatever its distance, a later one
-// replaces it iff its distance is strictly smaller — the first strict minimum, centroid 0 when its distance is NaN.
+// replaces it iff !(distance >= kept) — the replace test AS COMPILED (-ffast-math: vcomiss + jae; oracle/qadc_oracle.c
+// orc_select_k_neighbors): the first strict minimum after the last NaN, or the last centroid when its distance is NaN.
+// LDS: the codebooks (+ their norms for form 1), up to dim 2048 = 128 KiB + 2 KiB: above 64 KiB the launch raises the kernel's
+// dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize; gfx950 has 160 KiB per workgroup).
 // Two sub-quantizers per byte, the even one in the low nibble (multiple_set_bits_4, quantizers.hpp:49-68).
 // form 1 = that (the reference's form; parity: the oracle's orc_pq_encode, tests/test_gpu_parity.py); form 0 = the direct
 // sum (x - c)^2 in one sequential loop (this repository's encoder before round 6).  One thread per code byte.
@@ -2760,12 +2815,14 @@ __global__ __launch_bounds__(256) void pq_encode_kernel(const float* __restrict_
                                                         uint8_t* __restrict__ codes) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     float* cb = reinterpret_cast<float*>(dyn);                // [M][16][ds]
-    float* cnorm = cb + (size_t)M * 16 * (dim / M);           // [M][16] ||c||^2 (form 1)
+    float* cnorm = cb + (size_t)M * 16 * (dim / M);           // [M][16] ||c||^2 (form 1 only: not allocated for form 0)
     const int ds = dim / M, cs = M / 2;
     for (int i = threadIdx.x; i < M * 16 * ds; i += 256) cb[i] = codebooks[i];
     __syncthreads();
-    for (int e = threadIdx.x; e < M * 16; e += 256) cnorm[e] = form ? expansion_sqnorm(cb + (size_t)e * ds, ds, sum_mode) : 0.0f;
-    __syncthreads();
+    if (form) {
+        for (int e = threadIdx.x; e < M * 16; e += 256) cnorm[e] = expansion_sqnorm(cb + (size_t)e * ds, ds, sum_mode);
+        __syncthreads();
+    }
     const uint64_t total = n * (uint64_t)cs;
     for (uint64_t o = (uint64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (uint64_t)gridDim.x * 256) {
         const uint64_t vi = o / cs;
@@ -2788,7 +2845,7 @@ __global__ __launch_bounds__(256) void pq_encode_kernel(const float* __restrict_
                         s += t * t;
                     }
                 }
-                if (c == 0 || s < bestd) { bestd = s; best = c; }
+                if (c == 0 || !(s >= bestd)) { bestd = s; best = c; }   // (the compiled replace test, see above)
             }
             packed |= (uint32_t)best << (4 * h);
         }
@@ -2800,8 +2857,10 @@ void launch_pq_encode(const float* d_vectors, uint64_t n, int M, int dim, const 
                       uint8_t* d_codes, hipStream_t stream) {
     const uint64_t total = n * (uint64_t)(M / 2);
     const int grid = (int)std::min<uint64_t>((total + 255) / 256, 16384);
-    hipLaunchKernelGGL(pq_encode_kernel, dim3(grid), dim3(256), ((size_t)M * 16 * (dim / M) + (size_t)M * 16) * sizeof(float), stream,
-                       d_vectors, n, M, dim, d_codebooks, form, sum_mode, d_codes);
+    const size_t lds = ((size_t)M * 16 * (dim / M) + (form ? (size_t)M * 16 : 0)) * sizeof(float);
+    static std::atomic<uint64_t> lds_set{0};
+    if (lds > 65536) ensure_dynamic_lds(reinterpret_cast<const void*>(&pq_encode_kernel), (int)kPqEncodeMaxLds, lds_set);
+    hipLaunchKernelGGL(pq_encode_kernel, dim3(grid), dim3(256), lds, stream, d_vectors, n, M, dim, d_codebooks, form, sum_mode, d_codes);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -32,7 +32,7 @@ SYMBOLS = [
     "qadc_scan_i8_candidates", "qadc_scan_start", "qadc_query_scan_submit", "qadc_prescan_submit",
     "qadc_prescan_collect", "qadc_query_scan_submit_prescanned",
     "qadc_query_scan_collect", "qadc_index_set_pq", "qadc_index_set_rotation", "qadc_index_set_coarse", "qadc_search", "qadc_search_submit",
-    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset",
+    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset",
     "qadc_dist_unique_id", "qadc_dist_init", "qadc_dist_collect", "qadc_dist_shutdown", "qadc_dist_merge_blocks", "qadc_dist_merge_blocks_host",
     "qadc_dist_init_transport", "qadc_dist_init_loopback", "qadc_shm_transport_open", "qadc_shm_transport_allgather", "qadc_shm_transport_allgather_host",
     "qadc_shm_transport_close", "qadc_shm_transport_error", "qadc_slot_assign", "qadc_slot_qtables", "qadc_place_partitions",
@@ -121,6 +121,7 @@ def lib():
         L.qadc_ivf_encode_host_mode.argtypes = [C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, f32p, C.c_uint64, i32p, u8p, C.c_int, C.c_int,
                                                 C.c_int]
         L.qadc_kmeans_iterations_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, f32p, C.c_int, i32p, C.c_int]
+        L.qadc_coarse_assign_host.argtypes = [f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, i32p, C.c_int]
         L.qadc_kmeans_iterations_host_mode.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, f32p, C.c_int, i32p, C.c_int, C.c_int]
         L.qadc_replay_i8.argtypes = [C.c_uint64, u32p, i8p, C.c_int, C.c_int, u32p, i8p, i32p]
         L.qadc_sort_keys_i8.argtypes = [C.c_int, u32p, i8p, u32p]
@@ -308,6 +309,17 @@ def kmeans_iterations(vectors, centroids, iters, device=0, div_mode=1):
     _check(lib().qadc_kmeans_iterations_host_mode(_p(v, f32p), v.shape[0], v.shape[1], c.shape[0], _p(c, f32p), iters, _p(assign, i32p),
                                                   div_mode, device))
     return c, assign
+
+
+def coarse_assign(queries, coarse, ma, device=0):
+    """find_k_neighbors with k = ma on the GPU, as qadc_search's front selects coarse centroids: queries [nq][dim], coarse
+    [K][dim] -> assign int32 [nq][ma] (the reference's heap order, nearest first)."""
+    q = np.ascontiguousarray(queries, np.float32)
+    c = np.ascontiguousarray(coarse, np.float32)
+    assert q.ndim == 2 and c.ndim == 2 and q.shape[1] == c.shape[1]
+    assign = np.zeros((q.shape[0], ma), np.int32)
+    _check(lib().qadc_coarse_assign_host(_p(q, f32p), q.shape[0], _p(c, f32p), c.shape[0], c.shape[1], ma, _p(assign, i32p), device))
+    return assign
 
 
 def pq_encode(codebooks, vectors, device=0, encode_form=1, sum_mode=1):

@@ -40,3 +40,11 @@ def path_independent(fn):
     once instead of once per scan path."""
     fn._path_independent = True
     return fn
+
+
+def coarse_dists(x, c):
+    """The coarse distances of the rows x [n][dim] to the centroids c [K][dim] as find_k_neighbors gets them
+    (compute_cross_dists_blas, distances.hpp:151-183): the oracle's orc_cross_dists — (||x||^2 + ||c||^2) with the norms as the
+    reference compiles them, then -2 x.c as one sequential dot.  -> [n][K] float32."""
+    import pyoracle
+    return pyoracle.cross_dists(c, np.ascontiguousarray(x, np.float32).reshape(-1, c.shape[1]))

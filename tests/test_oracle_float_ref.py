@@ -313,6 +313,72 @@ def test_coarse_selection_against_the_reference_heaps(po):
     assert ndiff >= 10
 
 
+NAN_BITS = (0x7fc00000, 0xffc00000, 0x7fffffff, 0xffffffff)       # quiet NaN, its negative, the largest payloads of both signs
+K_SELECT = (1, 2, 5, 7, 8, 9, 16, 17, 32, 64, 256)
+
+
+def _f32(bits):
+    return np.array([bits], np.uint32).view(np.float32)[0]
+
+
+def nonfinite_rows(rng, K):
+    """Distance rows [n][K] with non-finite entries where selections go wrong: NaN of every bit pattern in NAN_BITS, +inf and
+    FLT_MAX, at index 0, in the middle, at K-1 and at the last entry of a 256-block (add_candidates_heaps' block edge); all-NaN
+    rows, all-+inf rows, and rows with only a few finite values."""
+    special = [_f32(b) for b in NAN_BITS] + [np.float32(np.inf), FMAX]
+    rows = []
+    spots = sorted({0, K // 2, K - 1, min(K - 1, 255), min(K - 1, 256)})
+    for v in special:
+        for at in spots:
+            r = (rng.random(K) * 10).astype(np.float32)
+            r[at] = v
+            rows.append(r)
+        r = (rng.random(K) * 10).astype(np.float32)
+        r[spots] = v
+        rows.append(r)
+        rows.append(np.full(K, v, np.float32))                                     # the whole row
+        r = np.full(K, v, np.float32)
+        few = rng.choice(K, size=min(K, 3), replace=False)
+        r[few] = rng.random(len(few)).astype(np.float32)                           # fewer finite values than most k
+        rows.append(r)
+    for frac in (0.05, 0.5, 0.95):                                                 # mixtures of all of them
+        r = (rng.random((8, K)) * 10).astype(np.float32)
+        m = rng.random((8, K)) < frac
+        r[m] = rng.choice(np.array(special, np.float32), size=int(m.sum()))
+        rows.extend(r)
+    r = np.floor(rng.random((4, K)) * 3).astype(np.float32)                        # exact ties around NaNs
+    r[:, ::5] = np.nan
+    rows.extend(r)
+    return np.stack(rows).astype(np.float32)
+
+
+def test_coarse_selection_on_non_finite_distances_is_the_reference_binary(po):
+    """find_k_neighbors' selection half on NaN, +inf and FLT_MAX distances.  The reference is built with -ffast-math, and its
+    replace-top test compiles to !(v >= top) (vcomiss + jae), not to the source's v < top: a NaN always replaces the heap top,
+    and the next value always replaces a NaN top.  orc_select_k_neighbors writes that predicate out and must equal the
+    reference's heaps entry for entry (indices, and distances bit for bit, NaN payloads included) for every k, with K below
+    and above k."""
+    _need_ref_float(po)
+    rng = np.random.default_rng(2024)
+    for K in (1, 3, 7, 16, 70, 255, 256, 257, 513, 1000):
+        d = nonfinite_rows(rng, K)
+        for k in K_SELECT:
+            a, sd = po.reff_select_k_neighbors(d, k)
+            b, sb = po.select_k_neighbors(d, k)
+            kk = min(k, K)
+            assert np.array_equal(b[:, :kk], a[:, :kk]), (K, k)
+            assert np.array_equal(sb[:, :kk].view(np.uint32), sd[:, :kk].view(np.uint32)), (K, k)
+            assert ((a[:, :kk] >= 0) & (a[:, :kk] < K)).all()
+    # the rule, on rows that show it: the result is the first strict minimum after the last NaN (k = 1)
+    d = np.full((1, 20), np.nan, np.float32)
+    d[0, 7] = 1
+    for sel in (po.reff_select_k_neighbors, po.select_k_neighbors):
+        assert sel(d, 1)[0].tolist() == [[19]] and sel(d, 4)[0].tolist() == [[17, 18, 2, 19]]
+        assert sel(np.full((1, 9), np.inf, np.float32), 3)[0].tolist() == [[0, 1, 2]]
+        assert sel(np.array([[np.nan, 3, 2, np.nan, 5, 4, 6]], np.float32), 1)[0].tolist() == [[5]]
+        assert sel(np.array([[2, 1, 3, np.nan]], np.float32), 1)[0].tolist() == [[3]]
+
+
 # ------------------------------------------------------------------------------------------------ N4: the encoder
 def _seq_rotate(po, v, rot):
     import importlib.util
@@ -340,6 +406,62 @@ def test_oracle_encoder_matches_reference_golden(po):
         direct_differs += int((po.pq_encode(c["codebooks"], c["vectors"], c["rotation"], form=0) != c["codes"]).any())
         ncase += 1
     assert ncase == 15 and direct_differs >= 4
+
+
+def _first_strict_min(d):
+    """k = 1 with the source's IEEE test (replace iff v < best): the first strict minimum, a NaN at index 0 never replaced."""
+    out = np.zeros(d.shape[0], np.int32)
+    for i, r in enumerate(d):
+        for c in range(1, d.shape[1]):
+            if r[c] < r[out[i]]:
+                out[i] = c
+    return out
+
+
+def _reference_encode_chain(po, codebooks, vectors, select=None):
+    """base_pq::encode_multiple_vectors as a chain of the reference's compiled pieces: extract_subvectors, compute_cross_dists_blas
+    up to its sgemm (the norms), then -2 x.c as one sequential dot added in one rounding (what orc_cross_dists restates for the
+    sgemm), find_k_neighbors' selection with k = 1 and multiple_set_bits_4.  (fma(-2, dot, base) of float32s is exact in float64
+    up to the final rounding.)"""
+    M, _, ds = codebooks.shape
+    assign = np.zeros((vectors.shape[0], M), np.int32)
+    for m in range(M):
+        sub = po.reff_extract_subvectors(vectors, ds, m)
+        base = po.reff_cross_norms(codebooks[m], sub)
+        dot = np.zeros((sub.shape[0], 16), np.float32)
+        for j in range(ds):
+            dot = (dot + (sub[:, j:j + 1] * codebooks[m][None, :, j]).astype(np.float32)).astype(np.float32)
+        with np.errstate(invalid="ignore", over="ignore"):
+            dist = (base.astype(np.float64) - 2.0 * dot.astype(np.float64)).astype(np.float32)
+        assign[:, m] = po.reff_select_k_neighbors(dist, 1)[0][:, 0] if select is None else select(dist)
+    return po.reff_pack4(assign, M)
+
+
+def test_oracle_encoder_on_nan_codebooks_and_vectors_is_the_reference_chain(po):
+    """orc_pq_encode (form 1) with NaN codebook centroids at index 0, in the middle and at 15 of a sub-quantizer, NaN vector
+    components, +inf and FLT_MAX-scale entries: the codes equal the chain of the reference's own compiled pieces — in particular
+    its k = 1 selection, which picks the first strict minimum after the LAST NaN distance, not the first centroid."""
+    _need_ref_float(po)
+    rng = np.random.default_rng(31)
+    nan_differs = 0
+    for M, ds, n in ((8, 4, 300), (16, 8, 200), (4, 16, 120)):
+        cb = rng.normal(size=(M, 16, ds)).astype(np.float32)
+        v = rng.normal(size=(n, M * ds)).astype(np.float32)
+        cb[0, 0, 1] = np.nan
+        cb[1, 7, :] = _f32(0xffc00000)
+        cb[2, 15, 0] = _f32(0x7fffffff)
+        cb[3, 0, :] = np.nan
+        cb[3, 15, :] = np.nan
+        v[::7, 1] = np.nan                                      # one NaN component: all 16 distances of sub-quantizer 0
+        v[3::11, M * ds - 1] = np.inf
+        v[5::13, ds] = np.float32(3e19)                         # squares overflow to +inf
+        got = po.pq_encode(cb, v)
+        want = _reference_encode_chain(po, cb, v)
+        assert np.array_equal(got, want), (M, ds)
+        # the IEEE '<' rule (first strict minimum, a NaN at centroid 0 kept) is what this repository restated before
+        ieee = _reference_encode_chain(po, cb, v, select=_first_strict_min)
+        nan_differs += int((ieee != got).any())
+    assert nan_differs
 
 
 def test_cross_norms_match_the_reference_as_compiled(po):

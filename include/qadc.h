@@ -466,6 +466,62 @@ typedef struct qadc_profile {
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);
 int qadc_profile_reset(qadc_index* idx);
 
+/* ---------------------------------------------------------------------------------------------
+ * Float ADC over whole-byte PQ codes — the reference's OTHER query front end, db_query's plain
+ * scanner_simple (db_query.cpp:17-46) with scan_standard<uint8_t, NSQ> (query_common.hpp:92-146).
+ * A separate engine: it shares no state or option with qadc_index above.  Float tables come from
+ * the caller, as scanner_simple receives them.  Candidates are summed in the grouping of the
+ * reference as compiled (sum_mode 1) or in source order (sum_mode 0); DESIGN.md section 11.
+ * ------------------------------------------------------------------------------------------- */
+#define QADC_ADC_MAX_R 65536  /* largest heap capacity the qadc_adc_query_* calls take (larger R -> QADC_E_ARG) */
+/* Candidate entries one qadc_adc_query_* call may hold on the device (12 bytes each).  Each query gets a region of
+ * max(R, 512) + 32 R (levels - 1) + 4096 entries, at most its probed code count; a region that overflows is grown to hold
+ * its query's whole candidate stream and the batch re-runs (a query whose scan order is sorted descending keeps every code).
+ * A batch whose regions would exceed this many entries returns QADC_E_CAPACITY: split it. */
+#define QADC_ADC_MAX_ENTRIES (1ull << 34)
+
+/* Threading: one host thread at a time per index (its staging buffers and results belong to the index); several indexes
+ * may be driven from several threads.  Every qadc_adc_* call selects the index's device and restores the calling thread's
+ * current device before it returns. */
+
+typedef struct qadc_adc_index qadc_adc_index;
+
+/* scanner_simple::prepare_database + get_scan_func (db_query.cpp:21-24, query_common.hpp:120-146): sq_bits 8 with
+ * sq_count 4, 8 or 16.  Anything else -> QADC_E_ARG with the reference's list of configurations (the 16-bit and 4-bit
+ * ones are the reference's but not this engine's). */
+int qadc_adc_index_create(qadc_adc_index** out, int sq_count, int sq_bits, int device_id);
+int qadc_adc_index_destroy(qadc_adc_index* idx);
+
+/* Append partitions as base_db::get_partition() yields them (databases.hpp:50-55): row-major codes [sizes[p]][sq_count],
+ * labels[p] = u32[sizes[p]] or labels == NULL (key = position inside the partition, as scan_standard keys).  All-or-none
+ * labels over every call and every non-empty partition (QADC_E_ARG otherwise); empty partitions are legal, their label
+ * pointer may be NULL either way.  Host buffers are copied to the GPU. */
+int qadc_adc_index_add_partitions(qadc_adc_index* idx, int part_count, const uint8_t* const* codes,
+                                  const uint32_t* const* labels, const uint32_t* sizes);
+int qadc_adc_index_partition_count(const qadc_adc_index* idx);
+uint32_t qadc_adc_index_partition_size(const qadc_adc_index* idx, int part);
+/* Diagnostics (no reference counterpart): how many query calls on this index were re-run because a candidate region overflowed. */
+uint64_t qadc_adc_index_reruns(const qadc_adc_index* idx);
+
+/* scanner_simple::query_scan (db_query.cpp:26-45) for nq queries:
+ *   assign  [nq][ma]                   probed partitions, each in [0, partition_count); duplicates legal; 1 <= ma < 16384
+ *   tables  [nq][ma][sq_count*256]     float tables, NOT mutated
+ *   R                                  heap capacity, 1 .. QADC_ADC_MAX_R
+ *   sum_mode                           1 = the reference's grouping as compiled, 0 = source order
+ * Outputs (any may be NULL): keys[q][R], values[q][R], sizes[q] = the ARRAYS of the reference's
+ * kv_binheap<unsigned,float>(R) after the query (R sentinel pushes (0, FLT_MAX - t) first, db_query.cpp:31-33).
+ * A query may probe at most 2^32 - 1 codes in all.  QADC_E_CAPACITY: see QADC_ADC_MAX_ENTRIES. */
+int qadc_adc_query_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R,
+                        int sum_mode, uint32_t* keys, float* values, int32_t* sizes);
+/* The ordered candidate stream instead: pushing (cand_keys[i], cand_vals[i]) for i in [offsets[q], offsets[q+1]) in
+ * order into the reference's kv_binheap<unsigned,float>(R), after its R sentinel pushes, leaves it in exactly the state
+ * the reference's scan would (a superset of its successful pushes, in scan order).  What a ScannerType wrapper pushes into
+ * the caller's own heap (host/scanner_simple_hip.hpp).  offsets has nq + 1 entries.  cand_capacity = entries available in
+ * cand_keys / cand_vals; if too small: QADC_E_CAPACITY, offsets filled, offsets[nq] = the entries needed (call again). */
+int qadc_adc_query_scan_candidates(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables,
+                                   int R, int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys,
+                                   float* cand_vals, uint64_t* offsets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,50 @@
+// Device side of the float-ADC engine for whole-byte PQ codes (the reference's scanner_simple / scan_standard<uint8_t, NSQ>,
+// db_query.cpp:17-46, query_common.hpp:92-146).  Internal header shared by csrc/qadc_adc_kernel.hip and csrc/qadc_adc.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace qadc {
+namespace adc {
+
+constexpr int kWG = 256;              // threads per workgroup of every kernel here
+
+// One contiguous run of codes of one probed partition, scanned with the table of (query, slot).
+struct Item {
+    uint32_t query;
+    uint32_t slot;    // position in assign[query][0 .. ma)
+    uint32_t start;   // first code of the run, position inside the partition
+    uint32_t count;   // codes in the run
+    uint32_t sbase;   // scan-order index of the run's first code within its query (probe slots in assign[] order, then position)
+    uint32_t pad[3];
+};
+
+// One region per query, of its own size: query q's emitted candidates (value, key, scan-order index) go to entries
+// [base[q], base[q] + cap[q]) of vals / keys / sidx.
+struct Emit {
+    uint32_t* count;        // [nq] candidates emitted (counted also beyond cap[q]: the host regrows that region and re-runs)
+    float* vals;
+    uint32_t* keys;
+    uint32_t* sidx;
+    const uint64_t* base;   // [nq] first entry of each region
+    const uint32_t* cap;    // [nq] entries of each region
+};
+
+struct Db {
+    const uint8_t* codes;     // every partition, row-major [n][NSQ], each starting on a 16-byte boundary, 16 bytes of tail padding
+    const uint64_t* off;      // [part] byte offset of the partition in codes
+    const uint32_t* labels;   // all partitions' labels, or nullptr (flat keys = position inside the partition)
+    const uint64_t* lab_off;  // [part] first label of the partition
+};
+
+// Scans items [first, first + n_items): emits (candidate, key, scan index) for every code with candidate < bound[query].
+hipError_t launch_adc_scan(int nsq, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, Db db, const int32_t* assign,
+                           int ma, const float* tables, const float* bound, Emit emit, hipStream_t s);
+// bound[q] = min(bound[q], the R-th smallest of the values query q has stored so far) where it stored at least R.
+hipError_t launch_adc_select(int nq, int R, Emit emit, float* bound, hipStream_t s);
+// Packs the stored records of every query densely in query order: record sum_{j<q} stored_j + i of `out` = three words
+// (value bits, key, scan index).
+hipError_t launch_adc_pack(int nq, Emit emit, uint32_t* out, hipStream_t s);
+
+}  // namespace adc
+}  // namespace qadc

@@ -51,6 +51,18 @@ __device__ __forceinline__ T adc_sum8_compiled_next(T s, const T* v) {
 #undef QADC_L
 #undef QADC_H
 
+// scan_standard<uint8_t, NSQ> (query_common.hpp:92-118) as compiled, t[m] = the entry looked up for sub-quantizer m
+// (host twin: adc_sum<N> in host/float_sum.hpp; NSQ 16 is adc_sum8_compiled_first with v[m] = t[m])
+template <typename T>
+__device__ __forceinline__ T adc_sum4_standard_compiled(const T* t) {
+    return (t[1] + t[2]) + (t[3] + t[0]);
+}
+
+template <typename T>
+__device__ __forceinline__ T adc_sum8_standard_compiled(const T* t) {
+    return ((t[1] + t[2]) + (t[3] + t[4])) + ((t[5] + t[6]) + (t[7] + t[0]));
+}
+
 // all CS = M/2 bytes: v[2b] = L_b, v[2b+1] = H_b
 template <int M, typename T>
 __device__ __forceinline__ T adc_sum_code(const T* v, int sum_mode, T zero) {

@@ -1,0 +1,100 @@
+// scanner_simple_hip — C++14 host mirror of the reference's plain ADC ScannerType on the GPU.
+//
+// scanner_simple (db_query.cpp:17-46) has three members: `typedef BhType`, `prepare_database(base_db&)` and
+// `query_scan(query, assign, ma, tables, table_dim, bh, metrics)`.  This type has the same three, with the same argument
+// meaning and error behaviour (get_scan_func's message + std::exit(1) for a configuration it does not take), and forwards to
+// the float-ADC engine of include/qadc.h (qadc_adc_*): db_query.cpp drops it in by swapping the scanner type.
+//   Db:   int partition_count(); void get_partition(int, const std::uint8_t*&, unsigned*&, unsigned&);
+//         pq->sq_count, pq->sq_bits                                      (databases.hpp:34-63)
+//   Heap: int capacity(); void push(unsigned, float)                     (kv_binheap<unsigned, float>, binheap.hpp)
+// Sums are in the reference's grouping as compiled (sum_mode 1) unless the constructor is given 0 (source order).
+#pragma once
+#include <cstdint>
+#include <cstdlib>
+#include <iostream>
+#include <limits>
+#include <vector>
+
+#include "../../include/qadc.h"
+#include "qadc_heap.hpp"
+
+namespace qadc {
+
+struct no_simple_metrics {};
+
+template <typename Db, typename Heap = kv_heap<unsigned, float>, typename Metrics = no_simple_metrics>
+struct scanner_simple_hip {
+    typedef Heap BhType;
+
+    int device, sum_mode;
+    int table_floats = 0;   // sq_count * 256
+    qadc_adc_index* index;
+    std::vector<std::uint32_t> cand_keys;
+    std::vector<float> cand_vals;
+
+    explicit scanner_simple_hip(int device_ = 0, int sum_mode_ = 1) : device(device_), sum_mode(sum_mode_), index(nullptr) {}
+    scanner_simple_hip(const scanner_simple_hip&) = delete;
+    scanner_simple_hip& operator=(const scanner_simple_hip&) = delete;
+    ~scanner_simple_hip() { qadc_adc_index_destroy(index); }
+
+    static void die(const char* what) {
+        std::cerr << what << ": " << qadc_last_error() << std::endl;
+        std::exit(1);
+    }
+
+    // scanner_simple::prepare_database + get_scan_func (db_query.cpp:21-24, query_common.hpp:120-146)
+    void prepare_database(Db& db) {
+        const int m = db.pq->sq_count, bits = db.pq->sq_bits;
+        if (bits != 8 || (m != 4 && m != 8 && m != 16)) {   // get_scan_func's message (the 4- and 16-bit ones are not on the GPU)
+            std::cerr << "Unsupported (nsq,nsq_bits) configuration." << std::endl;
+            std::cerr << "Supported configurations are: (16,4) (4,8) (8,8) (16,8) (2,16) (4,16) (8,16)." << std::endl;
+            std::cerr << "This GPU scanner takes (4,8) (8,8) (16,8)." << std::endl;
+            std::exit(1);
+        }
+        if (qadc_adc_index_create(&index, m, bits, device) != QADC_OK) die("Cannot create the GPU index");
+        table_floats = m * 256;
+        // every partition in one call (one upload of the partition table, one growth of the device copy)
+        const int part_count = db.partition_count();
+        std::vector<const std::uint8_t*> codes(part_count);
+        std::vector<const std::uint32_t*> labels(part_count);
+        std::vector<std::uint32_t> sizes(part_count);
+        bool labeled = false;
+        for (int part_i = 0; part_i < part_count; ++part_i) {
+            unsigned* lab;
+            unsigned size;
+            db.get_partition(part_i, codes[part_i], lab, size);
+            labels[part_i] = lab;
+            sizes[part_i] = size;
+            labeled = labeled || lab != nullptr;
+        }
+        if (qadc_adc_index_add_partitions(index, part_count, codes.data(), labeled ? labels.data() : nullptr, sizes.data()) != QADC_OK)
+            die("Cannot prepare database");
+    }
+
+    // scanner_simple::query_scan (db_query.cpp:26-45).  `query` is unused there too; the tables of the ma probes follow each
+    // other table_dim floats apart, which must be sq_count * 256 (what the engine reads).
+    void query_scan(const float* /*query*/, int* assign, int ma, float* tables, int table_dim, BhType& bh, Metrics& /*metrics*/) {
+        if (table_dim != table_floats) {
+            std::cerr << "query_scan: table_dim " << table_dim << " is not sq_count * 256" << std::endl;
+            std::exit(1);
+        }
+        std::uint64_t offsets[2] = {0, 0};
+        if (cand_keys.empty()) {
+            cand_keys.resize(1 << 16);
+            cand_vals.resize(1 << 16);
+        }
+        int rc = qadc_adc_query_scan_candidates(index, 1, ma, assign, tables, bh.capacity(), sum_mode, cand_keys.size(),
+                                                cand_keys.data(), cand_vals.data(), offsets);
+        if (rc == QADC_E_CAPACITY) {  // offsets[1] holds the required size: grow and ask again
+            cand_keys.resize(offsets[1]);
+            cand_vals.resize(offsets[1]);
+            rc = qadc_adc_query_scan_candidates(index, 1, ma, assign, tables, bh.capacity(), sum_mode, cand_keys.size(),
+                                                cand_keys.data(), cand_vals.data(), offsets);
+        }
+        if (rc != QADC_OK) die("query_scan");
+        for (int t = 0; t < bh.capacity(); ++t) bh.push(0, std::numeric_limits<float>::max() - t);   // "Fill binary heap"
+        for (std::uint64_t i = offsets[0]; i < offsets[1]; ++i) bh.push(cand_keys[i], cand_vals[i]);
+    }
+};
+
+}  // namespace qadc

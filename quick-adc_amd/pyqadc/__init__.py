@@ -36,6 +36,8 @@ SYMBOLS = [
     "qadc_dist_unique_id", "qadc_dist_init", "qadc_dist_collect", "qadc_dist_shutdown", "qadc_dist_merge_blocks", "qadc_dist_merge_blocks_host",
     "qadc_dist_init_transport", "qadc_dist_init_loopback", "qadc_shm_transport_open", "qadc_shm_transport_allgather", "qadc_shm_transport_allgather_host",
     "qadc_shm_transport_close", "qadc_shm_transport_error", "qadc_slot_assign", "qadc_slot_qtables", "qadc_place_partitions",
+    "qadc_adc_index_create", "qadc_adc_index_destroy", "qadc_adc_index_add_partitions", "qadc_adc_index_partition_count",
+    "qadc_adc_index_partition_size", "qadc_adc_query_scan", "qadc_adc_query_scan_candidates", "qadc_adc_index_reruns",
 ]
 
 
@@ -54,6 +56,9 @@ class Profile(C.Structure):
                 ("group_pass_codes8", C.c_uint64), ("group_pass_codes4", C.c_uint64), ("group_batches", C.c_uint64),
                 ("front_sharded_batches", C.c_uint64), ("dist_async_collects", C.c_uint64),
                 ("lone_front_launches", C.c_uint64)]
+
+
+QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h
 
 
 class QadcError(RuntimeError):
@@ -147,6 +152,17 @@ def lib():
         L.qadc_place_partitions.argtypes = [C.c_int, u32p, C.c_int, i32p]
         L.qadc_profile_read.argtypes = [C.c_void_p, C.POINTER(Profile)]
         L.qadc_profile_reset.argtypes = [C.c_void_p]
+        L.qadc_adc_index_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
+        L.qadc_adc_index_destroy.argtypes = [C.c_void_p]
+        L.qadc_adc_index_add_partitions.argtypes = [C.c_void_p, C.c_int, C.POINTER(u8p), C.POINTER(u32p), u32p]
+        L.qadc_adc_index_partition_count.argtypes = [C.c_void_p]
+        L.qadc_adc_index_partition_size.argtypes = [C.c_void_p, C.c_int]
+        L.qadc_adc_index_partition_size.restype = C.c_uint32
+        L.qadc_adc_index_reruns.argtypes = [C.c_void_p]
+        L.qadc_adc_index_reruns.restype = C.c_uint64
+        L.qadc_adc_query_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, u32p, f32p, i32p]
+        L.qadc_adc_query_scan_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, C.c_uint64,
+                                                     u32p, f32p, u64p]
         _lib = L
     return _lib
 
@@ -684,3 +700,89 @@ class Index:
 
     def profile_reset(self):
         _check(lib().qadc_profile_reset(self._h))
+
+
+class AdcIndex:
+    """One GPU-resident PQ database with whole-byte codes, scanned with float tables: the role of the reference's
+    scanner_simple after prepare_database (db_query.cpp:17-46).  sq_bits 8 with sq_count 4, 8 or 16."""
+
+    def __init__(self, sq_count, sq_bits, device=0):
+        self.sq_count = sq_count
+        self._h = C.c_void_p()
+        _check(lib().qadc_adc_index_create(C.byref(self._h), sq_count, sq_bits, device))
+
+    def close(self):
+        if self._h:
+            lib().qadc_adc_index_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_partitions(self, codes, labels=None):
+        codes = [np.ascontiguousarray(c, np.uint8).reshape(-1, self.sq_count) for c in codes]
+        sizes = np.array([c.shape[0] for c in codes], np.uint32)
+        ca = (u8p * len(codes))(*[_p(c, u8p) for c in codes])
+        la = None
+        if labels is not None:
+            labels = [None if l is None else np.ascontiguousarray(l, np.uint32) for l in labels]
+            la = (u32p * len(labels))(*[None if l is None else _p(l, u32p) for l in labels])
+        _check(lib().qadc_adc_index_add_partitions(self._h, len(codes), ca, la, _p(sizes, u32p)))
+
+    def partition_count(self):
+        return lib().qadc_adc_index_partition_count(self._h)
+
+    def partition_size(self, part):
+        return lib().qadc_adc_index_partition_size(self._h, part)
+
+    def reruns(self):
+        """query calls on this index that were re-run because a candidate region overflowed"""
+        return lib().qadc_adc_index_reruns(self._h)
+
+    def _inputs(self, assign, tables):
+        assign = np.ascontiguousarray(assign, np.int32)
+        if assign.ndim == 1:
+            assign = assign.reshape(1, -1)
+        nq, ma = assign.shape
+        tables = np.ascontiguousarray(tables, np.float32).reshape(nq, ma, self.sq_count * 256)
+        return assign, tables, nq, ma
+
+    def query_scan(self, assign, tables, R, sum_mode=1):
+        """assign [nq][ma], tables [nq][ma][sq_count*256] -> (keys [nq][R], vals [nq][R], sizes [nq]): the heap arrays
+        of scanner_simple::query_scan per query (rows are valid up to sizes[q])."""
+        assign, tables, nq, ma = self._inputs(assign, tables)
+        keys = np.zeros((nq, R), np.uint32)
+        vals = np.zeros((nq, R), np.float32)
+        sizes = np.zeros(nq, np.int32)
+        _check(lib().qadc_adc_query_scan(self._h, nq, ma, _p(assign, i32p), _p(tables, f32p), R, sum_mode, _p(keys, u32p),
+                                         _p(vals, f32p), _p(sizes, i32p)))
+        return keys, vals, sizes
+
+    def query_scan_candidates(self, assign, tables, R, sum_mode=1, capacity=None):
+        """-> (keys, vals, offsets [nq+1]): the ordered candidate stream (query q = [offsets[q], offsets[q+1])), to be pushed
+        after the R sentinels.  capacity=None sizes the buffers itself; a given capacity that is too small raises QadcError
+        (offsets[nq] then holds the entries needed: see query_scan_candidates_raw)."""
+        if capacity is not None:
+            rc, keys, vals, offsets = self.query_scan_candidates_raw(assign, tables, R, sum_mode, capacity)
+            _check(rc)
+            return keys, vals, offsets
+        cap = 1 << 16
+        while True:
+            rc, keys, vals, offsets = self.query_scan_candidates_raw(assign, tables, R, sum_mode, cap)
+            if rc != QADC_E_CAPACITY:
+                _check(rc)
+                return keys[:offsets[-1]], vals[:offsets[-1]], offsets
+            cap = int(offsets[-1])
+
+    def query_scan_candidates_raw(self, assign, tables, R, sum_mode, capacity):
+        """The C call as it is: -> (rc, keys [capacity], vals [capacity], offsets [nq+1])."""
+        assign, tables, nq, ma = self._inputs(assign, tables)
+        keys = np.zeros(max(capacity, 1), np.uint32)
+        vals = np.zeros(max(capacity, 1), np.float32)
+        offsets = np.zeros(nq + 1, np.uint64)
+        rc = lib().qadc_adc_query_scan_candidates(self._h, nq, ma, _p(assign, i32p), _p(tables, f32p), R, sum_mode,
+                                                  capacity, _p(keys, u32p), _p(vals, f32p), _p(offsets, u64p))
+        return rc, keys, vals, offsets

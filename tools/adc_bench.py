@@ -1,0 +1,133 @@
+"""Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
+single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
+
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu] [--iters N] [--out FILE]
+
+  flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
+  batch32   32 queries per call on the same list
+  lone1e6   the synchronous call-to-return time of one query on a 10^6-code flat list (SIFT1M shape)
+  ivf       10^6 codes in K = 256 partitions, ma = 24, 1024 queries per call; the call includes the upload of the
+            1024 x 24 float tables (8 KiB each)
+  cpu       the CPU scan_standard<uint8_t, 8> (the oracle's C restatement, and the reference's own build where it was
+            compiled into oracle/_ref) on the 10^6-code list, one thread
+Every time is a host clock around whole synchronous calls (median of --iters after warm-up); R = 100, sum_mode 1."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "quick-adc_amd"), os.path.join(ROOT, "oracle")):
+    sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+
+import pyqadc  # noqa: E402
+
+HBM_BPS = 8e12
+R = 100
+
+
+def tables_for(rng, nq, ma, nsq=8):
+    return ((rng.random((nq, ma, nsq * 256), dtype=np.float32) * np.float32(4.0)) ** 2).astype(np.float32)
+
+
+def timed(fn, iters, warmup=2):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), float(np.min(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="flat1e8,batch32,lone1e6,ivf,cpu")
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    legs = a.legs.split(",")
+    rng = np.random.default_rng(0)
+    res = {"R": R, "sum_mode": 1, "cpus_allowed": len(os.sched_getaffinity(0))}
+
+    if "flat1e8" in legs or "batch32" in legs:
+        n = 100_000_000
+        codes = rng.integers(0, 256, (n, 8), dtype=np.uint8)
+        idx = pyqadc.AdcIndex(8, 8)
+        idx.add_partitions([codes])
+        del codes
+        if "flat1e8" in legs:
+            tb = tables_for(rng, 1, 1)
+            med, best = timed(lambda: idx.query_scan(np.zeros((1, 1), np.int32), tb, R), a.iters)
+            res["flat1e8_one_query_ms"] = med * 1e3
+            res["flat1e8_codes_per_s"] = n / med
+            res["flat1e8_hbm_roofline_share"] = n * 8 / med / HBM_BPS
+            print("flat 8x8, 10^8 codes, 1 query/call: %.3f ms (best %.3f) = %.3g codes/s = %.3f of the HBM roofline"
+                  % (med * 1e3, best * 1e3, n / med, n * 8 / med / HBM_BPS), flush=True)
+        if "batch32" in legs:
+            tb = tables_for(rng, 32, 1)
+            med, best = timed(lambda: idx.query_scan(np.zeros((32, 1), np.int32), tb, R), max(3, a.iters // 2))
+            res["flat1e8_batch32_ms"] = med * 1e3
+            res["flat1e8_batch32_query_codes_per_s"] = 32 * n / med
+            print("flat 8x8, 10^8 codes, 32 queries/call: %.3f ms (best %.3f) = %.3g query-codes/s"
+                  % (med * 1e3, best * 1e3, 32 * n / med), flush=True)
+        idx.close()
+
+    n1 = 1_000_000
+    codes1 = rng.integers(0, 256, (n1, 8), dtype=np.uint8)
+    tb1 = tables_for(rng, 1, 1)
+    if "lone1e6" in legs:
+        idx = pyqadc.AdcIndex(8, 8)
+        idx.add_partitions([codes1])
+        med, best = timed(lambda: idx.query_scan(np.zeros((1, 1), np.int32), tb1, R), max(a.iters, 50), warmup=5)
+        res["lone1e6_call_us"] = med * 1e6
+        print("flat 8x8, 10^6 codes, one synchronous query: %.1f us (best %.1f)" % (med * 1e6, best * 1e6), flush=True)
+        idx.close()
+    if "cpu" in legs:
+        import pyoracle as po
+        parts = [codes1]
+        tt = tb1.reshape(1, -1)
+        med, _ = timed(lambda: po.scan_standard_u8(8, parts, None, tt, R), 5, warmup=1)
+        res["cpu_scan_standard_u8_8_restatement_us"] = med * 1e6
+        print("CPU scan_standard<uint8_t,8>, 10^6 codes, 1 thread (C restatement, -O2): %.1f us" % (med * 1e6), flush=True)
+        if po.have_ref_float():
+            med, _ = timed(lambda: po.reff_scan_standard_u8(8, parts, None, tt, R), 5, warmup=1)
+            res["cpu_scan_standard_u8_8_reference_build_us"] = med * 1e6
+            print("CPU scan_standard<uint8_t,8>, 10^6 codes, 1 thread (reference build, -O3 -ffast-math AVX2): %.1f us"
+                  % (med * 1e6), flush=True)
+        if "lone1e6_call_us" in res:
+            cpu = min(v for k, v in res.items() if k.startswith("cpu_scan_standard"))
+            res["lone1e6_speedup_vs_fastest_cpu_thread"] = cpu / res["lone1e6_call_us"]
+            print("GPU one-query call vs the faster single CPU thread: %.1fx" % res["lone1e6_speedup_vs_fastest_cpu_thread"])
+    if "ivf" in legs:
+        K, ma, nq = 256, 24, 1024
+        part_of = rng.integers(0, K, n1)
+        parts = [codes1[part_of == k] for k in range(K)]
+        labels = [np.nonzero(part_of == k)[0].astype(np.uint32) for k in range(K)]
+        idx = pyqadc.AdcIndex(8, 8)
+        idx.add_partitions(parts, labels)
+        assign = np.stack([rng.permutation(K)[:ma] for _ in range(nq)]).astype(np.int32)
+        tb = tables_for(rng, nq, ma)
+        med, best = timed(lambda: idx.query_scan(assign, tb, R), max(3, a.iters // 2), warmup=1)
+        probed = sum(len(parts[k]) for k in assign.ravel())
+        res["ivf_batch1024_ms"] = med * 1e3
+        res["ivf_us_per_query"] = med * 1e6 / nq
+        res["ivf_table_bytes_uploaded_per_call"] = int(tb.nbytes)
+        res["ivf_codes_probed_per_call"] = int(probed)
+        print("IVF K=256 ma=24, 1024 queries/call (with %.0f MB of float tables uploaded): %.2f ms = %.1f us/query"
+              % (tb.nbytes / 1e6, med * 1e3, med * 1e6 / nq), flush=True)
+        idx.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

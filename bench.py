@@ -5,16 +5,20 @@ Workload (BASELINE.json configs[3] shape, which fits one GPU): flat database of 
 whole list, through the whole scanner_4::query_scan path (float pre-scan of the starts -> qmax,
 quantizer, int8 scan of every code, candidate replay).
 
-ONE JSON line, several legs (SURVEY.md §8d keeps the two scan modes apart):
+ONE JSON line.  A plain run does only what the headline needs: it sets the list up, warms up, times the steps, writes
+--dump-outputs if asked, and prints `value` / `ms_per_step` with the `roofline` and `phases` of that same timed region.  With
+--full it also runs every other leg below, each after the headline's timed region (the PMC child passes before it, as
+child processes), and the line carries them (SURVEY.md §8d keeps the two scan modes apart):
 
 * headline `value` / `ms_per_step` / `roofline` (the timed region of the contract, ONE region for all three): the METRIC'S
   MODE — ONE QUERY PER PASS over the list, what the reference's scan_avx_4 does (simd_scan.hpp:125-187, one call per query at
   db_query_4.cpp:287-308).  A step = one batch of NQ = 32 queries (the reference's documented `-b32`, README.md:275-330), each
   of which walks the whole list BY ITSELF (library options share_variant = 0, mq = 0: no sibling launch, no multi-query
   pass; scan_i8_kernel<M,2,nt,chunk>): 8 B per (code, query) cross the HBM interface — `roofline.traffic` (rocprofv3 PMC
-  passes over the same kind of steps, collected IN THIS RUN by child processes, --pmc-leg; FETCH_SIZE x2 on gfx950, WRITE_SIZE,
-  separate passes) is within 2 % of the algorithmic bytes.  `roofline` (bound "hbm", frac <= 1) = algorithmic bytes of the
-  region's streaming launches / their HIP-event time on the library's stream.  With --gpus N the SAME mode runs on every rank
+  passes over the same kind of steps, collected IN THIS RUN by child processes with --full, --pmc-leg; FETCH_SIZE x2 on gfx950,
+  WRITE_SIZE, separate passes; a plain run prices its bytes by the committed profile's ratio) is within 2 % of the algorithmic
+  bytes.  `roofline` (bound "hbm", frac <= 1) = algorithmic bytes of the region's streaming launches / their HIP-event time on
+  the library's stream.  With --gpus N the SAME mode runs on every rank
   (its shard of the list, one gather per 32-query step) and `roofline` is rank 0's shard (traffic null: no PMC child at N > 1).
 * `value_batched` / `ms_per_step_batched` / `roofline_batched` (reported SEPARATELY): the same 32-query
   steps with the queries launched as L2-sharing siblings, 8 queries per pass (scan_i8_mq_kernel) — the codes cross the HBM
@@ -43,11 +47,12 @@ the driver's torchrun launch it is a rank.  The SAME 1B-code list is sharded ove
 contiguous ranges ("strong" scaling; keys are 32-bit as in the reference, so the list cannot grow
 past 2^32 anyway) and the per-shard push streams are gathered once per batch and replayed.
 
-    python bench.py --gpus 1 --steps 20 --warmup 2
+    python bench.py --gpus 1 --steps 20 --warmup 2            (headline only)
+    python bench.py --gpus 1 --steps 20 --warmup 2 --full     (every leg)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Environment overrides for quick runs: QADC_BENCH_CODES, QADC_BENCH_NQ, QADC_BENCH_M,
+Environment overrides for quick runs: QADC_BENCH_CODES, QADC_BENCH_NQ, QADC_BENCH_M; for the legs of --full:
 QADC_BENCH_CPU_SECONDS (0 disables the CPU legs), QADC_BENCH_SINGLE_QUERIES (0 = no one-query-per-call leg), QADC_BENCH_BATCHED
 (0 = no batched-mode leg), QADC_BENCH_PMC (0 = no
 in-run PMC child passes), QADC_BENCH_IVF_CODES (0 = no IVF leg), QADC_BENCH_IVF_C5 (0 = no 1B x 32x4 IVF leg), QADC_BENCH_32X4 (0 = no 32x4 leg),
@@ -895,6 +900,8 @@ def self_launch(args):
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
     if args.dump_outputs:
         cmd += ["--dump-outputs", args.dump_outputs]
+    if args.full:
+        cmd.append("--full")
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=None)
@@ -920,6 +927,9 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline's last timed step returned (neighbour keys, int8 "
                          "distance sums, heap sizes, status) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline (recall, PMC traffic, measured ceiling, batched mode, one query "
+                         "per call, 32x4, IVF, c2, latency, real encodings, CPU baselines, the multi-rank IVF legs) and report them")
     ap.add_argument("--pmc-leg", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.dump_outputs:
@@ -945,10 +955,10 @@ def main():
     backend = os.environ.get("QADC_BENCH_BACKEND", "nccl")
 
     # ---- in-run HBM traffic of the one-query-per-pass mode: child processes under rocprofv3, BEFORE this process
-    # touches the GPU (single rank only) ----
-    pmc, pmc_src = None, "skipped"
+    # touches the GPU (single rank, --full only) ----
+    pmc, pmc_src = None, "skipped" if args.full else "no PMC child pass in a plain run (--full collects it)"
     pmc32, pmc32_src = None, "skipped"
-    if world == 1 and os.environ.get("QADC_BENCH_PMC", "1") != "0" and not os.environ.get("QADC_BENCH_FORCE_DIST"):
+    if args.full and world == 1 and os.environ.get("QADC_BENCH_PMC", "1") != "0" and not os.environ.get("QADC_BENCH_FORCE_DIST"):
         pmc, pmc_src = pmc_traffic_in_run(M, N, NQ)
         if os.environ.get("QADC_BENCH_32X4", "1") != "0" and M == 16:
             pmc32, pmc32_src = pmc_traffic_in_run(32, N, 8)
@@ -1178,20 +1188,22 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, dict(zip(("keys", "values", "sizes"), last)) if use_dist else last)
 
-    # ---- Recall@100 against the exact float-ADC nearest code, last batch, untimed ----
-    tb = pool[(args.steps - 1) % len(pool)]
-    keys = last[0] if use_dist else last["keys"]
-    hits = 0
-    for q in range(NQ):
-        key, _, dist_q = idx.float_top1(0, tb[q, 0])
-        if use_dist:
-            cand = torch.tensor([dist_q, float(key)], dtype=torch.float64, device=cdev)
-            allc = torch.empty(2 * world, dtype=torch.float64, device=cdev)
-            dist.all_gather_into_tensor(allc, cand)
-            allc = allc.cpu().numpy().reshape(world, 2)
-            key = int(allc[np.lexsort((allc[:, 1], allc[:, 0]))[0], 1])   # min distance, lowest key on ties
-        hits += int(key in set(keys[q].tolist()))
-    recall = hits / NQ
+    # ---- Recall@100 against the exact float-ADC nearest code, last batch, untimed (--full) ----
+    recall = None
+    if args.full:
+        tb = pool[(args.steps - 1) % len(pool)]
+        keys = last[0] if use_dist else last["keys"]
+        hits = 0
+        for q in range(NQ):
+            key, _, dist_q = idx.float_top1(0, tb[q, 0])
+            if use_dist:
+                cand = torch.tensor([dist_q, float(key)], dtype=torch.float64, device=cdev)
+                allc = torch.empty(2 * world, dtype=torch.float64, device=cdev)
+                dist.all_gather_into_tensor(allc, cand)
+                allc = allc.cpu().numpy().reshape(world, 2)
+                key = int(allc[np.lexsort((allc[:, 1], allc[:, 0]))[0], 1])   # min distance, lowest key on ties
+            hits += int(key in set(keys[q].tolist()))
+        recall = hits / NQ
 
     # ---- `roofline`: the headline's OWN timed region (one query per pass), this rank's shard; rank 0's goes in the line ----
     alg = prof["scan_codes"] * cs / max(prof["scan_launches"], 1)
@@ -1216,7 +1228,7 @@ def main():
     # ---- the measured streaming-read ceiling of this box ("peak ... and also a measured streaming-read ceiling"):
     # the SAME steps through the kernel's PROBE variant (variant bit 4: the LDS lookups replaced by an XOR of the loaded words —
     # the loads, the tiling and the launches are the headline's; the heaps are meaningless), untimed leg, own HIP events ----
-    if world == 1 and not use_dist and os.environ.get("QADC_BENCH_CEILING", "1") != "0":
+    if args.full and world == 1 and not use_dist and os.environ.get("QADC_BENCH_CEILING", "1") != "0":
         idx.set_option("variant", 0x0d | 16)
         run_steps(1)
         idx.profile_reset()
@@ -1236,7 +1248,7 @@ def main():
 
     # ---- the batched mode, reported separately: the same steps, queries as L2-sharing siblings, 8 per pass ----
     batched_elapsed, bprof = None, None
-    if os.environ.get("QADC_BENCH_BATCHED", "1") != "0":
+    if args.full and os.environ.get("QADC_BENCH_BATCHED", "1") != "0":
         set_mode(idx, MODE_BATCHED)
         run_steps(args.warmup)
         idx.profile_reset()
@@ -1254,7 +1266,7 @@ def main():
 
     # ---- one query per CALL (sequential single-query batches): the strictest reading of the reference's mode, single rank only ----
     single = None
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         nsingle = int(os.environ.get("QADC_BENCH_SINGLE_QUERIES", 64))
         if nsingle > 0:
             sprof, sdt = single_query_leg(idx, M, N, pool, nsingle)
@@ -1274,13 +1286,11 @@ def main():
             "config": {"workload": "flat DB, %d x %dx4 PQ codes (%d B/code), R=%d, keep=%.2f%%, sharded over %d GPU(s); a step = "
                                    "%d queries, ONE QUERY PER PASS: every query scans the whole list by itself (the reference's "
                                    "mode, HBM-bound: `roofline` is this same timed region).  The multi-query-per-pass mode of the "
-                                   "same steps is reported separately as `value_batched` / `roofline_batched`"
+                                   "same steps is reported separately as `value_batched` / `roofline_batched` (--full)"
                                    % (N, M, cs, R, KEEP * 100, world, NQ),
                        "codes": N, "M": M, "R": R, "keep": KEEP, "queries_per_step": NQ, "mode": "one query per pass",
                        "parallelism": "shard%d" % world},
-            "recall_at_100": recall,
-            "recall_note": "uniform random codes: the exact float-ADC nearest code is in the returned 100 for every query (near-vacuous); "
-                           "the credible figures are `recall_at_100_real_encode(_ivf)` with `reference_heaps_equal`",
+            "full": args.full,
             "roofline": headline_roof,
             "phases": {"prescan_quantize_ms_per_step": prof["start_ms"] / args.steps,
                        "scan_kernel_ms_per_step": prof["scan_ms"] / args.steps,
@@ -1290,6 +1300,10 @@ def main():
             "multi_gpu_note": "no 8-GPU node was available to the builder: N > 1 has only run as N processes on ONE GPU over the "
                               "shared-memory transport (tests) and with one rank over RCCL; no scaling curve was measured",
         }
+        if recall is not None:
+            out["recall_at_100"] = recall
+            out["recall_note"] = ("uniform random codes: the exact float-ADC nearest code is in the returned 100 for every query "
+                                  "(near-vacuous); the credible figures are `recall_at_100_real_encode(_ivf)` with `reference_heaps_equal`")
         if single is not None:
             out["roofline_one_query_per_call"] = single
             out["value_one_query_per_call"] = single["codes_per_sec_wall"]
@@ -1321,7 +1335,7 @@ def main():
                             "%d B x (code, query) — see profiles/r02_batched_hbm_traffic.json; this mode is NOT priced "
                             "against the HBM roofline (SURVEY.md 8d)" % (NQ, cs)}
     cpu_s = float(os.environ.get("QADC_BENCH_CPU_SECONDS", 15))
-    if rank == 0 and world == 1 and not use_dist and cpu_s > 0:
+    if args.full and rank == 0 and world == 1 and not use_dist and cpu_s > 0:
         # the int8 tables of one bench batch, for the CPU legs (same tables on both sides)
         qt_cpu = idx.query_scan(assign, pool[0].copy(), R, want_qtables=True)["qtables"][:, 0]
     idx.close()
@@ -1329,7 +1343,7 @@ def main():
         flat_tr.close()
     # ---- BASELINE configs[2] / configs[4] shapes on N ranks: every rank holds its part of the partitions, the same query
     # batches go to every rank, qadc_dist_collect merges the push streams ----
-    if use_dist and int(float(os.environ.get("QADC_BENCH_IVF_CODES", 1e8))) > 0:
+    if args.full and use_dist and int(float(os.environ.get("QADC_BENCH_IVF_CODES", 1e8))) > 0:
         shm_tr = []
 
         def shard_init(ix):
@@ -1382,7 +1396,7 @@ def main():
             out["ivf"] = ivf_n
             if ivf_c5_n is not None:
                 out["ivf_c5"] = ivf_c5_n
-    if rank == 0 and world == 1 and not use_dist:
+    if args.full and rank == 0 and world == 1 and not use_dist:
         torch.cuda.synchronize()
         qt32_cpu = None
         if os.environ.get("QADC_BENCH_32X4", "1") != "0" and M == 16:

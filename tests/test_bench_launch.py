@@ -53,6 +53,29 @@ def test_self_launch_builds_one_rank_per_gpu(monkeypatch):
     assert cmd[cmd.index("--gpus") + 1] == "4" and cmd[cmd.index("--steps") + 1] == "3"
 
 
+@pytest.mark.parametrize("extra", [[], ["--full"]])
+def test_self_launch_passes_full_on_to_the_ranks(monkeypatch, extra):
+    """The ranks of a self-launch run the legs the parent was asked for: --full reaches them, a plain run stays plain."""
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    seen = {}
+
+    class FakeProc:
+        def __init__(self, cmd, env=None, stdout=None, stderr=None):
+            seen["cmd"] = cmd
+            self.stdout = [b'{"metric": "pq_codes_scanned_per_sec", "n_gpus": 2}\n']
+
+        def wait(self):
+            return 0
+
+    monkeypatch.setattr(bench.subprocess, "Popen", FakeProc)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1"] + extra)
+    bench.main()
+    assert ("--full" in seen["cmd"]) == bool(extra)
+
+
 def test_bench_prepares_the_stream_set_before_any_communicator():
     """A process that creates a communicator BEFORE the library's stream set runs a rank's IVF batch 14-60 % slower (DESIGN.md
     section 5): in bench.py's main() the qadc_device_prepare call must come before init_process_group and before any rank-side
@@ -76,7 +99,7 @@ def test_a_hung_multi_rank_leg_is_abandoned_with_a_nonzero_exit():
     non-zero instead of hanging."""
     env = _env(QADC_BENCH_BACKEND="gloo", QADC_BENCH_ONE_GPU=1, QADC_BENCH_IVF_TIMEOUT=0.2,
                **dict(SMALL, QADC_BENCH_IVF_CODES=int(4e6), QADC_BENCH_CODES=int(1e7)))
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1"], env=env,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode != 0
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -95,7 +118,7 @@ def test_gpus_n_self_launch_runs_the_multi_rank_loop_on_one_gpu(ranks, native):
     through the library's NATIVE merge over the shared-memory transport (what an 8-GPU node runs over RCCL), and through
     the older torch.distributed path."""
     env = _env(QADC_BENCH_BACKEND="gloo", QADC_BENCH_ONE_GPU=1, QADC_BENCH_NATIVE_DIST=native, **SMALL)
-    r = subprocess.run([sys.executable, BENCH, "--gpus", str(ranks), "--steps", "6", "--warmup", "2"], env=env,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -117,7 +140,7 @@ def test_gpus_2_ivf_legs_through_the_native_merge(placement):
     qadc_dist_collect on every rank — here 2 ranks on one GPU over the shared-memory transport (RCCL needs a GPU per rank)."""
     env = _env(QADC_BENCH_BACKEND="gloo", QADC_BENCH_ONE_GPU=1, QADC_BENCH_IVF_PLACEMENT=placement,
                **dict(SMALL, QADC_BENCH_IVF_CODES=int(4e6), QADC_BENCH_CODES=int(1e7)))
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1"], env=env,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -128,10 +151,35 @@ def test_gpus_2_ivf_legs_through_the_native_merge(placement):
 
 
 @pytest.mark.gpu
+def test_plain_run_times_the_headline_only(tmp_path):
+    """Without --full the run sets up, warms up, times the steps and dumps the last step's heaps, and nothing else: the line
+    holds the headline and the roofline of its own timed region, and none of the other legs."""
+    import numpy as np
+    env = _env(QADC_BENCH_CODES=int(4e7))
+    r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
+    assert line["full"] is False and line["metric"] == "pq_codes_scanned_per_sec" and line["unit"] == "codes/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "int8" and line["config"]["mode"] == "one query per pass"
+    assert line["value"] == pytest.approx(4e7 * 32 * 3 / (line["ms_per_step"] * 3e-3), rel=1e-6)
+    rf = line["roofline"]
+    assert rf["bound"] == "hbm" and 0 < rf["frac"] <= 1.0 and rf["region_queries"] == 32 * 3
+    assert "pmc" not in rf and "measured_ceiling_GBps" not in rf
+    legs = {"recall_at_100", "value_batched", "roofline_batched", "roofline_one_query_per_call", "roofline_32x4", "ivf",
+            "ivf_c5_one_gpu", "roofline_ivf", "c2", "latency_us_single_query", "recall_at_100_real_encode", "cpu_baseline",
+            "cpu_baseline_all_cores"}
+    assert not legs & set(line)
+    keys, sizes = np.load(tmp_path / "keys.npy"), np.load(tmp_path / "sizes.npy")
+    assert keys.shape == (32, 100) and np.all(sizes == 100) and np.all((keys >= 0) & (keys < 4e7))
+    assert np.load(tmp_path / "values.npy").shape == (32, 100) and np.all(np.load(tmp_path / "status.npy") == 0)
+
+
+@pytest.mark.gpu
 def test_single_gpu_line_keeps_the_two_modes_apart():
     env = _env(**dict(SMALL, QADC_BENCH_PMC=1, QADC_BENCH_IVF_CODES=int(4e6), QADC_BENCH_LATENCY=1, QADC_BENCH_32X4=1,
                       QADC_BENCH_SINGLE_QUERIES=8))
-    r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1"], env=env, stdout=subprocess.PIPE,
+    r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--full"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=1200)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -168,7 +216,7 @@ def test_multi_rank_loop_with_one_rank_over_rccl(native):
     the one RCCL rank a 1-GPU box allows: through the library's native merge (qadc_dist_collect) and through the
     torch.distributed path; recall 1.0 either way."""
     env = _env(QADC_BENCH_FORCE_DIST=1, QADC_BENCH_NATIVE_DIST=native, **SMALL)
-    r = subprocess.run([sys.executable, BENCH, "--steps", "6", "--warmup", "2"], env=env, stdout=subprocess.PIPE,
+    r = subprocess.run([sys.executable, BENCH, "--steps", "6", "--warmup", "2", "--full"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])

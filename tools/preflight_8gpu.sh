@@ -24,10 +24,10 @@ env $LEAN QADC_BENCH_IVF_CODES=0 python3 -m torch.distributed.run --nnodes=1 --n
 echo "C multi-rank loop, one RCCL rank:" >> $OUT
 env $LEAN QADC_BENCH_IVF_CODES=0 QADC_BENCH_FORCE_DIST=1 python3 $R/bench.py --steps 10 --warmup 2 2>/dev/null | python3 -c "$P" >> $OUT
 echo "D driver launch line, N=8, eight ranks on this one GPU (shared-memory transport in place of RCCL):" >> $OUT
-env $LEAN QADC_BENCH_BACKEND=gloo QADC_BENCH_ONE_GPU=1 timeout 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29612 $R/bench.py --gpus 8 --steps 10 --warmup 2 2>$R/gpurun_out/r06_preflight_D.err | python3 -c "$P" >> $OUT
+env $LEAN QADC_BENCH_BACKEND=gloo QADC_BENCH_ONE_GPU=1 timeout 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29612 $R/bench.py --gpus 8 --steps 10 --warmup 2 --full 2>${OUT%.txt}_D.err | python3 -c "$P" >> $OUT
 echo "  (launcher exit code ${PIPESTATUS[0]})" >> $OUT
 echo "E watchdog: the IVF legs given 0.2 s on 2 ranks:" >> $OUT
-env $LEAN QADC_BENCH_BACKEND=gloo QADC_BENCH_ONE_GPU=1 QADC_BENCH_CODES=4e7 QADC_BENCH_IVF_TIMEOUT=0.2 timeout 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29613 $R/bench.py --gpus 2 --steps 3 --warmup 1 2>/dev/null | python3 -c "$P" >> $OUT
+env $LEAN QADC_BENCH_BACKEND=gloo QADC_BENCH_ONE_GPU=1 QADC_BENCH_CODES=4e7 QADC_BENCH_IVF_TIMEOUT=0.2 timeout 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29613 $R/bench.py --gpus 2 --steps 3 --warmup 1 --full 2>/dev/null | python3 -c "$P" >> $OUT
 echo "  (launcher exit code ${PIPESTATUS[0]}; 124 would be the outer timeout = a hang)" >> $OUT
 echo "F PMC traffic of the headline's mode on a 125 M-code shard (32 queries per step):" >> $OUT
 cd /tmp && TMPDIR=/tmp python3 -c "

@@ -80,7 +80,8 @@ int qadc_index_add_partition_interleaved(qadc_index* idx, const uint8_t* interle
 
 /* Append one partition whose row-major codes (and labels) already live in device memory of this
  * GPU (borrowed, not freed; must stay valid; 16-byte aligned, readable up to size*M/2 rounded up
- * to 16 bytes). */
+ * to 16 bytes).  They are read in place at query time and may change between queries: such a
+ * partition gets no byte-plane copy for the split scan (qadc_index_set_split). */
 int qadc_index_add_partition_device(qadc_index* idx, const void* d_codes, const void* d_labels, uint32_t size);
 
 /* Append one synthetic flat partition generated on the GPU: 8-byte word w of the code stream =
@@ -461,10 +462,21 @@ typedef struct qadc_profile {
     uint64_t dist_async_collects;   /* multi-GPU: qadc_dist_collect calls served by a merge enqueued with the batch (one event wait) */
     uint64_t lone_front_launches;   /* lone queries on one long partition whose front ran sliced over workgroups, in a launch of its own
                                        in front of the walk (counted with or without "profile") */
+    uint64_t split_launches;        /* of scan_launches: launches of the split form (16x4 runs read from the byte-plane copy) */
+    uint64_t split_codes;           /* codes those launches scanned (they read 7 bytes per code, plus byte 7 of the survivors) */
+    uint64_t split_copy_bytes;      /* device bytes of the byte-plane copies qadc_index_finalize built (kept across resets) */
+    uint64_t split_copy_failed;     /* partitions whose copy could not be allocated: their runs take the row-major form */
 } qadc_profile;
 
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);
 int qadc_profile_reset(qadc_index* idx);
+
+/* Split scan (16x4): qadc_index_finalize builds a byte-plane copy of code bytes 0-6 (7 bytes per code
+ * held, padded to 16 Ki-code tiles) for every partition of at least min_codes codes (default 2^25; 0 = never), and the
+ * one-query-per-pass level launches read it for their runs of at least min_run codes (default 2^23) that start on a tile.
+ * min_codes must be set before qadc_index_finalize.  The copy is made from the codes as they are at finalize; partitions of
+ * borrowed device codes (qadc_index_add_partition_device) get none.  Defaults: profiles/r07_split_sweep.txt. */
+int qadc_index_set_split(qadc_index* idx, uint64_t min_codes, uint64_t min_run);
 
 /* ---------------------------------------------------------------------------------------------
  * Float ADC over whole-byte PQ codes — the reference's OTHER query front end, db_query's plain

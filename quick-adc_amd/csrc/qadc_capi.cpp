@@ -144,6 +144,9 @@ int plan_batch(qadc_index* idx, Slot& s, BatchPlan& plan) {
                     // padding-lane replay of the partition's last code (simd_layout.hpp:46-50, simd_scan.hpp:67)
                     it.dup_pos = (pt.first_pos + pt.n == pt.global_n) ? pt.n - 1u : 0xffffffffu;
                     it.dup_reps = (16u - pt.global_n % 16u) % 16u;
+                    // a long run that starts on a tile of the partition's byte-plane copy may take the split form
+                    it.split = pt.d_split && b0 % kSplitTile == 0 && len >= std::max<uint64_t>(idx->split_min_run, idx->small_run)
+                                   ? pt.d_split + b0 / kSplitTile * (uint64_t)kSplitBytes * kSplitTile : nullptr;
                     per_level[k].push_back(it);
                     b0 += len;
                 }
@@ -169,13 +172,15 @@ int plan_batch(qadc_index* idx, Slot& s, BatchPlan& plan) {
     const int wgs_cap = idx->wgs_per_item > 0 ? idx->wgs_per_item : (M == 16 ? 1024 : 512);   // (r02 sweep: 1024 reaches the streaming ceiling of the "probe" variant, 512 is 1.6 % below)
     for (int k = 0; k < kMaxLevels; ++k) {
         if (per_level[k].empty()) continue;
-        // one launch for the short runs of the level, one for the long ones
-        for (int small = 1; small >= 0; --small) {
+        // one launch for the short runs of the level, one for the long ones (one more for those of them with a byte-plane copy)
+        for (int cls = 0; cls < 3; ++cls) {
+            const int small = cls == 0 ? 1 : 0;
             uint64_t maxn = 0, codes = 0;
             size_t cnt = 0;
             bool same = true;
             for (auto& it : per_level[k]) {
                 if ((it.n < idx->small_run) != (small == 1)) continue;
+                if (!small && (it.split != nullptr) != (cls == 2)) continue;
                 if (cnt) {
                     const ScanItem& f = all_items[off];
                     same = same && it.codes == f.codes && it.n == f.n && it.pos0 == f.pos0 && it.labels == f.labels &&
@@ -195,6 +200,7 @@ int plan_batch(qadc_index* idx, Slot& s, BatchPlan& plan) {
             ll.early = false;
             ll.shared = !ll.small && same && cnt >= 2 && idx->share_variant != 0;
             ll.mq = ll.shared && idx->mq;
+            ll.split = cls == 2 && !ll.shared;
             if (ll.mq) {
                 // 8 queries per pass (scan_i8_mq_kernel): 256-thread workgroups, ~64 Ki codes each, groups of 8
                 // queries as L2-sharing siblings
@@ -225,9 +231,10 @@ int plan_batch(qadc_index* idx, Slot& s, BatchPlan& plan) {
             }
             else {
                 // each streaming workgroup builds a 64-128 KiB table: with many runs in the launch, give every
-                // workgroup more tiles instead of more workgroups per run
+                // workgroup more tiles instead of more workgroups per run (the split form: at least one 16 Ki-code tile each)
                 const uint64_t want = std::max<uint64_t>(1, 8192 / cnt);
-                ll.wgs = (int)std::min<uint64_t>(std::max<uint64_t>((nvec + 4095) / 4096, 1), std::min<uint64_t>(wgs_cap, want));
+                const uint64_t units = ll.split ? (maxn + kSplitTile - 1) / kSplitTile : (nvec + 4095) / 4096;
+                ll.wgs = (int)std::min<uint64_t>(std::max<uint64_t>(units, 1), std::min<uint64_t>(wgs_cap, want));
             }
             ll.codes = codes;
             s.launches.push_back(ll);
@@ -449,8 +456,8 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
                               (uint32_t)s.R, str, /*narrow=*/ll.nitems <= 4 ? 1 : 0);   // (8 queries per pass: the 8-seat
                                                                    // build, see scan_i8_mq_kernel; <= 4 runs: the build with the 4-seat body)
         else
-            launch_scan_i8(M, ll.shared ? idx->share_variant : (variant & ~64), s.d_items + ll.first, ll.nitems, ll.wgs,
-                           s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str);
+            launch_scan_i8(M, ll.shared ? (idx->share_variant & ~32) : (variant & ~(64 | 32)) | (ll.split ? 32 : 0), s.d_items + ll.first,
+                           ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str);
     };
     // The first levels of a batch are short launches in a dependent chain (each level's bound needs the previous
     // levels' candidates): latency, not work.  The head launch and the levels with short runs join the front — same
@@ -862,6 +869,8 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             idx->prof.scan_launches++;
             idx->prof.scan_codes += ll.codes;
             idx->prof.mq_launches += ll.mq ? 1 : 0;
+            idx->prof.split_launches += ll.split ? 1 : 0;
+            idx->prof.split_codes += ll.split ? ll.codes : 0;
             idx->prof.pass_codes += ll.mq ? ll.codes / (uint64_t)ll.nitems * (uint64_t)((ll.nitems + 7) / 8) : ll.codes;
             if (ll.ev < 0 || (size_t)ll.ev + 1 >= s.prof_used) continue;   // not the first launch of its timed group
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[ll.ev], s.prof_ev[ll.ev + 1]));
@@ -1309,6 +1318,9 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
     if (hooks && std::atoi(hooks) == 1) {
         if (const char* e = std::getenv("QADC_WGQ")) idx->wgq = std::atoi(e);   // force (2) / forbid (0) the one-workgroup-per-query path
         if (const char* e = std::getenv("QADC_HEAD_LEVEL")) idx->head_level = std::max(0, std::min(std::atoi(e), kMaxLevels - 1));
+        // the split scan's thresholds (e.g. both 1: every partition gets a byte-plane copy, every tile-aligned long run reads it)
+        if (const char* e = std::getenv("QADC_SPLIT_MIN_CODES")) idx->split_min_codes = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_SPLIT_MIN_RUN")) idx->split_min_run = std::strtoull(e, nullptr, 10);
     }
     if (int rc = attach_streams(idx)) {
         delete idx;
@@ -1332,6 +1344,7 @@ int qadc_index_destroy(qadc_index* idx) {
             if (p.d_labels) (void)hipFree(p.d_labels);
         }
         if (p.d_starts) (void)hipFree(p.d_starts);
+        if (p.d_split) (void)hipFree(p.d_split);
     }
     idx->feed.d_codebooks.release();
     idx->feed.d_rotation.release();
@@ -1589,6 +1602,30 @@ int qadc_index_finalize(qadc_index* idx, float keep) {
     }
     HIPCHECK(idx->d_partdesc.ensure(pd.size()));
     HIPCHECK(hipMemcpy(idx->d_partdesc.p, pd.data(), pd.size() * sizeof(PartDesc), hipMemcpyHostToDevice));
+    // byte-plane copies of code bytes 0-6 for the split scan (16x4, partitions of at least split_min_codes codes held here).  The
+    // row-major codes stay the source of every other kernel.  A copy that cannot be allocated is skipped (the runs of that
+    // partition take the row-major form) and counted in the profile.  Borrowed codes (qadc_index_add_partition_device) get no
+    // copy: the caller may change them after finalize, and a copy would then disagree with them.
+    idx->prof.split_copy_bytes = 0;
+    idx->prof.split_copy_failed = 0;
+    for (auto& p : idx->parts) {
+        if (p.d_split) {
+            HIPCHECK(hipDeviceSynchronize());
+            HIPCHECK(hipFree(p.d_split));
+            p.d_split = nullptr;
+        }
+        if (idx->M != 16 || idx->split_min_codes == 0 || p.n < idx->split_min_codes || !p.d_codes || !p.own) continue;
+        const uint64_t bytes = split_copy_bytes(p.n);
+        if (hipMalloc(reinterpret_cast<void**>(&p.d_split), bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p.d_split = nullptr;
+            idx->prof.split_copy_failed++;
+            continue;
+        }
+        launch_split_copy(p.d_codes, p.n, p.d_split, idx->stream);
+        HIPCHECK(hipGetLastError());
+        idx->prof.split_copy_bytes += bytes;
+    }
     // (the query kernels run on non-blocking streams, which do not wait for the null stream this copy from pageable memory is issued
     // on; whatever the runtime's staging does, nothing of the table is in flight when the first query is launched)
     HIPCHECK(hipDeviceSynchronize());
@@ -1932,7 +1969,19 @@ int qadc_profile_read(qadc_index* idx, qadc_profile* out) {
 
 int qadc_profile_reset(qadc_index* idx) {
     if (!idx) return fail(QADC_E_ARG, "null index");
+    const uint64_t copy_bytes = idx->prof.split_copy_bytes, copy_failed = idx->prof.split_copy_failed;   // (state, not counters)
     idx->prof = qadc_profile{};
+    idx->prof.split_copy_bytes = copy_bytes;
+    idx->prof.split_copy_failed = copy_failed;
+    return QADC_OK;
+}
+
+int qadc_index_set_split(qadc_index* idx, uint64_t min_codes, uint64_t min_run) {
+    if (!idx) return fail(QADC_E_ARG, "null index");
+    if (idx->finalized && min_codes != idx->split_min_codes)
+        return fail(QADC_E_STATE, "split_min_codes takes effect at qadc_index_finalize: set it before");
+    idx->split_min_codes = min_codes;
+    idx->split_min_run = min_run;
     return QADC_OK;
 }
 

@@ -98,6 +98,7 @@ struct Part {
     uint32_t start_n = 0;
     uint32_t key_base = 0;
     bool own = true;
+    uint8_t* d_split = nullptr;    // 16x4: byte-plane copy of code bytes 0-6 for the split scan (kSplitTile), or null
 };
 
 constexpr int kMergeStreams = 3;   // streams the enqueued merges MAY rotate over (measurement hook); the default creates ONE:
@@ -115,6 +116,7 @@ struct LevelLaunch {
     bool small;     // small-run kernel (runs below idx->small_run codes)
     bool shared;    // every run of the launch covers the same codes (one run per query): sibling-major launch
     bool mq;        // ... and groups of 8 of them share one pass (scan_i8_mq_kernel)
+    bool split;     // every run of the launch reads the byte-plane copy (split form of scan_i8_kernel)
     uint64_t maxn;  // longest run of the launch
     bool early;     // launched on the front stream, under the previous batch's long levels: counted, not event-timed
     int ev = -1;    // index of the HIP event recorded before the launch (the next one follows it), -1 = not timed
@@ -415,6 +417,10 @@ struct qadc_index {
     WorkerPool pool;                   // host replay workers (started on first use)
     uint32_t small_run = 1u << 17;  // runs shorter than this use the small-run kernel
     int variant = 0x0d;    // kernel tuning variant (see launch_scan_i8): U=2, non-temporal loads, chunked tiles
+    // split scan (16x4): qadc_index_finalize builds the byte-plane copy of every partition of at least split_min_codes codes
+    // (0 = never), and one-query-per-pass launches read it for runs of at least split_min_run codes (qadc_index_set_split)
+    uint64_t split_min_codes = 1ull << 25;
+    uint64_t split_min_run = 1ull << 23;
     // one workgroup per query (IVF batches, small lists): 0 = never, 1 = auto, 2 = whenever structurally possible
     int wgq = 1;
     uint32_t wgq_capacity = 4096;        // stream entries per query to start with

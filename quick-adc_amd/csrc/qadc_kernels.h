@@ -21,7 +21,17 @@ struct ScanItem {
     uint32_t dup_pos;        // position (in the partition) of the code the reference replays in its padding
                              // lanes, if this run's partition end is held here; else 0xffffffff
     uint32_t dup_reps;       // number of extra replays of that code: (16 - n % 16) % 16
+    const uint8_t* split;    // 16x4: the run's first tile in the partition's byte-plane copy (launch_split_copy), or nullptr
 };
+
+// Byte-plane copy of code bytes 0-6 (16x4 only), the input of the split form of scan_i8_kernel: tile t of a partition holds
+// codes [t * kSplitTile, (t + 1) * kSplitTile) as 7 planes of kSplitTile bytes each (plane b = byte b of consecutive codes) at
+// byte t * 7 * kSplitTile.  One tile is one workgroup iteration of the split form: 1024 lanes x 16 codes.  Padded to whole
+// tiles (codes past the partition's end read as 0).  Byte 7 stays in the row-major array only.
+constexpr uint32_t kSplitTile = 16384;
+constexpr uint32_t kSplitBytes = 7;
+inline uint64_t split_copy_bytes(uint32_t n) { return ((uint64_t)n + kSplitTile - 1) / kSplitTile * kSplitBytes * kSplitTile; }
+void launch_split_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipStream_t stream);
 
 // Candidate emitted by the scan: value < bound derived from a strict prefix of the scan order.
 struct Cand {

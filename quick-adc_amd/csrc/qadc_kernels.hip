@@ -315,6 +315,189 @@ __global__ __launch_bounds__(kWG, (M == 16 ? 8 : 4)) void scan_i8_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
+// Split form of scan_i8_kernel (16x4, one query per pass): the run is streamed from the partition's byte-plane copy of
+// code bytes 0-6 (kSplitTile, launch_split_copy), 7 of the 8 bytes per code.  Pair-table entries are >= 0, so the 7-byte
+// sum is a lower bound on the code's value: a code with min(127, partial7) >= bound cannot be a candidate and is dropped
+// without its last byte.  A survivor (partial7 < bound) reads byte 7 from the row-major array and is finished exactly as in
+// scan_i8_kernel: cand = min(127, partial7 + P_7[byte7]), emitted when cand < bound.  Survivors are resolved one
+// iteration late: their byte-7 loads are issued behind the NEXT iteration's plane loads, so the dependent misses overlap
+// the stream instead of stalling it.  A lane holds 16 codes per iteration (one 16-byte load per plane: a wave reads 1 KiB
+// contiguous of each plane, a workgroup one tile = 112 KiB contiguous).
+// PROBE: XOR of the 7 planes, no byte 7 (the streaming ceiling of this form; results meaningless).
+// ---------------------------------------------------------------------------------------------
+template <bool NT, bool CHUNK, bool PROBE>
+__global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
+    const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
+    CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R) {
+    using C = ScanCfg<16>;
+    const ScanItem it = items[blockIdx.y];
+    QueryState* qs = qstates + it.query;
+    out += (uint64_t)it.query * cand_cap;
+    build_pair_tables<16>(qtables + (uint64_t)it.table * 256);
+    const uint32_t bound = prefix_bound(qs, it.order >> 16, R, reinterpret_cast<uint32_t*>(smem + C::HIST_OFF),
+                                        reinterpret_cast<uint32_t*>(smem + C::BOUND_OFF));
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane_lo = (tid & 31u) * 4u;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) u32x4* gvec_t;
+    typedef const __attribute__((address_space(1))) unsigned char* gbyte_t;
+    const gvec_t planes = (gvec_t)(uintptr_t)it.split;
+    const gbyte_t byte7 = (gbyte_t)(uintptr_t)(it.codes + 7);     // byte 7 of run code r at 8 r
+    lds_base_is_zero();
+    const uint32_t n = it.n;
+    const uint32_t ntiles = (n + kSplitTile - 1) / kSplitTile;
+    uint32_t first = blockIdx.x, last = ntiles, step = gridDim.x;
+    if (CHUNK) {
+        const uint32_t per = (ntiles + gridDim.x - 1) / gridDim.x;
+        first = blockIdx.x * per;
+        last = min(ntiles, first + per);
+        step = 1;
+    }
+    const uint32_t tiles_full = n / kSplitTile;
+    const uint32_t full_last = min(last, tiles_full);
+
+    // survivors of the previous iteration: byte c of pend = min(127, partial7) of the lane's code c, 0xff = none
+    uint32_t pend[4] = {~0u, ~0u, ~0u, ~0u};
+    uint32_t pend_base = 0;                                     // run index of the lane's code 0 in that iteration
+    bool any_pend = false;
+    // ... and after their byte 7: byte c of res = the candidate's value (< bound), 0xff = none
+    uint32_t res[4];
+    uint32_t res_base = 0;
+    bool any_res = false;
+
+    auto resolve = [&]() __attribute__((always_inline)) {                                      // pend -> res (byte-7 loads all in flight together)
+        uint32_t x[16];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            x[c] = 0;
+            if (((pend[c >> 2] >> (8 * (c & 3))) & 0xffu) != 0xffu) x[c] = byte7[(uint64_t)(pend_base + c) * 8u];
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            uint32_t r = ~0u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t pv = (pend[w] >> (8 * k)) & 0xffu;
+                // P_7[x]: dword group g = 1 (+128), byte j = 3
+                const uint32_t s = pv + *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((x[4 * w + k] << 8) | lane_lo) + 131u));
+                const uint32_t cv = min(s, 127u);
+                if (pv != 0xffu && cv < bound) r &= ~(0xffu << (8 * k)) | (cv << (8 * k));
+            }
+            res[w] = r;
+        }
+        res_base = pend_base;
+        any_res = (res[0] & res[1] & res[2] & res[3]) != ~0u;
+    };
+    auto emit_res = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const uint32_t r = (res[c >> 2] >> (8 * (c & 3))) & 0xffu;
+            if (r != 0xffu)
+                emit_candidate(qs, hdr, out, cand_cap, it.labels, it.key_base, it.order, it.dup_pos, it.dup_reps,
+                               it.pos0 + res_base + c, r);
+        }
+    };
+    auto step_tile = [&](uint32_t t, auto full) __attribute__((always_inline)) {
+        u32x4 v[kSplitBytes];
+        const uint32_t e0 = t * (kSplitBytes * kSplitTile / 16) + tid;     // vector index of plane 0
+#pragma unroll
+        for (int b = 0; b < (int)kSplitBytes; ++b)
+            v[b] = NT ? __builtin_nontemporal_load(planes + e0 + b * (kSplitTile / 16)) : planes[e0 + b * (kSplitTile / 16)];
+        if (__builtin_expect(any_pend, 0)) resolve();           // the previous iteration's survivors, behind this one's loads
+        const uint32_t base = t * kSplitTile + tid * 16u;       // run index of the lane's code 0
+        uint32_t cv[16];
+        uint32_t best = 127u;
+        if (PROBE) {
+            u32x4 a = v[0];
+#pragma unroll
+            for (int b = 1; b < (int)kSplitBytes; ++b) a ^= v[b];
+            const uint32_t s = a.x ^ a.y ^ a.z ^ a.w;
+#pragma unroll
+            for (int c = 0; c < 16; ++c) cv[c] = 127u;
+            cv[0] = (s == 0x12345678u) ? 0u : 127u;
+            best = cv[0];
+        } else {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t d[kSplitBytes] = {v[0][w], v[1][w], v[2][w], v[3][w], v[4][w], v[5][w], v[6][w]};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    uint32_t s = 0;
+#pragma unroll
+                    for (int b = 0; b < (int)kSplitBytes; ++b) {
+                        // byte0 = bank*4, byte1 = code byte k of plane b; table b at (b >> 2) * 128 + (b & 3)
+                        const uint32_t a = __builtin_amdgcn_perm(d[b], lane_lo, 0x0c0c0000u | ((4u + k) << 8));
+                        s += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(a + (b >> 2) * 128 + (b & 3)));
+                    }
+                    uint32_t c = min(s, 127u);
+                    if (!decltype(full)::value) c = base + 4 * w + k < n ? c : 127u;   // past the run's end: never < bound
+                    cv[4 * w + k] = c;
+                    best = min(best, c);
+                }
+            }
+        }
+        any_pend = false;
+        if (__builtin_expect(best < bound, 0)) {                // rare: one branch per 16 codes
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                uint32_t p = ~0u;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (cv[4 * w + k] < bound) p &= ~(0xffu << (8 * k)) | (cv[4 * w + k] << (8 * k));
+                pend[w] = p;
+            }
+            pend_base = base;
+            any_pend = true;
+        }
+        if (__builtin_expect(any_res, 0)) {                     // the previous iteration's candidates
+            emit_res();
+            any_res = false;
+        }
+    };
+    using full_t = std::integral_constant<bool, true>;
+    using part_t = std::integral_constant<bool, false>;
+    uint32_t t = first;
+    for (; t < full_last; t += step) step_tile(t, full_t());
+    for (; t < last; t += step) step_tile(t, part_t());
+    if (any_pend) {
+        resolve();
+        if (any_res) emit_res();
+    }
+}
+
+// The byte-plane copy of a partition (kSplitTile layout): one thread per 16 codes of a tile, plane b's 16 bytes = byte b
+// of the 16 codes.  Reads the row-major codes once, writes 7/8 of them; run once per partition by qadc_index_finalize.
+__global__ __launch_bounds__(256) void split_copy_kernel(const uint8_t* __restrict__ codes, uint32_t n, uint8_t* __restrict__ copy,
+                                                         uint64_t nthreads) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nthreads) return;
+    const uint64_t tile = g / (kSplitTile / 16), lane = g % (kSplitTile / 16);
+    const uint64_t c0 = tile * kSplitTile + lane * 16;
+    uint32_t o[kSplitBytes][4] = {};
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        uint2 v = make_uint2(0u, 0u);
+        if (c0 + c < n) v = *reinterpret_cast<const uint2*>(codes + (c0 + c) * 8);
+#pragma unroll
+        for (int b = 0; b < (int)kSplitBytes; ++b) {
+            const uint32_t byte = ((b < 4 ? v.x : v.y) >> (8 * (b & 3))) & 0xffu;
+            o[b][c >> 2] |= byte << (8 * (c & 3));
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < (int)kSplitBytes; ++b)
+        *reinterpret_cast<uint4*>(copy + tile * kSplitBytes * kSplitTile + (uint64_t)b * kSplitTile + lane * 16) =
+            make_uint4(o[b][0], o[b][1], o[b][2], o[b][3]);
+}
+
+void launch_split_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipStream_t stream) {
+    const uint64_t nthreads = ((uint64_t)n + kSplitTile - 1) / kSplitTile * (kSplitTile / 16);
+    if (!nthreads) return;
+    hipLaunchKernelGGL(split_copy_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream, d_codes, n, d_copy, nthreads);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Multi-query streaming scan: ONE pass over the codes serves up to 8 queries.
 //
 // Once the queries of a batch share the codes through L2 (sibling-major launch above), scan_i8_kernel is bound
@@ -921,11 +1104,34 @@ static void launch_scan_variant(dim3 grid, hipStream_t stream, const ScanItem* d
     hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<M>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, sib_items);
 }
 
+template <bool NT, bool CHUNK, bool PROBE>
+static void launch_split_variant(dim3 grid, hipStream_t stream, const ScanItem* d_items, const int8_t* d_qtables,
+                                 QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap, uint32_t R) {
+    auto k = &scan_i8_split_kernel<NT, CHUNK, PROBE>;
+    static std::atomic<uint64_t> done{0};
+    ensure_dynamic_lds(reinterpret_cast<const void*>(k), ScanCfg<16>::LDS_BYTES, done);
+    hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<16>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R);
+}
+
 // variant bits: [2] NT (non-temporal loads)  [3] CHUNK  [4] PROBE (ceiling diagnostic)
+// [5] split form (16x4, every run of the launch has ScanItem::split; not with [6])
 // [6] sibling-major 1-D launch (every run of the launch covers the same codes; see the kernel's decode).  Other bits: ignored.
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap,
                     uint32_t R, hipStream_t stream) {
+    if (M == 16 && (variant & 32) && !(variant & 64)) {
+        const dim3 grid(wgs_per_item, nitems);
+#define QADC_SPLIT(PR)                                                                                                  \
+    switch ((variant >> 2) & 3) {                                                                                       \
+        case 0: launch_split_variant<false, false, PR>(grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R); break; \
+        case 1: launch_split_variant<true, false, PR>(grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R); break;  \
+        case 2: launch_split_variant<false, true, PR>(grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R); break;  \
+        default: launch_split_variant<true, true, PR>(grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R); break;  \
+    }
+        if (variant & 16) { QADC_SPLIT(true) } else { QADC_SPLIT(false) }
+#undef QADC_SPLIT
+        return;
+    }
     const bool sib = (variant & 64) != 0;
     const dim3 grid = sib ? dim3((unsigned)wgs_per_item * (unsigned)nitems) : dim3(wgs_per_item, nitems);
     const uint32_t sib_items = sib ? (uint32_t)nitems : 0u;

@@ -1,0 +1,79 @@
+"""Same-process A/B of the split scan and the sweep behind its two thresholds.
+usage: python tools/split_ab.py [reps]        (default 3 rounds; arms interleaved inside every round)
+
+Part 1, split_min_run: the headline's list and mode (10^9 codes, bench.py's one-query-per-pass options, 32-query steps
+pipelined three deep as bench.py's run_steps), ONE index with its byte-plane copy; arms: split off (row-major scan) and
+split_min_run = 2, 8, 32, 128 Mi.  Part 2, split_min_codes: lists of 1.6 x 10^7 codes (inside the 256 MiB Infinity Cache) and
+4 x 10^7 codes (above it), copy built, arms split off / on at split_min_run = 2^23.
+Prints one JSON line per (part, list, round, arm): ms per step over K steps and the library's split_codes per step."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+
+OFF = 1 << 40                     # split_min_run above any run: the row-major form
+MI = 1 << 20
+
+
+def main():
+    import torch
+    import pyqadc
+    torch.zeros(1, device="cuda:0")
+    pyqadc.device_prepare(0)
+    import gc
+    gc.collect(); gc.freeze(); gc.disable()
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
+    steps, warmup, nq, M = 10, 3, 32, 16
+    rng = np.random.default_rng(1234)
+    codebooks = rng.normal(size=(M, 16, 128 // M)).astype(np.float32)
+    pool = [bench.make_tables(rng, codebooks, nq) for _ in range(4)]
+    assign = np.zeros((nq, 1), np.int32)
+
+    def run(idx, k):
+        pending = []
+        for s in range(k):
+            idx.submit(s % 3, assign, pool[s % len(pool)].copy(), bench.R)
+            pending.append(s % 3)
+            if len(pending) == 3:
+                idx.collect(pending.pop(0))
+        while pending:
+            idx.collect(pending.pop(0))
+
+    def measure(idx, min_codes, min_run):
+        idx.set_split(min_codes, min_run)
+        run(idx, warmup)
+        idx.profile_reset()
+        t0 = time.perf_counter()
+        run(idx, steps)
+        ms = (time.perf_counter() - t0) * 1e3 / steps
+        return ms, idx.profile()["split_codes"] // steps
+
+    plan = [("min_run", int(1e9), [("off", OFF), ("2Mi", 2 * MI), ("8Mi", 8 * MI), ("32Mi", 32 * MI), ("128Mi", 128 * MI)]),
+            ("min_codes", int(1.6e7), [("off", OFF), ("on", 8 * MI)]),
+            ("min_codes", int(4e7), [("off", OFF), ("on", 8 * MI)])]
+    for part, n, arms in plan:
+        idx = pyqadc.Index(M, 0)
+        idx.set_split(1, OFF)                                  # build the copy whatever the list's size
+        idx.add_partition_synthetic_shard(n, 0, n, bench.SEED, max(1, int(np.float32(n) * np.float32(bench.KEEP))))
+        idx.finalize(bench.KEEP)
+        idx.set_option("profile", 1)
+        bench.set_mode(idx, bench.MODE_ONE_QUERY_PER_PASS)
+        copy_bytes = idx.profile()["split_copy_bytes"]
+        for rep in range(reps):
+            order = arms if rep % 2 == 0 else arms[::-1]       # alternate the order: no arm always follows the same one
+            for name, min_run in order:
+                ms, sc = measure(idx, 1, min_run)
+                print(json.dumps({"part": part, "codes": n, "round": rep, "arm": name, "ms_per_step": round(ms, 4),
+                                  "codes_per_s": round(n * nq / ms * 1e3, 1), "split_codes_per_step": int(sc),
+                                  "copy_bytes": int(copy_bytes)}), flush=True)
+        idx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -466,6 +466,10 @@ typedef struct qadc_profile {
     uint64_t split_codes;           /* codes those launches scanned (they read 7 bytes per code, plus byte 7 of the survivors) */
     uint64_t split_copy_bytes;      /* device bytes of the byte-plane copies qadc_index_finalize built (kept across resets) */
     uint64_t split_copy_failed;     /* partitions whose copy could not be allocated: their runs take the row-major form */
+    uint64_t split6_launches;       /* of split_launches: launches of the 6-plane form (qadc_index_set_split6) */
+    uint64_t split6_codes;          /* of split_codes: codes those scanned (6 bytes per code, plus one row-major line per survivor) */
+    uint64_t split_survivors;       /* (code, query) pairs of the 6-plane launches whose 6-byte partial sum was below the bound,
+                                       i.e. whose two deferred bytes were read (counted on the device, with "profile" on only) */
 } qadc_profile;
 
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);
@@ -477,6 +481,12 @@ int qadc_profile_reset(qadc_index* idx);
  * min_codes must be set before qadc_index_finalize.  The copy is made from the codes as they are at finalize; partitions of
  * borrowed device codes (qadc_index_add_partition_device) get none.  Defaults: profiles/r07_split_sweep.txt. */
 int qadc_index_set_split(qadc_index* idx, uint64_t min_codes, uint64_t min_run);
+
+/* 6-plane form of the split scan: a split launch whose runs all have at least min_run6 codes streams
+ * 6 of the copy's 7 planes; per query table, the byte whose pair-table entries are smallest is deferred together with byte 7
+ * and read, from the row-major codes, for the survivors only.  It needs no memory beyond the copy and changes no result.
+ * 0 = never.  May be set at any time; applies to batches submitted afterwards.  Default 2^25: profiles/r08_split6_sweep.txt. */
+int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6);
 
 /* ---------------------------------------------------------------------------------------------
  * Float ADC over whole-byte PQ codes — the reference's OTHER query front end, db_query's plain

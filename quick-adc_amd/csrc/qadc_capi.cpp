@@ -175,7 +175,7 @@ int plan_batch(qadc_index* idx, Slot& s, BatchPlan& plan) {
         // one launch for the short runs of the level, one for the long ones (one more for those of them with a byte-plane copy)
         for (int cls = 0; cls < 3; ++cls) {
             const int small = cls == 0 ? 1 : 0;
-            uint64_t maxn = 0, codes = 0;
+            uint64_t maxn = 0, minn = ~0ull, codes = 0;
             size_t cnt = 0;
             bool same = true;
             for (auto& it : per_level[k]) {
@@ -188,6 +188,7 @@ int plan_batch(qadc_index* idx, Slot& s, BatchPlan& plan) {
                 }
                 all_items[off + cnt++] = it;
                 maxn = std::max<uint64_t>(maxn, it.n);
+                minn = std::min<uint64_t>(minn, it.n);
                 codes += it.n;
             }
             if (!cnt) continue;
@@ -201,6 +202,7 @@ int plan_batch(qadc_index* idx, Slot& s, BatchPlan& plan) {
             ll.shared = !ll.small && same && cnt >= 2 && idx->share_variant != 0;
             ll.mq = ll.shared && idx->mq;
             ll.split = cls == 2 && !ll.shared;
+            ll.split6 = ll.split && idx->split6_min_run != 0 && minn >= idx->split6_min_run;
             if (ll.mq) {
                 // 8 queries per pass (scan_i8_mq_kernel): 256-thread workgroups, ~64 Ki codes each, groups of 8
                 // queries as L2-sharing siblings
@@ -344,6 +346,10 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
     s.h_export_flags = reinterpret_cast<uint32_t*>(s.h_result.p + sizeof(float) * (size_t)s.R * nq);
     HIPCHECK(s.d_cands.ensure((size_t)nq * s.cap_q));
     HIPCHECK(s.d_qtables.ensure(nt));
+    // the 6-plane split form's deferred byte per table, computed where the int8 tables become known (below)
+    bool any_split6 = false;
+    for (auto& ll : s.launches) any_split6 = any_split6 || ll.split6;
+    if (any_split6) HIPCHECK(s.d_plane_sel.ensure((size_t)nq * ma));
     // The front of the batch (state clear, table build, float pre-scan, selects, quantizer) depends on nothing the
     // previous batch produces: it runs on its own high-priority stream, under that batch's streaming launches, and
     // the first scan level waits for it.  Its short single-workgroup selects are pure latency; hidden this way they
@@ -433,11 +439,12 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
             launch_prescan_minmax(d_sel, s.inj_n, nq, s.d_qs, st);
         }
         launch_select_kth(d_sel, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 4, d_ft, s.d_qtables.p, tda,
-                          idx->quant_mode, st);
+                          idx->quant_mode, st, nullptr, nullptr, nullptr, 0, any_split6 ? s.d_plane_sel.p : nullptr);
         if (idx->profile) HIPCHECK(prof_event(s, st));
     } else {
         s.d_qt = s.front_sharded ? s.d_qtables.p                             // (a sharded-front batch redone here: the gathered tables)
                                  : reinterpret_cast<const int8_t*>(s.d_in.p + off_tables);     // caller's int8 tables, as uploaded
+        if (any_split6) launch_plane_choice(s.d_qt, nq * ma, s.d_plane_sel.p, st);
         if (idx->profile) { HIPCHECK(prof_event(s, st)); HIPCHECK(prof_event(s, st)); }
     }
 
@@ -457,7 +464,9 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
                                                                    // build, see scan_i8_mq_kernel; <= 4 runs: the build with the 4-seat body)
         else
             launch_scan_i8(M, ll.shared ? (idx->share_variant & ~32) : (variant & ~(64 | 32)) | (ll.split ? 32 : 0), s.d_items + ll.first,
-                           ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str);
+                           ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str,
+                           ll.split6 ? s.d_plane_sel.p : nullptr,
+                           ll.split6 && idx->profile ? reinterpret_cast<unsigned long long*>(s.d_hdr->pad) : nullptr);
     };
     // The first levels of a batch are short launches in a dependent chain (each level's bound needs the previous
     // levels' candidates): latency, not work.  The head launch and the levels with short runs join the front — same
@@ -860,6 +869,7 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[0], s.prof_ev[1]));
             if (s.float_path) idx->prof.start_ms += ms;
         }
+        bool count_survivors = false;
         for (auto& ll : s.launches) {
             if (ll.small || ll.early) {                      // counted, not timed (see plan_and_launch)
                 idx->prof.small_launches++;
@@ -871,10 +881,18 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             idx->prof.mq_launches += ll.mq ? 1 : 0;
             idx->prof.split_launches += ll.split ? 1 : 0;
             idx->prof.split_codes += ll.split ? ll.codes : 0;
+            idx->prof.split6_launches += ll.split6 ? 1 : 0;
+            idx->prof.split6_codes += ll.split6 ? ll.codes : 0;
+            count_survivors = count_survivors || ll.split6;
             idx->prof.pass_codes += ll.mq ? ll.codes / (uint64_t)ll.nitems * (uint64_t)((ll.nitems + 7) / 8) : ll.codes;
             if (ll.ev < 0 || (size_t)ll.ev + 1 >= s.prof_used) continue;   // not the first launch of its timed group
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[ll.ev], s.prof_ev[ll.ev + 1]));
             idx->prof.scan_ms += ms;
+        }
+        if (count_survivors) {                               // the 6-plane launches' counter in the batch header (profiling only: a blocking copy)
+            unsigned long long surv = 0;
+            HIPCHECK(hipMemcpy(&surv, s.d_hdr->pad, sizeof(surv), hipMemcpyDeviceToHost));
+            idx->prof.split_survivors += surv;
         }
         if (s.float_path) idx->prof.start_codes += s.start_codes;
     }
@@ -1321,6 +1339,7 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
         // the split scan's thresholds (e.g. both 1: every partition gets a byte-plane copy, every tile-aligned long run reads it)
         if (const char* e = std::getenv("QADC_SPLIT_MIN_CODES")) idx->split_min_codes = std::strtoull(e, nullptr, 10);
         if (const char* e = std::getenv("QADC_SPLIT_MIN_RUN")) idx->split_min_run = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_SPLIT6_MIN_RUN")) idx->split6_min_run = std::strtoull(e, nullptr, 10);   // (1: every split launch streams 6 planes)
     }
     if (int rc = attach_streams(idx)) {
         delete idx;
@@ -1357,7 +1376,7 @@ int qadc_index_destroy(qadc_index* idx) {
     for (Slot* sp : all_slots) {
         Slot& s = *sp;
         s.d_in.release(); s.h_in.release(); s.d_state.release(); s.h_result.release();
-        s.d_ftables.release(); s.d_qtables.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
+        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
         s.h_cands.release(); s.d_stream.release(); s.d_qflags.release(); s.d_fvals.release(); s.d_qcands.release(); s.h_fetch.release();
         s.d_fblock.release(); s.d_fgathered.release(); s.d_front_all.release(); s.h_fmap.release();
         if (s.ev_fa) (void)hipEventDestroy(s.ev_fa);
@@ -1982,6 +2001,12 @@ int qadc_index_set_split(qadc_index* idx, uint64_t min_codes, uint64_t min_run) 
         return fail(QADC_E_STATE, "split_min_codes takes effect at qadc_index_finalize: set it before");
     idx->split_min_codes = min_codes;
     idx->split_min_run = min_run;
+    return QADC_OK;
+}
+
+int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6) {
+    if (!idx) return fail(QADC_E_ARG, "null index");
+    idx->split6_min_run = min_run6;
     return QADC_OK;
 }
 

@@ -117,6 +117,7 @@ struct LevelLaunch {
     bool shared;    // every run of the launch covers the same codes (one run per query): sibling-major launch
     bool mq;        // ... and groups of 8 of them share one pass (scan_i8_mq_kernel)
     bool split;     // every run of the launch reads the byte-plane copy (split form of scan_i8_kernel)
+    bool split6;    // ... and has at least split6_min_run codes: the 6-plane form (the query's table defers a second byte)
     uint64_t maxn;  // longest run of the launch
     bool early;     // launched on the front stream, under the previous batch's long levels: counted, not event-timed
     int ev = -1;    // index of the HIP event recorded before the launch (the next one follows it), -1 = not timed
@@ -176,6 +177,7 @@ struct Slot {
     uint64_t* h_entries = nullptr;
     DevBuf<float> d_ftables;            // float tables built on the device (qadc_search)
     DevBuf<int8_t> d_qtables;
+    DevBuf<uint8_t> d_plane_sel;        // 16x4: the 6-plane split form's deferred byte of every table of the batch (written beside d_qt)
     DevBuf<Cand> d_cands;
     bool wgq_grouped = false;           // the batch took the partition-major second phase
     bool group_fell_back = false;       // ... and overflowed its candidate regions (redone on the level path): under the multi-GPU merge the
@@ -421,6 +423,9 @@ struct qadc_index {
     // (0 = never), and one-query-per-pass launches read it for runs of at least split_min_run codes (qadc_index_set_split)
     uint64_t split_min_codes = 1ull << 25;
     uint64_t split_min_run = 1ull << 23;
+    // ... and stream 6 of the 7 planes where every run of the launch has at least split6_min_run codes (0 = never;
+    // qadc_index_set_split6; profiles/r08_split6_sweep.txt)
+    uint64_t split6_min_run = 1ull << 25;
     // one workgroup per query (IVF batches, small lists): 0 = never, 1 = auto, 2 = whenever structurally possible
     int wgq = 1;
     uint32_t wgq_capacity = 4096;        // stream entries per query to start with

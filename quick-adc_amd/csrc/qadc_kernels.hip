@@ -57,6 +57,12 @@ static void ensure_dynamic_lds(const void* fn, int bytes, std::atomic<uint64_t>&
 // The byte address x*256 + bank*4 is formed by ONE v_perm_b32 from the code dword and the
 // lane constant; (g&1)*128 + j rides in the ds_read immediate offset.
 // ---------------------------------------------------------------------------------------------
+// 6-plane split form: the code byte whose pair table sits in slot s of the LDS image when byte `defer` (0..6) is deferred:
+// slots 0-5 = the streamed bytes 0..6 without `defer`, in order; slot 6 = `defer`; slot 7 = byte 7.
+__host__ __device__ __forceinline__ uint32_t split6_byte(uint32_t s, uint32_t defer) {
+    return s < 6u ? s + (s >= defer ? 1u : 0u) : (s == 6u ? defer : 7u);
+}
+
 template <int M>
 struct ScanCfg {
     static constexpr int CS = M / 2;             // code bytes
@@ -69,8 +75,9 @@ struct ScanCfg {
     static constexpr int LDS_BYTES = BOUND_OFF + 16;
 };
 
-template <int M>
-__device__ __forceinline__ void build_pair_tables(const int8_t* __restrict__ qt) {
+// PERM (6-plane split form): slot s of the image holds the pair table of code byte split6_byte(s, defer) instead of byte s.
+template <int M, bool PERM = false>
+__device__ __forceinline__ void build_pair_tables(const int8_t* __restrict__ qt, uint32_t defer = 0) {
     using C = ScanCfg<M>;
     const int t = threadIdx.x;
     // stage the int8 table (M*16 bytes) into LDS
@@ -92,7 +99,7 @@ __device__ __forceinline__ void build_pair_tables(const int8_t* __restrict__ qt)
         const uint32_t g = (k >> 2) * 2u + (within & 1u);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t b = 4u * g + j;
+            const uint32_t b = PERM ? split6_byte(4u * g + j, defer) : 4u * g + j;
             const uint32_t v = (uint32_t)T[(2 * b) * 16 + (x & 15u)] + (uint32_t)T[(2 * b + 1) * 16 + (x >> 4)];
             w |= v << (8 * j);
         }
@@ -316,34 +323,55 @@ __global__ __launch_bounds__(kWG, (M == 16 ? 8 : 4)) void scan_i8_kernel(
 
 // ---------------------------------------------------------------------------------------------
 // Split form of scan_i8_kernel (16x4, one query per pass): the run is streamed from the partition's byte-plane copy of
-// code bytes 0-6 (kSplitTile, launch_split_copy), 7 of the 8 bytes per code.  Pair-table entries are >= 0, so the 7-byte
-// sum is a lower bound on the code's value: a code with min(127, partial7) >= bound cannot be a candidate and is dropped
-// without its last byte.  A survivor (partial7 < bound) reads byte 7 from the row-major array and is finished exactly as in
-// scan_i8_kernel: cand = min(127, partial7 + P_7[byte7]), emitted when cand < bound.  Survivors are resolved one
-// iteration late: their byte-7 loads are issued behind the NEXT iteration's plane loads, so the dependent misses overlap
-// the stream instead of stalling it.  A lane holds 16 codes per iteration (one 16-byte load per plane: a wave reads 1 KiB
-// contiguous of each plane, a workgroup one tile = 112 KiB contiguous).
-// PROBE: XOR of the 7 planes, no byte 7 (the streaming ceiling of this form; results meaningless).
+// code bytes 0-6 (kSplitTile, launch_split_copy), PLANES = 7 or 6 of the 8 bytes per code.  Pair-table entries are >= 0, so
+// the sum over any subset of the bytes is a lower bound on the code's value: a code with min(127, partial) >= bound cannot
+// be a candidate and is dropped without its deferred bytes.  A survivor (partial < bound) reads them from the row-major
+// array and is finished exactly as in scan_i8_kernel: cand = min(127, partial + the deferred pair entries), emitted when
+// cand < bound.  Survivors are resolved one iteration late: their row-major loads are issued behind the NEXT iteration's
+// plane loads, so the dependent misses overlap the stream instead of stalling it.  A lane holds 16 codes per iteration (one
+// 16-byte load per plane: a wave reads 1 KiB contiguous of each plane, a workgroup one tile = PLANES x 16 KiB).
+//   PLANES = 7: planes 0-6, byte 7 deferred.
+//   PLANES = 6: the query's table also defers byte plane_sel[table] (0..6, plane_choice below: the byte whose pair entries
+//     are smallest, i.e. the one that tightens the partial sum least) and skips that plane of every tile.  The LDS image is
+//     built permuted (split6_byte: streamed bytes in slots 0-5, the deferred two in slots 6 and 7) and the permutation is
+//     folded into the six uniform plane offsets, so the loop's lookups are those of PLANES = 7 without its last.  Survivors
+//     are some 20 times as frequent as with 7 planes, so they are resolved by a loop over the lane's set
+//     survivor bits (the wave runs as many trips as its busiest lane has survivors, usually one), not by a sweep of 16 slots.
+// PROBE: XOR of the streamed planes, no deferred bytes (the streaming ceiling of this form; results meaningless).
+// surv (profile option only, else null): counts the survivors of the 6-plane form, one atomicAdd per workgroup at exit (one
+// per wave, half a million to one address per launch, cost the headline 3 ms a step; the 7-plane form has no register left
+// for the count and does not report it).
 // ---------------------------------------------------------------------------------------------
-template <bool NT, bool CHUNK, bool PROBE>
+template <int PLANES, bool NT, bool CHUNK, bool PROBE>
 __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
     const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
-    CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R) {
+    CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
+    const uint8_t* __restrict__ plane_sel, unsigned long long* __restrict__ surv) {
+    static_assert(PLANES == 6 || PLANES == (int)kSplitBytes, "6 or all 7 planes of the copy");
     using C = ScanCfg<16>;
     const ScanItem it = items[blockIdx.y];
     QueryState* qs = qstates + it.query;
     out += (uint64_t)it.query * cand_cap;
-    build_pair_tables<16>(qtables + (uint64_t)it.table * 256);
+    uint32_t defer = 6;                                         // PLANES == 6: the deferred byte beside byte 7
+    if (PLANES == 6) {
+        defer = min((uint32_t)plane_sel[it.table], 6u);
+        build_pair_tables<16, true>(qtables + (uint64_t)it.table * 256, defer);
+    } else {
+        build_pair_tables<16>(qtables + (uint64_t)it.table * 256);
+    }
     const uint32_t bound = prefix_bound(qs, it.order >> 16, R, reinterpret_cast<uint32_t*>(smem + C::HIST_OFF),
                                         reinterpret_cast<uint32_t*>(smem + C::BOUND_OFF));
 
     const uint32_t tid = threadIdx.x;
     const uint32_t lane_lo = (tid & 31u) * 4u;
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     typedef const __attribute__((address_space(1))) u32x4* gvec_t;
+    typedef const __attribute__((address_space(1))) u32x2* grow_t;
     typedef const __attribute__((address_space(1))) unsigned char* gbyte_t;
     const gvec_t planes = (gvec_t)(uintptr_t)it.split;
     const gbyte_t byte7 = (gbyte_t)(uintptr_t)(it.codes + 7);     // byte 7 of run code r at 8 r
+    const grow_t rows = (grow_t)(uintptr_t)it.codes;              // run code r, all 8 bytes
     lds_base_is_zero();
     const uint32_t n = it.n;
     const uint32_t ntiles = (n + kSplitTile - 1) / kSplitTile;
@@ -356,35 +384,66 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
     }
     const uint32_t tiles_full = n / kSplitTile;
     const uint32_t full_last = min(last, tiles_full);
+    // vector offset of the plane streamed into slot b (uniform; PLANES == 7: b itself)
+    uint32_t poff[PLANES];
+#pragma unroll
+    for (int b = 0; b < PLANES; ++b) poff[b] = (PLANES == 6 ? split6_byte(b, defer) : (uint32_t)b) * (kSplitTile / 16);
+    const uint32_t bound4 = bound * 0x01010101u;
 
-    // survivors of the previous iteration: byte c of pend = min(127, partial7) of the lane's code c, 0xff = none
+    // survivors of the previous iteration: byte c of pend = min(127, partial) of the lane's code c, 0xff = none
     uint32_t pend[4] = {~0u, ~0u, ~0u, ~0u};
     uint32_t pend_base = 0;                                     // run index of the lane's code 0 in that iteration
     bool any_pend = false;
-    // ... and after their byte 7: byte c of res = the candidate's value (< bound), 0xff = none
+    // ... and after their deferred bytes: byte c of res = the candidate's value (< bound), 0xff = none
     uint32_t res[4];
     uint32_t res_base = 0;
     bool any_res = false;
+    uint32_t nsurv = 0;
 
-    auto resolve = [&]() __attribute__((always_inline)) {                                      // pend -> res (byte-7 loads all in flight together)
-        uint32_t x[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            x[c] = 0;
-            if (((pend[c >> 2] >> (8 * (c & 3))) & 0xffu) != 0xffu) x[c] = byte7[(uint64_t)(pend_base + c) * 8u];
-        }
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            uint32_t r = ~0u;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t pv = (pend[w] >> (8 * k)) & 0xffu;
-                // P_7[x]: dword group g = 1 (+128), byte j = 3
-                const uint32_t s = pv + *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((x[4 * w + k] << 8) | lane_lo) + 131u));
+    auto resolve = [&]() __attribute__((always_inline)) {                                      // pend -> res
+        if constexpr (PLANES == 6) {
+            // bit 8 k + w of m = code 4 w + k survives (bit 7 of its byte in pend[w] is clear)
+            uint32_t m = ((~pend[0] & 0x80808080u) >> 7) | ((~pend[1] & 0x80808080u) >> 6) | ((~pend[2] & 0x80808080u) >> 5) |
+                         ((~pend[3] & 0x80808080u) >> 4);
+            if (surv) nsurv += (uint32_t)__builtin_popcount(m);
+            while (m) {
+                const uint32_t i = (uint32_t)__builtin_ctz(m);
+                m &= m - 1u;
+                const uint32_t w = i & 3u, sh = i & 24u;
+                const u32x2 x = rows[pend_base + 4u * w + (sh >> 3)];
+                const uint32_t pw = w == 0 ? pend[0] : w == 1 ? pend[1] : w == 2 ? pend[2] : pend[3];
+                const uint32_t xd = (uint32_t)(((((uint64_t)x.y) << 32) | x.x) >> (8u * defer)) & 0xffu;
+                // slot 6 (the deferred byte) and slot 7 (byte 7): dword group 1 (+128), bytes 2 and 3
+                const uint32_t s = ((pw >> sh) & 0xffu) +
+                                   *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((xd << 8) | lane_lo) + 130u)) +
+                                   *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((x.y >> 24 << 8) | lane_lo) + 131u));
                 const uint32_t cv = min(s, 127u);
-                if (pv != 0xffu && cv < bound) r &= ~(0xffu << (8 * k)) | (cv << (8 * k));
+                const uint32_t upd = (pw & ~(0xffu << sh)) | ((cv < bound ? cv : 0xffu) << sh);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) pend[u] = w == (uint32_t)u ? upd : pend[u];
             }
-            res[w] = r;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) res[w] = pend[w];
+        } else {
+            uint32_t x[16];                                     // (byte-7 loads all in flight together)
+#pragma unroll
+            for (int c = 0; c < 16; ++c) {
+                x[c] = 0;
+                if (((pend[c >> 2] >> (8 * (c & 3))) & 0xffu) != 0xffu) x[c] = byte7[(uint64_t)(pend_base + c) * 8u];
+            }
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                uint32_t r = ~0u;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t pv = (pend[w] >> (8 * k)) & 0xffu;
+                    // P_7[x]: dword group g = 1 (+128), byte j = 3
+                    const uint32_t s = pv + *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((x[4 * w + k] << 8) | lane_lo) + 131u));
+                    const uint32_t cv = min(s, 127u);
+                    if (pv != 0xffu && cv < bound) r &= ~(0xffu << (8 * k)) | (cv << (8 * k));
+                }
+                res[w] = r;
+            }
         }
         res_base = pend_base;
         any_res = (res[0] & res[1] & res[2] & res[3]) != ~0u;
@@ -399,11 +458,11 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
         }
     };
     auto step_tile = [&](uint32_t t, auto full) __attribute__((always_inline)) {
-        u32x4 v[kSplitBytes];
+        u32x4 v[PLANES];
         const uint32_t e0 = t * (kSplitBytes * kSplitTile / 16) + tid;     // vector index of plane 0
 #pragma unroll
-        for (int b = 0; b < (int)kSplitBytes; ++b)
-            v[b] = NT ? __builtin_nontemporal_load(planes + e0 + b * (kSplitTile / 16)) : planes[e0 + b * (kSplitTile / 16)];
+        for (int b = 0; b < PLANES; ++b)
+            v[b] = NT ? __builtin_nontemporal_load(planes + e0 + poff[b]) : planes[e0 + poff[b]];
         if (__builtin_expect(any_pend, 0)) resolve();           // the previous iteration's survivors, behind this one's loads
         const uint32_t base = t * kSplitTile + tid * 16u;       // run index of the lane's code 0
         uint32_t cv[16];
@@ -411,7 +470,7 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
         if (PROBE) {
             u32x4 a = v[0];
 #pragma unroll
-            for (int b = 1; b < (int)kSplitBytes; ++b) a ^= v[b];
+            for (int b = 1; b < PLANES; ++b) a ^= v[b];
             const uint32_t s = a.x ^ a.y ^ a.z ^ a.w;
 #pragma unroll
             for (int c = 0; c < 16; ++c) cv[c] = 127u;
@@ -420,14 +479,13 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
         } else {
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
-                const uint32_t d[kSplitBytes] = {v[0][w], v[1][w], v[2][w], v[3][w], v[4][w], v[5][w], v[6][w]};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     uint32_t s = 0;
 #pragma unroll
-                    for (int b = 0; b < (int)kSplitBytes; ++b) {
-                        // byte0 = bank*4, byte1 = code byte k of plane b; table b at (b >> 2) * 128 + (b & 3)
-                        const uint32_t a = __builtin_amdgcn_perm(d[b], lane_lo, 0x0c0c0000u | ((4u + k) << 8));
+                    for (int b = 0; b < PLANES; ++b) {
+                        // byte0 = bank*4, byte1 = code byte k of the plane in slot b; table slot b at (b >> 2) * 128 + (b & 3)
+                        const uint32_t a = __builtin_amdgcn_perm(v[b][w], lane_lo, 0x0c0c0000u | ((4u + k) << 8));
                         s += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(a + (b >> 2) * 128 + (b & 3)));
                     }
                     uint32_t c = min(s, 127u);
@@ -438,14 +496,21 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
             }
         }
         any_pend = false;
-        if (__builtin_expect(best < bound, 0)) {                // rare: one branch per 16 codes
+        if (__builtin_expect(best < bound, PLANES == 6)) {      // 7 planes: rare; 6: most wave iterations of a long level
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
-                uint32_t p = ~0u;
+                if constexpr (PLANES == 6) {
+                    // bytes >= bound -> 0xff, four at a time (all bytes and bound are <= 127: no borrow crosses a byte)
+                    const uint32_t p = cv[4 * w] | (cv[4 * w + 1] << 8) | (cv[4 * w + 2] << 16) | (cv[4 * w + 3] << 24);
+                    const uint32_t ge = ((p | 0x80808080u) - bound4) & 0x80808080u;
+                    pend[w] = p | ((ge >> 7) * 0xffu);
+                } else {
+                    uint32_t p = ~0u;
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (cv[4 * w + k] < bound) p &= ~(0xffu << (8 * k)) | (cv[4 * w + k] << (8 * k));
-                pend[w] = p;
+                    for (int k = 0; k < 4; ++k)
+                        if (cv[4 * w + k] < bound) p &= ~(0xffu << (8 * k)) | (cv[4 * w + k] << (8 * k));
+                    pend[w] = p;
+                }
             }
             pend_base = base;
             any_pend = true;
@@ -464,6 +529,40 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
         resolve();
         if (any_res) emit_res();
     }
+    if (PLANES == 6 && surv) {                                  // (uniform) one global atomic per workgroup: the waves' counts meet in LDS
+        uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + C::HIST_OFF);
+        __syncthreads();
+        if (tid == 0) *cnt = 0;
+        __syncthreads();
+        const uint32_t tot = dpp_wave_incl_sum(nsurv);          // lane 63: the wave's count
+        if ((tid & 63u) == 63u && tot) atomicAdd(cnt, tot);
+        __syncthreads();
+        if (tid == 0 && *cnt) atomicAdd(surv, (unsigned long long)*cnt);
+    }
+}
+
+// The deferred byte of the 6-plane split form, once per int8 table: the j in 0..6 whose 256 pair entries
+// q[2j][lo] + q[2j+1][hi] have the smallest sum = 16 x (the sum of the two 16-entry rows); ties: the highest j.
+// The choice changes the survivor rate only, never a result.
+__device__ __forceinline__ uint32_t plane_choice(const int8_t* __restrict__ qt) {
+    const uint8_t* T = reinterpret_cast<const uint8_t*>(qt);
+    uint32_t best = 0xffffffffu, bj = 6;
+    for (uint32_t j = 0; j < 7; ++j) {
+        uint32_t sum = 0;
+        for (int i = 0; i < 32; ++i) sum += T[32 * j + i];
+        if (sum <= best) { best = sum; bj = j; }
+    }
+    return bj;
+}
+
+__global__ __launch_bounds__(256) void plane_choice_kernel(const int8_t* __restrict__ qtables, int ntables, uint8_t* __restrict__ plane_sel) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < ntables) plane_sel[t] = (uint8_t)plane_choice(qtables + (size_t)t * 256);
+}
+
+void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream) {
+    if (ntables <= 0) return;
+    hipLaunchKernelGGL(plane_choice_kernel, dim3((ntables + 255) / 256), dim3(256), 0, stream, d_qtables, ntables, d_plane_sel);
 }
 
 // The byte-plane copy of a partition (kSplitTile layout): one thread per 16 codes of a tile, plane b's 16 bytes = byte b
@@ -1104,31 +1203,40 @@ static void launch_scan_variant(dim3 grid, hipStream_t stream, const ScanItem* d
     hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<M>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, sib_items);
 }
 
-template <bool NT, bool CHUNK, bool PROBE>
+template <int PLANES, bool NT, bool CHUNK, bool PROBE>
 static void launch_split_variant(dim3 grid, hipStream_t stream, const ScanItem* d_items, const int8_t* d_qtables,
-                                 QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap, uint32_t R) {
-    auto k = &scan_i8_split_kernel<NT, CHUNK, PROBE>;
+                                 QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap, uint32_t R,
+                                 const uint8_t* d_plane_sel, unsigned long long* d_surv) {
+    auto k = &scan_i8_split_kernel<PLANES, NT, CHUNK, PROBE>;
     static std::atomic<uint64_t> done{0};
     ensure_dynamic_lds(reinterpret_cast<const void*>(k), ScanCfg<16>::LDS_BYTES, done);
-    hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<16>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R);
+    hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<16>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R,
+                       d_plane_sel, d_surv);
 }
 
 // variant bits: [2] NT (non-temporal loads)  [3] CHUNK  [4] PROBE (ceiling diagnostic)
-// [5] split form (16x4, every run of the launch has ScanItem::split; not with [6])
+// [5] split form (16x4, every run of the launch has ScanItem::split; not with [6]): 6 planes when d_plane_sel (the deferred
+//     byte of every table, launch_plane_choice / launch_select_kth) is given, else 7; d_surv: survivor counter or nullptr
 // [6] sibling-major 1-D launch (every run of the launch covers the same codes; see the kernel's decode).  Other bits: ignored.
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap,
-                    uint32_t R, hipStream_t stream) {
+                    uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel, unsigned long long* d_surv) {
     if (M == 16 && (variant & 32) && !(variant & 64)) {
         const dim3 grid(wgs_per_item, nitems);
-#define QADC_SPLIT(PR)                                                                                                  \
-    switch ((variant >> 2) & 3) {                                                                                       \
-        case 0: launch_split_variant<false, false, PR>(grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R); break; \
-        case 1: launch_split_variant<true, false, PR>(grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R); break;  \
-        case 2: launch_split_variant<false, true, PR>(grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R); break;  \
-        default: launch_split_variant<true, true, PR>(grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R); break;  \
+#define QADC_SPLIT_ARGS grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, d_plane_sel, d_surv
+#define QADC_SPLIT(PL, PR)                                                       \
+    switch ((variant >> 2) & 3) {                                                \
+        case 0: launch_split_variant<PL, false, false, PR>(QADC_SPLIT_ARGS); break; \
+        case 1: launch_split_variant<PL, true, false, PR>(QADC_SPLIT_ARGS); break;  \
+        case 2: launch_split_variant<PL, false, true, PR>(QADC_SPLIT_ARGS); break;  \
+        default: launch_split_variant<PL, true, true, PR>(QADC_SPLIT_ARGS); break;  \
     }
-        if (variant & 16) { QADC_SPLIT(true) } else { QADC_SPLIT(false) }
+        if (d_plane_sel) {
+            if (variant & 16) { QADC_SPLIT(6, true) } else { QADC_SPLIT(6, false) }
+        } else {
+            if (variant & 16) { QADC_SPLIT(7, true) } else { QADC_SPLIT(7, false) }
+        }
+#undef QADC_SPLIT_ARGS
 #undef QADC_SPLIT
         return;
     }
@@ -1911,7 +2019,7 @@ void launch_start_scan_f32(int M, int sum_mode, const StartItem* d_items, int ni
 // evaluation of the same expressions.
 template <int BT>
 __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t* __restrict__ qt, QueryState* qs,
-                               float qmax, int quant_mode, float* red /* [BT] LDS */) {
+                               float qmax, int quant_mode, float* red /* [BT] LDS */, uint8_t* __restrict__ plane_sel) {
     const int t = threadIdx.x;
     float m = FLT_MAX;
     for (int i = t; i < table_dim_all; i += BT) m = fminf(m, tb[i]);
@@ -1936,6 +2044,10 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
         else o = (int8_t)(int)(quant_mode == 0 ? (v - qmin) / delta : (v - qmin) * scale);
         qt[i] = o;
     }
+    if (plane_sel) {                                       // 16x4: the 6-plane split form's deferred byte of each table
+        __syncthreads();
+        for (int i = t; i < table_dim_all / 256; i += BT) plane_sel[i] = (uint8_t)plane_choice(qt + (size_t)i * 256);
+    }
     if (t == 0) { qs->qmin = qmin; qs->flags |= flags; }   // keeps bit3 set by the pre-scan
 }
 
@@ -1949,7 +2061,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
                                                         float* __restrict__ ftables, int8_t* __restrict__ qtables,
                                                         int table_dim_all, int quant_mode,
                                                         float* __restrict__ export_vals,
-                                                        uint32_t* __restrict__ export_flags, uint32_t* __restrict__ front_out) {
+                                                        uint32_t* __restrict__ export_flags, uint32_t* __restrict__ front_out,
+                                                        uint8_t* __restrict__ plane_sel) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t s_prefix, s_k, s_hi, s_cnt;
     __shared__ float red[BT];
@@ -1973,7 +2086,7 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
         }
         if (tid == 0) qs->qmax = FLT_MAX;
         if (qtables) quantize_query<BT>(table_dim_all, ftables + (uint64_t)q * table_dim_all, qtables + (uint64_t)q * table_dim_all,
-                                        qs, FLT_MAX, quant_mode, red);
+                                        qs, FLT_MAX, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr);
         publish_front();
         return;
     }
@@ -2042,7 +2155,7 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
         for (uint32_t i = s_cnt + tid; i < R; i += BT) export_vals[(uint64_t)q * R + i] = qmax;
     }
     if (qtables) quantize_query<BT>(table_dim_all, ftables + (uint64_t)q * table_dim_all, qtables + (uint64_t)q * table_dim_all,
-                                    qs, qmax, quant_mode, red);
+                                    qs, qmax, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr);
     publish_front();
 }
 
@@ -2078,13 +2191,14 @@ void launch_prescan_minmax(const float* d_vals, uint32_t nvals, int nq, QuerySta
 
 void launch_select_kth(const float* d_fc, uint64_t fc_stride, const uint32_t* d_fc_init, int nq, uint32_t R, QueryState* d_qs,
                        int max_passes, float* d_ftables, int8_t* d_qtables, int table_dim_all, int quant_mode,
-                       hipStream_t stream, float* export_vals, uint32_t* export_flags, uint32_t* d_front_out, int small_wg) {
+                       hipStream_t stream, float* export_vals, uint32_t* export_flags, uint32_t* d_front_out, int small_wg,
+                       uint8_t* d_plane_sel) {
     if (small_wg)
         hipLaunchKernelGGL((select_kth_kernel<256>), dim3(nq), dim3(256), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
-                           d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out);
+                           d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel);
     else
         hipLaunchKernelGGL((select_kth_kernel<1024>), dim3(nq), dim3(1024), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
-                           d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out);
+                           d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel);
 }
 
 // ---- stream-layout probe (qadc_stream_probe): does a dispatch that WAITS FOR CUs on stream A hold up stream B? ----

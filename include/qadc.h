@@ -492,8 +492,9 @@ int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6);
  * Float ADC over whole-byte PQ codes — the reference's OTHER query front end, db_query's plain
  * scanner_simple (db_query.cpp:17-46) with scan_standard<uint8_t, NSQ> (query_common.hpp:92-146).
  * A separate engine: it shares no state or option with qadc_index above.  Float tables come from
- * the caller, as scanner_simple receives them.  Candidates are summed in the grouping of the
- * reference as compiled (sum_mode 1) or in source order (sum_mode 0); DESIGN.md section 11.
+ * the caller, as scanner_simple receives them (qadc_adc_query_scan*), or are built on the GPU from
+ * query vectors (qadc_adc_search*).  Candidates are summed in the grouping of the reference as
+ * compiled (sum_mode 1) or in source order (sum_mode 0); DESIGN.md section 11.
  * ------------------------------------------------------------------------------------------- */
 #define QADC_ADC_MAX_R 65536  /* largest heap capacity the qadc_adc_query_* calls take (larger R -> QADC_E_ARG) */
 /* Candidate entries one qadc_adc_query_* call may hold on the device (12 bytes each).  Each query gets a region of
@@ -543,6 +544,53 @@ int qadc_adc_query_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assi
 int qadc_adc_query_scan_candidates(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables,
                                    int R, int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys,
                                    float* cand_vals, uint64_t* offsets);
+
+/* ---- float ADC from query vectors: the feeders of nns_engine(_batch)::process_query (query_common.hpp:194-213, 283-297) on
+ * the GPU, so that no table crosses the bus.  assign_compute_residuals, rotate_multiple_vectors and the distance tables of
+ * every (query, probe) are computed in device memory and scanned there. ---- */
+
+/* base_pq with 8-bit sub-quantizers (quantizers.hpp:96-246): codebooks [sq_count][256][dim / sq_count], copied.  dim must be a
+ * multiple of sq_count, at most 4096 (QADC_E_ARG otherwise).  A new dim drops the rotation and the coarse centroids. */
+int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks);
+/* opq (quantizers.hpp:248-324): rotation [dim][dim], applied as rotate_multiple_vectors does (289-301):
+ * rotated[r] = sum_c x[c] * rotation[r][c], one sequential float sum.  NULL = plain PQ.  After qadc_adc_index_set_pq. */
+int qadc_adc_index_set_rotation(qadc_adc_index* idx, const float* rotation);
+/* index_db's coarse centroids (databases.hpp:176-211): centroids [K][dim]; K must equal the partition count when a search
+ * runs.  Not called, or K = 0: a flat index (flat_db::assign_compute_residuals, databases.hpp:93-101: every probe is
+ * partition 0, the residual is the query).  After qadc_adc_index_set_pq. */
+int qadc_adc_index_set_coarse(qadc_adc_index* idx, int K, const float* centroids);
+/* Device memory for the tables of one pass, in bytes (default 1 GiB, the reference's TABLES_BUFFER_SIZE, query_common.hpp:147;
+ * 0 = that default).  A batch whose tables need more is processed in sub-batches of whole queries, at least one query each;
+ * no result depends on it. */
+int qadc_adc_index_set_table_budget(qadc_adc_index* idx, uint64_t bytes);
+
+/* process_query + query_scan for nq queries [nq][dim]: find_k_neighbors(k = ma) on the coarse centroids (neighbors.cpp:30-76,
+ * exact ties and NaN as the reference's heaps select them), residual, rotation, tables, scan.
+ *   table_form  0 = direct (compute_dists_single_simd_cg, distances.hpp:294-311: what nns_engine builds for ma == 1),
+ *               1 = BLAS expansion (compute_dists_multiple_blas_cg, 277-292: nns_engine for ma > 1, nns_engine_batch always),
+ *               2 = nns_engine's rule (query_common.hpp:292-297)
+ *   sum_mode    of the table sums, the coarse distances and the candidates alike
+ * keys / values / sizes: exactly the outputs of qadc_adc_query_scan;  assign_out [nq][ma] (may be NULL): the probed
+ * partitions, nearest first.  QADC_E_ARG: no qadc_adc_index_set_pq yet; K differs from the partition count; ma > K; a flat
+ * index without a partition; a query whose coarse distances hold a NaN while ma > 256. */
+int qadc_adc_search(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,
+                    uint32_t* keys, float* values, int32_t* sizes, int32_t* assign_out);
+/* The same with the ordered candidate stream for output, as qadc_adc_query_scan_candidates returns it. */
+int qadc_adc_search_candidates(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form,
+                               int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals,
+                               uint64_t* offsets, int32_t* assign_out);
+/* Diagnostics: the feeders alone.  assign_out [nq][ma], tables_out [nq][ma][sq_count*256] (either may be NULL): what
+ * qadc_adc_search scans, fetched to the host. */
+int qadc_adc_search_tables(qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode,
+                           int32_t* assign_out, float* tables_out);
+
+/* Database build for 8-bit sub-quantizers, stateless: index_db::add_vectors' compute (databases.hpp:270-298) around
+ * base_pq::encode_multiple_vectors (quantizers.hpp:222-245).  Per vector: with K > 0 find_k_neighbors(k = 1) on coarse [K][dim]
+ * and the residual; the rotation if not NULL; per sub-quantizer the expansion distances to its 256 centroids and the pick of
+ * the capacity-1 heap as compiled (the first smallest distance after the last NaN; 255 if distance 255 is NaN).
+ * vectors [n][dim] -> codes [n][sq_count], assign_out [n] (may be NULL; written when K > 0).  sq_count 4, 8 or 16. */
+int qadc_adc_encode_host(int sq_count, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
+                         const float* vectors, uint64_t n, int sum_mode, int32_t* assign_out, uint8_t* codes, int device_id);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,12 @@
 // by the R-th smallest value the query emitted in the levels before it (FLT_MAX while fewer than R), which is the R-th
 // smallest of a subset of the codes that precede every code of the level.  The kept candidates come back to the host,
 // are put in scan order and pushed into kv_heap<unsigned, float>(R) after the R sentinels.  This engine shares nothing
-// with the 4-bit index but the device's stream set (qadc_device_prepare) and has no qadc_set_option names.
+// with the 4-bit index but the device's stream set (qadc_device_prepare), the coarse-assignment kernels and the float sums
+// of the feeders; it has no qadc_set_option names.
+//
+// The tables of a call come from the caller (qadc_adc_query_scan*) or are built on the device from query vectors
+// (qadc_adc_search*: coarse assignment, residual, OPQ rotation, tables — what nns_engine(_batch)::process_query does before
+// query_scan, query_common.hpp:194-213, 283-297); both share everything after the tables are in device memory.
 #include "../../include/qadc.h"
 
 #include <hip/hip_runtime.h>
@@ -68,6 +73,16 @@ struct qadc_adc_index {
     PinBuf<uint8_t> h_in;
     PinBuf<uint32_t> h_count, h_packed;
     uint64_t reruns = 0;                            // batches re-run because a candidate region overflowed
+    // feeders (qadc_adc_search*): quantizer, coarse centroids and the per-call buffers
+    int dim = 0, K = 0;                             // dim 0: no set_pq yet;  K 0: flat (no coarse quantizer)
+    bool rotated = false;
+    uint64_t table_budget = 1ull << 30;             // bytes of device tables per sub-batch (TABLES_BUFFER_SIZE, query_common.hpp:147)
+    DevBuf<float> d_codebooks, d_cbnorm;            // [nsq][256][dim/nsq];  [2][nsq*256] ||c||^2 under sum_mode 0 and 1
+    DevBuf<float> d_rotation, d_coarse, d_cnorm;    // [dim][dim];  [K][dim];  [2][K]
+    DevBuf<float> d_queries, d_qnorm, d_cdist, d_tables;
+    DevBuf<int32_t> d_assign;
+    PinBuf<int32_t> h_assign;
+    hipEvent_t ev_assign = nullptr;
     std::vector<uint64_t> stream_off;               // [nq + 1] the ordered stream of the last call
     std::vector<uint32_t> stream_keys;
     std::vector<float> stream_vals;
@@ -100,7 +115,7 @@ int grow_labels(DevBuf<uint32_t>& buf, uint64_t used, uint64_t need, hipStream_t
     return QADC_OK;
 }
 
-int check_query_args(const qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode) {
+int check_query_args(const qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const void* tables, int R, int sum_mode) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
     if (nq < 1 || ma < 1 || ma >= 16384) return fail(QADC_E_ARG, "need nq >= 1 and 1 <= ma < 16384");
     if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
@@ -115,8 +130,11 @@ int check_query_args(const qadc_adc_index* idx, int nq, int ma, const int32_t* a
 }
 
 // Scans the batch on the device and leaves the ordered candidate stream of every query in idx->stream_*.
-int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode) {
-    if (int rc = check_query_args(idx, nq, ma, assign, tables, R, sum_mode)) return rc;
+// The tables are the caller's (`tables`, uploaded with the items) or already in device memory (`d_ready`, enqueued on the
+// index's stream before this call; tables is null then).
+int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, const float* d_ready, int R,
+               int sum_mode) {
+    if (int rc = check_query_args(idx, nq, ma, assign, d_ready ? static_cast<const void*>(d_ready) : tables, R, sum_mode)) return rc;
     HIPCHECK(hipSetDevice(idx->device));
     // scan-order length of every query, and the levels
     std::vector<uint64_t> total(nq, 0);
@@ -175,9 +193,9 @@ int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const
     const size_t o_assign = o_base + align_up((size_t)nq * 8, 256);
     const size_t o_items = o_assign + align_up((size_t)nq * ma * 4, 256);
     const size_t o_tables = o_items + align_up(items.size() * sizeof(Item), 256);
-    const size_t in_bytes = o_tables + (size_t)nq * ma * table_floats * 4;
-    HIPCHECK(idx->h_in.ensure(in_bytes));
-    HIPCHECK(idx->d_in.ensure(in_bytes));
+    const size_t in_bytes = o_tables + (d_ready ? 0 : (size_t)nq * ma * table_floats * 4);
+    HIPCHECK(idx->h_in.ensure(std::max<size_t>(in_bytes, 256)));
+    HIPCHECK(idx->d_in.ensure(std::max<size_t>(in_bytes, 256)));
     uint8_t* h = idx->h_in.p;
     uint64_t* h_base = reinterpret_cast<uint64_t*>(h + o_base);
     // bound, counts and regions: written again before a re-run
@@ -195,7 +213,7 @@ int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const
     uint64_t entries = fill_state();
     std::memcpy(h + o_assign, assign, (size_t)nq * ma * 4);
     if (!items.empty()) std::memcpy(h + o_items, items.data(), items.size() * sizeof(Item));
-    std::memcpy(h + o_tables, tables, (size_t)nq * ma * table_floats * 4);
+    if (!d_ready) std::memcpy(h + o_tables, tables, (size_t)nq * ma * table_floats * 4);
     uint8_t* d = idx->d_in.p;
     float* d_bound = reinterpret_cast<float*>(d);
     uint32_t* d_count = reinterpret_cast<uint32_t*>(d + o_count);
@@ -203,7 +221,7 @@ int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const
     const uint64_t* d_base = reinterpret_cast<const uint64_t*>(d + o_base);
     const int32_t* d_assign = reinterpret_cast<const int32_t*>(d + o_assign);
     const Item* d_items = reinterpret_cast<const Item*>(d + o_items);
-    const float* d_tables = reinterpret_cast<const float*>(d + o_tables);
+    const float* d_tables = d_ready ? d_ready : reinterpret_cast<const float*>(d + o_tables);
     HIPCHECK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, idx->stream));
 
     qadc::adc::Db db{idx->codes.p, idx->d_off.p, idx->labeled == 1 ? idx->labels.p : nullptr, idx->d_lab_off.p};
@@ -298,6 +316,151 @@ int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const
     return QADC_OK;
 }
 
+// The heap arrays of every query from the ordered stream of the last scan (db_query.cpp:31-33: the R sentinels first).
+void replay_heaps(qadc_adc_index* idx, int nq, int R, uint32_t* keys, float* values, int32_t* sizes) {
+    auto replay = [&](int q) {
+        qadc::kv_heap<unsigned, float> bh(R);
+        for (int t = 0; t < R; ++t) bh.push(0, std::numeric_limits<float>::max() - t);   // db_query.cpp:31-33
+        for (uint64_t i = idx->stream_off[q]; i < idx->stream_off[q + 1]; ++i) bh.push(idx->stream_keys[i], idx->stream_vals[i]);
+        if (keys) std::copy(bh.keys(), bh.keys() + bh.size(), keys + (size_t)q * R);
+        if (values) std::copy(bh.values(), bh.values() + bh.size(), values + (size_t)q * R);
+        if (sizes) sizes[q] = bh.size();
+    };
+    idx->pool.run(nq, idx->stream_off[nq] > 65536 ? 16 : 1, replay);
+}
+
+// The ordered stream of the last scan into the caller's buffers (qadc_adc_query_scan_candidates' contract).
+int copy_stream(qadc_adc_index* idx, int nq, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets) {
+    std::copy(idx->stream_off.begin(), idx->stream_off.end(), offsets);
+    const uint64_t n = idx->stream_off[nq];
+    if (n > cand_capacity)
+        return fail(QADC_E_CAPACITY, "the candidate stream has " + std::to_string(n) + " entries (offsets[nq]); the buffers hold " +
+                                         std::to_string(cand_capacity));
+    if (n && (!cand_keys || !cand_vals)) return fail(QADC_E_ARG, "cand_keys and cand_vals are required");
+    std::copy(idx->stream_keys.begin(), idx->stream_keys.end(), cand_keys);
+    std::copy(idx->stream_vals.begin(), idx->stream_vals.end(), cand_vals);
+    return QADC_OK;
+}
+
+// ---- feeders: query vectors -> assign + device tables (qadc_adc_search*) ----
+
+constexpr int kCoarseChunk = 32768;   // queries per coarse-assignment pass (the distance scratch is chunk x K floats)
+
+int check_search_args(const qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (!idx->dim) return fail(QADC_E_ARG, "qadc_adc_index_set_pq has not been called: the index has no codebooks");
+    if (nq < 1 || ma < 1 || ma >= 16384 || !queries) return fail(QADC_E_ARG, "need queries, nq >= 1 and 1 <= ma < 16384");
+    if (table_form < 0 || table_form > 2) return fail(QADC_E_ARG, "table_form is 0 (direct), 1 (BLAS expansion) or 2 (nns_engine's rule)");
+    if (sum_mode != 0 && sum_mode != 1) return fail(QADC_E_ARG, "sum_mode is 0 (source order) or 1 (as compiled)");
+    const int parts = (int)idx->sizes.size();
+    if (idx->K) {
+        if (idx->K != parts)
+            return fail(QADC_E_ARG, "the coarse quantizer has " + std::to_string(idx->K) + " centroids and the index " +
+                                        std::to_string(parts) + " partitions");
+        if (ma > idx->K) return fail(QADC_E_ARG, "ma = " + std::to_string(ma) + " exceeds the " + std::to_string(idx->K) + " coarse centroids");
+    } else if (parts < 1) {
+        return fail(QADC_E_ARG, "a flat index (no coarse quantizer) probes partition 0: the index has no partition");
+    }
+    return QADC_OK;
+}
+
+// Uploads the queries and leaves assign [nq][ma] in idx->d_assign, its copy to idx->h_assign enqueued with idx->ev_assign
+// recorded behind it: find_k_neighbors (neighbors.cpp:30-76) through the coarse kernels of the 4-bit index, or all zero for a
+// flat index (flat_db::assign_compute_residuals, databases.hpp:93-101).
+int enqueue_assign(qadc_adc_index* idx, int nq, const float* queries, int ma, int sum_mode) {
+    const int dim = idx->dim;
+    HIPCHECK(idx->d_queries.ensure((size_t)nq * dim));
+    HIPCHECK(idx->d_assign.ensure((size_t)nq * ma));
+    HIPCHECK(idx->h_assign.ensure((size_t)nq * ma));
+    HIPCHECK(hipMemcpyAsync(idx->d_queries.p, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice, idx->stream));
+    if (idx->K) {
+        const int chunk = std::min(nq, kCoarseChunk);
+        HIPCHECK(idx->d_cdist.ensure((size_t)chunk * idx->K));
+        HIPCHECK(idx->d_qnorm.ensure(chunk));
+        if (ma > 256) HIPCHECK(qadc::coarse_nan_unreplayed_reset(idx->stream));
+        for (int o = 0; o < nq; o += kCoarseChunk)
+            qadc::launch_coarse_assign(idx->d_queries.p + (size_t)o * dim, idx->d_coarse.p, std::min(kCoarseChunk, nq - o), idx->K, dim, ma,
+                                       idx->d_qnorm.p, idx->d_cnorm.p + (size_t)sum_mode * idx->K, sum_mode, idx->d_cdist.p,
+                                       idx->d_assign.p + (size_t)o * ma, idx->stream);
+        HIPCHECK(hipGetLastError());
+    } else {
+        HIPCHECK(hipMemsetAsync(idx->d_assign.p, 0, (size_t)nq * ma * 4, idx->stream));
+    }
+    HIPCHECK(hipMemcpyAsync(idx->h_assign.p, idx->d_assign.p, (size_t)nq * ma * 4, hipMemcpyDeviceToHost, idx->stream));
+    HIPCHECK(hipEventRecord(idx->ev_assign, idx->stream));
+    return QADC_OK;
+}
+
+// Waits for the assign copy; refuses a NaN coarse row the selection could not replay (ma > 256: the counter of launch_coarse_assign).
+int wait_assign(qadc_adc_index* idx, int ma) {
+    HIPCHECK(hipEventSynchronize(idx->ev_assign));
+    if (idx->K && ma > 256) {
+        HIPCHECK(hipStreamSynchronize(idx->stream));
+        unsigned int unreplayed = 0;
+        HIPCHECK(qadc::coarse_nan_unreplayed_read(&unreplayed));
+        if (unreplayed)
+            return fail(QADC_E_ARG, "a query has a NaN coarse distance and ma > 256: the reference's heap replay is not available");
+    }
+    return QADC_OK;
+}
+
+int enqueue_tables(qadc_adc_index* idx, int q0, int nq, int ma, int table_form, int sum_mode) {
+    const int expansion = table_form == 2 ? (ma > 1) : table_form;   // nns_engine: direct for ma == 1 (query_common.hpp:292-297)
+    HIPCHECK(qadc::adc::launch_adc_tables(idx->d_queries.p + (size_t)q0 * idx->dim, idx->K ? idx->d_coarse.p : nullptr,
+                                          idx->d_assign.p + (size_t)q0 * ma, idx->d_codebooks.p,
+                                          idx->d_cbnorm.p + (size_t)sum_mode * idx->nsq * 256, idx->rotated ? idx->d_rotation.p : nullptr, nq, ma,
+                                          idx->nsq, idx->dim, expansion, sum_mode, idx->d_tables.p, idx->stream));
+    return QADC_OK;
+}
+
+// queries per sub-batch: whole queries whose tables fit the budget, at least one
+int queries_per_pass(const qadc_adc_index* idx, int nq, int ma) {
+    const uint64_t per_query = (uint64_t)ma * idx->nsq * 256 * 4;
+    return (int)std::min<uint64_t>((uint64_t)nq, std::max<uint64_t>(1, idx->table_budget / per_query));
+}
+
+// Feeders + scan of the whole batch in sub-batches; leaves the ordered stream of all nq queries in idx->stream_*.
+int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, int32_t* assign_out) {
+    if (int rc = check_search_args(idx, nq, queries, ma, table_form, sum_mode)) return rc;
+    if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
+    HIPCHECK(hipSetDevice(idx->device));
+    const int per = queries_per_pass(idx, nq, ma);
+    HIPCHECK(idx->d_tables.ensure((size_t)per * ma * idx->nsq * 256));
+    if (int rc = enqueue_assign(idx, nq, queries, ma, sum_mode)) return rc;
+    if (int rc = enqueue_tables(idx, 0, per, ma, table_form, sum_mode)) return rc;   // (runs while the host plans the first scan)
+    if (int rc = wait_assign(idx, ma)) return rc;
+    if (assign_out) std::memcpy(assign_out, idx->h_assign.p, (size_t)nq * ma * 4);
+    if (per == nq) return scan_batch(idx, nq, ma, idx->h_assign.p, nullptr, idx->d_tables.p, R, sum_mode);
+    std::vector<uint64_t> off{0};
+    std::vector<uint32_t> keys;
+    std::vector<float> vals;
+    for (int q0 = 0; q0 < nq; q0 += per) {
+        const int n = std::min(per, nq - q0);
+        if (q0)   // (the scan before it has been waited for: the table buffer is free)
+            if (int rc = enqueue_tables(idx, q0, n, ma, table_form, sum_mode)) return rc;
+        if (int rc = scan_batch(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, R, sum_mode)) return rc;
+        const uint64_t base = off.back();
+        for (int q = 1; q <= n; ++q) off.push_back(base + idx->stream_off[q]);
+        keys.insert(keys.end(), idx->stream_keys.begin(), idx->stream_keys.end());
+        vals.insert(vals.end(), idx->stream_vals.begin(), idx->stream_vals.end());
+    }
+    idx->stream_off.swap(off);
+    idx->stream_keys.swap(keys);
+    idx->stream_vals.swap(vals);
+    return QADC_OK;
+}
+
+struct Scratch {   // device memory of a stateless entry point, freed on every exit path
+    std::vector<void*> p;
+    ~Scratch() { for (void* x : p) if (x) (void)hipFree(x); }
+    template <typename T> hipError_t alloc(T** out, size_t bytes) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess) { p.push_back(q); *out = static_cast<T*>(q); }
+        return e;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -318,6 +481,12 @@ int qadc_adc_index_create(qadc_adc_index** out, int sq_count, int sq_bits, int d
     if (e != hipSuccess) {
         delete idx;
         return fail(QADC_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+    }
+    const hipError_t ee = hipEventCreateWithFlags(&idx->ev_assign, hipEventDisableTiming);
+    if (ee != hipSuccess) {
+        (void)hipStreamDestroy(idx->stream);
+        delete idx;
+        return fail(QADC_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(ee));
     }
     *out = idx;
     return QADC_OK;
@@ -340,6 +509,18 @@ int qadc_adc_index_destroy(qadc_adc_index* idx) {
     idx->h_in.release();
     idx->h_count.release();
     idx->h_packed.release();
+    idx->d_codebooks.release();
+    idx->d_cbnorm.release();
+    idx->d_rotation.release();
+    idx->d_coarse.release();
+    idx->d_cnorm.release();
+    idx->d_queries.release();
+    idx->d_qnorm.release();
+    idx->d_cdist.release();
+    idx->d_tables.release();
+    idx->d_assign.release();
+    idx->h_assign.release();
+    if (idx->ev_assign) (void)hipEventDestroy(idx->ev_assign);
     if (idx->stream) (void)hipStreamDestroy(idx->stream);
     delete idx;
     return QADC_OK;
@@ -408,16 +589,8 @@ uint32_t qadc_adc_index_partition_size(const qadc_adc_index* idx, int part) {
 int qadc_adc_query_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
                         uint32_t* keys, float* values, int32_t* sizes) {
     DeviceGuard guard;
-    if (int rc = scan_batch(idx, nq, ma, assign, tables, R, sum_mode)) return rc;
-    auto replay = [&](int q) {
-        qadc::kv_heap<unsigned, float> bh(R);
-        for (int t = 0; t < R; ++t) bh.push(0, std::numeric_limits<float>::max() - t);   // db_query.cpp:31-33
-        for (uint64_t i = idx->stream_off[q]; i < idx->stream_off[q + 1]; ++i) bh.push(idx->stream_keys[i], idx->stream_vals[i]);
-        if (keys) std::copy(bh.keys(), bh.keys() + bh.size(), keys + (size_t)q * R);
-        if (values) std::copy(bh.values(), bh.values() + bh.size(), values + (size_t)q * R);
-        if (sizes) sizes[q] = bh.size();
-    };
-    idx->pool.run(nq, idx->stream_off[nq] > 65536 ? 16 : 1, replay);
+    if (int rc = scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode)) return rc;
+    replay_heaps(idx, nq, R, keys, values, sizes);
     return QADC_OK;
 }
 
@@ -425,15 +598,162 @@ int qadc_adc_query_scan_candidates(qadc_adc_index* idx, int nq, int ma, const in
                                    int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets) {
     if (!offsets) return fail(QADC_E_ARG, "offsets is required");
     DeviceGuard guard;
-    if (int rc = scan_batch(idx, nq, ma, assign, tables, R, sum_mode)) return rc;
-    std::copy(idx->stream_off.begin(), idx->stream_off.end(), offsets);
-    const uint64_t n = idx->stream_off[nq];
-    if (n > cand_capacity)
-        return fail(QADC_E_CAPACITY, "the candidate stream has " + std::to_string(n) + " entries (offsets[nq]); the buffers hold " +
-                                         std::to_string(cand_capacity));
-    if (n && (!cand_keys || !cand_vals)) return fail(QADC_E_ARG, "cand_keys and cand_vals are required");
-    std::copy(idx->stream_keys.begin(), idx->stream_keys.end(), cand_keys);
-    std::copy(idx->stream_vals.begin(), idx->stream_vals.end(), cand_vals);
+    if (int rc = scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode)) return rc;
+    return copy_stream(idx, nq, cand_capacity, cand_keys, cand_vals, offsets);
+}
+
+int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks) {
+    if (!idx || !codebooks) return fail(QADC_E_ARG, "index or codebooks is null");
+    if (dim < 1 || dim % idx->nsq != 0)
+        return fail(QADC_E_ARG, "dim = " + std::to_string(dim) + " is not a multiple of sq_count = " + std::to_string(idx->nsq));
+    if (dim > qadc::adc::kAdcMaxDim) return fail(QADC_E_ARG, "dim must be <= " + std::to_string(qadc::adc::kAdcMaxDim));
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(idx->device));
+    const size_t rows = (size_t)idx->nsq * 256;
+    HIPCHECK(idx->d_codebooks.ensure(rows * (dim / idx->nsq)));
+    HIPCHECK(idx->d_cbnorm.ensure(2 * rows));
+    HIPCHECK(hipMemcpyAsync(idx->d_codebooks.p, codebooks, rows * (dim / idx->nsq) * 4, hipMemcpyHostToDevice, idx->stream));
+    for (int mode = 0; mode < 2; ++mode)   // ||c||^2 as compute_cross_dists_blas adds it, once per codebook set
+        qadc::launch_row_sqnorm(idx->d_codebooks.p, (int)rows, dim / idx->nsq, mode, idx->d_cbnorm.p + mode * rows, idx->stream);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(idx->stream));
+    if (dim != idx->dim) {   // a rotation and coarse centroids of another dimension do not carry over
+        idx->rotated = false;
+        idx->K = 0;
+    }
+    idx->dim = dim;
+    return QADC_OK;
+}
+
+int qadc_adc_index_set_rotation(qadc_adc_index* idx, const float* rotation) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (!idx->dim) return fail(QADC_E_ARG, "qadc_adc_index_set_pq comes first: the rotation is [dim][dim]");
+    if (!rotation) {
+        idx->rotated = false;
+        return QADC_OK;
+    }
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(idx->device));
+    HIPCHECK(idx->d_rotation.ensure((size_t)idx->dim * idx->dim));
+    HIPCHECK(hipMemcpyAsync(idx->d_rotation.p, rotation, (size_t)idx->dim * idx->dim * 4, hipMemcpyHostToDevice, idx->stream));
+    HIPCHECK(hipStreamSynchronize(idx->stream));
+    idx->rotated = true;
+    return QADC_OK;
+}
+
+int qadc_adc_index_set_coarse(qadc_adc_index* idx, int K, const float* centroids) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (!idx->dim) return fail(QADC_E_ARG, "qadc_adc_index_set_pq comes first: the centroids are [K][dim]");
+    if (K < 0 || (K > 0 && !centroids)) return fail(QADC_E_ARG, "need K >= 1 centroids (K = 0: a flat index)");
+    if (K == 0) {
+        idx->K = 0;
+        return QADC_OK;
+    }
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(idx->device));
+    HIPCHECK(idx->d_coarse.ensure((size_t)K * idx->dim));
+    HIPCHECK(idx->d_cnorm.ensure(2 * (size_t)K));
+    HIPCHECK(hipMemcpyAsync(idx->d_coarse.p, centroids, (size_t)K * idx->dim * 4, hipMemcpyHostToDevice, idx->stream));
+    for (int mode = 0; mode < 2; ++mode) qadc::launch_row_sqnorm(idx->d_coarse.p, K, idx->dim, mode, idx->d_cnorm.p + (size_t)mode * K, idx->stream);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(idx->stream));
+    idx->K = K;
+    return QADC_OK;
+}
+
+int qadc_adc_index_set_table_budget(qadc_adc_index* idx, uint64_t bytes) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    idx->table_budget = bytes ? bytes : 1ull << 30;
+    return QADC_OK;
+}
+
+int qadc_adc_search(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, uint32_t* keys,
+                    float* values, int32_t* sizes, int32_t* assign_out) {
+    DeviceGuard guard;
+    if (int rc = search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out)) return rc;
+    replay_heaps(idx, nq, R, keys, values, sizes);
+    return QADC_OK;
+}
+
+int qadc_adc_search_candidates(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,
+                               uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets, int32_t* assign_out) {
+    if (!offsets) return fail(QADC_E_ARG, "offsets is required");
+    DeviceGuard guard;
+    if (int rc = search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out)) return rc;
+    return copy_stream(idx, nq, cand_capacity, cand_keys, cand_vals, offsets);
+}
+
+int qadc_adc_search_tables(qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode, int32_t* assign_out,
+                           float* tables_out) {
+    DeviceGuard guard;
+    if (int rc = check_search_args(idx, nq, queries, ma, table_form, sum_mode)) return rc;
+    HIPCHECK(hipSetDevice(idx->device));
+    const int per = queries_per_pass(idx, nq, ma);
+    const size_t per_query = (size_t)ma * idx->nsq * 256;
+    HIPCHECK(idx->d_tables.ensure((size_t)per * per_query));
+    if (int rc = enqueue_assign(idx, nq, queries, ma, sum_mode)) return rc;
+    if (int rc = wait_assign(idx, ma)) return rc;
+    if (assign_out) std::memcpy(assign_out, idx->h_assign.p, (size_t)nq * ma * 4);
+    for (int q0 = 0; q0 < nq && tables_out; q0 += per) {
+        const int n = std::min(per, nq - q0);
+        if (int rc = enqueue_tables(idx, q0, n, ma, table_form, sum_mode)) return rc;
+        HIPCHECK(hipMemcpyAsync(tables_out + (size_t)q0 * per_query, idx->d_tables.p, (size_t)n * per_query * 4, hipMemcpyDeviceToHost, idx->stream));
+        HIPCHECK(hipStreamSynchronize(idx->stream));
+    }
+    return QADC_OK;
+}
+
+int qadc_adc_encode_host(int sq_count, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
+                         const float* vectors, uint64_t n, int sum_mode, int32_t* assign_out, uint8_t* codes, int device_id) {
+    if ((sq_count != 4 && sq_count != 8 && sq_count != 16) || dim < 1 || dim % sq_count != 0 || dim > qadc::adc::kAdcMaxDim || !codebooks ||
+        K < 0 || (K > 0 && !coarse) || (n && (!vectors || !codes)) || (sum_mode != 0 && sum_mode != 1))
+        return fail(QADC_E_ARG, "bad arguments (sq_count 4, 8 or 16; dim a multiple of it, at most " + std::to_string(qadc::adc::kAdcMaxDim) +
+                                    "; sum_mode 0 or 1)");
+    DeviceGuard guard;
+    if (int rc = qadc_device_prepare(device_id)) return rc;
+    HIPCHECK(hipSetDevice(device_id));
+    if (!n) return QADC_OK;
+    Scratch mem;
+    const int ds = dim / sq_count;
+    const size_t rows = (size_t)sq_count * 256;
+    float *d_cb = nullptr, *d_cbnorm = nullptr, *d_rot = nullptr, *d_coarse = nullptr, *d_v = nullptr, *d_x = nullptr, *d_dist = nullptr;
+    int32_t* d_assign = nullptr;
+    uint8_t* d_codes = nullptr;
+    HIPCHECK(mem.alloc(&d_cb, rows * ds * 4));
+    HIPCHECK(mem.alloc(&d_cbnorm, rows * 4));
+    HIPCHECK(hipMemcpy(d_cb, codebooks, rows * ds * 4, hipMemcpyHostToDevice));
+    qadc::launch_row_sqnorm(d_cb, (int)rows, ds, sum_mode, d_cbnorm, nullptr);
+    if (rotation) {
+        HIPCHECK(mem.alloc(&d_rot, (size_t)dim * dim * 4));
+        HIPCHECK(hipMemcpy(d_rot, rotation, (size_t)dim * dim * 4, hipMemcpyHostToDevice));
+    }
+    HIPCHECK(mem.alloc(&d_v, n * dim * 4));
+    HIPCHECK(mem.alloc(&d_codes, n * sq_count));
+    HIPCHECK(hipMemcpy(d_v, vectors, n * dim * 4, hipMemcpyHostToDevice));
+    const float* d_enc = d_v;
+    if (K > 0) {   // find_k_neighbors(k = 1) on the coarse centroids, chunk by chunk: [chunk][K] distances | chunk norms | K norms
+        const uint64_t chunk = std::min<uint64_t>(kCoarseChunk, n);
+        HIPCHECK(mem.alloc(&d_coarse, (size_t)K * dim * 4));
+        HIPCHECK(hipMemcpy(d_coarse, coarse, (size_t)K * dim * 4, hipMemcpyHostToDevice));
+        HIPCHECK(mem.alloc(&d_dist, (chunk * ((uint64_t)K + 1) + K) * 4));
+        HIPCHECK(mem.alloc(&d_assign, n * 4));
+        float* d_qnorm = d_dist + chunk * (uint64_t)K;
+        float* d_cnorm = d_qnorm + chunk;
+        qadc::launch_row_sqnorm(d_coarse, K, dim, sum_mode, d_cnorm, nullptr);
+        for (uint64_t o = 0; o < n; o += kCoarseChunk)
+            qadc::launch_coarse_assign(d_v + o * dim, d_coarse, (int)std::min<uint64_t>(kCoarseChunk, n - o), K, dim, 1, d_qnorm, d_cnorm, sum_mode,
+                                       d_dist, d_assign + o, nullptr);
+        HIPCHECK(hipGetLastError());
+    }
+    if (K > 0 || rotation) {
+        HIPCHECK(mem.alloc(&d_x, n * dim * 4));
+        qadc::launch_residual_rotate(d_v, n, dim, d_coarse, d_assign, d_rot, d_x, nullptr);
+        d_enc = d_x;
+    }
+    HIPCHECK(qadc::adc::launch_adc_encode(d_enc, n, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_codes, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(codes, d_codes, n * sq_count, hipMemcpyDeviceToHost));
+    if (assign_out && K > 0) HIPCHECK(hipMemcpy(assign_out, d_assign, n * 4, hipMemcpyDeviceToHost));
     return QADC_OK;
 }
 

@@ -6,9 +6,12 @@
 //                      emits (candidate, key, scan index) when candidate < bound[query];
 //   adc_select_kernel  one workgroup per query: bound = the R-th smallest value the query emitted so far (radix select on
 //                      the order-preserving integer image of the floats), the bound of the next level's runs;
-//   adc_pack_kernel    the per-query regions packed densely for one device-to-host copy.
+//   adc_pack_kernel    the per-query regions packed densely for one device-to-host copy;
+//   adc_tables_kernel  the float tables of every (query, probe) from query vectors (residual, OPQ rotation, both table forms);
+//   adc_encode_kernel  vectors -> one code byte per sub-quantizer.
 // The bound rule and why it is exact: DESIGN.md section 11.  Built with -ffp-contract=off and without fast-math (Makefile):
 // every sum rounds like the reference's.
+#include <algorithm>
 #include <cfloat>
 
 #include "qadc_adc_kernels.h"
@@ -191,6 +194,162 @@ hipError_t launch_scan_t(const Item* items, uint32_t first, uint32_t n_items, Db
     return hipGetLastError();
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Feeders: what nns_engine(_batch)::process_query does before query_scan (query_common.hpp:194-213, 283-297) and
+// base_pq::encode_multiple_vectors (quantizers.hpp:222-245) for 256 centroids per sub-quantizer.
+// Arithmetic entry for entry that of build_tables_kernel (csrc/qadc_kernels.hip) and of the host twin pq_bytes::tables /
+// tables_blas (host/scanner_simple.hpp): residual q - coarse[assign]; OPQ rotation rotated[r] = sum_c x[c] rotation[r][c],
+// one sequential sum in ascending c; direct form = direct_sqdist, expansion form = (||v||^2 + ||c||^2) + (-2 v.c) with the
+// norms of expansion_sqnorm and one sequential dot (qadc_float_sum.h).  ||c||^2 comes from the caller, once per codebook set.
+// ---------------------------------------------------------------------------------------------
+template <int DS>
+struct CentroidRow {   // DS = 8, 16, 32: the row in registers;  0: any sq_dim, read where it is used
+    float v[DS];
+    __device__ __forceinline__ void load(const float* __restrict__ row, int) {
+#pragma unroll
+        for (int i = 0; i < DS / 4; ++i) {
+            const float4 t = reinterpret_cast<const float4*>(row)[i];
+            v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
+        }
+    }
+    __device__ __forceinline__ float operator[](int d) const { return v[d]; }
+};
+template <>
+struct CentroidRow<0> {
+    const float* __restrict__ p;
+    __device__ __forceinline__ void load(const float* __restrict__ row, int) { p = row; }
+    __device__ __forceinline__ float operator[](int d) const { return p[d]; }
+};
+
+// Grid (query, probe group, sub-quantizer slice).  A workgroup holds the residuals of `probes` probes of one query in LDS
+// (only the components of its sub-quantizers m0 .. m0 + mper); lane c owns centroid c of the current sub-quantizer, keeps its
+// row and walks the probes: every store instruction of the workgroup writes one whole 1 KiB table row.
+// Dynamic LDS: res [probes][mper * ds] | vnorm [probes][mper] | (OPQ) whole un-rotated residuals [probes][dim].
+template <int DS>
+__global__ __launch_bounds__(kWG) void adc_tables_kernel(const float* __restrict__ queries, const float* __restrict__ coarse,
+                                                         const int32_t* __restrict__ assign, const float* __restrict__ codebooks,
+                                                         const float* __restrict__ cbnorm, const float* __restrict__ rotation,
+                                                         int ma, int nsq, int dim, int probes, int mper, int expansion,
+                                                         int sum_mode, float* __restrict__ tables) {
+    extern __shared__ __attribute__((aligned(16))) float dyn[];
+    const int ds = DS ? DS : dim / nsq;
+    const int qi = blockIdx.x, a0 = blockIdx.y * probes, m0 = blockIdx.z * mper, tid = threadIdx.x;
+    const int na = min(probes, ma - a0);
+    const int lo = m0 * ds, width = mper * ds;
+    float* res = dyn;
+    float* vnorm = res + probes * width;
+    float* whole = vnorm + probes * mper;
+    const float* __restrict__ q = queries + (size_t)qi * dim;
+    if (!rotation) {
+        for (int i = tid; i < na * width; i += kWG) {
+            const int a = i / width, j = i - a * width;
+            const float x = q[lo + j];
+            res[i] = coarse ? x - coarse[(size_t)assign[(size_t)qi * ma + a0 + a] * dim + lo + j] : x;
+        }
+    } else {
+        for (int i = tid; i < na * dim; i += kWG) {
+            const int a = i / dim, d = i - a * dim;
+            const float x = q[d];
+            whole[i] = coarse ? x - coarse[(size_t)assign[(size_t)qi * ma + a0 + a] * dim + d] : x;
+        }
+        __syncthreads();
+        // opq::rotate_multiple_vectors (quantizers.hpp:289-301): the rows this workgroup's sub-quantizers read
+        for (int i = tid; i < na * width; i += kWG) {
+            const int a = i / width, j = i - a * width;
+            const float* __restrict__ row = rotation + (size_t)(lo + j) * dim;
+            const float* x = whole + a * dim;
+            float acc = 0.0f;
+            for (int c = 0; c < dim; ++c) acc += x[c] * row[c];
+            res[i] = acc;
+        }
+    }
+    __syncthreads();
+    if (expansion) {
+        for (int i = tid; i < na * mper; i += kWG) vnorm[i] = expansion_sqnorm(res + (size_t)i * ds, ds, sum_mode);
+        __syncthreads();
+    }
+    for (int mm = 0; mm < mper; ++mm) {
+        const int m = m0 + mm;
+        CentroidRow<DS> ce;
+        ce.load(codebooks + ((size_t)m * 256 + tid) * ds, ds);
+        const float cn = expansion ? cbnorm[m * 256 + tid] : 0.0f;
+        float* __restrict__ out = tables + (((size_t)qi * ma + a0) * nsq + m) * 256 + tid;
+        for (int a = 0; a < na; ++a) {
+            const float* r = res + a * width + mm * ds;
+            float s;
+            if (expansion) s = expansion_dist(r, ce, ds, vnorm[a * mper + mm], cn);
+            else s = direct_sqdist(r, ce, ds, sum_mode);
+            out[(size_t)a * nsq * 256] = s;
+        }
+    }
+}
+
+// encode_multiple_vectors for 8-bit sub-quantizers: per (vector, sub-quantizer) the 256 expansion distances pushed in centroid
+// order into a kv_binheap of capacity 1 (find_k_neighbors with k = 1, neighbors.cpp:18-76), whose replace test AS COMPILED is
+// !(s >= kept): the pick is 255 when distance 255 is NaN, else the first smallest distance among the centroids after the last
+// NaN.  Lane c holds distance c, so every wave settles its 64 centroids by that rule — (value, index) keys, lanes up to its last
+// NaN left out — and one thread per vector then walks the four waves in order: a wave with a NaN restarts the history, a wave
+// whose lane 63 is NaN leaves a NaN kept, which the next wave's first centroid replaces whatever its distance.
+// Dynamic LDS: wave keys [vper][4] u64 | wave flags [vper][4] | x [vper][dim] | ||x_m||^2 [vper][nsq] | codes [vper][nsq].
+template <int DS>
+__global__ __launch_bounds__(kWG) void adc_encode_kernel(const float* __restrict__ x, uint64_t n, int nsq, int dim,
+                                                         const float* __restrict__ codebooks, const float* __restrict__ cbnorm,
+                                                         int vper, int sum_mode, uint8_t* __restrict__ codes) {
+    extern __shared__ __attribute__((aligned(16))) float dyn[];
+    const int ds = DS ? DS : dim / nsq;
+    unsigned long long* wkey = reinterpret_cast<unsigned long long*>(dyn);
+    uint32_t* wflag = reinterpret_cast<uint32_t*>(wkey + vper * 4);
+    float* xs = reinterpret_cast<float*>(wflag + vper * 4);
+    float* vnorm = xs + (size_t)vper * dim;
+    uint8_t* picked = reinterpret_cast<uint8_t*>(vnorm + vper * nsq);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint64_t v0 = (uint64_t)blockIdx.x * vper; v0 < n; v0 += (uint64_t)gridDim.x * vper) {
+        const int nv = (int)min((uint64_t)vper, n - v0);
+        __syncthreads();                                          // (the last chunk's picks have been written out)
+        for (int i = tid; i < nv * dim; i += kWG) xs[i] = x[v0 * dim + i];
+        __syncthreads();
+        for (int i = tid; i < nv * nsq; i += kWG) vnorm[i] = expansion_sqnorm(xs + (size_t)(i / nsq) * dim + (i % nsq) * ds, ds, sum_mode);
+        __syncthreads();
+        for (int m = 0; m < nsq; ++m) {
+            CentroidRow<DS> ce;
+            ce.load(codebooks + ((size_t)m * 256 + tid) * ds, ds);
+            const float cn = cbnorm[m * 256 + tid];
+            for (int v = 0; v < nv; ++v) {
+                const float s = expansion_dist(xs + (size_t)v * dim + m * ds, ce, ds, vnorm[v * nsq + m], cn) + 0.0f;   // (-0 -> +0)
+                const unsigned long long nans = __ballot(s != s);
+                const int last_nan = nans ? 63 - __builtin_clzll(nans) : -1;
+                unsigned long long key = lane > last_nan ? ((unsigned long long)order_key(s) << 32) | (uint32_t)tid : ~0ull;
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) {
+                    const unsigned long long o = __shfl_xor(key, d);
+                    key = o < key ? o : key;
+                }
+                if (lane == 0) {
+                    wkey[v * 4 + wave] = key;
+                    wflag[v * 4 + wave] = nans ? (last_nan == 63 ? 2u : 1u) : 0u;
+                }
+            }
+            __syncthreads();
+            if (tid < nv) {
+                unsigned long long best = ~0ull;
+                bool kept_nan = false;
+                uint32_t nan_at = 0;
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long k = wkey[tid * 4 + w];
+                    const uint32_t f = wflag[tid * 4 + w];
+                    if (f == 2u) { kept_nan = true; nan_at = 64u * w + 63u; }
+                    else if (f == 1u || kept_nan) { best = k; kept_nan = false; }
+                    else best = k < best ? k : best;
+                }
+                picked[tid * nsq + m] = (uint8_t)(kept_nan ? nan_at : (uint32_t)best);
+            }
+            __syncthreads();
+        }
+        for (int i = tid; i < nv * nsq; i += kWG) codes[v0 * nsq + i] = picked[i];
+    }
+}
+
 }  // namespace
 
 hipError_t launch_adc_scan(int nsq, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, Db db, const int32_t* assign,
@@ -215,6 +374,51 @@ hipError_t launch_adc_select(int nq, int R, Emit emit, float* bound, hipStream_t
 
 hipError_t launch_adc_pack(int nq, Emit emit, uint32_t* out, hipStream_t s) {
     hipLaunchKernelGGL(adc_pack_kernel, dim3(nq), dim3(kWG), 0, s, emit, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_adc_tables(const float* d_queries, const float* d_coarse, const int32_t* d_assign, const float* d_codebooks,
+                             const float* d_cbnorm, const float* d_rotation, int nq, int ma, int nsq, int dim, int expansion,
+                             int sum_mode, float* d_tables, hipStream_t s) {
+    if (nq <= 0 || ma <= 0) return hipSuccess;
+    if (dim <= 0 || dim > kAdcMaxDim || dim % nsq != 0) return hipErrorInvalidValue;
+    const int ds = dim / nsq;
+    // probes per workgroup: up to 16; a small batch is cut finer (sub-quantizers over grid.z, fewer probes) to fill the chip
+    long groups = (ma + 15) / 16;
+    int msplit = 1;
+    if ((long)nq * groups < 512) msplit = nsq;
+    if ((long)nq * groups * msplit < 512) groups = std::min<long>(ma, std::max<long>(groups, (512 + (long)nq * msplit - 1) / ((long)nq * msplit)));
+    int probes = (int)((ma + groups - 1) / groups);
+    const int mper = nsq / msplit;
+    auto lds_floats = [&](int p) { return (size_t)p * mper * ds + (size_t)p * mper + (d_rotation ? (size_t)p * dim : 0); };
+    while (probes > 1 && lds_floats(probes) * sizeof(float) > 48 * 1024) probes = (probes + 1) / 2;
+    const dim3 grid((unsigned)nq, (unsigned)((ma + probes - 1) / probes), (unsigned)msplit);
+    const size_t lds = lds_floats(probes) * sizeof(float);
+#define QADC_AT(DS) hipLaunchKernelGGL((adc_tables_kernel<DS>), grid, dim3(kWG), lds, s, d_queries, d_coarse, d_assign, d_codebooks, \
+                                       d_cbnorm, d_rotation, ma, nsq, dim, probes, mper, expansion, sum_mode, d_tables)
+    if (ds == 8) QADC_AT(8);
+    else if (ds == 16) QADC_AT(16);
+    else if (ds == 32) QADC_AT(32);
+    else QADC_AT(0);
+#undef QADC_AT
+    return hipGetLastError();
+}
+
+hipError_t launch_adc_encode(const float* d_x, uint64_t n, int nsq, int dim, const float* d_codebooks, const float* d_cbnorm,
+                             int sum_mode, uint8_t* d_codes, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (dim <= 0 || dim > kAdcMaxDim || dim % nsq != 0) return hipErrorInvalidValue;
+    const int ds = dim / nsq;
+    const int vper = std::max(1, std::min(32, 8192 / dim));
+    const size_t lds = (size_t)vper * (4 * 8 + 4 * 4 + (size_t)dim * 4 + (size_t)nsq * 4 + nsq);
+    const unsigned grid = (unsigned)std::min<uint64_t>((n + vper - 1) / vper, 8192);
+#define QADC_AE(DS) hipLaunchKernelGGL((adc_encode_kernel<DS>), dim3(grid), dim3(kWG), lds, s, d_x, n, nsq, dim, d_codebooks, d_cbnorm, \
+                                       vper, sum_mode, d_codes)
+    if (ds == 8) QADC_AE(8);
+    else if (ds == 16) QADC_AE(16);
+    else if (ds == 32) QADC_AE(32);
+    else QADC_AE(0);
+#undef QADC_AE
     return hipGetLastError();
 }
 

@@ -46,5 +46,21 @@ hipError_t launch_adc_select(int nq, int R, Emit emit, float* bound, hipStream_t
 // (value bits, key, scan index).
 hipError_t launch_adc_pack(int nq, Emit emit, uint32_t* out, hipStream_t s);
 
+
+constexpr int kAdcMaxDim = 4096;      // largest vector dimension the feeders take (their residuals live in LDS)
+
+// The float tables of nq queries from their vectors: d_tables [nq][ma][nsq][256], the layout launch_adc_scan reads.
+// d_assign [nq][ma] probed partitions (read only with d_coarse); d_coarse [K][dim] or nullptr (flat: residual = query);
+// d_rotation [dim][dim] or nullptr; d_codebooks [nsq][256][dim/nsq]; d_cbnorm [nsq*256] = launch_row_sqnorm of the codebook rows
+// under the same sum_mode (read by the expansion form only).  expansion 0 = the direct form (compute_dists_single_simd_cg),
+// 1 = the BLAS-expansion form (compute_dists_multiple_blas_cg).  dim <= kAdcMaxDim, dim % nsq == 0.
+hipError_t launch_adc_tables(const float* d_queries, const float* d_coarse, const int32_t* d_assign, const float* d_codebooks,
+                             const float* d_cbnorm, const float* d_rotation, int nq, int ma, int nsq, int dim, int expansion,
+                             int sum_mode, float* d_tables, hipStream_t s);
+// encode_multiple_vectors (quantizers.hpp:222-245) with 256 centroids per sub-quantizer on vectors already made residuals and
+// rotated: d_codes [n][nsq], the capacity-1 heap's pick as compiled on the expansion distances.
+hipError_t launch_adc_encode(const float* d_x, uint64_t n, int nsq, int dim, const float* d_codebooks, const float* d_cbnorm,
+                             int sum_mode, uint8_t* d_codes, hipStream_t s);
+
 }  // namespace adc
 }  // namespace qadc

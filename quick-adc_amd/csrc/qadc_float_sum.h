@@ -76,3 +76,70 @@ __device__ __forceinline__ T adc_sum_code(const T* v, int sum_mode, T zero) {
     if constexpr (M == 32) s = adc_sum8_compiled_next(s, v + 16);
     return s;
 }
+
+// ---- float distance sums shared by the feeders of both engines (csrc/qadc_kernels.hip, csrc/qadc_adc_kernel.hip) ----
+
+// ||x - c||^2 over ds components as the reference's direct table form adds it: fmanorm<ds/8, ds%8> called by
+// compute_dists_single_simd_cg (distances.hpp:60-76, 294-311) AS COMPILED with the reference's flags (pinned to that
+// build through the oracle's orc_tables_direct; host twin: host/float_sum.hpp sqdist):
+//   per AVX lane j: acc[j] = fma(d, d, acc[j]) over the ds/8 blocks, d = x - c;  reduceadd's tree acc[j] + acc[j+4],
+//   then (r0 + r2) + (r1 + r3);  the scalar remainder is paired p_k = fma(d_2k, d_2k, r(d_2k+1^2)), d = c - x:
+//   REM 4 -> (p0 + p1) + vec,  REM 6 -> (vec + p2) + (p0 + p1).
+// sum_mode 0, or a remainder the reference has no instance of (sq_dim 3 of BASELINE configs[4]; its dispatch is
+// distances.cpp:50-84): one sequential sum in ascending d.  X / C: anything indexable by int (pointer or register array).
+template <typename X, typename C>
+__device__ __forceinline__ float direct_sqdist(const X& x, const C& c, int ds, int sum_mode) {
+    const int blocks = ds >> 3, rem = ds & 7;
+    if (sum_mode == 0 || !(rem == 0 || rem == 4 || rem == 6)) {
+        float s = 0.0f;
+        for (int d = 0; d < ds; ++d) {
+            const float t = x[d] - c[d];
+            s += t * t;
+        }
+        return s;
+    }
+    float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int b = 0; b < blocks; ++b) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float d = x[b * 8 + j] - c[b * 8 + j];
+            acc[j] = __fmaf_rn(d, d, acc[j]);
+        }
+    }
+    const float r0 = acc[0] + acc[4], r1 = acc[1] + acc[5], r2 = acc[2] + acc[6], r3 = acc[3] + acc[7];
+    const float vec = (r0 + r2) + (r1 + r3);
+    if (rem == 0) return vec;
+    float p[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (2 * k < rem) {
+            const float d0 = c[blocks * 8 + 2 * k] - x[blocks * 8 + 2 * k];
+            const float d1 = c[blocks * 8 + 2 * k + 1] - x[blocks * 8 + 2 * k + 1];
+            p[k] = __fmaf_rn(d0, d0, d1 * d1);
+        }
+    }
+    if (rem == 4) return (p[0] + p[1]) + vec;
+    return (vec + p[2]) + (p[0] + p[1]);
+}
+
+// The BLAS-expansion distance compute_cross_dists_blas<DSQ> (distances.hpp:151-215) leaves in dists[v][c]:
+//   ||v||^2 + ||c||^2 (153-176), then cblas_sgemm(alpha = -2, beta = 1) adds -2 v.c (178-182).
+// expansion_sqnorm = fmanorm<DSQ/8, DSQ%8>(vec) / norm_4(vec) AS COMPILED with the reference's flags (sum_mode 1): the
+// grouping of direct_sqdist with c = 0 — pinned to the reference's own text compiled up to the sgemm call (oracle/_ref
+// qadc_reff_cross_norms, the 14 dimensions of its dispatch, 16 centroids) through the oracle's orc_sqnorm; host twin:
+// host/float_sum.hpp sqnorm.  sum_mode 0, or a remainder the reference has no instance of: one sequential sum.
+// The product is OpenBLAS's in the reference (not in this image: restated, unpinned): one sequential dot in ascending d,
+// then base + (-2 dot) — -2 dot is exact, so this is the single rounding of a gemm kernel's C += alpha * acc.
+struct zero_vec {
+    __device__ __forceinline__ float operator[](int) const { return 0.0f; }
+};
+template <typename X>
+__device__ __forceinline__ float expansion_sqnorm(const X& x, int ds, int sum_mode) {
+    return direct_sqdist(x, zero_vec{}, ds, sum_mode);
+}
+template <typename X, typename C>
+__device__ __forceinline__ float expansion_dist(const X& x, const C& c, int ds, float vn, float cn) {
+    float dot = 0.0f;
+    for (int d = 0; d < ds; ++d) dot += x[d] * c[d];
+    return (vn + cn) + (-2.0f * dot);
+}

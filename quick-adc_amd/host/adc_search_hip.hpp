@@ -1,0 +1,106 @@
+// adc_search_engine_hip — C++14 host mirror of nns_engine_batch<scanner_simple> on the GPU, queries in.
+//
+// nns_engine_batch (query_common.hpp:149-243) prepares the tables of `batch` queries on the CPU when the first query of a batch is
+// asked for (assign_compute_residuals, rotate_multiple_vectors, the distance tables: 194-213) and scanner_simple then scans every
+// query with them.  This engine offers the same contract — prepare_database(), process_query(query_i, queries, count, bh, metrics),
+// to be driven by the reference's process_queries<> loop (query_driver.hpp process_queries here) — and hands the query VECTORS to
+// qadc_adc_search_candidates (include/qadc.h): coarse assignment, residuals, OPQ rotation and tables are computed in GPU memory and
+// scanned there, so no table crosses the bus.  The per-query calls replay the batch's cached candidate stream into the caller's heap
+// after its R sentinel pushes (db_query.cpp:31-33), which leaves it in exactly the state the reference's scan would.
+//   Db:   int partition_count(); void get_partition(int, const std::uint8_t*&, unsigned*&, unsigned&);
+//         int coarse_count(); const float* coarse_centroids();            (0 / nullptr: a flat database)
+//         pq->sq_count, pq->sq_bits, pq->dim, pq->centroids, pq->rotation  (host/scanner_simple.hpp pq_bytes)
+//   Heap: int capacity(); void push(unsigned, float)                       (kv_binheap<unsigned, float>, binheap.hpp)
+// table_form: 1 = the BLAS-expansion tables nns_engine_batch builds (default), 0 = direct, 2 = nns_engine's rule.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <iostream>
+#include <limits>
+#include <vector>
+
+#include "../../include/qadc.h"
+#include "qadc_heap.hpp"
+#include "query_driver.hpp"
+
+namespace qadc {
+
+template <typename Db>
+struct adc_search_engine_hip {
+    Db& db;
+    int ma, batch, r, device, sum_mode, table_form;
+    qadc_adc_index* index;
+    std::vector<std::uint32_t> cand_keys;
+    std::vector<float> cand_vals;
+    std::vector<std::uint64_t> offsets;
+    std::vector<std::int32_t> assign;   // [batch][ma] of the last batch, nearest first
+
+    adc_search_engine_hip(Db& d, int ma_, int batch_, int r_, int device_ = 0, int sum_mode_ = 1, int table_form_ = 1)
+        : db(d), ma(ma_), batch(batch_), r(r_), device(device_), sum_mode(sum_mode_), table_form(table_form_), index(nullptr),
+          cand_keys(1 << 16), cand_vals(1 << 16), offsets((std::size_t)batch_ + 1), assign((std::size_t)batch_ * ma_) {}
+    adc_search_engine_hip(const adc_search_engine_hip&) = delete;
+    adc_search_engine_hip& operator=(const adc_search_engine_hip&) = delete;
+    ~adc_search_engine_hip() { qadc_adc_index_destroy(index); }
+
+    static void die(const char* what) {
+        std::cerr << what << ": " << qadc_last_error() << std::endl;
+        std::exit(1);
+    }
+
+    // scanner_simple::prepare_database (db_query.cpp:21-24) plus the quantizers the feeders need
+    void prepare_database() {
+        const int m = db.pq->sq_count, bits = db.pq->sq_bits;
+        if (qadc_adc_index_create(&index, m, bits, device) != QADC_OK) die("Cannot create the GPU index");
+        const int part_count = db.partition_count();
+        std::vector<const std::uint8_t*> codes(part_count);
+        std::vector<const std::uint32_t*> labels(part_count);
+        std::vector<std::uint32_t> sizes(part_count);
+        bool labeled = false;
+        for (int part_i = 0; part_i < part_count; ++part_i) {
+            unsigned* lab;
+            unsigned size;
+            db.get_partition(part_i, codes[part_i], lab, size);
+            labels[part_i] = lab;
+            sizes[part_i] = size;
+            labeled = labeled || lab != nullptr;
+        }
+        if (qadc_adc_index_add_partitions(index, part_count, codes.data(), labeled ? labels.data() : nullptr, sizes.data()) != QADC_OK)
+            die("Cannot prepare database");
+        if (qadc_adc_index_set_pq(index, db.pq->dim, db.pq->centroids.data()) != QADC_OK) die("Cannot set the codebooks");
+        if (!db.pq->rotation.empty() && qadc_adc_index_set_rotation(index, db.pq->rotation.data()) != QADC_OK) die("Cannot set the rotation");
+        if (db.coarse_count() > 0 && qadc_adc_index_set_coarse(index, db.coarse_count(), db.coarse_centroids()) != QADC_OK)
+            die("Cannot set the coarse centroids");
+    }
+
+    // nns_engine_batch::process_query (query_common.hpp:194-243): the whole batch is searched when its first query is asked for
+    template <typename Heap>
+    void process_query(int query_i, const float* queries, int count, Heap& bh, query_metrics& metrics) {
+        const int b = query_i % batch;
+        metrics = query_metrics();
+        const std::uint64_t t0 = ustime();
+        if (b == 0) {
+            const int nb = std::min(batch, count - query_i);
+            const float* q = queries + (std::size_t)query_i * db.pq->dim;
+            int rc = qadc_adc_search_candidates(index, nb, q, ma, r, table_form, sum_mode, cand_keys.size(), cand_keys.data(),
+                                                cand_vals.data(), offsets.data(), assign.data());
+            if (rc == QADC_E_CAPACITY) {  // offsets[nb] holds the required size: grow and ask again
+                cand_keys.resize(offsets[nb]);
+                cand_vals.resize(offsets[nb]);
+                rc = qadc_adc_search_candidates(index, nb, q, ma, r, table_form, sum_mode, cand_keys.size(), cand_keys.data(),
+                                                cand_vals.data(), offsets.data(), assign.data());
+            }
+            if (rc != QADC_OK) die("search");
+        }
+        for (int t = 0; t < bh.capacity(); ++t) bh.push(0, std::numeric_limits<float>::max() - t);   // "Fill binary heap"
+        for (std::uint64_t i = offsets[b]; i < offsets[b + 1]; ++i) bh.push(cand_keys[i], cand_vals[i]);
+        metrics.scan_us = ustime() - t0;   // (index, rotation and tables are part of the one GPU call)
+    }
+};
+
+template <typename Db, typename Heap>
+inline void call_engine(adc_search_engine_hip<Db>& e, int q, const float* queries, int count, int, Heap& bh, query_metrics& m) {
+    e.process_query(q, queries, count, bh, m);
+}
+
+}  // namespace qadc

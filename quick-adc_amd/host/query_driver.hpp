@@ -8,6 +8,7 @@
 //   flat_database  flat_db  (databases.hpp:77-167): one partition, key = position
 //   ivf_database   index_db (databases.hpp:176-331): coarse centroids, per-partition codes + labels,
 //                  assign = the ma nearest centroids in ascending distance, residual = x - centroid
+//                  (ivf_database_t<Pq> over any quantizer: pq4 here, pq_bytes of host/scanner_simple.hpp for 8-bit codes)
 //   nns_engine     per-query sequence assign -> (rotate: none for plain PQ) -> tables -> scanner.query_scan
 //                  with the four phase timers (query_common.hpp:245-309)
 //   process_queries  fresh heap per query, recall = true nearest neighbour among the R returned keys,
@@ -159,6 +160,8 @@ struct flat_database_t {                 // flat_db over any quantizer: pq4 here
         count += n;
     }
     int partition_count() const { return 1; }
+    int coarse_count() const { return 0; }                       // no coarse quantizer (adc_search_engine_hip asks)
+    const float* coarse_centroids() const { return nullptr; }
     void get_partition(int, const std::uint8_t*& c, unsigned*& labels, unsigned& size) {
         c = codes.data();
         labels = nullptr;
@@ -174,14 +177,15 @@ struct flat_database_t {                 // flat_db over any quantizer: pq4 here
 };
 typedef flat_database_t<pq4> flat_database;
 
-struct ivf_database {
-    std::unique_ptr<pq4> pq;
+template <typename Pq>
+struct ivf_database_t {
+    std::unique_ptr<Pq> pq;
     int part_count;
     std::vector<float> coarse;  // [K][dim]
     std::vector<std::vector<std::uint8_t>> partitions;
     std::vector<std::vector<unsigned>> labels;
 
-    ivf_database(std::unique_ptr<pq4> p, int k, std::vector<float> c)
+    ivf_database_t(std::unique_ptr<Pq> p, int k, std::vector<float> c)
         : pq(std::move(p)), part_count(k), coarse(std::move(c)), partitions(k), labels(k) {}
 
     // the coarse distance as find_k_neighbors gets it from compute_cross_dists_blas (distances.hpp:151-183): (||x||^2 + ||c||^2) with the
@@ -214,6 +218,8 @@ struct ivf_database {
         }
     }
     int partition_count() const { return part_count; }
+    int coarse_count() const { return part_count; }
+    const float* coarse_centroids() const { return coarse.data(); }
     void get_partition(int i, const std::uint8_t*& c, unsigned*& l, unsigned& size) {
         c = partitions[i].data();
         l = labels[i].data();
@@ -230,6 +236,7 @@ struct ivf_database {
                 residuals[(size_t)a * pq->dim + d] = x[d] - coarse[(size_t)assign[a] * pq->dim + d];
     }
 };
+typedef ivf_database_t<pq4> ivf_database;
 
 struct query_metrics {  // query_common.hpp:21-56
     std::uint64_t index_us = 0, rotate_us = 0, table_us = 0, scan_us = 0;

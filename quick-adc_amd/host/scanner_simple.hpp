@@ -3,7 +3,8 @@
 // ("Flat DB, PQ 8x8 scalar ADC on CPU, db_query reference path"), kept next to the accelerated scanner so that the
 // stand-alone driver (tests/cpp/db_query_simple.cpp) offers both of the reference's query front ends.
 //
-//   pq_bytes            base_pq with whole-byte codes (sq_bits 8 or 16; quantizers.hpp:96-246): encode, the two table forms
+//   pq_bytes            base_pq / opq with whole-byte codes (sq_bits 8 or 16; quantizers.hpp:96-324): encode, the OPQ rotation,
+//                       the two table forms (device twins: adc_tables_kernel, adc_encode_kernel in csrc/qadc_adc_kernel.hip)
 //   scan_standard<T,N>  query_common.hpp:92-118: candidate = sum of NSQ table entries in sub-quantizer order
 //   scan_4f<N>          query_common.hpp:59-90: the same on row-major 4-bit codes (low nibble = even sub-quantizer)
 //   get_scan_func       query_common.hpp:120-146: the (sq_count, sq_bits) dispatch and its error text
@@ -83,13 +84,29 @@ scan_func get_scan_func(const Pq& pq) {
 struct pq_bytes {
     int sq_count, sq_bits, dim;
     std::vector<float> centroids;                                // [sq_count][ncent][sq_dim]
+    std::vector<float> rotation;                                 // OPQ: [dim][dim], empty for plain PQ (quantizers.hpp:248-324)
     pq_bytes(int m, int bits, int d) : sq_count(m), sq_bits(bits), dim(d), centroids((std::size_t)m * (1u << bits) * (d / m)) {}
     int ncent() const { return 1 << sq_bits; }
     int sq_dim() const { return dim / sq_count; }
     int code_size() const { return sq_count * sq_bits / 8; }
     int table_dim() const { return sq_count * ncent(); }
     const float* centroid(int m, int c) const { return centroids.data() + ((std::size_t)m * ncent() + c) * sq_dim(); }
-    void rotate_multiple_vectors(float*, int) const {}           // plain PQ (quantizers.hpp:189-195)
+    // opq::rotate_multiple_vectors (quantizers.hpp:289-301): rotated[r] = sum_c x[c] * rotation[r][c], one sequential float sum
+    // in ascending c (pq4::rotate_multiple_vectors in host/query_driver.hpp; the device feeders add in the same order);
+    // plain PQ: no-op (189-195)
+    void rotate_multiple_vectors(float* vecs, int count) const {
+        if (rotation.empty()) return;
+        std::vector<float> out((std::size_t)dim);
+        for (int v = 0; v < count; ++v) {
+            float* x = vecs + (std::size_t)v * dim;
+            for (int r = 0; r < dim; ++r) {
+                float acc = 0;
+                for (int c = 0; c < dim; ++c) acc += x[c] * rotation[(std::size_t)r * dim + c];
+                out[r] = acc;
+            }
+            for (int r = 0; r < dim; ++r) x[r] = out[r];
+        }
+    }
     void tables(const float* x, float* out) const {              // ||x_m - c||^2 as fmanorm adds it (float_sum.hpp)
         const int ds = sq_dim(), nc = ncent();
         for (int m = 0; m < sq_count; ++m)
@@ -108,17 +125,24 @@ struct pq_bytes {
                     out[((std::size_t)v * sq_count + m) * nc + c] = expansion_dist(x, centroid(m, c), ds, vn, cn[m * nc + c]);
             }
     }
-    // encode_multiple_vectors (quantizers.hpp:222-245): find_k_neighbors with k = 1 on the expansion distances = their first
-    // strict minimum in centroid order
+    // encode_multiple_vectors (quantizers.hpp:222-245): the rotation (opq), then find_k_neighbors with k = 1 on the expansion
+    // distances: a capacity-1 kv_binheap fed in centroid order, whose replace test as compiled is !(s >= kept) — the first
+    // strict minimum after the last NaN (the last centroid when its distance is NaN); without NaN the first strict minimum
     void encode(const float* vecs, std::size_t n, std::uint8_t* codes) const {
         const int nc = ncent(), cs = code_size();
-        std::vector<float> t((std::size_t)table_dim());
+        std::vector<float> t((std::size_t)table_dim()), rot;
         for (std::size_t i = 0; i < n; ++i) {
-            tables_blas(vecs + i * dim, 1, t.data());
+            const float* x = vecs + i * dim;
+            if (!rotation.empty()) {
+                rot.assign(x, x + dim);
+                rotate_multiple_vectors(rot.data(), 1);
+                x = rot.data();
+            }
+            tables_blas(x, 1, t.data());
             for (int m = 0; m < sq_count; ++m) {
                 int best = 0;
                 for (int c = 1; c < nc; ++c)
-                    if (t[m * nc + c] < t[m * nc + best]) best = c;
+                    if (!(t[m * nc + c] >= t[m * nc + best])) best = c;
                 if (sq_bits == 8) codes[i * cs + m] = (std::uint8_t)best;
                 else { codes[i * cs + 2 * m] = (std::uint8_t)best; codes[i * cs + 2 * m + 1] = (std::uint8_t)(best >> 8); }
             }

@@ -38,6 +38,8 @@ SYMBOLS = [
     "qadc_shm_transport_close", "qadc_shm_transport_error", "qadc_slot_assign", "qadc_slot_qtables", "qadc_place_partitions",
     "qadc_adc_index_create", "qadc_adc_index_destroy", "qadc_adc_index_add_partitions", "qadc_adc_index_partition_count",
     "qadc_adc_index_partition_size", "qadc_adc_query_scan", "qadc_adc_query_scan_candidates", "qadc_adc_index_reruns",
+    "qadc_adc_index_set_pq", "qadc_adc_index_set_rotation", "qadc_adc_index_set_coarse", "qadc_adc_index_set_table_budget",
+    "qadc_adc_search", "qadc_adc_search_candidates", "qadc_adc_search_tables", "qadc_adc_encode_host",
 ]
 
 
@@ -164,6 +166,15 @@ def lib():
         L.qadc_adc_index_partition_size.restype = C.c_uint32
         L.qadc_adc_index_reruns.argtypes = [C.c_void_p]
         L.qadc_adc_index_reruns.restype = C.c_uint64
+        L.qadc_adc_index_set_pq.argtypes = [C.c_void_p, C.c_int, f32p]
+        L.qadc_adc_index_set_rotation.argtypes = [C.c_void_p, f32p]
+        L.qadc_adc_index_set_coarse.argtypes = [C.c_void_p, C.c_int, f32p]
+        L.qadc_adc_index_set_table_budget.argtypes = [C.c_void_p, C.c_uint64]
+        L.qadc_adc_search.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_int, u32p, f32p, i32p, i32p]
+        L.qadc_adc_search_candidates.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, u32p, f32p,
+                                                 u64p, i32p]
+        L.qadc_adc_search_tables.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, i32p, f32p]
+        L.qadc_adc_encode_host.argtypes = [C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, f32p, C.c_uint64, C.c_int, i32p, u8p, C.c_int]
         L.qadc_adc_query_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, u32p, f32p, i32p]
         L.qadc_adc_query_scan_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, C.c_uint64,
                                                      u32p, f32p, u64p]
@@ -351,6 +362,27 @@ def pq_encode(codebooks, vectors, device=0, encode_form=1, sum_mode=1):
     codes = np.zeros((v.shape[0], M // 2), np.uint8)
     _check(lib().qadc_pq_encode_host_mode(M, dim, _p(cb, f32p), _p(v, f32p), v.shape[0], _p(codes, u8p), encode_form, sum_mode, device))
     return codes
+
+
+def adc_encode(codebooks, vectors, coarse=None, rotation=None, device=0, sum_mode=1):
+    """Database build for 8-bit sub-quantizers on the GPU (qadc_adc_encode_host): nearest coarse centroid and residual (with
+    coarse [K][dim]), OPQ rotation (with rotation [dim][dim]), one code byte per sub-quantizer.  codebooks [sq_count][256][dsq],
+    vectors [n][dim] -> (assign int32 [n] or None for a flat database, codes uint8 [n][sq_count])."""
+    cb = np.ascontiguousarray(codebooks, np.float32)
+    v = np.ascontiguousarray(vectors, np.float32)
+    assert cb.ndim == 3 and cb.shape[1] == 256 and v.ndim == 2
+    nsq, dim, n = cb.shape[0], v.shape[1], v.shape[0]
+    assert cb.shape[2] * nsq == dim
+    co = None if coarse is None else np.ascontiguousarray(coarse, np.float32)
+    rot = None if rotation is None else np.ascontiguousarray(rotation, np.float32)
+    assert rot is None or rot.shape == (dim, dim)
+    assert co is None or co.shape[1] == dim
+    K = 0 if co is None else co.shape[0]
+    assign = np.zeros(n, np.int32) if K else None
+    codes = np.zeros((n, nsq), np.uint8)
+    _check(lib().qadc_adc_encode_host(nsq, dim, _p(cb, f32p), _p(rot, f32p), K, _p(co, f32p), _p(v, f32p), n, sum_mode, _p(assign, i32p),
+                                      _p(codes, u8p), device))
+    return assign, codes
 
 
 def pq_encode_device(codebooks, d_vectors_ptr, n, dim, d_codes_ptr, device=0):
@@ -799,3 +831,81 @@ class AdcIndex:
         rc = lib().qadc_adc_query_scan_candidates(self._h, nq, ma, _p(assign, i32p), _p(tables, f32p), R, sum_mode,
                                                   capacity, _p(keys, u32p), _p(vals, f32p), _p(offsets, u64p))
         return rc, keys, vals, offsets
+
+    # ---- from query vectors: the feeders run on the GPU (qadc_adc_search*) ----
+    def set_pq(self, codebooks):
+        """codebooks [sq_count][256][dim / sq_count]"""
+        cb = np.ascontiguousarray(codebooks, np.float32)
+        assert cb.ndim == 3 and cb.shape[0] == self.sq_count and cb.shape[1] == 256
+        self.set_pq_raw(self.sq_count * cb.shape[2], cb)
+
+    def set_pq_raw(self, dim, codebooks):
+        """The C call as it is (any dim: a bad one raises QadcError)."""
+        cb = np.ascontiguousarray(codebooks, np.float32)
+        _check(lib().qadc_adc_index_set_pq(self._h, dim, _p(cb, f32p)))
+        self.dim = dim
+
+    def set_rotation(self, rotation):
+        r = None if rotation is None else np.ascontiguousarray(rotation, np.float32)
+        dim = getattr(self, "dim", None)
+        assert r is None or dim is None or r.shape == (dim, dim)
+        _check(lib().qadc_adc_index_set_rotation(self._h, _p(r, f32p)))
+
+    def set_coarse(self, centroids):
+        """centroids [K][dim]; None = a flat index"""
+        if centroids is None:
+            _check(lib().qadc_adc_index_set_coarse(self._h, 0, None))
+            return
+        c = np.ascontiguousarray(centroids, np.float32)
+        assert c.ndim == 2 and c.shape[1] == getattr(self, "dim", c.shape[1])
+        _check(lib().qadc_adc_index_set_coarse(self._h, c.shape[0], _p(c, f32p)))
+
+    def set_table_budget(self, nbytes):
+        """device memory for the tables of one pass (0 = the default, 1 GiB); larger batches run in sub-batches of whole queries"""
+        _check(lib().qadc_adc_index_set_table_budget(self._h, int(nbytes)))
+
+    def _queries(self, queries):
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        assert q.ndim == 2 and q.shape[1] == getattr(self, "dim", q.shape[1])
+        return q
+
+    def search(self, queries, ma, R, table_form=2, sum_mode=1):
+        """queries [nq][dim] -> (keys [nq][R], vals [nq][R], sizes [nq], assign [nq][ma]): query_scan's heap arrays on tables
+        built on the GPU.  table_form 0 = direct, 1 = BLAS expansion, 2 = nns_engine's rule (direct iff ma == 1)."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        keys = np.zeros((nq, R), np.uint32)
+        vals = np.zeros((nq, R), np.float32)
+        sizes = np.zeros(nq, np.int32)
+        assign = np.zeros((nq, ma), np.int32)
+        _check(lib().qadc_adc_search(self._h, nq, _p(q, f32p), ma, R, table_form, sum_mode, _p(keys, u32p), _p(vals, f32p),
+                                     _p(sizes, i32p), _p(assign, i32p)))
+        return keys, vals, sizes, assign
+
+    def search_candidates(self, queries, ma, R, table_form=2, sum_mode=1):
+        """-> (keys, vals, offsets [nq+1], assign [nq][ma]): the ordered candidate stream, as query_scan_candidates returns it"""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        assign = np.zeros((nq, ma), np.int32)
+        offsets = np.zeros(nq + 1, np.uint64)
+        cap = 1 << 16
+        while True:
+            keys = np.zeros(cap, np.uint32)
+            vals = np.zeros(cap, np.float32)
+            rc = lib().qadc_adc_search_candidates(self._h, nq, _p(q, f32p), ma, R, table_form, sum_mode, cap, _p(keys, u32p),
+                                                  _p(vals, f32p), _p(offsets, u64p), _p(assign, i32p))
+            if rc != QADC_E_CAPACITY:
+                _check(rc)
+                return keys[:offsets[-1]], vals[:offsets[-1]], offsets, assign
+            cap = int(offsets[-1])
+
+    def search_tables(self, queries, ma, table_form=2, sum_mode=1):
+        """The feeders alone -> (assign [nq][ma], tables [nq][ma][sq_count*256])"""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        assign = np.zeros((nq, ma), np.int32)
+        tables = np.zeros((nq, ma, self.sq_count * 256), np.float32)
+        _check(lib().qadc_adc_search_tables(self._h, nq, _p(q, f32p), ma, table_form, sum_mode, _p(assign, i32p), _p(tables, f32p)))
+        return assign, tables

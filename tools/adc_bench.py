@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
   batch32   32 queries per call on the same list
@@ -10,6 +10,10 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             1024 x 24 float tables (8 KiB each)
   cpu       the CPU scan_standard<uint8_t, 8> (the oracle's C restatement, and the reference's own build where it was
             compiled into oracle/_ref) on the 10^6-code list, one thread
+  ivf_search   the ivf shape on real geometry: 10^6 clustered 128-d vectors encoded by adc_encode, K = 256, ma = 24, 1024 queries.
+            Arm A = query_scan(assign, tables) with the assign and tables arm B's feeders produce (201 MB uploaded in the
+            call); arm B = search(queries): coarse assignment and tables on the GPU.  The arms alternate in one process.
+  lone_search  one synchronous search() of one query at that shape, beside one CPU thread scanning the same 24 partitions
 Every time is a host clock around whole synchronous calls (median of --iters after warm-up); R = 100, sum_mode 1."""
 import argparse
 import json
@@ -44,9 +48,79 @@ def timed(fn, iters, warmup=2):
     return float(np.median(ts)), float(np.min(ts))
 
 
+def alternated(fa, fb, iters, warmup=2):
+    """medians of two arms timed in turn, A B A B ..., after a warm-up of each"""
+    for _ in range(warmup):
+        fa()
+        fb()
+    ta, tb = [], []
+    for _ in range(iters):
+        for f, ts in ((fa, ta), (fb, tb)):
+            t0 = time.perf_counter()
+            f()
+            ts.append(time.perf_counter() - t0)
+    return float(np.median(ta)), float(np.median(tb))
+
+
+def search_legs(legs, iters, res):
+    """10^6 clustered vectors, encoded and partitioned on the GPU: the feeders of search() against caller-made tables"""
+    rng = np.random.default_rng(1)
+    n, dim, nsq, K, ma, nq = 1_000_000, 128, 8, 256, 24, 1024
+    centers = (rng.normal(size=(2000, dim)) * 3).astype(np.float32)
+    vectors = centers[rng.integers(0, len(centers), n)]
+    vectors += rng.normal(size=(n, dim)).astype(np.float32)
+    queries = (centers[rng.integers(0, len(centers), nq)] + rng.normal(size=(nq, dim))).astype(np.float32)
+    coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, K, replace=False)], 5)
+    sample = vectors[rng.choice(n, 256, replace=False)]
+    near = pyqadc.coarse_assign(sample, coarse, 1)[:, 0]
+    codebooks = np.ascontiguousarray((sample - coarse[near]).reshape(256, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
+    t0 = time.perf_counter()
+    part_of, codes = pyqadc.adc_encode(codebooks, vectors, coarse)
+    res["adc_encode_1e6_s"] = time.perf_counter() - t0
+    print("adc_encode of 10^6 128-d vectors (K = 256, 8x8), host to host: %.2f s" % res["adc_encode_1e6_s"], flush=True)
+    del vectors
+    order = np.argsort(part_of, kind="stable")
+    bounds = np.searchsorted(part_of[order], np.arange(K + 1))
+    parts = [codes[order[bounds[k]:bounds[k + 1]]] for k in range(K)]
+    labels = [order[bounds[k]:bounds[k + 1]].astype(np.uint32) for k in range(K)]
+    idx = pyqadc.AdcIndex(nsq, 8)
+    idx.add_partitions(parts, labels)
+    idx.set_pq(codebooks)
+    idx.set_coarse(coarse)
+    if "ivf_search" in legs:
+        assign, tables = idx.search_tables(queries, ma)
+        got_a = idx.query_scan(assign, tables, R)
+        got_b = idx.search(queries, ma, R)
+        assert all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(got_a, got_b[:3])), "the arms disagree"
+        med_a, med_b = alternated(lambda: idx.query_scan(assign, tables, R), lambda: idx.search(queries, ma, R), max(5, iters))
+        res["ivf_search_arm_a_query_scan_ms"] = med_a * 1e3
+        res["ivf_search_arm_b_search_ms"] = med_b * 1e3
+        res["ivf_search_b_over_a"] = med_b / med_a
+        res["ivf_search_table_bytes"] = int(tables.nbytes)
+        res["ivf_search_codes_probed_per_call"] = int(sum(len(parts[k]) for k in assign.ravel()))
+        print("IVF on encoded vectors, K=256 ma=24, 1024 queries/call: A query_scan(assign, tables) with %.0f MB uploaded %.2f ms;"
+              " B search(queries) %.2f ms = %.1f us/query; B / A = %.3f"
+              % (tables.nbytes / 1e6, med_a * 1e3, med_b * 1e3, med_b * 1e6 / nq, med_b / med_a), flush=True)
+    if "lone_search" in legs:
+        q1 = queries[:1]
+        med, best = timed(lambda: idx.search(q1, ma, R), max(iters, 50), warmup=5)
+        res["lone_search_call_us"] = med * 1e6
+        print("one synchronous search() of one query, K=256 ma=24 on 10^6 codes: %.1f us (best %.1f)" % (med * 1e6, best * 1e6), flush=True)
+        import pyoracle as po
+        a1, t1 = idx.search_tables(q1, ma)
+        pp, ll = [parts[k] for k in a1[0]], [labels[k] for k in a1[0]]
+        scan = po.reff_scan_standard_u8 if po.have_ref_float() else po.scan_standard_u8
+        med_c, _ = timed(lambda: scan(nsq, pp, ll, t1[0], R), 20, warmup=2)
+        res["lone_search_cpu_scan_24_partitions_us"] = med_c * 1e6
+        res["lone_search_codes_probed"] = int(sum(len(p) for p in pp))
+        print("CPU scan_standard<uint8_t,8> over the same 24 partitions (%d codes), 1 thread, tables given (%s): %.1f us"
+              % (res["lone_search_codes_probed"], "reference build" if po.have_ref_float() else "C restatement", med_c * 1e6), flush=True)
+    idx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="flat1e8,batch32,lone1e6,ivf,cpu")
+    ap.add_argument("--legs", default="flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -121,6 +195,8 @@ def main():
         print("IVF K=256 ma=24, 1024 queries/call (with %.0f MB of float tables uploaded): %.2f ms = %.1f us/query"
               % (tb.nbytes / 1e6, med * 1e3, med * 1e6 / nq), flush=True)
         idx.close()
+    if "ivf_search" in legs or "lone_search" in legs:
+        search_legs(legs, a.iters, res)
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -526,6 +526,18 @@ uint32_t qadc_adc_index_partition_size(const qadc_adc_index* idx, int part);
 /* Diagnostics (no reference counterpart): how many query calls on this index were re-run because a candidate region overflowed. */
 uint64_t qadc_adc_index_reruns(const qadc_adc_index* idx);
 
+/* Where a query call is finished after its scan.  QADC_ADC_FINISH_HOST (the default): the kept candidates
+ * come back to the host, which orders them and replays the heaps.  QADC_ADC_FINISH_DEVICE: qadc_adc_query_scan and qadc_adc_search
+ * order and replay on the GPU and fetch only keys[nq][R], values[nq][R] and sizes[nq]; the arrays are the same bit for bit.  The
+ * device replay keeps its heap in LDS and covers R <= 4096; a call with a larger R is finished on the host whatever the mode.
+ * The *_candidates calls return the stream itself and are always finished on the host.  Any other mode -> QADC_E_ARG. */
+#define QADC_ADC_FINISH_HOST 0
+#define QADC_ADC_FINISH_DEVICE 1
+int qadc_adc_index_set_finish(qadc_adc_index* idx, int mode);
+/* Diagnostics: how many queries were finished on the host while the device finish was asked for (QADC_ADC_FINISH_DEVICE in force, or a
+ * *_device call), since the index was created.  The length of a query's candidate stream never causes one; R > 4096 does. */
+uint64_t qadc_adc_index_host_finishes(const qadc_adc_index* idx);
+
 /* scanner_simple::query_scan (db_query.cpp:26-45) for nq queries:
  *   assign  [nq][ma]                   probed partitions, each in [0, partition_count); duplicates legal; 1 <= ma < 16384
  *   tables  [nq][ma][sq_count*256]     float tables, NOT mutated
@@ -536,6 +548,13 @@ uint64_t qadc_adc_index_reruns(const qadc_adc_index* idx);
  * A query may probe at most 2^32 - 1 codes in all.  QADC_E_CAPACITY: see QADC_ADC_MAX_ENTRIES. */
 int qadc_adc_query_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R,
                         int sum_mode, uint32_t* keys, float* values, int32_t* sizes);
+/* The same with tables and outputs in device memory of the index's device: d_tables [nq][ma][sq_count*256] (as a kernel of the
+ * caller left them: nothing is uploaded but assign, which stays host memory), d_keys [nq][R], d_values [nq][R], d_sizes [nq], all
+ * required.  Always the device finish (a batch with R > 4096 is finished on the host and its arrays uploaded into the outputs).
+ * Synchronous for the host: the inputs must be complete before the call; the outputs are complete on return, the index's stream
+ * synchronised, so any stream may read them.  Arguments are checked and refused as by qadc_adc_query_scan. */
+int qadc_adc_query_scan_device(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, int R,
+                               int sum_mode, uint32_t* d_keys, float* d_values, int32_t* d_sizes);
 /* The ordered candidate stream instead: pushing (cand_keys[i], cand_vals[i]) for i in [offsets[q], offsets[q+1]) in
  * order into the reference's kv_binheap<unsigned,float>(R), after its R sentinel pushes, leaves it in exactly the state
  * the reference's scan would (a superset of its successful pushes, in scan order).  What a ScannerType wrapper pushes into
@@ -575,6 +594,11 @@ int qadc_adc_index_set_table_budget(qadc_adc_index* idx, uint64_t bytes);
  * index without a partition; a query whose coarse distances hold a NaN while ma > 256. */
 int qadc_adc_search(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,
                     uint32_t* keys, float* values, int32_t* sizes, int32_t* assign_out);
+/* The same from and to device memory of the index's device: d_queries [nq][dim], d_keys [nq][R], d_values [nq][R], d_sizes [nq],
+ * all required; no assign_out.  Always the device finish, synchronous for the host, as qadc_adc_query_scan_device; arguments are
+ * checked and refused as by qadc_adc_search (the NaN row with ma > 256 included) and the table budget applies unchanged. */
+int qadc_adc_search_device(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int R, int table_form, int sum_mode,
+                           uint32_t* d_keys, float* d_values, int32_t* d_sizes);
 /* The same with the ordered candidate stream for output, as qadc_adc_query_scan_candidates returns it. */
 int qadc_adc_search_candidates(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form,
                                int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals,

@@ -5,7 +5,9 @@
 // max(R, 512) codes of every query's scan order, each following level 16 times as far; the runs of a level are filtered
 // by the R-th smallest value the query emitted in the levels before it (FLT_MAX while fewer than R), which is the R-th
 // smallest of a subset of the codes that precede every code of the level.  The kept candidates come back to the host,
-// are put in scan order and pushed into kv_heap<unsigned, float>(R) after the R sentinels.  This engine shares nothing
+// are put in scan order and pushed into kv_heap<unsigned, float>(R) after the R sentinels — or, with the device finish
+// (qadc_adc_index_set_finish, the *_device entry points), are ordered and replayed by two more kernels, so
+// that only the heaps' arrays leave device memory, or nothing does.  This engine shares nothing
 // with the 4-bit index but the device's stream set (qadc_device_prepare), the coarse-assignment kernels and the float sums
 // of the feeders; it has no qadc_set_option names.
 //
@@ -73,6 +75,15 @@ struct qadc_adc_index {
     PinBuf<uint8_t> h_in;
     PinBuf<uint32_t> h_count, h_packed;
     uint64_t reruns = 0;                            // batches re-run because a candidate region overflowed
+    // device finish
+    int finish = QADC_ADC_FINISH_HOST;
+    uint64_t host_finishes = 0;                     // queries finished on the host although the device finish was asked for
+    DevBuf<float> d_ovals;                          // the ordered stream, region by region
+    DevBuf<uint32_t> d_okeys;
+    DevBuf<uint64_t> d_tmp_a, d_tmp_b;              // radix scratch of the order kernel (streams too long for LDS)
+    DevBuf<uint32_t> d_hkeys;                       // heap arrays of a call whose outputs are host memory
+    DevBuf<float> d_hvals;
+    DevBuf<int32_t> d_hsizes;
     // feeders (qadc_adc_search*): quantizer, coarse centroids and the per-call buffers
     int dim = 0, K = 0;                             // dim 0: no set_pq yet;  K 0: flat (no coarse quantizer)
     bool rotated = false;
@@ -80,6 +91,7 @@ struct qadc_adc_index {
     DevBuf<float> d_codebooks, d_cbnorm;            // [nsq][256][dim/nsq];  [2][nsq*256] ||c||^2 under sum_mode 0 and 1
     DevBuf<float> d_rotation, d_coarse, d_cnorm;    // [dim][dim];  [K][dim];  [2][K]
     DevBuf<float> d_queries, d_qnorm, d_cdist, d_tables;
+    const float* cur_queries = nullptr;             // the queries of the call: d_queries, or the caller's device memory
     DevBuf<int32_t> d_assign;
     PinBuf<int32_t> h_assign;
     hipEvent_t ev_assign = nullptr;
@@ -129,11 +141,20 @@ int check_query_args(const qadc_adc_index* idx, int nq, int ma, const int32_t* a
     return QADC_OK;
 }
 
-// Scans the batch on the device and leaves the ordered candidate stream of every query in idx->stream_*.
+// Where the device finish leaves the heaps' arrays of a batch: device memory, keys / values [nq][R], sizes [nq].
+struct DeviceOut {
+    uint32_t* keys;
+    float* values;
+    int32_t* sizes;
+};
+
+// Scans the batch on the device and leaves the ordered candidate stream of every query in idx->stream_* — or, given `out`
+// (R <= kAdcReplayMaxR), orders and replays the streams on the device: the heaps' arrays are in `out` and the stream
+// synchronised on return, and idx->stream_* is empty.
 // The tables are the caller's (`tables`, uploaded with the items) or already in device memory (`d_ready`, enqueued on the
 // index's stream before this call; tables is null then).
 int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, const float* d_ready, int R,
-               int sum_mode) {
+               int sum_mode, const DeviceOut* out = nullptr) {
     if (int rc = check_query_args(idx, nq, ma, assign, d_ready ? static_cast<const void*>(d_ready) : tables, R, sum_mode)) return rc;
     HIPCHECK(hipSetDevice(idx->device));
     // scan-order length of every query, and the levels
@@ -243,7 +264,7 @@ int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const
         }
         HIPCHECK(idx->h_count.ensure(nq));
         // small batches: pack and fetch all regions speculatively, with the counts, in one round trip
-        speculative = entries <= kSpeculativeEntries;
+        speculative = !out && entries <= kSpeculativeEntries;
         if (speculative) {
             HIPCHECK(idx->d_packed.ensure(3 * entries));
             HIPCHECK(idx->h_packed.ensure(3 * entries));
@@ -267,6 +288,24 @@ int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const
         ++idx->reruns;
         entries = fill_state();   // re-run the whole batch with the grown regions
         HIPCHECK(hipMemcpyAsync(d, h, o_assign, hipMemcpyHostToDevice, idx->stream));
+    }
+    if (out) {   // the device finish: order, replay; nothing of the stream crosses the bus
+        idx->stream_off.assign((size_t)nq + 1, 0);
+        idx->stream_keys.clear();
+        idx->stream_vals.clear();
+        HIPCHECK(idx->d_ovals.ensure(entries));
+        HIPCHECK(idx->d_okeys.ensure(entries));
+        int bits = 0;
+        while (bits < 32 && ((max_total - 1) >> bits)) ++bits;   // (max_total >= 1 where anything was stored)
+        if (*std::max_element(stored.begin(), stored.end()) > (uint32_t)qadc::adc::kOrderLds) {
+            if (bits > 8) HIPCHECK(idx->d_tmp_a.ensure(entries));
+            if (bits > 16) HIPCHECK(idx->d_tmp_b.ensure(entries));
+        }
+        const qadc::adc::Emit emit{d_count, idx->d_vals.p, idx->d_keys.p, idx->d_sidx.p, d_base, d_cap};
+        HIPCHECK(qadc::adc::launch_adc_order(nq, emit, bits, idx->d_ovals.p, idx->d_okeys.p, idx->d_tmp_a.p, idx->d_tmp_b.p, idx->stream));
+        HIPCHECK(qadc::adc::launch_adc_replay(nq, R, emit, idx->d_ovals.p, idx->d_okeys.p, out->keys, out->values, out->sizes, idx->stream));
+        HIPCHECK(hipStreamSynchronize(idx->stream));
+        return QADC_OK;
     }
     if (!speculative) {
         HIPCHECK(idx->d_packed.ensure(std::max<uint64_t>(3 * n_stored, 3)));
@@ -364,22 +403,27 @@ int check_search_args(const qadc_adc_index* idx, int nq, const float* queries, i
     return QADC_OK;
 }
 
-// Uploads the queries and leaves assign [nq][ma] in idx->d_assign, its copy to idx->h_assign enqueued with idx->ev_assign
+// Uploads the queries (d_side: they are device memory already and are read where they lie) and leaves assign [nq][ma] in idx->d_assign, its copy to idx->h_assign enqueued with idx->ev_assign
 // recorded behind it: find_k_neighbors (neighbors.cpp:30-76) through the coarse kernels of the 4-bit index, or all zero for a
 // flat index (flat_db::assign_compute_residuals, databases.hpp:93-101).
-int enqueue_assign(qadc_adc_index* idx, int nq, const float* queries, int ma, int sum_mode) {
+int enqueue_assign(qadc_adc_index* idx, int nq, const float* queries, int ma, int sum_mode, bool d_side = false) {
     const int dim = idx->dim;
     HIPCHECK(idx->d_queries.ensure((size_t)nq * dim));
     HIPCHECK(idx->d_assign.ensure((size_t)nq * ma));
     HIPCHECK(idx->h_assign.ensure((size_t)nq * ma));
-    HIPCHECK(hipMemcpyAsync(idx->d_queries.p, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice, idx->stream));
+    if (d_side) {   // read where they are (no memcpy on a caller's device pointer: see launch_adc_copy_words)
+        idx->cur_queries = queries;
+    } else {
+        HIPCHECK(hipMemcpyAsync(idx->d_queries.p, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice, idx->stream));
+        idx->cur_queries = idx->d_queries.p;
+    }
     if (idx->K) {
         const int chunk = std::min(nq, kCoarseChunk);
         HIPCHECK(idx->d_cdist.ensure((size_t)chunk * idx->K));
         HIPCHECK(idx->d_qnorm.ensure(chunk));
         if (ma > 256) HIPCHECK(qadc::coarse_nan_unreplayed_reset(idx->stream));
         for (int o = 0; o < nq; o += kCoarseChunk)
-            qadc::launch_coarse_assign(idx->d_queries.p + (size_t)o * dim, idx->d_coarse.p, std::min(kCoarseChunk, nq - o), idx->K, dim, ma,
+            qadc::launch_coarse_assign(idx->cur_queries + (size_t)o * dim, idx->d_coarse.p, std::min(kCoarseChunk, nq - o), idx->K, dim, ma,
                                        idx->d_qnorm.p, idx->d_cnorm.p + (size_t)sum_mode * idx->K, sum_mode, idx->d_cdist.p,
                                        idx->d_assign.p + (size_t)o * ma, idx->stream);
         HIPCHECK(hipGetLastError());
@@ -406,7 +450,7 @@ int wait_assign(qadc_adc_index* idx, int ma) {
 
 int enqueue_tables(qadc_adc_index* idx, int q0, int nq, int ma, int table_form, int sum_mode) {
     const int expansion = table_form == 2 ? (ma > 1) : table_form;   // nns_engine: direct for ma == 1 (query_common.hpp:292-297)
-    HIPCHECK(qadc::adc::launch_adc_tables(idx->d_queries.p + (size_t)q0 * idx->dim, idx->K ? idx->d_coarse.p : nullptr,
+    HIPCHECK(qadc::adc::launch_adc_tables(idx->cur_queries + (size_t)q0 * idx->dim, idx->K ? idx->d_coarse.p : nullptr,
                                           idx->d_assign.p + (size_t)q0 * ma, idx->d_codebooks.p,
                                           idx->d_cbnorm.p + (size_t)sum_mode * idx->nsq * 256, idx->rotated ? idx->d_rotation.p : nullptr, nq, ma,
                                           idx->nsq, idx->dim, expansion, sum_mode, idx->d_tables.p, idx->stream));
@@ -419,18 +463,21 @@ int queries_per_pass(const qadc_adc_index* idx, int nq, int ma) {
     return (int)std::min<uint64_t>((uint64_t)nq, std::max<uint64_t>(1, idx->table_budget / per_query));
 }
 
-// Feeders + scan of the whole batch in sub-batches; leaves the ordered stream of all nq queries in idx->stream_*.
-int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, int32_t* assign_out) {
+// Feeders + scan of the whole batch in sub-batches; leaves the ordered stream of all nq queries in idx->stream_*, or, given
+// `out`, the heaps' arrays of all nq queries there (scan_batch's device finish, sub-batch by sub-batch).  d_side: the queries
+// are in device memory.
+int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, int32_t* assign_out,
+                 const DeviceOut* out = nullptr, bool d_side = false) {
     if (int rc = check_search_args(idx, nq, queries, ma, table_form, sum_mode)) return rc;
     if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
     HIPCHECK(hipSetDevice(idx->device));
     const int per = queries_per_pass(idx, nq, ma);
     HIPCHECK(idx->d_tables.ensure((size_t)per * ma * idx->nsq * 256));
-    if (int rc = enqueue_assign(idx, nq, queries, ma, sum_mode)) return rc;
+    if (int rc = enqueue_assign(idx, nq, queries, ma, sum_mode, d_side)) return rc;
     if (int rc = enqueue_tables(idx, 0, per, ma, table_form, sum_mode)) return rc;   // (runs while the host plans the first scan)
     if (int rc = wait_assign(idx, ma)) return rc;
     if (assign_out) std::memcpy(assign_out, idx->h_assign.p, (size_t)nq * ma * 4);
-    if (per == nq) return scan_batch(idx, nq, ma, idx->h_assign.p, nullptr, idx->d_tables.p, R, sum_mode);
+    if (per == nq) return scan_batch(idx, nq, ma, idx->h_assign.p, nullptr, idx->d_tables.p, R, sum_mode, out);
     std::vector<uint64_t> off{0};
     std::vector<uint32_t> keys;
     std::vector<float> vals;
@@ -438,15 +485,64 @@ int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int 
         const int n = std::min(per, nq - q0);
         if (q0)   // (the scan before it has been waited for: the table buffer is free)
             if (int rc = enqueue_tables(idx, q0, n, ma, table_form, sum_mode)) return rc;
+        if (out) {
+            const DeviceOut sub{out->keys + (size_t)q0 * R, out->values + (size_t)q0 * R, out->sizes + q0};
+            if (int rc = scan_batch(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, R, sum_mode, &sub)) return rc;
+            continue;
+        }
         if (int rc = scan_batch(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, R, sum_mode)) return rc;
         const uint64_t base = off.back();
         for (int q = 1; q <= n; ++q) off.push_back(base + idx->stream_off[q]);
         keys.insert(keys.end(), idx->stream_keys.begin(), idx->stream_keys.end());
         vals.insert(vals.end(), idx->stream_vals.begin(), idx->stream_vals.end());
     }
+    if (out) return QADC_OK;
     idx->stream_off.swap(off);
     idx->stream_keys.swap(keys);
     idx->stream_vals.swap(vals);
+    return QADC_OK;
+}
+
+// ---- the device finish of the entry points ----
+
+bool device_replay_covers(int R) { return R >= 1 && R <= qadc::adc::kAdcReplayMaxR; }
+
+// The device buffers for the heaps' arrays of a call whose outputs are host memory.
+int host_call_out(qadc_adc_index* idx, int nq, int R, DeviceOut* out) {
+    HIPCHECK(hipSetDevice(idx->device));
+    HIPCHECK(idx->d_hkeys.ensure((size_t)nq * R));
+    HIPCHECK(idx->d_hvals.ensure((size_t)nq * R));
+    HIPCHECK(idx->d_hsizes.ensure(nq));
+    *out = DeviceOut{idx->d_hkeys.p, idx->d_hvals.p, idx->d_hsizes.p};
+    return QADC_OK;
+}
+
+// nq R keys, nq R values and nq sizes to the caller's host arrays (any may be null): all that crosses the bus after the scan.
+int fetch_heaps(qadc_adc_index* idx, int nq, int R, const DeviceOut& out, uint32_t* keys, float* values, int32_t* sizes) {
+    if (keys) HIPCHECK(hipMemcpyAsync(keys, out.keys, (size_t)nq * R * 4, hipMemcpyDeviceToHost, idx->stream));
+    if (values) HIPCHECK(hipMemcpyAsync(values, out.values, (size_t)nq * R * 4, hipMemcpyDeviceToHost, idx->stream));
+    if (sizes) HIPCHECK(hipMemcpyAsync(sizes, out.sizes, (size_t)nq * 4, hipMemcpyDeviceToHost, idx->stream));
+    HIPCHECK(hipStreamSynchronize(idx->stream));
+    return QADC_OK;
+}
+
+// A batch the device replay does not cover (R > kAdcReplayMaxR), finished on the host from idx->stream_* and uploaded into
+// the caller's device arrays (staged in the index's own buffers, then copied by a kernel): the *_device contract stays uniform.
+int upload_host_heaps(qadc_adc_index* idx, int nq, int R, const DeviceOut& out) {
+    std::vector<uint32_t> keys((size_t)nq * R);
+    std::vector<float> values((size_t)nq * R);
+    std::vector<int32_t> sizes(nq);
+    replay_heaps(idx, nq, R, keys.data(), values.data(), sizes.data());
+    idx->host_finishes += (uint64_t)nq;
+    DeviceOut own;
+    if (int rc = host_call_out(idx, nq, R, &own)) return rc;
+    HIPCHECK(hipMemcpyAsync(own.keys, keys.data(), keys.size() * 4, hipMemcpyHostToDevice, idx->stream));
+    HIPCHECK(hipMemcpyAsync(own.values, values.data(), values.size() * 4, hipMemcpyHostToDevice, idx->stream));
+    HIPCHECK(hipMemcpyAsync(own.sizes, sizes.data(), sizes.size() * 4, hipMemcpyHostToDevice, idx->stream));
+    HIPCHECK(qadc::adc::launch_adc_copy_words(own.keys, out.keys, keys.size(), idx->stream));
+    HIPCHECK(qadc::adc::launch_adc_copy_words(own.values, out.values, values.size(), idx->stream));
+    HIPCHECK(qadc::adc::launch_adc_copy_words(own.sizes, out.sizes, sizes.size(), idx->stream));
+    HIPCHECK(hipStreamSynchronize(idx->stream));
     return QADC_OK;
 }
 
@@ -506,6 +602,13 @@ int qadc_adc_index_destroy(qadc_adc_index* idx) {
     idx->d_keys.release();
     idx->d_sidx.release();
     idx->d_packed.release();
+    idx->d_ovals.release();
+    idx->d_okeys.release();
+    idx->d_tmp_a.release();
+    idx->d_tmp_b.release();
+    idx->d_hkeys.release();
+    idx->d_hvals.release();
+    idx->d_hsizes.release();
     idx->h_in.release();
     idx->h_count.release();
     idx->h_packed.release();
@@ -581,6 +684,16 @@ int qadc_adc_index_partition_count(const qadc_adc_index* idx) { return idx ? (in
 
 uint64_t qadc_adc_index_reruns(const qadc_adc_index* idx) { return idx ? idx->reruns : 0; }
 
+int qadc_adc_index_set_finish(qadc_adc_index* idx, int mode) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (mode != QADC_ADC_FINISH_HOST && mode != QADC_ADC_FINISH_DEVICE)
+        return fail(QADC_E_ARG, "finish mode is 0 (host: QADC_ADC_FINISH_HOST) or 1 (device: QADC_ADC_FINISH_DEVICE)");
+    idx->finish = mode;
+    return QADC_OK;
+}
+
+uint64_t qadc_adc_index_host_finishes(const qadc_adc_index* idx) { return idx ? idx->host_finishes : 0; }
+
 uint32_t qadc_adc_index_partition_size(const qadc_adc_index* idx, int part) {
     if (!idx || part < 0 || part >= (int)idx->sizes.size()) return 0;
     return idx->sizes[part];
@@ -589,9 +702,27 @@ uint32_t qadc_adc_index_partition_size(const qadc_adc_index* idx, int part) {
 int qadc_adc_query_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
                         uint32_t* keys, float* values, int32_t* sizes) {
     DeviceGuard guard;
+    if (idx && idx->finish == QADC_ADC_FINISH_DEVICE && nq >= 1 && device_replay_covers(R)) {
+        DeviceOut out;
+        if (int rc = host_call_out(idx, nq, R, &out)) return rc;
+        if (int rc = scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode, &out)) return rc;
+        return fetch_heaps(idx, nq, R, out, keys, values, sizes);
+    }
     if (int rc = scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode)) return rc;
     replay_heaps(idx, nq, R, keys, values, sizes);
+    if (idx->finish == QADC_ADC_FINISH_DEVICE) idx->host_finishes += (uint64_t)nq;
     return QADC_OK;
+}
+
+int qadc_adc_query_scan_device(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, int R, int sum_mode,
+                               uint32_t* d_keys, float* d_values, int32_t* d_sizes) {
+    if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
+    if (!d_keys || !d_values || !d_sizes) return fail(QADC_E_ARG, "d_keys, d_values and d_sizes are required");
+    DeviceGuard guard;
+    const DeviceOut out{d_keys, d_values, d_sizes};
+    if (device_replay_covers(R)) return scan_batch(idx, nq, ma, assign, nullptr, d_tables, R, sum_mode, &out);
+    if (int rc = scan_batch(idx, nq, ma, assign, nullptr, d_tables, R, sum_mode)) return rc;
+    return upload_host_heaps(idx, nq, R, out);
 }
 
 int qadc_adc_query_scan_candidates(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R,
@@ -670,9 +801,27 @@ int qadc_adc_index_set_table_budget(qadc_adc_index* idx, uint64_t bytes) {
 int qadc_adc_search(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, uint32_t* keys,
                     float* values, int32_t* sizes, int32_t* assign_out) {
     DeviceGuard guard;
+    if (idx && idx->finish == QADC_ADC_FINISH_DEVICE && nq >= 1 && device_replay_covers(R)) {
+        DeviceOut out;
+        if (int rc = host_call_out(idx, nq, R, &out)) return rc;
+        if (int rc = search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out, &out)) return rc;
+        return fetch_heaps(idx, nq, R, out, keys, values, sizes);
+    }
     if (int rc = search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out)) return rc;
     replay_heaps(idx, nq, R, keys, values, sizes);
+    if (idx->finish == QADC_ADC_FINISH_DEVICE) idx->host_finishes += (uint64_t)nq;
     return QADC_OK;
+}
+
+int qadc_adc_search_device(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int R, int table_form, int sum_mode,
+                           uint32_t* d_keys, float* d_values, int32_t* d_sizes) {
+    if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
+    if (!d_keys || !d_values || !d_sizes) return fail(QADC_E_ARG, "d_keys, d_values and d_sizes are required");
+    DeviceGuard guard;
+    const DeviceOut out{d_keys, d_values, d_sizes};
+    if (device_replay_covers(R)) return search_batch(idx, nq, d_queries, ma, R, table_form, sum_mode, nullptr, &out, true);
+    if (int rc = search_batch(idx, nq, d_queries, ma, R, table_form, sum_mode, nullptr, nullptr, true)) return rc;
+    return upload_host_heaps(idx, nq, R, out);
 }
 
 int qadc_adc_search_candidates(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,

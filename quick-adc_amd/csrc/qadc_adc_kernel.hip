@@ -7,6 +7,9 @@
 //   adc_select_kernel  one workgroup per query: bound = the R-th smallest value the query emitted so far (radix select on
 //                      the order-preserving integer image of the floats), the bound of the next level's runs;
 //   adc_pack_kernel    the per-query regions packed densely for one device-to-host copy;
+//   adc_order_kernel   the device finish: each query's stored candidates put in scan order (LDS sort, or radix passes through
+//                      global scratch for streams of any length);
+//   adc_replay_kernel  the device finish: the ordered stream pushed through kv_binheap<unsigned, float>(R) in LDS, one wave per query;
 //   adc_tables_kernel  the float tables of every (query, probe) from query vectors (residual, OPQ rotation, both table forms);
 //   adc_encode_kernel  vectors -> one code byte per sub-quantizer.
 // The bound rule and why it is exact: DESIGN.md section 11.  Built with -ffp-contract=off and without fast-math (Makefile):
@@ -184,6 +187,211 @@ __global__ __launch_bounds__(kWG) void adc_pack_kernel(Emit emit, uint32_t* __re
         r[1] = emit.keys[src + i];
         r[2] = emit.sidx[src + i];
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The device finish: what the host otherwise does with the packed stream.
+//
+// adc_order_kernel: one workgroup per query puts the query's stored candidates in scan order (scan indices are distinct
+// within a query) and writes (value, key) of the i-th candidate of the scan to ovals / okeys [base[q] + i].
+//   n <= kOrderLds   a bitonic sort of (scan index << 32 | position in the region) in LDS;
+//   longer streams   LSD radix passes of 8 bits over the `bits` low bits of the scan index (the host knows the longest scan
+//                    order of the batch), one workgroup per query, through the global scratch tmp_a / tmp_b [base[q] + i]:
+//                    a histogram of the digit, then a stable scatter tile by tile (256 entries, one per thread: rank among
+//                    the equal digits of the wave by ballots, of the waves before through LDS counts).  The last pass
+//                    writes (value, key) instead of the pair.  The passes of a query meet only inside its workgroup, so a
+//                    workgroup barrier orders them.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void wave_lds_sync() {
+    // LDS operations of one wave execute in order; this only stops the compiler from moving them
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(kWG) void adc_order_kernel(Emit emit, int bits, float* __restrict__ ovals,
+                                                        uint32_t* __restrict__ okeys, unsigned long long* tmp_a,
+                                                        unsigned long long* tmp_b) {
+    __shared__ unsigned long long lkey[kOrderLds];
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const uint32_t n = min(emit.count[q], emit.cap[q]);
+    if (n == 0) return;
+    const size_t region = emit.base[q];
+    const float* __restrict__ vals = emit.vals + region;
+    const uint32_t* __restrict__ keys = emit.keys + region;
+    const uint32_t* __restrict__ sidx = emit.sidx + region;
+    float* __restrict__ ov = ovals + region;
+    uint32_t* __restrict__ ok = okeys + region;
+
+    if (n <= (uint32_t)kOrderLds) {
+        uint32_t n2 = 1;
+        while (n2 < n) n2 <<= 1;
+        for (uint32_t i = tid; i < n2; i += kWG) lkey[i] = i < n ? ((unsigned long long)sidx[i] << 32) | i : ~0ull;
+        __syncthreads();
+        for (uint32_t k = 2; k <= n2; k <<= 1)
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                for (uint32_t t = tid; t < n2 / 2; t += kWG) {   // the t-th pair of this step: i has bit j clear
+                    const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+                    const unsigned long long a = lkey[i], b = lkey[p];
+                    if ((a > b) == ((i & k) == 0)) { lkey[i] = b; lkey[p] = a; }
+                }
+                __syncthreads();
+            }
+        for (uint32_t i = tid; i < n; i += kWG) {
+            const uint32_t j = (uint32_t)lkey[i];
+            ov[i] = vals[j];
+            ok[i] = keys[j];
+        }
+        return;
+    }
+
+    uint32_t* hist = reinterpret_cast<uint32_t*>(lkey);          // [256] entries of the digit, then its running write position
+    uint32_t* wcount = hist + 256;                               // [4][256] entries of the digit in each wave of the tile
+    unsigned long long* ta = tmp_a + region;
+    unsigned long long* tb = tmp_b + region;
+    const uint32_t lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1;
+    const int passes = (bits + 7) / 8;
+    for (int pass = 0; pass < passes; ++pass) {
+        const unsigned long long* src = (pass & 1) ? ta : tb;    // pass 0 reads the region itself
+        unsigned long long* dst = (pass & 1) ? tb : ta;
+        const int shift = 32 + 8 * pass;
+        const bool last = pass + 1 == passes;
+        auto entry = [&](uint32_t i) { return pass == 0 ? ((unsigned long long)sidx[i] << 32) | i : src[i]; };
+        hist[tid] = 0;
+        for (int w = 0; w < 4; ++w) wcount[w * 256 + tid] = 0;
+        __syncthreads();
+        for (unsigned long long i = tid; i < n; i += kWG) atomicAdd(&hist[(uint32_t)(entry((uint32_t)i) >> shift) & 255u], 1u);
+        __syncthreads();
+        if (tid < 64) {                                          // wave 0: exclusive prefix sums, lane l holds digits 4l .. 4l+3
+            const uint32_t h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+            uint32_t incl = h0 + h1 + h2 + h3;
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t o = __shfl_up(incl, d);
+                if (tid >= (uint32_t)d) incl += o;
+            }
+            const uint32_t excl = incl - (h0 + h1 + h2 + h3);
+            hist[4 * tid] = excl;
+            hist[4 * tid + 1] = excl + h0;
+            hist[4 * tid + 2] = excl + h0 + h1;
+            hist[4 * tid + 3] = excl + h0 + h1 + h2;
+        }
+        __syncthreads();
+        for (unsigned long long t0 = 0; t0 < n; t0 += kWG) {     // (64-bit: n may be within 256 of 2^32)
+            const bool valid = t0 + tid < n;
+            const uint32_t i = (uint32_t)(t0 + tid);
+            const unsigned long long e = valid ? entry(i) : 0ull;
+            const uint32_t d = (uint32_t)(e >> shift) & 255u;
+            unsigned long long same = __ballot(valid);           // lanes of this wave with the same digit
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const bool bit = (d >> b) & 1u;
+                const unsigned long long m = __ballot(bit);
+                same &= bit ? m : ~m;
+            }
+            const uint32_t rank = (uint32_t)__popcll(same & below);
+            if (valid && rank == 0) wcount[wave * 256 + d] = (uint32_t)__popcll(same);
+            __syncthreads();
+            if (valid) {
+                uint32_t pos = hist[d] + rank;
+                for (uint32_t w = 0; w < wave; ++w) pos += wcount[w * 256 + d];
+                if (last) {
+                    const uint32_t j = (uint32_t)e;
+                    ov[pos] = vals[j];
+                    ok[pos] = keys[j];
+                } else {
+                    dst[pos] = e;
+                }
+            }
+            __syncthreads();
+            {                                                    // thread d owns digit d: advance its position, clear the counts
+                uint32_t c = 0;
+                for (int w = 0; w < 4; ++w) {
+                    c += wcount[w * 256 + tid];
+                    wcount[w * 256 + tid] = 0;
+                }
+                hist[tid] += c;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// adc_replay_kernel: kv_binheap<unsigned, float>::push (binheap.hpp:75-116) on the device, the float twin of
+// replay_heap_kernel (csrc/qadc_kernels.hip).  One wave per query, `waves` queries per workgroup, each with its heap
+// [R] (key | value bits << 32) and a 64-entry stage in LDS.  The R sentinels come first (db_query.cpp:31-33) and
+// FLT_MAX - t is FLT_MAX for every t the engine takes, and equal values appended never move: the heap starts as R times
+// (0, FLT_MAX), full, and only the full branch of push remains — accepted iff strictly below the root, sinking with the
+// left child preferred unless the right one is strictly greater, stopping at a child <= the value.  All compares are float
+// compares (-0 == +0), as the reference's.  The lanes stage 64 entries of the ordered stream at a time and drop those not
+// below the root as it stands (the root only falls); lane 0 pushes the rest in order.  Output: the heap's arrays.
+__global__ __launch_bounds__(kWG) void adc_replay_kernel(int nq, int R, const uint32_t* __restrict__ count,
+                                                         const uint32_t* __restrict__ cap, const uint64_t* __restrict__ base,
+                                                         const float* __restrict__ ovals, const uint32_t* __restrict__ okeys,
+                                                         uint32_t* __restrict__ keys, float* __restrict__ values,
+                                                         int32_t* __restrict__ sizes) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long dyn64[];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = (int)(blockIdx.x * (blockDim.x >> 6) + wave);
+    if (q >= nq) return;                                         // (no workgroup barrier below: waves run on their own)
+    unsigned long long* hv = dyn64 + (size_t)wave * (R + 64);
+    unsigned long long* buf = hv + R;
+    const uint32_t n = min(count[q], cap[q]);
+    const float* __restrict__ sv = ovals + base[q];
+    const uint32_t* __restrict__ sk = okeys + base[q];
+    const uint32_t uR = (uint32_t)R;
+    for (uint32_t i = lane; i < uR; i += 64) hv[i] = (unsigned long long)__float_as_uint(FLT_MAX) << 32;
+    wave_lds_sync();
+    auto val_of = [](unsigned long long e) { return __uint_as_float((uint32_t)(e >> 32)); };
+    auto push = [&](unsigned long long e) {
+        const float value = val_of(e);
+        if (!(value < val_of(hv[0]))) return;
+        uint32_t i = 0;
+        for (;;) {
+            const uint32_t l = 2 * i + 1;
+            if (l >= uR) break;
+            unsigned long long ce = hv[l];
+            uint32_t c = l;
+            if (l + 1 < uR) {
+                const unsigned long long re = hv[l + 1];
+                if (val_of(re) > val_of(ce)) { ce = re; c = l + 1; }
+            }
+            if (val_of(ce) <= value) break;
+            hv[i] = ce;
+            i = c;
+        }
+        hv[i] = e;
+    };
+    float v = 0.0f;
+    uint32_t k = 0;
+    if (lane < n) { v = sv[lane]; k = sk[lane]; }
+    for (uint32_t at = 0; at < n; at += 64) {
+        const uint32_t m = min(64u, n - at);
+        const float cv = v;
+        const uint32_t ck = k;
+        if (at + 64 < n && lane < n - (at + 64)) {               // the next 64 are on their way while lane 0 pushes these
+            v = sv[at + 64 + lane];
+            k = sk[at + 64 + lane];
+        }
+        const unsigned long long live = __ballot(lane < m && cv < val_of(hv[0]));
+        if (live == 0) continue;
+        buf[lane] = (unsigned long long)ck | ((unsigned long long)__float_as_uint(cv) << 32);
+        wave_lds_sync();
+        if (lane == 0)
+            for (unsigned long long rest = live; rest; rest &= rest - 1) push(buf[__builtin_ctzll(rest)]);
+        wave_lds_sync();
+    }
+    for (uint32_t i = lane; i < uR; i += 64) {
+        const unsigned long long e = hv[i];
+        keys[(size_t)q * R + i] = (uint32_t)e;
+        values[(size_t)q * R + i] = val_of(e);
+    }
+    if (lane == 0) sizes[q] = R;
+}
+
+// Words from one device buffer to another by a kernel: a buffer of the caller's need not be known to this library's copy of
+// the HIP runtime (a tensor of a framework that carries its own), and a memcpy on a pointer the runtime does not know treats it as host memory.
+__global__ __launch_bounds__(kWG) void adc_copy_words_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * kWG + threadIdx.x; i < n; i += (size_t)gridDim.x * kWG) dst[i] = src[i];
 }
 
 template <int NSQ, int SUM>
@@ -374,6 +582,29 @@ hipError_t launch_adc_select(int nq, int R, Emit emit, float* bound, hipStream_t
 
 hipError_t launch_adc_pack(int nq, Emit emit, uint32_t* out, hipStream_t s) {
     hipLaunchKernelGGL(adc_pack_kernel, dim3(nq), dim3(kWG), 0, s, emit, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_adc_order(int nq, Emit emit, int bits, float* ovals, uint32_t* okeys, uint64_t* tmp_a, uint64_t* tmp_b, hipStream_t s) {
+    hipLaunchKernelGGL(adc_order_kernel, dim3(nq), dim3(kWG), 0, s, emit, bits, ovals, okeys,
+                       reinterpret_cast<unsigned long long*>(tmp_a), reinterpret_cast<unsigned long long*>(tmp_b));
+    return hipGetLastError();
+}
+
+hipError_t launch_adc_replay(int nq, int R, Emit emit, const float* ovals, const uint32_t* okeys, uint32_t* keys, float* values,
+                             int32_t* sizes, hipStream_t s) {
+    if (R < 1 || R > kAdcReplayMaxR) return hipErrorInvalidValue;
+    const size_t per_wave = (size_t)(R + 64) * 8;                // heap + stage of one query
+    const int waves = (int)std::max<size_t>(1, std::min<size_t>(kWG / 64, (60 * 1024) / per_wave));
+    hipLaunchKernelGGL(adc_replay_kernel, dim3((nq + waves - 1) / waves), dim3(64 * waves), waves * per_wave, s, nq, R, emit.count,
+                       emit.cap, emit.base, ovals, okeys, keys, values, sizes);
+    return hipGetLastError();
+}
+
+hipError_t launch_adc_copy_words(const void* src, void* dst, size_t words, hipStream_t s) {
+    if (words == 0) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<size_t>((words + kWG - 1) / kWG, 4096);
+    hipLaunchKernelGGL(adc_copy_words_kernel, dim3(grid), dim3(kWG), 0, s, static_cast<const uint32_t*>(src), static_cast<uint32_t*>(dst), words);
     return hipGetLastError();
 }
 

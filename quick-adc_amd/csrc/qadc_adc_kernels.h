@@ -47,6 +47,21 @@ hipError_t launch_adc_select(int nq, int R, Emit emit, float* bound, hipStream_t
 hipError_t launch_adc_pack(int nq, Emit emit, uint32_t* out, hipStream_t s);
 
 
+// The device finish.
+constexpr int kOrderLds = 4096;       // entries adc_order_kernel sorts in LDS (8 bytes each); longer streams take radix passes
+constexpr int kAdcReplayMaxR = 4096;  // largest heap adc_replay_kernel keeps in LDS (8 bytes per entry and 512 of stage)
+
+// Puts the stored candidates of every query in scan order: (value, key) of the i-th of query q to ovals / okeys [base[q] + i].
+// bits = bits of the largest scan index of the batch.  tmp_a, tmp_b: scratch of as many entries as the regions, read only by
+// queries that stored more than kOrderLds entries (tmp_a when bits > 8, tmp_b when bits > 16; else may be null).
+hipError_t launch_adc_order(int nq, Emit emit, int bits, float* ovals, uint32_t* okeys, uint64_t* tmp_a, uint64_t* tmp_b, hipStream_t s);
+// Replays every query's ordered stream through kv_binheap<unsigned, float>(R) after its R sentinels: keys / values [nq][R] and
+// sizes [nq] (device memory) = the heap's arrays.  R <= kAdcReplayMaxR.
+hipError_t launch_adc_replay(int nq, int R, Emit emit, const float* ovals, const uint32_t* okeys, uint32_t* keys, float* values,
+                             int32_t* sizes, hipStream_t s);
+// dst[i] = src[i] for `words` 32-bit words, by a kernel (either side may be memory this library's HIP runtime did not allocate).
+hipError_t launch_adc_copy_words(const void* src, void* dst, size_t words, hipStream_t s);
+
 constexpr int kAdcMaxDim = 4096;      // largest vector dimension the feeders take (their residuals live in LDS)
 
 // The float tables of nq queries from their vectors: d_tables [nq][ma][nsq][256], the layout launch_adc_scan reads.

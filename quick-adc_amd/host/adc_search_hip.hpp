@@ -12,6 +12,9 @@
 //         pq->sq_count, pq->sq_bits, pq->dim, pq->centroids, pq->rotation  (host/scanner_simple.hpp pq_bytes)
 //   Heap: int capacity(); void push(unsigned, float)                       (kv_binheap<unsigned, float>, binheap.hpp)
 // table_form: 1 = the BLAS-expansion tables nns_engine_batch builds (default), 0 = direct, 2 = nns_engine's rule.
+// set_finish(QADC_ADC_FINISH_DEVICE): the batch's heaps are ordered and replayed on the GPU (qadc_adc_search under
+// qadc_adc_index_set_finish) and a query's arrays are pushed into the caller's empty heap in array order, which rebuilds them
+// exactly; the default is the host finish, the candidate stream.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -30,6 +33,8 @@ template <typename Db>
 struct adc_search_engine_hip {
     Db& db;
     int ma, batch, r, device, sum_mode, table_form;
+    int finish = QADC_ADC_FINISH_HOST;
+    std::vector<std::int32_t> heap_sizes;   // device finish: [batch]; the arrays are in cand_keys / cand_vals [batch][r]
     qadc_adc_index* index;
     std::vector<std::uint32_t> cand_keys;
     std::vector<float> cand_vals;
@@ -48,10 +53,21 @@ struct adc_search_engine_hip {
         std::exit(1);
     }
 
+    // qadc_adc_index_set_finish: before or after prepare_database, between batches
+    void set_finish(int mode) {
+        if (mode != QADC_ADC_FINISH_HOST && mode != QADC_ADC_FINISH_DEVICE) {
+            std::cerr << "set_finish: mode is QADC_ADC_FINISH_HOST or QADC_ADC_FINISH_DEVICE" << std::endl;
+            std::exit(1);
+        }
+        finish = mode;
+        if (index && qadc_adc_index_set_finish(index, mode) != QADC_OK) die("set_finish");
+    }
+
     // scanner_simple::prepare_database (db_query.cpp:21-24) plus the quantizers the feeders need
     void prepare_database() {
         const int m = db.pq->sq_count, bits = db.pq->sq_bits;
         if (qadc_adc_index_create(&index, m, bits, device) != QADC_OK) die("Cannot create the GPU index");
+        if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
         const int part_count = db.partition_count();
         std::vector<const std::uint8_t*> codes(part_count);
         std::vector<const std::uint32_t*> labels(part_count);
@@ -79,6 +95,22 @@ struct adc_search_engine_hip {
         const int b = query_i % batch;
         metrics = query_metrics();
         const std::uint64_t t0 = ustime();
+        if (finish == QADC_ADC_FINISH_DEVICE) {   // the heaps' arrays of the batch from the GPU (bh is empty, as the driver hands it over)
+            if (b == 0) {
+                const int nb = std::min(batch, count - query_i);
+                if (cand_keys.size() < (std::size_t)batch * r) {
+                    cand_keys.resize((std::size_t)batch * r);
+                    cand_vals.resize((std::size_t)batch * r);
+                }
+                heap_sizes.resize(batch);
+                if (qadc_adc_search(index, nb, queries + (std::size_t)query_i * db.pq->dim, ma, r, table_form, sum_mode, cand_keys.data(),
+                                    cand_vals.data(), heap_sizes.data(), assign.data()) != QADC_OK)
+                    die("search");
+            }
+            for (std::int32_t i = 0; i < heap_sizes[b]; ++i) bh.push(cand_keys[(std::size_t)b * r + i], cand_vals[(std::size_t)b * r + i]);
+            metrics.scan_us = ustime() - t0;
+            return;
+        }
         if (b == 0) {
             const int nb = std::min(batch, count - query_i);
             const float* q = queries + (std::size_t)query_i * db.pq->dim;

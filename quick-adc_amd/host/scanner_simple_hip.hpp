@@ -8,6 +8,9 @@
 //         pq->sq_count, pq->sq_bits                                      (databases.hpp:34-63)
 //   Heap: int capacity(); void push(unsigned, float)                     (kv_binheap<unsigned, float>, binheap.hpp)
 // Sums are in the reference's grouping as compiled (sum_mode 1) unless the constructor is given 0 (source order).
+// set_finish(QADC_ADC_FINISH_DEVICE): the heap is ordered and replayed on the GPU (qadc_adc_query_scan under
+// qadc_adc_index_set_finish) and its arrays are pushed into the caller's empty heap in array order, which rebuilds them exactly
+// (no entry of a heap's array exceeds its parent, so none moves); the default is the host finish, the candidate stream below.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -28,6 +31,7 @@ struct scanner_simple_hip {
 
     int device, sum_mode;
     int table_floats = 0;   // sq_count * 256
+    int finish = QADC_ADC_FINISH_HOST;
     qadc_adc_index* index;
     std::vector<std::uint32_t> cand_keys;
     std::vector<float> cand_vals;
@@ -42,6 +46,16 @@ struct scanner_simple_hip {
         std::exit(1);
     }
 
+    // qadc_adc_index_set_finish: before or after prepare_database
+    void set_finish(int mode) {
+        if (mode != QADC_ADC_FINISH_HOST && mode != QADC_ADC_FINISH_DEVICE) {
+            std::cerr << "set_finish: mode is QADC_ADC_FINISH_HOST or QADC_ADC_FINISH_DEVICE" << std::endl;
+            std::exit(1);
+        }
+        finish = mode;
+        if (index && qadc_adc_index_set_finish(index, mode) != QADC_OK) die("set_finish");
+    }
+
     // scanner_simple::prepare_database + get_scan_func (db_query.cpp:21-24, query_common.hpp:120-146)
     void prepare_database(Db& db) {
         const int m = db.pq->sq_count, bits = db.pq->sq_bits;
@@ -52,6 +66,7 @@ struct scanner_simple_hip {
             std::exit(1);
         }
         if (qadc_adc_index_create(&index, m, bits, device) != QADC_OK) die("Cannot create the GPU index");
+        if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
         table_floats = m * 256;
         // every partition in one call (one upload of the partition table, one growth of the device copy)
         const int part_count = db.partition_count();
@@ -77,6 +92,18 @@ struct scanner_simple_hip {
         if (table_dim != table_floats) {
             std::cerr << "query_scan: table_dim " << table_dim << " is not sq_count * 256" << std::endl;
             std::exit(1);
+        }
+        if (finish == QADC_ADC_FINISH_DEVICE) {   // the heap's arrays from the GPU (bh is empty, as the engines hand it over)
+            const std::size_t r = (std::size_t)bh.capacity();
+            if (cand_keys.size() < r) {
+                cand_keys.resize(r);
+                cand_vals.resize(r);
+            }
+            std::int32_t size = 0;
+            if (qadc_adc_query_scan(index, 1, ma, assign, tables, bh.capacity(), sum_mode, cand_keys.data(), cand_vals.data(), &size) != QADC_OK)
+                die("query_scan");
+            for (std::int32_t i = 0; i < size; ++i) bh.push(cand_keys[i], cand_vals[i]);
+            return;
         }
         std::uint64_t offsets[2] = {0, 0};
         if (cand_keys.empty()) {

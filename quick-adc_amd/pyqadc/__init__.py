@@ -40,6 +40,7 @@ SYMBOLS = [
     "qadc_adc_index_partition_size", "qadc_adc_query_scan", "qadc_adc_query_scan_candidates", "qadc_adc_index_reruns",
     "qadc_adc_index_set_pq", "qadc_adc_index_set_rotation", "qadc_adc_index_set_coarse", "qadc_adc_index_set_table_budget",
     "qadc_adc_search", "qadc_adc_search_candidates", "qadc_adc_search_tables", "qadc_adc_encode_host",
+    "qadc_adc_index_set_finish", "qadc_adc_index_host_finishes", "qadc_adc_search_device", "qadc_adc_query_scan_device",
 ]
 
 
@@ -178,6 +179,13 @@ def lib():
         L.qadc_adc_query_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, u32p, f32p, i32p]
         L.qadc_adc_query_scan_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, C.c_uint64,
                                                      u32p, f32p, u64p]
+        L.qadc_adc_index_set_finish.argtypes = [C.c_void_p, C.c_int]
+        L.qadc_adc_index_host_finishes.argtypes = [C.c_void_p]
+        L.qadc_adc_index_host_finishes.restype = C.c_uint64
+        L.qadc_adc_search_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
+        L.qadc_adc_query_scan_device.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
         _lib = L
     return _lib
 
@@ -753,6 +761,7 @@ class AdcIndex:
 
     def __init__(self, sq_count, sq_bits, device=0):
         self.sq_count = sq_count
+        self.device = device
         self._h = C.c_void_p()
         _check(lib().qadc_adc_index_create(C.byref(self._h), sq_count, sq_bits, device))
 
@@ -786,6 +795,15 @@ class AdcIndex:
     def reruns(self):
         """query calls on this index that were re-run because a candidate region overflowed"""
         return lib().qadc_adc_index_reruns(self._h)
+
+    def set_finish(self, mode):
+        """0 (default): the host orders the kept candidates and replays the heaps; 1: query_scan and search do both on the GPU and
+        fetch only the heaps' arrays (same arrays, bit for bit)"""
+        _check(lib().qadc_adc_index_set_finish(self._h, int(mode)))
+
+    def host_finishes(self):
+        """queries finished on the host while the device finish was asked for (R > 4096 is the only cause)"""
+        return lib().qadc_adc_index_host_finishes(self._h)
 
     def _inputs(self, assign, tables):
         assign = np.ascontiguousarray(assign, np.int32)
@@ -909,3 +927,52 @@ class AdcIndex:
         tables = np.zeros((nq, ma, self.sq_count * 256), np.float32)
         _check(lib().qadc_adc_search_tables(self._h, nq, _p(q, f32p), ma, table_form, sum_mode, _p(assign, i32p), _p(tables, f32p)))
         return assign, tables
+
+    # ---- device memory in, device memory out: torch tensors by data_ptr() (torch is imported here only) ----
+    def _device_tensor(self, t, shape, what):
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, not %s" % (what, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be float32, not %s" % (what, t.dtype))
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise QadcError("%s is on %s; the index is on device %d" % (what, t.device, self.device))
+        if not t.is_contiguous():
+            raise QadcError("%s must be contiguous" % what)
+        if tuple(t.shape) != tuple(shape):
+            raise QadcError("%s has shape %s, expected %s" % (what, tuple(t.shape), tuple(shape)))
+        return t
+
+    def _device_outputs(self, nq, R):
+        import torch
+        dev = torch.device("cuda", self.device)
+        keys = torch.zeros((nq, R), dtype=torch.int32, device=dev)       # the uint32 keys' bits
+        vals = torch.zeros((nq, R), dtype=torch.float32, device=dev)
+        sizes = torch.zeros((nq,), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()                     # inputs and the zero fills are complete before the call
+        return keys, vals, sizes
+
+    def search_device(self, queries, ma, R, table_form=2, sum_mode=1):
+        """queries: float32 tensor [nq][dim] on the index's device -> tensors (keys int32 [nq][R] carrying the uint32 bits,
+        vals float32 [nq][R], sizes int32 [nq]) on that device: search()'s heap arrays, finished on the GPU; no host copy."""
+        if getattr(queries, "ndim", 0) != 2:
+            raise TypeError("queries must be a 2-d torch.Tensor")
+        nq = int(queries.shape[0])
+        q = self._device_tensor(queries, (nq, getattr(self, "dim", int(queries.shape[1]))), "queries")
+        keys, vals, sizes = self._device_outputs(nq, int(R))
+        _check(lib().qadc_adc_search_device(self._h, nq, q.data_ptr(), ma, R, table_form, sum_mode, keys.data_ptr(), vals.data_ptr(),
+                                            sizes.data_ptr()))
+        return keys, vals, sizes
+
+    def query_scan_device(self, assign, tables, R, sum_mode=1):
+        """assign [nq][ma] (host), tables: float32 tensor [nq][ma][sq_count*256] on the index's device -> tensors (keys, vals,
+        sizes) as search_device: query_scan()'s heap arrays without the upload of the tables."""
+        assign = np.ascontiguousarray(assign, np.int32)
+        if assign.ndim == 1:
+            assign = assign.reshape(1, -1)
+        nq, ma = assign.shape
+        t = self._device_tensor(tables, (nq, ma, self.sq_count * 256), "tables")
+        keys, vals, sizes = self._device_outputs(nq, int(R))
+        _check(lib().qadc_adc_query_scan_device(self._h, nq, ma, _p(assign, i32p), t.data_ptr(), R, sum_mode, keys.data_ptr(),
+                                                vals.data_ptr(), sizes.data_ptr()))
+        return keys, vals, sizes

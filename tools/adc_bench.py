@@ -7,13 +7,17 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
   batch32   32 queries per call on the same list
   lone1e6   the synchronous call-to-return time of one query on a 10^6-code flat list (SIFT1M shape)
   ivf       10^6 codes in K = 256 partitions, ma = 24, 1024 queries per call; the call includes the upload of the
-            1024 x 24 float tables (8 KiB each)
+            1024 x 24 float tables (8 KiB each).  With torch: alternated with query_scan_device on the same tables left in
+            device memory (a torch tensor; heaps stay on the device), asserted equal
   cpu       the CPU scan_standard<uint8_t, 8> (the oracle's C restatement, and the reference's own build where it was
             compiled into oracle/_ref) on the 10^6-code list, one thread
   ivf_search   the ivf shape on real geometry: 10^6 clustered 128-d vectors encoded by adc_encode, K = 256, ma = 24, 1024 queries.
             Arm A = query_scan(assign, tables) with the assign and tables arm B's feeders produce (201 MB uploaded in the
             call); arm B = search(queries): coarse assignment and tables on the GPU.  The arms alternate in one process.
-  lone_search  one synchronous search() of one query at that shape, beside one CPU thread scanning the same 24 partitions
+            Then arm B again (host finish) alternated with arm C = the same search() under set_finish(1), the device finish,
+            asserted equal, and the same pair at 1, 8, 32, 128 and 1024 queries per call.
+  lone_search  one synchronous search() of one query at that shape under the host finish and, alternated with it and asserted
+            equal, under the device finish, beside one CPU thread scanning the same 24 partitions
 Every time is a host clock around whole synchronous calls (median of --iters after warm-up); R = 100, sum_mode 1."""
 import argparse
 import json
@@ -62,6 +66,21 @@ def alternated(fa, fb, iters, warmup=2):
     return float(np.median(ta)), float(np.median(tb))
 
 
+def with_finish(idx, mode, fn):
+    """fn() under finish `mode`, the default (host) restored"""
+    def run():
+        idx.set_finish(mode)
+        try:
+            return fn()
+        finally:
+            idx.set_finish(0)
+    return run
+
+
+def same_heaps(a, b):
+    return all(np.array_equal(np.asarray(x).view(np.uint32), np.asarray(y).view(np.uint32)) for x, y in zip(a[:3], b[:3]))
+
+
 def search_legs(legs, iters, res):
     """10^6 clustered vectors, encoded and partitioned on the GPU: the feeders of search() against caller-made tables"""
     rng = np.random.default_rng(1)
@@ -101,11 +120,33 @@ def search_legs(legs, iters, res):
         print("IVF on encoded vectors, K=256 ma=24, 1024 queries/call: A query_scan(assign, tables) with %.0f MB uploaded %.2f ms;"
               " B search(queries) %.2f ms = %.1f us/query; B / A = %.3f"
               % (tables.nbytes / 1e6, med_a * 1e3, med_b * 1e3, med_b * 1e6 / nq, med_b / med_a), flush=True)
+        sweep = {}
+        for n in (1, 8, 32, 128, nq):
+            qs = queries[:n]
+            host = lambda: idx.search(qs, ma, R)
+            dev = with_finish(idx, 1, host)
+            assert same_heaps(host(), dev()), "host and device finish disagree at %d queries" % n
+            med_h, med_d = alternated(host, dev, max(5, iters) if n == nq else max(20, iters))
+            sweep[str(n)] = [med_h * 1e3, med_d * 1e3]
+            print("search() of %d queries: host finish %.3f ms, device finish %.3f ms (device / host = %.3f)"
+                  % (n, med_h * 1e3, med_d * 1e3, med_d / med_h), flush=True)
+        res["ivf_search_host_finish_ms"] = sweep[str(nq)][0]
+        res["ivf_search_device_finish_ms"] = sweep[str(nq)][1]
+        res["ivf_search_device_over_host_finish"] = sweep[str(nq)][1] / sweep[str(nq)][0]
+        res["ivf_search_finish_sweep_ms_host_device"] = sweep
+        res["ivf_search_host_finishes"] = int(idx.host_finishes())
     if "lone_search" in legs:
         q1 = queries[:1]
         med, best = timed(lambda: idx.search(q1, ma, R), max(iters, 50), warmup=5)
         res["lone_search_call_us"] = med * 1e6
         print("one synchronous search() of one query, K=256 ma=24 on 10^6 codes: %.1f us (best %.1f)" % (med * 1e6, best * 1e6), flush=True)
+        host = lambda: idx.search(q1, ma, R)
+        dev = with_finish(idx, 1, host)
+        assert same_heaps(host(), dev()), "host and device finish disagree on the lone query"
+        med_h, med_d = alternated(host, dev, max(iters, 50), warmup=5)
+        res["lone_search_host_finish_us"] = med_h * 1e6
+        res["lone_search_device_finish_us"] = med_d * 1e6
+        print("the same alternated: host finish %.1f us, device finish %.1f us" % (med_h * 1e6, med_d * 1e6), flush=True)
         import pyoracle as po
         a1, t1 = idx.search_tables(q1, ma)
         pp, ll = [parts[k] for k in a1[0]], [labels[k] for k in a1[0]]
@@ -125,6 +166,13 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     legs = a.legs.split(",")
+    torch = None
+    if "ivf" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+        try:
+            import torch
+            torch.zeros(1, device="cuda")
+        except Exception:
+            torch = None
     rng = np.random.default_rng(0)
     res = {"R": R, "sum_mode": 1, "cpus_allowed": len(os.sched_getaffinity(0))}
 
@@ -194,6 +242,19 @@ def main():
         res["ivf_codes_probed_per_call"] = int(probed)
         print("IVF K=256 ma=24, 1024 queries/call (with %.0f MB of float tables uploaded): %.2f ms = %.1f us/query"
               % (tb.nbytes / 1e6, med * 1e3, med * 1e6 / nq), flush=True)
+        if torch is not None:
+            d_tb = torch.from_numpy(tb).cuda()
+            torch.cuda.synchronize()
+            host = lambda: idx.query_scan(assign, tb, R)
+            dev = lambda: idx.query_scan_device(assign, d_tb, R)
+            got = dev()
+            got = (got[0].cpu().numpy(), got[1].cpu().numpy(), got[2].cpu().numpy())
+            assert same_heaps(host(), got), "query_scan and query_scan_device disagree"
+            med_h, med_d = alternated(host, dev, max(3, a.iters // 2), warmup=1)
+            res["ivf_query_scan_upload_ms"] = med_h * 1e3
+            res["ivf_query_scan_device_ms"] = med_d * 1e3
+            print("the same alternated with query_scan_device (tables and heaps stay in device memory): %.2f ms against %.2f ms"
+                  % (med_d * 1e3, med_h * 1e3), flush=True)
         idx.close()
     if "ivf_search" in legs or "lone_search" in legs:
         search_legs(legs, a.iters, res)

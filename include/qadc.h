@@ -64,6 +64,7 @@ const char* qadc_stream_layout(int device_id);
 
 /* M = 16 or 32 sub-quantizers of 4 bits (get_simd_scan_func_epi8, db_query_4.cpp:22-35). */
 int qadc_index_create(qadc_index** out, int M, int device_id);
+/* QADC_E_ARG, the index left intact, while a float-ADC view of it is alive (qadc_adc_index_create_view): destroy the views first. */
 int qadc_index_destroy(qadc_index* idx);
 
 /* Append partitions given as base_db::get_partition() yields them (databases.hpp:50-55):
@@ -489,8 +490,11 @@ int qadc_index_set_split(qadc_index* idx, uint64_t min_codes, uint64_t min_run);
 int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6);
 
 /* ---------------------------------------------------------------------------------------------
- * Float ADC over whole-byte PQ codes — the reference's OTHER query front end, db_query's plain
- * scanner_simple (db_query.cpp:17-46) with scan_standard<uint8_t, NSQ> (query_common.hpp:92-146).
+ * Float ADC — the reference's OTHER query front end, db_query's plain scanner_simple
+ * (db_query.cpp:17-46): over whole-byte PQ codes with scan_standard<uint8_t, NSQ>
+ * (query_common.hpp:92-146) in a database of its own (qadc_adc_index_create), and over the 4-bit
+ * codes of a qadc_index with scan_4<M> (query_common.hpp:59-90) as a VIEW of that index
+ * (qadc_adc_index_create_view), which reads the index's partitions in place.
  * A separate engine: it shares no state or option with qadc_index above.  Float tables come from
  * the caller, as scanner_simple receives them (qadc_adc_query_scan*), or are built on the GPU from
  * query vectors (qadc_adc_search*).  Candidates are summed in the grouping of the reference as
@@ -510,10 +514,29 @@ int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6);
 typedef struct qadc_adc_index qadc_adc_index;
 
 /* scanner_simple::prepare_database + get_scan_func (db_query.cpp:21-24, query_common.hpp:120-146): sq_bits 8 with
- * sq_count 4, 8 or 16.  Anything else -> QADC_E_ARG with the reference's list of configurations (the 16-bit and 4-bit
- * ones are the reference's but not this engine's). */
+ * sq_count 4, 8 or 16.  Anything else -> QADC_E_ARG with the reference's list of configurations (the 16-bit ones are the
+ * reference's but not this engine's; a 4-bit database is not uploaded a second time here: see qadc_adc_index_create_view). */
 int qadc_adc_index_create(qadc_adc_index** out, int sq_count, int sq_bits, int device_id);
 int qadc_adc_index_destroy(qadc_adc_index* idx);
+
+/* db_query on the database db_query_4 has open: an ADC index that is a view of the finalized 4-bit index `src` — sq_count = M
+ * (16 or 32), 4 bits, scan_4<M> (query_common.hpp:59-90, 121-125), on src's device, with src's all-or-none labels.  Nothing is
+ * copied: the view snapshots src's partition table (device pointers, sizes, key_base) and its scans read src's codes and
+ * labels where they lie, borrowed partitions (qadc_index_add_partition_device) included.  Keys are the label, else key_base +
+ * position (scan_4's key where key_base is 0).
+ *   src must be finalized (any keep) and hold every partition whole, on one GPU: an unfinalized or a sharded source ->
+ *   QADC_E_ARG, the message says which.
+ *   Every query call takes a view, with tables [nq][ma][M * 16] (table_dim = sq_count * 16): qadc_adc_query_scan, _device,
+ *   _candidates, qadc_adc_index_set_finish, _reruns, _host_finishes, _set_table_budget; sum_mode 1 is scan_4's grouping as
+ *   compiled, 0 its source order.  The qadc_adc_search* calls run src's quantizers (qadc_index_set_pq / _set_rotation /
+ *   _set_coarse, codebooks [M][16][dim / M]) as they stand at the call, with the call's table_form and sum_mode; no set_pq on
+ *   src -> QADC_E_ARG.  The table budget counts M * 16 * 4 bytes per (query, probe).
+ *   qadc_adc_index_add_partitions, _set_pq, _set_rotation and _set_coarse on a view -> QADC_E_ARG.
+ *   Lifetime: src counts its views.  qadc_index_destroy(src) with a live view -> QADC_E_ARG, src stays intact;
+ *   qadc_adc_index_destroy of the view releases the count and frees only the view's own buffers.  Partitions added to src
+ *   after the view was created are not seen by it.
+ * A view's calls run on the view's own stream and touch no slot, option or profile of src. */
+int qadc_adc_index_create_view(qadc_adc_index** out, qadc_index* src);
 
 /* Append partitions as base_db::get_partition() yields them (databases.hpp:50-55): row-major codes [sizes[p]][sq_count],
  * labels[p] = u32[sizes[p]] or labels == NULL (key = position inside the partition, as scan_standard keys).  All-or-none

@@ -14,6 +14,12 @@
 // The tables of a call come from the caller (qadc_adc_query_scan*) or are built on the device from query vectors
 // (qadc_adc_search*: coarse assignment, residual, OPQ rotation, tables — what nns_engine(_batch)::process_query does before
 // query_scan, query_common.hpp:194-213, 283-297); both share everything after the tables are in device memory.
+//
+// A VIEW (qadc_adc_index_create_view) is the same engine over the 4-bit codes of a finalized
+// qadc_index — db_query's scan_4<M> (query_common.hpp:59-90) on the database db_query_4 has resident.  It owns no codes: it
+// snapshots the index's partition table, scans with adc_scan4_kernel (tables [M][16]) and, for the search calls, runs the
+// index's quantizers (FeederState) through launch_coarse_assign and launch_build_tables on its own stream.  Levels, bounds,
+// regions, re-runs and both finishes are the ones above, unchanged: nothing in them depends on how a candidate is summed.
 #include "../../include/qadc.h"
 
 #include <hip/hip_runtime.h>
@@ -60,6 +66,11 @@ struct DeviceGuard {
 
 struct qadc_adc_index {
     int nsq = 0, device = 0;
+    int centroids = 256;                            // per sub-quantizer: a table is [nsq][centroids] floats (16: a view)
+    // A view (qadc_adc_index_create_view): the 4-bit index whose partitions, labels and quantizers it reads in place, counted
+    // in src->adc_views, and the partition table the nibble kernel takes — a snapshot of src->parts at creation.
+    qadc_index* src = nullptr;
+    DevBuf<qadc::adc::Part4> d_parts4;
     hipStream_t stream = nullptr;
     int labeled = -1;                               // unknown until the first non-empty add
     std::vector<uint32_t> sizes;
@@ -207,7 +218,7 @@ int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const
     for (int q = 0; q < nq; ++q) cap[q] = (uint32_t)std::max<uint64_t>(1, std::min(total[q], expect));
 
     // one upload: bound (FLT_MAX) | count (0) | region sizes | region bases | assign | items | tables
-    const size_t table_floats = (size_t)idx->nsq * 256;
+    const size_t table_floats = (size_t)idx->nsq * idx->centroids;
     const size_t o_count = align_up((size_t)nq * 4, 256);
     const size_t o_cap = o_count + align_up((size_t)nq * 4, 256);
     const size_t o_base = o_cap + align_up((size_t)nq * 4, 256);
@@ -258,8 +269,12 @@ int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const
         HIPCHECK(idx->d_sidx.ensure(entries));
         const qadc::adc::Emit emit{d_count, idx->d_vals.p, idx->d_keys.p, idx->d_sidx.p, d_base, d_cap};
         for (int l = 0; l < levels; ++l) {
-            HIPCHECK(qadc::adc::launch_adc_scan(idx->nsq, sum_mode, d_items, level_first[l], level_first[l + 1] - level_first[l], db,
-                                                d_assign, ma, d_tables, d_bound, emit, idx->stream));
+            if (idx->src)
+                HIPCHECK(qadc::adc::launch_adc_scan4(idx->nsq, sum_mode, d_items, level_first[l], level_first[l + 1] - level_first[l],
+                                                     idx->d_parts4.p, d_assign, ma, d_tables, d_bound, emit, idx->stream));
+            else
+                HIPCHECK(qadc::adc::launch_adc_scan(idx->nsq, sum_mode, d_items, level_first[l], level_first[l + 1] - level_first[l], db,
+                                                    d_assign, ma, d_tables, d_bound, emit, idx->stream));
             if (l + 1 < levels) HIPCHECK(qadc::adc::launch_adc_select(nq, R, emit, d_bound, idx->stream));
         }
         HIPCHECK(idx->h_count.ensure(nq));
@@ -385,9 +400,27 @@ int copy_stream(qadc_adc_index* idx, int nq, uint64_t cand_capacity, uint32_t* c
 
 constexpr int kCoarseChunk = 32768;   // queries per coarse-assignment pass (the distance scratch is chunk x K floats)
 
+// A view takes its quantizers from its source as they stand when the call is made.
+void bind_source_feeders(qadc_adc_index* idx) {
+    if (!idx || !idx->src) return;
+    const FeederState& f = idx->src->feed;
+    idx->dim = f.dim;
+    idx->K = f.K;
+    idx->rotated = f.has_rotation;
+}
+
+int refuse_on_view(const qadc_adc_index* idx, const char* call) {
+    if (idx && idx->src)
+        return fail(QADC_E_ARG, std::string(call) + ": the index is a view of a 4-bit index and takes its database and its quantizers from "
+                                                    "that index (qadc_index_add_partitions, qadc_index_set_pq / _set_rotation / _set_coarse)");
+    return QADC_OK;
+}
+
 int check_search_args(const qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
-    if (!idx->dim) return fail(QADC_E_ARG, "qadc_adc_index_set_pq has not been called: the index has no codebooks");
+    if (!idx->dim)
+        return fail(QADC_E_ARG, idx->src ? "qadc_index_set_pq has not been called on the view's source index: it has no codebooks"
+                                         : "qadc_adc_index_set_pq has not been called: the index has no codebooks");
     if (nq < 1 || ma < 1 || ma >= 16384 || !queries) return fail(QADC_E_ARG, "need queries, nq >= 1 and 1 <= ma < 16384");
     if (table_form < 0 || table_form > 2) return fail(QADC_E_ARG, "table_form is 0 (direct), 1 (BLAS expansion) or 2 (nns_engine's rule)");
     if (sum_mode != 0 && sum_mode != 1) return fail(QADC_E_ARG, "sum_mode is 0 (source order) or 1 (as compiled)");
@@ -417,14 +450,20 @@ int enqueue_assign(qadc_adc_index* idx, int nq, const float* queries, int ma, in
         HIPCHECK(hipMemcpyAsync(idx->d_queries.p, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice, idx->stream));
         idx->cur_queries = idx->d_queries.p;
     }
+    const float* coarse = idx->src ? idx->src->feed.d_coarse.p : idx->d_coarse.p;
+    if (idx->K && idx->src) {   // ||c||^2 of the source's centroids under this call's sum_mode (the source may have replaced them)
+        HIPCHECK(idx->d_cnorm.ensure((size_t)idx->K));
+        qadc::launch_row_sqnorm(coarse, idx->K, dim, sum_mode, idx->d_cnorm.p, idx->stream);
+    }
+    const float* cnorm = idx->src ? idx->d_cnorm.p : idx->d_cnorm.p + (size_t)sum_mode * idx->K;
     if (idx->K) {
         const int chunk = std::min(nq, kCoarseChunk);
         HIPCHECK(idx->d_cdist.ensure((size_t)chunk * idx->K));
         HIPCHECK(idx->d_qnorm.ensure(chunk));
         if (ma > 256) HIPCHECK(qadc::coarse_nan_unreplayed_reset(idx->stream));
         for (int o = 0; o < nq; o += kCoarseChunk)
-            qadc::launch_coarse_assign(idx->cur_queries + (size_t)o * dim, idx->d_coarse.p, std::min(kCoarseChunk, nq - o), idx->K, dim, ma,
-                                       idx->d_qnorm.p, idx->d_cnorm.p + (size_t)sum_mode * idx->K, sum_mode, idx->d_cdist.p,
+            qadc::launch_coarse_assign(idx->cur_queries + (size_t)o * dim, coarse, std::min(kCoarseChunk, nq - o), idx->K, dim, ma,
+                                       idx->d_qnorm.p, cnorm, sum_mode, idx->d_cdist.p,
                                        idx->d_assign.p + (size_t)o * ma, idx->stream);
         HIPCHECK(hipGetLastError());
     } else {
@@ -450,6 +489,14 @@ int wait_assign(qadc_adc_index* idx, int ma) {
 
 int enqueue_tables(qadc_adc_index* idx, int q0, int nq, int ma, int table_form, int sum_mode) {
     const int expansion = table_form == 2 ? (ma > 1) : table_form;   // nns_engine: direct for ma == 1 (query_common.hpp:292-297)
+    if (idx->src) {   // a view: the 16-centroid builder of the 4-bit index on the source's quantizers, [nq][ma][M][16]
+        const FeederState& f = idx->src->feed;
+        qadc::launch_build_tables(idx->cur_queries + (size_t)q0 * idx->dim, idx->K ? f.d_coarse.p : nullptr, idx->d_assign.p + (size_t)q0 * ma,
+                                  f.d_codebooks.p, idx->rotated ? f.d_rotation.p : nullptr, nq, ma, idx->nsq, idx->dim, expansion, sum_mode,
+                                  idx->d_tables.p, idx->stream);
+        HIPCHECK(hipGetLastError());
+        return QADC_OK;
+    }
     HIPCHECK(qadc::adc::launch_adc_tables(idx->cur_queries + (size_t)q0 * idx->dim, idx->K ? idx->d_coarse.p : nullptr,
                                           idx->d_assign.p + (size_t)q0 * ma, idx->d_codebooks.p,
                                           idx->d_cbnorm.p + (size_t)sum_mode * idx->nsq * 256, idx->rotated ? idx->d_rotation.p : nullptr, nq, ma,
@@ -459,7 +506,7 @@ int enqueue_tables(qadc_adc_index* idx, int q0, int nq, int ma, int table_form, 
 
 // queries per sub-batch: whole queries whose tables fit the budget, at least one
 int queries_per_pass(const qadc_adc_index* idx, int nq, int ma) {
-    const uint64_t per_query = (uint64_t)ma * idx->nsq * 256 * 4;
+    const uint64_t per_query = (uint64_t)ma * idx->nsq * idx->centroids * 4;
     return (int)std::min<uint64_t>((uint64_t)nq, std::max<uint64_t>(1, idx->table_budget / per_query));
 }
 
@@ -468,11 +515,12 @@ int queries_per_pass(const qadc_adc_index* idx, int nq, int ma) {
 // are in device memory.
 int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, int32_t* assign_out,
                  const DeviceOut* out = nullptr, bool d_side = false) {
+    bind_source_feeders(idx);
     if (int rc = check_search_args(idx, nq, queries, ma, table_form, sum_mode)) return rc;
     if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
     HIPCHECK(hipSetDevice(idx->device));
     const int per = queries_per_pass(idx, nq, ma);
-    HIPCHECK(idx->d_tables.ensure((size_t)per * ma * idx->nsq * 256));
+    HIPCHECK(idx->d_tables.ensure((size_t)per * ma * idx->nsq * idx->centroids));
     if (int rc = enqueue_assign(idx, nq, queries, ma, sum_mode, d_side)) return rc;
     if (int rc = enqueue_tables(idx, 0, per, ma, table_form, sum_mode)) return rc;   // (runs while the host plans the first scan)
     if (int rc = wait_assign(idx, ma)) return rc;
@@ -588,11 +636,54 @@ int qadc_adc_index_create(qadc_adc_index** out, int sq_count, int sq_bits, int d
     return QADC_OK;
 }
 
+int qadc_adc_index_create_view(qadc_adc_index** out, qadc_index* src) {
+    if (!out) return fail(QADC_E_ARG, "out is null");
+    *out = nullptr;
+    if (!src) return fail(QADC_E_ARG, "the source index is null");
+    if (!src->finalized) return fail(QADC_E_ARG, "the source index is not finalized: call qadc_index_finalize before creating a view");
+    if (src->dist) return fail(QADC_E_ARG, "the source index takes part in a multi-GPU merge: a view reads an index that lives on one GPU");
+    for (size_t p = 0; p < src->parts.size(); ++p) {
+        const Part& pt = src->parts[p];
+        if (pt.n != pt.global_n || pt.first_pos != 0 || pt.d_starts)
+            return fail(QADC_E_ARG, "the source index is sharded: partition " + std::to_string(p) + " holds " + std::to_string(pt.n) + " of its " +
+                                        std::to_string(pt.global_n) + " codes here; a view needs every partition whole");
+    }
+    DeviceGuard guard;
+    if (int rc = qadc_device_prepare(src->device)) return rc;
+    HIPCHECK(hipSetDevice(src->device));
+    qadc_adc_index* idx = new qadc_adc_index();
+    idx->nsq = src->M;
+    idx->centroids = 16;
+    idx->device = src->device;
+    idx->labeled = src->labeled;
+    std::vector<qadc::adc::Part4> table(src->parts.size());
+    for (size_t p = 0; p < src->parts.size(); ++p) {
+        const Part& pt = src->parts[p];
+        idx->sizes.push_back(pt.n);
+        table[p] = qadc::adc::Part4{pt.d_codes, src->labeled == 1 ? pt.d_labels : nullptr, pt.key_base, 0};
+    }
+    hipError_t e = hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&idx->ev_assign, hipEventDisableTiming);
+    if (e == hipSuccess) e = idx->d_parts4.ensure(std::max<size_t>(table.size(), 1));
+    if (e == hipSuccess && !table.empty())
+        e = hipMemcpy(idx->d_parts4.p, table.data(), table.size() * sizeof(qadc::adc::Part4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)qadc_adc_index_destroy(idx);
+        return fail(QADC_E_HIP, std::string("qadc_adc_index_create_view: ") + hipGetErrorString(e));
+    }
+    idx->src = src;     // (only now: a failed creation above releases no count)
+    ++src->adc_views;
+    *out = idx;
+    return QADC_OK;
+}
+
 int qadc_adc_index_destroy(qadc_adc_index* idx) {
     if (!idx) return QADC_OK;
     DeviceGuard guard;
     (void)hipSetDevice(idx->device);
     if (idx->stream) (void)hipStreamSynchronize(idx->stream);
+    if (idx->src) --idx->src->adc_views;   // the view's scans are over: the source may be destroyed again
+    idx->d_parts4.release();
     idx->codes.release();
     idx->labels.release();
     idx->d_off.release();
@@ -632,6 +723,7 @@ int qadc_adc_index_destroy(qadc_adc_index* idx) {
 int qadc_adc_index_add_partitions(qadc_adc_index* idx, int part_count, const uint8_t* const* codes, const uint32_t* const* labels,
                                   const uint32_t* sizes) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (int rc = refuse_on_view(idx, "qadc_adc_index_add_partitions")) return rc;
     if (part_count < 0 || (part_count > 0 && (!codes || !sizes))) return fail(QADC_E_ARG, "bad partition arrays");
     DeviceGuard guard;
     HIPCHECK(hipSetDevice(idx->device));
@@ -735,6 +827,7 @@ int qadc_adc_query_scan_candidates(qadc_adc_index* idx, int nq, int ma, const in
 
 int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks) {
     if (!idx || !codebooks) return fail(QADC_E_ARG, "index or codebooks is null");
+    if (int rc = refuse_on_view(idx, "qadc_adc_index_set_pq")) return rc;
     if (dim < 1 || dim % idx->nsq != 0)
         return fail(QADC_E_ARG, "dim = " + std::to_string(dim) + " is not a multiple of sq_count = " + std::to_string(idx->nsq));
     if (dim > qadc::adc::kAdcMaxDim) return fail(QADC_E_ARG, "dim must be <= " + std::to_string(qadc::adc::kAdcMaxDim));
@@ -758,6 +851,7 @@ int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks) 
 
 int qadc_adc_index_set_rotation(qadc_adc_index* idx, const float* rotation) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (int rc = refuse_on_view(idx, "qadc_adc_index_set_rotation")) return rc;
     if (!idx->dim) return fail(QADC_E_ARG, "qadc_adc_index_set_pq comes first: the rotation is [dim][dim]");
     if (!rotation) {
         idx->rotated = false;
@@ -774,6 +868,7 @@ int qadc_adc_index_set_rotation(qadc_adc_index* idx, const float* rotation) {
 
 int qadc_adc_index_set_coarse(qadc_adc_index* idx, int K, const float* centroids) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (int rc = refuse_on_view(idx, "qadc_adc_index_set_coarse")) return rc;
     if (!idx->dim) return fail(QADC_E_ARG, "qadc_adc_index_set_pq comes first: the centroids are [K][dim]");
     if (K < 0 || (K > 0 && !centroids)) return fail(QADC_E_ARG, "need K >= 1 centroids (K = 0: a flat index)");
     if (K == 0) {
@@ -835,10 +930,11 @@ int qadc_adc_search_candidates(qadc_adc_index* idx, int nq, const float* queries
 int qadc_adc_search_tables(qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode, int32_t* assign_out,
                            float* tables_out) {
     DeviceGuard guard;
+    bind_source_feeders(idx);
     if (int rc = check_search_args(idx, nq, queries, ma, table_form, sum_mode)) return rc;
     HIPCHECK(hipSetDevice(idx->device));
     const int per = queries_per_pass(idx, nq, ma);
-    const size_t per_query = (size_t)ma * idx->nsq * 256;
+    const size_t per_query = (size_t)ma * idx->nsq * idx->centroids;
     HIPCHECK(idx->d_tables.ensure((size_t)per * per_query));
     if (int rc = enqueue_assign(idx, nq, queries, ma, sum_mode)) return rc;
     if (int rc = wait_assign(idx, ma)) return rc;

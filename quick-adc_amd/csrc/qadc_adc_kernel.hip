@@ -4,7 +4,8 @@
 //   adc_scan_kernel    one workgroup per run of codes of one probed partition: the (query, slot) float table [NSQ][256]
 //                      goes to LDS, each lane sums the NSQ looked-up entries of its codes in the reference's grouping and
 //                      emits (candidate, key, scan index) when candidate < bound[query];
-//   adc_select_kernel  one workgroup per query: bound = the R-th smallest value the query emitted so far (radix select on
+//   adc_scan4_kernel   the same over the nibble codes of a 4-bit index read in place (scan_4<M>, tables [M][16]): the view;
+//   adc_select_kernel one workgroup per query: bound = the R-th smallest value the query emitted so far (radix select on
 //                      the order-preserving integer image of the floats), the bound of the next level's runs;
 //   adc_pack_kernel    the per-query regions packed densely for one device-to-host copy;
 //   adc_order_kernel   the device finish: each query's stored candidates put in scan order (LDS sort, or radix passes through
@@ -112,6 +113,67 @@ __global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ 
                 const size_t at = region + o;
                 emit.vals[at] = v;
                 emit.keys[at] = labels ? labels[it.start + r] : it.start + r;
+                emit.sidx[at] = it.sbase + r;
+            }
+        }
+    }
+}
+
+// The nibble form: scan_4<M> (query_common.hpp:59-90) over the partitions of a 4-bit index, read in place.  A code is
+// M/2 bytes = one dwordx2 (M 16) or dwordx4 (M 32) load; sub-quantizer m's entry is table[m][nibble m], nibble m = bits
+// 4(m % 8) .. of word m / 8 (the even sub-quantizer in the low nibble of its byte).  The (query, slot) table [M][16] is 1 or
+// 2 KiB of LDS.  Every lane of a wave reads sub-quantizer m in the same instruction: its 16 entries lie in 16 distinct
+// banks and equal addresses broadcast, so the lookups cannot conflict.  Same Item / Emit contract as adc_scan_kernel.
+template <int M, int SUM>
+__device__ __forceinline__ float candidate4(const float* lds, const CodeWords<M / 2>& c) {
+    float v[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) v[m] = lds[m * 16 + ((c.w[m / 8] >> (4 * (m % 8))) & 15u)];
+    return adc_sum_code<M>(v, SUM, 0.0f);
+}
+
+template <int M, int SUM>
+__global__ __launch_bounds__(kWG) void adc_scan4_kernel(const Item* __restrict__ items, uint32_t first,
+                                                        const Part4* __restrict__ parts, const int32_t* __restrict__ assign,
+                                                        int ma, const float* __restrict__ tables,
+                                                        const float* __restrict__ bound, Emit emit) {
+    constexpr int CS = M / 2;
+    __shared__ float lds[M * 16];
+    const Item it = items[first + blockIdx.x];
+    const Part4 part = parts[assign[(size_t)it.query * ma + it.slot]];
+    const float4* tab = reinterpret_cast<const float4*>(tables + ((size_t)it.query * ma + it.slot) * (M * 16));
+    for (int i = threadIdx.x; i < M * 4; i += kWG) reinterpret_cast<float4*>(lds)[i] = tab[i];
+    const float b = bound[it.query];
+    const uint64_t region = emit.base[it.query];
+    const uint32_t cap = emit.cap[it.query];
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1;
+    for (uint32_t base = 0; base < it.count; base += kWG * kUnroll) {
+        CodeWords<CS> c[kUnroll];
+        bool valid[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const uint32_t r = base + u * kWG + threadIdx.x;
+            valid[u] = r < it.count;
+            if (valid[u]) c[u] = load_code<CS>(part.codes + (size_t)(it.start + r) * CS);
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const float v = valid[u] ? candidate4<M, SUM>(lds, c[u]) : 0.0f;
+            const bool keep = valid[u] && v < b;                  // NaN, +inf and FLT_MAX never pass (b <= FLT_MAX)
+            const unsigned long long m = __ballot(keep);
+            if (m == 0) continue;
+            const int leader = __builtin_ctzll(m);
+            uint32_t o = 0;
+            if (lane == leader) o = atomicAdd(emit.count + it.query, (uint32_t)__popcll(m));
+            o = __shfl(o, leader) + (uint32_t)__popcll(m & below);
+            if (keep && o < cap) {
+                const uint32_t r = base + u * kWG + threadIdx.x;
+                const size_t at = region + o;
+                emit.vals[at] = v;
+                emit.keys[at] = part.labels ? part.labels[it.start + r] : part.key_base + it.start + r;
                 emit.sidx[at] = it.sbase + r;
             }
         }
@@ -573,6 +635,20 @@ hipError_t launch_adc_scan(int nsq, int sum_mode, const Item* items, uint32_t fi
                             : launch_scan_t<16, 1>(items, first, n_items, db, assign, ma, tables, bound, emit, s);
         default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_adc_scan4(int M, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const Part4* parts,
+                            const int32_t* assign, int ma, const float* tables, const float* bound, Emit emit, hipStream_t s) {
+    if (n_items == 0) return hipSuccess;
+#define QADC_S4(MM, SUM) hipLaunchKernelGGL((adc_scan4_kernel<MM, SUM>), dim3(n_items), dim3(kWG), 0, s, items, first, parts, assign, ma, \
+                                            tables, bound, emit)
+    if (M == 16 && sum_mode == 0) QADC_S4(16, 0);
+    else if (M == 16) QADC_S4(16, 1);
+    else if (M == 32 && sum_mode == 0) QADC_S4(32, 0);
+    else if (M == 32) QADC_S4(32, 1);
+    else return hipErrorInvalidValue;
+#undef QADC_S4
+    return hipGetLastError();
 }
 
 hipError_t launch_adc_select(int nq, int R, Emit emit, float* bound, hipStream_t s) {

@@ -40,6 +40,18 @@ struct Db {
 // Scans items [first, first + n_items): emits (candidate, key, scan index) for every code with candidate < bound[query].
 hipError_t launch_adc_scan(int nsq, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, Db db, const int32_t* assign,
                            int ma, const float* tables, const float* bound, Emit emit, hipStream_t s);
+// A 4-bit database read where a qadc_index keeps it (the view of qadc_adc_index_create_view): every partition is an
+// allocation of its own, row-major [n][M/2], 16-byte aligned; key = labels[position], else key_base + position.
+struct Part4 {
+    const uint8_t* codes;
+    const uint32_t* labels;   // nullptr: unlabelled
+    uint32_t key_base;
+    uint32_t pad;
+};
+// launch_adc_scan for nibble codes, scan_4<M> (query_common.hpp:59-90), M 16 or 32: the same items, bounds and Emit; tables
+// [nq][ma][M][16], summed as adc_sum_code<M> (csrc/qadc_float_sum.h).
+hipError_t launch_adc_scan4(int M, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const Part4* parts,
+                            const int32_t* assign, int ma, const float* tables, const float* bound, Emit emit, hipStream_t s);
 // bound[q] = min(bound[q], the R-th smallest of the values query q has stored so far) where it stored at least R.
 hipError_t launch_adc_select(int nq, int R, Emit emit, float* bound, hipStream_t s);
 // Packs the stored records of every query densely in query order: record sum_{j<q} stored_j + i of `out` = three words

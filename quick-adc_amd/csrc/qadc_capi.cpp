@@ -1351,6 +1351,9 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
 
 int qadc_index_destroy(qadc_index* idx) {
     if (!idx) return QADC_OK;
+    if (idx->adc_views > 0)   // a freed partition under a view's running scan would be a GPU fault
+        return fail(QADC_E_ARG, "the index has " + std::to_string(idx->adc_views) + " live float-ADC view(s) (qadc_adc_index_create_view): "
+                                "destroy them first; the index is intact");
     (void)hipSetDevice(idx->device);
     // a pre-scan (front stream) or an on-demand copy may still be in flight: drain all four streams before freeing
     for (hipStream_t st : {idx->stream, idx->wgq_stream, idx->front_stream, idx->copy_stream, idx->sort_stream})

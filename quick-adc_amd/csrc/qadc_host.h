@@ -449,6 +449,8 @@ struct qadc_index {
     FeederState feed;                   // qadc_ivf.cpp: N1, the feeders on the device
     GroupState group;                   // qadc_ivf.cpp: partition-major second phase of large IVF batches
     DistState* dist = nullptr;          // qadc_dist.cpp: qadc_dist_init
+    int adc_views = 0;                  // qadc_adc.cpp: live float-ADC views reading this index's partitions (qadc_adc_index_create_view);
+                                        // qadc_index_destroy refuses while there is one
 };
 
 namespace qadc {

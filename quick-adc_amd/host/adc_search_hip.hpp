@@ -9,7 +9,9 @@
 // after its R sentinel pushes (db_query.cpp:31-33), which leaves it in exactly the state the reference's scan would.
 //   Db:   int partition_count(); void get_partition(int, const std::uint8_t*&, unsigned*&, unsigned&);
 //         int coarse_count(); const float* coarse_centroids();            (0 / nullptr: a flat database)
-//         pq->sq_count, pq->sq_bits, pq->dim, pq->centroids, pq->rotation  (host/scanner_simple.hpp pq_bytes)
+//         pq->sq_count, pq->sq_bits, pq->dim, pq->centroids, pq->rotation  (host/scanner_simple.hpp pq_bytes; query_driver.hpp pq4)
+// 4-bit codes ((16,4) (32,4)): database and quantizers go into a qadc_index, and the engine searches through a view of it
+// (qadc_adc_index_create_view) — the index db_query_4's engine would use, asked the exact float question.
 //   Heap: int capacity(); void push(unsigned, float)                       (kv_binheap<unsigned, float>, binheap.hpp)
 // table_form: 1 = the BLAS-expansion tables nns_engine_batch builds (default), 0 = direct, 2 = nns_engine's rule.
 // set_finish(QADC_ADC_FINISH_DEVICE): the batch's heaps are ordered and replayed on the GPU (qadc_adc_search under
@@ -36,6 +38,7 @@ struct adc_search_engine_hip {
     int finish = QADC_ADC_FINISH_HOST;
     std::vector<std::int32_t> heap_sizes;   // device finish: [batch]; the arrays are in cand_keys / cand_vals [batch][r]
     qadc_adc_index* index;
+    qadc_index* source = nullptr;       // 4-bit codes: the index that holds database and quantizers; `index` is a view of it
     std::vector<std::uint32_t> cand_keys;
     std::vector<float> cand_vals;
     std::vector<std::uint64_t> offsets;
@@ -46,7 +49,10 @@ struct adc_search_engine_hip {
           cand_keys(1 << 16), cand_vals(1 << 16), offsets((std::size_t)batch_ + 1), assign((std::size_t)batch_ * ma_) {}
     adc_search_engine_hip(const adc_search_engine_hip&) = delete;
     adc_search_engine_hip& operator=(const adc_search_engine_hip&) = delete;
-    ~adc_search_engine_hip() { qadc_adc_index_destroy(index); }
+    ~adc_search_engine_hip() {
+        qadc_adc_index_destroy(index);   // (the view first: its source refuses to go while it lives)
+        qadc_index_destroy(source);
+    }
 
     static void die(const char* what) {
         std::cerr << what << ": " << qadc_last_error() << std::endl;
@@ -66,6 +72,10 @@ struct adc_search_engine_hip {
     // scanner_simple::prepare_database (db_query.cpp:21-24) plus the quantizers the feeders need
     void prepare_database() {
         const int m = db.pq->sq_count, bits = db.pq->sq_bits;
+        if (bits == 4 && (m == 16 || m == 32)) {
+            prepare_nibbles(m);
+            return;
+        }
         if (qadc_adc_index_create(&index, m, bits, device) != QADC_OK) die("Cannot create the GPU index");
         if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
         const int part_count = db.partition_count();
@@ -87,6 +97,27 @@ struct adc_search_engine_hip {
         if (!db.pq->rotation.empty() && qadc_adc_index_set_rotation(index, db.pq->rotation.data()) != QADC_OK) die("Cannot set the rotation");
         if (db.coarse_count() > 0 && qadc_adc_index_set_coarse(index, db.coarse_count(), db.coarse_centroids()) != QADC_OK)
             die("Cannot set the coarse centroids");
+    }
+
+    void prepare_nibbles(int m) {
+        if (qadc_index_create(&source, m, device) != QADC_OK) die("Cannot create the GPU index");
+        const int part_count = db.partition_count();
+        for (int part_i = 0; part_i < part_count; ++part_i) {
+            const std::uint8_t* codes;
+            unsigned* lab;
+            unsigned size;
+            db.get_partition(part_i, codes, lab, size);
+            const std::uint32_t* labels = lab;
+            const std::uint32_t sz = size;
+            if (qadc_index_add_partitions(source, 1, &codes, lab ? &labels : nullptr, &sz) != QADC_OK) die("Cannot prepare database");
+        }
+        if (qadc_index_finalize(source, 0.01f) != QADC_OK) die("Cannot prepare database");
+        if (qadc_index_set_pq(source, db.pq->dim, db.pq->centroids.data()) != QADC_OK) die("Cannot set the codebooks");
+        if (!db.pq->rotation.empty() && qadc_index_set_rotation(source, db.pq->rotation.data()) != QADC_OK) die("Cannot set the rotation");
+        if (db.coarse_count() > 0 && qadc_index_set_coarse(source, db.coarse_count(), db.coarse_centroids()) != QADC_OK)
+            die("Cannot set the coarse centroids");
+        if (qadc_adc_index_create_view(&index, source) != QADC_OK) die("Cannot create the view");
+        if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
     }
 
     // nns_engine_batch::process_query (query_common.hpp:194-243): the whole batch is searched when its first query is asked for

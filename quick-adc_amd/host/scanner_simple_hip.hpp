@@ -4,6 +4,8 @@
 // `query_scan(query, assign, ma, tables, table_dim, bh, metrics)`.  This type has the same three, with the same argument
 // meaning and error behaviour (get_scan_func's message + std::exit(1) for a configuration it does not take), and forwards to
 // the float-ADC engine of include/qadc.h (qadc_adc_*): db_query.cpp drops it in by swapping the scanner type.
+// Whole-byte codes ((4,8) (8,8) (16,8)) go into an ADC index of their own; 4-bit codes ((16,4) (32,4), scan_4<M>) go into a
+// qadc_index — the database db_query_4's scanner_hip uses — and are scanned through a view of it (qadc_adc_index_create_view).
 //   Db:   int partition_count(); void get_partition(int, const std::uint8_t*&, unsigned*&, unsigned&);
 //         pq->sq_count, pq->sq_bits                                      (databases.hpp:34-63)
 //   Heap: int capacity(); void push(unsigned, float)                     (kv_binheap<unsigned, float>, binheap.hpp)
@@ -30,16 +32,20 @@ struct scanner_simple_hip {
     typedef Heap BhType;
 
     int device, sum_mode;
-    int table_floats = 0;   // sq_count * 256
+    int table_floats = 0;   // sq_count * 256, or sq_count * 16 for 4-bit codes
     int finish = QADC_ADC_FINISH_HOST;
     qadc_adc_index* index;
+    qadc_index* source = nullptr;   // 4-bit codes: the index that holds the database; `index` is a view of it
     std::vector<std::uint32_t> cand_keys;
     std::vector<float> cand_vals;
 
     explicit scanner_simple_hip(int device_ = 0, int sum_mode_ = 1) : device(device_), sum_mode(sum_mode_), index(nullptr) {}
     scanner_simple_hip(const scanner_simple_hip&) = delete;
     scanner_simple_hip& operator=(const scanner_simple_hip&) = delete;
-    ~scanner_simple_hip() { qadc_adc_index_destroy(index); }
+    ~scanner_simple_hip() {
+        qadc_adc_index_destroy(index);   // (the view first: its source refuses to go while it lives)
+        qadc_index_destroy(source);
+    }
 
     static void die(const char* what) {
         std::cerr << what << ": " << qadc_last_error() << std::endl;
@@ -59,11 +65,16 @@ struct scanner_simple_hip {
     // scanner_simple::prepare_database + get_scan_func (db_query.cpp:21-24, query_common.hpp:120-146)
     void prepare_database(Db& db) {
         const int m = db.pq->sq_count, bits = db.pq->sq_bits;
-        if (bits != 8 || (m != 4 && m != 8 && m != 16)) {   // get_scan_func's message (the 4- and 16-bit ones are not on the GPU)
+        const bool nibbles = bits == 4 && (m == 16 || m == 32);
+        if (!nibbles && (bits != 8 || (m != 4 && m != 8 && m != 16))) {   // get_scan_func's message (the 16-bit ones are not on the GPU)
             std::cerr << "Unsupported (nsq,nsq_bits) configuration." << std::endl;
             std::cerr << "Supported configurations are: (16,4) (4,8) (8,8) (16,8) (2,16) (4,16) (8,16)." << std::endl;
-            std::cerr << "This GPU scanner takes (4,8) (8,8) (16,8)." << std::endl;
+            std::cerr << "This GPU scanner takes (16,4) (32,4) (4,8) (8,8) (16,8)." << std::endl;
             std::exit(1);
+        }
+        if (nibbles) {
+            prepare_nibbles(db, m);
+            return;
         }
         if (qadc_adc_index_create(&index, m, bits, device) != QADC_OK) die("Cannot create the GPU index");
         if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
@@ -86,11 +97,31 @@ struct scanner_simple_hip {
             die("Cannot prepare database");
     }
 
+    // (16,4) and (32,4): the partitions go into a qadc_index, finalized (the pre-scan share is scanner_4's business: any keep
+    // serves), and the scanner is a view of it
+    void prepare_nibbles(Db& db, int m) {
+        if (qadc_index_create(&source, m, device) != QADC_OK) die("Cannot create the GPU index");
+        const int part_count = db.partition_count();
+        for (int part_i = 0; part_i < part_count; ++part_i) {
+            const std::uint8_t* codes;
+            unsigned* lab;
+            unsigned size;
+            db.get_partition(part_i, codes, lab, size);
+            const std::uint32_t* labels = lab;
+            const std::uint32_t sz = size;
+            if (qadc_index_add_partitions(source, 1, &codes, lab ? &labels : nullptr, &sz) != QADC_OK) die("Cannot prepare database");
+        }
+        if (qadc_index_finalize(source, 0.01f) != QADC_OK) die("Cannot prepare database");
+        if (qadc_adc_index_create_view(&index, source) != QADC_OK) die("Cannot create the view");
+        if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
+        table_floats = m * 16;
+    }
+
     // scanner_simple::query_scan (db_query.cpp:26-45).  `query` is unused there too; the tables of the ma probes follow each
-    // other table_dim floats apart, which must be sq_count * 256 (what the engine reads).
+    // other table_dim floats apart, which must be sq_count * 256 (sq_count * 16 for 4-bit codes: what the engine reads).
     void query_scan(const float* /*query*/, int* assign, int ma, float* tables, int table_dim, BhType& bh, Metrics& /*metrics*/) {
         if (table_dim != table_floats) {
-            std::cerr << "query_scan: table_dim " << table_dim << " is not sq_count * 256" << std::endl;
+            std::cerr << "query_scan: table_dim " << table_dim << " is not " << table_floats << " (sq_count * centroids)" << std::endl;
             std::exit(1);
         }
         if (finish == QADC_ADC_FINISH_DEVICE) {   // the heap's arrays from the GPU (bh is empty, as the engines hand it over)

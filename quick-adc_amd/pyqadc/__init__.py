@@ -41,6 +41,7 @@ SYMBOLS = [
     "qadc_adc_index_set_pq", "qadc_adc_index_set_rotation", "qadc_adc_index_set_coarse", "qadc_adc_index_set_table_budget",
     "qadc_adc_search", "qadc_adc_search_candidates", "qadc_adc_search_tables", "qadc_adc_encode_host",
     "qadc_adc_index_set_finish", "qadc_adc_index_host_finishes", "qadc_adc_search_device", "qadc_adc_query_scan_device",
+    "qadc_adc_index_create_view",
 ]
 
 
@@ -161,6 +162,7 @@ def lib():
         L.qadc_profile_reset.argtypes = [C.c_void_p]
         L.qadc_adc_index_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
         L.qadc_adc_index_destroy.argtypes = [C.c_void_p]
+        L.qadc_adc_index_create_view.argtypes = [C.POINTER(C.c_void_p), C.c_void_p]
         L.qadc_adc_index_add_partitions.argtypes = [C.c_void_p, C.c_int, C.POINTER(u8p), C.POINTER(u32p), u32p]
         L.qadc_adc_index_partition_count.argtypes = [C.c_void_p]
         L.qadc_adc_index_partition_size.argtypes = [C.c_void_p, C.c_int]
@@ -404,13 +406,15 @@ class Index:
     def __init__(self, M, device=0):
         self.M = M
         self.cs = M // 2
+        self.device = device
         self._h = C.c_void_p()
         _check(lib().qadc_index_create(C.byref(self._h), M, device))
         self._keepalive = []
 
     def close(self):
+        """Raises QadcError, and leaves the index open, while an AdcIndex.view_of(self) is still open."""
         if self._h:
-            lib().qadc_index_destroy(self._h)
+            _check(lib().qadc_index_destroy(self._h))
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -757,18 +761,51 @@ class Index:
 
 class AdcIndex:
     """One GPU-resident PQ database with whole-byte codes, scanned with float tables: the role of the reference's
-    scanner_simple after prepare_database (db_query.cpp:17-46).  sq_bits 8 with sq_count 4, 8 or 16."""
+    scanner_simple after prepare_database (db_query.cpp:17-46).  sq_bits 8 with sq_count 4, 8 or 16.
+    AdcIndex.view_of(index): the same front end on the 4-bit codes of an Index, read in place (scan_4<M>)."""
 
     def __init__(self, sq_count, sq_bits, device=0):
         self.sq_count = sq_count
+        self.table_dim = sq_count * 256                                  # floats of one (query, probe) table
         self.device = device
+        self._source = None
         self._h = C.c_void_p()
         _check(lib().qadc_adc_index_create(C.byref(self._h), sq_count, sq_bits, device))
+
+    @classmethod
+    def view_of(cls, index):
+        """qadc_adc_index_create_view: an AdcIndex on the partitions of the finalized pyqadc.Index `index`, on its device, M
+        sub-quantizers of 4 bits, tables [nq][ma][M*16].  It copies nothing and keeps `index` referenced;
+        index.close() raises until the view is closed.  The search calls run the quantizers set on `index`."""
+        self = cls.__new__(cls)
+        self.sq_count = index.M
+        self.table_dim = index.M * 16
+        self.device = index.device
+        self._source = None
+        self._h = C.c_void_p()
+        _check(lib().qadc_adc_index_create_view(C.byref(self._h), index._h))
+        self._source = index                                             # (collected after the view: __del__ closes the view first)
+        return self
+
+    @property
+    def dim(self):
+        """the vector dimension: set_pq's, or for a view the one set on its source index (AttributeError before either)"""
+        if self._source is not None:
+            return self._source.dim
+        try:
+            return self.__dict__["_dim"]
+        except KeyError:
+            raise AttributeError("dim") from None
+
+    @dim.setter
+    def dim(self, value):
+        self.__dict__["_dim"] = value
 
     def close(self):
         if self._h:
             lib().qadc_adc_index_destroy(self._h)
             self._h = C.c_void_p()
+        self._source = None
 
     def __del__(self):
         try:
@@ -810,11 +847,11 @@ class AdcIndex:
         if assign.ndim == 1:
             assign = assign.reshape(1, -1)
         nq, ma = assign.shape
-        tables = np.ascontiguousarray(tables, np.float32).reshape(nq, ma, self.sq_count * 256)
+        tables = np.ascontiguousarray(tables, np.float32).reshape(nq, ma, self.table_dim)
         return assign, tables, nq, ma
 
     def query_scan(self, assign, tables, R, sum_mode=1):
-        """assign [nq][ma], tables [nq][ma][sq_count*256] -> (keys [nq][R], vals [nq][R], sizes [nq]): the heap arrays
+        """assign [nq][ma], tables [nq][ma][table_dim] (sq_count*256; a view: sq_count*16) -> (keys [nq][R], vals [nq][R], sizes [nq]): the heap arrays
         of scanner_simple::query_scan per query (rows are valid up to sizes[q])."""
         assign, tables, nq, ma = self._inputs(assign, tables)
         keys = np.zeros((nq, R), np.uint32)
@@ -924,7 +961,7 @@ class AdcIndex:
         q = self._queries(queries)
         nq = q.shape[0]
         assign = np.zeros((nq, ma), np.int32)
-        tables = np.zeros((nq, ma, self.sq_count * 256), np.float32)
+        tables = np.zeros((nq, ma, self.table_dim), np.float32)
         _check(lib().qadc_adc_search_tables(self._h, nq, _p(q, f32p), ma, table_form, sum_mode, _p(assign, i32p), _p(tables, f32p)))
         return assign, tables
 
@@ -971,7 +1008,7 @@ class AdcIndex:
         if assign.ndim == 1:
             assign = assign.reshape(1, -1)
         nq, ma = assign.shape
-        t = self._device_tensor(tables, (nq, ma, self.sq_count * 256), "tables")
+        t = self._device_tensor(tables, (nq, ma, self.table_dim), "tables")
         keys, vals, sizes = self._device_outputs(nq, int(R))
         _check(lib().qadc_adc_query_scan_device(self._h, nq, ma, _p(assign, i32p), t.data_ptr(), R, sum_mode, keys.data_ptr(),
                                                 vals.data_ptr(), sizes.data_ptr()))

@@ -2,6 +2,7 @@
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
   python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
   batch32   32 queries per call on the same list
@@ -18,6 +19,15 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             asserted equal, and the same pair at 1, 8, 32, 128 and 1024 queries per call.
   lone_search  one synchronous search() of one query at that shape under the host finish and, alternated with it and asserted
             equal, under the device finish, beside one CPU thread scanning the same 24 partitions
+  --bits 4   the float-ADC view of a 4-bit index instead (pyqadc.AdcIndex.view_of; legs lone,ivf_search):
+  lone      one synchronous query on 10^6 and on 10^8 codes at 16x4 and 32x4: median and range of the call, codes/s, the share
+            of the HBM roofline at 8 B / 16 B per code; at 16x4 alternated with the 8x8 engine on a list of the same n (the
+            same bytes per code); beside one CPU thread on scan_4<M> over the 10^6 list (the reference's build where
+            oracle/_ref has it, and the C restatement)
+  ivf_search   10^6 clustered 128-d vectors encoded at 16x4 by ivf_encode, K = 256, ma = 24, 1024 queries: search() on the view
+            under the host and the device finish, alternated and asserted equal
+  profile   not timed: five one-query calls on 10^8 codes through the 16x4 view, the 32x4 view and the 8x8 engine, in that order —
+            the workload of the rocprofv3 kernel-trace and LDS-counter runs (run it under rocprofv3, one kind of collection per run)
 Every time is a host clock around whole synchronous calls (median of --iters after warm-up); R = 100, sum_mode 1."""
 import argparse
 import json
@@ -159,13 +169,135 @@ def search_legs(legs, iters, res):
     idx.close()
 
 
+def spread(fn, iters, warmup=3):
+    """(median, min, max) seconds of fn()"""
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), float(np.min(ts)), float(np.max(ts))
+
+
+def view_legs(legs, iters, res):
+    """--bits 4: the float-ADC view of a 4-bit index"""
+    import pyoracle as po
+    rng = np.random.default_rng(4)
+    zero = np.zeros((1, 1), np.int32)
+    if "lone" in legs:
+        for n in (1_000_000, 100_000_000):
+            for M in (16, 32):
+                cs = M // 2
+                src = pyqadc.Index(M)
+                src.add_partition_synthetic(n, 1234 + M)
+                src.finalize(0.01)
+                view = pyqadc.AdcIndex.view_of(src)
+                tb = ((rng.random((1, 1, M * 16), dtype=np.float32) * np.float32(4.0)) ** 2).astype(np.float32)
+                it = max(iters, 50) if n <= 1_000_000 else iters
+                tag = "view%dx4_%.0e" % (M, n)
+                if M == 16:   # the 8x8 engine on as many codes of as many bytes, in turn with the view
+                    adc8 = pyqadc.AdcIndex(8, 8)
+                    adc8.add_partitions([rng.integers(0, 256, (n, 8), dtype=np.uint8)])
+                    tb8 = tables_for(rng, 1, 1)
+                    med_v, med_8 = alternated(lambda: view.query_scan(zero, tb, R), lambda: adc8.query_scan(zero, tb8, R), it, warmup=3)
+                    res[tag + "_alternated_ms"] = med_v * 1e3
+                    res["adc8x8_%.0e_alternated_ms" % n] = med_8 * 1e3
+                    print("n = %.0e, one query/call, alternated: 16x4 view %.3f ms, 8x8 engine %.3f ms (view / 8x8 = %.3f)"
+                          % (n, med_v * 1e3, med_8 * 1e3, med_v / med_8), flush=True)
+                    adc8.close()
+                med, lo, hi = spread(lambda: view.query_scan(zero, tb, R), it)
+                res[tag + "_ms_median_min_max"] = [med * 1e3, lo * 1e3, hi * 1e3]
+                res[tag + "_codes_per_s"] = n / med
+                res[tag + "_hbm_roofline_share"] = n * cs / med / HBM_BPS
+                print("%dx4 view, %.0e codes, one synchronous query: %.3f ms (%.3f .. %.3f) = %.3g codes/s = %.3f of the HBM roofline "
+                      "at %d B per code" % (M, n, med * 1e3, lo * 1e3, hi * 1e3, n / med, n * cs / med / HBM_BPS, cs), flush=True)
+                if n == 1_000_000:
+                    codes = src.read_codes(0, 0, n)
+                    tt = tb.reshape(1, -1)
+                    med_c, _ = timed(lambda: po.scan4_start(M, [codes], None, tt, R), 5, warmup=1)
+                    res["cpu_scan_4_%d_restatement_us" % M] = med_c * 1e6
+                    print("CPU scan_4<%d>, 10^6 codes, 1 thread (C restatement): %.1f us" % (M, med_c * 1e6), flush=True)
+                    if po.have_ref_float():
+                        med_c, _ = timed(lambda: po.reff_scan4_start(M, [codes], None, tt, R), 5, warmup=1)
+                        res["cpu_scan_4_%d_reference_build_us" % M] = med_c * 1e6
+                        print("CPU scan_4<%d>, 10^6 codes, 1 thread (reference build, -O3 -ffast-math AVX2): %.1f us = %.1fx the view's call"
+                              % (M, med_c * 1e6, med_c / med), flush=True)
+                view.close()
+                src.close()
+    if "profile" in legs:
+        n = 100_000_000
+        for M in (16, 32):
+            src = pyqadc.Index(M)
+            src.add_partition_synthetic(n, 1234 + M)
+            src.finalize(0.01)
+            view = pyqadc.AdcIndex.view_of(src)
+            tb = ((rng.random((1, 1, M * 16), dtype=np.float32) * np.float32(4.0)) ** 2).astype(np.float32)
+            for _ in range(5):
+                view.query_scan(zero, tb, R)
+            view.close()
+            src.close()
+        adc8 = pyqadc.AdcIndex(8, 8)
+        adc8.add_partitions([rng.integers(0, 256, (n, 8), dtype=np.uint8)])
+        tb8 = tables_for(rng, 1, 1)
+        for _ in range(5):
+            adc8.query_scan(zero, tb8, R)
+        adc8.close()
+    if "ivf_search" in legs:
+        n, dim, M, K, ma, nq = 1_000_000, 128, 16, 256, 24, 1024
+        centers = (rng.normal(size=(2000, dim)) * 3).astype(np.float32)
+        vectors = centers[rng.integers(0, len(centers), n)]
+        vectors += rng.normal(size=(n, dim)).astype(np.float32)
+        queries = (centers[rng.integers(0, len(centers), nq)] + rng.normal(size=(nq, dim))).astype(np.float32)
+        coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, K, replace=False)], 5)
+        sample = vectors[rng.choice(n, 16, replace=False)]
+        near = pyqadc.coarse_assign(sample, coarse, 1)[:, 0]
+        codebooks = np.ascontiguousarray((sample - coarse[near]).reshape(16, M, dim // M).transpose(1, 0, 2), np.float32)
+        part_of, codes = pyqadc.ivf_encode(codebooks, vectors, coarse)
+        del vectors
+        order = np.argsort(part_of, kind="stable")
+        bounds = np.searchsorted(part_of[order], np.arange(K + 1))
+        src = pyqadc.Index(M)
+        src.add_partitions([codes[order[bounds[k]:bounds[k + 1]]] for k in range(K)],
+                           [order[bounds[k]:bounds[k + 1]].astype(np.uint32) for k in range(K)])
+        src.finalize(0.01)
+        src.set_pq(codebooks)
+        src.set_coarse(coarse)
+        view = pyqadc.AdcIndex.view_of(src)
+        host = lambda: view.search(queries, ma, R)
+        dev = with_finish(view, 1, host)
+        assert same_heaps(host(), dev()), "host and device finish disagree"
+        med_h, med_d = alternated(host, dev, max(5, iters))
+        res["view16x4_ivf_search_host_finish_ms"] = med_h * 1e3
+        res["view16x4_ivf_search_device_finish_ms"] = med_d * 1e3
+        res["view16x4_ivf_search_host_finishes"] = int(view.host_finishes())
+        print("IVF 16x4 view on encoded vectors, K=256 ma=24, search() of 1024 queries: host finish %.2f ms = %.2f us/query, device finish "
+              "%.2f ms = %.2f us/query" % (med_h * 1e3, med_h * 1e6 / nq, med_d * 1e3, med_d * 1e6 / nq), flush=True)
+        view.close()
+        src.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search")
+    ap.add_argument("--legs", default=None)
+    ap.add_argument("--bits", type=int, default=8, choices=(4, 8))
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.legs is None:
+        a.legs = "flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search" if a.bits == 8 else "lone,ivf_search"
     legs = a.legs.split(",")
+    if a.bits == 4:
+        res = {"R": R, "sum_mode": 1, "bits": 4, "cpus_allowed": len(os.sched_getaffinity(0))}
+        view_legs(legs, a.iters, res)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     torch = None
     if "ivf" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:

@@ -17,8 +17,8 @@
 //
 // A VIEW (qadc_adc_index_create_view) is the same engine over the 4-bit codes of a finalized
 // qadc_index — db_query's scan_4<M> (query_common.hpp:59-90) on the database db_query_4 has resident.  It owns no codes: it
-// snapshots the index's partition table, scans with adc_scan4_kernel (tables [M][16]) and, for the search calls, runs the
-// index's quantizers (FeederState) through launch_coarse_assign and launch_build_tables on its own stream.  Levels, bounds,
+// snapshots the index's partition table, scans with adc_scan_kernel over NibbleCodes<M> (tables [M][16]) and, for the search
+// calls, reads the index's quantizers (FeederState) through launch_coarse_assign and launch_build_tables on its own stream.  Levels, bounds,
 // regions, re-runs and both finishes are the ones above, unchanged: nothing in them depends on how a candidate is summed.
 #include "../../include/qadc.h"
 
@@ -42,24 +42,14 @@ using qadc::host::PinBuf;
 
 namespace {
 
-constexpr uint32_t kLevel0 = 512;      // codes of level 0 (at least R)
-constexpr uint32_t kLevelGrowth = 16;  // each level spans 16 times the scan order before it
-constexpr uint32_t kWgTarget = 2048;   // workgroups a level is cut into, roughly
-constexpr uint32_t kRunMin = 2048, kRunMax = 65536;
 constexpr uint64_t kSpeculativeEntries = 1 << 16;   // regions up to this many entries in all come back with the counts
 constexpr uint64_t kMaxEntries = QADC_ADC_MAX_ENTRIES;   // candidate entries of one batch (12 B of device memory each)
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Every entry point works on the index's device and gives the calling thread its current device back.
 struct DeviceGuard {
     int prev = -1;
-    DeviceGuard() {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
+    DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
 }  // namespace
@@ -114,34 +104,28 @@ struct qadc_adc_index {
 
 namespace {
 
-using qadc::adc::Item;
+using namespace qadc::adc;
 
-int grow_device(DevBuf<uint8_t>& buf, uint64_t used, uint64_t need, hipStream_t s) {
+template <typename T>
+int grow_device(DevBuf<T>& buf, uint64_t used, uint64_t need, hipStream_t s) {
     if (need <= buf.cap) return QADC_OK;
-    DevBuf<uint8_t> nb;
+    DevBuf<T> nb;
     HIPCHECK(nb.ensure(std::max<uint64_t>(need, buf.cap + buf.cap / 2)));
-    if (used) HIPCHECK(hipMemcpyAsync(nb.p, buf.p, used, hipMemcpyDeviceToDevice, s));
+    if (used) HIPCHECK(hipMemcpyAsync(nb.p, buf.p, used * sizeof(T), hipMemcpyDeviceToDevice, s));
     HIPCHECK(hipStreamSynchronize(s));
     buf.release();
     buf = nb;
     return QADC_OK;
 }
 
-int grow_labels(DevBuf<uint32_t>& buf, uint64_t used, uint64_t need, hipStream_t s) {
-    if (need <= buf.cap) return QADC_OK;
-    DevBuf<uint32_t> nb;
-    HIPCHECK(nb.ensure(std::max<uint64_t>(need, buf.cap + buf.cap / 2)));
-    if (used) HIPCHECK(hipMemcpyAsync(nb.p, buf.p, used * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    buf.release();
-    buf = nb;
-    return QADC_OK;
+int check_R(int R) {
+    return R < 1 || R > QADC_ADC_MAX_R ? fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]") : QADC_OK;
 }
 
 int check_query_args(const qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const void* tables, int R, int sum_mode) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
     if (nq < 1 || ma < 1 || ma >= 16384) return fail(QADC_E_ARG, "need nq >= 1 and 1 <= ma < 16384");
-    if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
+    if (int rc = check_R(R)) return rc;
     if (sum_mode != 0 && sum_mode != 1) return fail(QADC_E_ARG, "sum_mode is 0 (source order) or 1 (as compiled)");
     if (!assign || !tables) return fail(QADC_E_ARG, "assign and tables are required");
     const int parts = (int)idx->sizes.size();
@@ -153,186 +137,153 @@ int check_query_args(const qadc_adc_index* idx, int nq, int ma, const int32_t* a
 }
 
 // Where the device finish leaves the heaps' arrays of a batch: device memory, keys / values [nq][R], sizes [nq].
-struct DeviceOut {
-    uint32_t* keys;
-    float* values;
-    int32_t* sizes;
+struct DeviceOut { uint32_t* keys; float* values; int32_t* sizes; };
+
+// The database as the scan launcher takes it: the owned codes, or the partition table of a view.
+ScanDb scan_db(const qadc_adc_index* idx) {
+    if (idx->src) return ScanDb{idx->nsq, idx->centroids, Db{}, idx->d_parts4.p};
+    return ScanDb{idx->nsq, idx->centroids, Db{idx->codes.p, idx->d_off.p, idx->labeled == 1 ? idx->labels.p : nullptr, idx->d_lab_off.p}, nullptr};
+}
+
+// One batch on its way through scan_batch: the plan, where the batch lies in the staging buffers idx->h_in / idx->d_in, uploaded in one copy —
+//   bound (FLT_MAX) | count (0) | region sizes | region bases | assign | items | tables (the caller's, unless already on the device)
+// of which the first four, bytes [0, o_assign), are the state a re-run writes again — and what the levels left.
+struct Batch {
+    Plan plan;
+    size_t o_count, o_cap, o_base, o_assign;
+    uint64_t entries = 0, n_stored = 0;   // entries of all regions together;  candidates they hold after the levels
+    float* d_bound;
+    const int32_t* d_assign;
+    const Item* d_items;
+    const float* d_tables;
+    Emit emit;                      // the regions: count, base and cap lie in d_in, vals / keys / sidx are set by every attempt
+    std::vector<uint32_t> stored;   // [nq] candidates each query's region holds after the levels (n_stored in all)
 };
 
-// Scans the batch on the device and leaves the ordered candidate stream of every query in idx->stream_* — or, given `out`
-// (R <= kAdcReplayMaxR), orders and replays the streams on the device: the heaps' arrays are in `out` and the stream
-// synchronised on return, and idx->stream_* is empty.
-// The tables are the caller's (`tables`, uploaded with the items) or already in device memory (`d_ready`, enqueued on the
-// index's stream before this call; tables is null then).
-int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, const float* d_ready, int R,
-               int sum_mode, const DeviceOut* out = nullptr) {
-    if (int rc = check_query_args(idx, nq, ma, assign, d_ready ? static_cast<const void*>(d_ready) : tables, R, sum_mode)) return rc;
-    HIPCHECK(hipSetDevice(idx->device));
-    // scan-order length of every query, and the levels
-    std::vector<uint64_t> total(nq, 0);
-    uint64_t max_total = 0;
-    for (int q = 0; q < nq; ++q) {
-        for (int a = 0; a < ma; ++a) total[q] += idx->sizes[assign[(size_t)q * ma + a]];
-        if (total[q] > 0xffffffffull)
-            return fail(QADC_E_ARG, "query " + std::to_string(q) + " probes " + std::to_string(total[q]) +
-                                        " codes: at most 2^32 - 1 per query");
-        max_total = std::max(max_total, total[q]);
+// bound, counts and the regions of plan.cap into the host staging buffer
+void fill_state(qadc_adc_index* idx, Batch& b) {
+    uint8_t* h = idx->h_in.p;
+    const size_t nq = b.plan.cap.size();
+    std::fill(reinterpret_cast<float*>(h), reinterpret_cast<float*>(h) + nq, FLT_MAX);
+    std::memset(h + b.o_count, 0, nq * 4);
+    std::memcpy(h + b.o_cap, b.plan.cap.data(), nq * 4);
+    uint64_t* base = reinterpret_cast<uint64_t*>(h + b.o_base);
+    b.entries = 0;
+    for (size_t q = 0; q < nq; ++q) {
+        base[q] = b.entries;
+        b.entries += b.plan.cap[q];
     }
-    std::vector<uint64_t> edge{0, std::max<uint64_t>((uint64_t)R, kLevel0)};
-    while (edge.back() < max_total) edge.push_back(edge.back() * kLevelGrowth);
-    const int levels = (int)edge.size() - 1;
-    // the runs of every level: per query, the level's stretch of the scan order cut at partition ends and into runs
-    std::vector<Item> items;
-    std::vector<uint32_t> level_first(levels + 1, 0);
-    for (int l = 0; l < levels; ++l) {
-        level_first[l] = (uint32_t)items.size();
-        uint64_t span = 0;
-        for (int q = 0; q < nq; ++q)
-            if (total[q] > edge[l]) span += std::min(total[q], edge[l + 1]) - edge[l];
-        const uint64_t run = std::min<uint64_t>(kRunMax, std::max<uint64_t>(kRunMin, align_up((span + kWgTarget - 1) / kWgTarget, 1024)));
-        for (int q = 0; q < nq; ++q) {
-            const uint64_t lo = edge[l], hi = std::min(total[q], edge[l + 1]);
-            uint64_t pbase = 0;
-            for (int a = 0; a < ma && pbase < hi; ++a) {
-                const uint64_t sz = idx->sizes[assign[(size_t)q * ma + a]];
-                const uint64_t s0 = std::max(lo, pbase), s1 = std::min(hi, pbase + sz);
-                for (uint64_t s = s0; s < s1; s += run) {
-                    Item it{};
-                    it.query = (uint32_t)q;
-                    it.slot = (uint32_t)a;
-                    it.start = (uint32_t)(s - pbase);
-                    it.count = (uint32_t)std::min<uint64_t>(run, s1 - s);
-                    it.sbase = (uint32_t)s;
-                    items.push_back(it);
-                }
-                pbase += sz;
-            }
-        }
-    }
-    level_first[levels] = (uint32_t)items.size();
+}
 
-    // Per-query regions: the expected stream (level 0 whole, then ~15 R per level) with room to spare, at most the query's
-    // code count.  They are sized per call, so nothing one call needed carries over to the next.
-    const uint64_t expect = std::max<uint64_t>((uint64_t)R, kLevel0) + 32ull * R * (levels - 1) + 4096;
-    std::vector<uint32_t> cap(nq);
-    for (int q = 0; q < nq; ++q) cap[q] = (uint32_t)std::max<uint64_t>(1, std::min(total[q], expect));
-
-    // one upload: bound (FLT_MAX) | count (0) | region sizes | region bases | assign | items | tables
-    const size_t table_floats = (size_t)idx->nsq * idx->centroids;
-    const size_t o_count = align_up((size_t)nq * 4, 256);
-    const size_t o_cap = o_count + align_up((size_t)nq * 4, 256);
-    const size_t o_base = o_cap + align_up((size_t)nq * 4, 256);
-    const size_t o_assign = o_base + align_up((size_t)nq * 8, 256);
-    const size_t o_items = o_assign + align_up((size_t)nq * ma * 4, 256);
+// Lays the batch out and enqueues its upload.  d_ready: the tables are in device memory already (tables is null then).
+int stage_batch(qadc_adc_index* idx, Batch& b, int nq, int ma, const int32_t* assign, const float* tables, const float* d_ready) {
+    const std::vector<Item>& items = b.plan.items;
+    const size_t table_bytes = d_ready ? 0 : (size_t)nq * ma * idx->nsq * idx->centroids * 4;
+    b.o_count = align_up((size_t)nq * 4, 256);
+    b.o_cap = b.o_count + align_up((size_t)nq * 4, 256);
+    b.o_base = b.o_cap + align_up((size_t)nq * 4, 256);
+    b.o_assign = b.o_base + align_up((size_t)nq * 8, 256);
+    const size_t o_items = b.o_assign + align_up((size_t)nq * ma * 4, 256);
     const size_t o_tables = o_items + align_up(items.size() * sizeof(Item), 256);
-    const size_t in_bytes = o_tables + (d_ready ? 0 : (size_t)nq * ma * table_floats * 4);
+    const size_t in_bytes = o_tables + table_bytes;
     HIPCHECK(idx->h_in.ensure(std::max<size_t>(in_bytes, 256)));
     HIPCHECK(idx->d_in.ensure(std::max<size_t>(in_bytes, 256)));
-    uint8_t* h = idx->h_in.p;
-    uint64_t* h_base = reinterpret_cast<uint64_t*>(h + o_base);
-    // bound, counts and regions: written again before a re-run
-    auto fill_state = [&]() -> uint64_t {
-        std::fill(reinterpret_cast<float*>(h), reinterpret_cast<float*>(h) + nq, FLT_MAX);
-        std::memset(h + o_count, 0, (size_t)nq * 4);
-        std::memcpy(h + o_cap, cap.data(), (size_t)nq * 4);
-        uint64_t entries = 0;
-        for (int q = 0; q < nq; ++q) {
-            h_base[q] = entries;
-            entries += cap[q];
-        }
-        return entries;
-    };
-    uint64_t entries = fill_state();
-    std::memcpy(h + o_assign, assign, (size_t)nq * ma * 4);
+    uint8_t *h = idx->h_in.p, *d = idx->d_in.p;
+    fill_state(idx, b);
+    std::memcpy(h + b.o_assign, assign, (size_t)nq * ma * 4);
     if (!items.empty()) std::memcpy(h + o_items, items.data(), items.size() * sizeof(Item));
-    if (!d_ready) std::memcpy(h + o_tables, tables, (size_t)nq * ma * table_floats * 4);
-    uint8_t* d = idx->d_in.p;
-    float* d_bound = reinterpret_cast<float*>(d);
-    uint32_t* d_count = reinterpret_cast<uint32_t*>(d + o_count);
-    const uint32_t* d_cap = reinterpret_cast<const uint32_t*>(d + o_cap);
-    const uint64_t* d_base = reinterpret_cast<const uint64_t*>(d + o_base);
-    const int32_t* d_assign = reinterpret_cast<const int32_t*>(d + o_assign);
-    const Item* d_items = reinterpret_cast<const Item*>(d + o_items);
-    const float* d_tables = d_ready ? d_ready : reinterpret_cast<const float*>(d + o_tables);
+    if (table_bytes) std::memcpy(h + o_tables, tables, table_bytes);
+    b.d_bound = reinterpret_cast<float*>(d);
+    b.d_assign = reinterpret_cast<const int32_t*>(d + b.o_assign);
+    b.d_items = reinterpret_cast<const Item*>(d + o_items);
+    b.d_tables = d_ready ? d_ready : reinterpret_cast<const float*>(d + o_tables);
+    b.emit = Emit{reinterpret_cast<uint32_t*>(d + b.o_count), nullptr, nullptr, nullptr, reinterpret_cast<const uint64_t*>(d + b.o_base),
+                  reinterpret_cast<const uint32_t*>(d + b.o_cap)};
     HIPCHECK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, idx->stream));
+    return QADC_OK;
+}
 
-    qadc::adc::Db db{idx->codes.p, idx->d_off.p, idx->labeled == 1 ? idx->labels.p : nullptr, idx->d_lab_off.p};
-    std::vector<uint32_t> stored(nq);
-    uint64_t n_stored = 0;
+// Runs the levels and reads the counts back; while a region overflowed, grows it and re-runs the whole batch.  fetch: the stored records come
+// back too, packed into idx->h_packed (three words each) — those of a small batch speculatively, with the counts, in one round trip.
+int run_levels(qadc_adc_index* idx, Batch& b, int nq, int ma, int R, int sum_mode, bool fetch) {
+    const ScanDb db = scan_db(idx);
+    const std::vector<uint32_t>& first = b.plan.level_first;
+    const int levels = b.plan.levels();
+    b.stored.resize(nq);
     bool speculative = false;
     for (;;) {
-        if (entries > kMaxEntries)
-            return fail(QADC_E_CAPACITY, "the candidate regions of this batch need " + std::to_string(entries) + " entries (at most " +
+        if (b.entries > kMaxEntries)
+            return fail(QADC_E_CAPACITY, "the candidate regions of this batch need " + std::to_string(b.entries) + " entries (at most " +
                                              std::to_string(kMaxEntries) + "): split the batch");
-        HIPCHECK(idx->d_vals.ensure(entries));
-        HIPCHECK(idx->d_keys.ensure(entries));
-        HIPCHECK(idx->d_sidx.ensure(entries));
-        const qadc::adc::Emit emit{d_count, idx->d_vals.p, idx->d_keys.p, idx->d_sidx.p, d_base, d_cap};
+        HIPCHECK(idx->d_vals.ensure(b.entries));
+        HIPCHECK(idx->d_keys.ensure(b.entries));
+        HIPCHECK(idx->d_sidx.ensure(b.entries));
+        b.emit.vals = idx->d_vals.p;
+        b.emit.keys = idx->d_keys.p;
+        b.emit.sidx = idx->d_sidx.p;
         for (int l = 0; l < levels; ++l) {
-            if (idx->src)
-                HIPCHECK(qadc::adc::launch_adc_scan4(idx->nsq, sum_mode, d_items, level_first[l], level_first[l + 1] - level_first[l],
-                                                     idx->d_parts4.p, d_assign, ma, d_tables, d_bound, emit, idx->stream));
-            else
-                HIPCHECK(qadc::adc::launch_adc_scan(idx->nsq, sum_mode, d_items, level_first[l], level_first[l + 1] - level_first[l], db,
-                                                    d_assign, ma, d_tables, d_bound, emit, idx->stream));
-            if (l + 1 < levels) HIPCHECK(qadc::adc::launch_adc_select(nq, R, emit, d_bound, idx->stream));
+            HIPCHECK(launch_adc_scan(db, sum_mode, b.d_items, first[l], first[l + 1] - first[l], b.d_assign, ma, b.d_tables, b.d_bound, b.emit,
+                                     idx->stream));
+            if (l + 1 < levels) HIPCHECK(launch_adc_select(nq, R, b.emit, b.d_bound, idx->stream));
         }
         HIPCHECK(idx->h_count.ensure(nq));
-        // small batches: pack and fetch all regions speculatively, with the counts, in one round trip
-        speculative = !out && entries <= kSpeculativeEntries;
+        speculative = fetch && b.entries <= kSpeculativeEntries;
         if (speculative) {
-            HIPCHECK(idx->d_packed.ensure(3 * entries));
-            HIPCHECK(idx->h_packed.ensure(3 * entries));
-            HIPCHECK(qadc::adc::launch_adc_pack(nq, emit, idx->d_packed.p, idx->stream));
+            HIPCHECK(idx->d_packed.ensure(3 * b.entries));
+            HIPCHECK(idx->h_packed.ensure(3 * b.entries));
+            HIPCHECK(launch_adc_pack(nq, b.emit, idx->d_packed.p, idx->stream));
         }
-        HIPCHECK(hipMemcpyAsync(idx->h_count.p, d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, idx->stream));
-        if (speculative) HIPCHECK(hipMemcpyAsync(idx->h_packed.p, idx->d_packed.p, 3 * entries * 4, hipMemcpyDeviceToHost, idx->stream));
+        HIPCHECK(hipMemcpyAsync(idx->h_count.p, b.emit.count, (size_t)nq * 4, hipMemcpyDeviceToHost, idx->stream));
+        if (speculative) HIPCHECK(hipMemcpyAsync(idx->h_packed.p, idx->d_packed.p, 3 * b.entries * 4, hipMemcpyDeviceToHost, idx->stream));
         HIPCHECK(hipStreamSynchronize(idx->stream));
         bool overflow = false;
-        n_stored = 0;
+        b.n_stored = 0;
         for (int q = 0; q < nq; ++q) {
+            uint32_t& cap = b.plan.cap[q];
             const uint32_t c = idx->h_count.p[q];
-            stored[q] = std::min(c, cap[q]);
-            n_stored += stored[q];
-            if (c > cap[q]) {   // every emitted candidate was counted: this region takes them all in the re-run
+            b.stored[q] = std::min(c, cap);
+            b.n_stored += b.stored[q];
+            if (c > cap) {   // every emitted candidate was counted: this region takes them all in the re-run
                 overflow = true;
-                cap[q] = (uint32_t)std::min<uint64_t>(total[q], std::max<uint64_t>((uint64_t)c + c / 2, 2ull * cap[q]));
+                cap = (uint32_t)std::min<uint64_t>(b.plan.total[q], std::max<uint64_t>((uint64_t)c + c / 2, 2ull * cap));
             }
         }
         if (!overflow) break;
         ++idx->reruns;
-        entries = fill_state();   // re-run the whole batch with the grown regions
-        HIPCHECK(hipMemcpyAsync(d, h, o_assign, hipMemcpyHostToDevice, idx->stream));
+        fill_state(idx, b);
+        HIPCHECK(hipMemcpyAsync(idx->d_in.p, idx->h_in.p, b.o_assign, hipMemcpyHostToDevice, idx->stream));
     }
-    if (out) {   // the device finish: order, replay; nothing of the stream crosses the bus
-        idx->stream_off.assign((size_t)nq + 1, 0);
-        idx->stream_keys.clear();
-        idx->stream_vals.clear();
-        HIPCHECK(idx->d_ovals.ensure(entries));
-        HIPCHECK(idx->d_okeys.ensure(entries));
-        int bits = 0;
-        while (bits < 32 && ((max_total - 1) >> bits)) ++bits;   // (max_total >= 1 where anything was stored)
-        if (*std::max_element(stored.begin(), stored.end()) > (uint32_t)qadc::adc::kOrderLds) {
-            if (bits > 8) HIPCHECK(idx->d_tmp_a.ensure(entries));
-            if (bits > 16) HIPCHECK(idx->d_tmp_b.ensure(entries));
-        }
-        const qadc::adc::Emit emit{d_count, idx->d_vals.p, idx->d_keys.p, idx->d_sidx.p, d_base, d_cap};
-        HIPCHECK(qadc::adc::launch_adc_order(nq, emit, bits, idx->d_ovals.p, idx->d_okeys.p, idx->d_tmp_a.p, idx->d_tmp_b.p, idx->stream));
-        HIPCHECK(qadc::adc::launch_adc_replay(nq, R, emit, idx->d_ovals.p, idx->d_okeys.p, out->keys, out->values, out->sizes, idx->stream));
-        HIPCHECK(hipStreamSynchronize(idx->stream));
-        return QADC_OK;
-    }
-    if (!speculative) {
-        HIPCHECK(idx->d_packed.ensure(std::max<uint64_t>(3 * n_stored, 3)));
-        HIPCHECK(idx->h_packed.ensure(std::max<uint64_t>(3 * n_stored, 3)));
-        const qadc::adc::Emit emit{d_count, idx->d_vals.p, idx->d_keys.p, idx->d_sidx.p, d_base, d_cap};
-        HIPCHECK(qadc::adc::launch_adc_pack(nq, emit, idx->d_packed.p, idx->stream));
-        if (n_stored)
-            HIPCHECK(hipMemcpyAsync(idx->h_packed.p, idx->d_packed.p, 3 * n_stored * 4, hipMemcpyDeviceToHost, idx->stream));
+    if (fetch && !speculative) {
+        HIPCHECK(idx->d_packed.ensure(std::max<uint64_t>(3 * b.n_stored, 3)));
+        HIPCHECK(idx->h_packed.ensure(std::max<uint64_t>(3 * b.n_stored, 3)));
+        HIPCHECK(launch_adc_pack(nq, b.emit, idx->d_packed.p, idx->stream));
+        if (b.n_stored) HIPCHECK(hipMemcpyAsync(idx->h_packed.p, idx->d_packed.p, 3 * b.n_stored * 4, hipMemcpyDeviceToHost, idx->stream));
         HIPCHECK(hipStreamSynchronize(idx->stream));
     }
+    return QADC_OK;
+}
 
-    // put every query's candidates in scan order (scan indices are distinct within a query)
+// The device finish: order, replay.  The heaps' arrays are in `out` and the stream synchronised on return; idx->stream_* is empty.
+int finish_on_device(qadc_adc_index* idx, const Batch& b, int nq, int R, const DeviceOut& out) {
+    idx->stream_off.assign((size_t)nq + 1, 0);
+    idx->stream_keys.clear();
+    idx->stream_vals.clear();
+    HIPCHECK(idx->d_ovals.ensure(b.entries));
+    HIPCHECK(idx->d_okeys.ensure(b.entries));
+    int bits = 0;
+    while (bits < 32 && ((b.plan.max_total - 1) >> bits)) ++bits;   // (max_total >= 1 where anything was stored)
+    if (*std::max_element(b.stored.begin(), b.stored.end()) > (uint32_t)kOrderLds) {
+        if (bits > 8) HIPCHECK(idx->d_tmp_a.ensure(b.entries));
+        if (bits > 16) HIPCHECK(idx->d_tmp_b.ensure(b.entries));
+    }
+    HIPCHECK(launch_adc_order(nq, b.emit, bits, idx->d_ovals.p, idx->d_okeys.p, idx->d_tmp_a.p, idx->d_tmp_b.p, idx->stream));
+    HIPCHECK(launch_adc_replay(nq, R, b.emit, idx->d_ovals.p, idx->d_okeys.p, out.keys, out.values, out.sizes, idx->stream));
+    HIPCHECK(hipStreamSynchronize(idx->stream));
+    return QADC_OK;
+}
+
+// Every query's records of idx->h_packed into idx->stream_* in scan order (scan indices are distinct within a query).
+void order_on_host(qadc_adc_index* idx, const std::vector<uint32_t>& stored, uint64_t n_stored, int nq) {
     idx->stream_off.assign((size_t)nq + 1, 0);
     for (int q = 0; q < nq; ++q) idx->stream_off[q + 1] = idx->stream_off[q] + stored[q];
     idx->stream_keys.resize(n_stored);
@@ -367,6 +318,22 @@ int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const
         }
     };
     idx->pool.run(nq, n_stored > 65536 ? 16 : 1, order);
+}
+
+// Scans the batch on the device and leaves the ordered candidate stream of every query in idx->stream_* — or, given `out`
+// (R <= kAdcReplayMaxR), orders and replays the streams on the device.  The tables are the caller's (`tables`, uploaded with the
+// items) or already in device memory (`d_ready`, enqueued on the index's stream before this call; tables is null then).
+int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, const float* d_ready, int R,
+               int sum_mode, const DeviceOut* out = nullptr) {
+    if (int rc = check_query_args(idx, nq, ma, assign, d_ready ? static_cast<const void*>(d_ready) : tables, R, sum_mode)) return rc;
+    HIPCHECK(hipSetDevice(idx->device));
+    Batch b;
+    b.plan = plan_levels(idx->sizes.data(), nq, ma, assign, R);
+    if (!b.plan.refused.empty()) return fail(QADC_E_ARG, b.plan.refused);
+    if (int rc = stage_batch(idx, b, nq, ma, assign, tables, d_ready)) return rc;
+    if (int rc = run_levels(idx, b, nq, ma, R, sum_mode, !out)) return rc;
+    if (out) return finish_on_device(idx, b, nq, R, *out);
+    order_on_host(idx, b.stored, b.n_stored, nq);
     return QADC_OK;
 }
 
@@ -400,14 +367,14 @@ int copy_stream(qadc_adc_index* idx, int nq, uint64_t cand_capacity, uint32_t* c
 
 constexpr int kCoarseChunk = 32768;   // queries per coarse-assignment pass (the distance scratch is chunk x K floats)
 
-// A view takes its quantizers from its source as they stand when the call is made.
-void bind_source_feeders(qadc_adc_index* idx) {
-    if (!idx || !idx->src) return;
-    const FeederState& f = idx->src->feed;
-    idx->dim = f.dim;
-    idx->K = f.K;
-    idx->rotated = f.has_rotation;
-}
+// The quantizers of one search call, read only: the index's own, or — a view — its source's as they stand when the call is
+// made.  Nothing of them is written into a view.
+struct Feeders {
+    int dim, K;                        // K 0: flat (no coarse quantizer)
+    const float *codebooks, *cbnorm;   // cbnorm: ||c||^2 of the codebook rows under the call's sum_mode (null for a view: its builder takes none)
+    const float *rotation, *coarse;    // [dim][dim], null: plain PQ;  [K][dim], null: flat
+    const float* cnorm;                // [K] ||centroid||^2 under the call's sum_mode
+};
 
 int refuse_on_view(const qadc_adc_index* idx, const char* call) {
     if (idx && idx->src)
@@ -416,22 +383,43 @@ int refuse_on_view(const qadc_adc_index* idx, const char* call) {
     return QADC_OK;
 }
 
-int check_search_args(const qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode) {
-    if (!idx) return fail(QADC_E_ARG, "index is null");
-    if (!idx->dim)
-        return fail(QADC_E_ARG, idx->src ? "qadc_index_set_pq has not been called on the view's source index: it has no codebooks"
-                                         : "qadc_adc_index_set_pq has not been called: the index has no codebooks");
+int check_search_args(const qadc_adc_index* idx, const Feeders& f, int nq, const float* queries, int ma, int table_form, int sum_mode) {
     if (nq < 1 || ma < 1 || ma >= 16384 || !queries) return fail(QADC_E_ARG, "need queries, nq >= 1 and 1 <= ma < 16384");
     if (table_form < 0 || table_form > 2) return fail(QADC_E_ARG, "table_form is 0 (direct), 1 (BLAS expansion) or 2 (nns_engine's rule)");
     if (sum_mode != 0 && sum_mode != 1) return fail(QADC_E_ARG, "sum_mode is 0 (source order) or 1 (as compiled)");
     const int parts = (int)idx->sizes.size();
-    if (idx->K) {
-        if (idx->K != parts)
-            return fail(QADC_E_ARG, "the coarse quantizer has " + std::to_string(idx->K) + " centroids and the index " +
+    if (f.K) {
+        if (f.K != parts)
+            return fail(QADC_E_ARG, "the coarse quantizer has " + std::to_string(f.K) + " centroids and the index " +
                                         std::to_string(parts) + " partitions");
-        if (ma > idx->K) return fail(QADC_E_ARG, "ma = " + std::to_string(ma) + " exceeds the " + std::to_string(idx->K) + " coarse centroids");
+        if (ma > f.K) return fail(QADC_E_ARG, "ma = " + std::to_string(ma) + " exceeds the " + std::to_string(f.K) + " coarse centroids");
     } else if (parts < 1) {
         return fail(QADC_E_ARG, "a flat index (no coarse quantizer) probes partition 0: the index has no partition");
+    }
+    return QADC_OK;
+}
+
+// Opens a search call: resolves the quantizers, checks the call's arguments against them and makes the index's device current.  A view's
+// ||centroid||^2 are computed here, under this call's sum_mode, on the index's stream (the source may have replaced its centroids).
+int resolve_feeders(qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode, Feeders* f) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    const size_t mode = sum_mode == 1;   // (a sum_mode that is neither 0 nor 1 is refused below)
+    if (idx->src) {
+        const FeederState& s = idx->src->feed;
+        *f = Feeders{s.dim, s.K, s.d_codebooks.p, nullptr, s.has_rotation ? s.d_rotation.p : nullptr, s.K ? s.d_coarse.p : nullptr, nullptr};
+    } else {
+        *f = Feeders{idx->dim, idx->K, idx->d_codebooks.p, idx->d_cbnorm.p + mode * idx->nsq * 256, idx->rotated ? idx->d_rotation.p : nullptr,
+                     idx->K ? idx->d_coarse.p : nullptr, idx->d_cnorm.p + mode * idx->K};
+    }
+    if (!f->dim)
+        return fail(QADC_E_ARG, idx->src ? "qadc_index_set_pq has not been called on the view's source index: it has no codebooks"
+                                         : "qadc_adc_index_set_pq has not been called: the index has no codebooks");
+    if (int rc = check_search_args(idx, *f, nq, queries, ma, table_form, sum_mode)) return rc;
+    HIPCHECK(hipSetDevice(idx->device));
+    if (idx->src && f->K) {
+        HIPCHECK(idx->d_cnorm.ensure((size_t)f->K));
+        qadc::launch_row_sqnorm(f->coarse, f->K, f->dim, sum_mode, idx->d_cnorm.p, idx->stream);
+        f->cnorm = idx->d_cnorm.p;
     }
     return QADC_OK;
 }
@@ -439,32 +427,24 @@ int check_search_args(const qadc_adc_index* idx, int nq, const float* queries, i
 // Uploads the queries (d_side: they are device memory already and are read where they lie) and leaves assign [nq][ma] in idx->d_assign, its copy to idx->h_assign enqueued with idx->ev_assign
 // recorded behind it: find_k_neighbors (neighbors.cpp:30-76) through the coarse kernels of the 4-bit index, or all zero for a
 // flat index (flat_db::assign_compute_residuals, databases.hpp:93-101).
-int enqueue_assign(qadc_adc_index* idx, int nq, const float* queries, int ma, int sum_mode, bool d_side = false) {
-    const int dim = idx->dim;
-    HIPCHECK(idx->d_queries.ensure((size_t)nq * dim));
+int enqueue_assign(qadc_adc_index* idx, const Feeders& f, int nq, const float* queries, int ma, int sum_mode, bool d_side = false) {
+    HIPCHECK(idx->d_queries.ensure((size_t)nq * f.dim));
     HIPCHECK(idx->d_assign.ensure((size_t)nq * ma));
     HIPCHECK(idx->h_assign.ensure((size_t)nq * ma));
     if (d_side) {   // read where they are (no memcpy on a caller's device pointer: see launch_adc_copy_words)
         idx->cur_queries = queries;
     } else {
-        HIPCHECK(hipMemcpyAsync(idx->d_queries.p, queries, (size_t)nq * dim * 4, hipMemcpyHostToDevice, idx->stream));
+        HIPCHECK(hipMemcpyAsync(idx->d_queries.p, queries, (size_t)nq * f.dim * 4, hipMemcpyHostToDevice, idx->stream));
         idx->cur_queries = idx->d_queries.p;
     }
-    const float* coarse = idx->src ? idx->src->feed.d_coarse.p : idx->d_coarse.p;
-    if (idx->K && idx->src) {   // ||c||^2 of the source's centroids under this call's sum_mode (the source may have replaced them)
-        HIPCHECK(idx->d_cnorm.ensure((size_t)idx->K));
-        qadc::launch_row_sqnorm(coarse, idx->K, dim, sum_mode, idx->d_cnorm.p, idx->stream);
-    }
-    const float* cnorm = idx->src ? idx->d_cnorm.p : idx->d_cnorm.p + (size_t)sum_mode * idx->K;
-    if (idx->K) {
+    if (f.K) {
         const int chunk = std::min(nq, kCoarseChunk);
-        HIPCHECK(idx->d_cdist.ensure((size_t)chunk * idx->K));
+        HIPCHECK(idx->d_cdist.ensure((size_t)chunk * f.K));
         HIPCHECK(idx->d_qnorm.ensure(chunk));
         if (ma > 256) HIPCHECK(qadc::coarse_nan_unreplayed_reset(idx->stream));
         for (int o = 0; o < nq; o += kCoarseChunk)
-            qadc::launch_coarse_assign(idx->cur_queries + (size_t)o * dim, coarse, std::min(kCoarseChunk, nq - o), idx->K, dim, ma,
-                                       idx->d_qnorm.p, cnorm, sum_mode, idx->d_cdist.p,
-                                       idx->d_assign.p + (size_t)o * ma, idx->stream);
+            qadc::launch_coarse_assign(idx->cur_queries + (size_t)o * f.dim, f.coarse, std::min(kCoarseChunk, nq - o), f.K, f.dim, ma,
+                                       idx->d_qnorm.p, f.cnorm, sum_mode, idx->d_cdist.p, idx->d_assign.p + (size_t)o * ma, idx->stream);
         HIPCHECK(hipGetLastError());
     } else {
         HIPCHECK(hipMemsetAsync(idx->d_assign.p, 0, (size_t)nq * ma * 4, idx->stream));
@@ -475,9 +455,9 @@ int enqueue_assign(qadc_adc_index* idx, int nq, const float* queries, int ma, in
 }
 
 // Waits for the assign copy; refuses a NaN coarse row the selection could not replay (ma > 256: the counter of launch_coarse_assign).
-int wait_assign(qadc_adc_index* idx, int ma) {
+int wait_assign(qadc_adc_index* idx, const Feeders& f, int ma) {
     HIPCHECK(hipEventSynchronize(idx->ev_assign));
-    if (idx->K && ma > 256) {
+    if (f.K && ma > 256) {
         HIPCHECK(hipStreamSynchronize(idx->stream));
         unsigned int unreplayed = 0;
         HIPCHECK(qadc::coarse_nan_unreplayed_read(&unreplayed));
@@ -487,20 +467,19 @@ int wait_assign(qadc_adc_index* idx, int ma) {
     return QADC_OK;
 }
 
-int enqueue_tables(qadc_adc_index* idx, int q0, int nq, int ma, int table_form, int sum_mode) {
+// The tables of queries [q0, q0 + nq) of the call into idx->d_tables.
+int enqueue_tables(qadc_adc_index* idx, const Feeders& f, int q0, int nq, int ma, int table_form, int sum_mode) {
     const int expansion = table_form == 2 ? (ma > 1) : table_form;   // nns_engine: direct for ma == 1 (query_common.hpp:292-297)
-    if (idx->src) {   // a view: the 16-centroid builder of the 4-bit index on the source's quantizers, [nq][ma][M][16]
-        const FeederState& f = idx->src->feed;
-        qadc::launch_build_tables(idx->cur_queries + (size_t)q0 * idx->dim, idx->K ? f.d_coarse.p : nullptr, idx->d_assign.p + (size_t)q0 * ma,
-                                  f.d_codebooks.p, idx->rotated ? f.d_rotation.p : nullptr, nq, ma, idx->nsq, idx->dim, expansion, sum_mode,
+    const float* queries = idx->cur_queries + (size_t)q0 * f.dim;
+    const int32_t* assign = idx->d_assign.p + (size_t)q0 * ma;
+    if (idx->src) {   // a view: the 16-centroid builder of the 4-bit index, [nq][ma][M][16]
+        qadc::launch_build_tables(queries, f.coarse, assign, f.codebooks, f.rotation, nq, ma, idx->nsq, f.dim, expansion, sum_mode,
                                   idx->d_tables.p, idx->stream);
         HIPCHECK(hipGetLastError());
         return QADC_OK;
     }
-    HIPCHECK(qadc::adc::launch_adc_tables(idx->cur_queries + (size_t)q0 * idx->dim, idx->K ? idx->d_coarse.p : nullptr,
-                                          idx->d_assign.p + (size_t)q0 * ma, idx->d_codebooks.p,
-                                          idx->d_cbnorm.p + (size_t)sum_mode * idx->nsq * 256, idx->rotated ? idx->d_rotation.p : nullptr, nq, ma,
-                                          idx->nsq, idx->dim, expansion, sum_mode, idx->d_tables.p, idx->stream));
+    HIPCHECK(launch_adc_tables(queries, f.coarse, assign, f.codebooks, f.cbnorm, f.rotation, nq, ma, idx->nsq, f.dim, expansion,
+                                          sum_mode, idx->d_tables.p, idx->stream));
     return QADC_OK;
 }
 
@@ -515,45 +494,43 @@ int queries_per_pass(const qadc_adc_index* idx, int nq, int ma) {
 // are in device memory.
 int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, int32_t* assign_out,
                  const DeviceOut* out = nullptr, bool d_side = false) {
-    bind_source_feeders(idx);
-    if (int rc = check_search_args(idx, nq, queries, ma, table_form, sum_mode)) return rc;
-    if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
-    HIPCHECK(hipSetDevice(idx->device));
+    Feeders f;
+    if (int rc = resolve_feeders(idx, nq, queries, ma, table_form, sum_mode, &f)) return rc;
+    if (int rc = check_R(R)) return rc;
     const int per = queries_per_pass(idx, nq, ma);
     HIPCHECK(idx->d_tables.ensure((size_t)per * ma * idx->nsq * idx->centroids));
-    if (int rc = enqueue_assign(idx, nq, queries, ma, sum_mode, d_side)) return rc;
-    if (int rc = enqueue_tables(idx, 0, per, ma, table_form, sum_mode)) return rc;   // (runs while the host plans the first scan)
-    if (int rc = wait_assign(idx, ma)) return rc;
+    if (int rc = enqueue_assign(idx, f, nq, queries, ma, sum_mode, d_side)) return rc;
+    if (int rc = enqueue_tables(idx, f, 0, per, ma, table_form, sum_mode)) return rc;   // (runs while the host plans the first scan)
+    if (int rc = wait_assign(idx, f, ma)) return rc;
     if (assign_out) std::memcpy(assign_out, idx->h_assign.p, (size_t)nq * ma * 4);
-    if (per == nq) return scan_batch(idx, nq, ma, idx->h_assign.p, nullptr, idx->d_tables.p, R, sum_mode, out);
+    const bool gather = !out && per < nq;   // a single pass leaves its stream where scan_batch put it
     std::vector<uint64_t> off{0};
     std::vector<uint32_t> keys;
     std::vector<float> vals;
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int n = std::min(per, nq - q0);
         if (q0)   // (the scan before it has been waited for: the table buffer is free)
-            if (int rc = enqueue_tables(idx, q0, n, ma, table_form, sum_mode)) return rc;
-        if (out) {
-            const DeviceOut sub{out->keys + (size_t)q0 * R, out->values + (size_t)q0 * R, out->sizes + q0};
-            if (int rc = scan_batch(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, R, sum_mode, &sub)) return rc;
-            continue;
-        }
-        if (int rc = scan_batch(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, R, sum_mode)) return rc;
+            if (int rc = enqueue_tables(idx, f, q0, n, ma, table_form, sum_mode)) return rc;
+        const DeviceOut sub = out ? DeviceOut{out->keys + (size_t)q0 * R, out->values + (size_t)q0 * R, out->sizes + q0} : DeviceOut{};
+        if (int rc = scan_batch(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, R, sum_mode, out ? &sub : nullptr))
+            return rc;
+        if (!gather) continue;
         const uint64_t base = off.back();
         for (int q = 1; q <= n; ++q) off.push_back(base + idx->stream_off[q]);
         keys.insert(keys.end(), idx->stream_keys.begin(), idx->stream_keys.end());
         vals.insert(vals.end(), idx->stream_vals.begin(), idx->stream_vals.end());
     }
-    if (out) return QADC_OK;
-    idx->stream_off.swap(off);
-    idx->stream_keys.swap(keys);
-    idx->stream_vals.swap(vals);
+    if (gather) {
+        idx->stream_off.swap(off);
+        idx->stream_keys.swap(keys);
+        idx->stream_vals.swap(vals);
+    }
     return QADC_OK;
 }
 
 // ---- the device finish of the entry points ----
 
-bool device_replay_covers(int R) { return R >= 1 && R <= qadc::adc::kAdcReplayMaxR; }
+bool device_replay_covers(int R) { return R >= 1 && R <= kAdcReplayMaxR; }
 
 // The device buffers for the heaps' arrays of a call whose outputs are host memory.
 int host_call_out(qadc_adc_index* idx, int nq, int R, DeviceOut* out) {
@@ -562,15 +539,6 @@ int host_call_out(qadc_adc_index* idx, int nq, int R, DeviceOut* out) {
     HIPCHECK(idx->d_hvals.ensure((size_t)nq * R));
     HIPCHECK(idx->d_hsizes.ensure(nq));
     *out = DeviceOut{idx->d_hkeys.p, idx->d_hvals.p, idx->d_hsizes.p};
-    return QADC_OK;
-}
-
-// nq R keys, nq R values and nq sizes to the caller's host arrays (any may be null): all that crosses the bus after the scan.
-int fetch_heaps(qadc_adc_index* idx, int nq, int R, const DeviceOut& out, uint32_t* keys, float* values, int32_t* sizes) {
-    if (keys) HIPCHECK(hipMemcpyAsync(keys, out.keys, (size_t)nq * R * 4, hipMemcpyDeviceToHost, idx->stream));
-    if (values) HIPCHECK(hipMemcpyAsync(values, out.values, (size_t)nq * R * 4, hipMemcpyDeviceToHost, idx->stream));
-    if (sizes) HIPCHECK(hipMemcpyAsync(sizes, out.sizes, (size_t)nq * 4, hipMemcpyDeviceToHost, idx->stream));
-    HIPCHECK(hipStreamSynchronize(idx->stream));
     return QADC_OK;
 }
 
@@ -587,11 +555,55 @@ int upload_host_heaps(qadc_adc_index* idx, int nq, int R, const DeviceOut& out) 
     HIPCHECK(hipMemcpyAsync(own.keys, keys.data(), keys.size() * 4, hipMemcpyHostToDevice, idx->stream));
     HIPCHECK(hipMemcpyAsync(own.values, values.data(), values.size() * 4, hipMemcpyHostToDevice, idx->stream));
     HIPCHECK(hipMemcpyAsync(own.sizes, sizes.data(), sizes.size() * 4, hipMemcpyHostToDevice, idx->stream));
-    HIPCHECK(qadc::adc::launch_adc_copy_words(own.keys, out.keys, keys.size(), idx->stream));
-    HIPCHECK(qadc::adc::launch_adc_copy_words(own.values, out.values, values.size(), idx->stream));
-    HIPCHECK(qadc::adc::launch_adc_copy_words(own.sizes, out.sizes, sizes.size(), idx->stream));
+    HIPCHECK(launch_adc_copy_words(own.keys, out.keys, keys.size(), idx->stream));
+    HIPCHECK(launch_adc_copy_words(own.values, out.values, values.size(), idx->stream));
+    HIPCHECK(launch_adc_copy_words(own.sizes, out.sizes, sizes.size(), idx->stream));
     HIPCHECK(hipStreamSynchronize(idx->stream));
     return QADC_OK;
+}
+
+// The three shapes of the query entry points.  `produce(out)` runs the batch — scan_batch or search_batch bound to the call's
+// arguments — with the device finish into `out`, or, out null, leaving the ordered stream in idx->stream_*.
+
+// Heaps into host arrays: the device finish and a copy of its arrays when it is asked for and covers R, else the host replay.
+template <typename Produce>
+int heaps_to_host(qadc_adc_index* idx, int nq, int R, uint32_t* keys, float* values, int32_t* sizes, Produce produce) {
+    DeviceGuard guard;
+    if (idx && idx->finish == QADC_ADC_FINISH_DEVICE && nq >= 1 && device_replay_covers(R)) {
+        DeviceOut out;
+        if (int rc = host_call_out(idx, nq, R, &out)) return rc;
+        if (int rc = produce(&out)) return rc;   // nq R keys, nq R values and nq sizes (any may be null) are all that crosses the bus
+        if (keys) HIPCHECK(hipMemcpyAsync(keys, out.keys, (size_t)nq * R * 4, hipMemcpyDeviceToHost, idx->stream));
+        if (values) HIPCHECK(hipMemcpyAsync(values, out.values, (size_t)nq * R * 4, hipMemcpyDeviceToHost, idx->stream));
+        if (sizes) HIPCHECK(hipMemcpyAsync(sizes, out.sizes, (size_t)nq * 4, hipMemcpyDeviceToHost, idx->stream));
+        HIPCHECK(hipStreamSynchronize(idx->stream));
+        return QADC_OK;
+    }
+    if (int rc = produce(nullptr)) return rc;
+    replay_heaps(idx, nq, R, keys, values, sizes);
+    if (idx->finish == QADC_ADC_FINISH_DEVICE) idx->host_finishes += (uint64_t)nq;
+    return QADC_OK;
+}
+
+// Heaps into the caller's device arrays.
+template <typename Produce>
+int heaps_to_device(qadc_adc_index* idx, int nq, int R, uint32_t* d_keys, float* d_values, int32_t* d_sizes, Produce produce) {
+    if (int rc = check_R(R)) return rc;
+    if (!d_keys || !d_values || !d_sizes) return fail(QADC_E_ARG, "d_keys, d_values and d_sizes are required");
+    DeviceGuard guard;
+    const DeviceOut out{d_keys, d_values, d_sizes};
+    if (device_replay_covers(R)) return produce(&out);
+    if (int rc = produce(nullptr)) return rc;
+    return upload_host_heaps(idx, nq, R, out);
+}
+
+// The ordered candidate stream into the caller's buffers.
+template <typename Produce>
+int stream_to_host(qadc_adc_index* idx, int nq, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets, Produce produce) {
+    if (!offsets) return fail(QADC_E_ARG, "offsets is required");
+    DeviceGuard guard;
+    if (int rc = produce(nullptr)) return rc;
+    return copy_stream(idx, nq, cand_capacity, cand_keys, cand_vals, offsets);
 }
 
 struct Scratch {   // device memory of a stateless entry point, freed on every exit path
@@ -656,17 +668,17 @@ int qadc_adc_index_create_view(qadc_adc_index** out, qadc_index* src) {
     idx->centroids = 16;
     idx->device = src->device;
     idx->labeled = src->labeled;
-    std::vector<qadc::adc::Part4> table(src->parts.size());
+    std::vector<Part4> table(src->parts.size());
     for (size_t p = 0; p < src->parts.size(); ++p) {
         const Part& pt = src->parts[p];
         idx->sizes.push_back(pt.n);
-        table[p] = qadc::adc::Part4{pt.d_codes, src->labeled == 1 ? pt.d_labels : nullptr, pt.key_base, 0};
+        table[p] = Part4{pt.d_codes, src->labeled == 1 ? pt.d_labels : nullptr, pt.key_base, 0};
     }
     hipError_t e = hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&idx->ev_assign, hipEventDisableTiming);
     if (e == hipSuccess) e = idx->d_parts4.ensure(std::max<size_t>(table.size(), 1));
     if (e == hipSuccess && !table.empty())
-        e = hipMemcpy(idx->d_parts4.p, table.data(), table.size() * sizeof(qadc::adc::Part4), hipMemcpyHostToDevice);
+        e = hipMemcpy(idx->d_parts4.p, table.data(), table.size() * sizeof(Part4), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)qadc_adc_index_destroy(idx);
         return fail(QADC_E_HIP, std::string("qadc_adc_index_create_view: ") + hipGetErrorString(e));
@@ -747,7 +759,7 @@ int qadc_adc_index_add_partitions(qadc_adc_index* idx, int part_count, const uin
     }
     if (int rc = grow_device(idx->codes, idx->code_bytes, bytes + 16, idx->stream)) return rc;
     if (lab == 1)
-        if (int rc = grow_labels(idx->labels, idx->label_count, std::max<uint64_t>(nlab, 1), idx->stream)) return rc;
+        if (int rc = grow_device(idx->labels, idx->label_count, std::max<uint64_t>(nlab, 1), idx->stream)) return rc;
     for (int p = 0; p < part_count; ++p) {
         if (!sizes[p]) continue;
         HIPCHECK(hipMemcpy(idx->codes.p + off[p], codes[p], (size_t)sizes[p] * idx->nsq, hipMemcpyHostToDevice));
@@ -793,36 +805,20 @@ uint32_t qadc_adc_index_partition_size(const qadc_adc_index* idx, int part) {
 
 int qadc_adc_query_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
                         uint32_t* keys, float* values, int32_t* sizes) {
-    DeviceGuard guard;
-    if (idx && idx->finish == QADC_ADC_FINISH_DEVICE && nq >= 1 && device_replay_covers(R)) {
-        DeviceOut out;
-        if (int rc = host_call_out(idx, nq, R, &out)) return rc;
-        if (int rc = scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode, &out)) return rc;
-        return fetch_heaps(idx, nq, R, out, keys, values, sizes);
-    }
-    if (int rc = scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode)) return rc;
-    replay_heaps(idx, nq, R, keys, values, sizes);
-    if (idx->finish == QADC_ADC_FINISH_DEVICE) idx->host_finishes += (uint64_t)nq;
-    return QADC_OK;
+    return heaps_to_host(idx, nq, R, keys, values, sizes,
+                         [&](const DeviceOut* out) { return scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode, out); });
 }
 
 int qadc_adc_query_scan_device(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, int R, int sum_mode,
                                uint32_t* d_keys, float* d_values, int32_t* d_sizes) {
-    if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
-    if (!d_keys || !d_values || !d_sizes) return fail(QADC_E_ARG, "d_keys, d_values and d_sizes are required");
-    DeviceGuard guard;
-    const DeviceOut out{d_keys, d_values, d_sizes};
-    if (device_replay_covers(R)) return scan_batch(idx, nq, ma, assign, nullptr, d_tables, R, sum_mode, &out);
-    if (int rc = scan_batch(idx, nq, ma, assign, nullptr, d_tables, R, sum_mode)) return rc;
-    return upload_host_heaps(idx, nq, R, out);
+    return heaps_to_device(idx, nq, R, d_keys, d_values, d_sizes,
+                           [&](const DeviceOut* out) { return scan_batch(idx, nq, ma, assign, nullptr, d_tables, R, sum_mode, out); });
 }
 
 int qadc_adc_query_scan_candidates(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R,
                                    int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets) {
-    if (!offsets) return fail(QADC_E_ARG, "offsets is required");
-    DeviceGuard guard;
-    if (int rc = scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode)) return rc;
-    return copy_stream(idx, nq, cand_capacity, cand_keys, cand_vals, offsets);
+    return stream_to_host(idx, nq, cand_capacity, cand_keys, cand_vals, offsets,
+                          [&](const DeviceOut*) { return scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode); });
 }
 
 int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks) {
@@ -830,7 +826,7 @@ int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks) 
     if (int rc = refuse_on_view(idx, "qadc_adc_index_set_pq")) return rc;
     if (dim < 1 || dim % idx->nsq != 0)
         return fail(QADC_E_ARG, "dim = " + std::to_string(dim) + " is not a multiple of sq_count = " + std::to_string(idx->nsq));
-    if (dim > qadc::adc::kAdcMaxDim) return fail(QADC_E_ARG, "dim must be <= " + std::to_string(qadc::adc::kAdcMaxDim));
+    if (dim > kAdcMaxDim) return fail(QADC_E_ARG, "dim must be <= " + std::to_string(kAdcMaxDim));
     DeviceGuard guard;
     HIPCHECK(hipSetDevice(idx->device));
     const size_t rows = (size_t)idx->nsq * 256;
@@ -895,53 +891,36 @@ int qadc_adc_index_set_table_budget(qadc_adc_index* idx, uint64_t bytes) {
 
 int qadc_adc_search(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, uint32_t* keys,
                     float* values, int32_t* sizes, int32_t* assign_out) {
-    DeviceGuard guard;
-    if (idx && idx->finish == QADC_ADC_FINISH_DEVICE && nq >= 1 && device_replay_covers(R)) {
-        DeviceOut out;
-        if (int rc = host_call_out(idx, nq, R, &out)) return rc;
-        if (int rc = search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out, &out)) return rc;
-        return fetch_heaps(idx, nq, R, out, keys, values, sizes);
-    }
-    if (int rc = search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out)) return rc;
-    replay_heaps(idx, nq, R, keys, values, sizes);
-    if (idx->finish == QADC_ADC_FINISH_DEVICE) idx->host_finishes += (uint64_t)nq;
-    return QADC_OK;
+    return heaps_to_host(idx, nq, R, keys, values, sizes,
+                         [&](const DeviceOut* out) { return search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out, out); });
 }
 
 int qadc_adc_search_device(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int R, int table_form, int sum_mode,
                            uint32_t* d_keys, float* d_values, int32_t* d_sizes) {
-    if (R < 1 || R > QADC_ADC_MAX_R) return fail(QADC_E_ARG, "R must be in [1, " + std::to_string(QADC_ADC_MAX_R) + "]");
-    if (!d_keys || !d_values || !d_sizes) return fail(QADC_E_ARG, "d_keys, d_values and d_sizes are required");
-    DeviceGuard guard;
-    const DeviceOut out{d_keys, d_values, d_sizes};
-    if (device_replay_covers(R)) return search_batch(idx, nq, d_queries, ma, R, table_form, sum_mode, nullptr, &out, true);
-    if (int rc = search_batch(idx, nq, d_queries, ma, R, table_form, sum_mode, nullptr, nullptr, true)) return rc;
-    return upload_host_heaps(idx, nq, R, out);
+    return heaps_to_device(idx, nq, R, d_keys, d_values, d_sizes,
+                           [&](const DeviceOut* out) { return search_batch(idx, nq, d_queries, ma, R, table_form, sum_mode, nullptr, out, true); });
 }
 
 int qadc_adc_search_candidates(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,
                                uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets, int32_t* assign_out) {
-    if (!offsets) return fail(QADC_E_ARG, "offsets is required");
-    DeviceGuard guard;
-    if (int rc = search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out)) return rc;
-    return copy_stream(idx, nq, cand_capacity, cand_keys, cand_vals, offsets);
+    return stream_to_host(idx, nq, cand_capacity, cand_keys, cand_vals, offsets,
+                          [&](const DeviceOut*) { return search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out); });
 }
 
 int qadc_adc_search_tables(qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode, int32_t* assign_out,
                            float* tables_out) {
     DeviceGuard guard;
-    bind_source_feeders(idx);
-    if (int rc = check_search_args(idx, nq, queries, ma, table_form, sum_mode)) return rc;
-    HIPCHECK(hipSetDevice(idx->device));
+    Feeders f;
+    if (int rc = resolve_feeders(idx, nq, queries, ma, table_form, sum_mode, &f)) return rc;
     const int per = queries_per_pass(idx, nq, ma);
     const size_t per_query = (size_t)ma * idx->nsq * idx->centroids;
     HIPCHECK(idx->d_tables.ensure((size_t)per * per_query));
-    if (int rc = enqueue_assign(idx, nq, queries, ma, sum_mode)) return rc;
-    if (int rc = wait_assign(idx, ma)) return rc;
+    if (int rc = enqueue_assign(idx, f, nq, queries, ma, sum_mode)) return rc;
+    if (int rc = wait_assign(idx, f, ma)) return rc;
     if (assign_out) std::memcpy(assign_out, idx->h_assign.p, (size_t)nq * ma * 4);
     for (int q0 = 0; q0 < nq && tables_out; q0 += per) {
         const int n = std::min(per, nq - q0);
-        if (int rc = enqueue_tables(idx, q0, n, ma, table_form, sum_mode)) return rc;
+        if (int rc = enqueue_tables(idx, f, q0, n, ma, table_form, sum_mode)) return rc;
         HIPCHECK(hipMemcpyAsync(tables_out + (size_t)q0 * per_query, idx->d_tables.p, (size_t)n * per_query * 4, hipMemcpyDeviceToHost, idx->stream));
         HIPCHECK(hipStreamSynchronize(idx->stream));
     }
@@ -950,9 +929,9 @@ int qadc_adc_search_tables(qadc_adc_index* idx, int nq, const float* queries, in
 
 int qadc_adc_encode_host(int sq_count, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
                          const float* vectors, uint64_t n, int sum_mode, int32_t* assign_out, uint8_t* codes, int device_id) {
-    if ((sq_count != 4 && sq_count != 8 && sq_count != 16) || dim < 1 || dim % sq_count != 0 || dim > qadc::adc::kAdcMaxDim || !codebooks ||
+    if ((sq_count != 4 && sq_count != 8 && sq_count != 16) || dim < 1 || dim % sq_count != 0 || dim > kAdcMaxDim || !codebooks ||
         K < 0 || (K > 0 && !coarse) || (n && (!vectors || !codes)) || (sum_mode != 0 && sum_mode != 1))
-        return fail(QADC_E_ARG, "bad arguments (sq_count 4, 8 or 16; dim a multiple of it, at most " + std::to_string(qadc::adc::kAdcMaxDim) +
+        return fail(QADC_E_ARG, "bad arguments (sq_count 4, 8 or 16; dim a multiple of it, at most " + std::to_string(kAdcMaxDim) +
                                     "; sum_mode 0 or 1)");
     DeviceGuard guard;
     if (int rc = qadc_device_prepare(device_id)) return rc;
@@ -995,7 +974,7 @@ int qadc_adc_encode_host(int sq_count, int dim, const float* codebooks, const fl
         qadc::launch_residual_rotate(d_v, n, dim, d_coarse, d_assign, d_rot, d_x, nullptr);
         d_enc = d_x;
     }
-    HIPCHECK(qadc::adc::launch_adc_encode(d_enc, n, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_codes, nullptr));
+    HIPCHECK(launch_adc_encode(d_enc, n, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_codes, nullptr));
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(codes, d_codes, n * sq_count, hipMemcpyDeviceToHost));
     if (assign_out && K > 0) HIPCHECK(hipMemcpy(assign_out, d_assign, n * 4, hipMemcpyDeviceToHost));

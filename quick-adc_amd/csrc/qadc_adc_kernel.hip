@@ -1,10 +1,10 @@
 // Float ADC over whole-byte PQ codes on gfx950: the GPU form of the reference's scan_standard<uint8_t, NSQ>
 // (query_common.hpp:92-118) as scanner_simple::query_scan drives it (db_query.cpp:26-45).  Host side: csrc/qadc_adc.cpp.
 //
-//   adc_scan_kernel    one workgroup per run of codes of one probed partition: the (query, slot) float table [NSQ][256]
-//                      goes to LDS, each lane sums the NSQ looked-up entries of its codes in the reference's grouping and
-//                      emits (candidate, key, scan index) when candidate < bound[query];
-//   adc_scan4_kernel   the same over the nibble codes of a 4-bit index read in place (scan_4<M>, tables [M][16]): the view;
+//   adc_scan_kernel    one workgroup per run of codes of one probed partition: the (query, slot) float table goes to LDS, each lane
+//                      sums the looked-up entries of its codes in the reference's grouping and emits (candidate, key, scan index)
+//                      when candidate < bound[query].  One body over ByteCodes<NSQ> (tables [NSQ][256], the owned database by
+//                      value) and NibbleCodes<M> (the view: a 4-bit index read in place, scan_4<M>, tables [M][16]);
 //   adc_select_kernel one workgroup per query: bound = the R-th smallest value the query emitted so far (radix select on
 //                      the order-preserving integer image of the floats), the bound of the next level's runs;
 //   adc_pack_kernel    the per-query regions packed densely for one device-to-host copy;
@@ -25,124 +25,77 @@ namespace qadc {
 namespace adc {
 namespace {
 
+template <int BYTES>
+struct alignas(BYTES) CodeWords {   // one code, 4, 8 or 16 bytes = one dword, dwordx2 or dwordx4 load
+    uint32_t w[BYTES / 4];
+};
+
+// What a code is and how its looked-up entries are summed: the only things the scan kernel leaves to a policy.  kBytes =
+// bytes per code (one dword, dwordx2 or dwordx4 load), kTable = floats of one (query, slot) table, sum<SUM>(lds, words) = the
+// candidate of one code in the reference's float grouping (SUM 0 source order, 1 as compiled).
 template <int NSQ>
-struct CodeWords;   // one code = one dword, dwordx2 or dwordx4 load
-template <>
-struct CodeWords<4> { uint32_t w[1]; };
-template <>
-struct CodeWords<8> { uint32_t w[2]; };
-template <>
-struct CodeWords<16> { uint32_t w[4]; };
-
-template <int NSQ>
-__device__ __forceinline__ CodeWords<NSQ> load_code(const uint8_t* p) {
-    CodeWords<NSQ> c;
-    if constexpr (NSQ == 4) {
-        c.w[0] = *reinterpret_cast<const uint32_t*>(p);
-    } else if constexpr (NSQ == 8) {
-        const uint2 v = *reinterpret_cast<const uint2*>(p);
-        c.w[0] = v.x; c.w[1] = v.y;
-    } else {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        c.w[0] = v.x; c.w[1] = v.y; c.w[2] = v.z; c.w[3] = v.w;
-    }
-    return c;
-}
-
-template <int NSQ, int SUM>
-__device__ __forceinline__ float candidate(const float* lds, const CodeWords<NSQ>& c) {
-    float t[NSQ];
+struct ByteCodes {   // scan_standard<uint8_t, NSQ>: one byte per sub-quantizer, tables [NSQ][256]
+    static constexpr int kBytes = NSQ, kTable = NSQ * 256;
+    template <int SUM>
+    static __device__ __forceinline__ float sum(const float* lds, const CodeWords<kBytes>& c) {
+        float t[NSQ];
 #pragma unroll
-    for (int m = 0; m < NSQ; ++m) t[m] = lds[m * 256 + ((c.w[m / 4] >> (8 * (m % 4))) & 0xffu)];
-    if constexpr (SUM == 0) {                                     // source order, from 0 like the reference's loop
-        float s = 0.0f;
+        for (int m = 0; m < NSQ; ++m) t[m] = lds[m * 256 + ((c.w[m / 4] >> (8 * (m % 4))) & 0xffu)];
+        if constexpr (SUM == 0) {                                 // source order, from 0 like the reference's loop
+            float s = 0.0f;
 #pragma unroll
-        for (int m = 0; m < NSQ; ++m) s += t[m];
-        return s;
-    } else if constexpr (NSQ == 4) {
-        return adc_sum4_standard_compiled(t);
-    } else if constexpr (NSQ == 8) {
-        return adc_sum8_standard_compiled(t);
-    } else {
-        return adc_sum8_compiled_first(t);
-    }
-}
-
-constexpr int kUnroll = 4;   // codes per lane in flight
-
-template <int NSQ, int SUM>
-__global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ items, uint32_t first, Db db,
-                                                       const int32_t* __restrict__ assign, int ma,
-                                                       const float* __restrict__ tables, const float* __restrict__ bound,
-                                                       Emit emit) {
-    __shared__ float lds[NSQ * 256];
-    const Item it = items[first + blockIdx.x];
-    const int part = assign[(size_t)it.query * ma + it.slot];
-    const float4* tab = reinterpret_cast<const float4*>(tables + ((size_t)it.query * ma + it.slot) * (NSQ * 256));
-    for (int i = threadIdx.x; i < NSQ * 64; i += kWG) reinterpret_cast<float4*>(lds)[i] = tab[i];
-    const float b = bound[it.query];
-    const uint64_t region = emit.base[it.query];
-    const uint32_t cap = emit.cap[it.query];
-    const uint8_t* codes = db.codes + db.off[part];
-    const uint32_t* labels = db.labels ? db.labels + db.lab_off[part] : nullptr;
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63;
-    const unsigned long long below = (1ull << lane) - 1;
-    for (uint32_t base = 0; base < it.count; base += kWG * kUnroll) {
-        CodeWords<NSQ> c[kUnroll];
-        bool valid[kUnroll];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const uint32_t r = base + u * kWG + threadIdx.x;
-            valid[u] = r < it.count;
-            if (valid[u]) c[u] = load_code<NSQ>(codes + (size_t)(it.start + r) * NSQ);
-        }
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const float v = valid[u] ? candidate<NSQ, SUM>(lds, c[u]) : 0.0f;
-            const bool keep = valid[u] && v < b;                  // NaN, +inf and FLT_MAX never pass (b <= FLT_MAX)
-            const unsigned long long m = __ballot(keep);
-            if (m == 0) continue;
-            const int leader = __builtin_ctzll(m);
-            uint32_t o = 0;
-            if (lane == leader) o = atomicAdd(emit.count + it.query, (uint32_t)__popcll(m));
-            o = __shfl(o, leader) + (uint32_t)__popcll(m & below);
-            if (keep && o < cap) {
-                const uint32_t r = base + u * kWG + threadIdx.x;
-                const size_t at = region + o;
-                emit.vals[at] = v;
-                emit.keys[at] = labels ? labels[it.start + r] : it.start + r;
-                emit.sidx[at] = it.sbase + r;
-            }
+            for (int m = 0; m < NSQ; ++m) s += t[m];
+            return s;
+        } else if constexpr (NSQ == 4) {
+            return adc_sum4_standard_compiled(t);
+        } else if constexpr (NSQ == 8) {
+            return adc_sum8_standard_compiled(t);
+        } else {
+            return adc_sum8_compiled_first(t);
         }
     }
-}
+};
 
 // The nibble form: scan_4<M> (query_common.hpp:59-90) over the partitions of a 4-bit index, read in place.  A code is
 // M/2 bytes = one dwordx2 (M 16) or dwordx4 (M 32) load; sub-quantizer m's entry is table[m][nibble m], nibble m = bits
 // 4(m % 8) .. of word m / 8 (the even sub-quantizer in the low nibble of its byte).  The (query, slot) table [M][16] is 1 or
 // 2 KiB of LDS.  Every lane of a wave reads sub-quantizer m in the same instruction: its 16 entries lie in 16 distinct
-// banks and equal addresses broadcast, so the lookups cannot conflict.  Same Item / Emit contract as adc_scan_kernel.
-template <int M, int SUM>
-__device__ __forceinline__ float candidate4(const float* lds, const CodeWords<M / 2>& c) {
-    float v[M];
+// banks and equal addresses broadcast, so the lookups cannot conflict.
+template <int M>
+struct NibbleCodes {
+    static constexpr int kBytes = M / 2, kTable = M * 16;
+    template <int SUM>
+    static __device__ __forceinline__ float sum(const float* lds, const CodeWords<kBytes>& c) {
+        float v[M];
 #pragma unroll
-    for (int m = 0; m < M; ++m) v[m] = lds[m * 16 + ((c.w[m / 8] >> (4 * (m % 8))) & 15u)];
-    return adc_sum_code<M>(v, SUM, 0.0f);
+        for (int m = 0; m < M; ++m) v[m] = lds[m * 16 + ((c.w[m / 8] >> (4 * (m % 8))) & 15u)];
+        return adc_sum_code<M>(v, SUM, 0.0f);
+    }
+};
+
+// Where a partition lies, from what the kernel was given (its Source): the owned database by value, or a view's partition table.
+struct PartRef { const uint8_t* codes; const uint32_t* labels; uint32_t key_base; };   // labels null: key = key_base + position
+__device__ __forceinline__ PartRef locate(const Db& db, int part) {
+    return PartRef{db.codes + db.off[part], db.labels ? db.labels + db.lab_off[part] : nullptr, 0u};
+}
+__device__ __forceinline__ PartRef locate(const Part4* parts, int part) {
+    const Part4 p = parts[part];
+    return PartRef{p.codes, p.labels, p.key_base};
 }
 
-template <int M, int SUM>
-__global__ __launch_bounds__(kWG) void adc_scan4_kernel(const Item* __restrict__ items, uint32_t first,
-                                                        const Part4* __restrict__ parts, const int32_t* __restrict__ assign,
-                                                        int ma, const float* __restrict__ tables,
-                                                        const float* __restrict__ bound, Emit emit) {
-    constexpr int CS = M / 2;
-    __shared__ float lds[M * 16];
+constexpr int kUnroll = 4;   // codes per lane in flight
+
+template <class Code, int SUM, class Source>
+__global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ items, uint32_t first, Source src,
+                                                       const int32_t* __restrict__ assign, int ma,
+                                                       const float* __restrict__ tables, const float* __restrict__ bound,
+                                                       Emit emit) {
+    constexpr int CS = Code::kBytes;
+    __shared__ float lds[Code::kTable];
     const Item it = items[first + blockIdx.x];
-    const Part4 part = parts[assign[(size_t)it.query * ma + it.slot]];
-    const float4* tab = reinterpret_cast<const float4*>(tables + ((size_t)it.query * ma + it.slot) * (M * 16));
-    for (int i = threadIdx.x; i < M * 4; i += kWG) reinterpret_cast<float4*>(lds)[i] = tab[i];
+    const PartRef part = locate(src, assign[(size_t)it.query * ma + it.slot]);
+    const float4* tab = reinterpret_cast<const float4*>(tables + ((size_t)it.query * ma + it.slot) * Code::kTable);
+    for (int i = threadIdx.x; i < Code::kTable / 4; i += kWG) reinterpret_cast<float4*>(lds)[i] = tab[i];
     const float b = bound[it.query];
     const uint64_t region = emit.base[it.query];
     const uint32_t cap = emit.cap[it.query];
@@ -157,11 +110,11 @@ __global__ __launch_bounds__(kWG) void adc_scan4_kernel(const Item* __restrict__
         for (int u = 0; u < kUnroll; ++u) {
             const uint32_t r = base + u * kWG + threadIdx.x;
             valid[u] = r < it.count;
-            if (valid[u]) c[u] = load_code<CS>(part.codes + (size_t)(it.start + r) * CS);
+            if (valid[u]) c[u] = reinterpret_cast<const CodeWords<CS>*>(part.codes)[it.start + r];
         }
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
-            const float v = valid[u] ? candidate4<M, SUM>(lds, c[u]) : 0.0f;
+            const float v = valid[u] ? Code::template sum<SUM>(lds, c[u]) : 0.0f;
             const bool keep = valid[u] && v < b;                  // NaN, +inf and FLT_MAX never pass (b <= FLT_MAX)
             const unsigned long long m = __ballot(keep);
             if (m == 0) continue;
@@ -456,15 +409,6 @@ __global__ __launch_bounds__(kWG) void adc_copy_words_kernel(const uint32_t* __r
     for (size_t i = (size_t)blockIdx.x * kWG + threadIdx.x; i < n; i += (size_t)gridDim.x * kWG) dst[i] = src[i];
 }
 
-template <int NSQ, int SUM>
-hipError_t launch_scan_t(const Item* items, uint32_t first, uint32_t n_items, Db db, const int32_t* assign, int ma,
-                         const float* tables, const float* bound, Emit emit, hipStream_t s) {
-    hipLaunchKernelGGL((adc_scan_kernel<NSQ, SUM>), dim3(n_items), dim3(kWG), 0, s, items, first, db, assign, ma, tables, bound,
-                       emit);
-    return hipGetLastError();
-}
-
-
 // ---------------------------------------------------------------------------------------------
 // Feeders: what nns_engine(_batch)::process_query does before query_scan (query_common.hpp:194-213, 283-297) and
 // base_pq::encode_multiple_vectors (quantizers.hpp:222-245) for 256 centroids per sub-quantizer.
@@ -622,33 +566,20 @@ __global__ __launch_bounds__(kWG) void adc_encode_kernel(const float* __restrict
 
 }  // namespace
 
-hipError_t launch_adc_scan(int nsq, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, Db db, const int32_t* assign,
+hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const int32_t* assign,
                            int ma, const float* tables, const float* bound, Emit emit, hipStream_t s) {
     if (n_items == 0) return hipSuccess;
-    const bool src = sum_mode == 0;
-    switch (nsq) {
-        case 4: return src ? launch_scan_t<4, 0>(items, first, n_items, db, assign, ma, tables, bound, emit, s)
-                           : launch_scan_t<4, 1>(items, first, n_items, db, assign, ma, tables, bound, emit, s);
-        case 8: return src ? launch_scan_t<8, 0>(items, first, n_items, db, assign, ma, tables, bound, emit, s)
-                           : launch_scan_t<8, 1>(items, first, n_items, db, assign, ma, tables, bound, emit, s);
-        case 16: return src ? launch_scan_t<16, 0>(items, first, n_items, db, assign, ma, tables, bound, emit, s)
-                            : launch_scan_t<16, 1>(items, first, n_items, db, assign, ma, tables, bound, emit, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_adc_scan4(int M, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const Part4* parts,
-                            const int32_t* assign, int ma, const float* tables, const float* bound, Emit emit, hipStream_t s) {
-    if (n_items == 0) return hipSuccess;
-#define QADC_S4(MM, SUM) hipLaunchKernelGGL((adc_scan4_kernel<MM, SUM>), dim3(n_items), dim3(kWG), 0, s, items, first, parts, assign, ma, \
-                                            tables, bound, emit)
-    if (M == 16 && sum_mode == 0) QADC_S4(16, 0);
-    else if (M == 16) QADC_S4(16, 1);
-    else if (M == 32 && sum_mode == 0) QADC_S4(32, 0);
-    else if (M == 32) QADC_S4(32, 1);
-    else return hipErrorInvalidValue;
-#undef QADC_S4
-    return hipGetLastError();
+    const auto scan = [&](auto code, auto src) {
+        const auto kernel = sum_mode == 0 ? adc_scan_kernel<decltype(code), 0, decltype(src)> : adc_scan_kernel<decltype(code), 1, decltype(src)>;
+        hipLaunchKernelGGL(kernel, dim3(n_items), dim3(kWG), 0, s, items, first, src, assign, ma, tables, bound, emit);
+        return hipGetLastError();
+    };
+    if (db.centroids == 256 && db.nsq == 4) return scan(ByteCodes<4>{}, db.bytes);
+    if (db.centroids == 256 && db.nsq == 8) return scan(ByteCodes<8>{}, db.bytes);
+    if (db.centroids == 256 && db.nsq == 16) return scan(ByteCodes<16>{}, db.bytes);
+    if (db.centroids == 16 && db.nsq == 16) return scan(NibbleCodes<16>{}, db.parts);
+    if (db.centroids == 16 && db.nsq == 32) return scan(NibbleCodes<32>{}, db.parts);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_adc_select(int nq, int R, Emit emit, float* bound, hipStream_t s) {

@@ -3,21 +3,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "../host/adc_plan.hpp"   // Item, the level constants, plan_levels
 
 namespace qadc {
 namespace adc {
 
 constexpr int kWG = 256;              // threads per workgroup of every kernel here
-
-// One contiguous run of codes of one probed partition, scanned with the table of (query, slot).
-struct Item {
-    uint32_t query;
-    uint32_t slot;    // position in assign[query][0 .. ma)
-    uint32_t start;   // first code of the run, position inside the partition
-    uint32_t count;   // codes in the run
-    uint32_t sbase;   // scan-order index of the run's first code within its query (probe slots in assign[] order, then position)
-    uint32_t pad[3];
-};
 
 // One region per query, of its own size: query q's emitted candidates (value, key, scan-order index) go to entries
 // [base[q], base[q] + cap[q]) of vals / keys / sidx.
@@ -37,9 +28,6 @@ struct Db {
     const uint64_t* lab_off;  // [part] first label of the partition
 };
 
-// Scans items [first, first + n_items): emits (candidate, key, scan index) for every code with candidate < bound[query].
-hipError_t launch_adc_scan(int nsq, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, Db db, const int32_t* assign,
-                           int ma, const float* tables, const float* bound, Emit emit, hipStream_t s);
 // A 4-bit database read where a qadc_index keeps it (the view of qadc_adc_index_create_view): every partition is an
 // allocation of its own, row-major [n][M/2], 16-byte aligned; key = labels[position], else key_base + position.
 struct Part4 {
@@ -48,16 +36,23 @@ struct Part4 {
     uint32_t key_base;
     uint32_t pad;
 };
-// launch_adc_scan for nibble codes, scan_4<M> (query_common.hpp:59-90), M 16 or 32: the same items, bounds and Emit; tables
-// [nq][ma][M][16], summed as adc_sum_code<M> (csrc/qadc_float_sum.h).
-hipError_t launch_adc_scan4(int M, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const Part4* parts,
-                            const int32_t* assign, int ma, const float* tables, const float* bound, Emit emit, hipStream_t s);
+
+// The database launch_adc_scan reads.  centroids 256: nsq 4, 8 or 16 whole-byte codes in `bytes`, tables [nq][ma][nsq][256] (scan_standard<uint8_t,
+// NSQ>).  centroids 16: nsq 16 or 32 nibble codes in `parts`, tables [nq][ma][nsq][16] summed as adc_sum_code<M> (scan_4<M>, query_common.hpp:59-90).
+struct ScanDb {
+    int nsq, centroids;
+    Db bytes;             // a kernel argument by value: the owned index's code loads are global loads
+    const Part4* parts;   // device memory, one entry per partition
+};
+
+// Scans items [first, first + n_items): emits (candidate, key, scan index) for every code with candidate < bound[query].
+hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const int32_t* assign,
+                           int ma, const float* tables, const float* bound, Emit emit, hipStream_t s);
 // bound[q] = min(bound[q], the R-th smallest of the values query q has stored so far) where it stored at least R.
 hipError_t launch_adc_select(int nq, int R, Emit emit, float* bound, hipStream_t s);
 // Packs the stored records of every query densely in query order: record sum_{j<q} stored_j + i of `out` = three words
 // (value bits, key, scan index).
 hipError_t launch_adc_pack(int nq, Emit emit, uint32_t* out, hipStream_t s);
-
 
 // The device finish.
 constexpr int kOrderLds = 4096;       // entries adc_order_kernel sorts in LDS (8 bytes each); longer streams take radix passes

@@ -22,229 +22,290 @@ thread_local std::string g_err;
 
 namespace {
 
-// Level boundaries in the concatenated scan position space of one query.
-void level_bounds(const qadc_index* idx, uint64_t* L) {
-    L[0] = 0;
-    uint64_t b = std::max<uint64_t>(idx->level_base, 16);
-    for (int k = 1; k < kMaxLevels; ++k) {
-        L[k] = b;
-        b = (b > (UINT64_MAX >> 8)) ? UINT64_MAX : b * std::max<uint64_t>(idx->level_growth, 2);
-    }
-    L[kMaxLevels] = UINT64_MAX;
-}
-
-// What the planner hands to the launcher: the work items of a batch in upload order.
-struct BatchPlan {
-    std::vector<ScanItem> all_items;             // runs, grouped by bound level (Slot::launches indexes into it)
-    std::vector<StartItem> sitems_a, sitems_b;   // pre-scan: phase A = unfiltered sample, phase B = filtered remainder
-    std::vector<uint32_t> fc_init;               // per query: {sample values, capacity} of its pre-scan buffer
-    uint64_t fc_stride = 1;
+// What the stages of plan_and_launch hand on to each other: the layouts of the batch's upload and result blocks.
+struct Staged {
+    bool alone = false;            // nothing else in flight: a synchronous call (see launch_wgq_batch)
+    size_t in_bytes = 0, off_tables = 0, off_inj = 0, off_hassign = 0;   // upload block
+    size_t state_bytes = 0, off_heaps = 0;
+    bool dev_stream = false;       // the ordered streams (also) stay in device memory
+    bool any_split6 = false;
 };
 
-// Host planning of one batch: cuts every query's scan order into bound levels, emits the runs (ScanItem) and the
-// pre-scan items (StartItem), and decides kernel and grid per level launch (Slot::launches).  No GPU calls.
-int plan_batch(qadc_index* idx, Slot& s, BatchPlan& plan) {
-    const int M = idx->M, cs = idx->cs, nq = s.nq, ma = s.ma;
-    const uint32_t cpl = 16 / cs;
-    uint64_t L[kMaxLevels + 1];
-    level_bounds(idx, L);
-    std::vector<std::vector<ScanItem>> per_level(kMaxLevels);
-    const int k0 = (s.mode != 1 && idx->head_level > 0) ? idx->head_level : 0;   // levels < k0 belong to the head launch
-    s.head_codes = k0 ? L[k0] : 0;
-    std::vector<StartItem>& sitems_a = plan.sitems_a;
-    std::vector<StartItem>& sitems_b = plan.sitems_b;
-    std::vector<uint32_t>& fc_init = plan.fc_init;
-    uint64_t& fc_stride = plan.fc_stride;
-    fc_init.assign(2 * (size_t)nq, 0);
-    fc_stride = 1;
-    s.start_codes = 0;
-    for (int q = 0; q < nq; ++q) {
-        uint64_t c = 0;
-        uint64_t stotal = 0;
-        // the starts of a partition this call pre-scans: all of them, or (mode 1) this rank's slice, cut at
-        // multiples of 16 codes so that every slice starts on a 16-byte boundary; (mode 2) none
-        auto starts_range = [&](const Part& pt, uint64_t& lo, uint64_t& len) {
-            lo = 0;
-            len = s.mode == 2 ? 0 : pt.start_n;
-            if (s.mode == 1 && s.pre_nslices > 1) {
-                lo = ((uint64_t)pt.start_n * s.pre_slice / s.pre_nslices) & ~15ull;
-                const uint64_t hi = s.pre_slice + 1 == s.pre_nslices
-                                        ? pt.start_n : (((uint64_t)pt.start_n * (s.pre_slice + 1) / s.pre_nslices) & ~15ull);
-                len = hi > lo ? hi - lo : 0;
-            }
-        };
-        if (s.float_path)
-            for (int a = 0; a < ma; ++a) {
-                const int p = s.assign[(size_t)q * ma + a];
-                if (p >= 0 && p < (int)idx->parts.size()) {
-                    uint64_t lo, len;
-                    starts_range(idx->parts[p], lo, len);
-                    stotal += len;
-                }
-            }
-        // two-phase pre-scan only pays (and is only needed) when the starts are many
-        uint64_t sample = (s.full_prescan || stotal <= 2ull * idx->prescan_sample) ? stotal : idx->prescan_sample;
-        uint64_t soff = 0;
-        for (int a = 0; a < ma; ++a) {
-            const int p = s.assign[(size_t)q * ma + a];
-            if (p < 0 || p >= (int)idx->parts.size())
-                return fail(QADC_E_ARG, "assign[] names a partition that does not exist");
-            const Part& pt = idx->parts[p];
-            if (pt.global_n == 0) continue;  // empty partition: db_query_4.cpp:291-293
-            uint64_t slo = 0, slen = 0;
-            if (s.float_path) starts_range(pt, slo, slen);
-            if (slen) {
-                const uint8_t* sc = (pt.d_starts ? pt.d_starts : pt.d_codes) + slo * cs;
-                const uint64_t in_a = soff < sample ? std::min<uint64_t>(slen, sample - soff) : 0;
-                StartItem si;
-                si.table = (uint32_t)((size_t)q * ma + a);
-                si.query = (uint32_t)q;
-                if (in_a) {
-                    si.codes = sc;
-                    si.n = (uint32_t)in_a;
-                    si.out_off = (uint32_t)soff;
-                    si.filter = 0;
-                    sitems_a.push_back(si);
-                }
-                if (in_a < slen) {
-                    si.codes = sc + in_a * cs;
-                    si.n = (uint32_t)(slen - in_a);
-                    si.out_off = 0;
-                    si.filter = 1;
-                    sitems_b.push_back(si);
-                }
-                soff += slen;
-                s.start_codes += slen;
-            }
-            if (pt.n == 0 || s.mode == 1) continue;   // no codes of the partition here (only its starts replica) / pre-scan only
-            uint64_t prev = 0;
-            for (int k = 0; k < kMaxLevels && prev < pt.n; ++k) {
-                uint64_t cut = pt.n;
-                if (L[k + 1] < c + pt.n) {
-                    cut = L[k + 1] > c ? L[k + 1] - c : 0;
-                    cut -= cut % cpl;  // keep every run 16-byte aligned
-                }
-                if (cut <= prev) continue;
-                if (k < k0) {                                 // scanned by the head launch (same cut: scan_query_kernel, HEAD)
-                    prev = cut;
-                    continue;
-                }
-                // runs longer than 2^31 codes are cut so that 32-bit vector indices cannot wrap
-                for (uint64_t b0 = prev; b0 < cut;) {
-                    const uint64_t len = std::min<uint64_t>(cut - b0, 1ull << 31);
-                    ScanItem it;
-                    it.codes = pt.d_codes + b0 * cs;
-                    it.labels = pt.d_labels;
-                    it.n = (uint32_t)len;
-                    it.pos0 = (uint32_t)b0;
-                    it.key_base = pt.key_base + pt.first_pos;
-                    it.table = (uint32_t)((size_t)q * ma + a);
-                    it.query = (uint32_t)q;
-                    it.order = ((uint32_t)k << 16) | (uint32_t)a;
-                    // padding-lane replay of the partition's last code (simd_layout.hpp:46-50, simd_scan.hpp:67)
-                    it.dup_pos = (pt.first_pos + pt.n == pt.global_n) ? pt.n - 1u : 0xffffffffu;
-                    it.dup_reps = (16u - pt.global_n % 16u) % 16u;
-                    // a long run that starts on a tile of the partition's byte-plane copy may take the split form
-                    it.split = pt.d_split && b0 % kSplitTile == 0 && len >= std::max<uint64_t>(idx->split_min_run, idx->small_run)
-                                   ? pt.d_split + b0 / kSplitTile * (uint64_t)kSplitBytes * kSplitTile : nullptr;
-                    per_level[k].push_back(it);
-                    b0 += len;
-                }
-                prev = cut;
-            }
-            c += pt.n;
-        }
-        // survivors of the filter: expected R * stotal / sample; 16x head-room, the overflow flag catches the rest
-        uint64_t cap = sample;
-        if (sample < stotal)
-            cap += std::min<uint64_t>(stotal - sample, std::max<uint64_t>(16ull * s.R * ((stotal + sample - 1) / sample), 4096));
-        if (s.mode == 2) sample = cap = s.inj_n;              // the gathered values are the whole "pre-scan output"
-        fc_init[2 * q] = (uint32_t)sample;
-        fc_init[2 * q + 1] = (uint32_t)cap;
-        fc_stride = std::max<uint64_t>(fc_stride, cap);
-    }
-    size_t nitems = 0;
-    for (auto& v : per_level) nitems += v.size();
-    std::vector<ScanItem>& all_items = plan.all_items;
-    all_items.assign(nitems, ScanItem());
-    s.launches.clear();
-    size_t off = 0;
-    const int wgs_cap = idx->wgs_per_item > 0 ? idx->wgs_per_item : (M == 16 ? 1024 : 512);   // (r02 sweep: 1024 reaches the streaming ceiling of the "probe" variant, 512 is 1.6 % below)
-    for (int k = 0; k < kMaxLevels; ++k) {
-        if (per_level[k].empty()) continue;
-        // one launch for the short runs of the level, one for the long ones (one more for those of them with a byte-plane copy)
-        for (int cls = 0; cls < 3; ++cls) {
-            const int small = cls == 0 ? 1 : 0;
-            uint64_t maxn = 0, minn = ~0ull, codes = 0;
-            size_t cnt = 0;
-            bool same = true;
-            for (auto& it : per_level[k]) {
-                if ((it.n < idx->small_run) != (small == 1)) continue;
-                if (!small && (it.split != nullptr) != (cls == 2)) continue;
-                if (cnt) {
-                    const ScanItem& f = all_items[off];
-                    same = same && it.codes == f.codes && it.n == f.n && it.pos0 == f.pos0 && it.labels == f.labels &&
-                           it.key_base == f.key_base && it.dup_pos == f.dup_pos && it.dup_reps == f.dup_reps;
-                }
-                all_items[off + cnt++] = it;
-                maxn = std::max<uint64_t>(maxn, it.n);
-                minn = std::min<uint64_t>(minn, it.n);
-                codes += it.n;
-            }
-            if (!cnt) continue;
-            const uint64_t nvec = (maxn + cpl - 1) / cpl;
-            LevelLaunch ll;
-            ll.first = off;
-            ll.nitems = (int)cnt;
-            ll.small = small == 1;
-            ll.maxn = maxn;
-            ll.early = false;
-            ll.shared = !ll.small && same && cnt >= 2 && idx->share_variant != 0;
-            ll.mq = ll.shared && idx->mq;
-            ll.split = cls == 2 && !ll.shared;
-            ll.split6 = ll.split && idx->split6_min_run != 0 && minn >= idx->split6_min_run;
-            if (ll.mq) {
-                // 8 queries per pass (scan_i8_mq_kernel): 256-thread workgroups, ~64 Ki codes each, groups of 8
-                // queries as L2-sharing siblings
-                const uint64_t tiles = std::max<uint64_t>((nvec + 255) / 256, 1);
-                uint64_t w = idx->wgs_per_item > 0 ? (uint64_t)idx->wgs_per_item
-                                                   : (maxn + kMqCodesPerWg - 1) / kMqCodesPerWg;
-                const uint64_t ngroups = (cnt + 7) / 8;
-                w = std::max<uint64_t>(w, (kMqMinWgs + ngroups - 1) / ngroups);   // >= 2 rounds of the 2048 resident workgroups
-                w = std::min<uint64_t>(std::min<uint64_t>(w, 65536), std::max<uint64_t>(tiles / kMqMinTiles, 1));
-                if (w >= 8) w &= ~7ull;
-                ll.wgs = (int)w;
-            } else if (ll.shared) {
-                // Queries of a batch over the same codes (flat database; IVF queries probing the same cell): the
-                // sibling-major launch makes them share every tile through one XCD's L2, so the codes cross the
-                // HBM interface about once per LAUNCH, not once per query, and the launch is bound by the LDS
-                // lookup rate instead.  Workgroups per run: ~2M codes each (amortises the table build, leaves the
-                // dispatcher room to balance), a multiple of 8 so that the XCD decode applies.
-                uint64_t w = idx->wgs_per_item > 0 ? (uint64_t)idx->wgs_per_item
-                                                   : (maxn + kShareCodesPerWg - 1) / kShareCodesPerWg;
-                w = std::min<uint64_t>(std::max<uint64_t>(w, 64), 512);
-                w = std::min<uint64_t>(w, std::max<uint64_t>((nvec + 4095) / 4096, 1));
-                if (w >= 8) w &= ~7ull;
-                ll.wgs = (int)w;
-            } else if (ll.small) {
-                // enough workgroups to fill the chip, but no more: each one pays a table build + bound fetch
-                const uint64_t want = std::max<uint64_t>(1, 4096 / cnt);
-                ll.wgs = (int)std::min<uint64_t>(std::max<uint64_t>((nvec + kSmallVecPerWg - 1) / kSmallVecPerWg, 1), want);
-            }
-            else {
-                // each streaming workgroup builds a 64-128 KiB table: with many runs in the launch, give every
-                // workgroup more tiles instead of more workgroups per run (the split form: at least one 16 Ki-code tile each)
-                const uint64_t want = std::max<uint64_t>(1, 8192 / cnt);
-                const uint64_t units = ll.split ? (maxn + kSplitTile - 1) / kSplitTile : (nvec + 4095) / 4096;
-                ll.wgs = (int)std::min<uint64_t>(std::max<uint64_t>(units, 1), std::min<uint64_t>(wgs_cap, want));
-            }
-            ll.codes = codes;
-            s.launches.push_back(ll);
-            off += cnt;
-        }
-    }
-
+// ---- upload: ONE block, ONE copy (enqueued by plan_and_launch: upload_and_wait) ----
+int stage_upload(qadc_index* idx, Slot& s, const BatchPlan& plan, Staged& g) {
+    const int nq = s.nq, ma = s.ma;
+    const size_t nitems = plan.all_items.size();
+    const size_t nt = (size_t)nq * ma * idx->M * 16;
+    const size_t na = plan.sitems_a.size(), nb = plan.sitems_b.size();
+    const size_t tables_bytes = s.float_path ? (s.device_tables ? 0 : nt * sizeof(float)) : (s.front_sharded ? 0 : nt);
+    const size_t inj_bytes = s.mode == 2 ? sizeof(float) * (size_t)nq * s.inj_n : 0;
+    const size_t hassign_bytes = s.head_codes ? sizeof(int32_t) * (size_t)nq * ma : 0;  // assign[] for the head launch (it walks the partition table itself)
+    auto place = [&g](size_t bytes) {                          // the next region of the block: 16-byte aligned
+        const size_t off = g.in_bytes;
+        g.in_bytes = (off + bytes + 15) & ~(size_t)15;
+        return off;
+    };
+    const size_t off_items = place(nitems * sizeof(ScanItem)), off_sitems = place((na + nb) * sizeof(StartItem));
+    const size_t off_init = place(plan.fc_init.size() * sizeof(uint32_t));
+    g.off_tables = place(tables_bytes);
+    g.off_inj = place(inj_bytes);
+    g.off_hassign = place(hassign_bytes);
+    HIPCHECK(s.h_in.ensure(g.in_bytes));
+    HIPCHECK(s.d_in.ensure(g.in_bytes));
+    if (nitems) std::memcpy(s.h_in.p + off_items, plan.all_items.data(), nitems * sizeof(ScanItem));
+    if (na) std::memcpy(s.h_in.p + off_sitems, plan.sitems_a.data(), na * sizeof(StartItem));
+    if (nb) std::memcpy(s.h_in.p + off_sitems + na * sizeof(StartItem), plan.sitems_b.data(), nb * sizeof(StartItem));
+    std::memcpy(s.h_in.p + off_init, plan.fc_init.data(), plan.fc_init.size() * sizeof(uint32_t));
+    if (s.float_path && !s.device_tables) std::memcpy(s.h_in.p + g.off_tables, s.tables, nt * sizeof(float));
+    if (!s.float_path && !s.front_sharded) std::memcpy(s.h_in.p + g.off_tables, s.qtables_in.data(), nt);
+    if (inj_bytes) std::memcpy(s.h_in.p + g.off_inj, s.inj_vals.data(), inj_bytes);
+    if (hassign_bytes) std::memcpy(s.h_in.p + g.off_hassign, s.assign.data(), hassign_bytes);
+    s.d_items = reinterpret_cast<ScanItem*>(s.d_in.p + off_items);
+    s.d_sitems = reinterpret_cast<StartItem*>(s.d_in.p + off_sitems);
+    s.d_fc_init = reinterpret_cast<uint32_t*>(s.d_in.p + off_init);
+    s.d_ftables_in = reinterpret_cast<float*>(s.d_in.p + g.off_tables);
     return QADC_OK;
+}
+
+// state block: [CandHeader, 64 B][QueryState[nq]]; result block: [QueryOut[nq]][u64 entries[out_cap]]
+int bind_state_and_result(qadc_index* idx, Slot& s, Staged& g) {
+    const int nq = s.nq, ma = s.ma;
+    g.state_bytes = 64 + sizeof(QueryState) * (size_t)nq;
+    s.dev_replay = s.mode != 1 && idx->device_replay_nq > 0 && nq >= replay_threshold(idx, g.alone) && s.R <= 4096;
+    g.off_heaps = sizeof(QueryOut) * (size_t)nq + sizeof(uint64_t) * (size_t)s.out_cap;
+    const size_t heaps_bytes = s.dev_replay ? (sizeof(uint64_t) * (size_t)s.R + sizeof(uint32_t)) * (size_t)nq : 0;
+    const size_t result_bytes = std::max(g.off_heaps + heaps_bytes, (sizeof(float) * (size_t)s.R + sizeof(uint32_t)) * (size_t)nq);
+    HIPCHECK(s.d_state.ensure(g.state_bytes));
+    if (int rc = map_result_block(s, result_bytes)) return rc;
+    unsigned char* d_result = s.d_result_mapped;
+    s.d_hdr = reinterpret_cast<CandHeader*>(s.d_state.p);
+    s.d_qs = reinterpret_cast<QueryState*>(s.d_state.p + 64);
+    s.d_qout = reinterpret_cast<QueryOut*>(d_result);
+    s.d_entries = reinterpret_cast<uint64_t*>(d_result + sizeof(QueryOut) * (size_t)nq);
+    s.h_qout = reinterpret_cast<QueryOut*>(s.h_result.p);
+    s.h_entries = reinterpret_cast<uint64_t*>(s.h_result.p + sizeof(QueryOut) * (size_t)nq);
+    s.h_heaps = reinterpret_cast<uint64_t*>(s.h_result.p + g.off_heaps);
+    s.h_heap_sizes = reinterpret_cast<uint32_t*>(s.h_result.p + g.off_heaps + sizeof(uint64_t) * (size_t)s.R * nq);
+    s.dist_batch = idx->dist != nullptr;
+    g.dev_stream = s.dev_replay || s.dist_batch;          // the native multi-GPU merge gathers from device memory
+    if (g.dev_stream) HIPCHECK(s.d_stream.ensure(s.out_cap));
+    s.h_export = reinterpret_cast<float*>(s.h_result.p);
+    s.h_export_flags = reinterpret_cast<uint32_t*>(s.h_result.p + sizeof(float) * (size_t)s.R * nq);
+    HIPCHECK(s.d_cands.ensure((size_t)nq * s.cap_q));
+    HIPCHECK(s.d_qtables.ensure((size_t)nq * ma * idx->M * 16));
+    // the 6-plane split form's deferred byte per table, computed where the int8 tables become known (launch_front)
+    for (auto& ll : s.launches) g.any_split6 = g.any_split6 || ll.split6;
+    if (g.any_split6) HIPCHECK(s.d_plane_sel.ensure((size_t)nq * ma));
+    return QADC_OK;
+}
+
+int record_done(Slot& s, hipStream_t st) {
+    if (!s.ev_done) HIPCHECK(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(s.ev_done, st));
+    return QADC_OK;
+}
+
+// The front of the batch on st: the float chain (table build, pre-scan, selects, quantizer -> s.d_qtables), or the caller's int8
+// tables taken as they are.  s.d_qt = the tables the scan reads.  A pre-scan-only batch (mode 1) ends here.
+int launch_front(qadc_index* idx, Slot& s, const BatchPlan& plan, const Staged& g, hipStream_t st) {
+    const int M = idx->M, nq = s.nq, ma = s.ma;
+    const size_t table_dim = (size_t)M * 16, nt = (size_t)nq * ma * table_dim;
+    const size_t na = plan.sitems_a.size(), nb = plan.sitems_b.size();
+    uint64_t fc_stride = plan.fc_stride;
+    s.d_qt = s.d_qtables.p;
+    if (!s.float_path) {
+        s.d_qt = s.front_sharded ? s.d_qtables.p                             // (a sharded-front batch redone here: the gathered tables)
+                                 : reinterpret_cast<const int8_t*>(s.d_in.p + g.off_tables);     // caller's int8 tables, as uploaded
+        if (g.any_split6) launch_plane_choice(s.d_qt, nq * ma, s.d_plane_sel.p, st);
+        if (idx->profile) { HIPCHECK(prof_event(s, st)); HIPCHECK(prof_event(s, st)); }
+        return QADC_OK;
+    }
+    float* d_ft = s.d_ftables_in;
+    if (s.device_tables) {
+        // residuals + float tables built on the GPU from the queries uploaded by search_submit
+        HIPCHECK(s.d_ftables.ensure(nt));
+        d_ft = s.d_ftables.p;
+        HIPCHECK(hipStreamWaitEvent(st, s.ev_feed, 0));
+        build_float_tables(idx, s.d_queries.p, nq, ma, s.d_assign.p, d_ft, st);
+    }
+    HIPCHECK(s.d_fc.ensure((size_t)nq * fc_stride));
+    if (idx->profile) HIPCHECK(prof_event(s, st));
+    auto wgs_for = [](const std::vector<StartItem>& v) {
+        uint32_t maxs = 0;
+        for (auto& si : v) maxs = std::max(maxs, si.n);
+        return (int)std::min<uint32_t>(std::max<uint32_t>((maxs + 4095) / 4096, 1), 512);
+    };
+    const int tda = (int)(ma * table_dim);
+    // phase A: the sample, unfiltered -> its R-th smallest; phase B: the rest, keeping only values <= that.
+    // The LAST select of the chain also quantizes the query's tables (QuantizerMAX) in the same workgroup.
+    // every query pre-scans the same starts (flat database, or one shared probe): 8 queries per pass
+    auto shared_items = [&](const std::vector<StartItem>& v) {
+        if (v.size() < 2) return false;
+        for (auto& si : v)
+            if (si.codes != v[0].codes || si.n != v[0].n || si.out_off != v[0].out_off || si.filter != v[0].filter) return false;
+        return true;
+    };
+    auto start_scan = [&](const std::vector<StartItem>& v, const StartItem* d_v) {
+        if (shared_items(v))
+            launch_start_scan_mq(M, idx->sum_mode, d_v, (int)v.size(), std::min(2 * wgs_for(v), 1024), d_ft, s.d_fc.p, fc_stride, s.d_fc_init,
+                                 s.d_qs, st);
+        else
+            launch_start_scan_f32(M, idx->sum_mode, d_v, (int)v.size(), wgs_for(v), d_ft, s.d_fc.p, fc_stride, s.d_fc_init, s.d_qs, st);
+    };
+    if (na) start_scan(plan.sitems_a, s.d_sitems);
+    if (nb) {
+        // (with a phase B the first select only has to bound the R-th smallest from above: 2 digit passes)
+        launch_select_kth(s.d_fc.p, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 2, nullptr, nullptr, tda, 0, st);
+        start_scan(plan.sitems_b, s.d_sitems + na);
+    }
+    if (s.mode == 1) {
+        // pre-scan only: the exact R-th smallest of this rank's slice, and the R smallest values themselves,
+        // stored straight into the pinned result block; nothing else runs
+        float* d_exp = reinterpret_cast<float*>(s.d_result_mapped);
+        uint32_t* d_expf = reinterpret_cast<uint32_t*>(s.d_result_mapped + sizeof(float) * (size_t)s.R * nq);
+        launch_select_kth(s.d_fc.p, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 4, nullptr, nullptr, tda, 0, st,
+                          d_exp, d_expf);
+        HIPCHECK(hipGetLastError());
+        if (idx->profile) HIPCHECK(prof_event(s, st));
+        return record_done(s, st);
+    }
+    const float* d_sel = s.d_fc.p;
+    if (s.mode == 2) {
+        // the ranks' gathered smallest values stand in for the pre-scan output
+        d_sel = reinterpret_cast<const float*>(s.d_in.p + g.off_inj);
+        fc_stride = s.inj_n;
+        launch_prescan_minmax(d_sel, s.inj_n, nq, s.d_qs, st);
+    }
+    launch_select_kth(d_sel, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 4, d_ft, s.d_qtables.p, tda,
+                      idx->quant_mode, st, nullptr, nullptr, nullptr, 0, g.any_split6 ? s.d_plane_sel.p : nullptr);
+    if (idx->profile) HIPCHECK(prof_event(s, st));
+    return QADC_OK;
+}
+
+void launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, hipStream_t str) {
+    if (ll.small)
+        launch_scan_i8_small(idx->M, s.d_items + ll.first, ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p,
+                             s.cap_q, (uint32_t)s.R, str);
+    else if (ll.mq)
+        launch_scan_i8_mq(idx->M, s.d_items + ll.first, ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q,
+                          (uint32_t)s.R, str, /*narrow=*/ll.nitems <= 4 ? 1 : 0);   // (8 queries per pass: the 8-seat
+                                                               // build, see scan_i8_mq_kernel; <= 4 runs: the build with the 4-seat body)
+    else
+        launch_scan_i8(idx->M, ll.shared ? (idx->share_variant & ~32) : (variant & ~(64 | 32)) | (ll.split ? 32 : 0), s.d_items + ll.first,
+                       ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str,
+                       ll.split6 ? s.d_plane_sel.p : nullptr,
+                       ll.split6 && idx->profile ? reinterpret_cast<unsigned long long*>(s.d_hdr->pad) : nullptr);
+}
+
+int launch_head(qadc_index* idx, Slot& s, const Staged& g, hipStream_t str) {
+    // ONE launch scans the first head_codes codes of every query (bound levels 0..k0-1): every query's scan order
+    // split over G workgroups that refresh their bound in LDS, instead of k0 dependent launches of a few
+    // microseconds of work each.  It emits into the same candidate regions / level-0 histogram the levels use.
+    const int nq = s.nq;
+    QueryKernelArgs H{};
+    H.parts = idx->d_partdesc.p;
+    H.assign = reinterpret_cast<const int32_t*>(s.d_in.p + g.off_hassign);
+    H.ma = s.ma;
+    H.qtables = const_cast<int8_t*>(s.d_qt);
+    H.R = (uint32_t)s.R;
+    H.head_codes = s.head_codes;
+    H.qstates = s.d_qs;
+    H.cand_regions = s.d_cands.p;
+    H.cand_cap = s.cap_q;
+    H.hdr = s.d_hdr;
+    H.nontemporal = 0;                                   // the queries of a batch share the head of a flat list through L2
+    int G = std::min<int>(nq <= 2 ? idx->wgq_split : std::min(idx->wgq_split, kSplitBatch), std::max(1, 256 / nq));   // (as launch_wgq_batch)
+    G = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)G, s.head_codes / 16384));
+    H.G = G;
+    HIPCHECK(launch_scan_query(idx->M, nq, H, str));
+    idx->prof.head_launches++;
+    return QADC_OK;
+}
+
+// ---- scan levels: the head and the early levels behind the front on st, the others on the main stream ----
+int launch_levels(qadc_index* idx, Slot& s, const Staged& g, hipStream_t st) {
+    const hipStream_t main_stream = idx->stream;
+    // a database that fits the 256 MiB Infinity Cache is re-read from it by every query: keep the default
+    // cache policy there; non-temporal loads only pay for lists that stream from HBM anyway
+    uint64_t db_bytes = 0;
+    for (auto& p : idx->parts) db_bytes += (uint64_t)p.n * idx->cs;
+    const int variant = db_bytes <= (200ull << 20) ? (idx->variant & ~4) : idx->variant;
+    // The first levels of a batch are short launches in a dependent chain (each level's bound needs the previous
+    // levels' candidates): latency, not work.  The head launch and the levels with short runs join the front — same
+    // stream, after the quantizer — and so run under the previous batch's long levels instead of in front of this
+    // batch's; only the long levels stay on the main stream.  Front-stream kernels only find room as workgroups of
+    // the long launches retire, so a level with real work is slower there than on the main stream: runs of <= 2 Mi
+    // codes go early (125M x 32 queries: 1.143 -> 1.10 ms per step; 1B x 32: -1 %), 8 Mi already costs more than it hides.
+    size_t n_early = 0;
+    uint64_t batch_codes = 0;
+    for (auto& ll : s.launches) batch_codes += ll.codes;
+    if (st != main_stream && (s.mode == 0 || s.mode == 2) && batch_codes >= kFrontMinBatch)
+        while (n_early < s.launches.size() && s.launches[n_early].maxn <= idx->front_run_max) ++n_early;
+    if (n_early == s.launches.size() && n_early) --n_early;        // the last level closes the batch on the main stream
+    // the head precedes every level: with the early levels (or on request) it joins the front as well
+    bool head_pending = s.head_codes != 0;
+    if (head_pending && st != main_stream) {
+        if (int rc = launch_head(idx, s, g, st)) return rc;
+        head_pending = false;
+    }
+    for (size_t li = 0; li < n_early; ++li) {
+        s.launches[li].early = true;
+        s.launches[li].ev = -1;
+        launch_level(idx, s, s.launches[li], variant, st);
+    }
+    if (st != main_stream) {
+        if (!s.ev_front) HIPCHECK(hipEventCreateWithFlags(&s.ev_front, hipEventDisableTiming));
+        HIPCHECK(hipEventRecord(s.ev_front, st));
+        st = main_stream;
+        HIPCHECK(hipStreamWaitEvent(st, s.ev_front, 0));
+    }
+    if (head_pending)
+        if (int rc = launch_head(idx, s, g, st)) return rc;
+    // HIP events cost ~10 us of stream time each: with profiling on, every run of consecutive streaming-kernel
+    // launches (the roofline figure) shares ONE event pair; small-run launches are counted, not timed
+    for (size_t li = n_early; li < s.launches.size(); ++li) {
+        LevelLaunch& ll = s.launches[li];
+        const bool timed = idx->profile && !ll.small;
+        const bool group_start = timed && (li == n_early || s.launches[li - 1].small);
+        const bool group_end = timed && (li + 1 == s.launches.size() || s.launches[li + 1].small);
+        ll.ev = -1;
+        if (group_start) { ll.ev = (int)s.prof_used; HIPCHECK(prof_event(s, st)); }
+        launch_level(idx, s, ll, variant, st);
+        if (group_end) HIPCHECK(prof_event(s, st));
+    }
+    return QADC_OK;
+}
+
+// Behind the last level on the main stream: the ordering pass, the device replay, the multi-GPU merge, ev_done.
+int finish_batch(qadc_index* idx, Slot& s, const Staged& g) {
+    const int nq = s.nq;
+    hipStream_t st = idx->stream;
+    // the ordering pass runs on a side stream: it only occupies nq CUs, and the main stream is free to start the
+    // next batch's kernels meanwhile (it uses the other slot's buffers).  It stores [QueryOut[nq]][entries] straight
+    // into the slot's pinned host block, so no device-to-host copy waits in the DMA queue behind this batch (a
+    // queued copy with an unmet dependency stalls every later copy of the process, see upload_and_wait).
+    if (!g.alone) {
+        if (!s.ev_scanned) HIPCHECK(hipEventCreateWithFlags(&s.ev_scanned, hipEventDisableTiming));
+        HIPCHECK(hipEventRecord(s.ev_scanned, st));
+        st = idx->sort_stream;
+        HIPCHECK(hipStreamWaitEvent(st, s.ev_scanned, 0));
+    }
+    launch_sort_cands(s.d_qs, s.d_cands.p, s.cap_q, nq, s.d_qout, s.d_entries, s.out_cap, s.d_hdr, st,
+                      g.dev_stream ? s.d_stream.p : nullptr);
+    s.heaps_ready = s.dev_replay && !s.dist_batch;           // (a merge batch is replayed after the gather, not here)
+    if (s.heaps_ready) {
+        uint64_t* d_heaps = reinterpret_cast<uint64_t*>(s.d_result_mapped + g.off_heaps);
+        uint32_t* d_sizes = reinterpret_cast<uint32_t*>(s.d_result_mapped + g.off_heaps + sizeof(uint64_t) * (size_t)s.R * nq);
+        if ((uint32_t)s.R <= replay_wave_max_R())     // one wave per query, all lanes at work (heap in registers)
+            HIPCHECK(launch_replay_heap_wave_states(s.d_qs, s.d_stream.p, s.out_cap, nq, (uint32_t)s.R, d_heaps, d_sizes, st));
+        else                                                              // one wave per query, lane 0 pushing into an LDS heap (any R)
+            launch_replay_heap(s.d_qs, s.d_stream.p, s.out_cap, nq, (uint32_t)s.R, d_heaps, d_sizes, st);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(take_launch_error());
+    if (s.dist_batch && !s.rerun && s.mode != 1)
+        if (int rc = enqueue_merge(idx, s, st)) return rc;
+    return record_done(s, st);
 }
 
 }  // namespace
@@ -267,89 +328,58 @@ hipError_t prof_event(Slot& s, hipStream_t st) {
     return hipEventRecord(s.prof_ev[s.prof_used++], st);
 }
 
-// Plans the batch in slot s and enqueues all of its GPU work (front, levels, ordering, optional device replay).
-int plan_and_launch(qadc_index* idx, Slot& s) {
-    if (s.wgq) return launch_wgq_batch(idx, s);
-    ScopedMs timer(idx->prof.host_plan_ms);
-    const int M = idx->M, cs = idx->cs, nq = s.nq, ma = s.ma;
-    // (tried, round 4: consecutive level-path batches alternating between two scan streams on the scan pipe, so that the first
-    // workgroups of batch s+1 fill the tail of batch s's last level — 125M-code shard 1.10-1.15 -> 1.15-1.35 ms per step, 1B
-    // 7.66 -> 7.72-7.76: the next batch's workgroups do not fill a tail, they compete with the current level for CUs)
-    hipStream_t st = idx->stream;
-    const size_t table_dim = (size_t)M * 16;
-    BatchPlan plan;
-    if (int rc = plan_batch(idx, s, plan)) return rc;
-    const std::vector<ScanItem>& all_items = plan.all_items;
-    const std::vector<StartItem>&sitems_a = plan.sitems_a, &sitems_b = plan.sitems_b;
-    const std::vector<uint32_t>& fc_init = plan.fc_init;
-    uint64_t fc_stride = plan.fc_stride;
-    const size_t nitems = all_items.size();
+// The upload goes on the copy stream, where it depends on nothing (the slot's previous batch was collected),
+// and st waits for it.  Issued on the scan stream it would sit in the DMA engine's queue until the
+// PREVIOUS batch's kernels finish, and every other copy of the process (the caller's streams, the RCCL gather of
+// the multi-GPU merge) would queue behind it: copies wait in engine order, not stream order.  A batch with nothing
+// else in flight has nothing to queue behind: its copy goes on st itself.
+int upload_and_wait(qadc_index* idx, Slot& s, size_t bytes, hipStream_t st, bool alone) {
+    if (alone) {
+        HIPCHECK(hipMemcpyAsync(s.d_in.p, s.h_in.p, bytes, hipMemcpyHostToDevice, st));
+    } else {
+        HIPCHECK(hipMemcpyAsync(s.d_in.p, s.h_in.p, bytes, hipMemcpyHostToDevice, idx->copy_stream));
+        if (!s.ev_up) HIPCHECK(hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
+        HIPCHECK(hipEventRecord(s.ev_up, idx->copy_stream));
+        HIPCHECK(hipStreamWaitEvent(st, s.ev_up, 0));
+    }
+    return QADC_OK;
+}
 
-    // ---- upload: ONE block, ONE copy ----------------------------------------------------------
-    const size_t nt = (size_t)nq * ma * table_dim;
-    const size_t na = sitems_a.size(), nb = sitems_b.size();
-    auto align16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t off_items = 0;
-    const size_t off_sitems = align16(off_items + nitems * sizeof(ScanItem));
-    const size_t off_init = align16(off_sitems + (na + nb) * sizeof(StartItem));
-    const size_t off_tables = align16(off_init + fc_init.size() * sizeof(uint32_t));
-    const size_t tables_bytes = s.float_path ? (s.device_tables ? 0 : nt * sizeof(float)) : (s.front_sharded ? 0 : nt);
-    const size_t off_inj = align16(off_tables + tables_bytes);
-    const size_t inj_bytes = s.mode == 2 ? sizeof(float) * (size_t)nq * s.inj_n : 0;
-    const size_t off_hassign = align16(off_inj + inj_bytes);  // assign[] for the head launch (it walks the partition table itself)
-    const size_t hassign_bytes = s.head_codes ? sizeof(int32_t) * (size_t)nq * ma : 0;
-    const size_t in_bytes = align16(off_hassign + hassign_bytes);
-    HIPCHECK(s.h_in.ensure(in_bytes));
-    HIPCHECK(s.d_in.ensure(in_bytes));
-    if (nitems) std::memcpy(s.h_in.p + off_items, all_items.data(), nitems * sizeof(ScanItem));
-    if (na) std::memcpy(s.h_in.p + off_sitems, sitems_a.data(), na * sizeof(StartItem));
-    if (nb) std::memcpy(s.h_in.p + off_sitems + na * sizeof(StartItem), sitems_b.data(), nb * sizeof(StartItem));
-    std::memcpy(s.h_in.p + off_init, fc_init.data(), fc_init.size() * sizeof(uint32_t));
-    if (s.float_path && !s.device_tables) std::memcpy(s.h_in.p + off_tables, s.tables, nt * sizeof(float));
-    if (!s.float_path && !s.front_sharded) std::memcpy(s.h_in.p + off_tables, s.qtables_in.data(), nt);
-    if (inj_bytes) std::memcpy(s.h_in.p + off_inj, s.inj_vals.data(), inj_bytes);
-    if (hassign_bytes) std::memcpy(s.h_in.p + off_hassign, s.assign.data(), hassign_bytes);
-    s.d_items = reinterpret_cast<ScanItem*>(s.d_in.p + off_items);
-    s.d_sitems = reinterpret_cast<StartItem*>(s.d_in.p + off_sitems);
-    s.d_fc_init = reinterpret_cast<uint32_t*>(s.d_in.p + off_init);
-    s.d_ftables_in = reinterpret_cast<float*>(s.d_in.p + off_tables);
-
-    // state block: [CandHeader, 64 B][QueryState[nq]]; result block: [QueryOut[nq]][u64 entries[out_cap]]
-    const size_t state_bytes = 64 + sizeof(QueryState) * (size_t)nq;
-    bool lone = s.mode != 1;                                    // nothing else in flight: a synchronous call (see launch_wgq_batch)
-    for (int i = 0; i < kSlots; ++i) lone = lone && (&idx->slot[i] == &s || !idx->slot[i].busy);
-    lone = lone && !idx->pre_slot[0].busy && !idx->pre_slot[1].busy;
-    const int replay_from = lone ? std::max(idx->device_replay_nq, idx->device_replay_alone_nq) : idx->device_replay_nq;
-    s.dev_replay = s.mode != 1 && idx->device_replay_nq > 0 && nq >= replay_from && s.R <= 4096;
-    const size_t off_heaps = sizeof(QueryOut) * (size_t)nq + sizeof(uint64_t) * (size_t)s.out_cap;
-    const size_t heaps_bytes = s.dev_replay ? (sizeof(uint64_t) * (size_t)s.R + sizeof(uint32_t)) * (size_t)nq : 0;
-    const size_t result_bytes = std::max(off_heaps + heaps_bytes, (sizeof(float) * (size_t)s.R + sizeof(uint32_t)) * (size_t)nq);
-    HIPCHECK(s.d_state.ensure(state_bytes));
-    HIPCHECK(s.h_result.ensure(result_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+int map_result_block(Slot& s, size_t bytes) {
+    HIPCHECK(s.h_result.ensure(bytes, hipHostMallocMapped | hipHostMallocCoherent));
     if (s.h_result.p != s.h_result_mapped) {               // (looked up once per allocation: the call costs ~0.1 ms)
         HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.d_result_mapped), s.h_result.p, 0));
         s.h_result_mapped = s.h_result.p;
     }
-    unsigned char* d_result = s.d_result_mapped;
-    s.d_hdr = reinterpret_cast<CandHeader*>(s.d_state.p);
-    s.d_qs = reinterpret_cast<QueryState*>(s.d_state.p + 64);
-    s.d_qout = reinterpret_cast<QueryOut*>(d_result);
-    s.d_entries = reinterpret_cast<uint64_t*>(d_result + sizeof(QueryOut) * (size_t)nq);
-    s.h_qout = reinterpret_cast<QueryOut*>(s.h_result.p);
-    s.h_entries = reinterpret_cast<uint64_t*>(s.h_result.p + sizeof(QueryOut) * (size_t)nq);
-    s.h_heaps = reinterpret_cast<uint64_t*>(s.h_result.p + off_heaps);
-    s.h_heap_sizes = reinterpret_cast<uint32_t*>(s.h_result.p + off_heaps + sizeof(uint64_t) * (size_t)s.R * nq);
-    s.dist_batch = idx->dist != nullptr;
-    const bool dev_stream = s.dev_replay || s.dist_batch;          // the native multi-GPU merge gathers from device memory
-    if (dev_stream) HIPCHECK(s.d_stream.ensure(s.out_cap));
-    s.h_export = reinterpret_cast<float*>(s.h_result.p);
-    s.h_export_flags = reinterpret_cast<uint32_t*>(s.h_result.p + sizeof(float) * (size_t)s.R * nq);
-    HIPCHECK(s.d_cands.ensure((size_t)nq * s.cap_q));
-    HIPCHECK(s.d_qtables.ensure(nt));
-    // the 6-plane split form's deferred byte per table, computed where the int8 tables become known (below)
-    bool any_split6 = false;
-    for (auto& ll : s.launches) any_split6 = any_split6 || ll.split6;
-    if (any_split6) HIPCHECK(s.d_plane_sel.ensure((size_t)nq * ma));
+    return QADC_OK;
+}
+
+// Residuals + float tables [nq][ma][M*16] of the queries d_queries, from the feeder state (qadc_index_set_pq / _set_rotation / _set_coarse)
+void build_float_tables(const qadc_index* idx, const float* d_queries, int nq, int ma, const int32_t* d_assign, float* d_out, hipStream_t stream) {
+    const FeederState& f = idx->feed;
+    launch_build_tables(d_queries, f.K ? f.d_coarse.p : nullptr, d_assign, f.d_codebooks.p, f.has_rotation ? f.d_rotation.p : nullptr, nq, ma,
+                        idx->M, f.dim, table_expansion(idx, ma), idx->sum_mode, d_out, stream);
+}
+
+// Plans the batch in slot s and enqueues all of its GPU work (front, levels, ordering, optional device replay).
+int plan_and_launch(qadc_index* idx, Slot& s) {
+    if (s.wgq) return launch_wgq_batch(idx, s);
+    ScopedMs timer(idx->prof.host_plan_ms);
+    // (tried, round 4: consecutive level-path batches alternating between two scan streams on the scan pipe, so that the first
+    // workgroups of batch s+1 fill the tail of batch s's last level — 125M-code shard 1.10-1.15 -> 1.15-1.35 ms per step, 1B
+    // 7.66 -> 7.72-7.76: the next batch's workgroups do not fill a tail, they compete with the current level for CUs)
+    const LevelOptions opt{idx->M, idx->level_base, idx->level_growth, idx->head_level, idx->small_run, idx->wgs_per_item,
+                           idx->share_variant, idx->mq, idx->prescan_sample, idx->split_min_run, idx->split6_min_run};
+    const LevelBatch batch{s.nq, s.ma, s.assign.data(), s.R, s.mode, s.float_path, s.full_prescan, s.pre_slice, s.pre_nslices, s.inj_n};
+    BatchPlan plan = plan_levels(idx->parts.data(), idx->parts.size(), opt, batch);      // (host/level_plan.hpp: no GPU calls)
+    if (!plan.refused.empty()) return fail(QADC_E_ARG, plan.refused);
+    s.launches.swap(plan.launches);
+    s.head_codes = plan.head_codes;
+    s.start_codes = plan.start_codes;
+    Staged g;
+    g.alone = s.mode != 1 && nothing_else_in_flight(idx, s);
+    if (int rc = stage_upload(idx, s, plan, g)) return rc;
+    if (int rc = bind_state_and_result(idx, s, g)) return rc;
     // The front of the batch (state clear, table build, float pre-scan, selects, quantizer) depends on nothing the
     // previous batch produces: it runs on its own high-priority stream, under that batch's streaming launches, and
     // the first scan level waits for it.  Its short single-workgroup selects are pure latency; hidden this way they
@@ -357,213 +387,14 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
     // A batch submitted while nothing else is in flight (a synchronous call, the first batch of a pipeline) has
     // nothing to overlap with: it runs front, levels and ordering on ONE stream, which spares it three cross-stream
     // event hops (~15 us of a ~130 us single query).
-    bool alone = s.mode != 1;
-    for (int i = 0; i < kSlots; ++i) alone = alone && (&idx->slot[i] == &s || !idx->slot[i].busy);
-    alone = alone && !idx->pre_slot[0].busy && !idx->pre_slot[1].busy;
-    hipStream_t main_stream = st;
-    if (!alone || s.mode == 1) st = idx->front_stream;
-    HIPCHECK(hipMemsetAsync(s.d_state.p, 0, state_bytes, st));
-    // The upload goes on the copy stream, where it depends on nothing (the slot's previous batch was collected),
-    // and the main stream waits for it.  Issued on the main stream it would sit in the DMA engine's queue until the
-    // PREVIOUS batch's kernels finish, and every other copy of the process (the caller's streams, the RCCL gather of
-    // the multi-GPU merge) would queue behind it: copies wait in engine order, not stream order.
-    if (alone) {
-        HIPCHECK(hipMemcpyAsync(s.d_in.p, s.h_in.p, in_bytes, hipMemcpyHostToDevice, st));
-    } else {
-        HIPCHECK(hipMemcpyAsync(s.d_in.p, s.h_in.p, in_bytes, hipMemcpyHostToDevice, idx->copy_stream));
-        if (!s.ev_up) HIPCHECK(hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
-        HIPCHECK(hipEventRecord(s.ev_up, idx->copy_stream));
-        HIPCHECK(hipStreamWaitEvent(st, s.ev_up, 0));
-    }
+    hipStream_t st = g.alone ? idx->stream : idx->front_stream;
+    HIPCHECK(hipMemsetAsync(s.d_state.p, 0, g.state_bytes, st));
+    if (int rc = upload_and_wait(idx, s, g.in_bytes, st, g.alone)) return rc;
     s.prof_used = 0;
-
-    s.d_qt = s.d_qtables.p;
-    if (s.float_path) {
-        float* d_ft = s.d_ftables_in;
-        if (s.device_tables) {
-            // residuals + float tables built on the GPU from the queries uploaded by search_submit
-            HIPCHECK(s.d_ftables.ensure(nt));
-            d_ft = s.d_ftables.p;
-            HIPCHECK(hipStreamWaitEvent(st, s.ev_feed, 0));
-            launch_build_tables(s.d_queries.p, idx->feed.K ? idx->feed.d_coarse.p : nullptr, s.d_assign.p, idx->feed.d_codebooks.p,
-                                idx->feed.has_rotation ? idx->feed.d_rotation.p : nullptr, nq, ma, M, idx->feed.dim, table_expansion(idx, ma), idx->sum_mode, d_ft, st);
-        }
-        HIPCHECK(s.d_fc.ensure((size_t)nq * fc_stride));
-        if (idx->profile) HIPCHECK(prof_event(s, st));
-        auto wgs_for = [](const std::vector<StartItem>& v) {
-            uint32_t maxs = 0;
-            for (auto& si : v) maxs = std::max(maxs, si.n);
-            return (int)std::min<uint32_t>(std::max<uint32_t>((maxs + 4095) / 4096, 1), 512);
-        };
-        const int tda = (int)(ma * table_dim);
-        // phase A: the sample, unfiltered -> its R-th smallest; phase B: the rest, keeping only values <= that.
-        // The LAST select of the chain also quantizes the query's tables (QuantizerMAX) in the same workgroup.
-        // every query pre-scans the same starts (flat database, or one shared probe): 8 queries per pass
-        auto shared_items = [&](const std::vector<StartItem>& v) {
-            if (v.size() < 2) return false;
-            for (auto& si : v)
-                if (si.codes != v[0].codes || si.n != v[0].n || si.out_off != v[0].out_off || si.filter != v[0].filter) return false;
-            return true;
-        };
-        auto start_scan = [&](const std::vector<StartItem>& v, const StartItem* d_v) {
-            if (shared_items(v))
-                launch_start_scan_mq(M, idx->sum_mode, d_v, (int)v.size(), std::min(2 * wgs_for(v), 1024), d_ft, s.d_fc.p, fc_stride, s.d_fc_init,
-                                     s.d_qs, st);
-            else
-                launch_start_scan_f32(M, idx->sum_mode, d_v, (int)v.size(), wgs_for(v), d_ft, s.d_fc.p, fc_stride, s.d_fc_init, s.d_qs, st);
-        };
-        if (na) start_scan(sitems_a, s.d_sitems);
-        if (nb) {
-            // (with a phase B the first select only has to bound the R-th smallest from above: 2 digit passes)
-            launch_select_kth(s.d_fc.p, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 2, nullptr, nullptr, tda, 0, st);
-            start_scan(sitems_b, s.d_sitems + na);
-        }
-        if (s.mode == 1) {
-            // pre-scan only: the exact R-th smallest of this rank's slice, and the R smallest values themselves,
-            // stored straight into the pinned result block; nothing else runs
-            float* d_exp = reinterpret_cast<float*>(d_result);
-            uint32_t* d_expf = reinterpret_cast<uint32_t*>(d_result + sizeof(float) * (size_t)s.R * nq);
-            launch_select_kth(s.d_fc.p, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 4, nullptr, nullptr, tda, 0, st,
-                              d_exp, d_expf);
-            HIPCHECK(hipGetLastError());
-            if (idx->profile) HIPCHECK(prof_event(s, st));
-            if (!s.ev_done) HIPCHECK(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
-            HIPCHECK(hipEventRecord(s.ev_done, st));
-            return QADC_OK;
-        }
-        const float* d_sel = s.d_fc.p;
-        if (s.mode == 2) {
-            // the ranks' gathered smallest values stand in for the pre-scan output
-            d_sel = reinterpret_cast<const float*>(s.d_in.p + off_inj);
-            fc_stride = s.inj_n;
-            launch_prescan_minmax(d_sel, s.inj_n, nq, s.d_qs, st);
-        }
-        launch_select_kth(d_sel, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 4, d_ft, s.d_qtables.p, tda,
-                          idx->quant_mode, st, nullptr, nullptr, nullptr, 0, any_split6 ? s.d_plane_sel.p : nullptr);
-        if (idx->profile) HIPCHECK(prof_event(s, st));
-    } else {
-        s.d_qt = s.front_sharded ? s.d_qtables.p                             // (a sharded-front batch redone here: the gathered tables)
-                                 : reinterpret_cast<const int8_t*>(s.d_in.p + off_tables);     // caller's int8 tables, as uploaded
-        if (any_split6) launch_plane_choice(s.d_qt, nq * ma, s.d_plane_sel.p, st);
-        if (idx->profile) { HIPCHECK(prof_event(s, st)); HIPCHECK(prof_event(s, st)); }
-    }
-
-    // ---- scan levels ------------------------------------------------------------------------
-    // a database that fits the 256 MiB Infinity Cache is re-read from it by every query: keep the default
-    // cache policy there; non-temporal loads only pay for lists that stream from HBM anyway
-    uint64_t db_bytes = 0;
-    for (auto& p : idx->parts) db_bytes += (uint64_t)p.n * cs;
-    const int variant = db_bytes <= (200ull << 20) ? (idx->variant & ~4) : idx->variant;
-    auto launch_level = [&](LevelLaunch& ll, hipStream_t str) {
-        if (ll.small)
-            launch_scan_i8_small(M, s.d_items + ll.first, ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p,
-                                 s.cap_q, (uint32_t)s.R, str);
-        else if (ll.mq)
-            launch_scan_i8_mq(M, s.d_items + ll.first, ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q,
-                              (uint32_t)s.R, str, /*narrow=*/ll.nitems <= 4 ? 1 : 0);   // (8 queries per pass: the 8-seat
-                                                                   // build, see scan_i8_mq_kernel; <= 4 runs: the build with the 4-seat body)
-        else
-            launch_scan_i8(M, ll.shared ? (idx->share_variant & ~32) : (variant & ~(64 | 32)) | (ll.split ? 32 : 0), s.d_items + ll.first,
-                           ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str,
-                           ll.split6 ? s.d_plane_sel.p : nullptr,
-                           ll.split6 && idx->profile ? reinterpret_cast<unsigned long long*>(s.d_hdr->pad) : nullptr);
-    };
-    // The first levels of a batch are short launches in a dependent chain (each level's bound needs the previous
-    // levels' candidates): latency, not work.  The head launch and the levels with short runs join the front — same
-    // stream, after the quantizer — and so run under the previous batch's long levels instead of in front of this
-    // batch's; only the long levels stay on the main stream.  Front-stream kernels only find room as workgroups of
-    // the long launches retire, so a level with real work is slower there than on the main stream: runs of <= 2 Mi
-    // codes go early (125M x 32 queries: 1.143 -> 1.10 ms per step; 1B x 32: -1 %), 8 Mi already costs more than it hides.
-    auto launch_head = [&](hipStream_t str) -> int {
-        // ONE launch scans the first head_codes codes of every query (bound levels 0..k0-1): every query's scan order
-        // split over G workgroups that refresh their bound in LDS, instead of k0 dependent launches of a few
-        // microseconds of work each.  It emits into the same candidate regions / level-0 histogram the levels use.
-        QueryKernelArgs H{};
-        H.parts = idx->d_partdesc.p;
-        H.assign = reinterpret_cast<const int32_t*>(s.d_in.p + off_hassign);
-        H.ma = ma;
-        H.qtables = const_cast<int8_t*>(s.d_qt);
-        H.R = (uint32_t)s.R;
-        H.head_codes = s.head_codes;
-        H.qstates = s.d_qs;
-        H.cand_regions = s.d_cands.p;
-        H.cand_cap = s.cap_q;
-        H.hdr = s.d_hdr;
-        H.nontemporal = 0;                                   // the queries of a batch share the head of a flat list through L2
-        int G = std::min<int>(nq <= 2 ? idx->wgq_split : std::min(idx->wgq_split, kSplitBatch), std::max(1, 256 / nq));   // (as launch_wgq_batch)
-        G = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)G, s.head_codes / 16384));
-        H.G = G;
-        HIPCHECK(launch_scan_query(M, nq, H, str));
-        idx->prof.head_launches++;
-        return QADC_OK;
-    };
-    size_t n_early = 0;
-    uint64_t batch_codes = 0;
-    for (auto& ll : s.launches) batch_codes += ll.codes;
-    if (st != main_stream && (s.mode == 0 || s.mode == 2) && batch_codes >= kFrontMinBatch)
-        while (n_early < s.launches.size() && s.launches[n_early].maxn <= idx->front_run_max) ++n_early;
-    if (n_early == s.launches.size() && n_early) --n_early;        // the last level closes the batch on the main stream
-    // the head precedes every level: with the early levels (or on request) it joins the front as well
-    bool head_pending = s.head_codes != 0;
-    if (head_pending && st != main_stream) {
-        if (int rc = launch_head(st)) return rc;
-        head_pending = false;
-    }
-    for (size_t li = 0; li < n_early; ++li) {
-        s.launches[li].early = true;
-        s.launches[li].ev = -1;
-        launch_level(s.launches[li], st);
-    }
-    if (st != main_stream) {
-        if (!s.ev_front) HIPCHECK(hipEventCreateWithFlags(&s.ev_front, hipEventDisableTiming));
-        HIPCHECK(hipEventRecord(s.ev_front, st));
-        st = main_stream;
-        HIPCHECK(hipStreamWaitEvent(st, s.ev_front, 0));
-    }
-    if (head_pending)
-        if (int rc = launch_head(st)) return rc;
-    // HIP events cost ~10 us of stream time each: with profiling on, every run of consecutive streaming-kernel
-    // launches (the roofline figure) shares ONE event pair; small-run launches are counted, not timed
-    for (size_t li = n_early; li < s.launches.size(); ++li) {
-        LevelLaunch& ll = s.launches[li];
-        const bool timed = idx->profile && !ll.small;
-        const bool group_start = timed && (li == n_early || s.launches[li - 1].small);
-        const bool group_end = timed && (li + 1 == s.launches.size() || s.launches[li + 1].small);
-        ll.ev = -1;
-        if (group_start) { ll.ev = (int)s.prof_used; HIPCHECK(prof_event(s, st)); }
-        launch_level(ll, st);
-        if (group_end) HIPCHECK(prof_event(s, st));
-    }
-    // the ordering pass runs on a side stream: it only occupies nq CUs, and the main stream is free to start the
-    // next batch's kernels meanwhile (it uses the other slot's buffers).  It stores [QueryOut[nq]][entries] straight
-    // into the slot's pinned host block, so no device-to-host copy waits in the DMA queue behind this batch (a
-    // queued copy with an unmet dependency stalls every later copy of the process, see the upload above).
-    if (!alone) {
-        hipStream_t main_st = st;
-        if (!s.ev_scanned) HIPCHECK(hipEventCreateWithFlags(&s.ev_scanned, hipEventDisableTiming));
-        HIPCHECK(hipEventRecord(s.ev_scanned, main_st));
-        st = idx->sort_stream;
-        HIPCHECK(hipStreamWaitEvent(st, s.ev_scanned, 0));
-    }
-    launch_sort_cands(s.d_qs, s.d_cands.p, s.cap_q, nq, s.d_qout, s.d_entries, s.out_cap, s.d_hdr, st,
-                      dev_stream ? s.d_stream.p : nullptr);
-    s.heaps_ready = s.dev_replay && !s.dist_batch;           // (a merge batch is replayed after the gather, not here)
-    if (s.heaps_ready) {
-        uint64_t* d_heaps = reinterpret_cast<uint64_t*>(d_result + off_heaps);
-        uint32_t* d_sizes = reinterpret_cast<uint32_t*>(d_result + off_heaps + sizeof(uint64_t) * (size_t)s.R * nq);
-        if ((uint32_t)s.R <= replay_wave_max_R())     // one wave per query, all lanes at work (heap in registers)
-            HIPCHECK(launch_replay_heap_wave_states(s.d_qs, s.d_stream.p, s.out_cap, nq, (uint32_t)s.R, d_heaps, d_sizes, st));
-        else                                                              // one wave per query, lane 0 pushing into an LDS heap (any R)
-            launch_replay_heap(s.d_qs, s.d_stream.p, s.out_cap, nq, (uint32_t)s.R, d_heaps, d_sizes, st);
-    }
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(take_launch_error());
-    if (s.dist_batch && !s.rerun && s.mode != 1)
-        if (int rc = enqueue_merge(idx, s, st)) return rc;
-
-    if (!s.ev_done) HIPCHECK(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(s.ev_done, st));
-    return QADC_OK;
+    if (int rc = launch_front(idx, s, plan, g, st)) return rc;
+    if (s.mode == 1 && s.float_path) return QADC_OK;            // pre-scan only: launch_front recorded ev_done
+    if (int rc = launch_levels(idx, s, g, st)) return rc;
+    return finish_batch(idx, s, g);
 }
 }  // namespace host
 }  // namespace qadc
@@ -623,9 +454,7 @@ int submit_common(qadc_index* idx, int slot_i, int nq, int ma, const int32_t* as
         }
         // (the rules for a LONE call of one or two queries hold when nothing else is in flight: a caller that pipelines single
         // queries over the slots gets them overlapped by the level path, not serialised on the query kernel's one stream)
-        bool alone = mode == 0;
-        for (int i = 0; i < kSlots; ++i) alone = alone && (&idx->slot[i] == &s || !idx->slot[i].busy);
-        alone = alone && !idx->pre_slot[0].busy && !idx->pre_slot[1].busy;
+        const bool alone = mode == 0 && nothing_else_in_flight(idx, s);
         s.wgq = wgq_eligible(idx, nq, ma, R, mode, max_codes, tables != nullptr, alone);
         s.wgq_codes = max_codes;
     }

@@ -1,9 +1,10 @@
 // Internal host-side header of libqadc_hip.so (not part of the C-ABI; see include/qadc.h for that): the state
 // structs and helpers shared by the translation units of the host side —
-//   qadc_capi.cpp   index / database side, level-path planner, submit / collect, the plain query entry points
+//   qadc_capi.cpp   index / database side, level-path launch stages (plan_and_launch), submit / collect, the plain query entry points
 //   qadc_ivf.cpp    one-workgroup-per-query batches, partition-major second phase, device-side feeders (qadc_search)
 //   qadc_dist.cpp   native multi-GPU merge (qadc_dist_*: RCCL by dlopen, or a caller-supplied all-gather)
 //   qadc_build.cpp  database build entry points (PQ / IVF encode, k-means iterations)
+// The level-path planner itself (items, launches, plan_levels) is host/level_plan.hpp: no HIP, checked on a CPU.
 // The last three keep their state in structs of their own hung off qadc_index (FeederState, GroupState, DistState).
 #pragma once
 #include "../../include/qadc.h"
@@ -87,18 +88,9 @@ struct PinBuf {
     }
 };
 
-struct Part {
-    uint8_t* d_codes = nullptr;    // row-major codes of the local range
-    uint32_t* d_labels = nullptr;  // labels of the local range (or null)
-    uint8_t* d_starts = nullptr;   // replica of the global partition's first codes (null: d_codes, first_pos == 0)
-    uint32_t n = 0;                // codes held here
-    uint32_t global_n = 0;         // codes of the whole partition (== n unless sharded)
-    uint32_t first_pos = 0;        // global position of local code 0
+struct Part : LevelPart {           // (the fields the level planner reads: host/level_plan.hpp)
     uint32_t starts_cap = 0;       // codes available for the pre-scan
-    uint32_t start_n = 0;
-    uint32_t key_base = 0;
     bool own = true;
-    uint8_t* d_split = nullptr;    // 16x4: byte-plane copy of code bytes 0-6 for the split scan (kSplitTile), or null
 };
 
 constexpr int kMergeStreams = 3;   // streams the enqueued merges MAY rotate over (measurement hook); the default creates ONE:
@@ -107,21 +99,6 @@ constexpr int kMergeStreams = 3;   // streams the enqueued merges MAY rotate ove
 constexpr int kSlots = 8;   // batches in flight: one being collected, one scanning, the others queued behind it with their fronts running
                             // ahead.  Three or four cover every loop measured so far (deeper pipelines of the multi-GPU IVF loop — six,
                             // eight batches — were tried and are no faster: its batches share the GPU, they do not wait for it)
-
-struct LevelLaunch {
-    size_t first;   // first item
-    int nitems;
-    int wgs;
-    uint64_t codes;
-    bool small;     // small-run kernel (runs below idx->small_run codes)
-    bool shared;    // every run of the launch covers the same codes (one run per query): sibling-major launch
-    bool mq;        // ... and groups of 8 of them share one pass (scan_i8_mq_kernel)
-    bool split;     // every run of the launch reads the byte-plane copy (split form of scan_i8_kernel)
-    bool split6;    // ... and has at least split6_min_run codes: the 6-plane form (the query's table defers a second byte)
-    uint64_t maxn;  // longest run of the launch
-    bool early;     // launched on the front stream, under the previous batch's long levels: counted, not event-timed
-    int ev = -1;    // index of the HIP event recorded before the launch (the next one follows it), -1 = not timed
-};
 
 struct Slot {
     bool busy = false;
@@ -349,11 +326,6 @@ struct FeederState {
 };
 
 // Fixed tuning constants (each was an option while it was being measured; the sweeps are in profiles/, see profiles/README.md)
-constexpr uint32_t kShareCodesPerWg = 1u << 20;    // codes per workgroup of a sibling-major shared launch
-constexpr uint32_t kMqCodesPerWg = 1u << 16;       // ... of a multi-query launch (8 queries per pass)
-constexpr uint32_t kMqMinWgs = 4096;               // workgroups a multi-query launch should have at least (2 rounds of the chip)
-constexpr uint32_t kMqMinTiles = 4;                // ... but never fewer than this many 4 KiB tiles per workgroup
-constexpr uint32_t kSmallVecPerWg = 512;           // 16-byte vectors one small-run workgroup covers
 constexpr uint64_t kFrontMinBatch = 3000000000ull; // leading levels join the front stream only in batches of at least this many (code, query)
                                                    // pairs: under a shorter last level they only make the front stream the step's longest chain
 constexpr int kWgqMinNq = 128;                     // query-kernel path, auto: batches of at least this many queries ...
@@ -475,6 +447,20 @@ int use_device(const qadc_index* idx);
 hipError_t prof_event(Slot& s, hipStream_t st);
 int plan_and_launch(qadc_index* idx, Slot& s);               // plans the batch in slot s and enqueues all of its GPU work
 int collect_common(qadc_index* idx, int slot_i, bool need_stream = true, bool from_dist = false);
+// ... shared by the level path and the query-kernel path (launch_wgq_batch):
+// no batch but slot s's own is in flight (a synchronous call, the first batch of a pipeline)
+inline bool nothing_else_in_flight(const qadc_index* idx, const Slot& s) {
+    for (int i = 0; i < kSlots; ++i)
+        if (&idx->slot[i] != &s && idx->slot[i].busy) return false;
+    return !idx->pre_slot[0].busy && !idx->pre_slot[1].busy;
+}
+// batches of at least this many queries replay their streams on the device
+inline int replay_threshold(const qadc_index* idx, bool alone) {
+    return alone ? std::max(idx->device_replay_nq, idx->device_replay_alone_nq) : idx->device_replay_nq;
+}
+int upload_and_wait(qadc_index* idx, Slot& s, size_t bytes, hipStream_t st, bool alone);   // h_in -> d_in before st's next operation
+int map_result_block(Slot& s, size_t bytes);                 // s.h_result of at least `bytes`, device-mapped: s.d_result_mapped
+void build_float_tables(const qadc_index* idx, const float* d_queries, int nq, int ma, const int32_t* d_assign, float* d_out, hipStream_t stream);
 void finish_float_outputs(qadc_index* idx, Slot& s, int32_t* status, float* qmin, float* qmax);
 int replay_outputs(qadc_index* idx, Slot& s, uint32_t* keys, int8_t* values, int32_t* sizes, const int32_t* status);
 // qadc_ivf.cpp

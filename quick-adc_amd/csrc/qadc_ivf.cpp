@@ -73,15 +73,12 @@ int launch_wgq_batch(qadc_index* idx, Slot& s) {
     // ---- result block in pinned, device-mapped host memory: [QueryOut[nq]][streams u64[nq][cap] unless they stay
     // on the device][heaps u64[nq][R]][sizes u32[nq]] ----
     const uint32_t cap = s.wgq_cap;
-    bool alone = true;
-    for (int i = 0; i < kSlots; ++i) alone = alone && (&idx->slot[i] == &s || !idx->slot[i].busy);
-    alone = alone && !idx->pre_slot[0].busy && !idx->pre_slot[1].busy;
+    const bool alone = nothing_else_in_flight(idx, s);
     // The lane-per-query replay takes ~1.3 ms whatever the batch size (one query's pushes are sequential): in a pipeline
     // that latency hides under the next batches and the host stays free, but a batch submitted while nothing else is in
     // flight — a synchronous call — is answered sooner by the host's threads up to a few hundred queries (C3 shape,
     // synchronous: 64 queries 1.41 -> 0.87 ms, 256: 1.89 -> 1.44, 512: 2.26 vs 2.41)
-    const int replay_from = alone ? std::max(idx->device_replay_nq, idx->device_replay_alone_nq) : idx->device_replay_nq;
-    s.dev_replay = idx->device_replay_nq > 0 && nq >= replay_from && (uint32_t)s.R <= replay_wave_max_R();
+    s.dev_replay = idx->device_replay_nq > 0 && nq >= replay_threshold(idx, alone) && (uint32_t)s.R <= replay_wave_max_R();
     s.dist_batch = idx->dist != nullptr;
     s.heaps_ready = s.dev_replay && !s.dist_batch;
     if (s.dist_batch) s.dev_replay = true;                   // streams stay on the device for the gather (qadc_dist_collect)
@@ -110,11 +107,7 @@ int launch_wgq_batch(qadc_index* idx, Slot& s) {
     const size_t host_stream_bytes = s.dev_replay ? 0 : sizeof(uint64_t) * stream_entries;
     const size_t off_heaps = sizeof(QueryOut) * (size_t)nsub + host_stream_bytes;
     const size_t heaps_bytes = s.dev_replay ? (sizeof(uint64_t) * (size_t)s.R + sizeof(uint32_t)) * (size_t)nq : 0;
-    HIPCHECK(s.h_result.ensure(off_heaps + heaps_bytes + 16, hipHostMallocMapped | hipHostMallocCoherent));
-    if (s.h_result.p != s.h_result_mapped) {
-        HIPCHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.d_result_mapped), s.h_result.p, 0));
-        s.h_result_mapped = s.h_result.p;
-    }
+    if (int rc = map_result_block(s, off_heaps + heaps_bytes + 16)) return rc;
     unsigned char* d_result = s.d_result_mapped;
     s.d_qout = reinterpret_cast<QueryOut*>(d_result);
     s.h_qout = reinterpret_cast<QueryOut*>(s.h_result.p);
@@ -175,16 +168,8 @@ int launch_wgq_batch(qadc_index* idx, Slot& s) {
     }
     if (lf_slices && !inl_bytes) lf_slices = 0;
     if (!inl_bytes) fill_upload();                               // (an inline query's input rides in the dispatch packet instead)
-    if (in_bytes && !inl_bytes) {
-        if (alone) {
-            HIPCHECK(hipMemcpyAsync(s.d_in.p, s.h_in.p, in_bytes, hipMemcpyHostToDevice, st));
-        } else {                                            // never queue a copy behind the previous batch's kernels
-            HIPCHECK(hipMemcpyAsync(s.d_in.p, s.h_in.p, in_bytes, hipMemcpyHostToDevice, idx->copy_stream));
-            if (!s.ev_up) HIPCHECK(hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
-            HIPCHECK(hipEventRecord(s.ev_up, idx->copy_stream));
-            HIPCHECK(hipStreamWaitEvent(st, s.ev_up, 0));
-        }
-    }
+    if (in_bytes && !inl_bytes)                              // (never queued behind the previous batch's kernels)
+        if (int rc = upload_and_wait(idx, s, in_bytes, st, alone)) return rc;
     s.prof_used = 0;
     // What a pipelined batch needs BEFORE its first scan launch but from nobody on the scan stream — the float tables (built
     // from assign[], which the copy stream's coarse kernels produce), the state clear, the partition-major plan (count /
@@ -208,8 +193,7 @@ int launch_wgq_batch(qadc_index* idx, Slot& s) {
         if (s.device_tables) {
             HIPCHECK(s.d_ftables.ensure(nt));
             HIPCHECK(hipStreamWaitEvent(pre_st, s.ev_feed, 0));
-            launch_build_tables(s.d_queries.p, idx->feed.K ? idx->feed.d_coarse.p : nullptr, s.d_assign.p, idx->feed.d_codebooks.p,
-                                idx->feed.has_rotation ? idx->feed.d_rotation.p : nullptr, nq, ma, M, idx->feed.dim, table_expansion(idx, ma), idx->sum_mode, s.d_ftables.p, pre_st);
+            build_float_tables(idx, s.d_queries.p, nq, ma, s.d_assign.p, s.d_ftables.p, pre_st);
             pre_used = pre_st != st;
             A.ftables = s.d_ftables.p;
         } else {
@@ -234,9 +218,7 @@ int launch_wgq_batch(qadc_index* idx, Slot& s) {
             if (s.front_n) {
                 const size_t nt_share = (size_t)s.front_n * tab;
                 HIPCHECK(s.d_ftables.ensure(nt_share));
-                launch_build_tables(s.d_queries.p, idx->feed.d_coarse.p, d_assign_share, idx->feed.d_codebooks.p,
-                                    idx->feed.has_rotation ? idx->feed.d_rotation.p : nullptr, s.front_n, ma, M, idx->feed.dim, table_expansion(idx, ma),
-                                    idx->sum_mode, s.d_ftables.p, fs);
+                build_float_tables(idx, s.d_queries.p, s.front_n, ma, d_assign_share, s.d_ftables.p, fs);   // (a sharded front: feed.K != 0)
                 QueryKernelArgs F{};
                 F.parts = idx->d_partdesc.p;
                 F.assign = d_assign_share;

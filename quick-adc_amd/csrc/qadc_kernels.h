@@ -5,31 +5,11 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "../host/level_plan.hpp"
+
 namespace qadc {
 
-// One contiguous run of codes of one probed partition, scanned with one int8 table.
-// (A probed partition is cut into one item per bound level, see DESIGN.md "Exact filtering".)
-struct ScanItem {
-    const uint8_t* codes;    // first code of the run (16-byte aligned)
-    const uint32_t* labels;  // partition labels (indexed by position in partition) or nullptr
-    uint32_t n;              // codes in the run
-    uint32_t pos0;           // position of the first code inside its partition
-    uint32_t key_base;       // added to the position when labels == nullptr (shard offset)
-    uint32_t table;          // table index: qtables + table * M * 16
-    uint32_t query;          // per-query state index
-    uint32_t order;          // (level << 16) | assign slot (< 2^14): scan-order major key of emitted entries
-    uint32_t dup_pos;        // position (in the partition) of the code the reference replays in its padding
-                             // lanes, if this run's partition end is held here; else 0xffffffff
-    uint32_t dup_reps;       // number of extra replays of that code: (16 - n % 16) % 16
-    const uint8_t* split;    // 16x4: the run's first tile in the partition's byte-plane copy (launch_split_copy), or nullptr
-};
-
-// Byte-plane copy of code bytes 0-6 (16x4 only), the input of the split form of scan_i8_kernel: tile t of a partition holds
-// codes [t * kSplitTile, (t + 1) * kSplitTile) as 7 planes of kSplitTile bytes each (plane b = byte b of consecutive codes) at
-// byte t * 7 * kSplitTile.  One tile is one workgroup iteration of the split form: 1024 lanes x 16 codes.  Padded to whole
-// tiles (codes past the partition's end read as 0).  Byte 7 stays in the row-major array only.
-constexpr uint32_t kSplitTile = 16384;
-constexpr uint32_t kSplitBytes = 7;
+// ScanItem, StartItem, kSplitTile / kSplitBytes (the byte-plane copy's layout) and kMaxLevels: host/level_plan.hpp
 inline uint64_t split_copy_bytes(uint32_t n) { return ((uint64_t)n + kSplitTile - 1) / kSplitTile * kSplitBytes * kSplitTile; }
 void launch_split_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipStream_t stream);
 
@@ -49,8 +29,6 @@ struct CandHeader {
     uint32_t out_overflow;  // sorted entries that did not fit the sorted output buffer
     uint32_t pad[2];
 };
-
-constexpr int kMaxLevels = 16;  // bound levels per query
 
 // Per-query device state.  hist[l][v] counts the candidates of value v emitted by level l.
 struct QueryState {
@@ -80,16 +58,6 @@ struct QueryOut {
     uint32_t out_off;  // first entry in the sorted output
     float qmin, qmax;
     uint32_t pad[2];
-};
-
-// Float ADC item for the "starts" pre-scan (scanner_4::query_scan_start).
-struct StartItem {
-    const uint8_t* codes;  // first code of the partition
-    uint32_t n;            // starts size of that partition
-    uint32_t table;        // float table index: ftables + table * M * 16
-    uint32_t query;
-    uint32_t out_off;      // filter == 0: offset inside the query's float value buffer
-    uint32_t filter;       // 1: append only values <= QueryState::qmax (the sample's R-th smallest)
 };
 
 // ---- one workgroup per query (qadc_query_kernel.hip): IVF batches and small lists ---------------------

@@ -1,0 +1,345 @@
+// The planner of the int8 level path: integer arithmetic on the partition table, the options and
+// the probe lists of a batch.  Every exactness argument of that section rests on what it emits — the level cuts, the 16-byte
+// alignment of every run, the 2^31 cut, dup_pos / dup_reps, which runs may take the split form, the pre-scan items — and it also
+// picks kernel and grid of every level launch.  No HIP here, and no pointer is dereferenced (the device pointers are only offset):
+// csrc/qadc_kernels.h and csrc/qadc_host.h include this header for the item and launch structs, csrc/qadc_capi.cpp plans every
+// level-path batch with plan_levels, and tests/cpp/level_plan_host.cpp checks the plan's invariants on a CPU.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace qadc {
+
+// One contiguous run of codes of one probed partition, scanned with one int8 table.
+// (A probed partition is cut into one item per bound level, see DESIGN.md "Exact filtering".)
+struct ScanItem {
+    const uint8_t* codes;    // first code of the run (16-byte aligned)
+    const uint32_t* labels;  // partition labels (indexed by position in partition) or nullptr
+    uint32_t n;              // codes in the run
+    uint32_t pos0;           // position of the first code inside its partition
+    uint32_t key_base;       // added to the position when labels == nullptr (shard offset)
+    uint32_t table;          // table index: qtables + table * M * 16
+    uint32_t query;          // per-query state index
+    uint32_t order;          // (level << 16) | assign slot (< 2^14): scan-order major key of emitted entries
+    uint32_t dup_pos;        // position (in the partition) of the code the reference replays in its padding
+                             // lanes, if this run's partition end is held here; else 0xffffffff
+    uint32_t dup_reps;       // number of extra replays of that code: (16 - n % 16) % 16
+    const uint8_t* split;    // 16x4: the run's first tile in the partition's byte-plane copy (launch_split_copy), or nullptr
+};
+
+// Byte-plane copy of code bytes 0-6 (16x4 only), the input of the split form of scan_i8_kernel: tile t of a partition holds
+// codes [t * kSplitTile, (t + 1) * kSplitTile) as 7 planes of kSplitTile bytes each (plane b = byte b of consecutive codes) at
+// byte t * 7 * kSplitTile.  One tile is one workgroup iteration of the split form: 1024 lanes x 16 codes.  Padded to whole
+// tiles (codes past the partition's end read as 0).  Byte 7 stays in the row-major array only.
+constexpr uint32_t kSplitTile = 16384;
+constexpr uint32_t kSplitBytes = 7;
+
+constexpr int kMaxLevels = 16;  // bound levels per query
+
+// Float ADC item for the "starts" pre-scan (scanner_4::query_scan_start).
+struct StartItem {
+    const uint8_t* codes;  // first code of the partition
+    uint32_t n;            // starts size of that partition
+    uint32_t table;        // float table index: ftables + table * M * 16
+    uint32_t query;
+    uint32_t out_off;      // filter == 0: offset inside the query's float value buffer
+    uint32_t filter;       // 1: append only values <= QueryState::qmax (the sample's R-th smallest)
+};
+
+namespace host {
+
+// Fixed tuning constants (each was an option while it was being measured; the sweeps are in profiles/, see profiles/README.md)
+constexpr uint32_t kShareCodesPerWg = 1u << 20;    // codes per workgroup of a sibling-major shared launch
+constexpr uint32_t kMqCodesPerWg = 1u << 16;       // ... of a multi-query launch (8 queries per pass)
+constexpr uint32_t kMqMinWgs = 4096;               // workgroups a multi-query launch should have at least (2 rounds of the chip)
+constexpr uint32_t kMqMinTiles = 4;                // ... but never fewer than this many 4 KiB tiles per workgroup
+constexpr uint32_t kSmallVecPerWg = 512;           // 16-byte vectors one small-run workgroup covers
+
+struct LevelLaunch {
+    size_t first;   // first item
+    int nitems;
+    int wgs;
+    uint64_t codes;
+    bool small;     // small-run kernel (runs below small_run codes)
+    bool shared;    // every run of the launch covers the same codes (one run per query): sibling-major launch
+    bool mq;        // ... and groups of 8 of them share one pass (scan_i8_mq_kernel)
+    bool split;     // every run of the launch reads the byte-plane copy (split form of scan_i8_kernel)
+    bool split6;    // ... and has at least split6_min_run codes: the 6-plane form (the query's table defers a second byte)
+    uint64_t maxn;  // longest run of the launch
+    bool early;     // launched on the front stream, under the previous batch's long levels: counted, not event-timed
+    int ev = -1;    // index of the HIP event recorded before the launch (the next one follows it), -1 = not timed
+};
+
+// What the planner reads of a partition (the index's Part derives from it: one partition table, no copy).
+struct LevelPart {
+    uint8_t* d_codes = nullptr;    // row-major codes of the local range
+    uint32_t* d_labels = nullptr;  // labels of the local range (or null)
+    uint8_t* d_starts = nullptr;   // replica of the global partition's first codes (null: d_codes, first_pos == 0)
+    uint8_t* d_split = nullptr;    // 16x4: byte-plane copy of code bytes 0-6 for the split scan (kSplitTile), or null
+    uint32_t n = 0;                // codes held here
+    uint32_t global_n = 0;         // codes of the whole partition (== n unless sharded)
+    uint32_t first_pos = 0;        // global position of local code 0
+    uint32_t start_n = 0;
+    uint32_t key_base = 0;
+};
+
+// ... of the index's options (qadc_index has the meaning of each), and of the batch (Slot has them).  Aggregates, in this order.
+struct LevelOptions {
+    int M;
+    uint64_t level_base, level_growth;
+    int head_level;
+    uint32_t small_run;
+    int wgs_per_item, share_variant, mq;
+    uint32_t prescan_sample;
+    uint64_t split_min_run, split6_min_run;
+};
+struct LevelBatch {
+    int nq, ma;
+    const int32_t* assign;   // [nq][ma]
+    int R, mode;
+    bool float_path, full_prescan;
+    int pre_slice, pre_nslices;
+    uint32_t inj_n;
+};
+
+// What the planner hands to the launcher: the work items of a batch in upload order.
+struct BatchPlan {
+    std::string refused;                         // not empty: the batch cannot be planned, and why (nothing below is to be used)
+    std::vector<ScanItem> all_items;             // runs, grouped by bound level (launches index into it)
+    std::vector<StartItem> sitems_a, sitems_b;   // pre-scan: phase A = unfiltered sample, phase B = filtered remainder
+    std::vector<uint32_t> fc_init;               // per query: {sample values, capacity} of its pre-scan buffer
+    uint64_t fc_stride = 1;
+    std::vector<LevelLaunch> launches;           // kernel and grid of every level launch, in launch order
+    uint64_t head_codes = 0;                     // codes of every query's scan order covered by the head launch (0 = none)
+    uint64_t start_codes = 0;                    // codes the pre-scan items cover
+};
+
+// Level boundaries in the concatenated scan position space of one query.
+inline void level_bounds(const LevelOptions& o, uint64_t* L) {
+    L[0] = 0;
+    uint64_t b = std::max<uint64_t>(o.level_base, 16);
+    for (int k = 1; k < kMaxLevels; ++k) {
+        L[k] = b;
+        b = (b > (UINT64_MAX >> 8)) ? UINT64_MAX : b * std::max<uint64_t>(o.level_growth, 2);
+    }
+    L[kMaxLevels] = UINT64_MAX;
+}
+
+// Workgroups per run (per group of 8 runs: mq) of a level launch, one function per launch class.  maxn = the longest run of the
+// launch, nvec = its 16-byte vectors, cnt = the runs of the launch.
+inline int wgs_mq(const LevelOptions& o, uint64_t maxn, uint64_t nvec, size_t cnt) {
+    // 8 queries per pass (scan_i8_mq_kernel): 256-thread workgroups, ~64 Ki codes each, groups of 8
+    // queries as L2-sharing siblings
+    const uint64_t tiles = std::max<uint64_t>((nvec + 255) / 256, 1);
+    uint64_t w = o.wgs_per_item > 0 ? (uint64_t)o.wgs_per_item
+                                    : (maxn + kMqCodesPerWg - 1) / kMqCodesPerWg;
+    const uint64_t ngroups = (cnt + 7) / 8;
+    w = std::max<uint64_t>(w, (kMqMinWgs + ngroups - 1) / ngroups);   // >= 2 rounds of the 2048 resident workgroups
+    w = std::min<uint64_t>(std::min<uint64_t>(w, 65536), std::max<uint64_t>(tiles / kMqMinTiles, 1));
+    if (w >= 8) w &= ~7ull;
+    return (int)w;
+}
+
+inline int wgs_shared(const LevelOptions& o, uint64_t maxn, uint64_t nvec) {
+    // Queries of a batch over the same codes (flat database; IVF queries probing the same cell): the
+    // sibling-major launch makes them share every tile through one XCD's L2, so the codes cross the
+    // HBM interface about once per LAUNCH, not once per query, and the launch is bound by the LDS
+    // lookup rate instead.  Workgroups per run: ~2M codes each (amortises the table build, leaves the
+    // dispatcher room to balance), a multiple of 8 so that the XCD decode applies.
+    uint64_t w = o.wgs_per_item > 0 ? (uint64_t)o.wgs_per_item
+                                    : (maxn + kShareCodesPerWg - 1) / kShareCodesPerWg;
+    w = std::min<uint64_t>(std::max<uint64_t>(w, 64), 512);
+    w = std::min<uint64_t>(w, std::max<uint64_t>((nvec + 4095) / 4096, 1));
+    if (w >= 8) w &= ~7ull;
+    return (int)w;
+}
+
+inline int wgs_small(uint64_t nvec, size_t cnt) {
+    // enough workgroups to fill the chip, but no more: each one pays a table build + bound fetch
+    const uint64_t want = std::max<uint64_t>(1, 4096 / cnt);
+    return (int)std::min<uint64_t>(std::max<uint64_t>((nvec + kSmallVecPerWg - 1) / kSmallVecPerWg, 1), want);
+}
+
+inline int wgs_streaming(const LevelOptions& o, uint64_t maxn, uint64_t nvec, size_t cnt, bool split) {
+    const int wgs_cap = o.wgs_per_item > 0 ? o.wgs_per_item : (o.M == 16 ? 1024 : 512);   // (r02 sweep: 1024 reaches the streaming ceiling of the "probe" variant, 512 is 1.6 % below)
+    // each streaming workgroup builds a 64-128 KiB table: with many runs in the launch, give every
+    // workgroup more tiles instead of more workgroups per run (the split form: at least one 16 Ki-code tile each)
+    const uint64_t want = std::max<uint64_t>(1, 8192 / cnt);
+    const uint64_t units = split ? (maxn + kSplitTile - 1) / kSplitTile : (nvec + 4095) / 4096;
+    return (int)std::min<uint64_t>(std::max<uint64_t>(units, 1), std::min<uint64_t>(wgs_cap, want));
+}
+
+// Host planning of one batch: cuts every query's scan order into bound levels, emits the runs (ScanItem) and the
+// pre-scan items (StartItem), and decides kernel and grid per level launch.  Part: LevelPart, or a struct derived from it.
+template <class Part>
+BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, const LevelBatch& b) {
+    BatchPlan plan;
+    const int cs = o.M / 2, nq = b.nq, ma = b.ma;
+    const uint32_t cpl = 16 / cs;
+    uint64_t L[kMaxLevels + 1];
+    level_bounds(o, L);
+    std::vector<std::vector<ScanItem>> per_level(kMaxLevels);
+    const int k0 = (b.mode != 1 && o.head_level > 0) ? o.head_level : 0;   // levels < k0 belong to the head launch
+    plan.head_codes = k0 ? L[k0] : 0;
+    plan.fc_init.assign(2 * (size_t)nq, 0);
+    for (int q = 0; q < nq; ++q) {
+        uint64_t c = 0;
+        uint64_t stotal = 0;
+        // the starts of a partition this call pre-scans: all of them, or (mode 1) this rank's slice, cut at
+        // multiples of 16 codes so that every slice starts on a 16-byte boundary; (mode 2) none
+        auto starts_range = [&](const LevelPart& pt, uint64_t& lo, uint64_t& len) {
+            lo = 0;
+            len = b.mode == 2 ? 0 : pt.start_n;
+            if (b.mode == 1 && b.pre_nslices > 1) {
+                lo = ((uint64_t)pt.start_n * b.pre_slice / b.pre_nslices) & ~15ull;
+                const uint64_t hi = b.pre_slice + 1 == b.pre_nslices
+                                        ? pt.start_n : (((uint64_t)pt.start_n * (b.pre_slice + 1) / b.pre_nslices) & ~15ull);
+                len = hi > lo ? hi - lo : 0;
+            }
+        };
+        if (b.float_path)
+            for (int a = 0; a < ma; ++a) {
+                const int p = b.assign[(size_t)q * ma + a];
+                if (p >= 0 && p < (int)nparts) {
+                    uint64_t lo, len;
+                    starts_range(parts[p], lo, len);
+                    stotal += len;
+                }
+            }
+        // two-phase pre-scan only pays (and is only needed) when the starts are many
+        uint64_t sample = (b.full_prescan || stotal <= 2ull * o.prescan_sample) ? stotal : o.prescan_sample;
+        uint64_t soff = 0;
+        for (int a = 0; a < ma; ++a) {
+            const int p = b.assign[(size_t)q * ma + a];
+            if (p < 0 || p >= (int)nparts) {
+                plan.refused = "assign[] names a partition that does not exist";
+                return plan;
+            }
+            const LevelPart& pt = parts[p];
+            if (pt.global_n == 0) continue;  // empty partition: db_query_4.cpp:291-293
+            uint64_t slo = 0, slen = 0;
+            if (b.float_path) starts_range(pt, slo, slen);
+            if (slen) {
+                const uint8_t* sc = (pt.d_starts ? pt.d_starts : pt.d_codes) + slo * cs;
+                const uint64_t in_a = soff < sample ? std::min<uint64_t>(slen, sample - soff) : 0;
+                StartItem si;
+                si.table = (uint32_t)((size_t)q * ma + a);
+                si.query = (uint32_t)q;
+                if (in_a) {
+                    si.codes = sc;
+                    si.n = (uint32_t)in_a;
+                    si.out_off = (uint32_t)soff;
+                    si.filter = 0;
+                    plan.sitems_a.push_back(si);
+                }
+                if (in_a < slen) {
+                    si.codes = sc + in_a * cs;
+                    si.n = (uint32_t)(slen - in_a);
+                    si.out_off = 0;
+                    si.filter = 1;
+                    plan.sitems_b.push_back(si);
+                }
+                soff += slen;
+                plan.start_codes += slen;
+            }
+            if (pt.n == 0 || b.mode == 1) continue;   // no codes of the partition here (only its starts replica) / pre-scan only
+            uint64_t prev = 0;
+            for (int k = 0; k < kMaxLevels && prev < pt.n; ++k) {
+                uint64_t cut = pt.n;
+                if (L[k + 1] < c + pt.n) {
+                    cut = L[k + 1] > c ? L[k + 1] - c : 0;
+                    cut -= cut % cpl;  // keep every run 16-byte aligned
+                }
+                if (cut <= prev) continue;
+                if (k < k0) {                                 // scanned by the head launch (same cut: scan_query_kernel, HEAD)
+                    prev = cut;
+                    continue;
+                }
+                // runs longer than 2^31 codes are cut so that 32-bit vector indices cannot wrap
+                for (uint64_t b0 = prev; b0 < cut;) {
+                    const uint64_t len = std::min<uint64_t>(cut - b0, 1ull << 31);
+                    ScanItem it;
+                    it.codes = pt.d_codes + b0 * cs;
+                    it.labels = pt.d_labels;
+                    it.n = (uint32_t)len;
+                    it.pos0 = (uint32_t)b0;
+                    it.key_base = pt.key_base + pt.first_pos;
+                    it.table = (uint32_t)((size_t)q * ma + a);
+                    it.query = (uint32_t)q;
+                    it.order = ((uint32_t)k << 16) | (uint32_t)a;
+                    // padding-lane replay of the partition's last code (simd_layout.hpp:46-50, simd_scan.hpp:67)
+                    it.dup_pos = (pt.first_pos + pt.n == pt.global_n) ? pt.n - 1u : 0xffffffffu;
+                    it.dup_reps = (16u - pt.global_n % 16u) % 16u;
+                    // a long run that starts on a tile of the partition's byte-plane copy may take the split form
+                    it.split = pt.d_split && b0 % kSplitTile == 0 && len >= std::max<uint64_t>(o.split_min_run, o.small_run)
+                                   ? pt.d_split + b0 / kSplitTile * (uint64_t)kSplitBytes * kSplitTile : nullptr;
+                    per_level[k].push_back(it);
+                    b0 += len;
+                }
+                prev = cut;
+            }
+            c += pt.n;
+        }
+        // survivors of the filter: expected R * stotal / sample; 16x head-room, the overflow flag catches the rest
+        uint64_t cap = sample;
+        if (sample < stotal)
+            cap += std::min<uint64_t>(stotal - sample, std::max<uint64_t>(16ull * b.R * ((stotal + sample - 1) / sample), 4096));
+        if (b.mode == 2) sample = cap = b.inj_n;              // the gathered values are the whole "pre-scan output"
+        plan.fc_init[2 * q] = (uint32_t)sample;
+        plan.fc_init[2 * q + 1] = (uint32_t)cap;
+        plan.fc_stride = std::max<uint64_t>(plan.fc_stride, cap);
+    }
+    size_t nitems = 0;
+    for (auto& v : per_level) nitems += v.size();
+    plan.all_items.assign(nitems, ScanItem());
+    size_t off = 0;
+    for (int k = 0; k < kMaxLevels; ++k) {
+        if (per_level[k].empty()) continue;
+        // one launch for the short runs of the level, one for the long ones (one more for those of them with a byte-plane copy)
+        for (int cls = 0; cls < 3; ++cls) {
+            const int small = cls == 0 ? 1 : 0;
+            uint64_t maxn = 0, minn = ~0ull, codes = 0;
+            size_t cnt = 0;
+            bool same = true;
+            for (auto& it : per_level[k]) {
+                if ((it.n < o.small_run) != (small == 1)) continue;
+                if (!small && (it.split != nullptr) != (cls == 2)) continue;
+                if (cnt) {
+                    const ScanItem& f = plan.all_items[off];
+                    same = same && it.codes == f.codes && it.n == f.n && it.pos0 == f.pos0 && it.labels == f.labels &&
+                           it.key_base == f.key_base && it.dup_pos == f.dup_pos && it.dup_reps == f.dup_reps;
+                }
+                plan.all_items[off + cnt++] = it;
+                maxn = std::max<uint64_t>(maxn, it.n);
+                minn = std::min<uint64_t>(minn, it.n);
+                codes += it.n;
+            }
+            if (!cnt) continue;
+            const uint64_t nvec = (maxn + cpl - 1) / cpl;
+            LevelLaunch ll;
+            ll.first = off;
+            ll.nitems = (int)cnt;
+            ll.small = small == 1;
+            ll.maxn = maxn;
+            ll.early = false;
+            ll.shared = !ll.small && same && cnt >= 2 && o.share_variant != 0;
+            ll.mq = ll.shared && o.mq;
+            ll.split = cls == 2 && !ll.shared;
+            ll.split6 = ll.split && o.split6_min_run != 0 && minn >= o.split6_min_run;
+            ll.wgs = ll.mq       ? wgs_mq(o, maxn, nvec, cnt)
+                     : ll.shared ? wgs_shared(o, maxn, nvec)
+                     : ll.small  ? wgs_small(nvec, cnt)
+                                 : wgs_streaming(o, maxn, nvec, cnt, ll.split);
+            ll.codes = codes;
+            plan.launches.push_back(ll);
+            off += cnt;
+        }
+    }
+    return plan;
+}
+
+}  // namespace host
+}  // namespace qadc

@@ -491,8 +491,9 @@ int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6);
 
 /* ---------------------------------------------------------------------------------------------
  * Float ADC — the reference's OTHER query front end, db_query's plain scanner_simple
- * (db_query.cpp:17-46): over whole-byte PQ codes with scan_standard<uint8_t, NSQ>
- * (query_common.hpp:92-146) in a database of its own (qadc_adc_index_create), and over the 4-bit
+ * (db_query.cpp:17-46): over whole-byte PQ codes with scan_standard<uint8_t, NSQ> and
+ * scan_standard<uint16_t, NSQ> (query_common.hpp:92-146) in a database of its own
+ * (qadc_adc_index_create, qadc_adc_index_create16), and over the 4-bit
  * codes of a qadc_index with scan_4<M> (query_common.hpp:59-90) as a VIEW of that index
  * (qadc_adc_index_create_view), which reads the index's partitions in place.
  * A separate engine: it shares no state or option with qadc_index above.  Float tables come from
@@ -514,9 +515,21 @@ int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6);
 typedef struct qadc_adc_index qadc_adc_index;
 
 /* scanner_simple::prepare_database + get_scan_func (db_query.cpp:21-24, query_common.hpp:120-146): sq_bits 8 with
- * sq_count 4, 8 or 16.  Anything else -> QADC_E_ARG with the reference's list of configurations (the 16-bit ones are the
- * reference's but not this engine's; a 4-bit database is not uploaded a second time here: see qadc_adc_index_create_view). */
+ * sq_count 4, 8 or 16.  Anything else -> QADC_E_ARG with the reference's list of configurations (the 16-bit ones have a
+ * constructor of their own, qadc_adc_index_create16; a 4-bit database is not uploaded a second time here: see
+ * qadc_adc_index_create_view). */
 int qadc_adc_index_create(qadc_adc_index** out, int sq_count, int sq_bits, int device_id);
+/* The same for 16-bit sub-quantizers, scan_standard<uint16_t, NSQ>: sq_count 2, 4 or 8, 65536 centroids each.  Anything else ->
+ * QADC_E_ARG with the reference's list of configurations.  The result is an ordinary owned index: every qadc_adc_* call that
+ * takes one works on it, with the layouts scaled from 256 to 65536 centroids per sub-quantizer:
+ *   codes      [n][sq_count] little-endian uint16, passed as bytes: rows of 2 * sq_count bytes (qadc_adc_index_add_partitions)
+ *   tables     [nq][ma][sq_count * 65536] floats: 512 KiB, 1 MiB or 2 MiB per (query, probe) (qadc_adc_query_scan*, _search_tables)
+ *   codebooks  [sq_count][65536][dim / sq_count] (qadc_adc_index_set_pq)
+ *   the table budget counts sq_count * 256 KiB per (query, probe) (qadc_adc_index_set_table_budget)
+ * sum_mode 1 is the grouping of the uint16_t instances as compiled (2: t0 + t1; 4 and 8: as the uint8_t instances), 0 the source
+ * order.  The tables are not staged in LDS but read from global memory through the L2.
+ * qadc_adc_encode_host has no 16-bit form. */
+int qadc_adc_index_create16(qadc_adc_index** out, int sq_count, int device_id);
 int qadc_adc_index_destroy(qadc_adc_index* idx);
 
 /* db_query on the database db_query_4 has open: an ADC index that is a view of the finalized 4-bit index `src` — sq_count = M
@@ -538,7 +551,8 @@ int qadc_adc_index_destroy(qadc_adc_index* idx);
  * A view's calls run on the view's own stream and touch no slot, option or profile of src. */
 int qadc_adc_index_create_view(qadc_adc_index** out, qadc_index* src);
 
-/* Append partitions as base_db::get_partition() yields them (databases.hpp:50-55): row-major codes [sizes[p]][sq_count],
+/* Append partitions as base_db::get_partition() yields them (databases.hpp:50-55): row-major codes [sizes[p]][sq_count]
+ * (bytes; an index of qadc_adc_index_create16: little-endian 16-bit words, 2 * sq_count bytes per code),
  * labels[p] = u32[sizes[p]] or labels == NULL (key = position inside the partition, as scan_standard keys).  All-or-none
  * labels over every call and every non-empty partition (QADC_E_ARG otherwise); empty partitions are legal, their label
  * pointer may be NULL either way.  Host buffers are copied to the GPU. */
@@ -563,12 +577,14 @@ uint64_t qadc_adc_index_host_finishes(const qadc_adc_index* idx);
 
 /* scanner_simple::query_scan (db_query.cpp:26-45) for nq queries:
  *   assign  [nq][ma]                   probed partitions, each in [0, partition_count); duplicates legal; 1 <= ma < 16384
- *   tables  [nq][ma][sq_count*256]     float tables, NOT mutated
+ *   tables  [nq][ma][sq_count*256]     float tables, NOT mutated (a 16-bit index: [sq_count*65536]; a view: [sq_count*16])
  *   R                                  heap capacity, 1 .. QADC_ADC_MAX_R
  *   sum_mode                           1 = the reference's grouping as compiled, 0 = source order
  * Outputs (any may be NULL): keys[q][R], values[q][R], sizes[q] = the ARRAYS of the reference's
  * kv_binheap<unsigned,float>(R) after the query (R sentinel pushes (0, FLT_MAX - t) first, db_query.cpp:31-33).
- * A query may probe at most 2^32 - 1 codes in all.  QADC_E_CAPACITY: see QADC_ADC_MAX_ENTRIES. */
+ * A query may probe at most 2^32 - 1 codes in all.  QADC_E_CAPACITY: see QADC_ADC_MAX_ENTRIES.
+ * A batch whose tables exceed the table budget (qadc_adc_index_set_table_budget) is scanned in sub-batches of whole queries, so
+ * that the library never stages more than one sub-batch's tables, on the host or on the device. */
 int qadc_adc_query_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R,
                         int sum_mode, uint32_t* keys, float* values, int32_t* sizes);
 /* The same with tables and outputs in device memory of the index's device: d_tables [nq][ma][sq_count*256] (as a kernel of the
@@ -591,7 +607,8 @@ int qadc_adc_query_scan_candidates(qadc_adc_index* idx, int nq, int ma, const in
  * the GPU, so that no table crosses the bus.  assign_compute_residuals, rotate_multiple_vectors and the distance tables of
  * every (query, probe) are computed in device memory and scanned there. ---- */
 
-/* base_pq with 8-bit sub-quantizers (quantizers.hpp:96-246): codebooks [sq_count][256][dim / sq_count], copied.  dim must be a
+/* base_pq with 8-bit sub-quantizers (quantizers.hpp:96-246): codebooks [sq_count][256][dim / sq_count] (a 16-bit index:
+ * [sq_count][65536][dim / sq_count]), copied.  dim must be a
  * multiple of sq_count, at most 4096 (QADC_E_ARG otherwise).  A new dim drops the rotation and the coarse centroids. */
 int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks);
 /* opq (quantizers.hpp:248-324): rotation [dim][dim], applied as rotate_multiple_vectors does (289-301):
@@ -603,7 +620,8 @@ int qadc_adc_index_set_rotation(qadc_adc_index* idx, const float* rotation);
 int qadc_adc_index_set_coarse(qadc_adc_index* idx, int K, const float* centroids);
 /* Device memory for the tables of one pass, in bytes (default 1 GiB, the reference's TABLES_BUFFER_SIZE, query_common.hpp:147;
  * 0 = that default).  A batch whose tables need more is processed in sub-batches of whole queries, at least one query each;
- * no result depends on it. */
+ * no result depends on it.  It governs the tables qadc_adc_search* build and the caller's host tables qadc_adc_query_scan and
+ * qadc_adc_query_scan_candidates upload; tables already in device memory (qadc_adc_query_scan_device) are read where they lie. */
 int qadc_adc_index_set_table_budget(qadc_adc_index* idx, uint64_t bytes);
 
 /* process_query + query_scan for nq queries [nq][dim]: find_k_neighbors(k = ma) on the coarse centroids (neighbors.cpp:30-76,
@@ -635,7 +653,8 @@ int qadc_adc_search_tables(qadc_adc_index* idx, int nq, const float* queries, in
  * base_pq::encode_multiple_vectors (quantizers.hpp:222-245).  Per vector: with K > 0 find_k_neighbors(k = 1) on coarse [K][dim]
  * and the residual; the rotation if not NULL; per sub-quantizer the expansion distances to its 256 centroids and the pick of
  * the capacity-1 heap as compiled (the first smallest distance after the last NaN; 255 if distance 255 is NaN).
- * vectors [n][dim] -> codes [n][sq_count], assign_out [n] (may be NULL; written when K > 0).  sq_count 4, 8 or 16. */
+ * vectors [n][dim] -> codes [n][sq_count], assign_out [n] (may be NULL; written when K > 0).  sq_count 4, 8 or 16.
+ * 8-bit only: there is no GPU encoder for the 16-bit sub-quantizers of qadc_adc_index_create16 (the host twin pq_bytes encodes them). */
 int qadc_adc_encode_host(int sq_count, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
                          const float* vectors, uint64_t n, int sum_mode, int32_t* assign_out, uint8_t* codes, int device_id);
 

@@ -1,5 +1,6 @@
 // Host side of the float-ADC engine for whole-byte PQ codes (qadc_adc_* in include/qadc.h): the GPU scanner_simple
-// (db_query.cpp:17-46) over scan_standard<uint8_t, NSQ> (query_common.hpp:92-118), NSQ 4, 8 or 16.
+// (db_query.cpp:17-46) over scan_standard<uint8_t, NSQ> (query_common.hpp:92-118), NSQ 4, 8 or 16, and over
+// scan_standard<uint16_t, NSQ>, NSQ 2, 4 or 8 (qadc_adc_index_create16).
 //
 // A call scans the probed partitions of nq queries in bound levels: level 0 is the first
 // max(R, 512) codes of every query's scan order, each following level 16 times as far; the runs of a level are filtered
@@ -56,7 +57,8 @@ struct DeviceGuard {
 
 struct qadc_adc_index {
     int nsq = 0, device = 0;
-    int centroids = 256;                            // per sub-quantizer: a table is [nsq][centroids] floats (16: a view)
+    int centroids = 256;                            // per sub-quantizer: a table is [nsq][centroids] floats (16: a view; 65536: 16-bit codes)
+    int code_size() const { return centroids == 65536 ? 2 * nsq : nsq; }   // bytes of one code of the owned database
     // A view (qadc_adc_index_create_view): the 4-bit index whose partitions, labels and quantizers it reads in place, counted
     // in src->adc_views, and the partition table the nibble kernel takes — a snapshot of src->parts at creation.
     qadc_index* src = nullptr;
@@ -89,7 +91,7 @@ struct qadc_adc_index {
     int dim = 0, K = 0;                             // dim 0: no set_pq yet;  K 0: flat (no coarse quantizer)
     bool rotated = false;
     uint64_t table_budget = 1ull << 30;             // bytes of device tables per sub-batch (TABLES_BUFFER_SIZE, query_common.hpp:147)
-    DevBuf<float> d_codebooks, d_cbnorm;            // [nsq][256][dim/nsq];  [2][nsq*256] ||c||^2 under sum_mode 0 and 1
+    DevBuf<float> d_codebooks, d_cbnorm;            // [nsq][centroids][dim/nsq];  [2][nsq*centroids] ||c||^2 under sum_mode 0 and 1
     DevBuf<float> d_rotation, d_coarse, d_cnorm;    // [dim][dim];  [K][dim];  [2][K]
     DevBuf<float> d_queries, d_qnorm, d_cdist, d_tables;
     const float* cur_queries = nullptr;             // the queries of the call: d_queries, or the caller's device memory
@@ -363,6 +365,54 @@ int copy_stream(qadc_adc_index* idx, int nq, uint64_t cand_capacity, uint32_t* c
     return QADC_OK;
 }
 
+// queries per sub-batch: whole queries whose tables fit the budget, at least one
+int queries_per_pass(const qadc_adc_index* idx, int nq, int ma) {
+    const uint64_t per_query = (uint64_t)ma * idx->nsq * idx->centroids * 4;
+    return (int)std::min<uint64_t>((uint64_t)nq, std::max<uint64_t>(1, idx->table_budget / per_query));
+}
+
+// The ordered streams of the sub-batches of one call, appended pass by pass; a single pass leaves its stream where scan_batch put it.
+struct StreamGather {
+    bool on;
+    std::vector<uint64_t> off{0};
+    std::vector<uint32_t> keys;
+    std::vector<float> vals;
+    explicit StreamGather(bool on_) : on(on_) {}
+    void append(const qadc_adc_index* idx, int n) {
+        if (!on) return;
+        const uint64_t base = off.back();
+        for (int q = 1; q <= n; ++q) off.push_back(base + idx->stream_off[q]);
+        keys.insert(keys.end(), idx->stream_keys.begin(), idx->stream_keys.end());
+        vals.insert(vals.end(), idx->stream_vals.begin(), idx->stream_vals.end());
+    }
+    void publish(qadc_adc_index* idx) {
+        if (!on) return;
+        idx->stream_off.swap(off);
+        idx->stream_keys.swap(keys);
+        idx->stream_vals.swap(vals);
+    }
+};
+
+// scan_batch on the caller's host tables, in sub-batches of whole queries whose tables fit the table budget: the host and the
+// device staging buffers never hold more than one pass's tables (a 16-bit table is up to 2 MiB per (query, probe)).
+int scan_host_tables(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
+                     const DeviceOut* out = nullptr) {
+    if (int rc = check_query_args(idx, nq, ma, assign, tables, R, sum_mode)) return rc;
+    const int per = queries_per_pass(idx, nq, ma);
+    if (per >= nq) return scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode, out);
+    const size_t per_query = (size_t)ma * idx->nsq * idx->centroids;
+    StreamGather gather(!out);
+    for (int q0 = 0; q0 < nq; q0 += per) {
+        const int n = std::min(per, nq - q0);
+        const DeviceOut sub = out ? DeviceOut{out->keys + (size_t)q0 * R, out->values + (size_t)q0 * R, out->sizes + q0} : DeviceOut{};
+        if (int rc = scan_batch(idx, n, ma, assign + (size_t)q0 * ma, tables + (size_t)q0 * per_query, nullptr, R, sum_mode, out ? &sub : nullptr))
+            return rc;
+        gather.append(idx, n);
+    }
+    gather.publish(idx);
+    return QADC_OK;
+}
+
 // ---- feeders: query vectors -> assign + device tables (qadc_adc_search*) ----
 
 constexpr int kCoarseChunk = 32768;   // queries per coarse-assignment pass (the distance scratch is chunk x K floats)
@@ -408,7 +458,7 @@ int resolve_feeders(qadc_adc_index* idx, int nq, const float* queries, int ma, i
         const FeederState& s = idx->src->feed;
         *f = Feeders{s.dim, s.K, s.d_codebooks.p, nullptr, s.has_rotation ? s.d_rotation.p : nullptr, s.K ? s.d_coarse.p : nullptr, nullptr};
     } else {
-        *f = Feeders{idx->dim, idx->K, idx->d_codebooks.p, idx->d_cbnorm.p + mode * idx->nsq * 256, idx->rotated ? idx->d_rotation.p : nullptr,
+        *f = Feeders{idx->dim, idx->K, idx->d_codebooks.p, idx->d_cbnorm.p + mode * idx->nsq * idx->centroids, idx->rotated ? idx->d_rotation.p : nullptr,
                      idx->K ? idx->d_coarse.p : nullptr, idx->d_cnorm.p + mode * idx->K};
     }
     if (!f->dim)
@@ -478,15 +528,9 @@ int enqueue_tables(qadc_adc_index* idx, const Feeders& f, int q0, int nq, int ma
         HIPCHECK(hipGetLastError());
         return QADC_OK;
     }
-    HIPCHECK(launch_adc_tables(queries, f.coarse, assign, f.codebooks, f.cbnorm, f.rotation, nq, ma, idx->nsq, f.dim, expansion,
+    HIPCHECK(launch_adc_tables(queries, f.coarse, assign, f.codebooks, f.cbnorm, f.rotation, nq, ma, idx->nsq, idx->centroids, f.dim, expansion,
                                           sum_mode, idx->d_tables.p, idx->stream));
     return QADC_OK;
-}
-
-// queries per sub-batch: whole queries whose tables fit the budget, at least one
-int queries_per_pass(const qadc_adc_index* idx, int nq, int ma) {
-    const uint64_t per_query = (uint64_t)ma * idx->nsq * idx->centroids * 4;
-    return (int)std::min<uint64_t>((uint64_t)nq, std::max<uint64_t>(1, idx->table_budget / per_query));
 }
 
 // Feeders + scan of the whole batch in sub-batches; leaves the ordered stream of all nq queries in idx->stream_*, or, given
@@ -503,10 +547,7 @@ int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int 
     if (int rc = enqueue_tables(idx, f, 0, per, ma, table_form, sum_mode)) return rc;   // (runs while the host plans the first scan)
     if (int rc = wait_assign(idx, f, ma)) return rc;
     if (assign_out) std::memcpy(assign_out, idx->h_assign.p, (size_t)nq * ma * 4);
-    const bool gather = !out && per < nq;   // a single pass leaves its stream where scan_batch put it
-    std::vector<uint64_t> off{0};
-    std::vector<uint32_t> keys;
-    std::vector<float> vals;
+    StreamGather gather(!out && per < nq);
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int n = std::min(per, nq - q0);
         if (q0)   // (the scan before it has been waited for: the table buffer is free)
@@ -514,17 +555,9 @@ int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int 
         const DeviceOut sub = out ? DeviceOut{out->keys + (size_t)q0 * R, out->values + (size_t)q0 * R, out->sizes + q0} : DeviceOut{};
         if (int rc = scan_batch(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, R, sum_mode, out ? &sub : nullptr))
             return rc;
-        if (!gather) continue;
-        const uint64_t base = off.back();
-        for (int q = 1; q <= n; ++q) off.push_back(base + idx->stream_off[q]);
-        keys.insert(keys.end(), idx->stream_keys.begin(), idx->stream_keys.end());
-        vals.insert(vals.end(), idx->stream_vals.begin(), idx->stream_vals.end());
+        gather.append(idx, n);
     }
-    if (gather) {
-        idx->stream_off.swap(off);
-        idx->stream_keys.swap(keys);
-        idx->stream_vals.swap(vals);
-    }
+    gather.publish(idx);
     return QADC_OK;
 }
 
@@ -621,17 +654,12 @@ struct Scratch {   // device memory of a stateless entry point, freed on every e
 
 extern "C" {
 
-int qadc_adc_index_create(qadc_adc_index** out, int sq_count, int sq_bits, int device_id) {
-    if (!out) return fail(QADC_E_ARG, "out is null");
-    DeviceGuard guard;
-    *out = nullptr;
-    if (sq_bits != 8 || (sq_count != 4 && sq_count != 8 && sq_count != 16))
-        return fail(QADC_E_ARG,
-                    "Unsupported (nsq,nsq_bits) configuration. Supported configurations are: (16,4) (4,8) (8,8) (16,8) (2,16) (4,16) "
-                    "(8,16); this engine takes (4,8) (8,8) (16,8)");
+// An index that owns its codes: nsq sub-quantizers of `centroids` centroids each (256: one byte per sub-quantizer, 65536: two).
+static int create_owned(qadc_adc_index** out, int nsq, int centroids, int device_id) {
     if (int rc = qadc_device_prepare(device_id)) return rc;   // (the device's stream set first: DESIGN.md section 5)
     qadc_adc_index* idx = new qadc_adc_index();
-    idx->nsq = sq_count;
+    idx->nsq = nsq;
+    idx->centroids = centroids;
     idx->device = device_id;
     const hipError_t e = hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -646,6 +674,29 @@ int qadc_adc_index_create(qadc_adc_index** out, int sq_count, int sq_bits, int d
     }
     *out = idx;
     return QADC_OK;
+}
+
+int qadc_adc_index_create(qadc_adc_index** out, int sq_count, int sq_bits, int device_id) {
+    if (!out) return fail(QADC_E_ARG, "out is null");
+    DeviceGuard guard;
+    *out = nullptr;
+    if (sq_bits != 8 || (sq_count != 4 && sq_count != 8 && sq_count != 16))
+        return fail(QADC_E_ARG,
+                    "Unsupported (nsq,nsq_bits) configuration. Supported configurations are: (16,4) (4,8) (8,8) (16,8) (2,16) (4,16) "
+                    "(8,16); this engine takes (4,8) (8,8) (16,8) here, (2,16) (4,16) (8,16) through qadc_adc_index_create16 and (16,4) "
+                    "(32,4) as a view (qadc_adc_index_create_view)");
+    return create_owned(out, sq_count, 256, device_id);
+}
+
+int qadc_adc_index_create16(qadc_adc_index** out, int sq_count, int device_id) {
+    if (!out) return fail(QADC_E_ARG, "out is null");
+    DeviceGuard guard;
+    *out = nullptr;
+    if (sq_count != 2 && sq_count != 4 && sq_count != 8)
+        return fail(QADC_E_ARG,
+                    "Unsupported (nsq,nsq_bits) configuration. Supported configurations are: (16,4) (4,8) (8,8) (16,8) (2,16) (4,16) "
+                    "(8,16); qadc_adc_index_create16 takes (2,16) (4,16) (8,16)");
+    return create_owned(out, sq_count, 65536, device_id);
 }
 
 int qadc_adc_index_create_view(qadc_adc_index** out, qadc_index* src) {
@@ -754,7 +805,7 @@ int qadc_adc_index_add_partitions(qadc_adc_index* idx, int part_count, const uin
     for (int p = 0; p < part_count; ++p) {
         off[p] = bytes;
         loff[p] = nlab;
-        bytes += align_up((uint64_t)sizes[p] * idx->nsq, 16);
+        bytes += align_up((uint64_t)sizes[p] * idx->code_size(), 16);
         if (lab == 1) nlab += sizes[p];
     }
     if (int rc = grow_device(idx->codes, idx->code_bytes, bytes + 16, idx->stream)) return rc;
@@ -762,7 +813,7 @@ int qadc_adc_index_add_partitions(qadc_adc_index* idx, int part_count, const uin
         if (int rc = grow_device(idx->labels, idx->label_count, std::max<uint64_t>(nlab, 1), idx->stream)) return rc;
     for (int p = 0; p < part_count; ++p) {
         if (!sizes[p]) continue;
-        HIPCHECK(hipMemcpy(idx->codes.p + off[p], codes[p], (size_t)sizes[p] * idx->nsq, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(idx->codes.p + off[p], codes[p], (size_t)sizes[p] * idx->code_size(), hipMemcpyHostToDevice));
         if (lab == 1) HIPCHECK(hipMemcpy(idx->labels.p + loff[p], labels[p], (size_t)sizes[p] * 4, hipMemcpyHostToDevice));
     }
     HIPCHECK(hipMemset(idx->codes.p + bytes, 0, 16));
@@ -806,7 +857,7 @@ uint32_t qadc_adc_index_partition_size(const qadc_adc_index* idx, int part) {
 int qadc_adc_query_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
                         uint32_t* keys, float* values, int32_t* sizes) {
     return heaps_to_host(idx, nq, R, keys, values, sizes,
-                         [&](const DeviceOut* out) { return scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode, out); });
+                         [&](const DeviceOut* out) { return scan_host_tables(idx, nq, ma, assign, tables, R, sum_mode, out); });
 }
 
 int qadc_adc_query_scan_device(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, int R, int sum_mode,
@@ -818,7 +869,7 @@ int qadc_adc_query_scan_device(qadc_adc_index* idx, int nq, int ma, const int32_
 int qadc_adc_query_scan_candidates(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R,
                                    int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets) {
     return stream_to_host(idx, nq, cand_capacity, cand_keys, cand_vals, offsets,
-                          [&](const DeviceOut*) { return scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode); });
+                          [&](const DeviceOut*) { return scan_host_tables(idx, nq, ma, assign, tables, R, sum_mode); });
 }
 
 int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks) {
@@ -829,7 +880,7 @@ int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks) 
     if (dim > kAdcMaxDim) return fail(QADC_E_ARG, "dim must be <= " + std::to_string(kAdcMaxDim));
     DeviceGuard guard;
     HIPCHECK(hipSetDevice(idx->device));
-    const size_t rows = (size_t)idx->nsq * 256;
+    const size_t rows = (size_t)idx->nsq * idx->centroids;
     HIPCHECK(idx->d_codebooks.ensure(rows * (dim / idx->nsq)));
     HIPCHECK(idx->d_cbnorm.ensure(2 * rows));
     HIPCHECK(hipMemcpyAsync(idx->d_codebooks.p, codebooks, rows * (dim / idx->nsq) * 4, hipMemcpyHostToDevice, idx->stream));

@@ -1,10 +1,11 @@
-// Float ADC over whole-byte PQ codes on gfx950: the GPU form of the reference's scan_standard<uint8_t, NSQ>
+// Float ADC over whole-byte PQ codes on gfx950: the GPU form of the reference's scan_standard<uint8_t | uint16_t, NSQ>
 // (query_common.hpp:92-118) as scanner_simple::query_scan drives it (db_query.cpp:26-45).  Host side: csrc/qadc_adc.cpp.
 //
 //   adc_scan_kernel    one workgroup per run of codes of one probed partition: the (query, slot) float table goes to LDS, each lane
 //                      sums the looked-up entries of its codes in the reference's grouping and emits (candidate, key, scan index)
 //                      when candidate < bound[query].  One body over ByteCodes<NSQ> (tables [NSQ][256], the owned database by
-//                      value) and NibbleCodes<M> (the view: a 4-bit index read in place, scan_4<M>, tables [M][16]);
+//                      value), NibbleCodes<M> (the view: a 4-bit index read in place, scan_4<M>, tables [M][16]) and
+//                      WordCodes<NSQ> (16-bit codes, tables [NSQ][65536]: too large for LDS, gathered from global memory);
 //   adc_select_kernel one workgroup per query: bound = the R-th smallest value the query emitted so far (radix select on
 //                      the order-preserving integer image of the floats), the bound of the next level's runs;
 //   adc_pack_kernel    the per-query regions packed densely for one device-to-host copy;
@@ -31,11 +32,13 @@ struct alignas(BYTES) CodeWords {   // one code, 4, 8 or 16 bytes = one dword, d
 };
 
 // What a code is and how its looked-up entries are summed: the only things the scan kernel leaves to a policy.  kBytes =
-// bytes per code (one dword, dwordx2 or dwordx4 load), kTable = floats of one (query, slot) table, sum<SUM>(lds, words) = the
-// candidate of one code in the reference's float grouping (SUM 0 source order, 1 as compiled).
+// bytes per code (one dword, dwordx2 or dwordx4 load), kTable = floats of one (query, slot) table, kTableInLds = the kernel
+// copies that table to LDS before it scans, sum<SUM>(table, words) = the candidate of one code in the reference's float
+// grouping (SUM 0 source order, 1 as compiled).
 template <int NSQ>
 struct ByteCodes {   // scan_standard<uint8_t, NSQ>: one byte per sub-quantizer, tables [NSQ][256]
     static constexpr int kBytes = NSQ, kTable = NSQ * 256;
+    static constexpr bool kTableInLds = true;
     template <int SUM>
     static __device__ __forceinline__ float sum(const float* lds, const CodeWords<kBytes>& c) {
         float t[NSQ];
@@ -64,6 +67,7 @@ struct ByteCodes {   // scan_standard<uint8_t, NSQ>: one byte per sub-quantizer,
 template <int M>
 struct NibbleCodes {
     static constexpr int kBytes = M / 2, kTable = M * 16;
+    static constexpr bool kTableInLds = true;
     template <int SUM>
     static __device__ __forceinline__ float sum(const float* lds, const CodeWords<kBytes>& c) {
         float v[M];
@@ -72,6 +76,59 @@ struct NibbleCodes {
         return adc_sum_code<M>(v, SUM, 0.0f);
     }
 };
+
+// scan_standard<uint16_t, NSQ>: one little-endian 16-bit word per sub-quantizer, tables [NSQ][65536] — 512 KiB, 1 MiB or 2 MiB per
+// (query, slot), which no LDS holds: the table stays in global memory and every entry is a cached 4-byte gather, served by
+// the L2 of the workgroup's XCD while the tables live in a launch fit it.  The kernel reads the
+// codes with non-temporal loads so that the code stream does not push table lines out.  gather() issues the NSQ loads of one
+// code and add<SUM>() sums them, so that the kernel can have the loads of all its codes in flight before the first add.
+// Grouping (pinned by tests/golden/ref_scan_standard_u16_cases.npz): NSQ 2 t0 + t1 (no leading 0 +), NSQ 4 and 8 as the
+// uint8_t instances.
+template <int NSQ>
+struct WordCodes {
+    static constexpr int kBytes = 2 * NSQ, kTable = NSQ * 65536;
+    static constexpr bool kTableInLds = false;
+    static __device__ __forceinline__ void gather(const float* __restrict__ tab, const CodeWords<kBytes>& c, float* t) {
+#pragma unroll
+        for (int m = 0; m < NSQ; ++m) t[m] = tab[m * 65536 + ((c.w[m / 2] >> (16 * (m % 2))) & 0xffffu)];
+    }
+    template <int SUM>
+    static __device__ __forceinline__ float add(const float* t) {
+        if constexpr (SUM == 0) {                                 // source order, from 0 like the reference's loop
+            float s = 0.0f;
+#pragma unroll
+            for (int m = 0; m < NSQ; ++m) s += t[m];
+            return s;
+        } else if constexpr (NSQ == 4) {
+            return adc_sum4_standard_compiled(t);
+        } else if constexpr (NSQ == 8) {
+            return adc_sum8_standard_compiled(t);
+        } else {
+            return t[0] + t[1];
+        }
+    }
+    template <int SUM>
+    static __device__ __forceinline__ float sum(const float* tab, const CodeWords<kBytes>& c) {
+        float t[NSQ];
+        gather(tab, c, t);
+        return add<SUM>(t);
+    }
+};
+
+// One code by a non-temporal load (the word policy: a code is read once and must not displace table lines in L2).
+template <int BYTES>
+__device__ __forceinline__ CodeWords<BYTES> load_code_streaming(const CodeWords<BYTES>* p) {
+    typedef uint32_t words_t __attribute__((ext_vector_type(BYTES / 4)));
+    CodeWords<BYTES> c;
+    if constexpr (BYTES == 4) {
+        c.w[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p));
+    } else {
+        const words_t v = __builtin_nontemporal_load(reinterpret_cast<const words_t*>(p));
+#pragma unroll
+        for (int i = 0; i < BYTES / 4; ++i) c.w[i] = v[i];
+    }
+    return c;
+}
 
 // Where a partition lies, from what the kernel was given (its Source): the owned database by value, or a view's partition table.
 struct PartRef { const uint8_t* codes; const uint32_t* labels; uint32_t key_base; };   // labels null: key = key_base + position
@@ -91,15 +148,19 @@ __global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ 
                                                        const float* __restrict__ tables, const float* __restrict__ bound,
                                                        Emit emit) {
     constexpr int CS = Code::kBytes;
-    __shared__ float lds[Code::kTable];
+    constexpr bool kLds = Code::kTableInLds;
+    __shared__ float lds[kLds ? Code::kTable : 1];                // (the word policy's table stays where it is)
     const Item it = items[first + blockIdx.x];
     const PartRef part = locate(src, assign[(size_t)it.query * ma + it.slot]);
-    const float4* tab = reinterpret_cast<const float4*>(tables + ((size_t)it.query * ma + it.slot) * Code::kTable);
-    for (int i = threadIdx.x; i < Code::kTable / 4; i += kWG) reinterpret_cast<float4*>(lds)[i] = tab[i];
+    const float* __restrict__ gtab = tables + ((size_t)it.query * ma + it.slot) * Code::kTable;
+    if constexpr (kLds) {
+        const float4* tab = reinterpret_cast<const float4*>(gtab);
+        for (int i = threadIdx.x; i < Code::kTable / 4; i += kWG) reinterpret_cast<float4*>(lds)[i] = tab[i];
+    }
     const float b = bound[it.query];
     const uint64_t region = emit.base[it.query];
     const uint32_t cap = emit.cap[it.query];
-    __syncthreads();
+    if constexpr (kLds) __syncthreads();
 
     const int lane = threadIdx.x & 63;
     const unsigned long long below = (1ull << lane) - 1;
@@ -110,11 +171,25 @@ __global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ 
         for (int u = 0; u < kUnroll; ++u) {
             const uint32_t r = base + u * kWG + threadIdx.x;
             valid[u] = r < it.count;
-            if (valid[u]) c[u] = reinterpret_cast<const CodeWords<CS>*>(part.codes)[it.start + r];
+            if constexpr (kLds) {
+                if (valid[u]) c[u] = reinterpret_cast<const CodeWords<CS>*>(part.codes)[it.start + r];
+            } else {   // no branch around the loads: a lane past the run's end reads the run's last code and its sum is dropped
+                c[u] = load_code_streaming(reinterpret_cast<const CodeWords<CS>*>(part.codes) + it.start + min(r, it.count - 1));
+            }
+        }
+        [[maybe_unused]] float t[kLds ? 1 : kUnroll][kLds ? 1 : Code::kBytes / 2];
+        if constexpr (!kLds) {                                    // every gather of the lane is issued before the first add
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) Code::gather(gtab, c[u], t[u]);
         }
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
-            const float v = valid[u] ? Code::template sum<SUM>(lds, c[u]) : 0.0f;
+            float v = 0.0f;
+            if constexpr (kLds) {
+                if (valid[u]) v = Code::template sum<SUM>(lds, c[u]);
+            } else {
+                v = Code::template add<SUM>(t[u]);
+            }
             const bool keep = valid[u] && v < b;                  // NaN, +inf and FLT_MAX never pass (b <= FLT_MAX)
             const unsigned long long m = __ballot(keep);
             if (m == 0) continue;
@@ -410,8 +485,8 @@ __global__ __launch_bounds__(kWG) void adc_copy_words_kernel(const uint32_t* __r
 }
 
 // ---------------------------------------------------------------------------------------------
-// Feeders: what nns_engine(_batch)::process_query does before query_scan (query_common.hpp:194-213, 283-297) and
-// base_pq::encode_multiple_vectors (quantizers.hpp:222-245) for 256 centroids per sub-quantizer.
+// Feeders: what nns_engine(_batch)::process_query does before query_scan (query_common.hpp:194-213, 283-297), for 256 or 65536
+// centroids per sub-quantizer, and base_pq::encode_multiple_vectors (quantizers.hpp:222-245) for 256.
 // Arithmetic entry for entry that of build_tables_kernel (csrc/qadc_kernels.hip) and of the host twin pq_bytes::tables /
 // tables_blas (host/scanner_simple.hpp): residual q - coarse[assign]; OPQ rotation rotated[r] = sum_c x[c] rotation[r][c],
 // one sequential sum in ascending c; direct form = direct_sqdist, expansion form = (||v||^2 + ||c||^2) + (-2 v.c) with the
@@ -436,19 +511,23 @@ struct CentroidRow<0> {
     __device__ __forceinline__ float operator[](int d) const { return p[d]; }
 };
 
-// Grid (query, probe group, sub-quantizer slice).  A workgroup holds the residuals of `probes` probes of one query in LDS
-// (only the components of its sub-quantizers m0 .. m0 + mper); lane c owns centroid c of the current sub-quantizer, keeps its
-// row and walks the probes: every store instruction of the workgroup writes one whole 1 KiB table row.
+// Grid (query, probe group, sub-quantizer slice x centroid slice).  A workgroup holds the residuals of `probes` probes of one
+// query in LDS (only the components of its sub-quantizers m0 .. m0 + mper) and builds `cper` blocks of 256 centroids of each
+// of them (one block is all there is of an 8-bit sub-quantizer; a 16-bit one has 256): lane c owns centroid block * 256 + c
+// of the current sub-quantizer, keeps its row and walks the probes: every store instruction of the workgroup writes one
+// contiguous 1 KiB of a table row.
 // Dynamic LDS: res [probes][mper * ds] | vnorm [probes][mper] | (OPQ) whole un-rotated residuals [probes][dim].
 template <int DS>
 __global__ __launch_bounds__(kWG) void adc_tables_kernel(const float* __restrict__ queries, const float* __restrict__ coarse,
                                                          const int32_t* __restrict__ assign, const float* __restrict__ codebooks,
                                                          const float* __restrict__ cbnorm, const float* __restrict__ rotation,
-                                                         int ma, int nsq, int dim, int probes, int mper, int expansion,
-                                                         int sum_mode, float* __restrict__ tables) {
+                                                         int ma, int nsq, int centroids, int dim, int probes, int mper, int cper,
+                                                         int expansion, int sum_mode, float* __restrict__ tables) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     const int ds = DS ? DS : dim / nsq;
-    const int qi = blockIdx.x, a0 = blockIdx.y * probes, m0 = blockIdx.z * mper, tid = threadIdx.x;
+    const int cslices = centroids / (256 * cper);
+    const int qi = blockIdx.x, a0 = blockIdx.y * probes, m0 = (blockIdx.z / cslices) * mper, tid = threadIdx.x;
+    const int c0 = (blockIdx.z % cslices) * cper * 256;
     const int na = min(probes, ma - a0);
     const int lo = m0 * ds, width = mper * ds;
     float* res = dyn;
@@ -485,16 +564,19 @@ __global__ __launch_bounds__(kWG) void adc_tables_kernel(const float* __restrict
     }
     for (int mm = 0; mm < mper; ++mm) {
         const int m = m0 + mm;
-        CentroidRow<DS> ce;
-        ce.load(codebooks + ((size_t)m * 256 + tid) * ds, ds);
-        const float cn = expansion ? cbnorm[m * 256 + tid] : 0.0f;
-        float* __restrict__ out = tables + (((size_t)qi * ma + a0) * nsq + m) * 256 + tid;
-        for (int a = 0; a < na; ++a) {
-            const float* r = res + a * width + mm * ds;
-            float s;
-            if (expansion) s = expansion_dist(r, ce, ds, vnorm[a * mper + mm], cn);
-            else s = direct_sqdist(r, ce, ds, sum_mode);
-            out[(size_t)a * nsq * 256] = s;
+        for (int cb = 0; cb < cper; ++cb) {
+            const size_t c = (size_t)m * centroids + c0 + cb * 256 + tid;
+            CentroidRow<DS> ce;
+            ce.load(codebooks + c * ds, ds);
+            const float cn = expansion ? cbnorm[c] : 0.0f;
+            float* __restrict__ out = tables + ((size_t)qi * ma + a0) * nsq * centroids + c;
+            for (int a = 0; a < na; ++a) {
+                const float* r = res + a * width + mm * ds;
+                float s;
+                if (expansion) s = expansion_dist(r, ce, ds, vnorm[a * mper + mm], cn);
+                else s = direct_sqdist(r, ce, ds, sum_mode);
+                out[(size_t)a * nsq * centroids] = s;
+            }
         }
     }
 }
@@ -579,6 +661,9 @@ hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, ui
     if (db.centroids == 256 && db.nsq == 16) return scan(ByteCodes<16>{}, db.bytes);
     if (db.centroids == 16 && db.nsq == 16) return scan(NibbleCodes<16>{}, db.parts);
     if (db.centroids == 16 && db.nsq == 32) return scan(NibbleCodes<32>{}, db.parts);
+    if (db.centroids == 65536 && db.nsq == 2) return scan(WordCodes<2>{}, db.bytes);
+    if (db.centroids == 65536 && db.nsq == 4) return scan(WordCodes<4>{}, db.bytes);
+    if (db.centroids == 65536 && db.nsq == 8) return scan(WordCodes<8>{}, db.bytes);
     return hipErrorInvalidValue;
 }
 
@@ -616,10 +701,10 @@ hipError_t launch_adc_copy_words(const void* src, void* dst, size_t words, hipSt
 }
 
 hipError_t launch_adc_tables(const float* d_queries, const float* d_coarse, const int32_t* d_assign, const float* d_codebooks,
-                             const float* d_cbnorm, const float* d_rotation, int nq, int ma, int nsq, int dim, int expansion,
-                             int sum_mode, float* d_tables, hipStream_t s) {
+                             const float* d_cbnorm, const float* d_rotation, int nq, int ma, int nsq, int centroids, int dim,
+                             int expansion, int sum_mode, float* d_tables, hipStream_t s) {
     if (nq <= 0 || ma <= 0) return hipSuccess;
-    if (dim <= 0 || dim > kAdcMaxDim || dim % nsq != 0) return hipErrorInvalidValue;
+    if (dim <= 0 || dim > kAdcMaxDim || dim % nsq != 0 || (centroids != 256 && centroids != 65536)) return hipErrorInvalidValue;
     const int ds = dim / nsq;
     // probes per workgroup: up to 16; a small batch is cut finer (sub-quantizers over grid.z, fewer probes) to fill the chip
     long groups = (ma + 15) / 16;
@@ -630,10 +715,15 @@ hipError_t launch_adc_tables(const float* d_queries, const float* d_coarse, cons
     const int mper = nsq / msplit;
     auto lds_floats = [&](int p) { return (size_t)p * mper * ds + (size_t)p * mper + (d_rotation ? (size_t)p * dim : 0); };
     while (probes > 1 && lds_floats(probes) * sizeof(float) > 48 * 1024) probes = (probes + 1) / 2;
-    const dim3 grid((unsigned)nq, (unsigned)((ma + probes - 1) / probes), (unsigned)msplit);
+    // blocks of 256 centroids per workgroup: all of them (one) for 8-bit sub-quantizers; the 256 blocks of a 16-bit one are cut
+    // into slices over grid.z until the launch has about 2048 workgroups (every slice computes the residuals again)
+    const long pgroups = (ma + probes - 1) / probes;
+    int cper = centroids / 256;
+    while (cper > 1 && (long)nq * pgroups * msplit * (centroids / (256 * cper)) < 2048) cper /= 2;
+    const dim3 grid((unsigned)nq, (unsigned)pgroups, (unsigned)(msplit * (centroids / (256 * cper))));
     const size_t lds = lds_floats(probes) * sizeof(float);
 #define QADC_AT(DS) hipLaunchKernelGGL((adc_tables_kernel<DS>), grid, dim3(kWG), lds, s, d_queries, d_coarse, d_assign, d_codebooks, \
-                                       d_cbnorm, d_rotation, ma, nsq, dim, probes, mper, expansion, sum_mode, d_tables)
+                                       d_cbnorm, d_rotation, ma, nsq, centroids, dim, probes, mper, cper, expansion, sum_mode, d_tables)
     if (ds == 8) QADC_AT(8);
     else if (ds == 16) QADC_AT(16);
     else if (ds == 32) QADC_AT(32);

@@ -22,7 +22,7 @@ struct Emit {
 };
 
 struct Db {
-    const uint8_t* codes;     // every partition, row-major [n][NSQ], each starting on a 16-byte boundary, 16 bytes of tail padding
+    const uint8_t* codes;     // every partition, row-major [n][code bytes], each starting on a 16-byte boundary, 16 bytes of tail padding
     const uint64_t* off;      // [part] byte offset of the partition in codes
     const uint32_t* labels;   // all partitions' labels, or nullptr (flat keys = position inside the partition)
     const uint64_t* lab_off;  // [part] first label of the partition
@@ -38,7 +38,9 @@ struct Part4 {
 };
 
 // The database launch_adc_scan reads.  centroids 256: nsq 4, 8 or 16 whole-byte codes in `bytes`, tables [nq][ma][nsq][256] (scan_standard<uint8_t,
-// NSQ>).  centroids 16: nsq 16 or 32 nibble codes in `parts`, tables [nq][ma][nsq][16] summed as adc_sum_code<M> (scan_4<M>, query_common.hpp:59-90).
+// NSQ>).  centroids 65536: nsq 2, 4 or 8 little-endian 16-bit codes in `bytes` (rows of 2 nsq bytes), tables [nq][ma][nsq][65536], read
+// from global memory (scan_standard<uint16_t, NSQ>).  centroids 16: nsq 16 or 32 nibble codes in `parts`, tables [nq][ma][nsq][16]
+// summed as adc_sum_code<M> (scan_4<M>, query_common.hpp:59-90).
 struct ScanDb {
     int nsq, centroids;
     Db bytes;             // a kernel argument by value: the owned index's code loads are global loads
@@ -71,14 +73,15 @@ hipError_t launch_adc_copy_words(const void* src, void* dst, size_t words, hipSt
 
 constexpr int kAdcMaxDim = 4096;      // largest vector dimension the feeders take (their residuals live in LDS)
 
-// The float tables of nq queries from their vectors: d_tables [nq][ma][nsq][256], the layout launch_adc_scan reads.
-// d_assign [nq][ma] probed partitions (read only with d_coarse); d_coarse [K][dim] or nullptr (flat: residual = query);
-// d_rotation [dim][dim] or nullptr; d_codebooks [nsq][256][dim/nsq]; d_cbnorm [nsq*256] = launch_row_sqnorm of the codebook rows
-// under the same sum_mode (read by the expansion form only).  expansion 0 = the direct form (compute_dists_single_simd_cg),
-// 1 = the BLAS-expansion form (compute_dists_multiple_blas_cg).  dim <= kAdcMaxDim, dim % nsq == 0.
+// The float tables of nq queries from their vectors: d_tables [nq][ma][nsq][centroids], the layout launch_adc_scan reads;
+// centroids is 256 or 65536.  d_assign [nq][ma] probed partitions (read only with d_coarse); d_coarse [K][dim] or nullptr (flat:
+// residual = query); d_rotation [dim][dim] or nullptr; d_codebooks [nsq][centroids][dim/nsq]; d_cbnorm [nsq*centroids] =
+// launch_row_sqnorm of the codebook rows under the same sum_mode (read by the expansion form only).  expansion 0 = the direct
+// form (compute_dists_single_simd_cg), 1 = the BLAS-expansion form (compute_dists_multiple_blas_cg).  dim <= kAdcMaxDim,
+// dim % nsq == 0.
 hipError_t launch_adc_tables(const float* d_queries, const float* d_coarse, const int32_t* d_assign, const float* d_codebooks,
-                             const float* d_cbnorm, const float* d_rotation, int nq, int ma, int nsq, int dim, int expansion,
-                             int sum_mode, float* d_tables, hipStream_t s);
+                             const float* d_cbnorm, const float* d_rotation, int nq, int ma, int nsq, int centroids, int dim,
+                             int expansion, int sum_mode, float* d_tables, hipStream_t s);
 // encode_multiple_vectors (quantizers.hpp:222-245) with 256 centroids per sub-quantizer on vectors already made residuals and
 // rotated: d_codes [n][nsq], the capacity-1 heap's pick as compiled on the expansion distances.
 hipError_t launch_adc_encode(const float* d_x, uint64_t n, int nsq, int dim, const float* d_codebooks, const float* d_cbnorm,

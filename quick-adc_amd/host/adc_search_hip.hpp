@@ -10,6 +10,7 @@
 //   Db:   int partition_count(); void get_partition(int, const std::uint8_t*&, unsigned*&, unsigned&);
 //         int coarse_count(); const float* coarse_centroids();            (0 / nullptr: a flat database)
 //         pq->sq_count, pq->sq_bits, pq->dim, pq->centroids, pq->rotation  (host/scanner_simple.hpp pq_bytes; query_driver.hpp pq4)
+// 16-bit codes ((2,16) (4,16) (8,16)): the index is qadc_adc_index_create16's, the codebooks [sq_count][65536][dim / sq_count].
 // 4-bit codes ((16,4) (32,4)): database and quantizers go into a qadc_index, and the engine searches through a view of it
 // (qadc_adc_index_create_view) — the index db_query_4's engine would use, asked the exact float question.
 //   Heap: int capacity(); void push(unsigned, float)                       (kv_binheap<unsigned, float>, binheap.hpp)
@@ -76,7 +77,8 @@ struct adc_search_engine_hip {
             prepare_nibbles(m);
             return;
         }
-        if (qadc_adc_index_create(&index, m, bits, device) != QADC_OK) die("Cannot create the GPU index");
+        if ((bits == 16 ? qadc_adc_index_create16(&index, m, device) : qadc_adc_index_create(&index, m, bits, device)) != QADC_OK)
+            die("Cannot create the GPU index");
         if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
         const int part_count = db.partition_count();
         std::vector<const std::uint8_t*> codes(part_count);

@@ -10,12 +10,14 @@
 //   adc_sum<N>(t)      N looked-up table entries of one code, t[0..N) in the source's order:
 //                        scan_standard<T,N> (query_common.hpp:92-118): t[m] = dists[m*NCENT + code[m]]
 //                        scan_4<N>          (query_common.hpp:59-90):  t[2b] = low-nibble entry, t[2b+1] = high-nibble entry
+//                      N 2:  t0 + t1 (no leading 0 +: two -0 give -0)
 //                      N 4:  (t1+t2) + (t3+t0)
 //                      N 8:  ((t1+t2)+(t3+t4)) + ((t5+t6)+(t7+t0))
 //                      N 16: ((A+B)+C)+D   A=(t5+t6)+(t7+t8)  B=(t1+t2)+(t3+t4)  C=(t11+t12)+(t9+t10)  D=(t13+t14)+(t15+t0)
 //                      N 32: the 16-term grouping of t[0..16), then s = s + ((t[j+2]+t[j+3]) + (t[j]+t[j+1])), j = 16, 20, 24, 28
-//                      other N, and every 16-bit instance (scan_standard<uint16_t, N>: no such instance of the reference was read or
-//                      pinned — adc_sum<N, false>): source order
+//                      The grouping depends on N alone: the uint16_t instances of scan_standard (N 2, 4, 8) group like the uint8_t
+//                      ones, pinned to the reference's text as compiled by tests/golden/ref_scan_standard_u16_cases.npz
+//                      (tools/gen_golden_adc16.py).  Other N: source order.
 //   sqdist(x, c, ds)   fmanorm<ds/8, ds%8>(x, c) (distances.hpp:60-76) as compute_dists_single_simd_cg calls it (294-311):
 //                      per AVX lane j acc[j] = fma(d, d, acc[j]) over the blocks (d = x - c), reduceadd's tree
 //                      (acc[j] + acc[j+4]; (r0+r2) + (r1+r3)); the scalar remainder is paired
@@ -38,13 +40,14 @@ inline int& float_sum_mode() {
     return mode;
 }
 
-template <int N, bool PINNED = true>
+template <int N>
 inline float adc_sum(const float* t) {
-    if (!PINNED || float_sum_mode() == 0 || !(N == 4 || N == 8 || N == 16 || N == 32)) {
+    if (float_sum_mode() == 0 || !(N == 2 || N == 4 || N == 8 || N == 16 || N == 32)) {
         float s = 0;
         for (int i = 0; i < N; ++i) s += t[i];
         return s;
     }
+    if (N == 2) return t[0] + t[1];
     if (N == 4) return (t[1] + t[2]) + (t[3] + t[0]);
     if (N == 8) return ((t[1] + t[2]) + (t[3] + t[4])) + ((t[5] + t[6]) + (t[7] + t[0]));
     const float a = (t[5] + t[6]) + (t[7] + t[8]);

@@ -4,7 +4,8 @@
 // `query_scan(query, assign, ma, tables, table_dim, bh, metrics)`.  This type has the same three, with the same argument
 // meaning and error behaviour (get_scan_func's message + std::exit(1) for a configuration it does not take), and forwards to
 // the float-ADC engine of include/qadc.h (qadc_adc_*): db_query.cpp drops it in by swapping the scanner type.
-// Whole-byte codes ((4,8) (8,8) (16,8)) go into an ADC index of their own; 4-bit codes ((16,4) (32,4), scan_4<M>) go into a
+// Whole-byte codes ((4,8) (8,8) (16,8), and (2,16) (4,16) (8,16) through qadc_adc_index_create16) go into an ADC index of their
+// own; 4-bit codes ((16,4) (32,4), scan_4<M>) go into a
 // qadc_index — the database db_query_4's scanner_hip uses — and are scanned through a view of it (qadc_adc_index_create_view).
 //   Db:   int partition_count(); void get_partition(int, const std::uint8_t*&, unsigned*&, unsigned&);
 //         pq->sq_count, pq->sq_bits                                      (databases.hpp:34-63)
@@ -32,7 +33,7 @@ struct scanner_simple_hip {
     typedef Heap BhType;
 
     int device, sum_mode;
-    int table_floats = 0;   // sq_count * 256, or sq_count * 16 for 4-bit codes
+    int table_floats = 0;   // sq_count * 256, sq_count * 65536 for 16-bit codes, sq_count * 16 for 4-bit codes
     int finish = QADC_ADC_FINISH_HOST;
     qadc_adc_index* index;
     qadc_index* source = nullptr;   // 4-bit codes: the index that holds the database; `index` is a view of it
@@ -66,19 +67,22 @@ struct scanner_simple_hip {
     void prepare_database(Db& db) {
         const int m = db.pq->sq_count, bits = db.pq->sq_bits;
         const bool nibbles = bits == 4 && (m == 16 || m == 32);
-        if (!nibbles && (bits != 8 || (m != 4 && m != 8 && m != 16))) {   // get_scan_func's message (the 16-bit ones are not on the GPU)
+        const bool bytes = bits == 8 && (m == 4 || m == 8 || m == 16);
+        const bool words = bits == 16 && (m == 2 || m == 4 || m == 8);
+        if (!nibbles && !bytes && !words) {   // get_scan_func's message
             std::cerr << "Unsupported (nsq,nsq_bits) configuration." << std::endl;
             std::cerr << "Supported configurations are: (16,4) (4,8) (8,8) (16,8) (2,16) (4,16) (8,16)." << std::endl;
-            std::cerr << "This GPU scanner takes (16,4) (32,4) (4,8) (8,8) (16,8)." << std::endl;
+            std::cerr << "This GPU scanner takes those and (32,4)." << std::endl;
             std::exit(1);
         }
         if (nibbles) {
             prepare_nibbles(db, m);
             return;
         }
-        if (qadc_adc_index_create(&index, m, bits, device) != QADC_OK) die("Cannot create the GPU index");
+        if ((words ? qadc_adc_index_create16(&index, m, device) : qadc_adc_index_create(&index, m, bits, device)) != QADC_OK)
+            die("Cannot create the GPU index");
         if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
-        table_floats = m * 256;
+        table_floats = m * (words ? 65536 : 256);
         // every partition in one call (one upload of the partition table, one growth of the device copy)
         const int part_count = db.partition_count();
         std::vector<const std::uint8_t*> codes(part_count);
@@ -118,7 +122,8 @@ struct scanner_simple_hip {
     }
 
     // scanner_simple::query_scan (db_query.cpp:26-45).  `query` is unused there too; the tables of the ma probes follow each
-    // other table_dim floats apart, which must be sq_count * 256 (sq_count * 16 for 4-bit codes: what the engine reads).
+    // other table_dim floats apart, which must be sq_count * 256 (sq_count * 65536 for 16-bit, sq_count * 16 for 4-bit codes: what
+    // the engine reads).
     void query_scan(const float* /*query*/, int* assign, int ma, float* tables, int table_dim, BhType& bh, Metrics& /*metrics*/) {
         if (table_dim != table_floats) {
             std::cerr << "query_scan: table_dim " << table_dim << " is not " << table_floats << " (sq_count * centroids)" << std::endl;

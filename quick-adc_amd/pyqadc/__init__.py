@@ -41,7 +41,7 @@ SYMBOLS = [
     "qadc_adc_index_set_pq", "qadc_adc_index_set_rotation", "qadc_adc_index_set_coarse", "qadc_adc_index_set_table_budget",
     "qadc_adc_search", "qadc_adc_search_candidates", "qadc_adc_search_tables", "qadc_adc_encode_host",
     "qadc_adc_index_set_finish", "qadc_adc_index_host_finishes", "qadc_adc_search_device", "qadc_adc_query_scan_device",
-    "qadc_adc_index_create_view",
+    "qadc_adc_index_create_view", "qadc_adc_index_create16",
 ]
 
 
@@ -163,6 +163,7 @@ def lib():
         L.qadc_adc_index_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
         L.qadc_adc_index_destroy.argtypes = [C.c_void_p]
         L.qadc_adc_index_create_view.argtypes = [C.POINTER(C.c_void_p), C.c_void_p]
+        L.qadc_adc_index_create16.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int]
         L.qadc_adc_index_add_partitions.argtypes = [C.c_void_p, C.c_int, C.POINTER(u8p), C.POINTER(u32p), u32p]
         L.qadc_adc_index_partition_count.argtypes = [C.c_void_p]
         L.qadc_adc_index_partition_size.argtypes = [C.c_void_p, C.c_int]
@@ -762,7 +763,10 @@ class Index:
 class AdcIndex:
     """One GPU-resident PQ database with whole-byte codes, scanned with float tables: the role of the reference's
     scanner_simple after prepare_database (db_query.cpp:17-46).  sq_bits 8 with sq_count 4, 8 or 16.
+    AdcIndex.create16(sq_count): 16-bit sub-quantizers, sq_count 2, 4 or 8 (scan_standard<uint16_t, NSQ>).
     AdcIndex.view_of(index): the same front end on the 4-bit codes of an Index, read in place (scan_4<M>)."""
+
+    centroids = 256                                                      # per sub-quantizer (create16: 65536; a view: 16)
 
     def __init__(self, sq_count, sq_bits, device=0):
         self.sq_count = sq_count
@@ -773,12 +777,28 @@ class AdcIndex:
         _check(lib().qadc_adc_index_create(C.byref(self._h), sq_count, sq_bits, device))
 
     @classmethod
+    def create16(cls, sq_count, device=0):
+        """qadc_adc_index_create16: an index of its own over 16-bit codes, sq_count 2, 4 or 8 with 65536 centroids each: codes
+        uint16 [n][sq_count] (or their little-endian bytes, uint8 [n][2*sq_count]), tables [nq][ma][sq_count*65536], codebooks
+        [sq_count][65536][dim/sq_count].  Every method of an AdcIndex works on it."""
+        self = cls.__new__(cls)
+        self.sq_count = sq_count
+        self.centroids = 65536
+        self.table_dim = sq_count * 65536
+        self.device = device
+        self._source = None
+        self._h = C.c_void_p()
+        _check(lib().qadc_adc_index_create16(C.byref(self._h), sq_count, device))
+        return self
+
+    @classmethod
     def view_of(cls, index):
         """qadc_adc_index_create_view: an AdcIndex on the partitions of the finalized pyqadc.Index `index`, on its device, M
         sub-quantizers of 4 bits, tables [nq][ma][M*16].  It copies nothing and keeps `index` referenced;
         index.close() raises until the view is closed.  The search calls run the quantizers set on `index`."""
         self = cls.__new__(cls)
         self.sq_count = index.M
+        self.centroids = 16
         self.table_dim = index.M * 16
         self.device = index.device
         self._source = None
@@ -813,8 +833,20 @@ class AdcIndex:
         except Exception:
             pass
 
+    def _code_rows(self, c):
+        """one partition's codes as the bytes the C call takes: uint8 [n][code bytes]"""
+        if self.centroids != 65536:
+            return np.ascontiguousarray(c, np.uint8).reshape(-1, self.sq_count)
+        c = np.asarray(c)
+        if c.dtype != np.uint8:                                          # uint16 [n][sq_count] -> little-endian bytes
+            if c.dtype.kind not in "ui" or (c.size and (int(c.min()) < 0 or int(c.max()) > 0xffff)):
+                raise QadcError("16-bit codes are uint16 [n][sq_count] or uint8 [n][2*sq_count]")
+            c = np.ascontiguousarray(c.reshape(-1, self.sq_count).astype("<u2")).view(np.uint8)
+        return np.ascontiguousarray(c, np.uint8).reshape(-1, 2 * self.sq_count)
+
     def add_partitions(self, codes, labels=None):
-        codes = [np.ascontiguousarray(c, np.uint8).reshape(-1, self.sq_count) for c in codes]
+        """codes: one array per partition, uint8 [n][sq_count] (a create16 index: uint16 [n][sq_count] or uint8 [n][2*sq_count])"""
+        codes = [self._code_rows(c) for c in codes]
         sizes = np.array([c.shape[0] for c in codes], np.uint32)
         ca = (u8p * len(codes))(*[_p(c, u8p) for c in codes])
         la = None
@@ -851,7 +883,7 @@ class AdcIndex:
         return assign, tables, nq, ma
 
     def query_scan(self, assign, tables, R, sum_mode=1):
-        """assign [nq][ma], tables [nq][ma][table_dim] (sq_count*256; a view: sq_count*16) -> (keys [nq][R], vals [nq][R], sizes [nq]): the heap arrays
+        """assign [nq][ma], tables [nq][ma][table_dim] (sq_count*256; create16: sq_count*65536; a view: sq_count*16) -> (keys [nq][R], vals [nq][R], sizes [nq]): the heap arrays
         of scanner_simple::query_scan per query (rows are valid up to sizes[q])."""
         assign, tables, nq, ma = self._inputs(assign, tables)
         keys = np.zeros((nq, R), np.uint32)
@@ -889,9 +921,9 @@ class AdcIndex:
 
     # ---- from query vectors: the feeders run on the GPU (qadc_adc_search*) ----
     def set_pq(self, codebooks):
-        """codebooks [sq_count][256][dim / sq_count]"""
+        """codebooks [sq_count][256][dim / sq_count] (a create16 index: [sq_count][65536][dim / sq_count])"""
         cb = np.ascontiguousarray(codebooks, np.float32)
-        assert cb.ndim == 3 and cb.shape[0] == self.sq_count and cb.shape[1] == 256
+        assert cb.ndim == 3 and cb.shape[0] == self.sq_count and cb.shape[1] == self.centroids
         self.set_pq_raw(self.sq_count * cb.shape[2], cb)
 
     def set_pq_raw(self, dim, codebooks):
@@ -957,7 +989,7 @@ class AdcIndex:
             cap = int(offsets[-1])
 
     def search_tables(self, queries, ma, table_form=2, sum_mode=1):
-        """The feeders alone -> (assign [nq][ma], tables [nq][ma][sq_count*256])"""
+        """The feeders alone -> (assign [nq][ma], tables [nq][ma][table_dim])"""
         q = self._queries(queries)
         nq = q.shape[0]
         assign = np.zeros((nq, ma), np.int32)
@@ -1002,7 +1034,7 @@ class AdcIndex:
         return keys, vals, sizes
 
     def query_scan_device(self, assign, tables, R, sum_mode=1):
-        """assign [nq][ma] (host), tables: float32 tensor [nq][ma][sq_count*256] on the index's device -> tensors (keys, vals,
+        """assign [nq][ma] (host), tables: float32 tensor [nq][ma][table_dim] on the index's device -> tensors (keys, vals,
         sizes) as search_device: query_scan()'s heap arrays without the upload of the tables."""
         assign = np.ascontiguousarray(assign, np.int32)
         if assign.ndim == 1:

@@ -3,6 +3,7 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
 
   python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
   batch32   32 queries per call on the same list
@@ -28,6 +29,16 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             under the host and the device finish, alternated and asserted equal
   profile   not timed: five one-query calls on 10^8 codes through the 16x4 view, the 32x4 view and the 8x8 engine, in that order —
             the workload of the rocprofv3 kernel-trace and LDS-counter runs (run it under rocprofv3, one kind of collection per run)
+  --bits 16  the engine on 16-bit codes instead (pyqadc.AdcIndex.create16; legs lone,ivf_search), tables read from global memory:
+  lone      one synchronous query on 10^6 and on 10^8 codes at 2x16, 4x16 and 8x16: median and range of the call, codes/s, the share
+            of the HBM roofline at 4 / 8 / 16 B per code, each alternated with the 8-bit engine at the same bytes per code (4x8,
+            8x8, 16x8) on a list of the same n; beside one CPU thread of the host twin's scan_standard<uint16_t, N> over the 10^6
+            list (tests/cpp/scan_standard16_host.cpp: a port, not the reference's build)
+  ivf_search   10^6 random codes in K = 256 partitions, random codebooks (128-d) and coarse centroids, ma = 24, 1024 queries:
+            search() per shape (the tables, 0.5 / 1 / 2 MiB per (query, probe), are built and scanned in passes of the 1 GiB table
+            budget), alternated with the 8-bit engine of the same bytes per code on the same partitions' sizes
+  profile   not timed: five one-query calls on 10^8 codes at 8x16, then two search() calls of 64 queries at the ivf_search shape —
+            the workload of a rocprofv3 --pmc run for the scan kernel's L2 hit rate (TCC_HIT_sum, TCC_MISS_sum)
 Every time is a host clock around whole synchronous calls (median of --iters after warm-up); R = 100, sum_mode 1."""
 import argparse
 import json
@@ -278,19 +289,126 @@ def view_legs(legs, iters, res):
         src.close()
 
 
+def cpu_twin_u16_us(nsq, codes, table, repeat=5):
+    """one thread of the host twin's scan_standard<uint16_t, nsq> (tests/cpp/scan_standard16_host.cpp) on one flat list: median us"""
+    import subprocess
+    import tempfile
+    exe = os.path.join(ROOT, "tests", "cpp", "scan_standard16_host")
+    if not os.path.exists(exe):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", exe + ".cpp", "-o", exe])
+    with tempfile.TemporaryDirectory() as d:
+        fin, fout = os.path.join(d, "in"), os.path.join(d, "out")
+        with open(fin, "wb") as f:
+            np.array([nsq, 1, 0, R, 1], np.int32).tofile(f)
+            np.array([len(codes)], np.uint32).tofile(f)
+            np.ascontiguousarray(codes, "<u2").tofile(f)
+            np.ascontiguousarray(table, np.float32).tofile(f)
+        out = subprocess.run([exe, fin, fout, str(repeat)], stdout=subprocess.PIPE, check=True).stdout.decode().split()
+    return float(out[out.index("us") + 1])
+
+
+def word_legs(legs, iters, res):
+    """--bits 16: the engine on 16-bit codes, beside the 8-bit engine at equal code bytes"""
+    rng = np.random.default_rng(16)
+    zero = np.zeros((1, 1), np.int32)
+
+    def tables16(nq, ma, nsq):
+        return ((rng.random((nq, ma, nsq * 65536), dtype=np.float32) * np.float32(4.0)) ** 2).astype(np.float32)
+
+    if "lone" in legs:
+        for n in (1_000_000, 100_000_000):
+            for nsq in (2, 4, 8):
+                cs = 2 * nsq
+                codes = rng.integers(0, 65536, (n, nsq), dtype=np.uint16)
+                idx = pyqadc.AdcIndex.create16(nsq)
+                idx.add_partitions([codes])
+                adc8 = pyqadc.AdcIndex(cs, 8)
+                adc8.add_partitions([codes.view(np.uint8)])             # the same bytes read as cs one-byte codes
+                tb, tb8 = tables16(1, 1, nsq), tables_for(rng, 1, 1, cs)
+                it = max(iters, 50) if n <= 1_000_000 else iters
+                tag = "adc%dx16_%.0e" % (nsq, n)
+                med_w, med_8 = alternated(lambda: idx.query_scan(zero, tb, R), lambda: adc8.query_scan(zero, tb8, R), it, warmup=3)
+                res[tag + "_alternated_ms"] = med_w * 1e3
+                res["adc%dx8_%.0e_alternated_ms" % (cs, n)] = med_8 * 1e3
+                print("n = %.0e, one query/call, alternated: %dx16 %.3f ms, %dx8 %.3f ms (16-bit / 8-bit = %.3f)"
+                      % (n, nsq, med_w * 1e3, cs, med_8 * 1e3, med_w / med_8), flush=True)
+                adc8.close()
+                med, lo, hi = spread(lambda: idx.query_scan(zero, tb, R), it)
+                res[tag + "_ms_median_min_max"] = [med * 1e3, lo * 1e3, hi * 1e3]
+                res[tag + "_codes_per_s"] = n / med
+                res[tag + "_hbm_roofline_share"] = n * cs / med / HBM_BPS
+                print("%dx16, %.0e codes, one synchronous query (%.1f MiB table uploaded in the call): %.3f ms (%.3f .. %.3f) = %.3g codes/s "
+                      "= %.3f of the HBM roofline at %d B per code"
+                      % (nsq, n, tb.nbytes / 2 ** 20, med * 1e3, lo * 1e3, hi * 1e3, n / med, n * cs / med / HBM_BPS, cs), flush=True)
+                if n == 1_000_000:
+                    us = cpu_twin_u16_us(nsq, codes, tb[0, 0])
+                    res["cpu_host_twin_scan_standard_u16_%d_us" % nsq] = us
+                    print("CPU host twin scan_standard<uint16_t,%d> (a port, -O2), 10^6 codes, 1 thread: %.1f us = %.1fx the GPU call"
+                          % (nsq, us, us / (med * 1e6)), flush=True)
+                idx.close()
+                del codes
+    if "ivf_search" in legs or "profile" in legs:
+        n, dim, K, ma, nq = 1_000_000, 128, 256, 24, 1024
+        part_of = rng.integers(0, K, n)
+        order = np.argsort(part_of, kind="stable")
+        bounds = np.searchsorted(part_of[order], np.arange(K + 1))
+        labels = [order[bounds[k]:bounds[k + 1]].astype(np.uint32) for k in range(K)]
+        coarse = (rng.normal(size=(K, dim)) * 3).astype(np.float32)
+        queries = (coarse[rng.integers(0, K, nq)] + rng.normal(size=(nq, dim))).astype(np.float32)
+
+        def make(nsq, bits):
+            cents = 1 << bits
+            idx = pyqadc.AdcIndex.create16(nsq) if bits == 16 else pyqadc.AdcIndex(nsq, 8)
+            codes = rng.integers(0, cents, (n, nsq), dtype=np.uint16 if bits == 16 else np.uint8)
+            idx.add_partitions([codes[order[bounds[k]:bounds[k + 1]]] for k in range(K)], labels)
+            idx.set_pq(rng.standard_normal((nsq, cents, dim // nsq), dtype=np.float32))
+            idx.set_coarse(coarse)
+            return idx
+
+        if "ivf_search" in legs:
+            for nsq in (2, 4, 8):
+                idx, adc8 = make(nsq, 16), make(2 * nsq, 8)
+                host = lambda: idx.search(queries, ma, R)
+                dev = with_finish(idx, 1, host)
+                assert same_heaps(host(), dev()), "host and device finish disagree"
+                med_w, med_8 = alternated(host, lambda: adc8.search(queries, ma, R), max(3, iters // 2), warmup=1)
+                res["adc%dx16_ivf_search_ms" % nsq] = med_w * 1e3
+                res["adc%dx8_ivf_search_ms" % (2 * nsq)] = med_8 * 1e3
+                res["adc%dx16_ivf_search_table_bytes_per_call" % nsq] = nq * ma * nsq * 65536 * 4
+                print("IVF K=256 ma=24 on 10^6 random codes, search() of 1024 queries: %dx16 %.2f ms = %.1f us/query (%.1f GiB of tables "
+                      "built and scanned in passes); %dx8 %.2f ms = %.1f us/query"
+                      % (nsq, med_w * 1e3, med_w * 1e6 / nq, nq * ma * nsq * 65536 * 4 / 2 ** 30, 2 * nsq, med_8 * 1e3, med_8 * 1e6 / nq),
+                      flush=True)
+                idx.close()
+                adc8.close()
+        if "profile" in legs:
+            idx = make(8, 16)
+            for _ in range(2):
+                idx.search(queries[:64], ma, R)
+            idx.close()
+    if "profile" in legs:
+        n = 100_000_000
+        idx = pyqadc.AdcIndex.create16(8)
+        idx.add_partitions([rng.integers(0, 65536, (n, 8), dtype=np.uint16)])
+        tb = tables16(1, 1, 8)
+        for _ in range(5):
+            idx.query_scan(zero, tb, R)
+        idx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default=None)
-    ap.add_argument("--bits", type=int, default=8, choices=(4, 8))
+    ap.add_argument("--bits", type=int, default=8, choices=(4, 8, 16))
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.legs is None:
         a.legs = "flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search" if a.bits == 8 else "lone,ivf_search"
     legs = a.legs.split(",")
-    if a.bits == 4:
-        res = {"R": R, "sum_mode": 1, "bits": 4, "cpus_allowed": len(os.sched_getaffinity(0))}
-        view_legs(legs, a.iters, res)
+    if a.bits != 8:
+        res = {"R": R, "sum_mode": 1, "bits": a.bits, "cpus_allowed": len(os.sched_getaffinity(0))}
+        (view_legs if a.bits == 4 else word_legs)(legs, a.iters, res)
         line = json.dumps(res)
         print(line)
         if a.out:

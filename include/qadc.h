@@ -528,7 +528,7 @@ int qadc_adc_index_create(qadc_adc_index** out, int sq_count, int sq_bits, int d
  *   the table budget counts sq_count * 256 KiB per (query, probe) (qadc_adc_index_set_table_budget)
  * sum_mode 1 is the grouping of the uint16_t instances as compiled (2: t0 + t1; 4 and 8: as the uint8_t instances), 0 the source
  * order.  The tables are not staged in LDS but read from global memory through the L2.
- * qadc_adc_encode_host has no 16-bit form. */
+ * qadc_adc_encode16_host makes the codes from vectors (qadc_adc_encode_host is the 8-bit encoder). */
 int qadc_adc_index_create16(qadc_adc_index** out, int sq_count, int device_id);
 int qadc_adc_index_destroy(qadc_adc_index* idx);
 
@@ -654,9 +654,25 @@ int qadc_adc_search_tables(qadc_adc_index* idx, int nq, const float* queries, in
  * and the residual; the rotation if not NULL; per sub-quantizer the expansion distances to its 256 centroids and the pick of
  * the capacity-1 heap as compiled (the first smallest distance after the last NaN; 255 if distance 255 is NaN).
  * vectors [n][dim] -> codes [n][sq_count], assign_out [n] (may be NULL; written when K > 0).  sq_count 4, 8 or 16.
- * 8-bit only: there is no GPU encoder for the 16-bit sub-quantizers of qadc_adc_index_create16 (the host twin pq_bytes encodes them). */
+ * 8-bit only: the 16-bit sub-quantizers of qadc_adc_index_create16 have an encoder of their own, qadc_adc_encode16_host. */
 int qadc_adc_encode_host(int sq_count, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
                          const float* vectors, uint64_t n, int sum_mode, int32_t* assign_out, uint8_t* codes, int device_id);
+
+/* The same for 16-bit sub-quantizers: sq_count 2, 4 or 8, codebooks [sq_count][65536][dim / sq_count].  codes [n][sq_count]
+ * little-endian uint16, passed as 2 * sq_count bytes per vector: the rows qadc_adc_index_add_partitions takes on an index of
+ * qadc_adc_index_create16.  The coarse assignment, the residual, the rotation, assign_out and every refusal are those of
+ * qadc_adc_encode_host (all arguments are checked before the device is touched).  Per (vector, sub-quantizer) the 65536
+ * expansion distances — (||v||^2 + ||c||^2) + (-2 v.c), the entry qadc_adc_search_tables returns for table_form 1 under the same
+ * sum_mode — go through find_k_neighbors(k = 1): one capacity-1 heap fed in centroid order over the 256 blocks of BLOCK_NEIGHS,
+ * not reset between blocks, replace test as compiled !(s >= kept).  The code is the first smallest distance among the
+ * centroids after the last NaN distance; 65535 if distance 65535 is NaN.
+ * Block b is taken to be centroids 256 b .. 256 b + 255, as everywhere in this library (coarse assignment with K > 256): the
+ * reference's text advances its neighbour pointer by block_count_neigh floats instead of rows (neighbors.cpp:64).
+ * The call uploads, assigns, rotates and encodes in passes of QADC_ADC_ENCODE16_CHUNK vectors, so its device memory is bounded
+ * by one pass and the codebooks (dim * 256 KiB) whatever n is; no result depends on the pass size. */
+#define QADC_ADC_ENCODE16_CHUNK 262144   /* vectors encoded per pass; bounds the device memory of a call */
+int qadc_adc_encode16_host(int sq_count, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
+                           const float* vectors, uint64_t n, int sum_mode, int32_t* assign_out, uint8_t* codes, int device_id);
 
 #ifdef __cplusplus
 }

@@ -1032,4 +1032,71 @@ int qadc_adc_encode_host(int sq_count, int dim, const float* codebooks, const fl
     return QADC_OK;
 }
 
+int qadc_adc_encode16_host(int sq_count, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
+                           const float* vectors, uint64_t n, int sum_mode, int32_t* assign_out, uint8_t* codes, int device_id) {
+    if ((sq_count != 2 && sq_count != 4 && sq_count != 8) || dim < 1 || dim % sq_count != 0 || dim > kAdcMaxDim || !codebooks ||
+        K < 0 || (K > 0 && !coarse) || (n && (!vectors || !codes)) || (sum_mode != 0 && sum_mode != 1))
+        return fail(QADC_E_ARG, "bad arguments (sq_count 2, 4 or 8; dim a multiple of it, at most " + std::to_string(kAdcMaxDim) +
+                                    "; sum_mode 0 or 1)");
+    DeviceGuard guard;
+    if (int rc = qadc_device_prepare(device_id)) return rc;
+    HIPCHECK(hipSetDevice(device_id));
+    if (!n) return QADC_OK;
+    Scratch mem;
+    const int ds = dim / sq_count;
+    const size_t rows = (size_t)sq_count * 65536;
+    const uint64_t pass = std::min<uint64_t>(QADC_ADC_ENCODE16_CHUNK, n);   // vectors in device memory at a time
+    float *d_cb = nullptr, *d_cbnorm = nullptr, *d_rot = nullptr, *d_coarse = nullptr, *d_v = nullptr, *d_x = nullptr, *d_dist = nullptr;
+    float *d_qnorm = nullptr, *d_cnorm = nullptr;
+    int32_t* d_assign = nullptr;
+    uint16_t* d_codes = nullptr;
+    unsigned long long* d_part = nullptr;
+    HIPCHECK(mem.alloc(&d_cb, rows * ds * 4));
+    HIPCHECK(mem.alloc(&d_cbnorm, rows * 4));
+    HIPCHECK(hipMemcpy(d_cb, codebooks, rows * ds * 4, hipMemcpyHostToDevice));
+    qadc::launch_row_sqnorm(d_cb, (int)rows, ds, sum_mode, d_cbnorm, nullptr);   // once per call, not per pass
+    if (rotation) {
+        HIPCHECK(mem.alloc(&d_rot, (size_t)dim * dim * 4));
+        HIPCHECK(hipMemcpy(d_rot, rotation, (size_t)dim * dim * 4, hipMemcpyHostToDevice));
+    }
+    if (K > 0) {   // [chunk][K] distances | chunk norms | K norms, as qadc_adc_encode_host
+        const uint64_t chunk = std::min<uint64_t>(kCoarseChunk, n);
+        HIPCHECK(mem.alloc(&d_coarse, (size_t)K * dim * 4));
+        HIPCHECK(hipMemcpy(d_coarse, coarse, (size_t)K * dim * 4, hipMemcpyHostToDevice));
+        HIPCHECK(mem.alloc(&d_dist, (chunk * ((uint64_t)K + 1) + K) * 4));
+        HIPCHECK(mem.alloc(&d_assign, pass * 4));
+        d_qnorm = d_dist + chunk * (uint64_t)K;
+        d_cnorm = d_qnorm + chunk;
+        qadc::launch_row_sqnorm(d_coarse, K, dim, sum_mode, d_cnorm, nullptr);
+    }
+    HIPCHECK(mem.alloc(&d_v, pass * dim * 4));
+    if (K > 0 || rotation) HIPCHECK(mem.alloc(&d_x, pass * dim * 4));
+    HIPCHECK(mem.alloc(&d_codes, pass * sq_count * 2));
+    // the partial picks of a pass: the slices of the largest pass and of the last one (a shorter pass is cut finer)
+    const uint64_t last = n % QADC_ADC_ENCODE16_CHUNK ? n % QADC_ADC_ENCODE16_CHUNK : pass;
+    const uint64_t part_entries = std::max(pass * encode16_slices((uint32_t)pass, sq_count, ds), last * encode16_slices((uint32_t)last, sq_count, ds));
+    HIPCHECK(mem.alloc(&d_part, part_entries * sq_count * 8));
+    HIPCHECK(hipGetLastError());
+    for (uint64_t o = 0; o < n; o += QADC_ADC_ENCODE16_CHUNK) {
+        const uint64_t cnt = std::min<uint64_t>(QADC_ADC_ENCODE16_CHUNK, n - o);
+        HIPCHECK(hipMemcpy(d_v, vectors + o * dim, cnt * dim * 4, hipMemcpyHostToDevice));
+        const float* d_enc = d_v;
+        if (K > 0) {   // find_k_neighbors(k = 1) on the coarse centroids
+            for (uint64_t c = 0; c < cnt; c += kCoarseChunk)
+                qadc::launch_coarse_assign(d_v + c * dim, d_coarse, (int)std::min<uint64_t>(kCoarseChunk, cnt - c), K, dim, 1, d_qnorm, d_cnorm,
+                                           sum_mode, d_dist, d_assign + c, nullptr);
+            HIPCHECK(hipGetLastError());
+        }
+        if (K > 0 || rotation) {
+            qadc::launch_residual_rotate(d_v, cnt, dim, d_coarse, d_assign, d_rot, d_x, nullptr);
+            d_enc = d_x;
+        }
+        HIPCHECK(launch_adc_encode16(d_enc, (uint32_t)cnt, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_part, d_codes, nullptr));
+        HIPCHECK(hipDeviceSynchronize());
+        HIPCHECK(hipMemcpy(codes + o * sq_count * 2, d_codes, cnt * sq_count * 2, hipMemcpyDeviceToHost));
+        if (assign_out && K > 0) HIPCHECK(hipMemcpy(assign_out + o, d_assign, cnt * 4, hipMemcpyDeviceToHost));
+    }
+    return QADC_OK;
+}
+
 }  // extern "C"

@@ -13,7 +13,8 @@
 //                      global scratch for streams of any length);
 //   adc_replay_kernel  the device finish: the ordered stream pushed through kv_binheap<unsigned, float>(R) in LDS, one wave per query;
 //   adc_tables_kernel  the float tables of every (query, probe) from query vectors (residual, OPQ rotation, both table forms);
-//   adc_encode_kernel  vectors -> one code byte per sub-quantizer.
+//   adc_encode_kernel  vectors -> one code byte per sub-quantizer;
+//   adc_encode16_kernel  vectors -> one 16-bit code per sub-quantizer of 65536 centroids (and adc_encode16_merge_kernel).
 // The bound rule and why it is exact: DESIGN.md section 11.  Built with -ffp-contract=off and without fast-math (Makefile):
 // every sum rounds like the reference's.
 #include <algorithm>
@@ -646,6 +647,137 @@ __global__ __launch_bounds__(kWG) void adc_encode_kernel(const float* __restrict
     }
 }
 
+// encode_multiple_vectors for 16-bit sub-quantizers: the same capacity-1 heap fed 65536 expansion distances in centroid order
+// (256 blocks of BLOCK_NEIGHS; the heap is not reset between blocks).  The roles of adc_encode_kernel are swapped: a LANE owns
+// vectors, not centroids.  Lane t keeps the sub-vectors of VL vectors of the current sub-quantizer in registers (DS 8 / 16: 4,
+// DS 32 / 64: 2; DS 0 reads its one vector where it lies) and the workgroup sweeps the centroid rows, staged kEnc16Tile at a time in
+// LDS, in ascending index: every lane reads the same row (a broadcast read: ds / 4 ds_read_b128 feed 2 * ds * VL VALU
+// operations per lane), so a loaded row meets V = 256 VL vectors and a sub-quantizer's codebook is read once per V vectors.
+// Because one lane sees all the distances of its vector in heap order, the pick IS the heap: kept starts as NaN (an empty heap
+// takes its first push), and `if (!(s >= kept))` is the replace test as compiled — NaN distances, ties and -0 need no second
+// look.  Pairs of vectors go through float2 arithmetic (v_pk_mul_f32 / v_pk_add_f32: every component rounds as the scalar
+// instruction, unfused under -ffp-contract=off), entry for entry expansion_dist.
+// Grid (x): vector tile fastest, then centroid slice, then sub-quantizer, so that workgroups resident together sweep the
+// same rows.  A small call cuts the 65536 centroids into `slices` runs (launch_adc_encode16) to fill the chip; every
+// (slice, sub-quantizer, vector) leaves its heap's state as distance bits << 32 | saw a NaN << 31 | centroid in `part`
+// [slices][nsq][n], and adc_encode16_merge_kernel continues the heap over the slices.
+// Dynamic LDS: rows [tile][ds] | ||c||^2 [tile].
+typedef float float2v __attribute__((ext_vector_type(2)));
+
+template <int DS>
+__global__ __launch_bounds__(kWG) void adc_encode16_kernel(const float* __restrict__ x, uint32_t n, int nsq, int dim,
+                                                           const float* __restrict__ codebooks, const float* __restrict__ cbnorm,
+                                                           int slices, int tile, int sum_mode, unsigned long long* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) float dyn[];
+    constexpr int VL = encode16_lane_vectors(DS);
+    const int ds = DS ? DS : dim / nsq;
+    const int tid = threadIdx.x;
+    const uint32_t vtiles = (n + kWG * VL - 1) / (kWG * VL);
+    const uint32_t vt = blockIdx.x % vtiles, rest = blockIdx.x / vtiles;
+    const int slice = (int)(rest % (uint32_t)slices), m = (int)(rest / (uint32_t)slices);
+    const int per = 65536 / slices, c_lo = slice * per;
+    float* rows = dyn;
+    float* norms = dyn + (size_t)tile * ds;
+    const float* __restrict__ cb = codebooks + (size_t)m * 65536 * ds;
+
+    // the lane's vectors: vt * 256 VL + j * 256 + tid.  A lane past the end computes on vector n - 1 and writes nothing.
+    uint32_t vi[VL];
+    const float* __restrict__ xp[VL];
+    float vn[VL], kept[VL];
+    uint32_t pick[VL];
+    unsigned long long saw_nan[VL];                           // per wave: the lanes whose vector j met a NaN distance (a scalar OR per centroid)
+    [[maybe_unused]] float xr[VL][DS ? DS : 1];
+#pragma unroll
+    for (int j = 0; j < VL; ++j) {
+        vi[j] = vt * (uint32_t)(kWG * VL) + (uint32_t)(j * kWG + tid);
+        xp[j] = x + (size_t)min(vi[j], n - 1) * dim + (size_t)m * ds;
+        if constexpr (DS != 0) {
+#pragma unroll
+            for (int i = 0; i < DS / 4; ++i) {
+                const float4 t = reinterpret_cast<const float4*>(xp[j])[i];
+                xr[j][4 * i] = t.x; xr[j][4 * i + 1] = t.y; xr[j][4 * i + 2] = t.z; xr[j][4 * i + 3] = t.w;
+            }
+            vn[j] = expansion_sqnorm(xr[j], ds, sum_mode);
+        } else {
+            vn[j] = expansion_sqnorm(xp[j], ds, sum_mode);
+        }
+        kept[j] = __uint_as_float(0x7fc00000u);                   // the empty heap: its first push always enters
+        pick[j] = 0;
+        saw_nan[j] = 0;
+    }
+
+    for (int c0 = c_lo; c0 < c_lo + per; c0 += tile) {
+        __syncthreads();                                          // (the last tile has been read)
+        if constexpr (DS != 0) {
+            const float4* src = reinterpret_cast<const float4*>(cb + (size_t)c0 * ds);
+            for (int i = tid; i < tile * (DS / 4); i += kWG) reinterpret_cast<float4*>(rows)[i] = src[i];
+        } else {
+            for (int i = tid; i < tile * ds; i += kWG) rows[i] = cb[(size_t)c0 * ds + i];
+        }
+        for (int i = tid; i < tile; i += kWG) norms[i] = cbnorm[(size_t)m * 65536 + c0 + i];
+        __syncthreads();
+        for (int c = 0; c < tile; ++c) {
+            const float cn = norms[c];
+            const uint32_t at = (uint32_t)(c0 + c);
+            if constexpr (DS != 0) {
+                CentroidRow<DS> ce;
+                ce.load(rows + c * DS, DS);
+#pragma unroll
+                for (int p = 0; p < VL / 2; ++p) {                // vectors 2p and 2p + 1, one component each
+                    float2v dot = {0.0f, 0.0f};
+#pragma unroll
+                    for (int d = 0; d < DS; ++d) {
+                        const float2v xv = {xr[2 * p][d], xr[2 * p + 1][d]};
+                        dot = dot + xv * ce[d];
+                    }
+                    const float2v base = {vn[2 * p] + cn, vn[2 * p + 1] + cn};
+                    const float2v s = base + (-2.0f * dot);
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const bool enter = !(s[h] >= kept[2 * p + h]);
+                        saw_nan[2 * p + h] |= __ballot(s[h] != s[h]);
+                        pick[2 * p + h] = enter ? at : pick[2 * p + h];
+                        kept[2 * p + h] = enter ? s[h] : kept[2 * p + h];
+                    }
+                }
+            } else {
+                const float s = expansion_dist(xp[0], rows + c * ds, ds, vn[0], cn);
+                saw_nan[0] |= __ballot(s != s);
+                if (!(s >= kept[0])) {
+                    pick[0] = at;
+                    kept[0] = s;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < VL; ++j)
+        if (vi[j] < n)
+            part[((size_t)slice * nsq + m) * n + vi[j]] = ((unsigned long long)__float_as_uint(kept[j]) << 32) | (((saw_nan[j] >> (tid & 63)) & 1) ? 0x80000000u : 0u) | pick[j];
+}
+
+// The heap carried over the slices of one (vector, sub-quantizer): a slice that saw a NaN has forgotten everything before it,
+// a kept NaN is replaced by whatever comes next, and otherwise a later slice's first smallest distance enters only when it is
+// strictly smaller.  One thread per (vector, sub-quantizer); codes [n][nsq] uint16.
+__global__ __launch_bounds__(kWG) void adc_encode16_merge_kernel(const unsigned long long* __restrict__ part, uint32_t n, int nsq,
+                                                                 int slices, uint16_t* __restrict__ codes) {
+    const size_t i = (size_t)blockIdx.x * kWG + threadIdx.x;
+    if (i >= (size_t)n * nsq) return;
+    const uint32_t v = (uint32_t)(i / nsq);
+    const int m = (int)(i % nsq);
+    float kept = __uint_as_float(0x7fc00000u);
+    uint32_t pick = 0;
+    for (int sl = 0; sl < slices; ++sl) {
+        const unsigned long long e = part[((size_t)sl * nsq + m) * n + v];
+        const float s = __uint_as_float((uint32_t)(e >> 32));
+        if (((uint32_t)e & 0x80000000u) || !(s >= kept)) {
+            kept = s;
+            pick = (uint32_t)e & 0xffffu;
+        }
+    }
+    codes[i] = (uint16_t)pick;
+}
+
 }  // namespace
 
 hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const int32_t* assign,
@@ -747,6 +879,42 @@ hipError_t launch_adc_encode(const float* d_x, uint64_t n, int nsq, int dim, con
     else if (ds == 32) QADC_AE(32);
     else QADC_AE(0);
 #undef QADC_AE
+    return hipGetLastError();
+}
+
+int encode16_slices(uint32_t n, int nsq, int ds) {
+    const int lane_vectors = encode16_lane_vectors(encode16_register_row(ds));
+    const uint64_t vtiles = ((uint64_t)n + kWG * lane_vectors - 1) / (kWG * lane_vectors);
+    int slices = 1;
+    while (slices < 65536 / kEnc16MinSlice && vtiles * nsq * slices < 512) slices *= 2;
+    return slices;
+}
+
+hipError_t launch_adc_encode16(const float* d_x, uint32_t n, int nsq, int dim, const float* d_codebooks, const float* d_cbnorm,
+                               int sum_mode, unsigned long long* d_part, uint16_t* d_codes, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (dim <= 0 || dim > kAdcMaxDim || dim % nsq != 0) return hipErrorInvalidValue;
+    const int ds = dim / nsq;
+    const int DS = encode16_register_row(ds);
+    const int lane_vectors = encode16_lane_vectors(DS);
+    const int slices = encode16_slices(n, nsq, ds);
+    // centroid rows per LDS tile: kEnc16Tile, fewer (a power of two) where the rows are long: at most 32 KiB of rows
+    int tile = kEnc16Tile;
+    while (tile > 1 && (size_t)tile * ds * 4 > 32 * 1024) tile /= 2;
+    const size_t lds = (size_t)tile * (ds + 1) * 4;
+    const uint64_t vtiles = ((uint64_t)n + kWG * lane_vectors - 1) / (kWG * lane_vectors);
+    const dim3 grid((unsigned)(vtiles * slices * nsq));
+#define QADC_AE16(D) hipLaunchKernelGGL((adc_encode16_kernel<D>), grid, dim3(kWG), lds, s, d_x, n, nsq, dim, d_codebooks, d_cbnorm, \
+                                        slices, tile, sum_mode, d_part)
+    if (DS == 8) QADC_AE16(8);
+    else if (DS == 16) QADC_AE16(16);
+    else if (DS == 32) QADC_AE16(32);
+    else if (DS == 64) QADC_AE16(64);   // 2x16 at 128 dimensions
+    else QADC_AE16(0);
+#undef QADC_AE16
+    if (hipError_t e = hipGetLastError()) return e;
+    const size_t total = (size_t)n * nsq;
+    hipLaunchKernelGGL(adc_encode16_merge_kernel, dim3((unsigned)((total + kWG - 1) / kWG)), dim3(kWG), 0, s, d_part, n, nsq, slices, d_codes);
     return hipGetLastError();
 }
 

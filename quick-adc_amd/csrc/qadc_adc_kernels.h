@@ -87,5 +87,21 @@ hipError_t launch_adc_tables(const float* d_queries, const float* d_coarse, cons
 hipError_t launch_adc_encode(const float* d_x, uint64_t n, int nsq, int dim, const float* d_codebooks, const float* d_cbnorm,
                              int sum_mode, uint8_t* d_codes, hipStream_t s);
 
+
+// encode_multiple_vectors with 65536 centroids per sub-quantizer (nsq 2, 4 or 8), on vectors already made residuals and rotated.
+// A lane owns `encode16_lane_vectors` vectors and the workgroup sweeps the centroids in ascending order, kEnc16Tile rows at a
+// time through LDS (fewer where the rows are long), so a workgroup encodes 256 * encode16_lane_vectors vectors of one sub-quantizer.  A call too small to fill
+// the chip with whole sweeps cuts the centroids into encode16_slices runs of at least kEnc16MinSlice (a power of two of them):
+// tests/test_gpu_adc16_encode.py places NaN rows on both sides of every multiple of kEnc16MinSlice.
+constexpr int kEnc16Tile = 256;
+constexpr int kEnc16MinSlice = 1024;
+constexpr int encode16_register_row(int ds) { return ds == 8 || ds == 16 || ds == 32 || ds == 64 ? ds : 0; }   // DS of a sq_dim: 0 = any other
+constexpr int encode16_lane_vectors(int DS) { return DS >= 32 ? 2 : DS ? 4 : 1; }
+int encode16_slices(uint32_t n, int nsq, int ds);
+// d_codes [n][nsq] uint16 = the capacity-1 heap's pick as compiled on the expansion distances; d_part: scratch of
+// encode16_slices(n, nsq, dim / nsq) * nsq * n entries.  n < 2^31 / nsq.
+hipError_t launch_adc_encode16(const float* d_x, uint32_t n, int nsq, int dim, const float* d_codebooks, const float* d_cbnorm,
+                               int sum_mode, unsigned long long* d_part, uint16_t* d_codes, hipStream_t s);
+
 }  // namespace adc
 }  // namespace qadc

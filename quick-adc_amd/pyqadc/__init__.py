@@ -41,7 +41,7 @@ SYMBOLS = [
     "qadc_adc_index_set_pq", "qadc_adc_index_set_rotation", "qadc_adc_index_set_coarse", "qadc_adc_index_set_table_budget",
     "qadc_adc_search", "qadc_adc_search_candidates", "qadc_adc_search_tables", "qadc_adc_encode_host",
     "qadc_adc_index_set_finish", "qadc_adc_index_host_finishes", "qadc_adc_search_device", "qadc_adc_query_scan_device",
-    "qadc_adc_index_create_view", "qadc_adc_index_create16",
+    "qadc_adc_index_create_view", "qadc_adc_index_create16", "qadc_adc_encode16_host",
 ]
 
 
@@ -65,6 +65,7 @@ class Profile(C.Structure):
 
 
 QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h
+QADC_ADC_ENCODE16_CHUNK = 262144   # include/qadc.h: vectors qadc_adc_encode16_host encodes per pass
 
 
 class QadcError(RuntimeError):
@@ -179,6 +180,7 @@ def lib():
                                                  u64p, i32p]
         L.qadc_adc_search_tables.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, i32p, f32p]
         L.qadc_adc_encode_host.argtypes = [C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, f32p, C.c_uint64, C.c_int, i32p, u8p, C.c_int]
+        L.qadc_adc_encode16_host.argtypes = L.qadc_adc_encode_host.argtypes
         L.qadc_adc_query_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, u32p, f32p, i32p]
         L.qadc_adc_query_scan_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, C.c_int, C.c_uint64,
                                                      u32p, f32p, u64p]
@@ -394,6 +396,27 @@ def adc_encode(codebooks, vectors, coarse=None, rotation=None, device=0, sum_mod
     _check(lib().qadc_adc_encode_host(nsq, dim, _p(cb, f32p), _p(rot, f32p), K, _p(co, f32p), _p(v, f32p), n, sum_mode, _p(assign, i32p),
                                       _p(codes, u8p), device))
     return assign, codes
+
+
+def adc_encode16(codebooks, vectors, coarse=None, rotation=None, device=0, sum_mode=1):
+    """Database build for 16-bit sub-quantizers on the GPU (qadc_adc_encode16_host): adc_encode with codebooks
+    [sq_count][65536][dsq], sq_count 2, 4 or 8.  vectors [n][dim] -> (assign int32 [n] or None for a flat database, codes uint16
+    [n][sq_count]: viewed as uint8 [n][2 * sq_count] they are the rows add_partitions takes on an AdcIndex of 16-bit codes)."""
+    cb = np.ascontiguousarray(codebooks, np.float32)
+    v = np.ascontiguousarray(vectors, np.float32)
+    assert cb.ndim == 3 and cb.shape[1] == 65536 and v.ndim == 2
+    nsq, dim, n = cb.shape[0], v.shape[1], v.shape[0]
+    assert cb.shape[2] * nsq == dim
+    co = None if coarse is None else np.ascontiguousarray(coarse, np.float32)
+    rot = None if rotation is None else np.ascontiguousarray(rotation, np.float32)
+    assert rot is None or rot.shape == (dim, dim)
+    assert co is None or co.shape[1] == dim
+    K = 0 if co is None else co.shape[0]
+    assign = np.zeros(n, np.int32) if K else None
+    codes = np.zeros((n, nsq), "<u2")
+    _check(lib().qadc_adc_encode16_host(nsq, dim, _p(cb, f32p), _p(rot, f32p), K, _p(co, f32p), _p(v, f32p), n, sum_mode,
+                                        _p(assign, i32p), codes.ctypes.data_as(u8p), device))
+    return assign, codes.astype(np.uint16, copy=False)
 
 
 def pq_encode_device(codebooks, d_vectors_ptr, n, dim, d_codes_ptr, device=0):

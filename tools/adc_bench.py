@@ -3,7 +3,7 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
 
   python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
   batch32   32 queries per call on the same list
@@ -37,6 +37,13 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
   ivf_search   10^6 random codes in K = 256 partitions, random codebooks (128-d) and coarse centroids, ma = 24, 1024 queries:
             search() per shape (the tables, 0.5 / 1 / 2 MiB per (query, probe), are built and scanned in passes of the 1 GiB table
             budget), alternated with the 8-bit engine of the same bytes per code on the same partitions' sizes
+            Then, per shape, the same search() on a database made by adc_encode16: 10^6 clustered 128-d vectors, K = 256 k-means
+            centroids, codebooks = 65536 sampled residuals; with recall@100 of the first 64 queries against exact float L2
+  encode16  adc_encode16 (host to host, flat) of 10^5 and 10^6 clustered 128-d vectors at 2x16, 4x16 and 8x16, codebooks = 65536
+            sampled vectors: seconds per call, vectors/s, the share of the packed-VALU roof (2 n dim 65536 unfused multiplies and
+            adds at 78.6e12 per second: half the 157.3 TFLOPS vector peak, which counts a fused multiply-add as two); beside one
+            CPU thread of the host twin's pq_bytes::encode (tools/encode16_host_twin.cpp: a port, not the reference's build) timed
+            on 256 of the vectors and EXTRAPOLATED to n, its codes asserted equal to the GPU's
   profile   not timed: five one-query calls on 10^8 codes at 8x16, then two search() calls of 64 queries at the ivf_search shape —
             the workload of a rocprofv3 --pmc run for the scan kernel's L2 hit rate (TCC_HIT_sum, TCC_MISS_sum)
 Every time is a host clock around whole synchronous calls (median of --iters after warm-up); R = 100, sum_mode 1."""
@@ -307,6 +314,96 @@ def cpu_twin_u16_us(nsq, codes, table, repeat=5):
     return float(out[out.index("us") + 1])
 
 
+PACKED_VALU_OPS = 78.6e12   # unfused f32 multiplies or adds per second with packed instructions: half the 157.3 TFLOPS vector peak
+
+
+def clustered(rng, n, dim, nq=0):
+    """n (and nq) vectors around 2000 centres"""
+    centers = (rng.normal(size=(2000, dim)) * 3).astype(np.float32)
+    vectors = centers[rng.integers(0, len(centers), n)]
+    vectors += rng.normal(size=(n, dim)).astype(np.float32)
+    queries = (centers[rng.integers(0, len(centers), nq)] + rng.normal(size=(nq, dim))).astype(np.float32)
+    return vectors, queries
+
+
+def cpu_twin_encode16(codebooks, vectors):
+    """one thread of the host twin's pq_bytes::encode (tools/encode16_host_twin.cpp) -> (seconds, codes uint16 [n][nsq])"""
+    import subprocess
+    import tempfile
+    nsq, dim = codebooks.shape[0], vectors.shape[1]
+    with tempfile.TemporaryDirectory() as d:
+        exe, fin, fout = os.path.join(d, "twin"), os.path.join(d, "in"), os.path.join(d, "out")
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", os.path.join(ROOT, "tools", "encode16_host_twin.cpp"), "-o", exe])
+        with open(fin, "wb") as f:
+            np.array([nsq, dim, len(vectors)], np.int32).tofile(f)
+            np.ascontiguousarray(codebooks, np.float32).tofile(f)
+            np.ascontiguousarray(vectors, np.float32).tofile(f)
+        out = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, check=True).stdout.decode().split()
+        codes = np.fromfile(fout, "<u2").reshape(len(vectors), nsq)
+    return float(out[out.index("us") + 1]) * 1e-6, codes
+
+
+def encode16_leg(iters, res):
+    rng = np.random.default_rng(1616)
+    dim, twin_n = 128, 256
+    vectors, _ = clustered(rng, 1_000_000, dim)
+    for nsq in (2, 4, 8):
+        codebooks = np.ascontiguousarray(vectors[rng.choice(len(vectors), 65536, replace=False)].reshape(65536, nsq, dim // nsq)
+                                         .transpose(1, 0, 2))
+        twin_s, twin_codes = cpu_twin_encode16(codebooks, vectors[:twin_n])
+        for n in (100_000, 1_000_000):
+            v = vectors[:n]
+            codes = pyqadc.adc_encode16(codebooks, v)[1]
+            assert np.array_equal(codes[:twin_n], twin_codes), "the GPU's codes differ from the host twin's"
+            med, lo, hi = spread(lambda: pyqadc.adc_encode16(codebooks, v), max(3, iters // 3), warmup=1)
+            roof = 2.0 * n * dim * 65536 / PACKED_VALU_OPS
+            tag = "encode16_%dx16_%.0e" % (nsq, n)
+            res[tag + "_s_median_min_max"] = [med, lo, hi]
+            res[tag + "_vectors_per_s"] = n / med
+            res[tag + "_packed_valu_roof_s"] = roof
+            res[tag + "_share_of_packed_valu_roof"] = roof / med
+            res[tag + "_host_twin_thread_extrapolated_s"] = twin_s * n / twin_n
+            print("adc_encode16 %dx16, %.0e 128-d vectors, host to host: %.3f s (%.3f .. %.3f) = %.3g vectors/s = %.3f of the packed-VALU "
+                  "roof (%.3f s); one CPU thread of the host twin's pq_bytes::encode (a port), %d vectors in %.2f s, EXTRAPOLATED to n: "
+                  "%.0f s = %.0fx the GPU call" % (nsq, n, med, lo, hi, n / med, roof / med, roof, twin_n, twin_s, twin_s * n / twin_n,
+                                                   twin_s * n / twin_n / med), flush=True)
+
+
+def encoded_search_leg(iters, res):
+    """search() at the ivf_search shape on a database adc_encode16 made, with recall against exact float L2"""
+    rng = np.random.default_rng(1617)
+    n, dim, K, ma, nq, nq_exact = 1_000_000, 128, 256, 24, 1024, 64
+    vectors, queries = clustered(rng, n, dim, nq)
+    coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, K, replace=False)], 5)
+    sample = vectors[rng.choice(n, 65536, replace=False)]
+    residual = sample - coarse[pyqadc.coarse_assign(sample, coarse, 1)[:, 0]]
+    vnorm = (vectors.astype(np.float64) ** 2).sum(axis=1)
+    exact = [np.argpartition(vnorm - 2.0 * (vectors @ queries[q]), R)[:R] for q in range(nq_exact)]
+    for nsq in (2, 4, 8):
+        codebooks = np.ascontiguousarray(residual.reshape(65536, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
+        t0 = time.perf_counter()
+        part_of, codes = pyqadc.adc_encode16(codebooks, vectors, coarse)
+        t_enc = time.perf_counter() - t0
+        order = np.argsort(part_of, kind="stable")
+        bounds = np.searchsorted(part_of[order], np.arange(K + 1))
+        idx = pyqadc.AdcIndex.create16(nsq)
+        idx.add_partitions([codes[order[bounds[k]:bounds[k + 1]]] for k in range(K)],
+                           [order[bounds[k]:bounds[k + 1]].astype(np.uint32) for k in range(K)])
+        idx.set_pq(codebooks)
+        idx.set_coarse(coarse)
+        keys, _, sizes, _ = idx.search(queries, ma, R)
+        hits = sum(len(np.intersect1d(exact[q], keys[q, :sizes[q]])) for q in range(nq_exact))
+        med, _ = timed(lambda: idx.search(queries, ma, R), max(3, iters // 2), warmup=1)
+        idx.close()
+        tag = "adc%dx16_encoded" % nsq
+        res[tag + "_ivf_encode_s"] = t_enc
+        res[tag + "_ivf_search_ms"] = med * 1e3
+        res[tag + "_recall_at_100"] = hits / float(nq_exact * R)
+        print("IVF K=256 ma=24 on 10^6 clustered vectors encoded by adc_encode16 at %dx16 (%.2f s, coarse assignment included): search() of "
+              "1024 queries %.2f ms = %.1f us/query; recall@100 against exact float L2 over %d queries: %.3f"
+              % (nsq, t_enc, med * 1e3, med * 1e6 / nq, nq_exact, hits / float(nq_exact * R)), flush=True)
+
+
 def word_legs(legs, iters, res):
     """--bits 16: the engine on 16-bit codes, beside the 8-bit engine at equal code bytes"""
     rng = np.random.default_rng(16)
@@ -381,11 +478,14 @@ def word_legs(legs, iters, res):
                       flush=True)
                 idx.close()
                 adc8.close()
+            encoded_search_leg(iters, res)
         if "profile" in legs:
             idx = make(8, 16)
             for _ in range(2):
                 idx.search(queries[:64], ma, R)
             idx.close()
+    if "encode16" in legs:
+        encode16_leg(iters, res)
     if "profile" in legs:
         n = 100_000_000
         idx = pyqadc.AdcIndex.create16(8)

@@ -471,6 +471,11 @@ typedef struct qadc_profile {
     uint64_t split6_codes;          /* of split_codes: codes those scanned (6 bytes per code, plus one row-major line per survivor) */
     uint64_t split_survivors;       /* (code, query) pairs of the 6-plane launches whose 6-byte partial sum was below the bound,
                                        i.e. whose two deferred bytes were read (counted on the device, with "profile" on only) */
+    uint64_t split5_launches;       /* of split_launches: launches of the 5-plane form (qadc_index_set_split5); a launch is counted
+                                       here or under split6_*, never both */
+    uint64_t split5_codes;          /* of split_codes: codes those scanned (5 bytes per code, plus one row-major line per survivor) */
+    uint64_t split5_survivors;      /* (code, query) pairs of the 5-plane launches whose 5-byte partial sum was below the bound less
+                                       the table's slack, i.e. whose three deferred bytes were read (with "profile" on only) */
 } qadc_profile;
 
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);
@@ -488,6 +493,16 @@ int qadc_index_set_split(qadc_index* idx, uint64_t min_codes, uint64_t min_run);
  * and read, from the row-major codes, for the survivors only.  It needs no memory beyond the copy and changes no result.
  * 0 = never.  May be set at any time; applies to batches submitted afterwards.  Default 2^25: profiles/r08_split6_sweep.txt. */
 int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6);
+
+/* 5-plane form of the split scan: a split launch whose runs all have at least min_run5 codes streams
+ * 5 of the copy's 7 planes and is preferred to the 6-plane form.  Per query table, two of the bytes 0..6 are deferred with
+ * byte 7: the two whose pair-table entries rise least above their minimum.  The sum c of the three deferred pair tables'
+ * minima is known before the scan and is a part of every code's sum, so only codes whose 5-byte partial sum is below
+ * bound - c are survivors; they are finished with all 8 bytes and compared with the bound itself.  No memory beyond the
+ * copy, no result changes.  0 = never.  May be set at any time; applies to batches submitted afterwards.  The
+ * QADC_SPLIT5_MIN_RUN environment variable overrides the default at qadc_index_create.
+ * Default 2^25: profiles/r09_split5_sweep.txt. */
+int qadc_index_set_split5(qadc_index* idx, uint64_t min_run5);
 
 /* ---------------------------------------------------------------------------------------------
  * Float ADC — the reference's OTHER query front end, db_query's plain scanner_simple

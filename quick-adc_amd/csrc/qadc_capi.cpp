@@ -22,13 +22,18 @@ thread_local std::string g_err;
 
 namespace {
 
+// The 5-plane launches' survivor counter (profiling): in the state block's 64-byte header, behind CandHeader (whose pad holds
+// the 6-plane launches' counter); cleared with the block.
+constexpr size_t kSurv5Off = 16;
+static_assert(sizeof(CandHeader) <= kSurv5Off && kSurv5Off + sizeof(unsigned long long) <= 64, "inside the state block's header");
+
 // What the stages of plan_and_launch hand on to each other: the layouts of the batch's upload and result blocks.
 struct Staged {
     bool alone = false;            // nothing else in flight: a synchronous call (see launch_wgq_batch)
     size_t in_bytes = 0, off_tables = 0, off_inj = 0, off_hassign = 0;   // upload block
     size_t state_bytes = 0, off_heaps = 0;
     bool dev_stream = false;       // the ordered streams (also) stay in device memory
-    bool any_split6 = false;
+    bool any_split6 = false, any_split5 = false;
 };
 
 // ---- upload: ONE block, ONE copy (enqueued by plan_and_launch: upload_and_wait) ----
@@ -94,8 +99,12 @@ int bind_state_and_result(qadc_index* idx, Slot& s, Staged& g) {
     HIPCHECK(s.d_cands.ensure((size_t)nq * s.cap_q));
     HIPCHECK(s.d_qtables.ensure((size_t)nq * ma * idx->M * 16));
     // the 6-plane split form's deferred byte per table, computed where the int8 tables become known (launch_front)
-    for (auto& ll : s.launches) g.any_split6 = g.any_split6 || ll.split6;
+    for (auto& ll : s.launches) {
+        g.any_split5 = g.any_split5 || ll.split5;
+        g.any_split6 = g.any_split6 || (ll.split6 && !ll.split5);
+    }
     if (g.any_split6) HIPCHECK(s.d_plane_sel.ensure((size_t)nq * ma));
+    if (g.any_split5) HIPCHECK(s.d_plane_sel5.ensure(2 * (size_t)nq * ma));
     return QADC_OK;
 }
 
@@ -116,7 +125,8 @@ int launch_front(qadc_index* idx, Slot& s, const BatchPlan& plan, const Staged& 
     if (!s.float_path) {
         s.d_qt = s.front_sharded ? s.d_qtables.p                             // (a sharded-front batch redone here: the gathered tables)
                                  : reinterpret_cast<const int8_t*>(s.d_in.p + g.off_tables);     // caller's int8 tables, as uploaded
-        if (g.any_split6) launch_plane_choice(s.d_qt, nq * ma, s.d_plane_sel.p, st);
+        if (g.any_split6 || g.any_split5)
+            launch_plane_choice(s.d_qt, nq * ma, g.any_split6 ? s.d_plane_sel.p : nullptr, st, g.any_split5 ? s.d_plane_sel5.p : nullptr);
         if (idx->profile) { HIPCHECK(prof_event(s, st)); HIPCHECK(prof_event(s, st)); }
         return QADC_OK;
     }
@@ -177,7 +187,8 @@ int launch_front(qadc_index* idx, Slot& s, const BatchPlan& plan, const Staged& 
         launch_prescan_minmax(d_sel, s.inj_n, nq, s.d_qs, st);
     }
     launch_select_kth(d_sel, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 4, d_ft, s.d_qtables.p, tda,
-                      idx->quant_mode, st, nullptr, nullptr, nullptr, 0, g.any_split6 ? s.d_plane_sel.p : nullptr);
+                      idx->quant_mode, st, nullptr, nullptr, nullptr, 0, g.any_split6 ? s.d_plane_sel.p : nullptr,
+                      g.any_split5 ? s.d_plane_sel5.p : nullptr);
     if (idx->profile) HIPCHECK(prof_event(s, st));
     return QADC_OK;
 }
@@ -193,8 +204,12 @@ void launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, 
     else
         launch_scan_i8(idx->M, ll.shared ? (idx->share_variant & ~32) : (variant & ~(64 | 32)) | (ll.split ? 32 : 0), s.d_items + ll.first,
                        ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str,
-                       ll.split6 ? s.d_plane_sel.p : nullptr,
-                       ll.split6 && idx->profile ? reinterpret_cast<unsigned long long*>(s.d_hdr->pad) : nullptr);
+                       ll.split6 && !ll.split5 ? s.d_plane_sel.p : nullptr,
+                       !idx->profile  ? nullptr
+                       : ll.split5    ? reinterpret_cast<unsigned long long*>(s.d_state.p + kSurv5Off)
+                       : ll.split6    ? reinterpret_cast<unsigned long long*>(s.d_hdr->pad)
+                                      : nullptr,
+                       ll.split5 ? s.d_plane_sel5.p : nullptr);
 }
 
 int launch_head(qadc_index* idx, Slot& s, const Staged& g, hipStream_t str) {
@@ -369,7 +384,8 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
     // workgroups of batch s+1 fill the tail of batch s's last level — 125M-code shard 1.10-1.15 -> 1.15-1.35 ms per step, 1B
     // 7.66 -> 7.72-7.76: the next batch's workgroups do not fill a tail, they compete with the current level for CUs)
     const LevelOptions opt{idx->M, idx->level_base, idx->level_growth, idx->head_level, idx->small_run, idx->wgs_per_item,
-                           idx->share_variant, idx->mq, idx->prescan_sample, idx->split_min_run, idx->split6_min_run};
+                           idx->share_variant, idx->mq, idx->prescan_sample, idx->split_min_run, idx->split6_min_run,
+                           idx->split5_min_run};
     const LevelBatch batch{s.nq, s.ma, s.assign.data(), s.R, s.mode, s.float_path, s.full_prescan, s.pre_slice, s.pre_nslices, s.inj_n};
     BatchPlan plan = plan_levels(idx->parts.data(), idx->parts.size(), opt, batch);      // (host/level_plan.hpp: no GPU calls)
     if (!plan.refused.empty()) return fail(QADC_E_ARG, plan.refused);
@@ -698,7 +714,7 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[0], s.prof_ev[1]));
             if (s.float_path) idx->prof.start_ms += ms;
         }
-        bool count_survivors = false;
+        bool count_survivors = false, count_survivors5 = false;
         for (auto& ll : s.launches) {
             if (ll.small || ll.early) {                      // counted, not timed (see plan_and_launch)
                 idx->prof.small_launches++;
@@ -710,9 +726,13 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             idx->prof.mq_launches += ll.mq ? 1 : 0;
             idx->prof.split_launches += ll.split ? 1 : 0;
             idx->prof.split_codes += ll.split ? ll.codes : 0;
-            idx->prof.split6_launches += ll.split6 ? 1 : 0;
-            idx->prof.split6_codes += ll.split6 ? ll.codes : 0;
-            count_survivors = count_survivors || ll.split6;
+            const bool ran6 = ll.split6 && !ll.split5;       // (the launcher prefers 5 planes over 6)
+            idx->prof.split6_launches += ran6 ? 1 : 0;
+            idx->prof.split6_codes += ran6 ? ll.codes : 0;
+            idx->prof.split5_launches += ll.split5 ? 1 : 0;
+            idx->prof.split5_codes += ll.split5 ? ll.codes : 0;
+            count_survivors = count_survivors || ran6;
+            count_survivors5 = count_survivors5 || ll.split5;
             idx->prof.pass_codes += ll.mq ? ll.codes / (uint64_t)ll.nitems * (uint64_t)((ll.nitems + 7) / 8) : ll.codes;
             if (ll.ev < 0 || (size_t)ll.ev + 1 >= s.prof_used) continue;   // not the first launch of its timed group
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[ll.ev], s.prof_ev[ll.ev + 1]));
@@ -722,6 +742,11 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             unsigned long long surv = 0;
             HIPCHECK(hipMemcpy(&surv, s.d_hdr->pad, sizeof(surv), hipMemcpyDeviceToHost));
             idx->prof.split_survivors += surv;
+        }
+        if (count_survivors5) {
+            unsigned long long surv = 0;
+            HIPCHECK(hipMemcpy(&surv, s.d_state.p + kSurv5Off, sizeof(surv), hipMemcpyDeviceToHost));
+            idx->prof.split5_survivors += surv;
         }
         if (s.float_path) idx->prof.start_codes += s.start_codes;
     }
@@ -1169,6 +1194,7 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
         if (const char* e = std::getenv("QADC_SPLIT_MIN_CODES")) idx->split_min_codes = std::strtoull(e, nullptr, 10);
         if (const char* e = std::getenv("QADC_SPLIT_MIN_RUN")) idx->split_min_run = std::strtoull(e, nullptr, 10);
         if (const char* e = std::getenv("QADC_SPLIT6_MIN_RUN")) idx->split6_min_run = std::strtoull(e, nullptr, 10);   // (1: every split launch streams 6 planes)
+        if (const char* e = std::getenv("QADC_SPLIT5_MIN_RUN")) idx->split5_min_run = std::strtoull(e, nullptr, 10);   // (1: ... 5 planes; 0: never)
     }
     if (int rc = attach_streams(idx)) {
         delete idx;
@@ -1208,7 +1234,7 @@ int qadc_index_destroy(qadc_index* idx) {
     for (Slot* sp : all_slots) {
         Slot& s = *sp;
         s.d_in.release(); s.h_in.release(); s.d_state.release(); s.h_result.release();
-        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
+        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_plane_sel5.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
         s.h_cands.release(); s.d_stream.release(); s.d_qflags.release(); s.d_fvals.release(); s.d_qcands.release(); s.h_fetch.release();
         s.d_fblock.release(); s.d_fgathered.release(); s.d_front_all.release(); s.h_fmap.release();
         if (s.ev_fa) (void)hipEventDestroy(s.ev_fa);
@@ -1839,6 +1865,12 @@ int qadc_index_set_split(qadc_index* idx, uint64_t min_codes, uint64_t min_run) 
 int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6) {
     if (!idx) return fail(QADC_E_ARG, "null index");
     idx->split6_min_run = min_run6;
+    return QADC_OK;
+}
+
+int qadc_index_set_split5(qadc_index* idx, uint64_t min_run5) {
+    if (!idx) return fail(QADC_E_ARG, "null index");
+    idx->split5_min_run = min_run5;
     return QADC_OK;
 }
 

@@ -155,6 +155,7 @@ struct Slot {
     DevBuf<float> d_ftables;            // float tables built on the device (qadc_search)
     DevBuf<int8_t> d_qtables;
     DevBuf<uint8_t> d_plane_sel;        // 16x4: the 6-plane split form's deferred byte of every table of the batch (written beside d_qt)
+    DevBuf<uint8_t> d_plane_sel5;       // ... and the 5-plane form's two bytes per table: j1 | j2 << 4, slack (launch_scan_i8)
     DevBuf<Cand> d_cands;
     bool wgq_grouped = false;           // the batch took the partition-major second phase
     bool group_fell_back = false;       // ... and overflowed its candidate regions (redone on the level path): under the multi-GPU merge the
@@ -398,6 +399,9 @@ struct qadc_index {
     // ... and stream 6 of the 7 planes where every run of the launch has at least split6_min_run codes (0 = never;
     // qadc_index_set_split6; profiles/r08_split6_sweep.txt)
     uint64_t split6_min_run = 1ull << 25;
+    // ... and 5 of them, with the slack of the deferred minima in the survivor test, from split5_min_run codes per run
+    // (0 = never; qadc_index_set_split5; profiles/r09_split5_sweep.txt)
+    uint64_t split5_min_run = 1ull << 25;
     // one workgroup per query (IVF batches, small lists): 0 = never, 1 = auto, 2 = whenever structurally possible
     int wgq = 1;
     uint32_t wgq_capacity = 4096;        // stream entries per query to start with

@@ -232,13 +232,18 @@ hipError_t take_launch_error();
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands,
                     uint32_t cap_per_query, uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel = nullptr,
-                    unsigned long long* d_surv = nullptr);
-// Split form only (variant bit 5).  d_plane_sel != nullptr: the 6-plane form, d_plane_sel[table] = the byte (0..6) deferred
-// beside byte 7; nullptr: the 7-plane form.  d_surv (profiling): incremented by the number of survivors, or nullptr.
+                    unsigned long long* d_surv = nullptr, const uint8_t* d_plane_sel5 = nullptr);
+// Split form only (variant bit 5).  d_plane_sel5 != nullptr: the 5-plane form, two bytes per table: j1 | j2 << 4 (the bytes
+// j1 < j2 of 0..6 deferred beside byte 7) and the slack c of its survivor test (min(127, the deferred pair tables' minima
+// summed): a code survives when its 5-byte partial is below bound - c).  Else d_plane_sel != nullptr: the 6-plane form,
+// d_plane_sel[table] = the byte (0..6) deferred beside byte 7; both nullptr: the 7-plane form.
+// d_surv (profiling, 6 and 5 planes): incremented by the number of survivors, or nullptr.
 
-// The deferred byte of every 16x4 int8 table (qtables + t * 256 -> d_plane_sel[t]) for tables the caller brings; tables
-// quantized here get theirs from launch_select_kth (d_plane_sel).
-void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream);
+// The deferred byte of every 16x4 int8 table (qtables + t * 256 -> d_plane_sel[t]) and the 5-plane form's two bytes per
+// table (d_plane_sel5[2 t], [2 t + 1]) for tables the caller brings, either or both; tables quantized here get theirs from
+// launch_select_kth (d_plane_sel, d_plane_sel5).
+void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream,
+                         uint8_t* d_plane_sel5 = nullptr);
 
 // Multi-query streaming scan: groups of up to 8 consecutive runs (all over the same codes, one per query) share
 // ONE pass; wgs_per_group workgroups of 256 threads per group, sibling-major over the groups.
@@ -327,10 +332,11 @@ void launch_select_kth(const float* d_fc, uint64_t fc_stride, const uint32_t* d_
                        QueryState* d_qs, int max_passes, float* d_ftables, int8_t* d_qtables, int table_dim_all,
                        int quant_mode, hipStream_t stream, float* export_vals = nullptr,
                        uint32_t* export_flags = nullptr, uint32_t* d_front_out = nullptr, int small_wg = 0,
-                       uint8_t* d_plane_sel = nullptr);
+                       uint8_t* d_plane_sel = nullptr, uint8_t* d_plane_sel5 = nullptr);
 // d_front_out (optional): {flags & 3, qmin, qmax, 0} per query = the front_in record of scan_query_kernel's HEAD; small_wg:
 // 256-thread workgroups (a batch of many queries beside running scans) instead of 1024.  d_plane_sel (optional, 16x4 with
-// d_qtables): the 6-plane split form's deferred byte of each quantized table, [nq][table_dim_all / 256].
+// d_qtables): the 6-plane split form's deferred byte of each quantized table, [nq][table_dim_all / 256]; d_plane_sel5: the
+// 5-plane form's two bytes per table (launch_scan_i8), [nq][table_dim_all / 256][2].
 
 // Stream-layout probe: a launch of spin_wgs two-per-CU workgroups spinning spin_ticks (100 MHz wall clock) each on stream a, then a
 // one-wave marker on stream b; d_t[0] = first spin workgroup's start (initialise to ~0), [1] = last one's end (0), [2] = marker start.

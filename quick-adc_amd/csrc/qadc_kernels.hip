@@ -57,10 +57,17 @@ static void ensure_dynamic_lds(const void* fn, int bytes, std::atomic<uint64_t>&
 // The byte address x*256 + bank*4 is formed by ONE v_perm_b32 from the code dword and the
 // lane constant; (g&1)*128 + j rides in the ds_read immediate offset.
 // ---------------------------------------------------------------------------------------------
-// 6-plane split form: the code byte whose pair table sits in slot s of the LDS image when byte `defer` (0..6) is deferred:
-// slots 0-5 = the streamed bytes 0..6 without `defer`, in order; slot 6 = `defer`; slot 7 = byte 7.
-__host__ __device__ __forceinline__ uint32_t split6_byte(uint32_t s, uint32_t defer) {
-    return s < 6u ? s + (s >= defer ? 1u : 0u) : (s == 6u ? defer : 7u);
+// 6- and 5-plane split forms: the code byte whose pair table sits in slot s of the LDS image when PLANES of the bytes 0..6
+// are streamed and the others are deferred (6: j1; 5: j1 < j2):
+// slots 0..PLANES-1 = the streamed bytes, in order; then the deferred ones, in order; slot 7 = byte 7.
+template <int PLANES>
+__host__ __device__ __forceinline__ uint32_t split_byte(uint32_t s, uint32_t j1, uint32_t j2 = 7u) {
+    if (PLANES == 6) return s < 6u ? s + (s >= j1 ? 1u : 0u) : (s == 6u ? j1 : 7u);
+    if (s < 5u) {
+        const uint32_t b = s + (s >= j1 ? 1u : 0u);
+        return b + (b >= j2 ? 1u : 0u);
+    }
+    return s == 5u ? j1 : (s == 6u ? j2 : 7u);
 }
 
 template <int M>
@@ -75,9 +82,10 @@ struct ScanCfg {
     static constexpr int LDS_BYTES = BOUND_OFF + 16;
 };
 
-// PERM (6-plane split form): slot s of the image holds the pair table of code byte split6_byte(s, defer) instead of byte s.
-template <int M, bool PERM = false>
-__device__ __forceinline__ void build_pair_tables(const int8_t* __restrict__ qt, uint32_t defer = 0) {
+// PERM = 6 or 5 (those split forms): slot s of the image holds the pair table of code byte split_byte<PERM>(s, defer, defer2)
+// instead of byte s.
+template <int M, int PERM = 0>
+__device__ __forceinline__ void build_pair_tables(const int8_t* __restrict__ qt, uint32_t defer = 0, uint32_t defer2 = 7) {
     using C = ScanCfg<M>;
     const int t = threadIdx.x;
     // stage the int8 table (M*16 bytes) into LDS
@@ -99,7 +107,7 @@ __device__ __forceinline__ void build_pair_tables(const int8_t* __restrict__ qt,
         const uint32_t g = (k >> 2) * 2u + (within & 1u);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t b = PERM ? split6_byte(4u * g + j, defer) : 4u * g + j;
+            const uint32_t b = PERM ? split_byte<PERM ? PERM : 6>(4u * g + j, defer, defer2) : 4u * g + j;
             const uint32_t v = (uint32_t)T[(2 * b) * 16 + (x & 15u)] + (uint32_t)T[(2 * b + 1) * 16 + (x >> 4)];
             w |= v << (8 * j);
         }
@@ -323,7 +331,7 @@ __global__ __launch_bounds__(kWG, (M == 16 ? 8 : 4)) void scan_i8_kernel(
 
 // ---------------------------------------------------------------------------------------------
 // Split form of scan_i8_kernel (16x4, one query per pass): the run is streamed from the partition's byte-plane copy of
-// code bytes 0-6 (kSplitTile, launch_split_copy), PLANES = 7 or 6 of the 8 bytes per code.  Pair-table entries are >= 0, so
+// code bytes 0-6 (kSplitTile, launch_split_copy), PLANES = 7, 6 or 5 of the 8 bytes per code.  Pair-table entries are >= 0, so
 // the sum over any subset of the bytes is a lower bound on the code's value: a code with min(127, partial) >= bound cannot
 // be a candidate and is dropped without its deferred bytes.  A survivor (partial < bound) reads them from the row-major
 // array and is finished exactly as in scan_i8_kernel: cand = min(127, partial + the deferred pair entries), emitted when
@@ -337,8 +345,15 @@ __global__ __launch_bounds__(kWG, (M == 16 ? 8 : 4)) void scan_i8_kernel(
 //     folded into the six uniform plane offsets, so the loop's lookups are those of PLANES = 7 without its last.  Survivors
 //     are some 20 times as frequent as with 7 planes, so they are resolved by a loop over the lane's set
 //     survivor bits (the wave runs as many trips as its busiest lane has survivors, usually one), not by a sweep of 16 slots.
+//   PLANES = 5: the table defers two bytes j1 < j2 of 0..6 (plane_choice5: the two that tighten the partial sum least beyond
+//     their minima) and byte 7; plane_sel holds 2 bytes per table here: j1 | j2 << 4, and the slack c = min(127, the sum of
+//     the three deferred pair tables' minima).  Every code's full sum is >= partial + c, so a code whose 5-byte partial is not
+//     below bound - c cannot be a candidate: the survivor test is min(127, partial) < bsurv = max(bound - c, 0) (0: no code
+//     survives), which brings the survivor rate of 5 planes down to that of the 6-plane form without slack.
+//     A survivor is finished with all three deferred entries and emitted against the real bound.  The 6- and 7-plane forms
+//     keep their test (bound itself).
 // PROBE: XOR of the streamed planes, no deferred bytes (the streaming ceiling of this form; results meaningless).
-// surv (profile option only, else null): counts the survivors of the 6-plane form, one atomicAdd per workgroup at exit (one
+// surv (profile option only, else null): counts the survivors of the 6- or 5-plane form, one atomicAdd per workgroup at exit (one
 // per wave, half a million to one address per launch, cost the headline 3 ms a step; the 7-plane form has no register left
 // for the count and does not report it).
 // ---------------------------------------------------------------------------------------------
@@ -347,15 +362,22 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
     const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
     CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
     const uint8_t* __restrict__ plane_sel, unsigned long long* __restrict__ surv) {
-    static_assert(PLANES == 6 || PLANES == (int)kSplitBytes, "6 or all 7 planes of the copy");
+    static_assert(PLANES >= 5 && PLANES <= (int)kSplitBytes, "5, 6 or all 7 planes of the copy");
     using C = ScanCfg<16>;
     const ScanItem it = items[blockIdx.y];
     QueryState* qs = qstates + it.query;
     out += (uint64_t)it.query * cand_cap;
     uint32_t defer = 6;                                         // PLANES == 6: the deferred byte beside byte 7
-    if (PLANES == 6) {
+    uint32_t defer2 = 7, slack = 0;                             // PLANES == 5: defer < defer2 <= 6, and the deferred minima's sum
+    if (PLANES == 5) {
+        const uint32_t sel = plane_sel[2u * it.table];
+        defer2 = min(max(sel >> 4, 1u), 6u);                    // (whatever the bytes hold, the plane offsets stay inside a tile)
+        defer = min(sel & 15u, defer2 - 1u);
+        slack = min((uint32_t)plane_sel[2u * it.table + 1u], 127u);
+        build_pair_tables<16, 5>(qtables + (uint64_t)it.table * 256, defer, defer2);
+    } else if (PLANES == 6) {
         defer = min((uint32_t)plane_sel[it.table], 6u);
-        build_pair_tables<16, true>(qtables + (uint64_t)it.table * 256, defer);
+        build_pair_tables<16, 6>(qtables + (uint64_t)it.table * 256, defer);
     } else {
         build_pair_tables<16>(qtables + (uint64_t)it.table * 256);
     }
@@ -387,8 +409,11 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
     // vector offset of the plane streamed into slot b (uniform; PLANES == 7: b itself)
     uint32_t poff[PLANES];
 #pragma unroll
-    for (int b = 0; b < PLANES; ++b) poff[b] = (PLANES == 6 ? split6_byte(b, defer) : (uint32_t)b) * (kSplitTile / 16);
-    const uint32_t bound4 = bound * 0x01010101u;
+    for (int b = 0; b < PLANES; ++b)
+        poff[b] = (PLANES == 7 ? (uint32_t)b : split_byte<PLANES == 7 ? 6 : PLANES>(b, defer, defer2)) * (kSplitTile / 16);
+    // a survivor has min(127, partial) < bsurv; 5 planes: the bound less the slack, 0 = no survivor (never wraps)
+    const uint32_t bsurv = PLANES == 5 ? (bound > slack ? bound - slack : 0u) : bound;
+    const uint32_t bound4 = bsurv * 0x01010101u;
 
     // survivors of the previous iteration: byte c of pend = min(127, partial) of the lane's code c, 0xff = none
     uint32_t pend[4] = {~0u, ~0u, ~0u, ~0u};
@@ -401,7 +426,7 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
     uint32_t nsurv = 0;
 
     auto resolve = [&]() __attribute__((always_inline)) {                                      // pend -> res
-        if constexpr (PLANES == 6) {
+        if constexpr (PLANES <= 6) {
             // bit 8 k + w of m = code 4 w + k survives (bit 7 of its byte in pend[w] is clear)
             uint32_t m = ((~pend[0] & 0x80808080u) >> 7) | ((~pend[1] & 0x80808080u) >> 6) | ((~pend[2] & 0x80808080u) >> 5) |
                          ((~pend[3] & 0x80808080u) >> 4);
@@ -412,11 +437,16 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
                 const uint32_t w = i & 3u, sh = i & 24u;
                 const u32x2 x = rows[pend_base + 4u * w + (sh >> 3)];
                 const uint32_t pw = w == 0 ? pend[0] : w == 1 ? pend[1] : w == 2 ? pend[2] : pend[3];
-                const uint32_t xd = (uint32_t)(((((uint64_t)x.y) << 32) | x.x) >> (8u * defer)) & 0xffu;
-                // slot 6 (the deferred byte) and slot 7 (byte 7): dword group 1 (+128), bytes 2 and 3
-                const uint32_t s = ((pw >> sh) & 0xffu) +
-                                   *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((xd << 8) | lane_lo) + 130u)) +
-                                   *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((x.y >> 24 << 8) | lane_lo) + 131u));
+                const uint64_t xw = (((uint64_t)x.y) << 32) | x.x;
+                const uint32_t xd = (uint32_t)(xw >> (8u * defer)) & 0xffu;
+                // the deferred bytes' slots PLANES..6 and slot 7 (byte 7): dword group 1 (+128), bytes 1 (5 planes only), 2 and 3
+                uint32_t s = ((pw >> sh) & 0xffu) +
+                             *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((xd << 8) | lane_lo) + (PLANES == 5 ? 129u : 130u))) +
+                             *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((x.y >> 24 << 8) | lane_lo) + 131u));
+                if constexpr (PLANES == 5) {
+                    const uint32_t xd2 = (uint32_t)(xw >> (8u * defer2)) & 0xffu;
+                    s += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((xd2 << 8) | lane_lo) + 130u));
+                }
                 const uint32_t cv = min(s, 127u);
                 const uint32_t upd = (pw & ~(0xffu << sh)) | ((cv < bound ? cv : 0xffu) << sh);
 #pragma unroll
@@ -496,11 +526,11 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
             }
         }
         any_pend = false;
-        if (__builtin_expect(best < bound, PLANES == 6)) {      // 7 planes: rare; 6: most wave iterations of a long level
+        if (__builtin_expect(best < bsurv, PLANES <= 6)) {      // 7 planes: rare; 6, 5: most wave iterations of a long level
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
-                if constexpr (PLANES == 6) {
-                    // bytes >= bound -> 0xff, four at a time (all bytes and bound are <= 127: no borrow crosses a byte)
+                if constexpr (PLANES <= 6) {
+                    // bytes >= bsurv -> 0xff, four at a time (all bytes and bsurv are <= 127: no borrow crosses a byte)
                     const uint32_t p = cv[4 * w] | (cv[4 * w + 1] << 8) | (cv[4 * w + 2] << 16) | (cv[4 * w + 3] << 24);
                     const uint32_t ge = ((p | 0x80808080u) - bound4) & 0x80808080u;
                     pend[w] = p | ((ge >> 7) * 0xffu);
@@ -529,7 +559,7 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
         resolve();
         if (any_res) emit_res();
     }
-    if (PLANES == 6 && surv) {                                  // (uniform) one global atomic per workgroup: the waves' counts meet in LDS
+    if (PLANES <= 6 && surv) {                                  // (uniform) one global atomic per workgroup: the waves' counts meet in LDS
         uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + C::HIST_OFF);
         __syncthreads();
         if (tid == 0) *cnt = 0;
@@ -555,14 +585,64 @@ __device__ __forceinline__ uint32_t plane_choice(const int8_t* __restrict__ qt) 
     return bj;
 }
 
-__global__ __launch_bounds__(256) void plane_choice_kernel(const int8_t* __restrict__ qtables, int ntables, uint8_t* __restrict__ plane_sel) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < ntables) plane_sel[t] = (uint8_t)plane_choice(qtables + (size_t)t * 256);
+// The two deferred bytes j1 < j2 of the 5-plane split form and its slack, once per int8 table: j1 | j2 << 4 | c << 8.
+// With min P_j = min q[2j] + min q[2j+1] (the smallest entry of pair table j), score_j = the sum of the two rows
+// - 16 min P_j = 1/16 of the sum of P_j[x] - min P_j over the 256 entries: what streaming byte j adds to the partial sum
+// beyond what the slack already accounts for.  The two smallest scores are deferred (ties: the highest j, one pick after the
+// other).  c = min(127, min P_j1 + min P_j2 + min P_7) is a lower bound of the deferred entries' sum for every code; a c
+// above that sum would lose candidates, a poor choice of j only costs survivors.
+__device__ __forceinline__ uint32_t plane_choice5(const int8_t* __restrict__ qt) {
+    const uint8_t* T = reinterpret_cast<const uint8_t*>(qt);
+    uint32_t score[7], minp[8];
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j) {
+        uint32_t sum = 0, m0 = 255u, m1 = 255u;
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t a = T[32 * j + i], b = T[32 * j + 16 + i];
+            sum += a + b;
+            m0 = min(m0, a);
+            m1 = min(m1, b);
+        }
+        minp[j] = m0 + m1;
+        if (j < 7) score[j] = sum - 16u * minp[j];
+    }
+    uint32_t a = 6, b = 6;                                      // first and second pick
+    uint32_t best = 0xffffffffu;
+#pragma unroll
+    for (uint32_t j = 0; j < 7; ++j)
+        if (score[j] <= best) { best = score[j]; a = j; }
+    best = 0xffffffffu;
+#pragma unroll
+    for (uint32_t j = 0; j < 7; ++j)
+        if (j != a && score[j] <= best) { best = score[j]; b = j; }
+    const uint32_t j1 = min(a, b), j2 = max(a, b);
+    uint32_t mj1 = 0, mj2 = 0;                                  // (no dynamic index into minp[]: it stays in registers)
+#pragma unroll
+    for (uint32_t j = 0; j < 7; ++j) {
+        mj1 = j == j1 ? minp[j] : mj1;
+        mj2 = j == j2 ? minp[j] : mj2;
+    }
+    const uint32_t c = min(127u, mj1 + mj2 + minp[7]);
+    return j1 | (j2 << 4) | (c << 8);
 }
 
-void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream) {
-    if (ntables <= 0) return;
-    hipLaunchKernelGGL(plane_choice_kernel, dim3((ntables + 255) / 256), dim3(256), 0, stream, d_qtables, ntables, d_plane_sel);
+// plane_sel (6-plane form, 1 byte per table) and plane_sel5 (5-plane form, 2 bytes per table): either may be null
+__global__ __launch_bounds__(256) void plane_choice_kernel(const int8_t* __restrict__ qtables, int ntables, uint8_t* __restrict__ plane_sel,
+                                                           uint8_t* __restrict__ plane_sel5) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= ntables) return;
+    if (plane_sel) plane_sel[t] = (uint8_t)plane_choice(qtables + (size_t)t * 256);
+    if (plane_sel5) {
+        const uint32_t c5 = plane_choice5(qtables + (size_t)t * 256);
+        plane_sel5[2 * (size_t)t] = (uint8_t)(c5 & 0xffu);
+        plane_sel5[2 * (size_t)t + 1] = (uint8_t)(c5 >> 8);
+    }
+}
+
+void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream, uint8_t* d_plane_sel5) {
+    if (ntables <= 0 || (!d_plane_sel && !d_plane_sel5)) return;
+    hipLaunchKernelGGL(plane_choice_kernel, dim3((ntables + 255) / 256), dim3(256), 0, stream, d_qtables, ntables, d_plane_sel,
+                       d_plane_sel5);
 }
 
 // The byte-plane copy of a partition (kSplitTile layout): one thread per 16 codes of a tile, plane b's 16 bytes = byte b
@@ -1215,12 +1295,14 @@ static void launch_split_variant(dim3 grid, hipStream_t stream, const ScanItem* 
 }
 
 // variant bits: [2] NT (non-temporal loads)  [3] CHUNK  [4] PROBE (ceiling diagnostic)
-// [5] split form (16x4, every run of the launch has ScanItem::split; not with [6]): 6 planes when d_plane_sel (the deferred
-//     byte of every table, launch_plane_choice / launch_select_kth) is given, else 7; d_surv: survivor counter or nullptr
+// [5] split form (16x4, every run of the launch has ScanItem::split; not with [6]): 5 planes when d_plane_sel5 (the two
+//     deferred bytes and the slack of every table) is given, else 6 planes when d_plane_sel (the deferred byte of every
+//     table) is, else 7 (launch_plane_choice / launch_select_kth write both); d_surv: survivor counter or nullptr
 // [6] sibling-major 1-D launch (every run of the launch covers the same codes; see the kernel's decode).  Other bits: ignored.
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap,
-                    uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel, unsigned long long* d_surv) {
+                    uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel, unsigned long long* d_surv,
+                    const uint8_t* d_plane_sel5) {
     if (M == 16 && (variant & 32) && !(variant & 64)) {
         const dim3 grid(wgs_per_item, nitems);
 #define QADC_SPLIT_ARGS grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, d_plane_sel, d_surv
@@ -1231,7 +1313,10 @@ void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int
         case 2: launch_split_variant<PL, false, true, PR>(QADC_SPLIT_ARGS); break;  \
         default: launch_split_variant<PL, true, true, PR>(QADC_SPLIT_ARGS); break;  \
     }
-        if (d_plane_sel) {
+        if (d_plane_sel5) {
+            d_plane_sel = d_plane_sel5;                          // (the kernel's one selection argument)
+            if (variant & 16) { QADC_SPLIT(5, true) } else { QADC_SPLIT(5, false) }
+        } else if (d_plane_sel) {
             if (variant & 16) { QADC_SPLIT(6, true) } else { QADC_SPLIT(6, false) }
         } else {
             if (variant & 16) { QADC_SPLIT(7, true) } else { QADC_SPLIT(7, false) }
@@ -2019,7 +2104,8 @@ void launch_start_scan_f32(int M, int sum_mode, const StartItem* d_items, int ni
 // evaluation of the same expressions.
 template <int BT>
 __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t* __restrict__ qt, QueryState* qs,
-                               float qmax, int quant_mode, float* red /* [BT] LDS */, uint8_t* __restrict__ plane_sel) {
+                               float qmax, int quant_mode, float* red /* [BT] LDS */, uint8_t* __restrict__ plane_sel,
+                               uint8_t* __restrict__ plane_sel5) {
     const int t = threadIdx.x;
     float m = FLT_MAX;
     for (int i = t; i < table_dim_all; i += BT) m = fminf(m, tb[i]);
@@ -2044,9 +2130,16 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
         else o = (int8_t)(int)(quant_mode == 0 ? (v - qmin) / delta : (v - qmin) * scale);
         qt[i] = o;
     }
-    if (plane_sel) {                                       // 16x4: the 6-plane split form's deferred byte of each table
+    if (plane_sel || plane_sel5) {                         // 16x4: the 6- and 5-plane split forms' deferred bytes of each table
         __syncthreads();
-        for (int i = t; i < table_dim_all / 256; i += BT) plane_sel[i] = (uint8_t)plane_choice(qt + (size_t)i * 256);
+        for (int i = t; i < table_dim_all / 256; i += BT) {
+            if (plane_sel) plane_sel[i] = (uint8_t)plane_choice(qt + (size_t)i * 256);
+            if (plane_sel5) {
+                const uint32_t c5 = plane_choice5(qt + (size_t)i * 256);
+                plane_sel5[2 * i] = (uint8_t)(c5 & 0xffu);
+                plane_sel5[2 * i + 1] = (uint8_t)(c5 >> 8);
+            }
+        }
     }
     if (t == 0) { qs->qmin = qmin; qs->flags |= flags; }   // keeps bit3 set by the pre-scan
 }
@@ -2062,7 +2155,7 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
                                                         int table_dim_all, int quant_mode,
                                                         float* __restrict__ export_vals,
                                                         uint32_t* __restrict__ export_flags, uint32_t* __restrict__ front_out,
-                                                        uint8_t* __restrict__ plane_sel) {
+                                                        uint8_t* __restrict__ plane_sel, uint8_t* __restrict__ plane_sel5) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t s_prefix, s_k, s_hi, s_cnt;
     __shared__ float red[BT];
@@ -2086,7 +2179,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
         }
         if (tid == 0) qs->qmax = FLT_MAX;
         if (qtables) quantize_query<BT>(table_dim_all, ftables + (uint64_t)q * table_dim_all, qtables + (uint64_t)q * table_dim_all,
-                                        qs, FLT_MAX, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr);
+                                        qs, FLT_MAX, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr,
+                                        plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr);
         publish_front();
         return;
     }
@@ -2155,7 +2249,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
         for (uint32_t i = s_cnt + tid; i < R; i += BT) export_vals[(uint64_t)q * R + i] = qmax;
     }
     if (qtables) quantize_query<BT>(table_dim_all, ftables + (uint64_t)q * table_dim_all, qtables + (uint64_t)q * table_dim_all,
-                                    qs, qmax, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr);
+                                    qs, qmax, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr,
+                                        plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr);
     publish_front();
 }
 
@@ -2192,13 +2287,15 @@ void launch_prescan_minmax(const float* d_vals, uint32_t nvals, int nq, QuerySta
 void launch_select_kth(const float* d_fc, uint64_t fc_stride, const uint32_t* d_fc_init, int nq, uint32_t R, QueryState* d_qs,
                        int max_passes, float* d_ftables, int8_t* d_qtables, int table_dim_all, int quant_mode,
                        hipStream_t stream, float* export_vals, uint32_t* export_flags, uint32_t* d_front_out, int small_wg,
-                       uint8_t* d_plane_sel) {
+                       uint8_t* d_plane_sel, uint8_t* d_plane_sel5) {
     if (small_wg)
         hipLaunchKernelGGL((select_kth_kernel<256>), dim3(nq), dim3(256), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
-                           d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel);
+                           d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel,
+                           d_plane_sel5);
     else
         hipLaunchKernelGGL((select_kth_kernel<1024>), dim3(nq), dim3(1024), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
-                           d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel);
+                           d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel,
+                           d_plane_sel5);
 }
 
 // ---- stream-layout probe (qadc_stream_probe): does a dispatch that WAITS FOR CUs on stream A hold up stream B? ----

@@ -71,6 +71,7 @@ struct LevelLaunch {
     uint64_t maxn;  // longest run of the launch
     bool early;     // launched on the front stream, under the previous batch's long levels: counted, not event-timed
     int ev = -1;    // index of the HIP event recorded before the launch (the next one follows it), -1 = not timed
+    bool split5 = false;   // split, and every run has at least split5_min_run codes: the 5-plane form (the launcher prefers 5 over 6 over 7)
 };
 
 // What the planner reads of a partition (the index's Part derives from it: one partition table, no copy).
@@ -95,6 +96,7 @@ struct LevelOptions {
     int wgs_per_item, share_variant, mq;
     uint32_t prescan_sample;
     uint64_t split_min_run, split6_min_run;
+    uint64_t split5_min_run = 0;   // 0 = never the 5-plane form
 };
 struct LevelBatch {
     int nq, ma;
@@ -329,6 +331,7 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
             ll.mq = ll.shared && o.mq;
             ll.split = cls == 2 && !ll.shared;
             ll.split6 = ll.split && o.split6_min_run != 0 && minn >= o.split6_min_run;
+            ll.split5 = ll.split && o.split5_min_run != 0 && minn >= o.split5_min_run;
             ll.wgs = ll.mq       ? wgs_mq(o, maxn, nvec, cnt)
                      : ll.shared ? wgs_shared(o, maxn, nvec)
                      : ll.small  ? wgs_small(nvec, cnt)

@@ -32,7 +32,7 @@ SYMBOLS = [
     "qadc_scan_i8_candidates", "qadc_scan_start", "qadc_query_scan_submit", "qadc_prescan_submit",
     "qadc_prescan_collect", "qadc_query_scan_submit_prescanned",
     "qadc_query_scan_collect", "qadc_index_set_pq", "qadc_index_set_rotation", "qadc_index_set_coarse", "qadc_search", "qadc_search_submit",
-    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6",
+    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6", "qadc_index_set_split5",
     "qadc_dist_unique_id", "qadc_dist_init", "qadc_dist_collect", "qadc_dist_shutdown", "qadc_dist_merge_blocks", "qadc_dist_merge_blocks_host",
     "qadc_dist_init_transport", "qadc_dist_init_loopback", "qadc_shm_transport_open", "qadc_shm_transport_allgather", "qadc_shm_transport_allgather_host",
     "qadc_shm_transport_close", "qadc_shm_transport_error", "qadc_slot_assign", "qadc_slot_qtables", "qadc_place_partitions",
@@ -61,7 +61,8 @@ class Profile(C.Structure):
                 ("front_sharded_batches", C.c_uint64), ("dist_async_collects", C.c_uint64),
                 ("lone_front_launches", C.c_uint64), ("split_launches", C.c_uint64), ("split_codes", C.c_uint64),
                 ("split_copy_bytes", C.c_uint64), ("split_copy_failed", C.c_uint64),
-                ("split6_launches", C.c_uint64), ("split6_codes", C.c_uint64), ("split_survivors", C.c_uint64)]
+                ("split6_launches", C.c_uint64), ("split6_codes", C.c_uint64), ("split_survivors", C.c_uint64),
+                ("split5_launches", C.c_uint64), ("split5_codes", C.c_uint64), ("split5_survivors", C.c_uint64)]
 
 
 QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h
@@ -106,6 +107,7 @@ def lib():
         L.qadc_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
         L.qadc_index_set_split.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
         L.qadc_index_set_split6.argtypes = [C.c_void_p, C.c_uint64]
+        L.qadc_index_set_split5.argtypes = [C.c_void_p, C.c_uint64]
         L.qadc_index_read_codes.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u8p]
         L.qadc_query_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, u32p, i8p, i32p, i32p,
                                       f32p, f32p, i8p]
@@ -499,6 +501,11 @@ class Index:
     def set_split6(self, min_run6):
         """Split launches whose runs all have >= min_run6 codes stream 6 of the 7 planes (0 = never); results do not change."""
         _check(lib().qadc_index_set_split6(self._h, int(min_run6)))
+
+    def set_split5(self, min_run5):
+        """Split launches whose runs all have >= min_run5 codes stream 5 of the 7 planes, preferred to the 6-plane form
+        (0 = never); results do not change."""
+        _check(lib().qadc_index_set_split5(self._h, int(min_run5)))
 
     def partition_count(self):
         return lib().qadc_index_partition_count(self._h)

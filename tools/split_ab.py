@@ -1,15 +1,18 @@
-"""Same-process A/B of the split scan and the sweeps behind its three thresholds.
+"""Same-process A/B of the split scan and the sweeps behind its four thresholds.
 usage: python tools/split_ab.py [reps] [part]   (default 3 rounds, all parts; arms interleaved inside every round;
-                                                 part = min_run | min_codes | split6: that part only)
+                                                 part = min_run | min_codes | split6 | split5: that part only)
 
 Part 1, split_min_run: the headline's list and mode (10^9 codes, bench.py's one-query-per-pass options, 32-query steps
 pipelined three deep as bench.py's run_steps), ONE index with its byte-plane copy; arms: split off (row-major scan) and
 split_min_run = 2, 8, 32, 128 Mi.  Part 2, split_min_codes: lists of 1.6 x 10^7 codes (inside the 256 MiB Infinity Cache) and
 4 x 10^7 codes (above it), copy built, arms split off / on at split_min_run = 2^23.  Part 3, split6_min_run: the headline's
 list again at the default split_min_run, arms: 6-plane form off (7 planes everywhere) and split6_min_run = 8, 32, 128, 512 Mi,
-i.e. from the level that starts at 2^23, 2^25, 2^27, 2^29 codes on.
-Prints one JSON line per (part, list, round, arm): ms per step over K steps and the library's split_codes, split6_codes and
-split_survivors per step."""
+i.e. from the level that starts at 2^23, 2^25, 2^27, 2^29 codes on.  Part 4, split5_min_run: the headline's list at the default
+split_min_run and split6_min_run, arms: 5-plane form off and split5_min_run = 8 (for information), 32, 128, 400 Mi, i.e. from
+the level that starts at 2^23, 2^25, 2^27, 2^29 codes on (the last level of 10^9 codes has 441.7 Mi codes: 512 Mi would be "off").
+Parts 1 to 3 keep the 5-plane form off.
+Prints one JSON line per (part, list, round, arm): ms per step over K steps and the library's split_codes, split6_codes,
+split_survivors, split5_codes and split5_survivors per step."""
 import json
 import os
 import sys
@@ -49,23 +52,27 @@ def main():
         while pending:
             idx.collect(pending.pop(0))
 
-    def measure(idx, min_codes, min_run, min_run6):
+    def measure(idx, min_codes, min_run, min_run6, min_run5):
         idx.set_split(min_codes, min_run)
         idx.set_split6(min_run6)
+        idx.set_split5(min_run5)
         run(idx, warmup)
         idx.profile_reset()
         t0 = time.perf_counter()
         run(idx, steps)
         ms = (time.perf_counter() - t0) * 1e3 / steps
         pr = idx.profile()
-        return ms, pr["split_codes"] // steps, pr["split6_codes"] // steps, pr["split_survivors"] // steps
+        return (ms, pr["split_codes"] // steps, pr["split6_codes"] // steps, pr["split_survivors"] // steps,
+                pr["split5_codes"] // steps, pr["split5_survivors"] // steps)
 
-    # arms: (name, split_min_run, split6_min_run); parts 1 and 2 keep the 6-plane form off
+    # arms: (name, split_min_run, split6_min_run[, split5_min_run = 0]); parts 1 and 2 keep the 6-plane form off
     plan = [("min_run", int(1e9), [("off", OFF, 0), ("2Mi", 2 * MI, 0), ("8Mi", 8 * MI, 0), ("32Mi", 32 * MI, 0), ("128Mi", 128 * MI, 0)]),
             ("min_codes", int(1.6e7), [("off", OFF, 0), ("on", 8 * MI, 0)]),
             ("min_codes", int(4e7), [("off", OFF, 0), ("on", 8 * MI, 0)]),
             ("split6", int(1e9), [("off", 8 * MI, 0), ("8Mi", 8 * MI, 8 * MI), ("32Mi", 8 * MI, 32 * MI), ("128Mi", 8 * MI, 128 * MI),
-                                  ("512Mi", 8 * MI, 512 * MI)])]
+                                  ("512Mi", 8 * MI, 512 * MI)]),
+            ("split5", int(1e9), [("off", 8 * MI, 32 * MI, 0), ("8Mi", 8 * MI, 32 * MI, 8 * MI), ("32Mi", 8 * MI, 32 * MI, 32 * MI),
+                                  ("128Mi", 8 * MI, 32 * MI, 128 * MI), ("400Mi", 8 * MI, 32 * MI, 400 * MI)])]
     only = sys.argv[2] if len(sys.argv) > 2 else None
     for part, n, arms in plan:
         if only and part != only:
@@ -79,11 +86,12 @@ def main():
         copy_bytes = idx.profile()["split_copy_bytes"]
         for rep in range(reps):
             order = arms if rep % 2 == 0 else arms[::-1]       # alternate the order: no arm always follows the same one
-            for name, min_run, min_run6 in order:
-                ms, sc, sc6, surv = measure(idx, 1, min_run, min_run6)
+            for name, min_run, min_run6, *rest in order:
+                ms, sc, sc6, surv, sc5, surv5 = measure(idx, 1, min_run, min_run6, rest[0] if rest else 0)
                 print(json.dumps({"part": part, "codes": n, "round": rep, "arm": name, "ms_per_step": round(ms, 4),
                                   "codes_per_s": round(n * nq / ms * 1e3, 1), "split_codes_per_step": int(sc),
                                   "split6_codes_per_step": int(sc6), "split_survivors_per_step": int(surv),
+                                  "split5_codes_per_step": int(sc5), "split5_survivors_per_step": int(surv5),
                                   "copy_bytes": int(copy_bytes)}), flush=True)
         idx.close()
 

@@ -10,7 +10,13 @@ survivor rate of a set of streamed bytes is P(min(127, partial) < bound).  Print
 the queries for 7 bytes (0-6), 6 fixed bytes (0-5), 6 bytes chosen by the library's rule (drop byte 7 and the byte of 0-6 whose
 pair entries have the smallest sum; ties: the highest) and the best single deferred byte, the two ratios rule / fixed and
 rule / best, and bytes per (code, query) = k + rate x G for G = 64 and 128 B per survivor, weighted over the levels.
-Compare the rates with the library's split_survivors / split6_codes (qadc_profile, tools/split_ab.py part split6).
+The slack columns use the survivor test of the 5-plane form: every deferred byte b contributes at least min P_b, so with
+c = min(127, the sum of min P_b over the deferred bytes) a code survives when min(127, partial) < bound - c.  "6 slack" is the
+6-plane rule's choice with that test (a what-if: the library's 6-plane form tests against the bound itself), "5 slack" the
+5-plane form as the library runs it (choose_planes5: byte 7 and the two bytes of 0-6 with the smallest
+score_j = sum of the two rows - 16 min P_j, ties: the highest j), "5 plain" the same bytes without the slack.
+Compare the rates with the library's split_survivors / split6_codes and split5_survivors / split5_codes (qadc_profile,
+tools/split_ab.py parts split6 and split5).
 One JSON line at the end."""
 import json
 import os
@@ -47,6 +53,25 @@ def choose_plane(qt):
     return int(max(j for j in range(7) if sums[j] == sums.min()))
 
 
+def choose_planes5(qt):
+    """The library's rule for the 5-plane form -> (j1, j2, c): the two bytes of 0..6 with the smallest
+    score_j = sum of rows 2j and 2j+1 - 16 (min row 2j + min row 2j+1), one pick after the other, ties: the highest j;
+    c = min(127, min P_j1 + min P_j2 + min P_7)."""
+    t = qt.reshape(M, 16).astype(np.int64)
+    minp = [int(t[2 * j].min() + t[2 * j + 1].min()) for j in range(8)]
+    score = [int(t[2 * j].sum() + t[2 * j + 1].sum()) - 16 * minp[j] for j in range(7)]
+    a = max(j for j in range(7) if score[j] == min(score))
+    rest = [j for j in range(7) if j != a]
+    b = max(j for j in rest if score[j] == min(score[r] for r in rest))
+    j1, j2 = min(a, b), max(a, b)
+    return j1, j2, min(127, minp[j1] + minp[j2] + minp[7])
+
+
+def slack(qt, deferred):
+    """min(127, the sum over the deferred bytes of their pair table's smallest entry): a part of every code's sum."""
+    return int(min(127, pair_entries(qt)[list(deferred)].min(axis=1).sum()))
+
+
 def sum_distribution(qt, planes):
     """P(sum over the bytes in `planes` = v) for v = 0 .. 254 * len(planes), codes iid uniform."""
     pe = pair_entries(qt)
@@ -64,8 +89,9 @@ def bound_at(qt, n_before, r=R):
     return int(hit[0]) if len(hit) else 127
 
 
-def survivor_rate(qt, planes, bound):
-    """P(min(127, partial sum over `planes`) < bound)."""
+def survivor_rate(qt, planes, bound, c=0):
+    """P(min(127, partial sum over `planes`) < bound - c); c = the slack of the deferred bytes (0: the plain test)."""
+    bound = max(bound - c, 0)
     return float(sum_distribution(qt, planes)[:min(bound, 127)].sum()) if bound > 0 else 0.0
 
 
@@ -104,7 +130,7 @@ def main():
         s = float_sums(tables[q], codes)
         qts.append(quantize(tables[q], np.partition(s, k - 1)[k - 1]))
     levels = [(a, min(b, n) - a) for a, b in zip(LEVEL_STARTS, LEVEL_STARTS[1:] + [1 << 62]) if a < n]
-    forms = ("7 bytes", "6 fixed", "6 rule", "6 best")
+    forms = ("7 bytes", "6 fixed", "6 rule", "6 best", "6 slack", "5 slack", "5 plain")
     out = {"codes": n, "queries": nq, "seed": seed, "levels": []}
     print("%-10s %-12s " % ("level", "codes") + " ".join("%-22s" % f for f in forms) + " rule/fixed  rule/best")
     for start, size in levels:
@@ -116,6 +142,13 @@ def main():
             rates["6 fixed"].append(per_j[6])
             rates["6 rule"].append(per_j[choose_plane(qt)])
             rates["6 best"].append(min(per_j))
+            j = choose_plane(qt)
+            rates["6 slack"].append(survivor_rate(qt, streamed(j), bound, slack(qt, (j, 7))))
+            j1, j2, c = choose_planes5(qt)
+            five = [b for b in range(7) if b not in (j1, j2)]
+            assert c == slack(qt, (j1, j2, 7))
+            rates["5 slack"].append(survivor_rate(qt, five, bound, c))
+            rates["5 plain"].append(survivor_rate(qt, five, bound))
         mean = {f: float(np.mean(v)) for f, v in rates.items()}
         print("2^%-8d %-12d " % (start.bit_length() - 1, size) +
               " ".join("%-22s" % ("%.2e (max %.1e)" % (mean[f], max(rates[f]))) for f in forms) +
@@ -123,7 +156,7 @@ def main():
         out["levels"].append({"start": start, "codes": size, "mean_rate": mean, "max_rate": {f: max(v) for f, v in rates.items()}})
     total = sum(size for _, size in levels)
     out["bytes_per_code"] = {}
-    for f, kbytes in zip(forms, (7, 6, 6, 6)):
+    for f, kbytes in zip(forms, (7, 6, 6, 6, 6, 5, 5)):
         p = sum(l["mean_rate"][f] * l["codes"] for l in out["levels"]) / total
         out["bytes_per_code"][f] = {"rate": p, "G64": kbytes + p * 64, "G128": kbytes + p * 128}
         print("%-8s weighted rate %.2e   bytes per (code, query): %.3f (G = 64 B)  %.3f (G = 128 B)" % (f, p, kbytes + p * 64, kbytes + p * 128))

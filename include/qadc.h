@@ -689,6 +689,44 @@ int qadc_adc_encode_host(int sq_count, int dim, const float* codebooks, const fl
 int qadc_adc_encode16_host(int sq_count, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
                            const float* vectors, uint64_t n, int sum_mode, int32_t* assign_out, uint8_t* codes, int device_id);
 
+/* ---- db_add: vectors in, index grown, on the GPU.  The quantizers are those the index holds at the
+ * call (qadc_adc_index_set_pq, _set_rotation, _set_coarse); an index of qadc_adc_index_create or _create16, never a view. ---- */
+
+/* index_db::add_vectors (databases.hpp:270-298) on an index with a coarse quantizer (K > 0), flat_db::add_vectors (136-156) on
+ * one without.  vectors [count][dim], host memory.
+ *   K > 0: per vector find_k_neighbors(k = 1) on the coarse centroids, the residual, the rotation if one is set, the code —
+ *     the steps and kernels of qadc_adc_encode_host / qadc_adc_encode16_host under the same sum_mode.  The code of vector i is
+ *     appended to partition assign[i] with label labels_offset + i; within a partition the new rows stand in input order, after
+ *     the rows already there.  The index holds 0 partitions (K empty ones are created) or exactly K, and is labelled or still
+ *     undecided.
+ *   K = 0: one partition, created if absent.  The code of vector i is written at row labels_offset + i; the partition's size
+ *     becomes max(size, labels_offset + count), also for count 0; rows of a gap are zero bytes (std::vector::resize); rows that
+ *     exist are overwritten.  The partition is unlabelled.
+ * QADC_E_ARG, the message says which: a view; no set_pq yet; sum_mode not 0 or 1; vectors NULL with count > 0; labels_offset +
+ * count above 2^32 - 1; a partition that would pass 2^32 - 1 codes; a partition count that is neither 0 nor K (flat: more than
+ * one); unlabelled non-empty partitions with K > 0; labelled ones with K = 0.  The arguments are checked before the device is
+ * touched, and a refused or failed call leaves the partitions and their contents as they were.
+ * Synchronous, on the index's own stream: when it returns every query call sees the new rows.  The call works in passes of
+ * QADC_ADC_ADD_CHUNK vectors, so its device scratch is bounded whatever count is; no result depends on the pass size. */
+#define QADC_ADC_ADD_CHUNK 262144   /* vectors per pass; bounds the device memory of a call */
+int qadc_adc_index_add_vectors(qadc_adc_index* idx, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode);
+/* The same with d_vectors [count][dim] in device memory of the index's device, complete before the call.  They are read where
+ * they lie and only by kernels, so memory of another HIP runtime (a framework's tensor) is legal, as for qadc_adc_search_device. */
+int qadc_adc_index_add_vectors_device(qadc_adc_index* idx, const float* d_vectors, uint64_t count, uint32_t labels_offset, int sum_mode);
+/* base_db::get_partition (databases.hpp:50-55) read back: rows [first, first + count) of partition `part` of an owned index,
+ * however it was filled: codes_out [count][code bytes], labels_out [count] (either may be NULL; labels_out is filled only on a
+ * labelled index).  A range outside the partition, a partition that does not exist, a view -> QADC_E_ARG. */
+int qadc_adc_index_read_partition(qadc_adc_index* idx, int part, uint32_t first, uint32_t count, uint8_t* codes_out, uint32_t* labels_out);
+/* std::vector::reserve on the partitions index_db::add_vectors pushes to (databases.hpp:291-297): capacities [part_count], in
+ * codes, are minimum capacities of the first part_count partitions; empty partitions are created up to part_count on an index
+ * that has fewer.  A capacity never shrinks.  qadc_adc_index_add_vectors writes in place while every partition it touches has
+ * room, else it moves the whole database once into a layout where every partition holds at least 1.5 times its new size: after
+ * a reserve of the final sizes a build never relocates. */
+int qadc_adc_index_reserve(qadc_adc_index* idx, int part_count, const uint32_t* capacities);
+/* Diagnostics (no reference counterpart; std::vector reallocates silently in databases.hpp:291-297): the qadc_adc_index_add_vectors
+ * calls that had to move the database to grow it. */
+uint64_t qadc_adc_index_relocations(const qadc_adc_index* idx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -778,6 +778,151 @@ __global__ __launch_bounds__(kWG) void adc_encode16_merge_kernel(const unsigned 
     codes[i] = (uint16_t)pick;
 }
 
+// ---------------------------------------------------------------------------------------------
+// db_add: index_db::add_vectors' dispatch of the encoded rows to their partitions
+// (databases.hpp:291-297), and the move of the database into a larger layout.
+//   adc_add_count_kernel    vectors per partition (atomics only count: no position depends on their order);
+//   adc_add_hist_kernel     digit histogram of every tile of kAddTile entries of one radix pass;
+//   adc_add_scan_kernel     the histograms turned into write positions, digit-major then tile order (one workgroup);
+//   adc_add_scatter_kernel  the stable scatter of the pass, tile by tile as adc_order_kernel's: rank among the equal digits
+//                           of the wave by ballots, of the waves before through LDS counts.  The last pass writes the code row
+//                           (one dword, dwordx2 or dwordx4 store) and the label instead of the permutation;
+//   adc_move_kernel         the relocation, one thread per (partition, 16-byte word) and per (partition, label).
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kAddCountLds = 8192;   // partitions + 1 the count kernel privatises in LDS; more go to global atomics
+
+__global__ __launch_bounds__(kWG) void adc_add_count_kernel(const int32_t* __restrict__ assign, uint32_t n, uint32_t K,
+                                                            uint32_t* __restrict__ count, uint32_t lds_bins) {
+    extern __shared__ uint32_t add_bins[];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < lds_bins; i += kWG) add_bins[i] = 0;
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * kWG + tid; i < n; i += (uint64_t)gridDim.x * kWG) {
+        const uint32_t a = (uint32_t)assign[i];                  // (a negative assignment is a large one)
+        const uint32_t b = a < K ? a : K;
+        if (lds_bins) atomicAdd(&add_bins[b], 1u);
+        else atomicAdd(&count[b], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < lds_bins; i += kWG)
+        if (add_bins[i]) atomicAdd(&count[i], add_bins[i]);
+}
+
+// entry `pos` of a pass: the vector it stands for (pass 0 reads the vectors in input order)
+__device__ __forceinline__ uint32_t add_entry(const uint32_t* __restrict__ perm, uint32_t pos) { return perm ? perm[pos] : pos; }
+
+__global__ __launch_bounds__(kWG) void adc_add_hist_kernel(const int32_t* __restrict__ assign, const uint32_t* __restrict__ perm,
+                                                           uint32_t n, int shift, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[256];
+    const uint32_t tid = threadIdx.x;
+    h[tid] = 0;
+    __syncthreads();
+    for (int r = 0; r < kAddTile / kWG; ++r) {
+        const uint64_t pos = (uint64_t)blockIdx.x * kAddTile + (uint32_t)r * kWG + tid;
+        if (pos < n) atomicAdd(&h[((uint32_t)assign[add_entry(perm, (uint32_t)pos)] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)blockIdx.x * 256 + tid] = h[tid];
+}
+
+// hist [tiles][256] counts -> the first write position of (tile, digit): the entries of smaller digits, then those of the same
+// digit in earlier tiles.  Thread d owns digit d.
+__global__ __launch_bounds__(kWG) void adc_add_scan_kernel(uint32_t* __restrict__ hist, uint32_t tiles) {
+    __shared__ uint32_t total[256];
+    const uint32_t d = threadIdx.x;
+    uint32_t sum = 0;
+    for (uint32_t t = 0; t < tiles; ++t) {
+        const uint32_t c = hist[(size_t)t * 256 + d];
+        hist[(size_t)t * 256 + d] = sum;
+        sum += c;
+    }
+    total[d] = sum;
+    __syncthreads();
+    uint32_t below = 0;
+    for (uint32_t j = 0; j < d; ++j) below += total[j];
+    if (below)
+        for (uint32_t t = 0; t < tiles; ++t) hist[(size_t)t * 256 + d] += below;
+}
+
+template <int BYTES>
+__global__ __launch_bounds__(kWG) void adc_add_scatter_kernel(const int32_t* __restrict__ assign, const uint32_t* __restrict__ perm,
+                                                              uint32_t n, uint32_t K, int shift, const uint32_t* __restrict__ hist,
+                                                              uint32_t* __restrict__ perm_out, bool last,
+                                                              const CodeWords<BYTES>* __restrict__ rows, uint32_t first_label,
+                                                              AddDst dst) {
+    __shared__ uint32_t run[256];                                // write position of the next entry of each digit
+    __shared__ uint32_t wcount[4 * 256];                         // entries of the digit in each wave of the round
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1;
+    run[tid] = hist[(size_t)blockIdx.x * 256 + tid];
+    for (int w = 0; w < 4; ++w) wcount[w * 256 + tid] = 0;
+    __syncthreads();
+    for (int r = 0; r < kAddTile / kWG; ++r) {
+        const uint64_t p0 = (uint64_t)blockIdx.x * kAddTile + (uint32_t)r * kWG;
+        if (p0 >= n) break;                                      // (the same for every thread of the workgroup)
+        const bool valid = p0 + tid < n;
+        const uint32_t i = valid ? add_entry(perm, (uint32_t)(p0 + tid)) : 0u;
+        const uint32_t a = valid ? (uint32_t)assign[i] : 0u;
+        const uint32_t d = (a >> shift) & 255u;
+        unsigned long long same = __ballot(valid);               // lanes of this wave with the same digit
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long m = __ballot(bit);
+            same &= bit ? m : ~m;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & below);
+        if (valid && rank == 0) wcount[wave * 256 + d] = (uint32_t)__popcll(same);
+        __syncthreads();
+        if (valid) {
+            uint32_t pos = run[d] + rank;
+            for (uint32_t w = 0; w < wave; ++w) pos += wcount[w * 256 + d];
+            if (!last) {
+                perm_out[pos] = i;
+            } else if (a < K) {
+                const uint32_t row = dst.base[a] + pos;          // (modulo 2^32: base = size - entries of the partitions below)
+                *reinterpret_cast<CodeWords<BYTES>*>(dst.codes + dst.off[a] + (uint64_t)row * BYTES) = rows[i];
+                if (dst.labels) dst.labels[dst.lab_off[a] + row] = first_label + i;
+            }
+        }
+        __syncthreads();
+        {                                                        // thread d owns digit d: advance its position, clear the counts
+            uint32_t c = 0;
+            for (int w = 0; w < 4; ++w) {
+                c += wcount[w * 256 + tid];
+                wcount[w * 256 + tid] = 0;
+            }
+            run[tid] += c;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kWG) void adc_move_kernel(int parts, int code_bytes, const uint32_t* __restrict__ sizes,
+                                                       const uint8_t* __restrict__ src_codes, const uint64_t* __restrict__ src_off,
+                                                       const uint32_t* __restrict__ src_labels, const uint64_t* __restrict__ src_lab_off,
+                                                       uint8_t* __restrict__ dst_codes, const uint64_t* __restrict__ dst_off,
+                                                       uint32_t* __restrict__ dst_labels, const uint64_t* __restrict__ dst_lab_off) {
+    const uint64_t t0 = (uint64_t)blockIdx.x * kWG + threadIdx.x, step = (uint64_t)gridDim.x * kWG;
+    for (int p = (int)blockIdx.y; p < parts; p += (int)gridDim.y) {
+        const uint64_t rows = sizes[p];
+        if (rows == 0) continue;
+        const uint64_t words = (rows * (uint64_t)code_bytes + 15) / 16;   // (both regions hold whole 16-byte words)
+        const uint4* __restrict__ s = reinterpret_cast<const uint4*>(src_codes + src_off[p]);
+        uint4* __restrict__ d = reinterpret_cast<uint4*>(dst_codes + dst_off[p]);
+        for (uint64_t w = t0; w < words; w += step) d[w] = s[w];
+        if (src_labels && dst_labels) {
+            const uint32_t* __restrict__ sl = src_labels + src_lab_off[p];
+            uint32_t* __restrict__ dl = dst_labels + dst_lab_off[p];
+            for (uint64_t j = t0; j < rows; j += step) dl[j] = sl[j];
+        }
+    }
+}
+
+__global__ __launch_bounds__(kWG) void adc_fill_words_kernel(uint32_t* __restrict__ dst, size_t n, uint32_t value) {
+    for (size_t i = (size_t)blockIdx.x * kWG + threadIdx.x; i < n; i += (size_t)gridDim.x * kWG) dst[i] = value;
+}
+
 }  // namespace
 
 hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const int32_t* assign,
@@ -915,6 +1060,61 @@ hipError_t launch_adc_encode16(const float* d_x, uint32_t n, int nsq, int dim, c
     if (hipError_t e = hipGetLastError()) return e;
     const size_t total = (size_t)n * nsq;
     hipLaunchKernelGGL(adc_encode16_merge_kernel, dim3((unsigned)((total + kWG - 1) / kWG)), dim3(kWG), 0, s, d_part, n, nsq, slices, d_codes);
+    return hipGetLastError();
+}
+
+hipError_t launch_adc_add_count(const int32_t* d_assign, uint32_t n, uint32_t K, uint32_t* d_count, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint32_t lds_bins = K + 1 <= kAddCountLds ? K + 1 : 0;
+    const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)n + 4 * kWG - 1) / (4 * kWG), 1024);
+    hipLaunchKernelGGL(adc_add_count_kernel, dim3(grid), dim3(kWG), lds_bins * sizeof(uint32_t), s, d_assign, n, K, d_count, lds_bins);
+    return hipGetLastError();
+}
+
+hipError_t launch_adc_add_scatter(const int32_t* d_assign, uint32_t n, uint32_t K, int code_bytes, const uint8_t* d_rows,
+                                  uint32_t first_label, AddDst dst, uint32_t* d_hist, uint32_t* d_perm_a, uint32_t* d_perm_b,
+                                  hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (K == 0 || (code_bytes != 4 && code_bytes != 8 && code_bytes != 16)) return hipErrorInvalidValue;
+    int bits = 0;
+    while (bits < 32 && ((K - 1) >> bits)) ++bits;
+    const int passes = std::max(1, (bits + 7) / 8);
+    const uint32_t tiles = (uint32_t)(((uint64_t)n + kAddTile - 1) / kAddTile);
+    for (int pass = 0; pass < passes; ++pass) {
+        const uint32_t* in = pass == 0 ? nullptr : (pass & 1) ? d_perm_a : d_perm_b;
+        uint32_t* out = (pass & 1) ? d_perm_b : d_perm_a;
+        const bool last = pass + 1 == passes;
+        const int shift = 8 * pass;
+        hipLaunchKernelGGL(adc_add_hist_kernel, dim3(tiles), dim3(kWG), 0, s, d_assign, in, n, shift, d_hist);
+        hipLaunchKernelGGL(adc_add_scan_kernel, dim3(1), dim3(kWG), 0, s, d_hist, tiles);
+#define QADC_AS(B) hipLaunchKernelGGL((adc_add_scatter_kernel<B>), dim3(tiles), dim3(kWG), 0, s, d_assign, in, n, K, shift, d_hist, out, last, \
+                                      reinterpret_cast<const CodeWords<B>*>(d_rows), first_label, dst)
+        if (code_bytes == 4) QADC_AS(4);
+        else if (code_bytes == 8) QADC_AS(8);
+        else QADC_AS(16);
+#undef QADC_AS
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_adc_move_partitions(int parts, int code_bytes, const uint32_t* d_sizes, uint32_t max_size, const uint8_t* src_codes,
+                                      const uint64_t* src_off, const uint32_t* src_labels, const uint64_t* src_lab_off, uint8_t* dst_codes,
+                                      const uint64_t* dst_off, uint32_t* dst_labels, const uint64_t* dst_lab_off, hipStream_t s) {
+    if (parts <= 0 || max_size == 0) return hipSuccess;
+    // grid.y walks the partitions, grid.x the words of the largest one (4 a thread), about 65536 workgroups at most
+    const unsigned gy = (unsigned)std::min(parts, 65535);
+    const uint64_t threads = std::max<uint64_t>(((uint64_t)max_size * code_bytes + 15) / 16, max_size);
+    const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((threads + 4 * kWG - 1) / (4 * kWG), std::max(1u, 65536u / gy)));
+    hipLaunchKernelGGL(adc_move_kernel, dim3(gx, gy), dim3(kWG), 0, s, parts, code_bytes, d_sizes, src_codes, src_off, src_labels, src_lab_off,
+                       dst_codes, dst_off, dst_labels, dst_lab_off);
+    return hipGetLastError();
+}
+
+hipError_t launch_adc_fill_words(void* dst, size_t words, uint32_t value, hipStream_t s) {
+    if (words == 0) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<size_t>((words + kWG - 1) / kWG, 4096);
+    hipLaunchKernelGGL(adc_fill_words_kernel, dim3(grid), dim3(kWG), 0, s, static_cast<uint32_t*>(dst), words, value);
     return hipGetLastError();
 }
 

@@ -103,5 +103,36 @@ int encode16_slices(uint32_t n, int nsq, int ds);
 hipError_t launch_adc_encode16(const float* d_x, uint32_t n, int nsq, int dim, const float* d_codebooks, const float* d_cbnorm,
                                int sum_mode, unsigned long long* d_part, uint16_t* d_codes, hipStream_t s);
 
+// ---- db_add: the dispatch of index_db::add_vectors (databases.hpp:291-297) and the growth of the owned database (DESIGN.md
+// section 11.5).  The code of vector i of a pass goes to row size[p] + rank of partition p = assign[i], rank = the earlier
+// vectors of the pass with the same assignment: a stable LSD radix sort of (assign, i) over the bits of K - 1, 8 bits a pass,
+// whose last pass writes the rows. ----
+constexpr int kAddTile = 1024;        // vectors one workgroup of the sort passes ranks (kAddTile / kWG rounds of one per thread)
+
+// d_count[p] += vectors of the pass assigned to p, d_count[K] += those outside [0, K).  d_count [K + 1], zeroed by the caller.
+hipError_t launch_adc_add_count(const int32_t* d_assign, uint32_t n, uint32_t K, uint32_t* d_count, hipStream_t s);
+// Where the rows go: the owned database and, per partition, base[p] = size[p] - (vectors of the pass assigned to partitions
+// below p), modulo 2^32: the i-th of the pass in (assign, i) order lands in row base[p] + i.
+struct AddDst {
+    uint8_t* codes;
+    const uint64_t* off;
+    uint32_t* labels;         // null: an unlabelled database
+    const uint64_t* lab_off;
+    const uint32_t* base;
+};
+// Scatters the pass: d_rows [n][code_bytes] (4, 8 or 16) and first_label + i.  Every assign[i] is in [0, K) (launch_adc_add_count
+// found none outside) and every destination row within its partition's capacity.  d_hist: (n / kAddTile + 1) * 256 words,
+// d_perm_a / d_perm_b: n words each (read only where K > 256 / K > 65536).
+hipError_t launch_adc_add_scatter(const int32_t* d_assign, uint32_t n, uint32_t K, int code_bytes, const uint8_t* d_rows,
+                                  uint32_t first_label, AddDst dst, uint32_t* d_hist, uint32_t* d_perm_a, uint32_t* d_perm_b,
+                                  hipStream_t s);
+// Moves every partition into a new layout, one thread per (partition, 16-byte word) and per (partition, label): sizes [parts] rows
+// held, offsets as Db's.  Labels are moved where both label buffers are given.
+hipError_t launch_adc_move_partitions(int parts, int code_bytes, const uint32_t* d_sizes, uint32_t max_size, const uint8_t* src_codes,
+                                      const uint64_t* src_off, const uint32_t* src_labels, const uint64_t* src_lab_off, uint8_t* dst_codes,
+                                      const uint64_t* dst_off, uint32_t* dst_labels, const uint64_t* dst_lab_off, hipStream_t s);
+// dst[i] = value for `words` 32-bit words.
+hipError_t launch_adc_fill_words(void* dst, size_t words, uint32_t value, hipStream_t s);
+
 }  // namespace adc
 }  // namespace qadc

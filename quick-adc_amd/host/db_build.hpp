@@ -14,6 +14,7 @@
 //                                          vector_io.hpp:231-288) fills a two-chunk queue from the .fvecs/.bvecs file while
 //                                          this thread encodes the previous chunk on the GPU; labels = index in chunk + the
 //                                          chunk's offset, as there.
+//   db_add_hip(qadc_adc_index*, dim, base_file, chunk_count)  the same into a float-ADC index: encode and append on the GPU
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -58,12 +59,12 @@ inline void add_chunk_hip(ivf_database& db, const io::vectors_chunk& c, int devi
 inline void add_chunk_cpu(flat_database& db, const io::vectors_chunk& c) { db.add_vectors(c.data.data(), c.count); }
 inline void add_chunk_cpu(ivf_database& db, const io::vectors_chunk& c) { db.add_vectors(c.data.data(), c.count, c.offset); }
 
-// db_add.cpp:52-82.  on_gpu = false runs the host loops instead (the definition the GPU build is compared with).
-// Returns the vectors added; throws with the reference's message if the reader fails (wrong dimension, unknown extension).
-template <typename Db>
-unsigned db_add_hip(Db& db, const char* base_filename, unsigned chunk_count = 1000000, int device = 0, bool on_gpu = true) {
+// db_add.cpp:52-82: `add` takes every chunk of the file in turn.  Returns the vectors added; throws with the reference's message
+// if the reader fails (wrong dimension, unknown extension), or with the first error of `add` — after the file has been drained.
+template <typename AddChunk>
+unsigned db_add_chunks(const char* base_filename, unsigned chunk_count, int dim, AddChunk add) {
     io::vectors_reader reader(base_filename, chunk_count);
-    if (reader.dim() != db.pq->dim) throw std::runtime_error("base vectors and quantizer disagree on the dimension");
+    if (reader.dim() != dim) throw std::runtime_error("base vectors and quantizer disagree on the dimension");
     std::thread read_thread([&reader] { reader.run(); });
     unsigned added = 0;
     std::string error;
@@ -75,8 +76,7 @@ unsigned db_add_hip(Db& db, const char* base_filename, unsigned chunk_count = 10
         }
         if (error.empty()) {
             try {
-                if (on_gpu) add_chunk_hip(db, chunk, device);
-                else add_chunk_cpu(db, chunk);
+                add(chunk);
                 added += chunk.count;
             } catch (const std::exception& e) {
                 error = e.what();                                // keep draining: the reader must not stay blocked on a full queue
@@ -86,6 +86,25 @@ unsigned db_add_hip(Db& db, const char* base_filename, unsigned chunk_count = 10
     read_thread.join();
     if (!error.empty()) throw std::runtime_error(error);
     return added;
+}
+
+// on_gpu = false runs the host loops instead (the definition the GPU build is compared with).
+template <typename Db>
+unsigned db_add_hip(Db& db, const char* base_filename, unsigned chunk_count = 1000000, int device = 0, bool on_gpu = true) {
+    return db_add_chunks(base_filename, chunk_count, db.pq->dim, [&](const io::vectors_chunk& chunk) {
+        if (on_gpu) add_chunk_hip(db, chunk, device);
+        else add_chunk_cpu(db, chunk);
+    });
+}
+
+// The same into a float-ADC index (qadc_adc_index_add_vectors): every chunk is encoded and appended in device memory with the
+// quantizers the index holds (`dim` = the dimension given to qadc_adc_index_set_pq), labels = index in chunk + the chunk's offset;
+// a flat index writes the chunk at that offset.  No code comes back to the host.
+inline unsigned db_add_hip(qadc_adc_index* idx, int dim, const char* base_filename, unsigned chunk_count = 1000000, int sum_mode = 1) {
+    return db_add_chunks(base_filename, chunk_count, dim, [&](const io::vectors_chunk& chunk) {
+        if (qadc_adc_index_add_vectors(idx, chunk.data.data(), chunk.count, chunk.offset, sum_mode) != QADC_OK)
+            throw std::runtime_error(std::string("qadc_adc_index_add_vectors: ") + qadc_last_error());
+    });
 }
 
 // databases.cpp:50-90 on the host: assign every vector to its closest centroid (find_k_neighbors with k = 1: the expansion

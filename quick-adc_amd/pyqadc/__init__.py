@@ -42,6 +42,8 @@ SYMBOLS = [
     "qadc_adc_search", "qadc_adc_search_candidates", "qadc_adc_search_tables", "qadc_adc_encode_host",
     "qadc_adc_index_set_finish", "qadc_adc_index_host_finishes", "qadc_adc_search_device", "qadc_adc_query_scan_device",
     "qadc_adc_index_create_view", "qadc_adc_index_create16", "qadc_adc_encode16_host",
+    "qadc_adc_index_add_vectors", "qadc_adc_index_add_vectors_device", "qadc_adc_index_read_partition", "qadc_adc_index_reserve",
+    "qadc_adc_index_relocations",
 ]
 
 
@@ -67,6 +69,7 @@ class Profile(C.Structure):
 
 QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h
 QADC_ADC_ENCODE16_CHUNK = 262144   # include/qadc.h: vectors qadc_adc_encode16_host encodes per pass
+QADC_ADC_ADD_CHUNK = 262144        # include/qadc.h: vectors qadc_adc_index_add_vectors encodes and appends per pass
 
 
 class QadcError(RuntimeError):
@@ -193,6 +196,12 @@ def lib():
                                              C.c_void_p]
         L.qadc_adc_query_scan_device.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]
+        L.qadc_adc_index_add_vectors.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_int]
+        L.qadc_adc_index_add_vectors_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int]
+        L.qadc_adc_index_read_partition.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u8p, u32p]
+        L.qadc_adc_index_reserve.argtypes = [C.c_void_p, C.c_int, u32p]
+        L.qadc_adc_index_relocations.argtypes = [C.c_void_p]
+        L.qadc_adc_index_relocations.restype = C.c_uint64
         _lib = L
     return _lib
 
@@ -890,6 +899,63 @@ class AdcIndex:
 
     def partition_size(self, part):
         return lib().qadc_adc_index_partition_size(self._h, part)
+
+    # ---- db_add: encode and append on the GPU with the index's own quantizers (qadc_adc_index_add_vectors) ----
+    def add_vectors(self, vectors, labels_offset=0, sum_mode=1):
+        """vectors [n][dim]: with a coarse quantizer the code of vector i is appended to its nearest centroid's partition with label
+        labels_offset + i (index_db::add_vectors); a flat index writes it at row labels_offset + i of its one partition
+        (flat_db::add_vectors)."""
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim == 1:
+            v = v.reshape(-1, getattr(self, "dim", 1))
+        assert v.ndim == 2 and (v.shape[0] == 0 or v.shape[1] == getattr(self, "dim", v.shape[1]))
+        self.add_vectors_raw(v, v.shape[0], labels_offset, sum_mode)
+
+    def add_vectors_raw(self, vectors, count, labels_offset, sum_mode):
+        """The C call as it is (vectors: a float32 array or None)."""
+        _check(lib().qadc_adc_index_add_vectors(self._h, _p(vectors, f32p), count, labels_offset, sum_mode))
+
+    def add_vectors_device(self, vectors, labels_offset=0, sum_mode=1):
+        """add_vectors for a float32 torch tensor [n][dim] on the index's device, read where it lies."""
+        if getattr(vectors, "ndim", 0) != 2:
+            raise TypeError("vectors must be a 2-d torch.Tensor")
+        n = int(vectors.shape[0])
+        v = self._device_tensor(vectors, (n, getattr(self, "dim", int(vectors.shape[1]))), "vectors")
+        import torch
+        torch.cuda.current_stream(v.device).synchronize()                # the vectors are complete before the call
+        _check(lib().qadc_adc_index_add_vectors_device(self._h, v.data_ptr(), n, labels_offset, sum_mode))
+
+    def read_partition(self, part, first=0, count=None):
+        """-> (codes uint8 [n][sq_count] — a create16 index: uint16 [n][sq_count] —, labels uint32 [n] or None on an index without
+        labels): rows [first, first + count) of the partition as they lie in device memory (default: all of it)."""
+        if count is None:
+            count = max(self.partition_size(part) - first, 0) if 0 <= part < self.partition_count() else 0
+        wide = self.centroids == 65536
+        codes = np.zeros((count, self.sq_count), "<u2" if wide else np.uint8)
+        labels = np.zeros(count, np.uint32) if self._labelled() else None
+        _check(lib().qadc_adc_index_read_partition(self._h, part, first, count, codes.ctypes.data_as(u8p), _p(labels, u32p)))
+        return (codes.astype(np.uint16, copy=False) if wide else codes), labels
+
+    def _labelled(self):
+        """whether the database has labels: the C call fills labels_out only then (probed on the first row the index holds)"""
+        for part in range(self.partition_count()):
+            if self.partition_size(part):
+                seen = []
+                for fill in (0, 1):
+                    one = np.full(1, fill, np.uint32)
+                    _check(lib().qadc_adc_index_read_partition(self._h, part, 0, 1, None, _p(one, u32p)))
+                    seen.append(int(one[0]))
+                return seen[0] == seen[1]
+        return False
+
+    def reserve(self, capacities):
+        """minimum capacities, in codes, of the first len(capacities) partitions (empty ones are created where the index has fewer)"""
+        c = np.ascontiguousarray(capacities, np.uint32).reshape(-1)
+        _check(lib().qadc_adc_index_reserve(self._h, len(c), _p(c, u32p)))
+
+    def relocations(self):
+        """add_vectors calls that had to move the database to grow it"""
+        return lib().qadc_adc_index_relocations(self._h)
 
     def reruns(self):
         """query calls on this index that were re-run because a candidate region overflowed"""

@@ -1,9 +1,9 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
   batch32   32 queries per call on the same list
@@ -20,6 +20,11 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             asserted equal, and the same pair at 1, 8, 32, 128 and 1024 queries per call.
   lone_search  one synchronous search() of one query at that shape under the host finish and, alternated with it and asserted
             equal, under the device finish, beside one CPU thread scanning the same 24 partitions
+  add       database build (not in the default legs; also under --bits 16, at 2x16): 10^6 clustered 128-d vectors, K = 256, 8x8.
+            add_vectors, call to return, into an empty index and into one reserved to the final sizes, alternated in one process with
+            the route without it: adc_encode (adc_encode16), the stable grouping by assign in numpy, add_partitions.  The partitions
+            of the routes are asserted equal.  Under rocprofv3 --kernel-trace --stats the same leg gives the dispatch kernels' time
+            beside the encoder's
   --bits 4   the float-ADC view of a 4-bit index instead (pyqadc.AdcIndex.view_of; legs lone,ivf_search):
   lone      one synchronous query on 10^6 and on 10^8 codes at 16x4 and 32x4: median and range of the call, codes/s, the share
             of the HBM roofline at 8 B / 16 B per code; at 16x4 alternated with the 8x8 engine on a list of the same n (the
@@ -343,6 +348,80 @@ def cpu_twin_encode16(codebooks, vectors):
     return float(out[out.index("us") + 1]) * 1e-6, codes
 
 
+def add_leg(bits, iters, res):
+    """database build: add_vectors (empty / reserved index) alternated with encode + numpy grouping + add_partitions"""
+    rng = np.random.default_rng(1700 + bits)
+    n, dim, K = 1_000_000, 128, 256
+    nsq = 8 if bits == 8 else 2
+    vectors, _ = clustered(rng, n, dim)
+    coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, K, replace=False)], 5)
+    sample = vectors[rng.choice(n, 1 << bits, replace=False)]
+    codebooks = np.ascontiguousarray(sample.reshape(1 << bits, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
+    encode = pyqadc.adc_encode if bits == 8 else pyqadc.adc_encode16
+
+    def make():
+        idx = pyqadc.AdcIndex(nsq, 8) if bits == 8 else pyqadc.AdcIndex.create16(nsq)
+        idx.set_pq(codebooks)
+        idx.set_coarse(coarse)
+        return idx
+
+    kept = {}
+
+    def parent_route():
+        idx = make()
+        a, codes = encode(codebooks, vectors, coarse)
+        order = np.argsort(a, kind="stable")
+        bounds = np.searchsorted(a[order], np.arange(K + 1))
+        idx.add_partitions([codes[order[bounds[k]:bounds[k + 1]]] for k in range(K)],
+                           [order[bounds[k]:bounds[k + 1]].astype(np.uint32) for k in range(K)])
+        kept["sizes"] = np.diff(bounds)
+        return idx
+
+    def new_route(reserve):
+        idx = make()
+        if reserve:
+            idx.reserve(kept["sizes"])
+        idx.add_vectors(vectors)
+        return idx
+
+    # the routes build the same database
+    a, b = parent_route(), new_route(False)
+    for k in range(K):
+        (ca, la), (cb, lb) = a.read_partition(k), b.read_partition(k)
+        assert np.array_equal(ca, cb) and np.array_equal(la, lb), "partition %d differs between the routes" % k
+    relocations = b.relocations()
+    a.close()
+    b.close()
+
+    def timed_build(route):
+        def run():                                                           # the index's creation and release are outside the clock
+            t0 = time.perf_counter()
+            idx = route()
+            t = time.perf_counter() - t0
+            idx.close()
+            return t
+        return run
+
+    arms = {"parent_route": timed_build(parent_route), "add_vectors_empty": timed_build(lambda: new_route(False)),
+            "add_vectors_reserved": timed_build(lambda: new_route(True))}
+    times = dict((name, []) for name in arms)
+    for it in range(1 + max(3, iters // 2)):                                 # one warm-up round, then the arms in turn
+        for name, run in arms.items():
+            t = run()
+            if it:
+                times[name].append(t)
+    tag = "add_%dx%d" % (nsq, bits)
+    for name, ts in times.items():
+        res["%s_%s_s_median_min_max" % (tag, name)] = [float(np.median(ts)), float(np.min(ts)), float(np.max(ts))]
+    res[tag + "_relocations_of_the_unreserved_call"] = int(relocations)
+    med = dict((name, float(np.median(ts))) for name, ts in times.items())
+    print("database build %dx%d, %.0e clustered 128-d vectors, K = %d (index creation and set_pq / set_coarse inside every arm): encode + numpy "
+          "grouping + add_partitions %.3f s; add_vectors into an empty index %.3f s (%d relocating passes' call); into a reserved one %.3f s "
+          "= %.2fx / %.2fx the route without it" % (nsq, bits, n, K, med["parent_route"], med["add_vectors_empty"], relocations,
+                                                     med["add_vectors_reserved"], med["parent_route"] / med["add_vectors_empty"],
+                                                     med["parent_route"] / med["add_vectors_reserved"]), flush=True)
+
+
 def encode16_leg(iters, res):
     rng = np.random.default_rng(1616)
     dim, twin_n = 128, 256
@@ -486,6 +565,8 @@ def word_legs(legs, iters, res):
             idx.close()
     if "encode16" in legs:
         encode16_leg(iters, res)
+    if "add" in legs:
+        add_leg(16, iters, res)
     if "profile" in legs:
         n = 100_000_000
         idx = pyqadc.AdcIndex.create16(8)
@@ -608,6 +689,8 @@ def main():
         idx.close()
     if "ivf_search" in legs or "lone_search" in legs:
         search_legs(legs, a.iters, res)
+    if "add" in legs:
+        add_leg(8, a.iters, res)
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -727,6 +727,55 @@ int qadc_adc_index_reserve(qadc_adc_index* idx, int part_count, const uint32_t* 
  * calls that had to move the database to grow it. */
 uint64_t qadc_adc_index_relocations(const qadc_adc_index* idx);
 
+/* ---- db_add on the 4-bit index: vectors in, index grown, on the GPU.  The quantizers are those the
+ * index holds at the call (qadc_index_set_pq, _set_rotation, _set_coarse). ---- */
+
+/* index_db::add_vectors (databases.hpp:270-298) on an index with a coarse quantizer (K > 0), flat_db::add_vectors (136-156) on
+ * one without.  vectors [count][dim], host memory.
+ *   K > 0: per vector find_k_neighbors(k = 1) on the coarse centroids, the residual, the rotation if one is set, the 4-bit code:
+ *     the steps and kernels of qadc_ivf_encode_host_mode(encode_form = 1, sum_mode).  The code of vector i is appended to
+ *     partition assign[i] with label labels_offset + i; within a partition the new rows stand in input order, behind the rows
+ *     already there.  The index holds 0 partitions (K empty ones are created) or exactly K, and is labelled or still undecided.
+ *     A call of n vectors equals any split of it into calls.
+ *   K = 0: one unlabelled partition, created if absent.  The code of vector i is written at row labels_offset + i; the size
+ *     becomes max(size, labels_offset + count), also for count 0; rows of a gap are zero bytes; rows that exist are overwritten.
+ * The call leaves the index not finalized, as every qadc_index_add_* does: call qadc_index_finalize again before querying.
+ * QADC_E_STATE while a submission slot is busy.  QADC_E_ARG, the message says which: no set_pq yet; sum_mode not 0 or 1; vectors
+ * NULL with count > 0; labels_offset + count above 2^32 - 1; a partition that would pass 2^32 - 1 codes; a partition count that
+ * is neither 0 nor K (flat: more than one); unlabelled non-empty partitions with K > 0; labelled ones with K = 0; a live float-ADC
+ * view (qadc_adc_index_create_view: it keeps the partitions' addresses, which a relocation changes); an index under
+ * qadc_dist_init, or one holding a shard or a starts replica; a borrowed partition (qadc_index_add_partition_device); a vector
+ * assigned outside [0, K).  The arguments are checked before the device is touched, and a refused call leaves the partitions and
+ * their contents as they were.  A call that fails later (a HIP error, no memory for a relocation or for a pass) leaves every
+ * partition with the number of rows it held and, with a coarse quantizer, with their contents: it only ever wrote behind them.
+ * Without one (K = 0) rows that existed and that the call was to overwrite may already hold the new codes.  Such a failed call may
+ * have moved the partitions or changed their rows, and then leaves the index not finalized: call qadc_index_finalize before the
+ * next query, as after a call that succeeded.
+ * Synchronous, on the index's scan stream, in passes of QADC_INDEX_ADD_CHUNK vectors: the device scratch of a call is bounded
+ * whatever count is, and no result depends on the pass size.
+ * Storage: the first call moves partitions that qadc_index_add_partitions / _interleaved / _synthetic allocated one by one into
+ * one arena of the index and frees them; an append that fits its partition's capacity writes in place, otherwise the whole
+ * database moves once into an arena where every partition holds 1.5 times its new size.  While it moves, the device holds the
+ * old and the new database at once. */
+#define QADC_INDEX_ADD_CHUNK 262144   /* vectors per pass; bounds the device memory of a call */
+int qadc_index_add_vectors(qadc_index* idx, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode);
+/* The same with d_vectors [count][dim] in device memory of the index's device, complete before the call.  They are read where
+ * they lie and only by kernels, so memory of another HIP runtime (a framework's tensor) is legal. */
+int qadc_index_add_vectors_device(qadc_index* idx, const float* d_vectors, uint64_t count, uint32_t labels_offset, int sum_mode);
+/* base_db::get_partition (databases.hpp:50-55) read back: rows [first, first + count) of partition `part`, however it was filled,
+ * as long as it is held whole: codes_out [count][M / 2], labels_out [count] (either may be NULL; labels_out is filled only on a
+ * labelled index).  A range outside the partition, a partition that does not exist, a shard -> QADC_E_ARG. */
+int qadc_index_read_partition(qadc_index* idx, int part, uint32_t first, uint32_t count, uint8_t* codes_out, uint32_t* labels_out);
+/* std::vector::reserve on the partitions index_db::add_vectors pushes to (databases.hpp:291-297): capacities [part_count], in
+ * codes, are minimum capacities of the first part_count partitions; empty partitions are created up to part_count on an index
+ * that has fewer.  A capacity never shrinks.  After a reserve of the final sizes a build never relocates.  Refused as
+ * qadc_index_add_vectors is (busy slots, views, multi-GPU, shards, borrowed partitions).  A reserve that moves the partitions
+ * leaves the index not finalized. */
+int qadc_index_reserve(qadc_index* idx, int part_count, const uint32_t* capacities);
+/* Diagnostics (std::vector reallocates silently in databases.hpp:291-297): the qadc_index_add_vectors calls that had to move the
+ * database to grow it. */
+uint64_t qadc_index_relocations(const qadc_index* idx);
+
 #ifdef __cplusplus
 }
 #endif

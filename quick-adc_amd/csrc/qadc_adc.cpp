@@ -47,13 +47,6 @@ namespace {
 constexpr uint64_t kSpeculativeEntries = 1 << 16;   // regions up to this many entries in all come back with the counts
 constexpr uint64_t kMaxEntries = QADC_ADC_MAX_ENTRIES;   // candidate entries of one batch (12 B of device memory each)
 
-// Every entry point works on the index's device and gives the calling thread its current device back.
-struct DeviceGuard {
-    int prev = -1;
-    DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
 struct qadc_adc_index {
@@ -419,7 +412,6 @@ int scan_host_tables(qadc_adc_index* idx, int nq, int ma, const int32_t* assign,
 
 // ---- feeders: query vectors -> assign + device tables (qadc_adc_search*) ----
 
-constexpr int kCoarseChunk = 32768;   // queries per coarse-assignment pass (the distance scratch is chunk x K floats)
 
 // The quantizers of one search call, read only: the index's own, or — a view — its source's as they stand when the call is
 // made.  Nothing of them is written into a view.
@@ -642,17 +634,6 @@ int stream_to_host(qadc_adc_index* idx, int nq, uint64_t cand_capacity, uint32_t
     if (int rc = produce(nullptr)) return rc;
     return copy_stream(idx, nq, cand_capacity, cand_keys, cand_vals, offsets);
 }
-
-struct Scratch {   // device memory of a stateless entry point, freed on every exit path
-    std::vector<void*> p;
-    ~Scratch() { for (void* x : p) if (x) (void)hipFree(x); }
-    template <typename T> hipError_t alloc(T** out, size_t bytes) {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) { p.push_back(q); *out = static_cast<T*>(q); }
-        return e;
-    }
-};
 
 // ---- db_add: qadc_adc_index_add_vectors, _reserve, _read_partition ----
 

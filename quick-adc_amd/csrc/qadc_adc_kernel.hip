@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cfloat>
 
+#include "../host/index_append_plan.hpp"   // index_padded_end: the span kept zero behind a partition's last row
 #include "qadc_adc_kernels.h"
 #include "qadc_float_sum.h"
 
@@ -919,6 +920,45 @@ __global__ __launch_bounds__(kWG) void adc_move_kernel(int parts, int code_bytes
     }
 }
 
+// ---- the growing storage of the 4-bit index ----
+// The gather-move of a relocation: partition p = blockIdx.y, y-strided, goes from wherever it lies (an allocation of its own on the
+// consolidating call, the old arena later; never the destination buffer) to its region of the new arena — whole 16-byte words, the
+// odd half of the last word of an 8-byte-row partition as one dwordx2, labels as dwords — and bytes [n * cs, align16(n * cs) + 64)
+// behind the last row are zeroed, for empty partitions too (host/index_append_plan.hpp has why).
+__global__ __launch_bounds__(kWG) void index_move_kernel(const IndexMove* __restrict__ moves, int parts, int code_bytes) {
+    const uint64_t t0 = (uint64_t)blockIdx.x * kWG + threadIdx.x, step = (uint64_t)gridDim.x * kWG;
+    for (int p = (int)blockIdx.y; p < parts; p += (int)gridDim.y) {
+        const IndexMove m = moves[p];
+        const uint64_t bytes = (uint64_t)m.n * (uint64_t)code_bytes;      // (a multiple of 8: rows are 8 or 16 bytes)
+        const uint64_t words = bytes / 16;
+        const uint4* __restrict__ s = reinterpret_cast<const uint4*>(m.src_codes);
+        uint4* __restrict__ d = reinterpret_cast<uint4*>(m.dst_codes);
+        for (uint64_t w = t0; w < words; w += step) d[w] = s[w];
+        if (t0 < 10) {                                           // the tail: the odd half word, then up to 9 dwordx2 of zeroes
+            const uint64_t u = words * 2 + t0, last = index_padded_end(bytes) / 8;
+            if (u < last) {
+                uint2 v = make_uint2(0u, 0u);
+                if (u * 8 < bytes) v = reinterpret_cast<const uint2*>(m.src_codes)[u];
+                reinterpret_cast<uint2*>(m.dst_codes)[u] = v;
+            }
+        }
+        if (m.src_labels && m.dst_labels)
+            for (uint64_t j = t0; j < m.n; j += step) m.dst_labels[j] = m.src_labels[j];
+    }
+}
+
+// Bytes [n * cs, align16(n * cs) + 64) behind the last row of every partition zeroed where the partitions lie now: 16 threads a
+// partition, 9 of them storing one dwordx2 each.  sizes [parts] rows held; off [parts] as AddDst's.
+__global__ __launch_bounds__(kWG) void index_zero_tails_kernel(uint8_t* __restrict__ codes, const uint64_t* __restrict__ off,
+                                                               const uint32_t* __restrict__ sizes, uint32_t parts, int code_bytes) {
+    const uint64_t t = (uint64_t)blockIdx.x * kWG + threadIdx.x;
+    const uint64_t p = t / 16, j = t % 16;
+    if (p >= parts) return;
+    const uint64_t bytes = (uint64_t)sizes[p] * (uint64_t)code_bytes;
+    const uint64_t u = bytes / 8 + j, last = index_padded_end(bytes) / 8;
+    if (u < last) reinterpret_cast<uint2*>(codes + off[p])[u] = make_uint2(0u, 0u);
+}
+
 __global__ __launch_bounds__(kWG) void adc_fill_words_kernel(uint32_t* __restrict__ dst, size_t n, uint32_t value) {
     for (size_t i = (size_t)blockIdx.x * kWG + threadIdx.x; i < n; i += (size_t)gridDim.x * kWG) dst[i] = value;
 }
@@ -1115,6 +1155,26 @@ hipError_t launch_adc_fill_words(void* dst, size_t words, uint32_t value, hipStr
     if (words == 0) return hipSuccess;
     const unsigned grid = (unsigned)std::min<size_t>((words + kWG - 1) / kWG, 4096);
     hipLaunchKernelGGL(adc_fill_words_kernel, dim3(grid), dim3(kWG), 0, s, static_cast<uint32_t*>(dst), words, value);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_move(const IndexMove* d_moves, int parts, int code_bytes, uint32_t max_size, hipStream_t s) {
+    if (parts <= 0) return hipSuccess;
+    if (code_bytes != 8 && code_bytes != 16) return hipErrorInvalidValue;
+    // grid.y walks the partitions, grid.x the 16-byte words of the largest one (4 a thread), about 65536 workgroups at most
+    const unsigned gy = (unsigned)std::min(parts, 65535);
+    const uint64_t threads = std::max<uint64_t>((uint64_t)max_size * code_bytes / 16, max_size);
+    const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((threads + 4 * kWG - 1) / (4 * kWG), std::max(1u, 65536u / gy)));
+    hipLaunchKernelGGL(index_move_kernel, dim3(gx, gy), dim3(kWG), 0, s, d_moves, parts, code_bytes);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_zero_tails(uint8_t* d_codes, const uint64_t* d_off, const uint32_t* d_sizes, uint32_t parts, int code_bytes,
+                                   hipStream_t s) {
+    if (parts == 0) return hipSuccess;
+    if (code_bytes != 8 && code_bytes != 16) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)(((uint64_t)parts * 16 + kWG - 1) / kWG);
+    hipLaunchKernelGGL(index_zero_tails_kernel, dim3(grid), dim3(kWG), 0, s, d_codes, d_off, d_sizes, parts, code_bytes);
     return hipGetLastError();
 }
 

@@ -134,5 +134,24 @@ hipError_t launch_adc_move_partitions(int parts, int code_bytes, const uint32_t*
 // dst[i] = value for `words` 32-bit words.
 hipError_t launch_adc_fill_words(void* dst, size_t words, uint32_t value, hipStream_t s);
 
+// ---- the growing storage of the 4-bit index (csrc/qadc_index_add.cpp) ----
+// One partition of a relocation: n rows from src_codes (null where n is 0) to dst_codes, its region of the new arena, and n labels
+// where both label pointers are given.  Source and destination never overlap: a relocation fills a new arena.
+struct IndexMove {
+    const uint8_t* src_codes;
+    uint8_t* dst_codes;
+    const uint32_t* src_labels;
+    uint32_t* dst_labels;
+    uint32_t n;
+    uint32_t pad;
+};
+// Moves every partition in one launch (grid.y over the partitions) and zeroes bytes [n * cs, align16(n * cs) + 64) behind the last
+// row of each, empty ones included.  code_bytes 8 or 16; max_size: the largest n.
+hipError_t launch_index_move(const IndexMove* d_moves, int parts, int code_bytes, uint32_t max_size, hipStream_t s);
+// The same zeroes behind the last row of partitions that stay where they are (after an append in place, after a restore):
+// partition p holds d_sizes[p] rows at d_codes + d_off[p].
+hipError_t launch_index_zero_tails(uint8_t* d_codes, const uint64_t* d_off, const uint32_t* d_sizes, uint32_t parts, int code_bytes,
+                                   hipStream_t s);
+
 }  // namespace adc
 }  // namespace qadc

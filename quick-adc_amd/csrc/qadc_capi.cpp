@@ -1216,13 +1216,14 @@ int qadc_index_destroy(qadc_index* idx) {
     (void)qadc_dist_shutdown(idx);      // drains the merge's stream and frees the communicator while the index's streams and
                                         // the slot buffers the pack kernel reads are still alive
     for (auto& p : idx->parts) {
-        if (p.own) {
+        if (p.own && !p.arena) {
             if (p.d_codes) (void)hipFree(p.d_codes);
             if (p.d_labels) (void)hipFree(p.d_labels);
         }
         if (p.d_starts) (void)hipFree(p.d_starts);
         if (p.d_split) (void)hipFree(p.d_split);
     }
+    idx->arena.release();               // (the partitions with Part::arena, all at once)
     idx->feed.d_codebooks.release();
     idx->feed.d_rotation.release();
     idx->feed.d_coarse.release();

@@ -4,6 +4,7 @@
 //   qadc_ivf.cpp    one-workgroup-per-query batches, partition-major second phase, device-side feeders (qadc_search)
 //   qadc_dist.cpp   native multi-GPU merge (qadc_dist_*: RCCL by dlopen, or a caller-supplied all-gather)
 //   qadc_build.cpp  database build entry points (PQ / IVF encode, k-means iterations)
+//   qadc_index_add.cpp  db_add on the index: qadc_index_add_vectors, _reserve, _read_partition (storage that grows)
 // The level-path planner itself (items, launches, plan_levels) is host/level_plan.hpp: no HIP, checked on a CPU.
 // The last three keep their state in structs of their own hung off qadc_index (FeederState, GroupState, DistState).
 #pragma once
@@ -88,9 +89,32 @@ struct PinBuf {
     }
 };
 
+// Every entry point that may be called with another device current works on the index's device and gives the calling thread its
+// current device back.
+struct DeviceGuard {
+    int prev = -1;
+    DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+struct Scratch {   // device memory of one call, freed on every exit path
+    std::vector<void*> p;
+    ~Scratch() { for (void* x : p) if (x) (void)hipFree(x); }
+    template <typename T> hipError_t alloc(T** out, size_t bytes) {
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess) { p.push_back(q); *out = static_cast<T*>(q); }
+        return e;
+    }
+};
+
+constexpr int kCoarseChunk = 32768;   // vectors per coarse-assignment launch of the float-ADC search and of the db_add encoders (the
+                                      // distance scratch is chunk x K floats)
+
 struct Part : LevelPart {           // (the fields the level planner reads: host/level_plan.hpp)
     uint32_t starts_cap = 0;       // codes available for the pre-scan
     bool own = true;
+    bool arena = false;            // d_codes / d_labels point into the index's arena (ArenaState): freed with it, not one by one
 };
 
 constexpr int kMergeStreams = 3;   // streams the enqueued merges MAY rotate over (measurement hook); the default creates ONE:
@@ -326,6 +350,25 @@ struct FeederState {
     int table_form = 2;          // float tables of qadc_search: 0 direct, 1 BLAS expansion, 2 the reference's nns_engine rule
 };
 
+// The storage that grows (qadc_index_add_vectors, qadc_index_reserve: qadc_index_add.cpp; layout: host/index_append_plan.hpp).
+// Empty until the first of those calls; from then on every partition of the index lies in `codes` / `labels` (Part::arena).
+struct ArenaState {
+    DevBuf<uint8_t> codes;             // the regions of all partitions, back to back
+    DevBuf<uint32_t> labels;           // cap[p] labels per partition (allocated once the index is labelled)
+    DevBuf<uint64_t> d_off, d_lab_off; // [parts] device copies of off / lab_off (AddDst)
+    std::vector<uint32_t> caps;        // [parts] rows each region holds
+    std::vector<uint64_t> off, lab_off;
+    uint64_t code_bytes = 0, label_count = 0;
+    uint64_t relocations = 0;          // add_vectors calls that moved the database to grow it
+    PinBuf<uint32_t> h_add;            // add_vectors: [counts K + 1 | bases K | sizes K]
+    bool active() const { return codes.p != nullptr; }
+    void release() {
+        codes.release(); labels.release(); d_off.release(); d_lab_off.release(); h_add.release();
+        caps.clear(); off.clear(); lab_off.clear();
+        code_bytes = label_count = 0;
+    }
+};
+
 // Fixed tuning constants (each was an option while it was being measured; the sweeps are in profiles/, see profiles/README.md)
 constexpr uint64_t kFrontMinBatch = 3000000000ull; // leading levels join the front stream only in batches of at least this many (code, query)
                                                    // pairs: under a shorter last level they only make the front stream the step's longest chain
@@ -425,6 +468,7 @@ struct qadc_index {
     FeederState feed;                   // qadc_ivf.cpp: N1, the feeders on the device
     GroupState group;                   // qadc_ivf.cpp: partition-major second phase of large IVF batches
     DistState* dist = nullptr;          // qadc_dist.cpp: qadc_dist_init
+    ArenaState arena;                   // qadc_index_add.cpp: the partitions of an index that has grown
     int adc_views = 0;                  // qadc_adc.cpp: live float-ADC views reading this index's partitions (qadc_adc_index_create_view);
                                         // qadc_index_destroy refuses while there is one
 };

@@ -31,8 +31,9 @@ struct AppendPlan {
     uint64_t label_count = 0;       // labels of all regions
 };
 
-// Regions of the given capacities, back to back.
-inline void append_layout(int code_size, AppendPlan* p) {
+// Regions of the given capacities, back to back.  region_pad: bytes every code region holds behind its rows (a multiple of 16;
+// 0 here, host/index_append_plan.hpp has the 4-bit index's).
+inline void append_layout(int code_size, AppendPlan* p, uint64_t region_pad = 0) {
     uint64_t bytes = 0, labels = 0;
     const size_t parts = p->cap.size();
     p->off.resize(parts);
@@ -40,7 +41,7 @@ inline void append_layout(int code_size, AppendPlan* p) {
     for (size_t i = 0; i < parts; ++i) {
         p->off[i] = bytes;
         p->lab_off[i] = labels;
-        bytes += append_align16((uint64_t)p->cap[i] * code_size);
+        bytes += append_align16((uint64_t)p->cap[i] * code_size) + region_pad;
         labels += p->cap[i];
     }
     p->code_bytes = bytes;
@@ -54,7 +55,7 @@ inline void append_layout(int code_size, AppendPlan* p) {
 // what is needed; never less than its old capacity or its floor; rounded up to the rows its 16-byte-aligned region holds anyway,
 // and never more than 2^32 - 1 rows.
 inline AppendPlan plan_append(int code_size, size_t parts, const uint32_t* sizes, const uint32_t* caps, const uint64_t* add,
-                              const uint32_t* floor, bool grow) {
+                              const uint32_t* floor, bool grow, uint64_t region_pad = 0) {
     AppendPlan p;
     bool fits = true;
     for (size_t i = 0; i < parts; ++i) {
@@ -67,7 +68,7 @@ inline AppendPlan plan_append(int code_size, size_t parts, const uint32_t* sizes
     }
     p.cap.assign(caps, caps + parts);
     if (fits) {
-        append_layout(code_size, &p);
+        append_layout(code_size, &p, region_pad);
         return p;
     }
     p.in_place = false;
@@ -80,7 +81,7 @@ inline AppendPlan plan_append(int code_size, size_t parts, const uint32_t* sizes
         want = append_align16(want * code_size) / code_size;   // the rows the aligned region holds
         p.cap[i] = (uint32_t)std::min<uint64_t>(want, kAppendMaxRows);
     }
-    append_layout(code_size, &p);
+    append_layout(code_size, &p, region_pad);
     return p;
 }
 

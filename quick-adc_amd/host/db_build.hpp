@@ -15,6 +15,7 @@
 //                                          this thread encodes the previous chunk on the GPU; labels = index in chunk + the
 //                                          chunk's offset, as there.
 //   db_add_hip(qadc_adc_index*, dim, base_file, chunk_count)  the same into a float-ADC index: encode and append on the GPU
+//   db_add_hip(qadc_index*, dim, base_file, chunk_count)      ... and into the 4-bit index (qadc_index_add_vectors)
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -104,6 +105,16 @@ inline unsigned db_add_hip(qadc_adc_index* idx, int dim, const char* base_filena
     return db_add_chunks(base_filename, chunk_count, dim, [&](const io::vectors_chunk& chunk) {
         if (qadc_adc_index_add_vectors(idx, chunk.data.data(), chunk.count, chunk.offset, sum_mode) != QADC_OK)
             throw std::runtime_error(std::string("qadc_adc_index_add_vectors: ") + qadc_last_error());
+    });
+}
+
+// The same into the 4-bit index (qadc_index_add_vectors): every chunk is encoded and appended in device memory with the quantizers
+// the index holds (`dim` = the dimension given to qadc_index_set_pq), labels = index in chunk + the chunk's offset; a flat index
+// writes the chunk at that offset.  No code comes back to the host; call qadc_index_finalize before querying.
+inline unsigned db_add_hip(qadc_index* idx, int dim, const char* base_filename, unsigned chunk_count = 1000000, int sum_mode = 1) {
+    return db_add_chunks(base_filename, chunk_count, dim, [&](const io::vectors_chunk& chunk) {
+        if (qadc_index_add_vectors(idx, chunk.data.data(), chunk.count, chunk.offset, sum_mode) != QADC_OK)
+            throw std::runtime_error(std::string("qadc_index_add_vectors: ") + qadc_last_error());
     });
 }
 

@@ -44,6 +44,8 @@ SYMBOLS = [
     "qadc_adc_index_create_view", "qadc_adc_index_create16", "qadc_adc_encode16_host",
     "qadc_adc_index_add_vectors", "qadc_adc_index_add_vectors_device", "qadc_adc_index_read_partition", "qadc_adc_index_reserve",
     "qadc_adc_index_relocations",
+    "qadc_index_add_vectors", "qadc_index_add_vectors_device", "qadc_index_read_partition", "qadc_index_reserve",
+    "qadc_index_relocations",
 ]
 
 
@@ -70,6 +72,7 @@ class Profile(C.Structure):
 QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h
 QADC_ADC_ENCODE16_CHUNK = 262144   # include/qadc.h: vectors qadc_adc_encode16_host encodes per pass
 QADC_ADC_ADD_CHUNK = 262144        # include/qadc.h: vectors qadc_adc_index_add_vectors encodes and appends per pass
+QADC_INDEX_ADD_CHUNK = 262144      # ... and qadc_index_add_vectors
 
 
 class QadcError(RuntimeError):
@@ -202,6 +205,12 @@ def lib():
         L.qadc_adc_index_reserve.argtypes = [C.c_void_p, C.c_int, u32p]
         L.qadc_adc_index_relocations.argtypes = [C.c_void_p]
         L.qadc_adc_index_relocations.restype = C.c_uint64
+        L.qadc_index_add_vectors.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_int]
+        L.qadc_index_add_vectors_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int]
+        L.qadc_index_read_partition.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u8p, u32p]
+        L.qadc_index_reserve.argtypes = [C.c_void_p, C.c_int, u32p]
+        L.qadc_index_relocations.argtypes = [C.c_void_p]
+        L.qadc_index_relocations.restype = C.c_uint64
         _lib = L
     return _lib
 
@@ -529,6 +538,68 @@ class Index:
         out = np.zeros((count, self.cs), np.uint8)
         _check(lib().qadc_index_read_codes(self._h, part, first, count, _p(out, u8p)))
         return out
+
+    # ---- db_add: encode and append on the GPU with the index's own quantizers (qadc_index_add_vectors) ----
+    def add_vectors(self, vectors, labels_offset=0, sum_mode=1):
+        """vectors [n][dim]: with a coarse quantizer the code of vector i is appended to its nearest centroid's partition with label
+        labels_offset + i (index_db::add_vectors); a flat index writes it at row labels_offset + i of its one partition
+        (flat_db::add_vectors).  The index is not finalized afterwards: call finalize before the next query."""
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim == 1:
+            v = v.reshape(-1, getattr(self, "dim", 1))
+        assert v.ndim == 2 and (v.shape[0] == 0 or v.shape[1] == getattr(self, "dim", v.shape[1]))
+        self.add_vectors_raw(v, v.shape[0], labels_offset, sum_mode)
+
+    def add_vectors_raw(self, vectors, count, labels_offset, sum_mode):
+        """The C call as it is (vectors: a float32 array or None)."""
+        _check(lib().qadc_index_add_vectors(self._h, _p(vectors, f32p), count, labels_offset, sum_mode))
+
+    def add_vectors_device(self, vectors, labels_offset=0, sum_mode=1):
+        """add_vectors for a contiguous float32 torch tensor [n][dim] on the index's device, read where it lies."""
+        import torch
+        if not isinstance(vectors, torch.Tensor) or vectors.ndim != 2:
+            raise TypeError("vectors must be a 2-d torch.Tensor")
+        if vectors.dtype != torch.float32:
+            raise TypeError("vectors must be float32, not %s" % vectors.dtype)
+        if vectors.device.type != "cuda" or vectors.device.index != self.device:
+            raise QadcError("vectors is on %s; the index is on device %d" % (vectors.device, self.device))
+        if not vectors.is_contiguous():
+            raise QadcError("vectors must be contiguous")
+        if vectors.shape[0] and int(vectors.shape[1]) != getattr(self, "dim", int(vectors.shape[1])):
+            raise QadcError("vectors has shape %s, expected [n][%d]" % (tuple(vectors.shape), self.dim))
+        torch.cuda.current_stream(vectors.device).synchronize()          # the vectors are complete before the call
+        _check(lib().qadc_index_add_vectors_device(self._h, vectors.data_ptr(), int(vectors.shape[0]), labels_offset, sum_mode))
+
+    def read_partition(self, part, first=0, count=None):
+        """-> (codes uint8 [n][M/2], labels uint32 [n] or None on an index without labels): rows [first, first + count) of the
+        partition as they lie in device memory (default: all of it)."""
+        if count is None:
+            count = max(self.partition_size(part) - first, 0) if 0 <= part < self.partition_count() else 0
+        codes = np.zeros((count, self.cs), np.uint8)
+        labels = np.zeros(count, np.uint32) if self._labelled() else None
+        _check(lib().qadc_index_read_partition(self._h, part, first, count, _p(codes, u8p), _p(labels, u32p)))
+        return codes, labels
+
+    def _labelled(self):
+        """whether the database has labels: the C call fills labels_out only then (probed on the first row the index holds)"""
+        for part in range(self.partition_count()):
+            if self.partition_size(part):
+                seen = []
+                for fill in (0, 1):
+                    one = np.full(1, fill, np.uint32)
+                    _check(lib().qadc_index_read_partition(self._h, part, 0, 1, None, _p(one, u32p)))
+                    seen.append(int(one[0]))
+                return seen[0] == seen[1]
+        return False
+
+    def reserve(self, capacities):
+        """minimum capacities, in codes, of the first len(capacities) partitions (empty ones are created where the index has fewer)"""
+        c = np.ascontiguousarray(capacities, np.uint32).reshape(-1)
+        _check(lib().qadc_index_reserve(self._h, len(c), _p(c, u32p)))
+
+    def relocations(self):
+        """add_vectors calls that had to move the database to grow it"""
+        return lib().qadc_index_relocations(self._h)
 
     # ---- queries ---------------------------------------------------------------------------
     @staticmethod

@@ -2,7 +2,7 @@
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
   python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
@@ -32,6 +32,10 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             oracle/_ref has it, and the C restatement)
   ivf_search   10^6 clustered 128-d vectors encoded at 16x4 by ivf_encode, K = 256, ma = 24, 1024 queries: search() on the view
             under the host and the device finish, alternated and asserted equal
+  add       not in the default legs: the database build of the 4-bit index itself (pyqadc.Index, 16x4) at the shape of the 8-bit `add`
+            leg: ivf_encode + the stable grouping in numpy + add_partitions, alternated in one process with Index.add_vectors into
+            an empty index and into one reserved to the final sizes; every arm is a whole build from an index with its quantizers
+            set, and the three are first asserted to leave equal partitions
   profile   not timed: five one-query calls on 10^8 codes through the 16x4 view, the 32x4 view and the 8x8 engine, in that order —
             the workload of the rocprofv3 kernel-trace and LDS-counter runs (run it under rocprofv3, one kind of collection per run)
   --bits 16  the engine on 16-bit codes instead (pyqadc.AdcIndex.create16; legs lone,ivf_search), tables read from global memory:
@@ -299,6 +303,8 @@ def view_legs(legs, iters, res):
               "%.2f ms = %.2f us/query" % (med_h * 1e3, med_h * 1e6 / nq, med_d * 1e3, med_d * 1e6 / nq), flush=True)
         view.close()
         src.close()
+    if "add" in legs:
+        add_leg(4, iters, res)
 
 
 def cpu_twin_u16_us(nsq, codes, table, repeat=5):
@@ -352,15 +358,15 @@ def add_leg(bits, iters, res):
     """database build: add_vectors (empty / reserved index) alternated with encode + numpy grouping + add_partitions"""
     rng = np.random.default_rng(1700 + bits)
     n, dim, K = 1_000_000, 128, 256
-    nsq = 8 if bits == 8 else 2
+    nsq = {4: 16, 8: 8, 16: 2}[bits]
     vectors, _ = clustered(rng, n, dim)
     coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, K, replace=False)], 5)
     sample = vectors[rng.choice(n, 1 << bits, replace=False)]
     codebooks = np.ascontiguousarray(sample.reshape(1 << bits, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
-    encode = pyqadc.adc_encode if bits == 8 else pyqadc.adc_encode16
+    encode = {4: pyqadc.ivf_encode, 8: pyqadc.adc_encode, 16: pyqadc.adc_encode16}[bits]
 
     def make():
-        idx = pyqadc.AdcIndex(nsq, 8) if bits == 8 else pyqadc.AdcIndex.create16(nsq)
+        idx = pyqadc.Index(nsq) if bits == 4 else pyqadc.AdcIndex(nsq, 8) if bits == 8 else pyqadc.AdcIndex.create16(nsq)
         idx.set_pq(codebooks)
         idx.set_coarse(coarse)
         return idx
@@ -386,12 +392,16 @@ def add_leg(bits, iters, res):
 
     # the routes build the same database
     a, b = parent_route(), new_route(False)
+    c = new_route(True)
     for k in range(K):
-        (ca, la), (cb, lb) = a.read_partition(k), b.read_partition(k)
+        (ca, la), (cb, lb), (cc, lc) = a.read_partition(k), b.read_partition(k), c.read_partition(k)
         assert np.array_equal(ca, cb) and np.array_equal(la, lb), "partition %d differs between the routes" % k
+        assert np.array_equal(ca, cc) and np.array_equal(la, lc), "partition %d of the reserved index differs" % k
     relocations = b.relocations()
+    assert c.relocations() == 0, "the reserved build relocated"
     a.close()
     b.close()
+    c.close()
 
     def timed_build(route):
         def run():                                                           # the index's creation and release are outside the clock

@@ -776,6 +776,45 @@ int qadc_index_reserve(qadc_index* idx, int part_count, const uint32_t* capaciti
  * database to grow it. */
 uint64_t qadc_index_relocations(const qadc_index* idx);
 
+/* ---- remove by label: vectors out, partitions compacted in place on the GPU.  No reference counterpart:
+ * its index_db only ever push_backs (databases.hpp:270-298).  After a removal the index is the index that would have been built
+ * had the removed vectors never been added, so every query returns what a freshly built index returns, bit for bit. ---- */
+
+/* Removes every row whose label is in labels [count] (host memory) from whichever partitions hold it: all rows of a label that
+ * was added more than once go; duplicates in the list and labels the index does not hold are ignored.  *removed_out (may be
+ * NULL) = the rows removed.  The survivors of a partition keep their relative order and move to the front of its region;
+ * capacities, offsets and buffers are unchanged, nothing relocates (qadc_adc_index_relocations does not move), and a later
+ * qadc_adc_index_add_vectors that fits the freed room appends in place.
+ * QADC_E_ARG, the message says which, checked before the device is touched, the index left as it was: idx NULL; labels NULL with
+ * count > 0; an index that holds rows and is not labelled (a flat index, unlabelled qadc_adc_index_add_partitions: it keys its
+ * vectors by position); a view (remove on the 4-bit index it views, after destroying the view).  count = 0, and a list that hits
+ * no row, change nothing: no byte of the database is written.
+ * Synchronous, on the index's own stream; every copy and memset of the call is asynchronous on that stream.  The call allocates a
+ * bitmap over [smallest label of the list, largest label]: at most 2^32 bits, 512 MiB, freed before it returns.
+ * QADC_E_HIP: a failure before the compaction started leaves the index as it was; after it started the contents of the partitions
+ * that hold a listed label are unspecified, their sizes are the old ones (sizes are committed only when the compaction has
+ * completed), and the index should be rebuilt. */
+int qadc_adc_index_remove_labels(qadc_adc_index* idx, const uint32_t* labels, uint64_t count, uint64_t* removed_out);
+/* The same with d_labels [count] in device memory of the index's device, complete before the call: read where they lie and only
+ * by kernels, so memory of another HIP runtime (a framework's tensor — the keys qadc_adc_search_device returned) is legal.  The
+ * span of the list is known only after a reduction kernel has run (one synchronise more than the host form), so a bitmap that
+ * cannot be allocated is refused (QADC_E_HIP) after the device was touched; no row is touched by then. */
+int qadc_adc_index_remove_labels_device(qadc_adc_index* idx, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out);
+/* qadc_adc_index_remove_labels on the 4-bit index, over its partitions where they lie — in the arena of an index that has grown,
+ * or in the allocations qadc_index_add_partitions made.  Nothing moves between regions: qadc_index_relocations does not move, and a
+ * later qadc_index_add_vectors that fits the freed room of an arena appends in place.
+ * A call that removed at least one row leaves the index not finalized (the start sizes, the partition table and the byte-plane
+ * copies describe the old rows): call qadc_index_finalize before the next query.  Behind every touched partition's new last row
+ * the bytes [n * M/2, align16(n * M/2) + 64) are zero, as qadc_index_add_partitions and qadc_index_add_vectors leave them.
+ * count = 0, and a list that hits no row, change nothing: a finalized index stays finalized and answers queries.
+ * Refused before the device is touched, the index left as it was: what qadc_adc_index_remove_labels refuses, and what
+ * qadc_index_add_vectors refuses of a growing call, with the same codes — QADC_E_STATE while a submission slot is busy;
+ * QADC_E_ARG for a live float-ADC view, an index under qadc_dist_init, a shard or a starts replica, a borrowed partition.
+ * QADC_E_HIP as above; after a failure behind the start of the compaction the index is left not finalized. */
+int qadc_index_remove_labels(qadc_index* idx, const uint32_t* labels, uint64_t count, uint64_t* removed_out);
+/* The same with d_labels [count] in device memory of the index's device, as qadc_adc_index_remove_labels_device. */
+int qadc_index_remove_labels_device(qadc_index* idx, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out);
+
 #ifdef __cplusplus
 }
 #endif

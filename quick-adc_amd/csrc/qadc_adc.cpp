@@ -37,6 +37,7 @@
 #include "../host/worker_pool.hpp"
 #include "qadc_adc_kernels.h"
 #include "qadc_host.h"
+#include "qadc_remove.h"
 
 using qadc::host::fail;
 using qadc::host::DevBuf;
@@ -885,6 +886,41 @@ int add_vectors(qadc_adc_index* idx, const float* vectors, uint64_t count, uint3
     return QADC_OK;
 }
 
+// Remove by label over the regions of the owned database: codes.p + off[p], labels.p + lab_off[p].
+// Capacities, offsets and buffers stay as they are; the sizes are committed once the compaction has completed.
+int remove_labels(qadc_adc_index* idx, const uint32_t* list, uint64_t count, uint64_t* removed_out, bool d_side, const char* call) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (idx->src)
+        return fail(QADC_E_ARG, std::string(call) + ": the index is a view of a 4-bit index and owns no rows: destroy the view and remove "
+                                                    "on the index it views (qadc_index_remove_labels)");
+    if (count && !list) return fail(QADC_E_ARG, std::string(call) + ": labels is null");
+    const bool holds = std::any_of(idx->sizes.begin(), idx->sizes.end(), [](uint32_t n) { return n != 0; });
+    if (holds && idx->labeled != 1)
+        return fail(QADC_E_ARG, std::string(call) + ": the index is not labelled: it keys its vectors by position, and a removal would renumber them");
+    if (removed_out) *removed_out = 0;
+    if (count == 0 || !holds) return QADC_OK;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(idx->device));
+    qadc::host::RemoveJob job;
+    job.stream = idx->stream;
+    job.code_size = idx->code_size();
+    job.sizes = idx->sizes;
+    job.pinned = &idx->h_add;
+    for (size_t p = 0; p < idx->sizes.size(); ++p) {
+        job.codes.push_back(idx->codes.p + idx->off[p]);
+        job.labels.push_back(idx->labels.p + idx->lab_off[p]);
+    }
+    if (int rc = qadc::host::remove_rows(job, list, count, d_side)) {
+        const std::string msg = qadc::host::g_err;
+        (void)hipStreamSynchronize(idx->stream);
+        qadc::host::g_err = msg;
+        return rc;   // (QADC_E_HIP: where the compaction had started, the touched partitions' contents are unspecified)
+    }
+    idx->sizes = job.plan.sizes;
+    if (removed_out) *removed_out = job.plan.removed;
+    return QADC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1078,6 +1114,14 @@ int qadc_adc_index_add_vectors(qadc_adc_index* idx, const float* vectors, uint64
 
 int qadc_adc_index_add_vectors_device(qadc_adc_index* idx, const float* d_vectors, uint64_t count, uint32_t labels_offset, int sum_mode) {
     return add_vectors(idx, d_vectors, count, labels_offset, sum_mode, true, "qadc_adc_index_add_vectors_device");
+}
+
+int qadc_adc_index_remove_labels(qadc_adc_index* idx, const uint32_t* labels, uint64_t count, uint64_t* removed_out) {
+    return remove_labels(idx, labels, count, removed_out, false, "qadc_adc_index_remove_labels");
+}
+
+int qadc_adc_index_remove_labels_device(qadc_adc_index* idx, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out) {
+    return remove_labels(idx, d_labels, count, removed_out, true, "qadc_adc_index_remove_labels_device");
 }
 
 int qadc_adc_index_read_partition(qadc_adc_index* idx, int part, uint32_t first, uint32_t count, uint8_t* codes_out, uint32_t* labels_out) {

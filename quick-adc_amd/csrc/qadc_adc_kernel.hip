@@ -14,7 +14,8 @@
 //   adc_replay_kernel  the device finish: the ordered stream pushed through kv_binheap<unsigned, float>(R) in LDS, one wave per query;
 //   adc_tables_kernel  the float tables of every (query, probe) from query vectors (residual, OPQ rotation, both table forms);
 //   adc_encode_kernel  vectors -> one code byte per sub-quantizer;
-//   adc_encode16_kernel  vectors -> one 16-bit code per sub-quantizer of 65536 centroids (and adc_encode16_merge_kernel).
+//   adc_encode16_kernel  vectors -> one 16-bit code per sub-quantizer of 65536 centroids (and adc_encode16_merge_kernel);
+//   adc_add_* / index_* / remove_*  the database that grows and shrinks in device memory (sections 11.5 to 11.7), further down.
 // The bound rule and why it is exact: DESIGN.md section 11.  Built with -ffp-contract=off and without fast-math (Makefile):
 // every sum rounds like the reference's.
 #include <algorithm>
@@ -963,6 +964,169 @@ __global__ __launch_bounds__(kWG) void adc_fill_words_kernel(uint32_t* __restric
     for (size_t i = (size_t)blockIdx.x * kWG + threadIdx.x; i < n; i += (size_t)gridDim.x * kWG) dst[i] = value;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Remove by label: the rows whose label is in the caller's list leave their partitions, the others
+// keep their order.
+//   remove_minmax_kernel   the smallest and largest label of a list that lies in device memory (reduced in the wave, then across
+//                          the waves through LDS: one atomicMin and one atomicMax per workgroup);
+//   remove_mark_kernel     bit (label - lo) of the bitmap set for every label of the list (atomicOr: duplicates set it twice);
+//   remove_count_kernel    per partition the rows whose label is marked and the first tile that holds one — labels only, one
+//                          atomicAdd and one atomicMin per (partition, tile) that was hit (atomics only count: no position
+//                          depends on their order);
+//   remove_compact_kernel  one workgroup per touched partition walks it front to back and moves the kept rows to the front.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kWG) void remove_minmax_kernel(const uint32_t* __restrict__ list, uint64_t count, uint32_t* __restrict__ lohi) {
+    __shared__ uint32_t wlo[kWG / 64], whi[kWG / 64];
+    uint32_t lo = 0xffffffffu, hi = 0u;
+    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < count; i += (uint64_t)gridDim.x * kWG) {
+        const uint32_t l = list[i];
+        lo = min(lo, l);
+        hi = max(hi, l);
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, d));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, d));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wlo[threadIdx.x >> 6] = lo;
+        whi[threadIdx.x >> 6] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kWG / 64; ++w) {
+            lo = min(lo, wlo[w]);
+            hi = max(hi, whi[w]);
+        }
+        atomicMin(&lohi[0], lo);
+        atomicMax(&lohi[1], hi);
+    }
+}
+
+__global__ __launch_bounds__(kWG) void remove_mark_kernel(const uint32_t* __restrict__ list, uint64_t count, uint32_t lo,
+                                                          uint32_t* __restrict__ bitmap) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < count; i += (uint64_t)gridDim.x * kWG) {
+        const uint32_t d = list[i] - lo;
+        atomicOr(&bitmap[d >> 5], 1u << (d & 31u));
+    }
+}
+
+// The label's bit, without a branch so that the loads of several rows go out together: the bitmap word of a label inside
+// [lo, lo + last] (word 0 for one outside: the bitmap has one word at least), then the test.
+__device__ __forceinline__ uint32_t remove_word(const uint32_t* __restrict__ bitmap, uint32_t lo, uint32_t last, uint32_t label) {
+    const uint32_t d = label - lo;
+    return bitmap[d <= last ? d >> 5 : 0u];
+}
+__device__ __forceinline__ bool remove_marked(uint32_t word, uint32_t lo, uint32_t last, uint32_t label) {
+    const uint32_t d = label - lo;
+    return d <= last && ((word >> (d & 31u)) & 1u);
+}
+
+// Partition p = blockIdx.y, y-strided; its tiles of kRemoveTile rows x-strided over grid.x; a thread tests one bit a round.
+__global__ __launch_bounds__(kWG) void remove_count_kernel(const RemoveSrc* __restrict__ src, int parts, const uint32_t* __restrict__ bitmap,
+                                                           uint32_t lo, uint32_t last, uint32_t* __restrict__ hits, uint32_t* __restrict__ first) {
+    __shared__ uint32_t wsum[kWG / 64];
+    const uint32_t tid = threadIdx.x;
+    for (int p = (int)blockIdx.y; p < parts; p += (int)gridDim.y) {
+        const RemoveSrc m = src[p];
+        const uint64_t tiles = ((uint64_t)m.n + kRemoveTile - 1) / kRemoveTile;
+        for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {          // (the same trip count for every thread of the workgroup)
+            uint32_t c = 0;                                                  // rows of the tile that go, seen by this wave
+#pragma unroll 4
+            for (int r = 0; r < kRemoveTile / kWG; ++r) {
+                const uint64_t row = t * kRemoveTile + (uint32_t)r * kWG + tid;
+                const uint32_t label = row < m.n ? m.labels[row] : 0u;
+                const bool hit = row < m.n && remove_marked(remove_word(bitmap, lo, last, label), lo, last, label);
+                c += (uint32_t)__popcll(__ballot(hit));
+            }
+            if ((tid & 63) == 0) wsum[tid >> 6] = c;
+            __syncthreads();
+            if (tid == 0) {
+                uint32_t sum = 0;
+                for (int w = 0; w < kWG / 64; ++w) sum += wsum[w];
+                if (sum) {
+                    atomicAdd(&hits[p], sum);
+                    atomicMin(&first[p], (uint32_t)t);
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <int BYTES> struct RowWord;                            // a code row as one dword, dwordx2 or dwordx4 register value
+template <> struct RowWord<4> { using type = uint32_t; };
+template <> struct RowWord<8> { typedef uint32_t type __attribute__((ext_vector_type(2))); };
+template <> struct RowWord<16> { typedef uint32_t type __attribute__((ext_vector_type(4))); };
+
+// One workgroup of kRemoveWG threads per touched partition.  An iteration takes one tile: every thread loads the labels and code
+// words of its kRemoveRows rows (row = tile + j * kRemoveWG + thread, so a wave's loads are contiguous) into registers and tests
+// their bits; the rank of a kept row among the kept rows of the tile is its rank in the wave's ballot (mbcnt) plus the kept rows
+// of the (j, wave) pairs before it — kRemoveRows * 16 = 64 counts in LDS, one per lane, summed by every wave for itself — plus the
+// write position w the tiles before left.  Only behind the __syncthreads() that follows the loads are rows stored, to [w, w + kept).
+//
+// Why in place is safe: w <= the tile's first row, so the stores of an iteration fall inside rows this
+// workgroup has loaded — earlier tiles, and this tile, whose loads the barrier has completed; the next tile's loads touch rows no
+// store of this iteration reaches; no workgroup reads or writes another partition's region.  The counts are double-buffered: a wave
+// that runs ahead into the next iteration writes the other half.
+template <int BYTES>
+__global__ __launch_bounds__(kRemoveWG) void remove_compact_kernel(const RemovePart* __restrict__ parts, const uint32_t* __restrict__ bitmap,
+                                                                   uint32_t lo, uint32_t last) {
+    static_assert(kRemoveRows * (kRemoveWG / 64) == 64, "one lane per (row slot, wave) count");
+    __shared__ uint32_t wcount[2][64];
+    const RemovePart m = parts[blockIdx.x];
+    using Row = typename RowWord<BYTES>::type;
+    Row* rows = reinterpret_cast<Row*>(m.codes);
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1;
+    uint32_t w = m.first_tile * (uint32_t)kRemoveTile;                      // the rows before the first tile stay where they are
+    int buf = 0;
+    for (uint64_t t0 = (uint64_t)m.first_tile * kRemoveTile; t0 < m.n; t0 += kRemoveTile, buf ^= 1) {
+        Row c[kRemoveRows];
+        uint32_t l[kRemoveRows], word[kRemoveRows], rank[kRemoveRows];
+        bool keep[kRemoveRows];
+#pragma unroll
+        for (int j = 0; j < kRemoveRows; ++j) {
+            const uint64_t r = t0 + (uint32_t)j * kRemoveWG + tid;
+            const uint64_t in = r < m.n ? r : m.n - 1;                       // (past the end: the last row again, never kept)
+            l[j] = m.labels[in];
+            c[j] = rows[in];
+        }
+#pragma unroll
+        for (int j = 0; j < kRemoveRows; ++j) word[j] = remove_word(bitmap, lo, last, l[j]);
+#pragma unroll
+        for (int j = 0; j < kRemoveRows; ++j) {
+            const uint64_t r = t0 + (uint32_t)j * kRemoveWG + tid;
+            keep[j] = r < m.n && !remove_marked(word[j], lo, last, l[j]);
+            const unsigned long long kept = __ballot(keep[j]);
+            rank[j] = (uint32_t)__popcll(kept & below);
+            if (lane == 0) wcount[buf][j * (kRemoveWG / 64) + wave] = (uint32_t)__popcll(kept);
+        }
+        __syncthreads();
+        uint32_t incl = wcount[buf][lane];                                   // inclusive sum of the 64 counts, in every wave
+        const uint32_t own = incl;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+            if (lane >= (uint32_t)d) incl += up;
+        }
+        const uint32_t excl = incl - own;
+        const uint32_t total = (uint32_t)__shfl((int)incl, 63);
+#pragma unroll
+        for (int j = 0; j < kRemoveRows; ++j) {
+            const uint32_t before = (uint32_t)__shfl((int)excl, j * (kRemoveWG / 64) + (int)wave);
+            const uint64_t r = t0 + (uint32_t)j * kRemoveWG + tid;
+            const uint32_t dst = w + before + rank[j];
+            if (keep[j] && dst != r) {                                       // (a row in front of the first removed one stays)
+                rows[dst] = c[j];
+                m.labels[dst] = l[j];
+            }
+        }
+        w += total;
+    }
+    if (tid * 8u < m.zero_bytes)                                             // the zero tail behind the new last row: dwordx2 each
+        *reinterpret_cast<uint2*>(m.codes + (uint64_t)w * BYTES + tid * 8u) = make_uint2(0u, 0u);
+}
+
 }  // namespace
 
 hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const int32_t* assign,
@@ -1175,6 +1339,43 @@ hipError_t launch_index_zero_tails(uint8_t* d_codes, const uint64_t* d_off, cons
     if (code_bytes != 8 && code_bytes != 16) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)(((uint64_t)parts * 16 + kWG - 1) / kWG);
     hipLaunchKernelGGL(index_zero_tails_kernel, dim3(grid), dim3(kWG), 0, s, d_codes, d_off, d_sizes, parts, code_bytes);
+    return hipGetLastError();
+}
+
+hipError_t launch_remove_minmax(const uint32_t* d_list, uint64_t count, uint32_t* d_lohi, hipStream_t s) {
+    if (count == 0) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)std::min<uint64_t>((count + 4 * kWG - 1) / (4 * kWG), 1024);
+    hipLaunchKernelGGL(remove_minmax_kernel, dim3(grid), dim3(kWG), 0, s, d_list, count, d_lohi);
+    return hipGetLastError();
+}
+
+hipError_t launch_remove_mark(const uint32_t* d_list, uint64_t count, uint32_t lo, uint32_t* d_bitmap, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<uint64_t>((count + 4 * kWG - 1) / (4 * kWG), 4096);
+    hipLaunchKernelGGL(remove_mark_kernel, dim3(grid), dim3(kWG), 0, s, d_list, count, lo, d_bitmap);
+    return hipGetLastError();
+}
+
+hipError_t launch_remove_count(const RemoveSrc* d_src, int parts, uint32_t max_size, const uint32_t* d_bitmap, uint32_t lo, uint32_t last,
+                               uint32_t* d_hits, uint32_t* d_first, hipStream_t s) {
+    if (parts <= 0 || max_size == 0) return hipSuccess;
+    // grid.y walks the partitions, grid.x the tiles of the largest one, about 65536 workgroups at most (adc_move_kernel's shape)
+    const unsigned gy = (unsigned)std::min(parts, 65535);
+    const uint64_t tiles = ((uint64_t)max_size + kRemoveTile - 1) / kRemoveTile;
+    const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, std::max(1u, 65536u / gy)));
+    hipLaunchKernelGGL(remove_count_kernel, dim3(gx, gy), dim3(kWG), 0, s, d_src, parts, d_bitmap, lo, last, d_hits, d_first);
+    return hipGetLastError();
+}
+
+hipError_t launch_remove_compact(const RemovePart* d_parts, uint32_t touched, int code_bytes, const uint32_t* d_bitmap, uint32_t lo,
+                                 uint32_t last, hipStream_t s) {
+    if (touched == 0) return hipSuccess;
+    if ((code_bytes != 4 && code_bytes != 8 && code_bytes != 16) || touched > 0x7fffffffu) return hipErrorInvalidValue;
+#define QADC_RC(B) hipLaunchKernelGGL((remove_compact_kernel<B>), dim3(touched), dim3(kRemoveWG), 0, s, d_parts, d_bitmap, lo, last)
+    if (code_bytes == 4) QADC_RC(4);
+    else if (code_bytes == 8) QADC_RC(8);
+    else QADC_RC(16);
+#undef QADC_RC
     return hipGetLastError();
 }
 

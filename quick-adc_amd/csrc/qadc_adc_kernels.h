@@ -153,5 +153,41 @@ hipError_t launch_index_move(const IndexMove* d_moves, int parts, int code_bytes
 hipError_t launch_index_zero_tails(uint8_t* d_codes, const uint64_t* d_off, const uint32_t* d_sizes, uint32_t parts, int code_bytes,
                                    hipStream_t s);
 
+// ---- remove by label: the partitions of both engines compacted in place (csrc/qadc_remove.h).  The labels
+// of the list are marked in a bitmap over [lo, lo + last]; a row goes when its label's bit is set. ----
+constexpr int kRemoveWG = 1024;       // threads of the one workgroup that compacts a partition
+constexpr int kRemoveRows = 4;        // rows a thread of it holds in registers per iteration (the loads in flight: 4 code words, 4 labels)
+constexpr int kRemoveTile = 4096;     // rows of one iteration of remove_compact_kernel, and of one count of remove_count_kernel
+static_assert(kRemoveTile == kRemoveWG * kRemoveRows, "a tile is what one workgroup holds in registers");
+
+// lohi[0] = min(lohi[0], every label), lohi[1] = max(lohi[1], every label): lohi preset to {2^32 - 1, 0} by the caller.  count > 0.
+hipError_t launch_remove_minmax(const uint32_t* d_list, uint64_t count, uint32_t* d_lohi, hipStream_t s);
+// bit (label - lo) of d_bitmap set for every label of the list; every label lies in [lo, lo + 2^32) of a bitmap zeroed by the caller.
+hipError_t launch_remove_mark(const uint32_t* d_list, uint64_t count, uint32_t lo, uint32_t* d_bitmap, hipStream_t s);
+// One partition as the count reads it: its labels and rows held.
+struct RemoveSrc {
+    const uint32_t* labels;
+    uint32_t n;
+    uint32_t pad;
+};
+// d_hits[p] += rows of partition p whose label is marked; d_first[p] = min(d_first[p], the first tile of kRemoveTile rows that
+// holds one).  d_hits zeroed, d_first preset to 2^32 - 1 by the caller.  max_size: the largest n.
+hipError_t launch_remove_count(const RemoveSrc* d_src, int parts, uint32_t max_size, const uint32_t* d_bitmap, uint32_t lo, uint32_t last,
+                               uint32_t* d_hits, uint32_t* d_first, hipStream_t s);
+// One touched partition of the compaction: its n rows and labels where they lie, the tile to start at (the rows before it hold no
+// marked label), and the bytes to zero behind the new last row (a multiple of 8; 0: none — the float-ADC index keeps none).
+struct RemovePart {
+    uint8_t* codes;
+    uint32_t* labels;
+    uint32_t n;
+    uint32_t first_tile;
+    uint32_t zero_bytes;
+    uint32_t pad;
+};
+// Compacts every partition of the table in place, one workgroup each: the rows whose label is not marked move to the front in their
+// old order, labels with them.  code_bytes 4, 8 or 16; touched <= 2^31 - 1.
+hipError_t launch_remove_compact(const RemovePart* d_parts, uint32_t touched, int code_bytes, const uint32_t* d_bitmap, uint32_t lo,
+                                 uint32_t last, hipStream_t s);
+
 }  // namespace adc
 }  // namespace qadc

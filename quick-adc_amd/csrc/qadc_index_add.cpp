@@ -1,6 +1,6 @@
 // db_add on the 4-bit index: qadc_index_add_vectors / _add_vectors_device encode vectors with the
 // quantizers the index holds (FeederState) and append the codes to partitions that grow in device memory; qadc_index_reserve,
-// _read_partition and _relocations complete the set.  index_db::add_vectors (databases.hpp:270-298) with a coarse quantizer,
+// _read_partition and _relocations complete the set, and qadc_index_remove_labels (section 11.7) takes rows out again.  index_db::add_vectors (databases.hpp:270-298) with a coarse quantizer,
 // flat_db::add_vectors (136-156) without.
 //
 // The encoder is the chain of qadc_ivf_encode_host_mode(encode_form = 1) — launch_coarse_assign, launch_residual_rotate,
@@ -13,6 +13,7 @@
 
 #include "../host/index_append_plan.hpp"
 #include "qadc_adc_kernels.h"
+#include "qadc_remove.h"
 
 using namespace qadc;
 using namespace qadc::host;
@@ -344,9 +345,61 @@ int add_vectors(qadc_index* idx, const float* vectors, uint64_t count, uint32_t 
     return QADC_OK;
 }
 
+// Remove by label over Part::d_codes / d_labels, in the arena or in allocations of their own: nothing
+// moves between regions, so neither the arena nor relocations() changes.  A call that removed a row leaves the index not
+// finalized — the start sizes, the partition table and the byte-plane copies describe the old rows — with the zeroed span of
+// alloc_part / index_padded_end behind every touched partition's new last row.
+int remove_labels(qadc_index* idx, const uint32_t* list, uint64_t count, uint64_t* removed_out, bool d_side, const char* call) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (int rc = refuse(idx, call)) return rc;
+    if (count && !list) return fail(QADC_E_ARG, std::string(call) + ": labels is null");
+    const bool holds = std::any_of(idx->parts.begin(), idx->parts.end(), [](const Part& p) { return p.n != 0; });
+    if (holds && idx->labeled != 1)
+        return fail(QADC_E_ARG, std::string(call) + ": the index is not labelled: it keys its vectors by position, and a removal would renumber them");
+    if (removed_out) *removed_out = 0;
+    if (count == 0 || !holds) return QADC_OK;
+    DeviceGuard guard;
+    if (int rc = use_device(idx)) return rc;
+    RemoveJob job;
+    job.stream = idx->stream;
+    job.code_size = idx->cs;
+    job.zero_tail = true;
+    job.pinned = &idx->arena.h_add;
+    for (const Part& pt : idx->parts) {
+        job.codes.push_back(pt.d_codes);
+        job.labels.push_back(pt.d_labels);
+        job.sizes.push_back(pt.n);
+    }
+    if (int rc = remove_rows(job, list, count, d_side)) {
+        const std::string msg = g_err;
+        (void)hipStreamSynchronize(idx->stream);
+        if (job.wrote) idx->finalized = false;   // (the touched partitions' contents are unspecified: nothing recorded of them is scanned)
+        g_err = msg;
+        return rc;
+    }
+    if (job.plan.removed == 0) return QADC_OK;   // no row was hit: nothing was written, a finalized index stays finalized
+    for (const RemoveEntry& e : job.plan.touched) {   // (as bind_parts sets them)
+        Part& pt = idx->parts[e.part];
+        pt.n = e.n_new;
+        pt.global_n = pt.n;
+        pt.starts_cap = pt.n;
+    }
+    idx->finalized = false;
+    if (removed_out) *removed_out = job.plan.removed;
+    return QADC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int qadc_index_remove_labels(qadc_index* idx, const uint32_t* labels, uint64_t count, uint64_t* removed_out) {
+    return remove_labels(idx, labels, count, removed_out, false, "qadc_index_remove_labels");
+}
+
+int qadc_index_remove_labels_device(qadc_index* idx, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out) {
+    return remove_labels(idx, d_labels, count, removed_out, true, "qadc_index_remove_labels_device");
+}
 
 int qadc_index_add_vectors(qadc_index* idx, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode) {
     return add_vectors(idx, vectors, count, labels_offset, sum_mode, false, "qadc_index_add_vectors");

@@ -46,6 +46,7 @@ SYMBOLS = [
     "qadc_adc_index_relocations",
     "qadc_index_add_vectors", "qadc_index_add_vectors_device", "qadc_index_read_partition", "qadc_index_reserve",
     "qadc_index_relocations",
+    "qadc_adc_index_remove_labels", "qadc_adc_index_remove_labels_device", "qadc_index_remove_labels", "qadc_index_remove_labels_device",
 ]
 
 
@@ -211,6 +212,9 @@ def lib():
         L.qadc_index_reserve.argtypes = [C.c_void_p, C.c_int, u32p]
         L.qadc_index_relocations.argtypes = [C.c_void_p]
         L.qadc_index_relocations.restype = C.c_uint64
+        for name in ("qadc_adc_index_remove_labels", "qadc_index_remove_labels"):
+            getattr(L, name).argtypes = [C.c_void_p, u32p, C.c_uint64, u64p]
+            getattr(L, name + "_device").argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p]
         _lib = L
     return _lib
 
@@ -222,6 +226,23 @@ def _p(a, t):
 def _check(rc):
     if rc != 0:
         raise QadcError("qadc error %d: %s" % (rc, lib().qadc_last_error().decode()))
+
+
+def _label_tensor(t, device):
+    """the list of a remove_labels_device call: a contiguous 1-d int32 torch tensor on `device` carrying the labels' uint32 bits"""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("labels must be a torch.Tensor, not %s" % type(t).__name__)
+    if t.dtype != torch.int32:
+        raise TypeError("labels must be int32 (the uint32 bits, as search_device returns keys), not %s" % t.dtype)
+    if t.device.type != "cuda" or t.device.index != device:
+        raise QadcError("labels is on %s; the index is on device %d" % (t.device, device))
+    if t.ndim != 1:
+        raise QadcError("labels has shape %s, expected [n]" % (tuple(t.shape),))
+    if not t.is_contiguous():
+        raise QadcError("labels must be contiguous")
+    torch.cuda.current_stream(t.device).synchronize()                    # the list is complete before the call
+    return t
 
 
 def replay_i8(keys, vals, R, sentinel=False):
@@ -600,6 +621,28 @@ class Index:
     def relocations(self):
         """add_vectors calls that had to move the database to grow it"""
         return lib().qadc_index_relocations(self._h)
+
+    # ---- remove by label: the partitions compacted in place on the GPU (qadc_index_remove_labels) ----
+    def remove_labels(self, labels):
+        """Removes every row whose label is in `labels` (anything np.asarray(..., np.uint32) accepts) from whichever partitions
+        hold it; the survivors keep their order.  -> the number of rows removed.  A call that removed a row
+        leaves the index not finalized: call finalize before the next query."""
+        l = np.ascontiguousarray(np.asarray(labels, np.uint32).reshape(-1))
+        return self.remove_labels_raw(l, l.size)
+
+    def remove_labels_raw(self, labels, count):
+        """The C call as it is (labels: a uint32 array or None)."""
+        removed = C.c_uint64(0)
+        _check(lib().qadc_index_remove_labels(self._h, _p(labels, u32p), count, C.byref(removed)))
+        return int(removed.value)
+
+    def remove_labels_device(self, labels):
+        """remove_labels for a contiguous 1-d int32 torch tensor on the index's device that carries the labels' uint32 bits — the
+        form in which search_device returns keys — read where it lies."""
+        t = _label_tensor(labels, self.device)
+        removed = C.c_uint64(0)
+        _check(lib().qadc_index_remove_labels_device(self._h, t.data_ptr(), int(t.shape[0]), C.byref(removed)))
+        return int(removed.value)
 
     # ---- queries ---------------------------------------------------------------------------
     @staticmethod
@@ -1027,6 +1070,27 @@ class AdcIndex:
     def relocations(self):
         """add_vectors calls that had to move the database to grow it"""
         return lib().qadc_adc_index_relocations(self._h)
+
+    # ---- remove by label: the partitions compacted in place on the GPU (qadc_adc_index_remove_labels) ----
+    def remove_labels(self, labels):
+        """Removes every row whose label is in `labels` (anything np.asarray(..., np.uint32) accepts) from whichever partitions
+        hold it; the survivors keep their order.  -> the number of rows removed."""
+        l = np.ascontiguousarray(np.asarray(labels, np.uint32).reshape(-1))
+        return self.remove_labels_raw(l, l.size)
+
+    def remove_labels_raw(self, labels, count):
+        """The C call as it is (labels: a uint32 array or None)."""
+        removed = C.c_uint64(0)
+        _check(lib().qadc_adc_index_remove_labels(self._h, _p(labels, u32p), count, C.byref(removed)))
+        return int(removed.value)
+
+    def remove_labels_device(self, labels):
+        """remove_labels for a contiguous 1-d int32 torch tensor on the index's device that carries the labels' uint32 bits — the
+        form in which search_device returns keys — read where it lies."""
+        t = _label_tensor(labels, self.device)
+        removed = C.c_uint64(0)
+        _check(lib().qadc_adc_index_remove_labels_device(self._h, t.data_ptr(), int(t.shape[0]), C.byref(removed)))
+        return int(removed.value)
 
     def reruns(self):
         """query calls on this index that were re-run because a candidate region overflowed"""

@@ -1,8 +1,8 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
@@ -25,6 +25,13 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             the route without it: adc_encode (adc_encode16), the stable grouping by assign in numpy, add_partitions.  The partitions
             of the routes are asserted equal.  Under rocprofv3 --kernel-trace --stats the same leg gives the dispatch kernels' time
             beside the encoder's
+  remove    remove by label (not in the default legs; also under --bits 4, on the 4-bit index itself at 16x4): 10^6 clustered 128-d
+            vectors put into K = 256 partitions by add_vectors, 8x8.  remove_labels of a random 1 %, 10 % and 50 % of the labels, call
+            to return, alternated in one process with the route without it: read_partition of every partition, np.isin on the host,
+            add_partitions into a new index (on the 4-bit index without the finalize either route needs, and without the move into the
+            arena only the route without the call needs).  Every arm starts from a fresh copy of the database, built outside the
+            clock; the two routes' partitions are first asserted equal.  Then 10 % at K = 8: a few very long partitions, which the
+            call compacts with one workgroup each
   --bits 4   the float-ADC view of a 4-bit index instead (pyqadc.AdcIndex.view_of; legs lone,ivf_search):
   lone      one synchronous query on 10^6 and on 10^8 codes at 16x4 and 32x4: median and range of the call, codes/s, the share
             of the HBM roofline at 8 B / 16 B per code; at 16x4 alternated with the 8x8 engine on a list of the same n (the
@@ -305,6 +312,8 @@ def view_legs(legs, iters, res):
         src.close()
     if "add" in legs:
         add_leg(4, iters, res)
+    if "remove" in legs:
+        remove_leg(4, iters, res)
 
 
 def cpu_twin_u16_us(nsq, codes, table, repeat=5):
@@ -430,6 +439,78 @@ def add_leg(bits, iters, res):
           "= %.2fx / %.2fx the route without it" % (nsq, bits, n, K, med["parent_route"], med["add_vectors_empty"], relocations,
                                                      med["add_vectors_reserved"], med["parent_route"] / med["add_vectors_empty"],
                                                      med["parent_route"] / med["add_vectors_reserved"]), flush=True)
+
+
+def remove_leg(bits, iters, res):
+    """remove_labels alternated with the route without it: read_partition of every partition, the filter on the host, add_partitions"""
+    rng = np.random.default_rng(1800 + bits)
+    n, dim = 1_000_000, 128
+    nsq = {4: 16, 8: 8}[bits]
+    vectors, _ = clustered(rng, n, dim)
+    coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, 256, replace=False)], 5)
+    sample = vectors[rng.choice(n, 1 << bits, replace=False)]
+    codebooks = np.ascontiguousarray(sample.reshape(1 << bits, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
+
+    def make():
+        return pyqadc.Index(nsq) if bits == 4 else pyqadc.AdcIndex(nsq, 8)
+
+    def read_all(idx):
+        return [idx.read_partition(k) for k in range(idx.partition_count())]
+
+    for K, fractions in ((256, (0.01, 0.1, 0.5)), (8, (0.1,))):                   # K = 8: a few very long partitions, one workgroup each
+        src = make()
+        src.set_pq(codebooks)
+        src.set_coarse(coarse[:K])
+        src.add_vectors(vectors)
+        base = read_all(src)                                                     # the database every arm starts from
+        src.close()
+        longest = max(len(c) for c, _ in base)
+
+        def fresh():
+            idx = make()
+            idx.add_partitions([c for c, _ in base], [l for _, l in base])
+            return idx
+
+        for f in fractions:
+            removed = rng.choice(n, int(f * n), replace=False).astype(np.uint32)
+
+            def new_route(idx):
+                assert idx.remove_labels(removed) == len(removed)
+                return idx
+
+            def old_route(idx):
+                parts = read_all(idx)
+                keep = [~np.isin(l, removed) for _, l in parts]
+                out = make()
+                out.add_partitions([c[m] for (c, _), m in zip(parts, keep)], [l[m] for (_, l), m in zip(parts, keep)])
+                return out
+
+            a, b = fresh(), fresh()                                              # both ends hold the same partitions
+            got, want = read_all(new_route(a)), read_all(old_route(b))
+            for k in range(K):
+                assert np.array_equal(got[k][0], want[k][0]) and np.array_equal(got[k][1], want[k][1]), "partition %d differs between the routes" % k
+            a.close()
+            b.close()
+            times = {"remove_labels": [], "read_filter_add_partitions": []}
+            for it in range(1 + max(3, iters // 2)):                             # one warm-up round, then the arms in turn
+                for name, route in (("remove_labels", new_route), ("read_filter_add_partitions", old_route)):
+                    idx = fresh()                                                # (outside the clock, as its release is)
+                    t0 = time.perf_counter()
+                    out = route(idx)
+                    t = time.perf_counter() - t0
+                    if out is not idx:
+                        out.close()
+                    idx.close()
+                    if it:
+                        times[name].append(t)
+            tag = "remove_%dx%d_K%d_%g" % (nsq, bits, K, f)
+            for name, ts in times.items():
+                res["%s_%s_ms_median_min_max" % (tag, name)] = [float(np.median(ts)) * 1e3, float(np.min(ts)) * 1e3, float(np.max(ts)) * 1e3]
+            res[tag + "_longest_partition"] = int(longest)
+            med_new, med_old = (float(np.median(times[k])) for k in ("remove_labels", "read_filter_add_partitions"))
+            print("remove %dx%d, %.0e codes in K = %d partitions (longest %d), %g of the labels: remove_labels %.3f ms; read_partition of every "
+                  "partition + np.isin + add_partitions into a new index %.3f ms = %.1fx the call"
+                  % (nsq, bits, n, K, longest, f, med_new * 1e3, med_old * 1e3, med_old / med_new), flush=True)
 
 
 def encode16_leg(iters, res):
@@ -701,6 +782,8 @@ def main():
         search_legs(legs, a.iters, res)
     if "add" in legs:
         add_leg(8, a.iters, res)
+    if "remove" in legs:
+        remove_leg(8, a.iters, res)
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -305,6 +305,30 @@ int qadc_coarse_assign_host(const float* queries, int nq, const float* coarse, i
 int qadc_kmeans_iterations_host_mode(const float* vectors, uint64_t n, int dim, int K, float* centroids, int iters,
                                      int32_t* assign_out, int div_mode, int device_id);
 
+/* Learning the product quantizer: `iters` rounds of k-means in every sub-space at once, on a learning set held once in device
+ * memory.  Sub-quantizer m of sq_count (dsub = dim / sq_count) ends as kmeans_fast_iterations_thread (databases.cpp:50-90)
+ * applied to the n x dsub matrix of columns [m dsub, (m + 1) dsub), started from codebooks[m]: the bits that
+ * qadc_kmeans_iterations_host_mode returns for that slice.  A round assigns with the encoder of the index the codebooks are for
+ * (sq_bits 4 with sq_count 16 or 32: qadc_pq_encode's reference form; sq_bits 8 with sq_count 4, 8 or 16: qadc_adc_encode_host's),
+ * then centroid = (its members' sub-vectors summed in ascending vector index into one running float from 0.0f) * (1.0f / count)
+ * (div_mode 1, as the reference is compiled; 0: divided by the count, as its source reads).  An empty cluster becomes NaN and
+ * stays NaN, as in the reference; nothing repairs it.  sum_mode: the norms' grouping, as for the encoders.
+ * K_coarse > 0: the learning set is first made residuals to the nearest of coarse [K_coarse][dim] (find_k_neighbors, k = 1);
+ * rotation [dim][dim] or NULL: ... and rotated (rotated[r] = sum_c x[c] * rotation[r][c]) — what index_db::add_vectors hands to
+ * the quantizer.  The caller seeds (the reference leaves learning to an outside project): codebooks [sq_count][2^sq_bits][dsub] in
+ * and out; iters == 0 returns them untouched and writes no code.  codes_out (nullable, host memory): the last round's
+ * assignment in the encoder's layout ([n][sq_count / 2] packed nibbles, or [n][sq_count] bytes) — the codes under the codebooks
+ * of BEFORE the last update.  empty_out (nullable): centroids with a NaN component at return.
+ * Limits: the learning set is resident for the call; 0 < n < 2^32; dim <= 2048 at 4 bits, <= 4096 at 8 bits (the encoders').
+ * sq_bits 16 is refused (QADC_E_ARG): a follow-up.  qadc_pq_train_device: the same with the vectors already in device memory
+ * (read only, by kernels); every other pointer is host memory. */
+int qadc_pq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                       const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                       int sum_mode, int device_id);
+int qadc_pq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                         const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                         int sum_mode, int device_id);
+
 /* Host-only helper (no GPU involved): push (keys[i], vals[i]), i = 0..n-1, in order into an empty
  * heap of capacity R with kv_binheap<unsigned,int8_t>::push semantics (binheap.hpp:75-116), after
  * an optional (0,127) sentinel (db_query_4.cpp:276), and return the heap arrays.  This is the

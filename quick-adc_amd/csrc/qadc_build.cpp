@@ -2,6 +2,10 @@
 // index_db::add_vectors (databases.hpp:270-298) and the k-means iterations (databases.cpp:50-90).  Stateless: host buffers
 // (or device pointers) in and out, any device.
 #include "qadc_host.h"
+#include "qadc_adc_kernels.h"   // launch_adc_encode: the assignment step of qadc_pq_train at 8 bits
+#include "qadc_pq_train.h"
+
+#include <cmath>
 
 using namespace qadc;
 using namespace qadc::host;
@@ -187,6 +191,126 @@ int qadc_kmeans_iterations_host_mode(const float* vectors, uint64_t n, int dim, 
     HIPCHECK(hipMemcpy(centroids, d_c, sizeof(float) * (size_t)K * dim, hipMemcpyDeviceToHost));
     if (assign_out) HIPCHECK(hipMemcpy(assign_out, d_assign, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     return QADC_OK;
+}
+
+/* ---- PQ training: `iters` rounds of k-means in every sub-space at once.  A round = the encoder the index
+   of that shape uses (launch_pq_encode at 4 bits, launch_adc_encode at 8: find_k_neighbors with k = 1 per sub-quantizer, norms of the
+   moved centroids recomputed) and one launch_pq_train_update over all sq_count * 2^bits centroids. ---- */
+extern "C++" {
+namespace {
+// the argument checks of both entry points: before the first HIP call
+int pq_train_check(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                   const float* codebooks, int iters, int div_mode, int sum_mode) {
+    if (sq_bits == 16)
+        return fail(QADC_E_ARG, "sq_bits 16 is not trained here (a follow-up: 65536 centroids per sub-quantizer need the sorted update); sq_bits 4 or 8");
+    if (sq_bits != 4 && sq_bits != 8) return fail(QADC_E_ARG, "sq_bits must be 4 or 8");
+    if (sq_bits == 4 && sq_count != 16 && sq_count != 32) return fail(QADC_E_ARG, "sq_bits 4 takes sq_count 16 or 32 (the 4-bit index's shapes)");
+    if (sq_bits == 8 && sq_count != 4 && sq_count != 8 && sq_count != 16)
+        return fail(QADC_E_ARG, "sq_bits 8 takes sq_count 4, 8 or 16 (the float-ADC index's shapes)");
+    if (dim <= 0 || dim % sq_count != 0) return fail(QADC_E_ARG, "dim must be a positive multiple of sq_count");
+    const int max_dim = sq_bits == 4 ? kPqEncodeMaxDim : adc::kAdcMaxDim;
+    if (dim > max_dim) return fail(QADC_E_ARG, "dim must be <= " + std::to_string(max_dim) + " (the encoder's limit at " + std::to_string(sq_bits) + " bits)");
+    PqTrainPlan plan;
+    if (!pq_train_plan(sq_count, sq_bits, dim, &plan))
+        return fail(QADC_E_ARG, "dim / sq_count must be <= " + std::to_string(kPqTrainMaxDsub) + " (the update kernel's staged window)");
+    if (!vectors || !codebooks) return fail(QADC_E_ARG, "vectors and codebooks must not be NULL");
+    if (n == 0 || n >= (1ull << 32)) return fail(QADC_E_ARG, "need 0 < n < 2^32 vectors");
+    if (iters < 0) return fail(QADC_E_ARG, "iters must be >= 0");
+    if (K_coarse < 0 || (K_coarse > 0 && !coarse)) return fail(QADC_E_ARG, "K_coarse > 0 needs the coarse centroids");
+    if ((div_mode != 0 && div_mode != 1) || (sum_mode != 0 && sum_mode != 1)) return fail(QADC_E_ARG, "div_mode and sum_mode are 0 or 1");
+    return QADC_OK;
+}
+
+uint64_t nan_rows(const float* cb, size_t rows, int ds) {
+    uint64_t bad = 0;
+    for (size_t r = 0; r < rows; ++r) {
+        bool nan = false;
+        for (int d = 0; d < ds; ++d) nan = nan || std::isnan(cb[r * ds + d]);
+        bad += nan;
+    }
+    return bad;
+}
+
+// d_vectors: the learning set in device memory (read by kernels only: it may belong to another HIP runtime of the process)
+int pq_train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                 const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode, int sum_mode,
+                 ScratchFree& mem) {
+    const int ds = dim / sq_count;
+    const size_t rows = (size_t)sq_count << sq_bits, code_bytes = sq_bits == 4 ? sq_count / 2 : sq_count;
+    float *d_cb = nullptr, *d_cbnorm = nullptr, *d_rot = nullptr, *d_coarse = nullptr, *d_x = nullptr, *d_dist = nullptr;
+    int32_t* d_assign = nullptr;
+    uint8_t* d_codes = nullptr;
+    HIPCHECK(mem.alloc(&d_cb, rows * ds * sizeof(float)));
+    HIPCHECK(hipMemcpy(d_cb, codebooks, rows * ds * sizeof(float), hipMemcpyHostToDevice));
+    if (sq_bits == 8) HIPCHECK(mem.alloc(&d_cbnorm, rows * sizeof(float)));
+    HIPCHECK(mem.alloc(&d_codes, n * code_bytes));
+    if (rotation) {
+        HIPCHECK(mem.alloc(&d_rot, sizeof(float) * (size_t)dim * dim));
+        HIPCHECK(hipMemcpy(d_rot, rotation, sizeof(float) * (size_t)dim * dim, hipMemcpyHostToDevice));
+    }
+    const float* d_enc = d_vectors;
+    if (K_coarse > 0) {                                         // as qadc_ivf_encode_host prepares its input
+        HIPCHECK(mem.alloc(&d_coarse, sizeof(float) * (size_t)K_coarse * dim));
+        HIPCHECK(hipMemcpy(d_coarse, coarse, sizeof(float) * (size_t)K_coarse * dim, hipMemcpyHostToDevice));
+        HIPCHECK(mem.alloc(&d_dist, sizeof(float) * ((size_t)std::min<uint64_t>(kBuildChunk, n) * (K_coarse + 1) + K_coarse)));
+        HIPCHECK(mem.alloc(&d_assign, sizeof(int32_t) * n));
+        if (int rc = assign_nearest(d_vectors, n, dim, K_coarse, d_coarse, d_dist, d_assign, sum_mode)) return rc;
+    }
+    if (K_coarse > 0 || rotation) {
+        HIPCHECK(mem.alloc(&d_x, sizeof(float) * n * dim));
+        launch_residual_rotate(d_vectors, n, dim, d_coarse, d_assign, d_rot, d_x, nullptr);
+        d_enc = d_x;
+    }
+    for (int it = 0; it < iters; ++it) {
+        if (sq_bits == 4) {
+            launch_pq_encode(d_enc, n, sq_count, dim, d_cb, 1, sum_mode, d_codes, nullptr);
+        } else {
+            launch_row_sqnorm(d_cb, (int)rows, ds, sum_mode, d_cbnorm, nullptr);
+            HIPCHECK(adc::launch_adc_encode(d_enc, n, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_codes, nullptr));
+        }
+        HIPCHECK(launch_pq_train_update(d_enc, n, dim, sq_count, sq_bits, d_codes, d_cb, div_mode, nullptr));
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(codebooks, d_cb, rows * ds * sizeof(float), hipMemcpyDeviceToHost));
+    if (codes_out) HIPCHECK(hipMemcpy(codes_out, d_codes, n * code_bytes, hipMemcpyDeviceToHost));
+    if (empty_out) *empty_out = nan_rows(codebooks, rows, ds);
+    return QADC_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int qadc_pq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                         const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                         int sum_mode, int device_id) {
+    if (int rc = pq_train_check(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (iters == 0) {                                          // the seed untouched, no code written
+        if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count << sq_bits, dim / sq_count);
+        return QADC_OK;
+    }
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(device_id));
+    ScratchFree mem;
+    return pq_train_run(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out,
+                        div_mode, sum_mode, mem);
+}
+
+int qadc_pq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                       const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                       int sum_mode, int device_id) {
+    if (int rc = pq_train_check(vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (iters == 0) {
+        if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count << sq_bits, dim / sq_count);
+        return QADC_OK;
+    }
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(device_id));
+    ScratchFree mem;                                           // the learning set goes up once, for every sub-space and round
+    float* d_v = nullptr;
+    HIPCHECK(mem.alloc(&d_v, sizeof(float) * n * dim));
+    HIPCHECK(hipMemcpy(d_v, vectors, sizeof(float) * n * dim, hipMemcpyHostToDevice));
+    return pq_train_run(d_v, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out, div_mode,
+                        sum_mode, mem);
 }
 
 }  // extern "C"

@@ -10,6 +10,10 @@
 //   learn_coarse_quantizer_hip(...)        learn_coarse_quantizer (databases.cpp:94-118) from a caller-provided seed:
 //                                          the reference seeds with two OpenCV k-means++ iterations (third-party, absent
 //                                          here), then runs kmeans_iter_max - 2 = 48 fast iterations — those run on the GPU
+//   pq_train_iterations(...)               CPU twin of qadc_pq_train_host: kmeans_fast_iterations on a copy of every sub-space's
+//                                          columns, behind the same residual / rotation front
+//   learn_pq_hip(...)                      the product quantizer learned on the GPU from a caller-provided seed, as an io::pq_data
+//                                          ready for pq_to_data_file (the reference's flatdb_create / indexdb_create2 read it)
 //   db_add_hip(db, base_file, chunk_count) db_add's add_vectors (db_add.cpp:52-82): a reader thread (io::vectors_reader,
 //                                          vector_io.hpp:231-288) fills a two-chunk queue from the .fvecs/.bvecs file while
 //                                          this thread encodes the previous chunk on the GPU; labels = index in chunk + the
@@ -17,6 +21,8 @@
 //   db_add_hip(qadc_adc_index*, dim, base_file, chunk_count)  the same into a float-ADC index: encode and append on the GPU
 //   db_add_hip(qadc_index*, dim, base_file, chunk_count)      ... and into the 4-bit index (qadc_index_add_vectors)
 #pragma once
+#include <algorithm>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -157,6 +163,93 @@ inline void kmeans_fast_iterations(const float* vecs, size_t n, int dim, int K, 
             }
         }
     }
+}
+
+// What the quantizer of an index sees of a learning set (index_db::add_vectors, databases.hpp:270-298): with K_coarse > 0 the
+// residual to the nearest coarse centroid (find_k_neighbors with k = 1: the loop of kmeans_fast_iterations above), with a rotation
+// rotated[r] = sum_c x[c] * rotation[r][c] in one sequential sum (pq4::rotate_multiple_vectors).  Either may be absent.
+inline std::vector<float> pq_train_front(const float* vecs, size_t n, int dim, int K_coarse, const float* coarse, const float* rotation) {
+    std::vector<float> out(vecs, vecs + n * (size_t)dim);
+    std::vector<float> cn((size_t)std::max(K_coarse, 0)), tmp((size_t)dim);
+    for (int k = 0; k < K_coarse; ++k) cn[k] = sqnorm(coarse + (size_t)k * dim, dim);
+    for (size_t i = 0; i < n; ++i) {
+        float* x = out.data() + i * dim;
+        if (K_coarse > 0) {
+            const float xn = sqnorm(x, dim);
+            int best = 0;
+            float bestd = expansion_dist(x, coarse, dim, xn, cn[0]);
+            for (int k = 1; k < K_coarse; ++k) {
+                const float s = expansion_dist(x, coarse + (size_t)k * dim, dim, xn, cn[k]);
+                if (!(s >= bestd)) { bestd = s; best = k; }
+            }
+            for (int d = 0; d < dim; ++d) x[d] = x[d] - coarse[(size_t)best * dim + d];
+        }
+        if (rotation) {
+            for (int r = 0; r < dim; ++r) {
+                float acc = 0;
+                for (int c = 0; c < dim; ++c) acc += x[c] * rotation[(size_t)r * dim + c];
+                tmp[r] = acc;
+            }
+            std::copy(tmp.begin(), tmp.end(), x);
+        }
+    }
+    return out;
+}
+
+// CPU twin of qadc_pq_train_host (the definition it is tested against bit for bit): sub-quantizer m = kmeans_fast_iterations on a
+// copy of columns [m dsub, (m + 1) dsub) of the front's output, started from codebooks[m].  codebooks [sq_count][2^sq_bits][dsub]
+// in and out; codes (nullable): the last round's assignment in the encoder's layout — sq_bits 4: [n][sq_count / 2], the even
+// sub-quantizer in the low nibble; 8: [n][sq_count].  Returns the centroids that hold a NaN.  iters == 0 changes nothing.
+inline std::uint64_t pq_train_iterations(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                                         const float* rotation, float* codebooks, int iters, std::uint8_t* codes, int div_mode = 1) {
+    if ((sq_bits != 4 && sq_bits != 8) || sq_count <= 0 || dim <= 0 || dim % sq_count || (sq_bits == 4 && sq_count % 2))
+        throw std::runtime_error("pq_train_iterations: sq_bits 4 or 8, dim a multiple of sq_count");
+    const int ds = dim / sq_count, K = 1 << sq_bits;
+    const size_t cs = sq_bits == 4 ? (size_t)sq_count / 2 : (size_t)sq_count;
+    if (iters > 0) {
+        const std::vector<float> x = pq_train_front(vecs, n, dim, K_coarse, coarse, rotation);
+        std::vector<float> slice(n * (size_t)ds);
+        std::vector<int> assign(n);
+        if (codes) std::fill(codes, codes + n * cs, (std::uint8_t)0);
+        for (int m = 0; m < sq_count; ++m) {
+            for (size_t i = 0; i < n; ++i) std::copy(x.begin() + i * dim + (size_t)m * ds, x.begin() + i * dim + (size_t)(m + 1) * ds, slice.begin() + i * ds);
+            kmeans_fast_iterations(slice.data(), n, ds, K, codebooks + (size_t)m * K * ds, iters, assign.data(), div_mode);
+            if (!codes) continue;
+            for (size_t i = 0; i < n; ++i) {
+                if (sq_bits == 8) codes[i * cs + m] = (std::uint8_t)assign[i];
+                else codes[i * cs + m / 2] |= (std::uint8_t)(assign[i] << (4 * (m & 1)));
+            }
+        }
+    }
+    std::uint64_t empty = 0;
+    for (size_t r = 0; r < (size_t)sq_count * K; ++r) {
+        bool nan = false;
+        for (int d = 0; d < ds; ++d) nan = nan || codebooks[r * ds + d] != codebooks[r * ds + d];
+        empty += nan;
+    }
+    return empty;
+}
+
+// The product quantizer learned on the GPU: `iters` rounds from `seed` [sq_count][2^sq_bits][dim / sq_count] on the learning set
+// (made residuals to `coarse` and rotated where given: what indexdb_create1 / indexdb_create2 put before the quantizer).  The
+// result carries the rotation, so that pq_to_data_file writes a .pq.data or .opq.data the reference's executables read.
+inline io::pq_data learn_pq_hip(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, const float* seed, int iters,
+                                int K_coarse = 0, const float* coarse = nullptr, const float* rotation = nullptr, int device = 0,
+                                std::uint64_t* empty_out = nullptr) {
+    io::pq_data pq;
+    pq.dim = dim;
+    pq.sq_count = sq_count;
+    pq.sq_bits = sq_bits;
+    if (sq_count <= 0 || dim <= 0 || sq_bits <= 0 || sq_bits > 16 || !seed) throw std::runtime_error("learn_pq_hip: bad arguments");
+    pq.centroids.assign(seed, seed + pq.all_centroids_dim());
+    if (rotation) {
+        pq.is_opq = true;
+        pq.rotation.assign(rotation, rotation + (size_t)dim * dim);
+    }
+    if (qadc_pq_train_host(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, pq.centroids.data(), iters, nullptr, empty_out, 1,
+                           1, device) != QADC_OK)
+        throw std::runtime_error(std::string("qadc_pq_train_host: ") + qadc_last_error());
+    return pq;
 }
 
 constexpr int kmeans_iter_max = 50;                            // databases.cpp:92

@@ -47,6 +47,7 @@ SYMBOLS = [
     "qadc_index_add_vectors", "qadc_index_add_vectors_device", "qadc_index_read_partition", "qadc_index_reserve",
     "qadc_index_relocations",
     "qadc_adc_index_remove_labels", "qadc_adc_index_remove_labels_device", "qadc_index_remove_labels", "qadc_index_remove_labels_device",
+    "qadc_pq_train_host", "qadc_pq_train_device",
 ]
 
 
@@ -212,6 +213,9 @@ def lib():
         L.qadc_index_reserve.argtypes = [C.c_void_p, C.c_int, u32p]
         L.qadc_index_relocations.argtypes = [C.c_void_p]
         L.qadc_index_relocations.restype = C.c_uint64
+        L.qadc_pq_train_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_int, C.c_void_p, u64p,
+                                         C.c_int, C.c_int, C.c_int]
+        L.qadc_pq_train_device.argtypes = [C.c_void_p] + L.qadc_pq_train_host.argtypes[1:]
         for name in ("qadc_adc_index_remove_labels", "qadc_index_remove_labels"):
             getattr(L, name).argtypes = [C.c_void_p, u32p, C.c_uint64, u64p]
             getattr(L, name + "_device").argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p]
@@ -394,6 +398,80 @@ def kmeans_iterations(vectors, centroids, iters, device=0, div_mode=1):
     _check(lib().qadc_kmeans_iterations_host_mode(_p(v, f32p), v.shape[0], v.shape[1], c.shape[0], _p(c, f32p), iters, _p(assign, i32p),
                                                   div_mode, device))
     return c, assign
+
+
+def _train_pq_args(dim, codebooks_seed, bits, coarse, rotation):
+    cb = np.array(codebooks_seed, np.float32, order="C", copy=True)
+    if cb.ndim != 3:
+        raise QadcError("codebooks_seed has shape %s, expected [sq_count][2^bits][dim / sq_count]" % (tuple(cb.shape),))
+    if bits is None:
+        bits = {16: 4, 256: 8, 65536: 16}.get(cb.shape[1])
+        if bits is None:
+            raise QadcError("cannot infer bits from %d centroids per sub-quantizer (16 or 256)" % cb.shape[1])
+    if cb.shape[1] != 1 << bits or cb.shape[0] * cb.shape[2] != dim:
+        raise QadcError("codebooks_seed has shape %s, expected [sq_count][%d][%d / sq_count]" % (tuple(cb.shape), 1 << bits, dim))
+    co = None if coarse is None else np.ascontiguousarray(coarse, np.float32)
+    rot = None if rotation is None else np.ascontiguousarray(rotation, np.float32)
+    if rot is not None and rot.shape != (dim, dim):
+        raise QadcError("rotation has shape %s, expected [%d][%d]" % (tuple(rot.shape), dim, dim))
+    if co is not None and (co.ndim != 2 or co.shape[1] != dim):
+        raise QadcError("coarse has shape %s, expected [K][%d]" % (tuple(co.shape), dim))
+    return cb, bits, co, rot
+
+
+def train_pq(vectors, codebooks_seed, iters, bits=None, coarse=None, rotation=None, device=0, div_mode=1, sum_mode=1):
+    """Learn a product quantizer on the GPU (qadc_pq_train_host): `iters` rounds of kmeans_fast_iterations_thread in every sub-space
+    at once, from the caller's seed [sq_count][2^bits][dim / sq_count] (pq_seed); bits (4 or 8) is inferred from the seed's second
+    axis.  With coarse [K][dim] the learning set is first made residuals to the nearest coarse centroid, with rotation
+    [dim][dim] those are rotated.  -> (codebooks float32 like the seed, codes uint8 of the last round in the encoder's layout —
+    [n][sq_count / 2] packed nibbles at 4 bits, [n][sq_count] at 8 —, empty = centroids that are NaN at return)."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2:
+        raise QadcError("vectors has shape %s, expected [n][dim]" % (tuple(v.shape),))
+    n, dim = v.shape
+    cb, bits, co, rot = _train_pq_args(dim, codebooks_seed, bits, coarse, rotation)
+    nsq = cb.shape[0]
+    codes = np.zeros((n, nsq // 2 if bits == 4 else nsq), np.uint8)
+    empty = C.c_uint64(0)
+    _check(lib().qadc_pq_train_host(_p(v, f32p), n, dim, nsq, bits, 0 if co is None else co.shape[0], _p(co, f32p), _p(rot, f32p),
+                                    _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode, sum_mode, device))
+    return cb, codes, int(empty.value)
+
+
+def train_pq_device(vectors, codebooks_seed, iters, bits=None, coarse=None, rotation=None, div_mode=1, sum_mode=1):
+    """train_pq on a learning set already in device memory: a contiguous float32 [n][dim] torch tensor on a GPU (read only).  The
+    seed, coarse and rotation are host arrays; the results come back as numpy arrays like train_pq's."""
+    import torch
+    if not isinstance(vectors, torch.Tensor):
+        raise TypeError("vectors must be a torch.Tensor, not %s" % type(vectors).__name__)
+    if vectors.dtype != torch.float32:
+        raise TypeError("vectors must be float32, not %s" % vectors.dtype)
+    if vectors.device.type != "cuda":
+        raise QadcError("vectors is on %s; train_pq_device takes a tensor in device memory" % vectors.device)
+    if vectors.ndim != 2 or not vectors.is_contiguous():
+        raise QadcError("vectors must be a contiguous [n][dim] tensor")
+    n, dim = int(vectors.shape[0]), int(vectors.shape[1])
+    cb, bits, co, rot = _train_pq_args(dim, codebooks_seed, bits, coarse, rotation)
+    nsq = cb.shape[0]
+    codes = np.zeros((n, nsq // 2 if bits == 4 else nsq), np.uint8)
+    empty = C.c_uint64(0)
+    torch.cuda.current_stream(vectors.device).synchronize()                # the learning set is complete before the call
+    _check(lib().qadc_pq_train_device(C.c_void_p(vectors.data_ptr()), n, dim, nsq, bits, 0 if co is None else co.shape[0], _p(co, f32p),
+                                      _p(rot, f32p), _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode,
+                                      sum_mode, vectors.device.index or 0))
+    return cb, codes, int(empty.value)
+
+
+def pq_seed(vectors, sq_count, bits, rng):
+    """A seed for train_pq: the sub-vectors of 2^bits distinct rows of `vectors`, drawn with the numpy Generator `rng` ->
+    float32 [sq_count][2^bits][dim / sq_count].  (Host only.)"""
+    v = np.ascontiguousarray(vectors, np.float32)
+    n, dim = v.shape
+    K = 1 << bits
+    if dim % sq_count or n < K:
+        raise QadcError("pq_seed needs dim %% sq_count == 0 and at least %d vectors" % K)
+    rows = v[rng.choice(n, K, replace=False)]
+    return np.ascontiguousarray(rows.reshape(K, sq_count, dim // sq_count).transpose(1, 0, 2))
 
 
 def coarse_assign(queries, coarse, ma, device=0):

@@ -1,8 +1,8 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
@@ -32,6 +32,12 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             arena only the route without the call needs).  Every arm starts from a fresh copy of the database, built outside the
             clock; the two routes' partitions are first asserted equal.  Then 10 % at K = 8: a few very long partitions, which the
             call compacts with one workgroup each
+  train     learning the product quantizer (not in the default legs; also under --bits 4, at 16x4): 10^5 and 10^6 clustered 128-d
+            vectors, 8x8, 10 rounds from a seed of 256 distinct rows (pyqadc.pq_seed).  train_pq, call to return (the upload of the
+            learning set included), alternated in one process with the route without it: kmeans_iterations on every host slice.
+            The two routes' codebooks and codes are first asserted equal bit for bit
+  --trained-codebooks   the add, remove and ivf_search legs (8 and 4 bits) learn their codebooks with train_pq (10 rounds on the
+            residuals of the first 10^5 vectors) instead of sampling them; off by default, so that recorded figures stay comparable
   --bits 4   the float-ADC view of a 4-bit index instead (pyqadc.AdcIndex.view_of; legs lone,ivf_search):
   lone      one synchronous query on 10^6 and on 10^8 codes at 16x4 and 32x4: median and range of the call, codes/s, the share
             of the HBM roofline at 8 B / 16 B per code; at 16x4 alternated with the 8x8 engine on a list of the same n (the
@@ -137,6 +143,8 @@ def search_legs(legs, iters, res):
     sample = vectors[rng.choice(n, 256, replace=False)]
     near = pyqadc.coarse_assign(sample, coarse, 1)[:, 0]
     codebooks = np.ascontiguousarray((sample - coarse[near]).reshape(256, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
+    if TRAINED:
+        codebooks = trained_codebooks(vectors, coarse, nsq, 8, rng)
     t0 = time.perf_counter()
     part_of, codes = pyqadc.adc_encode(codebooks, vectors, coarse)
     res["adc_encode_1e6_s"] = time.perf_counter() - t0
@@ -288,6 +296,8 @@ def view_legs(legs, iters, res):
         sample = vectors[rng.choice(n, 16, replace=False)]
         near = pyqadc.coarse_assign(sample, coarse, 1)[:, 0]
         codebooks = np.ascontiguousarray((sample - coarse[near]).reshape(16, M, dim // M).transpose(1, 0, 2), np.float32)
+        if TRAINED:
+            codebooks = trained_codebooks(vectors, coarse, M, 4, rng)
         part_of, codes = pyqadc.ivf_encode(codebooks, vectors, coarse)
         del vectors
         order = np.argsort(part_of, kind="stable")
@@ -314,6 +324,8 @@ def view_legs(legs, iters, res):
         add_leg(4, iters, res)
     if "remove" in legs:
         remove_leg(4, iters, res)
+    if "train" in legs:
+        train_leg(4, iters, res)
 
 
 def cpu_twin_u16_us(nsq, codes, table, repeat=5):
@@ -363,6 +375,59 @@ def cpu_twin_encode16(codebooks, vectors):
     return float(out[out.index("us") + 1]) * 1e-6, codes
 
 
+TRAINED = False   # --trained-codebooks
+
+
+def trained_codebooks(vectors, coarse, nsq, bits, rng):
+    """--trained-codebooks: 10 rounds of train_pq on the residuals of the first 10^5 vectors, seeded with 2^bits sampled residuals"""
+    learn = vectors[:100000]
+    sample = learn[rng.choice(len(learn), 1 << bits, replace=False)]
+    near = pyqadc.coarse_assign(sample, coarse, 1)[:, 0]
+    seed = np.ascontiguousarray((sample - coarse[near]).reshape(1 << bits, nsq, vectors.shape[1] // nsq).transpose(1, 0, 2), np.float32)
+    t0 = time.perf_counter()
+    codebooks, _, empty = pyqadc.train_pq(learn, seed, 10, coarse=coarse)
+    print("codebooks %dx%d learned by train_pq on %d residuals in %.2f s (%d empty clusters)" % (nsq, bits, len(learn), time.perf_counter() - t0, empty),
+          flush=True)
+    return codebooks
+
+
+def train_leg(bits, iters, res):
+    """train_pq alternated with the route without it: kmeans_iterations on every host slice"""
+    rng = np.random.default_rng(1900 + bits)
+    dim, rounds = 128, 10
+    nsq = {4: 16, 8: 8}[bits]
+    ds = dim // nsq
+    for n in (100_000, 1_000_000):
+        vectors, _ = clustered(rng, n, dim)
+        seed = pyqadc.pq_seed(vectors, nsq, bits, rng)
+
+        def new_route():
+            return pyqadc.train_pq(vectors, seed, rounds)
+
+        def slice_route():
+            cb = np.zeros_like(seed)
+            assign = np.zeros((n, nsq), np.uint8)
+            for m in range(nsq):
+                cb[m], a = pyqadc.kmeans_iterations(np.ascontiguousarray(vectors[:, m * ds:(m + 1) * ds]), seed[m], rounds)
+                assign[:, m] = a
+            return cb, assign
+
+        cb, codes, empty = new_route()
+        cb2, assign = slice_route()
+        packed = assign if bits == 8 else assign[:, 0::2] | (assign[:, 1::2] << 4)
+        nan = np.isnan(cb)
+        assert np.array_equal(nan, np.isnan(cb2)) and ((cb.view(np.uint32) == cb2.view(np.uint32)) | nan).all(), "the routes' codebooks differ"
+        assert np.array_equal(codes, packed), "the routes' codes differ"
+        med_new, med_old = alternated(new_route, slice_route, max(3, iters // 2), warmup=1)
+        tag = "train_%dx%d_n%d" % (nsq, bits, n)
+        res[tag + "_train_pq_s"] = med_new
+        res[tag + "_kmeans_per_slice_s"] = med_old
+        res[tag + "_slices_over_train_pq"] = med_old / med_new
+        res[tag + "_empty_clusters"] = int(empty)
+        print("PQ training %dx%d, %.0e clustered 128-d vectors, %d rounds, host to host: train_pq %.3f s; kmeans_iterations on %d host slices "
+              "%.3f s = %.2fx (equal bits; %d empty clusters)" % (nsq, bits, n, rounds, med_new, nsq, med_old, med_old / med_new, empty), flush=True)
+
+
 def add_leg(bits, iters, res):
     """database build: add_vectors (empty / reserved index) alternated with encode + numpy grouping + add_partitions"""
     rng = np.random.default_rng(1700 + bits)
@@ -372,6 +437,8 @@ def add_leg(bits, iters, res):
     coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, K, replace=False)], 5)
     sample = vectors[rng.choice(n, 1 << bits, replace=False)]
     codebooks = np.ascontiguousarray(sample.reshape(1 << bits, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
+    if TRAINED and bits != 16:
+        codebooks = trained_codebooks(vectors, coarse, nsq, bits, rng)
     encode = {4: pyqadc.ivf_encode, 8: pyqadc.adc_encode, 16: pyqadc.adc_encode16}[bits]
 
     def make():
@@ -450,6 +517,8 @@ def remove_leg(bits, iters, res):
     coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, 256, replace=False)], 5)
     sample = vectors[rng.choice(n, 1 << bits, replace=False)]
     codebooks = np.ascontiguousarray(sample.reshape(1 << bits, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
+    if TRAINED:
+        codebooks = trained_codebooks(vectors, coarse, nsq, bits, rng)
 
     def make():
         return pyqadc.Index(nsq) if bits == 4 else pyqadc.AdcIndex(nsq, 8)
@@ -674,7 +743,10 @@ def main():
     ap.add_argument("--bits", type=int, default=8, choices=(4, 8, 16))
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--trained-codebooks", action="store_true")
     a = ap.parse_args()
+    global TRAINED
+    TRAINED = a.trained_codebooks
     if a.legs is None:
         a.legs = "flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search" if a.bits == 8 else "lone,ivf_search"
     legs = a.legs.split(",")
@@ -784,6 +856,8 @@ def main():
         add_leg(8, a.iters, res)
     if "remove" in legs:
         remove_leg(8, a.iters, res)
+    if "train" in legs:
+        train_leg(8, a.iters, res)
     line = json.dumps(res)
     print(line)
     if a.out:

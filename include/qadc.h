@@ -500,6 +500,15 @@ typedef struct qadc_profile {
     uint64_t split5_codes;          /* of split_codes: codes those scanned (5 bytes per code, plus one row-major line per survivor) */
     uint64_t split5_survivors;      /* (code, query) pairs of the 5-plane launches whose 5-byte partial sum was below the bound less
                                        the table's slack, i.e. whose three deferred bytes were read (with "profile" on only) */
+    uint64_t nib_copy_bytes;        /* device bytes of the nibble-plane copies qadc_index_finalize built (8 per code; kept across resets) */
+    uint64_t nib_copy_failed;       /* partitions whose nibble-plane copy could not be allocated: their runs take the other forms */
+    uint64_t nib_launches;          /* of split_launches: launches of the nibble form that streamed 9 or 10 of the 16 sub-quantizers
+                                       (qadc_index_set_split_nib); a launch is counted here, under nib8_*, split5_* or split6_*, never two */
+    uint64_t nib_codes;             /* of split_codes: codes those scanned (4.5 or 5 bytes per code, plus one row-major line per survivor) */
+    uint64_t nib_survivors;         /* (code, query) pairs of those launches whose partial sum was below the bound less the slack */
+    uint64_t nib8_launches;         /* ... the same three for the launches that streamed 8 of 16 (4 bytes per code) */
+    uint64_t nib8_codes;
+    uint64_t nib8_survivors;
 } qadc_profile;
 
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);
@@ -527,6 +536,21 @@ int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6);
  * QADC_SPLIT5_MIN_RUN environment variable overrides the default at qadc_index_create.
  * Default 2^25: profiles/r09_split5_sweep.txt. */
 int qadc_index_set_split5(qadc_index* idx, uint64_t min_run5);
+
+/* Nibble form of the split scan (16x4): launches whose runs all have at least min_run codes stream ns = 9 or 10 of the 16
+ * sub-quantizers (4.5 or 5 of the 8 code bytes) from a nibble-plane copy, those with at least min_run8 codes 8 of them; which
+ * ones is chosen per table, byte 7's included, and the survivor test uses the deferred minima as the 5-plane form does.
+ * Preferred over 5 planes where both qualify; no result changes.  0 = never.  qadc_index_finalize builds the nibble-plane
+ * copy, 8 device bytes per code beside the byte-plane copy, for partitions of at least the smaller non-zero threshold in
+ * force THEN: set the thresholds before finalize; afterwards they may be changed at any time, but partitions without the
+ * copy keep the other forms.  QADC_NIB_MIN_RUN / QADC_NIB8_MIN_RUN / QADC_NIB_NS override the defaults at
+ * qadc_index_create (with QADC_TEST_HOOKS=1).  Defaults: profiles/r10_nib_sweep.txt. */
+int qadc_index_set_split_nib(qadc_index* idx, uint64_t min_run, uint64_t min_run8, int ns);
+
+/* The nibble form's choice for ntables 16x4 int8 tables ([ntables][16][16]), as the device computes it for every table of
+ * a batch: out[12 t + 4 (NS - 8) ..] = the deferred set of NS = 8, 9, 10 streamed sub-quantizers as a 16-bit mask (low byte
+ * first), the slack c, 0.  A diagnostic: the scan never needs it from the caller. */
+int qadc_nib_choice(int device_id, const int8_t* tables, int ntables, uint8_t* out);
 
 /* ---------------------------------------------------------------------------------------------
  * Float ADC — the reference's OTHER query front end, db_query's plain scanner_simple

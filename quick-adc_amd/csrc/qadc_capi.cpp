@@ -26,6 +26,9 @@ namespace {
 // the 6-plane launches' counter); cleared with the block.
 constexpr size_t kSurv5Off = 16;
 static_assert(sizeof(CandHeader) <= kSurv5Off && kSurv5Off + sizeof(unsigned long long) <= 64, "inside the state block's header");
+// ... and the nibble form's: launches of 9 or 10 streamed sub-quantizers, launches of 8
+constexpr size_t kSurvNibOff = 24, kSurvNib8Off = 32;
+static_assert(kSurvNib8Off + sizeof(unsigned long long) <= 64, "inside the state block's header");
 
 // What the stages of plan_and_launch hand on to each other: the layouts of the batch's upload and result blocks.
 struct Staged {
@@ -33,7 +36,7 @@ struct Staged {
     size_t in_bytes = 0, off_tables = 0, off_inj = 0, off_hassign = 0;   // upload block
     size_t state_bytes = 0, off_heaps = 0;
     bool dev_stream = false;       // the ordered streams (also) stay in device memory
-    bool any_split6 = false, any_split5 = false;
+    bool any_split6 = false, any_split5 = false, any_nib = false;
 };
 
 // ---- upload: ONE block, ONE copy (enqueued by plan_and_launch: upload_and_wait) ----
@@ -100,11 +103,13 @@ int bind_state_and_result(qadc_index* idx, Slot& s, Staged& g) {
     HIPCHECK(s.d_qtables.ensure((size_t)nq * ma * idx->M * 16));
     // the 6-plane split form's deferred byte per table, computed where the int8 tables become known (launch_front)
     for (auto& ll : s.launches) {
-        g.any_split5 = g.any_split5 || ll.split5;
-        g.any_split6 = g.any_split6 || (ll.split6 && !ll.split5);
+        g.any_nib = g.any_nib || ll.nib;
+        g.any_split5 = g.any_split5 || (ll.split5 && !ll.nib);
+        g.any_split6 = g.any_split6 || (ll.split6 && !ll.split5 && !ll.nib);
     }
     if (g.any_split6) HIPCHECK(s.d_plane_sel.ensure((size_t)nq * ma));
     if (g.any_split5) HIPCHECK(s.d_plane_sel5.ensure(2 * (size_t)nq * ma));
+    if (g.any_nib) HIPCHECK(s.d_nib_sel.ensure((size_t)kNibSelBytes * nq * ma));
     return QADC_OK;
 }
 
@@ -125,8 +130,9 @@ int launch_front(qadc_index* idx, Slot& s, const BatchPlan& plan, const Staged& 
     if (!s.float_path) {
         s.d_qt = s.front_sharded ? s.d_qtables.p                             // (a sharded-front batch redone here: the gathered tables)
                                  : reinterpret_cast<const int8_t*>(s.d_in.p + g.off_tables);     // caller's int8 tables, as uploaded
-        if (g.any_split6 || g.any_split5)
-            launch_plane_choice(s.d_qt, nq * ma, g.any_split6 ? s.d_plane_sel.p : nullptr, st, g.any_split5 ? s.d_plane_sel5.p : nullptr);
+        if (g.any_split6 || g.any_split5 || g.any_nib)
+            launch_plane_choice(s.d_qt, nq * ma, g.any_split6 ? s.d_plane_sel.p : nullptr, st, g.any_split5 ? s.d_plane_sel5.p : nullptr,
+                                g.any_nib ? s.d_nib_sel.p : nullptr);
         if (idx->profile) { HIPCHECK(prof_event(s, st)); HIPCHECK(prof_event(s, st)); }
         return QADC_OK;
     }
@@ -188,7 +194,7 @@ int launch_front(qadc_index* idx, Slot& s, const BatchPlan& plan, const Staged& 
     }
     launch_select_kth(d_sel, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 4, d_ft, s.d_qtables.p, tda,
                       idx->quant_mode, st, nullptr, nullptr, nullptr, 0, g.any_split6 ? s.d_plane_sel.p : nullptr,
-                      g.any_split5 ? s.d_plane_sel5.p : nullptr);
+                      g.any_split5 ? s.d_plane_sel5.p : nullptr, g.any_nib ? s.d_nib_sel.p : nullptr);
     if (idx->profile) HIPCHECK(prof_event(s, st));
     return QADC_OK;
 }
@@ -206,10 +212,11 @@ void launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, 
                        ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str,
                        ll.split6 && !ll.split5 ? s.d_plane_sel.p : nullptr,
                        !idx->profile  ? nullptr
+                       : ll.nib       ? reinterpret_cast<unsigned long long*>(s.d_state.p + (ll.nib == 8 ? kSurvNib8Off : kSurvNibOff))
                        : ll.split5    ? reinterpret_cast<unsigned long long*>(s.d_state.p + kSurv5Off)
                        : ll.split6    ? reinterpret_cast<unsigned long long*>(s.d_hdr->pad)
                                       : nullptr,
-                       ll.split5 ? s.d_plane_sel5.p : nullptr);
+                       ll.split5 ? s.d_plane_sel5.p : nullptr, ll.nib ? s.d_nib_sel.p : nullptr, ll.nib);   // (the nibble form first)
 }
 
 int launch_head(qadc_index* idx, Slot& s, const Staged& g, hipStream_t str) {
@@ -385,7 +392,7 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
     // 7.66 -> 7.72-7.76: the next batch's workgroups do not fill a tail, they compete with the current level for CUs)
     const LevelOptions opt{idx->M, idx->level_base, idx->level_growth, idx->head_level, idx->small_run, idx->wgs_per_item,
                            idx->share_variant, idx->mq, idx->prescan_sample, idx->split_min_run, idx->split6_min_run,
-                           idx->split5_min_run};
+                           idx->split5_min_run, idx->nib_min_run, idx->nib8_min_run, idx->nib_ns};
     const LevelBatch batch{s.nq, s.ma, s.assign.data(), s.R, s.mode, s.float_path, s.full_prescan, s.pre_slice, s.pre_nslices, s.inj_n};
     BatchPlan plan = plan_levels(idx->parts.data(), idx->parts.size(), opt, batch);      // (host/level_plan.hpp: no GPU calls)
     if (!plan.refused.empty()) return fail(QADC_E_ARG, plan.refused);
@@ -714,7 +721,7 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[0], s.prof_ev[1]));
             if (s.float_path) idx->prof.start_ms += ms;
         }
-        bool count_survivors = false, count_survivors5 = false;
+        bool count_survivors = false, count_survivors5 = false, count_nib = false, count_nib8 = false;
         for (auto& ll : s.launches) {
             if (ll.small || ll.early) {                      // counted, not timed (see plan_and_launch)
                 idx->prof.small_launches++;
@@ -726,13 +733,20 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             idx->prof.mq_launches += ll.mq ? 1 : 0;
             idx->prof.split_launches += ll.split ? 1 : 0;
             idx->prof.split_codes += ll.split ? ll.codes : 0;
-            const bool ran6 = ll.split6 && !ll.split5;       // (the launcher prefers 5 planes over 6)
+            const bool ran5 = ll.split5 && !ll.nib;          // (the launcher prefers the nibble form over 5 planes over 6)
+            const bool ran6 = ll.split6 && !ll.split5 && !ll.nib;
             idx->prof.split6_launches += ran6 ? 1 : 0;
             idx->prof.split6_codes += ran6 ? ll.codes : 0;
-            idx->prof.split5_launches += ll.split5 ? 1 : 0;
-            idx->prof.split5_codes += ll.split5 ? ll.codes : 0;
+            idx->prof.split5_launches += ran5 ? 1 : 0;
+            idx->prof.split5_codes += ran5 ? ll.codes : 0;
+            idx->prof.nib_launches += ll.nib > 8 ? 1 : 0;
+            idx->prof.nib_codes += ll.nib > 8 ? ll.codes : 0;
+            idx->prof.nib8_launches += ll.nib == 8 ? 1 : 0;
+            idx->prof.nib8_codes += ll.nib == 8 ? ll.codes : 0;
             count_survivors = count_survivors || ran6;
-            count_survivors5 = count_survivors5 || ll.split5;
+            count_survivors5 = count_survivors5 || ran5;
+            count_nib = count_nib || ll.nib > 8;
+            count_nib8 = count_nib8 || ll.nib == 8;
             idx->prof.pass_codes += ll.mq ? ll.codes / (uint64_t)ll.nitems * (uint64_t)((ll.nitems + 7) / 8) : ll.codes;
             if (ll.ev < 0 || (size_t)ll.ev + 1 >= s.prof_used) continue;   // not the first launch of its timed group
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[ll.ev], s.prof_ev[ll.ev + 1]));
@@ -747,6 +761,16 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             unsigned long long surv = 0;
             HIPCHECK(hipMemcpy(&surv, s.d_state.p + kSurv5Off, sizeof(surv), hipMemcpyDeviceToHost));
             idx->prof.split5_survivors += surv;
+        }
+        if (count_nib) {
+            unsigned long long surv = 0;
+            HIPCHECK(hipMemcpy(&surv, s.d_state.p + kSurvNibOff, sizeof(surv), hipMemcpyDeviceToHost));
+            idx->prof.nib_survivors += surv;
+        }
+        if (count_nib8) {
+            unsigned long long surv = 0;
+            HIPCHECK(hipMemcpy(&surv, s.d_state.p + kSurvNib8Off, sizeof(surv), hipMemcpyDeviceToHost));
+            idx->prof.nib8_survivors += surv;
         }
         if (s.float_path) idx->prof.start_codes += s.start_codes;
     }
@@ -1195,6 +1219,10 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
         if (const char* e = std::getenv("QADC_SPLIT_MIN_RUN")) idx->split_min_run = std::strtoull(e, nullptr, 10);
         if (const char* e = std::getenv("QADC_SPLIT6_MIN_RUN")) idx->split6_min_run = std::strtoull(e, nullptr, 10);   // (1: every split launch streams 6 planes)
         if (const char* e = std::getenv("QADC_SPLIT5_MIN_RUN")) idx->split5_min_run = std::strtoull(e, nullptr, 10);   // (1: ... 5 planes; 0: never)
+        // the nibble form: thresholds of the 9- or 10-plane and of the 8-plane launches (0: never), and which of 9 and 10
+        if (const char* e = std::getenv("QADC_NIB_MIN_RUN")) idx->nib_min_run = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_NIB8_MIN_RUN")) idx->nib8_min_run = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_NIB_NS")) idx->nib_ns = std::atoi(e) == 10 ? 10 : 9;
     }
     if (int rc = attach_streams(idx)) {
         delete idx;
@@ -1222,6 +1250,7 @@ int qadc_index_destroy(qadc_index* idx) {
         }
         if (p.d_starts) (void)hipFree(p.d_starts);
         if (p.d_split) (void)hipFree(p.d_split);
+        if (p.d_nib) (void)hipFree(p.d_nib);
     }
     idx->arena.release();               // (the partitions with Part::arena, all at once)
     idx->feed.d_codebooks.release();
@@ -1235,7 +1264,7 @@ int qadc_index_destroy(qadc_index* idx) {
     for (Slot* sp : all_slots) {
         Slot& s = *sp;
         s.d_in.release(); s.h_in.release(); s.d_state.release(); s.h_result.release();
-        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_plane_sel5.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
+        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_plane_sel5.release(); s.d_nib_sel.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
         s.h_cands.release(); s.d_stream.release(); s.d_qflags.release(); s.d_fvals.release(); s.d_qcands.release(); s.h_fetch.release();
         s.d_fblock.release(); s.d_fgathered.release(); s.d_front_all.release(); s.h_fmap.release();
         if (s.ev_fa) (void)hipEventDestroy(s.ev_fa);
@@ -1503,6 +1532,31 @@ int qadc_index_finalize(qadc_index* idx, float keep) {
         launch_split_copy(p.d_codes, p.n, p.d_split, idx->stream);
         HIPCHECK(hipGetLastError());
         idx->prof.split_copy_bytes += bytes;
+    }
+    // ... and the nibble-plane copies of all 16 sub-quantizers for the nibble form (8 bytes per code more), where that form is on:
+    // partitions with a byte-plane copy (the planner takes the form only for runs that have both) of at least the smaller of its
+    // non-zero thresholds.  A failed allocation is skipped and counted in the same way.
+    idx->prof.nib_copy_bytes = 0;
+    idx->prof.nib_copy_failed = 0;
+    const uint64_t nib_min = idx->nib_min_run && idx->nib8_min_run ? std::min(idx->nib_min_run, idx->nib8_min_run)
+                                                                   : std::max(idx->nib_min_run, idx->nib8_min_run);
+    for (auto& p : idx->parts) {
+        if (p.d_nib) {
+            HIPCHECK(hipDeviceSynchronize());
+            HIPCHECK(hipFree(p.d_nib));
+            p.d_nib = nullptr;
+        }
+        if (idx->M != 16 || nib_min == 0 || p.n < nib_min || !p.d_split) continue;
+        const uint64_t bytes = nib_copy_bytes(p.n);
+        if (hipMalloc(reinterpret_cast<void**>(&p.d_nib), bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p.d_nib = nullptr;
+            idx->prof.nib_copy_failed++;
+            continue;
+        }
+        launch_nib_copy(p.d_codes, p.n, p.d_nib, idx->stream);
+        HIPCHECK(hipGetLastError());
+        idx->prof.nib_copy_bytes += bytes;
     }
     // (the query kernels run on non-blocking streams, which do not wait for the null stream this copy from pageable memory is issued
     // on; whatever the runtime's staging does, nothing of the table is in flight when the first query is launched)
@@ -1848,9 +1902,12 @@ int qadc_profile_read(qadc_index* idx, qadc_profile* out) {
 int qadc_profile_reset(qadc_index* idx) {
     if (!idx) return fail(QADC_E_ARG, "null index");
     const uint64_t copy_bytes = idx->prof.split_copy_bytes, copy_failed = idx->prof.split_copy_failed;   // (state, not counters)
+    const uint64_t nib_bytes = idx->prof.nib_copy_bytes, nib_failed = idx->prof.nib_copy_failed;
     idx->prof = qadc_profile{};
     idx->prof.split_copy_bytes = copy_bytes;
     idx->prof.split_copy_failed = copy_failed;
+    idx->prof.nib_copy_bytes = nib_bytes;
+    idx->prof.nib_copy_failed = nib_failed;
     return QADC_OK;
 }
 
@@ -1872,6 +1929,36 @@ int qadc_index_set_split6(qadc_index* idx, uint64_t min_run6) {
 int qadc_index_set_split5(qadc_index* idx, uint64_t min_run5) {
     if (!idx) return fail(QADC_E_ARG, "null index");
     idx->split5_min_run = min_run5;
+    return QADC_OK;
+}
+
+int qadc_nib_choice(int device_id, const int8_t* tables, int ntables, uint8_t* out) {
+    if (!tables || !out || ntables <= 0) return fail(QADC_E_ARG, "bad arguments");
+    if (int rc = qadc_device_prepare(device_id)) return rc;
+    HIPCHECK(hipSetDevice(device_id));
+    DevBuf<int8_t> d_t;
+    DevBuf<uint8_t> d_o;
+    hipError_t e = d_t.ensure((size_t)ntables * 256);
+    if (e == hipSuccess) e = d_o.ensure((size_t)ntables * kNibSelBytes);
+    if (e == hipSuccess) e = hipMemcpy(d_t.p, tables, (size_t)ntables * 256, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_plane_choice(d_t.p, ntables, nullptr, nullptr, nullptr, d_o.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_o.p, (size_t)ntables * kNibSelBytes, hipMemcpyDeviceToHost);
+    d_t.release();
+    d_o.release();
+    HIPCHECK(e);
+    return QADC_OK;
+}
+
+int qadc_index_set_split_nib(qadc_index* idx, uint64_t min_run, uint64_t min_run8, int ns) {
+    if (!idx) return fail(QADC_E_ARG, "null index");
+    if (ns != 9 && ns != 10) return fail(QADC_E_ARG, "ns is 9 or 10");
+    idx->nib_min_run = min_run;
+    idx->nib8_min_run = min_run8;
+    idx->nib_ns = ns;
     return QADC_OK;
 }
 

@@ -179,6 +179,7 @@ struct Slot {
     DevBuf<float> d_ftables;            // float tables built on the device (qadc_search)
     DevBuf<int8_t> d_qtables;
     DevBuf<uint8_t> d_plane_sel;        // 16x4: the 6-plane split form's deferred byte of every table of the batch (written beside d_qt)
+    DevBuf<uint8_t> d_nib_sel;          // ... and the nibble form's kNibSelBytes per table (deferred masks and slacks for NS = 8, 9, 10)
     DevBuf<uint8_t> d_plane_sel5;       // ... and the 5-plane form's two bytes per table: j1 | j2 << 4, slack (launch_scan_i8)
     DevBuf<Cand> d_cands;
     bool wgq_grouped = false;           // the batch took the partition-major second phase
@@ -445,6 +446,13 @@ struct qadc_index {
     // ... and 5 of them, with the slack of the deferred minima in the survivor test, from split5_min_run codes per run
     // (0 = never; qadc_index_set_split5; profiles/r09_split5_sweep.txt)
     uint64_t split5_min_run = 1ull << 25;
+    // the nibble form (scan_i8_nib_kernel, preferred over 5 planes): launches whose runs all have at least nib8_min_run codes stream 8
+    // of the 16 sub-quantizers, else those with at least nib_min_run stream nib_ns (9 or 10) of them; 0 = never.  qadc_index_finalize
+    // builds the nibble-plane copy (8 bytes per code more) of the partitions that reach the smaller non-zero threshold
+    // (qadc_index_set_split_nib; profiles/r10_nib_sweep.txt)
+    uint64_t nib_min_run = 1ull << 25;       // defaults: the fastest arm of the sweep, 9 from the level at 2^25 on and 8 on runs of
+    uint64_t nib8_min_run = 400ull << 20;    // 400 Mi codes (the 10^9-code list's last level, which starts at 2^29, has 441.7 Mi)
+    int nib_ns = 9;
     // one workgroup per query (IVF batches, small lists): 0 = never, 1 = auto, 2 = whenever structurally possible
     int wgq = 1;
     uint32_t wgq_capacity = 4096;        // stream entries per query to start with

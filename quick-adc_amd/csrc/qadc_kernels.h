@@ -12,6 +12,9 @@ namespace qadc {
 // ScanItem, StartItem, kSplitTile / kSplitBytes (the byte-plane copy's layout) and kMaxLevels: host/level_plan.hpp
 inline uint64_t split_copy_bytes(uint32_t n) { return ((uint64_t)n + kSplitTile - 1) / kSplitTile * kSplitBytes * kSplitTile; }
 void launch_split_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipStream_t stream);
+// ... and kNibTileBytes / kNibSelBytes (the nibble-plane copy and the nibble form's choice bytes)
+inline uint64_t nib_copy_bytes(uint32_t n) { return ((uint64_t)n + kSplitTile - 1) / kSplitTile * kNibTileBytes; }
+void launch_nib_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipStream_t stream);
 
 // Candidate emitted by the scan: value < bound derived from a strict prefix of the scan order.
 struct Cand {
@@ -232,18 +235,21 @@ hipError_t take_launch_error();
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands,
                     uint32_t cap_per_query, uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel = nullptr,
-                    unsigned long long* d_surv = nullptr, const uint8_t* d_plane_sel5 = nullptr);
+                    unsigned long long* d_surv = nullptr, const uint8_t* d_plane_sel5 = nullptr,
+                    const uint8_t* d_nib_sel = nullptr, int nib_ns = 0);
 // Split form only (variant bit 5).  d_plane_sel5 != nullptr: the 5-plane form, two bytes per table: j1 | j2 << 4 (the bytes
 // j1 < j2 of 0..6 deferred beside byte 7) and the slack c of its survivor test (min(127, the deferred pair tables' minima
 // summed): a code survives when its 5-byte partial is below bound - c).  Else d_plane_sel != nullptr: the 6-plane form,
 // d_plane_sel[table] = the byte (0..6) deferred beside byte 7; both nullptr: the 7-plane form.
-// d_surv (profiling, 6 and 5 planes): incremented by the number of survivors, or nullptr.
+// d_surv (profiling, 6 and 5 planes and the nibble form): incremented by the number of survivors, or nullptr.
+// nib_ns = 8, 9 or 10 with d_nib_sel != nullptr: the nibble form (scan_i8_nib_kernel) instead, streaming that many of the 16
+// sub-quantizers from the nibble-plane copy, where ScanItem::split then points; d_nib_sel = kNibSelBytes per table: for each NS the deferred set (16-bit mask) and the slack.
 
 // The deferred byte of every 16x4 int8 table (qtables + t * 256 -> d_plane_sel[t]) and the 5-plane form's two bytes per
 // table (d_plane_sel5[2 t], [2 t + 1]) for tables the caller brings, either or both; tables quantized here get theirs from
 // launch_select_kth (d_plane_sel, d_plane_sel5).
 void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream,
-                         uint8_t* d_plane_sel5 = nullptr);
+                         uint8_t* d_plane_sel5 = nullptr, uint8_t* d_nib_sel = nullptr);
 
 // Multi-query streaming scan: groups of up to 8 consecutive runs (all over the same codes, one per query) share
 // ONE pass; wgs_per_group workgroups of 256 threads per group, sibling-major over the groups.
@@ -332,11 +338,12 @@ void launch_select_kth(const float* d_fc, uint64_t fc_stride, const uint32_t* d_
                        QueryState* d_qs, int max_passes, float* d_ftables, int8_t* d_qtables, int table_dim_all,
                        int quant_mode, hipStream_t stream, float* export_vals = nullptr,
                        uint32_t* export_flags = nullptr, uint32_t* d_front_out = nullptr, int small_wg = 0,
-                       uint8_t* d_plane_sel = nullptr, uint8_t* d_plane_sel5 = nullptr);
+                       uint8_t* d_plane_sel = nullptr, uint8_t* d_plane_sel5 = nullptr, uint8_t* d_nib_sel = nullptr);
 // d_front_out (optional): {flags & 3, qmin, qmax, 0} per query = the front_in record of scan_query_kernel's HEAD; small_wg:
 // 256-thread workgroups (a batch of many queries beside running scans) instead of 1024.  d_plane_sel (optional, 16x4 with
 // d_qtables): the 6-plane split form's deferred byte of each quantized table, [nq][table_dim_all / 256]; d_plane_sel5: the
-// 5-plane form's two bytes per table (launch_scan_i8), [nq][table_dim_all / 256][2].
+// 5-plane form's two bytes per table (launch_scan_i8), [nq][table_dim_all / 256][2]; d_nib_sel: the nibble form's
+// kNibSelBytes per table.
 
 // Stream-layout probe: a launch of spin_wgs two-per-CU workgroups spinning spin_ticks (100 MHz wall clock) each on stream a, then a
 // one-wave marker on stream b; d_t[0] = first spin workgroup's start (initialise to ~0), [1] = last one's end (0), [2] = marker start.

@@ -571,6 +571,283 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_split_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Nibble form of the split scan (16x4, one query per pass): the run is streamed from the partition's nibble-plane copy
+// (kNibTileBytes per kSplitTile-code tile, launch_nib_copy), NS = 8, 9 or 10 of the 16 sub-quantizers per code, i.e. 4, 4.5
+// or 5 of the 8 code bytes; which ones is the table's choice (plane_choice_nib: any of the 16, byte 7's two included).
+//   Table entries are >= 0, so the sum over the streamed sub-quantizers is a lower bound of the code's value, and with
+//   c = min(127, the sum over the deferred s of min T[s]) every code's full sum is >= partial + c.  A code whose partial is
+//   not below bound - c therefore cannot be a candidate: the survivor test is min(127, partial) < bsurv = bound > c ? bound - c : 0
+//   (0: no code survives).  A survivor reads its row-major 8-byte word, adds the deferred sub-quantizers' entries from the
+//   plain int8 table in LDS (the staging copy; bank conflicts do not matter there) and is emitted when min(127, full) < bound:
+//   the candidates are those of scan_i8_kernel.  The argument holds for ANY deferred set as long as c is a lower bound of the
+//   deferred entries' sum; the kernel derives the streamed list and its complement, the deferred set, from the choice bytes
+//   itself (nib_streamed: always NS distinct sub-quantizers, whatever the bytes hold), so only a wrong c could lose a
+//   candidate, and c is clamped to 127 as in the 5-plane form.
+//   Loop: the 5-plane form's.  A lane holds 16 codes per iteration: one 8-byte load per streamed plane (two dwords of eight
+//   codes each: codes 0-3 in the low nibbles of bytes 0-3, codes 4-7 in the high nibbles).  Two planes A, B merge into the
+//   byte indices of a pair table P[x] = T[a][x & 15] + T[b][x >> 4] with two bit-field inserts per eight codes:
+//   (A & 0x0f0f0f0f) | (B << 4 & 0xf0f0f0f0) for codes 0-3, (A >> 4 & 0x0f0f0f0f) | (B & 0xf0f0f0f0) for codes 4-7.  An odd
+//   NS leaves one single plane, which has two table slots, T[a][x & 15] and T[a][x >> 4], and so needs no mask: NS / 2 + (NS & 1)
+//   lookups per code.  The image is built permuted (build_nib_tables) with the bank replication of build_pair_tables.
+//   Survivors are packed, tested, resolved one iteration late and emitted exactly as with 5 planes.
+// PROBE: XOR of the streamed planes (the streaming ceiling of this form; results meaningless).
+// surv (profile option only, else null): survivor count, one atomicAdd per workgroup at exit.
+// ---------------------------------------------------------------------------------------------
+// The NS streamed sub-quantizers of a table as nibbles of a 64-bit list, from its deferred mask: the clear bits in ascending
+// order, cyclically, from the one behind the highest deferred sub-quantizer on (so an odd NS's single plane, the last of the
+// list, can be any of the 16), then (a mask with more than 16 - NS bits set: never written by plane_choice_nib) set bits in the
+// same order until there are NS.  used = the list as a bit set; its complement is the deferred set the kernel works with.
+template <int NS>
+__device__ __forceinline__ uint64_t nib_streamed(uint32_t mask, uint32_t& used) {
+    mask &= 0xffffu;
+    const uint32_t start = mask ? 32u - (uint32_t)__builtin_clz(mask) : 0u;
+    uint64_t list = 0;
+    uint32_t cnt = 0;
+    used = 0;
+#pragma unroll
+    for (uint32_t pass = 0; pass < 2; ++pass)
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) {
+            const uint32_t s = (start + i) & 15u;
+            if (((mask >> s) & 1u) == pass && cnt < (uint32_t)NS) {
+                list |= (uint64_t)s << (4u * cnt);
+                used |= 1u << s;
+                ++cnt;
+            }
+        }
+    return list;
+}
+
+// build_pair_tables for the nibble form: slot p < NS / 2 of the image holds the pair table of the streamed sub-quantizers
+// 2p and 2p + 1 of the list; NS odd: slot NS / 2 = T[last][x & 15], slot NS / 2 + 1 = T[last][x >> 4]; other slots 0.
+// The staging copy of the int8 table (ScanCfg::STAGE_OFF) stays in LDS for the survivors' deferred entries.
+template <int NS>
+__device__ __forceinline__ void build_nib_tables(const int8_t* __restrict__ qt, uint64_t list) {
+    using C = ScanCfg<16>;
+    constexpr uint32_t NP = NS / 2;
+    const int t = threadIdx.x;
+    if (t < 64) reinterpret_cast<uint32_t*>(smem + C::STAGE_OFF)[t] = reinterpret_cast<const uint32_t*>(qt)[t];
+    __syncthreads();
+    const unsigned char* T = smem + C::STAGE_OFF;
+    constexpr int kIter = C::TABLE_BYTES / 16 / kWG;
+    const uint32_t lane = (uint32_t)t & 63u, wave = (uint32_t)t >> 6;
+    uint32_t w = 0;
+    {
+        const uint32_t pi = lane & (8u * kIter - 1u);
+        const uint32_t k = pi >> 3, within = pi & 7u;
+        const uint32_t x = (k & 3u) * 64u + wave * 4u + (within >> 1);
+        const uint32_t g = (k >> 2) * 2u + (within & 1u);
+        const uint32_t last = (uint32_t)(list >> (4u * (NS - 1))) & 15u;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t slot = 4u * g + j;
+            uint32_t ra = 0, rb = 0, ma = 0, mb = 0;
+            if (slot < NP) {
+                ra = (uint32_t)(list >> (8u * slot)) & 15u;
+                rb = (uint32_t)(list >> (8u * slot + 4u)) & 15u;
+                ma = mb = 1;
+            } else if ((NS & 1) && slot == NP) {
+                ra = last;
+                ma = 1;
+            } else if ((NS & 1) && slot == NP + 1u) {
+                rb = last;
+                mb = 1;
+            }
+            const uint32_t v = (uint32_t)T[ra * 16u + (x & 15u)] * ma + (uint32_t)T[rb * 16u + (x >> 4)] * mb;
+            w |= v << (8u * j);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kIter; ++k) {
+        const uint32_t wk = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((k * 8u + (lane >> 3)) * 4u), (int)w);
+        *reinterpret_cast<uint4*>(smem + ((size_t)k * kWG + t) * 16) = make_uint4(wk, wk, wk, wk);
+    }
+}
+
+template <int NS, bool NT, bool CHUNK, bool PROBE>
+__global__ __launch_bounds__(kWG, 8) void scan_i8_nib_kernel(
+    const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
+    CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
+    const uint8_t* __restrict__ nib_sel, unsigned long long* __restrict__ surv) {
+    static_assert(NS >= 8 && NS <= 10, "8, 9 or 10 of the 16 nibble planes");
+    static_assert(kSplitTile == 16u * kWG, "a workgroup iteration is one tile: 16 codes per lane");
+    using C = ScanCfg<16>;
+    constexpr int NP = NS / 2;                                  // fused pairs
+    constexpr bool ODD = (NS & 1) != 0;                         // ... and one single plane
+    const ScanItem it = items[blockIdx.y];
+    QueryState* qs = qstates + it.query;
+    out += (uint64_t)it.query * cand_cap;
+    const uint8_t* sel = nib_sel + (size_t)it.table * kNibSelBytes + 4u * (NS - 8);
+    const uint32_t slack = min((uint32_t)sel[2], 127u);
+    uint32_t used;
+    const uint64_t list = nib_streamed<NS>((uint32_t)sel[0] | ((uint32_t)sel[1] << 8), used);
+    const uint32_t defmask = 0xffffu & ~used;                   // (whatever the bytes hold: the complement of what is streamed)
+    build_nib_tables<NS>(qtables + (uint64_t)it.table * 256, list);
+    const uint32_t bound = prefix_bound(qs, it.order >> 16, R, reinterpret_cast<uint32_t*>(smem + C::HIST_OFF),
+                                        reinterpret_cast<uint32_t*>(smem + C::BOUND_OFF));
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane_lo = (tid & 31u) * 4u;
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(1))) u32x2* gvec_t;
+    const gvec_t planes = (gvec_t)(uintptr_t)it.split;          // (a launch of this form: the tile in the nibble-plane copy)
+    const gvec_t rows = (gvec_t)(uintptr_t)it.codes;            // run code r, all 8 bytes
+    lds_base_is_zero();
+    const uint32_t n = it.n;
+    const uint32_t ntiles = (n + kSplitTile - 1) / kSplitTile;
+    uint32_t first = blockIdx.x, last = ntiles, step = gridDim.x;
+    if (CHUNK) {
+        const uint32_t per = (ntiles + gridDim.x - 1) / gridDim.x;
+        first = blockIdx.x * per;
+        last = min(ntiles, first + per);
+        step = 1;
+    }
+    const uint32_t tiles_full = n / kSplitTile;
+    const uint32_t full_last = min(last, tiles_full);
+    // 8-byte-vector offset of the plane streamed i-th (uniform; a sub-quantizer is 0..15: inside the tile)
+    uint32_t poff[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) poff[i] = ((uint32_t)(list >> (4 * i)) & 15u) * (kSplitTile / 16);
+    const uint32_t bsurv = bound > slack ? bound - slack : 0u;  // 0 = no survivor (never wraps)
+    const uint32_t bound4 = bsurv * 0x01010101u;
+
+    // survivors of the previous iteration: byte k of pend[w] = min(127, partial) of the lane's code 4 w + k, 0xff = none
+    uint32_t pend[4] = {~0u, ~0u, ~0u, ~0u};
+    uint32_t pend_base = 0;
+    bool any_pend = false;
+    uint32_t res[4];
+    uint32_t res_base = 0;
+    bool any_res = false;
+    uint32_t nsurv = 0;
+
+    auto resolve = [&]() __attribute__((always_inline)) {                                      // pend -> res
+        // bit 8 k + w of m = code 4 w + k survives (bit 7 of its byte in pend[w] is clear)
+        uint32_t m = ((~pend[0] & 0x80808080u) >> 7) | ((~pend[1] & 0x80808080u) >> 6) | ((~pend[2] & 0x80808080u) >> 5) |
+                     ((~pend[3] & 0x80808080u) >> 4);
+        if (surv) nsurv += (uint32_t)__builtin_popcount(m);
+        while (m) {
+            const uint32_t i = (uint32_t)__builtin_ctz(m);
+            m &= m - 1u;
+            const uint32_t w = i & 3u, sh = i & 24u;
+            const u32x2 x = rows[pend_base + 4u * w + (sh >> 3)];
+            const uint32_t pw = w == 0 ? pend[0] : w == 1 ? pend[1] : w == 2 ? pend[2] : pend[3];
+            const uint64_t xw = (((uint64_t)x.y) << 32) | x.x;
+            uint32_t s = (pw >> sh) & 0xffu;
+            for (uint32_t dm = defmask; dm; dm &= dm - 1u) {    // (uniform trip count) the deferred sub-quantizers' entries
+                const uint32_t sq = (uint32_t)__builtin_ctz(dm);
+                s += smem[C::STAGE_OFF + 16u * sq + ((uint32_t)(xw >> (4u * sq)) & 15u)];
+            }
+            const uint32_t cv = min(s, 127u);
+            const uint32_t upd = (pw & ~(0xffu << sh)) | ((cv < bound ? cv : 0xffu) << sh);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) pend[u] = w == (uint32_t)u ? upd : pend[u];
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) res[w] = pend[w];
+        res_base = pend_base;
+        any_res = (res[0] & res[1] & res[2] & res[3]) != ~0u;
+    };
+    auto emit_res = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const uint32_t r = (res[c >> 2] >> (8 * (c & 3))) & 0xffu;
+            if (r != 0xffu)
+                emit_candidate(qs, hdr, out, cand_cap, it.labels, it.key_base, it.order, it.dup_pos, it.dup_reps,
+                               it.pos0 + res_base + c, r);
+        }
+    };
+    auto step_tile = [&](uint32_t t, auto full) __attribute__((always_inline)) {
+        u32x2 v[NS];
+        const uint32_t e0 = t * (kNibTileBytes / 8) + tid;      // vector index of plane 0 (t < 2^17: no wrap)
+#pragma unroll
+        for (int i = 0; i < NS; ++i)
+            v[i] = NT ? __builtin_nontemporal_load(planes + e0 + poff[i]) : planes[e0 + poff[i]];
+        if (__builtin_expect(any_pend, 0)) resolve();           // the previous iteration's survivors, behind this one's loads
+        const uint32_t base = t * kSplitTile + tid * 16u;       // run index of the lane's code 0
+        uint32_t cv[16];
+        uint32_t best = 127u;
+        if (PROBE) {
+            u32x2 a = v[0];
+#pragma unroll
+            for (int i = 1; i < NS; ++i) a ^= v[i];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) cv[c] = 127u;
+            cv[0] = ((a.x ^ a.y) == 0x12345678u && base < n) ? 0u : 127u;
+            best = cv[0];
+        } else {
+            constexpr uint32_t LO = 0x0f0f0f0fu;
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                uint32_t idx[2][NP];                            // [codes 0-3 | 4-7 of the dword's eight][pair]: four byte indices each
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const uint32_t A = v[2 * p][w], B = v[2 * p + 1][w];
+                    idx[0][p] = (A & LO) | ((B << 4) & ~LO);
+                    idx[1][p] = ((A >> 4) & LO) | (B & ~LO);
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        uint32_t s = 0;
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) {
+                            // byte0 = bank*4, byte1 = byte k of the merged index; table slot p at (p >> 2) * 128 + (p & 3)
+                            const uint32_t a = __builtin_amdgcn_perm(idx[h][p], lane_lo, 0x0c0c0000u | ((4u + k) << 8));
+                            s += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(a + (p >> 2) * 128 + (p & 3)));
+                        }
+                        if (ODD) {                              // the single plane: slot NP reads the low nibble, slot NP + 1 the high one
+                            constexpr int sl = NP + 0;
+                            const uint32_t a = __builtin_amdgcn_perm(v[NS - 1][w], lane_lo, 0x0c0c0000u | ((4u + k) << 8));
+                            s += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(a + ((sl + h) >> 2) * 128 + ((sl + h) & 3)));
+                        }
+                        uint32_t c = min(s, 127u);
+                        if (!decltype(full)::value) c = base + 8 * w + 4 * h + k < n ? c : 127u;   // past the run's end: never < bound
+                        cv[8 * w + 4 * h + k] = c;
+                        best = min(best, c);
+                    }
+                }
+            }
+        }
+        any_pend = false;
+        if (__builtin_expect(best < bsurv, 1)) {                // most wave iterations of a long level
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                // bytes >= bsurv -> 0xff, four at a time (all bytes and bsurv are <= 127: no borrow crosses a byte)
+                const uint32_t p = cv[4 * w] | (cv[4 * w + 1] << 8) | (cv[4 * w + 2] << 16) | (cv[4 * w + 3] << 24);
+                const uint32_t ge = ((p | 0x80808080u) - bound4) & 0x80808080u;
+                pend[w] = p | ((ge >> 7) * 0xffu);
+            }
+            pend_base = base;
+            any_pend = true;
+        }
+        if (__builtin_expect(any_res, 0)) {                     // the previous iteration's candidates
+            emit_res();
+            any_res = false;
+        }
+    };
+    using full_t = std::integral_constant<bool, true>;
+    using part_t = std::integral_constant<bool, false>;
+    uint32_t t = first;
+    for (; t < full_last; t += step) step_tile(t, full_t());
+    for (; t < last; t += step) step_tile(t, part_t());
+    if (any_pend) {
+        resolve();
+        if (any_res) emit_res();
+    }
+    if (surv) {                                                 // (uniform) one global atomic per workgroup: the waves' counts meet in LDS
+        uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + C::HIST_OFF);
+        __syncthreads();
+        if (tid == 0) *cnt = 0;
+        __syncthreads();
+        const uint32_t tot = dpp_wave_incl_sum(nsurv);          // lane 63: the wave's count
+        if ((tid & 63u) == 63u && tot) atomicAdd(cnt, tot);
+        __syncthreads();
+        if (tid == 0 && *cnt) atomicAdd(surv, (unsigned long long)*cnt);
+    }
+}
+
 // The deferred byte of the 6-plane split form, once per int8 table: the j in 0..6 whose 256 pair entries
 // q[2j][lo] + q[2j+1][hi] have the smallest sum = 16 x (the sum of the two 16-entry rows); ties: the highest j.
 // The choice changes the survivor rate only, never a result.
@@ -626,9 +903,49 @@ __device__ __forceinline__ uint32_t plane_choice5(const int8_t* __restrict__ qt)
     return j1 | (j2 << 4) | (c << 8);
 }
 
-// plane_sel (6-plane form, 1 byte per table) and plane_sel5 (5-plane form, 2 bytes per table): either may be null
+// The nibble form's choice, once per int8 table: the deferred sets of NS = 10, 9 and 8 streamed sub-quantizers and their
+// slacks, kNibSelBytes bytes.  score_s = the sum of row s - 16 min T[s] = the sum of T[s][x] - min T[s] over the row: what
+// streaming sub-quantizer s adds to the partial sum beyond what the slack already accounts for.  The smallest scores are
+// deferred, one pick after the other (ties: the highest s), so the sets are nested: 6 picks for NS = 10, one more for 9, one
+// more for 8.  c = min(127, the sum of min T[s] over the set) is a lower bound of the deferred entries' sum for every code;
+// a c above that sum would lose candidates, a poor set only costs survivors.
+__device__ __forceinline__ void plane_choice_nib(const int8_t* __restrict__ qt, uint8_t* __restrict__ out) {
+    const uint8_t* T = reinterpret_cast<const uint8_t*>(qt);
+    uint32_t score[16], mn[16];
+#pragma unroll
+    for (uint32_t s = 0; s < 16; ++s) {
+        uint32_t sum = 0, m = 255u;
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t a = T[16 * s + i];
+            sum += a;
+            m = min(m, a);
+        }
+        mn[s] = m;
+        score[s] = sum - 16u * m;
+    }
+    uint32_t mask = 0, c = 0;
+#pragma unroll
+    for (uint32_t pick = 0; pick < 8; ++pick) {
+        uint32_t best = 0xffffffffu, bs = 15, bm = 0;
+#pragma unroll
+        for (uint32_t s = 0; s < 16; ++s)
+            if (!((mask >> s) & 1u) && score[s] <= best) { best = score[s]; bs = s; bm = mn[s]; }
+        mask |= 1u << bs;
+        c += bm;
+        if (pick >= 5) {                                        // 6, 7, 8 deferred = NS 10, 9, 8
+            uint8_t* o = out + 4u * (7u - pick);
+            o[0] = (uint8_t)(mask & 0xffu);
+            o[1] = (uint8_t)(mask >> 8);
+            o[2] = (uint8_t)min(c, 127u);
+            o[3] = 0;
+        }
+    }
+}
+
+// plane_sel (6-plane form, 1 byte per table), plane_sel5 (5-plane form, 2 bytes per table) and nib_sel (nibble form, kNibSelBytes
+// per table): each may be null
 __global__ __launch_bounds__(256) void plane_choice_kernel(const int8_t* __restrict__ qtables, int ntables, uint8_t* __restrict__ plane_sel,
-                                                           uint8_t* __restrict__ plane_sel5) {
+                                                           uint8_t* __restrict__ plane_sel5, uint8_t* __restrict__ nib_sel) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= ntables) return;
     if (plane_sel) plane_sel[t] = (uint8_t)plane_choice(qtables + (size_t)t * 256);
@@ -637,12 +954,14 @@ __global__ __launch_bounds__(256) void plane_choice_kernel(const int8_t* __restr
         plane_sel5[2 * (size_t)t] = (uint8_t)(c5 & 0xffu);
         plane_sel5[2 * (size_t)t + 1] = (uint8_t)(c5 >> 8);
     }
+    if (nib_sel) plane_choice_nib(qtables + (size_t)t * 256, nib_sel + (size_t)t * kNibSelBytes);
 }
 
-void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream, uint8_t* d_plane_sel5) {
-    if (ntables <= 0 || (!d_plane_sel && !d_plane_sel5)) return;
+void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream, uint8_t* d_plane_sel5,
+                         uint8_t* d_nib_sel) {
+    if (ntables <= 0 || (!d_plane_sel && !d_plane_sel5 && !d_nib_sel)) return;
     hipLaunchKernelGGL(plane_choice_kernel, dim3((ntables + 255) / 256), dim3(256), 0, stream, d_qtables, ntables, d_plane_sel,
-                       d_plane_sel5);
+                       d_plane_sel5, d_nib_sel);
 }
 
 // The byte-plane copy of a partition (kSplitTile layout): one thread per 16 codes of a tile, plane b's 16 bytes = byte b
@@ -674,6 +993,38 @@ void launch_split_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipS
     const uint64_t nthreads = ((uint64_t)n + kSplitTile - 1) / kSplitTile * (kSplitTile / 16);
     if (!nthreads) return;
     hipLaunchKernelGGL(split_copy_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream, d_codes, n, d_copy, nthreads);
+}
+
+// The nibble-plane copy of a partition (kNibTileBytes per tile): one thread per 16 codes of a tile; plane s gets the lane's two
+// dwords, byte k of dword w = sub-quantizer s of code 8 w + k (low nibble) and of code 8 w + 4 + k (high nibble).  Reads the
+// row-major codes once and writes as many bytes; run once per partition by qadc_index_finalize.
+__global__ __launch_bounds__(256) void nib_copy_kernel(const uint8_t* __restrict__ codes, uint32_t n, uint8_t* __restrict__ copy,
+                                                       uint64_t nthreads) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nthreads) return;
+    const uint64_t tile = g / (kSplitTile / 16), lane = g % (kSplitTile / 16);
+    const uint64_t c0 = tile * kSplitTile + lane * 16;
+    uint32_t o[16][2] = {};
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        uint2 v = make_uint2(0u, 0u);
+        if (c0 + c < n) v = *reinterpret_cast<const uint2*>(codes + (c0 + c) * 8);
+        const int sh = 8 * (c & 3) + 4 * ((c >> 2) & 1);
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const uint32_t nibble = ((s < 8 ? v.x : v.y) >> (4 * (s & 7))) & 15u;
+            o[s][c >> 3] |= nibble << sh;
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 16; ++s)
+        *reinterpret_cast<uint2*>(copy + tile * kNibTileBytes + (uint64_t)s * (kSplitTile / 2) + lane * 8) = make_uint2(o[s][0], o[s][1]);
+}
+
+void launch_nib_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipStream_t stream) {
+    const uint64_t nthreads = ((uint64_t)n + kSplitTile - 1) / kSplitTile * (kSplitTile / 16);
+    if (!nthreads) return;
+    hipLaunchKernelGGL(nib_copy_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream, d_codes, n, d_copy, nthreads);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1294,15 +1645,48 @@ static void launch_split_variant(dim3 grid, hipStream_t stream, const ScanItem* 
                        d_plane_sel, d_surv);
 }
 
+template <int NS, bool NT, bool CHUNK, bool PROBE>
+static void launch_nib_variant(dim3 grid, hipStream_t stream, const ScanItem* d_items, const int8_t* d_qtables,
+                               QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap, uint32_t R,
+                               const uint8_t* d_nib_sel, unsigned long long* d_surv) {
+    auto k = &scan_i8_nib_kernel<NS, NT, CHUNK, PROBE>;
+    static std::atomic<uint64_t> done{0};
+    ensure_dynamic_lds(reinterpret_cast<const void*>(k), ScanCfg<16>::LDS_BYTES, done);
+    hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<16>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R,
+                       d_nib_sel, d_surv);
+}
+
 // variant bits: [2] NT (non-temporal loads)  [3] CHUNK  [4] PROBE (ceiling diagnostic)
 // [5] split form (16x4, every run of the launch has ScanItem::split; not with [6]): 5 planes when d_plane_sel5 (the two
 //     deferred bytes and the slack of every table) is given, else 6 planes when d_plane_sel (the deferred byte of every
 //     table) is, else 7 (launch_plane_choice / launch_select_kth write both); d_surv: survivor counter or nullptr
+//     nib_ns = 8, 9 or 10 with d_nib_sel (ScanItem::split of every run points into the nibble-plane copy): the nibble form, before all of these
 // [6] sibling-major 1-D launch (every run of the launch covers the same codes; see the kernel's decode).  Other bits: ignored.
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap,
                     uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel, unsigned long long* d_surv,
-                    const uint8_t* d_plane_sel5) {
+                    const uint8_t* d_plane_sel5, const uint8_t* d_nib_sel, int nib_ns) {
+    if (M == 16 && (variant & 32) && !(variant & 64) && d_nib_sel && nib_ns >= 8 && nib_ns <= 10) {
+        const dim3 grid(wgs_per_item, nitems);
+#define QADC_NIB_ARGS grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, d_nib_sel, d_surv
+#define QADC_NIB(NS, PR)                                                       \
+    switch ((variant >> 2) & 3) {                                              \
+        case 0: launch_nib_variant<NS, false, false, PR>(QADC_NIB_ARGS); break; \
+        case 1: launch_nib_variant<NS, true, false, PR>(QADC_NIB_ARGS); break;  \
+        case 2: launch_nib_variant<NS, false, true, PR>(QADC_NIB_ARGS); break;  \
+        default: launch_nib_variant<NS, true, true, PR>(QADC_NIB_ARGS); break;  \
+    }
+        if (nib_ns == 8) {
+            if (variant & 16) { QADC_NIB(8, true) } else { QADC_NIB(8, false) }
+        } else if (nib_ns == 9) {
+            if (variant & 16) { QADC_NIB(9, true) } else { QADC_NIB(9, false) }
+        } else {
+            if (variant & 16) { QADC_NIB(10, true) } else { QADC_NIB(10, false) }
+        }
+#undef QADC_NIB_ARGS
+#undef QADC_NIB
+        return;
+    }
     if (M == 16 && (variant & 32) && !(variant & 64)) {
         const dim3 grid(wgs_per_item, nitems);
 #define QADC_SPLIT_ARGS grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, d_plane_sel, d_surv
@@ -2105,7 +2489,7 @@ void launch_start_scan_f32(int M, int sum_mode, const StartItem* d_items, int ni
 template <int BT>
 __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t* __restrict__ qt, QueryState* qs,
                                float qmax, int quant_mode, float* red /* [BT] LDS */, uint8_t* __restrict__ plane_sel,
-                               uint8_t* __restrict__ plane_sel5) {
+                               uint8_t* __restrict__ plane_sel5, uint8_t* __restrict__ nib_sel) {
     const int t = threadIdx.x;
     float m = FLT_MAX;
     for (int i = t; i < table_dim_all; i += BT) m = fminf(m, tb[i]);
@@ -2130,7 +2514,7 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
         else o = (int8_t)(int)(quant_mode == 0 ? (v - qmin) / delta : (v - qmin) * scale);
         qt[i] = o;
     }
-    if (plane_sel || plane_sel5) {                         // 16x4: the 6- and 5-plane split forms' deferred bytes of each table
+    if (plane_sel || plane_sel5 || nib_sel) {              // 16x4: the 6-, 5-plane and nibble forms' choices of each table
         __syncthreads();
         for (int i = t; i < table_dim_all / 256; i += BT) {
             if (plane_sel) plane_sel[i] = (uint8_t)plane_choice(qt + (size_t)i * 256);
@@ -2139,6 +2523,7 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
                 plane_sel5[2 * i] = (uint8_t)(c5 & 0xffu);
                 plane_sel5[2 * i + 1] = (uint8_t)(c5 >> 8);
             }
+            if (nib_sel) plane_choice_nib(qt + (size_t)i * 256, nib_sel + (size_t)i * kNibSelBytes);
         }
     }
     if (t == 0) { qs->qmin = qmin; qs->flags |= flags; }   // keeps bit3 set by the pre-scan
@@ -2155,7 +2540,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
                                                         int table_dim_all, int quant_mode,
                                                         float* __restrict__ export_vals,
                                                         uint32_t* __restrict__ export_flags, uint32_t* __restrict__ front_out,
-                                                        uint8_t* __restrict__ plane_sel, uint8_t* __restrict__ plane_sel5) {
+                                                        uint8_t* __restrict__ plane_sel, uint8_t* __restrict__ plane_sel5,
+                                                        uint8_t* __restrict__ nib_sel) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t s_prefix, s_k, s_hi, s_cnt;
     __shared__ float red[BT];
@@ -2180,7 +2566,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
         if (tid == 0) qs->qmax = FLT_MAX;
         if (qtables) quantize_query<BT>(table_dim_all, ftables + (uint64_t)q * table_dim_all, qtables + (uint64_t)q * table_dim_all,
                                         qs, FLT_MAX, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr,
-                                        plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr);
+                                        plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr,
+                                        nib_sel ? nib_sel + (size_t)kNibSelBytes * q * (table_dim_all / 256) : nullptr);
         publish_front();
         return;
     }
@@ -2250,7 +2637,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
     }
     if (qtables) quantize_query<BT>(table_dim_all, ftables + (uint64_t)q * table_dim_all, qtables + (uint64_t)q * table_dim_all,
                                     qs, qmax, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr,
-                                        plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr);
+                                        plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr,
+                                        nib_sel ? nib_sel + (size_t)kNibSelBytes * q * (table_dim_all / 256) : nullptr);
     publish_front();
 }
 
@@ -2287,15 +2675,15 @@ void launch_prescan_minmax(const float* d_vals, uint32_t nvals, int nq, QuerySta
 void launch_select_kth(const float* d_fc, uint64_t fc_stride, const uint32_t* d_fc_init, int nq, uint32_t R, QueryState* d_qs,
                        int max_passes, float* d_ftables, int8_t* d_qtables, int table_dim_all, int quant_mode,
                        hipStream_t stream, float* export_vals, uint32_t* export_flags, uint32_t* d_front_out, int small_wg,
-                       uint8_t* d_plane_sel, uint8_t* d_plane_sel5) {
+                       uint8_t* d_plane_sel, uint8_t* d_plane_sel5, uint8_t* d_nib_sel) {
     if (small_wg)
         hipLaunchKernelGGL((select_kth_kernel<256>), dim3(nq), dim3(256), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
                            d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel,
-                           d_plane_sel5);
+                           d_plane_sel5, d_nib_sel);
     else
         hipLaunchKernelGGL((select_kth_kernel<1024>), dim3(nq), dim3(1024), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
                            d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel,
-                           d_plane_sel5);
+                           d_plane_sel5, d_nib_sel);
 }
 
 // ---- stream-layout probe (qadc_stream_probe): does a dispatch that WAITS FOR CUs on stream A hold up stream B? ----

@@ -27,7 +27,8 @@ struct ScanItem {
     uint32_t dup_pos;        // position (in the partition) of the code the reference replays in its padding
                              // lanes, if this run's partition end is held here; else 0xffffffff
     uint32_t dup_reps;       // number of extra replays of that code: (16 - n % 16) % 16
-    const uint8_t* split;    // 16x4: the run's first tile in the partition's byte-plane copy (launch_split_copy), or nullptr
+    const uint8_t* split;    // 16x4: the run's first tile in the partition's byte-plane copy (launch_split_copy), or nullptr; in a
+                             // launch of the nibble form (LevelLaunch::nib): that tile in the nibble-plane copy (launch_nib_copy)
 };
 
 // Byte-plane copy of code bytes 0-6 (16x4 only), the input of the split form of scan_i8_kernel: tile t of a partition holds
@@ -36,6 +37,15 @@ struct ScanItem {
 // tiles (codes past the partition's end read as 0).  Byte 7 stays in the row-major array only.
 constexpr uint32_t kSplitTile = 16384;
 constexpr uint32_t kSplitBytes = 7;
+// Nibble-plane copy (16x4 only), the input of scan_i8_nib_kernel: the same kSplitTile-code tiles, 16 planes of kSplitTile / 2
+// bytes each at byte t * kNibTileBytes; plane s = sub-quantizer s of the tile's codes at half a byte each (8 bytes per code: byte 7
+// has its planes too).  A lane's 16 codes are the two dwords at byte 8 * lane of a plane; in a dword, codes 0-3 of its eight are the
+// low nibbles of bytes 0-3 and codes 4-7 the high nibbles, so two planes merge into eight pair-table indices with two
+// bit-field inserts.  Padded to whole tiles with zeros.
+constexpr uint32_t kNibTileBytes = 8 * kSplitTile;
+// The nibble form's choice bytes of one table: 4 bytes for each NS = 8, 9, 10 streamed sub-quantizers at 4 * (NS - 8):
+// the deferred set as a 16-bit mask (low byte first), the slack c, 0.
+constexpr uint32_t kNibSelBytes = 12;
 
 constexpr int kMaxLevels = 16;  // bound levels per query
 
@@ -72,6 +82,8 @@ struct LevelLaunch {
     bool early;     // launched on the front stream, under the previous batch's long levels: counted, not event-timed
     int ev = -1;    // index of the HIP event recorded before the launch (the next one follows it), -1 = not timed
     bool split5 = false;   // split, and every run has at least split5_min_run codes: the 5-plane form (the launcher prefers 5 over 6 over 7)
+    int nib = 0;           // 8, 9 or 10: split, every run starts on a tile of its partition's nibble-plane copy and has at least the form's
+                           // threshold of codes: scan_i8_nib_kernel streams that many of the 16 sub-quantizers (preferred over 5 planes); 0: not
 };
 
 // What the planner reads of a partition (the index's Part derives from it: one partition table, no copy).
@@ -80,6 +92,7 @@ struct LevelPart {
     uint32_t* d_labels = nullptr;  // labels of the local range (or null)
     uint8_t* d_starts = nullptr;   // replica of the global partition's first codes (null: d_codes, first_pos == 0)
     uint8_t* d_split = nullptr;    // 16x4: byte-plane copy of code bytes 0-6 for the split scan (kSplitTile), or null
+    uint8_t* d_nib = nullptr;      // 16x4: nibble-plane copy of all 16 sub-quantizers (kNibTileBytes per tile), or null
     uint32_t n = 0;                // codes held here
     uint32_t global_n = 0;         // codes of the whole partition (== n unless sharded)
     uint32_t first_pos = 0;        // global position of local code 0
@@ -97,6 +110,10 @@ struct LevelOptions {
     uint32_t prescan_sample;
     uint64_t split_min_run, split6_min_run;
     uint64_t split5_min_run = 0;   // 0 = never the 5-plane form
+    // the nibble form: runs of at least nib8_min_run codes stream 8 of the 16 sub-quantizers, else those of at least nib_min_run
+    // stream nib_ns (9 or 10) of them; 0 = never
+    uint64_t nib_min_run = 0, nib8_min_run = 0;
+    int nib_ns = 9;
 };
 struct LevelBatch {
     int nq, ma;
@@ -184,6 +201,7 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
     uint64_t L[kMaxLevels + 1];
     level_bounds(o, L);
     std::vector<std::vector<ScanItem>> per_level(kMaxLevels);
+    std::vector<std::vector<const uint8_t*>> per_level_nib(kMaxLevels);   // beside every run: its tile in the nibble-plane copy, or nullptr
     const int k0 = (b.mode != 1 && o.head_level > 0) ? o.head_level : 0;   // levels < k0 belong to the head launch
     plan.head_codes = k0 ? L[k0] : 0;
     plan.fc_init.assign(2 * (size_t)nq, 0);
@@ -278,6 +296,8 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
                     // a long run that starts on a tile of the partition's byte-plane copy may take the split form
                     it.split = pt.d_split && b0 % kSplitTile == 0 && len >= std::max<uint64_t>(o.split_min_run, o.small_run)
                                    ? pt.d_split + b0 / kSplitTile * (uint64_t)kSplitBytes * kSplitTile : nullptr;
+                    // ... and, where the partition has a nibble-plane copy as well, the nibble form (same tiles)
+                    per_level_nib[k].push_back(it.split && pt.d_nib ? pt.d_nib + b0 / kSplitTile * (uint64_t)kNibTileBytes : nullptr);
                     per_level[k].push_back(it);
                     b0 += len;
                 }
@@ -305,8 +325,10 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
             const int small = cls == 0 ? 1 : 0;
             uint64_t maxn = 0, minn = ~0ull, codes = 0;
             size_t cnt = 0;
-            bool same = true;
-            for (auto& it : per_level[k]) {
+            bool same = true, all_nib = true;
+            std::vector<const uint8_t*> nibs;
+            for (size_t r = 0; r < per_level[k].size(); ++r) {
+                const ScanItem& it = per_level[k][r];
                 if ((it.n < o.small_run) != (small == 1)) continue;
                 if (!small && (it.split != nullptr) != (cls == 2)) continue;
                 if (cnt) {
@@ -318,6 +340,8 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
                 maxn = std::max<uint64_t>(maxn, it.n);
                 minn = std::min<uint64_t>(minn, it.n);
                 codes += it.n;
+                all_nib = all_nib && per_level_nib[k][r] != nullptr;
+                nibs.push_back(per_level_nib[k][r]);
             }
             if (!cnt) continue;
             const uint64_t nvec = (maxn + cpl - 1) / cpl;
@@ -332,6 +356,12 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
             ll.split = cls == 2 && !ll.shared;
             ll.split6 = ll.split && o.split6_min_run != 0 && minn >= o.split6_min_run;
             ll.split5 = ll.split && o.split5_min_run != 0 && minn >= o.split5_min_run;
+            ll.nib = !(ll.split && all_nib)                              ? 0
+                     : o.nib8_min_run != 0 && minn >= o.nib8_min_run    ? 8
+                     : o.nib_min_run != 0 && minn >= o.nib_min_run      ? (o.nib_ns == 10 ? 10 : 9)
+                                                                        : 0;
+            if (ll.nib)                                                  // the launch reads the nibble-plane copy instead
+                for (size_t r = 0; r < cnt; ++r) plan.all_items[off + r].split = nibs[r];
             ll.wgs = ll.mq       ? wgs_mq(o, maxn, nvec, cnt)
                      : ll.shared ? wgs_shared(o, maxn, nvec)
                      : ll.small  ? wgs_small(nvec, cnt)

@@ -32,7 +32,7 @@ SYMBOLS = [
     "qadc_scan_i8_candidates", "qadc_scan_start", "qadc_query_scan_submit", "qadc_prescan_submit",
     "qadc_prescan_collect", "qadc_query_scan_submit_prescanned",
     "qadc_query_scan_collect", "qadc_index_set_pq", "qadc_index_set_rotation", "qadc_index_set_coarse", "qadc_search", "qadc_search_submit",
-    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6", "qadc_index_set_split5",
+    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6", "qadc_index_set_split5", "qadc_index_set_split_nib", "qadc_nib_choice",
     "qadc_dist_unique_id", "qadc_dist_init", "qadc_dist_collect", "qadc_dist_shutdown", "qadc_dist_merge_blocks", "qadc_dist_merge_blocks_host",
     "qadc_dist_init_transport", "qadc_dist_init_loopback", "qadc_shm_transport_open", "qadc_shm_transport_allgather", "qadc_shm_transport_allgather_host",
     "qadc_shm_transport_close", "qadc_shm_transport_error", "qadc_slot_assign", "qadc_slot_qtables", "qadc_place_partitions",
@@ -68,7 +68,10 @@ class Profile(C.Structure):
                 ("lone_front_launches", C.c_uint64), ("split_launches", C.c_uint64), ("split_codes", C.c_uint64),
                 ("split_copy_bytes", C.c_uint64), ("split_copy_failed", C.c_uint64),
                 ("split6_launches", C.c_uint64), ("split6_codes", C.c_uint64), ("split_survivors", C.c_uint64),
-                ("split5_launches", C.c_uint64), ("split5_codes", C.c_uint64), ("split5_survivors", C.c_uint64)]
+                ("split5_launches", C.c_uint64), ("split5_codes", C.c_uint64), ("split5_survivors", C.c_uint64),
+                ("nib_copy_bytes", C.c_uint64), ("nib_copy_failed", C.c_uint64),
+                ("nib_launches", C.c_uint64), ("nib_codes", C.c_uint64), ("nib_survivors", C.c_uint64),
+                ("nib8_launches", C.c_uint64), ("nib8_codes", C.c_uint64), ("nib8_survivors", C.c_uint64)]
 
 
 QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h
@@ -116,6 +119,8 @@ def lib():
         L.qadc_index_set_split.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
         L.qadc_index_set_split6.argtypes = [C.c_void_p, C.c_uint64]
         L.qadc_index_set_split5.argtypes = [C.c_void_p, C.c_uint64]
+        L.qadc_index_set_split_nib.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int]
+        L.qadc_nib_choice.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.qadc_index_read_codes.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u8p]
         L.qadc_query_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, u32p, i8p, i32p, i32p,
                                       f32p, f32p, i8p]
@@ -262,6 +267,15 @@ def replay_i8(keys, vals, R, sentinel=False):
 def device_prepare(device=0):
     """qadc_device_prepare: the library's per-device stream set, created now — call before any communicator is initialised."""
     _check(lib().qadc_device_prepare(int(device)))
+
+
+def nib_choice(qtables, device=0):
+    """qadc_nib_choice: the nibble form's choice bytes of 16x4 int8 tables [..., 16, 16] as the device computes them ->
+    uint8 [ntables, 3, 4]: for NS = 8, 9, 10 the deferred mask (two bytes, low first), the slack, 0."""
+    qt = np.ascontiguousarray(qtables, np.int8).reshape(-1, 256)
+    out = np.zeros((qt.shape[0], 3, 4), np.uint8)
+    _check(lib().qadc_nib_choice(int(device), qt.ctypes.data_as(C.c_void_p), int(qt.shape[0]), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def option_names():
@@ -623,6 +637,12 @@ class Index:
         """Split launches whose runs all have >= min_run5 codes stream 5 of the 7 planes, preferred to the 6-plane form
         (0 = never); results do not change."""
         _check(lib().qadc_index_set_split5(self._h, int(min_run5)))
+
+    def set_split_nib(self, min_run, min_run8=0, ns=9):
+        """Nibble form (16x4): split launches whose runs all have >= min_run codes stream ns = 9 or 10 of the 16 sub-quantizers
+        from a nibble-plane copy, those with >= min_run8 codes 8 of them; preferred to the 5-plane form (0 = never); results
+        do not change.  Set before finalize: the copy (8 bytes per code) is built there."""
+        _check(lib().qadc_index_set_split_nib(self._h, int(min_run), int(min_run8), int(ns)))
 
     def partition_count(self):
         return lib().qadc_index_partition_count(self._h)

@@ -15,6 +15,8 @@ c = min(127, the sum of min P_b over the deferred bytes) a code survives when mi
 6-plane rule's choice with that test (a what-if: the library's 6-plane form tests against the bound itself), "5 slack" the
 5-plane form as the library runs it (choose_planes5: byte 7 and the two bytes of 0-6 with the smallest
 score_j = sum of the two rows - 16 min P_j, ties: the highest j), "5 plain" the same bytes without the slack.
+"nib 10", "nib 9", "nib 8": the nibble form (choose_nib: 6, 7 or 8 of the 16 sub-quantizers deferred, any of them, byte 7's
+included, by the same score per row; the test with the slack of the deferred rows' minima); 5, 4.5 and 4 bytes streamed.
 Compare the rates with the library's split_survivors / split6_codes and split5_survivors / split5_codes (qadc_profile,
 tools/split_ab.py parts split6 and split5).
 One JSON line at the end."""
@@ -95,6 +97,42 @@ def survivor_rate(qt, planes, bound, c=0):
     return float(sum_distribution(qt, planes)[:min(bound, 127)].sum()) if bound > 0 else 0.0
 
 
+def choose_nib(qt, ns):
+    """The library's rule for the nibble form with ns streamed sub-quantizers (plane_choice_nib) -> (mask, c): the 16 - ns
+    sub-quantizers with the smallest score_s = sum of row s - 16 min row s, one pick after the other, ties: the highest s,
+    as a 16-bit mask; c = min(127, the sum of min row s over them)."""
+    t = qt.reshape(M, 16).astype(np.int64)
+    score = [int(t[s].sum()) - 16 * int(t[s].min()) for s in range(M)]
+    mask = 0
+    for _ in range(M - ns):
+        rest = [s for s in range(M) if not mask >> s & 1]
+        best = min(score[s] for s in rest)
+        mask |= 1 << max(s for s in rest if score[s] == best)
+    return mask, min(127, sum(int(t[s].min()) for s in range(M) if mask >> s & 1))
+
+
+def nib_streamed(mask):
+    """The streamed sub-quantizers in the kernel's order: ascending, cyclically, from behind the highest deferred one; fused in
+    pairs from the front, an odd count leaves the last one as the single plane."""
+    start = mask.bit_length() & 15
+    return [s for s in ((start + i) & 15 for i in range(M)) if not mask >> s & 1]
+
+
+def sum_distribution_nib(qt, subs):
+    """P(sum over the sub-quantizers in `subs` = v), codes iid uniform (a sub-quantizer's nibble is uniform in 0..15)."""
+    t = qt.reshape(M, 16).astype(np.int64)
+    d = np.ones(1)
+    for s in subs:
+        d = np.convolve(d, np.bincount(t[s], minlength=128) / 16.0)
+    return d
+
+
+def survivor_rate_nib(qt, subs, bound, c=0):
+    """P(min(127, partial sum over the sub-quantizers `subs`) < bound - c)."""
+    bound = max(bound - c, 0)
+    return float(sum_distribution_nib(qt, subs)[:min(bound, 127)].sum()) if bound > 0 else 0.0
+
+
 def streamed(j):
     return [b for b in range(7) if b != j]
 
@@ -130,7 +168,7 @@ def main():
         s = float_sums(tables[q], codes)
         qts.append(quantize(tables[q], np.partition(s, k - 1)[k - 1]))
     levels = [(a, min(b, n) - a) for a, b in zip(LEVEL_STARTS, LEVEL_STARTS[1:] + [1 << 62]) if a < n]
-    forms = ("7 bytes", "6 fixed", "6 rule", "6 best", "6 slack", "5 slack", "5 plain")
+    forms = ("7 bytes", "6 fixed", "6 rule", "6 best", "6 slack", "5 slack", "5 plain", "nib 10", "nib 9", "nib 8")
     out = {"codes": n, "queries": nq, "seed": seed, "levels": []}
     print("%-10s %-12s " % ("level", "codes") + " ".join("%-22s" % f for f in forms) + " rule/fixed  rule/best")
     for start, size in levels:
@@ -149,6 +187,9 @@ def main():
             assert c == slack(qt, (j1, j2, 7))
             rates["5 slack"].append(survivor_rate(qt, five, bound, c))
             rates["5 plain"].append(survivor_rate(qt, five, bound))
+            for ns in (10, 9, 8):
+                mask, cn = choose_nib(qt, ns)
+                rates["nib %d" % ns].append(survivor_rate_nib(qt, nib_streamed(mask), bound, cn))
         mean = {f: float(np.mean(v)) for f, v in rates.items()}
         print("2^%-8d %-12d " % (start.bit_length() - 1, size) +
               " ".join("%-22s" % ("%.2e (max %.1e)" % (mean[f], max(rates[f]))) for f in forms) +
@@ -156,7 +197,7 @@ def main():
         out["levels"].append({"start": start, "codes": size, "mean_rate": mean, "max_rate": {f: max(v) for f, v in rates.items()}})
     total = sum(size for _, size in levels)
     out["bytes_per_code"] = {}
-    for f, kbytes in zip(forms, (7, 6, 6, 6, 6, 5, 5)):
+    for f, kbytes in zip(forms, (7, 6, 6, 6, 6, 5, 5, 5, 4.5, 4)):
         p = sum(l["mean_rate"][f] * l["codes"] for l in out["levels"]) / total
         out["bytes_per_code"][f] = {"rate": p, "G64": kbytes + p * 64, "G128": kbytes + p * 128}
         print("%-8s weighted rate %.2e   bytes per (code, query): %.3f (G = 64 B)  %.3f (G = 128 B)" % (f, p, kbytes + p * 64, kbytes + p * 128))

@@ -320,7 +320,7 @@ int qadc_kmeans_iterations_host_mode(const float* vectors, uint64_t n, int dim, 
  * assignment in the encoder's layout ([n][sq_count / 2] packed nibbles, or [n][sq_count] bytes) — the codes under the codebooks
  * of BEFORE the last update.  empty_out (nullable): centroids with a NaN component at return.
  * Limits: the learning set is resident for the call; 0 < n < 2^32; dim <= 2048 at 4 bits, <= 4096 at 8 bits (the encoders').
- * sq_bits 16 is refused (QADC_E_ARG): a follow-up.  qadc_pq_train_device: the same with the vectors already in device memory
+ * sq_bits 16 is refused (QADC_E_ARG): qadc_pq_train16_host below learns those.  qadc_pq_train_device: the same with the vectors already in device memory
  * (read only, by kernels); every other pointer is host memory. */
 int qadc_pq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                        const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
@@ -328,6 +328,34 @@ int qadc_pq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, 
 int qadc_pq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                          const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
                          int sum_mode, int device_id);
+
+/* The same for 16-bit sub-quantizers: sq_count 2, 4 or 8, codebooks [sq_count][65536][dsub] in and out.
+ * No float semantics are new: sub-quantizer m ends as kmeans_fast_iterations_thread on columns [m dsub, (m + 1) dsub) started
+ * from codebooks[m].  A round assigns with the 16-bit encoder (qadc_adc_encode16_host's kernels, over the resident learning set in
+ * passes of QADC_ADC_ENCODE16_CHUNK vectors), then updates: per sub-quantizer the vectors are sorted by (code, index) on the GPU
+ * and centroid (m, k) = (its members' sub-vectors summed in ascending vector index into one running float from 0.0f)
+ * * (1.0f / (float)count) (div_mode 1) or / (float)count (div_mode 0).  An empty cluster becomes NaN and stays NaN; empty_out
+ * counts them, nothing repairs them.  K_coarse, coarse, rotation, sum_mode: as for qadc_pq_train_host.  codes_out (nullable,
+ * host memory): little-endian uint16 [n][sq_count], qadc_adc_encode16_host's layout — the last round's assignment, under the
+ * codebooks of BEFORE the last update.  iters == 0 returns the seed untouched, writes no code and touches no device.
+ * Refused with QADC_E_ARG before the first HIP call: sq_count outside {2, 4, 8}; dim not a multiple of it or > 4096; dsub > 2048;
+ * NULL vectors or codebooks; n == 0 or n >= 2^32; iters < 0; K_coarse < 0, or > 0 without coarse; div_mode or sum_mode not 0 or 1.
+ * Limits: the learning set, its residual copy (with coarse or rotation), the codes and two index permutations of n words are
+ * resident for the call.  The update's critical path is the largest cluster: one cluster holding every vector is n dependent
+ * additions on one lane group — correct, and slow.  The OPQ rotation is not learned, the seed is the caller's, and an empty
+ * cluster is not re-seeded.
+ * qadc_pq_train16_device: the vectors already in device memory (read only, by kernels); every other pointer is host memory. */
+int qadc_pq_train16_host(const float* vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                         const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                         int sum_mode, int device_id);
+int qadc_pq_train16_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                           const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                           int sum_mode, int device_id);
+/* The update of qadc_pq_train16_host alone, from codes the caller gives (a caller who assigns by other means): vectors [n][dim]
+ * as the quantizer sees them, codes [n][sq_count] -> codebooks_out [sq_count][65536][dsub], every centroid written (NaN where
+ * empty), and counts_out [sq_count][65536] (nullable) the cluster sizes.  Refusals as above, and NULL codes. */
+int qadc_pq_update16_host(const float* vectors, uint64_t n, int dim, int sq_count, const uint16_t* codes, float* codebooks_out,
+                          uint32_t* counts_out, int div_mode, int device_id);
 
 /* Host-only helper (no GPU involved): push (keys[i], vals[i]), i = 0..n-1, in order into an empty
  * heap of capacity R with kv_binheap<unsigned,int8_t>::push semantics (binheap.hpp:75-116), after

@@ -4,6 +4,7 @@
 #include "qadc_host.h"
 #include "qadc_adc_kernels.h"   // launch_adc_encode: the assignment step of qadc_pq_train at 8 bits
 #include "qadc_pq_train.h"
+#include "qadc_pq_train16.h"
 
 #include <cmath>
 
@@ -231,25 +232,18 @@ uint64_t nan_rows(const float* cb, size_t rows, int ds) {
     return bad;
 }
 
-// d_vectors: the learning set in device memory (read by kernels only: it may belong to another HIP runtime of the process)
-int pq_train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
-                 const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode, int sum_mode,
-                 ScratchFree& mem) {
-    const int ds = dim / sq_count;
-    const size_t rows = (size_t)sq_count << sq_bits, code_bytes = sq_bits == 4 ? sq_count / 2 : sq_count;
-    float *d_cb = nullptr, *d_cbnorm = nullptr, *d_rot = nullptr, *d_coarse = nullptr, *d_x = nullptr, *d_dist = nullptr;
+// What the quantizer sees of the learning set, in device memory: with K_coarse > 0 the residual to the nearest coarse centroid, with a
+// rotation those rotated (as qadc_ivf_encode_host prepares its input).  *d_enc = d_vectors itself where neither is given.
+int pq_train_front_device(const float* d_vectors, uint64_t n, int dim, int K_coarse, const float* coarse, const float* rotation,
+                          int sum_mode, ScratchFree& mem, const float** d_enc) {
+    float *d_rot = nullptr, *d_coarse = nullptr, *d_x = nullptr, *d_dist = nullptr;
     int32_t* d_assign = nullptr;
-    uint8_t* d_codes = nullptr;
-    HIPCHECK(mem.alloc(&d_cb, rows * ds * sizeof(float)));
-    HIPCHECK(hipMemcpy(d_cb, codebooks, rows * ds * sizeof(float), hipMemcpyHostToDevice));
-    if (sq_bits == 8) HIPCHECK(mem.alloc(&d_cbnorm, rows * sizeof(float)));
-    HIPCHECK(mem.alloc(&d_codes, n * code_bytes));
+    *d_enc = d_vectors;
     if (rotation) {
         HIPCHECK(mem.alloc(&d_rot, sizeof(float) * (size_t)dim * dim));
         HIPCHECK(hipMemcpy(d_rot, rotation, sizeof(float) * (size_t)dim * dim, hipMemcpyHostToDevice));
     }
-    const float* d_enc = d_vectors;
-    if (K_coarse > 0) {                                         // as qadc_ivf_encode_host prepares its input
+    if (K_coarse > 0) {
         HIPCHECK(mem.alloc(&d_coarse, sizeof(float) * (size_t)K_coarse * dim));
         HIPCHECK(hipMemcpy(d_coarse, coarse, sizeof(float) * (size_t)K_coarse * dim, hipMemcpyHostToDevice));
         HIPCHECK(mem.alloc(&d_dist, sizeof(float) * ((size_t)std::min<uint64_t>(kBuildChunk, n) * (K_coarse + 1) + K_coarse)));
@@ -259,8 +253,25 @@ int pq_train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int 
     if (K_coarse > 0 || rotation) {
         HIPCHECK(mem.alloc(&d_x, sizeof(float) * n * dim));
         launch_residual_rotate(d_vectors, n, dim, d_coarse, d_assign, d_rot, d_x, nullptr);
-        d_enc = d_x;
+        *d_enc = d_x;
     }
+    return QADC_OK;
+}
+
+// d_vectors: the learning set in device memory (read by kernels only: it may belong to another HIP runtime of the process)
+int pq_train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                 const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode, int sum_mode,
+                 ScratchFree& mem) {
+    const int ds = dim / sq_count;
+    const size_t rows = (size_t)sq_count << sq_bits, code_bytes = sq_bits == 4 ? sq_count / 2 : sq_count;
+    float *d_cb = nullptr, *d_cbnorm = nullptr;
+    uint8_t* d_codes = nullptr;
+    HIPCHECK(mem.alloc(&d_cb, rows * ds * sizeof(float)));
+    HIPCHECK(hipMemcpy(d_cb, codebooks, rows * ds * sizeof(float), hipMemcpyHostToDevice));
+    if (sq_bits == 8) HIPCHECK(mem.alloc(&d_cbnorm, rows * sizeof(float)));
+    HIPCHECK(mem.alloc(&d_codes, n * code_bytes));
+    const float* d_enc = nullptr;
+    if (int rc = pq_train_front_device(d_vectors, n, dim, K_coarse, coarse, rotation, sum_mode, mem, &d_enc)) return rc;
     for (int it = 0; it < iters; ++it) {
         if (sq_bits == 4) {
             launch_pq_encode(d_enc, n, sq_count, dim, d_cb, 1, sum_mode, d_codes, nullptr);
@@ -311,6 +322,147 @@ int qadc_pq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, 
     HIPCHECK(hipMemcpy(d_v, vectors, sizeof(float) * n * dim, hipMemcpyHostToDevice));
     return pq_train_run(d_v, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out, div_mode,
                         sum_mode, mem);
+}
+
+/* ---- PQ training for 16-bit sub-quantizers: a round = launch_adc_encode16 over the resident learning set
+   in passes of QADC_ADC_ENCODE16_CHUNK vectors (norms of the moved centroids recomputed), then launch_pq_train16_update: per
+   sub-quantizer a stable sort of the vectors by code and one chain per (cluster, component). ---- */
+extern "C++" {
+namespace {
+// the argument checks the three entry points share: before the first HIP call
+int pq_train16_check_shape(const float* vectors, uint64_t n, int dim, int sq_count, const float* codebooks, int div_mode) {
+    if (sq_count != 2 && sq_count != 4 && sq_count != 8) return fail(QADC_E_ARG, "sq_count must be 2, 4 or 8 (the 16-bit index's shapes)");
+    if (dim <= 0 || dim % sq_count != 0) return fail(QADC_E_ARG, "dim must be a positive multiple of sq_count");
+    if (dim > adc::kAdcMaxDim) return fail(QADC_E_ARG, "dim must be <= " + std::to_string(adc::kAdcMaxDim) + " (the 16-bit encoder's limit)");
+    PqTrain16Plan plan;
+    if (!pq_train16_plan(sq_count, dim, &plan))
+        return fail(QADC_E_ARG, "dim / sq_count must be <= " + std::to_string(kPqTrain16MaxDsub) + " (the sorted update's plan)");
+    if (!vectors || !codebooks) return fail(QADC_E_ARG, "vectors and codebooks must not be NULL");
+    if (n == 0 || n >= (1ull << 32)) return fail(QADC_E_ARG, "need 0 < n < 2^32 vectors");
+    if (div_mode != 0 && div_mode != 1) return fail(QADC_E_ARG, "div_mode and sum_mode are 0 or 1");
+    return QADC_OK;
+}
+
+int pq_train16_check(const float* vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse, const float* codebooks,
+                     int iters, int div_mode, int sum_mode) {
+    if (int rc = pq_train16_check_shape(vectors, n, dim, sq_count, codebooks, div_mode)) return rc;
+    if (iters < 0) return fail(QADC_E_ARG, "iters must be >= 0");
+    if (K_coarse < 0 || (K_coarse > 0 && !coarse)) return fail(QADC_E_ARG, "K_coarse > 0 needs the coarse centroids");
+    if (sum_mode != 0 && sum_mode != 1) return fail(QADC_E_ARG, "div_mode and sum_mode are 0 or 1");
+    return QADC_OK;
+}
+
+// the scratch of launch_pq_train16_update
+struct Train16Scratch {
+    uint32_t *perm_a = nullptr, *perm_b = nullptr, *hist = nullptr, *start = nullptr;
+    hipError_t alloc(ScratchFree& mem, uint64_t n) {
+        if (hipError_t e = mem.alloc(&perm_a, sizeof(uint32_t) * n)) return e;
+        if (hipError_t e = mem.alloc(&perm_b, sizeof(uint32_t) * n)) return e;
+        if (hipError_t e = mem.alloc(&hist, sizeof(uint32_t) * pq_train16_hist_words((uint32_t)n))) return e;
+        return mem.alloc(&start, sizeof(uint32_t) * (kPqTrain16K + 1));
+    }
+};
+
+// d_vectors: the learning set in device memory (read by kernels only)
+int pq_train16_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse, const float* rotation,
+                   float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode, int sum_mode, ScratchFree& mem) {
+    const int ds = dim / sq_count;
+    const size_t rows = (size_t)sq_count * kPqTrain16K;
+    float *d_cb = nullptr, *d_cbnorm = nullptr;
+    uint16_t* d_codes = nullptr;
+    unsigned long long* d_part = nullptr;
+    Train16Scratch sc;
+    HIPCHECK(mem.alloc(&d_cb, rows * ds * sizeof(float)));
+    HIPCHECK(hipMemcpy(d_cb, codebooks, rows * ds * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHECK(mem.alloc(&d_cbnorm, rows * sizeof(float)));
+    HIPCHECK(mem.alloc(&d_codes, n * sq_count * sizeof(uint16_t)));
+    HIPCHECK(sc.alloc(mem, n));
+    // the encoder's partial picks of a pass: the slices of the largest pass and of the last one (a shorter pass is cut finer)
+    const uint64_t pass = std::min<uint64_t>(QADC_ADC_ENCODE16_CHUNK, n);
+    const uint64_t last = n % QADC_ADC_ENCODE16_CHUNK ? n % QADC_ADC_ENCODE16_CHUNK : pass;
+    const uint64_t part_entries = std::max(pass * adc::encode16_slices((uint32_t)pass, sq_count, ds), last * adc::encode16_slices((uint32_t)last, sq_count, ds));
+    HIPCHECK(mem.alloc(&d_part, part_entries * sq_count * sizeof(unsigned long long)));
+    const float* d_enc = nullptr;
+    if (int rc = pq_train_front_device(d_vectors, n, dim, K_coarse, coarse, rotation, sum_mode, mem, &d_enc)) return rc;
+    for (int it = 0; it < iters; ++it) {                       // queued on the default stream: nothing waits inside a round
+        launch_row_sqnorm(d_cb, (int)rows, ds, sum_mode, d_cbnorm, nullptr);
+        for (uint64_t o = 0; o < n; o += QADC_ADC_ENCODE16_CHUNK) {
+            const uint64_t cnt = std::min<uint64_t>(QADC_ADC_ENCODE16_CHUNK, n - o);
+            HIPCHECK(adc::launch_adc_encode16(d_enc + o * dim, (uint32_t)cnt, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_part,
+                                              d_codes + o * sq_count, nullptr));
+        }
+        HIPCHECK(launch_pq_train16_update(d_enc, (uint32_t)n, dim, sq_count, d_codes, d_cb, nullptr, div_mode, sc.perm_a, sc.perm_b, sc.hist,
+                                          sc.start, nullptr));
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(codebooks, d_cb, rows * ds * sizeof(float), hipMemcpyDeviceToHost));
+    if (codes_out) HIPCHECK(hipMemcpy(codes_out, d_codes, n * sq_count * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (empty_out) *empty_out = nan_rows(codebooks, rows, ds);
+    return QADC_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int qadc_pq_train16_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                           const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                           int sum_mode, int device_id) {
+    if (int rc = pq_train16_check(d_vectors, n, dim, sq_count, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (iters == 0) {                                          // the seed untouched, no code written
+        if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count * kPqTrain16K, dim / sq_count);
+        return QADC_OK;
+    }
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(device_id));
+    ScratchFree mem;
+    return pq_train16_run(d_vectors, n, dim, sq_count, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out, div_mode,
+                          sum_mode, mem);
+}
+
+int qadc_pq_train16_host(const float* vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                         const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                         int sum_mode, int device_id) {
+    if (int rc = pq_train16_check(vectors, n, dim, sq_count, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (iters == 0) {
+        if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count * kPqTrain16K, dim / sq_count);
+        return QADC_OK;
+    }
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(device_id));
+    ScratchFree mem;                                           // the learning set goes up once, for every sub-space and round
+    float* d_v = nullptr;
+    HIPCHECK(mem.alloc(&d_v, sizeof(float) * n * dim));
+    HIPCHECK(hipMemcpy(d_v, vectors, sizeof(float) * n * dim, hipMemcpyHostToDevice));
+    return pq_train16_run(d_v, n, dim, sq_count, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out, div_mode, sum_mode,
+                          mem);
+}
+
+int qadc_pq_update16_host(const float* vectors, uint64_t n, int dim, int sq_count, const uint16_t* codes, float* codebooks_out,
+                          uint32_t* counts_out, int div_mode, int device_id) {
+    if (int rc = pq_train16_check_shape(vectors, n, dim, sq_count, codebooks_out, div_mode)) return rc;
+    if (!codes) return fail(QADC_E_ARG, "codes must not be NULL");
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(device_id));
+    ScratchFree mem;
+    const int ds = dim / sq_count;
+    const size_t rows = (size_t)sq_count * kPqTrain16K;
+    float *d_v = nullptr, *d_cb = nullptr;
+    uint16_t* d_codes = nullptr;
+    uint32_t* d_counts = nullptr;
+    Train16Scratch sc;
+    HIPCHECK(mem.alloc(&d_v, sizeof(float) * n * dim));
+    HIPCHECK(mem.alloc(&d_cb, rows * ds * sizeof(float)));
+    HIPCHECK(mem.alloc(&d_codes, n * sq_count * sizeof(uint16_t)));
+    if (counts_out) HIPCHECK(mem.alloc(&d_counts, rows * sizeof(uint32_t)));
+    HIPCHECK(sc.alloc(mem, n));
+    HIPCHECK(hipMemcpy(d_v, vectors, sizeof(float) * n * dim, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(d_codes, codes, n * sq_count * sizeof(uint16_t), hipMemcpyHostToDevice));
+    HIPCHECK(launch_pq_train16_update(d_v, (uint32_t)n, dim, sq_count, d_codes, d_cb, d_counts, div_mode, sc.perm_a, sc.perm_b, sc.hist,
+                                      sc.start, nullptr));
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(codebooks_out, d_cb, rows * ds * sizeof(float), hipMemcpyDeviceToHost));
+    if (counts_out) HIPCHECK(hipMemcpy(counts_out, d_counts, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return QADC_OK;
 }
 
 }  // extern "C"

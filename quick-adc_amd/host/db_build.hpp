@@ -12,6 +12,7 @@
 //                                          here), then runs kmeans_iter_max - 2 = 48 fast iterations — those run on the GPU
 //   pq_train_iterations(...)               CPU twin of qadc_pq_train_host: kmeans_fast_iterations on a copy of every sub-space's
 //                                          columns, behind the same residual / rotation front
+//   pq_train16_iterations(...), pq_update16(...)  the same for 16-bit sub-quantizers (qadc_pq_train16_host, qadc_pq_update16_host)
 //   learn_pq_hip(...)                      the product quantizer learned on the GPU from a caller-provided seed, as an io::pq_data
 //                                          ready for pq_to_data_file (the reference's flatdb_create / indexdb_create2 read it)
 //   db_add_hip(db, base_file, chunk_count) db_add's add_vectors (db_add.cpp:52-82): a reader thread (io::vectors_reader,
@@ -230,6 +231,59 @@ inline std::uint64_t pq_train_iterations(const float* vecs, size_t n, int dim, i
     return empty;
 }
 
+// CPU twin of qadc_pq_update16_host: the centroid update for 16-bit sub-quantizers alone, from given codes.  vecs [n][dim] as the
+// quantizer sees them, codes [n][sq_count] -> codebooks [sq_count][65536][dsub], every centroid written (NaN where empty), and
+// counts [sq_count][65536] (nullable).  One pass in vector order: every running sum takes its members in ascending index.
+inline void pq_update16(const float* vecs, size_t n, int dim, int sq_count, const std::uint16_t* codes, float* codebooks,
+                        std::uint32_t* counts, int div_mode = 1) {
+    if (sq_count <= 0 || dim <= 0 || dim % sq_count) throw std::runtime_error("pq_update16: dim a positive multiple of sq_count");
+    const int ds = dim / sq_count;
+    const size_t K = 65536;
+    std::vector<std::uint32_t> cnt((size_t)sq_count * K, 0u);
+    std::fill(codebooks, codebooks + (size_t)sq_count * K * ds, 0.0f);
+    for (size_t i = 0; i < n; ++i)
+        for (int m = 0; m < sq_count; ++m) {
+            const size_t r = (size_t)m * K + codes[i * sq_count + m];
+            cnt[r]++;
+            for (int d = 0; d < ds; ++d) codebooks[r * ds + d] += vecs[i * dim + (size_t)m * ds + d];
+        }
+    for (size_t r = 0; r < (size_t)sq_count * K; ++r) {
+        const volatile float rcp = 1.0f / (float)(int)cnt[r];     // (volatile: the host compiler must not fold the two forms)
+        for (int d = 0; d < ds; ++d) {
+            float& c = codebooks[r * ds + d];
+            c = div_mode ? c * rcp : c / (float)(int)cnt[r];
+        }
+    }
+    if (counts) std::copy(cnt.begin(), cnt.end(), counts);
+}
+
+// CPU twin of qadc_pq_train16_host: pq_train_iterations for 65536 centroids per sub-quantizer (sq_count 2, 4 or 8), codes (nullable)
+// uint16 [n][sq_count].  Returns the centroids that hold a NaN.  iters == 0 changes nothing and writes no code.
+inline std::uint64_t pq_train16_iterations(const float* vecs, size_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                                           const float* rotation, float* codebooks, int iters, std::uint16_t* codes, int div_mode = 1) {
+    if ((sq_count != 2 && sq_count != 4 && sq_count != 8) || dim <= 0 || dim % sq_count)
+        throw std::runtime_error("pq_train16_iterations: sq_count 2, 4 or 8, dim a multiple of it");
+    const int ds = dim / sq_count, K = 65536;
+    if (iters > 0) {
+        const std::vector<float> x = pq_train_front(vecs, n, dim, K_coarse, coarse, rotation);
+        std::vector<float> slice(n * (size_t)ds);
+        std::vector<int> assign(n);
+        for (int m = 0; m < sq_count; ++m) {
+            for (size_t i = 0; i < n; ++i) std::copy(x.begin() + i * dim + (size_t)m * ds, x.begin() + i * dim + (size_t)(m + 1) * ds, slice.begin() + i * ds);
+            kmeans_fast_iterations(slice.data(), n, ds, K, codebooks + (size_t)m * K * ds, iters, assign.data(), div_mode);
+            if (codes)
+                for (size_t i = 0; i < n; ++i) codes[i * sq_count + m] = (std::uint16_t)assign[i];
+        }
+    }
+    std::uint64_t empty = 0;
+    for (size_t r = 0; r < (size_t)sq_count * K; ++r) {
+        bool nan = false;
+        for (int d = 0; d < ds; ++d) nan = nan || codebooks[r * ds + d] != codebooks[r * ds + d];
+        empty += nan;
+    }
+    return empty;
+}
+
 // The product quantizer learned on the GPU: `iters` rounds from `seed` [sq_count][2^sq_bits][dim / sq_count] on the learning set
 // (made residuals to `coarse` and rotated where given: what indexdb_create1 / indexdb_create2 put before the quantizer).  The
 // result carries the rotation, so that pq_to_data_file writes a .pq.data or .opq.data the reference's executables read.
@@ -245,6 +299,12 @@ inline io::pq_data learn_pq_hip(const float* vecs, size_t n, int dim, int sq_cou
     if (rotation) {
         pq.is_opq = true;
         pq.rotation.assign(rotation, rotation + (size_t)dim * dim);
+    }
+    if (sq_bits == 16) {                                        // 65536 centroids per sub-quantizer: the sorted update
+        if (qadc_pq_train16_host(vecs, n, dim, sq_count, K_coarse, coarse, rotation, pq.centroids.data(), iters, nullptr, empty_out, 1, 1,
+                                 device) != QADC_OK)
+            throw std::runtime_error(std::string("qadc_pq_train16_host: ") + qadc_last_error());
+        return pq;
     }
     if (qadc_pq_train_host(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, pq.centroids.data(), iters, nullptr, empty_out, 1,
                            1, device) != QADC_OK)

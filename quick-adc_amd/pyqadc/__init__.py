@@ -48,6 +48,7 @@ SYMBOLS = [
     "qadc_index_relocations",
     "qadc_adc_index_remove_labels", "qadc_adc_index_remove_labels_device", "qadc_index_remove_labels", "qadc_index_remove_labels_device",
     "qadc_pq_train_host", "qadc_pq_train_device",
+    "qadc_pq_train16_host", "qadc_pq_train16_device", "qadc_pq_update16_host",
 ]
 
 
@@ -221,6 +222,10 @@ def lib():
         L.qadc_pq_train_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_int, C.c_void_p, u64p,
                                          C.c_int, C.c_int, C.c_int]
         L.qadc_pq_train_device.argtypes = [C.c_void_p] + L.qadc_pq_train_host.argtypes[1:]
+        L.qadc_pq_train16_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_int, C.c_void_p, u64p,
+                                           C.c_int, C.c_int, C.c_int]
+        L.qadc_pq_train16_device.argtypes = [C.c_void_p] + L.qadc_pq_train16_host.argtypes[1:]
+        L.qadc_pq_update16_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, f32p, u32p, C.c_int, C.c_int]
         for name in ("qadc_adc_index_remove_labels", "qadc_index_remove_labels"):
             getattr(L, name).argtypes = [C.c_void_p, u32p, C.c_uint64, u64p]
             getattr(L, name + "_device").argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p]
@@ -474,6 +479,74 @@ def train_pq_device(vectors, codebooks_seed, iters, bits=None, coarse=None, rota
                                       _p(rot, f32p), _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode,
                                       sum_mode, vectors.device.index or 0))
     return cb, codes, int(empty.value)
+
+
+def _train_pq16_args(dim, codebooks_seed, coarse, rotation):
+    cb, bits, co, rot = _train_pq_args(dim, codebooks_seed, None, coarse, rotation)
+    if bits != 16:
+        raise QadcError("codebooks_seed has shape %s, expected [sq_count][65536][dim / sq_count] (train_pq learns 4- and 8-bit "
+                        "sub-quantizers)" % (tuple(cb.shape),))
+    return cb, co, rot
+
+
+def train_pq16(vectors, codebooks_seed, iters, coarse=None, rotation=None, device=0, div_mode=1, sum_mode=1):
+    """Learn a product quantizer of 16-bit sub-quantizers on the GPU (qadc_pq_train16_host): train_pq with a seed
+    [sq_count][65536][dim / sq_count], sq_count 2, 4 or 8 (pq_seed(v, sq_count, 16, rng)).  A round is the 16-bit encoder and the
+    sorted centroid update.  -> (codebooks float32 like the seed, codes uint16 [n][sq_count] of the last round — adc_encode16's
+    layout —, empty = centroids that are NaN at return)."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2:
+        raise QadcError("vectors has shape %s, expected [n][dim]" % (tuple(v.shape),))
+    n, dim = v.shape
+    cb, co, rot = _train_pq16_args(dim, codebooks_seed, coarse, rotation)
+    nsq = cb.shape[0]
+    codes = np.zeros((n, nsq), "<u2")
+    empty = C.c_uint64(0)
+    _check(lib().qadc_pq_train16_host(_p(v, f32p), n, dim, nsq, 0 if co is None else co.shape[0], _p(co, f32p), _p(rot, f32p), _p(cb, f32p),
+                                      iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode, sum_mode, device))
+    return cb, codes.astype(np.uint16, copy=False), int(empty.value)
+
+
+def train_pq16_device(vectors, codebooks_seed, iters, coarse=None, rotation=None, div_mode=1, sum_mode=1):
+    """train_pq16 on a learning set already in device memory: a contiguous float32 [n][dim] torch tensor on a GPU (read only).  The
+    seed, coarse and rotation are host arrays; the results come back as numpy arrays like train_pq16's."""
+    import torch
+    if not isinstance(vectors, torch.Tensor):
+        raise TypeError("vectors must be a torch.Tensor, not %s" % type(vectors).__name__)
+    if vectors.dtype != torch.float32:
+        raise TypeError("vectors must be float32, not %s" % vectors.dtype)
+    if vectors.device.type != "cuda":
+        raise QadcError("vectors is on %s; train_pq16_device takes a tensor in device memory" % vectors.device)
+    if vectors.ndim != 2 or not vectors.is_contiguous():
+        raise QadcError("vectors must be a contiguous [n][dim] tensor")
+    n, dim = int(vectors.shape[0]), int(vectors.shape[1])
+    cb, co, rot = _train_pq16_args(dim, codebooks_seed, coarse, rotation)
+    nsq = cb.shape[0]
+    codes = np.zeros((n, nsq), "<u2")
+    empty = C.c_uint64(0)
+    torch.cuda.current_stream(vectors.device).synchronize()                # the learning set is complete before the call
+    _check(lib().qadc_pq_train16_device(C.c_void_p(vectors.data_ptr()), n, dim, nsq, 0 if co is None else co.shape[0], _p(co, f32p),
+                                        _p(rot, f32p), _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode,
+                                        sum_mode, vectors.device.index or 0))
+    return cb, codes.astype(np.uint16, copy=False), int(empty.value)
+
+
+def pq_update16(vectors, codes, sq_count, div_mode=1, device=0):
+    """The centroid update of train_pq16 alone (qadc_pq_update16_host), from codes the caller gives: vectors [n][dim] as the
+    quantizer sees them, codes uint16 [n][sq_count] -> (codebooks float32 [sq_count][65536][dim / sq_count], NaN where a cluster
+    is empty, counts uint32 [sq_count][65536])."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    c = np.ascontiguousarray(codes, "<u2")
+    if v.ndim != 2 or c.shape != (v.shape[0], sq_count):
+        raise QadcError("vectors %s and codes %s: expected [n][dim] and [n][%d]" % (tuple(v.shape), tuple(c.shape), sq_count))
+    n, dim = v.shape
+    if sq_count <= 0 or dim % sq_count:
+        raise QadcError("dim %d is not a multiple of sq_count %d" % (dim, sq_count))
+    cb = np.zeros((sq_count, 65536, dim // sq_count), np.float32)
+    counts = np.zeros((sq_count, 65536), np.uint32)
+    _check(lib().qadc_pq_update16_host(_p(v, f32p), n, dim, sq_count, c.ctypes.data_as(C.c_void_p), _p(cb, f32p), _p(counts, u32p), div_mode,
+                                       device))
+    return cb, counts
 
 
 def pq_seed(vectors, sq_count, bits, rng):

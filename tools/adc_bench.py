@@ -3,7 +3,7 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
 
   python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
   batch32   32 queries per call on the same list
@@ -66,6 +66,17 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             adds at 78.6e12 per second: half the 157.3 TFLOPS vector peak, which counts a fused multiply-add as two); beside one
             CPU thread of the host twin's pq_bytes::encode (tools/encode16_host_twin.cpp: a port, not the reference's build) timed
             on 256 of the vectors and EXTRAPOLATED to n, its codes asserted equal to the GPU's
+  train     learning 16-bit sub-quantizers (not in the default legs): 10^6 clustered 128-d vectors at 2x16, 4x16 and 8x16, 2 rounds from
+            a seed of 65536 distinct rows (pyqadc.pq_seed).  train_pq16, call to return (the upload of the learning set included),
+            alternated in one process with the route without it: kmeans_iterations on every host slice (8.6 GB of distance scratch
+            at 65536 centroids); the two routes' codebooks and codes are first asserted equal bit for bit.  Where that route cannot
+            get its scratch the leg says so and times one CPU thread of the host twin (tests/cpp/pq_train16_host.cpp) on 256 vectors,
+            EXTRAPOLATED to n.  A round's time is the difference of a 4-round and a 2-round call; beside it one adc_encode16 call on
+            the same vectors (its upload included), which bounds the share of a round spent outside the encoder from below.  Under
+            rocprofv3 --kernel-trace --stats the leg `train_profile` (one 2-round call per shape, not timed) gives the kernels' own share
+  remove    the 8-bit `remove` leg on an index of 16-bit codes at 2x16 (not in the default legs)
+  --trained-codebooks   the 16-bit add, remove and ivf_search (encoded database) legs learn their codebooks with train_pq16: 10 rounds
+            on the residuals of the first min(n, 10^6) vectors, seeded with 65536 sampled residuals
   profile   not timed: five one-query calls on 10^8 codes at 8x16, then two search() calls of 64 queries at the ivf_search shape —
             the workload of a rocprofv3 --pmc run for the scan kernel's L2 hit rate (TCC_HIT_sum, TCC_MISS_sum)
 Every time is a host clock around whole synchronous calls (median of --iters after warm-up); R = 100, sum_mode 1."""
@@ -391,6 +402,112 @@ def trained_codebooks(vectors, coarse, nsq, bits, rng):
     return codebooks
 
 
+def trained_codebooks16(vectors, coarse, nsq, rng):
+    """--trained-codebooks at 16 bits: 10 rounds of train_pq16 on the residuals of the first min(n, 10^6) vectors (at least 65536),
+    seeded with 65536 sampled residuals"""
+    learn = vectors[:1_000_000]
+    assert len(learn) >= 65536, "learning 16-bit sub-quantizers takes at least 65536 vectors"
+    sample = learn[rng.choice(len(learn), 65536, replace=False)]
+    near = pyqadc.coarse_assign(sample, coarse, 1)[:, 0]
+    seed = np.ascontiguousarray((sample - coarse[near]).reshape(65536, nsq, vectors.shape[1] // nsq).transpose(1, 0, 2), np.float32)
+    t0 = time.perf_counter()
+    codebooks, _, empty = pyqadc.train_pq16(learn, seed, 10, coarse=coarse)
+    print("codebooks %dx16 learned by train_pq16 on %d residuals in %.2f s (%d empty clusters)" % (nsq, len(learn), time.perf_counter() - t0, empty),
+          flush=True)
+    if empty:                                                    # an empty cluster is NaN and not repaired: it keeps its seed row here
+        nan = np.isnan(codebooks).any(axis=2)
+        codebooks[nan] = seed[nan]
+    return codebooks
+
+
+def cpu_twin_train16(vectors, seed, rounds):
+    """one thread of the host twin's pq_train16_iterations (tests/cpp/pq_train16_host.cpp) -> seconds"""
+    import subprocess
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        exe, fin, fout = os.path.join(d, "twin"), os.path.join(d, "in"), os.path.join(d, "out")
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", os.path.join(ROOT, "tests", "cpp", "pq_train16_host.cpp"), "-o", exe])
+        with open(fin, "wb") as f:
+            np.array([len(vectors), vectors.shape[1], seed.shape[0], 0, 0, rounds, 1], np.int32).tofile(f)
+            np.ascontiguousarray(vectors, np.float32).tofile(f)
+            np.ascontiguousarray(seed, np.float32).tofile(f)
+        t0 = time.perf_counter()
+        subprocess.run([exe, "run", fin, fout], stdout=subprocess.PIPE, check=True)
+        return time.perf_counter() - t0
+
+
+def same_bits(a, b):
+    nan = np.isnan(a)
+    return np.array_equal(nan, np.isnan(b)) and bool(((a.view(np.uint32) == b.view(np.uint32)) | nan).all())
+
+
+def train16_leg(iters, res, profile_only=False):
+    """train_pq16 alternated with the route without it: kmeans_iterations on every host slice"""
+    rng = np.random.default_rng(1916)
+    n, dim, rounds, twin_n = 1_000_000, 128, 2, 256
+    vectors, _ = clustered(rng, n, dim)
+    for nsq in (2, 4, 8):
+        ds = dim // nsq
+        seed = pyqadc.pq_seed(vectors, nsq, 16, rng)
+        tag = "train_%dx16_n%d" % (nsq, n)
+
+        def new_route(r=rounds):
+            return pyqadc.train_pq16(vectors, seed, r)
+
+        def slice_route():
+            cb = np.zeros_like(seed)
+            assign = np.zeros((n, nsq), np.uint16)
+            for m in range(nsq):
+                cb[m], a = pyqadc.kmeans_iterations(np.ascontiguousarray(vectors[:, m * ds:(m + 1) * ds]), seed[m], rounds)
+                assign[:, m] = a
+            return cb, assign
+
+        cb, codes, empty = new_route()
+        if profile_only:
+            continue
+        res[tag + "_empty_clusters"] = int(empty)
+        try:
+            cb2, assign = slice_route()
+        except pyqadc.QadcError as e:
+            twin_s = cpu_twin_train16(vectors[:twin_n], seed, rounds)
+            med_new, lo, hi = spread(new_route, max(5, iters // 2), warmup=1)
+            res[tag + "_train_pq16_s_median_min_max"] = [med_new, lo, hi]
+            res[tag + "_host_twin_thread_extrapolated_s"] = twin_s * n / twin_n
+            print("PQ training %dx16, %.0e clustered 128-d vectors, %d rounds: kmeans_iterations per host slice cannot run here (%s); train_pq16 "
+                  "%.3f s (%.3f .. %.3f); one CPU thread of the host twin, %d vectors in %.2f s, EXTRAPOLATED to n: %.0f s"
+                  % (nsq, n, rounds, e, med_new, lo, hi, twin_n, twin_s, twin_s * n / twin_n), flush=True)
+        else:
+            assert same_bits(cb, cb2), "the routes' codebooks differ"
+            assert np.array_equal(codes, assign), "the routes' codes differ"
+            count = max(5, iters // 2)
+            tn, to = [], []
+            for _ in range(count):                               # A B A B ...; the calls above were the warm-up of each arm
+                for f, ts in ((new_route, tn), (slice_route, to)):
+                    t0 = time.perf_counter()
+                    f()
+                    ts.append(time.perf_counter() - t0)
+            med_new, med_old = float(np.median(tn)), float(np.median(to))
+            res[tag + "_train_pq16_s_median_min_max"] = [med_new, min(tn), max(tn)]
+            res[tag + "_kmeans_per_slice_s_median_min_max"] = [med_old, min(to), max(to)]
+            res[tag + "_slices_over_train_pq16"] = med_old / med_new
+            print("PQ training %dx16, %.0e clustered 128-d vectors, %d rounds, host to host, %d alternations: train_pq16 %.3f s (%.3f .. %.3f); "
+                  "kmeans_iterations on %d host slices %.3f s (%.3f .. %.3f) = %.2fx (equal bits; %d empty clusters)"
+                  % (nsq, n, rounds, count, med_new, min(tn), max(tn), nsq, med_old, min(to), max(to), med_old / med_new, empty), flush=True)
+        # a round = the difference of a 2 * rounds call and a rounds call (the upload and the fixed costs cancel); the encoder's call
+        # carries its own upload, so 1 - encode / round is a lower bound of the share spent outside the encoder
+        long_s, _ = timed(lambda: new_route(2 * rounds), 3, warmup=0)
+        short_s, _ = timed(new_route, 3, warmup=0)
+        enc_s, _ = timed(lambda: pyqadc.adc_encode16(seed, vectors), 3, warmup=0)
+        round_s = (long_s - short_s) / rounds
+        roof = 2.0 * n * dim * 65536 / PACKED_VALU_OPS
+        res[tag + "_round_s"] = round_s
+        res[tag + "_adc_encode16_call_s"] = enc_s
+        outside = max(0.0, 1.0 - enc_s / round_s) if round_s > 0 else float("nan")      # (nan: the difference drowned in the clock's noise)
+        res[tag + "_share_outside_encoder_at_least"] = outside
+        print("  a round (4-round call minus 2-round call, halved): %.3f s; one adc_encode16 call, upload included: %.3f s (packed-VALU roof "
+              "%.3f s): the share of a round outside the encoder is at least %.3f" % (round_s, enc_s, roof, outside), flush=True)
+
+
 def train_leg(bits, iters, res):
     """train_pq alternated with the route without it: kmeans_iterations on every host slice"""
     rng = np.random.default_rng(1900 + bits)
@@ -437,8 +554,8 @@ def add_leg(bits, iters, res):
     coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, K, replace=False)], 5)
     sample = vectors[rng.choice(n, 1 << bits, replace=False)]
     codebooks = np.ascontiguousarray(sample.reshape(1 << bits, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
-    if TRAINED and bits != 16:
-        codebooks = trained_codebooks(vectors, coarse, nsq, bits, rng)
+    if TRAINED:
+        codebooks = trained_codebooks16(vectors, coarse, nsq, rng) if bits == 16 else trained_codebooks(vectors, coarse, nsq, bits, rng)
     encode = {4: pyqadc.ivf_encode, 8: pyqadc.adc_encode, 16: pyqadc.adc_encode16}[bits]
 
     def make():
@@ -512,16 +629,16 @@ def remove_leg(bits, iters, res):
     """remove_labels alternated with the route without it: read_partition of every partition, the filter on the host, add_partitions"""
     rng = np.random.default_rng(1800 + bits)
     n, dim = 1_000_000, 128
-    nsq = {4: 16, 8: 8}[bits]
+    nsq = {4: 16, 8: 8, 16: 2}[bits]
     vectors, _ = clustered(rng, n, dim)
     coarse, _ = pyqadc.kmeans_iterations(vectors[:100000], vectors[rng.choice(n, 256, replace=False)], 5)
     sample = vectors[rng.choice(n, 1 << bits, replace=False)]
     codebooks = np.ascontiguousarray(sample.reshape(1 << bits, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
     if TRAINED:
-        codebooks = trained_codebooks(vectors, coarse, nsq, bits, rng)
+        codebooks = trained_codebooks16(vectors, coarse, nsq, rng) if bits == 16 else trained_codebooks(vectors, coarse, nsq, bits, rng)
 
     def make():
-        return pyqadc.Index(nsq) if bits == 4 else pyqadc.AdcIndex(nsq, 8)
+        return pyqadc.Index(nsq) if bits == 4 else pyqadc.AdcIndex(nsq, 8) if bits == 8 else pyqadc.AdcIndex.create16(nsq)
 
     def read_all(idx):
         return [idx.read_partition(k) for k in range(idx.partition_count())]
@@ -620,6 +737,8 @@ def encoded_search_leg(iters, res):
     exact = [np.argpartition(vnorm - 2.0 * (vectors @ queries[q]), R)[:R] for q in range(nq_exact)]
     for nsq in (2, 4, 8):
         codebooks = np.ascontiguousarray(residual.reshape(65536, nsq, dim // nsq).transpose(1, 0, 2), np.float32)
+        if TRAINED:
+            codebooks = trained_codebooks16(vectors, coarse, nsq, rng)
         t0 = time.perf_counter()
         part_of, codes = pyqadc.adc_encode16(codebooks, vectors, coarse)
         t_enc = time.perf_counter() - t0
@@ -727,6 +846,10 @@ def word_legs(legs, iters, res):
         encode16_leg(iters, res)
     if "add" in legs:
         add_leg(16, iters, res)
+    if "remove" in legs:
+        remove_leg(16, iters, res)
+    if "train" in legs or "train_profile" in legs:
+        train16_leg(iters, res, profile_only="train" not in legs)
     if "profile" in legs:
         n = 100_000_000
         idx = pyqadc.AdcIndex.create16(8)

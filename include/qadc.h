@@ -891,6 +891,47 @@ int qadc_index_remove_labels(qadc_index* idx, const uint32_t* labels, uint64_t c
 /* The same with d_labels [count] in device memory of the index's device, as qadc_adc_index_remove_labels_device. */
 int qadc_index_remove_labels_device(qadc_index* idx, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out);
 
+/* ---- filtered float-ADC search: allow and exclude key sets ----
+ * The KEY of a row is what the scan emits for it: labels[i] on a labelled partition, else key_base + position (key_base 0 on an
+ * owned index; a view's qadc_index_set_key_base).  A filter is a set S of keys and a mode:
+ *   QADC_ADC_FILTER_EXCLUDE  a row is dropped iff its key is in S      (tombstones, "not these ids", access control)
+ *   QADC_ADC_FILTER_ALLOW    a row is dropped iff its key is not in S  ("only among these ids")
+ * With a filter set on an index, every scanning call — qadc_adc_query_scan, _query_scan_device, _query_scan_candidates, qadc_adc_search,
+ * _search_device, _search_candidates — returns what scanner_simple::query_scan (db_query.cpp:26-45) returns over partitions from which
+ * the dropped rows have been deleted, the surviving rows' keys given as labels: in the loops of scan_standard (query_common.hpp:92-118)
+ * and scan_4 (59-90) a dropped row is skipped before `candidate < min` is looked at, so it is never pushed and never lowers min for a
+ * later row.  On a labelled index under EXCLUDE these are the arrays after qadc_adc_index_remove_labels of S, with the index untouched.
+ * The *_candidates calls return the reference's pushes on that reduced database (a superset of them, as without a filter), in scan
+ * order.  qadc_adc_search_tables does not scan and is unaffected.  Every code is still read: a filter saves no scan time, and a very
+ * selective ALLOW set costs a full scan and a label read per row until R survivors have been seen. */
+#define QADC_ADC_FILTER_EXCLUDE 0
+#define QADC_ADC_FILTER_ALLOW 1
+typedef struct qadc_adc_filter qadc_adc_filter;
+/* A filter over keys [count] in host memory, on device_id: a bitmap over [lo, hi] of the keys in device memory (one bit per key of the
+ * span: at most 512 MiB, the whole key space), built on the GPU from the list uploaded once.  Duplicates are legal.  count = 0 is legal
+ * (keys may be NULL then): EXCLUDE of nothing filters nothing, ALLOW of nothing lets no row pass and every heap holds its R sentinels, as
+ * the reference's on empty partitions.  The filter is immutable and independent of any index; the call is synchronous.
+ * QADC_E_ARG before the device is touched: out NULL, a mode other than the two, keys NULL with count > 0.  QADC_E_HIP: the bitmap or
+ * the list could not be allocated; nothing is left behind. */
+int qadc_adc_filter_create(qadc_adc_filter** out, int mode, const uint32_t* keys, uint64_t count, int device_id);
+/* The same with d_keys [count] in device memory of device_id, complete before the call: read where they lie and only by kernels, so
+ * memory of another HIP runtime (the keys qadc_adc_search_device returned) is legal.  lo and hi come from a reduction kernel and one
+ * synchronise more than the host form. */
+int qadc_adc_filter_create_device(qadc_adc_filter** out, int mode, const uint32_t* d_keys, uint64_t count, int device_id);
+/* What the filter holds (any output may be NULL): its mode, the smallest and largest key of the set (an empty set: lo = 2^32 - 1,
+ * hi = 0) and the bytes of its bitmap, 4 * ceil((hi - lo + 1) / 32) (an empty set: 4). */
+int qadc_adc_filter_info(const qadc_adc_filter* f, int* mode, uint32_t* lo, uint32_t* hi, uint64_t* bitmap_bytes);
+/* Frees the filter.  QADC_E_STATE while it is set on an index (the filter stays intact); NULL is a no-op. */
+int qadc_adc_filter_destroy(qadc_adc_filter* f);
+/* Sets the filter every later scanning call of idx applies (an owned 8-bit or 16-bit index, or a view), or clears it (f NULL: the
+ * calls return what they returned before, bit for bit).  The index counts a use on the filter until it is cleared, replaced or the
+ * index destroyed; one filter may be set on several indexes of its device.  Applied in the scan kernel in front of the emit of every
+ * level launch, so levels, bounds, re-runs, sub-batches and both finishes (qadc_adc_index_set_finish) hold as they are on the reduced
+ * database.  qadc_adc_index_add_vectors* and _remove_labels* are legal while a filter is set: the filter is about keys, not rows, and
+ * stays as it is.  QADC_E_ARG: idx NULL, a filter of another device.  Not per query of a batch, and not on the int8 4-bit engine
+ * (qadc_query_scan, qadc_search), whose users filter through a view (qadc_adc_index_create_view). */
+int qadc_adc_index_set_filter(qadc_adc_index* idx, const qadc_adc_filter* f);
+
 #ifdef __cplusplus
 }
 #endif

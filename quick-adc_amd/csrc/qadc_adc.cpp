@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
 #include <cstring>
 #include <limits>
@@ -50,8 +51,20 @@ constexpr uint64_t kMaxEntries = QADC_ADC_MAX_ENTRIES;   // candidate entries of
 
 }  // namespace
 
+// A key filter (qadc_adc_filter_create*): the bitmap of the caller's key set in device memory, immutable
+// once created, and the number of indexes it is set on.
+struct qadc_adc_filter {
+    int device = 0, mode = QADC_ADC_FILTER_EXCLUDE;
+    uint32_t lo = 0xffffffffu, hi = 0;              // the smallest and largest key of the set (an empty set: lo > hi)
+    qadc::adc::RemoveSpan span;                     // the bitmap's span: [lo, hi], or the one zero word [0, 0] of an empty set
+    uint32_t* bitmap = nullptr;                     // span.words words, owned by mem
+    qadc::host::Scratch mem;
+    mutable std::atomic<int> uses{0};               // indexes that hold it (qadc_adc_index_set_filter)
+};
+
 struct qadc_adc_index {
     int nsq = 0, device = 0;
+    const qadc_adc_filter* filter = nullptr;        // set: every scan launch drops the rows whose key does not pass it
     int centroids = 256;                            // per sub-quantizer: a table is [nsq][centroids] floats (16: a view; 65536: 16-bit codes)
     int code_size() const { return centroids == 65536 ? 2 * nsq : nsq; }   // bytes of one code of the owned database
     // A view (qadc_adc_index_create_view): the 4-bit index whose partitions, labels and quantizers it reads in place, counted
@@ -141,8 +154,11 @@ struct DeviceOut { uint32_t* keys; float* values; int32_t* sizes; };
 
 // The database as the scan launcher takes it: the owned codes, or the partition table of a view.
 ScanDb scan_db(const qadc_adc_index* idx) {
-    if (idx->src) return ScanDb{idx->nsq, idx->centroids, Db{}, idx->d_parts4.p};
-    return ScanDb{idx->nsq, idx->centroids, Db{idx->codes.p, idx->d_off.p, idx->labeled == 1 ? idx->labels.p : nullptr, idx->d_lab_off.p}, nullptr};
+    ScanFilter filter;
+    if (const qadc_adc_filter* f = idx->filter) filter = ScanFilter{f->bitmap, f->span.lo, f->span.last, f->mode};
+    if (idx->src) return ScanDb{idx->nsq, idx->centroids, Db{}, idx->d_parts4.p, filter};
+    return ScanDb{idx->nsq, idx->centroids, Db{idx->codes.p, idx->d_off.p, idx->labeled == 1 ? idx->labels.p : nullptr, idx->d_lab_off.p}, nullptr,
+                  filter};
 }
 
 // One batch on its way through scan_batch: the plan, where the batch lies in the staging buffers idx->h_in / idx->d_in, uploaded in one copy —
@@ -921,9 +937,102 @@ int remove_labels(qadc_adc_index* idx, const uint32_t* list, uint64_t count, uin
     return QADC_OK;
 }
 
+// The index lets go of its filter (qadc_adc_index_set_filter, qadc_adc_index_destroy): no scan of the index is in flight, every
+// scanning call is synchronous.
+void release_filter(qadc_adc_index* idx) {
+    if (idx->filter) idx->filter->uses.fetch_sub(1);
+    idx->filter = nullptr;
+}
+
+// qadc_adc_filter_create / _create_device: the bitmap through the mark step of remove-by-label (mark_list, csrc/qadc_remove.h) on a
+// stream of the call's own, drained before the call returns — the filter is complete, and immutable, from then on.
+int create_filter(qadc_adc_filter** out, int mode, const uint32_t* keys, uint64_t count, int device_id, bool d_side) {
+    if (!out) return fail(QADC_E_ARG, "out is null");
+    *out = nullptr;
+    if (mode != QADC_ADC_FILTER_EXCLUDE && mode != QADC_ADC_FILTER_ALLOW)
+        return fail(QADC_E_ARG, "filter mode is 0 (QADC_ADC_FILTER_EXCLUDE) or 1 (QADC_ADC_FILTER_ALLOW)");
+    if (count && !keys) return fail(QADC_E_ARG, "keys is null");
+    DeviceGuard guard;
+    if (int rc = qadc_device_prepare(device_id)) return rc;
+    HIPCHECK(hipSetDevice(device_id));
+    qadc_adc_filter* f = new qadc_adc_filter();
+    f->device = device_id;
+    f->mode = mode;
+    hipStream_t s = nullptr;
+    Scratch tmp;
+    PinBuf<uint32_t> pinned;
+    auto run = [&]() -> int {
+        HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        if (count == 0) {   // no key: one zero word, in which no key is marked
+            f->span = remove_span(0, 0);
+            HIPCHECK(f->mem.alloc(&f->bitmap, 4));
+            HIPCHECK(hipMemsetAsync(f->bitmap, 0, 4, s));
+        } else {
+            if (int rc = qadc::host::mark_list(s, keys, count, d_side, &pinned, tmp, f->mem, &f->span, &f->bitmap)) return rc;
+            f->lo = f->span.lo;
+            f->hi = f->span.lo + f->span.last;
+        }
+        HIPCHECK(hipStreamSynchronize(s));
+        return QADC_OK;
+    };
+    const int rc = run();
+    const std::string msg = qadc::host::g_err;
+    if (s) {
+        (void)hipStreamSynchronize(s);   // (tmp is freed behind the stream's work on every path)
+        (void)hipStreamDestroy(s);
+    }
+    pinned.release();
+    if (rc != QADC_OK) {
+        delete f;
+        qadc::host::g_err = msg;
+        return rc;
+    }
+    *out = f;
+    return QADC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int qadc_adc_filter_create(qadc_adc_filter** out, int mode, const uint32_t* keys, uint64_t count, int device_id) {
+    return create_filter(out, mode, keys, count, device_id, false);
+}
+
+int qadc_adc_filter_create_device(qadc_adc_filter** out, int mode, const uint32_t* d_keys, uint64_t count, int device_id) {
+    return create_filter(out, mode, d_keys, count, device_id, true);
+}
+
+int qadc_adc_filter_info(const qadc_adc_filter* f, int* mode, uint32_t* lo, uint32_t* hi, uint64_t* bitmap_bytes) {
+    if (!f) return fail(QADC_E_ARG, "filter is null");
+    if (mode) *mode = f->mode;
+    if (lo) *lo = f->lo;
+    if (hi) *hi = f->hi;
+    if (bitmap_bytes) *bitmap_bytes = f->span.words * 4;
+    return QADC_OK;
+}
+
+int qadc_adc_filter_destroy(qadc_adc_filter* f) {
+    if (!f) return QADC_OK;
+    const int uses = f->uses.load();
+    if (uses)
+        return fail(QADC_E_STATE, "the filter is set on " + std::to_string(uses) + " index(es): clear it there first (qadc_adc_index_set_filter "
+                                  "with NULL, or destroy the index)");
+    DeviceGuard guard;
+    (void)hipSetDevice(f->device);
+    delete f;
+    return QADC_OK;
+}
+
+int qadc_adc_index_set_filter(qadc_adc_index* idx, const qadc_adc_filter* f) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (f && f->device != idx->device)
+        return fail(QADC_E_ARG, "the filter is on device " + std::to_string(f->device) + " and the index on device " + std::to_string(idx->device));
+    if (f) f->uses.fetch_add(1);   // (before the release: setting the filter that is set already keeps it)
+    release_filter(idx);
+    idx->filter = f;
+    return QADC_OK;
+}
 
 // An index that owns its codes: nsq sub-quantizers of `centroids` centroids each (256: one byte per sub-quantizer, 65536: two).
 static int create_owned(qadc_adc_index** out, int nsq, int centroids, int device_id) {
@@ -1017,6 +1126,7 @@ int qadc_adc_index_destroy(qadc_adc_index* idx) {
     (void)hipSetDevice(idx->device);
     if (idx->stream) (void)hipStreamSynchronize(idx->stream);
     if (idx->src) --idx->src->adc_views;   // the view's scans are over: the source may be destroyed again
+    release_filter(idx);
     idx->d_parts4.release();
     idx->codes.release();
     idx->labels.release();

@@ -6,6 +6,7 @@
 //                      when candidate < bound[query].  One body over ByteCodes<NSQ> (tables [NSQ][256], the owned database by
 //                      value), NibbleCodes<M> (the view: a 4-bit index read in place, scan_4<M>, tables [M][16]) and
 //                      WordCodes<NSQ> (16-bit codes, tables [NSQ][65536]: too large for LDS, gathered from global memory);
+//   adc_scan_filtered_kernel  the same body with a key filter in front of the emit (qadc_adc_index_set_filter, section 11.10);
 //   adc_select_kernel one workgroup per query: bound = the R-th smallest value the query emitted so far (radix select on
 //                      the order-preserving integer image of the floats), the bound of the next level's runs;
 //   adc_pack_kernel    the per-query regions packed densely for one device-to-host copy;
@@ -145,11 +146,37 @@ __device__ __forceinline__ PartRef locate(const Part4* parts, int part) {
 
 constexpr int kUnroll = 4;   // codes per lane in flight
 
-template <class Code, int SUM, class Source>
-__global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ items, uint32_t first, Source src,
-                                                       const int32_t* __restrict__ assign, int ma,
-                                                       const float* __restrict__ tables, const float* __restrict__ bound,
-                                                       Emit emit) {
+// The key bitmap of remove-by-label and of the filtered scan, without a branch so that the loads of several rows go out
+// together: the bitmap word of a key inside [lo, lo + last] (word 0 for one outside: the bitmap has one word at least), then the test.
+__device__ __forceinline__ uint32_t remove_word(const uint32_t* __restrict__ bitmap, uint32_t lo, uint32_t last, uint32_t label) {
+    const uint32_t d = label - lo;
+    return bitmap[d <= last ? d >> 5 : 0u];
+}
+__device__ __forceinline__ bool remove_marked(uint32_t word, uint32_t lo, uint32_t last, uint32_t label) {
+    const uint32_t d = label - lo;
+    return d <= last && ((word >> (d & 31u)) & 1u);
+}
+
+// Which rows the scan may emit (qadc_adc_index_set_filter): the compile-time policy of adc_scan_body.
+// NoFilter: every row, and the kernel's code is the unfiltered kernel's.  KeyFilter: the rows whose key passes the ScanFilter —
+// a key marked in the bitmap is dropped under QADC_ADC_FILTER_EXCLUDE and is the only kind kept under QADC_ADC_FILTER_ALLOW; a key
+// outside [lo, lo + last] is not marked.
+struct NoFilter {
+    static constexpr bool kOn = false;
+    __device__ __forceinline__ bool passes(uint32_t) const { return true; }
+};
+struct KeyFilter {
+    static constexpr bool kOn = true;
+    ScanFilter f;
+    __device__ __forceinline__ bool passes(uint32_t key) const {
+        return remove_marked(remove_word(f.bitmap, f.lo, f.last, key), f.lo, f.last, key) == (f.mode == kFilterAllow);
+    }
+};
+
+template <class Code, int SUM, class Source, class Filter>
+__device__ __forceinline__ void adc_scan_body(const Item* __restrict__ items, uint32_t first, Source src,
+                                              const int32_t* __restrict__ assign, int ma, const float* __restrict__ tables,
+                                              const float* __restrict__ bound, Emit emit, Filter filter) {
     constexpr int CS = Code::kBytes;
     constexpr bool kLds = Code::kTableInLds;
     __shared__ float lds[kLds ? Code::kTable : 1];                // (the word policy's table stays where it is)
@@ -193,7 +220,15 @@ __global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ 
             } else {
                 v = Code::template add<SUM>(t[u]);
             }
-            const bool keep = valid[u] && v < b;                  // NaN, +inf and FLT_MAX never pass (b <= FLT_MAX)
+            bool keep = valid[u] && v < b;                        // NaN, +inf and FLT_MAX never pass (b <= FLT_MAX)
+            [[maybe_unused]] uint32_t key = 0;
+            if constexpr (Filter::kOn) {                          // ahead of the ballot and the count: a dropped row is in no level's
+                if (keep) {                                       // stored values, so no bound ever comes from it; a lane that fails the
+                    const uint32_t r = base + u * kWG + threadIdx.x;   // bound reads neither label nor bitmap
+                    key = part.labels ? part.labels[it.start + r] : part.key_base + it.start + r;
+                    keep = filter.passes(key);
+                }
+            }
             const unsigned long long m = __ballot(keep);
             if (m == 0) continue;
             const int leader = __builtin_ctzll(m);
@@ -204,11 +239,30 @@ __global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ 
                 const uint32_t r = base + u * kWG + threadIdx.x;
                 const size_t at = region + o;
                 emit.vals[at] = v;
-                emit.keys[at] = part.labels ? part.labels[it.start + r] : part.key_base + it.start + r;
+                if constexpr (Filter::kOn) emit.keys[at] = key;
+                else emit.keys[at] = part.labels ? part.labels[it.start + r] : part.key_base + it.start + r;
                 emit.sidx[at] = it.sbase + r;
             }
         }
     }
+}
+
+// The two kernels over the body: the unfiltered one, whose arguments and code are what they were before there was a filter, and the
+// filtered one, which takes the filter by value behind them.
+template <class Code, int SUM, class Source>
+__global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ items, uint32_t first, Source src,
+                                                       const int32_t* __restrict__ assign, int ma,
+                                                       const float* __restrict__ tables, const float* __restrict__ bound,
+                                                       Emit emit) {
+    adc_scan_body<Code, SUM>(items, first, src, assign, ma, tables, bound, emit, NoFilter{});
+}
+
+template <class Code, int SUM, class Source>
+__global__ __launch_bounds__(kWG) void adc_scan_filtered_kernel(const Item* __restrict__ items, uint32_t first, Source src,
+                                                                const int32_t* __restrict__ assign, int ma,
+                                                                const float* __restrict__ tables, const float* __restrict__ bound,
+                                                                Emit emit, ScanFilter filter) {
+    adc_scan_body<Code, SUM>(items, first, src, assign, ma, tables, bound, emit, KeyFilter{filter});
 }
 
 // order-preserving image of a float (never NaN here): -x < -y < -0 < +0 < y < x
@@ -1010,16 +1064,7 @@ __global__ __launch_bounds__(kWG) void remove_mark_kernel(const uint32_t* __rest
     }
 }
 
-// The label's bit, without a branch so that the loads of several rows go out together: the bitmap word of a label inside
-// [lo, lo + last] (word 0 for one outside: the bitmap has one word at least), then the test.
-__device__ __forceinline__ uint32_t remove_word(const uint32_t* __restrict__ bitmap, uint32_t lo, uint32_t last, uint32_t label) {
-    const uint32_t d = label - lo;
-    return bitmap[d <= last ? d >> 5 : 0u];
-}
-__device__ __forceinline__ bool remove_marked(uint32_t word, uint32_t lo, uint32_t last, uint32_t label) {
-    const uint32_t d = label - lo;
-    return d <= last && ((word >> (d & 31u)) & 1u);
-}
+// (remove_word / remove_marked, the label's bit: beside the scan kernel, which tests keys with them too)
 
 // Partition p = blockIdx.y, y-strided; its tiles of kRemoveTile rows x-strided over grid.x; a thread tests one bit a round.
 __global__ __launch_bounds__(kWG) void remove_count_kernel(const RemoveSrc* __restrict__ src, int parts, const uint32_t* __restrict__ bitmap,
@@ -1133,6 +1178,12 @@ hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, ui
                            int ma, const float* tables, const float* bound, Emit emit, hipStream_t s) {
     if (n_items == 0) return hipSuccess;
     const auto scan = [&](auto code, auto src) {
+        if (db.filter.bitmap) {   // the index has a filter (qadc_adc_index_set_filter): the filtered instantiation
+            const auto kernel = sum_mode == 0 ? adc_scan_filtered_kernel<decltype(code), 0, decltype(src)>
+                                              : adc_scan_filtered_kernel<decltype(code), 1, decltype(src)>;
+            hipLaunchKernelGGL(kernel, dim3(n_items), dim3(kWG), 0, s, items, first, src, assign, ma, tables, bound, emit, db.filter);
+            return hipGetLastError();
+        }
         const auto kernel = sum_mode == 0 ? adc_scan_kernel<decltype(code), 0, decltype(src)> : adc_scan_kernel<decltype(code), 1, decltype(src)>;
         hipLaunchKernelGGL(kernel, dim3(n_items), dim3(kWG), 0, s, items, first, src, assign, ma, tables, bound, emit);
         return hipGetLastError();

@@ -41,13 +41,25 @@ struct Part4 {
 // NSQ>).  centroids 65536: nsq 2, 4 or 8 little-endian 16-bit codes in `bytes` (rows of 2 nsq bytes), tables [nq][ma][nsq][65536], read
 // from global memory (scan_standard<uint16_t, NSQ>).  centroids 16: nsq 16 or 32 nibble codes in `parts`, tables [nq][ma][nsq][16]
 // summed as adc_sum_code<M> (scan_4<M>, query_common.hpp:59-90).
+// The key filter of a scan (qadc_adc_filter, include/qadc.h): a bitmap over the keys [lo, lo + last], bit
+// key - lo set for every key of the caller's set — the bitmap launch_remove_mark fills.  mode kFilterExclude: a row whose key is
+// marked is dropped; kFilterAllow: a row whose key is not marked, or lies outside the span, is dropped.  bitmap null: no filter.
+constexpr int kFilterExclude = 0, kFilterAllow = 1;   // QADC_ADC_FILTER_EXCLUDE, QADC_ADC_FILTER_ALLOW
+struct ScanFilter {
+    const uint32_t* bitmap = nullptr;   // last / 32 + 1 words
+    uint32_t lo = 0, last = 0;
+    int mode = kFilterExclude;
+};
+
 struct ScanDb {
     int nsq, centroids;
     Db bytes;             // a kernel argument by value: the owned index's code loads are global loads
     const Part4* parts;   // device memory, one entry per partition
+    ScanFilter filter;    // a kernel argument by value of the filtered kernel; bitmap null: the unfiltered kernel is launched
 };
 
-// Scans items [first, first + n_items): emits (candidate, key, scan index) for every code with candidate < bound[query].
+// Scans items [first, first + n_items): emits (candidate, key, scan index) for every code with candidate < bound[query] whose key
+// passes db.filter.
 hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const int32_t* assign,
                            int ma, const float* tables, const float* bound, Emit emit, hipStream_t s);
 // bound[q] = min(bound[q], the R-th smallest of the values query q has stored so far) where it stored at least R.

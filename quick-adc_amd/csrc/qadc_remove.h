@@ -2,7 +2,7 @@
 // regions of the owned float-ADC database, qadc_index_remove_labels (csrc/qadc_index_add.cpp) over the partitions of a 4-bit
 // index, in the arena or not.  Internal header; the kernels are in csrc/qadc_adc_kernel.hip, the decisions in host/remove_plan.hpp.
 //
-//   1. mark     the list is uploaded (host form) or read where it lies (device form, whose lo / hi come from remove_minmax_kernel
+//   1. mark     (mark_list, which the key filters of the float-ADC scan share) the list is uploaded (host form) or read where it lies (device form, whose lo / hi come from remove_minmax_kernel
 //               and one synchronise of their own: the bitmap cannot be sized before them); a bitmap over [lo, hi] is allocated
 //               for the call, zeroed on the stream and filled by remove_mark_kernel;
 //   2. count    remove_count_kernel reads every label once; hits[] and first[] come back in one pinned copy — the call's only
@@ -31,40 +31,54 @@ struct RemoveJob {
     bool wrote = false;                     // the compaction was enqueued: after a failure the touched partitions are unspecified
 };
 
-// list: `count` > 0 labels in host memory, or (d_side) in device memory, read by kernels only.
-inline int remove_rows(RemoveJob& job, const uint32_t* list, uint64_t count, bool d_side) {
+// Step 1, shared with the key filters of the float-ADC scan (qadc_adc_filter_create*, csrc/qadc_adc.cpp): the bitmap of a list of
+// `count` > 0 keys in host memory, or (d_side) in device memory, read by kernels only.  Everything is enqueued on `s`; the device
+// form synchronises once for lo / hi.  `tmp` takes what only the call needs (the uploaded list, the two words of lo / hi) and must
+// outlive the stream's work; `own` takes the bitmap (span->words words), which the caller keeps as long as it tests keys with it.
+// pinned: a staging block for the two words of the device form.
+inline int mark_list(hipStream_t s, const uint32_t* list, uint64_t count, bool d_side, PinBuf<uint32_t>* pinned, Scratch& tmp, Scratch& own,
+                     adc::RemoveSpan* span, uint32_t** d_bitmap) {
     using namespace qadc::adc;
-    const size_t parts = job.sizes.size();
-    hipStream_t s = job.stream;
-    Scratch mem;
     uint32_t lo = 0xffffffffu, hi = 0;
     const uint32_t* d_list = list;
-    HIPCHECK(job.pinned->ensure(std::max<size_t>(2 * parts, 2)));
     if (d_side) {
         uint32_t* d_lohi = nullptr;
-        HIPCHECK(mem.alloc(&d_lohi, 8));
+        HIPCHECK(pinned->ensure(2));
+        HIPCHECK(tmp.alloc(&d_lohi, 8));
         HIPCHECK(hipMemsetAsync(d_lohi, 0xff, 4, s));
         HIPCHECK(hipMemsetAsync(d_lohi + 1, 0, 4, s));
         HIPCHECK(launch_remove_minmax(list, count, d_lohi, s));
-        HIPCHECK(hipMemcpyAsync(job.pinned->p, d_lohi, 8, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(pinned->p, d_lohi, 8, hipMemcpyDeviceToHost, s));
         HIPCHECK(hipStreamSynchronize(s));
-        lo = job.pinned->p[0];
-        hi = job.pinned->p[1];
+        lo = pinned->p[0];
+        hi = pinned->p[1];
     } else {
         for (uint64_t i = 0; i < count; ++i) {
             lo = std::min(lo, list[i]);
             hi = std::max(hi, list[i]);
         }
         uint32_t* d_up = nullptr;
-        HIPCHECK(mem.alloc(&d_up, count * 4));
+        HIPCHECK(tmp.alloc(&d_up, count * 4));
         HIPCHECK(hipMemcpyAsync(d_up, list, count * 4, hipMemcpyHostToDevice, s));
         d_list = d_up;
     }
-    const RemoveSpan span = remove_span(lo, hi);
+    *span = remove_span(lo, hi);
+    HIPCHECK(own.alloc(d_bitmap, span->words * 4));
+    HIPCHECK(hipMemsetAsync(*d_bitmap, 0, span->words * 4, s));
+    HIPCHECK(launch_remove_mark(d_list, count, span->lo, *d_bitmap, s));
+    return QADC_OK;
+}
+
+// list: `count` > 0 labels in host memory, or (d_side) in device memory, read by kernels only.
+inline int remove_rows(RemoveJob& job, const uint32_t* list, uint64_t count, bool d_side) {
+    using namespace qadc::adc;
+    const size_t parts = job.sizes.size();
+    hipStream_t s = job.stream;
+    Scratch mem;
+    HIPCHECK(job.pinned->ensure(std::max<size_t>(2 * parts, 2)));
+    RemoveSpan span;
     uint32_t* d_bitmap = nullptr;
-    HIPCHECK(mem.alloc(&d_bitmap, span.words * 4));
-    HIPCHECK(hipMemsetAsync(d_bitmap, 0, span.words * 4, s));
-    HIPCHECK(launch_remove_mark(d_list, count, span.lo, d_bitmap, s));
+    if (int rc = mark_list(s, list, count, d_side, job.pinned, mem, mem, &span, &d_bitmap)) return rc;
 
     std::vector<RemoveSrc> src(parts);
     uint32_t longest = 0;

@@ -18,6 +18,7 @@
 // set_finish(QADC_ADC_FINISH_DEVICE): the batch's heaps are ordered and replayed on the GPU (qadc_adc_search under
 // qadc_adc_index_set_finish) and a query's arrays are pushed into the caller's empty heap in array order, which rebuilds them
 // exactly; the default is the host finish, the candidate stream.
+// set_filter(f): the scans drop the rows whose key does not pass the qadc_adc_filter f (qadc_adc_index_set_filter).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -70,6 +71,14 @@ struct adc_search_engine_hip {
         if (index && qadc_adc_index_set_finish(index, mode) != QADC_OK) die("set_finish");
     }
 
+    // qadc_adc_index_set_filter: before or after prepare_database, between batches; null clears.  The filter is the caller's
+    // (qadc_adc_filter_create) and must outlive the engine or be cleared first.
+    const qadc_adc_filter* filter = nullptr;
+    void set_filter(const qadc_adc_filter* f) {
+        filter = f;
+        if (index && qadc_adc_index_set_filter(index, f) != QADC_OK) die("set_filter");
+    }
+
     // scanner_simple::prepare_database (db_query.cpp:21-24) plus the quantizers the feeders need
     void prepare_database() {
         const int m = db.pq->sq_count, bits = db.pq->sq_bits;
@@ -80,6 +89,7 @@ struct adc_search_engine_hip {
         if ((bits == 16 ? qadc_adc_index_create16(&index, m, device) : qadc_adc_index_create(&index, m, bits, device)) != QADC_OK)
             die("Cannot create the GPU index");
         if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
+        if (qadc_adc_index_set_filter(index, filter) != QADC_OK) die("set_filter");
         const int part_count = db.partition_count();
         std::vector<const std::uint8_t*> codes(part_count);
         std::vector<const std::uint32_t*> labels(part_count);
@@ -120,6 +130,7 @@ struct adc_search_engine_hip {
             die("Cannot set the coarse centroids");
         if (qadc_adc_index_create_view(&index, source) != QADC_OK) die("Cannot create the view");
         if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
+        if (qadc_adc_index_set_filter(index, filter) != QADC_OK) die("set_filter");
     }
 
     // nns_engine_batch::process_query (query_common.hpp:194-243): the whole batch is searched when its first query is asked for

@@ -9,10 +9,12 @@
 //   scan_4f<N>          query_common.hpp:59-90: the same on row-major 4-bit codes (low nibble = even sub-quantizer)
 //   get_scan_func       query_common.hpp:120-146: the (sq_count, sq_bits) dispatch and its error text
 //   scanner_simple      db_query.cpp:17-46: R sentinel pushes FLT_MAX - t, then every probed partition in assign[] order
+//   key_filter          no reference counterpart: the allow / exclude key set the scan loops skip rows by (set_filter)
 // Float sums take the grouping of the reference AS COMPILED with its -ffast-math (host/float_sum.hpp; float_sum_mode() = 0
 // gives the source order); this file itself is built without -ffast-math.  The oracle's orc_scan_standard_u8 /
 // orc_candidates_f32 / orc_tables_direct, pinned to the reference build, are the checkers (tests/test_scanner_hip_cpp.py).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <iostream>
@@ -26,13 +28,28 @@ namespace qadc {
 
 typedef kv_heap<unsigned, float> float_heap;
 
+// The key filter of a scan — the written definition of qadc_adc_index_set_filter (include/qadc.h), which the
+// reference does not have.  A row's key is what the scan would push for it (its label, else its position); the scan loops below skip a
+// row the filter drops before they look at its candidate, which is the reference's loop over the partition without that row, its key kept.
+struct key_filter {
+    enum { exclude = 0, allow = 1 };                             // QADC_ADC_FILTER_EXCLUDE, QADC_ADC_FILTER_ALLOW
+    int mode;
+    std::vector<unsigned> keys;                                  // sorted, unique
+    key_filter(int mode_, const unsigned* k, std::size_t count) : mode(mode_), keys(k, k + count) {
+        std::sort(keys.begin(), keys.end());
+        keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    }
+    bool drops(unsigned key) const { return std::binary_search(keys.begin(), keys.end(), key) == (mode == exclude); }
+};
+
 template <typename T, int NSQ>
 void scan_standard(const std::uint8_t* pqcodes_, const unsigned* labels, const unsigned pqcodes_count, const float* dists,
-                   float_heap& bh) {
+                   float_heap& bh, const key_filter* filter = nullptr) {
     const int NCENT = 1 << (sizeof(T) * 8);
     const T* const pqcodes = reinterpret_cast<const T*>(pqcodes_);
     float min = bh.max();
     for (unsigned i = 0; i < pqcodes_count; ++i) {
+        if (filter && filter->drops(labels != nullptr ? labels[i] : i)) continue;
         const T* const code = pqcodes + (std::size_t)i * NSQ;
         float t[NSQ];
         for (int sq = 0; sq < NSQ; ++sq) t[sq] = dists[sq * NCENT + code[sq]];
@@ -46,9 +63,10 @@ void scan_standard(const std::uint8_t* pqcodes_, const unsigned* labels, const u
 
 template <int NSQ>
 void scan_4f(const std::uint8_t* pqcodes, const unsigned* labels, const unsigned pqcodes_count, const float* dists,
-             float_heap& bh) {
+             float_heap& bh, const key_filter* filter = nullptr) {
     float min = bh.max();
     for (unsigned i = 0; i < pqcodes_count; ++i) {
+        if (filter && filter->drops(labels != nullptr ? labels[i] : i)) continue;
         const std::uint8_t* const code = pqcodes + (std::size_t)i * (NSQ / 2);
         float t[NSQ];
         for (int b = 0; b < NSQ / 2; ++b) {                      // byte b: low nibble = sub-quantizer 2b, high nibble = 2b + 1
@@ -63,7 +81,7 @@ void scan_4f(const std::uint8_t* pqcodes, const unsigned* labels, const unsigned
     }
 }
 
-typedef void (*scan_func)(const std::uint8_t*, const unsigned*, unsigned, const float*, float_heap&);
+typedef void (*scan_func)(const std::uint8_t*, const unsigned*, unsigned, const float*, float_heap&, const key_filter*);
 
 template <typename Pq>
 scan_func get_scan_func(const Pq& pq) {
@@ -156,6 +174,8 @@ struct scanner_simple {
     typedef float_heap BhType;
     Db* db = nullptr;
     scan_func scan = nullptr;
+    const key_filter* filter = nullptr;                          // set_filter: not owned, null = the reference's scan
+    void set_filter(const key_filter* f) { filter = f; }
     void prepare_database(Db& database) {
         db = &database;
         scan = get_scan_func(*database.pq);
@@ -168,7 +188,7 @@ struct scanner_simple {
         unsigned count;
         for (int a = 0; a < ma; ++a) {
             db->get_partition(assign[a], codes, labels, count);
-            scan(codes, labels, count, tables, bh);
+            scan(codes, labels, count, tables, bh, filter);
             tables += table_dim;
         }
     }

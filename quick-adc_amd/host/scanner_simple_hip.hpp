@@ -14,6 +14,7 @@
 // set_finish(QADC_ADC_FINISH_DEVICE): the heap is ordered and replayed on the GPU (qadc_adc_query_scan under
 // qadc_adc_index_set_finish) and its arrays are pushed into the caller's empty heap in array order, which rebuilds them exactly
 // (no entry of a heap's array exceeds its parent, so none moves); the default is the host finish, the candidate stream below.
+// set_filter(f): the scans drop the rows whose key does not pass the qadc_adc_filter f (qadc_adc_index_set_filter).
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -63,6 +64,14 @@ struct scanner_simple_hip {
         if (index && qadc_adc_index_set_finish(index, mode) != QADC_OK) die("set_finish");
     }
 
+    // qadc_adc_index_set_filter: before or after prepare_database; null clears.  The filter is the caller's (qadc_adc_filter_create)
+    // and must outlive the scanner or be cleared first; host/scanner_simple.hpp's key_filter is the CPU twin of what it does.
+    const qadc_adc_filter* filter = nullptr;
+    void set_filter(const qadc_adc_filter* f) {
+        filter = f;
+        if (index && qadc_adc_index_set_filter(index, f) != QADC_OK) die("set_filter");
+    }
+
     // scanner_simple::prepare_database + get_scan_func (db_query.cpp:21-24, query_common.hpp:120-146)
     void prepare_database(Db& db) {
         const int m = db.pq->sq_count, bits = db.pq->sq_bits;
@@ -82,6 +91,7 @@ struct scanner_simple_hip {
         if ((words ? qadc_adc_index_create16(&index, m, device) : qadc_adc_index_create(&index, m, bits, device)) != QADC_OK)
             die("Cannot create the GPU index");
         if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
+        if (qadc_adc_index_set_filter(index, filter) != QADC_OK) die("set_filter");
         table_floats = m * (words ? 65536 : 256);
         // every partition in one call (one upload of the partition table, one growth of the device copy)
         const int part_count = db.partition_count();
@@ -118,6 +128,7 @@ struct scanner_simple_hip {
         if (qadc_index_finalize(source, 0.01f) != QADC_OK) die("Cannot prepare database");
         if (qadc_adc_index_create_view(&index, source) != QADC_OK) die("Cannot create the view");
         if (qadc_adc_index_set_finish(index, finish) != QADC_OK) die("set_finish");
+        if (qadc_adc_index_set_filter(index, filter) != QADC_OK) die("set_filter");
         table_floats = m * 16;
     }
 

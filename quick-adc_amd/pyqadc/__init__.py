@@ -49,6 +49,7 @@ SYMBOLS = [
     "qadc_adc_index_remove_labels", "qadc_adc_index_remove_labels_device", "qadc_index_remove_labels", "qadc_index_remove_labels_device",
     "qadc_pq_train_host", "qadc_pq_train_device",
     "qadc_pq_train16_host", "qadc_pq_train16_device", "qadc_pq_update16_host",
+    "qadc_adc_filter_create", "qadc_adc_filter_create_device", "qadc_adc_filter_info", "qadc_adc_filter_destroy", "qadc_adc_index_set_filter",
 ]
 
 
@@ -229,6 +230,11 @@ def lib():
         for name in ("qadc_adc_index_remove_labels", "qadc_index_remove_labels"):
             getattr(L, name).argtypes = [C.c_void_p, u32p, C.c_uint64, u64p]
             getattr(L, name + "_device").argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+        L.qadc_adc_filter_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, u32p, C.c_uint64, C.c_int]
+        L.qadc_adc_filter_create_device.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_uint64, C.c_int]
+        L.qadc_adc_filter_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), u32p, u32p, u64p]
+        L.qadc_adc_filter_destroy.argtypes = [C.c_void_p]
+        L.qadc_adc_index_set_filter.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -1084,6 +1090,72 @@ class Index:
         _check(lib().qadc_profile_reset(self._h))
 
 
+QADC_ADC_FILTER_EXCLUDE, QADC_ADC_FILTER_ALLOW = 0, 1   # include/qadc.h
+_FILTER_MODES = {"exclude": QADC_ADC_FILTER_EXCLUDE, "allow": QADC_ADC_FILTER_ALLOW}
+
+
+class AdcFilter:
+    """A key set for AdcIndex.set_filter (qadc_adc_filter_create): mode "exclude" drops the rows whose key is in `keys`, "allow" the
+    rows whose key is not.  A row's key is its label, else its position (+ a view's key_base).  Immutable; may be set on several
+    indexes of its device; close() raises QadcError while it is set on one."""
+
+    def __init__(self, keys, mode="exclude", device=0):
+        k = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(-1))
+        self._create(lambda h: lib().qadc_adc_filter_create(h, self._mode(mode), _p(k, u32p), k.size, device), device)
+
+    @classmethod
+    def from_device(cls, keys, mode="exclude"):
+        """The set from a contiguous 1-d int32 torch tensor that carries the keys' uint32 bits — the form in which search_device
+        returns keys — read where it lies; the filter is on the tensor's device."""
+        import torch
+        if not isinstance(keys, torch.Tensor):
+            raise TypeError("keys must be a torch.Tensor, not %s" % type(keys).__name__)
+        if keys.device.type != "cuda":
+            raise QadcError("keys is on %s, not on a GPU" % keys.device)
+        device = keys.device.index
+        t = _label_tensor(keys, device)
+        self = cls.__new__(cls)
+        self._create(lambda h: lib().qadc_adc_filter_create_device(h, cls._mode(mode), t.data_ptr(), int(t.shape[0]), device), device)
+        return self
+
+    @classmethod
+    def create_raw(cls, mode, keys, count, device=0):
+        """The C call as it is (mode: an int; keys: a uint32 array or None)."""
+        self = cls.__new__(cls)
+        self._create(lambda h: lib().qadc_adc_filter_create(h, mode, _p(keys, u32p), count, device), device)
+        return self
+
+    @staticmethod
+    def _mode(mode):
+        if mode not in _FILTER_MODES:
+            raise ValueError('mode is "exclude" or "allow", not %r' % (mode,))
+        return _FILTER_MODES[mode]
+
+    def _create(self, call, device):
+        self._h = C.c_void_p()
+        self.device = device
+        _check(call(C.byref(self._h)))
+
+    def info(self):
+        """-> dict(mode "exclude" | "allow", lo, hi: the smallest and largest key (an empty set: lo 2^32 - 1, hi 0), bitmap_bytes)"""
+        mode, lo, hi, nbytes = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        _check(lib().qadc_adc_filter_info(self._h, C.byref(mode), C.byref(lo), C.byref(hi), C.byref(nbytes)))
+        return dict(mode="allow" if mode.value == QADC_ADC_FILTER_ALLOW else "exclude", lo=int(lo.value), hi=int(hi.value),
+                    bitmap_bytes=int(nbytes.value))
+
+    def close(self):
+        """qadc_adc_filter_destroy: raises QadcError (QADC_E_STATE) while the filter is set on an index"""
+        if getattr(self, "_h", None):
+            _check(lib().qadc_adc_filter_destroy(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class AdcIndex:
     """One GPU-resident PQ database with whole-byte codes, scanned with float tables: the role of the reference's
     scanner_simple after prepare_database (db_query.cpp:17-46).  sq_bits 8 with sq_count 4, 8 or 16.
@@ -1150,6 +1222,15 @@ class AdcIndex:
             lib().qadc_adc_index_destroy(self._h)
             self._h = C.c_void_p()
         self._source = None
+        self._filter = None
+
+    def set_filter(self, f):
+        """qadc_adc_index_set_filter: every later query_scan* / search* call drops the rows whose key does not pass the AdcFilter `f`;
+        None clears it.  The index keeps `f` referenced while it is set."""
+        if f is not None and not isinstance(f, AdcFilter):
+            raise TypeError("set_filter takes an AdcFilter or None, not %s" % type(f).__name__)
+        _check(lib().qadc_adc_index_set_filter(self._h, None if f is None else f._h))
+        self._filter = f
 
     def __del__(self):
         try:

@@ -1,9 +1,9 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,filter] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,filter] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
   batch32   32 queries per call on the same list
@@ -36,6 +36,11 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             vectors, 8x8, 10 rounds from a seed of 256 distinct rows (pyqadc.pq_seed).  train_pq, call to return (the upload of the
             learning set included), alternated in one process with the route without it: kmeans_iterations on every host slice.
             The two routes' codebooks and codes are first asserted equal bit for bit
+  filter    filtered search (not in the default legs; also under --bits 4 at 16x4 and --bits 16 at 4x16, part (a) only; DESIGN.md
+            section 11.10): (a) one synchronous query on 10^8 labelled codes (10^6 at --bits 4 and 16), unfiltered, EXCLUDE of 1 % and
+            50 % of the keys, ALLOW of 1 % and 0.01 %, each checked against an index built without the dropped rows; (b) search() of
+            1024 queries on the ivf_search database, unfiltered against EXCLUDE of 10 % of the keys, under both finishes; (c) the
+            creation of a 10^6-key filter from host and from device memory.
   --trained-codebooks   the add, remove and ivf_search legs (8 and 4 bits) learn their codebooks with train_pq (10 rounds on the
             residuals of the first 10^5 vectors) instead of sampling them; off by default, so that recorded figures stay comparable
   --bits 4   the float-ADC view of a 4-bit index instead (pyqadc.AdcIndex.view_of; legs lone,ivf_search):
@@ -198,6 +203,34 @@ def search_legs(legs, iters, res):
         res["ivf_search_device_over_host_finish"] = sweep[str(nq)][1] / sweep[str(nq)][0]
         res["ivf_search_finish_sweep_ms_host_device"] = sweep
         res["ivf_search_host_finishes"] = int(idx.host_finishes())
+    if "filter" in legs:   # (b): the same search() without a filter and with 10 % of the keys excluded, in turn, under both finishes
+        S = rng.permutation(n)[:n // 10].astype(np.uint32)
+        keep = ~np.isin(np.arange(n), S)
+        ref = pyqadc.AdcIndex(nsq, 8)
+        ref.add_partitions([p[keep[l]] for p, l in zip(parts, labels)], [l[keep[l]] for l in labels])
+        ref.set_pq(codebooks)
+        ref.set_coarse(coarse)
+        f = pyqadc.AdcFilter(S, "exclude")
+        plain = lambda: idx.search(queries, ma, R)
+
+        def masked():
+            idx.set_filter(f)
+            try:
+                return idx.search(queries, ma, R)
+            finally:
+                idx.set_filter(None)
+        for finish in (0, 1):
+            same = same_heaps(with_finish(idx, finish, masked)(), with_finish(ref, finish, lambda: ref.search(queries, ma, R))())
+            med_p, med_f = alternated(with_finish(idx, finish, plain), with_finish(idx, finish, masked), max(5, iters))
+            tag = "filter_ivf_search_%s_finish" % ("device" if finish else "host")
+            res[tag + "_unfiltered_ms"] = med_p * 1e3
+            res[tag + "_exclude10_ms"] = med_f * 1e3
+            res[tag + "_same_heaps"] = bool(same)
+            print("search() of 1024 queries, K=256 ma=24 on 10^6 codes, %s finish, alternated: unfiltered %.2f ms, EXCLUDE of 10 %% of the "
+                  "keys %.2f ms (filtered / unfiltered = %.3f); same heaps as an index without the rows: %s"
+                  % ("device" if finish else "host", med_p * 1e3, med_f * 1e3, med_f / med_p, same), flush=True)
+        ref.close()
+        f.close()
     if "lone_search" in legs:
         q1 = queries[:1]
         med, best = timed(lambda: idx.search(q1, ma, R), max(iters, 50), warmup=5)
@@ -220,6 +253,82 @@ def search_legs(legs, iters, res):
         print("CPU scan_standard<uint8_t,8> over the same 24 partitions (%d codes), 1 thread, tables given (%s): %.1f us"
               % (res["lone_search_codes_probed"], "reference build" if po.have_ref_float() else "C restatement", med_c * 1e6), flush=True)
     idx.close()
+
+
+def filter_leg(bits, iters, res, torch=None):
+    """(a) one synchronous query on labelled codes under key filters of several selectivities, each against an index built without
+    the dropped rows; (c) (torch given) the creation of a 10^6-key filter from host and from device memory"""
+    rng = np.random.default_rng(110)
+    zero = np.zeros((1, 1), np.int32)
+    n = 100_000_000 if bits == 8 else 1_000_000
+    shape = {8: (8, 8), 4: (16, 4), 16: (4, 16)}[bits]
+    nsq = shape[0]
+
+    def build(codes, labels):
+        if bits == 4:
+            src = pyqadc.Index(nsq)
+            src.add_partitions([codes], [labels])
+            src.finalize(0.01)
+            return pyqadc.AdcIndex.view_of(src), src
+        idx = pyqadc.AdcIndex(nsq, 8) if bits == 8 else pyqadc.AdcIndex.create16(nsq)
+        idx.add_partitions([codes], [labels])
+        return idx, None
+
+    def close(pair):
+        pair[0].close()
+        if pair[1] is not None:
+            pair[1].close()
+
+    if bits == 16:
+        codes = rng.integers(0, 65536, (n, nsq), dtype=np.uint16)
+    else:
+        codes = rng.integers(0, 256, (n, nsq if bits == 8 else nsq // 2), dtype=np.uint8)
+    labels = ((np.arange(n, dtype=np.uint64) * np.uint64(1000003)) % np.uint64(n)).astype(np.uint32)   # a permutation of 0 .. n - 1
+    tb = ((rng.random((1, 1, nsq << bits), dtype=np.float32) * np.float32(4.0)) ** 2).astype(np.float32)
+    full = build(codes, labels)
+    idx = full[0]
+    it = iters if n > 1_000_000 else max(iters, 50)
+    tag = "filter_lone_%dx%d_%.0e" % (nsq, bits, n)
+    med0, lo0, hi0 = spread(lambda: idx.query_scan(zero, tb, R), it)
+    res[tag + "_unfiltered_ms_median_min_max"] = [med0 * 1e3, lo0 * 1e3, hi0 * 1e3]
+    print("%dx%d, %.0e labelled codes, one synchronous query, no filter: %.3f ms (%.3f .. %.3f)" % (nsq, bits, n, med0 * 1e3, lo0 * 1e3, hi0 * 1e3),
+          flush=True)
+    for mode, share in (("exclude", 0.01), ("exclude", 0.5), ("allow", 0.01), ("allow", 0.0001)):
+        inside = rng.random(n) < share
+        S = labels[inside]
+        f = pyqadc.AdcFilter(S, mode)
+        idx.set_filter(f)
+        got = idx.query_scan(zero, tb, R)
+        med, lo, hi = spread(lambda: idx.query_scan(zero, tb, R), it)
+        med_u, med_f = alternated(lambda: (idx.set_filter(None), idx.query_scan(zero, tb, R)),
+                                  lambda: (idx.set_filter(f), idx.query_scan(zero, tb, R)), it, warmup=2)
+        idx.set_filter(None)
+        keep = ~inside if mode == "exclude" else inside
+        ref = build(codes[keep], labels[keep])
+        same = same_heaps(got, ref[0].query_scan(zero, tb, R))
+        close(ref)
+        name = "%s_%s_%g_percent" % (tag, mode, share * 100)
+        res[name + "_ms_median_min_max"] = [med * 1e3, lo * 1e3, hi * 1e3]
+        res[name + "_alternated_unfiltered_filtered_ms"] = [med_u * 1e3, med_f * 1e3]
+        res[name + "_keys"] = int(len(S))
+        res[name + "_bitmap_bytes"] = f.info()["bitmap_bytes"]
+        res[name + "_same_heaps"] = bool(same)
+        print("  %s of %g %% of the keys (%d keys, bitmap %.1f MiB): %.3f ms (%.3f .. %.3f); alternated with no filter: %.3f against %.3f ms "
+              "(filtered / unfiltered = %.3f); same heaps as an index of the %d surviving rows: %s"
+              % (mode.upper(), share * 100, len(S), f.info()["bitmap_bytes"] / 2 ** 20, med * 1e3, lo * 1e3, hi * 1e3, med_f * 1e3, med_u * 1e3,
+                 med_f / med_u, int(keep.sum()), same), flush=True)
+        f.close()
+    close(full)
+    if torch is not None:   # (c)
+        keys = rng.permutation(10_000_000)[:1_000_000].astype(np.uint32)
+        d_keys = torch.from_numpy(keys.view(np.int32)).cuda()
+        torch.cuda.synchronize()
+        med_h, _ = timed(lambda: pyqadc.AdcFilter(keys, "exclude").close(), max(iters, 20))
+        med_d, _ = timed(lambda: pyqadc.AdcFilter.from_device(d_keys, "exclude").close(), max(iters, 20))
+        res["filter_create_1e6_keys_host_ms"] = med_h * 1e3
+        res["filter_create_1e6_keys_device_ms"] = med_d * 1e3
+        print("creating (and destroying) a filter of 10^6 keys spread over 10^7 (bitmap 1.2 MiB): from host memory %.3f ms, from device memory "
+              "%.3f ms" % (med_h * 1e3, med_d * 1e3), flush=True)
 
 
 def spread(fn, iters, warmup=3):
@@ -331,6 +440,8 @@ def view_legs(legs, iters, res):
               "%.2f ms = %.2f us/query" % (med_h * 1e3, med_h * 1e6 / nq, med_d * 1e3, med_d * 1e6 / nq), flush=True)
         view.close()
         src.close()
+    if "filter" in legs:
+        filter_leg(4, iters, res)
     if "add" in legs:
         add_leg(4, iters, res)
     if "remove" in legs:
@@ -844,6 +955,8 @@ def word_legs(legs, iters, res):
             idx.close()
     if "encode16" in legs:
         encode16_leg(iters, res)
+    if "filter" in legs:
+        filter_leg(16, iters, res)
     if "add" in legs:
         add_leg(16, iters, res)
     if "remove" in legs:
@@ -884,7 +997,7 @@ def main():
                 f.write(line + "\n")
         return
     torch = None
-    if "ivf" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+    if "ivf" in legs or "filter" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:
             import torch
             torch.zeros(1, device="cuda")
@@ -973,8 +1086,10 @@ def main():
             print("the same alternated with query_scan_device (tables and heaps stay in device memory): %.2f ms against %.2f ms"
                   % (med_d * 1e3, med_h * 1e3), flush=True)
         idx.close()
-    if "ivf_search" in legs or "lone_search" in legs:
+    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs:
         search_legs(legs, a.iters, res)
+    if "filter" in legs:
+        filter_leg(8, a.iters, res, torch)
     if "add" in legs:
         add_leg(8, a.iters, res)
     if "remove" in legs:

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cfloat>
 
+#include "../host/adc_tables_plan.hpp"     // adc_tables_plan, adc_encode_plan: the feeders' launch geometry
 #include "../host/index_append_plan.hpp"   // index_padded_end: the span kept zero behind a partition's last row
 #include "qadc_adc_kernels.h"
 #include "qadc_float_sum.h"
@@ -1232,33 +1233,20 @@ hipError_t launch_adc_copy_words(const void* src, void* dst, size_t words, hipSt
     return hipGetLastError();
 }
 
+static_assert(kAdcPlanMaxDim == kAdcMaxDim, "host/adc_tables_plan.hpp plans for the dimensions the feeders take");
+
 hipError_t launch_adc_tables(const float* d_queries, const float* d_coarse, const int32_t* d_assign, const float* d_codebooks,
                              const float* d_cbnorm, const float* d_rotation, int nq, int ma, int nsq, int centroids, int dim,
                              int expansion, int sum_mode, float* d_tables, hipStream_t s) {
     if (nq <= 0 || ma <= 0) return hipSuccess;
-    if (dim <= 0 || dim > kAdcMaxDim || dim % nsq != 0 || (centroids != 256 && centroids != 65536)) return hipErrorInvalidValue;
-    const int ds = dim / nsq;
-    // probes per workgroup: up to 16; a small batch is cut finer (sub-quantizers over grid.z, fewer probes) to fill the chip
-    long groups = (ma + 15) / 16;
-    int msplit = 1;
-    if ((long)nq * groups < 512) msplit = nsq;
-    if ((long)nq * groups * msplit < 512) groups = std::min<long>(ma, std::max<long>(groups, (512 + (long)nq * msplit - 1) / ((long)nq * msplit)));
-    int probes = (int)((ma + groups - 1) / groups);
-    const int mper = nsq / msplit;
-    auto lds_floats = [&](int p) { return (size_t)p * mper * ds + (size_t)p * mper + (d_rotation ? (size_t)p * dim : 0); };
-    while (probes > 1 && lds_floats(probes) * sizeof(float) > 48 * 1024) probes = (probes + 1) / 2;
-    // blocks of 256 centroids per workgroup: all of them (one) for 8-bit sub-quantizers; the 256 blocks of a 16-bit one are cut
-    // into slices over grid.z until the launch has about 2048 workgroups (every slice computes the residuals again)
-    const long pgroups = (ma + probes - 1) / probes;
-    int cper = centroids / 256;
-    while (cper > 1 && (long)nq * pgroups * msplit * (centroids / (256 * cper)) < 2048) cper /= 2;
-    const dim3 grid((unsigned)nq, (unsigned)pgroups, (unsigned)(msplit * (centroids / (256 * cper))));
-    const size_t lds = lds_floats(probes) * sizeof(float);
-#define QADC_AT(DS) hipLaunchKernelGGL((adc_tables_kernel<DS>), grid, dim3(kWG), lds, s, d_queries, d_coarse, d_assign, d_codebooks, \
-                                       d_cbnorm, d_rotation, ma, nsq, centroids, dim, probes, mper, cper, expansion, sum_mode, d_tables)
-    if (ds == 8) QADC_AT(8);
-    else if (ds == 16) QADC_AT(16);
-    else if (ds == 32) QADC_AT(32);
+    AdcTablesPlan p;                                             // host/adc_tables_plan.hpp: the whole geometry
+    if (!adc_tables_plan(nq, ma, nsq, centroids, dim, d_rotation != nullptr, &p)) return hipErrorInvalidValue;
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+#define QADC_AT(DS) hipLaunchKernelGGL((adc_tables_kernel<DS>), grid, dim3(kWG), p.lds_bytes, s, d_queries, d_coarse, d_assign, d_codebooks, \
+                                       d_cbnorm, d_rotation, ma, nsq, centroids, dim, p.probes, p.mper, p.cper, expansion, sum_mode, d_tables)
+    if (p.DS == 8) QADC_AT(8);
+    else if (p.DS == 16) QADC_AT(16);
+    else if (p.DS == 32) QADC_AT(32);
     else QADC_AT(0);
 #undef QADC_AT
     return hipGetLastError();
@@ -1267,16 +1255,13 @@ hipError_t launch_adc_tables(const float* d_queries, const float* d_coarse, cons
 hipError_t launch_adc_encode(const float* d_x, uint64_t n, int nsq, int dim, const float* d_codebooks, const float* d_cbnorm,
                              int sum_mode, uint8_t* d_codes, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    if (dim <= 0 || dim > kAdcMaxDim || dim % nsq != 0) return hipErrorInvalidValue;
-    const int ds = dim / nsq;
-    const int vper = std::max(1, std::min(32, 8192 / dim));
-    const size_t lds = (size_t)vper * (4 * 8 + 4 * 4 + (size_t)dim * 4 + (size_t)nsq * 4 + nsq);
-    const unsigned grid = (unsigned)std::min<uint64_t>((n + vper - 1) / vper, 8192);
-#define QADC_AE(DS) hipLaunchKernelGGL((adc_encode_kernel<DS>), dim3(grid), dim3(kWG), lds, s, d_x, n, nsq, dim, d_codebooks, d_cbnorm, \
-                                       vper, sum_mode, d_codes)
-    if (ds == 8) QADC_AE(8);
-    else if (ds == 16) QADC_AE(16);
-    else if (ds == 32) QADC_AE(32);
+    AdcEncodePlan p;
+    if (!adc_encode_plan(n, nsq, dim, &p)) return hipErrorInvalidValue;
+#define QADC_AE(DS) hipLaunchKernelGGL((adc_encode_kernel<DS>), dim3(p.grid), dim3(kWG), p.lds_bytes, s, d_x, n, nsq, dim, d_codebooks, d_cbnorm, \
+                                       p.vper, sum_mode, d_codes)
+    if (p.DS == 8) QADC_AE(8);
+    else if (p.DS == 16) QADC_AE(16);
+    else if (p.DS == 32) QADC_AE(32);
     else QADC_AE(0);
 #undef QADC_AE
     return hipGetLastError();

@@ -6,7 +6,9 @@ scanner_simple::query_scan over scan_standard<uint16_t, NSQ>, composed in three 
   3. the R sentinels (0, FLT_MAX) and then every (key, candidate) in scan order go through the reference's own kv_binheap
      (po.ref_heap_replay_f32; the oracle's restatement where that build is absent), whose push rejects !(v < max) itself.
 The grouping of step 2 is pinned to the reference's text as compiled by tests/golden/ref_scan_standard_u16_cases.npz
-(tools/gen_golden_adc16.py), which fixture() loads; tests/test_adc16_host.py holds this helper to it."""
+(tools/gen_golden_adc16.py), which fixture() loads; tests/test_adc16_host.py holds this helper to it.
+tables_expansion / tables_direct: the tables [nsq][65536] the feeders must build, tests/adc_compose.py's steps with 65536-row
+codebooks."""
 import os
 
 import numpy as np
@@ -64,6 +66,26 @@ def heap(po, nsq, parts, labels, tables, R, sum_mode=1):
     """-> (keys, values): the heap arrays of one query"""
     k, v = stream(nsq, parts, labels, tables, sum_mode)
     return replay(po, k, v, R)
+
+
+def tables_expansion(po, codebooks, x, sum_mode):
+    """x [n][dim] -> [n][nsq*65536]: per sub-quantizer the oracle's compute_cross_dists_blas restatement"""
+    nsq, _, ds = codebooks.shape
+    out = np.zeros((x.shape[0], nsq, 65536), np.float32)
+    for m in range(nsq):
+        out[:, m, :] = po.cross_dists(codebooks[m], x[:, m * ds:(m + 1) * ds], sum_mode)
+    return out.reshape(x.shape[0], nsq * 65536)
+
+
+def tables_direct(po, codebooks, x, sum_mode):
+    """x [n][dim] -> [n][nsq*65536]: the oracle's compute_dists_single_simd_cg restatement, written for 16 centroids: the codebooks
+    [nsq][65536][ds] go in as [nsq*4096][16][ds] and every sub-vector is repeated 4096 times"""
+    nsq, _, ds = codebooks.shape
+    cb = np.ascontiguousarray(codebooks, np.float32).reshape(nsq * 4096, 16, ds)
+    out = np.zeros((x.shape[0], nsq * 65536), np.float32)
+    for i in range(x.shape[0]):
+        out[i] = po.tables_direct(cb, np.repeat(x[i].reshape(nsq, ds), 4096, axis=0).reshape(-1), sum_mode)
+    return out
 
 
 _fixture = None

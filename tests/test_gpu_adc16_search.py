@@ -8,33 +8,13 @@ import pytest
 import adc16_compose as a16
 import adc_compose as ac
 import pyqadc
-from adc16_compose import assert_heap
+from adc16_compose import assert_heap, tables_direct, tables_expansion
 from helpers import path_independent
 
 pytestmark = pytest.mark.gpu
 
 DIM = 16           # nsq 2: sub-vectors of 8 (the table kernel's register path); nsq 8: of 2 (its any-size path)
 NQ, MA = 5, 3
-
-
-def tables_expansion(po, codebooks, x, sum_mode):
-    """x [n][dim] -> [n][nsq*65536]: per sub-quantizer the oracle's compute_cross_dists_blas restatement"""
-    nsq, _, ds = codebooks.shape
-    out = np.zeros((x.shape[0], nsq, 65536), np.float32)
-    for m in range(nsq):
-        out[:, m, :] = po.cross_dists(codebooks[m], x[:, m * ds:(m + 1) * ds], sum_mode)
-    return out.reshape(x.shape[0], nsq * 65536)
-
-
-def tables_direct(po, codebooks, x, sum_mode):
-    """x [n][dim] -> [n][nsq*65536]: the oracle's compute_dists_single_simd_cg restatement, written for 16 centroids: the codebooks
-    [nsq][65536][ds] go in as [nsq*4096][16][ds] and every sub-vector is repeated 4096 times"""
-    nsq, _, ds = codebooks.shape
-    cb = np.ascontiguousarray(codebooks, np.float32).reshape(nsq * 4096, 16, ds)
-    out = np.zeros((x.shape[0], nsq * 65536), np.float32)
-    for i in range(x.shape[0]):
-        out[i] = po.tables_direct(cb, np.repeat(x[i].reshape(nsq, ds), 4096, axis=0).reshape(-1), sum_mode)
-    return out
 
 
 class Case:

@@ -537,6 +537,14 @@ typedef struct qadc_profile {
     uint64_t nib8_launches;         /* ... the same three for the launches that streamed 8 of 16 (4 bytes per code) */
     uint64_t nib8_codes;
     uint64_t nib8_survivors;
+    uint64_t bkt_copy_bytes;        /* device bytes of the bucket copies qadc_index_finalize built (tiles and side arrays; kept across resets) */
+    uint64_t bkt_copy_slots;        /* slots of those copies: codes plus padding (kept across resets) */
+    uint64_t bkt_copy_failed;       /* partitions whose bucket copy could not be allocated: their runs take the other forms */
+    uint64_t bkt_copy_padded_out;   /* partitions left without because padding inflated a block beyond bkt_max_pad x its codes */
+    uint64_t bkt_launches;          /* of split_launches: launches of the bucket form (qadc_index_set_split_bkt); counted here and nowhere else */
+    uint64_t bkt_codes;             /* of split_codes: codes their runs cover */
+    uint64_t bkt_slots;             /* slots they streamed: those codes plus the padding copies */
+    uint64_t bkt_survivors;         /* (slot, query) pairs of those launches whose partial sum was below the bound less the slack */
 } qadc_profile;
 
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);
@@ -574,6 +582,31 @@ int qadc_index_set_split5(qadc_index* idx, uint64_t min_run5);
  * copy keep the other forms.  QADC_NIB_MIN_RUN / QADC_NIB8_MIN_RUN / QADC_NIB_NS override the defaults at
  * qadc_index_create (with QADC_TEST_HOOKS=1).  Defaults: profiles/r10_nib_sweep.txt. */
 int qadc_index_set_split_nib(qadc_index* idx, uint64_t min_run, uint64_t min_run8, int ns);
+
+/* Bucket form of the split scan (16x4): qadc_index_finalize builds a bucket copy of every partition that
+ * has a byte-plane copy and at least bkt_min_run codes (0 = the form is off, no copy).  The partition is cut into blocks of
+ * bkt_block codes (a power of two from 16384 to 2^30; 0 = keep) and every block is stored grouped by its codes' first two bytes,
+ * so that sub-quantizers 0-3 cost 2 bytes per 16 codes; the copy holds about 18.4 bytes per code (6.125 streamed planes, the
+ * 8-byte code for survivors, a 4-byte position for candidates, 2 to 3 % padding on uniform codes).  A block whose slots exceed
+ * bkt_max_pad x its codes (0 = keep; default 1.125) leaves its partition without the copy.  Level launches whose runs all have
+ * at least bkt_min_run codes, start on a block and end on one or at the partition's end stream 7 of the other 12 sub-quantizers,
+ * those of at least min_run6 / min_run5 / min_run4 codes 6 / 5 / 4 (0 = never); preferred over the nibble form; runs that do not
+ * qualify keep the other forms, and no result changes.  The copy is built by qadc_index_finalize: turning the form on or off and
+ * bkt_block must be set before; the thresholds may change at any time.  QADC_BKT_MIN_RUN / QADC_BKT6_MIN_RUN /
+ * QADC_BKT5_MIN_RUN / QADC_BKT4_MIN_RUN override the defaults at qadc_index_create (with QADC_TEST_HOOKS=1).
+ * Defaults: profiles/r11_bkt_ab.txt. */
+int qadc_index_set_split_bkt(qadc_index* idx, uint64_t bkt_min_run, uint64_t bkt_block, uint64_t min_run6, uint64_t min_run5,
+                             uint64_t min_run4, double bkt_max_pad);
+
+/* The bucket form's choice for ntables 16x4 int8 tables: out[16 t + 4 (NSP - 4) ..] = the deferred set among sub-quantizers
+ * 4-15 for NSP = 4, 5, 6, 7 paid planes as a 16-bit mask (low byte first), the slack c, 0.  A diagnostic. */
+int qadc_bkt_choice(int device_id, const int8_t* tables, int ntables, uint8_t* out);
+
+/* Diagnostics of a partition's bucket copy: its block size (0 = no copy), blocks and slots; and the copy itself: block_off
+ * [blocks + 1] first slot of every block, tiles [slots / 16384][100352] (12 nibble planes of 8 KiB, then 1024 uint16 ids), side
+ * [slots / 16384][196608] (16384 8-byte codes, then 16384 uint32 positions, 0xffffffff = padding); each may be null. */
+int qadc_index_bkt_info(qadc_index* idx, int part, uint64_t* block, uint64_t* nblocks, uint64_t* slots);
+int qadc_index_bkt_read(qadc_index* idx, int part, uint64_t* block_off, uint8_t* tiles, uint8_t* side);
 
 /* The nibble form's choice for ntables 16x4 int8 tables ([ntables][16][16]), as the device computes it for every table of
  * a batch: out[12 t + 4 (NS - 8) ..] = the deferred set of NS = 8, 9, 10 streamed sub-quantizers as a 16-bit mask (low byte

@@ -29,6 +29,9 @@ static_assert(sizeof(CandHeader) <= kSurv5Off && kSurv5Off + sizeof(unsigned lon
 // ... and the nibble form's: launches of 9 or 10 streamed sub-quantizers, launches of 8
 constexpr size_t kSurvNibOff = 24, kSurvNib8Off = 32;
 static_assert(kSurvNib8Off + sizeof(unsigned long long) <= 64, "inside the state block's header");
+// ... and the bucket form's
+constexpr size_t kSurvBktOff = 40;
+static_assert(kSurvBktOff + sizeof(unsigned long long) <= 64, "inside the state block's header");
 
 // What the stages of plan_and_launch hand on to each other: the layouts of the batch's upload and result blocks.
 struct Staged {
@@ -36,7 +39,7 @@ struct Staged {
     size_t in_bytes = 0, off_tables = 0, off_inj = 0, off_hassign = 0;   // upload block
     size_t state_bytes = 0, off_heaps = 0;
     bool dev_stream = false;       // the ordered streams (also) stay in device memory
-    bool any_split6 = false, any_split5 = false, any_nib = false;
+    bool any_split6 = false, any_split5 = false, any_nib = false, any_bkt = false;
 };
 
 // ---- upload: ONE block, ONE copy (enqueued by plan_and_launch: upload_and_wait) ----
@@ -103,13 +106,15 @@ int bind_state_and_result(qadc_index* idx, Slot& s, Staged& g) {
     HIPCHECK(s.d_qtables.ensure((size_t)nq * ma * idx->M * 16));
     // the 6-plane split form's deferred byte per table, computed where the int8 tables become known (launch_front)
     for (auto& ll : s.launches) {
+        g.any_bkt = g.any_bkt || ll.bkt;
         g.any_nib = g.any_nib || ll.nib;
-        g.any_split5 = g.any_split5 || (ll.split5 && !ll.nib);
-        g.any_split6 = g.any_split6 || (ll.split6 && !ll.split5 && !ll.nib);
+        g.any_split5 = g.any_split5 || (ll.split5 && !ll.nib && !ll.bkt);
+        g.any_split6 = g.any_split6 || (ll.split6 && !ll.split5 && !ll.nib && !ll.bkt);
     }
     if (g.any_split6) HIPCHECK(s.d_plane_sel.ensure((size_t)nq * ma));
     if (g.any_split5) HIPCHECK(s.d_plane_sel5.ensure(2 * (size_t)nq * ma));
     if (g.any_nib) HIPCHECK(s.d_nib_sel.ensure((size_t)kNibSelBytes * nq * ma));
+    if (g.any_bkt) HIPCHECK(s.d_bkt_sel.ensure((size_t)kBktSelBytes * nq * ma));
     return QADC_OK;
 }
 
@@ -130,9 +135,9 @@ int launch_front(qadc_index* idx, Slot& s, const BatchPlan& plan, const Staged& 
     if (!s.float_path) {
         s.d_qt = s.front_sharded ? s.d_qtables.p                             // (a sharded-front batch redone here: the gathered tables)
                                  : reinterpret_cast<const int8_t*>(s.d_in.p + g.off_tables);     // caller's int8 tables, as uploaded
-        if (g.any_split6 || g.any_split5 || g.any_nib)
+        if (g.any_split6 || g.any_split5 || g.any_nib || g.any_bkt)
             launch_plane_choice(s.d_qt, nq * ma, g.any_split6 ? s.d_plane_sel.p : nullptr, st, g.any_split5 ? s.d_plane_sel5.p : nullptr,
-                                g.any_nib ? s.d_nib_sel.p : nullptr);
+                                g.any_nib ? s.d_nib_sel.p : nullptr, g.any_bkt ? s.d_bkt_sel.p : nullptr);
         if (idx->profile) { HIPCHECK(prof_event(s, st)); HIPCHECK(prof_event(s, st)); }
         return QADC_OK;
     }
@@ -194,7 +199,7 @@ int launch_front(qadc_index* idx, Slot& s, const BatchPlan& plan, const Staged& 
     }
     launch_select_kth(d_sel, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 4, d_ft, s.d_qtables.p, tda,
                       idx->quant_mode, st, nullptr, nullptr, nullptr, 0, g.any_split6 ? s.d_plane_sel.p : nullptr,
-                      g.any_split5 ? s.d_plane_sel5.p : nullptr, g.any_nib ? s.d_nib_sel.p : nullptr);
+                      g.any_split5 ? s.d_plane_sel5.p : nullptr, g.any_nib ? s.d_nib_sel.p : nullptr, g.any_bkt ? s.d_bkt_sel.p : nullptr);
     if (idx->profile) HIPCHECK(prof_event(s, st));
     return QADC_OK;
 }
@@ -212,11 +217,13 @@ void launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, 
                        ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str,
                        ll.split6 && !ll.split5 ? s.d_plane_sel.p : nullptr,
                        !idx->profile  ? nullptr
+                       : ll.bkt       ? reinterpret_cast<unsigned long long*>(s.d_state.p + kSurvBktOff)
                        : ll.nib       ? reinterpret_cast<unsigned long long*>(s.d_state.p + (ll.nib == 8 ? kSurvNib8Off : kSurvNibOff))
                        : ll.split5    ? reinterpret_cast<unsigned long long*>(s.d_state.p + kSurv5Off)
                        : ll.split6    ? reinterpret_cast<unsigned long long*>(s.d_hdr->pad)
                                       : nullptr,
-                       ll.split5 ? s.d_plane_sel5.p : nullptr, ll.nib ? s.d_nib_sel.p : nullptr, ll.nib);   // (the nibble form first)
+                       ll.split5 ? s.d_plane_sel5.p : nullptr, ll.nib ? s.d_nib_sel.p : nullptr, ll.nib,
+                       ll.bkt ? s.d_bkt_sel.p : nullptr, ll.bkt);   // (the bucket form first, then the nibble form)
 }
 
 int launch_head(qadc_index* idx, Slot& s, const Staged& g, hipStream_t str) {
@@ -392,7 +399,8 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
     // 7.66 -> 7.72-7.76: the next batch's workgroups do not fill a tail, they compete with the current level for CUs)
     const LevelOptions opt{idx->M, idx->level_base, idx->level_growth, idx->head_level, idx->small_run, idx->wgs_per_item,
                            idx->share_variant, idx->mq, idx->prescan_sample, idx->split_min_run, idx->split6_min_run,
-                           idx->split5_min_run, idx->nib_min_run, idx->nib8_min_run, idx->nib_ns};
+                           idx->split5_min_run, idx->nib_min_run, idx->nib8_min_run, idx->nib_ns,
+                           idx->bkt_min_run, idx->bkt6_min_run, idx->bkt5_min_run, idx->bkt4_min_run};
     const LevelBatch batch{s.nq, s.ma, s.assign.data(), s.R, s.mode, s.float_path, s.full_prescan, s.pre_slice, s.pre_nslices, s.inj_n};
     BatchPlan plan = plan_levels(idx->parts.data(), idx->parts.size(), opt, batch);      // (host/level_plan.hpp: no GPU calls)
     if (!plan.refused.empty()) return fail(QADC_E_ARG, plan.refused);
@@ -721,7 +729,7 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[0], s.prof_ev[1]));
             if (s.float_path) idx->prof.start_ms += ms;
         }
-        bool count_survivors = false, count_survivors5 = false, count_nib = false, count_nib8 = false;
+        bool count_survivors = false, count_survivors5 = false, count_nib = false, count_nib8 = false, count_bkt = false;
         for (auto& ll : s.launches) {
             if (ll.small || ll.early) {                      // counted, not timed (see plan_and_launch)
                 idx->prof.small_launches++;
@@ -733,8 +741,8 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             idx->prof.mq_launches += ll.mq ? 1 : 0;
             idx->prof.split_launches += ll.split ? 1 : 0;
             idx->prof.split_codes += ll.split ? ll.codes : 0;
-            const bool ran5 = ll.split5 && !ll.nib;          // (the launcher prefers the nibble form over 5 planes over 6)
-            const bool ran6 = ll.split6 && !ll.split5 && !ll.nib;
+            const bool ran5 = ll.split5 && !ll.nib && !ll.bkt;   // (the launcher prefers the bucket form over the nibble form over 5 planes over 6)
+            const bool ran6 = ll.split6 && !ll.split5 && !ll.nib && !ll.bkt;
             idx->prof.split6_launches += ran6 ? 1 : 0;
             idx->prof.split6_codes += ran6 ? ll.codes : 0;
             idx->prof.split5_launches += ran5 ? 1 : 0;
@@ -747,6 +755,10 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             count_survivors5 = count_survivors5 || ran5;
             count_nib = count_nib || ll.nib > 8;
             count_nib8 = count_nib8 || ll.nib == 8;
+            idx->prof.bkt_launches += ll.bkt ? 1 : 0;
+            idx->prof.bkt_codes += ll.bkt ? ll.codes : 0;
+            idx->prof.bkt_slots += ll.bkt ? ll.slots : 0;
+            count_bkt = count_bkt || ll.bkt;
             idx->prof.pass_codes += ll.mq ? ll.codes / (uint64_t)ll.nitems * (uint64_t)((ll.nitems + 7) / 8) : ll.codes;
             if (ll.ev < 0 || (size_t)ll.ev + 1 >= s.prof_used) continue;   // not the first launch of its timed group
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[ll.ev], s.prof_ev[ll.ev + 1]));
@@ -771,6 +783,11 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             unsigned long long surv = 0;
             HIPCHECK(hipMemcpy(&surv, s.d_state.p + kSurvNib8Off, sizeof(surv), hipMemcpyDeviceToHost));
             idx->prof.nib8_survivors += surv;
+        }
+        if (count_bkt) {
+            unsigned long long surv = 0;
+            HIPCHECK(hipMemcpy(&surv, s.d_state.p + kSurvBktOff, sizeof(surv), hipMemcpyDeviceToHost));
+            idx->prof.bkt_survivors += surv;
         }
         if (s.float_path) idx->prof.start_codes += s.start_codes;
     }
@@ -1223,6 +1240,11 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
         if (const char* e = std::getenv("QADC_NIB_MIN_RUN")) idx->nib_min_run = std::strtoull(e, nullptr, 10);
         if (const char* e = std::getenv("QADC_NIB8_MIN_RUN")) idx->nib8_min_run = std::strtoull(e, nullptr, 10);
         if (const char* e = std::getenv("QADC_NIB_NS")) idx->nib_ns = std::atoi(e) == 10 ? 10 : 9;
+        // the bucket form: 0 = off (no bucket copy at finalize); the thresholds of its 6-, 5- and 4-plane launches
+        if (const char* e = std::getenv("QADC_BKT_MIN_RUN")) idx->bkt_min_run = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_BKT6_MIN_RUN")) idx->bkt6_min_run = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_BKT5_MIN_RUN")) idx->bkt5_min_run = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_BKT4_MIN_RUN")) idx->bkt4_min_run = std::strtoull(e, nullptr, 10);
     }
     if (int rc = attach_streams(idx)) {
         delete idx;
@@ -1251,6 +1273,8 @@ int qadc_index_destroy(qadc_index* idx) {
         if (p.d_starts) (void)hipFree(p.d_starts);
         if (p.d_split) (void)hipFree(p.d_split);
         if (p.d_nib) (void)hipFree(p.d_nib);
+        if (p.d_bkt) (void)hipFree(p.d_bkt);
+        if (p.d_bkt_side) (void)hipFree(p.d_bkt_side);
     }
     idx->arena.release();               // (the partitions with Part::arena, all at once)
     idx->feed.d_codebooks.release();
@@ -1264,7 +1288,7 @@ int qadc_index_destroy(qadc_index* idx) {
     for (Slot* sp : all_slots) {
         Slot& s = *sp;
         s.d_in.release(); s.h_in.release(); s.d_state.release(); s.h_result.release();
-        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_plane_sel5.release(); s.d_nib_sel.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
+        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_plane_sel5.release(); s.d_nib_sel.release(); s.d_bkt_sel.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
         s.h_cands.release(); s.d_stream.release(); s.d_qflags.release(); s.d_fvals.release(); s.d_qcands.release(); s.h_fetch.release();
         s.d_fblock.release(); s.d_fgathered.release(); s.d_front_all.release(); s.h_fmap.release();
         if (s.ev_fa) (void)hipEventDestroy(s.ev_fa);
@@ -1466,6 +1490,75 @@ int qadc_index_set_key_base(qadc_index* idx, int part, uint32_t key_base) {
     return QADC_OK;
 }
 
+// The bucket copies of qadc_index_finalize (host/level_plan.hpp has the layout; launch_bkt_*: the kernels).  Per partition: the key
+// histogram and the buckets' first slots of every block, then (the blocks' slot counts known) the allocation, the scatter and the
+// padding / plane pass.  Borrowed codes get no copy, as with the byte-plane copy (which the partition must have).
+static int build_bkt_copies(qadc_index* idx) {
+    idx->prof.bkt_copy_bytes = idx->prof.bkt_copy_failed = idx->prof.bkt_copy_padded_out = idx->prof.bkt_copy_slots = 0;
+    for (auto& p : idx->parts) {
+        if (p.d_bkt || p.d_bkt_side) {
+            HIPCHECK(hipDeviceSynchronize());
+            if (p.d_bkt) HIPCHECK(hipFree(p.d_bkt));
+            if (p.d_bkt_side) HIPCHECK(hipFree(p.d_bkt_side));
+        }
+        p.d_bkt = p.d_bkt_side = nullptr;
+        p.bkt_off.clear();
+        p.bkt_block = 0;
+        if (idx->M != 16 || idx->bkt_min_run == 0 || p.n < idx->bkt_min_run || !p.d_split || !p.d_codes || !p.own) continue;
+        const uint64_t block = idx->bkt_block;
+        const size_t nblocks = (size_t)(((uint64_t)p.n + block - 1) / block);
+        Scratch tmp;
+        uint32_t *d_hist = nullptr, *d_off = nullptr, *d_info = nullptr;
+        if (tmp.alloc(&d_hist, nblocks * kBktKeys * sizeof(uint32_t)) != hipSuccess ||
+            tmp.alloc(&d_off, nblocks * kBktKeys * sizeof(uint32_t)) != hipSuccess ||
+            tmp.alloc(&d_info, nblocks * 2 * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            idx->prof.bkt_copy_failed++;
+            continue;
+        }
+        HIPCHECK(hipMemsetAsync(d_hist, 0, nblocks * kBktKeys * sizeof(uint32_t), idx->stream));
+        auto block_n = [&](size_t b) { return (uint32_t)std::min<uint64_t>(block, (uint64_t)p.n - b * block); };
+        for (size_t b = 0; b < nblocks; ++b)
+            launch_bkt_hist_scan(p.d_codes + b * block * 8, block_n(b), d_hist + b * kBktKeys, d_off + b * kBktKeys, d_info + 2 * b, idx->stream);
+        HIPCHECK(hipGetLastError());
+        std::vector<uint32_t> info(2 * nblocks);
+        HIPCHECK(hipMemcpyAsync(info.data(), d_info, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, idx->stream));
+        HIPCHECK(hipStreamSynchronize(idx->stream));
+        std::vector<uint64_t> off(nblocks + 1, 0);
+        bool padded_out = false;
+        for (size_t b = 0; b < nblocks; ++b) {
+            padded_out = padded_out || (double)info[2 * b] > idx->bkt_max_pad * (double)block_n(b);
+            off[b + 1] = off[b] + info[2 * b];
+        }
+        if (padded_out) {
+            idx->prof.bkt_copy_padded_out++;
+            continue;
+        }
+        const uint64_t ntiles = off[nblocks] / kSplitTile;
+        const uint64_t tile_bytes = ntiles * kBktTileBytes, side_bytes = ntiles * kBktSideBytes;
+        if (hipMalloc(reinterpret_cast<void**>(&p.d_bkt), tile_bytes) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&p.d_bkt_side), side_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            if (p.d_bkt) (void)hipFree(p.d_bkt);
+            p.d_bkt = p.d_bkt_side = nullptr;
+            idx->prof.bkt_copy_failed++;
+            continue;
+        }
+        HIPCHECK(hipMemsetAsync(p.d_bkt_side, 0xff, side_bytes, idx->stream));       // every perm word: kBktPad until a code lands there
+        for (size_t b = 0; b < nblocks; ++b)
+            launch_bkt_scatter_fill(p.d_codes + b * block * 8, block_n(b), (uint32_t)(b * block), d_off + b * kBktKeys, d_hist + b * kBktKeys,
+                                    p.d_bkt + off[b] / kSplitTile * kBktTileBytes, p.d_bkt_side + off[b] / kSplitTile * kBktSideBytes,
+                                    info[2 * b], info[2 * b + 1], idx->stream);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(idx->stream));             // (the scratch is freed on leaving this iteration)
+        p.bkt_block = block;
+        p.bkt_off.swap(off);
+        idx->prof.bkt_copy_bytes += tile_bytes + side_bytes;
+        idx->prof.bkt_copy_slots += p.bkt_off.back();
+    }
+    return QADC_OK;
+}
+
 int qadc_index_finalize(qadc_index* idx, float keep) {
     if (!idx) return fail(QADC_E_ARG, "null index");
     if (idx->parts.empty()) return fail(QADC_E_STATE, "no partitions");
@@ -1533,9 +1626,17 @@ int qadc_index_finalize(qadc_index* idx, float keep) {
         HIPCHECK(hipGetLastError());
         idx->prof.split_copy_bytes += bytes;
     }
+    // ... the bucket copies for the bucket form, where that form is on: partitions with a byte-plane copy of at least bkt_min_run
+    // codes.  A failed allocation, or a block that padding inflates beyond bkt_max_pad, leaves the partition without (counted).
+    if (int rc = build_bkt_copies(idx)) return rc;
+    const LevelOptions nib_opt{idx->M, idx->level_base, idx->level_growth, idx->head_level, idx->small_run, idx->wgs_per_item,
+                               idx->share_variant, idx->mq, idx->prescan_sample, idx->split_min_run, idx->split6_min_run,
+                               idx->split5_min_run, idx->nib_min_run, idx->nib8_min_run, idx->nib_ns,
+                               idx->bkt_min_run, idx->bkt6_min_run, idx->bkt5_min_run, idx->bkt4_min_run};
     // ... and the nibble-plane copies of all 16 sub-quantizers for the nibble form (8 bytes per code more), where that form is on:
     // partitions with a byte-plane copy (the planner takes the form only for runs that have both) of at least the smaller of its
-    // non-zero thresholds.  A failed allocation is skipped and counted in the same way.
+    // non-zero thresholds.  A failed allocation is skipped and counted in the same way.  A partition whose long runs all take the
+    // bucket form (nib_still_needed: the only partition of its index, levels cut on its blocks) gets none: it would never be read.
     idx->prof.nib_copy_bytes = 0;
     idx->prof.nib_copy_failed = 0;
     const uint64_t nib_min = idx->nib_min_run && idx->nib8_min_run ? std::min(idx->nib_min_run, idx->nib8_min_run)
@@ -1547,6 +1648,7 @@ int qadc_index_finalize(qadc_index* idx, float keep) {
             p.d_nib = nullptr;
         }
         if (idx->M != 16 || nib_min == 0 || p.n < nib_min || !p.d_split) continue;
+        if (!nib_still_needed(p, nib_opt, idx->parts.size() == 1)) continue;
         const uint64_t bytes = nib_copy_bytes(p.n);
         if (hipMalloc(reinterpret_cast<void**>(&p.d_nib), bytes) != hipSuccess) {
             (void)hipGetLastError();
@@ -1903,7 +2005,13 @@ int qadc_profile_reset(qadc_index* idx) {
     if (!idx) return fail(QADC_E_ARG, "null index");
     const uint64_t copy_bytes = idx->prof.split_copy_bytes, copy_failed = idx->prof.split_copy_failed;   // (state, not counters)
     const uint64_t nib_bytes = idx->prof.nib_copy_bytes, nib_failed = idx->prof.nib_copy_failed;
+    const uint64_t bkt_bytes = idx->prof.bkt_copy_bytes, bkt_failed = idx->prof.bkt_copy_failed, bkt_padded = idx->prof.bkt_copy_padded_out,
+                   bkt_cslots = idx->prof.bkt_copy_slots;
     idx->prof = qadc_profile{};
+    idx->prof.bkt_copy_bytes = bkt_bytes;
+    idx->prof.bkt_copy_failed = bkt_failed;
+    idx->prof.bkt_copy_padded_out = bkt_padded;
+    idx->prof.bkt_copy_slots = bkt_cslots;
     idx->prof.split_copy_bytes = copy_bytes;
     idx->prof.split_copy_failed = copy_failed;
     idx->prof.nib_copy_bytes = nib_bytes;
@@ -1959,6 +2067,69 @@ int qadc_index_set_split_nib(qadc_index* idx, uint64_t min_run, uint64_t min_run
     idx->nib_min_run = min_run;
     idx->nib8_min_run = min_run8;
     idx->nib_ns = ns;
+    return QADC_OK;
+}
+
+int qadc_index_set_split_bkt(qadc_index* idx, uint64_t bkt_min_run, uint64_t bkt_block, uint64_t min_run6, uint64_t min_run5,
+                             uint64_t min_run4, double bkt_max_pad) {
+    if (!idx) return fail(QADC_E_ARG, "null index");
+    if (bkt_block == 0) bkt_block = idx->bkt_block;
+    if (bkt_block < kSplitTile || bkt_block > (1ull << 30) || (bkt_block & (bkt_block - 1)) != 0)
+        return fail(QADC_E_ARG, "bkt_block is a power of two from 16384 to 2^30");
+    if (bkt_max_pad == 0) bkt_max_pad = idx->bkt_max_pad;
+    if (!(bkt_max_pad >= 1.0)) return fail(QADC_E_ARG, "bkt_max_pad is at least 1");
+    if (idx->finalized && (bkt_block != idx->bkt_block || (bkt_min_run == 0) != (idx->bkt_min_run == 0)))
+        return fail(QADC_E_STATE, "the bucket copy is built by qadc_index_finalize: turn it on or off, or change bkt_block, before");
+    idx->bkt_min_run = bkt_min_run;
+    idx->bkt_block = bkt_block;
+    idx->bkt6_min_run = min_run6;
+    idx->bkt5_min_run = min_run5;
+    idx->bkt4_min_run = min_run4;
+    idx->bkt_max_pad = bkt_max_pad;
+    return QADC_OK;
+}
+
+int qadc_bkt_choice(int device_id, const int8_t* tables, int ntables, uint8_t* out) {
+    if (!tables || !out || ntables <= 0) return fail(QADC_E_ARG, "bad arguments");
+    if (int rc = qadc_device_prepare(device_id)) return rc;
+    HIPCHECK(hipSetDevice(device_id));
+    DevBuf<int8_t> d_t;
+    DevBuf<uint8_t> d_o;
+    hipError_t e = d_t.ensure((size_t)ntables * 256);
+    if (e == hipSuccess) e = d_o.ensure((size_t)ntables * kBktSelBytes);
+    if (e == hipSuccess) e = hipMemcpy(d_t.p, tables, (size_t)ntables * 256, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_plane_choice(d_t.p, ntables, nullptr, nullptr, nullptr, nullptr, d_o.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_o.p, (size_t)ntables * kBktSelBytes, hipMemcpyDeviceToHost);
+    d_t.release();
+    d_o.release();
+    HIPCHECK(e);
+    return QADC_OK;
+}
+
+int qadc_index_bkt_info(qadc_index* idx, int part, uint64_t* block, uint64_t* nblocks, uint64_t* slots) {
+    if (!idx || part < 0 || part >= (int)idx->parts.size()) return fail(QADC_E_ARG, "bad arguments");
+    const Part& p = idx->parts[part];
+    const bool has = p.d_bkt && !p.bkt_off.empty();
+    if (block) *block = has ? p.bkt_block : 0;
+    if (nblocks) *nblocks = has ? p.bkt_off.size() - 1 : 0;
+    if (slots) *slots = has ? p.bkt_off.back() : 0;
+    return QADC_OK;
+}
+
+int qadc_index_bkt_read(qadc_index* idx, int part, uint64_t* block_off, uint8_t* tiles, uint8_t* side) {
+    if (!idx || part < 0 || part >= (int)idx->parts.size()) return fail(QADC_E_ARG, "bad arguments");
+    const Part& p = idx->parts[part];
+    if (!p.d_bkt || p.bkt_off.empty()) return fail(QADC_E_STATE, "the partition has no bucket copy");
+    if (int rc = use_device(idx)) return rc;
+    HIPCHECK(hipDeviceSynchronize());
+    const uint64_t ntiles = p.bkt_off.back() / kSplitTile;
+    if (block_off) std::memcpy(block_off, p.bkt_off.data(), p.bkt_off.size() * sizeof(uint64_t));
+    if (tiles) HIPCHECK(hipMemcpy(tiles, p.d_bkt, ntiles * kBktTileBytes, hipMemcpyDeviceToHost));
+    if (side) HIPCHECK(hipMemcpy(side, p.d_bkt_side, ntiles * kBktSideBytes, hipMemcpyDeviceToHost));
     return QADC_OK;
 }
 

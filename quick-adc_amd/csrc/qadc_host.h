@@ -179,6 +179,7 @@ struct Slot {
     DevBuf<float> d_ftables;            // float tables built on the device (qadc_search)
     DevBuf<int8_t> d_qtables;
     DevBuf<uint8_t> d_plane_sel;        // 16x4: the 6-plane split form's deferred byte of every table of the batch (written beside d_qt)
+    DevBuf<uint8_t> d_bkt_sel;          // ... and the bucket form's kBktSelBytes per table (deferred masks and slacks for NSP = 4..7)
     DevBuf<uint8_t> d_nib_sel;          // ... and the nibble form's kNibSelBytes per table (deferred masks and slacks for NS = 8, 9, 10)
     DevBuf<uint8_t> d_plane_sel5;       // ... and the 5-plane form's two bytes per table: j1 | j2 << 4, slack (launch_scan_i8)
     DevBuf<Cand> d_cands;
@@ -453,6 +454,17 @@ struct qadc_index {
     uint64_t nib_min_run = 1ull << 25;       // defaults: the fastest arm of the sweep, 9 from the level at 2^25 on and 8 on runs of
     uint64_t nib8_min_run = 400ull << 20;    // 400 Mi codes (the 10^9-code list's last level, which starts at 2^29, has 441.7 Mi)
     int nib_ns = 9;
+    // the bucket form (scan_i8_bkt_kernel, preferred over the nibble form): qadc_index_finalize builds the bucket copy (blocks of bkt_block
+    // codes grouped by code bytes 0 and 1; about 18.4 bytes per code) of every partition with a byte-plane copy and at least
+    // bkt_min_run codes (0 = the form is off), unless padding inflates a block beyond bkt_max_pad x its codes.  Runs of at least
+    // bkt_min_run codes that cover whole blocks take the form with 7 paid planes, 6 / 5 / 4 from bkt6 / bkt5 / bkt4_min_run on
+    // (0 = never; qadc_index_set_split_bkt; profiles/r11_bkt_ab.txt)
+    uint64_t bkt_min_run = 1ull << 25;
+    uint64_t bkt_block = 1ull << 25;
+    uint64_t bkt6_min_run = 1ull << 25;      // the level from 2^25 (3 x 2^25 codes per run): 6 paid planes
+    uint64_t bkt5_min_run = 1ull << 27;      // the levels from 2^27 and 2^29: 5
+    uint64_t bkt4_min_run = 0;
+    double bkt_max_pad = 1.125;
     // one workgroup per query (IVF batches, small lists): 0 = never, 1 = auto, 2 = whenever structurally possible
     int wgq = 1;
     uint32_t wgq_capacity = 4096;        // stream entries per query to start with

@@ -848,6 +848,238 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_nib_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Bucket form of the split scan (16x4, one query per pass): the run is streamed from the partition's bucket copy
+// (host/level_plan.hpp: kBktTileBytes per kSplitTile-slot tile, launch_bkt_*), in which every 16-slot lane group holds codes of
+// ONE key = code bytes 0 and 1, i.e. sub-quantizers 0-3.  A lane loads its group's uint16 id and NSP = 4, 5, 6 or 7 of the 12
+// nibble planes of sub-quantizers 4-15 (which: the table's choice, plane_choice_bkt): 2 bytes per 16 codes for four
+// sub-quantizers instead of 2 bytes per code.
+//   The partial sum starts from P01[id & 255] + P23[id >> 8], the pair tables of rows 0-3 (slots 0 and 1 of the LDS image):
+//   those four rows are EXACT.  The paid rows are exact too, and with c = min(127, the sum over the deferred s of min T[s]) every
+//   code's full sum is >= partial + c: the survivor test is the nibble form's, min(127, partial) < bsurv = bound > c ? bound - c : 0.
+//   A survivor reads its slot's 8-byte code from the side array, adds the deferred rows' entries from the staged int8 table and
+//   is a candidate when min(127, full) < bound.  A candidate reads perm[slot], its position in the partition; a padding slot
+//   (kBktPad: a copy of a code that has a real slot of its own) is dropped, every other one goes to emit_candidate with that
+//   position.  A block of the copy lies inside one bound level and a run covers whole blocks, so the run's slots hold exactly
+//   the codes of the row-major run: the candidate set is that of scan_i8_kernel, in another order, and the stream is sorted
+//   by position before the replay.
+//   Loop: the nibble form's (two planes merge into pair-table indices; an odd NSP leaves one single plane with two slots);
+//   a run is whole tiles, so there is no ragged end.
+// PROBE: XOR of the streamed planes and the id (the streaming ceiling of this form; results meaningless).
+// surv (profile option only, else null): survivor count (padding slots included), one atomicAdd per workgroup at exit.
+// ---------------------------------------------------------------------------------------------
+// The list build_nib_tables takes, NSP + 4 nibbles: sub-quantizers 0-3 (slots 0 and 1: the free pair tables), then the NSP
+// paid ones: the clear bits of the deferred mask among 4..15, ascending, then (a mask with more than 12 - NSP bits set: never
+// written by plane_choice_bkt) set bits until there are NSP.  used = the list as a bit set; its complement is the deferred set.
+template <int NSP>
+__device__ __forceinline__ uint64_t bkt_streamed(uint32_t mask, uint32_t& used) {
+    mask &= 0xfff0u;
+    uint64_t list = 0x3210ull;
+    uint32_t cnt = 4;
+    used = 0xfu;
+#pragma unroll
+    for (uint32_t pass = 0; pass < 2; ++pass)
+#pragma unroll
+        for (uint32_t s = 4; s < 16; ++s)
+            if (((mask >> s) & 1u) == pass && cnt < (uint32_t)NSP + 4u) {
+                list |= (uint64_t)s << (4u * cnt);
+                used |= 1u << s;
+                ++cnt;
+            }
+    return list;
+}
+
+template <int NSP, bool NT, bool CHUNK, bool PROBE>
+__global__ __launch_bounds__(kWG, 8) void scan_i8_bkt_kernel(
+    const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
+    CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
+    const uint8_t* __restrict__ bkt_sel, unsigned long long* __restrict__ surv) {
+    static_assert(NSP >= 4 && NSP <= 7, "4, 5, 6 or 7 of the 12 paid nibble planes");
+    static_assert(kSplitTile == 16u * kWG, "a workgroup iteration is one tile: 16 slots per lane");
+    static_assert(kBktTileBytes % 8 == 0 && kBktIdOff % 8 == 0, "8-byte plane vectors");
+    using C = ScanCfg<16>;
+    constexpr int NS = NSP + 4;                                 // rows in the LDS image
+    constexpr int NP = NSP / 2;                                 // fused paid pairs: slots 2 .. 2 + NP - 1
+    constexpr bool ODD = (NSP & 1) != 0;                        // ... and one single plane: slots 2 + NP and 3 + NP
+    const ScanItem it = items[blockIdx.y];
+    QueryState* qs = qstates + it.query;
+    out += (uint64_t)it.query * cand_cap;
+    const uint8_t* sel = bkt_sel + (size_t)it.table * kBktSelBytes + 4u * (NSP - 4);
+    const uint32_t slack = min((uint32_t)sel[2], 127u);
+    uint32_t used;
+    const uint64_t list = bkt_streamed<NSP>((uint32_t)sel[0] | ((uint32_t)sel[1] << 8), used);
+    const uint32_t defmask = 0xffffu & ~used;                   // (whatever the bytes hold: the complement of what is summed in the loop)
+    build_nib_tables<NS>(qtables + (uint64_t)it.table * 256, list);
+    const uint32_t bound = prefix_bound(qs, it.order >> 16, R, reinterpret_cast<uint32_t*>(smem + C::HIST_OFF),
+                                        reinterpret_cast<uint32_t*>(smem + C::BOUND_OFF));
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane_lo = (tid & 31u) * 4u;
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(1))) u32x2* gvec_t;
+    typedef const __attribute__((address_space(1))) unsigned short* gid_t;
+    typedef const __attribute__((address_space(1))) unsigned char* gbyte_t;
+    const gvec_t planes = (gvec_t)(uintptr_t)it.split;          // the run's first tile of the bucket copy
+    const gid_t ids = (gid_t)(uintptr_t)(it.split + kBktIdOff) + tid;
+    const gbyte_t side = (gbyte_t)(uintptr_t)it.codes;          // ... and of its side array
+    lds_base_is_zero();
+    const uint32_t ntiles = it.n / kSplitTile;                  // (n = slots: whole tiles)
+    uint32_t first = blockIdx.x, last = ntiles, step = gridDim.x;
+    if (CHUNK) {
+        const uint32_t per = (ntiles + gridDim.x - 1) / gridDim.x;
+        first = blockIdx.x * per;
+        last = min(ntiles, first + per);
+        step = 1;
+    }
+    // 8-byte-vector offset of the paid plane streamed i-th (uniform; sub-quantizer 4..15: plane 0..11, inside the tile)
+    uint32_t poff[NSP];
+#pragma unroll
+    for (int i = 0; i < NSP; ++i) poff[i] = (((uint32_t)(list >> (4 * (i + 4))) & 15u) - 4u) % kBktPlanes * (kSplitTile / 16);
+    const uint32_t bsurv = bound > slack ? bound - slack : 0u;  // 0 = no survivor (never wraps)
+    const uint32_t bound4 = bsurv * 0x01010101u;
+
+    // survivors of the previous iteration: byte k of pend[w] = min(127, partial) of the lane's slot 4 w + k, 0xff = none
+    uint32_t pend[4] = {~0u, ~0u, ~0u, ~0u};
+    uint32_t pend_base = 0;                                     // run slot of the lane's slot 0 in that iteration
+    bool any_pend = false;
+    uint32_t res[4];
+    uint32_t res_base = 0;
+    bool any_res = false;
+    uint32_t nsurv = 0;
+
+    // byte offset of run slot sl's tile in the side array (sl < 2^32: at most 2^18 tiles)
+    auto side_tile = [&](uint32_t sl) __attribute__((always_inline)) { return (uint64_t)(sl / kSplitTile) * kBktSideBytes; };
+    auto resolve = [&]() __attribute__((always_inline)) {                                      // pend -> res
+        uint32_t m = ((~pend[0] & 0x80808080u) >> 7) | ((~pend[1] & 0x80808080u) >> 6) | ((~pend[2] & 0x80808080u) >> 5) |
+                     ((~pend[3] & 0x80808080u) >> 4);
+        if (surv) nsurv += (uint32_t)__builtin_popcount(m);
+        const gbyte_t rows = side + side_tile(pend_base) + (uint64_t)(pend_base % kSplitTile) * 8u;   // the lane's 16 slot codes
+        while (m) {
+            const uint32_t i = (uint32_t)__builtin_ctz(m);
+            m &= m - 1u;
+            const uint32_t w = i & 3u, sh = i & 24u;
+            const u32x2 x = *(gvec_t)(rows + (4u * w + (sh >> 3)) * 8u);
+            const uint32_t pw = w == 0 ? pend[0] : w == 1 ? pend[1] : w == 2 ? pend[2] : pend[3];
+            const uint64_t xw = (((uint64_t)x.y) << 32) | x.x;
+            uint32_t s = (pw >> sh) & 0xffu;
+            for (uint32_t dm = defmask; dm; dm &= dm - 1u) {    // (uniform trip count) the deferred sub-quantizers' entries
+                const uint32_t sq = (uint32_t)__builtin_ctz(dm);
+                s += smem[C::STAGE_OFF + 16u * sq + ((uint32_t)(xw >> (4u * sq)) & 15u)];
+            }
+            const uint32_t cv = min(s, 127u);
+            const uint32_t upd = (pw & ~(0xffu << sh)) | ((cv < bound ? cv : 0xffu) << sh);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) pend[u] = w == (uint32_t)u ? upd : pend[u];
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) res[w] = pend[w];
+        res_base = pend_base;
+        any_res = (res[0] & res[1] & res[2] & res[3]) != ~0u;
+    };
+    auto emit_res = [&]() __attribute__((always_inline)) {
+        typedef const __attribute__((address_space(1))) uint32_t* gperm_t;
+        const gperm_t perm = (gperm_t)(side + side_tile(res_base) + kBktPermOff) + res_base % kSplitTile;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const uint32_t r = (res[c >> 2] >> (8 * (c & 3))) & 0xffu;
+            if (r != 0xffu) {
+                const uint32_t pos = perm[c];                   // position in the partition; a padding slot is a copy: dropped
+                if (pos != kBktPad)
+                    emit_candidate(qs, hdr, out, cand_cap, it.labels, it.key_base, it.order, it.dup_pos, it.dup_reps, pos, r);
+            }
+        }
+    };
+    auto step_tile = [&](uint32_t t) __attribute__((always_inline)) {
+        u32x2 v[NSP];
+        const uint32_t e0 = t * (kBktTileBytes / 8) + tid;      // vector index of plane 0 (t < 2^18: no wrap)
+        const gid_t idp = ids + (uint64_t)t * (kBktTileBytes / 2);
+        const uint32_t id = NT ? __builtin_nontemporal_load(idp) : *idp;
+#pragma unroll
+        for (int i = 0; i < NSP; ++i)
+            v[i] = NT ? __builtin_nontemporal_load(planes + e0 + poff[i]) : planes[e0 + poff[i]];
+        if (__builtin_expect(any_pend, 0)) resolve();           // the previous iteration's survivors, behind this one's loads
+        const uint32_t base = t * kSplitTile + tid * 16u;       // run slot of the lane's slot 0
+        uint32_t cv[16];
+        uint32_t best = 127u;
+        if (PROBE) {
+            u32x2 a = v[0];
+#pragma unroll
+            for (int i = 1; i < NSP; ++i) a ^= v[i];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) cv[c] = 127u;
+            cv[0] = ((a.x ^ a.y ^ id) == 0x12345678u) ? 0u : 127u;
+            best = cv[0];
+        } else {
+            constexpr uint32_t LO = 0x0f0f0f0fu;
+            // the group's four free rows: P01[id & 255] in slot 0, P23[id >> 8] in slot 1
+            const uint32_t s0 = *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id & 0xffu) << 8) | lane_lo) + 0u)) +
+                                *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id >> 8) & 0xffu) << 8 | lane_lo) + 1u));
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                uint32_t idx[2][NP > 0 ? NP : 1];               // [slots 0-3 | 4-7 of the dword's eight][pair]: four byte indices each
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const uint32_t A = v[2 * p][w], B = v[2 * p + 1][w];
+                    idx[0][p] = (A & LO) | ((B << 4) & ~LO);
+                    idx[1][p] = ((A >> 4) & LO) | (B & ~LO);
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        uint32_t s = s0;
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) {
+                            // byte0 = bank*4, byte1 = byte k of the merged index; table slot sl = p + 2 at (sl >> 2) * 128 + (sl & 3)
+                            const uint32_t a = __builtin_amdgcn_perm(idx[h][p], lane_lo, 0x0c0c0000u | ((4u + k) << 8));
+                            s += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(a + ((p + 2) >> 2) * 128 + ((p + 2) & 3)));
+                        }
+                        if (ODD) {                              // the single plane: its first slot reads the low nibble, the next one the high one
+                            constexpr int sl = NP + 2;
+                            const uint32_t a = __builtin_amdgcn_perm(v[NSP - 1][w], lane_lo, 0x0c0c0000u | ((4u + k) << 8));
+                            s += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(a + ((sl + h) >> 2) * 128 + ((sl + h) & 3)));
+                        }
+                        const uint32_t c = min(s, 127u);
+                        cv[8 * w + 4 * h + k] = c;
+                        best = min(best, c);
+                    }
+                }
+            }
+        }
+        any_pend = false;
+        if (__builtin_expect(best < bsurv, 1)) {                // most wave iterations of a long level
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                // bytes >= bsurv -> 0xff, four at a time (all bytes and bsurv are <= 127: no borrow crosses a byte)
+                const uint32_t p = cv[4 * w] | (cv[4 * w + 1] << 8) | (cv[4 * w + 2] << 16) | (cv[4 * w + 3] << 24);
+                const uint32_t ge = ((p | 0x80808080u) - bound4) & 0x80808080u;
+                pend[w] = p | ((ge >> 7) * 0xffu);
+            }
+            pend_base = base;
+            any_pend = true;
+        }
+        if (__builtin_expect(any_res, 0)) {                     // the previous iteration's candidates
+            emit_res();
+            any_res = false;
+        }
+    };
+    for (uint32_t t = first; t < last; t += step) step_tile(t);
+    if (any_pend) {
+        resolve();
+        if (any_res) emit_res();
+    }
+    if (surv) {                                                 // (uniform) one global atomic per workgroup: the waves' counts meet in LDS
+        uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + C::HIST_OFF);
+        __syncthreads();
+        if (tid == 0) *cnt = 0;
+        __syncthreads();
+        const uint32_t tot = dpp_wave_incl_sum(nsurv);          // lane 63: the wave's count
+        if ((tid & 63u) == 63u && tot) atomicAdd(cnt, tot);
+        __syncthreads();
+        if (tid == 0 && *cnt) atomicAdd(surv, (unsigned long long)*cnt);
+    }
+}
+
 // The deferred byte of the 6-plane split form, once per int8 table: the j in 0..6 whose 256 pair entries
 // q[2j][lo] + q[2j+1][hi] have the smallest sum = 16 x (the sum of the two 16-entry rows); ties: the highest j.
 // The choice changes the survivor rate only, never a result.
@@ -942,10 +1174,48 @@ __device__ __forceinline__ void plane_choice_nib(const int8_t* __restrict__ qt, 
     }
 }
 
-// plane_sel (6-plane form, 1 byte per table), plane_sel5 (5-plane form, 2 bytes per table) and nib_sel (nibble form, kNibSelBytes
-// per table): each may be null
+// The bucket form's choice, once per int8 table: sub-quantizers 0-3 are free (the lane group's id), so the deferred sets are
+// picked among 4..15 only, by plane_choice_nib's score and tie rule, nested: 5 picks for NSP = 7 paid planes, one more for
+// 6, 5 and 4.  kBktSelBytes bytes: at 4 * (NSP - 4) the set as a 16-bit mask (low byte first), c = min(127, the sum of min T[s]
+// over the set), 0.  A c above the deferred entries' sum would lose candidates, a poor set only costs survivors.
+__device__ __forceinline__ void plane_choice_bkt(const int8_t* __restrict__ qt, uint8_t* __restrict__ out) {
+    const uint8_t* T = reinterpret_cast<const uint8_t*>(qt);
+    uint32_t score[16], mn[16];
+#pragma unroll
+    for (uint32_t s = 4; s < 16; ++s) {
+        uint32_t sum = 0, m = 255u;
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t a = T[16 * s + i];
+            sum += a;
+            m = min(m, a);
+        }
+        mn[s] = m;
+        score[s] = sum - 16u * m;
+    }
+    uint32_t mask = 0, c = 0;
+#pragma unroll
+    for (uint32_t pick = 0; pick < 8; ++pick) {
+        uint32_t best = 0xffffffffu, bs = 15, bm = 0;
+#pragma unroll
+        for (uint32_t s = 4; s < 16; ++s)
+            if (!((mask >> s) & 1u) && score[s] <= best) { best = score[s]; bs = s; bm = mn[s]; }
+        mask |= 1u << bs;
+        c += bm;
+        if (pick >= 4) {                                        // 5, 6, 7, 8 deferred = NSP 7, 6, 5, 4
+            uint8_t* o = out + 4u * (7u - pick);
+            o[0] = (uint8_t)(mask & 0xffu);
+            o[1] = (uint8_t)(mask >> 8);
+            o[2] = (uint8_t)min(c, 127u);
+            o[3] = 0;
+        }
+    }
+}
+
+// plane_sel (6-plane form, 1 byte per table), plane_sel5 (5-plane form, 2 bytes per table), nib_sel (nibble form, kNibSelBytes
+// per table) and bkt_sel (bucket form, kBktSelBytes per table): each may be null
 __global__ __launch_bounds__(256) void plane_choice_kernel(const int8_t* __restrict__ qtables, int ntables, uint8_t* __restrict__ plane_sel,
-                                                           uint8_t* __restrict__ plane_sel5, uint8_t* __restrict__ nib_sel) {
+                                                           uint8_t* __restrict__ plane_sel5, uint8_t* __restrict__ nib_sel,
+                                                           uint8_t* __restrict__ bkt_sel) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= ntables) return;
     if (plane_sel) plane_sel[t] = (uint8_t)plane_choice(qtables + (size_t)t * 256);
@@ -955,13 +1225,14 @@ __global__ __launch_bounds__(256) void plane_choice_kernel(const int8_t* __restr
         plane_sel5[2 * (size_t)t + 1] = (uint8_t)(c5 >> 8);
     }
     if (nib_sel) plane_choice_nib(qtables + (size_t)t * 256, nib_sel + (size_t)t * kNibSelBytes);
+    if (bkt_sel) plane_choice_bkt(qtables + (size_t)t * 256, bkt_sel + (size_t)t * kBktSelBytes);
 }
 
 void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream, uint8_t* d_plane_sel5,
-                         uint8_t* d_nib_sel) {
-    if (ntables <= 0 || (!d_plane_sel && !d_plane_sel5 && !d_nib_sel)) return;
+                         uint8_t* d_nib_sel, uint8_t* d_bkt_sel) {
+    if (ntables <= 0 || (!d_plane_sel && !d_plane_sel5 && !d_nib_sel && !d_bkt_sel)) return;
     hipLaunchKernelGGL(plane_choice_kernel, dim3((ntables + 255) / 256), dim3(256), 0, stream, d_qtables, ntables, d_plane_sel,
-                       d_plane_sel5, d_nib_sel);
+                       d_plane_sel5, d_nib_sel, d_bkt_sel);
 }
 
 // The byte-plane copy of a partition (kSplitTile layout): one thread per 16 codes of a tile, plane b's 16 bytes = byte b
@@ -1025,6 +1296,118 @@ void launch_nib_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipStr
     const uint64_t nthreads = ((uint64_t)n + kSplitTile - 1) / kSplitTile * (kSplitTile / 16);
     if (!nthreads) return;
     hipLaunchKernelGGL(nib_copy_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream, d_codes, n, d_copy, nthreads);
+}
+
+// ---- the bucket copy of a partition (host/level_plan.hpp has the layout), block by block; run once per partition by
+// qadc_index_finalize, not timed.  The scatter is UNSTABLE: a code's slot inside its bucket is the order in which its atomicAdd on
+// the bucket's cursor lands, so two builds of the same partition may order a bucket differently.  No result depends on that order.
+// Key histogram of one block: codes = the block's first code, n = its codes; hist[kBktKeys], zeroed by the caller.
+__global__ __launch_bounds__(256) void bkt_hist_kernel(const uint8_t* __restrict__ codes, uint32_t n, uint32_t* __restrict__ hist) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        atomicAdd(&hist[*reinterpret_cast<const uint16_t*>(codes + i * 8)], 1u);
+}
+
+// Exclusive scan of the bucket sizes, each padded to a multiple of 16 slots: off[key] = first slot of the bucket in its block.
+// hist comes back zeroed (the scatter's cursors).  info[0] = the block's slots, padded to whole tiles; info[1] = its last real slot.
+// One workgroup of 1024 threads, 64 keys each.
+__global__ __launch_bounds__(1024) void bkt_scan_kernel(uint32_t* __restrict__ hist, uint32_t* __restrict__ off, uint32_t* __restrict__ info) {
+    static_assert(kBktKeys == 64 * 1024, "64 keys per thread");
+    __shared__ uint32_t wave_sum[16];
+    __shared__ uint32_t last_real;
+    const uint32_t t = threadIdx.x;
+    if (t == 0) last_real = 0;
+    uint32_t mine = 0;
+    for (uint32_t k = 0; k < 64; ++k) mine += (hist[64 * t + k] + 15u) & ~15u;
+    const uint32_t incl = dpp_wave_incl_sum(mine);
+    if ((t & 63u) == 63u) wave_sum[t >> 6] = incl;
+    __syncthreads();
+    uint32_t run = incl - mine;
+    for (uint32_t w = 0; w < (t >> 6); ++w) run += wave_sum[w];
+    uint32_t end_real = 0;
+    for (uint32_t k = 0; k < 64; ++k) {
+        const uint32_t c = hist[64 * t + k];
+        off[64 * t + k] = run;
+        if (c) end_real = run + c;
+        run += (c + 15u) & ~15u;
+        hist[64 * t + k] = 0;
+    }
+    if (end_real) atomicMax(&last_real, end_real - 1u);
+    __syncthreads();
+    if (t == 1023) {
+        info[0] = (run + kSplitTile - 1) / kSplitTile * kSplitTile;
+        info[1] = last_real;
+    }
+}
+
+// Scatter of one block: code i of the block goes to slot off[key] + (its turn at the bucket's cursor) of the block's first tile
+// `side` of the side array, with its position pos_first + i in the partition.  The side array's perm words are kBktPad beforehand.
+__global__ __launch_bounds__(256) void bkt_scatter_kernel(const uint8_t* __restrict__ codes, uint32_t n, uint32_t pos_first,
+                                                          const uint32_t* __restrict__ off, uint32_t* __restrict__ cursor,
+                                                          uint8_t* __restrict__ side) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint2 v = *reinterpret_cast<const uint2*>(codes + i * 8);
+        const uint32_t key = v.x & 0xffffu;
+        const uint32_t slot = off[key] + atomicAdd(&cursor[key], 1u);
+        uint8_t* tile = side + (uint64_t)(slot / kSplitTile) * kBktSideBytes;
+        *reinterpret_cast<uint2*>(tile + (uint64_t)(slot % kSplitTile) * 8) = v;
+        *reinterpret_cast<uint32_t*>(tile + kBktPermOff + (uint64_t)(slot % kSplitTile) * 4) = pos_first + (uint32_t)i;
+    }
+}
+
+// Padding and planes of one block, one thread per 16-slot group: the padding slots of the group (perm == kBktPad; they follow the
+// bucket's real slots) get the code of the group's last real slot, a group without one (the block's tail) the code of the block's
+// last real slot; then the group's 12 nibble planes (nib_copy_kernel's in-plane layout) and its id are written.
+__global__ __launch_bounds__(256) void bkt_fill_kernel(uint8_t* __restrict__ tiles, uint8_t* __restrict__ side, uint32_t slots,
+                                                       uint32_t last_real) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= slots / 16) return;
+    const uint64_t tile = g / (kSplitTile / 16), lane = g % (kSplitTile / 16);
+    uint8_t* st = side + tile * kBktSideBytes;
+    uint2 v[16];
+    int last = -1;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        v[c] = *reinterpret_cast<const uint2*>(st + (lane * 16 + c) * 8);
+        if (*reinterpret_cast<const uint32_t*>(st + kBktPermOff + (lane * 16 + c) * 4) != kBktPad) last = c;
+    }
+    uint2 fillv = *reinterpret_cast<const uint2*>(side + (uint64_t)(last_real / kSplitTile) * kBktSideBytes +
+                                                  (uint64_t)(last_real % kSplitTile) * 8);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) fillv = c == last ? v[c] : fillv;
+    uint32_t o[kBktPlanes][2] = {};
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        if (c > last) {
+            v[c] = fillv;
+            *reinterpret_cast<uint2*>(st + (lane * 16 + c) * 8) = fillv;
+        }
+        const int sh = 8 * (c & 3) + 4 * ((c >> 2) & 1);
+#pragma unroll
+        for (int s = 4; s < 16; ++s) {
+            const uint32_t nibble = ((s < 8 ? v[c].x : v[c].y) >> (4 * (s & 7))) & 15u;
+            o[s - 4][c >> 3] |= nibble << sh;
+        }
+    }
+    uint8_t* tt = tiles + tile * kBktTileBytes;
+#pragma unroll
+    for (int s = 0; s < (int)kBktPlanes; ++s)
+        *reinterpret_cast<uint2*>(tt + (uint64_t)s * (kSplitTile / 2) + lane * 8) = make_uint2(o[s][0], o[s][1]);
+    *reinterpret_cast<uint16_t*>(tt + kBktIdOff + lane * 2) = (uint16_t)(v[0].x & 0xffffu);
+}
+
+void launch_bkt_hist_scan(const uint8_t* d_codes, uint32_t n, uint32_t* d_hist, uint32_t* d_off, uint32_t* d_info, hipStream_t stream) {
+    if (!n) return;
+    const unsigned wgs = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, 8192);
+    hipLaunchKernelGGL(bkt_hist_kernel, dim3(wgs), dim3(256), 0, stream, d_codes, n, d_hist);
+    hipLaunchKernelGGL(bkt_scan_kernel, dim3(1), dim3(1024), 0, stream, d_hist, d_off, d_info);
+}
+
+void launch_bkt_scatter_fill(const uint8_t* d_codes, uint32_t n, uint32_t pos_first, const uint32_t* d_off, uint32_t* d_cursor,
+                             uint8_t* d_tiles, uint8_t* d_side, uint32_t slots, uint32_t last_real, hipStream_t stream) {
+    if (!n || !slots) return;
+    const unsigned wgs = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, 8192);
+    hipLaunchKernelGGL(bkt_scatter_kernel, dim3(wgs), dim3(256), 0, stream, d_codes, n, pos_first, d_off, d_cursor, d_side);
+    hipLaunchKernelGGL(bkt_fill_kernel, dim3((slots / 16 + 255) / 256), dim3(256), 0, stream, d_tiles, d_side, slots, last_real);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1656,16 +2039,51 @@ static void launch_nib_variant(dim3 grid, hipStream_t stream, const ScanItem* d_
                        d_nib_sel, d_surv);
 }
 
+template <int NSP, bool NT, bool CHUNK, bool PROBE>
+static void launch_bkt_variant(dim3 grid, hipStream_t stream, const ScanItem* d_items, const int8_t* d_qtables,
+                               QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap, uint32_t R,
+                               const uint8_t* d_bkt_sel, unsigned long long* d_surv) {
+    auto k = &scan_i8_bkt_kernel<NSP, NT, CHUNK, PROBE>;
+    static std::atomic<uint64_t> done{0};
+    ensure_dynamic_lds(reinterpret_cast<const void*>(k), ScanCfg<16>::LDS_BYTES, done);
+    hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<16>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R,
+                       d_bkt_sel, d_surv);
+}
+
 // variant bits: [2] NT (non-temporal loads)  [3] CHUNK  [4] PROBE (ceiling diagnostic)
 // [5] split form (16x4, every run of the launch has ScanItem::split; not with [6]): 5 planes when d_plane_sel5 (the two
 //     deferred bytes and the slack of every table) is given, else 6 planes when d_plane_sel (the deferred byte of every
 //     table) is, else 7 (launch_plane_choice / launch_select_kth write both); d_surv: survivor counter or nullptr
 //     nib_ns = 8, 9 or 10 with d_nib_sel (ScanItem::split of every run points into the nibble-plane copy): the nibble form, before all of these
+//     bkt_nsp = 4..7 with d_bkt_sel (every run of the launch is a bucket-form run, LevelLaunch::bkt): the bucket form, before the nibble form
 // [6] sibling-major 1-D launch (every run of the launch covers the same codes; see the kernel's decode).  Other bits: ignored.
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap,
                     uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel, unsigned long long* d_surv,
-                    const uint8_t* d_plane_sel5, const uint8_t* d_nib_sel, int nib_ns) {
+                    const uint8_t* d_plane_sel5, const uint8_t* d_nib_sel, int nib_ns, const uint8_t* d_bkt_sel, int bkt_nsp) {
+    if (M == 16 && (variant & 32) && !(variant & 64) && d_bkt_sel && bkt_nsp >= 4 && bkt_nsp <= 7) {
+        const dim3 grid(wgs_per_item, nitems);
+#define QADC_BKT_ARGS grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, d_bkt_sel, d_surv
+#define QADC_BKT(NSP, PR)                                                       \
+    switch ((variant >> 2) & 3) {                                               \
+        case 0: launch_bkt_variant<NSP, false, false, PR>(QADC_BKT_ARGS); break; \
+        case 1: launch_bkt_variant<NSP, true, false, PR>(QADC_BKT_ARGS); break;  \
+        case 2: launch_bkt_variant<NSP, false, true, PR>(QADC_BKT_ARGS); break;  \
+        default: launch_bkt_variant<NSP, true, true, PR>(QADC_BKT_ARGS); break;  \
+    }
+        if (bkt_nsp == 4) {
+            if (variant & 16) { QADC_BKT(4, true) } else { QADC_BKT(4, false) }
+        } else if (bkt_nsp == 5) {
+            if (variant & 16) { QADC_BKT(5, true) } else { QADC_BKT(5, false) }
+        } else if (bkt_nsp == 6) {
+            if (variant & 16) { QADC_BKT(6, true) } else { QADC_BKT(6, false) }
+        } else {
+            if (variant & 16) { QADC_BKT(7, true) } else { QADC_BKT(7, false) }
+        }
+#undef QADC_BKT_ARGS
+#undef QADC_BKT
+        return;
+    }
     if (M == 16 && (variant & 32) && !(variant & 64) && d_nib_sel && nib_ns >= 8 && nib_ns <= 10) {
         const dim3 grid(wgs_per_item, nitems);
 #define QADC_NIB_ARGS grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, d_nib_sel, d_surv
@@ -2489,7 +2907,7 @@ void launch_start_scan_f32(int M, int sum_mode, const StartItem* d_items, int ni
 template <int BT>
 __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t* __restrict__ qt, QueryState* qs,
                                float qmax, int quant_mode, float* red /* [BT] LDS */, uint8_t* __restrict__ plane_sel,
-                               uint8_t* __restrict__ plane_sel5, uint8_t* __restrict__ nib_sel) {
+                               uint8_t* __restrict__ plane_sel5, uint8_t* __restrict__ nib_sel, uint8_t* __restrict__ bkt_sel) {
     const int t = threadIdx.x;
     float m = FLT_MAX;
     for (int i = t; i < table_dim_all; i += BT) m = fminf(m, tb[i]);
@@ -2514,7 +2932,7 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
         else o = (int8_t)(int)(quant_mode == 0 ? (v - qmin) / delta : (v - qmin) * scale);
         qt[i] = o;
     }
-    if (plane_sel || plane_sel5 || nib_sel) {              // 16x4: the 6-, 5-plane and nibble forms' choices of each table
+    if (plane_sel || plane_sel5 || nib_sel || bkt_sel) {   // 16x4: the 6-, 5-plane, nibble and bucket forms' choices of each table
         __syncthreads();
         for (int i = t; i < table_dim_all / 256; i += BT) {
             if (plane_sel) plane_sel[i] = (uint8_t)plane_choice(qt + (size_t)i * 256);
@@ -2524,6 +2942,7 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
                 plane_sel5[2 * i + 1] = (uint8_t)(c5 >> 8);
             }
             if (nib_sel) plane_choice_nib(qt + (size_t)i * 256, nib_sel + (size_t)i * kNibSelBytes);
+            if (bkt_sel) plane_choice_bkt(qt + (size_t)i * 256, bkt_sel + (size_t)i * kBktSelBytes);
         }
     }
     if (t == 0) { qs->qmin = qmin; qs->flags |= flags; }   // keeps bit3 set by the pre-scan
@@ -2541,7 +2960,7 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
                                                         float* __restrict__ export_vals,
                                                         uint32_t* __restrict__ export_flags, uint32_t* __restrict__ front_out,
                                                         uint8_t* __restrict__ plane_sel, uint8_t* __restrict__ plane_sel5,
-                                                        uint8_t* __restrict__ nib_sel) {
+                                                        uint8_t* __restrict__ nib_sel, uint8_t* __restrict__ bkt_sel) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t s_prefix, s_k, s_hi, s_cnt;
     __shared__ float red[BT];
@@ -2567,7 +2986,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
         if (qtables) quantize_query<BT>(table_dim_all, ftables + (uint64_t)q * table_dim_all, qtables + (uint64_t)q * table_dim_all,
                                         qs, FLT_MAX, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr,
                                         plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr,
-                                        nib_sel ? nib_sel + (size_t)kNibSelBytes * q * (table_dim_all / 256) : nullptr);
+                                        nib_sel ? nib_sel + (size_t)kNibSelBytes * q * (table_dim_all / 256) : nullptr,
+                                        bkt_sel ? bkt_sel + (size_t)kBktSelBytes * q * (table_dim_all / 256) : nullptr);
         publish_front();
         return;
     }
@@ -2638,7 +3058,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
     if (qtables) quantize_query<BT>(table_dim_all, ftables + (uint64_t)q * table_dim_all, qtables + (uint64_t)q * table_dim_all,
                                     qs, qmax, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr,
                                         plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr,
-                                        nib_sel ? nib_sel + (size_t)kNibSelBytes * q * (table_dim_all / 256) : nullptr);
+                                        nib_sel ? nib_sel + (size_t)kNibSelBytes * q * (table_dim_all / 256) : nullptr,
+                                        bkt_sel ? bkt_sel + (size_t)kBktSelBytes * q * (table_dim_all / 256) : nullptr);
     publish_front();
 }
 
@@ -2675,15 +3096,15 @@ void launch_prescan_minmax(const float* d_vals, uint32_t nvals, int nq, QuerySta
 void launch_select_kth(const float* d_fc, uint64_t fc_stride, const uint32_t* d_fc_init, int nq, uint32_t R, QueryState* d_qs,
                        int max_passes, float* d_ftables, int8_t* d_qtables, int table_dim_all, int quant_mode,
                        hipStream_t stream, float* export_vals, uint32_t* export_flags, uint32_t* d_front_out, int small_wg,
-                       uint8_t* d_plane_sel, uint8_t* d_plane_sel5, uint8_t* d_nib_sel) {
+                       uint8_t* d_plane_sel, uint8_t* d_plane_sel5, uint8_t* d_nib_sel, uint8_t* d_bkt_sel) {
     if (small_wg)
         hipLaunchKernelGGL((select_kth_kernel<256>), dim3(nq), dim3(256), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
                            d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel,
-                           d_plane_sel5, d_nib_sel);
+                           d_plane_sel5, d_nib_sel, d_bkt_sel);
     else
         hipLaunchKernelGGL((select_kth_kernel<1024>), dim3(nq), dim3(1024), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
                            d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel,
-                           d_plane_sel5, d_nib_sel);
+                           d_plane_sel5, d_nib_sel, d_bkt_sel);
 }
 
 // ---- stream-layout probe (qadc_stream_probe): does a dispatch that WAITS FOR CUs on stream A hold up stream B? ----

@@ -29,6 +29,8 @@ struct ScanItem {
     uint32_t dup_reps;       // number of extra replays of that code: (16 - n % 16) % 16
     const uint8_t* split;    // 16x4: the run's first tile in the partition's byte-plane copy (launch_split_copy), or nullptr; in a
                              // launch of the nibble form (LevelLaunch::nib): that tile in the nibble-plane copy (launch_nib_copy)
+                             // In a launch of the bucket form (LevelLaunch::bkt): the run's first tile in the bucket copy's planes; codes =
+                             // that tile in the copy's per-slot side array (kBktSideBytes per tile), n = the run's SLOTS (whole tiles)
 };
 
 // Byte-plane copy of code bytes 0-6 (16x4 only), the input of the split form of scan_i8_kernel: tile t of a partition holds
@@ -46,6 +48,24 @@ constexpr uint32_t kNibTileBytes = 8 * kSplitTile;
 // The nibble form's choice bytes of one table: 4 bytes for each NS = 8, 9, 10 streamed sub-quantizers at 4 * (NS - 8):
 // the deferred set as a 16-bit mask (low byte first), the slack c, 0.
 constexpr uint32_t kNibSelBytes = 12;
+
+// Bucket copy (16x4 only), the input of scan_i8_bkt_kernel.  A partition is cut into blocks of bkt_block codes from its first code
+// (the last may be short); inside a block the codes are grouped by key = code byte 0 | code byte 1 << 8 (sub-quantizers 0-3).
+// Every non-empty bucket is padded to a multiple of 16 slots with copies of its last code, and the block to whole kSplitTile-slot
+// tiles with copies of its last code, so every 16-slot lane group has ONE key.  Tile t of the copy holds slots
+// [t * kSplitTile, (t + 1) * kSplitTile): 12 nibble planes of kSplitTile / 2 bytes (sub-quantizers 4-15, the nibble copy's
+// in-plane layout), then the id plane, one uint16 key per 16-slot group.  Beside it, per tile, the side array: the slots' 8-byte
+// codes (read by survivors), then their uint32 positions in the partition (perm; read by candidates; a padding slot: kBktPad).
+constexpr uint32_t kBktPlanes = 12;
+constexpr uint32_t kBktIdOff = kBktPlanes * (kSplitTile / 2);                  // byte offset of the id plane in a tile
+constexpr uint32_t kBktTileBytes = kBktIdOff + kSplitTile / 16 * 2;
+constexpr uint32_t kBktPermOff = 8 * kSplitTile;                               // byte offset of perm in a tile of the side array
+constexpr uint32_t kBktSideBytes = kBktPermOff + 4 * kSplitTile;
+constexpr uint32_t kBktPad = 0xffffffffu;
+constexpr uint32_t kBktKeys = 65536;
+// The bucket form's choice bytes of one table: 4 bytes for each NSP = 4, 5, 6, 7 paid sub-quantizers at 4 * (NSP - 4): the
+// deferred set among sub-quantizers 4-15 as a 16-bit mask (low byte first), the slack c, 0.
+constexpr uint32_t kBktSelBytes = 16;
 
 constexpr int kMaxLevels = 16;  // bound levels per query
 
@@ -84,6 +104,10 @@ struct LevelLaunch {
     bool split5 = false;   // split, and every run has at least split5_min_run codes: the 5-plane form (the launcher prefers 5 over 6 over 7)
     int nib = 0;           // 8, 9 or 10: split, every run starts on a tile of its partition's nibble-plane copy and has at least the form's
                            // threshold of codes: scan_i8_nib_kernel streams that many of the 16 sub-quantizers (preferred over 5 planes); 0: not
+    uint64_t slots = 0;    // bkt: the slots of the launch's runs (what it streams; codes stays what the runs cover)
+    int bkt = 0;           // 4, 5, 6 or 7: split, every run covers whole blocks of its partition's bucket copy (bkt_run_ok): scan_i8_bkt_kernel
+                           // streams that many of sub-quantizers 4-15 (preferred over the nibble form; nib is 0 then); 0: not.  The runs
+                           // then count slots (ScanItem::n) and wgs derives from them; codes and maxn stay the codes the runs cover
 };
 
 // What the planner reads of a partition (the index's Part derives from it: one partition table, no copy).
@@ -93,6 +117,10 @@ struct LevelPart {
     uint8_t* d_starts = nullptr;   // replica of the global partition's first codes (null: d_codes, first_pos == 0)
     uint8_t* d_split = nullptr;    // 16x4: byte-plane copy of code bytes 0-6 for the split scan (kSplitTile), or null
     uint8_t* d_nib = nullptr;      // 16x4: nibble-plane copy of all 16 sub-quantizers (kNibTileBytes per tile), or null
+    uint8_t* d_bkt = nullptr;      // 16x4: the bucket copy's tiles (kBktTileBytes per tile), or null
+    uint8_t* d_bkt_side = nullptr; // ... and its side array (kBktSideBytes per tile)
+    uint64_t bkt_block = 0;        // codes per block of the copy (a power of two, a multiple of kSplitTile)
+    std::vector<uint64_t> bkt_off; // [blocks + 1] first slot of every block (multiples of kSplitTile), and the copy's slots
     uint32_t n = 0;                // codes held here
     uint32_t global_n = 0;         // codes of the whole partition (== n unless sharded)
     uint32_t first_pos = 0;        // global position of local code 0
@@ -114,6 +142,9 @@ struct LevelOptions {
     // stream nib_ns (9 or 10) of them; 0 = never
     uint64_t nib_min_run = 0, nib8_min_run = 0;
     int nib_ns = 9;
+    // the bucket form: runs of at least bkt_min_run codes that cover whole blocks of a bucket copy stream 7 of sub-quantizers 4-15,
+    // those of at least bkt6_min_run 6, bkt5_min_run 5, bkt4_min_run 4 (the fewest whose threshold the launch's shortest run reaches); 0 = never
+    uint64_t bkt_min_run = 0, bkt6_min_run = 0, bkt5_min_run = 0, bkt4_min_run = 0;
 };
 struct LevelBatch {
     int nq, ma;
@@ -191,6 +222,23 @@ inline int wgs_streaming(const LevelOptions& o, uint64_t maxn, uint64_t nvec, si
     return (int)std::min<uint64_t>(std::max<uint64_t>(units, 1), std::min<uint64_t>(wgs_cap, want));
 }
 
+// May the run [b0, b0 + len) of partition pt take the bucket form?  The partition has the copy, the run starts on a block of it,
+// ends on one or at the partition's end, and has at least bkt_min_run codes.
+inline bool bkt_run_ok(const LevelPart& pt, const LevelOptions& o, uint64_t b0, uint64_t len) {
+    if (!pt.d_bkt || !pt.d_bkt_side || !pt.bkt_block || pt.bkt_off.empty() || o.bkt_min_run == 0 || len < o.bkt_min_run) return false;
+    return b0 % pt.bkt_block == 0 && ((b0 + len) % pt.bkt_block == 0 || b0 + len == pt.n);
+}
+// Paid planes of a bucket launch whose shortest run has minn codes
+inline int bkt_planes(const LevelOptions& o, uint64_t minn) {
+    return o.bkt4_min_run != 0 && minn >= o.bkt4_min_run ? 4 : o.bkt5_min_run != 0 && minn >= o.bkt5_min_run ? 5
+           : o.bkt6_min_run != 0 && minn >= o.bkt6_min_run ? 6 : 7;
+}
+
+// Can some run of a partition with a bucket copy still take the nibble form?  Exact for an index of ONE partition, whose
+// scan order always starts at the partition's first code (qadc_index_finalize skips the nibble-plane copy when this says no);
+// with more partitions the cuts depend on the probe lists, and the answer is yes.  Follows the cuts of plan_levels.
+inline bool nib_still_needed(const LevelPart& pt, const LevelOptions& o, bool only_partition);
+
 // Host planning of one batch: cuts every query's scan order into bound levels, emits the runs (ScanItem) and the
 // pre-scan items (StartItem), and decides kernel and grid per level launch.  Part: LevelPart, or a struct derived from it.
 template <class Part>
@@ -202,6 +250,8 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
     level_bounds(o, L);
     std::vector<std::vector<ScanItem>> per_level(kMaxLevels);
     std::vector<std::vector<const uint8_t*>> per_level_nib(kMaxLevels);   // beside every run: its tile in the nibble-plane copy, or nullptr
+    struct BktRun { const uint8_t* tiles; const uint8_t* side; uint64_t slots; };
+    std::vector<std::vector<BktRun>> per_level_bkt(kMaxLevels);           // ... and in the bucket copy (tiles == nullptr: the run does not qualify)
     const int k0 = (b.mode != 1 && o.head_level > 0) ? o.head_level : 0;   // levels < k0 belong to the head launch
     plan.head_codes = k0 ? L[k0] : 0;
     plan.fc_init.assign(2 * (size_t)nq, 0);
@@ -298,6 +348,16 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
                                    ? pt.d_split + b0 / kSplitTile * (uint64_t)kSplitBytes * kSplitTile : nullptr;
                     // ... and, where the partition has a nibble-plane copy as well, the nibble form (same tiles)
                     per_level_nib[k].push_back(it.split && pt.d_nib ? pt.d_nib + b0 / kSplitTile * (uint64_t)kNibTileBytes : nullptr);
+                    BktRun br{nullptr, nullptr, 0};
+                    if (it.split && bkt_run_ok(pt, o, b0, len)) {
+                        const size_t blk0 = (size_t)(b0 / pt.bkt_block);
+                        const size_t blk1 = std::min<size_t>((size_t)((b0 + len + pt.bkt_block - 1) / pt.bkt_block), pt.bkt_off.size() - 1);
+                        const uint64_t s0 = pt.bkt_off[blk0], s1 = pt.bkt_off[blk1];
+                        if (blk1 > blk0 && s1 > s0 && s1 - s0 <= 0xffffffffull && s0 % kSplitTile == 0 && s1 % kSplitTile == 0)
+                            br = BktRun{pt.d_bkt + s0 / kSplitTile * (uint64_t)kBktTileBytes,
+                                        pt.d_bkt_side + s0 / kSplitTile * (uint64_t)kBktSideBytes, s1 - s0};
+                    }
+                    per_level_bkt[k].push_back(br);
                     per_level[k].push_back(it);
                     b0 += len;
                 }
@@ -325,8 +385,9 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
             const int small = cls == 0 ? 1 : 0;
             uint64_t maxn = 0, minn = ~0ull, codes = 0;
             size_t cnt = 0;
-            bool same = true, all_nib = true;
+            bool same = true, all_nib = true, all_bkt = true;
             std::vector<const uint8_t*> nibs;
+            std::vector<BktRun> bkts;
             for (size_t r = 0; r < per_level[k].size(); ++r) {
                 const ScanItem& it = per_level[k][r];
                 if ((it.n < o.small_run) != (small == 1)) continue;
@@ -342,6 +403,8 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
                 codes += it.n;
                 all_nib = all_nib && per_level_nib[k][r] != nullptr;
                 nibs.push_back(per_level_nib[k][r]);
+                all_bkt = all_bkt && per_level_bkt[k][r].tiles != nullptr;
+                bkts.push_back(per_level_bkt[k][r]);
             }
             if (!cnt) continue;
             const uint64_t nvec = (maxn + cpl - 1) / cpl;
@@ -360,11 +423,25 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
                      : o.nib8_min_run != 0 && minn >= o.nib8_min_run    ? 8
                      : o.nib_min_run != 0 && minn >= o.nib_min_run      ? (o.nib_ns == 10 ? 10 : 9)
                                                                         : 0;
+            ll.bkt = ll.split && all_bkt ? bkt_planes(o, minn) : 0;
+            uint64_t max_slots = 0;
+            if (ll.bkt) {                                                // the launch reads the bucket copy: its runs count slots
+                ll.nib = 0;
+                for (size_t r = 0; r < cnt; ++r) {
+                    ScanItem& it = plan.all_items[off + r];
+                    it.split = bkts[r].tiles;
+                    it.codes = bkts[r].side;
+                    it.n = (uint32_t)bkts[r].slots;
+                    max_slots = std::max(max_slots, bkts[r].slots);
+                    ll.slots += bkts[r].slots;
+                }
+            }
             if (ll.nib)                                                  // the launch reads the nibble-plane copy instead
                 for (size_t r = 0; r < cnt; ++r) plan.all_items[off + r].split = nibs[r];
             ll.wgs = ll.mq       ? wgs_mq(o, maxn, nvec, cnt)
                      : ll.shared ? wgs_shared(o, maxn, nvec)
                      : ll.small  ? wgs_small(nvec, cnt)
+                     : ll.bkt    ? wgs_streaming(o, max_slots, (max_slots + cpl - 1) / cpl, cnt, true)
                                  : wgs_streaming(o, maxn, nvec, cnt, ll.split);
             ll.codes = codes;
             plan.launches.push_back(ll);
@@ -372,6 +449,30 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
         }
     }
     return plan;
+}
+
+inline bool nib_still_needed(const LevelPart& pt, const LevelOptions& o, bool only_partition) {
+    if (!pt.d_bkt || !only_partition) return true;
+    const uint64_t nib_min = o.nib_min_run && o.nib8_min_run ? std::min(o.nib_min_run, o.nib8_min_run) : std::max(o.nib_min_run, o.nib8_min_run);
+    if (nib_min == 0) return false;
+    const uint32_t cpl = 16 / (o.M / 2);
+    uint64_t L[kMaxLevels + 1];
+    level_bounds(o, L);
+    uint64_t prev = 0;
+    for (int k = 0; k < kMaxLevels && prev < pt.n; ++k) {
+        uint64_t cut = pt.n;
+        if (L[k + 1] < pt.n) cut = L[k + 1] - L[k + 1] % cpl;
+        if (cut <= prev) continue;
+        for (uint64_t b0 = prev; b0 < cut;) {
+            const uint64_t len = std::min<uint64_t>(cut - b0, 1ull << 31);
+            if (len >= std::max<uint64_t>(nib_min, std::max<uint64_t>(o.split_min_run, o.small_run)) && b0 % kSplitTile == 0 &&
+                !bkt_run_ok(pt, o, b0, len))
+                return true;
+            b0 += len;
+        }
+        prev = cut;
+    }
+    return false;
 }
 
 }  // namespace host

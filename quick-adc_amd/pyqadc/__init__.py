@@ -32,7 +32,7 @@ SYMBOLS = [
     "qadc_scan_i8_candidates", "qadc_scan_start", "qadc_query_scan_submit", "qadc_prescan_submit",
     "qadc_prescan_collect", "qadc_query_scan_submit_prescanned",
     "qadc_query_scan_collect", "qadc_index_set_pq", "qadc_index_set_rotation", "qadc_index_set_coarse", "qadc_search", "qadc_search_submit",
-    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6", "qadc_index_set_split5", "qadc_index_set_split_nib", "qadc_nib_choice",
+    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6", "qadc_index_set_split5", "qadc_index_set_split_nib", "qadc_nib_choice", "qadc_index_set_split_bkt", "qadc_bkt_choice", "qadc_index_bkt_info", "qadc_index_bkt_read",
     "qadc_dist_unique_id", "qadc_dist_init", "qadc_dist_collect", "qadc_dist_shutdown", "qadc_dist_merge_blocks", "qadc_dist_merge_blocks_host",
     "qadc_dist_init_transport", "qadc_dist_init_loopback", "qadc_shm_transport_open", "qadc_shm_transport_allgather", "qadc_shm_transport_allgather_host",
     "qadc_shm_transport_close", "qadc_shm_transport_error", "qadc_slot_assign", "qadc_slot_qtables", "qadc_place_partitions",
@@ -73,7 +73,10 @@ class Profile(C.Structure):
                 ("split5_launches", C.c_uint64), ("split5_codes", C.c_uint64), ("split5_survivors", C.c_uint64),
                 ("nib_copy_bytes", C.c_uint64), ("nib_copy_failed", C.c_uint64),
                 ("nib_launches", C.c_uint64), ("nib_codes", C.c_uint64), ("nib_survivors", C.c_uint64),
-                ("nib8_launches", C.c_uint64), ("nib8_codes", C.c_uint64), ("nib8_survivors", C.c_uint64)]
+                ("nib8_launches", C.c_uint64), ("nib8_codes", C.c_uint64), ("nib8_survivors", C.c_uint64),
+                ("bkt_copy_bytes", C.c_uint64), ("bkt_copy_slots", C.c_uint64), ("bkt_copy_failed", C.c_uint64),
+                ("bkt_copy_padded_out", C.c_uint64), ("bkt_launches", C.c_uint64), ("bkt_codes", C.c_uint64),
+                ("bkt_slots", C.c_uint64), ("bkt_survivors", C.c_uint64)]
 
 
 QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h
@@ -123,6 +126,10 @@ def lib():
         L.qadc_index_set_split5.argtypes = [C.c_void_p, C.c_uint64]
         L.qadc_index_set_split_nib.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int]
         L.qadc_nib_choice.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.qadc_index_set_split_bkt.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double]
+        L.qadc_bkt_choice.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.qadc_index_bkt_info.argtypes = [C.c_void_p, C.c_int, u64p, u64p, u64p]
+        L.qadc_index_bkt_read.argtypes = [C.c_void_p, C.c_int, u64p, u8p, u8p]
         L.qadc_index_read_codes.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u8p]
         L.qadc_query_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, u32p, i8p, i32p, i32p,
                                       f32p, f32p, i8p]
@@ -286,6 +293,15 @@ def nib_choice(qtables, device=0):
     qt = np.ascontiguousarray(qtables, np.int8).reshape(-1, 256)
     out = np.zeros((qt.shape[0], 3, 4), np.uint8)
     _check(lib().qadc_nib_choice(int(device), qt.ctypes.data_as(C.c_void_p), int(qt.shape[0]), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def bkt_choice(qtables, device=0):
+    """qadc_bkt_choice: the bucket form's choice bytes of 16x4 int8 tables [..., 16, 16] as the device computes them ->
+    uint8 [ntables, 4, 4]: for NSP = 4, 5, 6, 7 the deferred mask among sub-quantizers 4-15 (two bytes, low first), the slack, 0."""
+    qt = np.ascontiguousarray(qtables, np.int8).reshape(-1, 256)
+    out = np.zeros((qt.shape[0], 4, 4), np.uint8)
+    _check(lib().qadc_bkt_choice(int(device), qt.ctypes.data_as(C.c_void_p), int(qt.shape[0]), out.ctypes.data_as(C.c_void_p)))
     return out
 
 
@@ -722,6 +738,31 @@ class Index:
         from a nibble-plane copy, those with >= min_run8 codes 8 of them; preferred to the 5-plane form (0 = never); results
         do not change.  Set before finalize: the copy (8 bytes per code) is built there."""
         _check(lib().qadc_index_set_split_nib(self._h, int(min_run), int(min_run8), int(ns)))
+
+    def set_split_bkt(self, bkt_min_run, bkt_block=0, min_run6=0, min_run5=0, min_run4=0, bkt_max_pad=0.0):
+        """Bucket form (16x4): finalize builds a bucket copy (blocks of bkt_block codes grouped by their first two bytes; about
+        18.4 bytes per code) of partitions with >= bkt_min_run codes (0 = off); split launches whose runs all have >= bkt_min_run
+        codes and cover whole blocks stream 7 of sub-quantizers 4-15, those with >= min_run6 / min_run5 / min_run4 codes 6 / 5 / 4
+        (0 = never); preferred to the nibble form; results do not change.  bkt_block, bkt_max_pad: 0 = keep.  Turn the form on
+        or off and set bkt_block before finalize."""
+        _check(lib().qadc_index_set_split_bkt(self._h, int(bkt_min_run), int(bkt_block), int(min_run6), int(min_run5),
+                                              int(min_run4), float(bkt_max_pad)))
+
+    def bkt_copy(self, part):
+        """Diagnostic: partition part's bucket copy, or None.  -> dict(block, off uint64 [blocks + 1], tiles uint8
+        [ntiles, 100352], codes uint8 [slots, 8], perm uint32 [slots]) (include/qadc.h: qadc_index_bkt_read)."""
+        block, nblocks, slots = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().qadc_index_bkt_info(self._h, part, C.byref(block), C.byref(nblocks), C.byref(slots)))
+        if not block.value:
+            return None
+        nt = slots.value // 16384
+        off = np.zeros(nblocks.value + 1, np.uint64)
+        tiles = np.zeros((nt, 100352), np.uint8)
+        side = np.zeros((nt, 196608), np.uint8)
+        _check(lib().qadc_index_bkt_read(self._h, part, _p(off, u64p), _p(tiles, u8p), _p(side, u8p)))
+        codes = np.ascontiguousarray(side[:, :131072]).reshape(-1, 8)
+        perm = np.ascontiguousarray(side[:, 131072:]).view(np.uint32).reshape(-1)
+        return {"block": block.value, "off": off, "tiles": tiles, "codes": codes, "perm": perm}
 
     def partition_count(self):
         return lib().qadc_index_partition_count(self._h)

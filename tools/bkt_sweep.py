@@ -1,0 +1,104 @@
+"""Same-process sweep behind the bucket form's defaults (profiles/r11_bkt_ab.txt).
+usage: python tools/bkt_sweep.py [reps=2] [codes=1e9]
+
+One index of the headline's list and mode (bench.py's one-query-per-pass options, 32-query steps pipelined three deep) holding
+BOTH the bucket copy (blocks of 2^25) and the nibble-plane copy: it is finalized with bkt_min_run above every run (600 Mi), so
+that finalize still builds the nibble-plane copy, and the thresholds are moved afterwards.  Arms, interleaved inside every round,
+order alternated: "off" = the nibble defaults (9 / 9 / 8 streamed); "pXYZ" = X, Y and Z paid planes at the levels from 2^25, 2^27
+and 2^29 (runs of 96, 384 and 421 Mi codes) with bkt_min_run = 2^25; "b27:pYZ" = bkt_min_run = 2^27 (the level from 2^25 keeps 9
+nibble planes).  A first section times the PROBE builds (variant bit 16) of "off" and of two arms.  One JSON line per (section,
+round, arm): ms per step and the library's bkt_* and nib_* counters per step; a last line has the copies' sizes and the finalize time."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+
+MI = 1 << 20
+NEVER = 1 << 40
+
+
+def arm_thresholds(name):
+    """-> (bkt_min_run, min_run6, min_run5, min_run4)"""
+    if name == "off":
+        return NEVER, 0, 0, 0
+    lo = 128 * MI if name.startswith("b27:") else 32 * MI
+    planes = [int(c) for c in name.split("p")[1]]
+    planes = [planes[0]] * (3 - len(planes)) + planes          # per level from 2^25, 2^27, 2^29 (non-increasing)
+    reach = (32 * MI, 128 * MI, 400 * MI)                        # a threshold that the level's runs and the longer ones reach
+    t = {}
+    for want in (6, 5, 4):
+        first = [i for i, p in enumerate(planes) if p <= want]
+        t[want] = reach[first[0]] if first else 0
+    return lo, t[6], t[5], t[4]
+
+
+def main():
+    import torch
+    import pyqadc
+    torch.zeros(1, device="cuda:0")
+    pyqadc.device_prepare(0)
+    import gc
+    gc.collect(); gc.freeze(); gc.disable()
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 2
+    n = int(float(sys.argv[2])) if len(sys.argv) > 2 else int(1e9)
+    steps, warmup, nq, M = 10, 3, 32, 16
+    rng = np.random.default_rng(1234)
+    codebooks = rng.normal(size=(M, 16, 128 // M)).astype(np.float32)
+    pool = [bench.make_tables(rng, codebooks, nq) for _ in range(4)]
+    assign = np.zeros((nq, 1), np.int32)
+
+    def run(idx, k):
+        pending = []
+        for s in range(k):
+            idx.submit(s % 3, assign, pool[s % len(pool)].copy(), bench.R)
+            pending.append(s % 3)
+            if len(pending) == 3:
+                idx.collect(pending.pop(0))
+        while pending:
+            idx.collect(pending.pop(0))
+
+    idx = pyqadc.Index(M, 0)
+    idx.set_split_bkt(600 * MI, 1 << 25)
+    idx.add_partition_synthetic_shard(n, 0, n, bench.SEED, max(1, int(np.float32(n) * np.float32(bench.KEEP))))
+    t0 = time.perf_counter()
+    idx.finalize(bench.KEEP)
+    finalize_s = time.perf_counter() - t0
+    idx.set_option("profile", 1)
+    bench.set_mode(idx, bench.MODE_ONE_QUERY_PER_PASS)
+    sizes = {k: int(idx.profile()[k]) for k in ("split_copy_bytes", "nib_copy_bytes", "bkt_copy_bytes", "bkt_copy_slots")}
+
+    def measure(section, rep, name, variant):
+        idx.set_option("variant", variant)
+        lo, t6, t5, t4 = arm_thresholds(name)
+        idx.set_split_bkt(lo, 0, t6, t5, t4)
+        run(idx, warmup)
+        idx.profile_reset()
+        t0 = time.perf_counter()
+        run(idx, steps)
+        ms = (time.perf_counter() - t0) * 1e3 / steps
+        pr = idx.profile()
+        keys = ("bkt_launches", "bkt_codes", "bkt_slots", "bkt_survivors", "nib_codes", "nib_survivors", "nib8_codes", "nib8_survivors")
+        print(json.dumps({"section": section, "round": rep, "arm": name, "ms_per_step": round(ms, 4),
+                          **{k + "_per_step": int(pr[k] // steps) for k in keys}}), flush=True)
+
+    probe = ["off", "p655", "p654"]
+    arms = ["off", "p777", "p666", "p665", "p655", "p654", "p555", "p554", "p544", "p444", "p755", "p765",
+            "b27:p66", "b27:p65", "b27:p55", "b27:p54"]
+    for rep in range(reps):
+        for name in (probe if rep % 2 == 0 else probe[::-1]):
+            measure("probe", rep, name, 0x0d | 16)
+    for rep in range(reps):
+        for name in (arms if rep % 2 == 0 else arms[::-1]):
+            measure("sweep", rep, name, 0x0d)
+    print(json.dumps({"section": "sizes", "codes": n, "finalize_s": round(finalize_s, 3), **sizes}), flush=True)
+    idx.close()
+
+
+if __name__ == "__main__":
+    main()

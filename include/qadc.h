@@ -545,6 +545,10 @@ typedef struct qadc_profile {
     uint64_t bkt_codes;             /* of split_codes: codes their runs cover */
     uint64_t bkt_slots;             /* slots they streamed: those codes plus the padding copies */
     uint64_t bkt_survivors;         /* (slot, query) pairs of those launches whose partial sum was below the bound less the slack */
+    uint64_t bkt4_launches;         /* of bkt_launches: those that paid for 4 of sub-quantizers 4-15 (host/level_plan.hpp: bkt_planes), */
+    uint64_t bkt5_launches;         /* ... for 5, */
+    uint64_t bkt6_launches;         /* ... for 6 */
+    uint64_t bkt7_launches;         /* ... and for 7: the four add up to bkt_launches */
 } qadc_profile;
 
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);

@@ -756,6 +756,10 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             count_nib = count_nib || ll.nib > 8;
             count_nib8 = count_nib8 || ll.nib == 8;
             idx->prof.bkt_launches += ll.bkt ? 1 : 0;
+            idx->prof.bkt4_launches += ll.bkt == 4 ? 1 : 0;
+            idx->prof.bkt5_launches += ll.bkt == 5 ? 1 : 0;
+            idx->prof.bkt6_launches += ll.bkt == 6 ? 1 : 0;
+            idx->prof.bkt7_launches += ll.bkt == 7 ? 1 : 0;
             idx->prof.bkt_codes += ll.bkt ? ll.codes : 0;
             idx->prof.bkt_slots += ll.bkt ? ll.slots : 0;
             count_bkt = count_bkt || ll.bkt;

@@ -76,7 +76,9 @@ class Profile(C.Structure):
                 ("nib8_launches", C.c_uint64), ("nib8_codes", C.c_uint64), ("nib8_survivors", C.c_uint64),
                 ("bkt_copy_bytes", C.c_uint64), ("bkt_copy_slots", C.c_uint64), ("bkt_copy_failed", C.c_uint64),
                 ("bkt_copy_padded_out", C.c_uint64), ("bkt_launches", C.c_uint64), ("bkt_codes", C.c_uint64),
-                ("bkt_slots", C.c_uint64), ("bkt_survivors", C.c_uint64)]
+                ("bkt_slots", C.c_uint64), ("bkt_survivors", C.c_uint64),
+                ("bkt4_launches", C.c_uint64), ("bkt5_launches", C.c_uint64), ("bkt6_launches", C.c_uint64),
+                ("bkt7_launches", C.c_uint64)]
 
 
 QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h

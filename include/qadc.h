@@ -969,6 +969,59 @@ int qadc_adc_filter_destroy(qadc_adc_filter* f);
  * (qadc_query_scan, qadc_search), whose users filter through a view (qadc_adc_index_create_view). */
 int qadc_adc_index_set_filter(qadc_adc_index* idx, const qadc_adc_filter* f);
 
+/* ---- exact re-ranking: the vectors on the GPU, candidates reordered by L2 ----
+ * Both engines rank by a quantized distance.  A refine store keeps the original vectors in device memory, and a rerank call reorders
+ * the candidate keys a search returned — with a larger R than wanted — by the true squared L2 distance to those vectors.  The store
+ * belongs to no index: it consumes uint32 keys, whoever produced them, and is DENSE over a key range: row r holds the vector of key
+ * lo + r, which is how qadc_adc_index_add_vectors and qadc_index_add_vectors label (labels_offset + i) and how a flat index's
+ * position keys run.  Everything below is held, bit for bit, to the host twin quick-adc_amd/host/refine.hpp:
+ *   distance   D(q, x) in binary32, every operation rounded by itself, no fused multiply-add: 64 partial sums p[l] over the
+ *              components 64 j + l in ascending j (t = q[i] - x[i]; p[l] = p[l] + t * t), then p[l] = p[l] + p[l + s] for l < s at
+ *              s = 32, 16, 8, 4, 2, 1; D = p[0].  A row of an F16 store is the float value of the stored half, the stored half the
+ *              round-to-nearest-even conversion of the input float (subnormals kept, overflow to +-inf).
+ *   selection  of keys[q][0 .. count_q): an entry is skipped where values are given and values[q][i] == FLT_MAX (the float-ADC heap's
+ *              sentinel), missing (dropped, counted) where its key is outside [lo, lo + rows); the others are ordered ascending by
+ *              (distance, key) — a NaN distance behind +inf, returned as 0x7FC00000 — a key listed several times kept once, and the
+ *              first min(R, survivors) come out; the slots behind out_sizes[q] hold key 0xFFFFFFFF and distance +inf.
+ * The output is a sorted list, not a heap array, and depends only on the set of candidate keys.  Limits: keys dense from lo; rows are
+ * neither removed nor overwritten; r_in <= QADC_REFINE_MAX_IN; L2 only; one device; every call is synchronous. */
+#define QADC_REFINE_F32 0
+#define QADC_REFINE_F16 1
+#define QADC_REFINE_MAX_IN 8192   /* most candidates per query a rerank call takes */
+#define QADC_REFINE_MAX_DIM 4096
+typedef struct qadc_refine qadc_refine;
+/* An empty store of dim-float vectors (1 .. QADC_REFINE_MAX_DIM) kept as floats or halves on device_id.  QADC_E_ARG before the device
+ * is touched: out NULL, a bad dim or dtype. */
+int qadc_refine_create(qadc_refine** out, int dim, int dtype, int device_id);
+/* Frees the store; NULL is a no-op. */
+int qadc_refine_destroy(qadc_refine* r);
+/* Appends vectors [count][dim] from host memory as the rows of the keys first_key .. first_key + count - 1.  The first add fixes
+ * lo = first_key; a later one must continue at lo + rows.  The F16 conversion runs on the GPU.  The allocation grows by 1.5 x (or to
+ * what the call needs) with one device-to-device copy.  count = 0 is a no-op.  QADC_E_ARG before the device is touched, the store
+ * left as it was: r NULL, vectors NULL, a first_key that does not continue the store, first_key + count above 2^32. */
+int qadc_refine_add(qadc_refine* r, const float* vectors, uint64_t count, uint32_t first_key);
+/* The same with d_vectors in device memory of the store's device, complete before the call: read where they lie and only by a
+ * kernel, so memory of another HIP runtime is legal — and the library cannot tell which device a pointer belongs to: as with
+ * qadc_adc_filter_create_device, the store names the device. */
+int qadc_refine_add_device(qadc_refine* r, const float* d_vectors, uint64_t count, uint32_t first_key);
+/* Room for `rows` rows in all (no-op where the allocation holds them already): the adds up to there relocate nothing. */
+int qadc_refine_reserve(qadc_refine* r, uint64_t rows);
+/* Any output may be NULL: dim, dtype, lo (0 while empty), the rows held and the bytes of the allocation (capacity x row size). */
+int qadc_refine_info(const qadc_refine* r, int* dim, int* dtype, uint32_t* lo, uint64_t* rows, uint64_t* bytes);
+/* Adds that moved the rows held to grow the allocation. */
+uint64_t qadc_refine_relocations(const qadc_refine* r);
+/* Re-ranks, host arrays: queries [nq][dim], keys [nq][r_in], counts [nq] or NULL (every list is full), values [nq][r_in] or NULL ->
+ * out_keys [nq][R], out_dist [nq][R], out_sizes [nq], *missing_out (may be NULL) = the missing entries of all queries.
+ * 1 <= r_in <= QADC_REFINE_MAX_IN, 1 <= R (R > r_in is legal), nq = 0 is a no-op.  QADC_E_ARG before the device is touched: r NULL,
+ * a bad r_in or R, a required array NULL, a counts[q] outside [0, r_in]. */
+int qadc_refine_rerank(qadc_refine* r, int nq, const float* queries, int r_in, const uint32_t* keys, const int32_t* counts,
+                       const float* values, int R, uint32_t* out_keys, float* out_dist, int32_t* out_sizes, uint64_t* missing_out);
+/* The same with every array in device memory of the store's device (see qadc_refine_add_device), inputs complete before the call;
+ * missing_out stays a host pointer.  A d_counts[q] outside [0, r_in] is clamped to it.  Nothing but the missing count crosses the bus. */
+int qadc_refine_rerank_device(qadc_refine* r, int nq, const float* d_queries, int r_in, const uint32_t* d_keys, const int32_t* d_counts,
+                              const float* d_values, int R, uint32_t* d_out_keys, float* d_out_dist, int32_t* d_out_sizes,
+                              uint64_t* missing_out);
+
 #ifdef __cplusplus
 }
 #endif

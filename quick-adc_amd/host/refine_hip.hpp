@@ -1,0 +1,88 @@
+// refine_store_hip — C++14 RAII mirror of the refine store (qadc_refine_* in include/qadc.h): the original
+// vectors in device memory, dense over the keys [lo, lo + rows), and rerank(), which reorders candidate keys by their exact squared
+// L2 distance to them.  search_refined() composes it with adc_search_engine_hip (host/adc_search_hip.hpp): the engine's search with
+// R = the engine's r as r_in, then the re-ranking of the heaps' keys, the FLT_MAX sentinels left out.  The definition both are held
+// to is host/refine.hpp.
+#pragma once
+#include <cstdint>
+#include <cstdlib>
+#include <iostream>
+#include <vector>
+
+#include "../../include/qadc.h"
+#include "adc_search_hip.hpp"
+
+namespace qadc {
+
+struct refine_result {
+    int r = 0;                            // slots per query
+    std::vector<std::uint32_t> keys;      // [nq][r], ascending by (distance, key); behind sizes[q]: 0xFFFFFFFF
+    std::vector<float> dist;              // [nq][r]; behind sizes[q]: +inf
+    std::vector<std::int32_t> sizes;      // [nq]
+    std::uint64_t missing = 0;            // candidates whose key the store does not hold
+};
+
+struct refine_store_hip {
+    qadc_refine* store = nullptr;
+    int dim;
+
+    refine_store_hip(int dim_, int dtype = QADC_REFINE_F32, int device = 0) : dim(dim_) {
+        if (qadc_refine_create(&store, dim_, dtype, device) != QADC_OK) die("Cannot create the refine store");
+    }
+    refine_store_hip(const refine_store_hip&) = delete;
+    refine_store_hip& operator=(const refine_store_hip&) = delete;
+    ~refine_store_hip() { qadc_refine_destroy(store); }
+
+    static void die(const char* what) {
+        std::cerr << what << ": " << qadc_last_error() << std::endl;
+        std::exit(1);
+    }
+
+    void reserve(std::uint64_t rows) {
+        if (qadc_refine_reserve(store, rows) != QADC_OK) die("reserve");
+    }
+
+    // vectors [count][dim] become the rows of the keys first_key .. first_key + count - 1 (the first add fixes lo)
+    void add(const float* vectors, std::uint64_t count, std::uint32_t first_key) {
+        if (qadc_refine_add(store, vectors, count, first_key) != QADC_OK) die("add");
+    }
+
+    std::uint64_t rows() const {
+        std::uint64_t n = 0;
+        qadc_refine_info(store, nullptr, nullptr, nullptr, &n, nullptr);
+        return n;
+    }
+
+    // queries [nq][dim], keys [nq][r_in], counts [nq] or null, values [nq][r_in] or null -> the first r of every query's candidates
+    refine_result rerank(int nq, const float* queries, int r_in, const std::uint32_t* keys, const std::int32_t* counts, const float* values,
+                         int r) {
+        refine_result out;
+        out.r = r;
+        out.keys.resize((std::size_t)nq * r);
+        out.dist.resize((std::size_t)nq * r);
+        out.sizes.resize(nq);
+        if (qadc_refine_rerank(store, nq, queries, r_in, keys, counts, values, r, out.keys.data(), out.dist.data(), out.sizes.data(),
+                               &out.missing) != QADC_OK)
+            die("rerank");
+        return out;
+    }
+};
+
+// The engine's search of nq queries with heaps of e.r entries, then their keys re-ranked against `store`: the first r by (exact
+// distance, key).  cand_keys / cand_vals (may be null) receive the heaps' arrays [nq][e.r] the re-ranking consumed.
+template <typename Db>
+inline refine_result search_refined(adc_search_engine_hip<Db>& e, refine_store_hip& store, int nq, const float* queries, int r,
+                                    std::vector<std::uint32_t>* cand_keys = nullptr, std::vector<float>* cand_vals = nullptr) {
+    std::vector<std::uint32_t> keys((std::size_t)nq * e.r);
+    std::vector<float> vals((std::size_t)nq * e.r);
+    std::vector<std::int32_t> sizes(nq), assign((std::size_t)nq * e.ma);
+    if (qadc_adc_search(e.index, nq, queries, e.ma, e.r, e.table_form, e.sum_mode, keys.data(), vals.data(), sizes.data(), assign.data()) !=
+        QADC_OK)
+        adc_search_engine_hip<Db>::die("search");
+    refine_result out = store.rerank(nq, queries, e.r, keys.data(), nullptr, vals.data(), r);
+    if (cand_keys) cand_keys->swap(keys);
+    if (cand_vals) cand_vals->swap(vals);
+    return out;
+}
+
+}  // namespace qadc

@@ -50,6 +50,8 @@ SYMBOLS = [
     "qadc_pq_train_host", "qadc_pq_train_device",
     "qadc_pq_train16_host", "qadc_pq_train16_device", "qadc_pq_update16_host",
     "qadc_adc_filter_create", "qadc_adc_filter_create_device", "qadc_adc_filter_info", "qadc_adc_filter_destroy", "qadc_adc_index_set_filter",
+    "qadc_refine_create", "qadc_refine_destroy", "qadc_refine_add", "qadc_refine_add_device", "qadc_refine_reserve", "qadc_refine_info",
+    "qadc_refine_relocations", "qadc_refine_rerank", "qadc_refine_rerank_device",
 ]
 
 
@@ -244,6 +246,17 @@ def lib():
         L.qadc_adc_filter_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), u32p, u32p, u64p]
         L.qadc_adc_filter_destroy.argtypes = [C.c_void_p]
         L.qadc_adc_index_set_filter.argtypes = [C.c_void_p, C.c_void_p]
+        L.qadc_refine_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
+        L.qadc_refine_destroy.argtypes = [C.c_void_p]
+        L.qadc_refine_add.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32]
+        L.qadc_refine_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+        L.qadc_refine_reserve.argtypes = [C.c_void_p, C.c_uint64]
+        L.qadc_refine_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), u32p, u64p, u64p]
+        L.qadc_refine_relocations.argtypes = [C.c_void_p]
+        L.qadc_refine_relocations.restype = C.c_uint64
+        L.qadc_refine_rerank.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, u32p, i32p, f32p, C.c_int, u32p, f32p, i32p, u64p]
+        L.qadc_refine_rerank_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, u64p]
         _lib = L
     return _lib
 
@@ -1037,6 +1050,14 @@ class Index:
         return dict(heaps=self._heaps(nq, R, keys, vals, sizes), status=status, assign=assign, keys=keys,
                     values=vals, sizes=sizes)
 
+    def search_refined(self, queries, ma, R, r_in, store):
+        """search(queries, ma, r_in), then the heaps' keys re-ranked by their exact L2 distance to the vectors of the Refine `store`
+        -> (keys [nq][R], dist [nq][R], sizes [nq], missing), ascending by (distance, key).  Only the sizes[q] entries a heap holds are
+        candidates; a (0, 127) sentinel left among them is key 0, judged by its true distance like any other, once."""
+        q = np.ascontiguousarray(queries, np.float32)
+        got = self.search(q, ma, r_in)
+        return store.rerank(q, got["keys"], R, counts=got["sizes"])
+
     def search_submit(self, slot, queries, ma, R):
         """Asynchronous (slot 0..3) form of search(): enqueue a batch, collect it later (overlaps the host replay of
         one batch with the GPU work of the next)."""
@@ -1497,6 +1518,20 @@ class AdcIndex:
                                      _p(sizes, i32p), _p(assign, i32p)))
         return keys, vals, sizes, assign
 
+    def search_refined(self, queries, ma, R, r_in, store, table_form=2, sum_mode=1):
+        """search(queries, ma, r_in), then the heaps' keys re-ranked by their exact L2 distance to the vectors of the Refine `store`
+        -> (keys [nq][R], dist [nq][R], sizes [nq], missing), ascending by (distance, key).  The heaps' FLT_MAX sentinels are no
+        candidates; a filter set on the index holds for the refined keys, which are a subset of the heaps'."""
+        q = self._queries(queries)
+        keys, vals, _, _ = self.search(q, ma, r_in, table_form, sum_mode)
+        return store.rerank(q, keys, R, values=vals)
+
+    def search_refined_device(self, queries, ma, R, r_in, store, table_form=2, sum_mode=1):
+        """search_device, then store.rerank_device on its tensors: queries in device memory in, (keys int32 [nq][R] carrying the
+        uint32 bits, dist float32 [nq][R], sizes int32 [nq]) in device memory out, and the missing count; nothing else crosses the bus."""
+        keys, vals, _ = self.search_device(queries, ma, r_in, table_form, sum_mode)
+        return store.rerank_device(queries, keys, R, values=vals)
+
     def search_candidates(self, queries, ma, R, table_form=2, sum_mode=1):
         """-> (keys, vals, offsets [nq+1], assign [nq][ma]): the ordered candidate stream, as query_scan_candidates returns it"""
         q = self._queries(queries)
@@ -1571,3 +1606,149 @@ class AdcIndex:
         _check(lib().qadc_adc_query_scan_device(self._h, nq, ma, _p(assign, i32p), t.data_ptr(), R, sum_mode, keys.data_ptr(),
                                                 vals.data_ptr(), sizes.data_ptr()))
         return keys, vals, sizes
+
+
+QADC_REFINE_F32, QADC_REFINE_F16, QADC_REFINE_MAX_IN = 0, 1, 8192   # include/qadc.h
+_REFINE_DTYPES = {"f32": QADC_REFINE_F32, "f16": QADC_REFINE_F16}
+
+
+class Refine:
+    """The original vectors in device memory, for exact re-ranking (qadc_refine_*): dense over the keys
+    [lo, lo + rows), row r the vector of key lo + r, kept as float32 ("f32") or float16 ("f16").  rerank() reorders candidate keys —
+    a search's, with a larger R than wanted — by their exact squared L2 distance; AdcIndex.search_refined, .search_refined_device
+    and Index.search_refined compose the two."""
+
+    def __init__(self, dim, dtype="f32", device=0):
+        if dtype not in _REFINE_DTYPES:
+            raise ValueError('dtype is "f32" or "f16", not %r' % (dtype,))
+        self.dim, self.dtype, self.device = int(dim), dtype, device
+        self._h = C.c_void_p()
+        _check(lib().qadc_refine_create(C.byref(self._h), int(dim), _REFINE_DTYPES[dtype], device))
+
+    @classmethod
+    def create_raw(cls, dim, dtype, device=0):
+        """The C call as it is (dtype: an int)."""
+        self = cls.__new__(cls)
+        self.dim, self.dtype, self.device = dim, dtype, device
+        self._h = C.c_void_p()
+        _check(lib().qadc_refine_create(C.byref(self._h), dim, dtype, device))
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().qadc_refine_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _first_key(self, first_key):
+        if first_key is not None:
+            return int(first_key)
+        i = self.info()
+        return i["lo"] + i["rows"]                                         # continue; 0 on an empty store
+
+    def add(self, vectors, first_key=None):
+        """vectors [n][dim] become the rows of the keys first_key .. first_key + n - 1; None continues the store (0 on an empty one)"""
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.dim:
+            raise QadcError("vectors has shape %s, expected [n][%d]" % (v.shape, self.dim))
+        _check(lib().qadc_refine_add(self._h, _p(v, f32p), v.shape[0], self._first_key(first_key)))
+
+    def add_raw(self, vectors, count, first_key):
+        """The C call as it is (vectors: a float32 array or None)."""
+        _check(lib().qadc_refine_add(self._h, _p(vectors, f32p), count, first_key))
+
+    def add_device(self, vectors, first_key=None):
+        """the same from a contiguous float32 torch tensor [n][dim] on the store's device, read where it lies"""
+        if getattr(vectors, "ndim", 0) != 2:
+            raise TypeError("vectors must be a 2-d torch.Tensor")
+        t = self._tensor(vectors, "float32", (int(vectors.shape[0]), self.dim), "vectors")
+        self._sync()
+        _check(lib().qadc_refine_add_device(self._h, t.data_ptr(), int(t.shape[0]), self._first_key(first_key)))
+
+    def reserve(self, rows):
+        """room for `rows` rows in all: the adds up to there relocate nothing"""
+        _check(lib().qadc_refine_reserve(self._h, int(rows)))
+
+    def info(self):
+        """-> dict(dim, dtype "f32" | "f16", lo, rows, bytes: the allocation's)"""
+        dim, dtype, lo, rows, nbytes = C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().qadc_refine_info(self._h, C.byref(dim), C.byref(dtype), C.byref(lo), C.byref(rows), C.byref(nbytes)))
+        return dict(dim=dim.value, dtype="f16" if dtype.value == QADC_REFINE_F16 else "f32", lo=int(lo.value), rows=int(rows.value),
+                    bytes=int(nbytes.value))
+
+    def relocations(self):
+        """adds that moved the rows held to grow the allocation"""
+        return int(lib().qadc_refine_relocations(self._h))
+
+    def rerank(self, queries, keys, R, counts=None, values=None):
+        """queries [nq][dim], keys uint32 [nq][r_in], counts int32 [nq] or None, values float32 [nq][r_in] or None (FLT_MAX marks an
+        entry that is no candidate) -> (keys uint32 [nq][R], dist float32 [nq][R], sizes int32 [nq], missing): per query the first R
+        of its candidates by (exact squared L2 distance, key), every key once; behind sizes[q]: key 0xFFFFFFFF, distance +inf;
+        missing = the candidates whose key the store does not hold."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise QadcError("queries has shape %s, expected [nq][%d]" % (q.shape, self.dim))
+        nq = q.shape[0]
+        k = np.ascontiguousarray(keys, np.uint32).reshape(nq, -1)
+        c = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(nq)
+        v = None if values is None else np.ascontiguousarray(values, np.float32).reshape(k.shape)
+        return self.rerank_raw(nq, q, k.shape[1], k, c, v, int(R))
+
+    def rerank_raw(self, nq, queries, r_in, keys, counts, values, R, outputs=True):
+        """The C call as it is (arrays of the right dtype, or None)."""
+        ok = np.zeros((max(nq, 0), max(R, 0)), np.uint32) if outputs else None
+        od = np.zeros((max(nq, 0), max(R, 0)), np.float32) if outputs else None
+        osz = np.zeros(max(nq, 0), np.int32) if outputs else None
+        missing = C.c_uint64(0)
+        _check(lib().qadc_refine_rerank(self._h, nq, _p(queries, f32p), r_in, _p(keys, u32p), _p(counts, i32p), _p(values, f32p), R,
+                                        _p(ok, u32p), _p(od, f32p), _p(osz, i32p), C.byref(missing)))
+        return ok, od, osz, int(missing.value)
+
+    # ---- device memory in, device memory out: torch tensors by data_ptr() (torch is imported here only) ----
+    def _tensor(self, t, dtype, shape, what):
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, not %s" % (what, type(t).__name__))
+        if t.dtype != getattr(torch, dtype):
+            raise TypeError("%s must be %s, not %s" % (what, dtype, t.dtype))
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise QadcError("%s is on %s; the store is on device %d" % (what, t.device, self.device))
+        if not t.is_contiguous():
+            raise QadcError("%s must be contiguous" % what)
+        if tuple(t.shape) != tuple(shape):
+            raise QadcError("%s has shape %s, expected %s" % (what, tuple(t.shape), tuple(shape)))
+        return t
+
+    def _sync(self):
+        import torch
+        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()   # inputs are complete before the call
+
+    def rerank_device(self, queries, keys, R, counts=None, values=None):
+        """rerank() on torch tensors of the store's device: queries float32 [nq][dim], keys int32 [nq][r_in] carrying the uint32 bits
+        (as search_device returns them), counts int32 [nq] or None (clamped to [0, r_in]), values float32 [nq][r_in] or None ->
+        (keys int32 [nq][R], dist float32 [nq][R], sizes int32 [nq]) on that device, and missing (an int)."""
+        import torch
+        if getattr(queries, "ndim", 0) != 2 or getattr(keys, "ndim", 0) != 2:
+            raise TypeError("queries and keys must be 2-d torch.Tensors")
+        nq, r_in, R = int(queries.shape[0]), int(keys.shape[1]), int(R)
+        q = self._tensor(queries, "float32", (nq, self.dim), "queries")
+        k = self._tensor(keys, "int32", (nq, r_in), "keys")
+        c = None if counts is None else self._tensor(counts, "int32", (nq,), "counts")
+        v = None if values is None else self._tensor(values, "float32", (nq, r_in), "values")
+        dev = torch.device("cuda", self.device)
+        ok = torch.zeros((nq, max(R, 0)), dtype=torch.int32, device=dev)
+        od = torch.zeros((nq, max(R, 0)), dtype=torch.float32, device=dev)
+        osz = torch.zeros((nq,), dtype=torch.int32, device=dev)
+        self._sync()
+        missing = C.c_uint64(0)
+        _check(lib().qadc_refine_rerank_device(self._h, nq, q.data_ptr(), r_in, k.data_ptr(), None if c is None else c.data_ptr(),
+                                               None if v is None else v.data_ptr(), R, ok.data_ptr(), od.data_ptr(), osz.data_ptr(),
+                                               C.byref(missing)))
+        return ok, od, osz, int(missing.value)

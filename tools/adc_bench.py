@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter,refine] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,filter] [--iters N] [--out FILE]
 
@@ -41,6 +41,10 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             50 % of the keys, ALLOW of 1 % and 0.01 %, each checked against an index built without the dropped rows; (b) search() of
             1024 queries on the ivf_search database, unfiltered against EXCLUDE of 10 % of the keys, under both finishes; (c) the
             creation of a 10^6-key filter from host and from device memory.
+  refine    exact re-ranking (not in the default legs), on the ivf_search shape: recall@100 against exact
+            float L2 of search() alone and of search_refined_device with r_in = 400 and 1000 over a float and a half store; the time
+            of search_refined_device split into search_device and rerank_device; beside it a plain torch gather + (q - x)^2 sum +
+            topk on the same candidates, the only yardstick there is.
   --trained-codebooks   the add, remove and ivf_search legs (8 and 4 bits) learn their codebooks with train_pq (10 rounds on the
             residuals of the first 10^5 vectors) instead of sampling them; off by default, so that recorded figures stay comparable
   --bits 4   the float-ADC view of a 4-bit index instead (pyqadc.AdcIndex.view_of; legs lone,ivf_search):
@@ -165,7 +169,8 @@ def search_legs(legs, iters, res):
     part_of, codes = pyqadc.adc_encode(codebooks, vectors, coarse)
     res["adc_encode_1e6_s"] = time.perf_counter() - t0
     print("adc_encode of 10^6 128-d vectors (K = 256, 8x8), host to host: %.2f s" % res["adc_encode_1e6_s"], flush=True)
-    del vectors
+    if "refine" not in legs:
+        del vectors
     order = np.argsort(part_of, kind="stable")
     bounds = np.searchsorted(part_of[order], np.arange(K + 1))
     parts = [codes[order[bounds[k]:bounds[k + 1]]] for k in range(K)]
@@ -203,6 +208,9 @@ def search_legs(legs, iters, res):
         res["ivf_search_device_over_host_finish"] = sweep[str(nq)][1] / sweep[str(nq)][0]
         res["ivf_search_finish_sweep_ms_host_device"] = sweep
         res["ivf_search_host_finishes"] = int(idx.host_finishes())
+    if "refine" in legs:
+        refine_leg(idx, vectors, queries, ma, iters, res)
+        del vectors
     if "filter" in legs:   # (b): the same search() without a filter and with 10 % of the keys excluded, in turn, under both finishes
         S = rng.permutation(n)[:n // 10].astype(np.uint32)
         keep = ~np.isin(np.arange(n), S)
@@ -253,6 +261,64 @@ def search_legs(legs, iters, res):
         print("CPU scan_standard<uint8_t,8> over the same 24 partitions (%d codes), 1 thread, tables given (%s): %.1f us"
               % (res["lone_search_codes_probed"], "reference build" if po.have_ref_float() else "C restatement", med_c * 1e6), flush=True)
     idx.close()
+
+
+def refine_leg(idx, vectors, queries, ma, iters, res):
+    """search, then exact re-ranking on the GPU (pyqadc.Refine): what it buys in recall and what it costs"""
+    import torch
+    dev = torch.device("cuda", 0)
+    n, dim = vectors.shape
+    nq = len(queries)
+    tq = torch.from_numpy(queries).to(dev)
+    tx = torch.from_numpy(vectors).to(dev)
+    # ground truth: the R nearest by float L2 (||x||^2 - 2 q.x in chunks; the query's own norm does not change the order)
+    best_d = torch.full((nq, R), float("inf"), device=dev)
+    best_k = torch.zeros((nq, R), dtype=torch.int64, device=dev)
+    for first in range(0, n, 1 << 17):
+        x = tx[first:first + (1 << 17)]
+        d = (x * x).sum(1)[None, :] - 2.0 * (tq @ x.T)
+        cd, ck = torch.cat([best_d, d], 1).topk(R, dim=1, largest=False)
+        best_k = torch.cat([best_k, torch.arange(first, first + len(x), device=dev).expand(nq, -1)], 1).gather(1, ck)
+        best_d = cd
+    truth = best_k.cpu().numpy()
+
+    def recall(keys):
+        return float(np.mean([len(set(truth[q].tolist()) & set(np.asarray(keys[q]).tolist())) for q in range(nq)])) / R
+
+    plain = idx.search(queries, ma, R)
+    res["refine_recall_plain"] = recall(plain[0])
+    print("recall@%d of search() alone: %.4f" % (R, res["refine_recall_plain"]), flush=True)
+    for dtype in ("f32", "f16"):
+        st = pyqadc.Refine(dim, dtype)
+        st.add_device(tx)
+        for r_in in (400, 1000):
+            keys, dist, sizes, missing = idx.search_refined_device(tq, ma, R, r_in, st)
+            assert missing == 0
+            tag = "refine_%s_rin%d" % (dtype, r_in)
+            res[tag + "_recall"] = recall(keys.cpu().numpy().view(np.uint32))
+            ck, cv, _ = idx.search_device(tq, ma, r_in)
+            t_search, _ = timed(lambda: idx.search_device(tq, ma, r_in), max(5, iters))
+            t_rerank, _ = timed(lambda: st.rerank_device(tq, ck, R, values=cv), max(5, iters))
+            t_both, _ = timed(lambda: idx.search_refined_device(tq, ma, R, r_in, st), max(5, iters))
+            rows = tx if dtype == "f32" else tx.half()
+            ckl = ck.long() & 0xFFFFFFFF
+
+            def yardstick():
+                x = rows[ckl].float()                                       # gather [nq][r_in][dim]
+                d = ((tq[:, None, :] - x) ** 2).sum(-1)
+                d = torch.where(cv == 3.4028234663852886e38, torch.full_like(d, float("inf")), d)
+                out = d.topk(R, dim=1, largest=False)
+                torch.cuda.synchronize()
+                return out
+            t_torch, _ = timed(yardstick, max(5, iters))
+            res[tag + "_search_ms"], res[tag + "_rerank_ms"] = t_search * 1e3, t_rerank * 1e3
+            res[tag + "_search_refined_ms"], res[tag + "_torch_gather_topk_ms"] = t_both * 1e3, t_torch * 1e3
+            res[tag + "_gather_bytes"] = int(nq) * r_in * dim * (4 if dtype == "f32" else 2)
+            print("%s store, r_in %d: recall@%d %.4f; search_device %.3f ms + rerank_device %.3f ms (search_refined_device %.3f ms); torch "
+                  "gather + topk on the same candidates %.3f ms; %.0f MB gathered = %.2f TB/s in the rerank"
+                  % (dtype, r_in, R, res[tag + "_recall"], t_search * 1e3, t_rerank * 1e3, t_both * 1e3, t_torch * 1e3,
+                     res[tag + "_gather_bytes"] / 1e6, res[tag + "_gather_bytes"] / t_rerank / 1e12), flush=True)
+        st.close()
 
 
 def filter_leg(bits, iters, res, torch=None):
@@ -997,7 +1063,7 @@ def main():
                 f.write(line + "\n")
         return
     torch = None
-    if "ivf" in legs or "filter" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+    if "ivf" in legs or "filter" in legs or "refine" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:
             import torch
             torch.zeros(1, device="cuda")
@@ -1086,7 +1152,7 @@ def main():
             print("the same alternated with query_scan_device (tables and heaps stay in device memory): %.2f ms against %.2f ms"
                   % (med_d * 1e3, med_h * 1e3), flush=True)
         idx.close()
-    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs:
+    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "refine" in legs:
         search_legs(legs, a.iters, res)
     if "filter" in legs:
         filter_leg(8, a.iters, res, torch)

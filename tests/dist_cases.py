@@ -3,7 +3,8 @@ tests/test_gpu_dist_multiproc.py (the parent: starts the ranks, computes the uns
 
 Every case is one database + one query batch + the options that steer the native merge (qadc_dist_collect) through a
 particular branch: host-share replay with a second gather, lane-per-query device replay, a forced regrow of the gather
-block, the extra payload, R above the lane replay's limit, a query the device cannot order, a rank that fails locally.
+block, the extra payload, R above the lane replay's limit, a query the device cannot order, a rank that fails locally, shards
+scanned from the 16x4 code copies (the bucket form; the list and the cut sets are shared with tests/test_gpu_shard_forms.py).
 """
 import numpy as np
 
@@ -20,8 +21,44 @@ def start_size(n, keep):
     return min(n, max(1, int(np.float32(n) * np.float32(keep)))) if n else 0
 
 
+TILE = 16384                                                    # codes per tile of the 16x4 code copies (host/level_plan.hpp: kSplitTile)
+SHARD_FORMS_N = 12 * TILE + 37
+# What the ranks of "flat_forms" set before add_partition_shard and finalize (dist_worker.build_index): one query per pass, levels
+# [0, 16 Ki), [16 Ki, 64 Ki), [64 Ki, ...) as streaming launches, every 16x4 code copy with threshold 1, blocks of one tile
+SHARD_FORMS = dict(options=dict(share_variant=0, mq=0, front_run_max=0, wgq=0, head_level=0, small_run=1, level_base=TILE),
+                   split=(1, 1), split6=(1,), split5=(1,), split_nib=(1, 0, 9), split_bkt=(1, TILE, 0, 1, 0, 1e6))
+
+
+def shard_forms_cuts(n=SHARD_FORMS_N):
+    """{name: [(first_pos, local_n) per rank]}: the cut sets of tests/test_gpu_shard_forms.py."""
+    T = TILE
+    bounds = {"tile-aligned": [0, 6 * T, n], "three-ranks": [0, 4 * T + 16, 8 * T + 48, n],
+              "first-pos-2-mod-16": [0, 6 * T + 18, n]}
+    cuts = {k: [(a, b - a) for a, b in zip(v[:-1], v[1:])] for k, v in bounds.items()}
+    cuts["shard-ranges-2"] = shard_ranges(n, 2)
+    cuts["four-ranks"] = [(0, 12 * T), (12 * T, 32), (12 * T + 32, n - 12 * T - 32), (0, 0)]
+    return cuts
+
+
+def shard_forms_list():
+    """-> (codes [12 * 16384 + 37, 8], tables [3, 1, 256]): one flat 16x4 list of 1024 distinct keys (code bytes 0 and 1: buckets of some
+    16 codes per tile) in which the code with the smallest sum query 0's table allows is the partition's last code and, for
+    every cut set of shard_forms_cuts, rank 0's last local code and rank 1's first."""
+    rng = np.random.default_rng(4301)
+    tables = float_tables(rng, 3, 1, 16)
+    codes = rand_codes(rng, SHARD_FORMS_N, 16)
+    codes[:, 1] &= 3
+    b = tables[0, 0].reshape(16, 16).argmin(axis=1).astype(np.uint8)
+    best = b[0::2] | (b[1::2] << 4)
+    codes[-1] = best
+    for cut in shard_forms_cuts().values():
+        first1 = cut[1][0]
+        codes[first1 - 1] = codes[first1] = best
+    return codes, tables
+
+
 def build_case(name):
-    """-> dict(M, parts, labels, keep, R, assign, tables, options, index_options, placement, extra_n)."""
+    """-> dict(M, parts, labels, keep, R, assign, tables, options, index_options, placement, extra_n[, forms])."""
     c = dict(name=name, keep=0.01, R=100, labels=None, options={}, index_options={}, placement="range", extra_n=0,
              slots=(0,))
     if name == "flat32":
@@ -34,6 +71,15 @@ def build_case(name):
         c["extra_n"] = 37
         c["slots"] = (0, 1)
         c["repeat"] = 2                                    # the second pass fits the regrown block: merges enqueued with the batches
+    elif name == "flat_forms":
+        # the list of tests/test_gpu_shard_forms.py in real processes: every rank scans its range in the bucket form (and
+        # whatever the level cuts leave to the other forms) under the unmodified merge, two batches in flight
+        rng = np.random.default_rng(507)
+        codes, t3 = shard_forms_list()
+        c.update(M=16, parts=[codes], assign=np.zeros((32, 1), np.int32), keep=0.05)
+        c["tables"] = np.ascontiguousarray(np.concatenate([t3, float_tables(rng, 29, 1, 16)]))
+        c["forms"] = SHARD_FORMS
+        c["slots"] = (0, 1)
     elif name in ("ivf_lanes", "ivf_whole"):
         # >= 256 queries: the gathered streams are replayed on the GPU, one lane per query.  Ragged labelled partitions,
         # an empty one, some too small for every rank to hold a piece, tie-heavy tables.
@@ -113,7 +159,7 @@ def build_case(name):
     return c
 
 
-CASES = ["flat32", "ivf_lanes", "ivf_whole", "ivf_search", "ivf_search_whole", "ivf_search_regrow", "ivf_search_fallback",
+CASES = ["flat32", "flat_forms", "ivf_lanes", "ivf_whole", "ivf_search", "ivf_search_whole", "ivf_search_regrow", "ivf_search_fallback",
          "ivf_search_onerank", "ivf_search_fewstarts", "big_r", "unordered", "inject"]
 
 

@@ -25,6 +25,15 @@ def build_index(case, rank, world):
     idx = pyqadc.Index(M, 0)
     sizes = [p.shape[0] for p in case["parts"]]
     owner = pyqadc.place_partitions(sizes, world) if case["placement"] == "whole" else None
+    forms = case.get("forms")
+    if forms:                                              # the code copies are built at finalize: their thresholds come first
+        for k, v in forms["options"].items():
+            idx.set_option(k, v)
+        idx.set_split(*forms["split"])
+        idx.set_split6(*forms["split6"])
+        idx.set_split5(*forms["split5"])
+        idx.set_split_nib(*forms["split_nib"])
+        idx.set_split_bkt(*forms["split_bkt"])
     for p, codes in enumerate(case["parts"]):
         n = sizes[p]
         lab = None if case["labels"] is None else case["labels"][p]
@@ -107,6 +116,8 @@ def run_case(name, rank, world, transport):
     out["group_launches"] = np.array([prof["group_launches"]])
     out["host_sorted_queries"] = np.array([prof["host_sorted_queries"]])
     out["dist_async_collects"] = np.array([prof["dist_async_collects"]])
+    out["bkt_launches"] = np.array([prof["bkt_launches"]])
+    out["split_launches"] = np.array([prof["split_launches"]])
     idx.close()
     return out
 

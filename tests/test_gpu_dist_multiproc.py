@@ -19,7 +19,7 @@ import uuid
 import numpy as np
 import pytest
 
-from dist_cases import CASES, build_case, search_inputs
+from dist_cases import CASES, TILE, build_case, search_inputs, shard_ranges
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 WORKER = os.path.join(HERE, "dist_worker.py")
@@ -90,6 +90,11 @@ def test_native_merge_with_several_processes_on_one_gpu(po, world, tmp_path, sca
             assert all(int(res[r]["flat32.regrows"][0]) >= 1 for r in range(world))          # the 64-entry block was regrown everywhere
             # (32 queries < dist_device_nq: merged at collect time, the ranks replaying shares on the host)
             assert all(int(res[r]["flat32.dist_async_collects"][0]) == 0 for r in range(world))
+        if name == "flat_forms":                           # every rank of two tiles and more scanned its range in the bucket form
+            n = case["parts"][0].shape[0]
+            for r, (_, ln) in enumerate(shard_ranges(n, world)):
+                bkt, split = int(res[r]["flat_forms.bkt_launches"][0]), int(res[r]["flat_forms.split_launches"][0])
+                assert ln < 2 * TILE or 1 <= bkt <= split, (r, ln, bkt, split)
         if name in ("ivf_lanes", "big_r"):                 # second pass: merges enqueued with the batch, level path and query kernel alike
             assert all(int(res[r]["%s.dist_async_collects" % name][0]) >= 1 for r in range(world)), \
                 (name, [int(res[r]["%s.dist_async_collects" % name][0]) for r in range(world)])

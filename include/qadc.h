@@ -549,6 +549,17 @@ typedef struct qadc_profile {
     uint64_t bkt5_launches;         /* ... for 5, */
     uint64_t bkt6_launches;         /* ... for 6 */
     uint64_t bkt7_launches;         /* ... and for 7: the four add up to bkt_launches */
+    uint64_t bktw_copy_bytes;       /* device bytes of the bucket copies' wide octaves (tiles and side arrays; kept across resets; not in bkt_copy_bytes) */
+    uint64_t bktw_copy_slots;       /* slots of those octaves (kept across resets; not in bkt_copy_slots) */
+    uint64_t bktw_copy_fallback;    /* octaves that padding inflated beyond bkt_wide_max_pad x their codes: stored as narrow blocks (kept across resets) */
+    uint64_t bktw_launches;         /* of split_launches: launches of the wide form (qadc_index_set_split_bkt_wide); not in bkt_launches */
+    uint64_t bktw_codes;            /* of split_codes: codes their runs cover */
+    uint64_t bktw_slots;            /* slots they streamed */
+    uint64_t bktw_survivors;        /* (slot, query) pairs of those launches whose partial sum was below the bound less the slack */
+    uint64_t bktw3_launches;        /* of bktw_launches: those that paid for 3 of sub-quantizers 5-15 (host/level_plan.hpp: bktw_planes), */
+    uint64_t bktw4_launches;        /* ... for 4, */
+    uint64_t bktw5_launches;        /* ... for 5 */
+    uint64_t bktw6_launches;        /* ... and for 6: the four add up to bktw_launches */
 } qadc_profile;
 
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);
@@ -601,6 +612,31 @@ int qadc_index_set_split_nib(qadc_index* idx, uint64_t min_run, uint64_t min_run
  * Defaults: profiles/r11_bkt_ab.txt. */
 int qadc_index_set_split_bkt(qadc_index* idx, uint64_t bkt_min_run, uint64_t bkt_block, uint64_t min_run6, uint64_t min_run5,
                              uint64_t min_run4, double bkt_max_pad);
+
+/* Wide blocks of the bucket copy: positions from wide_block = W on (0 = none; a power of two, a multiple
+ * of bkt_block; default 2^27) are stored in octave blocks [W 2^j, W 2^(j+1)), the last clipped at the partition's end, grouped by
+ * the codes' first 20 bits, so that sub-quantizers 0-4 cost 3 bytes per 16 codes; 17.69 bytes per slot.  An octave whose
+ * padded slots exceed wide_max_pad x its codes (0 = keep; default 1.08) keeps narrow blocks; a range stored wide has no narrow
+ * blocks.  Level launches whose runs all have at least min_run codes, start on an octave, end on one or at the partition's end and
+ * cover wide octaves only stream 6 of the other 11 sub-quantizers, those of at least min_run5 / min_run4 / min_run3 codes 5 / 4 / 3
+ * (0 = never); preferred over the narrow form; no result changes.  The bucket form itself must be on (bkt_min_run != 0).
+ * wide_block and wide_max_pad must be set before qadc_index_finalize; the thresholds may change at any time.  A bkt_block raised above
+ * wide_block afterwards (qadc_index_set_split_bkt, or the env hooks) raises the octaves' start to bkt_block at finalize:
+ * qadc_index_bktw_info reports the W in use.
+ * QADC_BKT_WIDE_BLOCK / QADC_BKTW_MIN_RUN / QADC_BKTW5_MIN_RUN / QADC_BKTW4_MIN_RUN / QADC_BKTW3_MIN_RUN override the defaults at
+ * qadc_index_create (with QADC_TEST_HOOKS=1).  Defaults: profiles/r12_bktw_ab.txt. */
+int qadc_index_set_split_bkt_wide(qadc_index* idx, uint64_t wide_block, uint64_t min_run, uint64_t min_run5, uint64_t min_run4,
+                                  uint64_t min_run3, double wide_max_pad);
+
+/* The wide form's choice: out[16 t + 4 (NSP - 3) ..] = the deferred set among sub-quantizers 5-15 for NSP = 3, 4, 5, 6 paid
+ * planes as a 16-bit mask (low byte first), the slack c, 0.  A diagnostic. */
+int qadc_bktw_choice(int device_id, const int8_t* tables, int ntables, uint8_t* out);
+
+/* Diagnostics of a partition's wide octaves: W (0 = none), octaves and slots; and the copy itself: octave_off [octaves + 1]
+ * first slot of every octave (an octave without slots has narrow blocks), tiles [slots / 16384][93184] (11 nibble planes of
+ * 8 KiB, sub-quantizers 5-15; 1024 uint16 ids; 1024 bytes, sub-quantizer 4), side as in qadc_index_bkt_read; each may be null. */
+int qadc_index_bktw_info(qadc_index* idx, int part, uint64_t* wide_block, uint64_t* noctaves, uint64_t* slots);
+int qadc_index_bktw_read(qadc_index* idx, int part, uint64_t* octave_off, uint8_t* tiles, uint8_t* side);
 
 /* The bucket form's choice for ntables 16x4 int8 tables: out[16 t + 4 (NSP - 4) ..] = the deferred set among sub-quantizers
  * 4-15 for NSP = 4, 5, 6, 7 paid planes as a 16-bit mask (low byte first), the slack c, 0.  A diagnostic. */

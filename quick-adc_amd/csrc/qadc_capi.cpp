@@ -32,6 +32,9 @@ static_assert(kSurvNib8Off + sizeof(unsigned long long) <= 64, "inside the state
 // ... and the bucket form's
 constexpr size_t kSurvBktOff = 40;
 static_assert(kSurvBktOff + sizeof(unsigned long long) <= 64, "inside the state block's header");
+// ... and its wide form's
+constexpr size_t kSurvBktwOff = 48;
+static_assert(kSurvBktwOff + sizeof(unsigned long long) <= 64, "inside the state block's header");
 
 // What the stages of plan_and_launch hand on to each other: the layouts of the batch's upload and result blocks.
 struct Staged {
@@ -39,7 +42,7 @@ struct Staged {
     size_t in_bytes = 0, off_tables = 0, off_inj = 0, off_hassign = 0;   // upload block
     size_t state_bytes = 0, off_heaps = 0;
     bool dev_stream = false;       // the ordered streams (also) stay in device memory
-    bool any_split6 = false, any_split5 = false, any_nib = false, any_bkt = false;
+    bool any_split6 = false, any_split5 = false, any_nib = false, any_bkt = false, any_bktw = false;
 };
 
 // ---- upload: ONE block, ONE copy (enqueued by plan_and_launch: upload_and_wait) ----
@@ -106,15 +109,17 @@ int bind_state_and_result(qadc_index* idx, Slot& s, Staged& g) {
     HIPCHECK(s.d_qtables.ensure((size_t)nq * ma * idx->M * 16));
     // the 6-plane split form's deferred byte per table, computed where the int8 tables become known (launch_front)
     for (auto& ll : s.launches) {
+        g.any_bktw = g.any_bktw || ll.bktw;
         g.any_bkt = g.any_bkt || ll.bkt;
         g.any_nib = g.any_nib || ll.nib;
-        g.any_split5 = g.any_split5 || (ll.split5 && !ll.nib && !ll.bkt);
-        g.any_split6 = g.any_split6 || (ll.split6 && !ll.split5 && !ll.nib && !ll.bkt);
+        g.any_split5 = g.any_split5 || (ll.split5 && !ll.nib && !ll.bkt && !ll.bktw);
+        g.any_split6 = g.any_split6 || (ll.split6 && !ll.split5 && !ll.nib && !ll.bkt && !ll.bktw);
     }
     if (g.any_split6) HIPCHECK(s.d_plane_sel.ensure((size_t)nq * ma));
     if (g.any_split5) HIPCHECK(s.d_plane_sel5.ensure(2 * (size_t)nq * ma));
     if (g.any_nib) HIPCHECK(s.d_nib_sel.ensure((size_t)kNibSelBytes * nq * ma));
     if (g.any_bkt) HIPCHECK(s.d_bkt_sel.ensure((size_t)kBktSelBytes * nq * ma));
+    if (g.any_bktw) HIPCHECK(s.d_bktw_sel.ensure((size_t)kBktwSelBytes * nq * ma));
     return QADC_OK;
 }
 
@@ -135,9 +140,10 @@ int launch_front(qadc_index* idx, Slot& s, const BatchPlan& plan, const Staged& 
     if (!s.float_path) {
         s.d_qt = s.front_sharded ? s.d_qtables.p                             // (a sharded-front batch redone here: the gathered tables)
                                  : reinterpret_cast<const int8_t*>(s.d_in.p + g.off_tables);     // caller's int8 tables, as uploaded
-        if (g.any_split6 || g.any_split5 || g.any_nib || g.any_bkt)
+        if (g.any_split6 || g.any_split5 || g.any_nib || g.any_bkt || g.any_bktw)
             launch_plane_choice(s.d_qt, nq * ma, g.any_split6 ? s.d_plane_sel.p : nullptr, st, g.any_split5 ? s.d_plane_sel5.p : nullptr,
-                                g.any_nib ? s.d_nib_sel.p : nullptr, g.any_bkt ? s.d_bkt_sel.p : nullptr);
+                                g.any_nib ? s.d_nib_sel.p : nullptr, g.any_bkt ? s.d_bkt_sel.p : nullptr,
+                                g.any_bktw ? s.d_bktw_sel.p : nullptr);
         if (idx->profile) { HIPCHECK(prof_event(s, st)); HIPCHECK(prof_event(s, st)); }
         return QADC_OK;
     }
@@ -199,12 +205,16 @@ int launch_front(qadc_index* idx, Slot& s, const BatchPlan& plan, const Staged& 
     }
     launch_select_kth(d_sel, fc_stride, s.d_fc_init, nq, (uint32_t)s.R, s.d_qs, 4, d_ft, s.d_qtables.p, tda,
                       idx->quant_mode, st, nullptr, nullptr, nullptr, 0, g.any_split6 ? s.d_plane_sel.p : nullptr,
-                      g.any_split5 ? s.d_plane_sel5.p : nullptr, g.any_nib ? s.d_nib_sel.p : nullptr, g.any_bkt ? s.d_bkt_sel.p : nullptr);
+                      g.any_split5 ? s.d_plane_sel5.p : nullptr, g.any_nib ? s.d_nib_sel.p : nullptr, g.any_bkt ? s.d_bkt_sel.p : nullptr,
+                      g.any_bktw ? s.d_bktw_sel.p : nullptr);
     if (idx->profile) HIPCHECK(prof_event(s, st));
     return QADC_OK;
 }
 
-void launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, hipStream_t str) {
+int launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, hipStream_t str) {
+    // a wide bucket launch has no other form to fall back to (its runs count slots of the wide copy): refuse it loudly
+    if (ll.bktw && !(idx->M == 16 && ll.split && !ll.shared && !ll.small && !ll.mq && ll.bktw >= 3 && ll.bktw <= 6 && s.d_bktw_sel.p))
+        return fail(QADC_E_STATE, "the planner emitted a wide bucket launch whose preconditions do not hold");
     if (ll.small)
         launch_scan_i8_small(idx->M, s.d_items + ll.first, ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p,
                              s.cap_q, (uint32_t)s.R, str);
@@ -217,13 +227,16 @@ void launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, 
                        ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str,
                        ll.split6 && !ll.split5 ? s.d_plane_sel.p : nullptr,
                        !idx->profile  ? nullptr
+                       : ll.bktw      ? reinterpret_cast<unsigned long long*>(s.d_state.p + kSurvBktwOff)
                        : ll.bkt       ? reinterpret_cast<unsigned long long*>(s.d_state.p + kSurvBktOff)
                        : ll.nib       ? reinterpret_cast<unsigned long long*>(s.d_state.p + (ll.nib == 8 ? kSurvNib8Off : kSurvNibOff))
                        : ll.split5    ? reinterpret_cast<unsigned long long*>(s.d_state.p + kSurv5Off)
                        : ll.split6    ? reinterpret_cast<unsigned long long*>(s.d_hdr->pad)
                                       : nullptr,
                        ll.split5 ? s.d_plane_sel5.p : nullptr, ll.nib ? s.d_nib_sel.p : nullptr, ll.nib,
-                       ll.bkt ? s.d_bkt_sel.p : nullptr, ll.bkt);   // (the bucket form first, then the nibble form)
+                       ll.bktw ? s.d_bktw_sel.p : ll.bkt ? s.d_bkt_sel.p : nullptr, ll.bktw ? ll.bktw : ll.bkt,
+                       ll.bktw ? 5 : 4);                           // (the wide form first, then the bucket form, then the nibble form)
+    return QADC_OK;
 }
 
 int launch_head(qadc_index* idx, Slot& s, const Staged& g, hipStream_t str) {
@@ -280,7 +293,7 @@ int launch_levels(qadc_index* idx, Slot& s, const Staged& g, hipStream_t st) {
     for (size_t li = 0; li < n_early; ++li) {
         s.launches[li].early = true;
         s.launches[li].ev = -1;
-        launch_level(idx, s, s.launches[li], variant, st);
+        if (int rc = launch_level(idx, s, s.launches[li], variant, st)) return rc;
     }
     if (st != main_stream) {
         if (!s.ev_front) HIPCHECK(hipEventCreateWithFlags(&s.ev_front, hipEventDisableTiming));
@@ -299,7 +312,7 @@ int launch_levels(qadc_index* idx, Slot& s, const Staged& g, hipStream_t st) {
         const bool group_end = timed && (li + 1 == s.launches.size() || s.launches[li + 1].small);
         ll.ev = -1;
         if (group_start) { ll.ev = (int)s.prof_used; HIPCHECK(prof_event(s, st)); }
-        launch_level(idx, s, ll, variant, st);
+        if (int rc = launch_level(idx, s, ll, variant, st)) return rc;
         if (group_end) HIPCHECK(prof_event(s, st));
     }
     return QADC_OK;
@@ -400,7 +413,8 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
     const LevelOptions opt{idx->M, idx->level_base, idx->level_growth, idx->head_level, idx->small_run, idx->wgs_per_item,
                            idx->share_variant, idx->mq, idx->prescan_sample, idx->split_min_run, idx->split6_min_run,
                            idx->split5_min_run, idx->nib_min_run, idx->nib8_min_run, idx->nib_ns,
-                           idx->bkt_min_run, idx->bkt6_min_run, idx->bkt5_min_run, idx->bkt4_min_run};
+                           idx->bkt_min_run, idx->bkt6_min_run, idx->bkt5_min_run, idx->bkt4_min_run,
+                           idx->bktw_min_run, idx->bktw5_min_run, idx->bktw4_min_run, idx->bktw3_min_run};
     const LevelBatch batch{s.nq, s.ma, s.assign.data(), s.R, s.mode, s.float_path, s.full_prescan, s.pre_slice, s.pre_nslices, s.inj_n};
     BatchPlan plan = plan_levels(idx->parts.data(), idx->parts.size(), opt, batch);      // (host/level_plan.hpp: no GPU calls)
     if (!plan.refused.empty()) return fail(QADC_E_ARG, plan.refused);
@@ -729,7 +743,7 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[0], s.prof_ev[1]));
             if (s.float_path) idx->prof.start_ms += ms;
         }
-        bool count_survivors = false, count_survivors5 = false, count_nib = false, count_nib8 = false, count_bkt = false;
+        bool count_survivors = false, count_survivors5 = false, count_nib = false, count_nib8 = false, count_bkt = false, count_bktw = false;
         for (auto& ll : s.launches) {
             if (ll.small || ll.early) {                      // counted, not timed (see plan_and_launch)
                 idx->prof.small_launches++;
@@ -741,8 +755,8 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             idx->prof.mq_launches += ll.mq ? 1 : 0;
             idx->prof.split_launches += ll.split ? 1 : 0;
             idx->prof.split_codes += ll.split ? ll.codes : 0;
-            const bool ran5 = ll.split5 && !ll.nib && !ll.bkt;   // (the launcher prefers the bucket form over the nibble form over 5 planes over 6)
-            const bool ran6 = ll.split6 && !ll.split5 && !ll.nib && !ll.bkt;
+            const bool ran5 = ll.split5 && !ll.nib && !ll.bkt && !ll.bktw;   // (the launcher prefers the bucket forms over the nibble form over 5 planes over 6)
+            const bool ran6 = ll.split6 && !ll.split5 && !ll.nib && !ll.bkt && !ll.bktw;
             idx->prof.split6_launches += ran6 ? 1 : 0;
             idx->prof.split6_codes += ran6 ? ll.codes : 0;
             idx->prof.split5_launches += ran5 ? 1 : 0;
@@ -763,6 +777,14 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             idx->prof.bkt_codes += ll.bkt ? ll.codes : 0;
             idx->prof.bkt_slots += ll.bkt ? ll.slots : 0;
             count_bkt = count_bkt || ll.bkt;
+            idx->prof.bktw_launches += ll.bktw ? 1 : 0;
+            idx->prof.bktw3_launches += ll.bktw == 3 ? 1 : 0;
+            idx->prof.bktw4_launches += ll.bktw == 4 ? 1 : 0;
+            idx->prof.bktw5_launches += ll.bktw == 5 ? 1 : 0;
+            idx->prof.bktw6_launches += ll.bktw == 6 ? 1 : 0;
+            idx->prof.bktw_codes += ll.bktw ? ll.codes : 0;
+            idx->prof.bktw_slots += ll.bktw ? ll.slots : 0;
+            count_bktw = count_bktw || ll.bktw;
             idx->prof.pass_codes += ll.mq ? ll.codes / (uint64_t)ll.nitems * (uint64_t)((ll.nitems + 7) / 8) : ll.codes;
             if (ll.ev < 0 || (size_t)ll.ev + 1 >= s.prof_used) continue;   // not the first launch of its timed group
             HIPCHECK(hipEventElapsedTime(&ms, s.prof_ev[ll.ev], s.prof_ev[ll.ev + 1]));
@@ -792,6 +814,11 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             unsigned long long surv = 0;
             HIPCHECK(hipMemcpy(&surv, s.d_state.p + kSurvBktOff, sizeof(surv), hipMemcpyDeviceToHost));
             idx->prof.bkt_survivors += surv;
+        }
+        if (count_bktw) {
+            unsigned long long surv = 0;
+            HIPCHECK(hipMemcpy(&surv, s.d_state.p + kSurvBktwOff, sizeof(surv), hipMemcpyDeviceToHost));
+            idx->prof.bktw_survivors += surv;
         }
         if (s.float_path) idx->prof.start_codes += s.start_codes;
     }
@@ -1249,6 +1276,13 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
         if (const char* e = std::getenv("QADC_BKT6_MIN_RUN")) idx->bkt6_min_run = std::strtoull(e, nullptr, 10);
         if (const char* e = std::getenv("QADC_BKT5_MIN_RUN")) idx->bkt5_min_run = std::strtoull(e, nullptr, 10);
         if (const char* e = std::getenv("QADC_BKT4_MIN_RUN")) idx->bkt4_min_run = std::strtoull(e, nullptr, 10);
+        // its wide blocks: 0 = none; the thresholds of the wide form and of its 5-, 4- and 3-plane launches
+        if (const char* e = std::getenv("QADC_BKT_WIDE_BLOCK")) idx->bkt_wide_block = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_BKTW_MIN_RUN")) idx->bktw_min_run = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_BKTW5_MIN_RUN")) idx->bktw5_min_run = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_BKTW4_MIN_RUN")) idx->bktw4_min_run = std::strtoull(e, nullptr, 10);
+        if (const char* e = std::getenv("QADC_BKTW3_MIN_RUN")) idx->bktw3_min_run = std::strtoull(e, nullptr, 10);
+        if (idx->bkt_wide_block & (idx->bkt_wide_block - 1)) idx->bkt_wide_block = 0;     // (not a power of two: none)
     }
     if (int rc = attach_streams(idx)) {
         delete idx;
@@ -1279,6 +1313,8 @@ int qadc_index_destroy(qadc_index* idx) {
         if (p.d_nib) (void)hipFree(p.d_nib);
         if (p.d_bkt) (void)hipFree(p.d_bkt);
         if (p.d_bkt_side) (void)hipFree(p.d_bkt_side);
+        if (p.d_bktw) (void)hipFree(p.d_bktw);
+        if (p.d_bktw_side) (void)hipFree(p.d_bktw_side);
     }
     idx->arena.release();               // (the partitions with Part::arena, all at once)
     idx->feed.d_codebooks.release();
@@ -1292,7 +1328,7 @@ int qadc_index_destroy(qadc_index* idx) {
     for (Slot* sp : all_slots) {
         Slot& s = *sp;
         s.d_in.release(); s.h_in.release(); s.d_state.release(); s.h_result.release();
-        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_plane_sel5.release(); s.d_nib_sel.release(); s.d_bkt_sel.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
+        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_plane_sel5.release(); s.d_nib_sel.release(); s.d_bkt_sel.release(); s.d_bktw_sel.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
         s.h_cands.release(); s.d_stream.release(); s.d_qflags.release(); s.d_fvals.release(); s.d_qcands.release(); s.h_fetch.release();
         s.d_fblock.release(); s.d_fgathered.release(); s.d_front_all.release(); s.h_fmap.release();
         if (s.ev_fa) (void)hipEventDestroy(s.ev_fa);
@@ -1497,20 +1533,99 @@ int qadc_index_set_key_base(qadc_index* idx, int part, uint32_t key_base) {
 // The bucket copies of qadc_index_finalize (host/level_plan.hpp has the layout; launch_bkt_*: the kernels).  Per partition: the key
 // histogram and the buckets' first slots of every block, then (the blocks' slot counts known) the allocation, the scatter and the
 // padding / plane pass.  Borrowed codes get no copy, as with the byte-plane copy (which the partition must have).
+//   Wide octaves first (bkt_wide_block = W != 0 and the partition reaches beyond W): the 20-bit histogram of every octave
+// [W 2^j, W 2^(j+1)); an octave whose padded slots stay within bkt_wide_max_pad x its codes is stored wide, in an allocation of its
+// own.  Every narrow block inside a wide octave is left empty (W is a multiple of bkt_block, so a block lies inside one octave or
+// outside all); the others are built as before, octaves that fell back included (counted in bktw_copy_fallback).
 static int build_bkt_copies(qadc_index* idx) {
     idx->prof.bkt_copy_bytes = idx->prof.bkt_copy_failed = idx->prof.bkt_copy_padded_out = idx->prof.bkt_copy_slots = 0;
+    idx->prof.bktw_copy_bytes = idx->prof.bktw_copy_slots = idx->prof.bktw_copy_fallback = 0;
     for (auto& p : idx->parts) {
-        if (p.d_bkt || p.d_bkt_side) {
+        if (p.d_bkt || p.d_bkt_side || p.d_bktw || p.d_bktw_side) {
             HIPCHECK(hipDeviceSynchronize());
             if (p.d_bkt) HIPCHECK(hipFree(p.d_bkt));
             if (p.d_bkt_side) HIPCHECK(hipFree(p.d_bkt_side));
+            if (p.d_bktw) HIPCHECK(hipFree(p.d_bktw));
+            if (p.d_bktw_side) HIPCHECK(hipFree(p.d_bktw_side));
         }
-        p.d_bkt = p.d_bkt_side = nullptr;
+        p.d_bkt = p.d_bkt_side = p.d_bktw = p.d_bktw_side = nullptr;
         p.bkt_off.clear();
-        p.bkt_block = 0;
+        p.bktw_off.clear();
+        p.bkt_block = p.bktw_block = 0;
         if (idx->M != 16 || idx->bkt_min_run == 0 || p.n < idx->bkt_min_run || !p.d_split || !p.d_codes || !p.own) continue;
         const uint64_t block = idx->bkt_block;
         const size_t nblocks = (size_t)(((uint64_t)p.n + block - 1) / block);
+        // ---- wide octaves
+        // (both are powers of two: W is a multiple of block unless block is larger, e.g. raised after the wide setter's check or by the
+        // env hooks; the octaves then start at block, so that every narrow block still lies inside one octave or outside all)
+        const uint64_t W = idx->bkt_wide_block ? std::max<uint64_t>(idx->bkt_wide_block, block) : 0;
+        std::vector<uint64_t> woff;                              // [octaves + 1]
+        auto oct_lo = [&](size_t j) { return W << j; };
+        auto oct_n = [&](size_t j) { return (uint32_t)(std::min<uint64_t>(W << (j + 1), p.n) - (W << j)); };
+        size_t noct = 0;
+        if (W != 0 && W % block == 0 && (W & (W - 1)) == 0)
+            while (oct_lo(noct) < p.n) ++noct;
+        Scratch wtmp;
+        uint32_t *d_whist = nullptr, *d_woff = nullptr, *d_winfo = nullptr;
+        std::vector<uint32_t> winfo(2 * noct, 0);
+        if (noct) {
+            if (wtmp.alloc(&d_whist, noct * kBktwKeys * sizeof(uint32_t)) != hipSuccess ||
+                wtmp.alloc(&d_woff, noct * kBktwKeys * sizeof(uint32_t)) != hipSuccess ||
+                wtmp.alloc(&d_winfo, noct * 2 * sizeof(uint32_t)) != hipSuccess) {
+                (void)hipGetLastError();
+                idx->prof.bkt_copy_failed++;
+                noct = 0;
+            }
+        }
+        if (noct) {
+            HIPCHECK(hipMemsetAsync(d_whist, 0, noct * kBktwKeys * sizeof(uint32_t), idx->stream));
+            for (size_t j = 0; j < noct; ++j)
+                launch_bkt_hist_scan(p.d_codes + oct_lo(j) * 8, oct_n(j), d_whist + j * kBktwKeys, d_woff + j * kBktwKeys, d_winfo + 2 * j,
+                                     idx->stream, /*wide=*/true);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipMemcpyAsync(winfo.data(), d_winfo, winfo.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, idx->stream));
+            HIPCHECK(hipStreamSynchronize(idx->stream));
+            woff.assign(noct + 1, 0);
+            for (size_t j = 0; j < noct; ++j) {
+                const bool wide = (double)winfo[2 * j] <= idx->bkt_wide_max_pad * (double)oct_n(j);
+                if (!wide) idx->prof.bktw_copy_fallback++;
+                woff[j + 1] = woff[j] + (wide ? winfo[2 * j] : 0);
+            }
+            if (woff[noct] == 0) noct = 0;                       // no octave is stored wide
+        }
+        if (noct) {
+            const uint64_t ntiles = woff[noct] / kSplitTile;
+            const uint64_t tile_bytes = ntiles * kBktwTileBytes, side_bytes = ntiles * kBktSideBytes;
+            if (hipMalloc(reinterpret_cast<void**>(&p.d_bktw), tile_bytes) != hipSuccess ||
+                hipMalloc(reinterpret_cast<void**>(&p.d_bktw_side), side_bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                if (p.d_bktw) (void)hipFree(p.d_bktw);
+                p.d_bktw = p.d_bktw_side = nullptr;
+                idx->prof.bkt_copy_failed++;
+                noct = 0;
+            } else {
+                HIPCHECK(hipMemsetAsync(p.d_bktw_side, 0xff, side_bytes, idx->stream));   // every perm word: kBktPad until a code lands there
+                for (size_t j = 0; j < noct; ++j)
+                    if (woff[j + 1] > woff[j])
+                        launch_bkt_scatter_fill(p.d_codes + oct_lo(j) * 8, oct_n(j), (uint32_t)oct_lo(j), d_woff + j * kBktwKeys,
+                                                d_whist + j * kBktwKeys, p.d_bktw + woff[j] / kSplitTile * kBktwTileBytes,
+                                                p.d_bktw_side + woff[j] / kSplitTile * kBktSideBytes, winfo[2 * j], winfo[2 * j + 1],
+                                                idx->stream, /*wide=*/true);
+                HIPCHECK(hipGetLastError());
+                HIPCHECK(hipStreamSynchronize(idx->stream));
+                p.bktw_block = W;
+                p.bktw_off = woff;
+                idx->prof.bktw_copy_bytes += tile_bytes + side_bytes;
+                idx->prof.bktw_copy_slots += woff[noct];
+            }
+        }
+        // is narrow block b inside an octave that is stored wide?
+        auto in_wide = [&](size_t b) {
+            for (size_t j = 0; j < noct; ++j)
+                if (woff[j + 1] > woff[j] && b * block >= oct_lo(j) && b * block < oct_lo(j) + oct_n(j)) return true;
+            return false;
+        };
+        // ---- narrow blocks
         Scratch tmp;
         uint32_t *d_hist = nullptr, *d_off = nullptr, *d_info = nullptr;
         if (tmp.alloc(&d_hist, nblocks * kBktKeys * sizeof(uint32_t)) != hipSuccess ||
@@ -1521,9 +1636,14 @@ static int build_bkt_copies(qadc_index* idx) {
             continue;
         }
         HIPCHECK(hipMemsetAsync(d_hist, 0, nblocks * kBktKeys * sizeof(uint32_t), idx->stream));
+        HIPCHECK(hipMemsetAsync(d_info, 0, nblocks * 2 * sizeof(uint32_t), idx->stream));
         auto block_n = [&](size_t b) { return (uint32_t)std::min<uint64_t>(block, (uint64_t)p.n - b * block); };
-        for (size_t b = 0; b < nblocks; ++b)
+        size_t nnarrow = 0;
+        for (size_t b = 0; b < nblocks; ++b) {
+            if (in_wide(b)) continue;
+            ++nnarrow;
             launch_bkt_hist_scan(p.d_codes + b * block * 8, block_n(b), d_hist + b * kBktKeys, d_off + b * kBktKeys, d_info + 2 * b, idx->stream);
+        }
         HIPCHECK(hipGetLastError());
         std::vector<uint32_t> info(2 * nblocks);
         HIPCHECK(hipMemcpyAsync(info.data(), d_info, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, idx->stream));
@@ -1538,6 +1658,7 @@ static int build_bkt_copies(qadc_index* idx) {
             idx->prof.bkt_copy_padded_out++;
             continue;
         }
+        if (!nnarrow || off[nblocks] == 0) continue;             // (every block lies in a wide octave)
         const uint64_t ntiles = off[nblocks] / kSplitTile;
         const uint64_t tile_bytes = ntiles * kBktTileBytes, side_bytes = ntiles * kBktSideBytes;
         if (hipMalloc(reinterpret_cast<void**>(&p.d_bkt), tile_bytes) != hipSuccess ||
@@ -1550,9 +1671,10 @@ static int build_bkt_copies(qadc_index* idx) {
         }
         HIPCHECK(hipMemsetAsync(p.d_bkt_side, 0xff, side_bytes, idx->stream));       // every perm word: kBktPad until a code lands there
         for (size_t b = 0; b < nblocks; ++b)
-            launch_bkt_scatter_fill(p.d_codes + b * block * 8, block_n(b), (uint32_t)(b * block), d_off + b * kBktKeys, d_hist + b * kBktKeys,
-                                    p.d_bkt + off[b] / kSplitTile * kBktTileBytes, p.d_bkt_side + off[b] / kSplitTile * kBktSideBytes,
-                                    info[2 * b], info[2 * b + 1], idx->stream);
+            if (info[2 * b])
+                launch_bkt_scatter_fill(p.d_codes + b * block * 8, block_n(b), (uint32_t)(b * block), d_off + b * kBktKeys, d_hist + b * kBktKeys,
+                                        p.d_bkt + off[b] / kSplitTile * kBktTileBytes, p.d_bkt_side + off[b] / kSplitTile * kBktSideBytes,
+                                        info[2 * b], info[2 * b + 1], idx->stream);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipStreamSynchronize(idx->stream));             // (the scratch is freed on leaving this iteration)
         p.bkt_block = block;
@@ -1636,7 +1758,8 @@ int qadc_index_finalize(qadc_index* idx, float keep) {
     const LevelOptions nib_opt{idx->M, idx->level_base, idx->level_growth, idx->head_level, idx->small_run, idx->wgs_per_item,
                                idx->share_variant, idx->mq, idx->prescan_sample, idx->split_min_run, idx->split6_min_run,
                                idx->split5_min_run, idx->nib_min_run, idx->nib8_min_run, idx->nib_ns,
-                               idx->bkt_min_run, idx->bkt6_min_run, idx->bkt5_min_run, idx->bkt4_min_run};
+                               idx->bkt_min_run, idx->bkt6_min_run, idx->bkt5_min_run, idx->bkt4_min_run,
+                               idx->bktw_min_run, idx->bktw5_min_run, idx->bktw4_min_run, idx->bktw3_min_run};
     // ... and the nibble-plane copies of all 16 sub-quantizers for the nibble form (8 bytes per code more), where that form is on:
     // partitions with a byte-plane copy (the planner takes the form only for runs that have both) of at least the smaller of its
     // non-zero thresholds.  A failed allocation is skipped and counted in the same way.  A partition whose long runs all take the
@@ -2011,7 +2134,11 @@ int qadc_profile_reset(qadc_index* idx) {
     const uint64_t nib_bytes = idx->prof.nib_copy_bytes, nib_failed = idx->prof.nib_copy_failed;
     const uint64_t bkt_bytes = idx->prof.bkt_copy_bytes, bkt_failed = idx->prof.bkt_copy_failed, bkt_padded = idx->prof.bkt_copy_padded_out,
                    bkt_cslots = idx->prof.bkt_copy_slots;
+    const uint64_t bktw_bytes = idx->prof.bktw_copy_bytes, bktw_cslots = idx->prof.bktw_copy_slots, bktw_fb = idx->prof.bktw_copy_fallback;
     idx->prof = qadc_profile{};
+    idx->prof.bktw_copy_bytes = bktw_bytes;
+    idx->prof.bktw_copy_slots = bktw_cslots;
+    idx->prof.bktw_copy_fallback = bktw_fb;
     idx->prof.bkt_copy_bytes = bkt_bytes;
     idx->prof.bkt_copy_failed = bkt_failed;
     idx->prof.bkt_copy_padded_out = bkt_padded;
@@ -2090,6 +2217,68 @@ int qadc_index_set_split_bkt(qadc_index* idx, uint64_t bkt_min_run, uint64_t bkt
     idx->bkt5_min_run = min_run5;
     idx->bkt4_min_run = min_run4;
     idx->bkt_max_pad = bkt_max_pad;
+    return QADC_OK;
+}
+
+int qadc_index_set_split_bkt_wide(qadc_index* idx, uint64_t wide_block, uint64_t min_run, uint64_t min_run5, uint64_t min_run4,
+                                  uint64_t min_run3, double wide_max_pad) {
+    if (!idx) return fail(QADC_E_ARG, "null index");
+    if (wide_block != 0 && ((wide_block & (wide_block - 1)) != 0 || wide_block % idx->bkt_block != 0 || wide_block > (1ull << 31)))
+        return fail(QADC_E_ARG, "bkt_wide_block is 0 or a power of two, a multiple of bkt_block");
+    if (wide_max_pad == 0) wide_max_pad = idx->bkt_wide_max_pad;
+    if (!(wide_max_pad >= 1.0)) return fail(QADC_E_ARG, "bkt_wide_max_pad is at least 1");
+    if (idx->finalized && (wide_block != idx->bkt_wide_block || wide_max_pad != idx->bkt_wide_max_pad))
+        return fail(QADC_E_STATE, "the wide blocks are built by qadc_index_finalize: set bkt_wide_block and bkt_wide_max_pad before");
+    idx->bkt_wide_block = wide_block;
+    idx->bktw_min_run = min_run;
+    idx->bktw5_min_run = min_run5;
+    idx->bktw4_min_run = min_run4;
+    idx->bktw3_min_run = min_run3;
+    idx->bkt_wide_max_pad = wide_max_pad;
+    return QADC_OK;
+}
+
+int qadc_bktw_choice(int device_id, const int8_t* tables, int ntables, uint8_t* out) {
+    if (!tables || !out || ntables <= 0) return fail(QADC_E_ARG, "bad arguments");
+    if (int rc = qadc_device_prepare(device_id)) return rc;
+    HIPCHECK(hipSetDevice(device_id));
+    DevBuf<int8_t> d_t;
+    DevBuf<uint8_t> d_o;
+    hipError_t e = d_t.ensure((size_t)ntables * 256);
+    if (e == hipSuccess) e = d_o.ensure((size_t)ntables * kBktwSelBytes);
+    if (e == hipSuccess) e = hipMemcpy(d_t.p, tables, (size_t)ntables * 256, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_plane_choice(d_t.p, ntables, nullptr, nullptr, nullptr, nullptr, nullptr, d_o.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_o.p, (size_t)ntables * kBktwSelBytes, hipMemcpyDeviceToHost);
+    d_t.release();
+    d_o.release();
+    HIPCHECK(e);
+    return QADC_OK;
+}
+
+int qadc_index_bktw_info(qadc_index* idx, int part, uint64_t* wide_block, uint64_t* noctaves, uint64_t* slots) {
+    if (!idx || part < 0 || part >= (int)idx->parts.size()) return fail(QADC_E_ARG, "bad arguments");
+    const Part& p = idx->parts[part];
+    const bool has = p.d_bktw && !p.bktw_off.empty();
+    if (wide_block) *wide_block = has ? p.bktw_block : 0;
+    if (noctaves) *noctaves = has ? p.bktw_off.size() - 1 : 0;
+    if (slots) *slots = has ? p.bktw_off.back() : 0;
+    return QADC_OK;
+}
+
+int qadc_index_bktw_read(qadc_index* idx, int part, uint64_t* octave_off, uint8_t* tiles, uint8_t* side) {
+    if (!idx || part < 0 || part >= (int)idx->parts.size()) return fail(QADC_E_ARG, "bad arguments");
+    const Part& p = idx->parts[part];
+    if (!p.d_bktw || p.bktw_off.empty()) return fail(QADC_E_STATE, "the partition has no wide blocks");
+    if (int rc = use_device(idx)) return rc;
+    HIPCHECK(hipDeviceSynchronize());
+    const uint64_t ntiles = p.bktw_off.back() / kSplitTile;
+    if (octave_off) std::memcpy(octave_off, p.bktw_off.data(), p.bktw_off.size() * sizeof(uint64_t));
+    if (tiles) HIPCHECK(hipMemcpy(tiles, p.d_bktw, ntiles * kBktwTileBytes, hipMemcpyDeviceToHost));
+    if (side) HIPCHECK(hipMemcpy(side, p.d_bktw_side, ntiles * kBktSideBytes, hipMemcpyDeviceToHost));
     return QADC_OK;
 }
 

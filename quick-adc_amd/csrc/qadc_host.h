@@ -180,6 +180,7 @@ struct Slot {
     DevBuf<int8_t> d_qtables;
     DevBuf<uint8_t> d_plane_sel;        // 16x4: the 6-plane split form's deferred byte of every table of the batch (written beside d_qt)
     DevBuf<uint8_t> d_bkt_sel;          // ... and the bucket form's kBktSelBytes per table (deferred masks and slacks for NSP = 4..7)
+    DevBuf<uint8_t> d_bktw_sel;         // ... and its wide form's kBktwSelBytes per table (NSP = 3..6 among sub-quantizers 5-15)
     DevBuf<uint8_t> d_nib_sel;          // ... and the nibble form's kNibSelBytes per table (deferred masks and slacks for NS = 8, 9, 10)
     DevBuf<uint8_t> d_plane_sel5;       // ... and the 5-plane form's two bytes per table: j1 | j2 << 4, slack (launch_scan_i8)
     DevBuf<Cand> d_cands;
@@ -465,6 +466,16 @@ struct qadc_index {
     uint64_t bkt5_min_run = 1ull << 27;      // the levels from 2^27 and 2^29: 5
     uint64_t bkt4_min_run = 0;
     double bkt_max_pad = 1.125;
+    // wide blocks of the bucket copy (qadc_index_set_split_bkt_wide): positions from bkt_wide_block on are stored in
+    // octave blocks grouped by a 20-bit key (0 = none), unless padding inflates an octave beyond bkt_wide_max_pad x its codes (that
+    // octave keeps narrow blocks).  Runs of at least bktw_min_run codes that cover whole wide octaves take the wide form with 6 paid
+    // planes, 5 / 4 / 3 from bktw5 / bktw4 / bktw3_min_run on (0 = never; profiles/r12_bktw_ab.txt)
+    uint64_t bkt_wide_block = 1ull << 27;
+    uint64_t bktw_min_run = 1ull << 27;
+    uint64_t bktw5_min_run = 1ull << 27;
+    uint64_t bktw4_min_run = 1ull << 27;
+    uint64_t bktw3_min_run = 0;
+    double bkt_wide_max_pad = 1.08;
     // one workgroup per query (IVF batches, small lists): 0 = never, 1 = auto, 2 = whenever structurally possible
     int wgq = 1;
     uint32_t wgq_capacity = 4096;        // stream entries per query to start with

@@ -20,9 +20,12 @@ void launch_nib_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipStr
 // first slots d_off [kBktKeys] and d_info = {the block's slots (whole tiles), its last real slot};
 // launch_bkt_scatter_fill: the block's codes into their slots of d_side (whose perm words are kBktPad before), padding, planes and ids
 // of d_tiles.  d_tiles / d_side: the block's first tile; pos_first: the position of the block's first code in the partition.
-void launch_bkt_hist_scan(const uint8_t* d_codes, uint32_t n, uint32_t* d_hist, uint32_t* d_off, uint32_t* d_info, hipStream_t stream);
+void launch_bkt_hist_scan(const uint8_t* d_codes, uint32_t n, uint32_t* d_hist, uint32_t* d_off, uint32_t* d_info, hipStream_t stream,
+                          bool wide = false);
 void launch_bkt_scatter_fill(const uint8_t* d_codes, uint32_t n, uint32_t pos_first, const uint32_t* d_off, uint32_t* d_cursor,
-                             uint8_t* d_tiles, uint8_t* d_side, uint32_t slots, uint32_t last_real, hipStream_t stream);
+                             uint8_t* d_tiles, uint8_t* d_side, uint32_t slots, uint32_t last_real, hipStream_t stream,
+                             bool wide = false);
+// wide: a wide octave (kBktwKeys keys, d_hist / d_off of that many words, kBktwTileBytes per tile) instead of a narrow block.
 
 // Candidate emitted by the scan: value < bound derived from a strict prefix of the scan order.
 struct Cand {
@@ -244,7 +247,8 @@ void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands,
                     uint32_t cap_per_query, uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel = nullptr,
                     unsigned long long* d_surv = nullptr, const uint8_t* d_plane_sel5 = nullptr,
-                    const uint8_t* d_nib_sel = nullptr, int nib_ns = 0, const uint8_t* d_bkt_sel = nullptr, int bkt_nsp = 0);
+                    const uint8_t* d_nib_sel = nullptr, int nib_ns = 0, const uint8_t* d_bkt_sel = nullptr, int bkt_nsp = 0,
+                    int bkt_free = 4);
 // Split form only (variant bit 5).  d_plane_sel5 != nullptr: the 5-plane form, two bytes per table: j1 | j2 << 4 (the bytes
 // j1 < j2 of 0..6 deferred beside byte 7) and the slack c of its survivor test (min(127, the deferred pair tables' minima
 // summed): a code survives when its 5-byte partial is below bound - c).  Else d_plane_sel != nullptr: the 6-plane form,
@@ -254,12 +258,14 @@ void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int
 // sub-quantizers from the nibble-plane copy, where ScanItem::split then points; d_nib_sel = kNibSelBytes per table: for each NS the deferred set (16-bit mask) and the slack.
 // bkt_nsp = 4..7 with d_bkt_sel != nullptr: the bucket form (scan_i8_bkt_kernel) instead of all of these: the runs are bucket-form runs
 // (LevelLaunch::bkt: slots, tiles of the bucket copy and of its side array); d_bkt_sel = kBktSelBytes per table.
+// bkt_free = 5 with bkt_nsp = 3..6: the wide form (scan_i8_bktw_kernel; LevelLaunch::bktw); d_bkt_sel = its choice bytes, kBktwSelBytes per table.
 
 // The deferred byte of every 16x4 int8 table (qtables + t * 256 -> d_plane_sel[t]) and the 5-plane form's two bytes per
 // table (d_plane_sel5[2 t], [2 t + 1]) for tables the caller brings, either or both; tables quantized here get theirs from
 // launch_select_kth (d_plane_sel, d_plane_sel5).
 void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream,
-                         uint8_t* d_plane_sel5 = nullptr, uint8_t* d_nib_sel = nullptr, uint8_t* d_bkt_sel = nullptr);
+                         uint8_t* d_plane_sel5 = nullptr, uint8_t* d_nib_sel = nullptr, uint8_t* d_bkt_sel = nullptr,
+                         uint8_t* d_bktw_sel = nullptr);
 
 // Multi-query streaming scan: groups of up to 8 consecutive runs (all over the same codes, one per query) share
 // ONE pass; wgs_per_group workgroups of 256 threads per group, sibling-major over the groups.
@@ -349,7 +355,7 @@ void launch_select_kth(const float* d_fc, uint64_t fc_stride, const uint32_t* d_
                        int quant_mode, hipStream_t stream, float* export_vals = nullptr,
                        uint32_t* export_flags = nullptr, uint32_t* d_front_out = nullptr, int small_wg = 0,
                        uint8_t* d_plane_sel = nullptr, uint8_t* d_plane_sel5 = nullptr, uint8_t* d_nib_sel = nullptr,
-                       uint8_t* d_bkt_sel = nullptr);
+                       uint8_t* d_bkt_sel = nullptr, uint8_t* d_bktw_sel = nullptr);
 // d_front_out (optional): {flags & 3, qmin, qmax, 0} per query = the front_in record of scan_query_kernel's HEAD; small_wg:
 // 256-thread workgroups (a batch of many queries beside running scans) instead of 1024.  d_plane_sel (optional, 16x4 with
 // d_qtables): the 6-plane split form's deferred byte of each quantized table, [nq][table_dim_all / 256]; d_plane_sel5: the

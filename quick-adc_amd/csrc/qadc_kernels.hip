@@ -10,6 +10,7 @@
 // The op is a gather + byte add bound by HBM reads: no MFMA.
 #include "qadc_kernels.h"
 #include "qadc_float_sum.h"
+#include <cstdio>
 #include <cstdlib>
 
 #include <algorithm>
@@ -889,25 +890,66 @@ __device__ __forceinline__ uint64_t bkt_streamed(uint32_t mask, uint32_t& used) 
     return list;
 }
 
-template <int NSP, bool NT, bool CHUNK, bool PROBE>
-__global__ __launch_bounds__(kWG, 8) void scan_i8_bkt_kernel(
+// The wide form's lists (FREE = 5): the NSP paid sub-quantizers among 5..15 as nibbles of `paid` (the clear bits of the deferred
+// mask, ascending, then set bits until there are NSP), and the list build_nib_tables takes.  An even NSP: 0-3, the paid ones, then
+// row 4 as the single row at the end (its low-nibble slot is T4).  An odd NSP: 0-3, then row 4 FUSED with the first paid plane
+// into a pair table, then the other paid pairs.  used = the rows the loop sums; its complement is the deferred set.
+template <int NSP>
+__device__ __forceinline__ uint64_t bktw_streamed(uint32_t mask, uint32_t& used, uint64_t& paid) {
+    mask &= 0xffe0u;
+    paid = 0;
+    uint32_t cnt = 0;
+    used = 0x1fu;
+#pragma unroll
+    for (uint32_t pass = 0; pass < 2; ++pass)
+#pragma unroll
+        for (uint32_t s = 5; s < 16; ++s)
+            if (((mask >> s) & 1u) == pass && cnt < (uint32_t)NSP) {
+                paid |= (uint64_t)s << (4u * cnt);
+                used |= 1u << s;
+                ++cnt;
+            }
+    return (NSP & 1) ? (0x43210ull | (paid << 20)) : (0x3210ull | (paid << 16) | (4ull << (4u * (NSP + 4))));
+}
+
+// The body of both bucket kernels.  FREE = 4: narrow blocks (16-bit key, 12 planes of sub-quantizers 4-15, NSP = 4..7 of them
+// paid).  FREE = 5: wide octaves (20-bit key, 11 planes of sub-quantizers 5-15, NSP = 3..6 paid; the group's sub-quantizer 4 is
+// one more byte of its id: s0 = P01[id & 255] + P23[id >> 8] + T4[id4], or, NSP odd, row 4 joins the first paid plane's pair table
+// with id4 splatted into the low nibbles of the merged index).  sel = the form's choice bytes of every table.
+template <int FREE, int NSP, bool NT, bool CHUNK, bool PROBE>
+__device__ __forceinline__ void scan_bkt_body(
     const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
     CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
     const uint8_t* __restrict__ bkt_sel, unsigned long long* __restrict__ surv) {
-    static_assert(NSP >= 4 && NSP <= 7, "4, 5, 6 or 7 of the 12 paid nibble planes");
+    static_assert(FREE == 4 || FREE == 5, "16-bit or 20-bit key");
+    static_assert(FREE == 5 || (NSP >= 4 && NSP <= 7), "4, 5, 6 or 7 of the 12 paid nibble planes");
+    static_assert(FREE == 4 || (NSP >= 3 && NSP <= 6), "3, 4, 5 or 6 of the 11 paid nibble planes");
     static_assert(kSplitTile == 16u * kWG, "a workgroup iteration is one tile: 16 slots per lane");
     static_assert(kBktTileBytes % 8 == 0 && kBktIdOff % 8 == 0, "8-byte plane vectors");
+    static_assert(kBktwTileBytes % 8 == 0 && kBktwIdOff % 8 == 0, "8-byte plane vectors");
     using C = ScanCfg<16>;
-    constexpr int NS = NSP + 4;                                 // rows in the LDS image
-    constexpr int NP = NSP / 2;                                 // fused paid pairs: slots 2 .. 2 + NP - 1
-    constexpr bool ODD = (NSP & 1) != 0;                        // ... and one single plane: slots 2 + NP and 3 + NP
+    constexpr bool WIDE = FREE == 5;
+    constexpr bool FUSE = WIDE && (NSP & 1) != 0;               // row 4 and the first paid plane share a pair table
+    constexpr int NVP = NSP + (FUSE ? 1 : 0);                   // planes of the pair loop (FUSE: the first is the splatted id4)
+    constexpr int NS = NSP + FREE;                              // rows in the LDS image
+    constexpr int NP = NVP / 2;                                 // fused paid pairs: slots 2 .. 2 + NP - 1
+    constexpr bool ODD = !WIDE && (NSP & 1) != 0;               // ... and one single plane: slots 2 + NP and 3 + NP
+    static_assert(2 + NP + (ODD || (WIDE && !FUSE) ? 2 : 0) <= 8, "the LDS image has 8 slots");
+    constexpr uint32_t kTile = WIDE ? kBktwTileBytes : kBktTileBytes, kIdOff = WIDE ? kBktwIdOff : kBktIdOff;
     const ScanItem it = items[blockIdx.y];
     QueryState* qs = qstates + it.query;
     out += (uint64_t)it.query * cand_cap;
-    const uint8_t* sel = bkt_sel + (size_t)it.table * kBktSelBytes + 4u * (NSP - 4);
+    const uint8_t* sel = bkt_sel + (size_t)it.table * (WIDE ? kBktwSelBytes : kBktSelBytes) + 4u * (NSP - (WIDE ? 3 : 4));
     const uint32_t slack = min((uint32_t)sel[2], 127u);
     uint32_t used;
-    const uint64_t list = bkt_streamed<NSP>((uint32_t)sel[0] | ((uint32_t)sel[1] << 8), used);
+    uint64_t paid = 0;
+    uint64_t list;
+    if constexpr (WIDE) {
+        list = bktw_streamed<NSP>((uint32_t)sel[0] | ((uint32_t)sel[1] << 8), used, paid);
+    } else {
+        list = bkt_streamed<NSP>((uint32_t)sel[0] | ((uint32_t)sel[1] << 8), used);
+        paid = list >> 16;
+    }
     const uint32_t defmask = 0xffffu & ~used;                   // (whatever the bytes hold: the complement of what is summed in the loop)
     build_nib_tables<NS>(qtables + (uint64_t)it.table * 256, list);
     const uint32_t bound = prefix_bound(qs, it.order >> 16, R, reinterpret_cast<uint32_t*>(smem + C::HIST_OFF),
@@ -920,7 +962,8 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_bkt_kernel(
     typedef const __attribute__((address_space(1))) unsigned short* gid_t;
     typedef const __attribute__((address_space(1))) unsigned char* gbyte_t;
     const gvec_t planes = (gvec_t)(uintptr_t)it.split;          // the run's first tile of the bucket copy
-    const gid_t ids = (gid_t)(uintptr_t)(it.split + kBktIdOff) + tid;
+    const gid_t ids = (gid_t)(uintptr_t)(it.split + kIdOff) + tid;
+    [[maybe_unused]] const gbyte_t id4s = (gbyte_t)(uintptr_t)(it.split + kBktwId4Off) + tid;   // (WIDE only)
     const gbyte_t side = (gbyte_t)(uintptr_t)it.codes;          // ... and of its side array
     lds_base_is_zero();
     const uint32_t ntiles = it.n / kSplitTile;                  // (n = slots: whole tiles)
@@ -931,10 +974,11 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_bkt_kernel(
         last = min(ntiles, first + per);
         step = 1;
     }
-    // 8-byte-vector offset of the paid plane streamed i-th (uniform; sub-quantizer 4..15: plane 0..11, inside the tile)
+    // 8-byte-vector offset of the paid plane streamed i-th (uniform; sub-quantizer FREE..15: plane 0..15 - FREE, inside the tile)
     uint32_t poff[NSP];
 #pragma unroll
-    for (int i = 0; i < NSP; ++i) poff[i] = (((uint32_t)(list >> (4 * (i + 4))) & 15u) - 4u) % kBktPlanes * (kSplitTile / 16);
+    for (int i = 0; i < NSP; ++i)
+        poff[i] = (((uint32_t)(paid >> (4 * i)) & 15u) - (uint32_t)FREE) % (WIDE ? kBktwPlanes : kBktPlanes) * (kSplitTile / 16);
     const uint32_t bsurv = bound > slack ? bound - slack : 0u;  // 0 = no survivor (never wraps)
     const uint32_t bound4 = bsurv * 0x01010101u;
 
@@ -991,9 +1035,14 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_bkt_kernel(
     };
     auto step_tile = [&](uint32_t t) __attribute__((always_inline)) {
         u32x2 v[NSP];
-        const uint32_t e0 = t * (kBktTileBytes / 8) + tid;      // vector index of plane 0 (t < 2^18: no wrap)
-        const gid_t idp = ids + (uint64_t)t * (kBktTileBytes / 2);
+        const uint32_t e0 = t * (kTile / 8) + tid;              // vector index of plane 0 (t < 2^18: no wrap)
+        const gid_t idp = ids + (uint64_t)t * (kTile / 2);
         const uint32_t id = NT ? __builtin_nontemporal_load(idp) : *idp;
+        uint32_t id4 = 0;                                       // WIDE: the group's sub-quantizer 4
+        if constexpr (WIDE) {
+            const gbyte_t p4 = id4s + (uint64_t)t * kTile;
+            id4 = (NT ? __builtin_nontemporal_load(p4) : *p4) & 15u;
+        }
 #pragma unroll
         for (int i = 0; i < NSP; ++i)
             v[i] = NT ? __builtin_nontemporal_load(planes + e0 + poff[i]) : planes[e0 + poff[i]];
@@ -1007,19 +1056,25 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_bkt_kernel(
             for (int i = 1; i < NSP; ++i) a ^= v[i];
 #pragma unroll
             for (int c = 0; c < 16; ++c) cv[c] = 127u;
-            cv[0] = ((a.x ^ a.y ^ id) == 0x12345678u) ? 0u : 127u;
+            cv[0] = ((a.x ^ a.y ^ id ^ (id4 << 16)) == 0x12345678u) ? 0u : 127u;
             best = cv[0];
         } else {
             constexpr uint32_t LO = 0x0f0f0f0fu;
             // the group's four free rows: P01[id & 255] in slot 0, P23[id >> 8] in slot 1
-            const uint32_t s0 = *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id & 0xffu) << 8) | lane_lo) + 0u)) +
-                                *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id >> 8) & 0xffu) << 8 | lane_lo) + 1u));
+            uint32_t s0 = *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id & 0xffu) << 8) | lane_lo) + 0u)) +
+                          *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id >> 8) & 0xffu) << 8 | lane_lo) + 1u));
+            if constexpr (WIDE && !FUSE) {                      // the fifth free row: the single row's low-nibble slot, T4[x & 15]
+                constexpr int sl = NP + 2;
+                s0 += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((id4 << 8) | lane_lo) + (sl >> 2) * 128 + (sl & 3)));
+            }
+            [[maybe_unused]] const uint32_t id4s8 = id4 * 0x11111111u;           // FUSE: id4 in every nibble, the pair loop's plane 0
 #pragma unroll
             for (int w = 0; w < 2; ++w) {
                 uint32_t idx[2][NP > 0 ? NP : 1];               // [slots 0-3 | 4-7 of the dword's eight][pair]: four byte indices each
 #pragma unroll
                 for (int p = 0; p < NP; ++p) {
-                    const uint32_t A = v[2 * p][w], B = v[2 * p + 1][w];
+                    const uint32_t A = FUSE ? (p == 0 ? id4s8 : v[p > 0 ? 2 * p - 1 : 0][w]) : v[2 * p][w];
+                    const uint32_t B = FUSE ? v[2 * p][w] : v[2 * p + 1][w];
                     idx[0][p] = (A & LO) | ((B << 4) & ~LO);
                     idx[1][p] = ((A >> 4) & LO) | (B & ~LO);
                 }
@@ -1079,6 +1134,24 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_bkt_kernel(
         if (tid == 0 && *cnt) atomicAdd(surv, (unsigned long long)*cnt);
     }
 }
+
+template <int NSP, bool NT, bool CHUNK, bool PROBE>
+__global__ __launch_bounds__(kWG, 8) void scan_i8_bkt_kernel(
+    const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
+    CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
+    const uint8_t* __restrict__ bkt_sel, unsigned long long* __restrict__ surv) {
+    scan_bkt_body<4, NSP, NT, CHUNK, PROBE>(items, qtables, qstates, hdr, out, cand_cap, R, bkt_sel, surv);
+}
+
+// The wide form ("wide octaves"): the runs read wide tiles, bktw_sel = kBktwSelBytes per table (plane_choice_bktw).
+template <int NSP, bool NT, bool CHUNK, bool PROBE>
+__global__ __launch_bounds__(kWG, 8) void scan_i8_bktw_kernel(
+    const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
+    CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
+    const uint8_t* __restrict__ bktw_sel, unsigned long long* __restrict__ surv) {
+    scan_bkt_body<5, NSP, NT, CHUNK, PROBE>(items, qtables, qstates, hdr, out, cand_cap, R, bktw_sel, surv);
+}
+
 
 // The deferred byte of the 6-plane split form, once per int8 table: the j in 0..6 whose 256 pair entries
 // q[2j][lo] + q[2j+1][hi] have the smallest sum = 16 x (the sum of the two 16-entry rows); ties: the highest j.
@@ -1178,11 +1251,12 @@ __device__ __forceinline__ void plane_choice_nib(const int8_t* __restrict__ qt, 
 // picked among 4..15 only, by plane_choice_nib's score and tie rule, nested: 5 picks for NSP = 7 paid planes, one more for
 // 6, 5 and 4.  kBktSelBytes bytes: at 4 * (NSP - 4) the set as a 16-bit mask (low byte first), c = min(127, the sum of min T[s]
 // over the set), 0.  A c above the deferred entries' sum would lose candidates, a poor set only costs survivors.
-__device__ __forceinline__ void plane_choice_bkt(const int8_t* __restrict__ qt, uint8_t* __restrict__ out) {
+template <uint32_t FIRST>
+__device__ __forceinline__ void plane_choice_bkt_from(const int8_t* __restrict__ qt, uint8_t* __restrict__ out) {
     const uint8_t* T = reinterpret_cast<const uint8_t*>(qt);
     uint32_t score[16], mn[16];
 #pragma unroll
-    for (uint32_t s = 4; s < 16; ++s) {
+    for (uint32_t s = FIRST; s < 16; ++s) {
         uint32_t sum = 0, m = 255u;
         for (int i = 0; i < 16; ++i) {
             const uint32_t a = T[16 * s + i];
@@ -1197,11 +1271,11 @@ __device__ __forceinline__ void plane_choice_bkt(const int8_t* __restrict__ qt, 
     for (uint32_t pick = 0; pick < 8; ++pick) {
         uint32_t best = 0xffffffffu, bs = 15, bm = 0;
 #pragma unroll
-        for (uint32_t s = 4; s < 16; ++s)
+        for (uint32_t s = FIRST; s < 16; ++s)
             if (!((mask >> s) & 1u) && score[s] <= best) { best = score[s]; bs = s; bm = mn[s]; }
         mask |= 1u << bs;
         c += bm;
-        if (pick >= 4) {                                        // 5, 6, 7, 8 deferred = NSP 7, 6, 5, 4
+        if (pick >= 4) {                                        // 5, 6, 7, 8 deferred = NSP 7, 6, 5, 4 (FIRST = 5: NSP 6, 5, 4, 3)
             uint8_t* o = out + 4u * (7u - pick);
             o[0] = (uint8_t)(mask & 0xffu);
             o[1] = (uint8_t)(mask >> 8);
@@ -1210,12 +1284,21 @@ __device__ __forceinline__ void plane_choice_bkt(const int8_t* __restrict__ qt, 
         }
     }
 }
+__device__ __forceinline__ void plane_choice_bkt(const int8_t* __restrict__ qt, uint8_t* __restrict__ out) {
+    plane_choice_bkt_from<4>(qt, out);
+}
+// The wide form's choice: sub-quantizers 0-4 are free, so the same picks run among 5..15: 5 picks for NSP = 6 paid planes, one more
+// for 5, 4 and 3.  kBktwSelBytes bytes: at 4 * (NSP - 3) the mask, c, 0.
+__device__ __forceinline__ void plane_choice_bktw(const int8_t* __restrict__ qt, uint8_t* __restrict__ out) {
+    static_assert(kBktwSelBytes == kBktSelBytes, "the same four records");
+    plane_choice_bkt_from<5>(qt, out);
+}
 
 // plane_sel (6-plane form, 1 byte per table), plane_sel5 (5-plane form, 2 bytes per table), nib_sel (nibble form, kNibSelBytes
 // per table) and bkt_sel (bucket form, kBktSelBytes per table): each may be null
 __global__ __launch_bounds__(256) void plane_choice_kernel(const int8_t* __restrict__ qtables, int ntables, uint8_t* __restrict__ plane_sel,
                                                            uint8_t* __restrict__ plane_sel5, uint8_t* __restrict__ nib_sel,
-                                                           uint8_t* __restrict__ bkt_sel) {
+                                                           uint8_t* __restrict__ bkt_sel, uint8_t* __restrict__ bktw_sel) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= ntables) return;
     if (plane_sel) plane_sel[t] = (uint8_t)plane_choice(qtables + (size_t)t * 256);
@@ -1226,13 +1309,14 @@ __global__ __launch_bounds__(256) void plane_choice_kernel(const int8_t* __restr
     }
     if (nib_sel) plane_choice_nib(qtables + (size_t)t * 256, nib_sel + (size_t)t * kNibSelBytes);
     if (bkt_sel) plane_choice_bkt(qtables + (size_t)t * 256, bkt_sel + (size_t)t * kBktSelBytes);
+    if (bktw_sel) plane_choice_bktw(qtables + (size_t)t * 256, bktw_sel + (size_t)t * kBktwSelBytes);
 }
 
 void launch_plane_choice(const int8_t* d_qtables, int ntables, uint8_t* d_plane_sel, hipStream_t stream, uint8_t* d_plane_sel5,
-                         uint8_t* d_nib_sel, uint8_t* d_bkt_sel) {
-    if (ntables <= 0 || (!d_plane_sel && !d_plane_sel5 && !d_nib_sel && !d_bkt_sel)) return;
+                         uint8_t* d_nib_sel, uint8_t* d_bkt_sel, uint8_t* d_bktw_sel) {
+    if (ntables <= 0 || (!d_plane_sel && !d_plane_sel5 && !d_nib_sel && !d_bkt_sel && !d_bktw_sel)) return;
     hipLaunchKernelGGL(plane_choice_kernel, dim3((ntables + 255) / 256), dim3(256), 0, stream, d_qtables, ntables, d_plane_sel,
-                       d_plane_sel5, d_nib_sel, d_bkt_sel);
+                       d_plane_sel5, d_nib_sel, d_bkt_sel, d_bktw_sel);
 }
 
 // The byte-plane copy of a partition (kSplitTile layout): one thread per 16 codes of a tile, plane b's 16 bytes = byte b
@@ -1301,35 +1385,38 @@ void launch_nib_copy(const uint8_t* d_codes, uint32_t n, uint8_t* d_copy, hipStr
 // ---- the bucket copy of a partition (host/level_plan.hpp has the layout), block by block; run once per partition by
 // qadc_index_finalize, not timed.  The scatter is UNSTABLE: a code's slot inside its bucket is the order in which its atomicAdd on
 // the bucket's cursor lands, so two builds of the same partition may order a bucket differently.  No result depends on that order.
-// Key histogram of one block: codes = the block's first code, n = its codes; hist[kBktKeys], zeroed by the caller.
-__global__ __launch_bounds__(256) void bkt_hist_kernel(const uint8_t* __restrict__ codes, uint32_t n, uint32_t* __restrict__ hist) {
+// Key histogram of one block: codes = the block's first code, n = its codes; hist[nkeys], zeroed by the caller.  nkeys = kBktKeys
+// (narrow block: code bytes 0 and 1) or kBktwKeys (wide octave: and the low nibble of byte 2): key = the code's low bits.
+__global__ __launch_bounds__(256) void bkt_hist_kernel(const uint8_t* __restrict__ codes, uint32_t n, uint32_t* __restrict__ hist,
+                                                       uint32_t nkeys) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        atomicAdd(&hist[*reinterpret_cast<const uint16_t*>(codes + i * 8)], 1u);
+        atomicAdd(&hist[*reinterpret_cast<const uint32_t*>(codes + i * 8) & (nkeys - 1u)], 1u);
 }
 
 // Exclusive scan of the bucket sizes, each padded to a multiple of 16 slots: off[key] = first slot of the bucket in its block.
 // hist comes back zeroed (the scatter's cursors).  info[0] = the block's slots, padded to whole tiles; info[1] = its last real slot.
-// One workgroup of 1024 threads, 64 keys each.
-__global__ __launch_bounds__(1024) void bkt_scan_kernel(uint32_t* __restrict__ hist, uint32_t* __restrict__ off, uint32_t* __restrict__ info) {
-    static_assert(kBktKeys == 64 * 1024, "64 keys per thread");
+// One workgroup of 1024 threads, kpt = nkeys / 1024 consecutive keys each (64, or 1024 for a wide octave).
+__global__ __launch_bounds__(1024) void bkt_scan_kernel(uint32_t* __restrict__ hist, uint32_t* __restrict__ off, uint32_t* __restrict__ info,
+                                                        uint32_t kpt) {
+    static_assert(kBktKeys % 1024 == 0 && kBktwKeys % 1024 == 0, "whole keys per thread");
     __shared__ uint32_t wave_sum[16];
     __shared__ uint32_t last_real;
     const uint32_t t = threadIdx.x;
     if (t == 0) last_real = 0;
     uint32_t mine = 0;
-    for (uint32_t k = 0; k < 64; ++k) mine += (hist[64 * t + k] + 15u) & ~15u;
+    for (uint32_t k = 0; k < kpt; ++k) mine += (hist[kpt * t + k] + 15u) & ~15u;
     const uint32_t incl = dpp_wave_incl_sum(mine);
     if ((t & 63u) == 63u) wave_sum[t >> 6] = incl;
     __syncthreads();
     uint32_t run = incl - mine;
     for (uint32_t w = 0; w < (t >> 6); ++w) run += wave_sum[w];
     uint32_t end_real = 0;
-    for (uint32_t k = 0; k < 64; ++k) {
-        const uint32_t c = hist[64 * t + k];
-        off[64 * t + k] = run;
+    for (uint32_t k = 0; k < kpt; ++k) {
+        const uint32_t c = hist[kpt * t + k];
+        off[kpt * t + k] = run;
         if (c) end_real = run + c;
         run += (c + 15u) & ~15u;
-        hist[64 * t + k] = 0;
+        hist[kpt * t + k] = 0;
     }
     if (end_real) atomicMax(&last_real, end_real - 1u);
     __syncthreads();
@@ -1343,10 +1430,10 @@ __global__ __launch_bounds__(1024) void bkt_scan_kernel(uint32_t* __restrict__ h
 // `side` of the side array, with its position pos_first + i in the partition.  The side array's perm words are kBktPad beforehand.
 __global__ __launch_bounds__(256) void bkt_scatter_kernel(const uint8_t* __restrict__ codes, uint32_t n, uint32_t pos_first,
                                                           const uint32_t* __restrict__ off, uint32_t* __restrict__ cursor,
-                                                          uint8_t* __restrict__ side) {
+                                                          uint8_t* __restrict__ side, uint32_t nkeys) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint2 v = *reinterpret_cast<const uint2*>(codes + i * 8);
-        const uint32_t key = v.x & 0xffffu;
+        const uint32_t key = v.x & (nkeys - 1u);
         const uint32_t slot = off[key] + atomicAdd(&cursor[key], 1u);
         uint8_t* tile = side + (uint64_t)(slot / kSplitTile) * kBktSideBytes;
         *reinterpret_cast<uint2*>(tile + (uint64_t)(slot % kSplitTile) * 8) = v;
@@ -1356,7 +1443,9 @@ __global__ __launch_bounds__(256) void bkt_scatter_kernel(const uint8_t* __restr
 
 // Padding and planes of one block, one thread per 16-slot group: the padding slots of the group (perm == kBktPad; they follow the
 // bucket's real slots) get the code of the group's last real slot, a group without one (the block's tail) the code of the block's
-// last real slot; then the group's 12 nibble planes (nib_copy_kernel's in-plane layout) and its id are written.
+// last real slot; then the group's 12 nibble planes (nib_copy_kernel's in-plane layout) and its id are written.  WIDE: the 11
+// planes of sub-quantizers 5-15, the uint16 id and the byte of sub-quantizer 4 of a wide tile.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void bkt_fill_kernel(uint8_t* __restrict__ tiles, uint8_t* __restrict__ side, uint32_t slots,
                                                        uint32_t last_real) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1374,7 +1463,8 @@ __global__ __launch_bounds__(256) void bkt_fill_kernel(uint8_t* __restrict__ til
                                                   (uint64_t)(last_real % kSplitTile) * 8);
 #pragma unroll
     for (int c = 0; c < 16; ++c) fillv = c == last ? v[c] : fillv;
-    uint32_t o[kBktPlanes][2] = {};
+    constexpr int kFirst = WIDE ? 5 : 4, kPl = WIDE ? (int)kBktwPlanes : (int)kBktPlanes;
+    uint32_t o[kPl][2] = {};
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
         if (c > last) {
@@ -1383,31 +1473,38 @@ __global__ __launch_bounds__(256) void bkt_fill_kernel(uint8_t* __restrict__ til
         }
         const int sh = 8 * (c & 3) + 4 * ((c >> 2) & 1);
 #pragma unroll
-        for (int s = 4; s < 16; ++s) {
+        for (int s = kFirst; s < 16; ++s) {
             const uint32_t nibble = ((s < 8 ? v[c].x : v[c].y) >> (4 * (s & 7))) & 15u;
-            o[s - 4][c >> 3] |= nibble << sh;
+            o[s - kFirst][c >> 3] |= nibble << sh;
         }
     }
-    uint8_t* tt = tiles + tile * kBktTileBytes;
+    uint8_t* tt = tiles + tile * (WIDE ? kBktwTileBytes : kBktTileBytes);
 #pragma unroll
-    for (int s = 0; s < (int)kBktPlanes; ++s)
+    for (int s = 0; s < kPl; ++s)
         *reinterpret_cast<uint2*>(tt + (uint64_t)s * (kSplitTile / 2) + lane * 8) = make_uint2(o[s][0], o[s][1]);
-    *reinterpret_cast<uint16_t*>(tt + kBktIdOff + lane * 2) = (uint16_t)(v[0].x & 0xffffu);
+    *reinterpret_cast<uint16_t*>(tt + (WIDE ? kBktwIdOff : kBktIdOff) + lane * 2) = (uint16_t)(v[0].x & 0xffffu);
+    if (WIDE) tt[kBktwId4Off + lane] = (uint8_t)((v[0].x >> 16) & 15u);
 }
 
-void launch_bkt_hist_scan(const uint8_t* d_codes, uint32_t n, uint32_t* d_hist, uint32_t* d_off, uint32_t* d_info, hipStream_t stream) {
+void launch_bkt_hist_scan(const uint8_t* d_codes, uint32_t n, uint32_t* d_hist, uint32_t* d_off, uint32_t* d_info, hipStream_t stream,
+                          bool wide) {
     if (!n) return;
+    const uint32_t nkeys = wide ? kBktwKeys : kBktKeys;
     const unsigned wgs = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, 8192);
-    hipLaunchKernelGGL(bkt_hist_kernel, dim3(wgs), dim3(256), 0, stream, d_codes, n, d_hist);
-    hipLaunchKernelGGL(bkt_scan_kernel, dim3(1), dim3(1024), 0, stream, d_hist, d_off, d_info);
+    hipLaunchKernelGGL(bkt_hist_kernel, dim3(wgs), dim3(256), 0, stream, d_codes, n, d_hist, nkeys);
+    hipLaunchKernelGGL(bkt_scan_kernel, dim3(1), dim3(1024), 0, stream, d_hist, d_off, d_info, nkeys / 1024u);
 }
 
 void launch_bkt_scatter_fill(const uint8_t* d_codes, uint32_t n, uint32_t pos_first, const uint32_t* d_off, uint32_t* d_cursor,
-                             uint8_t* d_tiles, uint8_t* d_side, uint32_t slots, uint32_t last_real, hipStream_t stream) {
+                             uint8_t* d_tiles, uint8_t* d_side, uint32_t slots, uint32_t last_real, hipStream_t stream, bool wide) {
     if (!n || !slots) return;
     const unsigned wgs = (unsigned)std::min<uint64_t>(((uint64_t)n + 255) / 256, 8192);
-    hipLaunchKernelGGL(bkt_scatter_kernel, dim3(wgs), dim3(256), 0, stream, d_codes, n, pos_first, d_off, d_cursor, d_side);
-    hipLaunchKernelGGL(bkt_fill_kernel, dim3((slots / 16 + 255) / 256), dim3(256), 0, stream, d_tiles, d_side, slots, last_real);
+    hipLaunchKernelGGL(bkt_scatter_kernel, dim3(wgs), dim3(256), 0, stream, d_codes, n, pos_first, d_off, d_cursor, d_side,
+                       wide ? kBktwKeys : kBktKeys);
+    if (wide)
+        hipLaunchKernelGGL(bkt_fill_kernel<true>, dim3((slots / 16 + 255) / 256), dim3(256), 0, stream, d_tiles, d_side, slots, last_real);
+    else
+        hipLaunchKernelGGL(bkt_fill_kernel<false>, dim3((slots / 16 + 255) / 256), dim3(256), 0, stream, d_tiles, d_side, slots, last_real);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2050,17 +2147,58 @@ static void launch_bkt_variant(dim3 grid, hipStream_t stream, const ScanItem* d_
                        d_bkt_sel, d_surv);
 }
 
+template <int NSP, bool NT, bool CHUNK, bool PROBE>
+static void launch_bktw_variant(dim3 grid, hipStream_t stream, const ScanItem* d_items, const int8_t* d_qtables,
+                                QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap, uint32_t R,
+                                const uint8_t* d_bktw_sel, unsigned long long* d_surv) {
+    auto k = &scan_i8_bktw_kernel<NSP, NT, CHUNK, PROBE>;
+    static std::atomic<uint64_t> done{0};
+    ensure_dynamic_lds(reinterpret_cast<const void*>(k), ScanCfg<16>::LDS_BYTES, done);
+    hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<16>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R,
+                       d_bktw_sel, d_surv);
+}
+
 // variant bits: [2] NT (non-temporal loads)  [3] CHUNK  [4] PROBE (ceiling diagnostic)
 // [5] split form (16x4, every run of the launch has ScanItem::split; not with [6]): 5 planes when d_plane_sel5 (the two
 //     deferred bytes and the slack of every table) is given, else 6 planes when d_plane_sel (the deferred byte of every
 //     table) is, else 7 (launch_plane_choice / launch_select_kth write both); d_surv: survivor counter or nullptr
 //     nib_ns = 8, 9 or 10 with d_nib_sel (ScanItem::split of every run points into the nibble-plane copy): the nibble form, before all of these
 //     bkt_nsp = 4..7 with d_bkt_sel (every run of the launch is a bucket-form run, LevelLaunch::bkt): the bucket form, before the nibble form
+//     bkt_free = 5, bkt_nsp = 3..6, d_bkt_sel = the wide form's choice bytes (LevelLaunch::bktw): the wide form, before all of these
 // [6] sibling-major 1-D launch (every run of the launch covers the same codes; see the kernel's decode).  Other bits: ignored.
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap,
                     uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel, unsigned long long* d_surv,
-                    const uint8_t* d_plane_sel5, const uint8_t* d_nib_sel, int nib_ns, const uint8_t* d_bkt_sel, int bkt_nsp) {
+                    const uint8_t* d_plane_sel5, const uint8_t* d_nib_sel, int nib_ns, const uint8_t* d_bkt_sel, int bkt_nsp, int bkt_free) {
+    if (bkt_free == 5) {
+        // a wide launch is never anything else: launch_level (qadc_capi.cpp) refuses one whose preconditions do not hold with an error
+        // status before it gets here, so a violation is a programming error and must not pass as a level that was silently not scanned
+        if (!(M == 16 && (variant & 32) && !(variant & 64) && d_bkt_sel && bkt_nsp >= 3 && bkt_nsp <= 6)) {
+            std::fprintf(stderr, "qadc: launch_scan_i8: a wide bucket launch without its preconditions (M %d, variant 0x%x, nsp %d)\n", M, variant, bkt_nsp);
+            std::abort();
+        }
+        const dim3 grid(wgs_per_item, nitems);
+#define QADC_BKTW_ARGS grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, d_bkt_sel, d_surv
+#define QADC_BKTW(NSP, PR)                                                        \
+    switch ((variant >> 2) & 3) {                                                 \
+        case 0: launch_bktw_variant<NSP, false, false, PR>(QADC_BKTW_ARGS); break; \
+        case 1: launch_bktw_variant<NSP, true, false, PR>(QADC_BKTW_ARGS); break;  \
+        case 2: launch_bktw_variant<NSP, false, true, PR>(QADC_BKTW_ARGS); break;  \
+        default: launch_bktw_variant<NSP, true, true, PR>(QADC_BKTW_ARGS); break;  \
+    }
+        if (bkt_nsp == 3) {
+            if (variant & 16) { QADC_BKTW(3, true) } else { QADC_BKTW(3, false) }
+        } else if (bkt_nsp == 4) {
+            if (variant & 16) { QADC_BKTW(4, true) } else { QADC_BKTW(4, false) }
+        } else if (bkt_nsp == 5) {
+            if (variant & 16) { QADC_BKTW(5, true) } else { QADC_BKTW(5, false) }
+        } else {
+            if (variant & 16) { QADC_BKTW(6, true) } else { QADC_BKTW(6, false) }
+        }
+#undef QADC_BKTW_ARGS
+#undef QADC_BKTW
+        return;
+    }
     if (M == 16 && (variant & 32) && !(variant & 64) && d_bkt_sel && bkt_nsp >= 4 && bkt_nsp <= 7) {
         const dim3 grid(wgs_per_item, nitems);
 #define QADC_BKT_ARGS grid, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R, d_bkt_sel, d_surv
@@ -2907,7 +3045,8 @@ void launch_start_scan_f32(int M, int sum_mode, const StartItem* d_items, int ni
 template <int BT>
 __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t* __restrict__ qt, QueryState* qs,
                                float qmax, int quant_mode, float* red /* [BT] LDS */, uint8_t* __restrict__ plane_sel,
-                               uint8_t* __restrict__ plane_sel5, uint8_t* __restrict__ nib_sel, uint8_t* __restrict__ bkt_sel) {
+                               uint8_t* __restrict__ plane_sel5, uint8_t* __restrict__ nib_sel, uint8_t* __restrict__ bkt_sel,
+                               uint8_t* __restrict__ bktw_sel) {
     const int t = threadIdx.x;
     float m = FLT_MAX;
     for (int i = t; i < table_dim_all; i += BT) m = fminf(m, tb[i]);
@@ -2932,7 +3071,7 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
         else o = (int8_t)(int)(quant_mode == 0 ? (v - qmin) / delta : (v - qmin) * scale);
         qt[i] = o;
     }
-    if (plane_sel || plane_sel5 || nib_sel || bkt_sel) {   // 16x4: the 6-, 5-plane, nibble and bucket forms' choices of each table
+    if (plane_sel || plane_sel5 || nib_sel || bkt_sel || bktw_sel) {   // 16x4: the 6-, 5-plane, nibble and bucket forms' choices of each table
         __syncthreads();
         for (int i = t; i < table_dim_all / 256; i += BT) {
             if (plane_sel) plane_sel[i] = (uint8_t)plane_choice(qt + (size_t)i * 256);
@@ -2943,6 +3082,7 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
             }
             if (nib_sel) plane_choice_nib(qt + (size_t)i * 256, nib_sel + (size_t)i * kNibSelBytes);
             if (bkt_sel) plane_choice_bkt(qt + (size_t)i * 256, bkt_sel + (size_t)i * kBktSelBytes);
+            if (bktw_sel) plane_choice_bktw(qt + (size_t)i * 256, bktw_sel + (size_t)i * kBktwSelBytes);
         }
     }
     if (t == 0) { qs->qmin = qmin; qs->flags |= flags; }   // keeps bit3 set by the pre-scan
@@ -2960,7 +3100,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
                                                         float* __restrict__ export_vals,
                                                         uint32_t* __restrict__ export_flags, uint32_t* __restrict__ front_out,
                                                         uint8_t* __restrict__ plane_sel, uint8_t* __restrict__ plane_sel5,
-                                                        uint8_t* __restrict__ nib_sel, uint8_t* __restrict__ bkt_sel) {
+                                                        uint8_t* __restrict__ nib_sel, uint8_t* __restrict__ bkt_sel,
+                                                        uint8_t* __restrict__ bktw_sel) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t s_prefix, s_k, s_hi, s_cnt;
     __shared__ float red[BT];
@@ -2987,7 +3128,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
                                         qs, FLT_MAX, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr,
                                         plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr,
                                         nib_sel ? nib_sel + (size_t)kNibSelBytes * q * (table_dim_all / 256) : nullptr,
-                                        bkt_sel ? bkt_sel + (size_t)kBktSelBytes * q * (table_dim_all / 256) : nullptr);
+                                        bkt_sel ? bkt_sel + (size_t)kBktSelBytes * q * (table_dim_all / 256) : nullptr,
+                                        bktw_sel ? bktw_sel + (size_t)kBktwSelBytes * q * (table_dim_all / 256) : nullptr);
         publish_front();
         return;
     }
@@ -3059,7 +3201,8 @@ __global__ __launch_bounds__(BT) void select_kth_kernel(const float* __restrict_
                                     qs, qmax, quant_mode, red, plane_sel ? plane_sel + (size_t)q * (table_dim_all / 256) : nullptr,
                                         plane_sel5 ? plane_sel5 + 2 * (size_t)q * (table_dim_all / 256) : nullptr,
                                         nib_sel ? nib_sel + (size_t)kNibSelBytes * q * (table_dim_all / 256) : nullptr,
-                                        bkt_sel ? bkt_sel + (size_t)kBktSelBytes * q * (table_dim_all / 256) : nullptr);
+                                        bkt_sel ? bkt_sel + (size_t)kBktSelBytes * q * (table_dim_all / 256) : nullptr,
+                                        bktw_sel ? bktw_sel + (size_t)kBktwSelBytes * q * (table_dim_all / 256) : nullptr);
     publish_front();
 }
 
@@ -3096,15 +3239,16 @@ void launch_prescan_minmax(const float* d_vals, uint32_t nvals, int nq, QuerySta
 void launch_select_kth(const float* d_fc, uint64_t fc_stride, const uint32_t* d_fc_init, int nq, uint32_t R, QueryState* d_qs,
                        int max_passes, float* d_ftables, int8_t* d_qtables, int table_dim_all, int quant_mode,
                        hipStream_t stream, float* export_vals, uint32_t* export_flags, uint32_t* d_front_out, int small_wg,
-                       uint8_t* d_plane_sel, uint8_t* d_plane_sel5, uint8_t* d_nib_sel, uint8_t* d_bkt_sel) {
+                       uint8_t* d_plane_sel, uint8_t* d_plane_sel5, uint8_t* d_nib_sel, uint8_t* d_bkt_sel,
+                       uint8_t* d_bktw_sel) {
     if (small_wg)
         hipLaunchKernelGGL((select_kth_kernel<256>), dim3(nq), dim3(256), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
                            d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel,
-                           d_plane_sel5, d_nib_sel, d_bkt_sel);
+                           d_plane_sel5, d_nib_sel, d_bkt_sel, d_bktw_sel);
     else
         hipLaunchKernelGGL((select_kth_kernel<1024>), dim3(nq), dim3(1024), 0, stream, d_fc, fc_stride, d_fc_init, R, d_qs, max_passes,
                            d_ftables, d_qtables, table_dim_all, quant_mode, export_vals, export_flags, d_front_out, d_plane_sel,
-                           d_plane_sel5, d_nib_sel, d_bkt_sel);
+                           d_plane_sel5, d_nib_sel, d_bkt_sel, d_bktw_sel);
 }
 
 // ---- stream-layout probe (qadc_stream_probe): does a dispatch that WAITS FOR CUs on stream A hold up stream B? ----

@@ -66,6 +66,21 @@ constexpr uint32_t kBktKeys = 65536;
 // The bucket form's choice bytes of one table: 4 bytes for each NSP = 4, 5, 6, 7 paid sub-quantizers at 4 * (NSP - 4): the
 // deferred set among sub-quantizers 4-15 as a 16-bit mask (low byte first), the slack c, 0.
 constexpr uint32_t kBktSelBytes = 16;
+// Wide blocks of the bucket copy.  From position bkt_wide_block = W on, a partition is cut into octave blocks [W 2^j, W 2^(j+1)),
+// j = 0, 1, ... (the last clipped at the partition's end), and an octave is grouped by the 20-bit key = code bytes 0 and 1 and the
+// low nibble of byte 2 (sub-quantizers 0-4); padding as in a narrow block.  Wide tiles live in an allocation of their own: 11 nibble
+// planes (sub-quantizers 5-15, the same in-plane layout), then the id plane of the narrow tile (uint16 = sub-quantizers 0-3 of the
+// 16-slot group), then one byte per group, sub-quantizer 4 of the group.  The side array has the narrow copy's layout.  A range
+// that wide octaves cover has no slots in the narrow copy (its narrow blocks are empty); an octave whose padded slots exceed
+// bkt_wide_max_pad x its codes has no slots in the wide copy, and narrow blocks instead.
+constexpr uint32_t kBktwPlanes = 11;
+constexpr uint32_t kBktwIdOff = kBktwPlanes * (kSplitTile / 2);                // byte offset of the uint16 id plane in a wide tile
+constexpr uint32_t kBktwId4Off = kBktwIdOff + kSplitTile / 16 * 2;             // ... and of the byte plane of sub-quantizer 4
+constexpr uint32_t kBktwTileBytes = kBktwId4Off + kSplitTile / 16;
+constexpr uint32_t kBktwKeys = 1u << 20;
+// The wide form's choice bytes of one table: 4 bytes for each NSP = 3, 4, 5, 6 paid sub-quantizers at 4 * (NSP - 3): the deferred
+// set among sub-quantizers 5-15 as a 16-bit mask (low byte first), the slack c, 0.
+constexpr uint32_t kBktwSelBytes = 16;
 
 constexpr int kMaxLevels = 16;  // bound levels per query
 
@@ -108,6 +123,9 @@ struct LevelLaunch {
     int bkt = 0;           // 4, 5, 6 or 7: split, every run covers whole blocks of its partition's bucket copy (bkt_run_ok): scan_i8_bkt_kernel
                            // streams that many of sub-quantizers 4-15 (preferred over the nibble form; nib is 0 then); 0: not.  The runs
                            // then count slots (ScanItem::n) and wgs derives from them; codes and maxn stay the codes the runs cover
+    int bktw = 0;          // 3, 4, 5 or 6: split, every run covers whole wide octaves of its partition's bucket copy (bktw_run_ok): the wide
+                           // form of scan_i8_bkt_kernel streams that many of sub-quantizers 5-15 (preferred over the narrow form; bkt and
+                           // nib are 0 then); the runs count slots as in a narrow bucket launch
 };
 
 // What the planner reads of a partition (the index's Part derives from it: one partition table, no copy).
@@ -126,6 +144,11 @@ struct LevelPart {
     uint32_t first_pos = 0;        // global position of local code 0
     uint32_t start_n = 0;
     uint32_t key_base = 0;
+    uint8_t* d_bktw = nullptr;      // 16x4: the wide tiles of the bucket copy (kBktwTileBytes per tile), or null
+    uint8_t* d_bktw_side = nullptr; // ... and their side array (kBktSideBytes per tile)
+    uint64_t bktw_block = 0;        // W: octave j >= 0 covers positions [W 2^j, W 2^(j+1)) (a power of two, a multiple of bkt_block)
+    std::vector<uint64_t> bktw_off; // [octaves + 1] first slot of every octave in the wide copy (multiples of kSplitTile), and its
+                                    // slots; an octave without slots fell back to narrow blocks
 };
 
 // ... of the index's options (qadc_index has the meaning of each), and of the batch (Slot has them).  Aggregates, in this order.
@@ -145,6 +168,9 @@ struct LevelOptions {
     // the bucket form: runs of at least bkt_min_run codes that cover whole blocks of a bucket copy stream 7 of sub-quantizers 4-15,
     // those of at least bkt6_min_run 6, bkt5_min_run 5, bkt4_min_run 4 (the fewest whose threshold the launch's shortest run reaches); 0 = never
     uint64_t bkt_min_run = 0, bkt6_min_run = 0, bkt5_min_run = 0, bkt4_min_run = 0;
+    // the wide form: runs of at least bktw_min_run codes that cover whole wide octaves stream 6 of sub-quantizers 5-15, those of at
+    // least bktw5_min_run 5, bktw4_min_run 4, bktw3_min_run 3 (as above); 0 = never
+    uint64_t bktw_min_run = 0, bktw5_min_run = 0, bktw4_min_run = 0, bktw3_min_run = 0;
 };
 struct LevelBatch {
     int nq, ma;
@@ -234,6 +260,39 @@ inline int bkt_planes(const LevelOptions& o, uint64_t minn) {
            : o.bkt6_min_run != 0 && minn >= o.bkt6_min_run ? 6 : 7;
 }
 
+// The wide octaves of a partition: octave j = 0, 1, ... covers positions [W << j, min(W << (j + 1), n)).
+inline size_t bktw_octaves(const LevelPart& pt) { return pt.bktw_off.empty() ? 0 : pt.bktw_off.size() - 1; }
+inline bool bktw_is_wide(const LevelPart& pt, size_t j) { return pt.bktw_off[j + 1] > pt.bktw_off[j]; }
+// Does [b0, b0 + len) meet an octave that is stored wide?  Such a range has no narrow blocks: no narrow bucket run may cover it.
+inline bool bktw_meets(const LevelPart& pt, uint64_t b0, uint64_t len) {
+    if (!pt.d_bktw || !pt.bktw_block) return false;
+    for (size_t j = 0; j < bktw_octaves(pt); ++j)
+        if (bktw_is_wide(pt, j) && b0 < std::min<uint64_t>(pt.bktw_block << (j + 1), pt.n) && b0 + len > (pt.bktw_block << j)) return true;
+    return false;
+}
+// May the run [b0, b0 + len) take the wide form?  It starts on an octave, ends on one or at the partition's end, every octave it
+// covers is stored wide, and it has at least bktw_min_run codes.  first / last: the octaves it covers, [first, last).
+inline bool bktw_run_ok(const LevelPart& pt, const LevelOptions& o, uint64_t b0, uint64_t len, size_t* first = nullptr, size_t* last = nullptr) {
+    if (!pt.d_bktw || !pt.d_bktw_side || !pt.bktw_block || o.bktw_min_run == 0 || len < o.bktw_min_run || len == 0) return false;
+    const size_t noct = bktw_octaves(pt);
+    size_t j0 = noct, j1 = 0;                                // (not found: j0 >= noct, j1 <= j0)
+    for (size_t j = 0; j < noct; ++j) {
+        if (b0 == (pt.bktw_block << j)) j0 = j;
+        if (b0 + len == std::min<uint64_t>(pt.bktw_block << (j + 1), pt.n)) j1 = j + 1;
+    }
+    if (j0 >= noct || j1 > noct || j1 <= j0) return false;
+    for (size_t j = j0; j < j1; ++j)
+        if (!bktw_is_wide(pt, j)) return false;
+    if (first) *first = j0;
+    if (last) *last = j1;
+    return true;
+}
+// Paid planes of a wide launch whose shortest run has minn codes
+inline int bktw_planes(const LevelOptions& o, uint64_t minn) {
+    return o.bktw3_min_run != 0 && minn >= o.bktw3_min_run ? 3 : o.bktw4_min_run != 0 && minn >= o.bktw4_min_run ? 4
+           : o.bktw5_min_run != 0 && minn >= o.bktw5_min_run ? 5 : 6;
+}
+
 // Can some run of a partition with a bucket copy still take the nibble form?  Exact for an index of ONE partition, whose
 // scan order always starts at the partition's first code (qadc_index_finalize skips the nibble-plane copy when this says no);
 // with more partitions the cuts depend on the probe lists, and the answer is yes.  Follows the cuts of plan_levels.
@@ -252,6 +311,7 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
     std::vector<std::vector<const uint8_t*>> per_level_nib(kMaxLevels);   // beside every run: its tile in the nibble-plane copy, or nullptr
     struct BktRun { const uint8_t* tiles; const uint8_t* side; uint64_t slots; };
     std::vector<std::vector<BktRun>> per_level_bkt(kMaxLevels);           // ... and in the bucket copy (tiles == nullptr: the run does not qualify)
+    std::vector<std::vector<BktRun>> per_level_bktw(kMaxLevels);          // ... and in its wide tiles
     const int k0 = (b.mode != 1 && o.head_level > 0) ? o.head_level : 0;   // levels < k0 belong to the head launch
     plan.head_codes = k0 ? L[k0] : 0;
     plan.fc_init.assign(2 * (size_t)nq, 0);
@@ -349,7 +409,16 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
                     // ... and, where the partition has a nibble-plane copy as well, the nibble form (same tiles)
                     per_level_nib[k].push_back(it.split && pt.d_nib ? pt.d_nib + b0 / kSplitTile * (uint64_t)kNibTileBytes : nullptr);
                     BktRun br{nullptr, nullptr, 0};
-                    if (it.split && bkt_run_ok(pt, o, b0, len)) {
+                    BktRun bw{nullptr, nullptr, 0};
+                    size_t oc0 = 0, oc1 = 0;
+                    if (it.split && bktw_run_ok(pt, o, b0, len, &oc0, &oc1)) {
+                        const uint64_t s0 = pt.bktw_off[oc0], s1 = pt.bktw_off[oc1];
+                        if (s1 - s0 <= 0xffffffffull && s0 % kSplitTile == 0 && s1 % kSplitTile == 0)
+                            bw = BktRun{pt.d_bktw + s0 / kSplitTile * (uint64_t)kBktwTileBytes,
+                                        pt.d_bktw_side + s0 / kSplitTile * (uint64_t)kBktSideBytes, s1 - s0};
+                    }
+                    per_level_bktw[k].push_back(bw);
+                    if (it.split && bkt_run_ok(pt, o, b0, len) && !bktw_meets(pt, b0, len)) {
                         const size_t blk0 = (size_t)(b0 / pt.bkt_block);
                         const size_t blk1 = std::min<size_t>((size_t)((b0 + len + pt.bkt_block - 1) / pt.bkt_block), pt.bkt_off.size() - 1);
                         const uint64_t s0 = pt.bkt_off[blk0], s1 = pt.bkt_off[blk1];
@@ -385,9 +454,9 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
             const int small = cls == 0 ? 1 : 0;
             uint64_t maxn = 0, minn = ~0ull, codes = 0;
             size_t cnt = 0;
-            bool same = true, all_nib = true, all_bkt = true;
+            bool same = true, all_nib = true, all_bkt = true, all_bktw = true;
             std::vector<const uint8_t*> nibs;
-            std::vector<BktRun> bkts;
+            std::vector<BktRun> bkts, bktws;
             for (size_t r = 0; r < per_level[k].size(); ++r) {
                 const ScanItem& it = per_level[k][r];
                 if ((it.n < o.small_run) != (small == 1)) continue;
@@ -405,6 +474,8 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
                 nibs.push_back(per_level_nib[k][r]);
                 all_bkt = all_bkt && per_level_bkt[k][r].tiles != nullptr;
                 bkts.push_back(per_level_bkt[k][r]);
+                all_bktw = all_bktw && per_level_bktw[k][r].tiles != nullptr;
+                bktws.push_back(per_level_bktw[k][r]);
             }
             if (!cnt) continue;
             const uint64_t nvec = (maxn + cpl - 1) / cpl;
@@ -423,9 +494,11 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
                      : o.nib8_min_run != 0 && minn >= o.nib8_min_run    ? 8
                      : o.nib_min_run != 0 && minn >= o.nib_min_run      ? (o.nib_ns == 10 ? 10 : 9)
                                                                         : 0;
-            ll.bkt = ll.split && all_bkt ? bkt_planes(o, minn) : 0;
+            ll.bktw = ll.split && all_bktw ? bktw_planes(o, minn) : 0;
+            ll.bkt = ll.split && all_bkt && !ll.bktw ? bkt_planes(o, minn) : 0;
             uint64_t max_slots = 0;
-            if (ll.bkt) {                                                // the launch reads the bucket copy: its runs count slots
+            if (ll.bktw) bkts.swap(bktws);                               // the launch reads the wide tiles: the same bookkeeping
+            if (ll.bkt || ll.bktw) {                                                // the launch reads the bucket copy: its runs count slots
                 ll.nib = 0;
                 for (size_t r = 0; r < cnt; ++r) {
                     ScanItem& it = plan.all_items[off + r];
@@ -441,7 +514,7 @@ BatchPlan plan_levels(const Part* parts, size_t nparts, const LevelOptions& o, c
             ll.wgs = ll.mq       ? wgs_mq(o, maxn, nvec, cnt)
                      : ll.shared ? wgs_shared(o, maxn, nvec)
                      : ll.small  ? wgs_small(nvec, cnt)
-                     : ll.bkt    ? wgs_streaming(o, max_slots, (max_slots + cpl - 1) / cpl, cnt, true)
+                     : ll.bkt || ll.bktw ? wgs_streaming(o, max_slots, (max_slots + cpl - 1) / cpl, cnt, true)
                                  : wgs_streaming(o, maxn, nvec, cnt, ll.split);
             ll.codes = codes;
             plan.launches.push_back(ll);
@@ -466,7 +539,7 @@ inline bool nib_still_needed(const LevelPart& pt, const LevelOptions& o, bool on
         for (uint64_t b0 = prev; b0 < cut;) {
             const uint64_t len = std::min<uint64_t>(cut - b0, 1ull << 31);
             if (len >= std::max<uint64_t>(nib_min, std::max<uint64_t>(o.split_min_run, o.small_run)) && b0 % kSplitTile == 0 &&
-                !bkt_run_ok(pt, o, b0, len))
+                !(bkt_run_ok(pt, o, b0, len) && !bktw_meets(pt, b0, len)) && !bktw_run_ok(pt, o, b0, len))
                 return true;
             b0 += len;
         }

@@ -32,7 +32,7 @@ SYMBOLS = [
     "qadc_scan_i8_candidates", "qadc_scan_start", "qadc_query_scan_submit", "qadc_prescan_submit",
     "qadc_prescan_collect", "qadc_query_scan_submit_prescanned",
     "qadc_query_scan_collect", "qadc_index_set_pq", "qadc_index_set_rotation", "qadc_index_set_coarse", "qadc_search", "qadc_search_submit",
-    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6", "qadc_index_set_split5", "qadc_index_set_split_nib", "qadc_nib_choice", "qadc_index_set_split_bkt", "qadc_bkt_choice", "qadc_index_bkt_info", "qadc_index_bkt_read",
+    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6", "qadc_index_set_split5", "qadc_index_set_split_nib", "qadc_nib_choice", "qadc_index_set_split_bkt", "qadc_bkt_choice", "qadc_index_bkt_info", "qadc_index_bkt_read", "qadc_index_set_split_bkt_wide", "qadc_bktw_choice", "qadc_index_bktw_info", "qadc_index_bktw_read",
     "qadc_dist_unique_id", "qadc_dist_init", "qadc_dist_collect", "qadc_dist_shutdown", "qadc_dist_merge_blocks", "qadc_dist_merge_blocks_host",
     "qadc_dist_init_transport", "qadc_dist_init_loopback", "qadc_shm_transport_open", "qadc_shm_transport_allgather", "qadc_shm_transport_allgather_host",
     "qadc_shm_transport_close", "qadc_shm_transport_error", "qadc_slot_assign", "qadc_slot_qtables", "qadc_place_partitions",
@@ -80,7 +80,11 @@ class Profile(C.Structure):
                 ("bkt_copy_padded_out", C.c_uint64), ("bkt_launches", C.c_uint64), ("bkt_codes", C.c_uint64),
                 ("bkt_slots", C.c_uint64), ("bkt_survivors", C.c_uint64),
                 ("bkt4_launches", C.c_uint64), ("bkt5_launches", C.c_uint64), ("bkt6_launches", C.c_uint64),
-                ("bkt7_launches", C.c_uint64)]
+                ("bkt7_launches", C.c_uint64),
+                ("bktw_copy_bytes", C.c_uint64), ("bktw_copy_slots", C.c_uint64), ("bktw_copy_fallback", C.c_uint64),
+                ("bktw_launches", C.c_uint64), ("bktw_codes", C.c_uint64), ("bktw_slots", C.c_uint64),
+                ("bktw_survivors", C.c_uint64), ("bktw3_launches", C.c_uint64), ("bktw4_launches", C.c_uint64),
+                ("bktw5_launches", C.c_uint64), ("bktw6_launches", C.c_uint64)]
 
 
 QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h
@@ -134,6 +138,10 @@ def lib():
         L.qadc_bkt_choice.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.qadc_index_bkt_info.argtypes = [C.c_void_p, C.c_int, u64p, u64p, u64p]
         L.qadc_index_bkt_read.argtypes = [C.c_void_p, C.c_int, u64p, u8p, u8p]
+        L.qadc_index_set_split_bkt_wide.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double]
+        L.qadc_bktw_choice.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.qadc_index_bktw_info.argtypes = [C.c_void_p, C.c_int, u64p, u64p, u64p]
+        L.qadc_index_bktw_read.argtypes = [C.c_void_p, C.c_int, u64p, u8p, u8p]
         L.qadc_index_read_codes.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u8p]
         L.qadc_query_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, C.c_int, u32p, i8p, i32p, i32p,
                                       f32p, f32p, i8p]
@@ -308,6 +316,15 @@ def nib_choice(qtables, device=0):
     qt = np.ascontiguousarray(qtables, np.int8).reshape(-1, 256)
     out = np.zeros((qt.shape[0], 3, 4), np.uint8)
     _check(lib().qadc_nib_choice(int(device), qt.ctypes.data_as(C.c_void_p), int(qt.shape[0]), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def bktw_choice(qtables, device=0):
+    """qadc_bktw_choice: the wide bucket form's choice bytes of 16x4 int8 tables [..., 16, 16] as the device computes them ->
+    uint8 [ntables, 4, 4]: for NSP = 3, 4, 5, 6 the deferred mask among sub-quantizers 5-15 (two bytes, low first), the slack, 0."""
+    qt = np.ascontiguousarray(qtables, np.int8).reshape(-1, 256)
+    out = np.zeros((qt.shape[0], 4, 4), np.uint8)
+    _check(lib().qadc_bktw_choice(int(device), qt.ctypes.data_as(C.c_void_p), int(qt.shape[0]), out.ctypes.data_as(C.c_void_p)))
     return out
 
 
@@ -762,6 +779,31 @@ class Index:
         or off and set bkt_block before finalize."""
         _check(lib().qadc_index_set_split_bkt(self._h, int(bkt_min_run), int(bkt_block), int(min_run6), int(min_run5),
                                               int(min_run4), float(bkt_max_pad)))
+
+    def set_split_bkt_wide(self, wide_block, min_run=0, min_run5=0, min_run4=0, min_run3=0, wide_max_pad=0.0):
+        """Wide blocks of the bucket copy (16x4): finalize stores positions from wide_block = W on (0 = none; a power of two, a
+        multiple of bkt_block) in octave blocks [W 2^j, W 2^(j+1)) grouped by the codes' first 20 bits, unless padding inflates an
+        octave beyond wide_max_pad x its codes (0 = keep); split launches whose runs all have >= min_run codes and cover whole wide
+        octaves stream 6 of sub-quantizers 5-15, those with >= min_run5 / min_run4 / min_run3 codes 5 / 4 / 3 (0 = never);
+        preferred to the narrow form; results do not change.  Set wide_block and wide_max_pad before finalize."""
+        _check(lib().qadc_index_set_split_bkt_wide(self._h, int(wide_block), int(min_run), int(min_run5), int(min_run4),
+                                                   int(min_run3), float(wide_max_pad)))
+
+    def bktw_copy(self, part):
+        """Diagnostic: partition part's wide octaves, or None.  -> dict(block = W, off uint64 [octaves + 1], tiles uint8
+        [ntiles, 93184], codes uint8 [slots, 8], perm uint32 [slots]) (include/qadc.h: qadc_index_bktw_read)."""
+        block, noct, slots = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().qadc_index_bktw_info(self._h, part, C.byref(block), C.byref(noct), C.byref(slots)))
+        if not block.value:
+            return None
+        nt = slots.value // 16384
+        off = np.zeros(noct.value + 1, np.uint64)
+        tiles = np.zeros((nt, 93184), np.uint8)
+        side = np.zeros((nt, 196608), np.uint8)
+        _check(lib().qadc_index_bktw_read(self._h, part, _p(off, u64p), _p(tiles, u8p), _p(side, u8p)))
+        codes = np.ascontiguousarray(side[:, :131072]).reshape(-1, 8)
+        perm = np.ascontiguousarray(side[:, 131072:]).view(np.uint32).reshape(-1)
+        return {"block": block.value, "off": off, "tiles": tiles, "codes": codes, "perm": perm}
 
     def bkt_copy(self, part):
         """Diagnostic: partition part's bucket copy, or None.  -> dict(block, off uint64 [blocks + 1], tiles uint8

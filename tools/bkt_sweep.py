@@ -1,5 +1,5 @@
 """Same-process sweep behind the bucket form's defaults (profiles/r11_bkt_ab.txt).
-usage: python tools/bkt_sweep.py [reps=2] [codes=1e9]
+usage: python tools/bkt_sweep.py [reps=2] [codes=1e9] [wide=W]
 
 One index of the headline's list and mode (bench.py's one-query-per-pass options, 32-query steps pipelined three deep) holding
 BOTH the bucket copy (blocks of 2^25) and the nibble-plane copy: it is finalized with bkt_min_run above every run (600 Mi), so
@@ -7,7 +7,12 @@ that finalize still builds the nibble-plane copy, and the thresholds are moved a
 order alternated: "off" = the nibble defaults (9 / 9 / 8 streamed); "pXYZ" = X, Y and Z paid planes at the levels from 2^25, 2^27
 and 2^29 (runs of 96, 384 and 421 Mi codes) with bkt_min_run = 2^25; "b27:pYZ" = bkt_min_run = 2^27 (the level from 2^25 keeps 9
 nibble planes).  A first section times the PROBE builds (variant bit 16) of "off" and of two arms.  One JSON line per (section,
-round, arm): ms per step and the library's bkt_* and nib_* counters per step; a last line has the copies' sizes and the finalize time."""
+round, arm): ms per step and the library's bkt_* and nib_* counters per step; a last line has the copies' sizes and the finalize time.
+
+With a third argument wide=W (W = 2^27 or 2^29; profiles/r12_bktw_ab.txt) the index is the default one with wide blocks from W on
+(a range stored wide has no narrow blocks and the index no nibble-plane copy, so the narrow arms cannot run beside them): arms
+"w:pYZ" = Y and Z paid planes of rows 5-15 at the levels from 2^27 and 2^29 (W = 2^29: "w:pZ", the level from 2^27 keeps the narrow
+form's 5), the level from 2^25 the narrow form's 6; the PROBE section times "w:p44".  The lines carry the bktw_* counters as well."""
 import json
 import os
 import sys
@@ -38,6 +43,18 @@ def arm_thresholds(name):
     return lo, t[6], t[5], t[4]
 
 
+def wide_thresholds(name):
+    """"w:pYZ" / "w:pZ" -> (min_run5, min_run4, min_run3): thresholds that the level's runs and the longer ones reach."""
+    planes = [int(c) for c in name.split("p")[1]]
+    planes = [planes[0]] * (2 - len(planes)) + planes            # per level from 2^27, 2^29 (non-increasing)
+    reach = (128 * MI, 400 * MI)
+    t = {}
+    for want in (5, 4, 3):
+        first = [i for i, p in enumerate(planes) if p <= want]
+        t[want] = reach[first[0]] if first else 0
+    return t[5], t[4], t[3]
+
+
 def main():
     import torch
     import pyqadc
@@ -63,33 +80,46 @@ def main():
         while pending:
             idx.collect(pending.pop(0))
 
+    wide = int(float(sys.argv[3].split("=")[1])) if len(sys.argv) > 3 and sys.argv[3].startswith("wide=") else 0
     idx = pyqadc.Index(M, 0)
-    idx.set_split_bkt(600 * MI, 1 << 25)
+    if wide:
+        idx.set_split_bkt_wide(wide, min(max(wide, 128 * MI), 400 * MI), 0, 0, 0)
+    else:
+        idx.set_split_bkt(600 * MI, 1 << 25)
+        idx.set_split_bkt_wide(0)
     idx.add_partition_synthetic_shard(n, 0, n, bench.SEED, max(1, int(np.float32(n) * np.float32(bench.KEEP))))
     t0 = time.perf_counter()
     idx.finalize(bench.KEEP)
     finalize_s = time.perf_counter() - t0
     idx.set_option("profile", 1)
     bench.set_mode(idx, bench.MODE_ONE_QUERY_PER_PASS)
-    sizes = {k: int(idx.profile()[k]) for k in ("split_copy_bytes", "nib_copy_bytes", "bkt_copy_bytes", "bkt_copy_slots")}
+    sizes = {k: int(idx.profile()[k]) for k in ("split_copy_bytes", "nib_copy_bytes", "bkt_copy_bytes", "bkt_copy_slots",
+                                               "bktw_copy_bytes", "bktw_copy_slots", "bktw_copy_fallback")}
 
     def measure(section, rep, name, variant):
         idx.set_option("variant", variant)
-        lo, t6, t5, t4 = arm_thresholds(name)
-        idx.set_split_bkt(lo, 0, t6, t5, t4)
+        if wide:
+            idx.set_split_bkt_wide(wide, min(max(wide, 128 * MI), 400 * MI), *wide_thresholds(name))
+        else:
+            lo, t6, t5, t4 = arm_thresholds(name)
+            idx.set_split_bkt(lo, 0, t6, t5, t4)
         run(idx, warmup)
         idx.profile_reset()
         t0 = time.perf_counter()
         run(idx, steps)
         ms = (time.perf_counter() - t0) * 1e3 / steps
         pr = idx.profile()
-        keys = ("bkt_launches", "bkt_codes", "bkt_slots", "bkt_survivors", "nib_codes", "nib_survivors", "nib8_codes", "nib8_survivors")
+        keys = ("bkt_launches", "bkt_codes", "bkt_slots", "bkt_survivors", "nib_codes", "nib_survivors", "nib8_codes", "nib8_survivors",
+                "bktw_launches", "bktw_codes", "bktw_slots", "bktw_survivors")
         print(json.dumps({"section": section, "round": rep, "arm": name, "ms_per_step": round(ms, 4),
                           **{k + "_per_step": int(pr[k] // steps) for k in keys}}), flush=True)
 
     probe = ["off", "p655", "p654"]
     arms = ["off", "p777", "p666", "p665", "p655", "p654", "p555", "p554", "p544", "p444", "p755", "p765",
             "b27:p66", "b27:p65", "b27:p55", "b27:p54"]
+    if wide:
+        probe = ["w:p44"] if wide <= 128 * MI else ["w:p4"]
+        arms = ["w:p66", "w:p65", "w:p55", "w:p54", "w:p44", "w:p43", "w:p33"] if wide <= 128 * MI else ["w:p6", "w:p5", "w:p4", "w:p3"]
     for rep in range(reps):
         for name in (probe if rep % 2 == 0 else probe[::-1]):
             measure("probe", rep, name, 0x0d | 16)

@@ -1001,9 +1001,44 @@ int qadc_adc_filter_destroy(qadc_adc_filter* f);
  * index destroyed; one filter may be set on several indexes of its device.  Applied in the scan kernel in front of the emit of every
  * level launch, so levels, bounds, re-runs, sub-batches and both finishes (qadc_adc_index_set_finish) hold as they are on the reduced
  * database.  qadc_adc_index_add_vectors* and _remove_labels* are legal while a filter is set: the filter is about keys, not rows, and
- * stays as it is.  QADC_E_ARG: idx NULL, a filter of another device.  Not per query of a batch, and not on the int8 4-bit engine
- * (qadc_query_scan, qadc_search), whose users filter through a view (qadc_adc_index_create_view). */
+ * stays as it is.  QADC_E_ARG: idx NULL, a filter of another device.  This filter holds for every query of a batch; the *_filtered
+ * calls below add one per query and compose with it.  Not on the int8 4-bit engine (qadc_query_scan, qadc_search), whose users filter
+ * through a view (qadc_adc_index_create_view). */
 int qadc_adc_index_set_filter(qadc_adc_index* idx, const qadc_adc_filter* f);
+
+/* ---- one filter per query of a batch ----
+ * The _filtered form of a scanning call takes the arguments of its plain form and filters [nq] in HOST memory (in the _device forms
+ * too: the call uploads one small table entry per query next to assign), filters[q] the filter of query q or NULL for none.  A row is
+ * emitted for query q iff it passes the index's filter (qadc_adc_index_set_filter), if one is set, AND filters[q], if that is not NULL:
+ * for every query the outputs are those of the definition above on the partitions from which the rows dropped for THAT query have been
+ * deleted — the standing use is an index-wide EXCLUDE of tombstones with a per-query ALLOW of a tenant's keys.  One filter may stand at
+ * any number of positions; both modes and empty sets mix freely in a batch.  filters NULL, or every entry NULL, is the plain call: the
+ * same kernels are launched and the same outputs returned, bit for bit.  The calls are synchronous and take no use count: a filter
+ * need only stay alive for the call, and qadc_adc_filter_destroy never fails because of one.  Levels, bounds, re-runs, sub-batches of
+ * the table budget and both finishes hold per query as they are; qadc_adc_index_add_vectors* and _remove_labels* between calls are
+ * legal.  QADC_E_ARG before the first HIP call: an entry that is not NULL and lies on another device than the index; every other
+ * argument is checked and refused as by the plain form.  Every code is still read, nq distinct wide filters are nq bitmaps in device
+ * memory (they are the caller's), and there is no such form on the int8 4-bit engine or on sharded / multi-GPU indexes. */
+int qadc_adc_query_scan_filtered(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
+                                 uint32_t* keys, float* values, int32_t* sizes, const qadc_adc_filter* const* filters);
+/* qadc_adc_query_scan_device with filters [nq] (host memory). */
+int qadc_adc_query_scan_device_filtered(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, int R,
+                                        int sum_mode, uint32_t* d_keys, float* d_values, int32_t* d_sizes,
+                                        const qadc_adc_filter* const* filters);
+/* qadc_adc_query_scan_candidates with filters [nq]: every query's stream holds the pushes on the database reduced for that query. */
+int qadc_adc_query_scan_candidates_filtered(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R,
+                                            int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals,
+                                            uint64_t* offsets, const qadc_adc_filter* const* filters);
+/* qadc_adc_search with filters [nq]; filters[q] belongs to queries[q] whatever sub-batches the table budget cuts the call into. */
+int qadc_adc_search_filtered(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,
+                             uint32_t* keys, float* values, int32_t* sizes, int32_t* assign_out, const qadc_adc_filter* const* filters);
+/* qadc_adc_search_device with filters [nq] (host memory). */
+int qadc_adc_search_device_filtered(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int R, int table_form, int sum_mode,
+                                    uint32_t* d_keys, float* d_values, int32_t* d_sizes, const qadc_adc_filter* const* filters);
+/* qadc_adc_search_candidates with filters [nq]. */
+int qadc_adc_search_candidates_filtered(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,
+                                        uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets,
+                                        int32_t* assign_out, const qadc_adc_filter* const* filters);
 
 /* ---- exact re-ranking: the vectors on the GPU, candidates reordered by L2 ----
  * Both engines rank by a quantized distance.  A refine store keeps the original vectors in device memory, and a rerank call reorders

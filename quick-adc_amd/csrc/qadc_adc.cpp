@@ -152,17 +152,20 @@ int check_query_args(const qadc_adc_index* idx, int nq, int ma, const int32_t* a
 // Where the device finish leaves the heaps' arrays of a batch: device memory, keys / values [nq][R], sizes [nq].
 struct DeviceOut { uint32_t* keys; float* values; int32_t* sizes; };
 
+// A filter as the kernels read it — the index's, or the table entry of one query of a *_filtered call; none (bitmap null) for NULL.
+ScanFilter scan_filter(const qadc_adc_filter* f) { return f ? ScanFilter{f->bitmap, f->span.lo, f->span.last, f->mode} : ScanFilter{}; }
+
 // The database as the scan launcher takes it: the owned codes, or the partition table of a view.
 ScanDb scan_db(const qadc_adc_index* idx) {
-    ScanFilter filter;
-    if (const qadc_adc_filter* f = idx->filter) filter = ScanFilter{f->bitmap, f->span.lo, f->span.last, f->mode};
+    const ScanFilter filter = scan_filter(idx->filter);
     if (idx->src) return ScanDb{idx->nsq, idx->centroids, Db{}, idx->d_parts4.p, filter};
     return ScanDb{idx->nsq, idx->centroids, Db{idx->codes.p, idx->d_off.p, idx->labeled == 1 ? idx->labels.p : nullptr, idx->d_lab_off.p}, nullptr,
                   filter};
 }
 
 // One batch on its way through scan_batch: the plan, where the batch lies in the staging buffers idx->h_in / idx->d_in, uploaded in one copy —
-//   bound (FLT_MAX) | count (0) | region sizes | region bases | assign | items | tables (the caller's, unless already on the device)
+//   bound (FLT_MAX) | count (0) | region sizes | region bases | assign | items | query filters (a *_filtered call with one at least) |
+//   tables (the caller's, unless already on the device)
 // of which the first four, bytes [0, o_assign), are the state a re-run writes again — and what the levels left.
 struct Batch {
     Plan plan;
@@ -173,6 +176,8 @@ struct Batch {
     const Item* d_items;
     const float* d_tables;
     Emit emit;                      // the regions: count, base and cap lie in d_in, vals / keys / sidx are set by every attempt
+    const ScanFilter* d_qfilters = nullptr;   // [nq] the filters of the batch's queries (the *_filtered calls), behind the items in d_in: outside
+                                              // the state bytes, so every re-run scans under the same table.  Null: no query has one
     std::vector<uint32_t> stored;   // [nq] candidates each query's region holds after the levels (n_stored in all)
 };
 
@@ -191,8 +196,15 @@ void fill_state(qadc_adc_index* idx, Batch& b) {
     }
 }
 
-// Lays the batch out and enqueues its upload.  d_ready: the tables are in device memory already (tables is null then).
-int stage_batch(qadc_adc_index* idx, Batch& b, int nq, int ma, const int32_t* assign, const float* tables, const float* d_ready) {
+// The filters of queries [0, nq) hold one at least.
+bool any_filter(const qadc_adc_filter* const* filters, int nq) {
+    return filters && std::any_of(filters, filters + nq, [](const qadc_adc_filter* f) { return f != nullptr; });
+}
+
+// Lays the batch out and enqueues its upload.  d_ready: the tables are in device memory already (tables is null then).  qfilters: the
+// filters of the batch's nq queries, one of them at least not null, or null.
+int stage_batch(qadc_adc_index* idx, Batch& b, int nq, int ma, const int32_t* assign, const float* tables, const float* d_ready,
+                const qadc_adc_filter* const* qfilters) {
     const std::vector<Item>& items = b.plan.items;
     const size_t table_bytes = d_ready ? 0 : (size_t)nq * ma * idx->nsq * idx->centroids * 4;
     b.o_count = align_up((size_t)nq * 4, 256);
@@ -200,7 +212,8 @@ int stage_batch(qadc_adc_index* idx, Batch& b, int nq, int ma, const int32_t* as
     b.o_base = b.o_cap + align_up((size_t)nq * 4, 256);
     b.o_assign = b.o_base + align_up((size_t)nq * 8, 256);
     const size_t o_items = b.o_assign + align_up((size_t)nq * ma * 4, 256);
-    const size_t o_tables = o_items + align_up(items.size() * sizeof(Item), 256);
+    const size_t o_qfilters = o_items + align_up(items.size() * sizeof(Item), 256);
+    const size_t o_tables = o_qfilters + (qfilters ? align_up((size_t)nq * sizeof(ScanFilter), 256) : 0);
     const size_t in_bytes = o_tables + table_bytes;
     HIPCHECK(idx->h_in.ensure(std::max<size_t>(in_bytes, 256)));
     HIPCHECK(idx->d_in.ensure(std::max<size_t>(in_bytes, 256)));
@@ -208,6 +221,11 @@ int stage_batch(qadc_adc_index* idx, Batch& b, int nq, int ma, const int32_t* as
     fill_state(idx, b);
     std::memcpy(h + b.o_assign, assign, (size_t)nq * ma * 4);
     if (!items.empty()) std::memcpy(h + o_items, items.data(), items.size() * sizeof(Item));
+    if (qfilters) {
+        ScanFilter* table = reinterpret_cast<ScanFilter*>(h + o_qfilters);
+        for (int q = 0; q < nq; ++q) table[q] = scan_filter(qfilters[q]);
+        b.d_qfilters = reinterpret_cast<const ScanFilter*>(d + o_qfilters);
+    }
     if (table_bytes) std::memcpy(h + o_tables, tables, table_bytes);
     b.d_bound = reinterpret_cast<float*>(d);
     b.d_assign = reinterpret_cast<const int32_t*>(d + b.o_assign);
@@ -222,7 +240,8 @@ int stage_batch(qadc_adc_index* idx, Batch& b, int nq, int ma, const int32_t* as
 // Runs the levels and reads the counts back; while a region overflowed, grows it and re-runs the whole batch.  fetch: the stored records come
 // back too, packed into idx->h_packed (three words each) — those of a small batch speculatively, with the counts, in one round trip.
 int run_levels(qadc_adc_index* idx, Batch& b, int nq, int ma, int R, int sum_mode, bool fetch) {
-    const ScanDb db = scan_db(idx);
+    ScanDb db = scan_db(idx);
+    db.qfilters = b.d_qfilters;
     const std::vector<uint32_t>& first = b.plan.level_first;
     const int levels = b.plan.levels();
     b.stored.resize(nq);
@@ -338,15 +357,17 @@ void order_on_host(qadc_adc_index* idx, const std::vector<uint32_t>& stored, uin
 
 // Scans the batch on the device and leaves the ordered candidate stream of every query in idx->stream_* — or, given `out`
 // (R <= kAdcReplayMaxR), orders and replays the streams on the device.  The tables are the caller's (`tables`, uploaded with the
-// items) or already in device memory (`d_ready`, enqueued on the index's stream before this call; tables is null then).
+// items) or already in device memory (`d_ready`, enqueued on the index's stream before this call; tables is null then).  filters:
+// null, or the filters of these nq queries (entry 0 = the batch's first query; NULL entries legal) — a batch in which no query has
+// one is staged and scanned as a call without `filters`.
 int scan_batch(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, const float* d_ready, int R,
-               int sum_mode, const DeviceOut* out = nullptr) {
+               int sum_mode, const DeviceOut* out = nullptr, const qadc_adc_filter* const* filters = nullptr) {
     if (int rc = check_query_args(idx, nq, ma, assign, d_ready ? static_cast<const void*>(d_ready) : tables, R, sum_mode)) return rc;
     HIPCHECK(hipSetDevice(idx->device));
     Batch b;
     b.plan = plan_levels(idx->sizes.data(), nq, ma, assign, R);
     if (!b.plan.refused.empty()) return fail(QADC_E_ARG, b.plan.refused);
-    if (int rc = stage_batch(idx, b, nq, ma, assign, tables, d_ready)) return rc;
+    if (int rc = stage_batch(idx, b, nq, ma, assign, tables, d_ready, any_filter(filters, nq) ? filters : nullptr)) return rc;
     if (int rc = run_levels(idx, b, nq, ma, R, sum_mode, !out)) return rc;
     if (out) return finish_on_device(idx, b, nq, R, *out);
     order_on_host(idx, b.stored, b.n_stored, nq);
@@ -410,16 +431,17 @@ struct StreamGather {
 // scan_batch on the caller's host tables, in sub-batches of whole queries whose tables fit the table budget: the host and the
 // device staging buffers never hold more than one pass's tables (a 16-bit table is up to 2 MiB per (query, probe)).
 int scan_host_tables(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
-                     const DeviceOut* out = nullptr) {
+                     const DeviceOut* out = nullptr, const qadc_adc_filter* const* filters = nullptr) {
     if (int rc = check_query_args(idx, nq, ma, assign, tables, R, sum_mode)) return rc;
     const int per = queries_per_pass(idx, nq, ma);
-    if (per >= nq) return scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode, out);
+    if (per >= nq) return scan_batch(idx, nq, ma, assign, tables, nullptr, R, sum_mode, out, filters);
     const size_t per_query = (size_t)ma * idx->nsq * idx->centroids;
     StreamGather gather(!out);
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int n = std::min(per, nq - q0);
         const DeviceOut sub = out ? DeviceOut{out->keys + (size_t)q0 * R, out->values + (size_t)q0 * R, out->sizes + q0} : DeviceOut{};
-        if (int rc = scan_batch(idx, n, ma, assign + (size_t)q0 * ma, tables + (size_t)q0 * per_query, nullptr, R, sum_mode, out ? &sub : nullptr))
+        if (int rc = scan_batch(idx, n, ma, assign + (size_t)q0 * ma, tables + (size_t)q0 * per_query, nullptr, R, sum_mode, out ? &sub : nullptr,
+                                filters ? filters + q0 : nullptr))   // (a sub-batch numbers its queries from 0: its table starts at query q0 of the call)
             return rc;
         gather.append(idx, n);
     }
@@ -548,9 +570,9 @@ int enqueue_tables(qadc_adc_index* idx, const Feeders& f, int q0, int nq, int ma
 
 // Feeders + scan of the whole batch in sub-batches; leaves the ordered stream of all nq queries in idx->stream_*, or, given
 // `out`, the heaps' arrays of all nq queries there (scan_batch's device finish, sub-batch by sub-batch).  d_side: the queries
-// are in device memory.
+// are in device memory.  filters: null, or the filters of the call's nq queries.
 int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, int32_t* assign_out,
-                 const DeviceOut* out = nullptr, bool d_side = false) {
+                 const DeviceOut* out = nullptr, bool d_side = false, const qadc_adc_filter* const* filters = nullptr) {
     Feeders f;
     if (int rc = resolve_feeders(idx, nq, queries, ma, table_form, sum_mode, &f)) return rc;
     if (int rc = check_R(R)) return rc;
@@ -566,7 +588,8 @@ int search_batch(qadc_adc_index* idx, int nq, const float* queries, int ma, int 
         if (q0)   // (the scan before it has been waited for: the table buffer is free)
             if (int rc = enqueue_tables(idx, f, q0, n, ma, table_form, sum_mode)) return rc;
         const DeviceOut sub = out ? DeviceOut{out->keys + (size_t)q0 * R, out->values + (size_t)q0 * R, out->sizes + q0} : DeviceOut{};
-        if (int rc = scan_batch(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, R, sum_mode, out ? &sub : nullptr))
+        if (int rc = scan_batch(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, R, sum_mode, out ? &sub : nullptr,
+                                filters ? filters + q0 : nullptr))
             return rc;
         gather.append(idx, n);
     }
@@ -650,6 +673,65 @@ int stream_to_host(qadc_adc_index* idx, int nq, uint64_t cand_capacity, uint32_t
     DeviceGuard guard;
     if (int rc = produce(nullptr)) return rc;
     return copy_stream(idx, nq, cand_capacity, cand_keys, cand_vals, offsets);
+}
+
+// The filters of a *_filtered call, checked before the first HIP call: every entry that is not NULL is on the
+// index's device.
+int check_query_filters(const qadc_adc_index* idx, int nq, const qadc_adc_filter* const* filters) {
+    if (!idx || !filters) return QADC_OK;   // (a null index is refused by the call's own checks)
+    for (int q = 0; q < nq; ++q)
+        if (filters[q] && filters[q]->device != idx->device)
+            return fail(QADC_E_ARG, "filters[" + std::to_string(q) + "] is on device " + std::to_string(filters[q]->device) + " and the index on device " +
+                                        std::to_string(idx->device));
+    return QADC_OK;
+}
+
+// The six scanning calls, each entered by its plain form (filters null) and by its _filtered form.
+int query_scan_call(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode, uint32_t* keys,
+                    float* values, int32_t* sizes, const qadc_adc_filter* const* filters) {
+    if (int rc = check_query_filters(idx, nq, filters)) return rc;
+    return heaps_to_host(idx, nq, R, keys, values, sizes,
+                         [&](const DeviceOut* out) { return scan_host_tables(idx, nq, ma, assign, tables, R, sum_mode, out, filters); });
+}
+
+int query_scan_device_call(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, int R, int sum_mode,
+                           uint32_t* d_keys, float* d_values, int32_t* d_sizes, const qadc_adc_filter* const* filters) {
+    if (int rc = check_query_filters(idx, nq, filters)) return rc;
+    return heaps_to_device(idx, nq, R, d_keys, d_values, d_sizes,
+                           [&](const DeviceOut* out) { return scan_batch(idx, nq, ma, assign, nullptr, d_tables, R, sum_mode, out, filters); });
+}
+
+int query_scan_candidates_call(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
+                               uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets,
+                               const qadc_adc_filter* const* filters) {
+    if (int rc = check_query_filters(idx, nq, filters)) return rc;
+    return stream_to_host(idx, nq, cand_capacity, cand_keys, cand_vals, offsets,
+                          [&](const DeviceOut*) { return scan_host_tables(idx, nq, ma, assign, tables, R, sum_mode, nullptr, filters); });
+}
+
+int search_call(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, uint32_t* keys, float* values,
+                int32_t* sizes, int32_t* assign_out, const qadc_adc_filter* const* filters) {
+    if (int rc = check_query_filters(idx, nq, filters)) return rc;
+    return heaps_to_host(idx, nq, R, keys, values, sizes, [&](const DeviceOut* out) {
+        return search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out, out, false, filters);
+    });
+}
+
+int search_device_call(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int R, int table_form, int sum_mode, uint32_t* d_keys,
+                       float* d_values, int32_t* d_sizes, const qadc_adc_filter* const* filters) {
+    if (int rc = check_query_filters(idx, nq, filters)) return rc;
+    return heaps_to_device(idx, nq, R, d_keys, d_values, d_sizes, [&](const DeviceOut* out) {
+        return search_batch(idx, nq, d_queries, ma, R, table_form, sum_mode, nullptr, out, true, filters);
+    });
+}
+
+int search_candidates_call(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,
+                           uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets, int32_t* assign_out,
+                           const qadc_adc_filter* const* filters) {
+    if (int rc = check_query_filters(idx, nq, filters)) return rc;
+    return stream_to_host(idx, nq, cand_capacity, cand_keys, cand_vals, offsets, [&](const DeviceOut*) {
+        return search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out, nullptr, false, filters);
+    });
 }
 
 // ---- db_add: qadc_adc_index_add_vectors, _reserve, _read_partition ----
@@ -1303,20 +1385,33 @@ uint32_t qadc_adc_index_partition_size(const qadc_adc_index* idx, int part) {
 
 int qadc_adc_query_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
                         uint32_t* keys, float* values, int32_t* sizes) {
-    return heaps_to_host(idx, nq, R, keys, values, sizes,
-                         [&](const DeviceOut* out) { return scan_host_tables(idx, nq, ma, assign, tables, R, sum_mode, out); });
+    return query_scan_call(idx, nq, ma, assign, tables, R, sum_mode, keys, values, sizes, nullptr);
+}
+
+int qadc_adc_query_scan_filtered(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode,
+                                 uint32_t* keys, float* values, int32_t* sizes, const qadc_adc_filter* const* filters) {
+    return query_scan_call(idx, nq, ma, assign, tables, R, sum_mode, keys, values, sizes, filters);
 }
 
 int qadc_adc_query_scan_device(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, int R, int sum_mode,
                                uint32_t* d_keys, float* d_values, int32_t* d_sizes) {
-    return heaps_to_device(idx, nq, R, d_keys, d_values, d_sizes,
-                           [&](const DeviceOut* out) { return scan_batch(idx, nq, ma, assign, nullptr, d_tables, R, sum_mode, out); });
+    return query_scan_device_call(idx, nq, ma, assign, d_tables, R, sum_mode, d_keys, d_values, d_sizes, nullptr);
+}
+
+int qadc_adc_query_scan_device_filtered(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, int R, int sum_mode,
+                                        uint32_t* d_keys, float* d_values, int32_t* d_sizes, const qadc_adc_filter* const* filters) {
+    return query_scan_device_call(idx, nq, ma, assign, d_tables, R, sum_mode, d_keys, d_values, d_sizes, filters);
 }
 
 int qadc_adc_query_scan_candidates(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R,
                                    int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets) {
-    return stream_to_host(idx, nq, cand_capacity, cand_keys, cand_vals, offsets,
-                          [&](const DeviceOut*) { return scan_host_tables(idx, nq, ma, assign, tables, R, sum_mode); });
+    return query_scan_candidates_call(idx, nq, ma, assign, tables, R, sum_mode, cand_capacity, cand_keys, cand_vals, offsets, nullptr);
+}
+
+int qadc_adc_query_scan_candidates_filtered(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R,
+                                            int sum_mode, uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets,
+                                            const qadc_adc_filter* const* filters) {
+    return query_scan_candidates_call(idx, nq, ma, assign, tables, R, sum_mode, cand_capacity, cand_keys, cand_vals, offsets, filters);
 }
 
 int qadc_adc_index_set_pq(qadc_adc_index* idx, int dim, const float* codebooks) {
@@ -1389,20 +1484,33 @@ int qadc_adc_index_set_table_budget(qadc_adc_index* idx, uint64_t bytes) {
 
 int qadc_adc_search(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, uint32_t* keys,
                     float* values, int32_t* sizes, int32_t* assign_out) {
-    return heaps_to_host(idx, nq, R, keys, values, sizes,
-                         [&](const DeviceOut* out) { return search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out, out); });
+    return search_call(idx, nq, queries, ma, R, table_form, sum_mode, keys, values, sizes, assign_out, nullptr);
+}
+
+int qadc_adc_search_filtered(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode, uint32_t* keys,
+                             float* values, int32_t* sizes, int32_t* assign_out, const qadc_adc_filter* const* filters) {
+    return search_call(idx, nq, queries, ma, R, table_form, sum_mode, keys, values, sizes, assign_out, filters);
 }
 
 int qadc_adc_search_device(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int R, int table_form, int sum_mode,
                            uint32_t* d_keys, float* d_values, int32_t* d_sizes) {
-    return heaps_to_device(idx, nq, R, d_keys, d_values, d_sizes,
-                           [&](const DeviceOut* out) { return search_batch(idx, nq, d_queries, ma, R, table_form, sum_mode, nullptr, out, true); });
+    return search_device_call(idx, nq, d_queries, ma, R, table_form, sum_mode, d_keys, d_values, d_sizes, nullptr);
+}
+
+int qadc_adc_search_device_filtered(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int R, int table_form, int sum_mode,
+                                    uint32_t* d_keys, float* d_values, int32_t* d_sizes, const qadc_adc_filter* const* filters) {
+    return search_device_call(idx, nq, d_queries, ma, R, table_form, sum_mode, d_keys, d_values, d_sizes, filters);
 }
 
 int qadc_adc_search_candidates(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,
                                uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets, int32_t* assign_out) {
-    return stream_to_host(idx, nq, cand_capacity, cand_keys, cand_vals, offsets,
-                          [&](const DeviceOut*) { return search_batch(idx, nq, queries, ma, R, table_form, sum_mode, assign_out); });
+    return search_candidates_call(idx, nq, queries, ma, R, table_form, sum_mode, cand_capacity, cand_keys, cand_vals, offsets, assign_out, nullptr);
+}
+
+int qadc_adc_search_candidates_filtered(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,
+                                        uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets, int32_t* assign_out,
+                                        const qadc_adc_filter* const* filters) {
+    return search_candidates_call(idx, nq, queries, ma, R, table_form, sum_mode, cand_capacity, cand_keys, cand_vals, offsets, assign_out, filters);
 }
 
 int qadc_adc_search_tables(qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode, int32_t* assign_out,

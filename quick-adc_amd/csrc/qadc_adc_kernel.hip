@@ -7,6 +7,8 @@
 //                      value), NibbleCodes<M> (the view: a 4-bit index read in place, scan_4<M>, tables [M][16]) and
 //                      WordCodes<NSQ> (16-bit codes, tables [NSQ][65536]: too large for LDS, gathered from global memory);
 //   adc_scan_filtered_kernel  the same body with a key filter in front of the emit (qadc_adc_index_set_filter, section 11.10);
+//   adc_scan_qfiltered_kernel the same body with the index's filter and the filter of the workgroup's own query (the *_filtered
+//                             calls, section 11.12);
 //   adc_select_kernel one workgroup per query: bound = the R-th smallest value the query emitted so far (radix select on
 //                      the order-preserving integer image of the floats), the bound of the next level's runs;
 //   adc_pack_kernel    the per-query regions packed densely for one device-to-host copy;
@@ -21,6 +23,7 @@
 // every sum rounds like the reference's.
 #include <algorithm>
 #include <cfloat>
+#include <type_traits>
 
 #include "../host/adc_tables_plan.hpp"     // adc_tables_plan, adc_encode_plan: the feeders' launch geometry
 #include "../host/index_append_plan.hpp"   // index_padded_end: the span kept zero behind a partition's last row
@@ -161,7 +164,9 @@ __device__ __forceinline__ bool remove_marked(uint32_t word, uint32_t lo, uint32
 // Which rows the scan may emit (qadc_adc_index_set_filter): the compile-time policy of adc_scan_body.
 // NoFilter: every row, and the kernel's code is the unfiltered kernel's.  KeyFilter: the rows whose key passes the ScanFilter —
 // a key marked in the bitmap is dropped under QADC_ADC_FILTER_EXCLUDE and is the only kind kept under QADC_ADC_FILTER_ALLOW; a key
-// outside [lo, lo + last] is not marked.
+// outside [lo, lo + last] is not marked.  QueryFilter: the rows that pass both the index's ScanFilter and the one of the workgroup's
+// query (the *_filtered calls; section 11.12); either may be absent (bitmap null), which is a branch on a value the whole
+// workgroup shares, so remove_word never sees a null bitmap.
 struct NoFilter {
     static constexpr bool kOn = false;
     __device__ __forceinline__ bool passes(uint32_t) const { return true; }
@@ -173,11 +178,22 @@ struct KeyFilter {
         return remove_marked(remove_word(f.bitmap, f.lo, f.last, key), f.lo, f.last, key) == (f.mode == kFilterAllow);
     }
 };
+struct QueryFilter {
+    static constexpr bool kOn = true;
+    ScanFilter index, query;   // the same in every lane of the workgroup: kernel argument and table entry [it.query]
+    __device__ __forceinline__ bool passes(uint32_t key) const {
+        bool ok = true;
+        if (index.bitmap) ok = KeyFilter{index}.passes(key);
+        if (query.bitmap) ok = ok & KeyFilter{query}.passes(key);
+        return ok;
+    }
+};
 
 template <class Code, int SUM, class Source, class Filter>
 __device__ __forceinline__ void adc_scan_body(const Item* __restrict__ items, uint32_t first, Source src,
                                               const int32_t* __restrict__ assign, int ma, const float* __restrict__ tables,
-                                              const float* __restrict__ bound, Emit emit, Filter filter) {
+                                              const float* __restrict__ bound, Emit emit, Filter filter,
+                                              [[maybe_unused]] const ScanFilter* __restrict__ qfilters = nullptr) {
     constexpr int CS = Code::kBytes;
     constexpr bool kLds = Code::kTableInLds;
     __shared__ float lds[kLds ? Code::kTable : 1];                // (the word policy's table stays where it is)
@@ -188,6 +204,7 @@ __device__ __forceinline__ void adc_scan_body(const Item* __restrict__ items, ui
         const float4* tab = reinterpret_cast<const float4*>(gtab);
         for (int i = threadIdx.x; i < Code::kTable / 4; i += kWG) reinterpret_cast<float4*>(lds)[i] = tab[i];
     }
+    if constexpr (std::is_same<Filter, QueryFilter>::value) filter.query = qfilters[it.query];   // once per workgroup
     const float b = bound[it.query];
     const uint64_t region = emit.base[it.query];
     const uint32_t cap = emit.cap[it.query];
@@ -248,8 +265,8 @@ __device__ __forceinline__ void adc_scan_body(const Item* __restrict__ items, ui
     }
 }
 
-// The two kernels over the body: the unfiltered one, whose arguments and code are what they were before there was a filter, and the
-// filtered one, which takes the filter by value behind them.
+// The three kernels over the body: the unfiltered one, whose arguments and code are what they were before there was a filter, the
+// filtered one, which takes the filter by value behind them, and the per-query one, which takes the table of the call's queries too.
 template <class Code, int SUM, class Source>
 __global__ __launch_bounds__(kWG) void adc_scan_kernel(const Item* __restrict__ items, uint32_t first, Source src,
                                                        const int32_t* __restrict__ assign, int ma,
@@ -264,6 +281,14 @@ __global__ __launch_bounds__(kWG) void adc_scan_filtered_kernel(const Item* __re
                                                                 const float* __restrict__ tables, const float* __restrict__ bound,
                                                                 Emit emit, ScanFilter filter) {
     adc_scan_body<Code, SUM>(items, first, src, assign, ma, tables, bound, emit, KeyFilter{filter});
+}
+
+template <class Code, int SUM, class Source>
+__global__ __launch_bounds__(kWG) void adc_scan_qfiltered_kernel(const Item* __restrict__ items, uint32_t first, Source src,
+                                                                 const int32_t* __restrict__ assign, int ma,
+                                                                 const float* __restrict__ tables, const float* __restrict__ bound,
+                                                                 Emit emit, ScanFilter filter, const ScanFilter* __restrict__ qfilters) {
+    adc_scan_body<Code, SUM>(items, first, src, assign, ma, tables, bound, emit, QueryFilter{filter, ScanFilter{}}, qfilters);
 }
 
 // order-preserving image of a float (never NaN here): -x < -y < -0 < +0 < y < x
@@ -1179,6 +1204,12 @@ hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, ui
                            int ma, const float* tables, const float* bound, Emit emit, hipStream_t s) {
     if (n_items == 0) return hipSuccess;
     const auto scan = [&](auto code, auto src) {
+        if (db.qfilters) {        // the call carries a filter of a query (the *_filtered calls): the per-query instantiation
+            const auto kernel = sum_mode == 0 ? adc_scan_qfiltered_kernel<decltype(code), 0, decltype(src)>
+                                              : adc_scan_qfiltered_kernel<decltype(code), 1, decltype(src)>;
+            hipLaunchKernelGGL(kernel, dim3(n_items), dim3(kWG), 0, s, items, first, src, assign, ma, tables, bound, emit, db.filter, db.qfilters);
+            return hipGetLastError();
+        }
         if (db.filter.bitmap) {   // the index has a filter (qadc_adc_index_set_filter): the filtered instantiation
             const auto kernel = sum_mode == 0 ? adc_scan_filtered_kernel<decltype(code), 0, decltype(src)>
                                               : adc_scan_filtered_kernel<decltype(code), 1, decltype(src)>;

@@ -56,10 +56,12 @@ struct ScanDb {
     Db bytes;             // a kernel argument by value: the owned index's code loads are global loads
     const Part4* parts;   // device memory, one entry per partition
     ScanFilter filter;    // a kernel argument by value of the filtered kernel; bitmap null: the unfiltered kernel is launched
+    const ScanFilter* qfilters = nullptr;   // device memory, one entry per query of the launch (bitmap null: none for that query), or
+                                            // null: no query of the call has a filter of its own and the kernels above are launched
 };
 
 // Scans items [first, first + n_items): emits (candidate, key, scan index) for every code with candidate < bound[query] whose key
-// passes db.filter.
+// passes db.filter and db.qfilters[query].
 hipError_t launch_adc_scan(const ScanDb& db, int sum_mode, const Item* items, uint32_t first, uint32_t n_items, const int32_t* assign,
                            int ma, const float* tables, const float* bound, Emit emit, hipStream_t s);
 // bound[q] = min(bound[q], the R-th smallest of the values query q has stored so far) where it stored at least R.

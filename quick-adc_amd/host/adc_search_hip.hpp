@@ -19,6 +19,8 @@
 // qadc_adc_index_set_finish) and a query's arrays are pushed into the caller's empty heap in array order, which rebuilds them
 // exactly; the default is the host finish, the candidate stream.
 // set_filter(f): the scans drop the rows whose key does not pass the qadc_adc_filter f (qadc_adc_index_set_filter).
+// set_query_filters(per_query): one filter per query of the caller's query array on top of it (qadc_adc_search_filtered,
+// qadc_adc_search_candidates_filtered).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -79,6 +81,12 @@ struct adc_search_engine_hip {
         if (index && qadc_adc_index_set_filter(index, f) != QADC_OK) die("set_filter");
     }
 
+    // One filter per query: per_query[i] is the filter of query i of the `queries` array process_query is given (its query_i), NULL for
+    // none; a null array clears.  The array and its filters are the caller's and are read by every process_query that opens a batch: they
+    // stay alive until cleared.  A query's rows pass set_filter's filter and its own.
+    const qadc_adc_filter* const* query_filters = nullptr;
+    void set_query_filters(const qadc_adc_filter* const* per_query) { query_filters = per_query; }
+
     // scanner_simple::prepare_database (db_query.cpp:21-24) plus the quantizers the feeders need
     void prepare_database() {
         const int m = db.pq->sq_count, bits = db.pq->sq_bits;
@@ -133,6 +141,9 @@ struct adc_search_engine_hip {
         if (qadc_adc_index_set_filter(index, filter) != QADC_OK) die("set_filter");
     }
 
+    // the filters of the batch that opens at query_i (null: the plain call)
+    const qadc_adc_filter* const* batch_filters(int query_i) const { return query_filters ? query_filters + query_i : nullptr; }
+
     // nns_engine_batch::process_query (query_common.hpp:194-243): the whole batch is searched when its first query is asked for
     template <typename Heap>
     void process_query(int query_i, const float* queries, int count, Heap& bh, query_metrics& metrics) {
@@ -147,8 +158,8 @@ struct adc_search_engine_hip {
                     cand_vals.resize((std::size_t)batch * r);
                 }
                 heap_sizes.resize(batch);
-                if (qadc_adc_search(index, nb, queries + (std::size_t)query_i * db.pq->dim, ma, r, table_form, sum_mode, cand_keys.data(),
-                                    cand_vals.data(), heap_sizes.data(), assign.data()) != QADC_OK)
+                if (qadc_adc_search_filtered(index, nb, queries + (std::size_t)query_i * db.pq->dim, ma, r, table_form, sum_mode, cand_keys.data(),
+                                             cand_vals.data(), heap_sizes.data(), assign.data(), batch_filters(query_i)) != QADC_OK)
                     die("search");
             }
             for (std::int32_t i = 0; i < heap_sizes[b]; ++i) bh.push(cand_keys[(std::size_t)b * r + i], cand_vals[(std::size_t)b * r + i]);
@@ -158,13 +169,13 @@ struct adc_search_engine_hip {
         if (b == 0) {
             const int nb = std::min(batch, count - query_i);
             const float* q = queries + (std::size_t)query_i * db.pq->dim;
-            int rc = qadc_adc_search_candidates(index, nb, q, ma, r, table_form, sum_mode, cand_keys.size(), cand_keys.data(),
-                                                cand_vals.data(), offsets.data(), assign.data());
+            int rc = qadc_adc_search_candidates_filtered(index, nb, q, ma, r, table_form, sum_mode, cand_keys.size(), cand_keys.data(),
+                                                         cand_vals.data(), offsets.data(), assign.data(), batch_filters(query_i));
             if (rc == QADC_E_CAPACITY) {  // offsets[nb] holds the required size: grow and ask again
                 cand_keys.resize(offsets[nb]);
                 cand_vals.resize(offsets[nb]);
-                rc = qadc_adc_search_candidates(index, nb, q, ma, r, table_form, sum_mode, cand_keys.size(), cand_keys.data(),
-                                                cand_vals.data(), offsets.data(), assign.data());
+                rc = qadc_adc_search_candidates_filtered(index, nb, q, ma, r, table_form, sum_mode, cand_keys.size(), cand_keys.data(),
+                                                         cand_vals.data(), offsets.data(), assign.data(), batch_filters(query_i));
             }
             if (rc != QADC_OK) die("search");
         }

@@ -9,7 +9,8 @@
 //   scan_4f<N>          query_common.hpp:59-90: the same on row-major 4-bit codes (low nibble = even sub-quantizer)
 //   get_scan_func       query_common.hpp:120-146: the (sq_count, sq_bits) dispatch and its error text
 //   scanner_simple      db_query.cpp:17-46: R sentinel pushes FLT_MAX - t, then every probed partition in assign[] order
-//   key_filter          no reference counterpart: the allow / exclude key set the scan loops skip rows by (set_filter)
+//   key_filter          no reference counterpart: the allow / exclude key set the scan loops skip rows by (set_filter), and a
+//                       second one of the query's own chained to it (set_query_filter): a row must pass both
 // Float sums take the grouping of the reference AS COMPILED with its -ffast-math (host/float_sum.hpp; float_sum_mode() = 0
 // gives the source order); this file itself is built without -ffast-math.  The oracle's orc_scan_standard_u8 /
 // orc_candidates_f32 / orc_tables_direct, pinned to the reference build, are the checkers (tests/test_scanner_hip_cpp.py).
@@ -31,15 +32,25 @@ typedef kv_heap<unsigned, float> float_heap;
 // The key filter of a scan — the written definition of qadc_adc_index_set_filter (include/qadc.h), which the
 // reference does not have.  A row's key is what the scan would push for it (its label, else its position); the scan loops below skip a
 // row the filter drops before they look at its candidate, which is the reference's loop over the partition without that row, its key kept.
+// A filter may be chained to a second one (`also`): the written definition of the *_filtered calls, where a
+// row must pass the index's filter and its query's — it is dropped as soon as either drops it.
 struct key_filter {
     enum { exclude = 0, allow = 1 };                             // QADC_ADC_FILTER_EXCLUDE, QADC_ADC_FILTER_ALLOW
     int mode;
     std::vector<unsigned> keys;                                  // sorted, unique
+    const key_filter* also = nullptr;                            // not owned; null = this filter alone
     key_filter(int mode_, const unsigned* k, std::size_t count) : mode(mode_), keys(k, k + count) {
         std::sort(keys.begin(), keys.end());
         keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
     }
-    bool drops(unsigned key) const { return std::binary_search(keys.begin(), keys.end(), key) == (mode == exclude); }
+    key_filter chained(const key_filter* second) const {         // this set and mode, and `second` behind it
+        key_filter both(*this);
+        both.also = second;
+        return both;
+    }
+    bool drops(unsigned key) const {
+        return std::binary_search(keys.begin(), keys.end(), key) == (mode == exclude) || (also != nullptr && also->drops(key));
+    }
 };
 
 template <typename T, int NSQ>
@@ -176,6 +187,8 @@ struct scanner_simple {
     scan_func scan = nullptr;
     const key_filter* filter = nullptr;                          // set_filter: not owned, null = the reference's scan
     void set_filter(const key_filter* f) { filter = f; }
+    const key_filter* query_filter = nullptr;                    // set_query_filter: the filter of the query scanned next, on top of `filter`
+    void set_query_filter(const key_filter* f) { query_filter = f; }
     void prepare_database(Db& database) {
         db = &database;
         scan = get_scan_func(*database.pq);
@@ -186,9 +199,12 @@ struct scanner_simple {
         const std::uint8_t* codes;
         unsigned* labels;
         unsigned count;
+        const bool two = filter != nullptr && query_filter != nullptr;
+        const key_filter both = two ? filter->chained(query_filter) : key_filter(key_filter::exclude, nullptr, 0);
+        const key_filter* const pass = two ? &both : filter != nullptr ? filter : query_filter;   // one filter or none: as before
         for (int a = 0; a < ma; ++a) {
             db->get_partition(assign[a], codes, labels, count);
-            scan(codes, labels, count, tables, bh, filter);
+            scan(codes, labels, count, tables, bh, pass);
             tables += table_dim;
         }
     }

@@ -50,6 +50,8 @@ SYMBOLS = [
     "qadc_pq_train_host", "qadc_pq_train_device",
     "qadc_pq_train16_host", "qadc_pq_train16_device", "qadc_pq_update16_host",
     "qadc_adc_filter_create", "qadc_adc_filter_create_device", "qadc_adc_filter_info", "qadc_adc_filter_destroy", "qadc_adc_index_set_filter",
+    "qadc_adc_query_scan_filtered", "qadc_adc_query_scan_device_filtered", "qadc_adc_query_scan_candidates_filtered",
+    "qadc_adc_search_filtered", "qadc_adc_search_device_filtered", "qadc_adc_search_candidates_filtered",
     "qadc_refine_create", "qadc_refine_destroy", "qadc_refine_add", "qadc_refine_add_device", "qadc_refine_reserve", "qadc_refine_info",
     "qadc_refine_relocations", "qadc_refine_rerank", "qadc_refine_rerank_device",
 ]
@@ -254,6 +256,9 @@ def lib():
         L.qadc_adc_filter_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), u32p, u32p, u64p]
         L.qadc_adc_filter_destroy.argtypes = [C.c_void_p]
         L.qadc_adc_index_set_filter.argtypes = [C.c_void_p, C.c_void_p]
+        for name in ("qadc_adc_query_scan", "qadc_adc_query_scan_device", "qadc_adc_query_scan_candidates", "qadc_adc_search",
+                     "qadc_adc_search_device", "qadc_adc_search_candidates"):   # the plain form's arguments, then filters [nq]
+            getattr(L, name + "_filtered").argtypes = getattr(L, name).argtypes + [C.POINTER(C.c_void_p)]
         L.qadc_refine_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
         L.qadc_refine_destroy.argtypes = [C.c_void_p]
         L.qadc_refine_add.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32]
@@ -1344,6 +1349,31 @@ class AdcIndex:
         except Exception:
             pass
 
+    def _filters(self, filters, nq):
+        """filters= of a scanning call -> the array the *_filtered C call takes, or None (the plain call): a sequence of nq
+        AdcFilter | None.  ValueError: another length; TypeError: an entry of another type; QadcError: a closed filter."""
+        if filters is None:
+            return None
+        filters = list(filters)
+        if len(filters) != nq:
+            raise ValueError("filters has %d entries for %d queries" % (len(filters), nq))
+        arr = (C.c_void_p * nq)()
+        for q, f in enumerate(filters):
+            if f is None:
+                continue
+            if not isinstance(f, AdcFilter):
+                raise TypeError("filters[%d] is %s, not an AdcFilter or None" % (q, type(f).__name__))
+            if not getattr(f, "_h", None):
+                raise QadcError("filters[%d] is closed" % q)
+            arr[q] = f._h.value
+        return arr
+
+    def _scan_call(self, name, filters, *args):
+        """the plain C call, or with a filters array its _filtered form"""
+        if filters is None:
+            return getattr(lib(), name)(*args)
+        return getattr(lib(), name + "_filtered")(*args, filters)
+
     def _code_rows(self, c):
         """one partition's codes as the bytes the C call takes: uint8 [n][code bytes]"""
         if self.centroids != 65536:
@@ -1471,41 +1501,44 @@ class AdcIndex:
         tables = np.ascontiguousarray(tables, np.float32).reshape(nq, ma, self.table_dim)
         return assign, tables, nq, ma
 
-    def query_scan(self, assign, tables, R, sum_mode=1):
+    def query_scan(self, assign, tables, R, sum_mode=1, filters=None):
         """assign [nq][ma], tables [nq][ma][table_dim] (sq_count*256; create16: sq_count*65536; a view: sq_count*16) -> (keys [nq][R], vals [nq][R], sizes [nq]): the heap arrays
-        of scanner_simple::query_scan per query (rows are valid up to sizes[q])."""
+        of scanner_simple::query_scan per query (rows are valid up to sizes[q]).  filters: None, or a sequence of nq AdcFilter | None,
+        the filter of each query (qadc_adc_query_scan_filtered): query q also drops the rows whose key does not pass filters[q]."""
         assign, tables, nq, ma = self._inputs(assign, tables)
+        fl = self._filters(filters, nq)
         keys = np.zeros((nq, R), np.uint32)
         vals = np.zeros((nq, R), np.float32)
         sizes = np.zeros(nq, np.int32)
-        _check(lib().qadc_adc_query_scan(self._h, nq, ma, _p(assign, i32p), _p(tables, f32p), R, sum_mode, _p(keys, u32p),
-                                         _p(vals, f32p), _p(sizes, i32p)))
+        _check(self._scan_call("qadc_adc_query_scan", fl, self._h, nq, ma, _p(assign, i32p), _p(tables, f32p), R, sum_mode, _p(keys, u32p),
+                               _p(vals, f32p), _p(sizes, i32p)))
         return keys, vals, sizes
 
-    def query_scan_candidates(self, assign, tables, R, sum_mode=1, capacity=None):
+    def query_scan_candidates(self, assign, tables, R, sum_mode=1, capacity=None, filters=None):
         """-> (keys, vals, offsets [nq+1]): the ordered candidate stream (query q = [offsets[q], offsets[q+1])), to be pushed
         after the R sentinels.  capacity=None sizes the buffers itself; a given capacity that is too small raises QadcError
-        (offsets[nq] then holds the entries needed: see query_scan_candidates_raw)."""
+        (offsets[nq] then holds the entries needed: see query_scan_candidates_raw).  filters: as query_scan's."""
         if capacity is not None:
-            rc, keys, vals, offsets = self.query_scan_candidates_raw(assign, tables, R, sum_mode, capacity)
+            rc, keys, vals, offsets = self.query_scan_candidates_raw(assign, tables, R, sum_mode, capacity, filters)
             _check(rc)
             return keys, vals, offsets
         cap = 1 << 16
         while True:
-            rc, keys, vals, offsets = self.query_scan_candidates_raw(assign, tables, R, sum_mode, cap)
+            rc, keys, vals, offsets = self.query_scan_candidates_raw(assign, tables, R, sum_mode, cap, filters)
             if rc != QADC_E_CAPACITY:
                 _check(rc)
                 return keys[:offsets[-1]], vals[:offsets[-1]], offsets
             cap = int(offsets[-1])
 
-    def query_scan_candidates_raw(self, assign, tables, R, sum_mode, capacity):
+    def query_scan_candidates_raw(self, assign, tables, R, sum_mode, capacity, filters=None):
         """The C call as it is: -> (rc, keys [capacity], vals [capacity], offsets [nq+1])."""
         assign, tables, nq, ma = self._inputs(assign, tables)
+        fl = self._filters(filters, nq)
         keys = np.zeros(max(capacity, 1), np.uint32)
         vals = np.zeros(max(capacity, 1), np.float32)
         offsets = np.zeros(nq + 1, np.uint64)
-        rc = lib().qadc_adc_query_scan_candidates(self._h, nq, ma, _p(assign, i32p), _p(tables, f32p), R, sum_mode,
-                                                  capacity, _p(keys, u32p), _p(vals, f32p), _p(offsets, u64p))
+        rc = self._scan_call("qadc_adc_query_scan_candidates", fl, self._h, nq, ma, _p(assign, i32p), _p(tables, f32p), R, sum_mode,
+                             capacity, _p(keys, u32p), _p(vals, f32p), _p(offsets, u64p))
         return rc, keys, vals, offsets
 
     # ---- from query vectors: the feeders run on the GPU (qadc_adc_search*) ----
@@ -1547,45 +1580,49 @@ class AdcIndex:
         assert q.ndim == 2 and q.shape[1] == getattr(self, "dim", q.shape[1])
         return q
 
-    def search(self, queries, ma, R, table_form=2, sum_mode=1):
+    def search(self, queries, ma, R, table_form=2, sum_mode=1, filters=None):
         """queries [nq][dim] -> (keys [nq][R], vals [nq][R], sizes [nq], assign [nq][ma]): query_scan's heap arrays on tables
-        built on the GPU.  table_form 0 = direct, 1 = BLAS expansion, 2 = nns_engine's rule (direct iff ma == 1)."""
+        built on the GPU.  table_form 0 = direct, 1 = BLAS expansion, 2 = nns_engine's rule (direct iff ma == 1).  filters: None, or
+        a sequence of nq AdcFilter | None, the filter of each query (qadc_adc_search_filtered), on top of set_filter's."""
         q = self._queries(queries)
         nq = q.shape[0]
+        fl = self._filters(filters, nq)
         keys = np.zeros((nq, R), np.uint32)
         vals = np.zeros((nq, R), np.float32)
         sizes = np.zeros(nq, np.int32)
         assign = np.zeros((nq, ma), np.int32)
-        _check(lib().qadc_adc_search(self._h, nq, _p(q, f32p), ma, R, table_form, sum_mode, _p(keys, u32p), _p(vals, f32p),
-                                     _p(sizes, i32p), _p(assign, i32p)))
+        _check(self._scan_call("qadc_adc_search", fl, self._h, nq, _p(q, f32p), ma, R, table_form, sum_mode, _p(keys, u32p), _p(vals, f32p),
+                               _p(sizes, i32p), _p(assign, i32p)))
         return keys, vals, sizes, assign
 
-    def search_refined(self, queries, ma, R, r_in, store, table_form=2, sum_mode=1):
+    def search_refined(self, queries, ma, R, r_in, store, table_form=2, sum_mode=1, filters=None):
         """search(queries, ma, r_in), then the heaps' keys re-ranked by their exact L2 distance to the vectors of the Refine `store`
         -> (keys [nq][R], dist [nq][R], sizes [nq], missing), ascending by (distance, key).  The heaps' FLT_MAX sentinels are no
-        candidates; a filter set on the index holds for the refined keys, which are a subset of the heaps'."""
+        candidates; a filter set on the index, and the filters= of the queries, hold for the refined keys, which are a subset of the
+        heaps'."""
         q = self._queries(queries)
-        keys, vals, _, _ = self.search(q, ma, r_in, table_form, sum_mode)
+        keys, vals, _, _ = self.search(q, ma, r_in, table_form, sum_mode, filters=filters)
         return store.rerank(q, keys, R, values=vals)
 
-    def search_refined_device(self, queries, ma, R, r_in, store, table_form=2, sum_mode=1):
+    def search_refined_device(self, queries, ma, R, r_in, store, table_form=2, sum_mode=1, filters=None):
         """search_device, then store.rerank_device on its tensors: queries in device memory in, (keys int32 [nq][R] carrying the
         uint32 bits, dist float32 [nq][R], sizes int32 [nq]) in device memory out, and the missing count; nothing else crosses the bus."""
-        keys, vals, _ = self.search_device(queries, ma, r_in, table_form, sum_mode)
+        keys, vals, _ = self.search_device(queries, ma, r_in, table_form, sum_mode, filters=filters)
         return store.rerank_device(queries, keys, R, values=vals)
 
-    def search_candidates(self, queries, ma, R, table_form=2, sum_mode=1):
+    def search_candidates(self, queries, ma, R, table_form=2, sum_mode=1, filters=None):
         """-> (keys, vals, offsets [nq+1], assign [nq][ma]): the ordered candidate stream, as query_scan_candidates returns it"""
         q = self._queries(queries)
         nq = q.shape[0]
+        fl = self._filters(filters, nq)
         assign = np.zeros((nq, ma), np.int32)
         offsets = np.zeros(nq + 1, np.uint64)
         cap = 1 << 16
         while True:
             keys = np.zeros(cap, np.uint32)
             vals = np.zeros(cap, np.float32)
-            rc = lib().qadc_adc_search_candidates(self._h, nq, _p(q, f32p), ma, R, table_form, sum_mode, cap, _p(keys, u32p),
-                                                  _p(vals, f32p), _p(offsets, u64p), _p(assign, i32p))
+            rc = self._scan_call("qadc_adc_search_candidates", fl, self._h, nq, _p(q, f32p), ma, R, table_form, sum_mode, cap, _p(keys, u32p),
+                                 _p(vals, f32p), _p(offsets, u64p), _p(assign, i32p))
             if rc != QADC_E_CAPACITY:
                 _check(rc)
                 return keys[:offsets[-1]], vals[:offsets[-1]], offsets, assign
@@ -1624,19 +1661,20 @@ class AdcIndex:
         torch.cuda.current_stream(dev).synchronize()                     # inputs and the zero fills are complete before the call
         return keys, vals, sizes
 
-    def search_device(self, queries, ma, R, table_form=2, sum_mode=1):
+    def search_device(self, queries, ma, R, table_form=2, sum_mode=1, filters=None):
         """queries: float32 tensor [nq][dim] on the index's device -> tensors (keys int32 [nq][R] carrying the uint32 bits,
         vals float32 [nq][R], sizes int32 [nq]) on that device: search()'s heap arrays, finished on the GPU; no host copy."""
         if getattr(queries, "ndim", 0) != 2:
             raise TypeError("queries must be a 2-d torch.Tensor")
         nq = int(queries.shape[0])
         q = self._device_tensor(queries, (nq, getattr(self, "dim", int(queries.shape[1]))), "queries")
+        fl = self._filters(filters, nq)                                  # (host memory: AdcFilter | None per query, as search's)
         keys, vals, sizes = self._device_outputs(nq, int(R))
-        _check(lib().qadc_adc_search_device(self._h, nq, q.data_ptr(), ma, R, table_form, sum_mode, keys.data_ptr(), vals.data_ptr(),
-                                            sizes.data_ptr()))
+        _check(self._scan_call("qadc_adc_search_device", fl, self._h, nq, q.data_ptr(), ma, R, table_form, sum_mode, keys.data_ptr(),
+                               vals.data_ptr(), sizes.data_ptr()))
         return keys, vals, sizes
 
-    def query_scan_device(self, assign, tables, R, sum_mode=1):
+    def query_scan_device(self, assign, tables, R, sum_mode=1, filters=None):
         """assign [nq][ma] (host), tables: float32 tensor [nq][ma][table_dim] on the index's device -> tensors (keys, vals,
         sizes) as search_device: query_scan()'s heap arrays without the upload of the tables."""
         assign = np.ascontiguousarray(assign, np.int32)
@@ -1644,9 +1682,10 @@ class AdcIndex:
             assign = assign.reshape(1, -1)
         nq, ma = assign.shape
         t = self._device_tensor(tables, (nq, ma, self.table_dim), "tables")
+        fl = self._filters(filters, nq)
         keys, vals, sizes = self._device_outputs(nq, int(R))
-        _check(lib().qadc_adc_query_scan_device(self._h, nq, ma, _p(assign, i32p), t.data_ptr(), R, sum_mode, keys.data_ptr(),
-                                                vals.data_ptr(), sizes.data_ptr()))
+        _check(self._scan_call("qadc_adc_query_scan_device", fl, self._h, nq, ma, _p(assign, i32p), t.data_ptr(), R, sum_mode, keys.data_ptr(),
+                               vals.data_ptr(), sizes.data_ptr()))
         return keys, vals, sizes
 
 

@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter,refine] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter,qfilter,refine] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,filter] [--iters N] [--out FILE]
 
@@ -41,6 +41,11 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             50 % of the keys, ALLOW of 1 % and 0.01 %, each checked against an index built without the dropped rows; (b) search() of
             1024 queries on the ivf_search database, unfiltered against EXCLUDE of 10 % of the keys, under both finishes; (c) the
             creation of a 10^6-key filter from host and from device memory.
+  qfilter   one filter per query of a batch (not in the default legs), on the ivf_search database: 1024
+            queries, K = 256, ma = 24, R = 100, every query assigned one of T distinct EXCLUDE filters, each of a random 10 % of the keys,
+            T = 1, 16 and 1024.  Arm (a) = one search(filters=...) call; arm (b) = what there is without it: the batch grouped by
+            filter, set_filter + search per group, the outputs scattered back.  The arms are asserted to return identical arrays and
+            alternate in one process, under both finishes, with an unfiltered search() timed beside them for scale.
   refine    exact re-ranking (not in the default legs), on the ivf_search shape: recall@100 against exact
             float L2 of search() alone and of search_refined_device with r_in = 400 and 1000 over a float and a half store; the time
             of search_refined_device split into search_device and rerank_device; beside it a plain torch gather + (q - x)^2 sum +
@@ -239,6 +244,8 @@ def search_legs(legs, iters, res):
                   % ("device" if finish else "host", med_p * 1e3, med_f * 1e3, med_f / med_p, same), flush=True)
         ref.close()
         f.close()
+    if "qfilter" in legs:
+        qfilter_leg(idx, len(part_of), queries, ma, iters, res, rng)
     if "lone_search" in legs:
         q1 = queries[:1]
         med, best = timed(lambda: idx.search(q1, ma, R), max(iters, 50), warmup=5)
@@ -261,6 +268,61 @@ def search_legs(legs, iters, res):
         print("CPU scan_standard<uint8_t,8> over the same 24 partitions (%d codes), 1 thread, tables given (%s): %.1f us"
               % (res["lone_search_codes_probed"], "reference build" if po.have_ref_float() else "C restatement", med_c * 1e6), flush=True)
     idx.close()
+
+
+def qfilter_leg(idx, n, queries, ma, iters, res, rng):
+    """one search(filters=...) call against the batch grouped by filter, T distinct filters over the 1024 queries"""
+    nq = len(queries)
+    it = max(5, iters)
+    for T in (1, 16, 1024):
+        made = [pyqadc.AdcFilter(rng.permutation(n)[:n // 10].astype(np.uint32), "exclude") for _ in range(T)]
+        of_query = rng.integers(0, T, nq) if T < nq else rng.permutation(nq)                  # T = nq: one filter per query
+        groups = [np.flatnonzero(of_query == t) for t in range(T)]
+        filters = [made[t] for t in of_query]
+
+        def one_call():
+            return idx.search(queries, ma, R, filters=filters)
+
+        def grouped():
+            out = None
+            try:
+                for t, rows in enumerate(groups):
+                    if not len(rows):
+                        continue
+                    idx.set_filter(made[t])
+                    got = idx.search(queries[rows], ma, R)
+                    if out is None:
+                        out = [np.zeros((nq,) + g.shape[1:], g.dtype) for g in got]
+                    for o, g in zip(out, got):
+                        o[rows] = g
+            finally:
+                idx.set_filter(None)
+            return out
+
+        for finish in (0, 1):
+            name = "device" if finish else "host"
+            a, b = with_finish(idx, finish, one_call), with_finish(idx, finish, grouped)
+            got_a, got_b = a(), b()
+            assert same_heaps(got_a, got_b) and np.array_equal(got_a[3], got_b[3]), "T = %d, %s finish: the arms disagree" % (T, name)
+            ta, tb, tp = [], [], []
+            plain = with_finish(idx, finish, lambda: idx.search(queries, ma, R))
+            plain()
+            for _ in range(it):                                                                   # (both arms ran once above: the warm-up)
+                for f, ts in ((a, ta), (b, tb), (plain, tp)):
+                    t0 = time.perf_counter()
+                    f()
+                    ts.append(time.perf_counter() - t0)
+            tag = "qfilter_T%d_%s_finish" % (T, name)
+            for arm, ts in (("one_call", ta), ("grouped", tb), ("unfiltered", tp)):
+                res["%s_%s_ms_median_min_max" % (tag, arm)] = [float(np.median(ts)) * 1e3, float(np.min(ts)) * 1e3, float(np.max(ts)) * 1e3]
+            res[tag + "_grouped_over_one_call"] = float(np.median(tb) / np.median(ta))
+            print("search() of %d queries under %d distinct EXCLUDE filters of 10 %% of the keys, %s finish, %d alternations: one call with "
+                  "filters= %.2f ms (%.2f .. %.2f); grouped by filter %.2f ms (%.2f .. %.2f), grouped / one call = %.2f; unfiltered %.2f ms; "
+                  "identical arrays" % (nq, T, name, it, np.median(ta) * 1e3, min(ta) * 1e3, max(ta) * 1e3, np.median(tb) * 1e3, min(tb) * 1e3,
+                                        max(tb) * 1e3, np.median(tb) / np.median(ta), np.median(tp) * 1e3), flush=True)
+        res["qfilter_T%d_bitmap_bytes_in_all" % T] = int(sum(f.info()["bitmap_bytes"] for f in made))
+        for f in made:
+            f.close()
 
 
 def refine_leg(idx, vectors, queries, ma, iters, res):
@@ -1152,7 +1214,7 @@ def main():
             print("the same alternated with query_scan_device (tables and heaps stay in device memory): %.2f ms against %.2f ms"
                   % (med_d * 1e3, med_h * 1e3), flush=True)
         idx.close()
-    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "refine" in legs:
+    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs:
         search_legs(legs, a.iters, res)
     if "filter" in legs:
         filter_leg(8, a.iters, res, torch)

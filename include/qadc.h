@@ -1040,6 +1040,42 @@ int qadc_adc_search_candidates_filtered(qadc_adc_index* idx, int nq, const float
                                         uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets,
                                         int32_t* assign_out, const qadc_adc_filter* const* filters);
 
+/* ---- range search: every row within a radius, sorted on the GPU ----
+ * The other query of a PQ index: for query q, every row of its probed partitions that passes the filters and whose candidate — the
+ * float sum query_scan compares with the heap's maximum, same grouping, same sum_mode — is < radius[q] as a float compare.  A NaN
+ * candidate or a NaN radius keeps nothing, radius +inf keeps every candidate but NaN and +inf, a candidate equal to the radius is not
+ * kept.  Query q's rows are ordered ascending by the 64-bit word (image(candidate) << 32) | key, image = the order-preserving integer
+ * image of a float (-0 before +0); nothing is deduplicated, and two rows with the same key and candidate are both present.  There is no
+ * R, no heap and no cap on a query's rows.  The written definition is scanner_simple::range_scan (quick-adc_amd/host/scanner_simple.hpp),
+ * to which every output is held bit for bit.
+ *   radius [nq], filters [nq], lims [nq + 1]   HOST memory in every form.  filters may be NULL and may hold NULL entries; it composes
+ *                                              with qadc_adc_index_set_filter as in the _filtered calls above.
+ *   lims                                       out: query q's rows are [lims[q], lims[q + 1]) of the held result; lims[nq] = its rows.
+ * The result stays ON THE INDEX, in device memory no other call writes, until the next range call (which drops it, also when it fails)
+ * or qadc_adc_index_destroy; qadc_adc_range_collect* copies it out, any number of times, and query_scan / search / add / remove calls
+ * in between leave it as it is.  The calls are synchronous.  Each pass (the whole call, or a sub-batch of the table budget) scans
+ * once with a region of min(probed codes, 4096) entries per query and, where a region overflowed, a second time with regions of exactly
+ * the counted sizes (counted in qadc_adc_index_reruns).  Works on 8-bit, 16-bit and view indexes.  QADC_E_ARG as the plain calls, and
+ * for radius or lims NULL or a filter of another device; QADC_E_CAPACITY when the regions of one pass exceed QADC_ADC_MAX_ENTRIES. */
+#define QADC_ADC_RANGE_SORT_LDS 4096   /* a query's rows up to this many are sorted in LDS, more by radix passes through device memory */
+/* tables [nq][ma][table floats] in host memory, as qadc_adc_query_scan takes them. */
+int qadc_adc_range_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, const float* radius, int sum_mode,
+                        const qadc_adc_filter* const* filters, uint64_t* lims);
+/* d_tables in device memory, as qadc_adc_query_scan_device takes them. */
+int qadc_adc_range_scan_device(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, const float* radius,
+                               int sum_mode, const qadc_adc_filter* const* filters, uint64_t* lims);
+/* From query vectors (host memory), tables built on the GPU as qadc_adc_search builds them; assign_out [nq][ma] may be NULL. */
+int qadc_adc_range_search(qadc_adc_index* idx, int nq, const float* queries, int ma, const float* radius, int table_form, int sum_mode,
+                          const qadc_adc_filter* const* filters, int32_t* assign_out, uint64_t* lims);
+/* d_queries in device memory; assign_out is host memory and may be NULL. */
+int qadc_adc_range_search_device(qadc_adc_index* idx, int nq, const float* d_queries, int ma, const float* radius, int table_form,
+                                 int sum_mode, const qadc_adc_filter* const* filters, int32_t* assign_out, uint64_t* lims);
+/* Copies the held result into keys / values [capacity] (host memory).  QADC_E_CAPACITY when capacity < lims[nq]: nothing is copied
+ * and the result stays held.  QADC_E_STATE when no result is held. */
+int qadc_adc_range_collect(qadc_adc_index* idx, uint64_t capacity, uint32_t* keys, float* values);
+/* The same into device memory, copied by a kernel (the buffers may belong to another copy of the HIP runtime). */
+int qadc_adc_range_collect_device(qadc_adc_index* idx, uint64_t capacity, uint32_t* d_keys, float* d_values);
+
 /* ---- exact re-ranking: the vectors on the GPU, candidates reordered by L2 ----
  * Both engines rank by a quantized distance.  A refine store keeps the original vectors in device memory, and a rerank call reorders
  * the candidate keys a search returned — with a larger R than wanted — by the true squared L2 distance to those vectors.  The store

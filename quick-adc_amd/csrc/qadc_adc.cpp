@@ -112,6 +112,11 @@ struct qadc_adc_index {
     std::vector<uint64_t> stream_off;               // [nq + 1] the ordered stream of the last call
     std::vector<uint32_t> stream_keys;
     std::vector<float> stream_vals;
+    // range search (qadc_adc_range_*): the held result, in buffers no other call writes
+    DevBuf<uint32_t> d_rkeys;
+    DevBuf<float> d_rvals;
+    PinBuf<float> h_radius;
+    std::vector<uint64_t> range_lims;               // [nq + 1] rows of each query of the last range call; empty: nothing to collect
     qadc::WorkerPool pool;
 };
 
@@ -734,6 +739,151 @@ int search_candidates_call(qadc_adc_index* idx, int nq, const float* queries, in
     });
 }
 
+// ---- range search: qadc_adc_range_*  ----
+
+static_assert(kRangeSortLds == QADC_ADC_RANGE_SORT_LDS, "include/qadc.h names the LDS threshold of adc_range_sort_kernel");
+
+// One pass of a range call: queries [0, nq) scanned over one level under bound[q] = radius[q], their kept rows sorted and appended to the
+// held result behind lims.back(); lims grows by nq entries.  Tables as scan_batch takes them.  The first attempt gives every query a
+// region of kRangeFirstCap entries; the scan counts every kept row, so a second attempt, if one region overflowed, has room for exactly
+// what it keeps (host/adc_plan.hpp: plan_range, plan_range_rerun).
+int range_pass(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, const float* d_ready, const float* radius,
+               int sum_mode, const qadc_adc_filter* const* filters, std::vector<uint64_t>& lims) {
+    if (int rc = check_query_args(idx, nq, ma, assign, d_ready ? static_cast<const void*>(d_ready) : tables, 1, sum_mode)) return rc;
+    HIPCHECK(hipSetDevice(idx->device));
+    Batch b;
+    b.plan = plan_range(idx->sizes.data(), nq, ma, assign);
+    if (!b.plan.refused.empty()) return fail(QADC_E_ARG, b.plan.refused);
+    uint64_t entries = 0;
+    std::string over = range_entries(b.plan.cap, kMaxEntries, &entries);
+    if (!over.empty()) return fail(QADC_E_CAPACITY, over);
+    if (int rc = stage_batch(idx, b, nq, ma, assign, tables, d_ready, any_filter(filters, nq) ? filters : nullptr)) return rc;
+    ScanDb db = scan_db(idx);
+    db.qfilters = b.d_qfilters;
+    HIPCHECK(idx->h_count.ensure(nq));
+    HIPCHECK(idx->h_radius.ensure(nq));
+    std::memcpy(idx->h_radius.p, radius, (size_t)nq * 4);
+    for (int attempt = 0;; ++attempt) {
+        HIPCHECK(hipMemcpyAsync(b.d_bound, idx->h_radius.p, (size_t)nq * 4, hipMemcpyHostToDevice, idx->stream));   // over the staged FLT_MAX
+        HIPCHECK(idx->d_vals.ensure(b.entries));
+        HIPCHECK(idx->d_keys.ensure(b.entries));
+        HIPCHECK(idx->d_sidx.ensure(b.entries));
+        b.emit.vals = idx->d_vals.p;
+        b.emit.keys = idx->d_keys.p;
+        b.emit.sidx = idx->d_sidx.p;
+        HIPCHECK(launch_adc_scan(db, sum_mode, b.d_items, 0, (uint32_t)b.plan.items.size(), b.d_assign, ma, b.d_tables, b.d_bound, b.emit, idx->stream));
+        HIPCHECK(hipMemcpyAsync(idx->h_count.p, b.emit.count, (size_t)nq * 4, hipMemcpyDeviceToHost, idx->stream));
+        HIPCHECK(hipStreamSynchronize(idx->stream));
+        if (!plan_range_rerun(b.plan, idx->h_count.p)) break;
+        if (attempt) return fail(QADC_E_STATE, "a range pass kept more rows in its second scan than its first scan counted");
+        ++idx->reruns;
+        over = range_entries(b.plan.cap, kMaxEntries, &entries);
+        if (!over.empty()) return fail(QADC_E_CAPACITY, over);
+        fill_state(idx, b);
+        HIPCHECK(hipMemcpyAsync(idx->d_in.p, idx->h_in.p, b.o_assign, hipMemcpyHostToDevice, idx->stream));
+    }
+    const uint64_t held = lims.back();
+    uint64_t n_stored = 0;
+    uint32_t longest = 0;
+    for (int q = 0; q < nq; ++q) {
+        n_stored += idx->h_count.p[q];
+        longest = std::max(longest, idx->h_count.p[q]);
+    }
+    if (int rc = grow_device(idx->d_rkeys, held, held + n_stored, idx->stream)) return rc;
+    if (int rc = grow_device(idx->d_rvals, held, held + n_stored, idx->stream)) return rc;
+    if (longest > (uint32_t)kRangeSortLds) {
+        HIPCHECK(idx->d_tmp_a.ensure(b.entries));
+        HIPCHECK(idx->d_tmp_b.ensure(b.entries));
+    }
+    if (n_stored) {
+        HIPCHECK(launch_adc_range_sort(nq, b.emit, held, idx->d_rkeys.p, idx->d_rvals.p, idx->d_tmp_a.p, idx->d_tmp_b.p, idx->stream));
+        HIPCHECK(hipStreamSynchronize(idx->stream));
+    }
+    for (int q = 0; q < nq; ++q) lims.push_back(lims.back() + idx->h_count.p[q]);
+    return QADC_OK;
+}
+
+int check_range_args(const qadc_adc_index* idx, int nq, const float* radius, const uint64_t* lims, const qadc_adc_filter* const* filters) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (nq >= 1 && (!radius || !lims)) return fail(QADC_E_ARG, "radius [nq] and lims [nq + 1] are required");
+    return check_query_filters(idx, nq, filters);
+}
+
+// Closes a range call: the result is held (range_lims) and its row offsets go to the caller.
+int publish_range(qadc_adc_index* idx, std::vector<uint64_t>& lims, uint64_t* out) {
+    std::copy(lims.begin(), lims.end(), out);
+    idx->range_lims.swap(lims);
+    return QADC_OK;
+}
+
+// The passes of a range call on the caller's tables: host tables in sub-batches of the table budget (scan_host_tables' cut), device
+// tables in one.
+int range_scan_call(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, const float* d_tables, const float* radius,
+                    int sum_mode, const qadc_adc_filter* const* filters, uint64_t* lims_out) {
+    if (int rc = check_range_args(idx, nq, radius, lims_out, filters)) return rc;
+    if (int rc = check_query_args(idx, nq, ma, assign, d_tables ? static_cast<const void*>(d_tables) : tables, 1, sum_mode)) return rc;
+    DeviceGuard guard;
+    idx->range_lims.clear();
+    std::vector<uint64_t> lims(1, 0);
+    const int per = d_tables ? nq : queries_per_pass(idx, nq, ma);
+    const size_t per_query = (size_t)ma * idx->nsq * idx->centroids;
+    for (int q0 = 0; q0 < nq; q0 += per) {
+        const int n = std::min(per, nq - q0);
+        if (int rc = range_pass(idx, n, ma, assign + (size_t)q0 * ma, tables ? tables + (size_t)q0 * per_query : nullptr, d_tables, radius + q0,
+                                sum_mode, filters ? filters + q0 : nullptr, lims))
+            return rc;
+    }
+    return publish_range(idx, lims, lims_out);
+}
+
+// search_batch's feeders in front of range_pass, sub-batch by sub-batch.
+int range_search_call(qadc_adc_index* idx, int nq, const float* queries, int ma, const float* radius, int table_form, int sum_mode,
+                      const qadc_adc_filter* const* filters, int32_t* assign_out, uint64_t* lims_out, bool d_side) {
+    if (int rc = check_range_args(idx, nq, radius, lims_out, filters)) return rc;
+    DeviceGuard guard;
+    Feeders f;
+    if (int rc = resolve_feeders(idx, nq, queries, ma, table_form, sum_mode, &f)) return rc;
+    idx->range_lims.clear();
+    std::vector<uint64_t> lims(1, 0);
+    const int per = queries_per_pass(idx, nq, ma);
+    HIPCHECK(idx->d_tables.ensure((size_t)per * ma * idx->nsq * idx->centroids));
+    if (int rc = enqueue_assign(idx, f, nq, queries, ma, sum_mode, d_side)) return rc;
+    if (int rc = enqueue_tables(idx, f, 0, per, ma, table_form, sum_mode)) return rc;
+    if (int rc = wait_assign(idx, f, ma)) return rc;
+    if (assign_out) std::memcpy(assign_out, idx->h_assign.p, (size_t)nq * ma * 4);
+    for (int q0 = 0; q0 < nq; q0 += per) {
+        const int n = std::min(per, nq - q0);
+        if (q0)   // (the pass before it has been waited for: the table buffer is free)
+            if (int rc = enqueue_tables(idx, f, q0, n, ma, table_form, sum_mode)) return rc;
+        if (int rc = range_pass(idx, n, ma, idx->h_assign.p + (size_t)q0 * ma, nullptr, idx->d_tables.p, radius + q0, sum_mode,
+                                filters ? filters + q0 : nullptr, lims))
+            return rc;
+    }
+    return publish_range(idx, lims, lims_out);
+}
+
+// The held result into the caller's buffers: host memory by copies, device memory by a kernel (launch_adc_copy_words).
+int range_collect(qadc_adc_index* idx, uint64_t capacity, uint32_t* keys, float* values, bool d_side) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (idx->range_lims.empty()) return fail(QADC_E_STATE, "no range result is held: call qadc_adc_range_scan* or qadc_adc_range_search* first");
+    const uint64_t n = idx->range_lims.back();
+    if (capacity < n)
+        return fail(QADC_E_CAPACITY, "the range result has " + std::to_string(n) + " rows (lims[nq]); the buffers hold " + std::to_string(capacity));
+    if (n == 0) return QADC_OK;
+    if (!keys || !values) return fail(QADC_E_ARG, "keys and values are required");
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(idx->device));
+    if (d_side) {
+        HIPCHECK(launch_adc_copy_words(idx->d_rkeys.p, keys, n, idx->stream));
+        HIPCHECK(launch_adc_copy_words(idx->d_rvals.p, values, n, idx->stream));
+    } else {
+        HIPCHECK(hipMemcpyAsync(keys, idx->d_rkeys.p, n * 4, hipMemcpyDeviceToHost, idx->stream));
+        HIPCHECK(hipMemcpyAsync(values, idx->d_rvals.p, n * 4, hipMemcpyDeviceToHost, idx->stream));
+    }
+    HIPCHECK(hipStreamSynchronize(idx->stream));
+    return QADC_OK;
+}
+
 // ---- db_add: qadc_adc_index_add_vectors, _reserve, _read_partition ----
 
 // Puts the owned database into the layout of `plan` on the index's stream: new buffers, every partition moved by one kernel, the
@@ -1226,6 +1376,9 @@ int qadc_adc_index_destroy(qadc_adc_index* idx) {
     idx->d_hkeys.release();
     idx->d_hvals.release();
     idx->d_hsizes.release();
+    idx->d_rkeys.release();
+    idx->d_rvals.release();
+    idx->h_radius.release();
     idx->h_in.release();
     idx->h_count.release();
     idx->h_packed.release();
@@ -1511,6 +1664,36 @@ int qadc_adc_search_candidates_filtered(qadc_adc_index* idx, int nq, const float
                                         uint64_t cand_capacity, uint32_t* cand_keys, float* cand_vals, uint64_t* offsets, int32_t* assign_out,
                                         const qadc_adc_filter* const* filters) {
     return search_candidates_call(idx, nq, queries, ma, R, table_form, sum_mode, cand_capacity, cand_keys, cand_vals, offsets, assign_out, filters);
+}
+
+int qadc_adc_range_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, const float* radius, int sum_mode,
+                        const qadc_adc_filter* const* filters, uint64_t* lims) {
+    if (!tables) return fail(QADC_E_ARG, "assign and tables are required");
+    return range_scan_call(idx, nq, ma, assign, tables, nullptr, radius, sum_mode, filters, lims);
+}
+
+int qadc_adc_range_scan_device(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, const float* radius,
+                               int sum_mode, const qadc_adc_filter* const* filters, uint64_t* lims) {
+    if (!d_tables) return fail(QADC_E_ARG, "assign and tables are required");
+    return range_scan_call(idx, nq, ma, assign, nullptr, d_tables, radius, sum_mode, filters, lims);
+}
+
+int qadc_adc_range_search(qadc_adc_index* idx, int nq, const float* queries, int ma, const float* radius, int table_form, int sum_mode,
+                          const qadc_adc_filter* const* filters, int32_t* assign_out, uint64_t* lims) {
+    return range_search_call(idx, nq, queries, ma, radius, table_form, sum_mode, filters, assign_out, lims, false);
+}
+
+int qadc_adc_range_search_device(qadc_adc_index* idx, int nq, const float* d_queries, int ma, const float* radius, int table_form,
+                                 int sum_mode, const qadc_adc_filter* const* filters, int32_t* assign_out, uint64_t* lims) {
+    return range_search_call(idx, nq, d_queries, ma, radius, table_form, sum_mode, filters, assign_out, lims, true);
+}
+
+int qadc_adc_range_collect(qadc_adc_index* idx, uint64_t capacity, uint32_t* keys, float* values) {
+    return range_collect(idx, capacity, keys, values, false);
+}
+
+int qadc_adc_range_collect_device(qadc_adc_index* idx, uint64_t capacity, uint32_t* d_keys, float* d_values) {
+    return range_collect(idx, capacity, d_keys, d_values, true);
 }
 
 int qadc_adc_search_tables(qadc_adc_index* idx, int nq, const float* queries, int ma, int table_form, int sum_mode, int32_t* assign_out,

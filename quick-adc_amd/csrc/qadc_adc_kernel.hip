@@ -568,6 +568,161 @@ __global__ __launch_bounds__(kWG) void adc_copy_words_kernel(const uint32_t* __r
 }
 
 // ---------------------------------------------------------------------------------------------
+// Range search: the scan kernels above under bound[q] = radius[q] leave every kept row of query q in its
+// region, in no order.  adc_range_sort_kernel: one workgroup per query sorts the region's (value, key) pairs ascending by the word
+// order_key(value) << 32 | key and writes them densely behind the queries before it: entry out_base + sum_{j<q} stored_j + i of
+// out_vals / out_keys (the offset is summed here, as adc_pack_kernel sums it: the host has the counts but uploads nothing).
+//   n <= kRangeSortLds  a bitonic sort of the words in LDS;
+//   longer segments     LSD radix passes of 8 bits over the 64 bits of the word through the global scratch tmp_a / tmp_b
+//                       [base[q] + i], scattered tile by tile like adc_order_kernel's.  One sweep first ORs and ANDs all words: a
+//                       digit in which OR and AND agree is the same in every entry — its histogram has one bin — and its pass, which
+//                       would move nothing, is skipped; the last pass that runs writes (value, key) instead of the word.  Equal words
+//                       are the same pair, so the result is a function of the multiset alone.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kWG) void adc_range_sort_kernel(Emit emit, unsigned long long out_base, uint32_t* __restrict__ out_keys,
+                                                             float* __restrict__ out_vals, unsigned long long* tmp_a,
+                                                             unsigned long long* tmp_b) {
+    __shared__ unsigned long long lkey[kRangeSortLds];
+    __shared__ unsigned long long s_off, s_or, s_and;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {
+        s_off = 0;
+        s_or = 0;
+        s_and = ~0ull;
+    }
+    __syncthreads();
+    unsigned long long part = 0;
+    for (uint32_t j = tid; j < q; j += kWG) part += min(emit.count[j], emit.cap[j]);
+    if (part) atomicAdd(&s_off, part);
+    __syncthreads();
+    const uint32_t n = min(emit.count[q], emit.cap[q]);
+    if (n == 0) return;
+    const size_t region = emit.base[q];
+    const float* __restrict__ vals = emit.vals + region;
+    const uint32_t* __restrict__ keys = emit.keys + region;
+    float* __restrict__ ov = out_vals + out_base + s_off;
+    uint32_t* __restrict__ ok = out_keys + out_base + s_off;
+    auto word = [&](uint32_t i) { return ((unsigned long long)order_key(vals[i]) << 32) | keys[i]; };
+
+    if (n <= (uint32_t)kRangeSortLds) {
+        uint32_t n2 = 1;
+        while (n2 < n) n2 <<= 1;
+        for (uint32_t i = tid; i < n2; i += kWG) lkey[i] = i < n ? word(i) : ~0ull;   // (~0 is the image of a NaN: no kept row has it)
+        __syncthreads();
+        for (uint32_t k = 2; k <= n2; k <<= 1)
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                for (uint32_t t = tid; t < n2 / 2; t += kWG) {
+                    const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+                    const unsigned long long a = lkey[i], b = lkey[p];
+                    if ((a > b) == ((i & k) == 0)) { lkey[i] = b; lkey[p] = a; }
+                }
+                __syncthreads();
+            }
+        for (uint32_t i = tid; i < n; i += kWG) {
+            const unsigned long long e = lkey[i];
+            ov[i] = order_val((uint32_t)(e >> 32));
+            ok[i] = (uint32_t)e;
+        }
+        return;
+    }
+
+    {                                                            // which digits differ anywhere
+        unsigned long long o = 0, a = ~0ull;
+        for (unsigned long long i = tid; i < n; i += kWG) {
+            const unsigned long long e = word((uint32_t)i);
+            o |= e;
+            a &= e;
+        }
+        atomicOr(&s_or, o);
+        atomicAnd(&s_and, a);
+    }
+    __syncthreads();
+    const unsigned long long differ = s_or ^ s_and;
+    uint32_t active = 0;                                         // bit d: digit d (bits [8d, 8d + 8) of the word) gets a pass
+    for (int d = 0; d < 8; ++d)
+        if ((differ >> (8 * d)) & 255ull) active |= 1u << d;
+    if (active == 0) {                                           // every entry is the same pair
+        for (unsigned long long i = tid; i < n; i += kWG) {
+            ov[i] = vals[i];
+            ok[i] = keys[i];
+        }
+        return;
+    }
+
+    uint32_t* hist = reinterpret_cast<uint32_t*>(lkey);          // [256] entries of the digit, then its running write position
+    uint32_t* wcount = hist + 256;                               // [4][256] entries of the digit in each wave of the tile
+    unsigned long long* ta = tmp_a + region;
+    unsigned long long* tb = tmp_b + region;
+    const uint32_t lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1;
+    int pass = 0;
+    for (int digit = 0; digit < 8; ++digit) {
+        if (!((active >> digit) & 1u)) continue;                 // (the same in every lane)
+        const unsigned long long* src = (pass & 1) ? ta : tb;    // the first pass reads the region itself
+        unsigned long long* dst = (pass & 1) ? tb : ta;
+        const int shift = 8 * digit;
+        const bool first = pass == 0, last = (active >> (digit + 1)) == 0;
+        ++pass;
+        auto entry = [&](uint32_t i) { return first ? word(i) : src[i]; };
+        hist[tid] = 0;
+        for (int w = 0; w < 4; ++w) wcount[w * 256 + tid] = 0;
+        __syncthreads();
+        for (unsigned long long i = tid; i < n; i += kWG) atomicAdd(&hist[(uint32_t)(entry((uint32_t)i) >> shift) & 255u], 1u);
+        __syncthreads();
+        if (tid < 64) {                                          // wave 0: exclusive prefix sums, lane l holds digits 4l .. 4l+3
+            const uint32_t h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+            uint32_t incl = h0 + h1 + h2 + h3;
+            for (int step = 1; step < 64; step <<= 1) {
+                const uint32_t o = __shfl_up(incl, step);
+                if (tid >= (uint32_t)step) incl += o;
+            }
+            const uint32_t excl = incl - (h0 + h1 + h2 + h3);
+            hist[4 * tid] = excl;
+            hist[4 * tid + 1] = excl + h0;
+            hist[4 * tid + 2] = excl + h0 + h1;
+            hist[4 * tid + 3] = excl + h0 + h1 + h2;
+        }
+        __syncthreads();
+        for (unsigned long long t0 = 0; t0 < n; t0 += kWG) {     // (64-bit: n may be within 256 of 2^32)
+            const bool valid = t0 + tid < n;
+            const uint32_t i = (uint32_t)(t0 + tid);
+            const unsigned long long e = valid ? entry(i) : 0ull;
+            const uint32_t d = (uint32_t)(e >> shift) & 255u;
+            unsigned long long same = __ballot(valid);           // lanes of this wave with the same digit
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const bool bit = (d >> b) & 1u;
+                const unsigned long long m = __ballot(bit);
+                same &= bit ? m : ~m;
+            }
+            const uint32_t rank = (uint32_t)__popcll(same & below);
+            if (valid && rank == 0) wcount[wave * 256 + d] = (uint32_t)__popcll(same);
+            __syncthreads();
+            if (valid) {
+                uint32_t pos = hist[d] + rank;
+                for (uint32_t w = 0; w < wave; ++w) pos += wcount[w * 256 + d];
+                if (last) {
+                    ov[pos] = order_val((uint32_t)(e >> 32));
+                    ok[pos] = (uint32_t)e;
+                } else {
+                    dst[pos] = e;
+                }
+            }
+            __syncthreads();
+            {                                                    // thread d owns digit d: advance its position, clear the counts
+                uint32_t c = 0;
+                for (int w = 0; w < 4; ++w) {
+                    c += wcount[w * 256 + tid];
+                    wcount[w * 256 + tid] = 0;
+                }
+                hist[tid] += c;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Feeders: what nns_engine(_batch)::process_query does before query_scan (query_common.hpp:194-213, 283-297), for 256 or 65536
 // centroids per sub-quantizer, and base_pq::encode_multiple_vectors (quantizers.hpp:222-245) for 256.
 // Arithmetic entry for entry that of build_tables_kernel (csrc/qadc_kernels.hip) and of the host twin pq_bytes::tables /
@@ -1254,6 +1409,13 @@ hipError_t launch_adc_replay(int nq, int R, Emit emit, const float* ovals, const
     const int waves = (int)std::max<size_t>(1, std::min<size_t>(kWG / 64, (60 * 1024) / per_wave));
     hipLaunchKernelGGL(adc_replay_kernel, dim3((nq + waves - 1) / waves), dim3(64 * waves), waves * per_wave, s, nq, R, emit.count,
                        emit.cap, emit.base, ovals, okeys, keys, values, sizes);
+    return hipGetLastError();
+}
+
+hipError_t launch_adc_range_sort(int nq, Emit emit, uint64_t out_base, uint32_t* out_keys, float* out_vals, uint64_t* tmp_a, uint64_t* tmp_b,
+                                 hipStream_t s) {
+    hipLaunchKernelGGL(adc_range_sort_kernel, dim3(nq), dim3(kWG), 0, s, emit, (unsigned long long)out_base, out_keys, out_vals,
+                       reinterpret_cast<unsigned long long*>(tmp_a), reinterpret_cast<unsigned long long*>(tmp_b));
     return hipGetLastError();
 }
 

@@ -82,6 +82,14 @@ hipError_t launch_adc_order(int nq, Emit emit, int bits, float* ovals, uint32_t*
 // sizes [nq] (device memory) = the heap's arrays.  R <= kAdcReplayMaxR.
 hipError_t launch_adc_replay(int nq, int R, Emit emit, const float* ovals, const uint32_t* okeys, uint32_t* keys, float* values,
                              int32_t* sizes, hipStream_t s);
+// Range search.
+constexpr int kRangeSortLds = 4096;   // entries adc_range_sort_kernel sorts in LDS (QADC_ADC_RANGE_SORT_LDS; 8 bytes each: 32 KiB of the CU's
+                                      // 160 leave four workgroups resident); longer segments take radix passes through global scratch
+// Sorts the stored (value, key) pairs of every query ascending by order_key(value) << 32 | key and writes query q's densely to
+// out_vals / out_keys [out_base + sum_{j<q} stored_j + i].  tmp_a, tmp_b: scratch of as many entries as the regions, touched only by
+// queries that stored more than kRangeSortLds entries (else may be null).
+hipError_t launch_adc_range_sort(int nq, Emit emit, uint64_t out_base, uint32_t* out_keys, float* out_vals, uint64_t* tmp_a, uint64_t* tmp_b,
+                                 hipStream_t s);
 // dst[i] = src[i] for `words` 32-bit words, by a kernel (either side may be memory this library's HIP runtime did not allocate).
 hipError_t launch_adc_copy_words(const void* src, void* dst, size_t words, hipStream_t s);
 

@@ -88,5 +88,72 @@ inline Plan plan_levels(const uint32_t* sizes, int nq, int ma, const int32_t* as
     return p;
 }
 
+// ---- range search: one level over every query's whole scan order, scanned under a bound that never moves ----
+constexpr uint32_t kRangeFirstCap = 4096;   // entries of a query's region in the first attempt (at most its code count)
+
+// Adds up the regions of `cap`; refuses (not empty: why) above max_entries.
+inline std::string range_entries(const std::vector<uint32_t>& cap, uint64_t max_entries, uint64_t* entries) {
+    uint64_t n = 0;
+    for (uint32_t c : cap) n += c;
+    *entries = n;
+    if (n > max_entries)
+        return "the result regions of this pass need " + std::to_string(n) + " entries (at most " + std::to_string(max_entries) +
+               "): split the batch or lower the radii";
+    return std::string();
+}
+
+// The plan of a range pass: ONE level [0, max_total) whose runs are cut the way plan_levels cuts a level, and a first-attempt region of
+// min(total[q], kRangeFirstCap) entries per query (0 for a query that probes no code).  Refuses like plan_levels above 2^32 - 1 codes
+// per query.
+inline Plan plan_range(const uint32_t* sizes, int nq, int ma, const int32_t* assign) {
+    Plan p;
+    p.total.assign(nq, 0);
+    uint64_t span = 0;
+    for (int q = 0; q < nq; ++q) {
+        for (int a = 0; a < ma; ++a) p.total[q] += sizes[assign[(size_t)q * ma + a]];
+        if (p.total[q] > 0xffffffffull) {
+            p.refused = "query " + std::to_string(q) + " probes " + std::to_string(p.total[q]) + " codes: at most 2^32 - 1 per query";
+            return p;
+        }
+        p.max_total = std::max(p.max_total, p.total[q]);
+        span += p.total[q];
+    }
+    p.edge = {0, std::max<uint64_t>(p.max_total, 1)};
+    const uint64_t run = std::min<uint64_t>(kRunMax, std::max<uint64_t>(kRunMin, align_up((span + kWgTarget - 1) / kWgTarget, 1024)));
+    p.level_first.push_back(0);
+    for (int q = 0; q < nq; ++q) {
+        uint64_t pbase = 0;
+        for (int a = 0; a < ma; ++a) {
+            const uint64_t sz = sizes[assign[(size_t)q * ma + a]];
+            for (uint64_t s = 0; s < sz; s += run) {
+                Item it{};
+                it.query = (uint32_t)q;
+                it.slot = (uint32_t)a;
+                it.start = (uint32_t)s;
+                it.count = (uint32_t)std::min<uint64_t>(run, sz - s);
+                it.sbase = (uint32_t)(pbase + s);
+                p.items.push_back(it);
+            }
+            pbase += sz;
+        }
+    }
+    p.level_first.push_back((uint32_t)p.items.size());
+    p.cap.resize(nq);
+    for (int q = 0; q < nq; ++q) p.cap[q] = (uint32_t)std::min<uint64_t>(p.total[q], kRangeFirstCap);
+    return p;
+}
+
+// After an attempt: count[q] = rows query q emitted, counted past its region too.  Radius and filters are fixed, so the count is exact
+// and the re-run's region holds exactly that many: a pass scans at most twice.  True: a region overflowed and the pass must re-run.
+inline bool plan_range_rerun(Plan& p, const uint32_t* count) {
+    bool overflow = false;
+    for (size_t q = 0; q < p.cap.size(); ++q)
+        if (count[q] > p.cap[q]) {
+            overflow = true;
+            p.cap[q] = count[q];   // (<= total[q]: a row is counted once)
+        }
+    return overflow;
+}
+
 }  // namespace adc
 }  // namespace qadc

@@ -21,6 +21,8 @@
 // set_filter(f): the scans drop the rows whose key does not pass the qadc_adc_filter f (qadc_adc_index_set_filter).
 // set_query_filters(per_query): one filter per query of the caller's query array on top of it (qadc_adc_search_filtered,
 // qadc_adc_search_candidates_filtered).
+// range_search(...): every row below a radius per query instead of the R best, under the same filters (qadc_adc_range_search;
+// DESIGN.md section 11.13).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -182,6 +184,22 @@ struct adc_search_engine_hip {
         for (int t = 0; t < bh.capacity(); ++t) bh.push(0, std::numeric_limits<float>::max() - t);   // "Fill binary heap"
         for (std::uint64_t i = offsets[b]; i < offsets[b + 1]; ++i) bh.push(cand_keys[i], cand_vals[i]);
         metrics.scan_us = ustime() - t0;   // (index, rotation and tables are part of the one GPU call)
+    }
+
+    // Range search (qadc_adc_range_search): for queries [query_i, query_i + nq) of `queries`, every row of the
+    // ma nearest partitions whose candidate is < radius[q] and whose key passes set_filter's filter and the query's own
+    // (set_query_filters, indexed by query_i + q), ascending by (candidate, key).  lims [nq + 1]: query q's rows are
+    // [lims[q], lims[q + 1]) of keys / values.  The batch size and R of the engine play no part.
+    void range_search(int query_i, const float* queries, int nq, const float* radius, std::vector<std::uint64_t>& lims,
+                      std::vector<std::uint32_t>& keys, std::vector<float>& values) {
+        lims.assign((std::size_t)nq + 1, 0);
+        std::vector<std::int32_t> probes((std::size_t)nq * ma);
+        if (qadc_adc_range_search(index, nq, queries + (std::size_t)query_i * db.pq->dim, ma, radius, table_form, sum_mode, batch_filters(query_i),
+                                  probes.data(), lims.data()) != QADC_OK)
+            die("range_search");
+        keys.resize(lims[nq]);
+        values.resize(lims[nq]);
+        if (qadc_adc_range_collect(index, lims[nq], keys.data(), values.data()) != QADC_OK) die("range_search");
     }
 };
 

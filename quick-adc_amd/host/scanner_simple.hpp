@@ -11,6 +11,7 @@
 //   scanner_simple      db_query.cpp:17-46: R sentinel pushes FLT_MAX - t, then every probed partition in assign[] order
 //   key_filter          no reference counterpart: the allow / exclude key set the scan loops skip rows by (set_filter), and a
 //                       second one of the query's own chained to it (set_query_filter): a row must pass both
+//   range_scan          no reference counterpart: every row below a radius, sorted by (candidate, key) (range_standard, range_4f)
 // Float sums take the grouping of the reference AS COMPILED with its -ffast-math (host/float_sum.hpp; float_sum_mode() = 0
 // gives the source order); this file itself is built without -ffast-math.  The oracle's orc_scan_standard_u8 /
 // orc_candidates_f32 / orc_tables_direct, pinned to the reference build, are the checkers (tests/test_scanner_hip_cpp.py).
@@ -18,6 +19,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <limits>
 #include <vector>
@@ -109,6 +111,80 @@ scan_func get_scan_func(const Pq& pq) {
     std::exit(1);
 }
 
+// ---- range search: every row whose candidate lies below a radius (no reference counterpart; the written definition of
+// qadc_adc_range_*, include/qadc.h) ----
+// order_image: the order-preserving integer image of a float (order_key in csrc/qadc_adc_kernel.hip): -x < -y < -0 < +0 < y < x.
+inline std::uint32_t order_image(float v) {
+    std::uint32_t u;
+    std::memcpy(&u, &v, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+inline float order_image_value(std::uint32_t k) {
+    const std::uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float v;
+    std::memcpy(&v, &u, 4);
+    return v;
+}
+inline std::uint64_t range_word(unsigned key, float candidate) { return ((std::uint64_t)order_image(candidate) << 32) | key; }
+
+// The scan loops of a range query, beside scan_standard / scan_4f: the same candidate (adc_sum grouping, float_sum_mode), kept iff
+// candidate < radius as a float compare — a NaN on either side keeps nothing, a candidate equal to the radius is not kept — and
+// appended to `kept` as range_word(key, candidate).
+template <typename T, int NSQ>
+void range_standard(const std::uint8_t* pqcodes_, const unsigned* labels, const unsigned pqcodes_count, const float* dists,
+                    float radius, std::vector<std::uint64_t>& kept, const key_filter* filter = nullptr) {
+    const int NCENT = 1 << (sizeof(T) * 8);
+    const T* const pqcodes = reinterpret_cast<const T*>(pqcodes_);
+    for (unsigned i = 0; i < pqcodes_count; ++i) {
+        const unsigned key = labels != nullptr ? labels[i] : i;
+        if (filter && filter->drops(key)) continue;
+        const T* const code = pqcodes + (std::size_t)i * NSQ;
+        float t[NSQ];
+        for (int sq = 0; sq < NSQ; ++sq) t[sq] = dists[sq * NCENT + code[sq]];
+        const float candidate = adc_sum<NSQ>(t);
+        if (candidate < radius) kept.push_back(range_word(key, candidate));
+    }
+}
+
+template <int NSQ>
+void range_4f(const std::uint8_t* pqcodes, const unsigned* labels, const unsigned pqcodes_count, const float* dists, float radius,
+              std::vector<std::uint64_t>& kept, const key_filter* filter = nullptr) {
+    for (unsigned i = 0; i < pqcodes_count; ++i) {
+        const unsigned key = labels != nullptr ? labels[i] : i;
+        if (filter && filter->drops(key)) continue;
+        const std::uint8_t* const code = pqcodes + (std::size_t)i * (NSQ / 2);
+        float t[NSQ];
+        for (int b = 0; b < NSQ / 2; ++b) {
+            t[2 * b] = dists[(2 * b) * 16 + (code[b] & 0xf)];
+            t[2 * b + 1] = dists[(2 * b + 1) * 16 + (code[b] >> 4)];
+        }
+        const float candidate = adc_sum<NSQ>(t);
+        if (candidate < radius) kept.push_back(range_word(key, candidate));
+    }
+}
+
+typedef void (*range_func)(const std::uint8_t*, const unsigned*, unsigned, const float*, float, std::vector<std::uint64_t>&,
+                           const key_filter*);
+
+template <typename Pq>
+range_func get_range_func(const Pq& pq) {   // the shapes of get_scan_func, which has refused every other one before this is asked
+    if (pq.sq_count == 16 && pq.sq_bits == 4) return range_4f<16>;
+    if (pq.sq_count == 32 && pq.sq_bits == 4) return range_4f<32>;
+    if (pq.sq_count == 4 && pq.sq_bits == 8) return range_standard<std::uint8_t, 4>;
+    if (pq.sq_count == 8 && pq.sq_bits == 8) return range_standard<std::uint8_t, 8>;
+    if (pq.sq_count == 16 && pq.sq_bits == 8) return range_standard<std::uint8_t, 16>;
+    if (pq.sq_count == 2 && pq.sq_bits == 16) return range_standard<std::uint16_t, 2>;
+    if (pq.sq_count == 4 && pq.sq_bits == 16) return range_standard<std::uint16_t, 4>;
+    if (pq.sq_count == 8 && pq.sq_bits == 16) return range_standard<std::uint16_t, 8>;
+    return nullptr;
+}
+
+// The result of one range query: the kept (key, candidate) pairs ascending by range_word.
+struct range_result {
+    std::vector<unsigned> keys;
+    std::vector<float> values;
+};
+
 // base_pq with whole-byte codes: sq_bits 8 (one byte per sub-quantizer) or 16 (two, little endian).
 struct pq_bytes {
     int sq_count, sq_bits, dim;
@@ -185,6 +261,7 @@ struct scanner_simple {
     typedef float_heap BhType;
     Db* db = nullptr;
     scan_func scan = nullptr;
+    range_func range = nullptr;
     const key_filter* filter = nullptr;                          // set_filter: not owned, null = the reference's scan
     void set_filter(const key_filter* f) { filter = f; }
     const key_filter* query_filter = nullptr;                    // set_query_filter: the filter of the query scanned next, on top of `filter`
@@ -192,6 +269,7 @@ struct scanner_simple {
     void prepare_database(Db& database) {
         db = &database;
         scan = get_scan_func(*database.pq);
+        range = get_range_func(*database.pq);
     }
     template <typename Metrics>
     void query_scan(const float*, int* assign, int ma, float* tables, int table_dim, BhType& bh, Metrics&) {
@@ -206,6 +284,30 @@ struct scanner_simple {
             db->get_partition(assign[a], codes, labels, count);
             scan(codes, labels, count, tables, bh, pass);
             tables += table_dim;
+        }
+    }
+    // Range search: every row of the probed partitions, in assign[] order, that passes the chained filter
+    // as in query_scan and whose candidate is < radius; `out` = the kept pairs ascending by (order_image(candidate) << 32) | key.
+    // Nothing is deduplicated: the result depends only on the multiset of kept (candidate, key) pairs.
+    void range_scan(int* assign, int ma, float* tables, int table_dim, float radius, range_result& out) {
+        const std::uint8_t* codes;
+        unsigned* labels;
+        unsigned count;
+        const bool two = filter != nullptr && query_filter != nullptr;
+        const key_filter both = two ? filter->chained(query_filter) : key_filter(key_filter::exclude, nullptr, 0);
+        const key_filter* const pass = two ? &both : filter != nullptr ? filter : query_filter;
+        std::vector<std::uint64_t> kept;
+        for (int a = 0; a < ma; ++a) {
+            db->get_partition(assign[a], codes, labels, count);
+            range(codes, labels, count, tables, radius, kept, pass);
+            tables += table_dim;
+        }
+        std::sort(kept.begin(), kept.end());
+        out.keys.resize(kept.size());
+        out.values.resize(kept.size());
+        for (std::size_t i = 0; i < kept.size(); ++i) {
+            out.keys[i] = (unsigned)kept[i];
+            out.values[i] = order_image_value((std::uint32_t)(kept[i] >> 32));
         }
     }
 };

@@ -15,6 +15,7 @@
 // qadc_adc_index_set_finish) and its arrays are pushed into the caller's empty heap in array order, which rebuilds them exactly
 // (no entry of a heap's array exceeds its parent, so none moves); the default is the host finish, the candidate stream below.
 // set_filter(f): the scans drop the rows whose key does not pass the qadc_adc_filter f (qadc_adc_index_set_filter).
+// range_scan(...): every row below a radius instead of the R best (qadc_adc_range_scan).
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -168,6 +169,23 @@ struct scanner_simple_hip {
         if (rc != QADC_OK) die("query_scan");
         for (int t = 0; t < bh.capacity(); ++t) bh.push(0, std::numeric_limits<float>::max() - t);   // "Fill binary heap"
         for (std::uint64_t i = offsets[0]; i < offsets[1]; ++i) bh.push(cand_keys[i], cand_vals[i]);
+    }
+
+    // scanner_simple::range_scan (host/scanner_simple.hpp) on the GPU: every row of the probed partitions whose
+    // candidate is < radius and whose key passes set_filter's filter and `query_filter` (null: none), ascending by (candidate, key),
+    // into keys / values (qadc_adc_range_scan, qadc_adc_range_collect).
+    void range_scan(int* assign, int ma, float* tables, int table_dim, float radius, std::vector<std::uint32_t>& keys,
+                    std::vector<float>& values, const qadc_adc_filter* query_filter = nullptr) {
+        if (table_dim != table_floats) {
+            std::cerr << "range_scan: table_dim " << table_dim << " is not " << table_floats << " (sq_count * centroids)" << std::endl;
+            std::exit(1);
+        }
+        std::uint64_t lims[2] = {0, 0};
+        if (qadc_adc_range_scan(index, 1, ma, assign, tables, &radius, sum_mode, query_filter ? &query_filter : nullptr, lims) != QADC_OK)
+            die("range_scan");
+        keys.resize(lims[1]);
+        values.resize(lims[1]);
+        if (qadc_adc_range_collect(index, lims[1], keys.data(), values.data()) != QADC_OK) die("range_scan");
     }
 };
 

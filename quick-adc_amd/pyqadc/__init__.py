@@ -54,6 +54,8 @@ SYMBOLS = [
     "qadc_adc_search_filtered", "qadc_adc_search_device_filtered", "qadc_adc_search_candidates_filtered",
     "qadc_refine_create", "qadc_refine_destroy", "qadc_refine_add", "qadc_refine_add_device", "qadc_refine_reserve", "qadc_refine_info",
     "qadc_refine_relocations", "qadc_refine_rerank", "qadc_refine_rerank_device",
+    "qadc_adc_range_scan", "qadc_adc_range_scan_device", "qadc_adc_range_search", "qadc_adc_range_search_device",
+    "qadc_adc_range_collect", "qadc_adc_range_collect_device",
 ]
 
 
@@ -93,6 +95,7 @@ QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # inclu
 QADC_ADC_ENCODE16_CHUNK = 262144   # include/qadc.h: vectors qadc_adc_encode16_host encodes per pass
 QADC_ADC_ADD_CHUNK = 262144        # include/qadc.h: vectors qadc_adc_index_add_vectors encodes and appends per pass
 QADC_INDEX_ADD_CHUNK = 262144      # ... and qadc_index_add_vectors
+ADC_RANGE_SORT_LDS = 4096          # include/qadc.h QADC_ADC_RANGE_SORT_LDS: rows of a range query sorted in LDS; more take radix passes
 
 
 class QadcError(RuntimeError):
@@ -259,6 +262,13 @@ def lib():
         for name in ("qadc_adc_query_scan", "qadc_adc_query_scan_device", "qadc_adc_query_scan_candidates", "qadc_adc_search",
                      "qadc_adc_search_device", "qadc_adc_search_candidates"):   # the plain form's arguments, then filters [nq]
             getattr(L, name + "_filtered").argtypes = getattr(L, name).argtypes + [C.POINTER(C.c_void_p)]
+        filt = C.POINTER(C.c_void_p)
+        L.qadc_adc_range_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, f32p, f32p, C.c_int, filt, u64p]
+        L.qadc_adc_range_scan_device.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, C.c_void_p, f32p, C.c_int, filt, u64p]
+        L.qadc_adc_range_search.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, filt, i32p, u64p]
+        L.qadc_adc_range_search_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, f32p, C.c_int, C.c_int, filt, i32p, u64p]
+        L.qadc_adc_range_collect.argtypes = [C.c_void_p, C.c_uint64, u32p, f32p]
+        L.qadc_adc_range_collect_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.qadc_refine_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
         L.qadc_refine_destroy.argtypes = [C.c_void_p]
         L.qadc_refine_add.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32]
@@ -1687,6 +1697,97 @@ class AdcIndex:
         _check(self._scan_call("qadc_adc_query_scan_device", fl, self._h, nq, ma, _p(assign, i32p), t.data_ptr(), R, sum_mode, keys.data_ptr(),
                                vals.data_ptr(), sizes.data_ptr()))
         return keys, vals, sizes
+
+    # ---- range search: every row below a radius, sorted on the GPU (qadc_adc_range_*) ----
+    @staticmethod
+    def _radius(radius, nq):
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (nq,)) if np.ndim(radius) == 0 else radius, np.float32)
+        if r.shape != (nq,):
+            raise ValueError("radius is a scalar or has one entry per query (%d), not shape %s" % (nq, r.shape))
+        return r
+
+    def range_collect_raw(self, capacity):
+        """The C call as it is: -> (rc, keys [capacity], values [capacity])"""
+        keys = np.zeros(max(capacity, 1), np.uint32)
+        vals = np.zeros(max(capacity, 1), np.float32)
+        return lib().qadc_adc_range_collect(self._h, capacity, _p(keys, u32p), _p(vals, f32p)), keys, vals
+
+    def range_collect(self, lims=None):
+        """qadc_adc_range_collect: (keys uint32, values float32) of the range result the index holds, any number of times; lims: the
+        array the range call returned (default: the last one made through this object)."""
+        n = int(lims[-1]) if lims is not None else getattr(self, "_range_rows", 0)
+        rc, keys, vals = self.range_collect_raw(n)
+        _check(rc)
+        return keys[:n], vals[:n]
+
+    def _range_collect_device(self, lims):
+        import torch
+        dev = torch.device("cuda", self.device)
+        n = int(lims[-1])
+        keys = torch.zeros((n,), dtype=torch.int32, device=dev)          # the uint32 keys' bits
+        vals = torch.zeros((n,), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()                     # the zero fills are complete before the call
+        _check(lib().qadc_adc_range_collect_device(self._h, n, keys.data_ptr(), vals.data_ptr()))
+        return keys, vals
+
+    def range_scan(self, assign, tables, radius, sum_mode=1, filters=None):
+        """assign [nq][ma], tables [nq][ma][table_dim], radius a scalar or [nq] -> (lims int64 [nq+1], keys uint32, values float32): for
+        query q, rows [lims[q], lims[q+1]) = every row of its probed partitions whose candidate is < radius[q] (a float compare: NaN keeps
+        nothing) and whose key passes set_filter's filter and filters[q], ascending by (candidate, key); scanner_simple::range_scan."""
+        assign, tables, nq, ma = self._inputs(assign, tables)
+        r = self._radius(radius, nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        _check(lib().qadc_adc_range_scan(self._h, nq, ma, _p(assign, i32p), _p(tables, f32p), _p(r, f32p), sum_mode, self._filters(filters, nq),
+                                         _p(lims, u64p)))
+        self._range_rows = int(lims[-1])
+        keys, vals = self.range_collect(lims)
+        return lims.astype(np.int64), keys, vals
+
+    def range_search(self, queries, ma, radius, table_form=2, sum_mode=1, filters=None):
+        """queries [nq][dim] -> (lims, keys, values) as range_scan, on tables built on the GPU as search builds them."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        r = self._radius(radius, nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        _check(lib().qadc_adc_range_search(self._h, nq, _p(q, f32p), ma, _p(r, f32p), table_form, sum_mode, self._filters(filters, nq), None,
+                                           _p(lims, u64p)))
+        self._range_rows = int(lims[-1])
+        keys, vals = self.range_collect(lims)
+        return lims.astype(np.int64), keys, vals
+
+    def range_scan_device(self, assign, tables, radius, sum_mode=1, filters=None):
+        """tables: float32 tensor [nq][ma][table_dim] on the index's device -> (lims int64 [nq+1] numpy, keys int32 tensor carrying the
+        uint32 bits, values float32 tensor): range_scan without the upload of the tables or the download of the rows."""
+        assign = np.ascontiguousarray(assign, np.int32)
+        if assign.ndim == 1:
+            assign = assign.reshape(1, -1)
+        nq, ma = assign.shape
+        t = self._device_tensor(tables, (nq, ma, self.table_dim), "tables")
+        r = self._radius(radius, nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        import torch
+        torch.cuda.current_stream(t.device).synchronize()                # the tables are complete before the call
+        _check(lib().qadc_adc_range_scan_device(self._h, nq, ma, _p(assign, i32p), t.data_ptr(), _p(r, f32p), sum_mode,
+                                                self._filters(filters, nq), _p(lims, u64p)))
+        self._range_rows = int(lims[-1])
+        keys, vals = self._range_collect_device(lims)
+        return lims.astype(np.int64), keys, vals
+
+    def range_search_device(self, queries, ma, radius, table_form=2, sum_mode=1, filters=None):
+        """queries: float32 tensor [nq][dim] on the index's device -> (lims numpy, keys tensor, values tensor) as range_scan_device."""
+        if getattr(queries, "ndim", 0) != 2:
+            raise TypeError("queries must be a 2-d torch.Tensor")
+        nq = int(queries.shape[0])
+        q = self._device_tensor(queries, (nq, getattr(self, "dim", int(queries.shape[1]))), "queries")
+        r = self._radius(radius, nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        import torch
+        torch.cuda.current_stream(q.device).synchronize()                # the queries are complete before the call
+        _check(lib().qadc_adc_range_search_device(self._h, nq, q.data_ptr(), ma, _p(r, f32p), table_form, sum_mode, self._filters(filters, nq),
+                                                  None, _p(lims, u64p)))
+        self._range_rows = int(lims[-1])
+        keys, vals = self._range_collect_device(lims)
+        return lims.astype(np.int64), keys, vals
 
 
 QADC_REFINE_F32, QADC_REFINE_F16, QADC_REFINE_MAX_IN = 0, 1, 8192   # include/qadc.h

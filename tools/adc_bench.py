@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter,qfilter,refine] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter,qfilter,refine,range] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,filter] [--iters N] [--out FILE]
 
@@ -46,6 +46,10 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             T = 1, 16 and 1024.  Arm (a) = one search(filters=...) call; arm (b) = what there is without it: the batch grouped by
             filter, set_filter + search per group, the outputs scattered back.  The arms are asserted to return identical arrays and
             alternate in one process, under both finishes, with an unfiltered search() timed beside them for scale.
+  range     range search (not in the default legs), on the ivf_search database: range_search() of the 1024
+            queries with, per query, the radius that keeps about 100 rows (its own search() heap root at R = 100) and about 10^4 rows;
+            the re-runs per call and the rows kept; beside it search() at R = 100 under both finishes and the route it replaces,
+            search() at R = 65536 with a host threshold.
   refine    exact re-ranking (not in the default legs), on the ivf_search shape: recall@100 against exact
             float L2 of search() alone and of search_refined_device with r_in = 400 and 1000 over a float and a half store; the time
             of search_refined_device split into search_device and rerank_device; beside it a plain torch gather + (q - x)^2 sum +
@@ -246,6 +250,8 @@ def search_legs(legs, iters, res):
         f.close()
     if "qfilter" in legs:
         qfilter_leg(idx, len(part_of), queries, ma, iters, res, rng)
+    if "range" in legs:
+        range_leg(idx, queries, ma, iters, res)
     if "lone_search" in legs:
         q1 = queries[:1]
         med, best = timed(lambda: idx.search(q1, ma, R), max(iters, 50), warmup=5)
@@ -268,6 +274,48 @@ def search_legs(legs, iters, res):
         print("CPU scan_standard<uint8_t,8> over the same 24 partitions (%d codes), 1 thread, tables given (%s): %.1f us"
               % (res["lone_search_codes_probed"], "reference build" if po.have_ref_float() else "C restatement", med_c * 1e6), flush=True)
     idx.close()
+
+
+def range_leg(idx, queries, ma, iters, res):
+    """range_search() against the top-R calls it stands beside, in one process: each query's radius is the largest value of its own
+    search() heap at R = rows, so it keeps about `rows` rows (rows 100: the short segments sorted in LDS; 10^4: the radix passes)"""
+    nq = len(queries)
+    flt_max = np.float32(np.finfo(np.float32).max)
+    for rows in (100, 10000):
+        _, v, _, _ = idx.search(queries, ma, rows)
+        radius = np.ascontiguousarray(v.max(axis=1), np.float32)                 # the heap's root (FLT_MAX where fewer rows were probed)
+        before = idx.reruns()
+        lims, keys, vals = idx.range_search(queries, ma, radius)
+        reruns = int(idx.reruns() - before)
+        sizes = np.diff(lims)
+        full = radius < flt_max
+        assert (sizes[full] <= rows - 1).all() and (vals < np.repeat(radius, sizes)).all(), "a query keeps a row at or beyond its radius"
+        med, best = timed(lambda: idx.range_search(queries, ma, radius), max(5, iters))
+        tag = "range_%d" % rows
+        res[tag + "_range_search_ms"] = med * 1e3
+        res[tag + "_range_search_best_ms"] = best * 1e3
+        res[tag + "_reruns_per_call"] = reruns
+        res[tag + "_rows_min_median_max_total"] = [int(sizes.min()), float(np.median(sizes)), int(sizes.max()), int(sizes.sum())]
+        print("range_search() of %d queries, K=256 ma=%d on 10^6 codes, radius = the query's own R=%d heap root: %.2f ms (best %.2f), %d re-run(s) "
+              "per call, rows per query min %d median %.0f max %d, %d in all"
+              % (nq, ma, rows, med * 1e3, best * 1e3, reruns, sizes.min(), np.median(sizes), sizes.max(), sizes.sum()), flush=True)
+        if rows == 100:
+            host = lambda: idx.search(queries, ma, 100)
+            med_h, med_d = alternated(host, with_finish(idx, 1, host), max(5, iters))
+            res["range_search_R100_host_finish_ms"] = med_h * 1e3
+            res["range_search_R100_device_finish_ms"] = med_d * 1e3
+            print("search() at R = 100 beside it: host finish %.2f ms, device finish %.2f ms" % (med_h * 1e3, med_d * 1e3), flush=True)
+
+            def replaced():                                                     # the route range_search replaces: the widest heap, cut on the host
+                k, vv, _, _ = idx.search(queries, ma, 65536)
+                keep = vv < radius[:, None]
+                return k[keep], vv[keep], keep.sum(axis=1)
+            got = replaced()
+            med_r, best_r = timed(replaced, max(3, iters // 3), warmup=0)
+            res["range_100_search_R65536_threshold_ms"] = med_r * 1e3
+            res["range_100_search_R65536_threshold_same_counts"] = bool(np.array_equal(got[2], sizes))
+            print("search() at R = 65536 and a host threshold at the same radii: %.1f ms (best %.1f); same row counts as range_search: %s"
+                  % (med_r * 1e3, best_r * 1e3, res["range_100_search_R65536_threshold_same_counts"]), flush=True)
 
 
 def qfilter_leg(idx, n, queries, ma, iters, res, rng):
@@ -1214,7 +1262,7 @@ def main():
             print("the same alternated with query_scan_device (tables and heaps stay in device memory): %.2f ms against %.2f ms"
                   % (med_d * 1e3, med_h * 1e3), flush=True)
         idx.close()
-    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs:
+    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs or "range" in legs:
         search_legs(legs, a.iters, res)
     if "filter" in legs:
         filter_leg(8, a.iters, res, torch)

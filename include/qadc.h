@@ -862,6 +862,22 @@ int qadc_adc_index_add_vectors(qadc_adc_index* idx, const float* vectors, uint64
 /* The same with d_vectors [count][dim] in device memory of the index's device, complete before the call.  They are read where
  * they lie and only by kernels, so memory of another HIP runtime (a framework's tensor) is legal, as for qadc_adc_search_device. */
 int qadc_adc_index_add_vectors_device(qadc_adc_index* idx, const float* d_vectors, uint64_t count, uint32_t labels_offset, int sum_mode);
+/* qadc_adc_index_add_vectors with the caller's label of every vector (no reference counterpart: index_db::add_vectors numbers
+ * them).  labels [count], host memory.  The index after the call is the index after qadc_adc_index_add_vectors(vectors, count,
+ * labels_offset = 0, sum_mode) with the stored label i of every new row replaced by labels[i]: the same codes, partition sizes,
+ * order within a partition, passes, relocations and reserve behaviour.  Any uint32_t is a label, 0xFFFFFFFF included, and labels
+ * may repeat, as under qadc_adc_index_add_partitions (qadc_adc_index_remove_labels takes out every row that carries a label);
+ * there is no labels_offset, so the bound labels_offset + count <= 2^32 - 1 is a bound on count alone.  The labels of a pass are
+ * uploaded beside its vectors.
+ * QADC_E_STATE, the index left as it was: an index without a coarse quantizer (K = 0) or one that holds unlabelled partitions —
+ * its keys are positions.  Otherwise refused as qadc_adc_index_add_vectors is, with the same codes; labels NULL with count > 0 is
+ * QADC_E_ARG. */
+int qadc_adc_index_add_vectors_labelled(qadc_adc_index* idx, const float* vectors, const uint32_t* labels, uint64_t count, int sum_mode);
+/* The same with d_vectors [count][dim] and d_labels [count] in device memory of the index's device, complete before the call.
+ * Both are read where they lie and only by kernels (the labels by the scatter kernel of each pass), so memory of another HIP
+ * runtime is legal. */
+int qadc_adc_index_add_vectors_labelled_device(qadc_adc_index* idx, const float* d_vectors, const uint32_t* d_labels, uint64_t count,
+                                               int sum_mode);
 /* base_db::get_partition (databases.hpp:50-55) read back: rows [first, first + count) of partition `part` of an owned index,
  * however it was filled: codes_out [count][code bytes], labels_out [count] (either may be NULL; labels_out is filled only on a
  * labelled index).  A range outside the partition, a partition that does not exist, a view -> QADC_E_ARG. */
@@ -911,6 +927,14 @@ int qadc_index_add_vectors(qadc_index* idx, const float* vectors, uint64_t count
 /* The same with d_vectors [count][dim] in device memory of the index's device, complete before the call.  They are read where
  * they lie and only by kernels, so memory of another HIP runtime (a framework's tensor) is legal. */
 int qadc_index_add_vectors_device(qadc_index* idx, const float* d_vectors, uint64_t count, uint32_t labels_offset, int sum_mode);
+/* qadc_index_add_vectors with the caller's label of every vector, as qadc_adc_index_add_vectors_labelled: labels [count], host
+ * memory; the index after the call is the index after qadc_index_add_vectors(vectors, count, 0, sum_mode) with the stored label i
+ * of every new row replaced by labels[i].  Any uint32_t is a label and labels may repeat.  The call leaves the index not finalized,
+ * as the plain call does.  QADC_E_STATE on an index without a coarse quantizer or with unlabelled partitions (its keys are
+ * positions), the index left as it was, finalized if it was; otherwise refused as qadc_index_add_vectors is, with the same codes. */
+int qadc_index_add_vectors_labelled(qadc_index* idx, const float* vectors, const uint32_t* labels, uint64_t count, int sum_mode);
+/* The same with d_vectors and d_labels [count] in device memory of the index's device, read where they lie and only by kernels. */
+int qadc_index_add_vectors_labelled_device(qadc_index* idx, const float* d_vectors, const uint32_t* d_labels, uint64_t count, int sum_mode);
 /* base_db::get_partition (databases.hpp:50-55) read back: rows [first, first + count) of partition `part`, however it was filled,
  * as long as it is held whole: codes_out [count][M / 2], labels_out [count] (either may be NULL; labels_out is filled only on a
  * labelled index).  A range outside the partition, a partition that does not exist, a shard -> QADC_E_ARG. */
@@ -1128,6 +1152,43 @@ int qadc_refine_rerank(qadc_refine* r, int nq, const float* queries, int r_in, c
 int qadc_refine_rerank_device(qadc_refine* r, int nq, const float* d_queries, int r_in, const uint32_t* d_keys, const int32_t* d_counts,
                               const float* d_values, int R, uint32_t* d_out_keys, float* d_out_dist, int32_t* d_out_sizes,
                               uint64_t* missing_out);
+
+/* ---- the keyed refine store: put, overwrite and remove by label ----
+ * A second kind of store holds a map from key to vector in place of a dense range, for an index whose labels the caller chose
+ * (qadc_adc_index_add_vectors_labelled) and whose rows come and go (qadc_adc_index_remove_labels).  qadc_refine_rerank and
+ * _rerank_device work on it as above, word for word, with "the store holds the key" = "the map has the key now": the output is a
+ * function of the map's contents and the call's arguments alone.  The twin is refine::keyed_store of quick-adc_amd/host/refine.hpp.
+ * In device memory the map is the row array of a dense store, a key and a free list per row, and an open-addressing hash table of
+ * 2^bits slots (key, row) with linear probing, at most half used; which slot and which row a key occupies shows in no result.
+ * The kinds do not mix: qadc_refine_add* on a keyed store and qadc_refine_put* / _remove* / _keyed_info on a dense one are
+ * QADC_E_STATE.  On a keyed store qadc_refine_info reports lo = 0 and rows = the keys held, qadc_refine_reserve(rows) makes room
+ * for `rows` keys in the row arrays and in the table, and qadc_refine_relocations counts the puts that moved the rows.
+ * Limits: memory is reused, never returned (no shrink); at most 2^30 keys; key 0xFFFFFFFF cannot be held (it is rerank's filler
+ * key); one device; every call is synchronous.  The key 0 a 4-bit heap's sentinel carries is missing on a store that does not
+ * hold key 0. */
+int qadc_refine_create_keyed(qadc_refine** out, int dim, int dtype, int device_id);
+/* For i ascending the vector of key labels[i] becomes vectors[i] ([count][dim], host memory), converted as qadc_refine_add
+ * converts: a key not held becomes held, a key held is overwritten, the last occurrence of a key within the call wins.  A call
+ * whose keys are all held allocates nothing and moves nothing.  New keys take the rows that removals freed first.
+ * QADC_E_ARG, the store left exactly as it was: a label 0xFFFFFFFF (checked over the whole call before anything is written);
+ * vectors or labels NULL with count > 0; more than 2^30 keys.  count = 0 is a no-op. */
+int qadc_refine_put(qadc_refine* r, const float* vectors, const uint32_t* labels, uint64_t count);
+/* The same with d_vectors and d_labels in device memory of the store's device, complete before the call, read where they lie and
+ * only by kernels (the label 0xFFFFFFFF is looked for by a kernel before anything is written). */
+int qadc_refine_put_device(qadc_refine* r, const float* d_vectors, const uint32_t* d_labels, uint64_t count);
+/* Every key of labels [count] (host memory) that is held leaves; keys not held are ignored.  *removed_out (may be NULL) = the
+ * keys that left: a key listed twice counts once.  The rows are reused by later puts. */
+int qadc_refine_remove(qadc_refine* r, const uint32_t* labels, uint64_t count, uint64_t* removed_out);
+/* The same with d_labels in device memory of the store's device, read only by kernels. */
+int qadc_refine_remove_device(qadc_refine* r, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out);
+/* Any output may be NULL: the keys held; the rows allocated so far (held or free) and those of them that are free; the table's
+ * slots and how many are used (by a key held or by one removed since the last rebuild; at most half); the bytes of all
+ * allocations (capacity x (row size + 8) + slots x 12). */
+int qadc_refine_keyed_info(const qadc_refine* r, uint64_t* live, uint64_t* rows_allocated, uint64_t* rows_free, uint64_t* table_slots,
+                           uint64_t* table_used, uint64_t* bytes);
+/* The home slot of a key in a table of 2^table_bits slots — the hash, exported for tests and tools: the upper table_bits bits of
+ * MurmurHash3's 32-bit finalizer of the key. */
+uint32_t qadc_refine_keyed_slot(uint32_t key, int table_bits);
 
 #ifdef __cplusplus
 }

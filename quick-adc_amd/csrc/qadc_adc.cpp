@@ -1013,9 +1013,10 @@ struct AddEncoder {
     }
 };
 
-// index_db::add_vectors (databases.hpp:270-298) pass by pass: encode, count, plan, relocate if needed, scatter.
-int add_ivf(qadc_adc_index* idx, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode, bool d_side, bool fresh,
-            bool* moved) {
+// index_db::add_vectors (databases.hpp:270-298) pass by pass: encode, count, plan, relocate if needed, scatter.  labels [count]
+// (host or device memory, as the vectors) or null: the label of vector i, in place of labels_offset + i.
+int add_ivf(qadc_adc_index* idx, const float* vectors, const uint32_t* labels, uint64_t count, uint32_t labels_offset, int sum_mode,
+            bool d_side, bool fresh, bool* moved) {
     const uint32_t K = (uint32_t)idx->K;
     std::vector<uint64_t> add(K, 0);
     if (count == 0) return fresh ? make_room(idx, add, false, true, moved) : QADC_OK;
@@ -1027,11 +1028,18 @@ int add_ivf(qadc_adc_index* idx, const float* vectors, uint64_t count, uint32_t 
     HIPCHECK(enc.mem.alloc(&d_hist, (enc.pass / kAddTile + 1) * 256 * 4));
     if (K > 256) HIPCHECK(enc.mem.alloc(&d_perm_a, enc.pass * 4));
     if (K > 65536) HIPCHECK(enc.mem.alloc(&d_perm_b, enc.pass * 4));
+    uint32_t* d_lab = nullptr;   // the labels of a pass, uploaded beside its vectors
+    if (labels && !d_side) HIPCHECK(enc.mem.alloc(&d_lab, enc.pass * 4));
     HIPCHECK(idx->h_add.ensure(2 * (size_t)K + 1));
     uint32_t *h_count = idx->h_add.p, *h_base = idx->h_add.p + K + 1;
     for (uint64_t o = 0; o < count; o += QADC_ADC_ADD_CHUNK) {
         const uint64_t cnt = std::min<uint64_t>(QADC_ADC_ADD_CHUNK, count - o);
         if (int rc = enc.encode(idx, vectors + o * idx->dim, cnt, sum_mode, d_side)) return rc;
+        const uint32_t* d_pass_lab = labels ? labels + o : nullptr;
+        if (d_lab) {
+            HIPCHECK(hipMemcpyAsync(d_lab, labels + o, cnt * 4, hipMemcpyHostToDevice, idx->stream));
+            d_pass_lab = d_lab;
+        }
         HIPCHECK(hipMemsetAsync(d_count, 0, ((size_t)K + 1) * 4, idx->stream));
         HIPCHECK(launch_adc_add_count(enc.d_assign, (uint32_t)cnt, K, d_count, idx->stream));
         HIPCHECK(hipMemcpyAsync(h_count, d_count, ((size_t)K + 1) * 4, hipMemcpyDeviceToHost, idx->stream));
@@ -1047,8 +1055,8 @@ int add_ivf(qadc_adc_index* idx, const float* vectors, uint64_t count, uint32_t 
         if (int rc = make_room(idx, add, true, fresh && o == 0, moved)) return rc;
         HIPCHECK(hipMemcpyAsync(d_base, h_base, (size_t)K * 4, hipMemcpyHostToDevice, idx->stream));
         const AddDst dst{idx->codes.p, idx->d_off.p, idx->labels.p, idx->d_lab_off.p, d_base};
-        HIPCHECK(launch_adc_add_scatter(enc.d_assign, (uint32_t)cnt, K, idx->code_size(), enc.d_codes, labels_offset + (uint32_t)o, dst, d_hist,
-                                        d_perm_a, d_perm_b, idx->stream));
+        HIPCHECK(launch_adc_add_scatter(enc.d_assign, (uint32_t)cnt, K, idx->code_size(), enc.d_codes, labels_offset + (uint32_t)o, d_pass_lab, dst,
+                                        d_hist, d_perm_a, d_perm_b, idx->stream));
         HIPCHECK(hipStreamSynchronize(idx->stream));   // (h_base is written again by the next pass)
         for (uint32_t p = 0; p < K; ++p) idx->sizes[p] += h_count[p];
         idx->labeled = 1;
@@ -1081,9 +1089,18 @@ int add_flat(qadc_adc_index* idx, const float* vectors, uint64_t count, uint32_t
     return QADC_OK;
 }
 
-int add_vectors(qadc_adc_index* idx, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode, bool d_side, const char* call) {
+// labelled: the call is qadc_adc_index_add_vectors_labelled / _device, which takes labels [count] and no labels_offset.
+int add_vectors(qadc_adc_index* idx, const float* vectors, const uint32_t* labels, bool labelled, uint64_t count, uint32_t labels_offset,
+                int sum_mode, bool d_side, const char* call) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
     if (int rc = refuse_on_view(idx, call)) return rc;
+    if (labelled) {   // (the keys of a flat or unlabelled index are positions: it has no label to set)
+        if (idx->dim && !idx->K)
+            return fail(QADC_E_STATE, std::string(call) + ": a flat index (no coarse quantizer) keys its vectors by position and takes no labels");
+        if (idx->labeled == 0 && std::any_of(idx->sizes.begin(), idx->sizes.end(), [](uint32_t s) { return s != 0; }))
+            return fail(QADC_E_STATE, std::string(call) + ": the index holds unlabelled partitions, whose keys are positions");
+        if (count && !labels) return fail(QADC_E_ARG, "labels is null");
+    }
     if (!idx->dim) return fail(QADC_E_ARG, "qadc_adc_index_set_pq has not been called: the index has no codebooks");
     if (sum_mode != 0 && sum_mode != 1) return fail(QADC_E_ARG, "sum_mode is 0 (source order) or 1 (as compiled)");
     if (count && !vectors) return fail(QADC_E_ARG, "vectors is null");
@@ -1114,7 +1131,7 @@ int add_vectors(qadc_adc_index* idx, const float* vectors, uint64_t count, uint3
         idx->lab_off.assign(n, 0);
     }
     bool moved = false;
-    const int rc = idx->K ? add_ivf(idx, vectors, count, labels_offset, sum_mode, d_side, fresh, &moved)
+    const int rc = idx->K ? add_ivf(idx, vectors, labels, count, labels_offset, sum_mode, d_side, fresh, &moved)
                           : add_flat(idx, vectors, count, labels_offset, sum_mode, d_side, fresh, &moved);
     if (rc != QADC_OK) {
         (void)hipStreamSynchronize(idx->stream);
@@ -1454,11 +1471,20 @@ int qadc_adc_index_add_partitions(qadc_adc_index* idx, int part_count, const uin
 }
 
 int qadc_adc_index_add_vectors(qadc_adc_index* idx, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode) {
-    return add_vectors(idx, vectors, count, labels_offset, sum_mode, false, "qadc_adc_index_add_vectors");
+    return add_vectors(idx, vectors, nullptr, false, count, labels_offset, sum_mode, false, "qadc_adc_index_add_vectors");
 }
 
 int qadc_adc_index_add_vectors_device(qadc_adc_index* idx, const float* d_vectors, uint64_t count, uint32_t labels_offset, int sum_mode) {
-    return add_vectors(idx, d_vectors, count, labels_offset, sum_mode, true, "qadc_adc_index_add_vectors_device");
+    return add_vectors(idx, d_vectors, nullptr, false, count, labels_offset, sum_mode, true, "qadc_adc_index_add_vectors_device");
+}
+
+int qadc_adc_index_add_vectors_labelled(qadc_adc_index* idx, const float* vectors, const uint32_t* labels, uint64_t count, int sum_mode) {
+    return add_vectors(idx, vectors, labels, true, count, 0, sum_mode, false, "qadc_adc_index_add_vectors_labelled");
+}
+
+int qadc_adc_index_add_vectors_labelled_device(qadc_adc_index* idx, const float* d_vectors, const uint32_t* d_labels, uint64_t count,
+                                               int sum_mode) {
+    return add_vectors(idx, d_vectors, d_labels, true, count, 0, sum_mode, true, "qadc_adc_index_add_vectors_labelled_device");
 }
 
 int qadc_adc_index_remove_labels(qadc_adc_index* idx, const uint32_t* labels, uint64_t count, uint64_t* removed_out) {

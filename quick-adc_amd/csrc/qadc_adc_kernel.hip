@@ -1023,7 +1023,8 @@ __global__ __launch_bounds__(kWG) void adc_encode16_merge_kernel(const unsigned 
 //   adc_add_scan_kernel     the histograms turned into write positions, digit-major then tile order (one workgroup);
 //   adc_add_scatter_kernel  the stable scatter of the pass, tile by tile as adc_order_kernel's: rank among the equal digits
 //                           of the wave by ballots, of the waves before through LDS counts.  The last pass writes the code row
-//                           (one dword, dwordx2 or dwordx4 store) and the label instead of the permutation;
+//                           (one dword, dwordx2 or dwordx4 store) and the label instead of the permutation: the caller's
+//                           row_labels[i] where given, else first_label + i;
 //   adc_move_kernel         the relocation, one thread per (partition, 16-byte word) and per (partition, label).
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t kAddCountLds = 8192;   // partitions + 1 the count kernel privatises in LDS; more go to global atomics
@@ -1086,7 +1087,7 @@ __global__ __launch_bounds__(kWG) void adc_add_scatter_kernel(const int32_t* __r
                                                               uint32_t n, uint32_t K, int shift, const uint32_t* __restrict__ hist,
                                                               uint32_t* __restrict__ perm_out, bool last,
                                                               const CodeWords<BYTES>* __restrict__ rows, uint32_t first_label,
-                                                              AddDst dst) {
+                                                              const uint32_t* __restrict__ row_labels, AddDst dst) {
     __shared__ uint32_t run[256];                                // write position of the next entry of each digit
     __shared__ uint32_t wcount[4 * 256];                         // entries of the digit in each wave of the round
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1119,7 +1120,7 @@ __global__ __launch_bounds__(kWG) void adc_add_scatter_kernel(const int32_t* __r
             } else if (a < K) {
                 const uint32_t row = dst.base[a] + pos;          // (modulo 2^32: base = size - entries of the partitions below)
                 *reinterpret_cast<CodeWords<BYTES>*>(dst.codes + dst.off[a] + (uint64_t)row * BYTES) = rows[i];
-                if (dst.labels) dst.labels[dst.lab_off[a] + row] = first_label + i;
+                if (dst.labels) dst.labels[dst.lab_off[a] + row] = row_labels ? row_labels[i] : first_label + i;
             }
         }
         __syncthreads();
@@ -1505,8 +1506,8 @@ hipError_t launch_adc_add_count(const int32_t* d_assign, uint32_t n, uint32_t K,
 }
 
 hipError_t launch_adc_add_scatter(const int32_t* d_assign, uint32_t n, uint32_t K, int code_bytes, const uint8_t* d_rows,
-                                  uint32_t first_label, AddDst dst, uint32_t* d_hist, uint32_t* d_perm_a, uint32_t* d_perm_b,
-                                  hipStream_t s) {
+                                  uint32_t first_label, const uint32_t* d_row_labels, AddDst dst, uint32_t* d_hist, uint32_t* d_perm_a,
+                                  uint32_t* d_perm_b, hipStream_t s) {
     if (n == 0) return hipSuccess;
     if (K == 0 || (code_bytes != 4 && code_bytes != 8 && code_bytes != 16)) return hipErrorInvalidValue;
     int bits = 0;
@@ -1521,7 +1522,7 @@ hipError_t launch_adc_add_scatter(const int32_t* d_assign, uint32_t n, uint32_t 
         hipLaunchKernelGGL(adc_add_hist_kernel, dim3(tiles), dim3(kWG), 0, s, d_assign, in, n, shift, d_hist);
         hipLaunchKernelGGL(adc_add_scan_kernel, dim3(1), dim3(kWG), 0, s, d_hist, tiles);
 #define QADC_AS(B) hipLaunchKernelGGL((adc_add_scatter_kernel<B>), dim3(tiles), dim3(kWG), 0, s, d_assign, in, n, K, shift, d_hist, out, last, \
-                                      reinterpret_cast<const CodeWords<B>*>(d_rows), first_label, dst)
+                                      reinterpret_cast<const CodeWords<B>*>(d_rows), first_label, d_row_labels, dst)
         if (code_bytes == 4) QADC_AS(4);
         else if (code_bytes == 8) QADC_AS(8);
         else QADC_AS(16);

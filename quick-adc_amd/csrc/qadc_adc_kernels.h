@@ -142,12 +142,13 @@ struct AddDst {
     const uint64_t* lab_off;
     const uint32_t* base;
 };
-// Scatters the pass: d_rows [n][code_bytes] (4, 8 or 16) and first_label + i.  Every assign[i] is in [0, K) (launch_adc_add_count
-// found none outside) and every destination row within its partition's capacity.  d_hist: (n / kAddTile + 1) * 256 words,
-// d_perm_a / d_perm_b: n words each (read only where K > 256 / K > 65536).
+// Scatters the pass: d_rows [n][code_bytes] (4, 8 or 16) and the label of vector i: d_row_labels[i] where d_row_labels [n] is given
+// (device memory, read only by the last pass' kernel), first_label + i where it is null.  Every assign[i] is in [0, K)
+// (launch_adc_add_count found none outside) and every destination row within its partition's capacity.  d_hist: (n / kAddTile + 1)
+// * 256 words, d_perm_a / d_perm_b: n words each (read only where K > 256 / K > 65536).
 hipError_t launch_adc_add_scatter(const int32_t* d_assign, uint32_t n, uint32_t K, int code_bytes, const uint8_t* d_rows,
-                                  uint32_t first_label, AddDst dst, uint32_t* d_hist, uint32_t* d_perm_a, uint32_t* d_perm_b,
-                                  hipStream_t s);
+                                  uint32_t first_label, const uint32_t* d_row_labels, AddDst dst, uint32_t* d_hist, uint32_t* d_perm_a,
+                                  uint32_t* d_perm_b, hipStream_t s);
 // Moves every partition into a new layout, one thread per (partition, 16-byte word) and per (partition, label): sizes [parts] rows
 // held, offsets as Db's.  Labels are moved where both label buffers are given.
 hipError_t launch_adc_move_partitions(int parts, int code_bytes, const uint32_t* d_sizes, uint32_t max_size, const uint8_t* src_codes,

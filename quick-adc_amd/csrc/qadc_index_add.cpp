@@ -208,9 +208,10 @@ int zero_tails(qadc_index* idx, const std::vector<uint32_t>& sizes, uint32_t* h_
 }
 
 // index_db::add_vectors (databases.hpp:270-298) pass by pass: encode, count, plan, relocate if needed, scatter.  sizes: the rows
-// every partition holds, advanced pass by pass (the partitions take them when the call has succeeded).
-int add_ivf(qadc_index* idx, std::vector<uint32_t>& sizes, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode, bool d_side,
-            bool* moved) {
+// every partition holds, advanced pass by pass (the partitions take them when the call has succeeded).  labels [count] (host or
+// device memory, as the vectors) or null: the label of vector i, in place of labels_offset + i.
+int add_ivf(qadc_index* idx, std::vector<uint32_t>& sizes, const float* vectors, const uint32_t* labels, uint64_t count, uint32_t labels_offset,
+            int sum_mode, bool d_side, bool* moved) {
     const uint32_t K = (uint32_t)idx->feed.K;
     std::vector<uint64_t> add(K, 0);
     if (count == 0) return resident(idx) ? QADC_OK : make_room(idx, sizes, add, idx->labeled == 1, moved);
@@ -223,11 +224,18 @@ int add_ivf(qadc_index* idx, std::vector<uint32_t>& sizes, const float* vectors,
     HIPCHECK(enc.mem.alloc(&d_hist, (enc.pass / kAddTile + 1) * 256 * 4));
     if (K > 256) HIPCHECK(enc.mem.alloc(&d_perm_a, enc.pass * 4));
     if (K > 65536) HIPCHECK(enc.mem.alloc(&d_perm_b, enc.pass * 4));
+    uint32_t* d_lab = nullptr;   // the labels of a pass, uploaded beside its vectors
+    if (labels && !d_side) HIPCHECK(enc.mem.alloc(&d_lab, enc.pass * 4));
     HIPCHECK(idx->arena.h_add.ensure(3 * (size_t)K + 1));
     uint32_t *h_count = idx->arena.h_add.p, *h_base = h_count + K + 1, *h_sizes = h_base + K;
     for (uint64_t o = 0; o < count; o += QADC_INDEX_ADD_CHUNK) {
         const uint64_t cnt = std::min<uint64_t>(QADC_INDEX_ADD_CHUNK, count - o);
         if (int rc = enc.encode(idx, vectors + o * idx->feed.dim, cnt, sum_mode, d_side)) return rc;
+        const uint32_t* d_pass_lab = labels ? labels + o : nullptr;
+        if (d_lab) {
+            HIPCHECK(hipMemcpyAsync(d_lab, labels + o, cnt * 4, hipMemcpyHostToDevice, idx->stream));
+            d_pass_lab = d_lab;
+        }
         HIPCHECK(hipMemsetAsync(d_count, 0, ((size_t)K + 1) * 4, idx->stream));
         HIPCHECK(launch_adc_add_count(enc.d_assign, (uint32_t)cnt, K, d_count, idx->stream));
         HIPCHECK(hipMemcpyAsync(h_count, d_count, ((size_t)K + 1) * 4, hipMemcpyDeviceToHost, idx->stream));
@@ -245,8 +253,8 @@ int add_ivf(qadc_index* idx, std::vector<uint32_t>& sizes, const float* vectors,
         HIPCHECK(hipMemcpyAsync(d_base, h_base, (size_t)K * 4, hipMemcpyHostToDevice, idx->stream));
         const ArenaState& a = idx->arena;
         const AddDst dst{a.codes.p, a.d_off.p, a.labels.p, a.d_lab_off.p, d_base};
-        HIPCHECK(launch_adc_add_scatter(enc.d_assign, (uint32_t)cnt, K, idx->cs, enc.d_codes, labels_offset + (uint32_t)o, dst, d_hist, d_perm_a,
-                                        d_perm_b, idx->stream));
+        HIPCHECK(launch_adc_add_scatter(enc.d_assign, (uint32_t)cnt, K, idx->cs, enc.d_codes, labels_offset + (uint32_t)o, d_pass_lab, dst, d_hist,
+                                        d_perm_a, d_perm_b, idx->stream));
         HIPCHECK(hipMemcpyAsync(d_sizes, h_sizes, (size_t)K * 4, hipMemcpyHostToDevice, idx->stream));
         HIPCHECK(launch_index_zero_tails(a.codes.p, a.d_off.p, d_sizes, K, idx->cs, idx->stream));
         HIPCHECK(hipStreamSynchronize(idx->stream));   // (the pinned block is written again by the next pass)
@@ -282,10 +290,19 @@ int add_flat(qadc_index* idx, std::vector<uint32_t>& sizes, const float* vectors
     return zero_tails(idx, sizes, idx->arena.h_add.p, d_size);
 }
 
-int add_vectors(qadc_index* idx, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode, bool d_side, const char* call) {
+// labelled: the call is qadc_index_add_vectors_labelled / _device, which takes labels [count] and no labels_offset.
+int add_vectors(qadc_index* idx, const float* vectors, const uint32_t* labels, bool labelled, uint64_t count, uint32_t labels_offset, int sum_mode,
+                bool d_side, const char* call) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
     if (int rc = refuse(idx, call)) return rc;
     const FeederState& f = idx->feed;
+    if (labelled) {   // (the keys of a flat or unlabelled index are positions: it has no label to set)
+        if (f.dim && !f.K)
+            return fail(QADC_E_STATE, std::string(call) + ": a flat index (no coarse quantizer) keys its vectors by position and takes no labels");
+        if (idx->labeled == 0 && std::any_of(idx->parts.begin(), idx->parts.end(), [](const Part& p) { return p.n != 0; }))
+            return fail(QADC_E_STATE, std::string(call) + ": the index holds unlabelled partitions, whose keys are positions");
+        if (count && !labels) return fail(QADC_E_ARG, "labels is null");
+    }
     if (!f.dim) return fail(QADC_E_ARG, "qadc_index_set_pq has not been called: the index has no codebooks");
     if (f.dim > kPqEncodeMaxDim) return fail(QADC_E_ARG, "dim must be <= 2048 (the encoder keeps the codebooks in LDS)");
     if (sum_mode != 0 && sum_mode != 1) return fail(QADC_E_ARG, "sum_mode is 0 (source order) or 1 (as compiled)");
@@ -320,7 +337,7 @@ int add_vectors(qadc_index* idx, const float* vectors, uint64_t count, uint32_t 
         idx->labeled = 0;
     }
     bool moved = false;
-    const int rc = f.K ? add_ivf(idx, sizes, vectors, count, labels_offset, sum_mode, d_side, &moved)
+    const int rc = f.K ? add_ivf(idx, sizes, vectors, labels, count, labels_offset, sum_mode, d_side, &moved)
                        : add_flat(idx, sizes, vectors, count, labels_offset, sum_mode, d_side, &moved);
     if (rc != QADC_OK) {
         const std::string msg = g_err;
@@ -402,11 +419,19 @@ int qadc_index_remove_labels_device(qadc_index* idx, const uint32_t* d_labels, u
 }
 
 int qadc_index_add_vectors(qadc_index* idx, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode) {
-    return add_vectors(idx, vectors, count, labels_offset, sum_mode, false, "qadc_index_add_vectors");
+    return add_vectors(idx, vectors, nullptr, false, count, labels_offset, sum_mode, false, "qadc_index_add_vectors");
 }
 
 int qadc_index_add_vectors_device(qadc_index* idx, const float* d_vectors, uint64_t count, uint32_t labels_offset, int sum_mode) {
-    return add_vectors(idx, d_vectors, count, labels_offset, sum_mode, true, "qadc_index_add_vectors_device");
+    return add_vectors(idx, d_vectors, nullptr, false, count, labels_offset, sum_mode, true, "qadc_index_add_vectors_device");
+}
+
+int qadc_index_add_vectors_labelled(qadc_index* idx, const float* vectors, const uint32_t* labels, uint64_t count, int sum_mode) {
+    return add_vectors(idx, vectors, labels, true, count, 0, sum_mode, false, "qadc_index_add_vectors_labelled");
+}
+
+int qadc_index_add_vectors_labelled_device(qadc_index* idx, const float* d_vectors, const uint32_t* d_labels, uint64_t count, int sum_mode) {
+    return add_vectors(idx, d_vectors, d_labels, true, count, 0, sum_mode, true, "qadc_index_add_vectors_labelled_device");
 }
 
 int qadc_index_read_partition(qadc_index* idx, int part, uint32_t first, uint32_t count, uint8_t* codes_out, uint32_t* labels_out) {

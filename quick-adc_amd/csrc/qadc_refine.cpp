@@ -1,6 +1,6 @@
-// Host side of exact re-ranking (qadc_refine_* in include/qadc.h): a store of the original vectors in
-// device memory, dense over a key range, and the call that reorders the candidate keys a search returned by their L2 distance to
-// those vectors.  The store belongs to no index and shares nothing with either engine but the device's stream set
+// Host side of exact re-ranking (qadc_refine_* in include/qadc.h; DESIGN.md sections 11.11 and 11.14): a store of the original
+// vectors in device memory, dense over a key range or keyed by label through a hash table, and the call that reorders the candidate
+// keys a search returned by their L2 distance to those vectors.  The store belongs to no index and shares nothing with either engine but the device's stream set
 // (qadc_device_prepare): it consumes uint32 keys, whoever produced them.  The definition it is held to is host/refine.hpp, the
 // launch geometry host/refine_plan.hpp, the kernels csrc/qadc_refine_kernel.hip.
 //
@@ -33,6 +33,13 @@ struct qadc_refine {
     void* data = nullptr;                           // [cap][dim] floats or halves
     uint64_t relocations = 0;                       // adds that moved the rows to grow the allocation
     hipStream_t stream = nullptr;
+    // a keyed store (qadc_refine_create_keyed): `rows` are the rows allocated so far, each live or on the free list
+    bool keyed = false;
+    uint64_t live = 0, used = 0, free_rows = 0;     // keys held / slots live or dead / rows on the free list
+    uint32_t *row_key = nullptr, *free_list = nullptr;   // [cap] each: a row's key (0xFFFFFFFF: free) / the free rows' numbers
+    qadc::refine::KeyedTable table{nullptr, nullptr, nullptr, 0};
+    DevBuf<unsigned long long> d_cnt;               // the counters of a put or a remove
+    DevBuf<uint32_t> d_labels, d_slot_of, d_dst;    // a pass of a put: its labels (host form), slots and destination rows
     // per call
     DevBuf<float> d_stage;                          // add from host memory: floats on their way to the convert kernel
     DevBuf<uint64_t> d_words;                       // [pass_nq][r_in]
@@ -72,8 +79,228 @@ int ensure_rows(qadc_refine* r, uint64_t need, bool exact) {
     return QADC_OK;
 }
 
-int add_rows(qadc_refine* r, const float* vectors, uint64_t count, uint32_t first_key, bool d_side) {
+// ---- the keyed store ----
+
+uint64_t table_bytes(int bits) { return bits ? (1ull << bits) * kKeyedSlotBytes : 0; }
+
+void free_table(KeyedTable& t) {
+    if (t.key) (void)hipFree(t.key);
+    if (t.row) (void)hipFree(t.row);
+    if (t.win) (void)hipFree(t.win);
+    t = KeyedTable{nullptr, nullptr, nullptr, 0};
+}
+
+// A cleared table of 2^bits slots holding the live rows of the store; it replaces the store's table, whose dead slots are gone.
+int rebuild_table(qadc_refine* r, int bits) {
+    KeyedTable t{nullptr, nullptr, nullptr, bits};
+    const size_t bytes = (size_t)4 << bits;
+    auto run = [&]() -> int {
+        HIPCHECK(hipMalloc((void**)&t.key, bytes));
+        HIPCHECK(hipMalloc((void**)&t.row, bytes));
+        HIPCHECK(hipMalloc((void**)&t.win, bytes));
+        HIPCHECK(hipMemsetAsync(t.key, 0xFF, bytes, r->stream));
+        HIPCHECK(hipMemsetAsync(t.row, 0xFF, bytes, r->stream));
+        HIPCHECK(hipMemsetAsync(t.win, 0, bytes, r->stream));
+        HIPCHECK(launch_keyed_rebuild(r->row_key, (uint32_t)r->rows, t, r->stream));
+        HIPCHECK(hipStreamSynchronize(r->stream));
+        return QADC_OK;
+    };
+    if (int rc = run()) {
+        (void)hipStreamSynchronize(r->stream);
+        free_table(t);
+        return rc;
+    }
+    free_table(r->table);
+    r->table = t;
+    r->used = r->live;
+    return QADC_OK;
+}
+
+// room for `need` allocated rows of a keyed store: the rows, their keys and the free list, moved by one copy each
+int ensure_keyed_rows(qadc_refine* r, uint64_t need, bool exact) {
+    if (need <= r->cap) return QADC_OK;
+    const uint64_t cap = exact ? need : std::max<uint64_t>(need, r->cap + r->cap / 2);
+    void* data = nullptr;
+    uint32_t *row_key = nullptr, *free_list = nullptr;
+    auto run = [&]() -> int {
+        HIPCHECK(hipMalloc(&data, std::max<size_t>((size_t)cap * r->row_bytes(), 16)));
+        HIPCHECK(hipMalloc((void**)&row_key, (size_t)cap * 4));
+        HIPCHECK(hipMalloc((void**)&free_list, (size_t)cap * 4));
+        HIPCHECK(hipMemsetAsync(row_key + r->rows, 0xFF, (size_t)(cap - r->rows) * 4, r->stream));
+        if (r->rows) {
+            HIPCHECK(hipMemcpyAsync(data, r->data, (size_t)r->rows * r->row_bytes(), hipMemcpyDeviceToDevice, r->stream));
+            HIPCHECK(hipMemcpyAsync(row_key, r->row_key, (size_t)r->rows * 4, hipMemcpyDeviceToDevice, r->stream));
+        }
+        if (r->free_rows) HIPCHECK(hipMemcpyAsync(free_list, r->free_list, (size_t)r->free_rows * 4, hipMemcpyDeviceToDevice, r->stream));
+        HIPCHECK(hipStreamSynchronize(r->stream));
+        return QADC_OK;
+    };
+    if (int rc = run()) {
+        (void)hipStreamSynchronize(r->stream);
+        if (data) (void)hipFree(data);
+        if (row_key) (void)hipFree(row_key);
+        if (free_list) (void)hipFree(free_list);
+        return rc;
+    }
+    if (r->rows) ++r->relocations;
+    if (r->data) (void)hipFree(r->data);
+    if (r->row_key) (void)hipFree(r->row_key);
+    if (r->free_list) (void)hipFree(r->free_list);
+    r->data = data;
+    r->row_key = row_key;
+    r->free_list = free_list;
+    r->cap = cap;
+    return QADC_OK;
+}
+
+int read_counters(qadc_refine* r, unsigned long long* h) {
+    HIPCHECK(hipMemcpyAsync(h, r->d_cnt.p, kKeyedCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    return QADC_OK;
+}
+
+int keyed_call(qadc_refine* r, const char* call, bool want_keyed) {
     if (!r) return fail(QADC_E_ARG, "store is null");
+    if (r->keyed != want_keyed)
+        return fail(QADC_E_STATE, std::string(call) + (want_keyed ? ": the store is dense over a key range (qadc_refine_create): it takes qadc_refine_add"
+                                                                  : ": the store is keyed (qadc_refine_create_keyed): it takes qadc_refine_put"));
+    return QADC_OK;
+}
+
+int put_rows(qadc_refine* r, const float* vectors, const uint32_t* labels, uint64_t count, bool d_side, const char* call) {
+    if (int rc = keyed_call(r, call, true)) return rc;
+    if (count == 0) return QADC_OK;
+    if (!vectors || !labels) return fail(QADC_E_ARG, "vectors and labels must not be null");
+    if (!d_side)
+        for (uint64_t i = 0; i < count; ++i)
+            if (labels[i] == kKeyedEmpty)
+                return fail(QADC_E_ARG, "labels[" + std::to_string(i) + "] is 0xFFFFFFFF, the filler key of qadc_refine_rerank: no vector can be kept under it");
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    const uint64_t pass = keyed_pass(r->dim);
+    HIPCHECK(r->d_cnt.ensure(kKeyedCounters));
+    HIPCHECK(r->d_slot_of.ensure((size_t)std::min(pass, count)));
+    HIPCHECK(r->d_dst.ensure((size_t)std::min(pass, count)));
+    if (!d_side) {
+        HIPCHECK(r->d_labels.ensure((size_t)std::min(pass, count)));
+        HIPCHECK(r->d_stage.ensure((size_t)(std::min(pass, count) * r->dim)));
+    }
+    unsigned long long h[kKeyedCounters];
+    // before anything is written: the filler key among the labels (device form), and the keys the table does not know
+    HIPCHECK(hipMemsetAsync(r->d_cnt.p, 0, kKeyedCounters * sizeof(unsigned long long), r->stream));
+    for (uint64_t o = 0; o < count; o += pass) {
+        const uint64_t cnt = std::min(pass, count - o);
+        const uint32_t* d_lab = labels + o;
+        if (!d_side) {
+            HIPCHECK(hipMemcpyAsync(r->d_labels.p, labels + o, (size_t)cnt * 4, hipMemcpyHostToDevice, r->stream));
+            d_lab = r->d_labels.p;
+        }
+        HIPCHECK(launch_keyed_precheck(d_lab, cnt, r->table, r->d_cnt.p, r->stream));
+        if (!d_side) HIPCHECK(hipStreamSynchronize(r->stream));   // (the label stage is written again by the next pass)
+    }
+    if (int rc = read_counters(r, h)) return rc;
+    if (h[kKeyedCntBad])
+        return fail(QADC_E_ARG, std::to_string(h[kKeyedCntBad]) + " labels are 0xFFFFFFFF, the filler key of qadc_refine_rerank: no vector can be kept under it");
+    const KeyedPutPlan plan = plan_put(r->table.bits, r->live, r->used - r->live, h[kKeyedCntAbsent]);
+    if (plan.refused) return fail(QADC_E_ARG, "a keyed store holds at most 2^30 keys");
+    if (plan.rebuild)
+        if (int rc = rebuild_table(r, plan.bits)) return rc;
+    const bool f16 = r->dtype == QADC_REFINE_F16;
+    for (uint64_t o = 0; o < count; o += pass) {
+        const uint32_t cnt = (uint32_t)std::min(pass, count - o);
+        const uint32_t* d_lab = labels + o;
+        const float* d_vec = vectors + o * r->dim;
+        if (!d_side) {
+            HIPCHECK(hipMemcpyAsync(r->d_labels.p, labels + o, (size_t)cnt * 4, hipMemcpyHostToDevice, r->stream));
+            HIPCHECK(hipMemcpyAsync(r->d_stage.p, vectors + o * r->dim, (size_t)cnt * r->dim * 4, hipMemcpyHostToDevice, r->stream));
+            d_lab = r->d_labels.p;
+            d_vec = r->d_stage.p;
+        }
+        HIPCHECK(hipMemsetAsync(r->d_cnt.p, 0, kKeyedCounters * sizeof(unsigned long long), r->stream));
+        HIPCHECK(launch_keyed_claim(d_lab, cnt, r->table, r->d_slot_of.p, r->d_cnt.p, r->stream));
+        HIPCHECK(launch_keyed_count(cnt, r->table, r->d_slot_of.p, r->d_dst.p, r->d_cnt.p, r->stream));
+        if (int rc = read_counters(r, h)) return rc;
+        r->used += h[kKeyedCntClaimed];                      // (claimed slots stay, dead, if the pass fails from here on)
+        const uint64_t need = h[kKeyedCntNeed], fresh = need > r->free_rows ? need - r->free_rows : 0;
+        int rc = r->rows + fresh > kKeyedMaxKeys ? fail(QADC_E_ARG, "a keyed store allocates at most 2^30 rows") : QADC_OK;
+        if (rc == QADC_OK && fresh) rc = ensure_keyed_rows(r, r->rows + fresh, false);   // exactly the rows of the new keys; an overwrite allocates nothing
+        if (rc != QADC_OK) {
+            const std::string msg = qadc_last_error();
+            (void)launch_keyed_reset(cnt, r->table, r->d_slot_of.p, r->stream);
+            (void)hipStreamSynchronize(r->stream);
+            return fail(rc, msg);
+        }
+        HIPCHECK(launch_keyed_assign(d_lab, cnt, r->table, r->d_slot_of.p, r->d_dst.p, r->row_key, r->free_list, (uint32_t)r->free_rows,
+                                     (uint32_t)r->rows, r->d_cnt.p, r->stream));
+        HIPCHECK(launch_keyed_store(d_vec, r->d_dst.p, cnt, r->dim, r->data, f16, r->stream));
+        HIPCHECK(hipStreamSynchronize(r->stream));
+        r->live += need;
+        r->free_rows -= need - fresh;
+        r->rows += fresh;
+    }
+    return QADC_OK;
+}
+
+int remove_rows(qadc_refine* r, const uint32_t* labels, uint64_t count, uint64_t* removed_out, bool d_side, const char* call) {
+    if (int rc = keyed_call(r, call, true)) return rc;
+    if (removed_out) *removed_out = 0;
+    if (count == 0) return QADC_OK;
+    if (!labels) return fail(QADC_E_ARG, "labels is null");
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    const uint64_t pass = keyed_pass(0);
+    HIPCHECK(r->d_cnt.ensure(kKeyedCounters));
+    if (!d_side) HIPCHECK(r->d_labels.ensure((size_t)std::min(pass, count)));
+    uint64_t removed = 0;
+    for (uint64_t o = 0; o < count && r->live; o += pass) {
+        const uint32_t cnt = (uint32_t)std::min(pass, count - o);
+        const uint32_t* d_lab = labels + o;
+        if (!d_side) {
+            HIPCHECK(hipMemcpyAsync(r->d_labels.p, labels + o, (size_t)cnt * 4, hipMemcpyHostToDevice, r->stream));
+            d_lab = r->d_labels.p;
+        }
+        HIPCHECK(hipMemsetAsync(r->d_cnt.p, 0, kKeyedCounters * sizeof(unsigned long long), r->stream));
+        HIPCHECK(launch_keyed_remove(d_lab, cnt, r->table, r->row_key, r->free_list, (uint32_t)r->free_rows, r->d_cnt.p, r->stream));
+        unsigned long long h[kKeyedCounters];
+        if (int rc = read_counters(r, h)) return rc;
+        r->live -= h[kKeyedCntRemoved];
+        r->free_rows += h[kKeyedCntRemoved];
+        removed += h[kKeyedCntRemoved];
+    }
+    if (removed_out) *removed_out = removed;
+    return QADC_OK;
+}
+
+int create_store(qadc_refine** out, int dim, int dtype, int device_id, bool keyed) {
+    if (!out) return fail(QADC_E_ARG, "out is null");
+    *out = nullptr;
+    if (dim < 1 || dim > QADC_REFINE_MAX_DIM) return fail(QADC_E_ARG, "dim is 1 .. " + std::to_string(QADC_REFINE_MAX_DIM));
+    if (dtype != QADC_REFINE_F32 && dtype != QADC_REFINE_F16) return fail(QADC_E_ARG, "dtype is 0 (QADC_REFINE_F32) or 1 (QADC_REFINE_F16)");
+    DeviceGuard guard;
+    if (int rc = qadc_device_prepare(device_id)) return rc;   // (the device's stream set first: DESIGN.md section 5)
+    HIPCHECK(hipSetDevice(device_id));
+    qadc_refine* r = new qadc_refine();
+    r->dim = dim;
+    r->dtype = dtype;
+    r->device = device_id;
+    r->keyed = keyed;
+    const hipError_t e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        delete r;
+        return fail(QADC_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+    }
+    if (keyed)   // the smallest table from the start: every rerank finds one to probe
+        if (int rc = rebuild_table(r, kKeyedMinBits)) {
+            const std::string msg = qadc_last_error();
+            qadc_refine_destroy(r);
+            return fail(rc, msg);
+        }
+    *out = r;
+    return QADC_OK;
+}
+
+int add_rows(qadc_refine* r, const float* vectors, uint64_t count, uint32_t first_key, bool d_side) {
+    if (int rc = keyed_call(r, "qadc_refine_add", false)) return rc;
     if (count == 0) return QADC_OK;
     if (!vectors) return fail(QADC_E_ARG, "vectors is null");
     if (r->rows && (uint64_t)first_key != (uint64_t)r->lo + r->rows)
@@ -130,6 +357,9 @@ int rerank_passes(qadc_refine* r, int nq, const float* queries, int r_in, const 
         p.f16 = r->dtype == QADC_REFINE_F16;
         p.lo = r->lo;
         p.nrows = r->rows;
+        p.tkey = r->keyed ? r->table.key : nullptr;
+        p.trow = r->table.row;
+        p.tbits = r->table.bits;
         p.dim = r->dim;
         p.nq = std::min(plan.pass_nq, nq - q0);
         p.r_in = r_in;
@@ -157,26 +387,39 @@ int rerank_passes(qadc_refine* r, int nq, const float* queries, int r_in, const 
 
 extern "C" {
 
-int qadc_refine_create(qadc_refine** out, int dim, int dtype, int device_id) {
-    if (!out) return fail(QADC_E_ARG, "out is null");
-    *out = nullptr;
-    if (dim < 1 || dim > QADC_REFINE_MAX_DIM) return fail(QADC_E_ARG, "dim is 1 .. " + std::to_string(QADC_REFINE_MAX_DIM));
-    if (dtype != QADC_REFINE_F32 && dtype != QADC_REFINE_F16) return fail(QADC_E_ARG, "dtype is 0 (QADC_REFINE_F32) or 1 (QADC_REFINE_F16)");
-    DeviceGuard guard;
-    if (int rc = qadc_device_prepare(device_id)) return rc;   // (the device's stream set first: DESIGN.md section 5)
-    HIPCHECK(hipSetDevice(device_id));
-    qadc_refine* r = new qadc_refine();
-    r->dim = dim;
-    r->dtype = dtype;
-    r->device = device_id;
-    const hipError_t e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete r;
-        return fail(QADC_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-    }
-    *out = r;
+int qadc_refine_create(qadc_refine** out, int dim, int dtype, int device_id) { return create_store(out, dim, dtype, device_id, false); }
+
+int qadc_refine_create_keyed(qadc_refine** out, int dim, int dtype, int device_id) { return create_store(out, dim, dtype, device_id, true); }
+
+int qadc_refine_put(qadc_refine* r, const float* vectors, const uint32_t* labels, uint64_t count) {
+    return put_rows(r, vectors, labels, count, false, "qadc_refine_put");
+}
+
+int qadc_refine_put_device(qadc_refine* r, const float* d_vectors, const uint32_t* d_labels, uint64_t count) {
+    return put_rows(r, d_vectors, d_labels, count, true, "qadc_refine_put_device");
+}
+
+int qadc_refine_remove(qadc_refine* r, const uint32_t* labels, uint64_t count, uint64_t* removed_out) {
+    return remove_rows(r, labels, count, removed_out, false, "qadc_refine_remove");
+}
+
+int qadc_refine_remove_device(qadc_refine* r, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out) {
+    return remove_rows(r, d_labels, count, removed_out, true, "qadc_refine_remove_device");
+}
+
+int qadc_refine_keyed_info(const qadc_refine* r, uint64_t* live, uint64_t* rows_allocated, uint64_t* rows_free, uint64_t* table_slots,
+                           uint64_t* table_used, uint64_t* bytes) {
+    if (int rc = keyed_call(const_cast<qadc_refine*>(r), "qadc_refine_keyed_info", true)) return rc;
+    if (live) *live = r->live;
+    if (rows_allocated) *rows_allocated = r->rows;
+    if (rows_free) *rows_free = r->free_rows;
+    if (table_slots) *table_slots = 1ull << r->table.bits;
+    if (table_used) *table_used = r->used;
+    if (bytes) *bytes = r->cap * ((uint64_t)r->row_bytes() + 8) + table_bytes(r->table.bits);
     return QADC_OK;
 }
+
+uint32_t qadc_refine_keyed_slot(uint32_t key, int table_bits) { return qadc::refine::keyed_slot(key, table_bits); }
 
 int qadc_refine_destroy(qadc_refine* r) {
     if (!r) return QADC_OK;
@@ -187,6 +430,10 @@ int qadc_refine_destroy(qadc_refine* r) {
         (void)hipStreamDestroy(r->stream);
     }
     if (r->data) (void)hipFree(r->data);
+    if (r->row_key) (void)hipFree(r->row_key);
+    if (r->free_list) (void)hipFree(r->free_list);
+    free_table(r->table);
+    r->d_cnt.release(); r->d_labels.release(); r->d_slot_of.release(); r->d_dst.release();
     r->d_stage.release(); r->d_words.release(); r->d_missing.release(); r->d_queries.release(); r->d_values.release();
     r->d_out_dist.release(); r->d_keys.release(); r->d_out_keys.release(); r->d_counts.release(); r->d_out_sizes.release();
     delete r;
@@ -206,6 +453,12 @@ int qadc_refine_reserve(qadc_refine* r, uint64_t rows) {
     if (rows > (1ull << 32)) return fail(QADC_E_ARG, "a store holds at most 2^32 rows");
     DeviceGuard guard;
     HIPCHECK(hipSetDevice(r->device));
+    if (r->keyed) {   // room for `rows` live keys in the row arrays and in the table
+        const KeyedPutPlan plan = plan_reserve(r->table.bits, rows);
+        if (plan.refused) return fail(QADC_E_ARG, "a keyed store holds at most 2^30 keys");
+        if (int rc = ensure_keyed_rows(r, rows, true)) return rc;
+        return plan.rebuild ? rebuild_table(r, plan.bits) : QADC_OK;
+    }
     return ensure_rows(r, rows, true);
 }
 
@@ -213,9 +466,9 @@ int qadc_refine_info(const qadc_refine* r, int* dim, int* dtype, uint32_t* lo, u
     if (!r) return fail(QADC_E_ARG, "store is null");
     if (dim) *dim = r->dim;
     if (dtype) *dtype = r->dtype;
-    if (lo) *lo = r->lo;
-    if (rows) *rows = r->rows;
-    if (bytes) *bytes = r->cap * (uint64_t)r->row_bytes();
+    if (lo) *lo = r->keyed ? 0 : r->lo;
+    if (rows) *rows = r->keyed ? r->live : r->rows;
+    if (bytes) *bytes = r->keyed ? r->cap * ((uint64_t)r->row_bytes() + 8) + table_bytes(r->table.bits) : r->cap * (uint64_t)r->row_bytes();
     return QADC_OK;
 }
 

@@ -1,9 +1,10 @@
 // Exact re-ranking (qadc_refine_* in include/qadc.h): what the host unit (qadc_refine.cpp) and the kernels
-// (qadc_refine_kernel.hip) share.  The launch geometry is host/refine_plan.hpp; the definition the kernels are held to, bit for
-// bit, is host/refine.hpp.
+// (qadc_refine_kernel.hip) share.  The launch geometry is host/refine_plan.hpp, that of the keyed store host/refine_keyed_plan.hpp;
+// the definition the kernels are held to, bit for bit, is host/refine.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "../host/refine_keyed_plan.hpp"
 #include "../host/refine_plan.hpp"
 
 namespace qadc {
@@ -16,6 +17,9 @@ struct RefinePass {
     bool f16;
     uint32_t lo;
     uint64_t nrows;
+    const uint32_t* tkey;          // a keyed store: its table's keys and rows [2^tbits] in place of [lo, lo + nrows); else null
+    const uint32_t* trow;
+    int tbits;
     int dim, nq, r_in, R;
     const float* queries;          // [nq][dim]
     const uint32_t* keys;          // [nq][r_in]
@@ -34,6 +38,44 @@ hipError_t launch_refine_dist(const RefinePass& p, const RefinePlan& plan, hipSt
 hipError_t launch_refine_select(const RefinePass& p, const RefinePlan& plan, hipStream_t stream);
 // refine_convert_kernel<Row>: dst[i] = Row(src[i]) for n floats (Row float: a copy; __half: round to nearest even)
 hipError_t launch_refine_convert(const float* src, void* dst, bool f16, uint64_t n, hipStream_t stream);
+
+// ---- the keyed store.  Every launch takes at most kKeyedPass inputs; labels are device memory read by
+// kernels only. ----
+
+// The table, 2^bits slots: key (kKeyedEmpty = empty), row (kKeyedNoRow = empty or dead), win (the put's scratch word per slot, zero
+// between calls).
+struct KeyedTable {
+    uint32_t* key;
+    uint32_t* row;
+    uint32_t* win;
+    int bits;
+};
+// The counters of a call, device memory, zeroed by the host before the launches that add to them.
+enum { kKeyedCntBad = 0, kKeyedCntAbsent, kKeyedCntClaimed, kKeyedCntNeed, kKeyedCntTaken, kKeyedCntRemoved, kKeyedCounters = 8 };
+// What keyed_count leaves in dst[i] for an input that writes no row / that wins a slot without a row
+constexpr uint32_t kKeyedLoser = 0xFFFFFFFFu, kKeyedNeedsRow = 0xFFFFFFFEu;
+
+// cnt[Bad] += the labels equal to 0xFFFFFFFF, cnt[Absent] += the others the table does not know, live or dead.  Writes nothing else.
+hipError_t launch_keyed_precheck(const uint32_t* labels, uint64_t n, KeyedTable t, unsigned long long* cnt, hipStream_t stream);
+// Claim: slot_of[i] = the slot of labels[i], found or claimed by a CAS on the key word; win[slot] = max over its inputs of i + 1;
+// cnt[Claimed] += the empty slots claimed.  The caller has made sure that the claims fit (plan_put).
+hipError_t launch_keyed_claim(const uint32_t* labels, uint32_t n, KeyedTable t, uint32_t* slot_of, unsigned long long* cnt, hipStream_t stream);
+// dst[i] = kKeyedLoser where a later input holds the same key, else the slot's row, or kKeyedNeedsRow (cnt[Need] += 1) where it has none
+hipError_t launch_keyed_count(uint32_t n, KeyedTable t, const uint32_t* slot_of, uint32_t* dst, unsigned long long* cnt, hipStream_t stream);
+// Winners without a row take one — the free list's last `free_rows` entries first, then alloc_rows, alloc_rows + 1, ... — and write
+// row_key and the slot's row; every winner clears its slot's win word.  The caller has made room for the rows.
+hipError_t launch_keyed_assign(const uint32_t* labels, uint32_t n, KeyedTable t, const uint32_t* slot_of, uint32_t* dst, uint32_t* row_key,
+                               const uint32_t* free_list, uint32_t free_rows, uint32_t alloc_rows, unsigned long long* cnt, hipStream_t stream);
+// win[slot_of[i]] = 0 for every input: what a put that fails between claim and assign leaves behind it
+hipError_t launch_keyed_reset(uint32_t n, KeyedTable t, const uint32_t* slot_of, hipStream_t stream);
+// rows[dst[i]] = the store's element type of src[i] for every input whose dst[i] is a row
+hipError_t launch_keyed_store(const float* src, const uint32_t* dst, uint32_t n, int dim, void* rows, bool f16, hipStream_t stream);
+// Every listed key that is live: its slot's row becomes none (the slot dead), its row free (row_key, the free list from entry
+// free_rows on); cnt[Removed] += 1 each.  A key listed twice frees its row once.
+hipError_t launch_keyed_remove(const uint32_t* labels, uint32_t n, KeyedTable t, uint32_t* row_key, uint32_t* free_list, uint32_t free_rows,
+                               unsigned long long* cnt, hipStream_t stream);
+// (row_key[r], r) of every live row r < alloc_rows into the cleared table t
+hipError_t launch_keyed_rebuild(const uint32_t* row_key, uint32_t alloc_rows, KeyedTable t, hipStream_t stream);
 
 }  // namespace refine
 }  // namespace qadc

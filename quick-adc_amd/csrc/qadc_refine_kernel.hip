@@ -3,6 +3,8 @@
 //   refine_dist_kernel<Row>     one candidate per wave: the 64-bit word (image of the L2 distance << 32 | key) of every candidate
 //   refine_select_kernel<N, T>  one workgroup per query: bitonic sort of the words in LDS, equal words kept once, the first R out
 //   refine_convert_kernel<Row>  the append: float -> the store's element type
+// The keyed store: refine_dist_kernel finds a candidate's row through a lookup policy, DenseLookup (the
+// range test) or KeyedLookup (a probe of the table); keyed_*_kernel are the put, the remove and the rebuild.
 #include "qadc_refine.h"
 
 #include <hip/hip_fp16.h>
@@ -21,10 +23,39 @@ constexpr uint64_t kNoWord = ~0ull;
 __device__ inline float row_value(const float* x, int i) { return x[i]; }
 __device__ inline float row_value(const __half* x, int i) { return __half2float(x[i]); }
 
+// Where a candidate's row lies.  The key is uniform over the wave, so both are uniform code with no per-lane state.
+struct DenseLookup {                                  // the keys [lo, lo + nrows), row = key - lo
+    uint32_t lo;
+    uint64_t nrows;
+    __device__ inline bool row_of(uint32_t key, uint64_t* row) const {
+        *row = (uint64_t)key - lo;
+        return key >= lo && *row < nrows;
+    }
+};
+
+struct KeyedLookup {                                  // linear probing from the key's home slot; the table is at most half used
+    const uint32_t* __restrict__ tkey;
+    const uint32_t* __restrict__ trow;
+    int bits;
+    __device__ inline bool row_of(uint32_t key, uint64_t* row) const {
+        if (key == kKeyedEmpty) return false;         // (rerank's filler key: never held)
+        const uint32_t mask = (1u << bits) - 1u;
+        for (uint32_t s = keyed_slot(key, bits);; s = (s + 1u) & mask) {
+            const uint32_t k = tkey[s];
+            if (k == key) {                           // live, or dead: a removed key is missing
+                const uint32_t r = trow[s];
+                *row = r;
+                return r != kKeyedNoRow;
+            }
+            if (k == kKeyedEmpty) return false;
+        }
+    }
+};
+
 // Lane l of a wave owns the partial sum p[l] of the definition: the components 64 j + l, in ascending j, then the tree at the
 // strides 32 .. 1 (lane l < s adds lane l + s; what the lanes at and above s compute is never read by a lane below).
-template <typename Row>
-__global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Row* __restrict__ rows, uint32_t lo, uint64_t nrows, int dim,
+template <typename Row, typename Lookup>
+__global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Row* __restrict__ rows, Lookup look, int dim,
                                                                         const float* __restrict__ queries, int r_in,
                                                                         const uint32_t* __restrict__ keys, const int32_t* __restrict__ counts,
                                                                         const float* __restrict__ values, int cands_per_wg, int chunks,
@@ -54,8 +85,8 @@ __global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Ro
             p[c] = 0.0f;
             if (i < c1 && i < count && !(values && values[list + i] == FLT_MAX)) {
                 key[c] = keys[list + i];
-                const uint64_t row = (uint64_t)key[c] - lo;
-                if (key[c] >= lo && row < nrows)
+                uint64_t row;
+                if (look.row_of(key[c], &row))
                     x[c] = rows + row * (uint64_t)dim;
                 else
                     ++lost;
@@ -159,6 +190,137 @@ __global__ __launch_bounds__(256) void refine_convert_kernel(const float* __rest
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) store_as(dst, i, src[i]);
 }
 
+// ---- the keyed store: put (precheck, claim, count, assign, store), remove, rebuild.  One input, row or slot per thread, strided
+// over the grid; every counter is added to once per wave. ----
+
+__device__ inline void keyed_add(unsigned long long* cnt, bool flag) {
+    const unsigned long long m = __ballot(flag);
+    if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(cnt, (unsigned long long)__popcll(m));
+}
+
+// the slot that holds `key`, live or dead, or kKeyedNoRow at the chain's end.  No slot of the table changes its key meanwhile.
+__device__ inline uint32_t keyed_find(const uint32_t* __restrict__ tkey, int bits, uint32_t key) {
+    const uint32_t mask = (1u << bits) - 1u;
+    for (uint32_t s = keyed_slot(key, bits);; s = (s + 1u) & mask) {
+        const uint32_t k = tkey[s];
+        if (k == key) return s;
+        if (k == kKeyedEmpty) return kKeyedNoRow;
+    }
+}
+
+__global__ __launch_bounds__(kKeyedThreads) void keyed_precheck_kernel(const uint32_t* __restrict__ labels, uint64_t n, const uint32_t* __restrict__ tkey,
+                                                                       int bits, unsigned long long* __restrict__ cnt) {
+    const uint64_t span = ((n + kKeyedThreads - 1) / kKeyedThreads) * kKeyedThreads;   // (whole waves reach the ballots)
+    for (uint64_t i = (uint64_t)blockIdx.x * kKeyedThreads + threadIdx.x; i < span; i += (uint64_t)gridDim.x * kKeyedThreads) {
+        const uint32_t key = i < n ? labels[i] : 0u;
+        const bool bad = i < n && key == kKeyedEmpty;
+        keyed_add(cnt + kKeyedCntBad, bad);
+        keyed_add(cnt + kKeyedCntAbsent, i < n && !bad && keyed_find(tkey, bits, key) == kKeyedNoRow);
+    }
+}
+
+__global__ __launch_bounds__(kKeyedThreads) void keyed_claim_kernel(const uint32_t* __restrict__ labels, uint32_t n, uint32_t* tkey, uint32_t* win, int bits,
+                                                                    uint32_t* __restrict__ slot_of, unsigned long long* __restrict__ cnt) {
+    const uint32_t i = blockIdx.x * kKeyedThreads + threadIdx.x;
+    bool claimed = false;
+    if (i < n) {
+        const uint32_t key = labels[i], mask = (1u << bits) - 1u;
+        uint32_t s = keyed_slot(key, bits);
+        for (;; s = (s + 1u) & mask) {                // (slots only go from empty to a key here, so a stale read costs one CAS at most)
+            uint32_t k = *reinterpret_cast<volatile const uint32_t*>(tkey + s);
+            if (k == kKeyedEmpty) {
+                k = atomicCAS(tkey + s, kKeyedEmpty, key);
+                claimed = k == kKeyedEmpty;
+                if (claimed) break;
+            }
+            if (k == key) break;
+        }
+        slot_of[i] = s;
+        atomicMax(win + s, i + 1u);
+    }
+    keyed_add(cnt + kKeyedCntClaimed, claimed);
+}
+
+__global__ __launch_bounds__(kKeyedThreads) void keyed_count_kernel(uint32_t n, const uint32_t* __restrict__ trow, const uint32_t* __restrict__ win,
+                                                                    const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ dst,
+                                                                    unsigned long long* __restrict__ cnt) {
+    const uint32_t i = blockIdx.x * kKeyedThreads + threadIdx.x;
+    bool need = false;
+    if (i < n) {
+        const uint32_t s = slot_of[i];
+        uint32_t d = kKeyedLoser;
+        if (win[s] == i + 1u) {
+            d = trow[s];
+            need = d == kKeyedNoRow;
+            if (need) d = kKeyedNeedsRow;
+        }
+        dst[i] = d;
+    }
+    keyed_add(cnt + kKeyedCntNeed, need);
+}
+
+__global__ __launch_bounds__(kKeyedThreads) void keyed_assign_kernel(const uint32_t* __restrict__ labels, uint32_t n, uint32_t* __restrict__ trow,
+                                                                     uint32_t* __restrict__ win, const uint32_t* __restrict__ slot_of,
+                                                                     uint32_t* __restrict__ dst, uint32_t* __restrict__ row_key,
+                                                                     const uint32_t* __restrict__ free_list, uint32_t free_rows, uint32_t alloc_rows,
+                                                                     unsigned long long* __restrict__ cnt) {
+    const uint32_t i = blockIdx.x * kKeyedThreads + threadIdx.x;
+    if (i >= n || dst[i] == kKeyedLoser) return;      // (one winner per slot: nobody else touches what is written below)
+    const uint32_t s = slot_of[i];
+    if (dst[i] == kKeyedNeedsRow) {
+        const uint32_t t = (uint32_t)atomicAdd(cnt + kKeyedCntTaken, 1ull);
+        const uint32_t r = t < free_rows ? free_list[free_rows - 1u - t] : alloc_rows + (t - free_rows);
+        row_key[r] = labels[i];
+        trow[s] = r;
+        dst[i] = r;
+    }
+    win[s] = 0u;
+}
+
+__global__ __launch_bounds__(kKeyedThreads) void keyed_reset_kernel(uint32_t n, uint32_t* __restrict__ win, const uint32_t* __restrict__ slot_of) {
+    const uint32_t i = blockIdx.x * kKeyedThreads + threadIdx.x;
+    if (i < n) win[slot_of[i]] = 0u;
+}
+
+// refine_convert_kernel's work with a destination row per input: consecutive threads take consecutive components
+template <typename Row>
+__global__ __launch_bounds__(kKeyedThreads) void keyed_store_kernel(const float* __restrict__ src, const uint32_t* __restrict__ dst, uint64_t total,
+                                                                    uint32_t dim, Row* __restrict__ rows) {
+    for (uint64_t e = (uint64_t)blockIdx.x * kKeyedThreads + threadIdx.x; e < total; e += (uint64_t)gridDim.x * kKeyedThreads) {
+        const uint64_t i = e / dim;
+        const uint32_t r = dst[i];
+        if (r != kKeyedLoser) store_as(rows + (uint64_t)r * dim, (size_t)(e - i * dim), src[e]);
+    }
+}
+
+__global__ __launch_bounds__(kKeyedThreads) void keyed_remove_kernel(const uint32_t* __restrict__ labels, uint32_t n, const uint32_t* __restrict__ tkey,
+                                                                     uint32_t* trow, int bits, uint32_t* __restrict__ row_key,
+                                                                     uint32_t* __restrict__ free_list, uint32_t free_rows,
+                                                                     unsigned long long* __restrict__ cnt) {
+    const uint32_t i = blockIdx.x * kKeyedThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t key = labels[i];
+    if (key == kKeyedEmpty) return;
+    const uint32_t s = keyed_find(tkey, bits, key);
+    if (s == kKeyedNoRow) return;
+    const uint32_t r = atomicExch(trow + s, kKeyedNoRow);    // whoever gets the row back frees it: a key listed twice counts once
+    if (r == kKeyedNoRow) return;
+    row_key[r] = kKeyedEmpty;
+    free_list[free_rows + (uint32_t)atomicAdd(cnt + kKeyedCntRemoved, 1ull)] = r;
+}
+
+__global__ __launch_bounds__(kKeyedThreads) void keyed_rebuild_kernel(const uint32_t* __restrict__ row_key, uint32_t alloc_rows, uint32_t* tkey,
+                                                                      uint32_t* __restrict__ trow, int bits) {
+    const uint32_t mask = (1u << bits) - 1u;
+    for (uint64_t r = (uint64_t)blockIdx.x * kKeyedThreads + threadIdx.x; r < alloc_rows; r += (uint64_t)gridDim.x * kKeyedThreads) {
+        const uint32_t key = row_key[r];
+        if (key == kKeyedEmpty) continue;
+        uint32_t s = keyed_slot(key, bits);
+        while (atomicCAS(tkey + s, kKeyedEmpty, key) != kKeyedEmpty) s = (s + 1u) & mask;   // (the live keys differ: no slot matches)
+        trow[s] = (uint32_t)r;
+    }
+}
+
 template <int N, int T>
 hipError_t launch_select(const RefinePass& p, const RefinePlan& plan, hipStream_t stream) {
     if (plan.select_lds_bytes > kRefineLdsDefault) {   // the largest instantiation: above the default limit of dynamic LDS
@@ -175,12 +337,19 @@ hipError_t launch_select(const RefinePass& p, const RefinePlan& plan, hipStream_
 
 hipError_t launch_refine_dist(const RefinePass& p, const RefinePlan& plan, hipStream_t stream) {
     const dim3 grid((unsigned)((uint64_t)p.nq * plan.chunks)), block(kRefineWaves * 64);
-    if (p.f16)
-        hipLaunchKernelGGL(refine_dist_kernel<__half>, grid, block, plan.dist_lds_bytes, stream, static_cast<const __half*>(p.rows), p.lo,
-                           p.nrows, p.dim, p.queries, p.r_in, p.keys, p.counts, p.values, plan.cands_per_wg, plan.chunks, p.words, p.missing);
-    else
-        hipLaunchKernelGGL(refine_dist_kernel<float>, grid, block, plan.dist_lds_bytes, stream, static_cast<const float*>(p.rows), p.lo,
-                           p.nrows, p.dim, p.queries, p.r_in, p.keys, p.counts, p.values, plan.cands_per_wg, plan.chunks, p.words, p.missing);
+    const DenseLookup dense{p.lo, p.nrows};
+    const KeyedLookup keyed{p.tkey, p.trow, p.tbits};
+#define QADC_RD(ROW, LOOKUP, look)                                                                                                       \
+    hipLaunchKernelGGL((refine_dist_kernel<ROW, LOOKUP>), grid, block, plan.dist_lds_bytes, stream, static_cast<const ROW*>(p.rows), look, \
+                       p.dim, p.queries, p.r_in, p.keys, p.counts, p.values, plan.cands_per_wg, plan.chunks, p.words, p.missing)
+    if (p.tkey) {
+        if (p.f16) QADC_RD(__half, KeyedLookup, keyed);
+        else QADC_RD(float, KeyedLookup, keyed);
+    } else {
+        if (p.f16) QADC_RD(__half, DenseLookup, dense);
+        else QADC_RD(float, DenseLookup, dense);
+    }
+#undef QADC_RD
     return hipGetLastError();
 }
 
@@ -200,6 +369,69 @@ hipError_t launch_refine_convert(const float* src, void* dst, bool f16, uint64_t
         hipLaunchKernelGGL(refine_convert_kernel<__half>, grid, block, 0, stream, src, static_cast<__half*>(dst), n);
     else
         hipLaunchKernelGGL(refine_convert_kernel<float>, grid, block, 0, stream, src, static_cast<float*>(dst), n);
+    return hipGetLastError();
+}
+
+hipError_t launch_keyed_precheck(const uint32_t* labels, uint64_t n, KeyedTable t, unsigned long long* cnt, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(keyed_precheck_kernel, dim3(keyed_grid(n)), dim3(kKeyedThreads), 0, stream, labels, n, t.key, t.bits, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_keyed_claim(const uint32_t* labels, uint32_t n, KeyedTable t, uint32_t* slot_of, unsigned long long* cnt, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (n > kKeyedPass) return hipErrorInvalidValue;   // (one input per thread, no stride)
+    hipLaunchKernelGGL(keyed_claim_kernel, dim3(keyed_grid(n)), dim3(kKeyedThreads), 0, stream, labels, n, t.key, t.win, t.bits, slot_of, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_keyed_count(uint32_t n, KeyedTable t, const uint32_t* slot_of, uint32_t* dst, unsigned long long* cnt, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (n > kKeyedPass) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keyed_count_kernel, dim3(keyed_grid(n)), dim3(kKeyedThreads), 0, stream, n, t.row, t.win, slot_of, dst, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_keyed_assign(const uint32_t* labels, uint32_t n, KeyedTable t, const uint32_t* slot_of, uint32_t* dst, uint32_t* row_key,
+                               const uint32_t* free_list, uint32_t free_rows, uint32_t alloc_rows, unsigned long long* cnt, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (n > kKeyedPass) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keyed_assign_kernel, dim3(keyed_grid(n)), dim3(kKeyedThreads), 0, stream, labels, n, t.row, t.win, slot_of, dst, row_key,
+                       free_list, free_rows, alloc_rows, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_keyed_reset(uint32_t n, KeyedTable t, const uint32_t* slot_of, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (n > kKeyedPass) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keyed_reset_kernel, dim3(keyed_grid(n)), dim3(kKeyedThreads), 0, stream, n, t.win, slot_of);
+    return hipGetLastError();
+}
+
+hipError_t launch_keyed_store(const float* src, const uint32_t* dst, uint32_t n, int dim, void* rows, bool f16, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint64_t total = (uint64_t)n * (uint64_t)dim;
+    if (f16)
+        hipLaunchKernelGGL(keyed_store_kernel<__half>, dim3(keyed_grid(total)), dim3(kKeyedThreads), 0, stream, src, dst, total, (uint32_t)dim,
+                           static_cast<__half*>(rows));
+    else
+        hipLaunchKernelGGL(keyed_store_kernel<float>, dim3(keyed_grid(total)), dim3(kKeyedThreads), 0, stream, src, dst, total, (uint32_t)dim,
+                           static_cast<float*>(rows));
+    return hipGetLastError();
+}
+
+hipError_t launch_keyed_remove(const uint32_t* labels, uint32_t n, KeyedTable t, uint32_t* row_key, uint32_t* free_list, uint32_t free_rows,
+                               unsigned long long* cnt, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (n > kKeyedPass) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keyed_remove_kernel, dim3(keyed_grid(n)), dim3(kKeyedThreads), 0, stream, labels, n, t.key, t.row, t.bits, row_key, free_list,
+                       free_rows, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_keyed_rebuild(const uint32_t* row_key, uint32_t alloc_rows, KeyedTable t, hipStream_t stream) {
+    if (alloc_rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(keyed_rebuild_kernel, dim3(keyed_grid(alloc_rows)), dim3(kKeyedThreads), 0, stream, row_key, alloc_rows, t.key, t.row, t.bits);
     return hipGetLastError();
 }
 

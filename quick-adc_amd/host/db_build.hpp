@@ -125,6 +125,24 @@ inline unsigned db_add_hip(qadc_index* idx, int dim, const char* base_filename, 
     });
 }
 
+// Both with the caller's labels (qadc_adc_index_add_vectors_labelled, qadc_index_add_vectors_labelled): labels [vectors of the
+// file], vector i of the file gets labels[i] — ids from a database, sparse, permuted or repeated.  An index with a coarse quantizer
+// only: a flat one keys its vectors by position and refuses.
+inline unsigned db_add_hip(qadc_adc_index* idx, int dim, const char* base_filename, const std::uint32_t* labels, unsigned chunk_count = 1000000,
+                           int sum_mode = 1) {
+    return db_add_chunks(base_filename, chunk_count, dim, [&](const io::vectors_chunk& chunk) {
+        if (qadc_adc_index_add_vectors_labelled(idx, chunk.data.data(), labels + chunk.offset, chunk.count, sum_mode) != QADC_OK)
+            throw std::runtime_error(std::string("qadc_adc_index_add_vectors_labelled: ") + qadc_last_error());
+    });
+}
+inline unsigned db_add_hip(qadc_index* idx, int dim, const char* base_filename, const std::uint32_t* labels, unsigned chunk_count = 1000000,
+                           int sum_mode = 1) {
+    return db_add_chunks(base_filename, chunk_count, dim, [&](const io::vectors_chunk& chunk) {
+        if (qadc_index_add_vectors_labelled(idx, chunk.data.data(), labels + chunk.offset, chunk.count, sum_mode) != QADC_OK)
+            throw std::runtime_error(std::string("qadc_index_add_vectors_labelled: ") + qadc_last_error());
+    });
+}
+
 // databases.cpp:50-90 on the host: assign every vector to its closest centroid (find_k_neighbors with k = 1: the expansion
 // distances, the compiled replace test !(s >= kept) — the first strict minimum after the last NaN), then centroid = (sum of its members in vector order) times the reciprocal of the count — what the reference
 // binary does under -ffast-math (div_mode 1, pinned to its loops as compiled: oracle/_ref) — or divided by it as the source

@@ -205,6 +205,12 @@ struct ivf_database_t {
         h.sort_keys(out);
     }
     void add_vectors(const float* vecs, unsigned n, unsigned labels_offset) {  // databases.hpp:270-298
+        add_vectors(vecs, n, nullptr, labels_offset);
+    }
+    // the same with the caller's label of every vector (qadc_index_add_vectors_labelled; its argument order, which also keeps a
+    // literal 0 offset of the call above unambiguous): lab [n], any value, duplicates allowed
+    void add_vectors(const float* vecs, const unsigned* lab, unsigned n) { add_vectors(vecs, n, lab, 0); }
+    void add_vectors(const float* vecs, unsigned n, const unsigned* lab, unsigned labels_offset) {
         std::vector<float> res(pq->dim);
         std::vector<std::uint8_t> code(pq->code_size());
         for (unsigned i = 0; i < n; ++i) {
@@ -214,7 +220,7 @@ struct ivf_database_t {
             for (int d = 0; d < pq->dim; ++d) res[d] = x[d] - coarse[(size_t)p * pq->dim + d];
             pq->encode(res.data(), 1, code.data());
             partitions[p].insert(partitions[p].end(), code.begin(), code.end());
-            labels[p].push_back(i + labels_offset);
+            labels[p].push_back(lab ? lab[i] : i + labels_offset);
         }
     }
     int partition_count() const { return part_count; }

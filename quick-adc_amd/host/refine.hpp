@@ -21,6 +21,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <vector>
 
 namespace qadc {
@@ -141,9 +142,60 @@ struct store {
     }
 };
 
+// The keyed store (qadc_refine_create_keyed): a map from key to vector in place of a dense range.  holds(key)
+// = "the map has the key"; the selection above reads nothing else of a store, so a result is a function of the map's contents and
+// the call's arguments alone — no slot, row or order of earlier puts can show in it.
+struct keyed_store {
+    int dim = 0, dtype = kF32;
+    std::map<uint32_t, std::vector<float>> f32;      // one of the two is in use, by dtype
+    std::map<uint32_t, std::vector<uint16_t>> f16;
+
+    keyed_store(int dim_, int dtype_) : dim(dim_), dtype(dtype_) {}
+
+    uint64_t live() const { return dtype == kF16 ? f16.size() : f32.size(); }
+
+    // For i ascending the vector of key labels[i] becomes vectors[i], converted as store::add converts: a key not held becomes
+    // held, the last occurrence of a key wins.  false: a label is 0xFFFFFFFF, the filler key of rerank (the map is left as it was).
+    bool put(const float* vectors, const uint32_t* labels, uint64_t count) {
+        for (uint64_t i = 0; i < count; ++i)
+            if (labels[i] == kNoKey) return false;
+        for (uint64_t i = 0; i < count; ++i) {
+            const float* v = vectors + (size_t)i * dim;
+            if (dtype == kF16) {
+                std::vector<uint16_t>& row = f16[labels[i]];
+                row.resize(dim);
+                for (int j = 0; j < dim; ++j) row[j] = float_to_half(v[j]);
+            } else {
+                f32[labels[i]].assign(v, v + dim);
+            }
+        }
+        return true;
+    }
+
+    // Every listed key that is held leaves; returns how many left (a key listed twice counts once, a key not held is ignored)
+    uint64_t remove(const uint32_t* labels, uint64_t count) {
+        uint64_t removed = 0;
+        for (uint64_t i = 0; i < count; ++i) removed += dtype == kF16 ? f16.erase(labels[i]) : f32.erase(labels[i]);
+        return removed;
+    }
+
+    bool holds(uint32_t key) const { return dtype == kF16 ? f16.count(key) != 0 : f32.count(key) != 0; }
+
+    float distance_to(const float* q, uint32_t key) const {
+        if (dtype == kF16) {
+            const uint16_t* x = f16.find(key)->second.data();
+            return distance(q, dim, [x](int i) { return half_to_float(x[i]); });
+        }
+        const float* x = f32.find(key)->second.data();
+        return distance(q, dim, [x](int i) { return x[i]; });
+    }
+};
+
 // queries [nq][dim], keys [nq][r_in], counts [nq] or null (every count in [0, r_in]), values [nq][r_in] or null ->
-// out_keys [nq][R], out_dist [nq][R], out_sizes [nq]; returns the missing entries of all queries
-inline uint64_t rerank(const store& s, int nq, const float* queries, int r_in, const uint32_t* keys, const int32_t* counts,
+// out_keys [nq][R], out_dist [nq][R], out_sizes [nq]; returns the missing entries of all queries.  Store: store or keyed_store —
+// the definition reads a store through dim, holds and distance_to alone.
+template <typename Store>
+inline uint64_t rerank(const Store& s, int nq, const float* queries, int r_in, const uint32_t* keys, const int32_t* counts,
                        const float* values, int R, uint32_t* out_keys, float* out_dist, int32_t* out_sizes) {
     uint64_t missing = 0;
     std::vector<uint64_t> words;

@@ -1,6 +1,6 @@
-// refine_store_hip — C++14 RAII mirror of the refine store (qadc_refine_* in include/qadc.h): the original
-// vectors in device memory, dense over the keys [lo, lo + rows), and rerank(), which reorders candidate keys by their exact squared
-// L2 distance to them.  search_refined() composes it with adc_search_engine_hip (host/adc_search_hip.hpp): the engine's search with
+// refine_store_hip — C++14 RAII mirror of the refine store (qadc_refine_* in include/qadc.h; DESIGN.md sections 11.11 and 11.14): the
+// original vectors in device memory, dense over the keys [lo, lo + rows) or, with keyed = true, a map from key to vector filled by
+// put() and emptied by remove(); and rerank(), which reorders candidate keys by their exact squared L2 distance to them.  search_refined() composes it with adc_search_engine_hip (host/adc_search_hip.hpp): the engine's search with
 // R = the engine's r as r_in, then the re-ranking of the heaps' keys, the FLT_MAX sentinels left out.  The definition both are held
 // to is host/refine.hpp.
 #pragma once
@@ -26,8 +26,9 @@ struct refine_store_hip {
     qadc_refine* store = nullptr;
     int dim;
 
-    refine_store_hip(int dim_, int dtype = QADC_REFINE_F32, int device = 0) : dim(dim_) {
-        if (qadc_refine_create(&store, dim_, dtype, device) != QADC_OK) die("Cannot create the refine store");
+    refine_store_hip(int dim_, int dtype = QADC_REFINE_F32, int device = 0, bool keyed = false) : dim(dim_) {
+        if ((keyed ? qadc_refine_create_keyed(&store, dim_, dtype, device) : qadc_refine_create(&store, dim_, dtype, device)) != QADC_OK)
+            die("Cannot create the refine store");
     }
     refine_store_hip(const refine_store_hip&) = delete;
     refine_store_hip& operator=(const refine_store_hip&) = delete;
@@ -47,6 +48,19 @@ struct refine_store_hip {
         if (qadc_refine_add(store, vectors, count, first_key) != QADC_OK) die("add");
     }
 
+    // a keyed store: the vector of key labels[i] becomes vectors[i] ([count][dim]); the last occurrence of a key wins
+    void put(const float* vectors, const std::uint32_t* labels, std::uint64_t count) {
+        if (qadc_refine_put(store, vectors, labels, count) != QADC_OK) die("put");
+    }
+
+    // a keyed store: every listed key that is held leaves; returns how many left
+    std::uint64_t remove(const std::uint32_t* labels, std::uint64_t count) {
+        std::uint64_t removed = 0;
+        if (qadc_refine_remove(store, labels, count, &removed) != QADC_OK) die("remove");
+        return removed;
+    }
+
+    // the rows a dense store holds, the keys a keyed one holds
     std::uint64_t rows() const {
         std::uint64_t n = 0;
         qadc_refine_info(store, nullptr, nullptr, nullptr, &n, nullptr);

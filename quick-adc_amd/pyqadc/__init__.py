@@ -44,6 +44,8 @@ SYMBOLS = [
     "qadc_adc_index_create_view", "qadc_adc_index_create16", "qadc_adc_encode16_host",
     "qadc_adc_index_add_vectors", "qadc_adc_index_add_vectors_device", "qadc_adc_index_read_partition", "qadc_adc_index_reserve",
     "qadc_adc_index_relocations",
+    "qadc_adc_index_add_vectors_labelled", "qadc_adc_index_add_vectors_labelled_device",
+    "qadc_index_add_vectors_labelled", "qadc_index_add_vectors_labelled_device",
     "qadc_index_add_vectors", "qadc_index_add_vectors_device", "qadc_index_read_partition", "qadc_index_reserve",
     "qadc_index_relocations",
     "qadc_adc_index_remove_labels", "qadc_adc_index_remove_labels_device", "qadc_index_remove_labels", "qadc_index_remove_labels_device",
@@ -54,6 +56,8 @@ SYMBOLS = [
     "qadc_adc_search_filtered", "qadc_adc_search_device_filtered", "qadc_adc_search_candidates_filtered",
     "qadc_refine_create", "qadc_refine_destroy", "qadc_refine_add", "qadc_refine_add_device", "qadc_refine_reserve", "qadc_refine_info",
     "qadc_refine_relocations", "qadc_refine_rerank", "qadc_refine_rerank_device",
+    "qadc_refine_create_keyed", "qadc_refine_put", "qadc_refine_put_device", "qadc_refine_remove", "qadc_refine_remove_device",
+    "qadc_refine_keyed_info", "qadc_refine_keyed_slot",
     "qadc_adc_range_scan", "qadc_adc_range_scan_device", "qadc_adc_range_search", "qadc_adc_range_search_device",
     "qadc_adc_range_collect", "qadc_adc_range_collect_device",
 ]
@@ -239,6 +243,10 @@ def lib():
         L.qadc_adc_index_relocations.argtypes = [C.c_void_p]
         L.qadc_adc_index_relocations.restype = C.c_uint64
         L.qadc_index_add_vectors.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_int]
+        L.qadc_adc_index_add_vectors_labelled.argtypes = [C.c_void_p, f32p, u32p, C.c_uint64, C.c_int]
+        L.qadc_adc_index_add_vectors_labelled_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+        L.qadc_index_add_vectors_labelled.argtypes = [C.c_void_p, f32p, u32p, C.c_uint64, C.c_int]
+        L.qadc_index_add_vectors_labelled_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
         L.qadc_index_add_vectors_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int]
         L.qadc_index_read_partition.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, u8p, u32p]
         L.qadc_index_reserve.argtypes = [C.c_void_p, C.c_int, u32p]
@@ -271,6 +279,14 @@ def lib():
         L.qadc_adc_range_collect_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.qadc_refine_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
         L.qadc_refine_destroy.argtypes = [C.c_void_p]
+        L.qadc_refine_create_keyed.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
+        L.qadc_refine_put.argtypes = [C.c_void_p, f32p, u32p, C.c_uint64]
+        L.qadc_refine_put_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.qadc_refine_remove.argtypes = [C.c_void_p, u32p, C.c_uint64, u64p]
+        L.qadc_refine_remove_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p]
+        L.qadc_refine_keyed_info.argtypes = [C.c_void_p, u64p, u64p, u64p, u64p, u64p, u64p]
+        L.qadc_refine_keyed_slot.argtypes = [C.c_uint32, C.c_int]
+        L.qadc_refine_keyed_slot.restype = C.c_uint32
         L.qadc_refine_add.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32]
         L.qadc_refine_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.qadc_refine_reserve.argtypes = [C.c_void_p, C.c_uint64]
@@ -291,6 +307,35 @@ def _p(a, t):
 def _check(rc):
     if rc != 0:
         raise QadcError("qadc error %d: %s" % (rc, lib().qadc_last_error().decode()))
+
+
+def _add_labels(labels, n, labels_offset):
+    """the labels of an add_vectors(labels=...) call: a uint32 array [n], given without a labels_offset"""
+    if labels_offset != 0:
+        raise ValueError("labels and a non-zero labels_offset exclude each other: labels[i] is the whole label of vector i")
+    if not isinstance(labels, np.ndarray) or labels.dtype != np.uint32:
+        raise ValueError("labels must be a numpy uint32 array, not %s" % (getattr(labels, "dtype", type(labels).__name__),))
+    if labels.ndim != 1 or labels.shape[0] != n:
+        raise ValueError("labels has shape %s, expected [%d]: one label per vector" % (tuple(labels.shape), n))
+    return np.ascontiguousarray(labels)
+
+
+def _add_labels_tensor(t, n, labels_offset, device):
+    """the labels of an add_vectors_device(labels=...) call: a contiguous 1-d int32 torch tensor [n] on `device` that carries the
+    labels' uint32 bits (the form in which search_device returns keys), or a uint32 one"""
+    import torch
+    if labels_offset != 0:
+        raise ValueError("labels and a non-zero labels_offset exclude each other: labels[i] is the whole label of vector i")
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+        raise ValueError("labels must be an int32 torch.Tensor (the uint32 bits), not %s" % (getattr(t, "dtype", type(t).__name__),))
+    if t.ndim != 1 or int(t.shape[0]) != n:
+        raise ValueError("labels has shape %s, expected [%d]: one label per vector" % (tuple(t.shape), n))
+    if t.device.type != "cuda" or t.device.index != device:
+        raise QadcError("labels is on %s; the index is on device %d" % (t.device, device))
+    if not t.is_contiguous():
+        raise QadcError("labels must be contiguous")
+    torch.cuda.current_stream(t.device).synchronize()                    # the labels are complete before the call
+    return t
 
 
 def _label_tensor(t, device):
@@ -851,22 +896,29 @@ class Index:
         return out
 
     # ---- db_add: encode and append on the GPU with the index's own quantizers (qadc_index_add_vectors) ----
-    def add_vectors(self, vectors, labels_offset=0, sum_mode=1):
+    def add_vectors(self, vectors, labels_offset=0, sum_mode=1, labels=None):
         """vectors [n][dim]: with a coarse quantizer the code of vector i is appended to its nearest centroid's partition with label
         labels_offset + i (index_db::add_vectors); a flat index writes it at row labels_offset + i of its one partition
-        (flat_db::add_vectors).  The index is not finalized afterwards: call finalize before the next query."""
+        (flat_db::add_vectors).  labels (a uint32 array [n], any values, repeats allowed; not together with a labels_offset): the
+        label of vector i is labels[i] (qadc_index_add_vectors_labelled; an index with a coarse quantizer only).  The index is not
+        finalized afterwards: call finalize before the next query."""
         v = np.ascontiguousarray(vectors, np.float32)
         if v.ndim == 1:
             v = v.reshape(-1, getattr(self, "dim", 1))
         assert v.ndim == 2 and (v.shape[0] == 0 or v.shape[1] == getattr(self, "dim", v.shape[1]))
-        self.add_vectors_raw(v, v.shape[0], labels_offset, sum_mode)
+        if labels is None:
+            self.add_vectors_raw(v, v.shape[0], labels_offset, sum_mode)
+        else:
+            lab = _add_labels(labels, v.shape[0], labels_offset)
+            _check(lib().qadc_index_add_vectors_labelled(self._h, _p(v, f32p), _p(lab, u32p), v.shape[0], sum_mode))
 
     def add_vectors_raw(self, vectors, count, labels_offset, sum_mode):
         """The C call as it is (vectors: a float32 array or None)."""
         _check(lib().qadc_index_add_vectors(self._h, _p(vectors, f32p), count, labels_offset, sum_mode))
 
-    def add_vectors_device(self, vectors, labels_offset=0, sum_mode=1):
-        """add_vectors for a contiguous float32 torch tensor [n][dim] on the index's device, read where it lies."""
+    def add_vectors_device(self, vectors, labels_offset=0, sum_mode=1, labels=None):
+        """add_vectors for a contiguous float32 torch tensor [n][dim] on the index's device, read where it lies; labels: an int32
+        torch tensor [n] there that carries the labels' uint32 bits."""
         import torch
         if not isinstance(vectors, torch.Tensor) or vectors.ndim != 2:
             raise TypeError("vectors must be a 2-d torch.Tensor")
@@ -879,7 +931,11 @@ class Index:
         if vectors.shape[0] and int(vectors.shape[1]) != getattr(self, "dim", int(vectors.shape[1])):
             raise QadcError("vectors has shape %s, expected [n][%d]" % (tuple(vectors.shape), self.dim))
         torch.cuda.current_stream(vectors.device).synchronize()          # the vectors are complete before the call
-        _check(lib().qadc_index_add_vectors_device(self._h, vectors.data_ptr(), int(vectors.shape[0]), labels_offset, sum_mode))
+        if labels is None:
+            _check(lib().qadc_index_add_vectors_device(self._h, vectors.data_ptr(), int(vectors.shape[0]), labels_offset, sum_mode))
+        else:
+            lab = _add_labels_tensor(labels, int(vectors.shape[0]), labels_offset, self.device)
+            _check(lib().qadc_index_add_vectors_labelled_device(self._h, vectors.data_ptr(), lab.data_ptr(), int(vectors.shape[0]), sum_mode))
 
     def read_partition(self, part, first=0, count=None):
         """-> (codes uint8 [n][M/2], labels uint32 [n] or None on an index without labels): rows [first, first + count) of the
@@ -1413,29 +1469,39 @@ class AdcIndex:
         return lib().qadc_adc_index_partition_size(self._h, part)
 
     # ---- db_add: encode and append on the GPU with the index's own quantizers (qadc_adc_index_add_vectors) ----
-    def add_vectors(self, vectors, labels_offset=0, sum_mode=1):
+    def add_vectors(self, vectors, labels_offset=0, sum_mode=1, labels=None):
         """vectors [n][dim]: with a coarse quantizer the code of vector i is appended to its nearest centroid's partition with label
         labels_offset + i (index_db::add_vectors); a flat index writes it at row labels_offset + i of its one partition
-        (flat_db::add_vectors)."""
+        (flat_db::add_vectors).  labels (a uint32 array [n], any values, repeats allowed; not together with a labels_offset): the
+        label of vector i is labels[i] (qadc_adc_index_add_vectors_labelled; an index with a coarse quantizer only)."""
         v = np.ascontiguousarray(vectors, np.float32)
         if v.ndim == 1:
             v = v.reshape(-1, getattr(self, "dim", 1))
         assert v.ndim == 2 and (v.shape[0] == 0 or v.shape[1] == getattr(self, "dim", v.shape[1]))
-        self.add_vectors_raw(v, v.shape[0], labels_offset, sum_mode)
+        if labels is None:
+            self.add_vectors_raw(v, v.shape[0], labels_offset, sum_mode)
+        else:
+            lab = _add_labels(labels, v.shape[0], labels_offset)
+            _check(lib().qadc_adc_index_add_vectors_labelled(self._h, _p(v, f32p), _p(lab, u32p), v.shape[0], sum_mode))
 
     def add_vectors_raw(self, vectors, count, labels_offset, sum_mode):
         """The C call as it is (vectors: a float32 array or None)."""
         _check(lib().qadc_adc_index_add_vectors(self._h, _p(vectors, f32p), count, labels_offset, sum_mode))
 
-    def add_vectors_device(self, vectors, labels_offset=0, sum_mode=1):
-        """add_vectors for a float32 torch tensor [n][dim] on the index's device, read where it lies."""
+    def add_vectors_device(self, vectors, labels_offset=0, sum_mode=1, labels=None):
+        """add_vectors for a float32 torch tensor [n][dim] on the index's device, read where it lies; labels: an int32 torch tensor
+        [n] there that carries the labels' uint32 bits."""
         if getattr(vectors, "ndim", 0) != 2:
             raise TypeError("vectors must be a 2-d torch.Tensor")
         n = int(vectors.shape[0])
         v = self._device_tensor(vectors, (n, getattr(self, "dim", int(vectors.shape[1]))), "vectors")
         import torch
         torch.cuda.current_stream(v.device).synchronize()                # the vectors are complete before the call
-        _check(lib().qadc_adc_index_add_vectors_device(self._h, v.data_ptr(), n, labels_offset, sum_mode))
+        if labels is None:
+            _check(lib().qadc_adc_index_add_vectors_device(self._h, v.data_ptr(), n, labels_offset, sum_mode))
+        else:
+            lab = _add_labels_tensor(labels, n, labels_offset, self.device)
+            _check(lib().qadc_adc_index_add_vectors_labelled_device(self._h, v.data_ptr(), lab.data_ptr(), n, sum_mode))
 
     def read_partition(self, part, first=0, count=None):
         """-> (codes uint8 [n][sq_count] — a create16 index: uint16 [n][sq_count] —, labels uint32 [n] or None on an index without
@@ -1794,18 +1860,72 @@ QADC_REFINE_F32, QADC_REFINE_F16, QADC_REFINE_MAX_IN = 0, 1, 8192   # include/qa
 _REFINE_DTYPES = {"f32": QADC_REFINE_F32, "f16": QADC_REFINE_F16}
 
 
+def refine_keyed_slot(key, bits):
+    """qadc_refine_keyed_slot: the home slot of `key` in a keyed store's table of 2**bits slots"""
+    return int(lib().qadc_refine_keyed_slot(int(key) & 0xFFFFFFFF, int(bits)))
+
+
 class Refine:
     """The original vectors in device memory, for exact re-ranking (qadc_refine_*): dense over the keys
     [lo, lo + rows), row r the vector of key lo + r, kept as float32 ("f32") or float16 ("f16").  rerank() reorders candidate keys —
     a search's, with a larger R than wanted — by their exact squared L2 distance; AdcIndex.search_refined, .search_refined_device
-    and Index.search_refined compose the two."""
+    and Index.search_refined compose the two.
+    keyed=True (qadc_refine_create_keyed; section 11.14): a map from key to vector in place of the dense range, filled by put(),
+    emptied by remove(); add() belongs to the dense kind, put() and remove() to the keyed one (QadcError otherwise)."""
 
-    def __init__(self, dim, dtype="f32", device=0):
+    def __init__(self, dim, dtype="f32", device=0, keyed=False):
         if dtype not in _REFINE_DTYPES:
             raise ValueError('dtype is "f32" or "f16", not %r' % (dtype,))
-        self.dim, self.dtype, self.device = int(dim), dtype, device
+        self.dim, self.dtype, self.device, self.keyed = int(dim), dtype, device, bool(keyed)
         self._h = C.c_void_p()
-        _check(lib().qadc_refine_create(C.byref(self._h), int(dim), _REFINE_DTYPES[dtype], device))
+        create = lib().qadc_refine_create_keyed if keyed else lib().qadc_refine_create
+        _check(create(C.byref(self._h), int(dim), _REFINE_DTYPES[dtype], device))
+
+    # ---- the keyed kind ----
+    def put(self, vectors, labels):
+        """vectors [n][dim], labels uint32 [n]: the vector of key labels[i] becomes vectors[i]; a key not held becomes held, the
+        last occurrence of a key wins.  0xFFFFFFFF is refused (rerank's filler key) and the store left as it was."""
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.dim:
+            raise QadcError("vectors has shape %s, expected [n][%d]" % (v.shape, self.dim))
+        lab = np.ascontiguousarray(np.asarray(labels, np.uint32).reshape(-1))
+        if lab.shape[0] != v.shape[0]:
+            raise ValueError("labels has %d entries for %d vectors" % (lab.shape[0], v.shape[0]))
+        _check(lib().qadc_refine_put(self._h, _p(v, f32p), _p(lab, u32p), v.shape[0]))
+
+    def put_device(self, vectors, labels):
+        """the same from torch tensors of the store's device, read where they lie: vectors float32 [n][dim], labels int32 [n]
+        carrying the uint32 bits"""
+        if getattr(vectors, "ndim", 0) != 2:
+            raise TypeError("vectors must be a 2-d torch.Tensor")
+        n = int(vectors.shape[0])
+        t = self._tensor(vectors, "float32", (n, self.dim), "vectors")
+        lab = self._tensor(labels, "int32", (n,), "labels")
+        self._sync()
+        _check(lib().qadc_refine_put_device(self._h, t.data_ptr(), lab.data_ptr(), n))
+
+    def remove(self, labels):
+        """every listed key that is held leaves -> how many left (a key listed twice counts once)"""
+        lab = np.ascontiguousarray(np.asarray(labels, np.uint32).reshape(-1))
+        removed = C.c_uint64(0)
+        _check(lib().qadc_refine_remove(self._h, _p(lab, u32p), lab.shape[0], C.byref(removed)))
+        return int(removed.value)
+
+    def remove_device(self, labels):
+        """remove() for an int32 torch tensor [n] of the store's device that carries the keys' uint32 bits"""
+        if getattr(labels, "ndim", 0) != 1:
+            raise TypeError("labels must be a 1-d torch.Tensor")
+        lab = self._tensor(labels, "int32", (int(labels.shape[0]),), "labels")
+        self._sync()
+        removed = C.c_uint64(0)
+        _check(lib().qadc_refine_remove_device(self._h, lab.data_ptr(), int(lab.shape[0]), C.byref(removed)))
+        return int(removed.value)
+
+    def keyed_info(self):
+        """-> dict(live, rows_allocated, rows_free, table_slots, table_used, bytes) of a keyed store"""
+        out = [C.c_uint64(0) for _ in range(6)]
+        _check(lib().qadc_refine_keyed_info(self._h, *[C.byref(x) for x in out]))
+        return dict(zip(("live", "rows_allocated", "rows_free", "table_slots", "table_used", "bytes"), (int(x.value) for x in out)))
 
     @classmethod
     def create_raw(cls, dim, dtype, device=0):

@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter,qfilter,refine,range] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter,qfilter,refine,range,keyed] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,filter] [--iters N] [--out FILE]
 
@@ -54,6 +54,9 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             float L2 of search() alone and of search_refined_device with r_in = 400 and 1000 over a float and a half store; the time
             of search_refined_device split into search_device and rerank_device; beside it a plain torch gather + (q - x)^2 sum +
             topk on the same candidates, the only yardstick there is.
+  keyed     caller-chosen labels (not in the default legs), on the ivf_search / refine shape: rerank_device on a
+            keyed store against the dense store holding the same vectors, alternated, at the refine leg's r_in values; put_device and
+            remove_device rows/s at 10^6 keys, fresh and overwriting; add_vectors_device(labels=...) against the plain call.
   --trained-codebooks   the add, remove and ivf_search legs (8 and 4 bits) learn their codebooks with train_pq (10 rounds on the
             residuals of the first 10^5 vectors) instead of sampling them; off by default, so that recorded figures stay comparable
   --bits 4   the float-ADC view of a 4-bit index instead (pyqadc.AdcIndex.view_of; legs lone,ivf_search):
@@ -178,7 +181,7 @@ def search_legs(legs, iters, res):
     part_of, codes = pyqadc.adc_encode(codebooks, vectors, coarse)
     res["adc_encode_1e6_s"] = time.perf_counter() - t0
     print("adc_encode of 10^6 128-d vectors (K = 256, 8x8), host to host: %.2f s" % res["adc_encode_1e6_s"], flush=True)
-    if "refine" not in legs:
+    if "refine" not in legs and "keyed" not in legs:
         del vectors
     order = np.argsort(part_of, kind="stable")
     bounds = np.searchsorted(part_of[order], np.arange(K + 1))
@@ -219,6 +222,9 @@ def search_legs(legs, iters, res):
         res["ivf_search_host_finishes"] = int(idx.host_finishes())
     if "refine" in legs:
         refine_leg(idx, vectors, queries, ma, iters, res)
+    if "keyed" in legs:
+        keyed_leg(idx, vectors, queries, ma, iters, res, codebooks, coarse)
+    if "refine" in legs or "keyed" in legs:
         del vectors
     if "filter" in legs:   # (b): the same search() without a filter and with 10 % of the keys excluded, in turn, under both finishes
         S = rng.permutation(n)[:n // 10].astype(np.uint32)
@@ -429,6 +435,90 @@ def refine_leg(idx, vectors, queries, ma, iters, res):
                   % (dtype, r_in, R, res[tag + "_recall"], t_search * 1e3, t_rerank * 1e3, t_both * 1e3, t_torch * 1e3,
                      res[tag + "_gather_bytes"] / 1e6, res[tag + "_gather_bytes"] / t_rerank / 1e12), flush=True)
         st.close()
+
+
+def keyed_leg(idx, vectors, queries, ma, iters, res, codebooks, coarse):
+    """caller-chosen labels: what the keyed store's probe costs beside the dense store's range test, what
+    put and remove sustain, and what a label array costs add_vectors"""
+    import torch
+    dev = torch.device("cuda", 0)
+    n, dim = vectors.shape
+    nq = len(queries)
+    tq = torch.from_numpy(queries).to(dev)
+    tx = torch.from_numpy(vectors).to(dev)
+    positions = torch.arange(n, dtype=torch.int32, device=dev)                  # the index's keys are positions: both stores hold them
+    rng = np.random.default_rng(7)
+    # 1. the same vectors under the same keys in a dense and in a keyed store: rerank_device in turn
+    for dtype in ("f32", "f16"):
+        dense, keyed = pyqadc.Refine(dim, dtype), pyqadc.Refine(dim, dtype, keyed=True)
+        dense.add_device(tx)
+        keyed.put_device(tx, positions)
+        info = keyed.keyed_info()
+        res["keyed_%s_table_and_row_state_bytes_per_key" % dtype] = (12 * info["table_slots"] + 8 * info["rows_allocated"]) / info["live"]
+        for r_in in (400, 1000):
+            ck, cv, _ = idx.search_device(tq, ma, r_in)
+            a, b = dense.rerank_device(tq, ck, R, values=cv), keyed.rerank_device(tq, ck, R, values=cv)
+            assert a[3] == b[3] == 0 and all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a[:3], b[:3])), "the stores disagree"
+            t_dense, t_keyed = alternated(lambda: dense.rerank_device(tq, ck, R, values=cv), lambda: keyed.rerank_device(tq, ck, R, values=cv),
+                                          max(10, iters))
+            tag = "keyed_%s_rin%d" % (dtype, r_in)
+            res[tag + "_dense_rerank_ms"], res[tag + "_keyed_rerank_ms"] = t_dense * 1e3, t_keyed * 1e3
+            res[tag + "_keyed_over_dense"] = t_keyed / t_dense
+            print("%s stores, r_in %d, rerank_device of %d queries, alternated: dense %.3f ms, keyed %.3f ms (keyed / dense = %.3f); table of %d "
+                  "slots, %d used" % (dtype, r_in, nq, t_dense * 1e3, t_keyed * 1e3, t_keyed / t_dense, info["table_slots"], info["table_used"]),
+                  flush=True)
+        dense.close()
+        keyed.close()
+    # 2. put_device and remove_device at 10^6 keys drawn from all 32 bits
+    sparse = np.unique(rng.integers(0, 0xFFFFFFFF, 2 * n, dtype=np.uint64).astype(np.uint32))
+    tl = torch.from_numpy(rng.permutation(sparse)[:n].view(np.int32).copy()).to(dev)
+    for dtype in ("f32", "f16"):
+        fresh, reserved, over, gone, again = [], [], [], [], []
+        for _ in range(max(3, iters // 3)):
+            for bucket, reserve in ((fresh, False), (reserved, True)):
+                st = pyqadc.Refine(dim, dtype, keyed=True)
+                if reserve:
+                    st.reserve(n)
+                t0 = time.perf_counter()
+                st.put_device(tx, tl)
+                bucket.append(time.perf_counter() - t0)
+                if not reserve:
+                    st.close()
+            t0 = time.perf_counter()
+            st.put_device(tx, tl)                                               # every key is held: an overwrite
+            over.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            removed = st.remove_device(tl)
+            gone.append(time.perf_counter() - t0)
+            assert removed == n
+            t0 = time.perf_counter()
+            st.put_device(tx, tl)                                               # into dead slots and freed rows
+            again.append(time.perf_counter() - t0)
+            st.close()
+        for name, ts in (("put_fresh", fresh), ("put_reserved", reserved), ("put_overwrite", over), ("remove", gone), ("put_after_remove", again)):
+            res["keyed_%s_%s_rows_per_s" % (dtype, name)] = n / float(np.median(ts))
+        print("%s keyed store, 10^6 keys of dim %d in one call (device forms): put into an empty store %.3g rows/s, after reserve %.3g, overwriting "
+              "%.3g, remove %.3g, put after the remove %.3g" % ((dtype, dim) + tuple(res["keyed_%s_%s_rows_per_s" % (dtype, k)] for k in
+              ("put_fresh", "put_reserved", "put_overwrite", "remove", "put_after_remove"))), flush=True)
+    # 3. add_vectors_device with a label array against the plain call
+    def build(labels):
+        ix = pyqadc.AdcIndex(idx.sq_count, 8)
+        ix.set_pq(codebooks)
+        ix.set_coarse(coarse)
+        t0 = time.perf_counter()
+        ix.add_vectors_device(tx, labels=labels)
+        t = time.perf_counter() - t0
+        ix.close()
+        return t
+    build(None), build(tl)
+    plain, labelled = [], []
+    for _ in range(max(3, iters // 3)):
+        plain.append(build(None))
+        labelled.append(build(tl))
+    res["keyed_add_vectors_device_plain_s"], res["keyed_add_vectors_device_labelled_s"] = float(np.median(plain)), float(np.median(labelled))
+    res["keyed_add_labelled_over_plain"] = res["keyed_add_vectors_device_labelled_s"] / res["keyed_add_vectors_device_plain_s"]
+    print("add_vectors_device of 10^6 vectors into an empty index, alternated: plain %.3f s, labels=... %.3f s (labelled / plain = %.3f)"
+          % (res["keyed_add_vectors_device_plain_s"], res["keyed_add_vectors_device_labelled_s"], res["keyed_add_labelled_over_plain"]), flush=True)
 
 
 def filter_leg(bits, iters, res, torch=None):
@@ -1173,7 +1263,7 @@ def main():
                 f.write(line + "\n")
         return
     torch = None
-    if "ivf" in legs or "filter" in legs or "refine" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:
             import torch
             torch.zeros(1, device="cuda")
@@ -1262,7 +1352,7 @@ def main():
             print("the same alternated with query_scan_device (tables and heaps stay in device memory): %.2f ms against %.2f ms"
                   % (med_d * 1e3, med_h * 1e3), flush=True)
         idx.close()
-    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs or "range" in legs:
+    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs or "range" in legs or "keyed" in legs:
         search_legs(legs, a.iters, res)
     if "filter" in legs:
         filter_leg(8, a.iters, res, torch)

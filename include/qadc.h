@@ -560,6 +560,9 @@ typedef struct qadc_profile {
     uint64_t bktw4_launches;        /* ... for 4, */
     uint64_t bktw5_launches;        /* ... for 5 */
     uint64_t bktw6_launches;        /* ... and for 6: the four add up to bktw_launches */
+    uint64_t bktw_prune_skipped;    /* wide launches with the group test (qadc_index_set_bkt_prune): wave iterations (64 lane groups of 16 slots) that loaded no plane, */
+    uint64_t bktw_prune_run;        /* ... wave iterations that ran (skipped + run = bktw_slots / 1024 of those launches) */
+    uint64_t bktw_prune_groups;     /* ... and lane groups whose free rows reached the bound, in skipped and in run iterations */
 } qadc_profile;
 
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);
@@ -624,9 +627,17 @@ int qadc_index_set_split_bkt(qadc_index* idx, uint64_t bkt_min_run, uint64_t bkt
  * wide_block afterwards (qadc_index_set_split_bkt, or the env hooks) raises the octaves' start to bkt_block at finalize:
  * qadc_index_bktw_info reports the W in use.
  * QADC_BKT_WIDE_BLOCK / QADC_BKTW_MIN_RUN / QADC_BKTW5_MIN_RUN / QADC_BKTW4_MIN_RUN / QADC_BKTW3_MIN_RUN override the defaults at
- * qadc_index_create (with QADC_TEST_HOOKS=1).  Defaults: profiles/r12_bktw_ab.txt. */
+ * qadc_index_create (with QADC_TEST_HOOKS=1).  Defaults: min_run = 2^27 and no other threshold (6 paid planes) since the group test
+ * below: profiles/r13_prune_ab.txt (4 planes from 2^27 on before it: profiles/r12_bktw_ab.txt). */
 int qadc_index_set_split_bkt_wide(qadc_index* idx, uint64_t wide_block, uint64_t min_run, uint64_t min_run5, uint64_t min_run4,
                                   uint64_t min_run3, double wide_max_pad);
+
+/* Group test of the wide form ("pruned groups"): mode 1 = a wave iteration whose 64 lane groups all have
+ * (their five free rows' entries) + (the paid rows' minima) >= bound - c loads no plane and looks nothing up; 0 = the form as it
+ * was, the same kernels.  Exact for any codes and tables: no result, survivor count or candidate changes.  May be set at any time;
+ * applies to batches submitted afterwards.  QADC_BKT_PRUNE overrides the default at qadc_index_create (with QADC_TEST_HOOKS=1).
+ * Default 1: profiles/r13_prune_ab.txt. */
+int qadc_index_set_bkt_prune(qadc_index* idx, int mode);
 
 /* The wide form's choice: out[16 t + 4 (NSP - 3) ..] = the deferred set among sub-quantizers 5-15 for NSP = 3, 4, 5, 6 paid
  * planes as a 16-bit mask (low byte first), the slack c, 0.  A diagnostic. */

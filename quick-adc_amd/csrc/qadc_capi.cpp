@@ -120,6 +120,8 @@ int bind_state_and_result(qadc_index* idx, Slot& s, Staged& g) {
     if (g.any_nib) HIPCHECK(s.d_nib_sel.ensure((size_t)kNibSelBytes * nq * ma));
     if (g.any_bkt) HIPCHECK(s.d_bkt_sel.ensure((size_t)kBktSelBytes * nq * ma));
     if (g.any_bktw) HIPCHECK(s.d_bktw_sel.ensure((size_t)kBktwSelBytes * nq * ma));
+    s.prune_counted = g.any_bktw && idx->profile && idx->bkt_prune != 0;
+    if (s.prune_counted) HIPCHECK(s.d_prune_cnt.ensure(3));
     return QADC_OK;
 }
 
@@ -235,7 +237,8 @@ int launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, h
                                       : nullptr,
                        ll.split5 ? s.d_plane_sel5.p : nullptr, ll.nib ? s.d_nib_sel.p : nullptr, ll.nib,
                        ll.bktw ? s.d_bktw_sel.p : ll.bkt ? s.d_bkt_sel.p : nullptr, ll.bktw ? ll.bktw : ll.bkt,
-                       ll.bktw ? 5 : 4);                           // (the wide form first, then the bucket form, then the nibble form)
+                       ll.bktw ? 5 : 4,                            // (the wide form first, then the bucket form, then the nibble form)
+                       ll.bktw ? idx->bkt_prune : 0, ll.bktw && s.prune_counted ? s.d_prune_cnt.p : nullptr);
     return QADC_OK;
 }
 
@@ -434,6 +437,7 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
     // event hops (~15 us of a ~130 us single query).
     hipStream_t st = g.alone ? idx->stream : idx->front_stream;
     HIPCHECK(hipMemsetAsync(s.d_state.p, 0, g.state_bytes, st));
+    if (s.prune_counted) HIPCHECK(hipMemsetAsync(s.d_prune_cnt.p, 0, 3 * sizeof(unsigned long long), st));
     if (int rc = upload_and_wait(idx, s, g.in_bytes, st, g.alone)) return rc;
     s.prof_used = 0;
     if (int rc = launch_front(idx, s, plan, g, st)) return rc;
@@ -819,6 +823,13 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             unsigned long long surv = 0;
             HIPCHECK(hipMemcpy(&surv, s.d_state.p + kSurvBktwOff, sizeof(surv), hipMemcpyDeviceToHost));
             idx->prof.bktw_survivors += surv;
+        }
+        if (count_bktw && s.prune_counted) {
+            unsigned long long cnt[3] = {0, 0, 0};
+            HIPCHECK(hipMemcpy(cnt, s.d_prune_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost));
+            idx->prof.bktw_prune_skipped += cnt[0];
+            idx->prof.bktw_prune_run += cnt[1];
+            idx->prof.bktw_prune_groups += cnt[2];
         }
         if (s.float_path) idx->prof.start_codes += s.start_codes;
     }
@@ -1283,6 +1294,7 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
         if (const char* e = std::getenv("QADC_BKTW4_MIN_RUN")) idx->bktw4_min_run = std::strtoull(e, nullptr, 10);
         if (const char* e = std::getenv("QADC_BKTW3_MIN_RUN")) idx->bktw3_min_run = std::strtoull(e, nullptr, 10);
         if (idx->bkt_wide_block & (idx->bkt_wide_block - 1)) idx->bkt_wide_block = 0;     // (not a power of two: none)
+        if (const char* e = std::getenv("QADC_BKT_PRUNE")) idx->bkt_prune = std::atoi(e) != 0 ? 1 : 0;   // the wide form's group test
     }
     if (int rc = attach_streams(idx)) {
         delete idx;
@@ -1328,7 +1340,7 @@ int qadc_index_destroy(qadc_index* idx) {
     for (Slot* sp : all_slots) {
         Slot& s = *sp;
         s.d_in.release(); s.h_in.release(); s.d_state.release(); s.h_result.release();
-        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_plane_sel5.release(); s.d_nib_sel.release(); s.d_bkt_sel.release(); s.d_bktw_sel.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
+        s.d_ftables.release(); s.d_qtables.release(); s.d_plane_sel.release(); s.d_plane_sel5.release(); s.d_nib_sel.release(); s.d_bkt_sel.release(); s.d_bktw_sel.release(); s.d_prune_cnt.release(); s.d_cands.release(); s.d_fc.release(); s.d_lfstate.release();
         s.h_cands.release(); s.d_stream.release(); s.d_qflags.release(); s.d_fvals.release(); s.d_qcands.release(); s.h_fetch.release();
         s.d_fblock.release(); s.d_fgathered.release(); s.d_front_all.release(); s.h_fmap.release();
         if (s.ev_fa) (void)hipEventDestroy(s.ev_fa);
@@ -2235,6 +2247,13 @@ int qadc_index_set_split_bkt_wide(qadc_index* idx, uint64_t wide_block, uint64_t
     idx->bktw4_min_run = min_run4;
     idx->bktw3_min_run = min_run3;
     idx->bkt_wide_max_pad = wide_max_pad;
+    return QADC_OK;
+}
+
+int qadc_index_set_bkt_prune(qadc_index* idx, int mode) {
+    if (!idx) return fail(QADC_E_ARG, "null index");
+    if (mode != 0 && mode != 1) return fail(QADC_E_ARG, "bkt_prune is 0 or 1");
+    idx->bkt_prune = mode;
     return QADC_OK;
 }
 

@@ -181,6 +181,8 @@ struct Slot {
     DevBuf<uint8_t> d_plane_sel;        // 16x4: the 6-plane split form's deferred byte of every table of the batch (written beside d_qt)
     DevBuf<uint8_t> d_bkt_sel;          // ... and the bucket form's kBktSelBytes per table (deferred masks and slacks for NSP = 4..7)
     DevBuf<uint8_t> d_bktw_sel;         // ... and its wide form's kBktwSelBytes per table (NSP = 3..6 among sub-quantizers 5-15)
+    DevBuf<unsigned long long> d_prune_cnt;   // profiling: the wide form's group-test counters of the batch (skipped, run, pruned)
+    bool prune_counted = false;         // ... are in use by this batch
     DevBuf<uint8_t> d_nib_sel;          // ... and the nibble form's kNibSelBytes per table (deferred masks and slacks for NS = 8, 9, 10)
     DevBuf<uint8_t> d_plane_sel5;       // ... and the 5-plane form's two bytes per table: j1 | j2 << 4, slack (launch_scan_i8)
     DevBuf<Cand> d_cands;
@@ -469,13 +471,19 @@ struct qadc_index {
     // wide blocks of the bucket copy (qadc_index_set_split_bkt_wide): positions from bkt_wide_block on are stored in
     // octave blocks grouped by a 20-bit key (0 = none), unless padding inflates an octave beyond bkt_wide_max_pad x its codes (that
     // octave keeps narrow blocks).  Runs of at least bktw_min_run codes that cover whole wide octaves take the wide form with 6 paid
-    // planes, 5 / 4 / 3 from bktw5 / bktw4 / bktw3_min_run on (0 = never; profiles/r12_bktw_ab.txt)
+    // planes, 5 / 4 / 3 from bktw5 / bktw4 / bktw3_min_run on (0 = never; profiles/r12_bktw_ab.txt).  With the group test below a paid
+    // plane is loaded for the kept wave iterations only and 6 / 6 paid planes became the fastest arm (profiles/r13_prune_ab.txt; they
+    // were 4 / 4 without it)
     uint64_t bkt_wide_block = 1ull << 27;
     uint64_t bktw_min_run = 1ull << 27;
-    uint64_t bktw5_min_run = 1ull << 27;
-    uint64_t bktw4_min_run = 1ull << 27;
+    uint64_t bktw5_min_run = 0;
+    uint64_t bktw4_min_run = 0;
     uint64_t bktw3_min_run = 0;
     double bkt_wide_max_pad = 1.08;
+    // the wide form's group test (qadc_index_set_bkt_prune; profiles/r13_prune_ab.txt): 1 = wave iterations in which no lane group's free
+    // rows leave room under the bound load no plane, 0 = the kernels without the test (then set bktw5_min_run = bktw4_min_run = 2^27 as
+    // well: without the test 4 paid planes are the fastest arm and 6 the slowest even one)
+    int bkt_prune = 1;
     // one workgroup per query (IVF batches, small lists): 0 = never, 1 = auto, 2 = whenever structurally possible
     int wgq = 1;
     uint32_t wgq_capacity = 4096;        // stream entries per query to start with

@@ -916,11 +916,11 @@ __device__ __forceinline__ uint64_t bktw_streamed(uint32_t mask, uint32_t& used,
 // paid).  FREE = 5: wide octaves (20-bit key, 11 planes of sub-quantizers 5-15, NSP = 3..6 paid; the group's sub-quantizer 4 is
 // one more byte of its id: s0 = P01[id & 255] + P23[id >> 8] + T4[id4], or, NSP odd, row 4 joins the first paid plane's pair table
 // with id4 splatted into the low nibbles of the merged index).  sel = the form's choice bytes of every table.
-template <int FREE, int NSP, bool NT, bool CHUNK, bool PROBE>
+template <int FREE, int NSP, bool NT, bool CHUNK, bool PROBE, bool PRUNE>
 __device__ __forceinline__ void scan_bkt_body(
     const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
     CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
-    const uint8_t* __restrict__ bkt_sel, unsigned long long* __restrict__ surv) {
+    const uint8_t* __restrict__ bkt_sel, unsigned long long* __restrict__ surv, unsigned long long* __restrict__ prune_cnt) {
     static_assert(FREE == 4 || FREE == 5, "16-bit or 20-bit key");
     static_assert(FREE == 5 || (NSP >= 4 && NSP <= 7), "4, 5, 6 or 7 of the 12 paid nibble planes");
     static_assert(FREE == 4 || (NSP >= 3 && NSP <= 6), "3, 4, 5 or 6 of the 11 paid nibble planes");
@@ -981,6 +981,27 @@ __device__ __forceinline__ void scan_bkt_body(
         poff[i] = (((uint32_t)(paid >> (4 * i)) & 15u) - (uint32_t)FREE) % (WIDE ? kBktwPlanes : kBktPlanes) * (kSplitTile / 16);
     const uint32_t bsurv = bound > slack ? bound - slack : 0u;  // 0 = no survivor (never wraps)
     const uint32_t bound4 = bsurv * 0x01010101u;
+    // PRUNE: pmin = the sum over the rows the pair loop adds (the paid ones and, FUSE, row 4) of min T[s], from the staged int8
+    // table (build_nib_tables' barrier is behind us).  With s0 = the rows the loop starts from, every slot of a lane group has
+    // partial >= s0 + pmin, so s0 + pmin >= bsurv means min(127, partial) >= bsurv in all 16: no survivor, and the group needs
+    // neither its planes nor its pair lookups (bsurv <= 127; 32-bit sums: s0 <= 5 x 127, pmin <= 7 x 127; bsurv = 0 keeps nothing).
+    [[maybe_unused]] uint32_t pmin = 0;
+    if constexpr (PRUNE) {
+        auto row_min = [&](uint32_t sq) __attribute__((always_inline)) {
+            const uint32_t* row = reinterpret_cast<const uint32_t*>(smem + C::STAGE_OFF + 16u * sq);
+            uint32_t m = 255u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t x = row[j];
+                m = min(min(m, x & 0xffu), min((x >> 8) & 0xffu, min((x >> 16) & 0xffu, x >> 24)));
+            }
+            return m;
+        };
+#pragma unroll
+        for (int i = 0; i < NSP; ++i) pmin += row_min((uint32_t)(paid >> (4 * i)) & 15u);
+        if constexpr (FUSE) pmin += row_min(4u);
+    }
+    [[maybe_unused]] uint32_t nskip = 0, niter = 0, npruned = 0;   // (wave-uniform) PRUNE: wave iterations skipped / all, lane groups pruned
 
     // survivors of the previous iteration: byte k of pend[w] = min(127, partial) of the lane's slot 4 w + k, 0xff = none
     uint32_t pend[4] = {~0u, ~0u, ~0u, ~0u};
@@ -1033,20 +1054,57 @@ __device__ __forceinline__ void scan_bkt_body(
             }
         }
     };
-    auto step_tile = [&](uint32_t t) __attribute__((always_inline)) {
-        u32x2 v[NSP];
-        const uint32_t e0 = t * (kTile / 8) + tid;              // vector index of plane 0 (t < 2^18: no wrap)
+    // the lane group's id of tile t (and, WIDE, its sub-quantizer 4)
+    auto load_ids = [&](uint32_t t, uint32_t& id, uint32_t& id4) __attribute__((always_inline)) {
         const gid_t idp = ids + (uint64_t)t * (kTile / 2);
-        const uint32_t id = NT ? __builtin_nontemporal_load(idp) : *idp;
-        uint32_t id4 = 0;                                       // WIDE: the group's sub-quantizer 4
+        id = NT ? __builtin_nontemporal_load(idp) : *idp;
+        id4 = 0;
         if constexpr (WIDE) {
             const gbyte_t p4 = id4s + (uint64_t)t * kTile;
             id4 = (NT ? __builtin_nontemporal_load(p4) : *p4) & 15u;
         }
+    };
+    // the rows the pair loop starts from: P01[id & 255] in slot 0, P23[id >> 8] in slot 1 and, WIDE with an even NSP, the fifth free
+    // row: the single row's low-nibble slot, T4[x & 15] (FUSE: row 4 is in the first pair table, not here)
+    auto free_rows = [&](uint32_t id, uint32_t id4) __attribute__((always_inline)) {
+        uint32_t s0 = *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id & 0xffu) << 8) | lane_lo) + 0u)) +
+                      *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id >> 8) & 0xffu) << 8 | lane_lo) + 1u));
+        if constexpr (WIDE && !FUSE) {
+            constexpr int sl = NP + 2;
+            s0 += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((id4 << 8) | lane_lo) + (sl >> 2) * 128 + (sl & 3)));
+        }
+        return s0;
+    };
+    // PRUNE: pid / pid4 = the tile's ids, loaded one iteration early, so that the decision comes before the plane loads
+    auto step_tile = [&](uint32_t t, [[maybe_unused]] uint32_t pid, [[maybe_unused]] uint32_t pid4) __attribute__((always_inline)) {
+        u32x2 v[NSP];
+        const uint32_t e0 = t * (kTile / 8) + tid;              // vector index of plane 0 (t < 2^18: no wrap)
+        uint32_t id, id4;                                       // (id4: WIDE, the group's sub-quantizer 4)
+        [[maybe_unused]] uint32_t s0p = 0;
+        bool run = true;                                        // (uniform) PRUNE: some lane of the wave keeps its group
+        if constexpr (PRUNE) {
+            id = pid;
+            id4 = pid4;
+            s0p = free_rows(id, id4);
+            const uint64_t keep = __builtin_amdgcn_ballot_w64(s0p + pmin < bsurv);   // lanes whose group may hold a survivor
+            ++niter;
+            npruned += 64u - (uint32_t)__builtin_popcountll(keep);
+            run = keep != 0;                                    // no lane keeps: an iteration with no survivor, without its loads and lookups
+            nskip += run ? 0u : 1u;
+        } else {
+            load_ids(t, id, id4);
+        }
+        if (run) {
 #pragma unroll
-        for (int i = 0; i < NSP; ++i)
-            v[i] = NT ? __builtin_nontemporal_load(planes + e0 + poff[i]) : planes[e0 + poff[i]];
+            for (int i = 0; i < NSP; ++i)
+                v[i] = NT ? __builtin_nontemporal_load(planes + e0 + poff[i]) : planes[e0 + poff[i]];
+        }
         if (__builtin_expect(any_pend, 0)) resolve();           // the previous iteration's survivors, behind this one's loads
+        if (!run) {
+            // as after an iteration with no survivor: that one leaves pend's bytes as resolve() wrote them too and clears the flag
+            // only; pend is read under any_pend alone (resolve, the drain), res under any_res alone
+            any_pend = false;
+        } else {
         const uint32_t base = t * kSplitTile + tid * 16u;       // run slot of the lane's slot 0
         uint32_t cv[16];
         uint32_t best = 127u;
@@ -1060,13 +1118,7 @@ __device__ __forceinline__ void scan_bkt_body(
             best = cv[0];
         } else {
             constexpr uint32_t LO = 0x0f0f0f0fu;
-            // the group's four free rows: P01[id & 255] in slot 0, P23[id >> 8] in slot 1
-            uint32_t s0 = *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id & 0xffu) << 8) | lane_lo) + 0u)) +
-                          *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id >> 8) & 0xffu) << 8 | lane_lo) + 1u));
-            if constexpr (WIDE && !FUSE) {                      // the fifth free row: the single row's low-nibble slot, T4[x & 15]
-                constexpr int sl = NP + 2;
-                s0 += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((id4 << 8) | lane_lo) + (sl >> 2) * 128 + (sl & 3)));
-            }
+            const uint32_t s0 = PRUNE ? s0p : free_rows(id, id4);   // the group's free rows
             [[maybe_unused]] const uint32_t id4s8 = id4 * 0x11111111u;           // FUSE: id4 in every nibble, the pair loop's plane 0
 #pragma unroll
             for (int w = 0; w < 2; ++w) {
@@ -1113,12 +1165,23 @@ __device__ __forceinline__ void scan_bkt_body(
             pend_base = base;
             any_pend = true;
         }
+        }
         if (__builtin_expect(any_res, 0)) {                     // the previous iteration's candidates
             emit_res();
             any_res = false;
         }
     };
-    for (uint32_t t = first; t < last; t += step) step_tile(t);
+    if constexpr (PRUNE) {
+        uint32_t nid = 0, nid4 = 0;
+        if (first < last) load_ids(first, nid, nid4);
+        for (uint32_t t = first; t < last; t += step) {
+            const uint32_t id = nid, id4 = nid4;
+            if (t + step < last) load_ids(t + step, nid, nid4);   // (t + step < 2^19: no wrap)
+            step_tile(t, id, id4);
+        }
+    } else {
+        for (uint32_t t = first; t < last; t += step) step_tile(t, 0u, 0u);
+    }
     if (any_pend) {
         resolve();
         if (any_res) emit_res();
@@ -1133,6 +1196,21 @@ __device__ __forceinline__ void scan_bkt_body(
         __syncthreads();
         if (tid == 0 && *cnt) atomicAdd(surv, (unsigned long long)*cnt);
     }
+    if constexpr (PRUNE) {
+        if (prune_cnt) {                                        // (uniform; profile option only) skipped, run, pruned: the same way
+            uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + C::HIST_OFF);
+            __syncthreads();
+            if (tid < 3) cnt[tid] = 0;
+            __syncthreads();
+            if ((tid & 63u) == 0) {
+                atomicAdd(cnt, nskip);
+                atomicAdd(cnt + 1, niter - nskip);
+                atomicAdd(cnt + 2, npruned);
+            }
+            __syncthreads();
+            if (tid < 3 && cnt[tid]) atomicAdd(prune_cnt + tid, (unsigned long long)cnt[tid]);
+        }
+    }
 }
 
 template <int NSP, bool NT, bool CHUNK, bool PROBE>
@@ -1140,7 +1218,7 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_bkt_kernel(
     const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
     CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
     const uint8_t* __restrict__ bkt_sel, unsigned long long* __restrict__ surv) {
-    scan_bkt_body<4, NSP, NT, CHUNK, PROBE>(items, qtables, qstates, hdr, out, cand_cap, R, bkt_sel, surv);
+    scan_bkt_body<4, NSP, NT, CHUNK, PROBE, false>(items, qtables, qstates, hdr, out, cand_cap, R, bkt_sel, surv, nullptr);
 }
 
 // The wide form ("wide octaves"): the runs read wide tiles, bktw_sel = kBktwSelBytes per table (plane_choice_bktw).
@@ -1149,7 +1227,18 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_bktw_kernel(
     const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
     CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
     const uint8_t* __restrict__ bktw_sel, unsigned long long* __restrict__ surv) {
-    scan_bkt_body<5, NSP, NT, CHUNK, PROBE>(items, qtables, qstates, hdr, out, cand_cap, R, bktw_sel, surv);
+    scan_bkt_body<5, NSP, NT, CHUNK, PROBE, false>(items, qtables, qstates, hdr, out, cand_cap, R, bktw_sel, surv, nullptr);
+}
+
+// ... with the group test ("pruned groups"): a wave iteration in which no lane group can hold a survivor loads no
+// plane and issues no pair lookup.  prune_cnt (profile option only, else null): wave iterations skipped, wave iterations run, lane
+// groups pruned, one atomicAdd each per workgroup at exit.
+template <int NSP, bool NT, bool CHUNK, bool PROBE>
+__global__ __launch_bounds__(kWG, 8) void scan_i8_bktw_prune_kernel(
+    const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
+    CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
+    const uint8_t* __restrict__ bktw_sel, unsigned long long* __restrict__ surv, unsigned long long* __restrict__ prune_cnt) {
+    scan_bkt_body<5, NSP, NT, CHUNK, PROBE, true>(items, qtables, qstates, hdr, out, cand_cap, R, bktw_sel, surv, prune_cnt);
 }
 
 
@@ -2158,6 +2247,17 @@ static void launch_bktw_variant(dim3 grid, hipStream_t stream, const ScanItem* d
                        d_bktw_sel, d_surv);
 }
 
+template <int NSP, bool NT, bool CHUNK, bool PROBE>
+static void launch_bktw_prune_variant(dim3 grid, hipStream_t stream, const ScanItem* d_items, const int8_t* d_qtables,
+                                      QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap, uint32_t R,
+                                      const uint8_t* d_bktw_sel, unsigned long long* d_surv, unsigned long long* d_prune_cnt) {
+    auto k = &scan_i8_bktw_prune_kernel<NSP, NT, CHUNK, PROBE>;
+    static std::atomic<uint64_t> done{0};
+    ensure_dynamic_lds(reinterpret_cast<const void*>(k), ScanCfg<16>::LDS_BYTES, done);
+    hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<16>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R,
+                       d_bktw_sel, d_surv, d_prune_cnt);
+}
+
 // variant bits: [2] NT (non-temporal loads)  [3] CHUNK  [4] PROBE (ceiling diagnostic)
 // [5] split form (16x4, every run of the launch has ScanItem::split; not with [6]): 5 planes when d_plane_sel5 (the two
 //     deferred bytes and the slack of every table) is given, else 6 planes when d_plane_sel (the deferred byte of every
@@ -2165,11 +2265,13 @@ static void launch_bktw_variant(dim3 grid, hipStream_t stream, const ScanItem* d
 //     nib_ns = 8, 9 or 10 with d_nib_sel (ScanItem::split of every run points into the nibble-plane copy): the nibble form, before all of these
 //     bkt_nsp = 4..7 with d_bkt_sel (every run of the launch is a bucket-form run, LevelLaunch::bkt): the bucket form, before the nibble form
 //     bkt_free = 5, bkt_nsp = 3..6, d_bkt_sel = the wide form's choice bytes (LevelLaunch::bktw): the wide form, before all of these
+//     ... bkt_prune != 0: its build with the group test (scan_i8_bktw_prune_kernel; d_prune_cnt: its three counters or nullptr)
 // [6] sibling-major 1-D launch (every run of the launch covers the same codes; see the kernel's decode).  Other bits: ignored.
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap,
                     uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel, unsigned long long* d_surv,
-                    const uint8_t* d_plane_sel5, const uint8_t* d_nib_sel, int nib_ns, const uint8_t* d_bkt_sel, int bkt_nsp, int bkt_free) {
+                    const uint8_t* d_plane_sel5, const uint8_t* d_nib_sel, int nib_ns, const uint8_t* d_bkt_sel, int bkt_nsp, int bkt_free,
+                    int bkt_prune, unsigned long long* d_prune_cnt) {
     if (bkt_free == 5) {
         // a wide launch is never anything else: launch_level (qadc_capi.cpp) refuses one whose preconditions do not hold with an error
         // status before it gets here, so a violation is a programming error and must not pass as a level that was silently not scanned
@@ -2186,7 +2288,24 @@ void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int
         case 2: launch_bktw_variant<NSP, false, true, PR>(QADC_BKTW_ARGS); break;  \
         default: launch_bktw_variant<NSP, true, true, PR>(QADC_BKTW_ARGS); break;  \
     }
-        if (bkt_nsp == 3) {
+#define QADC_BKTWP(NSP, PR)                                                                           \
+    switch ((variant >> 2) & 3) {                                                                    \
+        case 0: launch_bktw_prune_variant<NSP, false, false, PR>(QADC_BKTW_ARGS, d_prune_cnt); break; \
+        case 1: launch_bktw_prune_variant<NSP, true, false, PR>(QADC_BKTW_ARGS, d_prune_cnt); break;  \
+        case 2: launch_bktw_prune_variant<NSP, false, true, PR>(QADC_BKTW_ARGS, d_prune_cnt); break;  \
+        default: launch_bktw_prune_variant<NSP, true, true, PR>(QADC_BKTW_ARGS, d_prune_cnt); break;  \
+    }
+        if (bkt_prune) {
+            if (bkt_nsp == 3) {
+                if (variant & 16) { QADC_BKTWP(3, true) } else { QADC_BKTWP(3, false) }
+            } else if (bkt_nsp == 4) {
+                if (variant & 16) { QADC_BKTWP(4, true) } else { QADC_BKTWP(4, false) }
+            } else if (bkt_nsp == 5) {
+                if (variant & 16) { QADC_BKTWP(5, true) } else { QADC_BKTWP(5, false) }
+            } else {
+                if (variant & 16) { QADC_BKTWP(6, true) } else { QADC_BKTWP(6, false) }
+            }
+        } else if (bkt_nsp == 3) {
             if (variant & 16) { QADC_BKTW(3, true) } else { QADC_BKTW(3, false) }
         } else if (bkt_nsp == 4) {
             if (variant & 16) { QADC_BKTW(4, true) } else { QADC_BKTW(4, false) }
@@ -2197,6 +2316,7 @@ void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int
         }
 #undef QADC_BKTW_ARGS
 #undef QADC_BKTW
+#undef QADC_BKTWP
         return;
     }
     if (M == 16 && (variant & 32) && !(variant & 64) && d_bkt_sel && bkt_nsp >= 4 && bkt_nsp <= 7) {

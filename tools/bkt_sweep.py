@@ -1,5 +1,5 @@
 """Same-process sweep behind the bucket form's defaults (profiles/r11_bkt_ab.txt).
-usage: python tools/bkt_sweep.py [reps=2] [codes=1e9] [wide=W]
+usage: python tools/bkt_sweep.py [reps=2] [codes=1e9] [wide=W] [prune=1]
 
 One index of the headline's list and mode (bench.py's one-query-per-pass options, 32-query steps pipelined three deep) holding
 BOTH the bucket copy (blocks of 2^25) and the nibble-plane copy: it is finalized with bkt_min_run above every run (600 Mi), so
@@ -12,7 +12,12 @@ round, arm): ms per step and the library's bkt_* and nib_* counters per step; a 
 With a third argument wide=W (W = 2^27 or 2^29; profiles/r12_bktw_ab.txt) the index is the default one with wide blocks from W on
 (a range stored wide has no narrow blocks and the index no nibble-plane copy, so the narrow arms cannot run beside them): arms
 "w:pYZ" = Y and Z paid planes of rows 5-15 at the levels from 2^27 and 2^29 (W = 2^29: "w:pZ", the level from 2^27 keeps the narrow
-form's 5), the level from 2^25 the narrow form's 6; the PROBE section times "w:p44".  The lines carry the bktw_* counters as well."""
+form's 5), the level from 2^25 the narrow form's 6; the PROBE section times "w:p44".  The lines carry the bktw_* counters as well.
+
+With a fourth argument prune=1 (profiles/r13_prune_ab.txt) every wide arm runs twice, interleaved: without the wide form's group
+test (Index.set_bkt_prune(0)) and, named "w:pYZ+g", with it; without the argument the arms run under the library's default, which
+is the test on.  A fifth argument variant=V (default 0x0d) sets the loop form of the sweep section: 0x05 = strided tiles in place of chunks; the PROBE section times both builds of "w:p44", and the lines carry the
+group test's counters (wave iterations skipped and run, lane groups pruned)."""
 import json
 import os
 import sys
@@ -45,7 +50,7 @@ def arm_thresholds(name):
 
 def wide_thresholds(name):
     """"w:pYZ" / "w:pZ" -> (min_run5, min_run4, min_run3): thresholds that the level's runs and the longer ones reach."""
-    planes = [int(c) for c in name.split("p")[1]]
+    planes = [int(c) for c in name.split("+")[0].split("p")[1]]
     planes = [planes[0]] * (2 - len(planes)) + planes            # per level from 2^27, 2^29 (non-increasing)
     reach = (128 * MI, 400 * MI)
     t = {}
@@ -81,6 +86,8 @@ def main():
             idx.collect(pending.pop(0))
 
     wide = int(float(sys.argv[3].split("=")[1])) if len(sys.argv) > 3 and sys.argv[3].startswith("wide=") else 0
+    prune = len(sys.argv) > 4 and sys.argv[4] == "prune=1"
+    sweep_variant = int(sys.argv[5].split("=")[1], 0) if len(sys.argv) > 5 and sys.argv[5].startswith("variant=") else 0x0d
     idx = pyqadc.Index(M, 0)
     if wide:
         idx.set_split_bkt_wide(wide, min(max(wide, 128 * MI), 400 * MI), 0, 0, 0)
@@ -100,6 +107,8 @@ def main():
         idx.set_option("variant", variant)
         if wide:
             idx.set_split_bkt_wide(wide, min(max(wide, 128 * MI), 400 * MI), *wide_thresholds(name))
+            if prune:                                            # (without prune=1 the library's default stays)
+                idx.set_bkt_prune(int(name.endswith("+g")))
         else:
             lo, t6, t5, t4 = arm_thresholds(name)
             idx.set_split_bkt(lo, 0, t6, t5, t4)
@@ -110,7 +119,7 @@ def main():
         ms = (time.perf_counter() - t0) * 1e3 / steps
         pr = idx.profile()
         keys = ("bkt_launches", "bkt_codes", "bkt_slots", "bkt_survivors", "nib_codes", "nib_survivors", "nib8_codes", "nib8_survivors",
-                "bktw_launches", "bktw_codes", "bktw_slots", "bktw_survivors")
+                "bktw_launches", "bktw_codes", "bktw_slots", "bktw_survivors", "bktw_prune_skipped", "bktw_prune_run", "bktw_prune_groups")
         print(json.dumps({"section": section, "round": rep, "arm": name, "ms_per_step": round(ms, 4),
                           **{k + "_per_step": int(pr[k] // steps) for k in keys}}), flush=True)
 
@@ -118,14 +127,17 @@ def main():
     arms = ["off", "p777", "p666", "p665", "p655", "p654", "p555", "p554", "p544", "p444", "p755", "p765",
             "b27:p66", "b27:p65", "b27:p55", "b27:p54"]
     if wide:
-        probe = ["w:p44"] if wide <= 128 * MI else ["w:p4"]
-        arms = ["w:p66", "w:p65", "w:p55", "w:p54", "w:p44", "w:p43", "w:p33"] if wide <= 128 * MI else ["w:p6", "w:p5", "w:p4", "w:p3"]
+        probe = ["w:p44", "w:p66"] if wide <= 128 * MI else ["w:p4"]
+        arms = ["w:p66", "w:p65", "w:p64", "w:p55", "w:p54", "w:p44", "w:p43", "w:p33"] if wide <= 128 * MI else ["w:p6", "w:p5", "w:p4", "w:p3"]
+    if wide and prune:
+        probe = [a + g for a in probe for g in ("", "+g")]
+        arms = [a + g for a in arms for g in ("", "+g")]
     for rep in range(reps):
         for name in (probe if rep % 2 == 0 else probe[::-1]):
             measure("probe", rep, name, 0x0d | 16)
     for rep in range(reps):
         for name in (arms if rep % 2 == 0 else arms[::-1]):
-            measure("sweep", rep, name, 0x0d)
+            measure("sweep", rep, name, sweep_variant)
     print(json.dumps({"section": "sizes", "codes": n, "finalize_s": round(finalize_s, 3), **sizes}), flush=True)
     idx.close()
 

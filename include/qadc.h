@@ -563,6 +563,7 @@ typedef struct qadc_profile {
     uint64_t bktw_prune_skipped;    /* wide launches with the group test (qadc_index_set_bkt_prune): wave iterations (64 lane groups of 16 slots) that loaded no plane, */
     uint64_t bktw_prune_run;        /* ... wave iterations that ran (skipped + run = bktw_slots / 1024 of those launches) */
     uint64_t bktw_prune_groups;     /* ... and lane groups whose free rows reached the bound, in skipped and in run iterations */
+    uint64_t bktw_prune_quarters;   /* ... with qadc_index_set_bkt_prune_lanes(16): aligned 16-lane quarters of the iterations that ran which loaded no plane */
 } qadc_profile;
 
 int qadc_profile_read(qadc_index* idx, qadc_profile* out);
@@ -638,6 +639,20 @@ int qadc_index_set_split_bkt_wide(qadc_index* idx, uint64_t wide_block, uint64_t
  * applies to batches submitted afterwards.  QADC_BKT_PRUNE overrides the default at qadc_index_create (with QADC_TEST_HOOKS=1).
  * Default 1: profiles/r13_prune_ab.txt. */
 int qadc_index_set_bkt_prune(qadc_index* idx, int mode);
+
+/* Granularity of the group test's loads ("pruned groups"; only with bkt_prune = 1): lanes 16 = in a wave
+ * iteration that runs, an aligned 16-lane quarter (128 contiguous bytes of each plane) none of whose lane groups passes the test
+ * loads no plane either; its lanes go through the pair loop with index 0, which cannot make a survivor of them.  64 = whole wave
+ * iterations only.  Any other value: QADC_E_ARG.  Exact; no result, survivor count, candidate or other counter changes.  May be set at
+ * any time.  QADC_BKT_PRUNE_LANES overrides the default at qadc_index_create (with QADC_TEST_HOOKS=1).
+ * Default: profiles/r14_bkt_tiles_lanes.txt. */
+int qadc_index_set_bkt_prune_lanes(qadc_index* idx, int lanes);
+
+/* Tile order of the bucket launches, narrow and wide: mode 1 = a workgroup walks the run's tiles strided by the workgroups of the
+ * run, whatever bit 3 (chunks) of the "variant" option says; 0 = they follow variant like every other streaming launch.  The copy
+ * is key-ordered, so a chunk is one stretch of keys.  Any other value: QADC_E_ARG.  No result changes.  May be set at any time.
+ * QADC_BKT_TILES overrides the default at qadc_index_create (with QADC_TEST_HOOKS=1).  Default: profiles/r14_bkt_tiles_lanes.txt. */
+int qadc_index_set_bkt_tiles(qadc_index* idx, int mode);
 
 /* The wide form's choice: out[16 t + 4 (NSP - 3) ..] = the deferred set among sub-quantizers 5-15 for NSP = 3, 4, 5, 6 paid
  * planes as a 16-bit mask (low byte first), the slack c, 0.  A diagnostic. */

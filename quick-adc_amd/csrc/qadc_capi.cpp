@@ -121,7 +121,7 @@ int bind_state_and_result(qadc_index* idx, Slot& s, Staged& g) {
     if (g.any_bkt) HIPCHECK(s.d_bkt_sel.ensure((size_t)kBktSelBytes * nq * ma));
     if (g.any_bktw) HIPCHECK(s.d_bktw_sel.ensure((size_t)kBktwSelBytes * nq * ma));
     s.prune_counted = g.any_bktw && idx->profile && idx->bkt_prune != 0;
-    if (s.prune_counted) HIPCHECK(s.d_prune_cnt.ensure(3));
+    if (s.prune_counted) HIPCHECK(s.d_prune_cnt.ensure(4));
     return QADC_OK;
 }
 
@@ -225,7 +225,9 @@ int launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, h
                           (uint32_t)s.R, str, /*narrow=*/ll.nitems <= 4 ? 1 : 0);   // (8 queries per pass: the 8-seat
                                                                // build, see scan_i8_mq_kernel; <= 4 runs: the build with the 4-seat body)
     else
-        launch_scan_i8(idx->M, ll.shared ? (idx->share_variant & ~32) : (variant & ~(64 | 32)) | (ll.split ? 32 : 0), s.d_items + ll.first,
+        // (bkt_tiles = 1: the bucket launches walk strided tiles whatever variant says; the copy is key-ordered)
+        launch_scan_i8(idx->M, ll.shared ? (idx->share_variant & ~32)
+                                         : (variant & ~(64 | 32) & ~((ll.bkt || ll.bktw) && idx->bkt_tiles ? 8 : 0)) | (ll.split ? 32 : 0), s.d_items + ll.first,
                        ll.nitems, ll.wgs, s.d_qt, s.d_qs, s.d_hdr, s.d_cands.p, s.cap_q, (uint32_t)s.R, str,
                        ll.split6 && !ll.split5 ? s.d_plane_sel.p : nullptr,
                        !idx->profile  ? nullptr
@@ -238,7 +240,7 @@ int launch_level(qadc_index* idx, Slot& s, const LevelLaunch& ll, int variant, h
                        ll.split5 ? s.d_plane_sel5.p : nullptr, ll.nib ? s.d_nib_sel.p : nullptr, ll.nib,
                        ll.bktw ? s.d_bktw_sel.p : ll.bkt ? s.d_bkt_sel.p : nullptr, ll.bktw ? ll.bktw : ll.bkt,
                        ll.bktw ? 5 : 4,                            // (the wide form first, then the bucket form, then the nibble form)
-                       ll.bktw ? idx->bkt_prune : 0, ll.bktw && s.prune_counted ? s.d_prune_cnt.p : nullptr);
+                       ll.bktw ? idx->bkt_prune : 0, ll.bktw && s.prune_counted ? s.d_prune_cnt.p : nullptr, idx->bkt_prune_lanes);
     return QADC_OK;
 }
 
@@ -437,7 +439,7 @@ int plan_and_launch(qadc_index* idx, Slot& s) {
     // event hops (~15 us of a ~130 us single query).
     hipStream_t st = g.alone ? idx->stream : idx->front_stream;
     HIPCHECK(hipMemsetAsync(s.d_state.p, 0, g.state_bytes, st));
-    if (s.prune_counted) HIPCHECK(hipMemsetAsync(s.d_prune_cnt.p, 0, 3 * sizeof(unsigned long long), st));
+    if (s.prune_counted) HIPCHECK(hipMemsetAsync(s.d_prune_cnt.p, 0, 4 * sizeof(unsigned long long), st));
     if (int rc = upload_and_wait(idx, s, g.in_bytes, st, g.alone)) return rc;
     s.prof_used = 0;
     if (int rc = launch_front(idx, s, plan, g, st)) return rc;
@@ -825,11 +827,12 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
             idx->prof.bktw_survivors += surv;
         }
         if (count_bktw && s.prune_counted) {
-            unsigned long long cnt[3] = {0, 0, 0};
+            unsigned long long cnt[4] = {0, 0, 0, 0};
             HIPCHECK(hipMemcpy(cnt, s.d_prune_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost));
             idx->prof.bktw_prune_skipped += cnt[0];
             idx->prof.bktw_prune_run += cnt[1];
             idx->prof.bktw_prune_groups += cnt[2];
+            idx->prof.bktw_prune_quarters += cnt[3];
         }
         if (s.float_path) idx->prof.start_codes += s.start_codes;
     }
@@ -1295,6 +1298,8 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
         if (const char* e = std::getenv("QADC_BKTW3_MIN_RUN")) idx->bktw3_min_run = std::strtoull(e, nullptr, 10);
         if (idx->bkt_wide_block & (idx->bkt_wide_block - 1)) idx->bkt_wide_block = 0;     // (not a power of two: none)
         if (const char* e = std::getenv("QADC_BKT_PRUNE")) idx->bkt_prune = std::atoi(e) != 0 ? 1 : 0;   // the wide form's group test
+        if (const char* e = std::getenv("QADC_BKT_PRUNE_LANES")) idx->bkt_prune_lanes = std::atoi(e) == 16 ? 16 : 64;   // ... by quarters or by waves
+        if (const char* e = std::getenv("QADC_BKT_TILES")) idx->bkt_tiles = std::atoi(e) != 0 ? 1 : 0;   // the bucket launches' tile order
     }
     if (int rc = attach_streams(idx)) {
         delete idx;
@@ -2254,6 +2259,20 @@ int qadc_index_set_bkt_prune(qadc_index* idx, int mode) {
     if (!idx) return fail(QADC_E_ARG, "null index");
     if (mode != 0 && mode != 1) return fail(QADC_E_ARG, "bkt_prune is 0 or 1");
     idx->bkt_prune = mode;
+    return QADC_OK;
+}
+
+int qadc_index_set_bkt_prune_lanes(qadc_index* idx, int lanes) {
+    if (!idx) return fail(QADC_E_ARG, "null index");
+    if (lanes != 64 && lanes != 16) return fail(QADC_E_ARG, "bkt_prune_lanes is 64 or 16");
+    idx->bkt_prune_lanes = lanes;
+    return QADC_OK;
+}
+
+int qadc_index_set_bkt_tiles(qadc_index* idx, int mode) {
+    if (!idx) return fail(QADC_E_ARG, "null index");
+    if (mode != 0 && mode != 1) return fail(QADC_E_ARG, "bkt_tiles is 0 or 1");
+    idx->bkt_tiles = mode;
     return QADC_OK;
 }
 

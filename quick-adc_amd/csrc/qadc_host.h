@@ -181,7 +181,7 @@ struct Slot {
     DevBuf<uint8_t> d_plane_sel;        // 16x4: the 6-plane split form's deferred byte of every table of the batch (written beside d_qt)
     DevBuf<uint8_t> d_bkt_sel;          // ... and the bucket form's kBktSelBytes per table (deferred masks and slacks for NSP = 4..7)
     DevBuf<uint8_t> d_bktw_sel;         // ... and its wide form's kBktwSelBytes per table (NSP = 3..6 among sub-quantizers 5-15)
-    DevBuf<unsigned long long> d_prune_cnt;   // profiling: the wide form's group-test counters of the batch (skipped, run, pruned)
+    DevBuf<unsigned long long> d_prune_cnt;   // profiling: the wide form's group-test counters of the batch (skipped, run, pruned, quarters)
     bool prune_counted = false;         // ... are in use by this batch
     DevBuf<uint8_t> d_nib_sel;          // ... and the nibble form's kNibSelBytes per table (deferred masks and slacks for NS = 8, 9, 10)
     DevBuf<uint8_t> d_plane_sel5;       // ... and the 5-plane form's two bytes per table: j1 | j2 << 4, slack (launch_scan_i8)
@@ -484,6 +484,12 @@ struct qadc_index {
     // rows leave room under the bound load no plane, 0 = the kernels without the test (then set bktw5_min_run = bktw4_min_run = 2^27 as
     // well: without the test 4 paid planes are the fastest arm and 6 the slowest even one)
     int bkt_prune = 1;
+    // ... by 16-lane quarters (qadc_index_set_bkt_prune_lanes; profiles/r14_bkt_tiles_lanes.txt): 16 = in a wave iteration that runs, a
+    // quarter none of whose lane groups keeps loads no plane either; 64 = whole waves only
+    int bkt_prune_lanes = 16;
+    // the bucket launches' tile order (qadc_index_set_bkt_tiles): 1 = narrow and wide bucket launches walk strided tiles whatever variant
+    // bit 3 says (the copy is key-ordered: a chunk is one stretch of keys, pruned or hot as a whole); 0 = they follow variant
+    int bkt_tiles = 1;
     // one workgroup per query (IVF batches, small lists): 0 = never, 1 = auto, 2 = whenever structurally possible
     int wgq = 1;
     uint32_t wgq_capacity = 4096;        // stream entries per query to start with

@@ -248,7 +248,7 @@ void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int
                     uint32_t cap_per_query, uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel = nullptr,
                     unsigned long long* d_surv = nullptr, const uint8_t* d_plane_sel5 = nullptr,
                     const uint8_t* d_nib_sel = nullptr, int nib_ns = 0, const uint8_t* d_bkt_sel = nullptr, int bkt_nsp = 0,
-                    int bkt_free = 4, int bkt_prune = 0, unsigned long long* d_prune_cnt = nullptr);
+                    int bkt_free = 4, int bkt_prune = 0, unsigned long long* d_prune_cnt = nullptr, int bkt_prune_lanes = 64);
 // Split form only (variant bit 5).  d_plane_sel5 != nullptr: the 5-plane form, two bytes per table: j1 | j2 << 4 (the bytes
 // j1 < j2 of 0..6 deferred beside byte 7) and the slack c of its survivor test (min(127, the deferred pair tables' minima
 // summed): a code survives when its 5-byte partial is below bound - c).  Else d_plane_sel != nullptr: the 6-plane form,

@@ -916,12 +916,13 @@ __device__ __forceinline__ uint64_t bktw_streamed(uint32_t mask, uint32_t& used,
 // paid).  FREE = 5: wide octaves (20-bit key, 11 planes of sub-quantizers 5-15, NSP = 3..6 paid; the group's sub-quantizer 4 is
 // one more byte of its id: s0 = P01[id & 255] + P23[id >> 8] + T4[id4], or, NSP odd, row 4 joins the first paid plane's pair table
 // with id4 splatted into the low nibbles of the merged index).  sel = the form's choice bytes of every table.
-template <int FREE, int NSP, bool NT, bool CHUNK, bool PROBE, bool PRUNE>
+template <int FREE, int NSP, bool NT, bool CHUNK, bool PROBE, bool PRUNE, bool QUARTER = false>
 __device__ __forceinline__ void scan_bkt_body(
     const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
     CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
     const uint8_t* __restrict__ bkt_sel, unsigned long long* __restrict__ surv, unsigned long long* __restrict__ prune_cnt) {
     static_assert(FREE == 4 || FREE == 5, "16-bit or 20-bit key");
+    static_assert(PRUNE || !QUARTER, "the quarter skip is a form of the group test");
     static_assert(FREE == 5 || (NSP >= 4 && NSP <= 7), "4, 5, 6 or 7 of the 12 paid nibble planes");
     static_assert(FREE == 4 || (NSP >= 3 && NSP <= 6), "3, 4, 5 or 6 of the 11 paid nibble planes");
     static_assert(kSplitTile == 16u * kWG, "a workgroup iteration is one tile: 16 slots per lane");
@@ -1001,7 +1002,8 @@ __device__ __forceinline__ void scan_bkt_body(
         for (int i = 0; i < NSP; ++i) pmin += row_min((uint32_t)(paid >> (4 * i)) & 15u);
         if constexpr (FUSE) pmin += row_min(4u);
     }
-    [[maybe_unused]] uint32_t nskip = 0, niter = 0, npruned = 0;   // (wave-uniform) PRUNE: wave iterations skipped / all, lane groups pruned
+    // (wave-uniform) PRUNE: wave iterations skipped, lane groups pruned and, QUARTER, quarters of run iterations without a load
+    [[maybe_unused]] uint32_t nskip = 0, npruned = 0, nquart = 0;
 
     // survivors of the previous iteration: byte k of pend[w] = min(127, partial) of the lane's slot 4 w + k, 0xff = none
     uint32_t pend[4] = {~0u, ~0u, ~0u, ~0u};
@@ -1082,22 +1084,34 @@ __device__ __forceinline__ void scan_bkt_body(
         uint32_t id, id4;                                       // (id4: WIDE, the group's sub-quantizer 4)
         [[maybe_unused]] uint32_t s0p = 0;
         bool run = true;                                        // (uniform) PRUNE: some lane of the wave keeps its group
+        [[maybe_unused]] bool mine = true;                      // QUARTER: some lane of this lane's aligned 16-lane quarter does
         if constexpr (PRUNE) {
             id = pid;
             id4 = pid4;
             s0p = free_rows(id, id4);
             const uint64_t keep = __builtin_amdgcn_ballot_w64(s0p + pmin < bsurv);   // lanes whose group may hold a survivor
-            ++niter;
             npruned += 64u - (uint32_t)__builtin_popcountll(keep);
             run = keep != 0;                                    // no lane keeps: an iteration with no survivor, without its loads and lookups
             nskip += run ? 0u : 1u;
+            if constexpr (QUARTER) {
+                // a quarter reads 128 contiguous, 128-byte-aligned bytes of each plane: one none of whose lanes keeps loads nothing
+                mine = ((uint32_t)(keep >> (tid & 48u)) & 0xffffu) != 0;
+                uint32_t idle = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) idle += ((uint32_t)(keep >> (16 * j)) & 0xffffu) == 0 ? 1u : 0u;
+                nquart += run ? idle : 0u;
+            }
         } else {
             load_ids(t, id, id4);
         }
         if (run) {
 #pragma unroll
-            for (int i = 0; i < NSP; ++i)
-                v[i] = NT ? __builtin_nontemporal_load(planes + e0 + poff[i]) : planes[e0 + poff[i]];
+            for (int i = 0; i < NSP; ++i) v[i] = u32x2{0u, 0u};  // (QUARTER: what a lane of a quarter without a load presents)
+            if (!QUARTER || mine) {
+#pragma unroll
+                for (int i = 0; i < NSP; ++i)
+                    v[i] = NT ? __builtin_nontemporal_load(planes + e0 + poff[i]) : planes[e0 + poff[i]];
+            }
         }
         if (__builtin_expect(any_pend, 0)) resolve();           // the previous iteration's survivors, behind this one's loads
         if (!run) {
@@ -1197,18 +1211,20 @@ __device__ __forceinline__ void scan_bkt_body(
         if (tid == 0 && *cnt) atomicAdd(surv, (unsigned long long)*cnt);
     }
     if constexpr (PRUNE) {
-        if (prune_cnt) {                                        // (uniform; profile option only) skipped, run, pruned: the same way
+        if (prune_cnt) {                                        // (uniform; profile option only) skipped, run, pruned, quarters: the same way
             uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + C::HIST_OFF);
+            const uint32_t niter = first < last ? (last - first + step - 1u) / step : 0u;   // the tile loop's trip count
             __syncthreads();
-            if (tid < 3) cnt[tid] = 0;
+            if (tid < 4) cnt[tid] = 0;
             __syncthreads();
             if ((tid & 63u) == 0) {
                 atomicAdd(cnt, nskip);
                 atomicAdd(cnt + 1, niter - nskip);
                 atomicAdd(cnt + 2, npruned);
+                atomicAdd(cnt + 3, nquart);
             }
             __syncthreads();
-            if (tid < 3 && cnt[tid]) atomicAdd(prune_cnt + tid, (unsigned long long)cnt[tid]);
+            if (tid < 4 && cnt[tid]) atomicAdd(prune_cnt + tid, (unsigned long long)cnt[tid]);
         }
     }
 }
@@ -1231,14 +1247,20 @@ __global__ __launch_bounds__(kWG, 8) void scan_i8_bktw_kernel(
 }
 
 // ... with the group test ("pruned groups"): a wave iteration in which no lane group can hold a survivor loads no
-// plane and issues no pair lookup.  prune_cnt (profile option only, else null): wave iterations skipped, wave iterations run, lane
-// groups pruned, one atomicAdd each per workgroup at exit.
-template <int NSP, bool NT, bool CHUNK, bool PROBE>
+// plane and issues no pair lookup.  QUARTER (bkt_prune_lanes = 16): in an iteration that runs, a lane loads its planes only if
+// some lane of its aligned 16-lane quarter keeps; the others present index 0 to the pair loop, which cannot make a survivor of
+// them (every pair entry >= the sum of its rows' minima).  prune_cnt (profile option only, else null): wave iterations skipped,
+// wave iterations run, lane groups pruned, quarters of run iterations without a load: one atomicAdd each per workgroup at exit.
+// The second launch bound stays 8 like every streaming kernel's: it holds the compiler to 78 SGPRs, some 40 of the loop's uniform
+// values then live in VGPR lanes, but with more than 80 SGPRs a SIMD takes fewer than 8 waves and a CU one workgroup of 1024, not
+// two: the build with bound 2 (106 SGPRs, 10-12 spilled) ran the headline at 15.21 ms per step against 11.78
+// (profiles/r14_bkt_tiles_lanes.txt).
+template <int NSP, bool NT, bool CHUNK, bool PROBE, bool QUARTER>
 __global__ __launch_bounds__(kWG, 8) void scan_i8_bktw_prune_kernel(
     const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
     CandHeader* __restrict__ hdr, Cand* __restrict__ out, uint32_t cand_cap, uint32_t R,
     const uint8_t* __restrict__ bktw_sel, unsigned long long* __restrict__ surv, unsigned long long* __restrict__ prune_cnt) {
-    scan_bkt_body<5, NSP, NT, CHUNK, PROBE, true>(items, qtables, qstates, hdr, out, cand_cap, R, bktw_sel, surv, prune_cnt);
+    scan_bkt_body<5, NSP, NT, CHUNK, PROBE, true, QUARTER>(items, qtables, qstates, hdr, out, cand_cap, R, bktw_sel, surv, prune_cnt);
 }
 
 
@@ -2247,11 +2269,11 @@ static void launch_bktw_variant(dim3 grid, hipStream_t stream, const ScanItem* d
                        d_bktw_sel, d_surv);
 }
 
-template <int NSP, bool NT, bool CHUNK, bool PROBE>
+template <int NSP, bool NT, bool CHUNK, bool PROBE, bool QUARTER>
 static void launch_bktw_prune_variant(dim3 grid, hipStream_t stream, const ScanItem* d_items, const int8_t* d_qtables,
                                       QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap, uint32_t R,
                                       const uint8_t* d_bktw_sel, unsigned long long* d_surv, unsigned long long* d_prune_cnt) {
-    auto k = &scan_i8_bktw_prune_kernel<NSP, NT, CHUNK, PROBE>;
+    auto k = &scan_i8_bktw_prune_kernel<NSP, NT, CHUNK, PROBE, QUARTER>;
     static std::atomic<uint64_t> done{0};
     ensure_dynamic_lds(reinterpret_cast<const void*>(k), ScanCfg<16>::LDS_BYTES, done);
     hipLaunchKernelGGL(k, grid, dim3(kWG), ScanCfg<16>::LDS_BYTES, stream, d_items, d_qtables, d_qs, d_hdr, d_cands, cand_cap, R,
@@ -2265,13 +2287,14 @@ static void launch_bktw_prune_variant(dim3 grid, hipStream_t stream, const ScanI
 //     nib_ns = 8, 9 or 10 with d_nib_sel (ScanItem::split of every run points into the nibble-plane copy): the nibble form, before all of these
 //     bkt_nsp = 4..7 with d_bkt_sel (every run of the launch is a bucket-form run, LevelLaunch::bkt): the bucket form, before the nibble form
 //     bkt_free = 5, bkt_nsp = 3..6, d_bkt_sel = the wide form's choice bytes (LevelLaunch::bktw): the wide form, before all of these
-//     ... bkt_prune != 0: its build with the group test (scan_i8_bktw_prune_kernel; d_prune_cnt: its three counters or nullptr)
+//     ... bkt_prune != 0: its build with the group test (scan_i8_bktw_prune_kernel; d_prune_cnt: its four counters or nullptr;
+//     bkt_prune_lanes = 16: kept wave iterations load by 16-lane quarters, any other value: by whole waves)
 // [6] sibling-major 1-D launch (every run of the launch covers the same codes; see the kernel's decode).  Other bits: ignored.
 void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int wgs_per_item,
                     const int8_t* d_qtables, QueryState* d_qs, CandHeader* d_hdr, Cand* d_cands, uint32_t cand_cap,
                     uint32_t R, hipStream_t stream, const uint8_t* d_plane_sel, unsigned long long* d_surv,
                     const uint8_t* d_plane_sel5, const uint8_t* d_nib_sel, int nib_ns, const uint8_t* d_bkt_sel, int bkt_nsp, int bkt_free,
-                    int bkt_prune, unsigned long long* d_prune_cnt) {
+                    int bkt_prune, unsigned long long* d_prune_cnt, int bkt_prune_lanes) {
     if (bkt_free == 5) {
         // a wide launch is never anything else: launch_level (qadc_capi.cpp) refuses one whose preconditions do not hold with an error
         // status before it gets here, so a violation is a programming error and must not pass as a level that was silently not scanned
@@ -2288,13 +2311,15 @@ void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int
         case 2: launch_bktw_variant<NSP, false, true, PR>(QADC_BKTW_ARGS); break;  \
         default: launch_bktw_variant<NSP, true, true, PR>(QADC_BKTW_ARGS); break;  \
     }
-#define QADC_BKTWP(NSP, PR)                                                                           \
-    switch ((variant >> 2) & 3) {                                                                    \
-        case 0: launch_bktw_prune_variant<NSP, false, false, PR>(QADC_BKTW_ARGS, d_prune_cnt); break; \
-        case 1: launch_bktw_prune_variant<NSP, true, false, PR>(QADC_BKTW_ARGS, d_prune_cnt); break;  \
-        case 2: launch_bktw_prune_variant<NSP, false, true, PR>(QADC_BKTW_ARGS, d_prune_cnt); break;  \
-        default: launch_bktw_prune_variant<NSP, true, true, PR>(QADC_BKTW_ARGS, d_prune_cnt); break;  \
+#define QADC_BKTWPQ(NSP, PR, QU)                                                                           \
+    switch ((variant >> 2) & 3) {                                                                         \
+        case 0: launch_bktw_prune_variant<NSP, false, false, PR, QU>(QADC_BKTW_ARGS, d_prune_cnt); break; \
+        case 1: launch_bktw_prune_variant<NSP, true, false, PR, QU>(QADC_BKTW_ARGS, d_prune_cnt); break;  \
+        case 2: launch_bktw_prune_variant<NSP, false, true, PR, QU>(QADC_BKTW_ARGS, d_prune_cnt); break;  \
+        default: launch_bktw_prune_variant<NSP, true, true, PR, QU>(QADC_BKTW_ARGS, d_prune_cnt); break;  \
     }
+#define QADC_BKTWP(NSP, PR) \
+    if (bkt_prune_lanes == 16) { QADC_BKTWPQ(NSP, PR, true) } else { QADC_BKTWPQ(NSP, PR, false) }
         if (bkt_prune) {
             if (bkt_nsp == 3) {
                 if (variant & 16) { QADC_BKTWP(3, true) } else { QADC_BKTWP(3, false) }
@@ -2317,6 +2342,7 @@ void launch_scan_i8(int M, int variant, const ScanItem* d_items, int nitems, int
 #undef QADC_BKTW_ARGS
 #undef QADC_BKTW
 #undef QADC_BKTWP
+#undef QADC_BKTWPQ
         return;
     }
     if (M == 16 && (variant & 32) && !(variant & 64) && d_bkt_sel && bkt_nsp >= 4 && bkt_nsp <= 7) {

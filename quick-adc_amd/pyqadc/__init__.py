@@ -32,7 +32,7 @@ SYMBOLS = [
     "qadc_scan_i8_candidates", "qadc_scan_start", "qadc_query_scan_submit", "qadc_prescan_submit",
     "qadc_prescan_collect", "qadc_query_scan_submit_prescanned",
     "qadc_query_scan_collect", "qadc_index_set_pq", "qadc_index_set_rotation", "qadc_index_set_coarse", "qadc_search", "qadc_search_submit",
-    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6", "qadc_index_set_split5", "qadc_index_set_split_nib", "qadc_nib_choice", "qadc_index_set_split_bkt", "qadc_bkt_choice", "qadc_index_bkt_info", "qadc_index_bkt_read", "qadc_index_set_split_bkt_wide", "qadc_index_set_bkt_prune", "qadc_bktw_choice", "qadc_index_bktw_info", "qadc_index_bktw_read",
+    "qadc_search_collect", "qadc_device_prepare", "qadc_stream_probe", "qadc_stream_layout", "qadc_pq_encode", "qadc_pq_encode_host", "qadc_ivf_encode_host", "qadc_pq_encode_mode", "qadc_pq_encode_host_mode", "qadc_ivf_encode_host_mode", "qadc_kmeans_iterations_host", "qadc_coarse_assign_host", "qadc_kmeans_iterations_host_mode", "qadc_replay_i8", "qadc_sort_keys_i8", "qadc_merge_streams_i8", "qadc_candidates_i8", "qadc_float_top1", "qadc_profile_read", "qadc_profile_reset", "qadc_index_set_split", "qadc_index_set_split6", "qadc_index_set_split5", "qadc_index_set_split_nib", "qadc_nib_choice", "qadc_index_set_split_bkt", "qadc_bkt_choice", "qadc_index_bkt_info", "qadc_index_bkt_read", "qadc_index_set_split_bkt_wide", "qadc_index_set_bkt_prune", "qadc_index_set_bkt_prune_lanes", "qadc_index_set_bkt_tiles", "qadc_bktw_choice", "qadc_index_bktw_info", "qadc_index_bktw_read",
     "qadc_dist_unique_id", "qadc_dist_init", "qadc_dist_collect", "qadc_dist_shutdown", "qadc_dist_merge_blocks", "qadc_dist_merge_blocks_host",
     "qadc_dist_init_transport", "qadc_dist_init_loopback", "qadc_shm_transport_open", "qadc_shm_transport_allgather", "qadc_shm_transport_allgather_host",
     "qadc_shm_transport_close", "qadc_shm_transport_error", "qadc_slot_assign", "qadc_slot_qtables", "qadc_place_partitions",
@@ -93,7 +93,8 @@ class Profile(C.Structure):
                 ("bktw_launches", C.c_uint64), ("bktw_codes", C.c_uint64), ("bktw_slots", C.c_uint64),
                 ("bktw_survivors", C.c_uint64), ("bktw3_launches", C.c_uint64), ("bktw4_launches", C.c_uint64),
                 ("bktw5_launches", C.c_uint64), ("bktw6_launches", C.c_uint64),
-                ("bktw_prune_skipped", C.c_uint64), ("bktw_prune_run", C.c_uint64), ("bktw_prune_groups", C.c_uint64)]
+                ("bktw_prune_skipped", C.c_uint64), ("bktw_prune_run", C.c_uint64), ("bktw_prune_groups", C.c_uint64),
+                ("bktw_prune_quarters", C.c_uint64)]
 
 
 QADC_E_ARG, QADC_E_HIP, QADC_E_CAPACITY, QADC_E_STATE = -1, -2, -3, -4   # include/qadc.h
@@ -150,6 +151,8 @@ def lib():
         L.qadc_index_bkt_read.argtypes = [C.c_void_p, C.c_int, u64p, u8p, u8p]
         L.qadc_index_set_split_bkt_wide.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double]
         L.qadc_index_set_bkt_prune.argtypes = [C.c_void_p, C.c_int]
+        L.qadc_index_set_bkt_prune_lanes.argtypes = [C.c_void_p, C.c_int]
+        L.qadc_index_set_bkt_tiles.argtypes = [C.c_void_p, C.c_int]
         L.qadc_bktw_choice.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.qadc_index_bktw_info.argtypes = [C.c_void_p, C.c_int, u64p, u64p, u64p]
         L.qadc_index_bktw_read.argtypes = [C.c_void_p, C.c_int, u64p, u8p, u8p]
@@ -855,6 +858,16 @@ class Index:
         """Group test of the wide form: 1 = wave iterations whose lane groups' free rows all reach the bound load no plane and look
         nothing up, 0 = the form without the test; results do not change."""
         _check(lib().qadc_index_set_bkt_prune(self._h, int(mode)))
+
+    def set_bkt_prune_lanes(self, lanes):
+        """Granularity of the group test's loads (with set_bkt_prune(1)): 16 = a 16-lane quarter of a running wave iteration none of
+        whose lane groups keeps loads no plane either, 64 = whole wave iterations only; results do not change."""
+        _check(lib().qadc_index_set_bkt_prune_lanes(self._h, int(lanes)))
+
+    def set_bkt_tiles(self, mode):
+        """Tile order of the bucket launches: 1 = strided tiles whatever bit 3 of "variant" says, 0 = they follow variant; results
+        do not change."""
+        _check(lib().qadc_index_set_bkt_tiles(self._h, int(mode)))
 
     def bktw_copy(self, part):
         """Diagnostic: partition part's wide octaves, or None.  -> dict(block = W, off uint64 [octaves + 1], tiles uint8

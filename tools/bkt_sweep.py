@@ -17,7 +17,13 @@ form's 5), the level from 2^25 the narrow form's 6; the PROBE section times "w:p
 With a fourth argument prune=1 (profiles/r13_prune_ab.txt) every wide arm runs twice, interleaved: without the wide form's group
 test (Index.set_bkt_prune(0)) and, named "w:pYZ+g", with it; without the argument the arms run under the library's default, which
 is the test on.  A fifth argument variant=V (default 0x0d) sets the loop form of the sweep section: 0x05 = strided tiles in place of chunks; the PROBE section times both builds of "w:p44", and the lines carry the
-group test's counters (wave iterations skipped and run, lane groups pruned)."""
+group test's counters (wave iterations skipped and run, lane groups pruned).
+
+With tiles_lanes=1 anywhere after the fourth argument (profiles/r14_bkt_tiles_lanes.txt) every "+g" arm runs four times, interleaved:
+"/c64" and "/c16" = the bucket launches follow the variant (Index.set_bkt_tiles(0); chunks under 0x0d) with the group test by whole waves
+and by 16-lane quarters (Index.set_bkt_prune_lanes), "/s64" and "/s16" = strided tiles for the bucket launches alone
+(set_bkt_tiles(1)); the lines carry the fourth counter (idle quarters of the wave iterations that ran).  arms=A,B,.. keeps only the
+named arms (before the suffixes), probe=0 leaves the PROBE section out."""
 import json
 import os
 import sys
@@ -50,7 +56,7 @@ def arm_thresholds(name):
 
 def wide_thresholds(name):
     """"w:pYZ" / "w:pZ" -> (min_run5, min_run4, min_run3): thresholds that the level's runs and the longer ones reach."""
-    planes = [int(c) for c in name.split("+")[0].split("p")[1]]
+    planes = [int(c) for c in name.split("/")[0].split("+")[0].split("p")[1]]
     planes = [planes[0]] * (2 - len(planes)) + planes            # per level from 2^27, 2^29 (non-increasing)
     reach = (128 * MI, 400 * MI)
     t = {}
@@ -88,6 +94,8 @@ def main():
     wide = int(float(sys.argv[3].split("=")[1])) if len(sys.argv) > 3 and sys.argv[3].startswith("wide=") else 0
     prune = len(sys.argv) > 4 and sys.argv[4] == "prune=1"
     sweep_variant = int(sys.argv[5].split("=")[1], 0) if len(sys.argv) > 5 and sys.argv[5].startswith("variant=") else 0x0d
+    extra = dict(a.split("=", 1) for a in sys.argv[5:] if "=" in a)
+    tiles_lanes = extra.get("tiles_lanes") == "1"
     idx = pyqadc.Index(M, 0)
     if wide:
         idx.set_split_bkt_wide(wide, min(max(wide, 128 * MI), 400 * MI), 0, 0, 0)
@@ -108,7 +116,10 @@ def main():
         if wide:
             idx.set_split_bkt_wide(wide, min(max(wide, 128 * MI), 400 * MI), *wide_thresholds(name))
             if prune:                                            # (without prune=1 the library's default stays)
-                idx.set_bkt_prune(int(name.endswith("+g")))
+                idx.set_bkt_prune(int("+g" in name))
+            if "/" in name:                                      # tile order and granularity of the group test's loads
+                idx.set_bkt_tiles(int(name.split("/")[1][0] == "s"))
+                idx.set_bkt_prune_lanes(int(name.split("/")[1][1:]))
         else:
             lo, t6, t5, t4 = arm_thresholds(name)
             idx.set_split_bkt(lo, 0, t6, t5, t4)
@@ -119,7 +130,7 @@ def main():
         ms = (time.perf_counter() - t0) * 1e3 / steps
         pr = idx.profile()
         keys = ("bkt_launches", "bkt_codes", "bkt_slots", "bkt_survivors", "nib_codes", "nib_survivors", "nib8_codes", "nib8_survivors",
-                "bktw_launches", "bktw_codes", "bktw_slots", "bktw_survivors", "bktw_prune_skipped", "bktw_prune_run", "bktw_prune_groups")
+                "bktw_launches", "bktw_codes", "bktw_slots", "bktw_survivors", "bktw_prune_skipped", "bktw_prune_run", "bktw_prune_groups", "bktw_prune_quarters")
         print(json.dumps({"section": section, "round": rep, "arm": name, "ms_per_step": round(ms, 4),
                           **{k + "_per_step": int(pr[k] // steps) for k in keys}}), flush=True)
 
@@ -132,6 +143,12 @@ def main():
     if wide and prune:
         probe = [a + g for a in probe for g in ("", "+g")]
         arms = [a + g for a in arms for g in ("", "+g")]
+    if "arms" in extra:
+        arms = [a for a in arms if a.split("+")[0] in extra["arms"].split(",")]
+    if tiles_lanes:
+        arms = [a + t for a in arms if a.endswith("+g") for t in ("/c64", "/s64", "/c16", "/s16")]   # (needs prune=1)
+    if extra.get("probe") == "0":
+        probe = []
     for rep in range(reps):
         for name in (probe if rep % 2 == 0 else probe[::-1]):
             measure("probe", rep, name, 0x0d | 16)

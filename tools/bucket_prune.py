@@ -12,7 +12,13 @@ each, and counts the windows of 64 groups that touch no kept key.
 Printed per level from 2^27 on, octave (codes per key) and NSP, as means over the headline's queries: groups pruned, waves
 skipped, bytes per (code, query) = (NSP / 2) x (1 - waves skipped) + 3 / 16 + 128 x survivor rate.  The narrow form (16-bit key,
 4 free rows) gets the group figure only.  Compare with the library's bktw_prune_groups, bktw_prune_skipped and bktw_prune_run
-(qadc_profile).  One JSON line at the end."""
+(qadc_profile).  One JSON line at the end.
+
+With bkt_prune_lanes = 16 a wave iteration that runs loads by aligned 16-lane quarters (128 contiguous bytes of a plane each): the
+same count over windows of 16 groups gives the fraction of the plane bytes that is not read ("quarters skipped": the quarters of
+skipped wave iterations and the idle quarters of the others), and the byte model becomes (NSP / 2) x (1 - plane bytes skipped) +
+3 / 16 + 128 x survivor rate ("bytes16").  The library's bktw_prune_quarters counts the idle quarters of the wave iterations that
+ran only: quarter_counter_fraction x bktw_slots / 256."""
 import json
 import os
 import sys
@@ -25,6 +31,7 @@ import split_survivors as ss  # noqa: E402
 
 M = bs.M
 WAVE_GROUPS = 64
+QUARTER_GROUPS = 16
 
 
 def key_sums(qt, rows):
@@ -82,6 +89,36 @@ def wave_fraction(keep, codes_per_key):
     return float(np.count_nonzero(cum[k1] == cum[k0])) / nwaves
 
 
+def window_fraction(keep, codes_per_key, groups):
+    """wave_fraction's count over windows of `groups` consecutive lane groups (64: a wave iteration, 16: one of its quarters; a
+    divisor of 64, so that the windows tile the wave iterations)."""
+    g = float(codes_per_key) / 16.0
+    nwin = int(keep.size * g // WAVE_GROUPS) * (WAVE_GROUPS // groups)
+    if nwin == 0:
+        return 0.0
+    w = np.arange(nwin, dtype=np.float64)
+    k0 = np.floor(w * groups / g).astype(np.int64)
+    k1 = np.minimum(np.ceil((w + 1) * groups / g).astype(np.int64), keep.size)
+    cum = np.concatenate([[0], np.cumsum(keep.astype(np.int64))])
+    return float(np.count_nonzero(cum[k1] == cum[k0])) / nwin
+
+
+def quarter_fraction(keep, codes_per_key):
+    """Fraction of the 16-lane quarters that load no plane with bkt_prune_lanes = 16 = fraction of the plane bytes skipped: the
+    quarters of skipped wave iterations and the idle quarters of those that run.  Between wave_fraction and group_fraction."""
+    return window_fraction(keep, codes_per_key, QUARTER_GROUPS)
+
+
+def quarter_counter_fraction(keep, codes_per_key):
+    """What bktw_prune_quarters counts, as a fraction of all quarters: idle quarters of the wave iterations that run."""
+    return quarter_fraction(keep, codes_per_key) - wave_fraction(keep, codes_per_key)
+
+
+def plane_bytes(nsp, skipped, rate):
+    """Bytes per (code, query): the paid planes that are read, the ids (3 / 16) and 128 bytes of side array per survivor."""
+    return nsp / 2 * (1 - skipped) + 0.1875 + 128 * rate
+
+
 def octaves(n, start):
     """Codes per 20-bit key of the octaves a level from `start` covers in a list of n codes (wide blocks from 2^27)."""
     stop = min(n, 4 * start)
@@ -99,22 +136,26 @@ def main():
     seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1234
     qts = bs.headline_qtables(n, nq, seed)
     out = {"codes": n, "queries": nq, "seed": seed, "wide": [], "narrow": []}
-    print("%-6s %-9s %-4s %-14s %-14s %-22s %s" % ("level", "codes/key", "NSP", "groups pruned", "waves skipped", "waves: min..max", "bytes"))
+    print("%-6s %-9s %-4s %-14s %-14s %-22s %-8s %-16s %s" % ("level", "codes/key", "NSP", "groups pruned", "waves skipped", "waves: min..max", "bytes",
+                                                        "quarters skipped", "bytes16"))
     for start in (s for s in bs.WIDE_STARTS if s < n):
         for cpk in octaves(n, start):
             for nsp in bs.NSPS_WIDE:
-                gf, wf, rate = [], [], []
+                gf, wf, rate, qf = [], [], [], []
                 for qt in qts:
                     bound = ss.bound_at(qt, start)
                     keep = kept_keys(wide_terms(qt, nsp, bound))
                     gf.append(group_fraction(keep))
                     wf.append(wave_fraction(keep, cpk))
+                    qf.append(quarter_fraction(keep, cpk))
                     rate.append(bs.survivor_rate_bktw(qt, nsp, bound))
-                b = nsp / 2 * (1 - np.mean(wf)) + 0.1875 + 128 * np.mean(rate)
-                print("2^%-4d %-9.0f %-4d %-14.3f %-14.3f %-22s %.2f B" %
-                      (start.bit_length() - 1, cpk, nsp, np.mean(gf), np.mean(wf), "%.2f..%.2f" % (min(wf), max(wf)), b))
+                b = plane_bytes(nsp, np.mean(wf), np.mean(rate))
+                b16 = plane_bytes(nsp, np.mean(qf), np.mean(rate))
+                print("2^%-4d %-9.0f %-4d %-14.3f %-14.3f %-22s %.2f B   %-16.3f %.2f B" %
+                      (start.bit_length() - 1, cpk, nsp, np.mean(gf), np.mean(wf), "%.2f..%.2f" % (min(wf), max(wf)), b, np.mean(qf), b16))
                 out["wide"].append({"start": start, "codes_per_key": cpk, "nsp": nsp, "groups": float(np.mean(gf)),
-                                    "waves": float(np.mean(wf)), "waves_min": min(wf), "waves_max": max(wf), "bytes": float(b)})
+                                    "waves": float(np.mean(wf)), "waves_min": min(wf), "waves_max": max(wf), "bytes": float(b),
+                                    "quarters": float(np.mean(qf)), "bytes16": float(b16)})
     for nsp in bs.NSPS:
         gf = [group_fraction(kept_keys(narrow_terms(qt, nsp, ss.bound_at(qt, 1 << 25)))) for qt in qts]
         print("2^25   narrow    %-4d %-14.3f" % (nsp, np.mean(gf)))

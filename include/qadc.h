@@ -357,6 +357,62 @@ int qadc_pq_train16_device(const float* d_vectors, uint64_t n, int dim, int sq_c
 int qadc_pq_update16_host(const float* vectors, uint64_t n, int dim, int sq_count, const uint16_t* codes, float* codebooks_out,
                           uint32_t* counts_out, int div_mode, int device_id);
 
+/* ---- Learning the OPQ rotation: non-parametric OPQ, Procrustes rounds around qadc_pq_train_*. ----
+ *
+ * X0 = the learning set as the quantizer sees it BEFORE rotation: with K_coarse > 0 the residual to the nearest of
+ * coarse [K_coarse][dim] (what qadc_pq_train_* computes in front of a NULL rotation), else the vectors themselves.
+ *
+ * qadc_opq_cross_host: the cross matrix M = X0^T Y between X0 and its reconstruction in the rotated space,
+ *   Y[i][b] = codebooks[m][code(i, m)][b - m dsub], m = b / dsub, code(i, m) read from `codes` in the encoder's layout (sq_bits 4:
+ *   packed nibbles [n][sq_count / 2], the even sub-quantizer in the low nibble; 8: bytes [n][sq_count]).  Every float is pinned:
+ *   for block j = vectors [QADC_OPQ_BLOCK j, min(n, QADC_OPQ_BLOCK (j + 1))), partial_j[a][b] is the float chain
+ *   acc = fmaf(X0[i][a], Y[i][b], acc) over ascending i from 0.0f; M_out[a][b] (double [dim][dim], row a = component of X0, column
+ *   b = component of Y) = the sum of (double)partial_j[a][b] over ascending j from 0.0.  Host twin: host/db_build.hpp opq_cross.
+ *   Limits: the learning set, its residual (with a coarse quantizer), the codes, the codebooks and
+ *   ceil(n / QADC_OPQ_BLOCK) * dim^2 * 4 bytes of partials are resident for the call; one device; synchronous.
+ *   Refused with QADC_E_ARG before the first HIP call: everything qadc_pq_train_host refuses (sq_bits 16 included: a follow-up
+ *   on the sorted update), dim > 1024, NULL codes or M_out.  qadc_opq_cross_device: the vectors already in device memory (read
+ *   only, by kernels); every other pointer is host memory. */
+#define QADC_OPQ_BLOCK 2048   /* vectors per float partial sum of the cross matrix */
+int qadc_opq_cross_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                        const void* codes, const float* codebooks, double* M_out, int sum_mode, int device_id);
+int qadc_opq_cross_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                          const void* codes, const float* codebooks, double* M_out, int sum_mode, int device_id);
+/* Host only (no GPU involved; host/procrustes.hpp): the orthogonal rotation_out [dim][dim] that maximises tr(R M) for M [dim][dim]
+ *   doubles — with M = U S V^T, R = V U^T, rounded to float.  In the project's convention rotated[r] = sum_c x[c] R[r][c], so for
+ *   M = X0^T Y it is the rotation with X0 R^T closest to Y.  A deterministic one-sided (Hestenes) Jacobi SVD in double, cyclic
+ *   order; sweeps_out (nullable): the sweeps it took.  A rank-deficient M (the zero matrix included) still gives an orthogonal R:
+ *   the missing left vectors are completed by Gram-Schmidt against the unit vectors in index order; a positive diagonal M gives
+ *   the identity exactly.  QADC_E_ARG: a non-finite entry of M, NULL pointers, dim outside [1, 1024] (O(dim^3) per sweep).
+ *   QADC_E_STATE: the sweep cap (64) was reached — no matrix is returned, never a non-orthogonal one.  rotation_out is
+ *   untouched on every error. */
+int qadc_procrustes_host(const double* M, int dim, float* rotation_out, int* sweeps_out);
+/* qadc_opq_train_host: rotation [dim][dim] in and out (the identity for "none": it is applied like any rotation), codebooks
+ *   [sq_count][2^sq_bits][dsub] in and out, seeded by the caller as for qadc_pq_train_host; outer >= 0, inner >= 1.
+ *     for t in 0 .. outer - 1:
+ *         (codebooks, codes) = qadc_pq_train_host(..., rotation, codebooks, iters = inner)
+ *         M = qadc_opq_cross_host(..., codes, codebooks)        -- the codes of the last round, the codebooks after its update
+ *         if M has a non-finite entry: leave the loop            -- rotation untouched, rounds_done = t
+ *         rotation = qadc_procrustes_host(M)
+ *     (codebooks, codes) = qadc_pq_train_host(..., rotation, codebooks, iters = inner)    -- the closing rounds, always run
+ *   and every returned float and code equals, bit for bit, that loop written with the three public calls (host twin:
+ *   host/db_build.hpp opq_train_iterations).  outer == 0 is qadc_pq_train_host with iters = inner.  The learning set goes up
+ *   once; X0, its rotated copy (refreshed per outer round by the training call's own kernel), the codes and the codebooks stay
+ *   in device memory; the coarse assignment is computed once; per outer round only M comes down and the rotation goes up.
+ *   codes_out, empty_out: as for qadc_pq_train_host, after the closing rounds.  rounds_done_out (nullable): rotation updates
+ *   completed.  div_mode, sum_mode: as for qadc_pq_train_host.
+ *   Refused with QADC_E_ARG before the first HIP call: everything qadc_pq_train_host refuses; sq_bits 16; dim > 1024; NULL
+ *   rotation; outer < 0; inner < 1.  QADC_E_STATE: a Procrustes solve hit its sweep cap (rotation and codebooks are then not
+ *   a fitted pair).  Limits: 4 and 8 bits; dim <= 1024; the learning set, its residual, its rotated copy, the codes and the
+ *   partials are resident for the call; one device; synchronous.  Not done: the parametric initialisation, k-means++ seeding,
+ *   empty-cluster repair, 16-bit codebooks.  qadc_opq_train_device: the vectors already in device memory (read only, by kernels). */
+int qadc_opq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                        float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
+                        int* rounds_done_out, int div_mode, int sum_mode, int device_id);
+int qadc_opq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                          float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
+                          int* rounds_done_out, int div_mode, int sum_mode, int device_id);
+
 /* Host-only helper (no GPU involved): push (keys[i], vals[i]), i = 0..n-1, in order into an empty
  * heap of capacity R with kv_binheap<unsigned,int8_t>::push semantics (binheap.hpp:75-116), after
  * an optional (0,127) sentinel (db_query_4.cpp:276), and return the heap arrays.  This is the

@@ -1,7 +1,7 @@
 // Database build entry points: PQ encode (quantizers.hpp:222-245), the compute of
 // index_db::add_vectors (databases.hpp:270-298) and the k-means iterations (databases.cpp:50-90).  Stateless: host buffers
 // (or device pointers) in and out, any device.
-#include "qadc_host.h"
+#include "qadc_build_shared.h"
 #include "qadc_adc_kernels.h"   // launch_adc_encode: the assignment step of qadc_pq_train at 8 bits
 #include "qadc_pq_train.h"
 #include "qadc_pq_train16.h"
@@ -10,6 +10,7 @@
 
 using namespace qadc;
 using namespace qadc::host;
+using namespace qadc::build;
 
 extern "C" {
 
@@ -57,19 +58,8 @@ int qadc_pq_encode_host_mode(int M, int dim, const float* codebooks, const float
 
 /* ---- database build (N4): index_db::add_vectors' compute and the k-means iterations, host buffers in and out ---- */
 extern "C++" {
-namespace {
-struct ScratchFree {                                           // hipFree on every exit path
-    std::vector<void*> p;
-    ~ScratchFree() { for (void* x : p) if (x) (void)hipFree(x); }
-    template <typename T> hipError_t alloc(T** out, size_t bytes) {
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) { p.push_back(q); *out = static_cast<T*>(q); }
-        return e;
-    }
-};
-constexpr uint64_t kBuildChunk = 32768;                        // vectors per pass (the distance scratch is chunk x K floats)
-
+namespace qadc {
+namespace build {                                              // (shared with csrc/qadc_opq.cpp: qadc_build_shared.h)
 // nearest centroid of every vector, chunk by chunk: the coarse kernels of qadc_search with ma = 1 (find_k_neighbors with k = 1 on the
 // expansion distances).  d_dist: chunk x K distances + chunk query norms + K centroid norms (the centroids may have moved: each call).
 int assign_nearest(const float* d_vectors, uint64_t n, int dim, int K, const float* d_coarse, float* d_dist, int32_t* d_assign, int sum_mode) {
@@ -84,7 +74,8 @@ int assign_nearest(const float* d_vectors, uint64_t n, int dim, int K, const flo
     HIPCHECK(hipGetLastError());
     return QADC_OK;
 }
-}  // namespace
+}  // namespace build
+}  // namespace qadc
 }  // extern "C++"
 
 int qadc_ivf_encode_host(int M, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
@@ -198,7 +189,8 @@ int qadc_kmeans_iterations_host_mode(const float* vectors, uint64_t n, int dim, 
    of that shape uses (launch_pq_encode at 4 bits, launch_adc_encode at 8: find_k_neighbors with k = 1 per sub-quantizer, norms of the
    moved centroids recomputed) and one launch_pq_train_update over all sq_count * 2^bits centroids. ---- */
 extern "C++" {
-namespace {
+namespace qadc {
+namespace build {                                              // (shared with csrc/qadc_opq.cpp: qadc_build_shared.h)
 // the argument checks of both entry points: before the first HIP call
 int pq_train_check(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                    const float* codebooks, int iters, int div_mode, int sum_mode) {
@@ -232,6 +224,26 @@ uint64_t nan_rows(const float* cb, size_t rows, int ds) {
     return bad;
 }
 
+// the rounds themselves, on the learning set as the quantizer sees it: qadc_pq_train_* and the outer rounds of qadc_opq_train_* run these
+int pq_train_rounds(const float* d_enc, uint64_t n, int dim, int sq_count, int sq_bits, float* d_cb, float* d_cbnorm, uint8_t* d_codes,
+                    int iters, int div_mode, int sum_mode) {
+    const int ds = dim / sq_count;
+    const size_t rows = (size_t)sq_count << sq_bits;
+    for (int it = 0; it < iters; ++it) {
+        if (sq_bits == 4) {
+            launch_pq_encode(d_enc, n, sq_count, dim, d_cb, 1, sum_mode, d_codes, nullptr);
+        } else {
+            launch_row_sqnorm(d_cb, (int)rows, ds, sum_mode, d_cbnorm, nullptr);
+            HIPCHECK(adc::launch_adc_encode(d_enc, n, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_codes, nullptr));
+        }
+        HIPCHECK(launch_pq_train_update(d_enc, n, dim, sq_count, sq_bits, d_codes, d_cb, div_mode, nullptr));
+    }
+    return QADC_OK;
+}
+}  // namespace build
+}  // namespace qadc
+
+namespace {
 // What the quantizer sees of the learning set, in device memory: with K_coarse > 0 the residual to the nearest coarse centroid, with a
 // rotation those rotated (as qadc_ivf_encode_host prepares its input).  *d_enc = d_vectors itself where neither is given.
 int pq_train_front_device(const float* d_vectors, uint64_t n, int dim, int K_coarse, const float* coarse, const float* rotation,
@@ -272,15 +284,7 @@ int pq_train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int 
     HIPCHECK(mem.alloc(&d_codes, n * code_bytes));
     const float* d_enc = nullptr;
     if (int rc = pq_train_front_device(d_vectors, n, dim, K_coarse, coarse, rotation, sum_mode, mem, &d_enc)) return rc;
-    for (int it = 0; it < iters; ++it) {
-        if (sq_bits == 4) {
-            launch_pq_encode(d_enc, n, sq_count, dim, d_cb, 1, sum_mode, d_codes, nullptr);
-        } else {
-            launch_row_sqnorm(d_cb, (int)rows, ds, sum_mode, d_cbnorm, nullptr);
-            HIPCHECK(adc::launch_adc_encode(d_enc, n, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_codes, nullptr));
-        }
-        HIPCHECK(launch_pq_train_update(d_enc, n, dim, sq_count, sq_bits, d_codes, d_cb, div_mode, nullptr));
-    }
+    if (int rc = pq_train_rounds(d_enc, n, dim, sq_count, sq_bits, d_cb, d_cbnorm, d_codes, iters, div_mode, sum_mode)) return rc;
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(codebooks, d_cb, rows * ds * sizeof(float), hipMemcpyDeviceToHost));

@@ -15,6 +15,11 @@
 //   pq_train16_iterations(...), pq_update16(...)  the same for 16-bit sub-quantizers (qadc_pq_train16_host, qadc_pq_update16_host)
 //   learn_pq_hip(...)                      the product quantizer learned on the GPU from a caller-provided seed, as an io::pq_data
 //                                          ready for pq_to_data_file (the reference's flatdb_create / indexdb_create2 read it)
+//   opq_cross(...), opq_train_iterations(...)  CPU twins of qadc_opq_cross_host and qadc_opq_train_host: the cross matrix between
+//                                          the learning set and its reconstruction, and the Procrustes rounds (host/procrustes.hpp)
+//                                          around pq_train_iterations
+//   learn_opq_hip(...)                     the OPQ rotation and its product quantizer learned on the GPU, as an io::pq_data with
+//                                          is_opq set, ready for pq_to_data_file (.opq.data)
 //   db_add_hip(db, base_file, chunk_count) db_add's add_vectors (db_add.cpp:52-82): a reader thread (io::vectors_reader,
 //                                          vector_io.hpp:231-288) fills a two-chunk queue from the .fvecs/.bvecs file while
 //                                          this thread encodes the previous chunk on the GPU; labels = index in chunk + the
@@ -31,6 +36,9 @@
 #include <thread>
 
 #include "../../include/qadc.h"
+#include <cmath>
+
+#include "procrustes.hpp"
 #include "qadc_io.hpp"
 #include "query_driver.hpp"
 
@@ -327,6 +335,77 @@ inline io::pq_data learn_pq_hip(const float* vecs, size_t n, int dim, int sq_cou
     if (qadc_pq_train_host(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, pq.centroids.data(), iters, nullptr, empty_out, 1,
                            1, device) != QADC_OK)
         throw std::runtime_error(std::string("qadc_pq_train_host: ") + qadc_last_error());
+    return pq;
+}
+
+// CPU twin of qadc_opq_cross_host (the definition it is tested against bit for bit): M [dim][dim] doubles = X0^T Y.  X0 = the front's
+// output without a rotation; Y[i][b] = codebooks[m][code(i, m)][b - m dsub], m = b / dsub, the codes in the encoder's layout.  Per
+// block of QADC_OPQ_BLOCK vectors one float chain acc = fmaf(X0[i][a], Y[i][b], acc) in ascending i from 0.0f; the blocks' partials
+// are added in ascending order in double.
+inline void opq_cross(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                      const std::uint8_t* codes, const float* codebooks, double* M) {
+    if ((sq_bits != 4 && sq_bits != 8) || sq_count <= 0 || dim <= 0 || dim % sq_count || (sq_bits == 4 && sq_count % 2))
+        throw std::runtime_error("opq_cross: sq_bits 4 or 8, dim a multiple of sq_count");
+    const int ds = dim / sq_count, K = 1 << sq_bits;
+    const size_t cs = sq_bits == 4 ? (size_t)sq_count / 2 : (size_t)sq_count, d = (size_t)dim;
+    const std::vector<float> x0 = pq_train_front(vecs, n, dim, K_coarse, coarse, nullptr);
+    std::vector<float> partial(d * d), y(d);
+    std::fill(M, M + d * d, 0.0);
+    for (size_t first = 0; first < n; first += QADC_OPQ_BLOCK) {
+        std::fill(partial.begin(), partial.end(), 0.0f);
+        for (size_t i = first; i < std::min(n, first + (size_t)QADC_OPQ_BLOCK); ++i) {
+            for (int m = 0; m < sq_count; ++m) {
+                const int code = sq_bits == 8 ? codes[i * cs + m] : (codes[i * cs + m / 2] >> (4 * (m & 1))) & 15;
+                std::copy(codebooks + ((size_t)m * K + code) * ds, codebooks + ((size_t)m * K + code + 1) * ds, y.begin() + (size_t)m * ds);
+            }
+            for (size_t a = 0; a < d; ++a)
+                for (size_t b = 0; b < d; ++b) partial[a * d + b] = std::fmaf(x0[i * d + a], y[b], partial[a * d + b]);
+        }
+        for (size_t e = 0; e < d * d; ++e) M[e] += (double)partial[e];
+    }
+}
+
+// CPU twin of qadc_opq_train_host: the loop of include/qadc.h written with pq_train_iterations, opq_cross and procrustes.
+// rotation [dim][dim] in and out (the identity for none), codebooks in and out, codes (nullable) of the closing rounds.  Returns the
+// centroids that hold a NaN; *rounds_done (nullable): rotation updates completed.  Throws where a Procrustes solve does not converge.
+inline std::uint64_t opq_train_iterations(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                                          float* rotation, float* codebooks, int outer, int inner, std::uint8_t* codes, int div_mode = 1,
+                                          int* rounds_done = nullptr) {
+    if (!rotation || outer < 0 || inner < 1) throw std::runtime_error("opq_train_iterations: a rotation, outer >= 0, inner >= 1");
+    const size_t cs = sq_bits == 4 ? (size_t)sq_count / 2 : (size_t)sq_count;
+    std::vector<std::uint8_t> round_codes(n * cs);
+    std::vector<double> M((size_t)dim * dim);
+    int done = 0;
+    for (int t = 0; t < outer; ++t) {
+        pq_train_iterations(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, inner, round_codes.data(), div_mode);
+        opq_cross(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, round_codes.data(), codebooks, M.data());
+        const int rc = procrustes(M.data(), dim, rotation);
+        if (rc == kProcrustesNotFinite) break;                      // the rotation stays as it is
+        if (rc != kProcrustesOk) throw std::runtime_error("opq_train_iterations: the Procrustes solve did not converge");
+        ++done;
+    }
+    if (rounds_done) *rounds_done = done;
+    return pq_train_iterations(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, inner, codes, div_mode);
+}
+
+// The OPQ rotation and its product quantizer learned on the GPU (qadc_opq_train_host) from `seed` and a start rotation (NULL: the
+// identity): an io::pq_data with is_opq set, so that pq_to_data_file writes the .opq.data the reference's executables read.
+inline io::pq_data learn_opq_hip(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, const float* seed, int outer, int inner = 1,
+                                 int K_coarse = 0, const float* coarse = nullptr, const float* rotation = nullptr, int device = 0,
+                                 std::uint64_t* empty_out = nullptr, int* rounds_done_out = nullptr) {
+    io::pq_data pq;
+    pq.dim = dim;
+    pq.sq_count = sq_count;
+    pq.sq_bits = sq_bits;
+    if (sq_count <= 0 || dim <= 0 || sq_bits <= 0 || sq_bits > 16 || !seed) throw std::runtime_error("learn_opq_hip: bad arguments");
+    pq.centroids.assign(seed, seed + pq.all_centroids_dim());
+    pq.is_opq = true;
+    pq.rotation.assign((size_t)dim * dim, 0.0f);
+    for (int r = 0; r < dim; ++r) pq.rotation[(size_t)r * dim + r] = 1.0f;
+    if (rotation) pq.rotation.assign(rotation, rotation + (size_t)dim * dim);
+    if (qadc_opq_train_host(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, pq.rotation.data(), pq.centroids.data(), outer, inner, nullptr,
+                            empty_out, rounds_done_out, 1, 1, device) != QADC_OK)
+        throw std::runtime_error(std::string("qadc_opq_train_host: ") + qadc_last_error());
     return pq;
 }
 

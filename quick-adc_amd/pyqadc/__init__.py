@@ -51,6 +51,7 @@ SYMBOLS = [
     "qadc_adc_index_remove_labels", "qadc_adc_index_remove_labels_device", "qadc_index_remove_labels", "qadc_index_remove_labels_device",
     "qadc_pq_train_host", "qadc_pq_train_device",
     "qadc_pq_train16_host", "qadc_pq_train16_device", "qadc_pq_update16_host",
+    "qadc_opq_cross_host", "qadc_opq_cross_device", "qadc_procrustes_host", "qadc_opq_train_host", "qadc_opq_train_device",
     "qadc_adc_filter_create", "qadc_adc_filter_create_device", "qadc_adc_filter_info", "qadc_adc_filter_destroy", "qadc_adc_index_set_filter",
     "qadc_adc_query_scan_filtered", "qadc_adc_query_scan_device_filtered", "qadc_adc_query_scan_candidates_filtered",
     "qadc_adc_search_filtered", "qadc_adc_search_device_filtered", "qadc_adc_search_candidates_filtered",
@@ -264,6 +265,13 @@ def lib():
                                            C.c_int, C.c_int, C.c_int]
         L.qadc_pq_train16_device.argtypes = [C.c_void_p] + L.qadc_pq_train16_host.argtypes[1:]
         L.qadc_pq_update16_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, f32p, u32p, C.c_int, C.c_int]
+        f64p = C.POINTER(C.c_double)
+        L.qadc_opq_cross_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p, f32p, f64p, C.c_int, C.c_int]
+        L.qadc_opq_cross_device.argtypes = [C.c_void_p] + L.qadc_opq_cross_host.argtypes[1:]
+        L.qadc_procrustes_host.argtypes = [f64p, C.c_int, f32p, i32p]
+        L.qadc_opq_train_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_void_p,
+                                          u64p, i32p, C.c_int, C.c_int, C.c_int]
+        L.qadc_opq_train_device.argtypes = [C.c_void_p] + L.qadc_opq_train_host.argtypes[1:]
         for name in ("qadc_adc_index_remove_labels", "qadc_index_remove_labels"):
             getattr(L, name).argtypes = [C.c_void_p, u32p, C.c_uint64, u64p]
             getattr(L, name + "_device").argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p]
@@ -666,6 +674,110 @@ def pq_update16(vectors, codes, sq_count, div_mode=1, device=0):
     _check(lib().qadc_pq_update16_host(_p(v, f32p), n, dim, sq_count, c.ctypes.data_as(C.c_void_p), _p(cb, f32p), _p(counts, u32p), div_mode,
                                        device))
     return cb, counts
+
+
+QADC_OPQ_BLOCK = 2048              # include/qadc.h: vectors per float partial sum of the OPQ cross matrix
+
+
+def _device_vectors(vectors, who):
+    import torch
+    if not isinstance(vectors, torch.Tensor):
+        raise TypeError("vectors must be a torch.Tensor, not %s" % type(vectors).__name__)
+    if vectors.dtype != torch.float32:
+        raise TypeError("vectors must be float32, not %s" % vectors.dtype)
+    if vectors.device.type != "cuda":
+        raise QadcError("vectors is on %s; %s takes a tensor in device memory" % (vectors.device, who))
+    if vectors.ndim != 2 or not vectors.is_contiguous():
+        raise QadcError("vectors must be a contiguous [n][dim] tensor")
+    torch.cuda.current_stream(vectors.device).synchronize()                # the learning set is complete before the call
+    return int(vectors.shape[0]), int(vectors.shape[1])
+
+
+def _opq_cross_args(n, dim, codes, codebooks, coarse):
+    cb, bits, co, _ = _train_pq_args(dim, codebooks, None, coarse, None)
+    nsq = cb.shape[0]
+    c = np.ascontiguousarray(codes, np.uint8)
+    if c.shape != (n, nsq // 2 if bits == 4 else nsq):
+        raise QadcError("codes has shape %s, expected the encoder's layout [%d][%d]" % (tuple(c.shape), n, nsq // 2 if bits == 4 else nsq))
+    return cb, bits, co, c
+
+
+def opq_cross(vectors, codes, codebooks, coarse=None, device=0, sum_mode=1):
+    """The cross matrix of OPQ learning on the GPU (qadc_opq_cross_host): M = X0^T Y, float64 [dim][dim], between the learning set
+    as the quantizer sees it before rotation (X0: residuals to the nearest of coarse [K][dim] where given) and its reconstruction
+    Y[i] = the centroids `codes` [n] (the encoder's layout, as train_pq returns them) select in codebooks
+    [sq_count][2^bits][dim / sq_count].  Per block of QADC_OPQ_BLOCK vectors a float fmaf chain in vector order, the blocks added in
+    float64."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2:
+        raise QadcError("vectors has shape %s, expected [n][dim]" % (tuple(v.shape),))
+    n, dim = v.shape
+    cb, bits, co, c = _opq_cross_args(n, dim, codes, codebooks, coarse)
+    M = np.zeros((dim, dim), np.float64)
+    _check(lib().qadc_opq_cross_host(_p(v, f32p), n, dim, cb.shape[0], bits, 0 if co is None else co.shape[0], _p(co, f32p),
+                                     c.ctypes.data_as(C.c_void_p), _p(cb, f32p), _p(M, C.POINTER(C.c_double)), sum_mode, device))
+    return M
+
+
+def opq_cross_device(vectors, codes, codebooks, coarse=None, sum_mode=1):
+    """opq_cross on a learning set already in device memory: a contiguous float32 [n][dim] torch tensor on a GPU (read only).
+    Everything else is a host array."""
+    n, dim = _device_vectors(vectors, "opq_cross_device")
+    cb, bits, co, c = _opq_cross_args(n, dim, codes, codebooks, coarse)
+    M = np.zeros((dim, dim), np.float64)
+    _check(lib().qadc_opq_cross_device(C.c_void_p(vectors.data_ptr()), n, dim, cb.shape[0], bits, 0 if co is None else co.shape[0],
+                                       _p(co, f32p), c.ctypes.data_as(C.c_void_p), _p(cb, f32p), _p(M, C.POINTER(C.c_double)), sum_mode,
+                                       vectors.device.index or 0))
+    return M
+
+
+def procrustes(M):
+    """The orthogonal rotation that maximises tr(R M) (qadc_procrustes_host; host only): M float64 [dim][dim] ->
+    (rotation float32 [dim][dim], Jacobi sweeps).  For M = opq_cross(...) it is the rotation under which the learning set is closest
+    to its reconstruction."""
+    m = np.ascontiguousarray(M, np.float64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise QadcError("M has shape %s, expected [dim][dim]" % (tuple(m.shape),))
+    rot = np.zeros(m.shape, np.float32)
+    sweeps = C.c_int32(0)
+    _check(lib().qadc_procrustes_host(_p(m, C.POINTER(C.c_double)), m.shape[0], _p(rot, f32p), C.byref(sweeps)))
+    return rot, int(sweeps.value)
+
+
+def _train_opq_args(n, dim, codebooks_seed, bits, coarse, rotation):
+    cb, bits, co, rot = _train_pq_args(dim, codebooks_seed, bits, coarse, rotation)
+    rot = np.eye(dim, dtype=np.float32) if rot is None else np.array(rot, np.float32, order="C", copy=True)
+    nsq = cb.shape[0]
+    return cb, bits, co, rot, np.zeros((n, nsq // 2 if bits == 4 else nsq), np.uint8)
+
+
+def train_opq(vectors, codebooks_seed, outer, inner=1, rotation=None, coarse=None, bits=None, device=0, div_mode=1, sum_mode=1):
+    """Learn an OPQ rotation and its product quantizer on the GPU (qadc_opq_train_host): `outer` times [train_pq with `inner`
+    rounds under the current rotation, opq_cross, procrustes], then `inner` closing rounds under the final rotation — bit for bit
+    that loop of the public calls, with the learning set uploaded once.  rotation: the start [dim][dim] (None: the identity).
+    -> (rotation float32 [dim][dim], codebooks, codes, empty, rounds_done) — codebooks, codes and empty as train_pq returns them;
+    rounds_done < outer where a cross matrix was not finite (the rotation then stays as it was)."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2:
+        raise QadcError("vectors has shape %s, expected [n][dim]" % (tuple(v.shape),))
+    n, dim = v.shape
+    cb, bits, co, rot, codes = _train_opq_args(n, dim, codebooks_seed, bits, coarse, rotation)
+    empty, done = C.c_uint64(0), C.c_int32(0)
+    _check(lib().qadc_opq_train_host(_p(v, f32p), n, dim, cb.shape[0], bits, 0 if co is None else co.shape[0], _p(co, f32p), _p(rot, f32p),
+                                     _p(cb, f32p), outer, inner, codes.ctypes.data_as(C.c_void_p), C.byref(empty), C.byref(done),
+                                     div_mode, sum_mode, device))
+    return rot, cb, codes, int(empty.value), int(done.value)
+
+
+def train_opq_device(vectors, codebooks_seed, outer, inner=1, rotation=None, coarse=None, bits=None, div_mode=1, sum_mode=1):
+    """train_opq on a learning set already in device memory: a contiguous float32 [n][dim] torch tensor on a GPU (read only)."""
+    n, dim = _device_vectors(vectors, "train_opq_device")
+    cb, bits, co, rot, codes = _train_opq_args(n, dim, codebooks_seed, bits, coarse, rotation)
+    empty, done = C.c_uint64(0), C.c_int32(0)
+    _check(lib().qadc_opq_train_device(C.c_void_p(vectors.data_ptr()), n, dim, cb.shape[0], bits, 0 if co is None else co.shape[0],
+                                       _p(co, f32p), _p(rot, f32p), _p(cb, f32p), outer, inner, codes.ctypes.data_as(C.c_void_p),
+                                       C.byref(empty), C.byref(done), div_mode, sum_mode, vectors.device.index or 0))
+    return rot, cb, codes, int(empty.value), int(done.value)
 
 
 def pq_seed(vectors, sq_count, bits, rng):

@@ -1,8 +1,8 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,filter,qfilter,refine,range,keyed] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,filter] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,filter,qfilter,refine,range,keyed] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,opq,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,filter] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
@@ -36,6 +36,12 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             vectors, 8x8, 10 rounds from a seed of 256 distinct rows (pyqadc.pq_seed).  train_pq, call to return (the upload of the
             learning set included), alternated in one process with the route without it: kmeans_iterations on every host slice.
             The two routes' codebooks and codes are first asserted equal bit for bit
+  opq       learning the OPQ rotation (not in the default legs; also under --bits 4, at 16x4): 10^6 clustered
+            128-d vectors, 8x8, train_opq(outer = 4, inner = 2) from the identity and a seed of distinct rows — ten k-means rounds with
+            the closing ones — call to return, alternated in one process with the same loop composed from the public calls (train_pq
+            with the rotation, opq_cross, procrustes: the learning set uploaded twice per outer round); the two routes' arrays are
+            first asserted identical.  Beside it train_pq with ten rounds, and the reconstruction error
+            (tests/pq_train_compose.reconstruction_error) of the learned pair against plain PQ's at those ten rounds
   filter    filtered search (not in the default legs; also under --bits 4 at 16x4 and --bits 16 at 4x16, part (a) only; DESIGN.md
             section 11.10): (a) one synchronous query on 10^8 labelled codes (10^6 at --bits 4 and 16), unfiltered, EXCLUDE of 1 % and
             50 % of the keys, ALLOW of 1 % and 0.01 %, each checked against an index built without the dropped rows; (b) search() of
@@ -714,6 +720,8 @@ def view_legs(legs, iters, res):
         remove_leg(4, iters, res)
     if "train" in legs:
         train_leg(4, iters, res)
+    if "opq" in legs:
+        opq_leg(4, iters, res)
 
 
 def cpu_twin_u16_us(nsq, codes, table, repeat=5):
@@ -920,6 +928,54 @@ def train_leg(bits, iters, res):
         res[tag + "_empty_clusters"] = int(empty)
         print("PQ training %dx%d, %.0e clustered 128-d vectors, %d rounds, host to host: train_pq %.3f s; kmeans_iterations on %d host slices "
               "%.3f s = %.2fx (equal bits; %d empty clusters)" % (nsq, bits, n, rounds, med_new, nsq, med_old, med_old / med_new, empty), flush=True)
+
+
+def opq_leg(bits, iters, res):
+    """train_opq alternated with the same loop composed from the public calls; the learned pair's reconstruction error beside plain PQ's"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pq_train_compose as ptc
+    rng = np.random.default_rng(2100 + bits)
+    n, dim, outer, inner = 1_000_000, 128, 4, 2                  # 4 x 2 rounds and 2 closing ones: 10 k-means rounds
+    nsq = {4: 16, 8: 8}[bits]
+    vectors, _ = clustered(rng, n, dim)
+    seed = pyqadc.pq_seed(vectors, nsq, bits, rng)
+    eye = np.eye(dim, dtype=np.float32)
+
+    def new_route():
+        return pyqadc.train_opq(vectors, seed, outer, inner)
+
+    def composed_route():
+        rot, cb = eye, seed
+        for _ in range(outer):
+            cb, codes, _ = pyqadc.train_pq(vectors, cb, inner, rotation=rot)
+            rot = pyqadc.procrustes(pyqadc.opq_cross(vectors, codes, cb))[0]
+        cb, codes, empty = pyqadc.train_pq(vectors, cb, inner, rotation=rot)
+        return rot, cb, codes, empty, outer
+
+    got, want = new_route(), composed_route()
+    nan = np.isnan(got[1])
+    assert np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32)), "the routes' rotations differ"
+    assert np.array_equal(nan, np.isnan(want[1])) and ((got[1].view(np.uint32) == want[1].view(np.uint32)) | nan).all(), "the routes' codebooks differ"
+    assert np.array_equal(got[2], want[2]) and got[3:] == want[3:], "the routes' codes differ"
+    med_new, med_old = alternated(new_route, composed_route, max(3, iters // 2), warmup=1)
+    rounds = (outer + 1) * inner
+    pq_cb, pq_codes, pq_empty = pyqadc.train_pq(vectors, seed, rounds)
+    err_pq = ptc.reconstruction_error(vectors, pq_cb, pq_codes)
+    err_opq = ptc.reconstruction_error(vectors.astype(np.float64) @ got[0].astype(np.float64).T, got[1], got[2])
+    t_pq, _ = timed(lambda: pyqadc.train_pq(vectors, seed, rounds), 3, warmup=0)
+    tag = "opq_%dx%d_n%d" % (nsq, bits, n)
+    res[tag + "_train_opq_s"] = med_new
+    res[tag + "_composed_s"] = med_old
+    res[tag + "_composed_over_train_opq"] = med_old / med_new
+    res[tag + "_train_pq_same_rounds_s"] = t_pq
+    res[tag + "_error_opq"] = err_opq
+    res[tag + "_error_pq"] = err_pq
+    res[tag + "_empty_clusters"] = [int(got[3]), int(pq_empty)]
+    print("OPQ training %dx%d, %.0e clustered 128-d vectors, outer %d x inner %d + %d closing = %d rounds, host to host: train_opq %.3f s; "
+          "the loop of train_pq / opq_cross / procrustes %.3f s = %.2fx (equal bits); train_pq with %d rounds %.3f s.  Reconstruction error: "
+          "OPQ %.4g, PQ %.4g (%.3f of it; %d and %d empty clusters)"
+          % (nsq, bits, n, outer, inner, inner, rounds, med_new, med_old, med_old / med_new, rounds, t_pq, err_opq, err_pq, err_opq / err_pq,
+             got[3], pq_empty), flush=True)
 
 
 def add_leg(bits, iters, res):
@@ -1362,6 +1418,8 @@ def main():
         remove_leg(8, a.iters, res)
     if "train" in legs:
         train_leg(8, a.iters, res)
+    if "opq" in legs:
+        opq_leg(8, a.iters, res)
     line = json.dumps(res)
     print(line)
     if a.out:

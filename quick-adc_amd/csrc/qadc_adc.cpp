@@ -8,9 +8,11 @@
 // smallest of a subset of the codes that precede every code of the level.  The kept candidates come back to the host,
 // are put in scan order and pushed into kv_heap<unsigned, float>(R) after the R sentinels — or, with the device finish
 // (qadc_adc_index_set_finish, the *_device entry points), are ordered and replayed by two more kernels, so
-// that only the heaps' arrays leave device memory, or nothing does.  This engine shares nothing
+// that only the heaps' arrays leave device memory, or nothing does.  On the query side this engine shares nothing
 // with the 4-bit index but the device's stream set (qadc_device_prepare), the coarse-assignment kernels and the float sums
-// of the feeders; it has no qadc_set_option names.
+// of the feeders; it has no qadc_set_option names.  The owned database is a RowStore (csrc/qadc_host.h), and what changes it —
+// add_vectors, reserve, read_partition (csrc/qadc_append.h) and remove_labels (csrc/qadc_remove.h) — is the host flow both
+// engines run: this file supplies the move step of a relocation and the encoders' last launch (DESIGN.md sections 11.5, 11.7).
 //
 // The tables of a call come from the caller (qadc_adc_query_scan*) or are built on the device from query vectors
 // (qadc_adc_search*: coarse assignment, residual, OPQ rotation, tables — what nns_engine(_batch)::process_query does before
@@ -37,6 +39,7 @@
 #include "../host/qadc_heap.hpp"
 #include "../host/worker_pool.hpp"
 #include "qadc_adc_kernels.h"
+#include "qadc_append.h"
 #include "qadc_host.h"
 #include "qadc_remove.h"
 
@@ -73,15 +76,8 @@ struct qadc_adc_index {
     DevBuf<qadc::adc::Part4> d_parts4;
     hipStream_t stream = nullptr;
     int labeled = -1;                               // unknown until the first non-empty add
-    std::vector<uint32_t> sizes;
-    std::vector<uint32_t> caps;                     // rows each partition's region holds (>= sizes; host/adc_append_plan.hpp)
-    std::vector<uint64_t> off, lab_off;             // byte offset of each partition's codes / first label
-    uint64_t code_bytes = 0, label_count = 0;       // bytes / labels of all regions
-    uint64_t relocations = 0;                       // add_vectors calls that moved the database to grow it
-    PinBuf<uint32_t> h_add;                         // add_vectors: [counts K + 1 | bases K]
-    DevBuf<uint8_t> codes;                          // code_bytes + 16 bytes of tail padding
-    DevBuf<uint32_t> labels;
-    DevBuf<uint64_t> d_off, d_lab_off;
+    std::vector<uint32_t> sizes;                    // rows each partition holds (a view: of the index it reads)
+    qadc::host::RowStore store;                     // the owned database: region_pad 0, code_bytes + kAppendTailPad bytes of codes
     // per call
     DevBuf<uint8_t> d_in;                           // [bound | count | assign | items | tables]
     DevBuf<float> d_vals;
@@ -164,8 +160,8 @@ ScanFilter scan_filter(const qadc_adc_filter* f) { return f ? ScanFilter{f->bitm
 ScanDb scan_db(const qadc_adc_index* idx) {
     const ScanFilter filter = scan_filter(idx->filter);
     if (idx->src) return ScanDb{idx->nsq, idx->centroids, Db{}, idx->d_parts4.p, filter};
-    return ScanDb{idx->nsq, idx->centroids, Db{idx->codes.p, idx->d_off.p, idx->labeled == 1 ? idx->labels.p : nullptr, idx->d_lab_off.p}, nullptr,
-                  filter};
+    return ScanDb{idx->nsq, idx->centroids, Db{idx->store.codes.p, idx->store.d_off.p, idx->labeled == 1 ? idx->store.labels.p : nullptr,
+                                                  idx->store.d_lab_off.p}, nullptr, filter};
 }
 
 // One batch on its way through scan_batch: the plan, where the batch lies in the staging buffers idx->h_in / idx->d_in, uploaded in one copy —
@@ -884,209 +880,60 @@ int range_collect(qadc_adc_index* idx, uint64_t capacity, uint32_t* keys, float*
     return QADC_OK;
 }
 
-// ---- db_add: qadc_adc_index_add_vectors, _reserve, _read_partition ----
+// ---- db_add: qadc_adc_index_add_vectors, _reserve, _read_partition.  The flow is csrc/qadc_append.h's, shared
+// with the 4-bit index, over idx->store; here are the move step of a relocation and the encoders' last step ----
 
-// Puts the owned database into the layout of `plan` on the index's stream: new buffers, every partition moved by one kernel, the
-// tail padding zeroed, the offset tables uploaded; the old buffers are freed once the move is complete.  labels: the new layout
-// has a label buffer (the index is labelled or about to be).
-int relocate(qadc_adc_index* idx, const AppendPlan& plan, bool labels) {
-    const size_t parts = plan.cap.size();
-    DevBuf<uint8_t> codes;
-    DevBuf<uint32_t> labs, d_sizes;
-    DevBuf<uint64_t> d_off, d_lab_off;
-    auto drop = [&]() { codes.release(); labs.release(); d_sizes.release(); d_off.release(); d_lab_off.release(); };
-    auto run = [&]() -> int {
-        HIPCHECK(codes.ensure(plan.code_bytes + kAppendTailPad));
-        if (labels) HIPCHECK(labs.ensure(std::max<uint64_t>(plan.label_count, 1)));
-        HIPCHECK(d_off.ensure(std::max<size_t>(parts, 1)));
-        HIPCHECK(d_lab_off.ensure(std::max<size_t>(parts, 1)));
-        HIPCHECK(d_sizes.ensure(std::max<size_t>(parts, 1)));
-        if (parts) {
-            HIPCHECK(hipMemcpyAsync(d_off.p, plan.off.data(), parts * 8, hipMemcpyHostToDevice, idx->stream));
-            HIPCHECK(hipMemcpyAsync(d_lab_off.p, plan.lab_off.data(), parts * 8, hipMemcpyHostToDevice, idx->stream));
-            HIPCHECK(hipMemcpyAsync(d_sizes.p, idx->sizes.data(), parts * 4, hipMemcpyHostToDevice, idx->stream));
-        }
-        const uint32_t longest = parts ? *std::max_element(idx->sizes.begin(), idx->sizes.end()) : 0;
-        if (longest)   // (a partition that holds rows lies in the old buffers and in the old tables)
-            HIPCHECK(launch_adc_move_partitions((int)parts, idx->code_size(), d_sizes.p, longest, idx->codes.p, idx->d_off.p,
-                                                idx->labeled == 1 ? idx->labels.p : nullptr, idx->d_lab_off.p, codes.p, d_off.p,
-                                                idx->labeled == 1 ? labs.p : nullptr, d_lab_off.p, idx->stream));
-        HIPCHECK(launch_adc_fill_words(codes.p + plan.code_bytes, kAppendTailPad / 4, 0u, idx->stream));
-        HIPCHECK(hipStreamSynchronize(idx->stream));
-        return QADC_OK;
-    };
-    if (int rc = run()) {
-        (void)hipStreamSynchronize(idx->stream);
-        drop();
-        return rc;
-    }
-    idx->codes.release();
-    idx->d_off.release();
-    idx->d_lab_off.release();
-    idx->codes = codes;
-    idx->d_off = d_off;
-    idx->d_lab_off = d_lab_off;
-    if (labels) {
-        idx->labels.release();
-        idx->labels = labs;
-    }
-    d_sizes.release();
-    idx->caps = plan.cap;
-    idx->off = plan.off;
-    idx->lab_off = plan.lab_off;
-    idx->code_bytes = plan.code_bytes;
-    idx->label_count = plan.label_count;
+// The move step of a relocation: every partition from the old buffers, by their offset tables, into the new ones.
+int move_parts(const qadc_adc_index* idx, const Relocation& r) {
+    const RowStore& st = idx->store;
+    const size_t parts = r.plan.cap.size();
+    const uint32_t longest = parts ? *std::max_element(r.sizes.begin(), r.sizes.end()) : 0;
+    uint32_t* d_sizes = nullptr;
+    HIPCHECK(r.tmp.alloc(&d_sizes, parts * 4));
+    if (parts) HIPCHECK(hipMemcpyAsync(d_sizes, r.sizes.data(), parts * 4, hipMemcpyHostToDevice, idx->stream));   // (drained before the sizes change)
+    if (longest)   // (a partition that holds rows lies in the old buffers and in the old tables)
+        HIPCHECK(launch_adc_move_partitions((int)parts, st.code_size, d_sizes, longest, st.codes.p, st.d_off.p, idx->labeled == 1 ? st.labels.p : nullptr,
+                                            st.d_lab_off.p, r.codes, r.d_off, idx->labeled == 1 ? r.labels : nullptr, r.d_lab_off, idx->stream));
     return QADC_OK;
 }
 
-// Room for add[p] more rows in every partition: nothing to do where they fit, else one relocation.  `fresh`: the partitions were
-// created by this call and have no device tables yet.
-int make_room(qadc_adc_index* idx, const std::vector<uint64_t>& add, bool labels, bool fresh, bool* moved) {
-    const AppendPlan plan = plan_append(idx->code_size(), idx->sizes.size(), idx->sizes.data(), idx->caps.data(), add.data(), nullptr, true);
-    if (!plan.refused.empty()) return fail(QADC_E_ARG, plan.refused);
-    if (!plan.in_place) *moved = true;
-    if (!plan.in_place || fresh) return relocate(idx, plan, labels);
-    if (labels && idx->labels.cap < std::max<uint64_t>(plan.label_count, 1))   // (capacity reserved before the index had labels)
-        HIPCHECK(idx->labels.ensure(std::max<uint64_t>(plan.label_count, 1)));
-    return QADC_OK;
-}
-
-// The encoder of one call: the steps and kernels of qadc_adc_encode_host / qadc_adc_encode16_host on the index's own quantizers
-// and stream, into device scratch sized for one pass.
-struct AddEncoder {
-    Scratch mem;
-    uint64_t pass = 0;   // vectors of the largest pass
-    float *d_v = nullptr, *d_x = nullptr, *d_dist = nullptr, *d_qnorm = nullptr;
-    int32_t* d_assign = nullptr;
-    uint8_t* d_codes = nullptr;
-    unsigned long long* d_part = nullptr;
-
-    int prepare(const qadc_adc_index* idx, uint64_t count, bool d_side) {
-        pass = std::min<uint64_t>(QADC_ADC_ADD_CHUNK, count);
-        const int dim = idx->dim, ds = dim / idx->nsq;
-        if (!d_side) HIPCHECK(mem.alloc(&d_v, pass * dim * 4));
-        if (idx->K || idx->rotated) HIPCHECK(mem.alloc(&d_x, pass * dim * 4));
-        HIPCHECK(mem.alloc(&d_codes, pass * idx->code_size()));
-        if (idx->K) {
-            const uint64_t chunk = std::min<uint64_t>(kCoarseChunk, pass);
-            HIPCHECK(mem.alloc(&d_dist, chunk * ((uint64_t)idx->K + 1) * 4));
-            d_qnorm = d_dist + chunk * (uint64_t)idx->K;
-            HIPCHECK(mem.alloc(&d_assign, pass * 4));
-        }
-        if (idx->centroids == 65536) {   // the partial picks: the slices of the largest pass and of the last one (a shorter pass is cut finer)
-            const uint64_t last = count % QADC_ADC_ADD_CHUNK ? count % QADC_ADC_ADD_CHUNK : pass;
-            const uint64_t entries = std::max(pass * encode16_slices((uint32_t)pass, idx->nsq, ds), last * encode16_slices((uint32_t)last, idx->nsq, ds));
-            HIPCHECK(mem.alloc(&d_part, entries * idx->nsq * 8));
-        }
-        return QADC_OK;
-    }
-
-    // vectors [cnt][dim] (host memory, or device memory read where it lies) -> d_assign [cnt] (with a coarse quantizer), d_codes [cnt]
-    int encode(qadc_adc_index* idx, const float* vectors, uint64_t cnt, int sum_mode, bool d_side) {
-        const int dim = idx->dim;
-        const size_t mode = sum_mode == 1;
-        const float* src = vectors;
-        if (!d_side) {
-            HIPCHECK(hipMemcpyAsync(d_v, vectors, cnt * dim * 4, hipMemcpyHostToDevice, idx->stream));
-            src = d_v;
-        }
-        const float* d_enc = src;
-        if (idx->K) {   // find_k_neighbors(k = 1) on the coarse centroids
-            for (uint64_t c = 0; c < cnt; c += kCoarseChunk)
-                qadc::launch_coarse_assign(src + c * dim, idx->d_coarse.p, (int)std::min<uint64_t>(kCoarseChunk, cnt - c), idx->K, dim, 1, d_qnorm,
-                                           idx->d_cnorm.p + mode * idx->K, sum_mode, d_dist, d_assign + c, idx->stream);
-            HIPCHECK(hipGetLastError());
-        }
-        if (idx->K || idx->rotated) {
-            qadc::launch_residual_rotate(src, cnt, dim, idx->K ? idx->d_coarse.p : nullptr, d_assign, idx->rotated ? idx->d_rotation.p : nullptr, d_x,
-                                         idx->stream);
-            HIPCHECK(hipGetLastError());
-            d_enc = d_x;
-        }
+// The index as the shared flow takes it.  sum_mode: the call's (which of the cached norms the encoders read).
+AppendJob make_job(qadc_adc_index* idx, int sum_mode) {
+    const size_t mode = sum_mode == 1;
+    AppendJob job;
+    job.store = &idx->store;
+    job.stream = idx->stream;
+    job.device = idx->device;
+    job.labeled = &idx->labeled;
+    job.sizes = idx->sizes;
+    job.dim = idx->dim;
+    job.K = idx->K;
+    job.set_pq = "qadc_adc_index_set_pq";
+    job.d_coarse = idx->d_coarse.p;
+    job.d_rotation = idx->rotated ? idx->d_rotation.p : nullptr;
+    job.d_cnorm = idx->d_cnorm.p + mode * idx->K;
+    job.move = [idx](const Relocation& r) { return move_parts(idx, r); };
+    job.set_sizes = [idx](const std::vector<uint32_t>& sizes) { idx->sizes = sizes; };
+    // the steps and kernels of qadc_adc_encode_host / qadc_adc_encode16_host on the index's own quantizers; the 16-bit encoder's partial
+    // picks: the slices of the largest pass and of the last one (a shorter pass is cut finer)
+    if (idx->centroids == 65536)
+        job.prepare = [idx](AddEncoder& enc, uint64_t count) {
+            const int ds = idx->dim / idx->nsq;
+            const uint64_t last = count % kAddChunk ? count % kAddChunk : enc.pass;
+            const uint64_t entries = std::max(enc.pass * encode16_slices((uint32_t)enc.pass, idx->nsq, ds), last * encode16_slices((uint32_t)last, idx->nsq, ds));
+            HIPCHECK(enc.mem.alloc(&enc.d_part, entries * idx->nsq * 8));
+            return QADC_OK;
+        };
+    job.encode = [idx, sum_mode, mode](AddEncoder& enc, const float* d_enc, uint64_t cnt) {
         const float* cbnorm = idx->d_cbnorm.p + mode * idx->nsq * idx->centroids;
         if (idx->centroids == 65536)
-            HIPCHECK(launch_adc_encode16(d_enc, (uint32_t)cnt, idx->nsq, dim, idx->d_codebooks.p, cbnorm, sum_mode, d_part,
-                                         reinterpret_cast<uint16_t*>(d_codes), idx->stream));
+            HIPCHECK(launch_adc_encode16(d_enc, (uint32_t)cnt, idx->nsq, idx->dim, idx->d_codebooks.p, cbnorm, sum_mode, enc.d_part,
+                                         reinterpret_cast<uint16_t*>(enc.d_codes), idx->stream));
         else
-            HIPCHECK(launch_adc_encode(d_enc, cnt, idx->nsq, dim, idx->d_codebooks.p, cbnorm, sum_mode, d_codes, idx->stream));
+            HIPCHECK(launch_adc_encode(d_enc, cnt, idx->nsq, idx->dim, idx->d_codebooks.p, cbnorm, sum_mode, enc.d_codes, idx->stream));
         return QADC_OK;
-    }
-};
-
-// index_db::add_vectors (databases.hpp:270-298) pass by pass: encode, count, plan, relocate if needed, scatter.  labels [count]
-// (host or device memory, as the vectors) or null: the label of vector i, in place of labels_offset + i.
-int add_ivf(qadc_adc_index* idx, const float* vectors, const uint32_t* labels, uint64_t count, uint32_t labels_offset, int sum_mode,
-            bool d_side, bool fresh, bool* moved) {
-    const uint32_t K = (uint32_t)idx->K;
-    std::vector<uint64_t> add(K, 0);
-    if (count == 0) return fresh ? make_room(idx, add, false, true, moved) : QADC_OK;
-    AddEncoder enc;
-    if (int rc = enc.prepare(idx, count, d_side)) return rc;
-    uint32_t *d_count = nullptr, *d_base = nullptr, *d_hist = nullptr, *d_perm_a = nullptr, *d_perm_b = nullptr;
-    HIPCHECK(enc.mem.alloc(&d_count, ((size_t)K + 1) * 4));
-    HIPCHECK(enc.mem.alloc(&d_base, (size_t)K * 4));
-    HIPCHECK(enc.mem.alloc(&d_hist, (enc.pass / kAddTile + 1) * 256 * 4));
-    if (K > 256) HIPCHECK(enc.mem.alloc(&d_perm_a, enc.pass * 4));
-    if (K > 65536) HIPCHECK(enc.mem.alloc(&d_perm_b, enc.pass * 4));
-    uint32_t* d_lab = nullptr;   // the labels of a pass, uploaded beside its vectors
-    if (labels && !d_side) HIPCHECK(enc.mem.alloc(&d_lab, enc.pass * 4));
-    HIPCHECK(idx->h_add.ensure(2 * (size_t)K + 1));
-    uint32_t *h_count = idx->h_add.p, *h_base = idx->h_add.p + K + 1;
-    for (uint64_t o = 0; o < count; o += QADC_ADC_ADD_CHUNK) {
-        const uint64_t cnt = std::min<uint64_t>(QADC_ADC_ADD_CHUNK, count - o);
-        if (int rc = enc.encode(idx, vectors + o * idx->dim, cnt, sum_mode, d_side)) return rc;
-        const uint32_t* d_pass_lab = labels ? labels + o : nullptr;
-        if (d_lab) {
-            HIPCHECK(hipMemcpyAsync(d_lab, labels + o, cnt * 4, hipMemcpyHostToDevice, idx->stream));
-            d_pass_lab = d_lab;
-        }
-        HIPCHECK(hipMemsetAsync(d_count, 0, ((size_t)K + 1) * 4, idx->stream));
-        HIPCHECK(launch_adc_add_count(enc.d_assign, (uint32_t)cnt, K, d_count, idx->stream));
-        HIPCHECK(hipMemcpyAsync(h_count, d_count, ((size_t)K + 1) * 4, hipMemcpyDeviceToHost, idx->stream));
-        HIPCHECK(hipStreamSynchronize(idx->stream));
-        if (h_count[K])
-            return fail(QADC_E_ARG, std::to_string(h_count[K]) + " vectors were assigned outside the " + std::to_string(K) + " partitions");
-        uint32_t below = 0;
-        for (uint32_t p = 0; p < K; ++p) {
-            add[p] = h_count[p];
-            h_base[p] = idx->sizes[p] - below;   // (modulo 2^32: the kernel adds the position in (assign, i) order)
-            below += h_count[p];
-        }
-        if (int rc = make_room(idx, add, true, fresh && o == 0, moved)) return rc;
-        HIPCHECK(hipMemcpyAsync(d_base, h_base, (size_t)K * 4, hipMemcpyHostToDevice, idx->stream));
-        const AddDst dst{idx->codes.p, idx->d_off.p, idx->labels.p, idx->d_lab_off.p, d_base};
-        HIPCHECK(launch_adc_add_scatter(enc.d_assign, (uint32_t)cnt, K, idx->code_size(), enc.d_codes, labels_offset + (uint32_t)o, d_pass_lab, dst,
-                                        d_hist, d_perm_a, d_perm_b, idx->stream));
-        HIPCHECK(hipStreamSynchronize(idx->stream));   // (h_base is written again by the next pass)
-        for (uint32_t p = 0; p < K; ++p) idx->sizes[p] += h_count[p];
-        idx->labeled = 1;
-    }
-    return QADC_OK;
-}
-
-// flat_db::add_vectors (databases.hpp:136-156): the rows go to [labels_offset, labels_offset + count) of the one partition.
-int add_flat(qadc_adc_index* idx, const float* vectors, uint64_t count, uint32_t labels_offset, int sum_mode, bool d_side, bool fresh,
-             bool* moved) {
-    const uint32_t old = idx->sizes[0];
-    const uint32_t size = (uint32_t)std::max<uint64_t>(old, (uint64_t)labels_offset + count);
-    const int cs = idx->code_size();
-    if (int rc = make_room(idx, std::vector<uint64_t>{(uint64_t)size - old}, false, fresh, moved)) return rc;
-    uint8_t* part = idx->codes.p + idx->off[0];
-    if (labels_offset > old)   // the rows of the gap are zero bytes, as std::vector::resize leaves them
-        HIPCHECK(launch_adc_fill_words(part + (uint64_t)old * cs, ((uint64_t)labels_offset - old) * cs / 4, 0u, idx->stream));
-    if (count) {
-        AddEncoder enc;
-        if (int rc = enc.prepare(idx, count, d_side)) return rc;
-        for (uint64_t o = 0; o < count; o += QADC_ADC_ADD_CHUNK) {
-            const uint64_t cnt = std::min<uint64_t>(QADC_ADC_ADD_CHUNK, count - o);
-            if (int rc = enc.encode(idx, vectors + o * idx->dim, cnt, sum_mode, d_side)) return rc;
-            HIPCHECK(launch_adc_copy_words(enc.d_codes, part + ((uint64_t)labels_offset + o) * cs, cnt * cs / 4, idx->stream));
-        }
-    }
-    HIPCHECK(hipStreamSynchronize(idx->stream));
-    idx->sizes[0] = size;
-    if (size) idx->labeled = 0;
-    return QADC_OK;
+    };
+    return job;
 }
 
 // labelled: the call is qadc_adc_index_add_vectors_labelled / _device, which takes labels [count] and no labels_offset.
@@ -1094,64 +941,11 @@ int add_vectors(qadc_adc_index* idx, const float* vectors, const uint32_t* label
                 int sum_mode, bool d_side, const char* call) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
     if (int rc = refuse_on_view(idx, call)) return rc;
-    if (labelled) {   // (the keys of a flat or unlabelled index are positions: it has no label to set)
-        if (idx->dim && !idx->K)
-            return fail(QADC_E_STATE, std::string(call) + ": a flat index (no coarse quantizer) keys its vectors by position and takes no labels");
-        if (idx->labeled == 0 && std::any_of(idx->sizes.begin(), idx->sizes.end(), [](uint32_t s) { return s != 0; }))
-            return fail(QADC_E_STATE, std::string(call) + ": the index holds unlabelled partitions, whose keys are positions");
-        if (count && !labels) return fail(QADC_E_ARG, "labels is null");
-    }
-    if (!idx->dim) return fail(QADC_E_ARG, "qadc_adc_index_set_pq has not been called: the index has no codebooks");
-    if (sum_mode != 0 && sum_mode != 1) return fail(QADC_E_ARG, "sum_mode is 0 (source order) or 1 (as compiled)");
-    if (count && !vectors) return fail(QADC_E_ARG, "vectors is null");
-    if ((uint64_t)labels_offset + count > kAppendMaxRows)
-        return fail(QADC_E_ARG, "labels_offset + count = " + std::to_string((uint64_t)labels_offset + count) + " exceeds 2^32 - 1");
-    const size_t parts = idx->sizes.size();
-    const bool holds = std::any_of(idx->sizes.begin(), idx->sizes.end(), [](uint32_t s) { return s != 0; });
-    if (idx->K) {
-        if (parts != 0 && parts != (size_t)idx->K)
-            return fail(QADC_E_ARG, "the coarse quantizer has " + std::to_string(idx->K) + " centroids and the index " + std::to_string(parts) +
-                                        " partitions");
-        if (idx->labeled == 0 && holds) return fail(QADC_E_ARG, "the index holds unlabelled partitions: vectors added through a coarse quantizer are labelled");
-    } else {
-        if (parts > 1) return fail(QADC_E_ARG, "a flat index (no coarse quantizer) has one partition: the index has " + std::to_string(parts));
-        if (idx->labeled == 1 && holds) return fail(QADC_E_ARG, "the index is labelled: a flat index keys its vectors by position");
-    }
-    DeviceGuard guard;
-    HIPCHECK(hipSetDevice(idx->device));
-    // what a refused or failed call puts back: the rows of every partition (rows written beyond them are not part of the database)
-    const std::vector<uint32_t> sizes0 = idx->sizes;
-    const int labeled0 = idx->labeled;
-    const bool fresh = parts == 0;
-    if (fresh) {
-        const size_t n = idx->K ? (size_t)idx->K : 1;
-        idx->sizes.assign(n, 0);
-        idx->caps.assign(n, 0);
-        idx->off.assign(n, 0);
-        idx->lab_off.assign(n, 0);
-    }
-    bool moved = false;
-    const int rc = idx->K ? add_ivf(idx, vectors, labels, count, labels_offset, sum_mode, d_side, fresh, &moved)
-                          : add_flat(idx, vectors, count, labels_offset, sum_mode, d_side, fresh, &moved);
-    if (rc != QADC_OK) {
-        (void)hipStreamSynchronize(idx->stream);
-        idx->labeled = labeled0;
-        if (fresh) {   // the index held no partition: it holds none again
-            idx->sizes.clear();
-            idx->caps.clear();
-            idx->off.clear();
-            idx->lab_off.clear();
-            idx->code_bytes = idx->label_count = 0;
-        } else {
-            idx->sizes = sizes0;
-        }
-        return rc;
-    }
-    if (moved) ++idx->relocations;
-    return QADC_OK;
+    AppendJob job = make_job(idx, sum_mode);
+    return append_vectors(job, vectors, labels, labelled, count, labels_offset, sum_mode, d_side, call);
 }
 
-// Remove by label over the regions of the owned database: codes.p + off[p], labels.p + lab_off[p].
+// Remove by label over the regions of the owned database (idx->store).
 // Capacities, offsets and buffers stay as they are; the sizes are committed once the compaction has completed.
 int remove_labels(qadc_adc_index* idx, const uint32_t* list, uint64_t count, uint64_t* removed_out, bool d_side, const char* call) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
@@ -1170,10 +964,10 @@ int remove_labels(qadc_adc_index* idx, const uint32_t* list, uint64_t count, uin
     job.stream = idx->stream;
     job.code_size = idx->code_size();
     job.sizes = idx->sizes;
-    job.pinned = &idx->h_add;
+    job.pinned = &idx->store.h_add;
     for (size_t p = 0; p < idx->sizes.size(); ++p) {
-        job.codes.push_back(idx->codes.p + idx->off[p]);
-        job.labels.push_back(idx->labels.p + idx->lab_off[p]);
+        job.codes.push_back(idx->store.part_codes(p));
+        job.labels.push_back(idx->store.part_labels(p));
     }
     if (int rc = qadc::host::remove_rows(job, list, count, d_side)) {
         const std::string msg = qadc::host::g_err;
@@ -1289,6 +1083,7 @@ static int create_owned(qadc_adc_index** out, int nsq, int centroids, int device
     qadc_adc_index* idx = new qadc_adc_index();
     idx->nsq = nsq;
     idx->centroids = centroids;
+    idx->store.code_size = idx->code_size();
     idx->device = device_id;
     const hipError_t e = hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -1377,10 +1172,7 @@ int qadc_adc_index_destroy(qadc_adc_index* idx) {
     if (idx->src) --idx->src->adc_views;   // the view's scans are over: the source may be destroyed again
     release_filter(idx);
     idx->d_parts4.release();
-    idx->codes.release();
-    idx->labels.release();
-    idx->d_off.release();
-    idx->d_lab_off.release();
+    idx->store.release();
     idx->d_in.release();
     idx->d_vals.release();
     idx->d_keys.release();
@@ -1399,7 +1191,6 @@ int qadc_adc_index_destroy(qadc_adc_index* idx) {
     idx->h_in.release();
     idx->h_count.release();
     idx->h_packed.release();
-    idx->h_add.release();
     idx->d_codebooks.release();
     idx->d_cbnorm.release();
     idx->d_rotation.release();
@@ -1434,7 +1225,8 @@ int qadc_adc_index_add_partitions(qadc_adc_index* idx, int part_count, const uin
         if (lab == -1) lab = has;
         else if (lab != has) return fail(QADC_E_ARG, "Some partitions have labels and some have not");
     }
-    uint64_t bytes = idx->code_bytes, nlab = idx->label_count;
+    RowStore& st = idx->store;
+    uint64_t bytes = st.code_bytes, nlab = st.label_count;
     std::vector<uint64_t> off(part_count), loff(part_count);
     for (int p = 0; p < part_count; ++p) {
         off[p] = bytes;
@@ -1442,30 +1234,30 @@ int qadc_adc_index_add_partitions(qadc_adc_index* idx, int part_count, const uin
         bytes += align_up((uint64_t)sizes[p] * idx->code_size(), 16);
         if (lab == 1) nlab += sizes[p];
     }
-    if (int rc = grow_device(idx->codes, idx->code_bytes, bytes + 16, idx->stream)) return rc;
+    if (int rc = grow_device(st.codes, st.code_bytes, bytes + 16, idx->stream)) return rc;
     if (lab == 1)
-        if (int rc = grow_device(idx->labels, idx->label_count, std::max<uint64_t>(nlab, 1), idx->stream)) return rc;
+        if (int rc = grow_device(st.labels, st.label_count, std::max<uint64_t>(nlab, 1), idx->stream)) return rc;
     for (int p = 0; p < part_count; ++p) {
         if (!sizes[p]) continue;
-        HIPCHECK(hipMemcpy(idx->codes.p + off[p], codes[p], (size_t)sizes[p] * idx->code_size(), hipMemcpyHostToDevice));
-        if (lab == 1) HIPCHECK(hipMemcpy(idx->labels.p + loff[p], labels[p], (size_t)sizes[p] * 4, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(st.codes.p + off[p], codes[p], (size_t)sizes[p] * idx->code_size(), hipMemcpyHostToDevice));
+        if (lab == 1) HIPCHECK(hipMemcpy(st.labels.p + loff[p], labels[p], (size_t)sizes[p] * 4, hipMemcpyHostToDevice));
     }
-    HIPCHECK(hipMemset(idx->codes.p + bytes, 0, 16));
+    HIPCHECK(hipMemset(st.codes.p + bytes, 0, 16));
     idx->labeled = lab;
-    idx->code_bytes = bytes;
-    idx->label_count = nlab;
+    st.code_bytes = bytes;
+    st.label_count = nlab;
     for (int p = 0; p < part_count; ++p) {
         idx->sizes.push_back(sizes[p]);
-        idx->caps.push_back(sizes[p]);   // (the region is the aligned size: an append to it relocates)
-        idx->off.push_back(off[p]);
-        idx->lab_off.push_back(loff[p]);
+        st.caps.push_back(sizes[p]);   // (the region is the aligned size: an append to it relocates)
+        st.off.push_back(off[p]);
+        st.lab_off.push_back(loff[p]);
     }
     const size_t np = idx->sizes.size();
-    HIPCHECK(idx->d_off.ensure(std::max<size_t>(np, 1)));
-    HIPCHECK(idx->d_lab_off.ensure(std::max<size_t>(np, 1)));
+    HIPCHECK(st.d_off.ensure(std::max<size_t>(np, 1)));
+    HIPCHECK(st.d_lab_off.ensure(std::max<size_t>(np, 1)));
     if (np) {
-        HIPCHECK(hipMemcpy(idx->d_off.p, idx->off.data(), np * 8, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(idx->d_lab_off.p, idx->lab_off.data(), np * 8, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(st.d_off.p, st.off.data(), np * 8, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(st.d_lab_off.p, st.lab_off.data(), np * 8, hipMemcpyHostToDevice));
     }
     return QADC_OK;
 }
@@ -1498,50 +1290,20 @@ int qadc_adc_index_remove_labels_device(qadc_adc_index* idx, const uint32_t* d_l
 int qadc_adc_index_read_partition(qadc_adc_index* idx, int part, uint32_t first, uint32_t count, uint8_t* codes_out, uint32_t* labels_out) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
     if (int rc = refuse_on_view(idx, "qadc_adc_index_read_partition")) return rc;
-    if (part < 0 || part >= (int)idx->sizes.size())
-        return fail(QADC_E_ARG, "partition " + std::to_string(part) + " does not exist (" + std::to_string(idx->sizes.size()) + " partitions)");
-    if ((uint64_t)first + count > idx->sizes[part])
-        return fail(QADC_E_ARG, "rows [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) + ") are outside partition " +
-                                    std::to_string(part) + " of " + std::to_string(idx->sizes[part]) + " codes");
-    if (!count) return QADC_OK;
-    DeviceGuard guard;
-    HIPCHECK(hipSetDevice(idx->device));
-    const size_t cs = (size_t)idx->code_size();
-    if (codes_out)
-        HIPCHECK(hipMemcpyAsync(codes_out, idx->codes.p + idx->off[part] + first * cs, count * cs, hipMemcpyDeviceToHost, idx->stream));
-    if (labels_out && idx->labeled == 1)
-        HIPCHECK(hipMemcpyAsync(labels_out, idx->labels.p + idx->lab_off[part] + first, (size_t)count * 4, hipMemcpyDeviceToHost, idx->stream));
-    HIPCHECK(hipStreamSynchronize(idx->stream));
-    return QADC_OK;
+    const AppendJob job = make_job(idx, 1);
+    const bool exists = part >= 0 && part < (int)idx->sizes.size();
+    return read_rows(job, part, first, count, exists ? idx->store.part_codes(part) : nullptr,
+                     exists && idx->labeled == 1 ? idx->store.part_labels(part) : nullptr, codes_out, labels_out);
 }
 
 int qadc_adc_index_reserve(qadc_adc_index* idx, int part_count, const uint32_t* capacities) {
     if (!idx) return fail(QADC_E_ARG, "index is null");
     if (int rc = refuse_on_view(idx, "qadc_adc_index_reserve")) return rc;
-    if (part_count < 0 || (part_count > 0 && !capacities)) return fail(QADC_E_ARG, "bad capacity array");
-    DeviceGuard guard;
-    HIPCHECK(hipSetDevice(idx->device));
-    const size_t before = idx->sizes.size(), parts = std::max(before, (size_t)part_count);
-    std::vector<uint32_t> floor(parts, 0);
-    std::copy(capacities, capacities + part_count, floor.begin());
-    idx->sizes.resize(parts, 0);
-    idx->caps.resize(parts, 0);
-    idx->off.resize(parts, idx->code_bytes);
-    idx->lab_off.resize(parts, idx->label_count);
-    const std::vector<uint64_t> add(parts, 0);
-    const AppendPlan plan = plan_append(idx->code_size(), parts, idx->sizes.data(), idx->caps.data(), add.data(), floor.data(), false);
-    int rc = plan.refused.empty() ? QADC_OK : fail(QADC_E_ARG, plan.refused);
-    if (rc == QADC_OK && (!plan.in_place || parts != before)) rc = relocate(idx, plan, idx->labeled == 1);
-    if (rc != QADC_OK) {
-        idx->sizes.resize(before);
-        idx->caps.resize(before);
-        idx->off.resize(before);
-        idx->lab_off.resize(before);
-    }
-    return rc;
+    AppendJob job = make_job(idx, 1);
+    return reserve_rows(job, part_count, capacities);
 }
 
-uint64_t qadc_adc_index_relocations(const qadc_adc_index* idx) { return idx ? idx->relocations : 0; }
+uint64_t qadc_adc_index_relocations(const qadc_adc_index* idx) { return idx ? idx->store.relocations : 0; }
 
 int qadc_adc_index_partition_count(const qadc_adc_index* idx) { return idx ? (int)idx->sizes.size() : 0; }
 

@@ -1267,6 +1267,8 @@ int qadc_index_create(qadc_index** out, int M, int device_id) {
     qadc_index* idx = new qadc_index();
     idx->M = M;
     idx->cs = M / 2;
+    idx->arena.code_size = idx->cs;
+    idx->arena.region_pad = qadc::adc::kIndexRegionPad;
     if (M == 16) idx->head_wg = 512;                           // the partition-major batches' head at 16x4: 8 waves per query (same-box A/B,
                                                                // profiles/r06_head_wg_ab.txt: C3 0.656 -> 0.612 us per query; 32x4 keeps 16 waves)
     idx->device = device_id;

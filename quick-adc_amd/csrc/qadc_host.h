@@ -4,7 +4,8 @@
 //   qadc_ivf.cpp    one-workgroup-per-query batches, partition-major second phase, device-side feeders (qadc_search)
 //   qadc_dist.cpp   native multi-GPU merge (qadc_dist_*: RCCL by dlopen, or a caller-supplied all-gather)
 //   qadc_build.cpp  database build entry points (PQ / IVF encode, k-means iterations)
-//   qadc_index_add.cpp  db_add on the index: qadc_index_add_vectors, _reserve, _read_partition (storage that grows)
+//   qadc_index_add.cpp  db_add on the index: qadc_index_add_vectors, _reserve, _read_partition (RowStore; the flow is qadc_append.h)
+//   qadc_adc.cpp    the float-ADC engine, which keeps its owned database in a RowStore too
 // The level-path planner itself (items, launches, plan_levels) is host/level_plan.hpp: no HIP, checked on a CPU.
 // The last three keep their state in structs of their own hung off qadc_index (FeederState, GroupState, DistState).
 #pragma once
@@ -28,6 +29,7 @@
 #include <thread>
 #include <vector>
 
+#include "../host/index_append_plan.hpp"
 #include "../host/qadc_heap.hpp"
 #include "../host/worker_pool.hpp"
 #include "qadc_kernels.h"
@@ -114,7 +116,7 @@ constexpr int kCoarseChunk = 32768;   // vectors per coarse-assignment launch of
 struct Part : LevelPart {           // (the fields the level planner reads: host/level_plan.hpp)
     uint32_t starts_cap = 0;       // codes available for the pre-scan
     bool own = true;
-    bool arena = false;            // d_codes / d_labels point into the index's arena (ArenaState): freed with it, not one by one
+    bool arena = false;            // d_codes / d_labels point into the index's row store (RowStore): freed with it, not one by one
 };
 
 constexpr int kMergeStreams = 3;   // streams the enqueued merges MAY rotate over (measurement hook); the default creates ONE:
@@ -355,18 +357,27 @@ struct FeederState {
     int table_form = 2;          // float tables of qadc_search: 0 direct, 1 BLAS expansion, 2 the reference's nns_engine rule
 };
 
-// The storage that grows (qadc_index_add_vectors, qadc_index_reserve: qadc_index_add.cpp; layout: host/index_append_plan.hpp).
-// Empty until the first of those calls; from then on every partition of the index lies in `codes` / `labels` (Part::arena).
-struct ArenaState {
+// The row store of both engines (the flow over it: csrc/qadc_append.h): the partitions of an index that
+// grows, region after region in one code buffer and one label buffer, in the layout of host/adc_append_plan.hpp.  What tells the
+// two layouts apart is data: the float-ADC engine (csrc/qadc_adc.cpp) has region_pad 0 and kAppendTailPad bytes behind the last
+// region; the 4-bit index (csrc/qadc_index_add.cpp) has region_pad kIndexRegionPad, and bytes [n * code_size,
+// index_padded_end(n * code_size)) of every region are zero whenever a call returns.  The 4-bit index's store is empty until its
+// first growing call (until then its partitions are allocations of their own: Part::arena).
+struct RowStore {
+    int code_size = 0;                 // bytes of a row
+    uint64_t region_pad = 0;           // bytes every code region holds behind its rows
     DevBuf<uint8_t> codes;             // the regions of all partitions, back to back
     DevBuf<uint32_t> labels;           // cap[p] labels per partition (allocated once the index is labelled)
-    DevBuf<uint64_t> d_off, d_lab_off; // [parts] device copies of off / lab_off (AddDst)
+    DevBuf<uint64_t> d_off, d_lab_off; // [parts] device copies of off / lab_off (AddDst, the scan's Db)
     std::vector<uint32_t> caps;        // [parts] rows each region holds
-    std::vector<uint64_t> off, lab_off;
-    uint64_t code_bytes = 0, label_count = 0;
+    std::vector<uint64_t> off, lab_off;   // [parts] byte offset of each partition's codes / its first label
+    uint64_t code_bytes = 0, label_count = 0;   // bytes / labels of all regions
     uint64_t relocations = 0;          // add_vectors calls that moved the database to grow it
-    PinBuf<uint32_t> h_add;            // add_vectors: [counts K + 1 | bases K | sizes K]
+    PinBuf<uint32_t> h_add;            // add_vectors: [counts K + 1 | bases K | sizes K]; remove_labels: [hits | first]
     bool active() const { return codes.p != nullptr; }
+    bool covers(size_t parts) const { return active() && caps.size() == parts; }   // the tables describe `parts` partitions
+    uint8_t* part_codes(size_t p) const { return codes.p + off[p]; }
+    uint32_t* part_labels(size_t p) const { return labels.p + lab_off[p]; }
     void release() {
         codes.release(); labels.release(); d_off.release(); d_lab_off.release(); h_add.release();
         caps.clear(); off.clear(); lab_off.clear();
@@ -513,7 +524,7 @@ struct qadc_index {
     FeederState feed;                   // qadc_ivf.cpp: N1, the feeders on the device
     GroupState group;                   // qadc_ivf.cpp: partition-major second phase of large IVF batches
     DistState* dist = nullptr;          // qadc_dist.cpp: qadc_dist_init
-    ArenaState arena;                   // qadc_index_add.cpp: the partitions of an index that has grown
+    RowStore arena;                     // qadc_index_add.cpp: the partitions of an index that has grown (region_pad kIndexRegionPad)
     int adc_views = 0;                  // qadc_adc.cpp: live float-ADC views reading this index's partitions (qadc_adc_index_create_view);
                                         // qadc_index_destroy refuses while there is one
 };

@@ -1,7 +1,7 @@
 // The append planner of the float-ADC engine: where the partitions of an owned index lie after rows are
-// added to them.  Integer arithmetic on sizes and capacities only.  No HIP here: csrc/qadc_adc.cpp plans every
-// qadc_adc_index_add_vectors pass and every qadc_adc_index_reserve with plan_append, and tests/cpp/adc_append_plan_host.cpp checks
-// the layout's invariants on a CPU.
+// added to them.  Integer arithmetic on sizes and capacities only.  No HIP here: the flow both engines share (csrc/qadc_append.h)
+// plans every add_vectors pass and every reserve with plan_append and takes a pass's row bases from append_bases, and
+// tests/cpp/adc_append_plan_host.cpp checks the layout's invariants and the bases on a CPU.
 //
 // Layout: partition p owns cap[p] code rows at byte offset off[p] of the code buffer and cap[p] labels from label lab_off[p];
 // regions follow one another in partition order, each code region is align16(cap[p] * code_size) bytes — so every partition
@@ -83,6 +83,17 @@ inline AppendPlan plan_append(int code_size, size_t parts, const uint32_t* sizes
     }
     append_layout(code_size, &p, region_pad);
     return p;
+}
+
+// The bases of one add_vectors pass: sizes [parts] rows held, count [parts] rows the pass adds to each partition.  The scatter
+// kernel (launch_adc_add_scatter) writes the vector at position j of the pass's (assign, i) order to row base[assign] + j, so
+// base[p] is sizes[p] less the vectors of the partitions below p — modulo 2^32, as the kernel adds.
+inline void append_bases(size_t parts, const uint32_t* sizes, const uint32_t* count, uint32_t* base) {
+    uint32_t below = 0;
+    for (size_t p = 0; p < parts; ++p) {
+        base[p] = sizes[p] - below;
+        below += count[p];
+    }
 }
 
 }  // namespace adc

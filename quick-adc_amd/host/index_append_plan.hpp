@@ -1,7 +1,7 @@
 // The append planner of the 4-bit index: where the partitions of a qadc_index lie once they live in the
-// index's arena and rows are added to them.  Integer arithmetic only, no HIP: csrc/qadc_index_add.cpp plans every
-// qadc_index_add_vectors pass and every qadc_index_reserve with plan_index_append, and tests/cpp/index_append_plan_host.cpp
-// checks the layout's invariants on a CPU.
+// index's arena and rows are added to them.  Integer arithmetic only, no HIP: the shared flow (csrc/qadc_append.h) plans every
+// qadc_index_add_vectors pass and every qadc_index_reserve with plan_append at region_pad = kIndexRegionPad — plan_index_append
+// here — and tests/cpp/index_append_plan_host.cpp checks the layout's invariants on a CPU.
 //
 // Layout: the one of host/adc_append_plan.hpp — partition p owns cap[p] >= n rows at byte offset off[p] of the code arena and
 // cap[p] labels from label lab_off[p] of the label arena, regions back to back in partition order, capacities by plan_append's

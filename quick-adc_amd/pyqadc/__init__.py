@@ -861,7 +861,105 @@ def pq_encode_device(codebooks, d_vectors_ptr, n, dim, d_codes_ptr, device=0):
     _check(lib().qadc_pq_encode(cb.shape[0], dim, _p(cb, f32p), C.c_void_p(d_vectors_ptr), n, C.c_void_p(d_codes_ptr), device))
 
 
-class Index:
+class _RowStoreMixin:
+    """db_add and remove by label, the same calls on both engines (DESIGN.md sections 11.5 to 11.7): Index binds them to qadc_index_*,
+    AdcIndex to qadc_adc_index_*.  The class gives _c_prefix, _row_format() -> (values per row, dtype) of read_partition's codes, and
+    _device_vectors(t) -> the checked torch tensor of add_vectors_device."""
+
+    def _c(self, name):
+        return getattr(lib(), self._c_prefix + name)
+
+    # ---- db_add: encode and append on the GPU with the index's own quantizers (*_add_vectors) ----
+    def add_vectors(self, vectors, labels_offset=0, sum_mode=1, labels=None):
+        """vectors [n][dim]: with a coarse quantizer the code of vector i is appended to its nearest centroid's partition with label
+        labels_offset + i (index_db::add_vectors); a flat index writes it at row labels_offset + i of its one partition
+        (flat_db::add_vectors).  labels (a uint32 array [n], any values, repeats allowed; not together with a labels_offset): the
+        label of vector i is labels[i] (*_add_vectors_labelled; an index with a coarse quantizer only).  A 4-bit Index is not
+        finalized afterwards: call finalize before the next query."""
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim == 1:
+            v = v.reshape(-1, getattr(self, "dim", 1))
+        assert v.ndim == 2 and (v.shape[0] == 0 or v.shape[1] == getattr(self, "dim", v.shape[1]))
+        if labels is None:
+            self.add_vectors_raw(v, v.shape[0], labels_offset, sum_mode)
+        else:
+            lab = _add_labels(labels, v.shape[0], labels_offset)
+            _check(self._c("add_vectors_labelled")(self._h, _p(v, f32p), _p(lab, u32p), v.shape[0], sum_mode))
+
+    def add_vectors_raw(self, vectors, count, labels_offset, sum_mode):
+        """The C call as it is (vectors: a float32 array or None)."""
+        _check(self._c("add_vectors")(self._h, _p(vectors, f32p), count, labels_offset, sum_mode))
+
+    def add_vectors_device(self, vectors, labels_offset=0, sum_mode=1, labels=None):
+        """add_vectors for a contiguous float32 torch tensor [n][dim] on the index's device, read where it lies; labels: an int32
+        torch tensor [n] there that carries the labels' uint32 bits."""
+        import torch
+        v = self._device_vectors(vectors)
+        n = int(v.shape[0])
+        torch.cuda.current_stream(v.device).synchronize()                # the vectors are complete before the call
+        if labels is None:
+            _check(self._c("add_vectors_device")(self._h, v.data_ptr(), n, labels_offset, sum_mode))
+        else:
+            lab = _add_labels_tensor(labels, n, labels_offset, self.device)
+            _check(self._c("add_vectors_labelled_device")(self._h, v.data_ptr(), lab.data_ptr(), n, sum_mode))
+
+    def read_partition(self, part, first=0, count=None):
+        """-> (codes, labels uint32 [n] or None on an index without labels): rows [first, first + count) of the partition as they
+        lie in device memory (default: all of it).  codes: uint8 [n][M/2] of an Index, uint8 [n][sq_count] of an AdcIndex — a
+        create16 index: uint16 [n][sq_count]."""
+        if count is None:
+            count = max(self.partition_size(part) - first, 0) if 0 <= part < self.partition_count() else 0
+        width, dtype = self._row_format()
+        codes = np.zeros((count, width), dtype)
+        labels = np.zeros(count, np.uint32) if self._labelled() else None
+        _check(self._c("read_partition")(self._h, part, first, count, _p(codes, u8p), _p(labels, u32p)))
+        return (codes.astype(np.uint16, copy=False) if codes.dtype.itemsize == 2 else codes), labels
+
+    def _labelled(self):
+        """whether the database has labels: the C call fills labels_out only then (probed on the first row the index holds)"""
+        for part in range(self.partition_count()):
+            if self.partition_size(part):
+                seen = []
+                for fill in (0, 1):
+                    one = np.full(1, fill, np.uint32)
+                    _check(self._c("read_partition")(self._h, part, 0, 1, None, _p(one, u32p)))
+                    seen.append(int(one[0]))
+                return seen[0] == seen[1]
+        return False
+
+    def reserve(self, capacities):
+        """minimum capacities, in codes, of the first len(capacities) partitions (empty ones are created where the index has fewer)"""
+        c = np.ascontiguousarray(capacities, np.uint32).reshape(-1)
+        _check(self._c("reserve")(self._h, len(c), _p(c, u32p)))
+
+    def relocations(self):
+        """add_vectors calls that had to move the database to grow it"""
+        return self._c("relocations")(self._h)
+
+    # ---- remove by label: the partitions compacted in place on the GPU (*_remove_labels) ----
+    def remove_labels(self, labels):
+        """Removes every row whose label is in `labels` (anything np.asarray(..., np.uint32) accepts) from whichever partitions
+        hold it; the survivors keep their order.  -> the number of rows removed.  A call that removed a row leaves a 4-bit Index
+        not finalized: call finalize before the next query."""
+        l = np.ascontiguousarray(np.asarray(labels, np.uint32).reshape(-1))
+        return self.remove_labels_raw(l, l.size)
+
+    def remove_labels_raw(self, labels, count):
+        """The C call as it is (labels: a uint32 array or None)."""
+        removed = C.c_uint64(0)
+        _check(self._c("remove_labels")(self._h, _p(labels, u32p), count, C.byref(removed)))
+        return int(removed.value)
+
+    def remove_labels_device(self, labels):
+        """remove_labels for a contiguous 1-d int32 torch tensor on the index's device that carries the labels' uint32 bits — the
+        form in which search_device returns keys — read where it lies."""
+        t = _label_tensor(labels, self.device)
+        removed = C.c_uint64(0)
+        _check(self._c("remove_labels_device")(self._h, t.data_ptr(), int(t.shape[0]), C.byref(removed)))
+        return int(removed.value)
+
+
+class Index(_RowStoreMixin):
     """One GPU-resident Quick-ADC database (the role of scanner_4 after prepare_database)."""
 
     def __init__(self, M, device=0):
@@ -1027,30 +1125,13 @@ class Index:
         _check(lib().qadc_index_read_codes(self._h, part, first, count, _p(out, u8p)))
         return out
 
-    # ---- db_add: encode and append on the GPU with the index's own quantizers (qadc_index_add_vectors) ----
-    def add_vectors(self, vectors, labels_offset=0, sum_mode=1, labels=None):
-        """vectors [n][dim]: with a coarse quantizer the code of vector i is appended to its nearest centroid's partition with label
-        labels_offset + i (index_db::add_vectors); a flat index writes it at row labels_offset + i of its one partition
-        (flat_db::add_vectors).  labels (a uint32 array [n], any values, repeats allowed; not together with a labels_offset): the
-        label of vector i is labels[i] (qadc_index_add_vectors_labelled; an index with a coarse quantizer only).  The index is not
-        finalized afterwards: call finalize before the next query."""
-        v = np.ascontiguousarray(vectors, np.float32)
-        if v.ndim == 1:
-            v = v.reshape(-1, getattr(self, "dim", 1))
-        assert v.ndim == 2 and (v.shape[0] == 0 or v.shape[1] == getattr(self, "dim", v.shape[1]))
-        if labels is None:
-            self.add_vectors_raw(v, v.shape[0], labels_offset, sum_mode)
-        else:
-            lab = _add_labels(labels, v.shape[0], labels_offset)
-            _check(lib().qadc_index_add_vectors_labelled(self._h, _p(v, f32p), _p(lab, u32p), v.shape[0], sum_mode))
+    # ---- db_add and remove by label (qadc_index_add_vectors*, _reserve, _read_partition, _remove_labels*): _RowStoreMixin ----
+    _c_prefix = "qadc_index_"
 
-    def add_vectors_raw(self, vectors, count, labels_offset, sum_mode):
-        """The C call as it is (vectors: a float32 array or None)."""
-        _check(lib().qadc_index_add_vectors(self._h, _p(vectors, f32p), count, labels_offset, sum_mode))
+    def _row_format(self):
+        return self.cs, np.uint8
 
-    def add_vectors_device(self, vectors, labels_offset=0, sum_mode=1, labels=None):
-        """add_vectors for a contiguous float32 torch tensor [n][dim] on the index's device, read where it lies; labels: an int32
-        torch tensor [n] there that carries the labels' uint32 bits."""
+    def _device_vectors(self, vectors):
         import torch
         if not isinstance(vectors, torch.Tensor) or vectors.ndim != 2:
             raise TypeError("vectors must be a 2-d torch.Tensor")
@@ -1062,65 +1143,7 @@ class Index:
             raise QadcError("vectors must be contiguous")
         if vectors.shape[0] and int(vectors.shape[1]) != getattr(self, "dim", int(vectors.shape[1])):
             raise QadcError("vectors has shape %s, expected [n][%d]" % (tuple(vectors.shape), self.dim))
-        torch.cuda.current_stream(vectors.device).synchronize()          # the vectors are complete before the call
-        if labels is None:
-            _check(lib().qadc_index_add_vectors_device(self._h, vectors.data_ptr(), int(vectors.shape[0]), labels_offset, sum_mode))
-        else:
-            lab = _add_labels_tensor(labels, int(vectors.shape[0]), labels_offset, self.device)
-            _check(lib().qadc_index_add_vectors_labelled_device(self._h, vectors.data_ptr(), lab.data_ptr(), int(vectors.shape[0]), sum_mode))
-
-    def read_partition(self, part, first=0, count=None):
-        """-> (codes uint8 [n][M/2], labels uint32 [n] or None on an index without labels): rows [first, first + count) of the
-        partition as they lie in device memory (default: all of it)."""
-        if count is None:
-            count = max(self.partition_size(part) - first, 0) if 0 <= part < self.partition_count() else 0
-        codes = np.zeros((count, self.cs), np.uint8)
-        labels = np.zeros(count, np.uint32) if self._labelled() else None
-        _check(lib().qadc_index_read_partition(self._h, part, first, count, _p(codes, u8p), _p(labels, u32p)))
-        return codes, labels
-
-    def _labelled(self):
-        """whether the database has labels: the C call fills labels_out only then (probed on the first row the index holds)"""
-        for part in range(self.partition_count()):
-            if self.partition_size(part):
-                seen = []
-                for fill in (0, 1):
-                    one = np.full(1, fill, np.uint32)
-                    _check(lib().qadc_index_read_partition(self._h, part, 0, 1, None, _p(one, u32p)))
-                    seen.append(int(one[0]))
-                return seen[0] == seen[1]
-        return False
-
-    def reserve(self, capacities):
-        """minimum capacities, in codes, of the first len(capacities) partitions (empty ones are created where the index has fewer)"""
-        c = np.ascontiguousarray(capacities, np.uint32).reshape(-1)
-        _check(lib().qadc_index_reserve(self._h, len(c), _p(c, u32p)))
-
-    def relocations(self):
-        """add_vectors calls that had to move the database to grow it"""
-        return lib().qadc_index_relocations(self._h)
-
-    # ---- remove by label: the partitions compacted in place on the GPU (qadc_index_remove_labels) ----
-    def remove_labels(self, labels):
-        """Removes every row whose label is in `labels` (anything np.asarray(..., np.uint32) accepts) from whichever partitions
-        hold it; the survivors keep their order.  -> the number of rows removed.  A call that removed a row
-        leaves the index not finalized: call finalize before the next query."""
-        l = np.ascontiguousarray(np.asarray(labels, np.uint32).reshape(-1))
-        return self.remove_labels_raw(l, l.size)
-
-    def remove_labels_raw(self, labels, count):
-        """The C call as it is (labels: a uint32 array or None)."""
-        removed = C.c_uint64(0)
-        _check(lib().qadc_index_remove_labels(self._h, _p(labels, u32p), count, C.byref(removed)))
-        return int(removed.value)
-
-    def remove_labels_device(self, labels):
-        """remove_labels for a contiguous 1-d int32 torch tensor on the index's device that carries the labels' uint32 bits — the
-        form in which search_device returns keys — read where it lies."""
-        t = _label_tensor(labels, self.device)
-        removed = C.c_uint64(0)
-        _check(lib().qadc_index_remove_labels_device(self._h, t.data_ptr(), int(t.shape[0]), C.byref(removed)))
-        return int(removed.value)
+        return vectors
 
     # ---- queries ---------------------------------------------------------------------------
     @staticmethod
@@ -1465,7 +1488,7 @@ class AdcFilter:
             pass
 
 
-class AdcIndex:
+class AdcIndex(_RowStoreMixin):
     """One GPU-resident PQ database with whole-byte codes, scanned with float tables: the role of the reference's
     scanner_simple after prepare_database (db_query.cpp:17-46).  sq_bits 8 with sq_count 4, 8 or 16.
     AdcIndex.create16(sq_count): 16-bit sub-quantizers, sq_count 2, 4 or 8 (scan_standard<uint16_t, NSQ>).
@@ -1600,93 +1623,16 @@ class AdcIndex:
     def partition_size(self, part):
         return lib().qadc_adc_index_partition_size(self._h, part)
 
-    # ---- db_add: encode and append on the GPU with the index's own quantizers (qadc_adc_index_add_vectors) ----
-    def add_vectors(self, vectors, labels_offset=0, sum_mode=1, labels=None):
-        """vectors [n][dim]: with a coarse quantizer the code of vector i is appended to its nearest centroid's partition with label
-        labels_offset + i (index_db::add_vectors); a flat index writes it at row labels_offset + i of its one partition
-        (flat_db::add_vectors).  labels (a uint32 array [n], any values, repeats allowed; not together with a labels_offset): the
-        label of vector i is labels[i] (qadc_adc_index_add_vectors_labelled; an index with a coarse quantizer only)."""
-        v = np.ascontiguousarray(vectors, np.float32)
-        if v.ndim == 1:
-            v = v.reshape(-1, getattr(self, "dim", 1))
-        assert v.ndim == 2 and (v.shape[0] == 0 or v.shape[1] == getattr(self, "dim", v.shape[1]))
-        if labels is None:
-            self.add_vectors_raw(v, v.shape[0], labels_offset, sum_mode)
-        else:
-            lab = _add_labels(labels, v.shape[0], labels_offset)
-            _check(lib().qadc_adc_index_add_vectors_labelled(self._h, _p(v, f32p), _p(lab, u32p), v.shape[0], sum_mode))
+    # ---- db_add and remove by label (qadc_adc_index_add_vectors*, _reserve, _read_partition, _remove_labels*): _RowStoreMixin ----
+    _c_prefix = "qadc_adc_index_"
 
-    def add_vectors_raw(self, vectors, count, labels_offset, sum_mode):
-        """The C call as it is (vectors: a float32 array or None)."""
-        _check(lib().qadc_adc_index_add_vectors(self._h, _p(vectors, f32p), count, labels_offset, sum_mode))
+    def _row_format(self):
+        return self.sq_count, ("<u2" if self.centroids == 65536 else np.uint8)
 
-    def add_vectors_device(self, vectors, labels_offset=0, sum_mode=1, labels=None):
-        """add_vectors for a float32 torch tensor [n][dim] on the index's device, read where it lies; labels: an int32 torch tensor
-        [n] there that carries the labels' uint32 bits."""
+    def _device_vectors(self, vectors):
         if getattr(vectors, "ndim", 0) != 2:
             raise TypeError("vectors must be a 2-d torch.Tensor")
-        n = int(vectors.shape[0])
-        v = self._device_tensor(vectors, (n, getattr(self, "dim", int(vectors.shape[1]))), "vectors")
-        import torch
-        torch.cuda.current_stream(v.device).synchronize()                # the vectors are complete before the call
-        if labels is None:
-            _check(lib().qadc_adc_index_add_vectors_device(self._h, v.data_ptr(), n, labels_offset, sum_mode))
-        else:
-            lab = _add_labels_tensor(labels, n, labels_offset, self.device)
-            _check(lib().qadc_adc_index_add_vectors_labelled_device(self._h, v.data_ptr(), lab.data_ptr(), n, sum_mode))
-
-    def read_partition(self, part, first=0, count=None):
-        """-> (codes uint8 [n][sq_count] — a create16 index: uint16 [n][sq_count] —, labels uint32 [n] or None on an index without
-        labels): rows [first, first + count) of the partition as they lie in device memory (default: all of it)."""
-        if count is None:
-            count = max(self.partition_size(part) - first, 0) if 0 <= part < self.partition_count() else 0
-        wide = self.centroids == 65536
-        codes = np.zeros((count, self.sq_count), "<u2" if wide else np.uint8)
-        labels = np.zeros(count, np.uint32) if self._labelled() else None
-        _check(lib().qadc_adc_index_read_partition(self._h, part, first, count, codes.ctypes.data_as(u8p), _p(labels, u32p)))
-        return (codes.astype(np.uint16, copy=False) if wide else codes), labels
-
-    def _labelled(self):
-        """whether the database has labels: the C call fills labels_out only then (probed on the first row the index holds)"""
-        for part in range(self.partition_count()):
-            if self.partition_size(part):
-                seen = []
-                for fill in (0, 1):
-                    one = np.full(1, fill, np.uint32)
-                    _check(lib().qadc_adc_index_read_partition(self._h, part, 0, 1, None, _p(one, u32p)))
-                    seen.append(int(one[0]))
-                return seen[0] == seen[1]
-        return False
-
-    def reserve(self, capacities):
-        """minimum capacities, in codes, of the first len(capacities) partitions (empty ones are created where the index has fewer)"""
-        c = np.ascontiguousarray(capacities, np.uint32).reshape(-1)
-        _check(lib().qadc_adc_index_reserve(self._h, len(c), _p(c, u32p)))
-
-    def relocations(self):
-        """add_vectors calls that had to move the database to grow it"""
-        return lib().qadc_adc_index_relocations(self._h)
-
-    # ---- remove by label: the partitions compacted in place on the GPU (qadc_adc_index_remove_labels) ----
-    def remove_labels(self, labels):
-        """Removes every row whose label is in `labels` (anything np.asarray(..., np.uint32) accepts) from whichever partitions
-        hold it; the survivors keep their order.  -> the number of rows removed."""
-        l = np.ascontiguousarray(np.asarray(labels, np.uint32).reshape(-1))
-        return self.remove_labels_raw(l, l.size)
-
-    def remove_labels_raw(self, labels, count):
-        """The C call as it is (labels: a uint32 array or None)."""
-        removed = C.c_uint64(0)
-        _check(lib().qadc_adc_index_remove_labels(self._h, _p(labels, u32p), count, C.byref(removed)))
-        return int(removed.value)
-
-    def remove_labels_device(self, labels):
-        """remove_labels for a contiguous 1-d int32 torch tensor on the index's device that carries the labels' uint32 bits — the
-        form in which search_device returns keys — read where it lies."""
-        t = _label_tensor(labels, self.device)
-        removed = C.c_uint64(0)
-        _check(lib().qadc_adc_index_remove_labels_device(self._h, t.data_ptr(), int(t.shape[0]), C.byref(removed)))
-        return int(removed.value)
+        return self._device_tensor(vectors, (int(vectors.shape[0]), getattr(self, "dim", int(vectors.shape[1]))), "vectors")
 
     def reruns(self):
         """query calls on this index that were re-run because a candidate region overflowed"""

@@ -6,7 +6,9 @@
 //   out: steps x { int32 status (0 in place, 1 moved, 2 refused) | unless refused: uint32 cap[parts] | uint64 off[parts]
 //        | uint64 lab_off[parts] | uint64 code_bytes, label_count }
 // A refused step changes nothing.  stdout: "ok", then one line "refused <step>: <message>" per refused step.
+//   bases <sizes: a,b,...> <counts: a,b,...>: the bases of one add_vectors pass (append_bases), one per line on stdout.
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -19,7 +21,25 @@ static bool get(FILE* f, std::vector<T>& v) { return v.empty() || fread(v.data()
 template <typename T>
 static bool put(FILE* f, const std::vector<T>& v) { return v.empty() || fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
 
+static std::vector<uint32_t> list(const std::string& s) {
+    std::vector<uint32_t> v;
+    for (size_t at = 0; at <= s.size();) {
+        const size_t comma = s.find(',', at) == std::string::npos ? s.size() : s.find(',', at);
+        v.push_back((uint32_t)std::strtoull(s.substr(at, comma - at).c_str(), nullptr, 10));
+        at = comma + 1;
+    }
+    return v;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 4 && std::string(argv[1]) == "bases") {
+        const std::vector<uint32_t> sizes = list(argv[2]), count = list(argv[3]);
+        if (sizes.size() != count.size()) return 2;
+        std::vector<uint32_t> base(sizes.size());
+        append_bases(sizes.size(), sizes.data(), count.data(), base.data());
+        for (uint32_t b : base) printf("%u\n", b);
+        return 0;
+    }
     if (argc != 3) return 2;
     FILE* in = fopen(argv[1], "rb");
     std::vector<int32_t> head(3);

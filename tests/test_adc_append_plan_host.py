@@ -170,3 +170,30 @@ def test_totals_over_2_32_minus_1_are_refused(driver, tmp_path, code_size):
     assert plans[1] == ("refused", REFUSAL % (0, LIMIT + 1))
     assert plans[2][0] == "refused"
     assert isinstance(plans[3], dict) and plans[3]["moved"]
+
+
+def bases(exe, sizes, counts):
+    out = subprocess.run([exe, "bases", ",".join(map(str, sizes)), ",".join(map(str, counts))], stdout=subprocess.PIPE, timeout=60)
+    assert out.returncode == 0
+    return [int(l) for l in out.stdout.decode().split()]
+
+
+def test_pass_bases_place_every_vector_behind_its_partition_s_rows(driver):
+    """append_bases: the vector at position j of a pass's (assign, i) order goes to row base[assign] + j modulo 2^32, which must be
+    the next free row of its partition — also where the running sum of the counts, or a base itself, wraps."""
+    rng = np.random.default_rng(11)
+    cases = [([0, 0, 0], [0, 0, 0]), ([5], [7]), ([3, 0, 9, 1], [2, 0, 0, 4]),
+             ([0, 1, 0], [10, 10, 10]),                              # a base below zero: wraps, and comes back with j
+             ([LIMIT - 6, 0, 7], [6, LIMIT, 5]),                     # the running sum of the counts passes 2^32
+             ([LIMIT - 1, LIMIT - 1], [1, 1])]
+    cases += [(rng.integers(0, 2 ** 31, 9).tolist(), rng.integers(0, 2 ** 30, 9).tolist()) for _ in range(4)]
+    for sizes, counts in cases:
+        got = bases(driver, sizes, counts)
+        assert len(got) == len(sizes)
+        below = 0
+        for p, (n, c) in enumerate(zip(sizes, counts)):
+            assert got[p] == (n - below) % 2 ** 32
+            assert (got[p] + below) % 2 ** 32 == n                   # the partition's first vector lands on its first free row
+            if c:
+                assert (got[p] + below + c - 1) % 2 ** 32 == (n + c - 1) % 2 ** 32
+            below += c

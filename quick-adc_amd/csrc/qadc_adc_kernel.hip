@@ -238,7 +238,9 @@ __device__ __forceinline__ void adc_scan_body(const Item* __restrict__ items, ui
             } else {
                 v = Code::template add<SUM>(t[u]);
             }
-            bool keep = valid[u] && v < b;                        // NaN, +inf and FLT_MAX never pass (b <= FLT_MAX)
+            bool keep = valid[u] && v < b;                        // a NaN v or b and v = +inf never pass.  Top-R: b <= FLT_MAX, so FLT_MAX
+                                                                  // does not either; range: b is the radius, any float, and under
+                                                                  // +inf FLT_MAX passes, under NaN and -inf nothing, -inf under the rest
             [[maybe_unused]] uint32_t key = 0;
             if constexpr (Filter::kOn) {                          // ahead of the ballot and the count: a dropped row is in no level's
                 if (keep) {                                       // stored values, so no bound ever comes from it; a lane that fails the

@@ -4,9 +4,11 @@ restatement tests/adc_range_cases.py, keys and value bit patterns compared exact
 
 Shapes 8x8, 16x4 (nibbles) and 4x16; labelled and unlabelled partitions; all four filter mode pairs and empty filter sets; the radii
 NaN, -inf, +inf, FLT_MAX, a value present in the data (the strict compare excludes it) and its nextafter (which includes it); tables
-holding NaN, +inf, -0 and +0."""
+holding NaN, +inf, -0 and +0; and the cases tests/test_gpu_adc_range_edges.py runs on the device (digit_case, signed_case, nonfinite_case), so that
+the twin is held to the restatement on them before a GPU is."""
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -153,7 +155,7 @@ def test_tables_with_nan_inf_and_signed_zeros_and_tied_rows(driver, tmp_path, sh
     zeros = v[v == 0]
     assert np.signbit(zeros).any() and not np.signbit(zeros).all(), "both zeros occur among the candidates"
     cases = [dict(shape=shape, parts=parts, labels=labels, tables=tables, radius=r, sum_mode=sm)
-             for sm in (1, 0) for r in (INF, FLT_MAX, np.float32(0.0), np.float32(-0.0), np.float32(1e-45), np.float32(2.0), np.float32(np.nan))]
+             for sm in (1, 0) for r in (INF, FLT_MAX, np.float32(0.0), np.float32(-0.0), rc.TINY, np.float32(2.0), np.float32(np.nan))]
     got = check(driver, tmp_path, cases)
     keys, vals = got[0]
     assert len(keys) == int((v < INF).sum()) and not np.isnan(vals).any() and not np.isposinf(vals).any()
@@ -163,6 +165,78 @@ def test_tables_with_nan_inf_and_signed_zeros_and_tied_rows(driver, tmp_path, sh
     assert sign.any() and not sign.all() and (sign[:-1] >= sign[1:]).all(), "every -0 sorts before every +0"
     assert np.array_equal(got[2][0], got[3][0]), "radius +0 and -0 compare alike"
     assert len(got[2][0]) and (got[2][1] < 0).all(), "radius 0 keeps the negative candidates and neither zero"
+
+
+# ---- the builders the GPU edge tests share: the twin on their inputs -------------------------------------------------------------------
+
+@pytest.mark.parametrize("shape", SHAPES, ids=fc.shape_id)
+def test_the_twin_on_segments_that_differ_in_chosen_sort_digits(driver, tmp_path, shape):
+    """every mask, at the length that takes the device's radix passes and at the one that sorts in LDS, under both groupings"""
+    cases = [c for mask in rc.DIGIT_MASKS for n in (6000, 3000) for sm in (1, 0) for c in rc.queries_of(rc.digit_case(shape, mask, n), sm)]
+    got = check(driver, tmp_path, cases)
+    assert [len(g[0]) for g in got] == [6000, 6000, 3000, 3000] * len(rc.DIGIT_MASKS), "radius +inf keeps every row"
+    masks = [rc.active_digits(rc.words(g[0], g[1])) for g in got[::4]]
+    assert masks == rc.DIGIT_MASKS, "the twin's own rows differ in the digits %s" % [hex(m) for m in masks]
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=fc.shape_id)
+def test_the_twin_on_candidates_of_both_signs_signed_zeros_and_subnormals(driver, tmp_path, shape):
+    case = rc.signed_case(shape)
+    got = check(driver, tmp_path, rc.queries_of(case, 1) + rc.queries_of(case, 0))
+    assert len(got[0][0]) > rc.RANGE_SORT_LDS > len(got[1][0])
+    for keys, vals in got[:3]:                                   # sum_mode 1: the all -0 row before the all +0 row of the same label
+        twins = vals[(vals.view(np.uint32) << 1 == 0) & (keys == rc.SIGNED_TWIN)]   # (bits: a process may compare subnormals equal to 0)
+        assert list(np.signbit(twins)) == [True, False]
+        assert (vals[:-1] <= vals[1:]).all() and vals[0] < 0 < vals[-1]
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=fc.shape_id)
+def test_the_twin_on_nan_infinite_and_flt_max_candidates_at_every_radius(driver, tmp_path, shape):
+    case = rc.nonfinite_case(shape)
+    batch = rc.nonfinite_batch(case, case["radii"])
+    got = check(driver, tmp_path, rc.queries_of(batch, 1) + rc.queries_of(batch, 0))
+    n = len(case["radii"])
+    for sm in (0, 1):
+        rows = dict(zip(["inf", "max", "below", "nan", "-inf", "0", "-0", "tiny"], got[sm * n:(sm + 1) * n]))
+        assert (rows["inf"][1] == FLT_MAX).sum() == 1 and (rows["max"][1] == FLT_MAX).sum() == 0, "FLT_MAX passes under +inf alone"
+        assert len(rows["inf"][0]) == len(rows["max"][0]) + 1 == len(rows["below"][0]) + 1
+        assert len(rows["nan"][0]) == 0 and len(rows["-inf"][0]) == 0
+        assert np.isneginf(rows["0"][1]).any() and (rows["0"][1] < 0).all() and np.array_equal(rows["0"][0], rows["-0"][0])
+        assert len(rows["tiny"][0]) > len(rows["0"][0]) and (rows["tiny"][1] <= 0).all(), "1e-45 keeps the zeros too"
+
+
+def test_the_restatement_keeps_subnormals_after_a_fast_math_library_is_loaded(tmp_path):
+    """a shared library linked with -ffast-math turns on flush-to-zero in the thread that loads it (the reference build does, in the
+    test process); rc.ieee keeps the restatement's sums and compares IEEE 754 all the same, and leaves the caller's mode as it was"""
+    so = str(tmp_path / "libfast.so")
+    src = tmp_path / "fast.c"
+    src.write_text("int qadc_test_fast_math_marker(void) { return 1; }\n")
+    subprocess.check_call(["gcc", "-shared", "-fPIC", "-O2", "-ffast-math", str(src), "-o", so])
+    script = """
+import ctypes, sys
+import numpy as np
+sys.path.insert(0, %r)
+import adc_range_cases as rc
+one = np.array([1, 0x80000003], np.uint32).view(np.float32)              # 2^-149 and -3 x 2^-149
+table = np.zeros((2, 256), np.float32)
+table[0, :2] = one
+codes = np.array([[0, 5], [1, 5]], np.uint8)
+plain = lambda: (one + np.float32(0)).view(np.uint32).tolist()
+before = plain()
+ctypes.CDLL(%r)
+flushed = plain()
+for sum_mode in (1, 0):
+    v = rc.candidates((2, 8), codes, table, sum_mode)
+    assert v.view(np.uint32).tolist() == [1, 0x80000003], v
+    keys, vals = rc.expected((2, 8), [codes], [np.array([8, 9], np.uint32)], table, rc.TINY, sum_mode=sum_mode)
+    assert keys.tolist() == [9] and vals.view(np.uint32).tolist() == [0x80000003], (keys, vals)
+assert plain() == flushed, "the caller's mode is restored"
+print(before == [1, 0x80000003], flushed != before)
+""" % (os.path.join(ROOT, "tests"), so)
+    out = subprocess.run([sys.executable, "-W", "ignore", "-c", script], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert out.returncode == 0, out.stderr.decode()
+    ieee_before, _library_flushes = out.stdout.decode().split()           # (a toolchain whose library does not flush: the asserts above hold anyway)
+    assert ieee_before == "True", "a fresh process adds subnormals as IEEE 754 does"
 
 
 def test_the_driver_is_clean_under_address_and_undefined_sanitizers(tmp_path):

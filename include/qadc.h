@@ -32,6 +32,27 @@ const char* qadc_last_error(void);
 const char* qadc_version(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * Device pointers of the caller (every parameter named d_*): memory behaviour.
+ * A call reads the documented extent of its inputs and nothing else of the caller's, writes every element the comment of the
+ * entry point lists as an output and no other byte, and a refused call (QADC_E_ARG, QADC_E_STATE, or QADC_E_CAPACITY from a
+ * *_collect* / *_candidates call whose buffer is too small) writes no caller buffer but the `offsets` / `lims` arrays documented
+ * for that case.  Such buffers are only ever touched by kernels, never by a memcpy of this library's HIP runtime, so they may
+ * belong to another copy of the runtime (a framework's allocator).
+ * Alignment: a kernel dereferences each pointer as a type of the size below, so the ADDRESS must be a multiple of it.  A pointer
+ * that is not is refused with QADC_E_ARG ("<name> must be <n>-byte aligned") before any HIP call; nothing is written and the index
+ * or store answers as before.  A slice of a larger allocation is a legal argument as long as its first byte obeys the table.
+ *   16 bytes  d_tables    qadc_adc_query_scan_device(_filtered), qadc_adc_range_scan_device: the scan stages a table with 16-byte loads
+ *             d_vectors   qadc_adc_index_add_vectors_device, _labelled_device, qadc_pq_train16_device: the 16-bit encoder loads a
+ *                         sub-vector 16 bytes at a time (stated for every float-ADC index, whatever its code width)
+ *             d_codes     qadc_index_add_partition_device: a borrowed partition (readable up to size * M/2 rounded up to 16 bytes)
+ *    4 bytes  every other float, uint32 and int32 array: d_queries, d_keys, d_values, d_sizes, d_labels, d_counts, d_out_keys,
+ *             d_out_dist, d_out_sizes, and d_vectors of qadc_index_add_vectors_device, _labelled_device, qadc_refine_add_device,
+ *             qadc_refine_put_device, qadc_pq_encode(_mode), qadc_pq_train_device, qadc_opq_cross_device, qadc_opq_train_device
+ *    1 byte   d_codes of qadc_pq_encode(_mode): [n][M/2] bytes, each written by itself
+ * Host arrays carry no such requirement beyond their element type's.
+ * ------------------------------------------------------------------------------------------- */
+
+/* ---------------------------------------------------------------------------------------------
  * Database side — replaces scanner_4::prepare_database (db_query_4.cpp:210-228) and the layout
  * step interleave_partition_4 (simd_layout.hpp:55-65).  The device layout is plain row-major
  * [n][M/2] (one coalesced 16-byte load per lane); the 16-code block transpose is an AVX2 need.

@@ -687,6 +687,13 @@ int check_query_filters(const qadc_adc_index* idx, int nq, const qadc_adc_filter
     return QADC_OK;
 }
 
+// The heaps' arrays in the caller's device memory: written word by word (adc_replay_kernel, adc_copy_words_kernel).
+int check_device_heaps(const uint32_t* d_keys, const float* d_values, const int32_t* d_sizes) {
+    if (int rc = check_aligned(d_keys, 4, "d_keys")) return rc;
+    if (int rc = check_aligned(d_values, 4, "d_values")) return rc;
+    return check_aligned(d_sizes, 4, "d_sizes");
+}
+
 // The six scanning calls, each entered by its plain form (filters null) and by its _filtered form.
 int query_scan_call(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* tables, int R, int sum_mode, uint32_t* keys,
                     float* values, int32_t* sizes, const qadc_adc_filter* const* filters) {
@@ -697,6 +704,8 @@ int query_scan_call(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, 
 
 int query_scan_device_call(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, int R, int sum_mode,
                            uint32_t* d_keys, float* d_values, int32_t* d_sizes, const qadc_adc_filter* const* filters) {
+    if (int rc = check_aligned(d_tables, 16, "d_tables")) return rc;   // (adc_scan_body stages a table with 16-byte loads)
+    if (int rc = check_device_heaps(d_keys, d_values, d_sizes)) return rc;
     if (int rc = check_query_filters(idx, nq, filters)) return rc;
     return heaps_to_device(idx, nq, R, d_keys, d_values, d_sizes,
                            [&](const DeviceOut* out) { return scan_batch(idx, nq, ma, assign, nullptr, d_tables, R, sum_mode, out, filters); });
@@ -720,6 +729,8 @@ int search_call(qadc_adc_index* idx, int nq, const float* queries, int ma, int R
 
 int search_device_call(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int R, int table_form, int sum_mode, uint32_t* d_keys,
                        float* d_values, int32_t* d_sizes, const qadc_adc_filter* const* filters) {
+    if (int rc = check_aligned(d_queries, 4, "d_queries")) return rc;
+    if (int rc = check_device_heaps(d_keys, d_values, d_sizes)) return rc;
     if (int rc = check_query_filters(idx, nq, filters)) return rc;
     return heaps_to_device(idx, nq, R, d_keys, d_values, d_sizes, [&](const DeviceOut* out) {
         return search_batch(idx, nq, d_queries, ma, R, table_form, sum_mode, nullptr, out, true, filters);
@@ -995,6 +1006,8 @@ int create_filter(qadc_adc_filter** out, int mode, const uint32_t* keys, uint64_
     if (mode != QADC_ADC_FILTER_EXCLUDE && mode != QADC_ADC_FILTER_ALLOW)
         return fail(QADC_E_ARG, "filter mode is 0 (QADC_ADC_FILTER_EXCLUDE) or 1 (QADC_ADC_FILTER_ALLOW)");
     if (count && !keys) return fail(QADC_E_ARG, "keys is null");
+    if (d_side)
+        if (int rc = check_aligned(keys, 4, "d_keys")) return rc;
     DeviceGuard guard;
     if (int rc = qadc_device_prepare(device_id)) return rc;
     HIPCHECK(hipSetDevice(device_id));
@@ -1267,6 +1280,7 @@ int qadc_adc_index_add_vectors(qadc_adc_index* idx, const float* vectors, uint64
 }
 
 int qadc_adc_index_add_vectors_device(qadc_adc_index* idx, const float* d_vectors, uint64_t count, uint32_t labels_offset, int sum_mode) {
+    if (int rc = check_aligned(d_vectors, 16, "d_vectors")) return rc;   // (adc_encode16_kernel loads a lane's sub-vector 16 bytes at a time)
     return add_vectors(idx, d_vectors, nullptr, false, count, labels_offset, sum_mode, true, "qadc_adc_index_add_vectors_device");
 }
 
@@ -1276,6 +1290,8 @@ int qadc_adc_index_add_vectors_labelled(qadc_adc_index* idx, const float* vector
 
 int qadc_adc_index_add_vectors_labelled_device(qadc_adc_index* idx, const float* d_vectors, const uint32_t* d_labels, uint64_t count,
                                                int sum_mode) {
+    if (int rc = check_aligned(d_vectors, 16, "d_vectors")) return rc;
+    if (int rc = check_aligned(d_labels, 4, "d_labels")) return rc;
     return add_vectors(idx, d_vectors, d_labels, true, count, 0, sum_mode, true, "qadc_adc_index_add_vectors_labelled_device");
 }
 
@@ -1284,6 +1300,7 @@ int qadc_adc_index_remove_labels(qadc_adc_index* idx, const uint32_t* labels, ui
 }
 
 int qadc_adc_index_remove_labels_device(qadc_adc_index* idx, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out) {
+    if (int rc = check_aligned(d_labels, 4, "d_labels")) return rc;
     return remove_labels(idx, d_labels, count, removed_out, true, "qadc_adc_index_remove_labels_device");
 }
 
@@ -1463,6 +1480,7 @@ int qadc_adc_range_scan(qadc_adc_index* idx, int nq, int ma, const int32_t* assi
 int qadc_adc_range_scan_device(qadc_adc_index* idx, int nq, int ma, const int32_t* assign, const float* d_tables, const float* radius,
                                int sum_mode, const qadc_adc_filter* const* filters, uint64_t* lims) {
     if (!d_tables) return fail(QADC_E_ARG, "assign and tables are required");
+    if (int rc = check_aligned(d_tables, 16, "d_tables")) return rc;
     return range_scan_call(idx, nq, ma, assign, nullptr, d_tables, radius, sum_mode, filters, lims);
 }
 
@@ -1473,6 +1491,7 @@ int qadc_adc_range_search(qadc_adc_index* idx, int nq, const float* queries, int
 
 int qadc_adc_range_search_device(qadc_adc_index* idx, int nq, const float* d_queries, int ma, const float* radius, int table_form,
                                  int sum_mode, const qadc_adc_filter* const* filters, int32_t* assign_out, uint64_t* lims) {
+    if (int rc = check_aligned(d_queries, 4, "d_queries")) return rc;
     return range_search_call(idx, nq, d_queries, ma, radius, table_form, sum_mode, filters, assign_out, lims, true);
 }
 
@@ -1481,6 +1500,8 @@ int qadc_adc_range_collect(qadc_adc_index* idx, uint64_t capacity, uint32_t* key
 }
 
 int qadc_adc_range_collect_device(qadc_adc_index* idx, uint64_t capacity, uint32_t* d_keys, float* d_values) {
+    if (int rc = check_aligned(d_keys, 4, "d_keys")) return rc;
+    if (int rc = check_aligned(d_values, 4, "d_values")) return rc;
     return range_collect(idx, capacity, d_keys, d_values, true);
 }
 

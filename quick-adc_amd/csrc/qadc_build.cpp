@@ -23,6 +23,7 @@ int qadc_pq_encode_mode(int M, int dim, const float* codebooks, const void* d_ve
     if ((M != 16 && M != 32) || dim <= 0 || dim % M != 0 || !codebooks || (n && (!d_vectors || !d_codes)))
         return fail(QADC_E_ARG, "bad arguments");
     if (dim > kPqEncodeMaxDim) return fail(QADC_E_ARG, "dim must be <= 2048 (the encoder keeps the codebooks in LDS)");
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;   // (d_codes is written byte by byte: any address)
     HIPCHECK(hipSetDevice(device_id));
     const size_t ncb = (size_t)M * 16 * (dim / M);
     float* d_cb = nullptr;
@@ -299,6 +300,7 @@ int qadc_pq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_cou
                          const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
                          int sum_mode, int device_id) {
     if (int rc = pq_train_check(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
     if (iters == 0) {                                          // the seed untouched, no code written
         if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count << sq_bits, dim / sq_count);
         return QADC_OK;
@@ -412,6 +414,7 @@ int qadc_pq_train16_device(const float* d_vectors, uint64_t n, int dim, int sq_c
                            const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
                            int sum_mode, int device_id) {
     if (int rc = pq_train16_check(d_vectors, n, dim, sq_count, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (int rc = check_aligned(d_vectors, 16, "d_vectors")) return rc;   // (the 16-bit encoder of a round: adc_encode16_kernel's 16-byte loads)
     if (iters == 0) {                                          // the seed untouched, no code written
         if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count * kPqTrain16K, dim / sq_count);
         return QADC_OK;

@@ -1439,6 +1439,7 @@ int qadc_index_add_partition_interleaved(qadc_index* idx, const uint8_t* interle
 int qadc_index_add_partition_device(qadc_index* idx, const void* d_codes, const void* d_labels, uint32_t size) {
     if (!idx || (size && !d_codes)) return fail(QADC_E_ARG, "bad arguments");
     if ((reinterpret_cast<uintptr_t>(d_codes) & 15u) != 0) return fail(QADC_E_ARG, "d_codes must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_labels) & 3u) != 0) return fail(QADC_E_ARG, "d_labels must be 4-byte aligned");
     Part pt;
     if (!size && idx->parts.empty() && idx->labeled < 0) idx->labeled = d_labels != nullptr ? 1 : 0;
     if (size) {

@@ -44,6 +44,14 @@ inline int fail(int code, const std::string& msg) {
     return code;
 }
 
+// A caller's device pointer against the alignment include/qadc.h states for it ("Device pointers of the caller"): the kernels
+// dereference it as a type of that size.  Checked in the host front of the entry point, before any HIP call.  NULL passes: the
+// call's own checks refuse it where the pointer is required.
+inline int check_aligned(const void* p, size_t bytes, const char* name) {
+    if ((reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0) return QADC_OK;
+    return fail(QADC_E_ARG, std::string(name) + " must be " + std::to_string(bytes) + "-byte aligned");
+}
+
 #define HIPCHECK(expr)                                                                                   \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \

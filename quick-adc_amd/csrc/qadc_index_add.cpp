@@ -180,6 +180,7 @@ int qadc_index_remove_labels(qadc_index* idx, const uint32_t* labels, uint64_t c
 }
 
 int qadc_index_remove_labels_device(qadc_index* idx, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out) {
+    if (int rc = check_aligned(d_labels, 4, "d_labels")) return rc;
     return remove_labels(idx, d_labels, count, removed_out, true, "qadc_index_remove_labels_device");
 }
 
@@ -188,6 +189,7 @@ int qadc_index_add_vectors(qadc_index* idx, const float* vectors, uint64_t count
 }
 
 int qadc_index_add_vectors_device(qadc_index* idx, const float* d_vectors, uint64_t count, uint32_t labels_offset, int sum_mode) {
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;   // (every kernel of the 4-bit encoder reads single floats)
     return add_vectors(idx, d_vectors, nullptr, false, count, labels_offset, sum_mode, true, "qadc_index_add_vectors_device");
 }
 
@@ -196,6 +198,8 @@ int qadc_index_add_vectors_labelled(qadc_index* idx, const float* vectors, const
 }
 
 int qadc_index_add_vectors_labelled_device(qadc_index* idx, const float* d_vectors, const uint32_t* d_labels, uint64_t count, int sum_mode) {
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
+    if (int rc = check_aligned(d_labels, 4, "d_labels")) return rc;
     return add_vectors(idx, d_vectors, d_labels, true, count, 0, sum_mode, true, "qadc_index_add_vectors_labelled_device");
 }
 

@@ -165,6 +165,7 @@ int qadc_opq_cross_device(const float* d_vectors, uint64_t n, int dim, int sq_co
                           const void* codes, const float* codebooks, double* M_out, int sum_mode, int device_id) {
     if (int rc = opq_check(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, codebooks, 1, sum_mode)) return rc;
     if (!codes || !M_out) return fail(QADC_E_ARG, "codes and M_out must not be NULL");
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
     DeviceGuard guard;
     HIPCHECK(hipSetDevice(device_id));
     ScratchFree mem;
@@ -189,6 +190,7 @@ int qadc_opq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_co
                           int* rounds_done_out, int div_mode, int sum_mode, int device_id) {
     if (int rc = train_check(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, div_mode, sum_mode))
         return rc;
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
     DeviceGuard guard;
     HIPCHECK(hipSetDevice(device_id));
     ScratchFree mem;

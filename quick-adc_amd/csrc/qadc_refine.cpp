@@ -18,6 +18,7 @@
 #include "qadc_host.h"
 #include "qadc_refine.h"
 
+using qadc::host::check_aligned;
 using qadc::host::fail;
 using qadc::host::DevBuf;
 using qadc::host::DeviceGuard;
@@ -396,6 +397,8 @@ int qadc_refine_put(qadc_refine* r, const float* vectors, const uint32_t* labels
 }
 
 int qadc_refine_put_device(qadc_refine* r, const float* d_vectors, const uint32_t* d_labels, uint64_t count) {
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
+    if (int rc = check_aligned(d_labels, 4, "d_labels")) return rc;
     return put_rows(r, d_vectors, d_labels, count, true, "qadc_refine_put_device");
 }
 
@@ -404,6 +407,7 @@ int qadc_refine_remove(qadc_refine* r, const uint32_t* labels, uint64_t count, u
 }
 
 int qadc_refine_remove_device(qadc_refine* r, const uint32_t* d_labels, uint64_t count, uint64_t* removed_out) {
+    if (int rc = check_aligned(d_labels, 4, "d_labels")) return rc;
     return remove_rows(r, d_labels, count, removed_out, true, "qadc_refine_remove_device");
 }
 
@@ -445,6 +449,7 @@ int qadc_refine_add(qadc_refine* r, const float* vectors, uint64_t count, uint32
 }
 
 int qadc_refine_add_device(qadc_refine* r, const float* d_vectors, uint64_t count, uint32_t first_key) {
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
     return add_rows(r, d_vectors, count, first_key, true);
 }
 
@@ -516,6 +521,10 @@ int qadc_refine_rerank(qadc_refine* r, int nq, const float* queries, int r_in, c
 int qadc_refine_rerank_device(qadc_refine* r, int nq, const float* d_queries, int r_in, const uint32_t* d_keys, const int32_t* d_counts,
                               const float* d_values, int R, uint32_t* d_out_keys, float* d_out_dist, int32_t* d_out_sizes,
                               uint64_t* missing_out) {
+    const void* const d_ptrs[] = {d_queries, d_keys, d_counts, d_values, d_out_keys, d_out_dist, d_out_sizes};
+    const char* const d_names[] = {"d_queries", "d_keys", "d_counts", "d_values", "d_out_keys", "d_out_dist", "d_out_sizes"};
+    for (int i = 0; i < 7; ++i)
+        if (int rc = check_aligned(d_ptrs[i], 4, d_names[i])) return rc;
     if (int rc = check_rerank(r, nq, d_queries, r_in, d_keys, R, d_out_keys, d_out_dist, d_out_sizes)) return rc;
     if (missing_out) *missing_out = 0;
     if (nq == 0) return QADC_OK;

@@ -1293,6 +1293,31 @@ int qadc_refine_keyed_info(const qadc_refine* r, uint64_t* live, uint64_t* rows_
  * MurmurHash3's 32-bit finalizer of the key. */
 uint32_t qadc_refine_keyed_slot(uint32_t key, int table_bits);
 
+/* ---- exhaustive search: the R nearest rows of a whole store ----
+ * For every query: of every key the store holds — dense or keyed, F32 or F16 — that passes `filter`, the word (image of D(q, x_key))
+ * << 32 | key, D and the image exactly as above; the words sorted ascending, the first min(R, n) returned as (key, distance), the
+ * slots behind them key 0xFFFFFFFF and distance +inf, out_sizes[q] = min(R, n).  That is qadc_refine_rerank with keys[q] = every
+ * held key that passes and no r_in limit, bit for bit; the twin is refine::knn of quick-adc_amd/host/refine.hpp.  filter NULL: every
+ * key passes; else qadc_adc_filter's rule: EXCLUDE drops the listed keys, ALLOW keeps only the listed keys (an empty ALLOW set keeps
+ * nothing).  The filter need only be alive for the call and no use is counted on it.  An empty store gives sizes 0 and fillers; R
+ * above the rows held is legal.  The result is a function of the store's contents and the arguments alone: no chunk, tile, pass or
+ * arrival order shows in it.
+ * Limits: every row is read whatever the filter says (a filter saves no time); R <= QADC_REFINE_KNN_MAX_R; L2 only; one device; one
+ * filter per call; synchronous, on the store's stream. */
+#define QADC_REFINE_KNN_MAX_R 1024
+/* Host arrays: queries [nq][dim] -> out_keys [nq][R], out_dist [nq][R], out_sizes [nq].  nq = 0 is a no-op.  QADC_E_ARG before the
+ * device is touched: r NULL, R outside [1, QADC_REFINE_KNN_MAX_R], a required array NULL with nq > 0, a filter of another device. */
+int qadc_refine_knn(qadc_refine* r, int nq, const float* queries, int R, const qadc_adc_filter* filter, uint32_t* out_keys, float* out_dist,
+                    int32_t* out_sizes);
+/* The same with every array in device memory of the store's device (see qadc_refine_rerank_device), the queries complete before the
+ * call: the arrays are touched by kernels only and nothing crosses the bus.  4-byte alignment of every array is checked first. */
+int qadc_refine_knn_device(qadc_refine* r, int nq, const float* d_queries, int R, const qadc_adc_filter* filter, uint32_t* d_out_keys,
+                           float* d_out_dist, int32_t* d_out_sizes);
+/* A tuning and test knob: the rows of a group per launch (1 .. 7168) and the queries per pass of the later knn calls; 0 = the plan's
+ * default (quick-adc_amd/host/refine_knn_plan.hpp).  No value changes a result.  QADC_E_ARG: r NULL, chunk_rows above 7168, a
+ * negative pass_nq. */
+int qadc_refine_set_knn_plan(qadc_refine* r, uint64_t chunk_rows, int pass_nq);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,15 @@ struct DeviceOut { uint32_t* keys; float* values; int32_t* sizes; };
 // A filter as the kernels read it — the index's, or the table entry of one query of a *_filtered call; none (bitmap null) for NULL.
 ScanFilter scan_filter(const qadc_adc_filter* f) { return f ? ScanFilter{f->bitmap, f->span.lo, f->span.last, f->mode} : ScanFilter{}; }
 
+}  // namespace
+
+void qadc::host::adc_filter_view(const qadc_adc_filter* f, qadc::adc::ScanFilter* out, int* device) {
+    *out = scan_filter(f);
+    *device = f ? f->device : -1;
+}
+
+namespace {
+
 // The database as the scan launcher takes it: the owned codes, or the partition table of a view.
 ScanDb scan_db(const qadc_adc_index* idx) {
     const ScanFilter filter = scan_filter(idx->filter);

@@ -35,6 +35,9 @@
 #include "qadc_kernels.h"
 
 namespace qadc {
+namespace adc {
+struct ScanFilter;   // csrc/qadc_adc_kernels.h
+}
 namespace host {
 
 extern thread_local std::string g_err;                       // message of the last failure on this thread (qadc_last_error)
@@ -588,6 +591,9 @@ int load_rccl(DistState& d, std::string& err);
 int enqueue_merge(qadc_index* idx, Slot& s, hipStream_t scan_stream);
 int flush_merges(qadc_index* idx, uint64_t upto);
 int flush_shares(qadc_index* idx, uint64_t upto);            // heap-share gathers of sharded replays (qadc_dist.cpp)
+// qadc_adc.cpp: what a key filter (qadc_adc_filter, private to that unit) gives a kernel, and the device it lives on — for the
+// callers outside the float-ADC engine (qadc_refine_knn)
+void adc_filter_view(const qadc_adc_filter* f, adc::ScanFilter* out, int* device);
 
 }  // namespace host
 }  // namespace qadc

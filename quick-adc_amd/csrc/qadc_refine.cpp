@@ -2,7 +2,9 @@
 // vectors in device memory, dense over a key range or keyed by label through a hash table, and the call that reorders the candidate
 // keys a search returned by their L2 distance to those vectors.  The store belongs to no index and shares nothing with either engine but the device's stream set
 // (qadc_device_prepare): it consumes uint32 keys, whoever produced them.  The definition it is held to is host/refine.hpp, the
-// launch geometry host/refine_plan.hpp, the kernels csrc/qadc_refine_kernel.hip.
+// launch geometry host/refine_plan.hpp, the kernels csrc/qadc_refine_kernel.hip.  qadc_refine_knn is the
+// exhaustive form of the same call, every held key of the store against a batch of queries: geometry host/refine_knn_plan.hpp,
+// kernels csrc/qadc_refine_knn_kernel.hip.
 //
 // Every array of the *_device calls is read and written by kernels only, so memory of another HIP runtime (torch tensors) is
 // legal; for the same reason the library cannot ask which device such a pointer lives on, and does not: as for
@@ -25,6 +27,10 @@ using qadc::host::DeviceGuard;
 
 static_assert(QADC_REFINE_MAX_IN == qadc::refine::kRefinePlanMaxIn && QADC_REFINE_MAX_IN == qadc::refine::kMaxIn, "one limit on r_in");
 static_assert(QADC_REFINE_MAX_DIM == qadc::refine::kRefinePlanMaxDim && QADC_REFINE_MAX_DIM == qadc::refine::kMaxDim, "one limit on dim");
+static_assert(QADC_REFINE_KNN_MAX_R == qadc::refine::kKnnMaxR, "one limit on the R of knn");
+static_assert(QADC_ADC_FILTER_EXCLUDE == qadc::adc::kFilterExclude && QADC_ADC_FILTER_ALLOW == qadc::adc::kFilterAllow &&
+                  QADC_ADC_FILTER_EXCLUDE == qadc::refine::kFilterExclude && QADC_ADC_FILTER_ALLOW == qadc::refine::kFilterAllow,
+              "the filter modes of the scan, of knn and of its twin");
 static_assert(QADC_REFINE_F32 == qadc::refine::kF32 && QADC_REFINE_F16 == qadc::refine::kF16, "the twin's element types");
 
 struct qadc_refine {
@@ -48,6 +54,11 @@ struct qadc_refine {
     DevBuf<float> d_queries, d_values, d_out_dist;  // the host form's arrays in device memory
     DevBuf<uint32_t> d_keys, d_out_keys;
     DevBuf<int32_t> d_counts, d_out_sizes;
+    // exhaustive search (qadc_refine_knn): the plan's knobs (0: its default) and the scratch of a pass
+    uint64_t knn_chunk_rows = 0;
+    int knn_pass_nq = 0;
+    DevBuf<uint64_t> d_knn_buf, d_knn_bound;        // [pass_nq][groups][buf_cap] / [pass_nq][groups]
+    DevBuf<uint32_t> d_knn_cnt;                     // [pass_nq][groups]
     size_t elem() const { return dtype == QADC_REFINE_F16 ? 2 : 4; }
     size_t row_bytes() const { return (size_t)dim * elem(); }
 };
@@ -384,6 +395,61 @@ int rerank_passes(qadc_refine* r, int nq, const float* queries, int r_in, const 
     return QADC_OK;
 }
 
+int check_knn(const qadc_refine* r, int nq, const float* queries, int R, const qadc_adc_filter* filter, adc::ScanFilter* scan,
+              const uint32_t* out_keys, const float* out_dist, const int32_t* out_sizes) {
+    if (!r) return fail(QADC_E_ARG, "store is null");
+    if (nq < 0) return fail(QADC_E_ARG, "nq is negative");
+    if (R < 1 || R > QADC_REFINE_KNN_MAX_R) return fail(QADC_E_ARG, "R is 1 .. " + std::to_string(QADC_REFINE_KNN_MAX_R) + " (QADC_REFINE_KNN_MAX_R)");
+    if (nq && (!queries || !out_keys || !out_dist || !out_sizes))
+        return fail(QADC_E_ARG, "queries, out_keys, out_dist and out_sizes must not be null");
+    int fdev = -1;
+    adc_filter_view(filter, scan, &fdev);
+    if (filter && fdev != r->device)
+        return fail(QADC_E_ARG, "the filter is on device " + std::to_string(fdev) + " and the store on device " + std::to_string(r->device));
+    return QADC_OK;
+}
+
+// The passes of an exhaustive search on arrays in device memory; the stream is drained before the call returns.
+int knn_passes(qadc_refine* r, int nq, const float* queries, int R, const adc::ScanFilter& filter, uint32_t* out_keys, float* out_dist,
+               int32_t* out_sizes) {
+    KnnPlan plan;
+    if (!knn_plan(nq, r->rows, r->dim, r->dtype, R, r->knn_chunk_rows, r->knn_pass_nq, &plan))
+        return fail(QADC_E_ARG, "no launch geometry for this call (qadc_refine_set_knn_plan: R + chunk_rows is at most " +
+                                    std::to_string(kKnnMaxSort) + ")");
+    const size_t slots = (size_t)plan.pass_nq * plan.groups;
+    HIPCHECK(r->d_knn_buf.ensure(slots * (size_t)plan.buf_cap));
+    HIPCHECK(r->d_knn_bound.ensure(slots));
+    HIPCHECK(r->d_knn_cnt.ensure(slots));
+    for (int q0 = 0; q0 < nq; q0 += plan.pass_nq) {
+        KnnPass p;
+        p.rows = r->data;
+        p.f16 = r->dtype == QADC_REFINE_F16;
+        p.dim = r->dim;
+        p.lo = r->lo;
+        p.nrows = r->rows;
+        p.row_key = r->keyed ? r->row_key : nullptr;
+        p.filter = filter;
+        p.nq = std::min(plan.pass_nq, nq - q0);
+        p.R = R;
+        p.queries = queries + (size_t)q0 * r->dim;
+        p.buf = r->d_knn_buf.p;
+        p.cnt = r->d_knn_cnt.p;
+        p.bound = r->d_knn_bound.p;
+        p.out_keys = out_keys + (size_t)q0 * R;
+        p.out_dist = out_dist + (size_t)q0 * R;
+        p.out_sizes = out_sizes + q0;
+        HIPCHECK(hipMemsetAsync(p.cnt, 0, slots * sizeof(uint32_t), r->stream));
+        HIPCHECK(hipMemsetAsync(p.bound, 0xFF, slots * sizeof(uint64_t), r->stream));
+        for (uint64_t l = 0; l < plan.launches; ++l) {
+            HIPCHECK(launch_knn_dist(p, plan, l, r->stream));
+            HIPCHECK(launch_knn_select(p, plan, l, r->stream));
+        }
+        HIPCHECK(launch_knn_final(p, plan, r->stream));
+    }
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    return QADC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -440,6 +506,7 @@ int qadc_refine_destroy(qadc_refine* r) {
     r->d_cnt.release(); r->d_labels.release(); r->d_slot_of.release(); r->d_dst.release();
     r->d_stage.release(); r->d_words.release(); r->d_missing.release(); r->d_queries.release(); r->d_values.release();
     r->d_out_dist.release(); r->d_keys.release(); r->d_out_keys.release(); r->d_counts.release(); r->d_out_sizes.release();
+    r->d_knn_buf.release(); r->d_knn_bound.release(); r->d_knn_cnt.release();
     delete r;
     return QADC_OK;
 }
@@ -531,6 +598,52 @@ int qadc_refine_rerank_device(qadc_refine* r, int nq, const float* d_queries, in
     DeviceGuard guard;
     HIPCHECK(hipSetDevice(r->device));
     return rerank_passes(r, nq, d_queries, r_in, d_keys, d_counts, d_values, R, d_out_keys, d_out_dist, d_out_sizes, missing_out);
+}
+
+int qadc_refine_set_knn_plan(qadc_refine* r, uint64_t chunk_rows, int pass_nq) {
+    if (!r) return fail(QADC_E_ARG, "store is null");
+    if (chunk_rows > kKnnDefaultChunk)
+        return fail(QADC_E_ARG, "chunk_rows is at most " + std::to_string(kKnnDefaultChunk) + " (a select sorts R + chunk_rows <= " +
+                                    std::to_string(kKnnMaxSort) + " words)");
+    if (pass_nq < 0) return fail(QADC_E_ARG, "pass_nq is negative");
+    r->knn_chunk_rows = chunk_rows;
+    r->knn_pass_nq = pass_nq;
+    return QADC_OK;
+}
+
+int qadc_refine_knn(qadc_refine* r, int nq, const float* queries, int R, const qadc_adc_filter* filter, uint32_t* out_keys, float* out_dist,
+                    int32_t* out_sizes) {
+    adc::ScanFilter scan;
+    if (int rc = check_knn(r, nq, queries, R, filter, &scan, out_keys, out_dist, out_sizes)) return rc;
+    if (nq == 0) return QADC_OK;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    const size_t nout = (size_t)nq * R;
+    HIPCHECK(r->d_queries.ensure((size_t)nq * r->dim));
+    HIPCHECK(r->d_out_keys.ensure(nout));
+    HIPCHECK(r->d_out_dist.ensure(nout));
+    HIPCHECK(r->d_out_sizes.ensure(nq));
+    HIPCHECK(hipMemcpyAsync(r->d_queries.p, queries, (size_t)nq * r->dim * 4, hipMemcpyHostToDevice, r->stream));
+    if (int rc = knn_passes(r, nq, r->d_queries.p, R, scan, r->d_out_keys.p, r->d_out_dist.p, r->d_out_sizes.p)) return rc;
+    HIPCHECK(hipMemcpyAsync(out_keys, r->d_out_keys.p, nout * 4, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipMemcpyAsync(out_dist, r->d_out_dist.p, nout * 4, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipMemcpyAsync(out_sizes, r->d_out_sizes.p, (size_t)nq * 4, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    return QADC_OK;
+}
+
+int qadc_refine_knn_device(qadc_refine* r, int nq, const float* d_queries, int R, const qadc_adc_filter* filter, uint32_t* d_out_keys,
+                           float* d_out_dist, int32_t* d_out_sizes) {
+    const void* const d_ptrs[] = {d_queries, d_out_keys, d_out_dist, d_out_sizes};
+    const char* const d_names[] = {"d_queries", "d_out_keys", "d_out_dist", "d_out_sizes"};
+    for (int i = 0; i < 4; ++i)
+        if (int rc = check_aligned(d_ptrs[i], 4, d_names[i])) return rc;
+    adc::ScanFilter scan;
+    if (int rc = check_knn(r, nq, d_queries, R, filter, &scan, d_out_keys, d_out_dist, d_out_sizes)) return rc;
+    if (nq == 0) return QADC_OK;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    return knn_passes(r, nq, d_queries, R, scan, d_out_keys, d_out_dist, d_out_sizes);
 }
 
 }  // extern "C"

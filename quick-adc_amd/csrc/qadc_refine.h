@@ -5,7 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../host/refine_keyed_plan.hpp"
+#include "../host/refine_knn_plan.hpp"
 #include "../host/refine_plan.hpp"
+#include "qadc_adc_kernels.h"   // ScanFilter
 
 namespace qadc {
 namespace refine {
@@ -76,6 +78,32 @@ hipError_t launch_keyed_remove(const uint32_t* labels, uint32_t n, KeyedTable t,
                                unsigned long long* cnt, hipStream_t stream);
 // (row_key[r], r) of every live row r < alloc_rows into the cleared table t
 hipError_t launch_keyed_rebuild(const uint32_t* row_key, uint32_t alloc_rows, KeyedTable t, hipStream_t stream);
+
+// ---- exhaustive search (qadc_refine_knn; kernels: csrc/qadc_refine_knn_kernel.hip; geometry:
+// host/refine_knn_plan.hpp).  One pass of the plan over nq queries; every pointer is device memory touched by kernels only. ----
+struct KnnPass {
+    const void* rows;              // the store's rows [nrows][dim], `f16` says which element type
+    bool f16;
+    int dim;
+    uint32_t lo;                   // a dense store: the key of row r is lo + r
+    uint64_t nrows;                // rows to walk (a keyed store: the rows allocated so far)
+    const uint32_t* row_key;       // a keyed store: a row's key, 0xFFFFFFFF for a free row (skipped); else null
+    adc::ScanFilter filter;        // bitmap null: none
+    int nq, R;
+    const float* queries;          // [nq][dim]
+    uint64_t* buf;                 // scratch [nq][groups][buf_cap] words
+    uint32_t* cnt;                 // scratch [nq][groups]: words in the buffer (zero before the first launch)
+    uint64_t* bound;               // scratch [nq][groups]: the largest word that may still enter (~0 before the first launch)
+    uint32_t* out_keys;            // [nq][R]
+    float* out_dist;               // [nq][R]
+    int32_t* out_sizes;            // [nq]
+};
+// refine_knn_dist_kernel<Row, QT, J>: the words of launch `launch`'s rows that are <= their (query, group)'s bound, appended
+hipError_t launch_knn_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream);
+// refine_knn_select_kernel: every buffer of the launch's groups that holds at least R words keeps its first R, sorted; bound = the R-th
+hipError_t launch_knn_select(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream);
+// refine_knn_final_kernel: the groups' lists merged: the first R words, the fillers behind them and the size of every query
+hipError_t launch_knn_final(const KnnPass& p, const KnnPlan& plan, hipStream_t stream);
 
 }  // namespace refine
 }  // namespace qadc

@@ -15,6 +15,9 @@
 // word (img(D) << 32) | key, img(D) = D's bit pattern (D >= +0: ordered as an unsigned integer), 0x7FC00000 for every NaN.  The
 // words are sorted ascending, equal words kept once, and the first min(R, survivors) are the output, ascending by (distance,
 // key); the slots behind them hold key 0xFFFFFFFF and distance +inf.
+//
+// Exhaustive search (knn, at the end): the selection above over every key the store holds that passes a
+// key filter — the definition of qadc_refine_knn.
 #pragma once
 #include <algorithm>
 #include <cfloat>
@@ -131,6 +134,13 @@ struct store {
 
     bool holds(uint32_t key) const { return key >= lo && (uint64_t)key - lo < rows; }
 
+    // every key held, ascending (what knn ranks)
+    std::vector<uint32_t> held_keys() const {
+        std::vector<uint32_t> k((size_t)rows);
+        for (uint64_t r = 0; r < rows; ++r) k[(size_t)r] = (uint32_t)(lo + r);
+        return k;
+    }
+
     float distance_to(const float* q, uint32_t key) const {
         const size_t base = (size_t)(key - lo) * dim;
         if (dtype == kF16) {
@@ -181,6 +191,17 @@ struct keyed_store {
 
     bool holds(uint32_t key) const { return dtype == kF16 ? f16.count(key) != 0 : f32.count(key) != 0; }
 
+    // every key held, ascending (what knn ranks)
+    std::vector<uint32_t> held_keys() const {
+        std::vector<uint32_t> k;
+        k.reserve((size_t)live());
+        if (dtype == kF16)
+            for (const auto& e : f16) k.push_back(e.first);
+        else
+            for (const auto& e : f32) k.push_back(e.first);
+        return k;
+    }
+
     float distance_to(const float* q, uint32_t key) const {
         if (dtype == kF16) {
             const uint16_t* x = f16.find(key)->second.data();
@@ -221,6 +242,40 @@ inline uint64_t rerank(const Store& s, int nq, const float* queries, int r_in, c
         out_sizes[q] = n;
     }
     return missing;
+}
+
+// ---- exhaustive search (qadc_refine_knn) ----
+// A key filter with qadc_adc_filter's semantics (csrc/qadc_adc_kernels.h, ScanFilter): kFilterExclude drops the listed keys,
+// kFilterAllow keeps only the listed keys; an empty allow set keeps nothing.  `keys` is sorted ascending (duplicates are harmless).
+constexpr int kFilterExclude = 0, kFilterAllow = 1;   // QADC_ADC_FILTER_EXCLUDE, QADC_ADC_FILTER_ALLOW
+struct filter {
+    int mode = kFilterExclude;
+    std::vector<uint32_t> keys;
+    bool passes(uint32_t key) const { return std::binary_search(keys.begin(), keys.end(), key) == (mode == kFilterAllow); }
+};
+
+// The R nearest rows of the whole store: rerank with keys[q] = every held key that passes `filter` (null: every held key), with no
+// limit on their number (and nothing to skip, miss or dedupe: a store holds a key once).  queries [nq][dim] -> out_keys [nq][R],
+// out_dist [nq][R], out_sizes [nq] = min(R, the keys that pass).
+template <typename Store>
+inline void knn(const Store& s, int nq, const float* queries, int R, const filter* f, uint32_t* out_keys, float* out_dist,
+                int32_t* out_sizes) {
+    std::vector<uint32_t> keys;
+    for (uint32_t k : s.held_keys())
+        if (!f || f->passes(k)) keys.push_back(k);
+    const int n = (int)keys.size();
+    for (int q = 0; q < nq; ++q) {   // one query at a time: every list of the rerank call is `keys`
+        if (n == 0) {                // (rerank takes r_in >= 1)
+            for (int j = 0; j < R; ++j) {
+                out_keys[(size_t)q * R + j] = kNoKey;
+                out_dist[(size_t)q * R + j] = bits_float(kInfImage);
+            }
+            out_sizes[q] = 0;
+            continue;
+        }
+        rerank(s, 1, queries + (size_t)q * s.dim, n, keys.data(), nullptr, nullptr, R, out_keys + (size_t)q * R, out_dist + (size_t)q * R,
+               out_sizes + q);
+    }
 }
 
 }  // namespace refine

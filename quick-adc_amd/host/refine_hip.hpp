@@ -80,6 +80,29 @@ struct refine_store_hip {
             die("rerank");
         return out;
     }
+
+    // Exhaustive search (qadc_refine_knn): queries [nq][dim] -> per query the first r of every key the store
+    // holds that passes `filter` (null: every key), by (exact distance, key)
+    refine_result knn(int nq, const float* queries, int r, const qadc_adc_filter* filter = nullptr) {
+        refine_result out;
+        out.r = r;
+        out.keys.resize((std::size_t)nq * r);
+        out.dist.resize((std::size_t)nq * r);
+        out.sizes.resize(nq);
+        if (qadc_refine_knn(store, nq, queries, r, filter, out.keys.data(), out.dist.data(), out.sizes.data()) != QADC_OK) die("knn");
+        return out;
+    }
+
+    // the same with every array in device memory of the store's device: d_queries [nq][dim] -> d_keys [nq][r], d_dist [nq][r], d_sizes [nq]
+    void knn_device(int nq, const float* d_queries, int r, const qadc_adc_filter* filter, std::uint32_t* d_keys, float* d_dist,
+                    std::int32_t* d_sizes) {
+        if (qadc_refine_knn_device(store, nq, d_queries, r, filter, d_keys, d_dist, d_sizes) != QADC_OK) die("knn_device");
+    }
+
+    // a tuning and test knob (qadc_refine_set_knn_plan): 0 = the plan's default; no value changes a result
+    void set_knn_plan(std::uint64_t chunk_rows, int pass_nq) {
+        if (qadc_refine_set_knn_plan(store, chunk_rows, pass_nq) != QADC_OK) die("set_knn_plan");
+    }
 };
 
 // The engine's search of nq queries with heaps of e.r entries, then their keys re-ranked against `store`: the first r by (exact

@@ -59,6 +59,7 @@ SYMBOLS = [
     "qadc_refine_relocations", "qadc_refine_rerank", "qadc_refine_rerank_device",
     "qadc_refine_create_keyed", "qadc_refine_put", "qadc_refine_put_device", "qadc_refine_remove", "qadc_refine_remove_device",
     "qadc_refine_keyed_info", "qadc_refine_keyed_slot",
+    "qadc_refine_knn", "qadc_refine_knn_device", "qadc_refine_set_knn_plan",
     "qadc_adc_range_scan", "qadc_adc_range_scan_device", "qadc_adc_range_search", "qadc_adc_range_search_device",
     "qadc_adc_range_collect", "qadc_adc_range_collect_device",
 ]
@@ -309,6 +310,9 @@ def lib():
         L.qadc_refine_rerank.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, u32p, i32p, f32p, C.c_int, u32p, f32p, i32p, u64p]
         L.qadc_refine_rerank_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, u64p]
+        L.qadc_refine_knn.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_void_p, u32p, f32p, i32p]
+        L.qadc_refine_knn_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.qadc_refine_set_knn_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
         _lib = L
     return _lib
 
@@ -2132,3 +2136,49 @@ class Refine:
                                                None if v is None else v.data_ptr(), R, ok.data_ptr(), od.data_ptr(), osz.data_ptr(),
                                                C.byref(missing)))
         return ok, od, osz, int(missing.value)
+
+    # ---- exhaustive search (qadc_refine_knn) ----
+    def knn(self, queries, R, filter=None):
+        """queries [nq][dim] -> (keys uint32 [nq][R], dist float32 [nq][R], sizes int32 [nq]): per query the first R of EVERY key the
+        store holds that passes `filter` (an AdcFilter of the store's device, or None), by (exact squared L2 distance, key) — rerank()
+        fed every held key, bit for bit; behind sizes[q]: key 0xFFFFFFFF, distance +inf.  1 <= R <= 1024."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise QadcError("queries has shape %s, expected [nq][%d]" % (q.shape, self.dim))
+        return self.knn_raw(q.shape[0], q, int(R), filter)
+
+    def knn_raw(self, nq, queries, R, filter=None, outputs=True):
+        """The C call as it is (queries: a float32 array or None; filter: an AdcFilter or None)."""
+        ok = np.zeros((max(nq, 0), max(R, 0)), np.uint32) if outputs else None
+        od = np.zeros((max(nq, 0), max(R, 0)), np.float32) if outputs else None
+        osz = np.zeros(max(nq, 0), np.int32) if outputs else None
+        _check(lib().qadc_refine_knn(self._h, nq, _p(queries, f32p), R, None if filter is None else filter._h, _p(ok, u32p), _p(od, f32p),
+                                     _p(osz, i32p)))
+        return ok, od, osz
+
+    def knn_device(self, queries, R, filter=None, out=None):
+        """knn() on torch tensors of the store's device: queries float32 [nq][dim] -> (keys int32 [nq][R] carrying the uint32 bits,
+        dist float32 [nq][R], sizes int32 [nq]) on that device; nothing crosses the bus.  out: the three tensors to write into."""
+        import torch
+        if getattr(queries, "ndim", 0) != 2:
+            raise TypeError("queries must be a 2-d torch.Tensor")
+        nq, R = int(queries.shape[0]), int(R)
+        q = self._tensor(queries, "float32", (nq, self.dim), "queries")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = (torch.zeros((nq, max(R, 0)), dtype=torch.int32, device=dev), torch.zeros((nq, max(R, 0)), dtype=torch.float32, device=dev),
+                   torch.zeros((nq,), dtype=torch.int32, device=dev))
+        ok = self._tensor(out[0], "int32", (nq, max(R, 0)), "out keys")
+        od = self._tensor(out[1], "float32", (nq, max(R, 0)), "out dist")
+        osz = self._tensor(out[2], "int32", (nq,), "out sizes")
+        self._sync()
+        _check(lib().qadc_refine_knn_device(self._h, nq, q.data_ptr(), R, None if filter is None else filter._h, ok.data_ptr(), od.data_ptr(),
+                                            osz.data_ptr()))
+        return ok, od, osz
+
+    def set_knn_plan(self, chunk_rows=0, pass_nq=0):
+        """qadc_refine_set_knn_plan: the rows of a group per launch and the queries per pass of the later knn calls (0: the plan's
+        default) — a tuning and test knob; no value changes a result"""
+        _check(lib().qadc_refine_set_knn_plan(self._h, int(chunk_rows), int(pass_nq)))

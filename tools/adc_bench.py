@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,filter,qfilter,refine,range,keyed] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,filter,qfilter,refine,range,keyed,knn] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,opq,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,filter] [--iters N] [--out FILE]
 
@@ -63,6 +63,11 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
   keyed     caller-chosen labels (not in the default legs), on the ivf_search / refine shape: rerank_device on a
             keyed store against the dense store holding the same vectors, alternated, at the refine leg's r_in values; put_device and
             remove_device rows/s at 10^6 keys, fresh and overwriting; add_vectors_device(labels=...) against the plain call.
+  knn       exhaustive search over a refine store (not in the default legs): Refine.knn_device and Refine.knn
+            on 10^6 rows of dim 128, float and half store, nq = 1, 32 and 1024, R = 100, from call to return, as pairs/s and as a share
+            of the estimated roof of 2 x 10^11 pairs/s (3 dim component operations a pair at 32 packed non-FMA float operations per
+            clock and SIMD — derived, not measured); beside it, in the same process, the route the benchmarks use for ground truth today,
+            a chunked torch |x|^2 - 2 q.x and topk, and the share of queries whose key sets agree (other arithmetic: not asserted).
   --trained-codebooks   the add, remove and ivf_search legs (8 and 4 bits) learn their codebooks with train_pq (10 rounds on the
             residuals of the first 10^5 vectors) instead of sampling them; off by default, so that recorded figures stay comparable
   --bits 4   the float-ADC view of a 4-bit index instead (pyqadc.AdcIndex.view_of; legs lone,ivf_search):
@@ -1295,6 +1300,59 @@ def word_legs(legs, iters, res):
         idx.close()
 
 
+KNN_ROOF_PAIRS_PER_S = 2e11   # estimated: 3 * 128 component operations a pair, 32 packed non-FMA f32 operations per clock and SIMD
+
+
+def knn_leg(iters, res, torch):
+    """Refine.knn / knn_device over 10^6 rows of dim 128 beside a chunked torch |x|^2 - 2 q.x + topk on the same rows"""
+    if torch is None:
+        print("knn leg: needs torch on the GPU (the rows are made there and the yardstick is torch)", flush=True)
+        return
+    n, dim, chunk = 1_000_000, 128, 1 << 18
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    x = torch.randn((n, dim), generator=gen, device="cuda", dtype=torch.float32)
+    out = res.setdefault("knn", {"rows": n, "dim": dim, "R": R, "roof_pairs_per_s_estimated": KNN_ROOF_PAIRS_PER_S})
+    for dtype in ("f32", "f16"):
+        st = pyqadc.Refine(dim, dtype)
+        st.add_device(x, 0)
+        held = x if dtype == "f32" else x.half().float()                   # the values the store holds
+        norms = (held * held).sum(1)
+
+        def torch_route(q):
+            best_d = best_k = None
+            for first in range(0, n, chunk):
+                d = norms[first:first + chunk][None, :] - 2.0 * (q @ held[first:first + chunk].T)
+                dd, kk = torch.topk(d, R, dim=1, largest=False)
+                kk = kk + first
+                if best_d is not None:
+                    dd, kk = torch.cat([best_d, dd], 1), torch.cat([best_k, kk], 1)
+                    dd, pick = torch.topk(dd, R, dim=1, largest=False)
+                    kk = torch.gather(kk, 1, pick)
+                best_d, best_k = dd, kk
+            torch.cuda.synchronize()
+            return best_k
+
+        for nq in (1, 32, 1024):
+            q = torch.randn((nq, dim), generator=gen, device="cuda", dtype=torch.float32)
+            q_host = q.cpu().numpy()
+            its = max(3, iters if nq < 1024 else iters // 2)
+            med_d, best_d = timed(lambda: st.knn_device(q, R), its)
+            med_h, _ = timed(lambda: st.knn(q_host, R), its)
+            med_t, _ = timed(lambda: torch_route(q), its)
+            keys = st.knn_device(q, R)[0].cpu().numpy().view(np.uint32)
+            want = torch_route(q).cpu().numpy()
+            agree = float(np.mean([set(a.tolist()) == set(b.tolist()) for a, b in zip(keys, want)]))
+            pairs = nq * n / med_d
+            out["%s_nq%d" % (dtype, nq)] = {"knn_device_ms": med_d * 1e3, "knn_device_best_ms": best_d * 1e3, "knn_host_arrays_ms": med_h * 1e3,
+                                            "torch_route_ms": med_t * 1e3, "pairs_per_s": pairs, "share_of_estimated_roof": pairs / KNN_ROOF_PAIRS_PER_S,
+                                            "queries_whose_key_sets_agree": agree}
+            print("knn %s, 10^6 x 128, nq %4d, R %d: knn_device %.3f ms (best %.3f; host arrays %.3f) = %.3g pairs/s = %.3f of the estimated roof; "
+                  "torch |x|^2 - 2 q.x + topk %.3f ms; key sets agree on %.3f of the queries"
+                  % (dtype, nq, R, med_d * 1e3, best_d * 1e3, med_h * 1e3, pairs, pairs / KNN_ROOF_PAIRS_PER_S, med_t * 1e3, agree), flush=True)
+        st.close()
+        del held, norms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default=None)
@@ -1319,7 +1377,7 @@ def main():
                 f.write(line + "\n")
         return
     torch = None
-    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:
             import torch
             torch.zeros(1, device="cuda")
@@ -1420,6 +1478,8 @@ def main():
         train_leg(8, a.iters, res)
     if "opq" in legs:
         opq_leg(8, a.iters, res)
+    if "knn" in legs:
+        knn_leg(a.iters, res, torch)
     line = json.dumps(res)
     print(line)
     if a.out:

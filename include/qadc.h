@@ -47,7 +47,8 @@ const char* qadc_version(void);
  *             d_codes     qadc_index_add_partition_device: a borrowed partition (readable up to size * M/2 rounded up to 16 bytes)
  *    4 bytes  every other float, uint32 and int32 array: d_queries, d_keys, d_values, d_sizes, d_labels, d_counts, d_out_keys,
  *             d_out_dist, d_out_sizes, and d_vectors of qadc_index_add_vectors_device, _labelled_device, qadc_refine_add_device,
- *             qadc_refine_put_device, qadc_pq_encode(_mode), qadc_pq_train_device, qadc_opq_cross_device, qadc_opq_train_device
+ *             qadc_refine_put_device, qadc_pq_encode(_mode), qadc_pq_train_device, qadc_opq_cross_device, qadc_opq_train_device,
+ *             qadc_kmeans_seed_device
  *    1 byte   d_codes of qadc_pq_encode(_mode): [n][M/2] bytes, each written by itself
  * Host arrays carry no such requirement beyond their element type's.
  * ------------------------------------------------------------------------------------------- */
@@ -309,7 +310,8 @@ int qadc_pq_encode_host_mode(int M, int dim, const float* codebooks, const float
  *   -ffast-math g++ replaces the source's division (databases.cpp:83-88) by a reciprocal and a multiplication, pinned to those
  *   loops compiled here with the reference's flags (tests/test_oracle_float_ref.py); an empty cluster becomes NaN either way;
  *   centroids [K][dim] in and out.  qadc_kmeans_iterations_host_mode: div_mode 1 = that, 0 = the source's division.  The reference seeds these iterations with two OpenCV
- *   k-means++ iterations (databases.cpp:96-113) — third-party, not restated: the caller provides the seed. */
+ *   k-means++ iterations (databases.cpp:96-113) — third-party, not restated: the caller provides the seed, or takes
+ *   qadc_kmeans_seed_host's (k-means++ seeding, below). */
 int qadc_ivf_encode_host(int M, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
                          const float* vectors, uint64_t n, int32_t* assign_out, uint8_t* codes, int device_id);
 int qadc_ivf_encode_host_mode(int M, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
@@ -336,7 +338,7 @@ int qadc_kmeans_iterations_host_mode(const float* vectors, uint64_t n, int dim, 
  * stays NaN, as in the reference; nothing repairs it.  sum_mode: the norms' grouping, as for the encoders.
  * K_coarse > 0: the learning set is first made residuals to the nearest of coarse [K_coarse][dim] (find_k_neighbors, k = 1);
  * rotation [dim][dim] or NULL: ... and rotated (rotated[r] = sum_c x[c] * rotation[r][c]) — what index_db::add_vectors hands to
- * the quantizer.  The caller seeds (the reference leaves learning to an outside project): codebooks [sq_count][2^sq_bits][dsub] in
+ * the quantizer.  The caller seeds (the reference leaves learning to an outside project; qadc_kmeans_seed_host below is one seed): codebooks [sq_count][2^sq_bits][dsub] in
  * and out; iters == 0 returns them untouched and writes no code.  codes_out (nullable, host memory): the last round's
  * assignment in the encoder's layout ([n][sq_count / 2] packed nibbles, or [n][sq_count] bytes) — the codes under the codebooks
  * of BEFORE the last update.  empty_out (nullable): centroids with a NaN component at return.
@@ -425,7 +427,7 @@ int qadc_procrustes_host(const double* M, int dim, float* rotation_out, int* swe
  *   Refused with QADC_E_ARG before the first HIP call: everything qadc_pq_train_host refuses; sq_bits 16; dim > 1024; NULL
  *   rotation; outer < 0; inner < 1.  QADC_E_STATE: a Procrustes solve hit its sweep cap (rotation and codebooks are then not
  *   a fitted pair).  Limits: 4 and 8 bits; dim <= 1024; the learning set, its residual, its rotated copy, the codes and the
- *   partials are resident for the call; one device; synchronous.  Not done: the parametric initialisation, k-means++ seeding,
+ *   partials are resident for the call; one device; synchronous.  Not done: the parametric initialisation, seeding (qadc_kmeans_seed_host below),
  *   empty-cluster repair, 16-bit codebooks.  qadc_opq_train_device: the vectors already in device memory (read only, by kernels). */
 int qadc_opq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                         float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
@@ -433,6 +435,46 @@ int qadc_opq_train_host(const float* vectors, uint64_t n, int dim, int sq_count,
 int qadc_opq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                           float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
                           int* rounds_done_out, int div_mode, int sum_mode, int device_id);
+
+/* ---- k-means++ seeding: D^2 picks in every sub-space at once, the seed of the learning calls above. ----
+ *
+ * vectors [n][dim]; sq_count sub-spaces of dsub = dim / sq_count columns; k centres per sub-space; a 64-bit seed.  K_coarse,
+ * coarse, rotation: the learning set first goes through the trainers' front (qadc_pq_train_host's: residual to the nearest coarse
+ * centroid, then rotated; sum_mode 1) — x below is its output.  Sub-space m is seeded on columns [m dsub, (m + 1) dsub), independently:
+ *   Random numbers (splitmix64's finaliser, arithmetic mod 2^64):
+ *     z = seed + 0x9E3779B97F4A7C15 * ((((uint64)m << 32) | t) + 1);  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31;  u(m, t) = (double)(z >> 11) * 2^-53, in [0, 1).
+ *   Pick 0: row min(n - 1, (uint64)(u(m, 0) * (double)n)).
+ *   Distance of row i to a centre c: ONE float chain acc = fmaf(x[i][d] - c[d], x[i][d] - c[d], acc) from 0.0f over ascending d (the
+ *     direct form: a row's distance to itself is exactly 0).  mind_i starts at +inf and becomes d < mind_i ? d : mind_i after every
+ *     pick (a NaN never replaces).  Weight w_i = mind_i if mind_i < +inf, else 0: rows with a NaN or overflowing distance are never
+ *     drawn; picked rows and their exact duplicates weigh 0.
+ *   Sum tree, radix 64, indexed by the row alone (no launch geometry enters): level 0 is (double)w_i; node j of level L + 1 is the
+ *     balanced binary tree sum, in double, of nodes [64 j, 64 j + 64) of level L, missing nodes counting as 0.0 (a 64-lane
+ *     xor-butterfly gives exactly this value: double addition commutes).  Levels 1 and 2 always exist; above them the tree goes up
+ *     to the first level with a single node, the root.
+ *   Pick t >= 1: target = u(m, t) * root, in double.  From the root down, at a node its children are walked in ascending order
+ *     under a sequential double prefix c (c = c + child): the first child with target < c + child is entered and the walk goes on
+ *     below it with target - c.  If rounding leaves no such child, the last child with a value > 0 is entered, with its own prefix.
+ *     At level 0 the same rule names the row.  A zero child is never entered: the row has w > 0 and differs from every earlier centre.
+ *   Fallback: root == 0 (fewer distinct finite sub-vectors than k, or pick 0 hit a non-finite row) — the pick is the smallest row
+ *     index not yet picked in this sub-space; such picks are counted.
+ * Outputs (host memory): centres_out [sq_count][k][dsub] = the picked rows' sub-vectors of x, copied bit for bit; rows_out
+ * [sq_count][k] (nullable) their indices; fallbacks_out (nullable) the fallback picks of all sub-spaces.  Host twin:
+ * host/kmeans_seed.hpp kmeans_seed (behind host/db_build.hpp's pq_train_front); the device result equals it bit for bit.
+ * A run is k rounds on one stream (per round one pass over x for all sub-spaces, then one pick launch); synchronous.
+ * Refused with QADC_E_ARG before the first HIP call, the message naming the cause: NULL vectors or centres_out; n == 0 or
+ * n >= 2^32; k < 1 or k > n; sq_count outside [1, 32]; dim not a positive multiple of sq_count; dim > 4096; K_coarse < 0, or > 0
+ * without coarse; d_vectors not 4-byte aligned.  Limits: the learning set, its front copy, sq_count * n floats of distances and the
+ * tree are resident for the call; one device.  Not done: empty-cluster repair inside the training rounds, cv::kmeans' own variant
+ * (its local trials, its RNG), k-means||, learning sets larger than device memory, more than one device.
+ * qadc_kmeans_seed_device: the vectors already in device memory (read only, by kernels); every other pointer is host memory. */
+int qadc_kmeans_seed_host(const float* vectors, uint64_t n, int dim, int sq_count, int64_t k, int K_coarse, const float* coarse,
+                          const float* rotation, uint64_t seed, float* centres_out, uint32_t* rows_out, uint64_t* fallbacks_out,
+                          int device_id);
+int qadc_kmeans_seed_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int64_t k, int K_coarse, const float* coarse,
+                            const float* rotation, uint64_t seed, float* centres_out, uint32_t* rows_out, uint64_t* fallbacks_out,
+                            int device_id);
 
 /* Host-only helper (no GPU involved): push (keys[i], vals[i]), i = 0..n-1, in order into an empty
  * heap of capacity R with kv_binheap<unsigned,int8_t>::push semantics (binheap.hpp:75-116), after

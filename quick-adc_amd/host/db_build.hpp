@@ -9,12 +9,16 @@
 //                                          definition the device version is tested against bit for bit
 //   learn_coarse_quantizer_hip(...)        learn_coarse_quantizer (databases.cpp:94-118) from a caller-provided seed:
 //                                          the reference seeds with two OpenCV k-means++ iterations (third-party, absent
-//                                          here), then runs kmeans_iter_max - 2 = 48 fast iterations — those run on the GPU
+//                                          here), then runs kmeans_iter_max - 2 = 48 fast iterations — those run on the GPU.
+//                                          With a std::uint64_t seed instead of a seed array: seeded by seed_kmeanspp_hip
+//   kmeans_seed(..., K_coarse, coarse, rotation, ...)  CPU twin of qadc_kmeans_seed_host: host/kmeans_seed.hpp behind pq_train_front
+//   seed_kmeanspp_hip(...)                 k-means++ seeding on the GPU (qadc_kmeans_seed_host): [sq_count][k][dim / sq_count]
 //   pq_train_iterations(...)               CPU twin of qadc_pq_train_host: kmeans_fast_iterations on a copy of every sub-space's
 //                                          columns, behind the same residual / rotation front
 //   pq_train16_iterations(...), pq_update16(...)  the same for 16-bit sub-quantizers (qadc_pq_train16_host, qadc_pq_update16_host)
 //   learn_pq_hip(...)                      the product quantizer learned on the GPU from a caller-provided seed, as an io::pq_data
-//                                          ready for pq_to_data_file (the reference's flatdb_create / indexdb_create2 read it)
+//                                          ready for pq_to_data_file (the reference's flatdb_create / indexdb_create2 read it);
+//                                          with a std::uint64_t seed: seeded by seed_kmeanspp_hip (learn_opq_hip likewise)
 //   opq_cross(...), opq_train_iterations(...)  CPU twins of qadc_opq_cross_host and qadc_opq_train_host: the cross matrix between
 //                                          the learning set and its reconstruction, and the Procrustes rounds (host/procrustes.hpp)
 //                                          around pq_train_iterations
@@ -38,6 +42,7 @@
 #include "../../include/qadc.h"
 #include <cmath>
 
+#include "kmeans_seed.hpp"
 #include "procrustes.hpp"
 #include "qadc_io.hpp"
 #include "query_driver.hpp"
@@ -409,6 +414,48 @@ inline io::pq_data learn_opq_hip(const float* vecs, size_t n, int dim, int sq_co
     return pq;
 }
 
+// CPU twin of qadc_kmeans_seed_host (the definition it is tested against bit for bit): kmeans_seed of host/kmeans_seed.hpp on the
+// front's output.  centres [sq_count][k][dim / sq_count], rows [sq_count][k] (nullable); returns the fallback picks.
+inline std::uint64_t kmeans_seed(const float* vecs, size_t n, int dim, int sq_count, size_t k, int K_coarse, const float* coarse,
+                                 const float* rotation, std::uint64_t seed, float* centres, std::uint32_t* rows) {
+    if (!vecs || n == 0 || dim <= 0) throw std::runtime_error("kmeans_seed: vectors [n][dim], n > 0");
+    const std::vector<float> x = pq_train_front(vecs, n, dim, K_coarse, coarse, rotation);
+    return kmeans_seed(x.data(), n, dim, sq_count, k, seed, centres, rows);
+}
+
+// k-means++ seeding on the GPU (qadc_kmeans_seed_host): k D^2 picks in every sub-space at once -> [sq_count][k][dim / sq_count], the
+// sub-vectors of the picked rows of the learning set as the quantizer sees it (residuals to `coarse`, rotated, where given).
+// rows_out [sq_count][k] and fallbacks_out: nullable.
+inline std::vector<float> seed_kmeanspp_hip(const float* vecs, size_t n, int dim, int sq_count, size_t k, std::uint64_t seed, int K_coarse = 0,
+                                            const float* coarse = nullptr, const float* rotation = nullptr, int device = 0,
+                                            std::uint32_t* rows_out = nullptr, std::uint64_t* fallbacks_out = nullptr) {
+    if (sq_count <= 0 || dim <= 0 || dim % sq_count) throw std::runtime_error("seed_kmeanspp_hip: dim a positive multiple of sq_count");
+    std::vector<float> centres(k * (size_t)dim);
+    if (qadc_kmeans_seed_host(vecs, n, dim, sq_count, (std::int64_t)k, K_coarse, coarse, rotation, seed, centres.data(), rows_out, fallbacks_out,
+                              device) != QADC_OK)
+        throw std::runtime_error(std::string("qadc_kmeans_seed_host: ") + qadc_last_error());
+    return centres;
+}
+
+// learn_pq_hip / learn_opq_hip without a caller-made seed: the codebooks start from seed_kmeanspp_hip(k = 2^sq_bits) on the same front
+inline io::pq_data learn_pq_hip(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, std::uint64_t seed, int iters, int K_coarse = 0,
+                                const float* coarse = nullptr, const float* rotation = nullptr, int device = 0,
+                                std::uint64_t* empty_out = nullptr) {
+    if (sq_bits <= 0 || sq_bits > 16) throw std::runtime_error("learn_pq_hip: bad arguments");
+    const std::vector<float> start = seed_kmeanspp_hip(vecs, n, dim, sq_count, (size_t)1 << sq_bits, seed, K_coarse, coarse, rotation, device);
+    return learn_pq_hip(vecs, n, dim, sq_count, sq_bits, start.data(), iters, K_coarse, coarse, rotation, device, empty_out);
+}
+
+// (seeded under the start rotation, NULL: the identity)
+inline io::pq_data learn_opq_hip(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, std::uint64_t seed, int outer, int inner = 1,
+                                 int K_coarse = 0, const float* coarse = nullptr, const float* rotation = nullptr, int device = 0,
+                                 std::uint64_t* empty_out = nullptr, int* rounds_done_out = nullptr) {
+    if (sq_bits <= 0 || sq_bits > 16) throw std::runtime_error("learn_opq_hip: bad arguments");
+    const std::vector<float> start = seed_kmeanspp_hip(vecs, n, dim, sq_count, (size_t)1 << sq_bits, seed, K_coarse, coarse, rotation, device);
+    return learn_opq_hip(vecs, n, dim, sq_count, sq_bits, start.data(), outer, inner, K_coarse, coarse, rotation, device, empty_out,
+                         rounds_done_out);
+}
+
 constexpr int kmeans_iter_max = 50;                            // databases.cpp:92
 
 // `seed` [K][dim]: what the reference gets from cv::kmeans(KMEANS_PP_CENTERS, 2 iterations)
@@ -418,6 +465,14 @@ inline std::vector<float> learn_coarse_quantizer_hip(const float* vecs, size_t n
     if (qadc_kmeans_iterations_host(vecs, n, dim, K, centroids.data(), kmeans_iter_max - 2, nullptr, device) != QADC_OK)
         throw std::runtime_error(std::string("qadc_kmeans_iterations_host: ") + qadc_last_error());
     return centroids;
+}
+
+// The same without a caller-made seed: K k-means++ picks on the whole vectors (seed_kmeanspp_hip with one sub-space) stand in for the
+// reference's two OpenCV iterations, then the kmeans_iter_max - 2 fast iterations.
+inline std::vector<float> learn_coarse_quantizer_hip(const float* vecs, size_t n, int dim, int K, std::uint64_t seed, int device = 0) {
+    if (K <= 0) throw std::runtime_error("learn_coarse_quantizer_hip: K > 0");
+    const std::vector<float> start = seed_kmeanspp_hip(vecs, n, dim, 1, (size_t)K, seed, 0, nullptr, nullptr, device);
+    return learn_coarse_quantizer_hip(vecs, n, dim, K, start.data(), device);
 }
 
 }  // namespace qadc

@@ -52,6 +52,7 @@ SYMBOLS = [
     "qadc_pq_train_host", "qadc_pq_train_device",
     "qadc_pq_train16_host", "qadc_pq_train16_device", "qadc_pq_update16_host",
     "qadc_opq_cross_host", "qadc_opq_cross_device", "qadc_procrustes_host", "qadc_opq_train_host", "qadc_opq_train_device",
+    "qadc_kmeans_seed_host", "qadc_kmeans_seed_device",
     "qadc_adc_filter_create", "qadc_adc_filter_create_device", "qadc_adc_filter_info", "qadc_adc_filter_destroy", "qadc_adc_index_set_filter",
     "qadc_adc_query_scan_filtered", "qadc_adc_query_scan_device_filtered", "qadc_adc_query_scan_candidates_filtered",
     "qadc_adc_search_filtered", "qadc_adc_search_device_filtered", "qadc_adc_search_candidates_filtered",
@@ -273,6 +274,9 @@ def lib():
         L.qadc_opq_train_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_void_p,
                                           u64p, i32p, C.c_int, C.c_int, C.c_int]
         L.qadc_opq_train_device.argtypes = [C.c_void_p] + L.qadc_opq_train_host.argtypes[1:]
+        L.qadc_kmeans_seed_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_int, f32p, f32p, C.c_uint64, f32p, u32p, u64p,
+                                            C.c_int]
+        L.qadc_kmeans_seed_device.argtypes = [C.c_void_p] + L.qadc_kmeans_seed_host.argtypes[1:]
         for name in ("qadc_adc_index_remove_labels", "qadc_index_remove_labels"):
             getattr(L, name).argtypes = [C.c_void_p, u32p, C.c_uint64, u64p]
             getattr(L, name + "_device").argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p]
@@ -794,6 +798,67 @@ def pq_seed(vectors, sq_count, bits, rng):
         raise QadcError("pq_seed needs dim %% sq_count == 0 and at least %d vectors" % K)
     rows = v[rng.choice(n, K, replace=False)]
     return np.ascontiguousarray(rows.reshape(K, sq_count, dim // sq_count).transpose(1, 0, 2))
+
+
+def _kmeans_seed_args(n, dim, k, sq_count, seed, coarse, rotation):
+    if int(sq_count) != sq_count or sq_count < 1 or dim % sq_count:
+        raise QadcError("dim %d is not a multiple of sq_count %s" % (dim, sq_count))
+    if int(k) != k or k < 1 or k > n:
+        raise QadcError("need 1 <= k <= n centres per sub-space, not k = %s with n = %d" % (k, n))
+    if int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise QadcError("seed must be an integer in [0, 2^64)")
+    co = None if coarse is None else np.ascontiguousarray(coarse, np.float32)
+    rot = None if rotation is None else np.ascontiguousarray(rotation, np.float32)
+    if rot is not None and rot.shape != (dim, dim):
+        raise QadcError("rotation has shape %s, expected [%d][%d]" % (tuple(rot.shape), dim, dim))
+    if co is not None and (co.ndim != 2 or co.shape[1] != dim or co.shape[0] == 0):
+        raise QadcError("coarse has shape %s, expected [K][%d]" % (tuple(co.shape), dim))
+    sq_count, k = int(sq_count), int(k)
+    return co, rot, np.zeros((sq_count, k, dim // sq_count), np.float32), np.zeros((sq_count, k), np.uint32)
+
+
+def _kmeans_seed_result(centres, rows, fallbacks, return_rows):
+    c = centres[0] if centres.shape[0] == 1 else centres
+    return (c, rows[0] if centres.shape[0] == 1 else rows, int(fallbacks.value)) if return_rows else c
+
+
+def kmeans_seed(vectors, k, sq_count=1, seed=0, coarse=None, rotation=None, device=0, return_rows=False):
+    """k-means++ seeding on the GPU (qadc_kmeans_seed_host): k D^2 picks in each of sq_count sub-spaces at once, from the 64-bit
+    `seed` (include/qadc.h states every bit).  With coarse [K][dim] the learning set is first made residuals to the nearest coarse
+    centroid, with rotation [dim][dim] those are rotated, as the trainers do.  -> centres float32 [k][dim] for sq_count == 1 (a seed
+    for kmeans_iterations), else [sq_count][k][dim / sq_count] (a seed for train_pq / train_pq16 / train_opq): the picked rows'
+    sub-vectors, bit for bit.  return_rows: -> (centres, rows uint32 [k] or [sq_count][k], fallbacks) — fallbacks counts picks taken in
+    index order because no weight was left (fewer distinct finite sub-vectors than k)."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2:
+        raise QadcError("vectors has shape %s, expected [n][dim]" % (tuple(v.shape),))
+    n, dim = v.shape
+    co, rot, centres, rows = _kmeans_seed_args(n, dim, k, sq_count, seed, coarse, rotation)
+    fallbacks = C.c_uint64(0)
+    _check(lib().qadc_kmeans_seed_host(_p(v, f32p), n, dim, int(sq_count), int(k), 0 if co is None else co.shape[0], _p(co, f32p),
+                                       _p(rot, f32p), int(seed), _p(centres, f32p), _p(rows, u32p), C.byref(fallbacks), device))
+    return _kmeans_seed_result(centres, rows, fallbacks, return_rows)
+
+
+def kmeans_seed_device(vectors, k, sq_count=1, seed=0, coarse=None, rotation=None, return_rows=False):
+    """kmeans_seed on a learning set already in device memory: a contiguous float32 [n][dim] torch tensor on a GPU (read only).
+    coarse and rotation are host arrays; the results come back as numpy arrays like kmeans_seed's."""
+    n, dim = _device_vectors(vectors, "kmeans_seed_device")
+    co, rot, centres, rows = _kmeans_seed_args(n, dim, k, sq_count, seed, coarse, rotation)
+    fallbacks = C.c_uint64(0)
+    _check(lib().qadc_kmeans_seed_device(C.c_void_p(vectors.data_ptr()), n, dim, int(sq_count), int(k), 0 if co is None else co.shape[0],
+                                         _p(co, f32p), _p(rot, f32p), int(seed), _p(centres, f32p), _p(rows, u32p), C.byref(fallbacks),
+                                         vectors.device.index or 0))
+    return _kmeans_seed_result(centres, rows, fallbacks, return_rows)
+
+
+def pq_seed_pp(vectors, sq_count, bits, seed, **kw):
+    """A k-means++ seed for train_pq / train_pq16 / train_opq: kmeans_seed with k = 2^bits -> float32 [sq_count][2^bits][dim / sq_count]
+    (pq_seed's shape; `seed` is an integer, and the keywords are kmeans_seed's)."""
+    out = kmeans_seed(vectors, 1 << bits, sq_count=sq_count, seed=seed, **kw)
+    if sq_count != 1:
+        return out
+    return (out[0][None], out[1][None], out[2]) if kw.get("return_rows") else out[None]
 
 
 def coarse_assign(queries, coarse, ma, device=0):

@@ -1,9 +1,9 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,filter,qfilter,refine,range,keyed,knn] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,opq,filter] [--iters N] [--out FILE]
-  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,filter] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,opq,seed,filter] [--iters N] [--out FILE]
+  python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,seed,filter] [--iters N] [--out FILE]
 
   flat1e8   flat 8x8 list of 10^8 codes, one query per call: codes/s and its share of the 8 TB/s HBM roofline at 8 B per code
   batch32   32 queries per call on the same list
@@ -42,6 +42,11 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             with the rotation, opq_cross, procrustes: the learning set uploaded twice per outer round); the two routes' arrays are
             first asserted identical.  Beside it train_pq with ten rounds, and the reconstruction error
             (tests/pq_train_compose.reconstruction_error) of the learned pair against plain PQ's at those ten rounds
+  seed      k-means++ seeding (not in the default legs; also under --bits 4 at 16x4 and --bits 16 at 2x16): 10^6
+            clustered 128-d vectors; kmeans_seed per call at the index shape (and for K = 4096 coarse centroids at 8 bits), a round's
+            time from the difference of a k and a k / 2 call and the bytes per second of its one pass over the learning set, one
+            thread of the CPU twin per round, and the mean squared quantization error and the empty clusters after the train leg's
+            rounds from kmeans_seed and from pq_seed.
   filter    filtered search (not in the default legs; also under --bits 4 at 16x4 and --bits 16 at 4x16, part (a) only; DESIGN.md
             section 11.10): (a) one synchronous query on 10^8 labelled codes (10^6 at --bits 4 and 16), unfiltered, EXCLUDE of 1 % and
             50 % of the keys, ALLOW of 1 % and 0.01 %, each checked against an index built without the dropped rows; (b) search() of
@@ -727,6 +732,8 @@ def view_legs(legs, iters, res):
         train_leg(4, iters, res)
     if "opq" in legs:
         opq_leg(4, iters, res)
+    if "seed" in legs:
+        seed_leg(4, iters, res)
 
 
 def cpu_twin_u16_us(nsq, codes, table, repeat=5):
@@ -981,6 +988,74 @@ def opq_leg(bits, iters, res):
           "OPQ %.4g, PQ %.4g (%.3f of it; %d and %d empty clusters)"
           % (nsq, bits, n, outer, inner, inner, rounds, med_new, med_old, med_old / med_new, rounds, t_pq, err_opq, err_pq, err_opq / err_pq,
              got[3], pq_empty), flush=True)
+
+
+def cpu_twin_seed_round_s(vectors, sq_count):
+    """seconds per round of one thread of the host twin (host/kmeans_seed.hpp through tests/cpp/kmeans_seed_host.cpp): the
+    difference of a k = 5 and a k = 3 run of its driver, halved — the file's read and the process start cancel"""
+    import subprocess
+    import tempfile
+    n, dim = vectors.shape
+    with tempfile.TemporaryDirectory() as d:
+        exe, fin, fout = os.path.join(d, "twin"), os.path.join(d, "in"), os.path.join(d, "out")
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", os.path.join(ROOT, "tests", "cpp", "kmeans_seed_host.cpp"), "-o", exe])
+        ts = []
+        for k in (3, 5):
+            with open(fin, "wb") as f:
+                np.array([n, dim, sq_count, k, 0, 0, 1, 1], np.uint64).tofile(f)
+                vectors.tofile(f)
+            t0 = time.perf_counter()
+            subprocess.run([exe, "rows", fin, fout], stdout=subprocess.PIPE, check=True)
+            ts.append(time.perf_counter() - t0)
+    return (ts[1] - ts[0]) / 2
+
+
+def seed_leg(bits, iters, res):
+    """k-means++ seeding: kmeans_seed per call, the update launches' bytes per second, the CPU twin per
+    round, and the quantization error and empty clusters after the leg's usual training rounds from kmeans_seed and from pq_seed"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pq_train16_compose as p16c
+    import pq_train_compose as ptc
+    rng = np.random.default_rng(2300 + bits)
+    n, dim = 1_000_000, 128
+    nsq, rounds = {4: (16, 10), 8: (8, 10), 16: (2, 2)}[bits]
+    vectors, _ = clustered(rng, n, dim)
+    shapes = [("pq_%dx%d" % (nsq, bits), nsq, 1 << bits)] + ([("coarse_K4096", 1, 4096)] if bits == 8 else [])
+    for name, S, k in shapes:
+        tag = "seed_%s_n%d" % (name, n)
+        count = 1 if k > 4096 else max(3, iters // 3)
+        full_s, _ = timed(lambda: pyqadc.kmeans_seed(vectors, k, sq_count=S, seed=1), count, warmup=0 if k > 4096 else 1)
+        half_s, _ = timed(lambda: pyqadc.kmeans_seed(vectors, k // 2, sq_count=S, seed=1), count, warmup=0)
+        round_s = (full_s - half_s) / (k - k // 2)                # the upload and the fixed costs cancel
+        round_bytes = n * dim * 4 + 2 * n * S * 4
+        twin_s = cpu_twin_seed_round_s(vectors, S)
+        res[tag + "_call_s"] = full_s
+        res[tag + "_half_k_call_s"] = half_s
+        res[tag + "_round_s"] = round_s
+        res[tag + "_round_bytes"] = round_bytes
+        res[tag + "_round_bytes_per_s"] = round_bytes / round_s
+        res[tag + "_cpu_twin_round_s"] = twin_s
+        print("k-means++ seeding %s, k = %d in %d sub-spaces, %.0e clustered 128-d vectors, host to host: %.3f s per call (k / 2: %.3f s); a "
+              "round (update + pick) %.1f us = %.2f TB/s of its %d MB; the CPU twin on one thread %.3f s per round"
+              % (name, k, S, n, full_s, half_s, round_s * 1e6, round_bytes / round_s / 1e12, round_bytes >> 20, twin_s), flush=True)
+    # the quality after the leg's usual rounds, from both seeds on the same data
+    K = 1 << bits
+    seeds = {"kmeans_seed": pyqadc.pq_seed_pp(vectors, nsq, bits, 1), "pq_seed": pyqadc.pq_seed(vectors, nsq, bits, rng)}
+    for who, seed in seeds.items():
+        if bits == 16:
+            cb, codes, empty = pyqadc.train_pq16(vectors, seed, rounds)
+            codes = pyqadc.adc_encode16(np.nan_to_num(cb, nan=1e18), vectors)[1]      # the codes under the final codebooks (empty clusters far away)
+            err = p16c.reconstruction_error(vectors, np.nan_to_num(cb, nan=1e18), codes)
+        else:
+            cb, codes, empty = pyqadc.train_pq(vectors, seed, rounds)
+            final = np.nan_to_num(cb, nan=1e18)
+            codes = pyqadc.pq_encode(final, vectors) if bits == 4 else pyqadc.adc_encode(final, vectors)[1]
+            err = ptc.reconstruction_error(vectors, final, codes)
+        tag = "seed_quality_%dx%d_n%d_%s" % (nsq, bits, n, who)
+        res[tag + "_mse"] = err / n
+        res[tag + "_empty_clusters"] = int(empty)
+        print("  %d rounds of train_pq%s from %s: mean squared quantization error %.4f, %d of %d clusters empty"
+              % (rounds, "16" if bits == 16 else "", who, err / n, empty, nsq * K), flush=True)
 
 
 def add_leg(bits, iters, res):
@@ -1290,6 +1365,8 @@ def word_legs(legs, iters, res):
         remove_leg(16, iters, res)
     if "train" in legs or "train_profile" in legs:
         train16_leg(iters, res, profile_only="train" not in legs)
+    if "seed" in legs:
+        seed_leg(16, iters, res)
     if "profile" in legs:
         n = 100_000_000
         idx = pyqadc.AdcIndex.create16(8)
@@ -1478,6 +1555,8 @@ def main():
         train_leg(8, a.iters, res)
     if "opq" in legs:
         opq_leg(8, a.iters, res)
+    if "seed" in legs:
+        seed_leg(8, a.iters, res)
     if "knn" in legs:
         knn_leg(a.iters, res, torch)
     line = json.dumps(res)

@@ -188,7 +188,18 @@ int qadc_index_read_codes(qadc_index* idx, int part, uint32_t first, uint32_t co
  *                                        after the query (incl. the (0,127) sentinel if it survived)
  *   status[q]   0 ok; 1 = qmax > 1e30: the reference prints "Max quantization bound too high" and
  *               exit(1)s (db_query_4.cpp:271-274); here the query is skipped (sizes[q] = 0)
- *   qmin[q], qmax[q], qtables[q][ma][M][16]   the quantizer inputs/outputs (diagnostics, parity) */
+ *   qmin[q], qmax[q], qtables[q][ma][M][16]   the quantizer inputs/outputs (diagnostics, parity)
+ * Non-finite tables follow the reference BUILD (compiled with -ffast-math):
+ *   - a pre-scan sum that is not below FLT_MAX (NaN of either sign, +inf, FLT_MAX) is never among the R smallest and
+ *     does not count towards them: with fewer than R sums below FLT_MAX, qmax = FLT_MAX and status[q] = 1;
+ *   - qmin is the build's min reduction: a NaN in the last table entry makes it NaN (nothing is clamped then, the
+ *     caller's tables stay as they are), a NaN elsewhere can leave it above the smallest entry;
+ *   - a NaN entry's int8 value is 127 (the worst score).  An entry below qmax whose scaled value is NaN or outside int32
+ *     is 0, otherwise the low byte of the truncation: entries below a qmin that overshoots come out NEGATIVE.  The
+ *     streaming int8 scans are exact for entries in [0, 127] only; the heap of such a query (found from the caller's
+ *     tables at collect time) is made from the exact saturating sums of every probed code instead, synchronously.
+ *     This covers the calls that return heaps from caller-supplied tables on unsharded partitions; the candidate-
+ *     stream forms, qadc_dist_collect and qadc_search do not detect it. */
 int qadc_query_scan(qadc_index* idx, int nq, int ma, const int32_t* assign, float* tables, int R,
                     uint32_t* keys, int8_t* values, int32_t* sizes, int32_t* status,
                     float* qmin, float* qmax, int8_t* qtables);

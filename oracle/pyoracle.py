@@ -238,6 +238,14 @@ def quantize_tables(tables, qmin, qmax, mode=1):
     return out
 
 
+def min_element_compiled(tables):
+    """*std::min_element over all tables as the reference build reduces it (orc_min_element_compiled): what query_scan's
+    qmin is before the clamp under quant_mode 1, NaN entries included."""
+    tb = np.ascontiguousarray(tables, np.float32)
+    lib().orc_min_element_compiled.restype = C.c_float
+    return np.float32(lib().orc_min_element_compiled(_p(tb, f32p), C.c_long(tb.size)))
+
+
 def tables_direct(centroids, vector, sum_mode=1):
     """Direct table form (compute_dists_single_simd_cg): centroids [M][16][dsq], vector [M*dsq] -> [M*16] float32."""
     cf = np.ascontiguousarray(centroids, np.float32)
@@ -302,7 +310,8 @@ def query_scan(M, parts, labels, keep, assign, tables, R, quant_mode=1, sum_mode
     rc = lib().orc_query_scan(M, pa, la, _p(sizes, u32p), C.c_float(keep), _p(assign, i32p), ma,
                               _p(tables, f32p), R, quant_mode, sum_mode, C.byref(qmin), C.byref(qmax),
                               _p(qt, i8p), _p(ok, u32p), _p(ov, i8p), C.byref(osz))
-    return dict(rc=rc, qmin=qmin.value, qmax=qmax.value, qtables=qt,
+    bits = [int(np.frombuffer(bytes(x), np.uint32)[0]) for x in (qmin, qmax)]     # (a NaN qmin keeps its sign and payload)
+    return dict(rc=rc, qmin=qmin.value, qmax=qmax.value, qmin_bits=bits[0], qmax_bits=bits[1], qtables=qt,
                 keys=ok[:osz.value].copy(), values=ov[:osz.value].copy())
 
 

@@ -583,17 +583,90 @@ int orc_scan_standard_u8(int NSQ, int nparts, const uint8_t* const* parts, const
  * mode 0: source-level  int8(((val - min) / delta)),  delta = (max - min) / 127   (44-55)
  * mode 1: as compiled by g++ 11.4 with the reference's flags (-O3 -ffast-math): one
  *         scale = 127.0f / (max - min), then int8((val - min) * scale)  (SURVEY.md §8 A5 [probe]).
- * The two can differ by 1 at bucket edges.  PARITY UNPINNED (see header).
+ * The two can differ by 1 at bucket edges.
+ *
+ * Non-finite entries, mode 1.  Read off the reference build (objdump -d of scanner_4::query_scan, where quantize_tables
+ * is inlined; 16 entries per iteration):
+ *   vcmpltps qmax,v            mask = v < qmax                 (ordered: false when either is NaN)
+ *   vsubps / vmulps            q = (v - qmin) * scale
+ *   vcvttps2dq                 r = trunc(q) as int32, 0x80000000 when q is NaN or outside [-2^31, 2^31)
+ *   vpand / vpackusdw / vpand / vpackuswb                      the LOW BYTE of r (no saturation: the masks clear the
+ *                                                              upper bytes before each pack)
+ *   vpblendvb mask             out = mask ? low byte : 127
+ * So the compiled test is !(v < qmax) -> 127, not the source's v >= qmax: a NaN entry becomes 127, the worst score,
+ * where the source's operators would send it through the conversion.  An entry below qmax whose product is NaN or out of
+ * int32's range becomes 0; one inside the range wraps modulo 256.  Both are written out below in strict IEEE C.
+ * Mode 0 stays the source text (its conversion of an unrepresentable value is whatever cvttss2si gives: the same
+ * 0x80000000).  Pinned by tests/test_oracle_float_ref.py on NaN, infinite and FLT_MAX tables.
  * ---------------------------------------------------------------------------------------- */
+static inline int8_t orc_cvtt_low8(float q) {                     /* vcvttps2dq, then the low byte */
+    const int32_t r = (q >= -2147483648.0f && q < 2147483648.0f) ? (int32_t)q : INT32_MIN;
+    return (int8_t)(uint8_t)((uint32_t)r & 0xffu);
+}
+
 void orc_quantize_tables(const float* tables, long count, float qmin, float qmax, int mode, int8_t* out) {
     const float delta = (qmax - qmin) / 127;
     const float scale = 127.0f / (qmax - qmin);
     for (long i = 0; i < count; ++i) {
         const float v = tables[i];
-        if (v >= qmax) { out[i] = 127; continue; }
-        const float q = mode == 0 ? (v - qmin) / delta : (v - qmin) * scale;
-        out[i] = (int8_t)(int)q;
+        if (mode == 0) {
+            if (v >= qmax) { out[i] = 127; continue; }
+            out[i] = orc_cvtt_low8((v - qmin) / delta);
+        } else {
+            if (!(v < qmax)) { out[i] = 127; continue; }                  /* the compiled test: NaN -> 127 */
+            out[i] = orc_cvtt_low8((v - qmin) * scale);
+        }
     }
+}
+
+/* ------------------------------------------------------------------------------------------
+ * *std::min_element(tables, tables + all) — db_query_4.cpp:258, as compiled (the same build, the same function).
+ * -ffast-math lets g++ turn the iterator loop into a float min reduction; every step is one x86 MINPS / MINSS, whose
+ * result is  a < b ? a : b  with a = the FIRST source: the SECOND source comes back whenever either is NaN.  The loads
+ * are unaligned forms (VEX memory operands), there is no alignment peel: the result is a function of the values and of
+ * `all` alone.  With m = t[0] and the remaining all - 1 entries p[] = t + 1:
+ *   8 lanes      acc[j] = m;  for each whole block of 8:  acc[j] = acc[j] < p[8b + j] ? acc[j] : p[8b + j]
+ *                (the ACCUMULATOR is the first source: a NaN entry replaces it, and the entry after a NaN replaces the
+ *                NaN — a NaN forgets everything its lane saw before it)
+ *   reduce       r[j] = min(acc[4 + j], acc[j]);  s0 = min(r[2], r[0]);  s1 = min(r[3], r[1]);  m = min(s1, s0)
+ *                (min(a, b) = a < b ? a : b throughout)
+ *   4 lanes      when 4..7 entries are left:  u[j] = min(m, p[j]);  m = min(min(u[3], u[1]), min(u[2], u[0]))
+ *   scalar tail  up to 3 entries:  m = min(m, p[i])
+ * all is a multiple of 256, so all - 1 leaves 7: one 4-lane step over entries all-7 .. all-4 and three scalar steps.
+ * Consequences the tests pin: a NaN in the LAST entry is the result (then nothing is clamped, and every entry below qmax
+ * quantizes to 0); a NaN in one of the two entries before it leaves the minimum of what follows it; a NaN elsewhere
+ * hides the entries its lane saw before it, so the result can lie above the table's true minimum.
+ * ---------------------------------------------------------------------------------------- */
+static inline float orc_minps(float a, float b) { return a < b ? a : b; }
+
+float orc_min_element_compiled(const float* t, long all) {
+    float m = t[0];
+    const float* p = t + 1;
+    long left = all - 1, done = 0;
+    if (left <= 0) return m;
+    if (all > 8) {
+        float acc[8];
+        for (int j = 0; j < 8; ++j) acc[j] = m;
+        const long blocks = left >> 3;
+        for (long b = 0; b < blocks; ++b)
+            for (int j = 0; j < 8; ++j) acc[j] = orc_minps(acc[j], p[8 * b + j]);
+        float r[4];
+        for (int j = 0; j < 4; ++j) r[j] = orc_minps(acc[4 + j], acc[j]);
+        const float s0 = orc_minps(r[2], r[0]), s1 = orc_minps(r[3], r[1]);
+        m = orc_minps(s1, s0);
+        done = blocks * 8;
+        left -= done;
+    }
+    if (left > 3) {
+        float u[4];
+        for (int j = 0; j < 4; ++j) u[j] = orc_minps(m, p[done + j]);
+        const float v0 = orc_minps(u[2], u[0]), v1 = orc_minps(u[3], u[1]);
+        m = orc_minps(v1, v0);
+        done += 4;
+        left -= 4;
+    }
+    for (long i = 0; i < left && i < 3; ++i) m = orc_minps(m, p[done + i]);
+    return m;
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -819,7 +892,11 @@ int orc_query_scan(int M, const uint8_t* const* all_parts, const uint32_t* const
     /* qmin + clamp (258-269) */
     const long all = (long)ma * table_dim;
     float qmin = tables[0];
-    for (long i = 1; i < all; ++i) if (tables[i] < qmin) qmin = tables[i];
+    if (quant_mode == 0) {
+        for (long i = 1; i < all; ++i) if (tables[i] < qmin) qmin = tables[i];
+    } else {
+        qmin = orc_min_element_compiled(tables, all);             /* the min reduction the build runs (see above) */
+    }
     if (qmin < 0) {
         qmin = 0;
         for (long i = 0; i < all; ++i) if (tables[i] < 0) tables[i] = 0;

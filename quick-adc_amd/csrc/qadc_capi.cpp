@@ -10,6 +10,7 @@
 // The product path never touches oracle/: if the HIP runtime or the GPU is missing every entry
 // point fails loudly with QADC_E_HIP.
 #include "qadc_host.h"
+#include <cstdint>
 
 using namespace qadc;
 using namespace qadc::host;
@@ -478,6 +479,7 @@ int submit_common(qadc_index* idx, int slot_i, int nq, int ma, const int32_t* as
     s.R = R;
     s.float_path = tables != nullptr;
     s.tables = tables;
+    s.signed_q.clear();
     s.device_tables = false;
     s.assign.assign(assign, assign + (size_t)nq * ma);
     if (qtables) {
@@ -960,7 +962,17 @@ int collect_common(qadc_index* idx, int slot_i, bool need_stream, bool from_dist
     return QADC_OK;
 }
 
+// QuantizerMAX<int8_t> of one entry as the fronts evaluate it (csrc/qadc_front_nonfinite.h: qadc_quantize_entry), same IEEE steps
+static int8_t quantize_entry_host(float v, float qmin, float qmax, float scale, float delta, int quant_mode) {
+    if (quant_mode == 0 ? v >= qmax : !(v < qmax)) return 127;
+    const volatile float d = v - qmin;                         // (one rounding per step: no contraction)
+    const float x = quant_mode == 0 ? d / delta : d * scale;
+    const int32_t r = (x >= -2147483648.0f && x < 2147483648.0f) ? (int32_t)x : INT32_MIN;
+    return (int8_t)(uint8_t)((uint32_t)r & 0xffu);
+}
+
 void finish_float_outputs(qadc_index* idx, Slot& s, int32_t* status, float* qmin, float* qmax) {
+    s.signed_q.clear();
     const size_t per_q = (size_t)s.ma * idx->M * 16;
     const int stride = s.wgq ? s.wgq_G : 1;                      // (a query's workgroups report the same qmin / qmax / flags)
     for (int q = 0; q < s.nq; ++q) {
@@ -979,15 +991,91 @@ void finish_float_outputs(qadc_index* idx, Slot& s, int32_t* status, float* qmin
             for (size_t i = 0; i < per_q; ++i)
                 if (t[i] < 0) t[i] = 0;
         }
+        // A NaN entry can leave the reference build's qmin ABOVE finite entries (qadc_front_nonfinite.h), which then quantize below
+        // 0: the streaming scans are exact for [0, 127] only, so such a query's heap is made by replay_signed_query.  Without a
+        // NaN, qmin is the minimum and nothing is negative: one pass for a NaN, and only then the quantizer's own expression.
+        if (s.tables && !(qs.flags & 1u)) {
+            const float* t = s.tables + (size_t)q * per_q;
+            bool nan = false;
+            for (size_t i = 0; i < per_q; ++i) nan |= t[i] != t[i];
+            if (nan) {
+                const float delta = (qs.qmax - qs.qmin) / 127, scale = 127.0f / (qs.qmax - qs.qmin);
+                bool neg = false;
+                for (size_t i = 0; i < per_q && !neg; ++i) neg = quantize_entry_host(t[i], qs.qmin, qs.qmax, scale, delta, idx->quant_mode) < 0;
+                if (neg) {
+                    if (s.signed_q.size() != (size_t)s.nq) s.signed_q.assign(s.nq, 0);
+                    s.signed_q[q] = 1;
+                }
+            }
+        }
     }
+}
+
+// Heap of ONE query whose int8 tables hold negative entries: every probed partition's exact candidate values from
+// candidates_i8_signed_kernel (scan_avx_4's saturating chains), pushed by the reference's rule (simd_scan.hpp:63-187 as
+// oracle/qadc_oracle.c's scan_i8_blocks restates it): per block of 16 codes, push iff cand < the bound sampled at the block's
+// start, lanes past the end replay code n - 1, the bound is refreshed after a block with a push.  Rare (NaN tables): synchronous.
+// Returns false (nothing done) for a sharded partition.
+static bool replay_signed_query(qadc_index* idx, Slot& s, int q, kv_heap<uint32_t, int8_t>& bh) {
+    for (int a = 0; a < s.ma; ++a) {
+        const Part& p = idx->parts[s.assign[(size_t)q * s.ma + a]];
+        if (p.global_n != p.n || p.first_pos != 0) return false;
+    }
+    bh.reset();
+    bh.push(0, 127);
+    std::vector<int8_t> cand;
+    std::vector<uint32_t> labels;
+    for (int a = 0; a < s.ma; ++a) {
+        const Part& p = idx->parts[s.assign[(size_t)q * s.ma + a]];
+        if (p.n == 0) continue;
+        int8_t* d_o = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&d_o), p.n) != hipSuccess) return false;
+        launch_candidates_i8_signed(idx->M, p.d_codes, p.n, s.d_qt + ((size_t)q * s.ma + a) * idx->M * 16, d_o, idx->copy_stream);
+        cand.resize(p.n);
+        bool ok = hipMemcpyAsync(cand.data(), d_o, p.n, hipMemcpyDeviceToHost, idx->copy_stream) == hipSuccess;
+        if (ok && p.d_labels) {
+            labels.resize(p.n);
+            ok = hipMemcpyAsync(labels.data(), p.d_labels, sizeof(uint32_t) * p.n, hipMemcpyDeviceToHost, idx->copy_stream) == hipSuccess;
+        }
+        ok = hipStreamSynchronize(idx->copy_stream) == hipSuccess && ok;
+        (void)hipFree(d_o);
+        if (!ok) return false;
+        int8_t bound = bh.max();
+        for (uint64_t b0 = 0; b0 < p.n; b0 += 16) {
+            const int8_t bound_blk = bound;
+            bool any = false;
+            for (uint32_t j = 0; j < 16; ++j) {
+                const uint32_t ci = (uint32_t)std::min<uint64_t>(b0 + j, (uint64_t)p.n - 1);
+                if (cand[ci] < bound_blk) {
+                    bh.push(p.d_labels ? labels[ci] : p.key_base + ci, cand[ci]);
+                    any = true;
+                }
+            }
+            if (any) bound = bh.max();
+        }
+    }
+    return true;
 }
 
 int replay_outputs(qadc_index* idx, Slot& s, uint32_t* keys, int8_t* values, int32_t* sizes, const int32_t* status) {
     ScopedMs timer(idx->prof.host_heap_ms);
+    std::vector<uint8_t> done;                                   // queries answered by replay_signed_query
+    if (s.tables && s.signed_q.size() == (size_t)s.nq) {
+        kv_heap<uint32_t, int8_t> bh(s.R);
+        for (int q = 0; q < s.nq; ++q) {
+            if (!s.signed_q[q] || (status && status[q]) || !replay_signed_query(idx, s, q, bh)) continue;
+            if (done.empty()) done.assign(s.nq, 0);
+            done[q] = 1;
+            if (sizes) sizes[q] = bh.size();
+            if (keys) std::memcpy(keys + (size_t)q * s.R, bh.keys(), sizeof(uint32_t) * bh.size());
+            if (values) std::memcpy(values + (size_t)q * s.R, bh.values(), bh.size());
+        }
+    }
     auto work = [&](int q0, int q1) {
         kv_heap<uint32_t, int8_t> bh(s.R);
         for (int q = q0; q < q1; ++q) {
             bh.reset();
+            if (!done.empty() && done[q]) continue;
             if (status && status[q]) {
                 if (sizes) sizes[q] = 0;
                 continue;

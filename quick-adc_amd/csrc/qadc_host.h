@@ -144,6 +144,8 @@ struct Slot {
     int nq = 0, ma = 0, R = 0;
     float* tables = nullptr;            // caller's float tables (float path)
     std::vector<int32_t> assign;
+    std::vector<uint8_t> signed_q;      // [nq] 1 = the query's int8 tables hold a negative entry (a NaN made qmin overshoot): set by
+                                        // finish_float_outputs from the caller's tables, read by replay_outputs (replay_signed_query)
     std::vector<int8_t> qtables_in;     // int8 path input copy
     uint32_t cap_q = 0;                 // candidate region entries per query
     uint32_t out_cap = 0;               // entries of the device-sorted output

@@ -384,5 +384,8 @@ void launch_deinterleave(uint8_t* d_rowmajor, const uint8_t* d_inter, uint32_t n
 // All-code candidate values min(127, sum) (diagnostic / parity helper; not on the query path).
 void launch_candidates_i8(int M, const uint8_t* d_codes, uint64_t n, const int8_t* d_qtable, int8_t* d_out,
                           hipStream_t stream);
+// The same under a SIGNED int8 table: scan_avx_4's saturating chains, exact for entries in [-128, 127] (d_qtable on the device).
+void launch_candidates_i8_signed(int M, const uint8_t* d_codes, uint64_t n, const int8_t* d_qtable, int8_t* d_out,
+                                 hipStream_t stream);
 
 }  // namespace qadc

@@ -10,6 +10,7 @@
 // The op is a gather + byte add bound by HBM reads: no MFMA.
 #include "qadc_kernels.h"
 #include "qadc_float_sum.h"
+#include "qadc_front_nonfinite.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -2801,14 +2802,58 @@ void launch_candidates_i8(int M, const uint8_t* d_codes, uint64_t n, const int8_
     }
 }
 
+// All candidate values of a partition under a SIGNED int8 table, exactly as scan_avx_4<M> adds them (simd_scan.hpp:138-179):
+//   lo chain  T[0][p0.lo] (+) T[1][p0.hi] (+) T[4][p2.lo] (+) T[5][p2.hi] ...    hi chain  T[2][p1.lo] (+) T[3][p1.hi] (+) ...
+//   cand = hi (+) lo,   (+) = _mm256_adds_epi8: every partial sum saturates to [-128, 127]
+// Negative entries exist only when a NaN made the reference build's qmin overshoot finite table entries (qadc_front_nonfinite.h);
+// the streaming scan kernels, written for entries in [0, 127] where this equals min(127, sum), are not used for such a query:
+// the host replays these values through the reference's block-wise push rule (qadc_capi.cpp: replay_signed_query).
+__device__ __forceinline__ int sat_add8(int a, int b) { return max(-128, min(127, a + b)); }
+
+template <int M>
+__global__ __launch_bounds__(256) void candidates_i8_signed_kernel(const uint8_t* __restrict__ codes, uint64_t n,
+                                                                   const int8_t* __restrict__ qtable, int8_t* __restrict__ out) {
+    constexpr int CS = M / 2;
+    __shared__ int8_t qt[M * 16];
+    for (int i = threadIdx.x; i < M * 16; i += 256) qt[i] = qtable[i];
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint8_t* __restrict__ c = codes + i * CS;
+        int lo = 0, hi = 0;
+#pragma unroll
+        for (int r = 0; r < M / 4; ++r) {
+            const uint32_t p0 = c[2 * r], p1 = c[2 * r + 1];
+            const int a = qt[(4 * r) * 16 + (p0 & 15u)], b = qt[(4 * r + 1) * 16 + (p0 >> 4)];
+            const int cc = qt[(4 * r + 2) * 16 + (p1 & 15u)], d = qt[(4 * r + 3) * 16 + (p1 >> 4)];
+            if (r == 0) {
+                lo = sat_add8(b, a);
+                hi = sat_add8(d, cc);
+            } else {
+                lo = sat_add8(b, sat_add8(a, lo));
+                hi = sat_add8(d, sat_add8(cc, hi));
+            }
+        }
+        out[i] = (int8_t)sat_add8(hi, lo);
+    }
+}
+
+void launch_candidates_i8_signed(int M, const uint8_t* d_codes, uint64_t n, const int8_t* d_qtable, int8_t* d_out,
+                                 hipStream_t stream) {
+    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 2048));
+    if (M == 16) hipLaunchKernelGGL(candidates_i8_signed_kernel<16>, dim3(grid), dim3(256), 0, stream, d_codes, n, d_qtable, d_out);
+    else         hipLaunchKernelGGL(candidates_i8_signed_kernel<32>, dim3(grid), dim3(256), 0, stream, d_codes, n, d_qtable, d_out);
+}
+
 // ---------------------------------------------------------------------------------------------
 // float pre-scan of the "starts" (scan_4<M>, query_common.hpp:59-90): the same IEEE adds in the grouping
 // sum_mode names (qadc_float_sum.h): 1 = the reference as compiled with its -ffast-math, 0 = source order.
 // The 16 lanes-distinct entries of one table sit in 16 consecutive LDS dwords, so every lookup
 // instruction (all lanes in the same table) is bank-conflict-free without replication.
 // ---------------------------------------------------------------------------------------------
+// (of the value's RANK image: everything that is not below FLT_MAX — NaN sums of either sign, +inf — ranks as FLT_MAX, the
+// sentinel the reference's heap never lets them replace; qadc_front_nonfinite.h)
 __device__ __forceinline__ uint32_t fkey(float f) {
-    const uint32_t b = __float_as_uint(f);
+    const uint32_t b = __float_as_uint(qadc_prescan_rank_value(f));
     return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
 __device__ __forceinline__ float funkey(uint32_t k) {
@@ -3033,8 +3078,9 @@ __global__ __launch_bounds__(256) void start_scan_mq_kernel(const StartItem* __r
             for (int j = 0; j < kMQ; ++j) {
                 if (j >= nq) continue;
                 fc[(uint64_t)its[j].query * fc_stride + it.out_off + i] = cand[j];
-                vmin[j] = fminf(vmin[j], cand[j]);
-                vmax[j] = fmaxf(vmax[j], cand[j]);
+                const float rv = qadc_prescan_rank_value(cand[j]);   // (the key range is that of the rank images: fkey)
+                vmin[j] = fminf(vmin[j], rv);
+                vmax[j] = fmaxf(vmax[j], rv);
             }
         } else {
             bool any = false;
@@ -3045,7 +3091,7 @@ __global__ __launch_bounds__(256) void start_scan_mq_kernel(const StartItem* __r
 #pragma unroll
                 for (int j = 0; j < kMQ; ++j) {
                     if (j >= nq || !(cand[j] <= thr[j])) continue;
-                    vmin[j] = fminf(vmin[j], cand[j]);
+                    vmin[j] = fminf(vmin[j], cand[j]);               // (cand <= thr <= FLT_MAX: its own rank image)
                     vmax[j] = fmaxf(vmax[j], cand[j]);
                     const uint32_t ls = atomicAdd(&stage_n[j], 1u);
                     if (ls < (uint32_t)kStageQ) {
@@ -3195,14 +3241,15 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
                                uint8_t* __restrict__ bktw_sel) {
     const int t = threadIdx.x;
     float m = FLT_MAX;
-    for (int i = t; i < table_dim_all; i += BT) m = fminf(m, tb[i]);
+    for (int i = t; i < table_dim_all; i += BT) m = qadc_min_keep_nan(m, tb[i]);
     red[t] = m;
     __syncthreads();
     for (int d = BT / 2; d >= 1; d >>= 1) {
-        if (t < d) red[t] = fminf(red[t], red[t + d]);
+        if (t < d) red[t] = qadc_min_keep_nan(red[t], red[t + d]);
         __syncthreads();
     }
     float qmin = red[0];
+    if (qmin != qmin) qmin = qadc_min_element_compiled(tb, table_dim_all, red, t);   // a NaN entry: the build's own order decides
     uint32_t flags = 0;
     if (qmin < 0) { qmin = 0; flags |= 2u; }
     if ((double)qmax > 1e30) flags |= 1u;                       // (a double compare, as db_query_4.cpp:271: 1e30f itself is above 1e30)
@@ -3210,11 +3257,10 @@ __device__ void quantize_query(int table_dim_all, float* __restrict__ tb, int8_t
     const float scale = 127.0f / (qmax - qmin);
     for (int i = t; i < table_dim_all; i += BT) {
         float v = tb[i];
-        if (v < 0) { v = 0; tb[i] = 0; }
+        if ((flags & 2u) && v < 0) { v = 0; tb[i] = 0; }       // (the clamp runs only when qmin < 0: not under a NaN qmin)
         int8_t o;
         if (flags & 1u) o = 127;   // query is skipped by the host; emit nothing
-        else if (v >= qmax) o = 127;
-        else o = (int8_t)(int)(quant_mode == 0 ? (v - qmin) / delta : (v - qmin) * scale);
+        else o = qadc_quantize_entry(v, qmin, qmax, scale, delta, quant_mode);
         qt[i] = o;
     }
     if (plane_sel || plane_sel5 || nib_sel || bkt_sel || bktw_sel) {   // 16x4: the 6-, 5-plane, nibble and bucket forms' choices of each table

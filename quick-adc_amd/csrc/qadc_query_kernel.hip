@@ -33,6 +33,7 @@
 // level-structured path, and the head of a partition-major IVF batch).  gfx950 only.
 #include "qadc_kernels.h"
 #include "qadc_float_sum.h"
+#include "qadc_front_nonfinite.h"
 
 #include <atomic>
 #include <cfloat>
@@ -57,8 +58,9 @@ constexpr int kQWaves = kQWG / 64;
 
 extern __shared__ __attribute__((aligned(16))) unsigned char qsmem[];
 
+// (of the value's RANK image: NaN sums of either sign and +inf rank as FLT_MAX; qadc_front_nonfinite.h)
 __device__ __forceinline__ uint32_t q_fkey(float f) {
-    const uint32_t b = __float_as_uint(f);
+    const uint32_t b = __float_as_uint(qadc_prescan_rank_value(f));
     return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
 __device__ __forceinline__ float q_funkey(uint32_t k) {
@@ -237,7 +239,7 @@ __device__ __forceinline__ uint32_t q_wave_sum(uint32_t x) {     // the wave's t
 }
 __device__ __forceinline__ float q_wave_min(float x) {
     const uint32_t r = q_wave_scan_bits(__float_as_uint(x), __float_as_uint(FLT_MAX),
-                                        [](uint32_t a, uint32_t b) { return __float_as_uint(fminf(__uint_as_float(a), __uint_as_float(b))); });
+                                        [](uint32_t a, uint32_t b) { return __float_as_uint(qadc_min_keep_nan(__uint_as_float(a), __uint_as_float(b))); });
     return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)r, 63));
 }
 
@@ -741,7 +743,7 @@ __device__ __forceinline__ void scan_query_body(const QueryKernelArgs& A) {
 #pragma unroll
                 for (int k = 0; k < kTV; ++k) {
                     mytab[k * 64 + (int)lane] = cur.tv[k];
-                    if (sub == 0) lmin = fminf(lmin, cur.tv[k]);
+                    if (sub == 0) lmin = qadc_min_keep_nan(lmin, cur.tv[k]);
                 }
                 q_wave_lds_sync();
                 if (sub == 0 && sn) {
@@ -807,7 +809,8 @@ __device__ __forceinline__ void scan_query_body(const QueryKernelArgs& A) {
         __syncthreads();
         qmin = redf[0];
 #pragma unroll
-        for (int w = 1; w < kQWaves; ++w) qmin = fminf(qmin, redf[w]);
+        for (int w = 1; w < kQWaves; ++w) qmin = qadc_min_keep_nan(qmin, redf[w]);
+        if (qmin != qmin) qmin = qadc_min_element_compiled(ft_all, all, redf, (int)tid);   // a NaN entry: the build's own order decides
 
         STAMP(4);
         // ---- R-th smallest of the pre-scan values = tmp_bh.max() (db_query_4.cpp:259); FLT_MAX if fewer than R ----
@@ -1081,11 +1084,11 @@ __device__ __forceinline__ void scan_query_body(const QueryKernelArgs& A) {
                 const int i = i0 + u * kQWG;
                 if (i >= all) continue;
                 float v = tv[u];
-                if (v < 0) { v = 0; if (G == 1) ft_all[i] = 0; }    // (G > 1: another workgroup may still pre-scan the unclamped tables)
+                // (the clamp runs only when qmin < 0: not under a NaN qmin.  G > 1: another workgroup may still pre-scan the unclamped tables)
+                if ((flags & 2u) && v < 0) { v = 0; if (G == 1) ft_all[i] = 0; }
                 int8_t o;
                 if (flags & 1u) o = 127;
-                else if (v >= qmax) o = 127;
-                else o = (int8_t)(int)(A.quant_mode == 0 ? (v - qmin) / delta : (v - qmin) * scale);
+                else o = qadc_quantize_entry(v, qmin, qmax, scale, delta, A.quant_mode);
                 qt_all[i] = o;
                 if constexpr (RES) {                             // the first probed partition's table: straight into LDS as well
                     if (resident && i / (M * 16) == a_res) tq[i % (M * 16)] = (unsigned char)o;
@@ -1971,13 +1974,14 @@ __global__ __launch_bounds__(kQWG, 2) void lone_front_kernel(LoneFrontArgs A) {
     float qmax = FLT_MAX;                                        // (fewer starts than R: the reference's exit path)
     if (sn >= A.R) qmax = q_funkey(lf_select(keys, nk, A.R, scr, tid));
     float lmin = FLT_MAX;
-    for (uint32_t i = tid; i < (uint32_t)(M * 16); i += kQWG) lmin = fminf(lmin, tab[i]);
+    for (uint32_t i = tid; i < (uint32_t)(M * 16); i += kQWG) lmin = qadc_min_keep_nan(lmin, tab[i]);
     lmin = q_wave_min(lmin);
     if (lane == 0) s_red[wave] = lmin;
     __syncthreads();
     float qmin = s_red[0];
 #pragma unroll
-    for (int w = 1; w < kQWaves; ++w) qmin = fminf(qmin, s_red[w]);
+    for (int w = 1; w < kQWaves; ++w) qmin = qadc_min_keep_nan(qmin, s_red[w]);
+    if (qmin != qmin) qmin = qadc_min_element_compiled(tab, M * 16, s_red, (int)tid);   // a NaN entry: the build's own order decides
     uint32_t flags = 0;
     if (qmin < 0) { qmin = 0; flags |= 2u; }
     if ((double)qmax > 1e30) flags |= 1u;
@@ -1985,11 +1989,10 @@ __global__ __launch_bounds__(kQWG, 2) void lone_front_kernel(LoneFrontArgs A) {
     const float scale = 127.0f / (qmax - qmin);
     for (uint32_t i = tid; i < (uint32_t)(M * 16); i += kQWG) {
         float v = tab[i];
-        if (v < 0) v = 0;
+        if ((flags & 2u) && v < 0) v = 0;                        // (the clamp runs only when qmin < 0: not under a NaN qmin)
         int8_t o;
         if (flags & 1u) o = 127;
-        else if (v >= qmax) o = 127;
-        else o = (int8_t)(int)(A.quant_mode == 0 ? (v - qmin) / delta : (v - qmin) * scale);
+        else o = qadc_quantize_entry(v, qmin, qmax, scale, delta, A.quant_mode);
         A.qtables[i] = o;
     }
     if (tid == 0) {

@@ -6,7 +6,8 @@ tests/test_oracle_float_ref.py::test_coarse_selection_on_non_finite_distances_is
 here is that selection on the oracle's coarse distances (and, where oracle/_ref is built, the reference's own selection too) —
 never numpy's argmin / argsort, which order NaN differently.  Every assign[] entry must also lie in [0, K).
 
-Out of scope: qadc_search end to end with NaN centroids or queries (NaN float tables through the pre-scan and QuantizerMAX)."""
+NaN and infinite float tables through the pre-scan, qmin and QuantizerMAX (query_scan, qadc_search with a NaN query vector) are
+tests/test_gpu_nonfinite_tables.py's.  Out of scope: qadc_search refusing a NaN coarse row with ma > 256."""
 import numpy as np
 import pytest
 

@@ -181,6 +181,229 @@ def test_query_scan_whole_matches_the_reference_as_compiled(po, M):
     assert nq >= 4500
 
 
+# ---- NaN, +-inf and +-FLT_MAX tables: the float front as the reference BUILD runs it (oracle/qadc_oracle.c: orc_min_element_compiled,
+# orc_quantize_tables; the start scan needs no special rule: cand < top never holds for a NaN)
+def _bits(b):
+    return np.array([b], np.uint32).view(np.float32)[0]
+
+
+NF_NAN = (0x7fc00000, 0xffc00000)
+NF_VALUES = NF_NAN + (0x7f800000, 0xff800000, 0x7f7fffff, 0xff7fffff, 0x7fffffff, 0xffffffff)
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
+
+
+def _aligned_copy(tables, offset_floats):
+    """A C-contiguous copy of `tables` that starts `offset_floats` floats past a 64-byte boundary."""
+    buf = np.zeros(tables.size + 32, np.float32)
+    first = (-(buf.ctypes.data // 4)) % 16 + offset_floats
+    out = buf[first:first + tables.size].reshape(tables.shape)
+    out[...] = tables
+    assert out.flags.c_contiguous and (out.ctypes.data // 4) % 16 == offset_floats % 16
+    return out
+
+
+def _check_whole_against_reference(po, sc, M, parts, labels, keep, assign, tables, R, tag, may_exit=False, offset=0):
+    """start heap, exit status, final heap, in-place clamp (as bits) of the reference build == the oracle's; the build's own
+    QuantizerMAX instance on the clamped tables with the oracle's (qmin, qmax) == the oracle's int8 tables."""
+    starts = [parts[p][:po.start_size(parts[p].shape[0], keep)] for p in assign]
+    fk, fv = sc.query_start(assign, tables, R)
+    ok, ov = po.scan4_start(M, starts, None if labels is None else [labels[p][:len(s)] for p, s in zip(assign, starts)], tables, R)
+    assert np.array_equal(fk, ok) and _same_bits(fv, ov), tag
+    assert not np.isnan(fv).any(), tag                            # the binary never pushes a NaN candidate
+    ot = _aligned_copy(tables, offset)
+    want = po.query_scan(M, parts, labels, keep, assign, ot, R)
+    assert want["qmax_bits"] == int(fv[:1].view(np.uint32)[0]), tag
+    code = sc.try_query(assign, tables, R) if may_exit else 0
+    assert (float(fv[0]) > 1e30) == bool(code) if may_exit else float(fv[0]) <= 1e30, tag
+    assert want["rc"] == code, tag
+    if code:
+        return want
+    rt = _aligned_copy(tables, offset)
+    hk, hv = sc.query_scan(assign, rt, R)
+    assert np.array_equal(hk, want["keys"]) and np.array_equal(hv, want["values"]), tag
+    assert _same_bits(rt, ot), tag                                # the clamp: negatives to +0 only when qmin < 0, NaN bits kept
+    qt = po.reff_quantize_tables(rt.reshape(len(assign), M, 16), _bits(want["qmin_bits"]), fv[0])
+    assert np.array_equal(qt, want["qtables"]), tag
+    return want
+
+
+@pytest.mark.parametrize("M", [16, 32])
+def test_one_nan_at_every_table_entry_matches_the_reference_as_compiled(po, M):
+    """One NaN swept over EVERY entry of the tables, ma = 1 and 3, both NaN signs, with and without negative entries, the tables at
+    two alignments (the build's min reduction uses unaligned loads and has no peel: orc_min_element_compiled is a function of the
+    values alone).  The NaN's position decides qmin — a lane of the reduction forgets what it saw before a NaN, a NaN in the last
+    entry IS qmin, one in the two entries before it leaves only what follows — and through it the int8 tables and the final heap."""
+    _need_ref_float(po)
+    rng = np.random.default_rng(4100 + M)
+    sizes = [4000, 3500, 4500]
+    parts = [rand_codes(rng, s, M) for s in sizes]
+    labels = [np.arange(s, dtype=np.uint32) * 3 + i for i, s in enumerate(sizes)]
+    keep, R, n = np.float32(0.05), 100, 0
+    qmins = set()
+    for ma in (1, 3):
+        sc = po.RefScanner4(M, parts[:ma], labels[:ma], keep)
+        assign = np.arange(ma, dtype=np.int32)
+        plain, negs = rand_tables(rng, ma, M), rand_tables(rng, ma, M, negatives=True)
+        for bits in NF_NAN:
+            for e in range(ma * M * 16):
+                for base in ((plain, negs) if e % 4 == 0 or e >= ma * M * 16 - 8 else (plain,)):
+                    t = base.copy()
+                    t.reshape(-1)[e] = _bits(bits)
+                    w = _check_whole_against_reference(po, sc, M, parts[:ma], labels[:ma], keep, assign, t, R, (ma, hex(bits), e),
+                                                       offset=(0 if e % 3 else 5))
+                    qmins.add(("nan" if np.isnan(w["qmin"]) else "above" if w["qmin"] > max(0, np.nanmin(t)) else "min", base is negs))
+                    n += 1
+        sc.close()
+    assert n >= 2 * 4 * M * 16 * 5 // 4
+    # every outcome of the rule was met (a NaN two or three entries before the end hides ALL the negatives: a positive qmin, no clamp)
+    assert qmins == {(k, b) for k in ("nan", "above", "min") for b in (False, True)}
+
+
+@pytest.mark.parametrize("M", [16, 32])
+def test_query_scan_on_nonfinite_tables_matches_the_reference_as_compiled(po, M):
+    """Random non-finite tables through the reference's scanner_4, whole, and orc_query_scan: single entries, whole rows, sparse
+    entries and whole tables of NaN (both signs, two payloads), +-inf and +-FLT_MAX, alone and mixed, with negatives, flat and IVF,
+    R = 1 / 10 / 100, tie-rounded tables; rows of +inf and -inf whose sums are NaN, in numbers that leave about R pushable starts,
+    so that the "Max quantization bound too high" exit is taken on both sides of its edge."""
+    _need_ref_float(po)
+    rng = np.random.default_rng(5200 + M)
+    nexit = nrun = 0
+    for db in range(6):
+        ivf = db % 2 == 1
+        sizes = [int(s) for s in rng.integers(1500, 5000, 5)] if ivf else [int(rng.integers(15000, 25000))]
+        parts = [rand_codes(rng, s, M) for s in sizes]
+        labels = [rng.integers(0, 2 ** 32, s, dtype=np.uint64).astype(np.uint32) for s in sizes] if ivf else None
+        keep = np.float32(0.05)
+        sc = po.RefScanner4(M, parts, labels, keep)
+        for q in range(120):
+            ma = int(rng.integers(2, 5)) if ivf else 1
+            assign = rng.permutation(len(sizes))[:ma].astype(np.int32)
+            R = int(rng.choice([1, 10, 100, 100]))
+            t = rand_tables(rng, ma, M, negatives=(q % 3 == 0))
+            if q % 7 == 0:
+                t = (np.round(t / t.max() * 6) * np.float32(0.5)).astype(np.float32)
+            flat, kind = t.reshape(-1), q % 6
+            vals = [_bits(b) for b in (NF_VALUES if q % 2 else NF_NAN)]
+            if kind == 0:
+                flat[int(rng.integers(flat.size))] = vals[q % len(vals)]
+            elif kind == 1:
+                r = int(rng.integers(ma * M))
+                flat[r * 16:r * 16 + 16] = [vals[(q + i) % len(vals)] for i in range(16)]
+            elif kind == 2:
+                for e in rng.choice(flat.size, 12, replace=False):
+                    flat[e] = vals[int(rng.integers(len(vals)))]
+            elif kind == 3:                                         # NaN sums: +inf in some rows, -inf in others
+                for r, v in ((1, 0x7f800000), (2, 0x7f800000), (3, 0x7f800000), (6, 0xff800000)):
+                    flat[r * 16:r * 16 + int(rng.integers(4, 12))] = _bits(v)
+            elif kind == 4:                                         # most starts NaN: around the exit's edge
+                flat[:int(rng.integers(12, 16))] = vals[q % 2]
+                for e in rng.choice(np.arange(16, M * 16), int(rng.integers(0, 5)), replace=False):
+                    flat[e] = vals[(q + 1) % 2]
+            else:
+                flat[:] = vals[q % len(vals)] if q % 12 == 5 else flat
+                flat[-1 - int(rng.integers(0, 8))] = vals[q % len(vals)]
+            w = _check_whole_against_reference(po, sc, M, parts, labels, keep, assign, t, R, (db, q), may_exit=True, offset=q % 4)
+            nexit += w["rc"]
+            nrun += 1 - w["rc"]
+        sc.close()
+    assert nexit >= 20 and nrun >= 300
+
+
+def test_quantizer_on_nonfinite_entries_and_bounds_matches_the_reference_as_compiled(po):
+    """QuantizerMAX<int8_t> of the build on NaN / inf / FLT_MAX entries and on the bounds the non-finite rules produce: a NaN qmin,
+    qmin above qmax, qmax = -inf, qmax = qmin.  A NaN entry is 127; a product that is NaN or outside int32 is 0; the rest is the
+    low byte of the truncation (no saturation)."""
+    _need_ref_float(po)
+    rng = np.random.default_rng(77)
+    seen127 = seen_wrap = 0
+    for t in range(400):
+        qmin, qmax = np.float32(rng.random() * 2), np.float32(2 + rng.random() * 50)
+        if t % 8 == 1:
+            qmin = _bits(NF_NAN[t % 2])
+        elif t % 8 == 2:
+            qmin, qmax = qmax, qmin                                # the reduction forgot the small entries: qmin above qmax
+        elif t % 8 == 3:
+            qmax = _bits(0xff800000)
+        elif t % 8 == 4:
+            qmax = np.float32(qmin)
+        elif t % 8 == 5:
+            qmax = np.nextafter(qmin, np.float32(np.inf))          # scale = 127 / ulp: products far outside int8, some outside int32
+        v = (rng.random(1600).astype(np.float32) * np.float32(60) - np.float32(3 if t % 3 == 0 else 0)).astype(np.float32)
+        for e in rng.choice(1600, 160, replace=False):
+            v[e] = _bits(NF_VALUES[int(rng.integers(len(NF_VALUES)))])
+        if t % 8 == 5:
+            v[::5] = (qmin - rng.random(320).astype(np.float32) * np.float32([1e-6, 1e-3, 1.0, 1e6][t % 4])).astype(np.float32)
+        v = np.ascontiguousarray(v.reshape(-1, 16))
+        want = po.reff_quantize_tables(v, qmin, qmax)
+        got = po.quantize_tables(v, qmin, qmax, mode=1)
+        assert np.array_equal(want, got), t
+        assert (got[np.isnan(v)] == 127).all()
+        seen127 += int(np.isnan(v).sum())
+        seen_wrap += int((got < 0).sum())
+    assert seen127 > 1000 and seen_wrap > 100
+
+
+def test_nonfinite_fixture_is_what_the_oracle_computes(po):
+    """tests/golden/ref_query_scan_nonfinite_cases.npz (the reference build's outputs, oracle/gen_golden_float.py) against
+    orc_query_scan: runs everywhere.  Start heap and qmax as bits, exit status, final heap, sort_keys, the tables after the call."""
+    fam, nexit = set(), 0
+    for c in golden_cases.nonfinite_cases(po):
+        M, R, assign, keep = c["M"], c["R"], c["assign"], c["keep"]
+        starts = [c["parts"][p][:po.start_size(c["parts"][p].shape[0], keep)] for p in assign]
+        slab = None if c["labels"] is None else [c["labels"][p][:len(s)] for p, s in zip(assign, starts)]
+        ok, ov = po.scan4_start(M, starts, slab, c["tables"], R)
+        assert np.array_equal(ok, c["start_keys"]) and _same_bits(ov, c["start_vals"]), c["cid"]
+        tb = c["tables"].copy()
+        o = po.query_scan(M, c["parts"], c["labels"], keep, assign, tb, R)
+        assert o["rc"] == c["exit"] and o["qmax_bits"] == int(c["start_vals"][:1].view(np.uint32)[0]), c["cid"]
+        fam.add(c["family"].rstrip("0123456789_"))
+        if c["exit"]:
+            nexit += 1
+            continue
+        assert np.array_equal(o["keys"], c["keys"]) and np.array_equal(o["values"], c["vals"]), (c["cid"], c["family"])
+        assert np.array_equal(po.sort_keys_i8(o["keys"], o["values"]), c["sorted"]), c["cid"]
+        assert np.array_equal(tb.view(np.uint32), c["after"]), c["cid"]
+    assert nexit >= 4 and len(fam) >= 25
+
+
+def test_the_nan_rules_are_not_the_source_text(po):
+    """The pin is not vacuous: on the fixture's cases the SOURCE-level expressions (quant_mode 0: the iterator loop of min_element,
+    v >= max) give other heaps than the reference build where a NaN entry is in reach of a code's score, and the build's qmin is
+    neither the source loop's nor the minimum over the non-NaN entries once a NaN sits in the table's last three entries."""
+    differ = ncase = 0
+    for c in golden_cases.nonfinite_cases(po):
+        nan = np.isnan(c["tables"])
+        if c["exit"] or not nan.any():
+            continue
+        o0 = po.query_scan(c["M"], c["parts"], c["labels"], c["keep"], c["assign"], c["tables"].copy(), c["R"], quant_mode=0)
+        o1 = po.query_scan(c["M"], c["parts"], c["labels"], c["keep"], c["assign"], c["tables"].copy(), c["R"], quant_mode=1)
+        assert (o1["qtables"].reshape(nan.shape)[nan] == 127).all() and (o0["qtables"].reshape(nan.shape)[nan] == 0).all(), c["cid"]
+        differ += int(not (np.array_equal(o0["keys"], c["keys"]) and np.array_equal(o0["values"], c["vals"])))
+        ncase += 1
+    assert ncase >= 20 and differ >= ncase // 2
+    rng = np.random.default_rng(1)
+    t = (rng.random(256).astype(np.float32) + np.float32(1))
+    for e in (255, 254, 253, 252, 0, 7):
+        u = t.copy()
+        u[e] = np.nan
+        u[(e + 100) % 256] = np.float32(0.5)                        # the true minimum, in another lane than the NaN
+        got = po.min_element_compiled(u)
+        if e == 255:
+            assert np.isnan(got)                                    # the last scalar step: the NaN is the second operand
+        elif e >= 253:
+            assert got == u[e + 1:].min() > np.float32(0.5)         # a scalar step on a NaN forgets EVERYTHING before it
+        else:
+            assert got == np.float32(0.5), (e, got)
+    u = t.copy()
+    u[1 + 8 * 3 + 2] = np.float32(0.25)                             # lane 2 of the 8-lane loop, block 3
+    u[1 + 8 * 9 + 2] = np.nan                                       # the same lane, later: the 0.25 is forgotten
+    u[200] = np.float32(0.75)                                       # (lane 7)
+    assert po.min_element_compiled(u) == np.float32(0.75) and np.nanmin(u) == np.float32(0.25)
+
+
 def test_reference_exit_paths(po):
     """qmax > 1e30 (fewer than R starts: heap not full, or only the sentinel evicted...) -> the reference prints its warning
     and exit(1)s (db_query_4.cpp:271-274); mixed labelled / unlabelled partitions -> exit(1) in prepare_database (118-124)."""
@@ -552,7 +775,8 @@ def test_extraction_refuses_a_drifted_reference(tmp_path):
 
 
 @pytest.mark.parametrize("script,committed", [("gen_golden_float.py", "ref_query_scan_cases.npz"), ("gen_golden.py", "ref_scan_cases.npz"),
-                                              ("gen_golden_encode.py", "ref_encode_cases.npz")])
+                                              ("gen_golden_encode.py", "ref_encode_cases.npz"),
+                                              ("gen_golden_float.py", "ref_query_scan_nonfinite_cases.npz")])
 def test_golden_fixtures_regenerate_from_the_reference_build(po, tmp_path, script, committed):
     """The committed fixtures ARE what the generators produce from the reference build today: every array, bit for bit."""
     import os

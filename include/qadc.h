@@ -42,13 +42,13 @@ const char* qadc_version(void);
  * that is not is refused with QADC_E_ARG ("<name> must be <n>-byte aligned") before any HIP call; nothing is written and the index
  * or store answers as before.  A slice of a larger allocation is a legal argument as long as its first byte obeys the table.
  *   16 bytes  d_tables    qadc_adc_query_scan_device(_filtered), qadc_adc_range_scan_device: the scan stages a table with 16-byte loads
- *             d_vectors   qadc_adc_index_add_vectors_device, _labelled_device, qadc_pq_train16_device: the 16-bit encoder loads a
+ *             d_vectors   qadc_adc_index_add_vectors_device, _labelled_device, qadc_pq_train16_device, qadc_pq_train16_repair_device: the 16-bit encoder loads a
  *                         sub-vector 16 bytes at a time (stated for every float-ADC index, whatever its code width)
  *             d_codes     qadc_index_add_partition_device: a borrowed partition (readable up to size * M/2 rounded up to 16 bytes)
  *    4 bytes  every other float, uint32 and int32 array: d_queries, d_keys, d_values, d_sizes, d_labels, d_counts, d_out_keys,
  *             d_out_dist, d_out_sizes, and d_vectors of qadc_index_add_vectors_device, _labelled_device, qadc_refine_add_device,
  *             qadc_refine_put_device, qadc_pq_encode(_mode), qadc_pq_train_device, qadc_opq_cross_device, qadc_opq_train_device,
- *             qadc_kmeans_seed_device
+ *             qadc_kmeans_seed_device, qadc_pq_train_repair_device, qadc_opq_train_repair_device
  *    1 byte   d_codes of qadc_pq_encode(_mode): [n][M/2] bytes, each written by itself
  * Host arrays carry no such requirement beyond their element type's.
  * ------------------------------------------------------------------------------------------- */
@@ -346,7 +346,7 @@ int qadc_kmeans_iterations_host_mode(const float* vectors, uint64_t n, int dim, 
  * (sq_bits 4 with sq_count 16 or 32: qadc_pq_encode's reference form; sq_bits 8 with sq_count 4, 8 or 16: qadc_adc_encode_host's),
  * then centroid = (its members' sub-vectors summed in ascending vector index into one running float from 0.0f) * (1.0f / count)
  * (div_mode 1, as the reference is compiled; 0: divided by the count, as its source reads).  An empty cluster becomes NaN and
- * stays NaN, as in the reference; nothing repairs it.  sum_mode: the norms' grouping, as for the encoders.
+ * stays NaN, as in the reference; qadc_pq_train_repair_host below repairs it on request ("Empty-cluster repair").  sum_mode: the norms' grouping, as for the encoders.
  * K_coarse > 0: the learning set is first made residuals to the nearest of coarse [K_coarse][dim] (find_k_neighbors, k = 1);
  * rotation [dim][dim] or NULL: ... and rotated (rotated[r] = sum_c x[c] * rotation[r][c]) — what index_db::add_vectors hands to
  * the quantizer.  The caller seeds (the reference leaves learning to an outside project; qadc_kmeans_seed_host below is one seed): codebooks [sq_count][2^sq_bits][dsub] in
@@ -369,7 +369,7 @@ int qadc_pq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_cou
  * passes of QADC_ADC_ENCODE16_CHUNK vectors), then updates: per sub-quantizer the vectors are sorted by (code, index) on the GPU
  * and centroid (m, k) = (its members' sub-vectors summed in ascending vector index into one running float from 0.0f)
  * * (1.0f / (float)count) (div_mode 1) or / (float)count (div_mode 0).  An empty cluster becomes NaN and stays NaN; empty_out
- * counts them, nothing repairs them.  K_coarse, coarse, rotation, sum_mode: as for qadc_pq_train_host.  codes_out (nullable,
+ * counts them, and qadc_pq_train16_repair_host below repairs them on request ("Empty-cluster repair").  K_coarse, coarse, rotation, sum_mode: as for qadc_pq_train_host.  codes_out (nullable,
  * host memory): little-endian uint16 [n][sq_count], qadc_adc_encode16_host's layout — the last round's assignment, under the
  * codebooks of BEFORE the last update.  iters == 0 returns the seed untouched, writes no code and touches no device.
  * Refused with QADC_E_ARG before the first HIP call: sq_count outside {2, 4, 8}; dim not a multiple of it or > 4096; dsub > 2048;
@@ -377,7 +377,7 @@ int qadc_pq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_cou
  * Limits: the learning set, its residual copy (with coarse or rotation), the codes and two index permutations of n words are
  * resident for the call.  The update's critical path is the largest cluster: one cluster holding every vector is n dependent
  * additions on one lane group — correct, and slow.  The OPQ rotation is not learned, the seed is the caller's, and an empty
- * cluster is not re-seeded.
+ * cluster is re-seeded only by qadc_pq_train16_repair_host.
  * qadc_pq_train16_device: the vectors already in device memory (read only, by kernels); every other pointer is host memory. */
 int qadc_pq_train16_host(const float* vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
                          const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
@@ -439,7 +439,7 @@ int qadc_procrustes_host(const double* M, int dim, float* rotation_out, int* swe
  *   rotation; outer < 0; inner < 1.  QADC_E_STATE: a Procrustes solve hit its sweep cap (rotation and codebooks are then not
  *   a fitted pair).  Limits: 4 and 8 bits; dim <= 1024; the learning set, its residual, its rotated copy, the codes and the
  *   partials are resident for the call; one device; synchronous.  Not done: the parametric initialisation, seeding (qadc_kmeans_seed_host below),
- *   empty-cluster repair, 16-bit codebooks.  qadc_opq_train_device: the vectors already in device memory (read only, by kernels). */
+ *   16-bit codebooks.  Empty-cluster repair: qadc_opq_train_repair_host below.  qadc_opq_train_device: the vectors already in device memory (read only, by kernels). */
 int qadc_opq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                         float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
                         int* rounds_done_out, int div_mode, int sum_mode, int device_id);
@@ -477,7 +477,7 @@ int qadc_opq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_co
  * Refused with QADC_E_ARG before the first HIP call, the message naming the cause: NULL vectors or centres_out; n == 0 or
  * n >= 2^32; k < 1 or k > n; sq_count outside [1, 32]; dim not a positive multiple of sq_count; dim > 4096; K_coarse < 0, or > 0
  * without coarse; d_vectors not 4-byte aligned.  Limits: the learning set, its front copy, sq_count * n floats of distances and the
- * tree are resident for the call; one device.  Not done: empty-cluster repair inside the training rounds, cv::kmeans' own variant
+ * tree are resident for the call; one device.  Empty-cluster repair inside the training rounds: qadc_pq_train_repair_host below.  Not done: cv::kmeans' own variant
  * (its local trials, its RNG), k-means||, learning sets larger than device memory, more than one device.
  * qadc_kmeans_seed_device: the vectors already in device memory (read only, by kernels); every other pointer is host memory. */
 int qadc_kmeans_seed_host(const float* vectors, uint64_t n, int dim, int sq_count, int64_t k, int K_coarse, const float* coarse,
@@ -486,6 +486,67 @@ int qadc_kmeans_seed_host(const float* vectors, uint64_t n, int dim, int sq_coun
 int qadc_kmeans_seed_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int64_t k, int K_coarse, const float* coarse,
                             const float* rotation, uint64_t seed, float* centres_out, uint32_t* rows_out, uint64_t* fallbacks_out,
                             int device_id);
+
+/* ---- Empty-cluster repair: a step between the assignment and the update of a training round. ----
+ *
+ * Why: the assignment is pinned to the reference's heap as compiled — a NaN distance replaces the kept centroid and any later
+ * value replaces a NaN — so ONE NaN centroid at index j hides every centroid below j from every vector of the next round, and the
+ * returned codebook encodes by the same rule.  The repair is defined per sub-space m, independently.  Inputs: x, the learning set as
+ * the quantizer sees it (behind the trainers' residual and rotation front); cb, the codebooks this round's assignment used; the
+ * round's codes.  K = 2^sq_bits, c_i = the code of vector i in sub-space m.
+ *   1. count[k] = the number of i with c_i == k; first[k] = the smallest such i.  The empties are the k with count[k] == 0 in
+ *      ascending order, e_0 < e_1 < ... < e_{E-1}.  E == 0 changes nothing.
+ *   2. d_i = ONE float chain acc = fmaf(t, t, acc), t = x[i][d] - cb[m][c_i][d], from 0.0f over the ascending columns d of
+ *      sub-space m (the seeding's direct form).
+ *   3. Vector i is eligible iff d_i is finite (neither NaN nor +inf), d_i > 0, and i != first[c_i]: every cluster keeps its
+ *      lowest-index member, so a repair never empties a cluster.
+ *   4. key_i = ((uint64)bits(d_i) << 32) | (0xFFFFFFFF - i).  Chosen are the min(E, number eligible) eligible vectors with the
+ *      largest keys: farthest first, among equal distances the lower index.
+ *   5. The chosen vectors in ascending index are s_0 < s_1 < ...; c_{s_j} = e_j.  moved[m] = the number chosen.  Empties beyond
+ *      that stay empty: they become NaN in the update and are counted by empty_out as before.
+ * A repaired round is assign, repair, update.  The update is unchanged and sees the rewritten codes: a filled cluster's centroid
+ * is exactly its one vector's sub-vector, the donor's mean loses that vector, every sum keeps its pinned order, and no float meets
+ * an atomic.  codes_out reports the repaired codes of the last round.  Host twin: host/pq_repair.hpp pq_repair, and the `repair`
+ * overloads of pq_train_iterations, pq_train16_iterations, opq_train_iterations (host/db_build.hpp); the device equals them bit for
+ * bit.
+ *
+ * qadc_pq_repair_host: the step alone on the caller's codes (the counterpart of qadc_pq_update16_host).  vectors [n][dim] as the
+ *   quantizer sees them, codebooks [sq_count][2^sq_bits][dsub], codes in and out in the encoder's layout (sq_bits 4: packed nibbles
+ *   [n][sq_count / 2], the even sub-quantizer in the low nibble; 8: bytes [n][sq_count]; 16: little-endian uint16 [n][sq_count]),
+ *   moved_out [sq_count] (nullable).  Refused with QADC_E_ARG before the first HIP call, the message naming the cause: sq_bits
+ *   outside {4, 8, 16}; everything the trainer of that width refuses (qadc_pq_train_host at 4 and 8 bits, qadc_pq_train16_host at
+ *   16); NULL codes.
+ * qadc_pq_train_repair_host / _device, qadc_pq_train16_repair_host / _device, qadc_opq_train_repair_host / _device: the calls
+ *   above with two more arguments.  repair 0: the call above, bit for bit (which is now a thin caller of these); 1: every round is
+ *   a repaired round — for OPQ the contract stays "the loop of the public calls", now of the repaired ones.  repaired_out
+ *   (nullable): the moves of all rounds and sub-spaces.  Another value of repair is refused (QADC_E_ARG).
+ * Limits: with repair 1, sq_count * n keys of 8 bytes are resident for the call beside the trainer's own memory, plus count,
+ *   first and the empties (12 bytes per centroid), the histograms and one word per 1024 vectors and sub-space.  A round on a
+ *   codebook without an empty cluster costs one integer pass over the codes and launches that return at once: nothing waits on
+ *   the host inside a round, E stays in device memory.  Not done: the coarse k-means qadc_kmeans_iterations_host (int32
+ *   assignment, arbitrary K, its own update: a follow-up on the same kernels); splitting large clusters by any other rule;
+ *   learning sets larger than device memory. */
+int qadc_pq_repair_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, const float* codebooks, void* codes,
+                        uint32_t* moved_out, int device_id);
+int qadc_pq_train_repair_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                              const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                              int sum_mode, int repair, uint64_t* repaired_out, int device_id);
+int qadc_pq_train_repair_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse,
+                                const float* coarse, const float* rotation, float* codebooks, int iters, void* codes_out,
+                                uint64_t* empty_out, int div_mode, int sum_mode, int repair, uint64_t* repaired_out, int device_id);
+int qadc_pq_train16_repair_host(const float* vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                                const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                                int sum_mode, int repair, uint64_t* repaired_out, int device_id);
+int qadc_pq_train16_repair_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                                  const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out,
+                                  int div_mode, int sum_mode, int repair, uint64_t* repaired_out, int device_id);
+int qadc_opq_train_repair_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                               float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
+                               int* rounds_done_out, int div_mode, int sum_mode, int repair, uint64_t* repaired_out, int device_id);
+int qadc_opq_train_repair_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse,
+                                 const float* coarse, float* rotation, float* codebooks, int outer, int inner, void* codes_out,
+                                 uint64_t* empty_out, int* rounds_done_out, int div_mode, int sum_mode, int repair,
+                                 uint64_t* repaired_out, int device_id);
 
 /* Host-only helper (no GPU involved): push (keys[i], vals[i]), i = 0..n-1, in order into an empty
  * heap of capacity R with kv_binheap<unsigned,int8_t>::push semantics (binheap.hpp:75-116), after

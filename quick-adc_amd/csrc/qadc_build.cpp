@@ -227,7 +227,7 @@ uint64_t nan_rows(const float* cb, size_t rows, int ds) {
 
 // the rounds themselves, on the learning set as the quantizer sees it: qadc_pq_train_* and the outer rounds of qadc_opq_train_* run these
 int pq_train_rounds(const float* d_enc, uint64_t n, int dim, int sq_count, int sq_bits, float* d_cb, float* d_cbnorm, uint8_t* d_codes,
-                    int iters, int div_mode, int sum_mode) {
+                    int iters, int div_mode, int sum_mode, PqRepairScratch* repair) {
     const int ds = dim / sq_count;
     const size_t rows = (size_t)sq_count << sq_bits;
     for (int it = 0; it < iters; ++it) {
@@ -237,6 +237,8 @@ int pq_train_rounds(const float* d_enc, uint64_t n, int dim, int sq_count, int s
             launch_row_sqnorm(d_cb, (int)rows, ds, sum_mode, d_cbnorm, nullptr);
             HIPCHECK(adc::launch_adc_encode(d_enc, n, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_codes, nullptr));
         }
+        if (repair)                                            // the codes are rewritten before the update reads them
+            if (int rc = repair->run(d_enc, d_cb, d_codes)) return rc;
         HIPCHECK(launch_pq_train_update(d_enc, n, dim, sq_count, sq_bits, d_codes, d_cb, div_mode, nullptr));
     }
     return QADC_OK;
@@ -274,23 +276,29 @@ int pq_train_front_device(const float* d_vectors, uint64_t n, int dim, int K_coa
 // d_vectors: the learning set in device memory (read by kernels only: it may belong to another HIP runtime of the process)
 int pq_train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                  const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode, int sum_mode,
-                 ScratchFree& mem) {
+                 int repair, uint64_t* repaired_out, ScratchFree& mem) {
     const int ds = dim / sq_count;
     const size_t rows = (size_t)sq_count << sq_bits, code_bytes = sq_bits == 4 ? sq_count / 2 : sq_count;
     float *d_cb = nullptr, *d_cbnorm = nullptr;
     uint8_t* d_codes = nullptr;
+    PqRepairScratch rp;
+    if (repair)
+        if (int rc = rp.alloc(mem, n, dim, sq_count, sq_bits)) return rc;
     HIPCHECK(mem.alloc(&d_cb, rows * ds * sizeof(float)));
     HIPCHECK(hipMemcpy(d_cb, codebooks, rows * ds * sizeof(float), hipMemcpyHostToDevice));
     if (sq_bits == 8) HIPCHECK(mem.alloc(&d_cbnorm, rows * sizeof(float)));
     HIPCHECK(mem.alloc(&d_codes, n * code_bytes));
     const float* d_enc = nullptr;
     if (int rc = pq_train_front_device(d_vectors, n, dim, K_coarse, coarse, rotation, sum_mode, mem, &d_enc)) return rc;
-    if (int rc = pq_train_rounds(d_enc, n, dim, sq_count, sq_bits, d_cb, d_cbnorm, d_codes, iters, div_mode, sum_mode)) return rc;
+    if (int rc = pq_train_rounds(d_enc, n, dim, sq_count, sq_bits, d_cb, d_cbnorm, d_codes, iters, div_mode, sum_mode, repair ? &rp : nullptr))
+        return rc;
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(codebooks, d_cb, rows * ds * sizeof(float), hipMemcpyDeviceToHost));
     if (codes_out) HIPCHECK(hipMemcpy(codes_out, d_codes, n * code_bytes, hipMemcpyDeviceToHost));
     if (empty_out) *empty_out = nan_rows(codebooks, rows, ds);
+    if (repair && repaired_out)
+        if (int rc = rp.total(repaired_out)) return rc;
     return QADC_OK;
 }
 }  // namespace
@@ -299,8 +307,24 @@ int pq_train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int 
 int qadc_pq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                          const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
                          int sum_mode, int device_id) {
+    return qadc_pq_train_repair_device(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out,
+                                       div_mode, sum_mode, 0, nullptr, device_id);
+}
+
+int qadc_pq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                       const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                       int sum_mode, int device_id) {
+    return qadc_pq_train_repair_host(vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out,
+                                     div_mode, sum_mode, 0, nullptr, device_id);
+}
+
+int qadc_pq_train_repair_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                                const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                                int sum_mode, int repair, uint64_t* repaired_out, int device_id) {
     if (int rc = pq_train_check(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (repair != 0 && repair != 1) return fail(QADC_E_ARG, "repair is 0 or 1");
     if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
+    if (repaired_out) *repaired_out = 0;
     if (iters == 0) {                                          // the seed untouched, no code written
         if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count << sq_bits, dim / sq_count);
         return QADC_OK;
@@ -309,13 +333,15 @@ int qadc_pq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_cou
     HIPCHECK(hipSetDevice(device_id));
     ScratchFree mem;
     return pq_train_run(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out,
-                        div_mode, sum_mode, mem);
+                        div_mode, sum_mode, repair, repaired_out, mem);
 }
 
-int qadc_pq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
-                       const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
-                       int sum_mode, int device_id) {
+int qadc_pq_train_repair_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                              const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                              int sum_mode, int repair, uint64_t* repaired_out, int device_id) {
     if (int rc = pq_train_check(vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (repair != 0 && repair != 1) return fail(QADC_E_ARG, "repair is 0 or 1");
+    if (repaired_out) *repaired_out = 0;
     if (iters == 0) {
         if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count << sq_bits, dim / sq_count);
         return QADC_OK;
@@ -327,7 +353,7 @@ int qadc_pq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, 
     HIPCHECK(mem.alloc(&d_v, sizeof(float) * n * dim));
     HIPCHECK(hipMemcpy(d_v, vectors, sizeof(float) * n * dim, hipMemcpyHostToDevice));
     return pq_train_run(d_v, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out, div_mode,
-                        sum_mode, mem);
+                        sum_mode, repair, repaired_out, mem);
 }
 
 /* ---- PQ training for 16-bit sub-quantizers: a round = launch_adc_encode16 over the resident learning set
@@ -371,13 +397,17 @@ struct Train16Scratch {
 
 // d_vectors: the learning set in device memory (read by kernels only)
 int pq_train16_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse, const float* rotation,
-                   float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode, int sum_mode, ScratchFree& mem) {
+                   float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode, int sum_mode, int repair,
+                   uint64_t* repaired_out, ScratchFree& mem) {
     const int ds = dim / sq_count;
     const size_t rows = (size_t)sq_count * kPqTrain16K;
     float *d_cb = nullptr, *d_cbnorm = nullptr;
     uint16_t* d_codes = nullptr;
     unsigned long long* d_part = nullptr;
     Train16Scratch sc;
+    PqRepairScratch rp;
+    if (repair)
+        if (int rc = rp.alloc(mem, n, dim, sq_count, 16)) return rc;
     HIPCHECK(mem.alloc(&d_cb, rows * ds * sizeof(float)));
     HIPCHECK(hipMemcpy(d_cb, codebooks, rows * ds * sizeof(float), hipMemcpyHostToDevice));
     HIPCHECK(mem.alloc(&d_cbnorm, rows * sizeof(float)));
@@ -397,6 +427,8 @@ int pq_train16_run(const float* d_vectors, uint64_t n, int dim, int sq_count, in
             HIPCHECK(adc::launch_adc_encode16(d_enc + o * dim, (uint32_t)cnt, sq_count, dim, d_cb, d_cbnorm, sum_mode, d_part,
                                               d_codes + o * sq_count, nullptr));
         }
+        if (repair)                                            // the codes are rewritten before the update sorts them
+            if (int rc = rp.run(d_enc, d_cb, d_codes)) return rc;
         HIPCHECK(launch_pq_train16_update(d_enc, (uint32_t)n, dim, sq_count, d_codes, d_cb, nullptr, div_mode, sc.perm_a, sc.perm_b, sc.hist,
                                           sc.start, nullptr));
     }
@@ -405,6 +437,8 @@ int pq_train16_run(const float* d_vectors, uint64_t n, int dim, int sq_count, in
     HIPCHECK(hipMemcpy(codebooks, d_cb, rows * ds * sizeof(float), hipMemcpyDeviceToHost));
     if (codes_out) HIPCHECK(hipMemcpy(codes_out, d_codes, n * sq_count * sizeof(uint16_t), hipMemcpyDeviceToHost));
     if (empty_out) *empty_out = nan_rows(codebooks, rows, ds);
+    if (repair && repaired_out)
+        if (int rc = rp.total(repaired_out)) return rc;
     return QADC_OK;
 }
 }  // namespace
@@ -413,7 +447,23 @@ int pq_train16_run(const float* d_vectors, uint64_t n, int dim, int sq_count, in
 int qadc_pq_train16_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
                            const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
                            int sum_mode, int device_id) {
+    return qadc_pq_train16_repair_device(d_vectors, n, dim, sq_count, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out, div_mode,
+                                         sum_mode, 0, nullptr, device_id);
+}
+
+int qadc_pq_train16_host(const float* vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                         const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                         int sum_mode, int device_id) {
+    return qadc_pq_train16_repair_host(vectors, n, dim, sq_count, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out, div_mode,
+                                       sum_mode, 0, nullptr, device_id);
+}
+
+int qadc_pq_train16_repair_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                                  const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                                  int sum_mode, int repair, uint64_t* repaired_out, int device_id) {
     if (int rc = pq_train16_check(d_vectors, n, dim, sq_count, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (repair != 0 && repair != 1) return fail(QADC_E_ARG, "repair is 0 or 1");
+    if (repaired_out) *repaired_out = 0;
     if (int rc = check_aligned(d_vectors, 16, "d_vectors")) return rc;   // (the 16-bit encoder of a round: adc_encode16_kernel's 16-byte loads)
     if (iters == 0) {                                          // the seed untouched, no code written
         if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count * kPqTrain16K, dim / sq_count);
@@ -423,13 +473,15 @@ int qadc_pq_train16_device(const float* d_vectors, uint64_t n, int dim, int sq_c
     HIPCHECK(hipSetDevice(device_id));
     ScratchFree mem;
     return pq_train16_run(d_vectors, n, dim, sq_count, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out, div_mode,
-                          sum_mode, mem);
+                          sum_mode, repair, repaired_out, mem);
 }
 
-int qadc_pq_train16_host(const float* vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
-                         const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
-                         int sum_mode, int device_id) {
+int qadc_pq_train16_repair_host(const float* vectors, uint64_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                                const float* rotation, float* codebooks, int iters, void* codes_out, uint64_t* empty_out, int div_mode,
+                                int sum_mode, int repair, uint64_t* repaired_out, int device_id) {
     if (int rc = pq_train16_check(vectors, n, dim, sq_count, K_coarse, coarse, codebooks, iters, div_mode, sum_mode)) return rc;
+    if (repair != 0 && repair != 1) return fail(QADC_E_ARG, "repair is 0 or 1");
+    if (repaired_out) *repaired_out = 0;
     if (iters == 0) {
         if (empty_out) *empty_out = nan_rows(codebooks, (size_t)sq_count * kPqTrain16K, dim / sq_count);
         return QADC_OK;
@@ -441,7 +493,7 @@ int qadc_pq_train16_host(const float* vectors, uint64_t n, int dim, int sq_count
     HIPCHECK(mem.alloc(&d_v, sizeof(float) * n * dim));
     HIPCHECK(hipMemcpy(d_v, vectors, sizeof(float) * n * dim, hipMemcpyHostToDevice));
     return pq_train16_run(d_v, n, dim, sq_count, K_coarse, coarse, rotation, codebooks, iters, codes_out, empty_out, div_mode, sum_mode,
-                          mem);
+                          repair, repaired_out, mem);
 }
 
 int qadc_pq_update16_host(const float* vectors, uint64_t n, int dim, int sq_count, const uint16_t* codes, float* codebooks_out,
@@ -469,6 +521,43 @@ int qadc_pq_update16_host(const float* vectors, uint64_t n, int dim, int sq_coun
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(codebooks_out, d_cb, rows * ds * sizeof(float), hipMemcpyDeviceToHost));
     if (counts_out) HIPCHECK(hipMemcpy(counts_out, d_counts, rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return QADC_OK;
+}
+
+/* ---- empty-cluster repair alone: launch_pq_repair on the caller's codes ---- */
+int qadc_pq_repair_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, const float* codebooks, void* codes,
+                        uint32_t* moved_out, int device_id) {
+    if (sq_bits != 4 && sq_bits != 8 && sq_bits != 16) return fail(QADC_E_ARG, "sq_bits must be 4, 8 or 16");
+    if (sq_bits == 16) {
+        if (int rc = pq_train16_check_shape(vectors, n, dim, sq_count, codebooks, 1)) return rc;
+    } else if (int rc = pq_train_check(vectors, n, dim, sq_count, sq_bits, 0, nullptr, codebooks, 0, 1, 1)) {
+        return rc;
+    }
+    if (!codes) return fail(QADC_E_ARG, "codes must not be NULL");
+    PqRepairPlan plan;
+    if (!pq_repair_plan(n, dim, sq_count, sq_bits, &plan)) return fail(QADC_E_ARG, "the repair kernels do not take this shape");
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(device_id));
+    ScratchFree mem;
+    const size_t cb_bytes = (size_t)sq_count * plan.K * plan.dsub * sizeof(float), code_bytes = (size_t)plan.units * plan.unit_bytes;
+    float *d_v = nullptr, *d_cb = nullptr;
+    uint8_t* d_codes = nullptr;
+    PqRepairScratch rp;
+    HIPCHECK(mem.alloc(&d_v, sizeof(float) * n * dim));
+    HIPCHECK(mem.alloc(&d_cb, cb_bytes));
+    HIPCHECK(mem.alloc(&d_codes, code_bytes));
+    if (int rc = rp.alloc(mem, n, dim, sq_count, sq_bits)) return rc;
+    HIPCHECK(hipMemcpy(d_v, vectors, sizeof(float) * n * dim, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(d_cb, codebooks, cb_bytes, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(d_codes, codes, code_bytes, hipMemcpyHostToDevice));
+    if (int rc = rp.run(d_v, d_cb, d_codes)) return rc;
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(codes, d_codes, code_bytes, hipMemcpyDeviceToHost));
+    if (moved_out) {
+        unsigned long long per[kPqRepairMaxSq];
+        HIPCHECK(hipMemcpy(per, rp.st.moved_total, sizeof per, hipMemcpyDeviceToHost));
+        for (int m = 0; m < sq_count; ++m) moved_out[m] = (uint32_t)per[m];
+    }
     return QADC_OK;
 }
 

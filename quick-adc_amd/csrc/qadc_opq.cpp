@@ -105,7 +105,7 @@ int train_check(const float* vectors, uint64_t n, int dim, int sq_count, int sq_
 // d_vectors: the learning set in device memory (read by kernels only)
 int train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse, float* rotation,
               float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out, int* rounds_done_out, int div_mode,
-              int sum_mode, ScratchFree& mem) {
+              int sum_mode, int repair, uint64_t* repaired_out, ScratchFree& mem) {
     const int ds = dim / sq_count;
     const size_t rows = (size_t)sq_count << sq_bits, code_bytes = sq_bits == 4 ? sq_count / 2 : sq_count;
     const size_t rot_bytes = sizeof(float) * (size_t)dim * dim;
@@ -114,6 +114,9 @@ int train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_
     int32_t* d_assign = nullptr;
     uint8_t* d_codes = nullptr;
     CrossScratch sc;
+    PqRepairScratch rp;
+    if (repair)
+        if (int rc = rp.alloc(mem, n, dim, sq_count, sq_bits)) return rc;
     HIPCHECK(mem.alloc(&d_cb, rows * ds * sizeof(float)));
     HIPCHECK(hipMemcpy(d_cb, codebooks, rows * ds * sizeof(float), hipMemcpyHostToDevice));
     if (sq_bits == 8) HIPCHECK(mem.alloc(&d_cbnorm, rows * sizeof(float)));
@@ -130,7 +133,8 @@ int train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_
     for (;;) {
         HIPCHECK(hipMemcpy(d_rot, rotation, rot_bytes, hipMemcpyHostToDevice));
         launch_residual_rotate(d_vectors, n, dim, d_coarse, d_assign, d_rot, d_x, nullptr);   // pq_train_front_device's own floats
-        if (int rc = pq_train_rounds(d_x, n, dim, sq_count, sq_bits, d_cb, d_cbnorm, d_codes, inner, div_mode, sum_mode)) return rc;
+        if (int rc = pq_train_rounds(d_x, n, dim, sq_count, sq_bits, d_cb, d_cbnorm, d_codes, inner, div_mode, sum_mode, repair ? &rp : nullptr))
+            return rc;
         if (closing) break;
         HIPCHECK(launch_opq_cross(d_x0, n, dim, sq_count, sq_bits, d_codes, d_cb, sc.d_partials, sc.d_M, nullptr));
         HIPCHECK(hipDeviceSynchronize());
@@ -150,6 +154,8 @@ int train_run(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_
     if (codes_out) HIPCHECK(hipMemcpy(codes_out, d_codes, n * code_bytes, hipMemcpyDeviceToHost));
     if (empty_out) *empty_out = nan_rows(codebooks, rows, ds);
     if (rounds_done_out) *rounds_done_out = done;
+    if (repair && repaired_out)
+        if (int rc = rp.total(repaired_out)) return rc;
     return QADC_OK;
 }
 
@@ -188,21 +194,39 @@ int qadc_opq_cross_host(const float* vectors, uint64_t n, int dim, int sq_count,
 int qadc_opq_train_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                           float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
                           int* rounds_done_out, int div_mode, int sum_mode, int device_id) {
-    if (int rc = train_check(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, div_mode, sum_mode))
-        return rc;
-    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
-    DeviceGuard guard;
-    HIPCHECK(hipSetDevice(device_id));
-    ScratchFree mem;
-    return train_run(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, codes_out, empty_out,
-                     rounds_done_out, div_mode, sum_mode, mem);
+    return qadc_opq_train_repair_device(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, codes_out,
+                                        empty_out, rounds_done_out, div_mode, sum_mode, 0, nullptr, device_id);
 }
 
 int qadc_opq_train_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
                         float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
                         int* rounds_done_out, int div_mode, int sum_mode, int device_id) {
+    return qadc_opq_train_repair_host(vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, codes_out,
+                                      empty_out, rounds_done_out, div_mode, sum_mode, 0, nullptr, device_id);
+}
+
+int qadc_opq_train_repair_device(const float* d_vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                                 float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
+                                 int* rounds_done_out, int div_mode, int sum_mode, int repair, uint64_t* repaired_out, int device_id) {
+    if (int rc = train_check(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, div_mode, sum_mode))
+        return rc;
+    if (repair != 0 && repair != 1) return fail(QADC_E_ARG, "repair is 0 or 1");
+    if (repaired_out) *repaired_out = 0;
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(device_id));
+    ScratchFree mem;
+    return train_run(d_vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, codes_out, empty_out,
+                     rounds_done_out, div_mode, sum_mode, repair, repaired_out, mem);
+}
+
+int qadc_opq_train_repair_host(const float* vectors, uint64_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                               float* rotation, float* codebooks, int outer, int inner, void* codes_out, uint64_t* empty_out,
+                               int* rounds_done_out, int div_mode, int sum_mode, int repair, uint64_t* repaired_out, int device_id) {
     if (int rc = train_check(vectors, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, div_mode, sum_mode))
         return rc;
+    if (repair != 0 && repair != 1) return fail(QADC_E_ARG, "repair is 0 or 1");
+    if (repaired_out) *repaired_out = 0;
     DeviceGuard guard;
     HIPCHECK(hipSetDevice(device_id));
     ScratchFree mem;                                           // the learning set goes up once, for every outer round
@@ -210,7 +234,7 @@ int qadc_opq_train_host(const float* vectors, uint64_t n, int dim, int sq_count,
     HIPCHECK(mem.alloc(&d_v, sizeof(float) * n * dim));
     HIPCHECK(hipMemcpy(d_v, vectors, sizeof(float) * n * dim, hipMemcpyHostToDevice));
     return train_run(d_v, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, codes_out, empty_out,
-                     rounds_done_out, div_mode, sum_mode, mem);
+                     rounds_done_out, div_mode, sum_mode, repair, repaired_out, mem);
 }
 
 }  // extern "C"

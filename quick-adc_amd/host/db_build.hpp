@@ -16,6 +16,9 @@
 //   pq_train_iterations(...)               CPU twin of qadc_pq_train_host: kmeans_fast_iterations on a copy of every sub-space's
 //                                          columns, behind the same residual / rotation front
 //   pq_train16_iterations(...), pq_update16(...)  the same for 16-bit sub-quantizers (qadc_pq_train16_host, qadc_pq_update16_host)
+//   pq_train_iterations(..., repair, repaired), pq_train16_iterations(..., repair, repaired), opq_train_iterations(..., repair,
+//                                          repaired)  CPU twins of the qadc_*_train_repair_host calls: every round is assign,
+//                                          pq_repair_slice (host/pq_repair.hpp), update
 //   learn_pq_hip(...)                      the product quantizer learned on the GPU from a caller-provided seed, as an io::pq_data
 //                                          ready for pq_to_data_file (the reference's flatdb_create / indexdb_create2 read it);
 //                                          with a std::uint64_t seed: seeded by seed_kmeanspp_hip (learn_opq_hip likewise)
@@ -43,6 +46,7 @@
 #include <cmath>
 
 #include "kmeans_seed.hpp"
+#include "pq_repair.hpp"
 #include "procrustes.hpp"
 #include "qadc_io.hpp"
 #include "query_driver.hpp"
@@ -159,9 +163,10 @@ inline unsigned db_add_hip(qadc_index* idx, int dim, const char* base_filename, 
 // databases.cpp:50-90 on the host: assign every vector to its closest centroid (find_k_neighbors with k = 1: the expansion
 // distances, the compiled replace test !(s >= kept) — the first strict minimum after the last NaN), then centroid = (sum of its members in vector order) times the reciprocal of the count — what the reference
 // binary does under -ffast-math (div_mode 1, pinned to its loops as compiled: oracle/_ref) — or divided by it as the source
-// reads (div_mode 0).  An empty cluster becomes NaN either way.
+// reads (div_mode 0).  An empty cluster becomes NaN either way.  repair: the empty-cluster repair of include/qadc.h between the
+// assignment and the update of every round; *repaired (nullable) grows by the vectors it moved.
 inline void kmeans_fast_iterations(const float* vecs, size_t n, int dim, int K, float* centroids, int iters, int* assign,
-                                   int div_mode = 1) {
+                                   int div_mode = 1, bool repair = false, std::uint64_t* repaired = nullptr) {
     std::vector<int> cnt((size_t)K);
     std::vector<float> cn((size_t)K);
     for (int it = 0; it < iters; ++it) {
@@ -179,6 +184,10 @@ inline void kmeans_fast_iterations(const float* vecs, size_t n, int dim, int K, 
                 if (!(s >= bestd)) { bestd = s; best = k; }
             }
             assign[i] = best;
+        }
+        if (repair) {
+            const std::uint32_t moved = pq_repair_slice(vecs, n, (size_t)dim, dim, K, centroids, assign);
+            if (repaired) *repaired += moved;
         }
         std::fill(centroids, centroids + (size_t)K * dim, 0.0f);
         std::fill(cnt.begin(), cnt.end(), 0);
@@ -232,8 +241,12 @@ inline std::vector<float> pq_train_front(const float* vecs, size_t n, int dim, i
 // copy of columns [m dsub, (m + 1) dsub) of the front's output, started from codebooks[m].  codebooks [sq_count][2^sq_bits][dsub]
 // in and out; codes (nullable): the last round's assignment in the encoder's layout — sq_bits 4: [n][sq_count / 2], the even
 // sub-quantizer in the low nibble; 8: [n][sq_count].  Returns the centroids that hold a NaN.  iters == 0 changes nothing.
+// repair: every round is a repaired round (include/qadc.h "Empty-cluster repair"); *repaired (nullable) = the vectors moved in all
+// rounds and sub-spaces.
 inline std::uint64_t pq_train_iterations(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
-                                         const float* rotation, float* codebooks, int iters, std::uint8_t* codes, int div_mode = 1) {
+                                         const float* rotation, float* codebooks, int iters, std::uint8_t* codes, int div_mode, bool repair,
+                                         std::uint64_t* repaired) {
+    if (repaired) *repaired = 0;
     if ((sq_bits != 4 && sq_bits != 8) || sq_count <= 0 || dim <= 0 || dim % sq_count || (sq_bits == 4 && sq_count % 2))
         throw std::runtime_error("pq_train_iterations: sq_bits 4 or 8, dim a multiple of sq_count");
     const int ds = dim / sq_count, K = 1 << sq_bits;
@@ -245,7 +258,7 @@ inline std::uint64_t pq_train_iterations(const float* vecs, size_t n, int dim, i
         if (codes) std::fill(codes, codes + n * cs, (std::uint8_t)0);
         for (int m = 0; m < sq_count; ++m) {
             for (size_t i = 0; i < n; ++i) std::copy(x.begin() + i * dim + (size_t)m * ds, x.begin() + i * dim + (size_t)(m + 1) * ds, slice.begin() + i * ds);
-            kmeans_fast_iterations(slice.data(), n, ds, K, codebooks + (size_t)m * K * ds, iters, assign.data(), div_mode);
+            kmeans_fast_iterations(slice.data(), n, ds, K, codebooks + (size_t)m * K * ds, iters, assign.data(), div_mode, repair, repaired);
             if (!codes) continue;
             for (size_t i = 0; i < n; ++i) {
                 if (sq_bits == 8) codes[i * cs + m] = (std::uint8_t)assign[i];
@@ -260,6 +273,11 @@ inline std::uint64_t pq_train_iterations(const float* vecs, size_t n, int dim, i
         empty += nan;
     }
     return empty;
+}
+
+inline std::uint64_t pq_train_iterations(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                                         const float* rotation, float* codebooks, int iters, std::uint8_t* codes, int div_mode = 1) {
+    return pq_train_iterations(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, iters, codes, div_mode, false, nullptr);
 }
 
 // CPU twin of qadc_pq_update16_host: the centroid update for 16-bit sub-quantizers alone, from given codes.  vecs [n][dim] as the
@@ -290,8 +308,11 @@ inline void pq_update16(const float* vecs, size_t n, int dim, int sq_count, cons
 
 // CPU twin of qadc_pq_train16_host: pq_train_iterations for 65536 centroids per sub-quantizer (sq_count 2, 4 or 8), codes (nullable)
 // uint16 [n][sq_count].  Returns the centroids that hold a NaN.  iters == 0 changes nothing and writes no code.
+// repair, repaired: as for pq_train_iterations.
 inline std::uint64_t pq_train16_iterations(const float* vecs, size_t n, int dim, int sq_count, int K_coarse, const float* coarse,
-                                           const float* rotation, float* codebooks, int iters, std::uint16_t* codes, int div_mode = 1) {
+                                           const float* rotation, float* codebooks, int iters, std::uint16_t* codes, int div_mode, bool repair,
+                                           std::uint64_t* repaired) {
+    if (repaired) *repaired = 0;
     if ((sq_count != 2 && sq_count != 4 && sq_count != 8) || dim <= 0 || dim % sq_count)
         throw std::runtime_error("pq_train16_iterations: sq_count 2, 4 or 8, dim a multiple of it");
     const int ds = dim / sq_count, K = 65536;
@@ -301,7 +322,7 @@ inline std::uint64_t pq_train16_iterations(const float* vecs, size_t n, int dim,
         std::vector<int> assign(n);
         for (int m = 0; m < sq_count; ++m) {
             for (size_t i = 0; i < n; ++i) std::copy(x.begin() + i * dim + (size_t)m * ds, x.begin() + i * dim + (size_t)(m + 1) * ds, slice.begin() + i * ds);
-            kmeans_fast_iterations(slice.data(), n, ds, K, codebooks + (size_t)m * K * ds, iters, assign.data(), div_mode);
+            kmeans_fast_iterations(slice.data(), n, ds, K, codebooks + (size_t)m * K * ds, iters, assign.data(), div_mode, repair, repaired);
             if (codes)
                 for (size_t i = 0; i < n; ++i) codes[i * sq_count + m] = (std::uint16_t)assign[i];
         }
@@ -315,12 +336,17 @@ inline std::uint64_t pq_train16_iterations(const float* vecs, size_t n, int dim,
     return empty;
 }
 
+inline std::uint64_t pq_train16_iterations(const float* vecs, size_t n, int dim, int sq_count, int K_coarse, const float* coarse,
+                                           const float* rotation, float* codebooks, int iters, std::uint16_t* codes, int div_mode = 1) {
+    return pq_train16_iterations(vecs, n, dim, sq_count, K_coarse, coarse, rotation, codebooks, iters, codes, div_mode, false, nullptr);
+}
+
 // The product quantizer learned on the GPU: `iters` rounds from `seed` [sq_count][2^sq_bits][dim / sq_count] on the learning set
 // (made residuals to `coarse` and rotated where given: what indexdb_create1 / indexdb_create2 put before the quantizer).  The
 // result carries the rotation, so that pq_to_data_file writes a .pq.data or .opq.data the reference's executables read.
 inline io::pq_data learn_pq_hip(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, const float* seed, int iters,
                                 int K_coarse = 0, const float* coarse = nullptr, const float* rotation = nullptr, int device = 0,
-                                std::uint64_t* empty_out = nullptr) {
+                                std::uint64_t* empty_out = nullptr, bool repair = false, std::uint64_t* repaired_out = nullptr) {
     io::pq_data pq;
     pq.dim = dim;
     pq.sq_count = sq_count;
@@ -332,13 +358,13 @@ inline io::pq_data learn_pq_hip(const float* vecs, size_t n, int dim, int sq_cou
         pq.rotation.assign(rotation, rotation + (size_t)dim * dim);
     }
     if (sq_bits == 16) {                                        // 65536 centroids per sub-quantizer: the sorted update
-        if (qadc_pq_train16_host(vecs, n, dim, sq_count, K_coarse, coarse, rotation, pq.centroids.data(), iters, nullptr, empty_out, 1, 1,
-                                 device) != QADC_OK)
+        if (qadc_pq_train16_repair_host(vecs, n, dim, sq_count, K_coarse, coarse, rotation, pq.centroids.data(), iters, nullptr, empty_out, 1, 1,
+                                        repair ? 1 : 0, repaired_out, device) != QADC_OK)
             throw std::runtime_error(std::string("qadc_pq_train16_host: ") + qadc_last_error());
         return pq;
     }
-    if (qadc_pq_train_host(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, pq.centroids.data(), iters, nullptr, empty_out, 1,
-                           1, device) != QADC_OK)
+    if (qadc_pq_train_repair_host(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, pq.centroids.data(), iters, nullptr, empty_out, 1,
+                                  1, repair ? 1 : 0, repaired_out, device) != QADC_OK)
         throw std::runtime_error(std::string("qadc_pq_train_host: ") + qadc_last_error());
     return pq;
 }
@@ -373,16 +399,20 @@ inline void opq_cross(const float* vecs, size_t n, int dim, int sq_count, int sq
 // CPU twin of qadc_opq_train_host: the loop of include/qadc.h written with pq_train_iterations, opq_cross and procrustes.
 // rotation [dim][dim] in and out (the identity for none), codebooks in and out, codes (nullable) of the closing rounds.  Returns the
 // centroids that hold a NaN; *rounds_done (nullable): rotation updates completed.  Throws where a Procrustes solve does not converge.
+// repair: the loop of the repaired calls; *repaired (nullable) = the vectors moved in all rounds and sub-spaces.
 inline std::uint64_t opq_train_iterations(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
-                                          float* rotation, float* codebooks, int outer, int inner, std::uint8_t* codes, int div_mode = 1,
-                                          int* rounds_done = nullptr) {
+                                          float* rotation, float* codebooks, int outer, int inner, std::uint8_t* codes, int div_mode,
+                                          int* rounds_done, bool repair, std::uint64_t* repaired) {
+    std::uint64_t moved = 0, total = 0;
+    if (repaired) *repaired = 0;
     if (!rotation || outer < 0 || inner < 1) throw std::runtime_error("opq_train_iterations: a rotation, outer >= 0, inner >= 1");
     const size_t cs = sq_bits == 4 ? (size_t)sq_count / 2 : (size_t)sq_count;
     std::vector<std::uint8_t> round_codes(n * cs);
     std::vector<double> M((size_t)dim * dim);
     int done = 0;
     for (int t = 0; t < outer; ++t) {
-        pq_train_iterations(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, inner, round_codes.data(), div_mode);
+        pq_train_iterations(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, inner, round_codes.data(), div_mode, repair, &moved);
+        total += moved;
         opq_cross(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, round_codes.data(), codebooks, M.data());
         const int rc = procrustes(M.data(), dim, rotation);
         if (rc == kProcrustesNotFinite) break;                      // the rotation stays as it is
@@ -390,14 +420,24 @@ inline std::uint64_t opq_train_iterations(const float* vecs, size_t n, int dim, 
         ++done;
     }
     if (rounds_done) *rounds_done = done;
-    return pq_train_iterations(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, inner, codes, div_mode);
+    const std::uint64_t empty = pq_train_iterations(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, inner, codes, div_mode, repair, &moved);
+    if (repaired) *repaired = total + moved;
+    return empty;
+}
+
+inline std::uint64_t opq_train_iterations(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, int K_coarse, const float* coarse,
+                                          float* rotation, float* codebooks, int outer, int inner, std::uint8_t* codes, int div_mode = 1,
+                                          int* rounds_done = nullptr) {
+    return opq_train_iterations(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, rotation, codebooks, outer, inner, codes, div_mode, rounds_done, false,
+                                nullptr);
 }
 
 // The OPQ rotation and its product quantizer learned on the GPU (qadc_opq_train_host) from `seed` and a start rotation (NULL: the
 // identity): an io::pq_data with is_opq set, so that pq_to_data_file writes the .opq.data the reference's executables read.
 inline io::pq_data learn_opq_hip(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, const float* seed, int outer, int inner = 1,
                                  int K_coarse = 0, const float* coarse = nullptr, const float* rotation = nullptr, int device = 0,
-                                 std::uint64_t* empty_out = nullptr, int* rounds_done_out = nullptr) {
+                                 std::uint64_t* empty_out = nullptr, int* rounds_done_out = nullptr, bool repair = false,
+                                 std::uint64_t* repaired_out = nullptr) {
     io::pq_data pq;
     pq.dim = dim;
     pq.sq_count = sq_count;
@@ -408,8 +448,8 @@ inline io::pq_data learn_opq_hip(const float* vecs, size_t n, int dim, int sq_co
     pq.rotation.assign((size_t)dim * dim, 0.0f);
     for (int r = 0; r < dim; ++r) pq.rotation[(size_t)r * dim + r] = 1.0f;
     if (rotation) pq.rotation.assign(rotation, rotation + (size_t)dim * dim);
-    if (qadc_opq_train_host(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, pq.rotation.data(), pq.centroids.data(), outer, inner, nullptr,
-                            empty_out, rounds_done_out, 1, 1, device) != QADC_OK)
+    if (qadc_opq_train_repair_host(vecs, n, dim, sq_count, sq_bits, K_coarse, coarse, pq.rotation.data(), pq.centroids.data(), outer, inner, nullptr,
+                                   empty_out, rounds_done_out, 1, 1, repair ? 1 : 0, repaired_out, device) != QADC_OK)
         throw std::runtime_error(std::string("qadc_opq_train_host: ") + qadc_last_error());
     return pq;
 }
@@ -440,20 +480,21 @@ inline std::vector<float> seed_kmeanspp_hip(const float* vecs, size_t n, int dim
 // learn_pq_hip / learn_opq_hip without a caller-made seed: the codebooks start from seed_kmeanspp_hip(k = 2^sq_bits) on the same front
 inline io::pq_data learn_pq_hip(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, std::uint64_t seed, int iters, int K_coarse = 0,
                                 const float* coarse = nullptr, const float* rotation = nullptr, int device = 0,
-                                std::uint64_t* empty_out = nullptr) {
+                                std::uint64_t* empty_out = nullptr, bool repair = false, std::uint64_t* repaired_out = nullptr) {
     if (sq_bits <= 0 || sq_bits > 16) throw std::runtime_error("learn_pq_hip: bad arguments");
     const std::vector<float> start = seed_kmeanspp_hip(vecs, n, dim, sq_count, (size_t)1 << sq_bits, seed, K_coarse, coarse, rotation, device);
-    return learn_pq_hip(vecs, n, dim, sq_count, sq_bits, start.data(), iters, K_coarse, coarse, rotation, device, empty_out);
+    return learn_pq_hip(vecs, n, dim, sq_count, sq_bits, start.data(), iters, K_coarse, coarse, rotation, device, empty_out, repair, repaired_out);
 }
 
 // (seeded under the start rotation, NULL: the identity)
 inline io::pq_data learn_opq_hip(const float* vecs, size_t n, int dim, int sq_count, int sq_bits, std::uint64_t seed, int outer, int inner = 1,
                                  int K_coarse = 0, const float* coarse = nullptr, const float* rotation = nullptr, int device = 0,
-                                 std::uint64_t* empty_out = nullptr, int* rounds_done_out = nullptr) {
+                                 std::uint64_t* empty_out = nullptr, int* rounds_done_out = nullptr, bool repair = false,
+                                 std::uint64_t* repaired_out = nullptr) {
     if (sq_bits <= 0 || sq_bits > 16) throw std::runtime_error("learn_opq_hip: bad arguments");
     const std::vector<float> start = seed_kmeanspp_hip(vecs, n, dim, sq_count, (size_t)1 << sq_bits, seed, K_coarse, coarse, rotation, device);
     return learn_opq_hip(vecs, n, dim, sq_count, sq_bits, start.data(), outer, inner, K_coarse, coarse, rotation, device, empty_out,
-                         rounds_done_out);
+                         rounds_done_out, repair, repaired_out);
 }
 
 constexpr int kmeans_iter_max = 50;                            // databases.cpp:92

@@ -53,6 +53,8 @@ SYMBOLS = [
     "qadc_pq_train16_host", "qadc_pq_train16_device", "qadc_pq_update16_host",
     "qadc_opq_cross_host", "qadc_opq_cross_device", "qadc_procrustes_host", "qadc_opq_train_host", "qadc_opq_train_device",
     "qadc_kmeans_seed_host", "qadc_kmeans_seed_device",
+    "qadc_pq_repair_host", "qadc_pq_train_repair_host", "qadc_pq_train_repair_device", "qadc_pq_train16_repair_host",
+    "qadc_pq_train16_repair_device", "qadc_opq_train_repair_host", "qadc_opq_train_repair_device",
     "qadc_adc_filter_create", "qadc_adc_filter_create_device", "qadc_adc_filter_info", "qadc_adc_filter_destroy", "qadc_adc_index_set_filter",
     "qadc_adc_query_scan_filtered", "qadc_adc_query_scan_device_filtered", "qadc_adc_query_scan_candidates_filtered",
     "qadc_adc_search_filtered", "qadc_adc_search_device_filtered", "qadc_adc_search_candidates_filtered",
@@ -277,6 +279,11 @@ def lib():
         L.qadc_kmeans_seed_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_int, f32p, f32p, C.c_uint64, f32p, u32p, u64p,
                                             C.c_int]
         L.qadc_kmeans_seed_device.argtypes = [C.c_void_p] + L.qadc_kmeans_seed_host.argtypes[1:]
+        L.qadc_pq_repair_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p, u32p, C.c_int]
+        for name in ("qadc_pq_train", "qadc_pq_train16", "qadc_opq_train"):    # ..., sum_mode, repair, repaired_out, device_id
+            for form in ("_host", "_device"):
+                old = getattr(L, name + form).argtypes
+                getattr(L, name + "_repair" + form).argtypes = old[:-1] + [C.c_int, u64p, C.c_int]
         for name in ("qadc_adc_index_remove_labels", "qadc_index_remove_labels"):
             getattr(L, name).argtypes = [C.c_void_p, u32p, C.c_uint64, u64p]
             getattr(L, name + "_device").argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, u64p]
@@ -573,12 +580,18 @@ def _train_pq_args(dim, codebooks_seed, bits, coarse, rotation):
     return cb, bits, co, rot
 
 
-def train_pq(vectors, codebooks_seed, iters, bits=None, coarse=None, rotation=None, device=0, div_mode=1, sum_mode=1):
+def _repair_result(out, repair, repaired):
+    return out + (int(repaired.value),) if repair else out
+
+
+def train_pq(vectors, codebooks_seed, iters, bits=None, coarse=None, rotation=None, device=0, div_mode=1, sum_mode=1, repair=False):
     """Learn a product quantizer on the GPU (qadc_pq_train_host): `iters` rounds of kmeans_fast_iterations_thread in every sub-space
     at once, from the caller's seed [sq_count][2^bits][dim / sq_count] (pq_seed); bits (4 or 8) is inferred from the seed's second
     axis.  With coarse [K][dim] the learning set is first made residuals to the nearest coarse centroid, with rotation
     [dim][dim] those are rotated.  -> (codebooks float32 like the seed, codes uint8 of the last round in the encoder's layout —
-    [n][sq_count / 2] packed nibbles at 4 bits, [n][sq_count] at 8 —, empty = centroids that are NaN at return)."""
+    [n][sq_count / 2] packed nibbles at 4 bits, [n][sq_count] at 8 —, empty = centroids that are NaN at return).
+    repair=True (qadc_pq_train_repair_host): every round refills its empty clusters between the assignment and the update
+    (include/qadc.h "Empty-cluster repair"), and the tuple gains a last element `repaired`, the vectors moved in all rounds."""
     v = np.ascontiguousarray(vectors, np.float32)
     if v.ndim != 2:
         raise QadcError("vectors has shape %s, expected [n][dim]" % (tuple(v.shape),))
@@ -586,13 +599,14 @@ def train_pq(vectors, codebooks_seed, iters, bits=None, coarse=None, rotation=No
     cb, bits, co, rot = _train_pq_args(dim, codebooks_seed, bits, coarse, rotation)
     nsq = cb.shape[0]
     codes = np.zeros((n, nsq // 2 if bits == 4 else nsq), np.uint8)
-    empty = C.c_uint64(0)
-    _check(lib().qadc_pq_train_host(_p(v, f32p), n, dim, nsq, bits, 0 if co is None else co.shape[0], _p(co, f32p), _p(rot, f32p),
-                                    _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode, sum_mode, device))
-    return cb, codes, int(empty.value)
+    empty, repaired = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().qadc_pq_train_repair_host(_p(v, f32p), n, dim, nsq, bits, 0 if co is None else co.shape[0], _p(co, f32p), _p(rot, f32p),
+                                           _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode, sum_mode,
+                                           int(bool(repair)), C.byref(repaired), device))
+    return _repair_result((cb, codes, int(empty.value)), repair, repaired)
 
 
-def train_pq_device(vectors, codebooks_seed, iters, bits=None, coarse=None, rotation=None, div_mode=1, sum_mode=1):
+def train_pq_device(vectors, codebooks_seed, iters, bits=None, coarse=None, rotation=None, div_mode=1, sum_mode=1, repair=False):
     """train_pq on a learning set already in device memory: a contiguous float32 [n][dim] torch tensor on a GPU (read only).  The
     seed, coarse and rotation are host arrays; the results come back as numpy arrays like train_pq's."""
     import torch
@@ -608,12 +622,12 @@ def train_pq_device(vectors, codebooks_seed, iters, bits=None, coarse=None, rota
     cb, bits, co, rot = _train_pq_args(dim, codebooks_seed, bits, coarse, rotation)
     nsq = cb.shape[0]
     codes = np.zeros((n, nsq // 2 if bits == 4 else nsq), np.uint8)
-    empty = C.c_uint64(0)
+    empty, repaired = C.c_uint64(0), C.c_uint64(0)
     torch.cuda.current_stream(vectors.device).synchronize()                # the learning set is complete before the call
-    _check(lib().qadc_pq_train_device(C.c_void_p(vectors.data_ptr()), n, dim, nsq, bits, 0 if co is None else co.shape[0], _p(co, f32p),
-                                      _p(rot, f32p), _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode,
-                                      sum_mode, vectors.device.index or 0))
-    return cb, codes, int(empty.value)
+    _check(lib().qadc_pq_train_repair_device(C.c_void_p(vectors.data_ptr()), n, dim, nsq, bits, 0 if co is None else co.shape[0], _p(co, f32p),
+                                             _p(rot, f32p), _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode,
+                                             sum_mode, int(bool(repair)), C.byref(repaired), vectors.device.index or 0))
+    return _repair_result((cb, codes, int(empty.value)), repair, repaired)
 
 
 def _train_pq16_args(dim, codebooks_seed, coarse, rotation):
@@ -624,11 +638,12 @@ def _train_pq16_args(dim, codebooks_seed, coarse, rotation):
     return cb, co, rot
 
 
-def train_pq16(vectors, codebooks_seed, iters, coarse=None, rotation=None, device=0, div_mode=1, sum_mode=1):
+def train_pq16(vectors, codebooks_seed, iters, coarse=None, rotation=None, device=0, div_mode=1, sum_mode=1, repair=False):
     """Learn a product quantizer of 16-bit sub-quantizers on the GPU (qadc_pq_train16_host): train_pq with a seed
     [sq_count][65536][dim / sq_count], sq_count 2, 4 or 8 (pq_seed(v, sq_count, 16, rng)).  A round is the 16-bit encoder and the
     sorted centroid update.  -> (codebooks float32 like the seed, codes uint16 [n][sq_count] of the last round — adc_encode16's
-    layout —, empty = centroids that are NaN at return)."""
+    layout —, empty = centroids that are NaN at return).  repair=True (qadc_pq_train16_repair_host): as for train_pq, the tuple
+    gains `repaired`."""
     v = np.ascontiguousarray(vectors, np.float32)
     if v.ndim != 2:
         raise QadcError("vectors has shape %s, expected [n][dim]" % (tuple(v.shape),))
@@ -636,13 +651,14 @@ def train_pq16(vectors, codebooks_seed, iters, coarse=None, rotation=None, devic
     cb, co, rot = _train_pq16_args(dim, codebooks_seed, coarse, rotation)
     nsq = cb.shape[0]
     codes = np.zeros((n, nsq), "<u2")
-    empty = C.c_uint64(0)
-    _check(lib().qadc_pq_train16_host(_p(v, f32p), n, dim, nsq, 0 if co is None else co.shape[0], _p(co, f32p), _p(rot, f32p), _p(cb, f32p),
-                                      iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode, sum_mode, device))
-    return cb, codes.astype(np.uint16, copy=False), int(empty.value)
+    empty, repaired = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().qadc_pq_train16_repair_host(_p(v, f32p), n, dim, nsq, 0 if co is None else co.shape[0], _p(co, f32p), _p(rot, f32p), _p(cb, f32p),
+                                             iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode, sum_mode, int(bool(repair)),
+                                             C.byref(repaired), device))
+    return _repair_result((cb, codes.astype(np.uint16, copy=False), int(empty.value)), repair, repaired)
 
 
-def train_pq16_device(vectors, codebooks_seed, iters, coarse=None, rotation=None, div_mode=1, sum_mode=1):
+def train_pq16_device(vectors, codebooks_seed, iters, coarse=None, rotation=None, div_mode=1, sum_mode=1, repair=False):
     """train_pq16 on a learning set already in device memory: a contiguous float32 [n][dim] torch tensor on a GPU (read only).  The
     seed, coarse and rotation are host arrays; the results come back as numpy arrays like train_pq16's."""
     import torch
@@ -658,12 +674,12 @@ def train_pq16_device(vectors, codebooks_seed, iters, coarse=None, rotation=None
     cb, co, rot = _train_pq16_args(dim, codebooks_seed, coarse, rotation)
     nsq = cb.shape[0]
     codes = np.zeros((n, nsq), "<u2")
-    empty = C.c_uint64(0)
+    empty, repaired = C.c_uint64(0), C.c_uint64(0)
     torch.cuda.current_stream(vectors.device).synchronize()                # the learning set is complete before the call
-    _check(lib().qadc_pq_train16_device(C.c_void_p(vectors.data_ptr()), n, dim, nsq, 0 if co is None else co.shape[0], _p(co, f32p),
-                                        _p(rot, f32p), _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode,
-                                        sum_mode, vectors.device.index or 0))
-    return cb, codes.astype(np.uint16, copy=False), int(empty.value)
+    _check(lib().qadc_pq_train16_repair_device(C.c_void_p(vectors.data_ptr()), n, dim, nsq, 0 if co is None else co.shape[0], _p(co, f32p),
+                                               _p(rot, f32p), _p(cb, f32p), iters, codes.ctypes.data_as(C.c_void_p), C.byref(empty), div_mode,
+                                               sum_mode, int(bool(repair)), C.byref(repaired), vectors.device.index or 0))
+    return _repair_result((cb, codes.astype(np.uint16, copy=False), int(empty.value)), repair, repaired)
 
 
 def pq_update16(vectors, codes, sq_count, div_mode=1, device=0):
@@ -682,6 +698,25 @@ def pq_update16(vectors, codes, sq_count, div_mode=1, device=0):
     _check(lib().qadc_pq_update16_host(_p(v, f32p), n, dim, sq_count, c.ctypes.data_as(C.c_void_p), _p(cb, f32p), _p(counts, u32p), div_mode,
                                        device))
     return cb, counts
+
+
+def pq_repair(vectors, codebooks, codes, device=0):
+    """The empty-cluster repair of the training rounds alone (qadc_pq_repair_host; include/qadc.h "Empty-cluster repair"): vectors
+    [n][dim] as the quantizer sees them, codebooks [sq_count][2^bits][dim / sq_count] (bits 4, 8 or 16 from the second axis), codes in
+    the encoder's layout (uint8 [n][sq_count / 2] packed nibbles, uint8 [n][sq_count], or uint16 [n][sq_count]) -> (codes with every
+    empty cluster given the farthest eligible vector, moved uint32 [sq_count])."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2:
+        raise QadcError("vectors has shape %s, expected [n][dim]" % (tuple(v.shape),))
+    n, dim = v.shape
+    cb, bits, _, _ = _train_pq_args(dim, codebooks, None, None, None)
+    nsq = cb.shape[0]
+    c = np.array(codes, "<u2" if bits == 16 else np.uint8, order="C", copy=True)
+    if c.shape != (n, nsq // 2 if bits == 4 else nsq):
+        raise QadcError("codes has shape %s, expected the encoder's layout [%d][%d]" % (tuple(c.shape), n, nsq // 2 if bits == 4 else nsq))
+    moved = np.zeros(nsq, np.uint32)
+    _check(lib().qadc_pq_repair_host(_p(v, f32p), n, dim, nsq, bits, _p(cb, f32p), c.ctypes.data_as(C.c_void_p), _p(moved, u32p), device))
+    return (c.astype(np.uint16, copy=False) if bits == 16 else c), moved
 
 
 QADC_OPQ_BLOCK = 2048              # include/qadc.h: vectors per float partial sum of the OPQ cross matrix
@@ -759,33 +794,35 @@ def _train_opq_args(n, dim, codebooks_seed, bits, coarse, rotation):
     return cb, bits, co, rot, np.zeros((n, nsq // 2 if bits == 4 else nsq), np.uint8)
 
 
-def train_opq(vectors, codebooks_seed, outer, inner=1, rotation=None, coarse=None, bits=None, device=0, div_mode=1, sum_mode=1):
+def train_opq(vectors, codebooks_seed, outer, inner=1, rotation=None, coarse=None, bits=None, device=0, div_mode=1, sum_mode=1, repair=False):
     """Learn an OPQ rotation and its product quantizer on the GPU (qadc_opq_train_host): `outer` times [train_pq with `inner`
     rounds under the current rotation, opq_cross, procrustes], then `inner` closing rounds under the final rotation — bit for bit
     that loop of the public calls, with the learning set uploaded once.  rotation: the start [dim][dim] (None: the identity).
     -> (rotation float32 [dim][dim], codebooks, codes, empty, rounds_done) — codebooks, codes and empty as train_pq returns them;
-    rounds_done < outer where a cross matrix was not finite (the rotation then stays as it was)."""
+    rounds_done < outer where a cross matrix was not finite (the rotation then stays as it was).  repair=True
+    (qadc_opq_train_repair_host): the loop of train_pq(repair=True); the tuple gains a last element `repaired`."""
     v = np.ascontiguousarray(vectors, np.float32)
     if v.ndim != 2:
         raise QadcError("vectors has shape %s, expected [n][dim]" % (tuple(v.shape),))
     n, dim = v.shape
     cb, bits, co, rot, codes = _train_opq_args(n, dim, codebooks_seed, bits, coarse, rotation)
-    empty, done = C.c_uint64(0), C.c_int32(0)
-    _check(lib().qadc_opq_train_host(_p(v, f32p), n, dim, cb.shape[0], bits, 0 if co is None else co.shape[0], _p(co, f32p), _p(rot, f32p),
-                                     _p(cb, f32p), outer, inner, codes.ctypes.data_as(C.c_void_p), C.byref(empty), C.byref(done),
-                                     div_mode, sum_mode, device))
-    return rot, cb, codes, int(empty.value), int(done.value)
+    empty, done, repaired = C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
+    _check(lib().qadc_opq_train_repair_host(_p(v, f32p), n, dim, cb.shape[0], bits, 0 if co is None else co.shape[0], _p(co, f32p), _p(rot, f32p),
+                                            _p(cb, f32p), outer, inner, codes.ctypes.data_as(C.c_void_p), C.byref(empty), C.byref(done),
+                                            div_mode, sum_mode, int(bool(repair)), C.byref(repaired), device))
+    return _repair_result((rot, cb, codes, int(empty.value), int(done.value)), repair, repaired)
 
 
-def train_opq_device(vectors, codebooks_seed, outer, inner=1, rotation=None, coarse=None, bits=None, div_mode=1, sum_mode=1):
+def train_opq_device(vectors, codebooks_seed, outer, inner=1, rotation=None, coarse=None, bits=None, div_mode=1, sum_mode=1, repair=False):
     """train_opq on a learning set already in device memory: a contiguous float32 [n][dim] torch tensor on a GPU (read only)."""
     n, dim = _device_vectors(vectors, "train_opq_device")
     cb, bits, co, rot, codes = _train_opq_args(n, dim, codebooks_seed, bits, coarse, rotation)
-    empty, done = C.c_uint64(0), C.c_int32(0)
-    _check(lib().qadc_opq_train_device(C.c_void_p(vectors.data_ptr()), n, dim, cb.shape[0], bits, 0 if co is None else co.shape[0],
-                                       _p(co, f32p), _p(rot, f32p), _p(cb, f32p), outer, inner, codes.ctypes.data_as(C.c_void_p),
-                                       C.byref(empty), C.byref(done), div_mode, sum_mode, vectors.device.index or 0))
-    return rot, cb, codes, int(empty.value), int(done.value)
+    empty, done, repaired = C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
+    _check(lib().qadc_opq_train_repair_device(C.c_void_p(vectors.data_ptr()), n, dim, cb.shape[0], bits, 0 if co is None else co.shape[0],
+                                              _p(co, f32p), _p(rot, f32p), _p(cb, f32p), outer, inner, codes.ctypes.data_as(C.c_void_p),
+                                              C.byref(empty), C.byref(done), div_mode, sum_mode, int(bool(repair)), C.byref(repaired),
+                                              vectors.device.index or 0))
+    return _repair_result((rot, cb, codes, int(empty.value), int(done.value)), repair, repaired)
 
 
 def pq_seed(vectors, sq_count, bits, rng):

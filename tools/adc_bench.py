@@ -42,6 +42,14 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             with the rotation, opq_cross, procrustes: the learning set uploaded twice per outer round); the two routes' arrays are
             first asserted identical.  Beside it train_pq with ten rounds, and the reconstruction error
             (tests/pq_train_compose.reconstruction_error) of the learned pair against plain PQ's at those ten rounds
+  --repair  the train and opq legs measure the empty-cluster repair instead (also under --bits 4 at 16x4 and
+            --bits 16 at 2x16).  train: (a) on the leg's own 10^6 x 128 set (no empty cluster) the plain call and the repaired call,
+            alternated in one process, and the time per round of each; with --parent-lib FILE a third arm alternates with them: the
+            plain C call of that other build of the library (the parent commit's), loaded beside this one.  (b) the same set with
+            REPAIR_DUP of its rows overwritten by copies of other rows and sub-space 0 zeroed on REPAIR_ZERO of the rows, seeded by
+            pq_seed: empty, repaired, and the mean squared quantization error (pq_train_compose.reconstruction_error / n, the
+            vectors re-encoded under the final codebooks by the index's own encoder) with and without the repair.  opq: train_opq
+            with and without repair=True on set (b), times, empty and repaired
   seed      k-means++ seeding (not in the default legs; also under --bits 4 at 16x4 and --bits 16 at 2x16): 10^6
             clustered 128-d vectors; kmeans_seed per call at the index shape (and for K = 4096 coarse centroids at 8 bits), a round's
             time from the difference of a k and a k / 2 call and the bytes per second of its one pass over the learning set, one
@@ -905,9 +913,111 @@ def train16_leg(iters, res, profile_only=False):
               "%.3f s): the share of a round outside the encoder is at least %.3f" % (round_s, enc_s, roof, outside), flush=True)
 
 
+REPAIR = False      # --repair
+PARENT_LIB = None   # --parent-lib
+REPAIR_DUP, REPAIR_ZERO = 0.10, 0.30
+
+
+def repair_sets(bits):
+    """-> (nsq, rounds, healthy set, dying set, rng): the train leg's 10^6 x 128 set, and the same with REPAIR_DUP of its rows
+    overwritten by copies of other rows and sub-space 0 zeroed on REPAIR_ZERO of the rows"""
+    rng = np.random.default_rng(1900 + bits)
+    n, dim = 1_000_000, 128
+    nsq, rounds = {4: (16, 10), 8: (8, 10), 16: (2, 2)}[bits]
+    vectors, _ = clustered(rng, n, dim)
+    dying = vectors.copy()
+    dup = rng.choice(n, int(n * REPAIR_DUP), replace=False)
+    dying[dup] = vectors[rng.integers(0, n, len(dup))]
+    dying[rng.choice(n, int(n * REPAIR_ZERO), replace=False), :dim // nsq] = 0
+    return nsq, rounds, vectors, dying, rng
+
+
+def repair_leg(bits, iters, res):
+    """the empty-cluster repair: its cost where no cluster is empty, its effect where clusters die"""
+    import ctypes as C
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pq_train_compose as ptc
+    import pq_train16_compose as pt16
+    nsq, rounds, vectors, dying, rng = repair_sets(bits)
+    n, dim = vectors.shape
+    train = pyqadc.train_pq16 if bits == 16 else pyqadc.train_pq
+    encode = {4: pyqadc.pq_encode, 8: pyqadc.adc_encode, 16: pyqadc.adc_encode16}[bits]
+    error = (pt16 if bits == 16 else ptc).reconstruction_error
+    tag = "repair_%dx%d_n%d" % (nsq, bits, n)
+    seed = pyqadc.pq_seed(vectors, nsq, bits, rng)
+    plain = train(vectors, seed, rounds)
+    fixed = train(vectors, seed, rounds, repair=True)
+    arms = {"plain": lambda: train(vectors, seed, rounds), "repair": lambda: train(vectors, seed, rounds, repair=True)}
+    if PARENT_LIB:                                             # the other build's plain C call, in this process, in turn with ours
+        old = C.CDLL(PARENT_LIB)
+        f32p = C.POINTER(C.c_float)
+        fn = old.qadc_pq_train16_host if bits == 16 else old.qadc_pq_train_host
+        fn.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int] + ([C.c_int] if bits != 16 else []) + [C.c_int, f32p, f32p, f32p, C.c_int, C.c_void_p,
+                                                                                                  C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int]
+        cols = nsq // 2 if bits == 4 else nsq
+
+        def parent():
+            cb = seed.copy()
+            codes = np.zeros((n, cols), "<u2" if bits == 16 else np.uint8)
+            empty = C.c_uint64(0)
+            head = (vectors.ctypes.data_as(f32p), n, dim, nsq) + ((bits,) if bits != 16 else ())
+            assert fn(*head, 0, None, None, cb.ctypes.data_as(f32p), rounds, codes.ctypes.data_as(C.c_void_p), C.byref(empty), 1, 1, 0) == 0
+            return cb, codes, empty.value
+        assert np.array_equal(parent()[0].view(np.uint32), plain[0].view(np.uint32)), "the parent build's codebooks differ from the plain call's"
+        arms["parent"] = parent
+    times = {k: [] for k in arms}
+    for f in arms.values():
+        f()
+    for _ in range(max(3, iters // 2)):                        # A B C A B C ...
+        for k, f in arms.items():
+            t0 = time.perf_counter()
+            f()
+            times[k].append(time.perf_counter() - t0)
+    for k, ts in times.items():
+        res[tag + "_healthy_%s_s" % k] = float(np.median(ts))
+        res[tag + "_healthy_%s_all_s" % k] = [float(t) for t in ts]
+    base = res[tag + "_healthy_%s_s" % ("parent" if PARENT_LIB else "plain")]
+    res[tag + "_healthy_rounds"] = rounds
+    res[tag + "_healthy_repair_over_%s" % ("parent" if PARENT_LIB else "plain")] = res[tag + "_healthy_repair_s"] / base
+    res[tag + "_healthy_empty"] = [int(plain[2]), int(fixed[2])]
+    res[tag + "_healthy_repaired"] = int(fixed[3])
+    print("repair %dx%d, %.0e clustered 128-d vectors, %d rounds, call to return (upload included): %s; repaired / %s = %.4f; empty %d and %d, "
+          "repaired %d" % (nsq, bits, n, rounds, ", ".join("%s %.4f s" % (k, float(np.median(ts))) for k, ts in times.items()),
+                           "parent" if PARENT_LIB else "plain", res[tag + "_healthy_repair_s"] / base, plain[2], fixed[2], fixed[3]), flush=True)
+    seed = pyqadc.pq_seed(dying, nsq, bits, rng)
+    for name, kw in (("plain", {}), ("repair", {"repair": True})):
+        out = train(dying, seed, rounds, **kw)
+        with np.errstate(all="ignore"):
+            codes = encode(out[0], dying)
+            codes = codes[-1] if isinstance(codes, tuple) else codes
+            mse = error(dying, out[0], codes) / n
+        res[tag + "_dying_%s_empty" % name] = int(out[2])
+        res[tag + "_dying_%s_repaired" % name] = int(out[3]) if kw else 0
+        res[tag + "_dying_%s_mse" % name] = float(mse)
+        print("repair %dx%d, the same set with %.0f %% of the rows duplicated and sub-space 0 zeroed on %.0f %%, %d rounds, %s: empty %d, repaired "
+              "%d, mean squared quantization error %.6g" % (nsq, bits, 100 * REPAIR_DUP, 100 * REPAIR_ZERO, rounds, name, out[2], int(out[3]) if kw else 0,
+                                                            mse), flush=True)
+
+
+def opq_repair_leg(bits, iters, res):
+    """train_opq with and without the repair on the train leg's dying set"""
+    nsq, _, _, dying, rng = repair_sets(bits)
+    seed = pyqadc.pq_seed(dying, nsq, bits, rng)
+    tag = "repair_opq_%dx%d_n%d" % (nsq, bits, len(dying))
+    plain, fixed = pyqadc.train_opq(dying, seed, 4, 2), pyqadc.train_opq(dying, seed, 4, 2, repair=True)
+    t_plain, t_fixed = alternated(lambda: pyqadc.train_opq(dying, seed, 4, 2), lambda: pyqadc.train_opq(dying, seed, 4, 2, repair=True), 3, warmup=0)
+    res[tag + "_plain_s"], res[tag + "_repair_s"] = t_plain, t_fixed
+    res[tag + "_empty"] = [int(plain[3]), int(fixed[3])]
+    res[tag + "_repaired"] = int(fixed[5])
+    print("repair, OPQ %dx%d on the dying set, outer 4 x inner 2: train_opq %.3f s, with repair %.3f s; empty %d and %d, repaired %d"
+          % (nsq, bits, t_plain, t_fixed, plain[3], fixed[3], fixed[5]), flush=True)
+
+
 def train_leg(bits, iters, res):
     """train_pq alternated with the route without it: kmeans_iterations on every host slice"""
     rng = np.random.default_rng(1900 + bits)
+    if REPAIR:
+        return repair_leg(bits, iters, res)
     dim, rounds = 128, 10
     nsq = {4: 16, 8: 8}[bits]
     ds = dim // nsq
@@ -944,6 +1054,8 @@ def train_leg(bits, iters, res):
 
 def opq_leg(bits, iters, res):
     """train_opq alternated with the same loop composed from the public calls; the learned pair's reconstruction error beside plain PQ's"""
+    if REPAIR:
+        return opq_repair_leg(bits, iters, res)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import pq_train_compose as ptc
     rng = np.random.default_rng(2100 + bits)
@@ -1363,7 +1475,9 @@ def word_legs(legs, iters, res):
         add_leg(16, iters, res)
     if "remove" in legs:
         remove_leg(16, iters, res)
-    if "train" in legs or "train_profile" in legs:
+    if "train" in legs and REPAIR:
+        repair_leg(16, iters, res)
+    elif "train" in legs or "train_profile" in legs:
         train16_leg(iters, res, profile_only="train" not in legs)
     if "seed" in legs:
         seed_leg(16, iters, res)
@@ -1437,9 +1551,11 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--trained-codebooks", action="store_true")
+    ap.add_argument("--repair", action="store_true")
+    ap.add_argument("--parent-lib", default=None)
     a = ap.parse_args()
-    global TRAINED
-    TRAINED = a.trained_codebooks
+    global TRAINED, REPAIR, PARENT_LIB
+    TRAINED, REPAIR, PARENT_LIB = a.trained_codebooks, a.repair, a.parent_lib
     if a.legs is None:
         a.legs = "flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search" if a.bits == 8 else "lone,ivf_search"
     legs = a.legs.split(",")

@@ -48,8 +48,11 @@ const char* qadc_version(void);
  *    4 bytes  every other float, uint32 and int32 array: d_queries, d_keys, d_values, d_sizes, d_labels, d_counts, d_out_keys,
  *             d_out_dist, d_out_sizes, and d_vectors of qadc_index_add_vectors_device, _labelled_device, qadc_refine_add_device,
  *             qadc_refine_put_device, qadc_pq_encode(_mode), qadc_pq_train_device, qadc_opq_cross_device, qadc_opq_train_device,
- *             qadc_kmeans_seed_device, qadc_pq_train_repair_device, qadc_opq_train_repair_device
- *    1 byte   d_codes of qadc_pq_encode(_mode): [n][M/2] bytes, each written by itself
+ *             qadc_kmeans_seed_device, qadc_pq_train_repair_device, qadc_opq_train_repair_device; d_assign, d_vectors, d_out and
+ *             d_err_out of qadc_pq_decode_device, d_keys, d_out and d_where_out of qadc_adc_index_reconstruct(_rows)_device
+ *             (a where entry is written as its two 32-bit words)
+ *    1 byte   d_codes of qadc_pq_encode(_mode): [n][M/2] bytes, each written by itself; d_codes of qadc_pq_decode_device, read
+ *             byte by byte at every code width
  * Host arrays carry no such requirement beyond their element type's.
  * ------------------------------------------------------------------------------------------- */
 
@@ -1108,6 +1111,74 @@ int qadc_adc_index_reserve(qadc_adc_index* idx, int part_count, const uint32_t* 
 /* Diagnostics (no reference counterpart; std::vector reallocates silently in databases.hpp:291-297): the qadc_adc_index_add_vectors
  * calls that had to move the database to grow it. */
 uint64_t qadc_adc_index_relocations(const qadc_adc_index* idx);
+
+/* ---- Reconstruction: PQ codes back to vectors, on the GPU.  No reference counterpart (the reference
+ * never decodes), so every bit is defined here and pinned to a CPU twin, host/pq_decode.hpp pq_decode; the device equals it bit
+ * for bit. ----
+ *
+ * Row i has the sub-quantizer codes code(i, m), m < sq_count, and with a coarse quantizer (K > 0) a partition p(i).
+ *   1. Gather.  y[b] = codebooks[m][code(i, m)][b - m dsub], m = b / dsub, dsub = dim / sq_count: a copy, no arithmetic.  The code
+ *      layouts are the encoders': sq_bits 4 packed nibbles [n][sq_count / 2], the even sub-quantizer in the low nibble; 8: bytes
+ *      [n][sq_count]; 16: little-endian uint16 [n][sq_count].  Accepted (sq_count, sq_bits): 16 x 4, 32 x 4; 4 x 8, 8 x 8, 16 x 8;
+ *      2 x 16, 4 x 16, 8 x 16.  codebooks [sq_count][2^sq_bits][dsub].
+ *   2. Un-rotate.  With a rotation [dim][dim], z[c] = ONE float chain acc = fmaf(y[r], rotation[r][c], acc) over ascending r from
+ *      0.0f: the transpose of the encoders' rotated[r] = sum_c x[c] rotation[r][c], hence the inverse for the orthogonal matrices the
+ *      trainers return.  For any other matrix it is still exactly this chain (the transpose, not an inverse).  Without a rotation
+ *      z = y bit for bit.  Consequence: under a rotation ONE NaN (or infinite: 0 * inf) component of y makes the whole row NaN,
+ *      since every chain passes every component; without one only that component is NaN.
+ *   3. Coarse centroid.  With K > 0, x[c] = z[c] + coarse[p(i)][c], one float add — the inverse of the encoder's
+ *      x[d] - coarse[best][d]; with K = 0, x = z.
+ *   4. Error (optional).  Given the originals v, err[i] = ONE chain acc = fmaf(d, d, acc), d = v[c] - x[c], over ascending c from
+ *      0.0f: the k-means objective of row i.  No total is formed on the device (pyqadc.quant_error sums in float64, ascending i).
+ * A MISSING row (below: a partition outside [0, K), a key no row holds) is 0x7FC00000 in every float of its out row; its err, where
+ * asked for, follows from the chain (NaN).  NaN payloads: wherever arithmetic was done — steps 2, 3 and 4 — a NaN result is written
+ * as 0x7FC00000 (payloads differ between processors); the copy of step 1 alone, no rotation and K = 0, keeps a centroid's bits.
+ *
+ * qadc_pq_decode_host: stateless, the inverse of qadc_ivf_encode_host, qadc_adc_encode_host and qadc_adc_encode16_host.
+ *   assign [n] (the encoders' assign_out; read with K > 0 only), codes [n][code bytes], vectors [n][dim] (nullable: read for
+ *   err_out only) -> out [n][dim], err_out [n] (nullable).  An assign entry outside [0, K) is not a refusal: that row is a missing
+ *   row.  Works in passes of QADC_DECODE_CHUNK rows: the device scratch is bounded by one pass and the quantizers whatever n is, and
+ *   no result depends on the pass size.  n = 0 is legal and touches nothing.  Synchronous.
+ *   Refused with QADC_E_ARG before the first HIP call, the message naming the cause: a (sq_count, sq_bits) pair outside the list;
+ *   dim not a positive multiple of sq_count; dim > 2048 at 4 bits, > 4096 at 8 and 16 bits (the encoders' limits); NULL codebooks;
+ *   K < 0; NULL coarse or NULL assign with K > 0; NULL vectors with err_out given; NULL codes or out with n > 0.
+ * qadc_pq_decode_device: d_assign, d_codes, d_vectors, d_out and d_err_out in device memory of device_id, read and written where
+ *   they lie and only by kernels ("Device pointers of the caller" above: 4-byte aligned, d_codes 1 byte; a d_out on a 16-byte
+ *   boundary with dim a multiple of 4 is written with 16-byte stores); every out float and err entry is written and no other
+ *   byte.  codebooks, rotation and coarse are host memory. */
+#define QADC_DECODE_CHUNK 262144   /* rows decoded per pass; bounds the device scratch of a call */
+int qadc_pq_decode_host(int sq_count, int sq_bits, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
+                        const int32_t* assign, const void* codes, uint64_t n, const float* vectors, float* out, float* err_out, int device_id);
+int qadc_pq_decode_device(int sq_count, int sq_bits, int dim, const float* codebooks, const float* rotation, int K, const float* coarse,
+                          const int32_t* d_assign, const void* d_codes, uint64_t n, const float* d_vectors, float* d_out, float* d_err_out,
+                          int device_id);
+/* qadc_adc_index_reconstruct: the vectors behind keys.  The KEY of a row is what the scan emits for it: the label on a labelled
+ *   index, else key_base + position (an owned index: the position), so the keys of qadc_adc_search* can be fed back unchanged.
+ *   keys [count] -> out [count][dim], where_out [count] (nullable): ((uint64)partition << 32) | row of the row taken.  On an owned
+ *   8-bit or 16-bit index and on a view of a 4-bit index (which reads the source's partitions in place).  The quantizers are those
+ *   the index holds at the call, on a view the source's, as for qadc_adc_search*; with K > 0 a row's coarse centroid is its
+ *   partition's.  A key held by several rows (labels may repeat; unlabelled partitions share positions) takes the row with the
+ *   smallest (partition, row); repeats in keys each get their row; a key no row holds is a missing row, its where_out
+ *   QADC_RECONSTRUCT_MISSING.  Filters set on the index are ignored — a lookup, not a search — and nothing in the index changes.
+ *   How: a bitmap over [min key, max key] (at most 512 MiB, as for qadc_adc_index_remove_labels), one pass over the index's keys in
+ *   which a marked row finds its key among the sorted distinct requested keys and lowers that key's slot with a 64-bit atomicMin
+ *   (the minimum makes the result independent of scheduling), then the found rows' codes are gathered into a pass of
+ *   QADC_DECODE_CHUNK rows and decoded by qadc_pq_decode_device's kernels.  The distinct keys are ordered on the host.
+ *   Refused with QADC_E_ARG before the device is touched: a null index; no set_pq (a view: on its source); a coarse K that is
+ *   neither 0 nor the partition count; a dim above the decoder's limit; NULL keys or out with count > 0; count >= 2^32; more than
+ *   65535 partitions.  count = 0 is legal.  Synchronous, on the index's own stream; selects and restores the device.
+ * qadc_adc_index_reconstruct_device: d_keys, d_out and d_where_out (4-byte aligned, all three) in device memory of the index's device, read
+ *   and written by kernels only; every out float and where entry is written, missing rows included, and no other byte.
+ * qadc_adc_index_reconstruct_rows / _device: rows [first, first + count) of partition `part`, no lookup -> out [count][dim].  A
+ *   range outside the partition or a partition that does not exist is QADC_E_ARG, as for qadc_adc_index_read_partition; on a view
+ *   too.
+ * Not done: removing or overwriting by reconstruction; sharded or multi-GPU indexes (a view of one cannot be created); an error
+ * total on the device; the shortcut for a single unlabelled partition (it takes the general pass). */
+#define QADC_RECONSTRUCT_MISSING (~0ull)
+int qadc_adc_index_reconstruct(qadc_adc_index* idx, const uint32_t* keys, uint64_t count, float* out, uint64_t* where_out);
+int qadc_adc_index_reconstruct_device(qadc_adc_index* idx, const uint32_t* d_keys, uint64_t count, float* d_out, uint64_t* d_where_out);
+int qadc_adc_index_reconstruct_rows(qadc_adc_index* idx, int part, uint32_t first, uint32_t count, float* out);
+int qadc_adc_index_reconstruct_rows_device(qadc_adc_index* idx, int part, uint32_t first, uint32_t count, float* d_out);
 
 /* ---- db_add on the 4-bit index: vectors in, index grown, on the GPU.  The quantizers are those the
  * index holds at the call (qadc_index_set_pq, _set_rotation, _set_coarse). ---- */

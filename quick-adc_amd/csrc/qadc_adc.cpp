@@ -40,6 +40,7 @@
 #include "../host/worker_pool.hpp"
 #include "qadc_adc_kernels.h"
 #include "qadc_append.h"
+#include "qadc_decode.h"
 #include "qadc_host.h"
 #include "qadc_remove.h"
 
@@ -74,6 +75,7 @@ struct qadc_adc_index {
     // in src->adc_views, and the partition table the nibble kernel takes — a snapshot of src->parts at creation.
     qadc_index* src = nullptr;
     DevBuf<qadc::adc::Part4> d_parts4;
+    std::vector<qadc::adc::Part4> parts4;           // the same table on the host (the reconstruction reads a view's partitions through it)
     hipStream_t stream = nullptr;
     int labeled = -1;                               // unknown until the first non-empty add
     std::vector<uint32_t> sizes;                    // rows each partition holds (a view: of the index it reads)
@@ -1056,9 +1058,184 @@ int create_filter(qadc_adc_filter** out, int mode, const uint32_t* keys, uint64_
     return QADC_OK;
 }
 
+// ---- Reconstruction: the index forms of the PQ decode.  A call first produces a contiguous pass of
+// (partition or -1, code row) in scratch and then runs the stateless form's kernels (decode_passes, csrc/qadc_decode.cpp). ----
+
+struct Reconstruct {
+    qadc::DecodeQuantizers q;
+    int sq_bits = 0, code_bytes = 0, dim = 0;
+    std::vector<qadc::DecodePart> parts;
+};
+
+// The quantizers and partitions as they stand at the call, and every refusal: before the device is touched.
+int reconstruct_open(const qadc_adc_index* idx, const char* call, Reconstruct* rc) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (idx->src) {
+        const FeederState& s = idx->src->feed;
+        rc->dim = s.dim;
+        rc->q = qadc::DecodeQuantizers{s.d_codebooks.p, s.has_rotation ? s.d_rotation.p : nullptr, s.K ? s.d_coarse.p : nullptr, s.K};
+    } else {
+        rc->dim = idx->dim;
+        rc->q = qadc::DecodeQuantizers{idx->d_codebooks.p, idx->rotated ? idx->d_rotation.p : nullptr, idx->K ? idx->d_coarse.p : nullptr, idx->K};
+    }
+    if (!rc->dim)
+        return fail(QADC_E_ARG, std::string(call) + (idx->src ? ": qadc_index_set_pq has not been called on the view's source index: it has no codebooks"
+                                                              : ": qadc_adc_index_set_pq has not been called: the index has no codebooks"));
+    const size_t parts = idx->sizes.size();
+    if (rc->q.K && (size_t)rc->q.K != parts)
+        return fail(QADC_E_ARG, std::string(call) + ": the coarse quantizer has " + std::to_string(rc->q.K) + " centroids and the index " +
+                                    std::to_string(parts) + " partitions");
+    rc->sq_bits = idx->centroids == 16 ? 4 : idx->centroids == 256 ? 8 : 16;
+    rc->code_bytes = idx->src ? idx->nsq / 2 : idx->code_size();
+    if (int e = qadc::host::decode_shape_check(idx->nsq, rc->sq_bits, rc->dim)) return e;
+    rc->parts.resize(parts);
+    for (size_t p = 0; p < parts; ++p) {
+        const uint32_t n = idx->sizes[p];
+        if (idx->src)
+            rc->parts[p] = qadc::DecodePart{idx->parts4[p].codes, idx->parts4[p].labels, idx->parts4[p].key_base, n};
+        else
+            rc->parts[p] = qadc::DecodePart{n ? idx->store.part_codes(p) : nullptr, n && idx->labeled == 1 ? idx->store.part_labels(p) : nullptr, 0, n};
+    }
+    return QADC_OK;
+}
+
+// d_where [count] -> out [count][dim] (d_side: device memory, written by kernels only) in passes of kDecodeChunk rows
+int reconstruct_decode(qadc_adc_index* idx, const Reconstruct& rc, const qadc::DecodePart* d_parts, const unsigned long long* d_where,
+                       uint64_t count, float* out, bool d_side, Scratch& mem) {
+    hipStream_t s = idx->stream;
+    const uint64_t chunk = std::min<uint64_t>(qadc::kDecodeChunk, count);
+    int32_t* d_assign = nullptr;
+    uint8_t* d_codes = nullptr;
+    float* d_out = nullptr;
+    HIPCHECK(mem.alloc(&d_assign, sizeof(int32_t) * chunk));
+    HIPCHECK(mem.alloc(&d_codes, chunk * (uint64_t)rc.code_bytes));
+    if (!d_side) HIPCHECK(mem.alloc(&d_out, sizeof(float) * chunk * (uint64_t)rc.dim));
+    for (uint64_t first = 0; first < count; first += chunk) {
+        const uint64_t rows = std::min(chunk, count - first);
+        float* dst = d_side ? out + first * (uint64_t)rc.dim : d_out;
+        HIPCHECK(qadc::launch_reconstruct_gather(d_parts, d_where + first, rows, rc.code_bytes, d_assign, d_codes, s));
+        if (int e = qadc::host::decode_passes(idx->nsq, rc.sq_bits, rc.dim, rc.q, d_assign, d_codes, rows, nullptr, dst, nullptr, s)) return e;
+        if (!d_side) HIPCHECK(hipMemcpyAsync(out + first * (uint64_t)rc.dim, d_out, sizeof(float) * rows * (uint64_t)rc.dim, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));                        // the pass buffers are reused
+    }
+    return QADC_OK;
+}
+
+int upload_parts(const Reconstruct& rc, hipStream_t s, Scratch& mem, qadc::DecodePart** d_parts) {
+    HIPCHECK(mem.alloc(d_parts, std::max<size_t>(rc.parts.size(), 1) * sizeof(qadc::DecodePart)));
+    if (!rc.parts.empty())
+        HIPCHECK(hipMemcpyAsync(*d_parts, rc.parts.data(), rc.parts.size() * sizeof(qadc::DecodePart), hipMemcpyHostToDevice, s));
+    return QADC_OK;
+}
+
+// keys [count] -> out [count][dim], where_out [count] (nullable).  d_side: keys, out and where_out are device memory of the index's
+// device, read and written by kernels only.
+int reconstruct_keys(qadc_adc_index* idx, const uint32_t* keys, uint64_t count, float* out, uint64_t* where_out, bool d_side, const char* call) {
+    Reconstruct rc;
+    if (int e = reconstruct_open(idx, call, &rc)) return e;
+    if (count && (!keys || !out)) return fail(QADC_E_ARG, std::string(call) + ": keys and out must not be null with count > 0");
+    if (count >= (1ull << 32)) return fail(QADC_E_ARG, std::string(call) + ": count must be below 2^32");
+    if (rc.parts.size() > 65535) return fail(QADC_E_ARG, std::string(call) + ": the lookup takes an index of at most 65535 partitions");
+    if (count == 0) return QADC_OK;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(idx->device));
+    hipStream_t s = idx->stream;
+    Scratch mem;
+    qadc::DecodePart* d_parts = nullptr;
+    if (int e = upload_parts(rc, s, mem, &d_parts)) return e;
+    // the sorted distinct keys: ordered on the host.  The device form's list is copied into scratch by a kernel first (the caller's
+    // memory is only ever touched by kernels) — the call's one download before the results
+    std::vector<uint32_t> sorted(count);
+    uint32_t* d_list = nullptr;
+    HIPCHECK(mem.alloc(&d_list, count * 4));
+    if (d_side) {
+        HIPCHECK(qadc::launch_decode_copy_u32(keys, count, d_list, s));
+        HIPCHECK(hipMemcpyAsync(sorted.data(), d_list, count * 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipStreamSynchronize(s));
+    } else {
+        std::copy(keys, keys + count, sorted.begin());
+        HIPCHECK(hipMemcpyAsync(d_list, keys, count * 4, hipMemcpyHostToDevice, s));
+    }
+    std::sort(sorted.begin(), sorted.end());
+    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+    const uint64_t distinct = sorted.size();
+    const RemoveSpan span = remove_span(sorted.front(), sorted.back());
+    uint32_t *d_bitmap = nullptr, *d_sorted = nullptr;
+    unsigned long long *d_slots = nullptr, *d_where = nullptr;
+    HIPCHECK(mem.alloc(&d_bitmap, span.words * 4));
+    HIPCHECK(hipMemsetAsync(d_bitmap, 0, span.words * 4, s));
+    HIPCHECK(launch_remove_mark(d_list, count, span.lo, d_bitmap, s));
+    HIPCHECK(mem.alloc(&d_sorted, distinct * 4));
+    HIPCHECK(hipMemcpyAsync(d_sorted, sorted.data(), distinct * 4, hipMemcpyHostToDevice, s));
+    HIPCHECK(mem.alloc(&d_slots, distinct * 8));
+    HIPCHECK(hipMemsetAsync(d_slots, 0xff, distinct * 8, s));
+    uint32_t longest = 0;
+    for (const qadc::DecodePart& p : rc.parts) longest = std::max(longest, p.size);
+    HIPCHECK(qadc::launch_reconstruct_find(d_parts, (int)rc.parts.size(), longest, d_bitmap, span.lo, span.last, d_sorted, distinct, d_slots, s));
+    HIPCHECK(mem.alloc(&d_where, count * 8));
+    HIPCHECK(qadc::launch_reconstruct_read(d_list, count, d_sorted, distinct, d_slots, d_where, s));
+    if (where_out) {
+        if (d_side)
+            HIPCHECK(qadc::launch_decode_copy_where(d_where, count, reinterpret_cast<uint32_t*>(where_out), s));
+        else
+            HIPCHECK(hipMemcpyAsync(where_out, d_where, count * 8, hipMemcpyDeviceToHost, s));
+    }
+    const int e = reconstruct_decode(idx, rc, d_parts, d_where, count, out, d_side, mem);
+    const std::string msg = qadc::host::g_err;
+    (void)hipStreamSynchronize(s);                                // `sorted` and the scratch outlive the stream's work
+    qadc::host::g_err = msg;
+    return e;
+}
+
+// rows [first, first + count) of partition `part`: no lookup
+int reconstruct_rows(qadc_adc_index* idx, int part, uint32_t first, uint32_t count, float* out, bool d_side, const char* call) {
+    Reconstruct rc;
+    if (int e = reconstruct_open(idx, call, &rc)) return e;
+    if (part < 0 || part >= (int)rc.parts.size()) return fail(QADC_E_ARG, std::string(call) + ": partition " + std::to_string(part) + " does not exist");
+    if ((uint64_t)first + count > rc.parts[(size_t)part].size)
+        return fail(QADC_E_ARG, std::string(call) + ": rows [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                    ") lie outside partition " + std::to_string(part) + " of " + std::to_string(rc.parts[(size_t)part].size) + " rows");
+    if (count && !out) return fail(QADC_E_ARG, std::string(call) + ": out must not be null with count > 0");
+    if (count == 0) return QADC_OK;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(idx->device));
+    hipStream_t s = idx->stream;
+    Scratch mem;
+    qadc::DecodePart* d_parts = nullptr;
+    unsigned long long* d_where = nullptr;
+    if (int e = upload_parts(rc, s, mem, &d_parts)) return e;
+    HIPCHECK(mem.alloc(&d_where, (uint64_t)count * 8));
+    HIPCHECK(qadc::launch_reconstruct_iota((uint32_t)part, first, count, d_where, s));
+    const int e = reconstruct_decode(idx, rc, d_parts, d_where, count, out, d_side, mem);
+    const std::string msg = qadc::host::g_err;
+    (void)hipStreamSynchronize(s);
+    qadc::host::g_err = msg;
+    return e;
+}
+
 }  // namespace
 
 extern "C" {
+
+int qadc_adc_index_reconstruct(qadc_adc_index* idx, const uint32_t* keys, uint64_t count, float* out, uint64_t* where_out) {
+    return reconstruct_keys(idx, keys, count, out, where_out, false, "qadc_adc_index_reconstruct");
+}
+
+int qadc_adc_index_reconstruct_device(qadc_adc_index* idx, const uint32_t* d_keys, uint64_t count, float* d_out, uint64_t* d_where_out) {
+    if (int rc = check_aligned(d_keys, 4, "d_keys")) return rc;
+    if (int rc = check_aligned(d_out, 4, "d_out")) return rc;
+    if (int rc = check_aligned(d_where_out, 4, "d_where_out")) return rc;
+    return reconstruct_keys(idx, d_keys, count, d_out, d_where_out, true, "qadc_adc_index_reconstruct_device");
+}
+
+int qadc_adc_index_reconstruct_rows(qadc_adc_index* idx, int part, uint32_t first, uint32_t count, float* out) {
+    return reconstruct_rows(idx, part, first, count, out, false, "qadc_adc_index_reconstruct_rows");
+}
+
+int qadc_adc_index_reconstruct_rows_device(qadc_adc_index* idx, int part, uint32_t first, uint32_t count, float* d_out) {
+    if (int rc = check_aligned(d_out, 4, "d_out")) return rc;
+    return reconstruct_rows(idx, part, first, count, d_out, true, "qadc_adc_index_reconstruct_rows_device");
+}
 
 int qadc_adc_filter_create(qadc_adc_filter** out, int mode, const uint32_t* keys, uint64_t count, int device_id) {
     return create_filter(out, mode, keys, count, device_id, false);
@@ -1180,6 +1357,7 @@ int qadc_adc_index_create_view(qadc_adc_index** out, qadc_index* src) {
         (void)qadc_adc_index_destroy(idx);
         return fail(QADC_E_HIP, std::string("qadc_adc_index_create_view: ") + hipGetErrorString(e));
     }
+    idx->parts4 = table;
     idx->src = src;     // (only now: a failed creation above releases no count)
     ++src->adc_views;
     *out = idx;

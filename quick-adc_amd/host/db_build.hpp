@@ -33,6 +33,8 @@
 //                                          chunk's offset, as there.
 //   db_add_hip(qadc_adc_index*, dim, base_file, chunk_count)  the same into a float-ADC index: encode and append on the GPU
 //   db_add_hip(qadc_index*, dim, base_file, chunk_count)      ... and into the 4-bit index (qadc_index_add_vectors)
+//   pq_decode_hip(...)                     PQ codes back to vectors on the GPU (qadc_pq_decode_host; CPU twin: host/pq_decode.hpp pq_decode)
+//   reconstruct_hip(qadc_adc_index*, ...)  the vectors behind keys of a float-ADC index or a view (qadc_adc_index_reconstruct)
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -46,6 +48,7 @@
 #include <cmath>
 
 #include "kmeans_seed.hpp"
+#include "pq_decode.hpp"
 #include "pq_repair.hpp"
 #include "procrustes.hpp"
 #include "qadc_io.hpp"
@@ -514,6 +517,29 @@ inline std::vector<float> learn_coarse_quantizer_hip(const float* vecs, size_t n
     if (K <= 0) throw std::runtime_error("learn_coarse_quantizer_hip: K > 0");
     const std::vector<float> start = seed_kmeanspp_hip(vecs, n, dim, 1, (size_t)K, seed, 0, nullptr, nullptr, device);
     return learn_coarse_quantizer_hip(vecs, n, dim, K, start.data(), device);
+}
+
+// PQ codes back to vectors on the GPU: out [n][dim]; err (nullable) [n] against vectors.  The CPU twin is pq_decode (host/pq_decode.hpp).
+inline std::vector<float> pq_decode_hip(int sq_count, int sq_bits, int dim, const float* codebooks, const float* rotation, int K,
+                                        const float* coarse, const std::int32_t* assign, const void* codes, size_t n,
+                                        const float* vectors = nullptr, std::vector<float>* err = nullptr, int device = 0) {
+    std::vector<float> out(n * (size_t)dim);
+    if (err) err->assign(n, 0.0f);
+    if (qadc_pq_decode_host(sq_count, sq_bits, dim, codebooks, rotation, K, coarse, assign, codes, n, vectors, out.data(),
+                            err ? err->data() : nullptr, device) != QADC_OK)
+        throw std::runtime_error(std::string("qadc_pq_decode_host: ") + qadc_last_error());
+    return out;
+}
+
+// The vectors behind `keys` of a float-ADC index (or a view of a 4-bit index) under the quantizers it holds: [count][dim];
+// where (nullable): (partition << 32 | row) of each key's row, QADC_RECONSTRUCT_MISSING where no row holds it.
+inline std::vector<float> reconstruct_hip(qadc_adc_index* idx, int dim, const std::uint32_t* keys, size_t count,
+                                          std::vector<std::uint64_t>* where = nullptr) {
+    std::vector<float> out(count * (size_t)dim);
+    if (where) where->assign(count, 0);
+    if (qadc_adc_index_reconstruct(idx, keys, count, out.data(), where ? where->data() : nullptr) != QADC_OK)
+        throw std::runtime_error(std::string("qadc_adc_index_reconstruct: ") + qadc_last_error());
+    return out;
 }
 
 }  // namespace qadc

@@ -63,6 +63,8 @@ SYMBOLS = [
     "qadc_refine_create_keyed", "qadc_refine_put", "qadc_refine_put_device", "qadc_refine_remove", "qadc_refine_remove_device",
     "qadc_refine_keyed_info", "qadc_refine_keyed_slot",
     "qadc_refine_knn", "qadc_refine_knn_device", "qadc_refine_set_knn_plan",
+    "qadc_pq_decode_host", "qadc_pq_decode_device", "qadc_adc_index_reconstruct", "qadc_adc_index_reconstruct_device",
+    "qadc_adc_index_reconstruct_rows", "qadc_adc_index_reconstruct_rows_device",
     "qadc_adc_range_scan", "qadc_adc_range_scan_device", "qadc_adc_range_search", "qadc_adc_range_search_device",
     "qadc_adc_range_collect", "qadc_adc_range_collect_device",
 ]
@@ -324,6 +326,14 @@ def lib():
         L.qadc_refine_knn.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_void_p, u32p, f32p, i32p]
         L.qadc_refine_knn_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qadc_refine_set_knn_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+        L.qadc_pq_decode_host.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, i32p, C.c_void_p, C.c_uint64, f32p, f32p, f32p,
+                                          C.c_int]
+        L.qadc_pq_decode_device.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int]
+        L.qadc_adc_index_reconstruct.argtypes = [C.c_void_p, u32p, C.c_uint64, f32p, u64p]
+        L.qadc_adc_index_reconstruct_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.qadc_adc_index_reconstruct_rows.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, f32p]
+        L.qadc_adc_index_reconstruct_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
 
@@ -717,6 +727,103 @@ def pq_repair(vectors, codebooks, codes, device=0):
     moved = np.zeros(nsq, np.uint32)
     _check(lib().qadc_pq_repair_host(_p(v, f32p), n, dim, nsq, bits, _p(cb, f32p), c.ctypes.data_as(C.c_void_p), _p(moved, u32p), device))
     return (c.astype(np.uint16, copy=False) if bits == 16 else c), moved
+
+
+QADC_DECODE_CHUNK = 262144         # include/qadc.h: rows decoded per pass
+QADC_RECONSTRUCT_MISSING = 0xFFFFFFFFFFFFFFFF   # include/qadc.h: where[i] of a key no row holds
+DECODE_NAN_BITS = 0x7FC00000       # every float of a missing row
+
+
+def _pq_decode_args(codebooks, coarse, rotation):
+    cb = np.ascontiguousarray(codebooks, np.float32)
+    if cb.ndim != 3:
+        raise QadcError("codebooks has shape %s, expected [sq_count][2^bits][dim / sq_count]" % (tuple(cb.shape),))
+    bits = {16: 4, 256: 8, 65536: 16}.get(cb.shape[1])
+    if bits is None:
+        raise QadcError("cannot infer bits from %d centroids per sub-quantizer (16, 256 or 65536)" % cb.shape[1])
+    dim = cb.shape[0] * cb.shape[2]
+    co = None if coarse is None else np.ascontiguousarray(coarse, np.float32)
+    rot = None if rotation is None else np.ascontiguousarray(rotation, np.float32)
+    if rot is not None and rot.shape != (dim, dim):
+        raise QadcError("rotation has shape %s, expected [%d][%d]" % (tuple(rot.shape), dim, dim))
+    if co is not None and (co.ndim != 2 or co.shape[1] != dim):
+        raise QadcError("coarse has shape %s, expected [K][%d]" % (tuple(co.shape), dim))
+    return cb, bits, dim, co, rot
+
+
+def pq_decode(codebooks, codes, assign=None, coarse=None, rotation=None, vectors=None, device=0):
+    """PQ codes back to vectors on the GPU (qadc_pq_decode_host; include/qadc.h "Reconstruction"): the inverse of ivf_encode,
+    adc_encode and adc_encode16.  codebooks [sq_count][2^bits][dim / sq_count] (bits 4, 8 or 16 from the second axis), codes in the
+    encoder's layout (uint8 [n][sq_count / 2] packed nibbles, uint8 [n][sq_count], or uint16 [n][sq_count]), assign int32 [n] with
+    coarse [K][dim] (a row whose entry lies outside [0, K) comes back as a missing row, every float 0x7FC00000), rotation [dim][dim].
+    -> vectors float32 [n][dim]; with vectors= (the originals) -> (vectors, err float32 [n]), err[i] the squared distance between
+    vectors[i] and its reconstruction as one fmaf chain."""
+    cb, bits, dim, co, rot = _pq_decode_args(codebooks, coarse, rotation)
+    nsq = cb.shape[0]
+    c = np.ascontiguousarray(codes, "<u2" if bits == 16 else np.uint8)
+    cols = nsq // 2 if bits == 4 else nsq
+    if c.ndim != 2 or c.shape[1] != cols:
+        raise QadcError("codes has shape %s, expected the encoder's layout [n][%d]" % (tuple(c.shape), cols))
+    n = c.shape[0]
+    a = None if assign is None else np.ascontiguousarray(assign, np.int32).reshape(-1)
+    if a is not None and a.shape[0] != n:
+        raise QadcError("assign has %d entries for %d codes" % (a.shape[0], n))
+    v = None if vectors is None else np.ascontiguousarray(vectors, np.float32)
+    if v is not None and v.shape != (n, dim):
+        raise QadcError("vectors has shape %s, expected [%d][%d]" % (tuple(v.shape), n, dim))
+    out = np.zeros((n, dim), np.float32)
+    err = None if v is None else np.zeros(n, np.float32)
+    _check(lib().qadc_pq_decode_host(nsq, bits, dim, _p(cb, f32p), _p(rot, f32p), 0 if co is None else co.shape[0], _p(co, f32p), _p(a, i32p),
+                                     c.ctypes.data_as(C.c_void_p), n, _p(v, f32p), _p(out, f32p), _p(err, f32p), device))
+    return out if v is None else (out, err)
+
+
+def pq_decode_device(codebooks, codes, assign=None, coarse=None, rotation=None, vectors=None, out=None):
+    """pq_decode from and to device memory (qadc_pq_decode_device): codes a contiguous uint8 torch tensor [n][code bytes] on a GPU
+    (16-bit codes as their little-endian bytes, [n][2 * sq_count], or an int16 tensor [n][sq_count] carrying the uint16 bits), assign
+    an int32 tensor [n], vectors a float32 tensor [n][dim], all on that GPU and read where they lie.  -> a float32 tensor [n][dim]
+    (out=: written into it), with vectors= -> (that, err float32 tensor [n]).  The quantizers are host arrays."""
+    import torch
+    cb, bits, dim, co, rot = _pq_decode_args(codebooks, coarse, rotation)
+    nsq = cb.shape[0]
+    if not isinstance(codes, torch.Tensor) or codes.device.type != "cuda" or codes.ndim != 2 or not codes.is_contiguous():
+        raise QadcError("codes must be a contiguous 2-d torch.Tensor in device memory")
+    width = codes.shape[1] * codes.element_size()
+    if codes.dtype not in (torch.uint8, torch.int16) or width != (nsq // 2 if bits == 4 else nsq if bits == 8 else 2 * nsq):
+        raise QadcError("codes is %s %s, expected rows of %d code bytes" % (codes.dtype, tuple(codes.shape), nsq // 2 if bits == 4 else nsq * bits // 8))
+    dev, n = codes.device, int(codes.shape[0])
+
+    def there(t, dtype, shape, what):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise QadcError("%s must be a contiguous %s tensor %s on %s" % (what, dtype, shape, dev))
+        return t
+
+    a = there(assign, torch.int32, (n,), "assign")
+    v = there(vectors, torch.float32, (n, dim), "vectors")
+    res = there(out, torch.float32, (n, dim), "out")
+    if res is None:
+        res = torch.zeros((n, dim), dtype=torch.float32, device=dev)
+    err = None if v is None else torch.zeros((n,), dtype=torch.float32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()                         # the inputs and the zero fills are complete before the call
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    if n:                                                                # (an empty tensor has no address to pass)
+        _check(lib().qadc_pq_decode_device(nsq, bits, dim, _p(cb, f32p), _p(rot, f32p), 0 if co is None else co.shape[0], _p(co, f32p), ptr(a),
+                                           ptr(codes), n, ptr(v), ptr(res), ptr(err), dev.index or 0))
+    return res if v is None else (res, err)
+
+
+def quant_error(vectors, assign, codes, codebooks, coarse=None, rotation=None, device=0):
+    """The distortion of a quantizer on vectors it encoded (the k-means objective the trainers minimise): vectors [n][dim], their
+    coarse assignment (None without a coarse quantizer) and codes as the encoders and trainers return them
+    -> (err float32 [n], total float64): err[i] = |vectors[i] - its reconstruction|^2 as pq_decode defines it, total the sum of
+    err in float64 in ascending i (no total is formed on the device)."""
+    _, err = pq_decode(codebooks, codes, assign=assign, coarse=coarse, rotation=rotation, vectors=vectors, device=device)
+    total = 0.0
+    for e in err.astype(np.float64):
+        total += float(e)
+    return err, np.float64(total)
 
 
 QADC_OPQ_BLOCK = 2048              # include/qadc.h: vectors per float partial sum of the OPQ cross matrix
@@ -1411,6 +1518,16 @@ class Index(_RowStoreMixin):
         c = np.ascontiguousarray(centroids, np.float32)
         _check(lib().qadc_index_set_coarse(self._h, c.shape[0], _p(c, f32p)))
 
+    def reconstruct(self, keys):
+        """The approximate vectors behind keys of this 4-bit index -> (vectors float32 [n][dim], where uint64 [n]), as
+        AdcIndex.reconstruct: a float-ADC view of the index is made, asked, and destroyed.  Needs a finalized index (a view does)
+        with set_pq called."""
+        view = AdcIndex.view_of(self)
+        try:
+            return view.reconstruct(keys)
+        finally:
+            view.close()
+
     def search(self, queries, ma, R):
         q = np.ascontiguousarray(queries, np.float32)
         nq = q.shape[0]
@@ -1947,6 +2064,71 @@ class AdcIndex(_RowStoreMixin):
         _check(self._scan_call("qadc_adc_query_scan_device", fl, self._h, nq, ma, _p(assign, i32p), t.data_ptr(), R, sum_mode, keys.data_ptr(),
                                vals.data_ptr(), sizes.data_ptr()))
         return keys, vals, sizes
+
+    # ---- reconstruction: stored codes back to vectors (qadc_adc_index_reconstruct*) ----
+    def reconstruct(self, keys):
+        """keys (anything np.asarray(..., np.uint32) accepts; what search returns) -> (vectors float32 [n][dim], where uint64 [n]):
+        the approximate vector behind each key under the quantizers the index holds now, and (partition << 32 | row) of the row
+        taken — the smallest (partition, row) where several rows hold the key.  A key no row holds: a row of NaN (0x7FC00000) and
+        where = QADC_RECONSTRUCT_MISSING.  Filters set on the index are ignored."""
+        k = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(-1))
+        dim = getattr(self, "dim", 0) or 0
+        out = np.zeros((k.size, dim), np.float32)
+        where = np.zeros(k.size, np.uint64)
+        _check(lib().qadc_adc_index_reconstruct(self._h, _p(k, u32p), k.size, _p(out, f32p), _p(where, u64p)))
+        return out, where
+
+    def reconstruct_device(self, keys, out=None):
+        """reconstruct for a contiguous int32 torch tensor on the index's device that carries the keys' uint32 bits — any shape, so
+        search_device's keys go in unchanged -> (vectors float32 tensor keys.shape + (dim,), where int64 tensor keys.shape carrying
+        the uint64 bits: -1 for a missing key) on that device.  out=: a float32 tensor of that shape to write into."""
+        import torch
+        t = _label_tensor(keys.reshape(-1) if isinstance(keys, torch.Tensor) and keys.is_contiguous() else keys, self.device)
+        n, dim = int(t.shape[0]), getattr(self, "dim", 0) or 0
+        dev = torch.device("cuda", self.device)
+        shape = tuple(keys.shape)
+        if out is None:
+            out = torch.zeros(shape + (dim,), dtype=torch.float32, device=dev)
+        else:
+            self._device_tensor(out, shape + (dim,), "out")
+        where = torch.zeros(shape, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()                     # the inputs and the zero fills are complete before the call
+        _check(lib().qadc_adc_index_reconstruct_device(self._h, t.data_ptr(), n, out.data_ptr(), where.data_ptr()))
+        return out, where
+
+    def reconstruct_rows(self, part, first=0, count=None):
+        """rows [first, first + count) of partition `part` (default: all of it) -> vectors float32 [count][dim]; no lookup"""
+        if count is None:
+            count = max(self.partition_size(part) - first, 0) if 0 <= part < self.partition_count() else 0
+        out = np.zeros((count, getattr(self, "dim", 0) or 0), np.float32)
+        _check(lib().qadc_adc_index_reconstruct_rows(self._h, part, first, count, _p(out, f32p)))
+        return out
+
+    def reconstruct_rows_device(self, part, first, count, out=None):
+        """reconstruct_rows into a float32 torch tensor [count][dim] on the index's device"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        dim = getattr(self, "dim", 0) or 0
+        if out is None:
+            out = torch.zeros((count, dim), dtype=torch.float32, device=dev)
+        else:
+            self._device_tensor(out, (count, dim), "out")
+        torch.cuda.current_stream(dev).synchronize()
+        _check(lib().qadc_adc_index_reconstruct_rows_device(self._h, part, first, count, out.data_ptr()))
+        return out
+
+    def search_reconstruct(self, queries, ma, R, table_form=2, sum_mode=1, filters=None):
+        """search_device, then reconstruct_device on its keys: queries a float32 tensor [nq][dim] on the index's device ->
+        (keys, vals, sizes as search_device returns them, vectors float32 tensor [nq][R][dim], where int64 tensor [nq][R]).  The
+        slots behind sizes[q] hold no candidate: they are missing rows (NaN, where -1) whatever their key slot holds."""
+        import torch
+        keys, vals, sizes = self.search_device(queries, ma, R, table_form, sum_mode, filters=filters)
+        vectors, where = self.reconstruct_device(keys)
+        empty = torch.arange(int(R), device=keys.device).unsqueeze(0) >= sizes.unsqueeze(1)
+        nan = torch.tensor([DECODE_NAN_BITS], dtype=torch.int32, device=keys.device).view(torch.float32)
+        vectors[empty] = nan
+        where[empty] = -1
+        return keys, vals, sizes, vectors, where
 
     # ---- range search: every row below a radius, sorted on the GPU (qadc_adc_range_*; DESIGN.md section 11.13) ----
     @staticmethod

@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn,decode] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,opq,seed,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,seed,filter] [--iters N] [--out FILE]
 
@@ -76,6 +76,9 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
   keyed     caller-chosen labels (not in the default legs), on the ivf_search / refine shape: rerank_device on a
             keyed store against the dense store holding the same vectors, alternated, at the refine leg's r_in values; put_device and
             remove_device rows/s at 10^6 keys, fresh and overwriting; add_vectors_device(labels=...) against the plain call.
+  decode    PQ decode and reconstruction (not in the default legs; also under --bits 4 at 16x4 and --bits 16 at 2x16; DESIGN.md section
+            11.19), dim 128, with and without a rotation: pq_decode_device on 10^6 codes, and reconstruct_device on the keys of a
+            1024 x 100 search, each alternated with the route it replaces (read_partition, numpy gather and matmul, upload)
   knn       exhaustive search over a refine store (not in the default legs): Refine.knn_device and Refine.knn
             on 10^6 rows of dim 128, float and half store, nq = 1, 32 and 1024, R = 100, from call to return, as pairs/s and as a share
             of the estimated roof of 2 x 10^11 pairs/s (3 dim component operations a pair at 32 packed non-FMA float operations per
@@ -1544,6 +1547,127 @@ def knn_leg(iters, res, torch):
         del held, norms
 
 
+VALU_FMA_PER_S = 157.3e12 / 2   # the FP32 vector peak (spec), in fused multiply-adds
+
+
+def decode_leg(bits, iters, res, torch):
+    """PQ decode and reconstruction at 16x4, 8x8 or 2x16, dim 128, with and without a rotation:
+    (a) pq_decode_device on 10^6 x 128 with K = 256 coarse centroids, codes and assignment in device memory;
+    (b) reconstruct_device on the keys of a 1024 x 100 search_device over 10^6 encoded vectors (K = 256, ma = 8).
+    Each against the route it replaces, alternated in the same process: the codes fetched to the host (read_partition), a numpy gather
+    (+ a matmul under a rotation, + the coarse centroid), and the upload of the result.  Whole synchronous calls under a host clock."""
+    if torch is None:
+        raise SystemExit("the decode leg hands torch tensors over: torch with a GPU is required")
+    nsq = {4: 16, 8: 8, 16: 2}[bits]
+    dim, n, K, nq, ma = 128, 1_000_000, 256, 1024, 8
+    ds, cent = dim // nsq, 1 << bits
+    code_bytes = nsq // 2 if bits == 4 else nsq * bits // 8
+    rng = np.random.default_rng(7)
+    coarse = (rng.normal(size=(K, dim)) * 4).astype(np.float32)
+    cb = rng.normal(size=(nsq, cent, ds)).astype(np.float32)
+    rot = np.ascontiguousarray(np.linalg.qr(rng.normal(size=(dim, dim)))[0], np.float32)
+    vec = (coarse[rng.integers(0, K, n)] + rng.normal(size=(n, dim))).astype(np.float32)
+    labels = rng.permutation(n).astype(np.uint32)
+
+    def unpacked(codes):
+        c = np.asarray(codes)
+        if bits == 4:
+            out = np.empty((c.shape[0], nsq), np.int64)
+            out[:, 0::2], out[:, 1::2] = c & 15, c >> 4
+            return out
+        return c.astype(np.int64)
+
+    def host_decode(codes, assign, rotation):
+        a = unpacked(codes)
+        y = np.concatenate([cb[m][a[:, m]] for m in range(nsq)], axis=1)
+        if rotation is not None:
+            y = y @ rotation                                               # z[c] = sum_r y[r] rotation[r][c]
+        return y + coarse[assign]
+
+    for rotated in (False, True):
+        tag = "decode%d_%s" % (bits, "opq" if rotated else "pq")
+        rotation = rot if rotated else None
+        if bits == 4:
+            base = pyqadc.Index(nsq)
+        else:
+            base = pyqadc.AdcIndex(nsq, 8) if bits == 8 else pyqadc.AdcIndex.create16(nsq)
+        base.set_pq(cb)
+        if rotated:
+            base.set_rotation(rot)
+        base.set_coarse(coarse)
+        base.add_vectors(vec, labels=labels)
+        if bits == 4:
+            base.finalize(0.01)
+        idx = pyqadc.AdcIndex.view_of(base) if bits == 4 else base
+        parts = [base.read_partition(p) for p in range(K)]
+        codes = np.concatenate([c for c, _ in parts])
+        assign = np.concatenate([np.full(len(c), p, np.int32) for p, (c, _) in enumerate(parts)])
+        # (a) stateless
+        d_codes = torch.from_numpy(np.ascontiguousarray(codes).view(np.uint8).reshape(n, code_bytes)).cuda()
+        d_assign = torch.from_numpy(assign).cuda()
+        d_out = torch.zeros((n, dim), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        gpu = lambda: pyqadc.pq_decode_device(cb, d_codes, assign=d_assign, coarse=coarse, rotation=rotation, out=d_out)
+
+        def route():
+            c = d_codes.cpu().numpy()                                      # what read_partition costs: the codes to the host
+            c = c.view("<u2").reshape(n, nsq) if bits == 16 else c
+            t = torch.from_numpy(host_decode(c, assign, rotation).astype(np.float32)).cuda()
+            torch.cuda.synchronize()
+            return t
+        got, want = gpu().cpu().numpy(), route().cpu().numpy()
+        err = float(np.abs(got - want).max())
+        assert err < 1e-3 * (1 + float(np.abs(want).max())), "the two routes disagree: %g" % err
+        med_r, med_g = alternated(route, gpu, max(3, iters // 2), warmup=1)
+        res[tag + "_stateless_ms"] = med_g * 1e3
+        res[tag + "_stateless_route_ms"] = med_r * 1e3
+        res[tag + "_stateless_rows_per_s"] = n / med_g
+        res[tag + "_stateless_out_bytes_per_s"] = n * dim * 4 / med_g
+        line = "decode %dx%d%s, 10^6 x 128: pq_decode_device %.3f ms = %.3g rows/s = %.3g B/s written; host route %.1f ms (x%.0f)" % (
+            nsq, bits, " + rotation" if rotated else "", med_g * 1e3, n / med_g, n * dim * 4 / med_g, med_r * 1e3, med_r / med_g)
+        if rotated:
+            res[tag + "_stateless_fma_per_s"] = n * dim * dim / med_g
+            res[tag + "_stateless_valu_peak_share"] = n * dim * dim / med_g / VALU_FMA_PER_S
+            line += "; %.3g fmaf/s = %.3f of the FP32 vector peak" % (n * dim * dim / med_g, n * dim * dim / med_g / VALU_FMA_PER_S)
+        else:
+            share = (n * dim * 4 + n * code_bytes) / med_g / HBM_BPS
+            res[tag + "_stateless_hbm_peak_share"] = share
+            line += "; out + code bytes = %.3f of the HBM peak" % share
+        print(line, flush=True)
+        # (b) the keys of a search
+        q = torch.from_numpy((coarse[rng.integers(0, K, nq)] + rng.normal(size=(nq, dim))).astype(np.float32)).cuda()
+        keys, _, _ = idx.search_device(q, ma, R)
+        rec = lambda: idx.reconstruct_device(keys)
+
+        def lookup_route():
+            got = [base.read_partition(p) for p in range(K)]
+            all_codes = np.concatenate([c for c, _ in got])
+            all_labels = np.concatenate([l for _, l in got])
+            owner = np.concatenate([np.full(len(c), p, np.int32) for p, (c, _) in enumerate(got)])
+            order = np.argsort(all_labels, kind="stable")
+            k = keys.cpu().numpy().view(np.uint32).reshape(-1)
+            rows = order[np.minimum(np.searchsorted(all_labels[order], k), len(order) - 1)]
+            t = torch.from_numpy(host_decode(all_codes[rows], owner[rows], rotation).astype(np.float32)).cuda()
+            torch.cuda.synchronize()
+            return t
+        got, where = rec()
+        found = (where.reshape(-1) != -1).cpu().numpy()
+        want = lookup_route().cpu().numpy()
+        err = float(np.abs(got.reshape(-1, dim).cpu().numpy()[found] - want[found]).max())
+        assert err < 1e-3 * (1 + float(np.abs(want).max())), "the two lookup routes disagree: %g" % err
+        med_r, med_g = alternated(lookup_route, rec, max(3, iters // 2), warmup=1)
+        res[tag + "_reconstruct_ms"] = med_g * 1e3
+        res[tag + "_reconstruct_route_ms"] = med_r * 1e3
+        res[tag + "_reconstruct_rows_per_s"] = nq * R / med_g
+        print("decode %dx%d%s, the %d keys of a 1024 x 100 search over 10^6 rows: reconstruct_device %.3f ms = %.3g rows/s = %.3g B/s written; "
+              "read_partition + numpy route %.1f ms (x%.0f)" % (nsq, bits, " + rotation" if rotated else "", nq * R, med_g * 1e3, nq * R / med_g,
+                                                               nq * R * dim * 4 / med_g, med_r * 1e3, med_r / med_g), flush=True)
+        if bits == 4:
+            idx.close()
+        base.close()
+        del d_codes, d_assign, d_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default=None)
@@ -1561,7 +1685,11 @@ def main():
     legs = a.legs.split(",")
     if a.bits != 8:
         res = {"R": R, "sum_mode": 1, "bits": a.bits, "cpus_allowed": len(os.sched_getaffinity(0))}
-        (view_legs if a.bits == 4 else word_legs)(legs, a.iters, res)
+        if "decode" in legs:                                               # (torch's HIP runtime has to come up before the library's)
+            import torch
+            torch.zeros(1, device="cuda")
+            decode_leg(a.bits, a.iters, res, torch)
+        (view_legs if a.bits == 4 else word_legs)([l for l in legs if l != "decode"], a.iters, res)
         line = json.dumps(res)
         print(line)
         if a.out:
@@ -1570,7 +1698,7 @@ def main():
                 f.write(line + "\n")
         return
     torch = None
-    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs or "decode" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:
             import torch
             torch.zeros(1, device="cuda")
@@ -1675,6 +1803,8 @@ def main():
         seed_leg(8, a.iters, res)
     if "knn" in legs:
         knn_leg(a.iters, res, torch)
+    if "decode" in legs:
+        decode_leg(8, a.iters, res, torch)
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -917,6 +917,12 @@ __device__ __forceinline__ uint64_t bktw_streamed(uint32_t mask, uint32_t& used,
 // paid).  FREE = 5: wide octaves (20-bit key, 11 planes of sub-quantizers 5-15, NSP = 3..6 paid; the group's sub-quantizer 4 is
 // one more byte of its id: s0 = P01[id & 255] + P23[id >> 8] + T4[id4], or, NSP odd, row 4 joins the first paid plane's pair table
 // with id4 splatted into the low nibbles of the merged index).  sel = the form's choice bytes of every table.
+// Depth of the id ring of the PRUNE tile loop (below): the ids of a workgroup's tiles are requested this many tiles ahead.  1, 2 and 3
+// were measured (profiles/r15_bktw_loop.txt); 3 takes the QUARTER kernels past 64 VGPRs.  With 2 those kernels stand at 62 - 63 of the
+// 64 VGPRs that 8 waves per SIMD allow (58 - 59 before the ring): one more live value in scan_bkt_body costs scratch or occupancy, so
+// read -Rpass-analysis=kernel-resource-usage after any change to it.  tests/test_gpu_bktw_prefetch.py reads the depth from the next
+// line as it is written; keep its form.
+constexpr uint32_t kBktwRing = 2;
 template <int FREE, int NSP, bool NT, bool CHUNK, bool PROBE, bool PRUNE, bool QUARTER = false>
 __device__ __forceinline__ void scan_bkt_body(
     const ScanItem* __restrict__ items, const int8_t* __restrict__ qtables, QueryState* __restrict__ qstates,
@@ -1057,14 +1063,16 @@ __device__ __forceinline__ void scan_bkt_body(
             }
         }
     };
-    // the lane group's id of tile t (and, WIDE, its sub-quantizer 4)
+    // the lane group's id of tile t (and, WIDE, its sub-quantizer 4).  id4 is the RAW byte: its users mask it (free_rows, the FUSE
+    // splat).  A mask here sits between the load and the back edge of the PRUNE loop, which carries the value, and with it a wait for
+    // the NEXT tile's id4 at the top of every iteration, before this tile's decision and plane loads.
     auto load_ids = [&](uint32_t t, uint32_t& id, uint32_t& id4) __attribute__((always_inline)) {
         const gid_t idp = ids + (uint64_t)t * (kTile / 2);
         id = NT ? __builtin_nontemporal_load(idp) : *idp;
         id4 = 0;
         if constexpr (WIDE) {
             const gbyte_t p4 = id4s + (uint64_t)t * kTile;
-            id4 = (NT ? __builtin_nontemporal_load(p4) : *p4) & 15u;
+            id4 = NT ? __builtin_nontemporal_load(p4) : *p4;
         }
     };
     // the rows the pair loop starts from: P01[id & 255] in slot 0, P23[id >> 8] in slot 1 and, WIDE with an even NSP, the fifth free
@@ -1074,11 +1082,11 @@ __device__ __forceinline__ void scan_bkt_body(
                       *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id >> 8) & 0xffu) << 8 | lane_lo) + 1u));
         if constexpr (WIDE && !FUSE) {
             constexpr int sl = NP + 2;
-            s0 += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>(((id4 << 8) | lane_lo) + (sl >> 2) * 128 + (sl & 3)));
+            s0 += *reinterpret_cast<lds_bytes_t>(static_cast<uintptr_t>((((id4 & 15u) << 8) | lane_lo) + (sl >> 2) * 128 + (sl & 3)));
         }
         return s0;
     };
-    // PRUNE: pid / pid4 = the tile's ids, loaded one iteration early, so that the decision comes before the plane loads
+    // PRUNE: pid / pid4 = the tile's ids, loaded kBktwRing iterations early, so that the decision comes before the plane loads
     auto step_tile = [&](uint32_t t, [[maybe_unused]] uint32_t pid, [[maybe_unused]] uint32_t pid4) __attribute__((always_inline)) {
         u32x2 v[NSP];
         const uint32_t e0 = t * (kTile / 8) + tid;              // vector index of plane 0 (t < 2^18: no wrap)
@@ -1129,12 +1137,12 @@ __device__ __forceinline__ void scan_bkt_body(
             for (int i = 1; i < NSP; ++i) a ^= v[i];
 #pragma unroll
             for (int c = 0; c < 16; ++c) cv[c] = 127u;
-            cv[0] = ((a.x ^ a.y ^ id ^ (id4 << 16)) == 0x12345678u) ? 0u : 127u;
+            cv[0] = ((a.x ^ a.y ^ id ^ ((id4 & 15u) << 16)) == 0x12345678u) ? 0u : 127u;
             best = cv[0];
         } else {
             constexpr uint32_t LO = 0x0f0f0f0fu;
             const uint32_t s0 = PRUNE ? s0p : free_rows(id, id4);   // the group's free rows
-            [[maybe_unused]] const uint32_t id4s8 = id4 * 0x11111111u;           // FUSE: id4 in every nibble, the pair loop's plane 0
+            [[maybe_unused]] const uint32_t id4s8 = (id4 & 15u) * 0x11111111u;   // FUSE: id4 in every nibble, the pair loop's plane 0
 #pragma unroll
             for (int w = 0; w < 2; ++w) {
                 uint32_t idx[2][NP > 0 ? NP : 1];               // [slots 0-3 | 4-7 of the dword's eight][pair]: four byte indices each
@@ -1187,12 +1195,34 @@ __device__ __forceinline__ void scan_bkt_body(
         }
     };
     if constexpr (PRUNE) {
-        uint32_t nid = 0, nid4 = 0;
-        if (first < last) load_ids(first, nid, nid4);
-        for (uint32_t t = first; t < last; t += step) {
-            const uint32_t id = nid, id4 = nid4;
-            if (t + step < last) load_ids(t + step, nid, nid4);   // (t + step < 2^19: no wrap)
-            step_tile(t, id, id4);
+        // The ids run kBktwRing tiles ahead of the tile loop, in a ring of registers: slot k holds the ids of the workgroup's tiles
+        // k, k + D, k + 2 D, ...  The loop is unrolled D times, so that a slot is a fixed register and an iteration uses ids requested D
+        // iterations ago.  That is the intent; what the compiler makes of it is less: it sizes the first body's wait as if one pair
+        // were in flight, not D - 1, and zero-extends the narrow ids behind a full wait at the latch, so every D-th tile still ends
+        // on the loads it has just issued (profiles/r15_bktw_loop.txt, with the rewrites that cured this and ran slower).  Every slot
+        // is always loaded (no branch around a load): past the workgroup's last tile the ring re-reads that tile's ids (tlast), never
+        // an id beyond the run; a workgroup without a tile loads nothing.
+        if (first < last) {
+            constexpr uint32_t D = kBktwRing;
+            const uint32_t tlast = first + (last - 1u - first) / step * step;
+            uint32_t rid[D], rid4[D];
+#pragma unroll
+            for (uint32_t k = 0; k < D; ++k) load_ids(min(first + k * step, tlast), rid[k], rid4[k]);   // (t + D step < 2^20: no wrap)
+            uint32_t t = first;
+            bool more = true;
+            while (more) {
+#pragma unroll
+                for (uint32_t k = 0; k < D; ++k) {
+                    const uint32_t id = rid[k], id4 = rid4[k];
+                    load_ids(min(t + D * step, tlast), rid[k], rid4[k]);
+                    step_tile(t, id, id4);
+                    t += step;
+                    if (t >= last) {
+                        more = false;
+                        break;
+                    }
+                }
+            }
         }
     } else {
         for (uint32_t t = first; t < last; t += step) step_tile(t, 0u, 0u);

@@ -1503,6 +1503,46 @@ int qadc_refine_knn_device(qadc_refine* r, int nq, const float* d_queries, int R
  * negative pass_nq. */
 int qadc_refine_set_knn_plan(qadc_refine* r, uint64_t chunk_rows, int pass_nq);
 
+/* ---- SQ8 rows: one byte per component under a per-dimension range; read-back ----
+ * A third element type: a store of dim bytes per row (no padding) with the parameters vmin[dim] and step[dim], both finite,
+ * step >= 0.  The store derives inv[i] = 1.0f / step[i] where step[i] > 0 (+inf for a subnormal step), else 0, on the host, once.
+ * All arithmetic is binary32, every operation rounded by itself, no fused multiply-add; the twin is sq_encode, sq_decode and
+ * sq_range of quick-adc_amd/host/refine.hpp, and the GPU equals it bit for bit (stored bytes and the clamp counter included).
+ *   encode   component x of dimension i: d = x - vmin[i]; u = d * inv[i]; byte 0 where !(u > 0) (NaN, below the range, a constant
+ *            dimension), else 255 where u >= 255, else u rounded to the nearest integer, ties to even.
+ *   decode   vmin[i] + (float)byte * step[i]: the product rounded, then the sum.  D(q, x) and the selection are those above with the
+ *            row's i-th component decoded so; nothing else of rerank or knn changes.
+ *   clamped  a component written to a row counts where step[i] > 0 and (!(d >= 0) or !(u <= 255)), or where step[i] == 0 and x
+ *            differs in value from vmin[i] (a NaN does; -0 does not differ from +0).  Only what reaches a row counts: of equal keys
+ *            within one put, the winner.  A sum, so no order shows in it.
+ *   range    per dimension the minimum and maximum over the finite components of a learning set, in the order of the
+ *            sign-magnitude image (-0 below +0); none: 0 and 0.  vmin = the minimum, step = (max - min) / 255.0f, divided on the
+ *            host.  A function of the set alone.  step is +inf where max - min overflows: no store takes such a range.
+ * Every call above works on such a store unchanged; qadc_refine_info reports dtype 2 and bytes = capacity x dim.
+ * Limits: the range is fixed at creation (no re-encoding); uniform steps only; L2 only; one device. */
+#define QADC_REFINE_SQ8 2
+/* An empty SQ8 store on device_id, dense (keyed = 0) or keyed.  qadc_refine_create and _create_keyed refuse dtype 2: the type needs
+ * its parameters.  QADC_E_ARG before the device is touched: out, vmin or step NULL, a bad dim, a vmin[i] or step[i] that is not
+ * finite, a negative step[i]. */
+int qadc_refine_create_sq8(qadc_refine** out, int dim, const float* vmin, const float* step, int keyed, int device_id);
+/* The range of vectors [n][dim] (host memory) -> vmin_out [dim], step_out [dim] (host memory), minimum and maximum found on
+ * device_id.  n = 0 is legal and gives zeros.  QADC_E_ARG: a bad dim, an output NULL, vectors NULL with n > 0. */
+int qadc_refine_sq_range_host(const float* vectors, uint64_t n, int dim, int device_id, float* vmin_out, float* step_out);
+/* The same with d_vectors in device memory of device_id, complete before the call, read by a kernel only; the outputs stay host
+ * memory. */
+int qadc_refine_sq_range_device(const float* d_vectors, uint64_t n, int dim, int device_id, float* vmin_out, float* step_out);
+/* Any output may be NULL: the store's vmin [dim] and step [dim] and the clamped components counted so far.  QADC_E_STATE on an F32
+ * or F16 store. */
+int qadc_refine_sq_info(const qadc_refine* r, float* vmin_out, float* step_out, uint64_t* clamped_out);
+/* Read-back, on stores of every kind and element type: out_vectors [count][dim] (host memory) = the rows of keys [count] as floats,
+ * decoded by the store's type (an F32 row as it is, an F16 row as the float value of the stored half); a key the store does not
+ * hold gives a row of 0x7FC00000 and found_out[i] = 0, else found_out[i] = 1.  found_out may be NULL; count = 0 is a no-op.
+ * QADC_E_ARG: r NULL, keys or out_vectors NULL with count > 0. */
+int qadc_refine_get(qadc_refine* r, const uint32_t* keys, uint64_t count, float* out_vectors, uint8_t* found_out);
+/* The same with every array in device memory of the store's device (see qadc_refine_add_device), d_keys complete before the call;
+ * d_keys and d_out_vectors are checked for 4-byte alignment first. */
+int qadc_refine_get_device(qadc_refine* r, const uint32_t* d_keys, uint64_t count, float* d_out_vectors, uint8_t* d_found_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../host/refine.hpp"
 #include "qadc_host.h"
@@ -31,13 +32,23 @@ static_assert(QADC_REFINE_KNN_MAX_R == qadc::refine::kKnnMaxR, "one limit on the
 static_assert(QADC_ADC_FILTER_EXCLUDE == qadc::adc::kFilterExclude && QADC_ADC_FILTER_ALLOW == qadc::adc::kFilterAllow &&
                   QADC_ADC_FILTER_EXCLUDE == qadc::refine::kFilterExclude && QADC_ADC_FILTER_ALLOW == qadc::refine::kFilterAllow,
               "the filter modes of the scan, of knn and of its twin");
-static_assert(QADC_REFINE_F32 == qadc::refine::kF32 && QADC_REFINE_F16 == qadc::refine::kF16, "the twin's element types");
+static_assert(QADC_REFINE_F32 == qadc::refine::kF32 && QADC_REFINE_F16 == qadc::refine::kF16 && QADC_REFINE_SQ8 == qadc::refine::kSQ8,
+              "the twin's element types");
+static_assert(QADC_REFINE_F32 == (int)qadc::refine::Elem::kF32 && QADC_REFINE_F16 == (int)qadc::refine::Elem::kF16 &&
+                  QADC_REFINE_SQ8 == (int)qadc::refine::Elem::kSQ8,
+              "the kernels' element types");
 
 struct qadc_refine {
     int dim = 0, dtype = QADC_REFINE_F32, device = 0;
     uint32_t lo = 0;                                // key of row 0 (fixed by the first add)
     uint64_t rows = 0, cap = 0;                     // rows held / rows the allocation holds
-    void* data = nullptr;                           // [cap][dim] floats or halves
+    void* data = nullptr;                           // [cap][dim] floats, halves or bytes
+    // an SQ8 store (qadc_refine_create_sq8): vmin, step, inv [dim] each in one allocation, the clamp counter
+    float* d_sq = nullptr;
+    unsigned long long* d_clamped = nullptr;
+    std::vector<float> sq_vmin, sq_step;            // what qadc_refine_sq_info reports
+    DevBuf<float> d_get_out;                        // qadc_refine_get: a pass of rows on their way to host memory
+    DevBuf<uint8_t> d_get_found;
     uint64_t relocations = 0;                       // adds that moved the rows to grow the allocation
     hipStream_t stream = nullptr;
     // a keyed store (qadc_refine_create_keyed): `rows` are the rows allocated so far, each live or on the free list
@@ -59,8 +70,12 @@ struct qadc_refine {
     int knn_pass_nq = 0;
     DevBuf<uint64_t> d_knn_buf, d_knn_bound;        // [pass_nq][groups][buf_cap] / [pass_nq][groups]
     DevBuf<uint32_t> d_knn_cnt;                     // [pass_nq][groups]
-    size_t elem() const { return dtype == QADC_REFINE_F16 ? 2 : 4; }
+    qadc::refine::Elem elem_type() const { return (qadc::refine::Elem)dtype; }
+    size_t elem() const { return qadc::refine::elem_bytes(elem_type()); }
     size_t row_bytes() const { return (size_t)dim * elem(); }
+    qadc::refine::SqParams sq() const {
+        return d_sq ? qadc::refine::SqParams{d_sq, d_sq + dim, d_sq + 2 * (size_t)dim, d_clamped} : qadc::refine::SqParams{nullptr, nullptr, nullptr, nullptr};
+    }
 };
 
 namespace {
@@ -217,7 +232,6 @@ int put_rows(qadc_refine* r, const float* vectors, const uint32_t* labels, uint6
     if (plan.refused) return fail(QADC_E_ARG, "a keyed store holds at most 2^30 keys");
     if (plan.rebuild)
         if (int rc = rebuild_table(r, plan.bits)) return rc;
-    const bool f16 = r->dtype == QADC_REFINE_F16;
     for (uint64_t o = 0; o < count; o += pass) {
         const uint32_t cnt = (uint32_t)std::min(pass, count - o);
         const uint32_t* d_lab = labels + o;
@@ -244,7 +258,7 @@ int put_rows(qadc_refine* r, const float* vectors, const uint32_t* labels, uint6
         }
         HIPCHECK(launch_keyed_assign(d_lab, cnt, r->table, r->d_slot_of.p, r->d_dst.p, r->row_key, r->free_list, (uint32_t)r->free_rows,
                                      (uint32_t)r->rows, r->d_cnt.p, r->stream));
-        HIPCHECK(launch_keyed_store(d_vec, r->d_dst.p, cnt, r->dim, r->data, f16, r->stream));
+        HIPCHECK(launch_keyed_store(d_vec, r->d_dst.p, cnt, r->dim, r->data, r->elem_type(), r->sq(), r->stream));
         HIPCHECK(hipStreamSynchronize(r->stream));
         r->live += need;
         r->free_rows -= need - fresh;
@@ -283,11 +297,35 @@ int remove_rows(qadc_refine* r, const uint32_t* labels, uint64_t count, uint64_t
     return QADC_OK;
 }
 
-int create_store(qadc_refine** out, int dim, int dtype, int device_id, bool keyed) {
+// the parameters of an SQ8 store into device memory: inv derived here, once, by the host's division
+int upload_sq(qadc_refine* r, const float* vmin, const float* step) {
+    const size_t dim = (size_t)r->dim;
+    std::vector<float> h(3 * dim);
+    std::copy(vmin, vmin + dim, h.begin());
+    std::copy(step, step + dim, h.begin() + dim);
+    sq_derive_inv(step, r->dim, h.data() + 2 * dim);   // (IEEE division whatever the calling thread's floating-point mode)
+    r->sq_vmin.assign(vmin, vmin + dim);
+    r->sq_step.assign(step, step + dim);
+    HIPCHECK(hipMalloc((void**)&r->d_sq, 3 * dim * sizeof(float)));
+    HIPCHECK(hipMalloc((void**)&r->d_clamped, sizeof(unsigned long long)));
+    HIPCHECK(hipMemcpyAsync(r->d_sq, h.data(), 3 * dim * sizeof(float), hipMemcpyHostToDevice, r->stream));
+    HIPCHECK(hipMemsetAsync(r->d_clamped, 0, sizeof(unsigned long long), r->stream));
+    HIPCHECK(hipStreamSynchronize(r->stream));   // (h leaves with this call)
+    return QADC_OK;
+}
+
+// vmin and step: null but for an SQ8 store (qadc_refine_create_sq8), whose parameters they are
+int create_store(qadc_refine** out, int dim, int dtype, int device_id, bool keyed, const float* vmin = nullptr, const float* step = nullptr) {
     if (!out) return fail(QADC_E_ARG, "out is null");
     *out = nullptr;
     if (dim < 1 || dim > QADC_REFINE_MAX_DIM) return fail(QADC_E_ARG, "dim is 1 .. " + std::to_string(QADC_REFINE_MAX_DIM));
-    if (dtype != QADC_REFINE_F32 && dtype != QADC_REFINE_F16) return fail(QADC_E_ARG, "dtype is 0 (QADC_REFINE_F32) or 1 (QADC_REFINE_F16)");
+    if (dtype == QADC_REFINE_SQ8) {
+        if (!vmin || !step)
+            return fail(QADC_E_ARG, "dtype 2 (QADC_REFINE_SQ8) needs the range of its rows: qadc_refine_create_sq8");
+        if (!sq_params_ok(vmin, step, dim)) return fail(QADC_E_ARG, "vmin and step must be finite and step not negative");
+    } else if (dtype != QADC_REFINE_F32 && dtype != QADC_REFINE_F16) {
+        return fail(QADC_E_ARG, "dtype is 0 (QADC_REFINE_F32) or 1 (QADC_REFINE_F16)");
+    }
     DeviceGuard guard;
     if (int rc = qadc_device_prepare(device_id)) return rc;   // (the device's stream set first: DESIGN.md section 5)
     HIPCHECK(hipSetDevice(device_id));
@@ -301,12 +339,14 @@ int create_store(qadc_refine** out, int dim, int dtype, int device_id, bool keye
         delete r;
         return fail(QADC_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
     }
-    if (keyed)   // the smallest table from the start: every rerank finds one to probe
-        if (int rc = rebuild_table(r, kKeyedMinBits)) {
-            const std::string msg = qadc_last_error();
-            qadc_refine_destroy(r);
-            return fail(rc, msg);
-        }
+    int rc = QADC_OK;
+    if (keyed) rc = rebuild_table(r, kKeyedMinBits);   // the smallest table from the start: every rerank finds one to probe
+    if (rc == QADC_OK && dtype == QADC_REFINE_SQ8) rc = upload_sq(r, vmin, step);
+    if (rc != QADC_OK) {
+        const std::string msg = qadc_last_error();
+        qadc_refine_destroy(r);
+        return fail(rc, msg);
+    }
     *out = r;
     return QADC_OK;
 }
@@ -323,18 +363,19 @@ int add_rows(qadc_refine* r, const float* vectors, uint64_t count, uint32_t firs
     HIPCHECK(hipSetDevice(r->device));
     if (int rc = ensure_rows(r, r->rows + count, false)) return rc;
     char* dst = static_cast<char*>(r->data) + (size_t)r->rows * r->row_bytes();
-    const bool f16 = r->dtype == QADC_REFINE_F16;
+    const Elem elem = r->elem_type();
     const uint64_t n = count * (uint64_t)r->dim;
     if (d_side) {
-        HIPCHECK(launch_refine_convert(vectors, dst, f16, n, r->stream));
-    } else if (!f16) {
+        HIPCHECK(launch_refine_convert(vectors, dst, elem, r->sq(), r->dim, n, r->stream));
+    } else if (elem == Elem::kF32) {
         HIPCHECK(hipMemcpyAsync(dst, vectors, (size_t)n * 4, hipMemcpyHostToDevice, r->stream));
     } else {
-        HIPCHECK(r->d_stage.ensure((size_t)std::min(n, kStageFloats)));
-        for (uint64_t i = 0; i < n; i += kStageFloats) {
-            const uint64_t m = std::min(kStageFloats, n - i);
+        const uint64_t stage = kStageFloats / (uint64_t)r->dim * (uint64_t)r->dim;   // whole rows: a pass starts at a row's component 0
+        HIPCHECK(r->d_stage.ensure((size_t)std::min(n, stage)));
+        for (uint64_t i = 0; i < n; i += stage) {
+            const uint64_t m = std::min(stage, n - i);
             HIPCHECK(hipMemcpyAsync(r->d_stage.p, vectors + i, (size_t)m * 4, hipMemcpyHostToDevice, r->stream));
-            HIPCHECK(launch_refine_convert(r->d_stage.p, dst + (size_t)i * 2, true, m, r->stream));
+            HIPCHECK(launch_refine_convert(r->d_stage.p, dst + (size_t)i * r->elem(), elem, r->sq(), r->dim, m, r->stream));
             HIPCHECK(hipStreamSynchronize(r->stream));   // (the stage is written again by the next pass)
         }
     }
@@ -366,7 +407,8 @@ int rerank_passes(qadc_refine* r, int nq, const float* queries, int r_in, const 
     for (int q0 = 0; q0 < nq; q0 += plan.pass_nq) {
         RefinePass p;
         p.rows = r->data;
-        p.f16 = r->dtype == QADC_REFINE_F16;
+        p.elem = r->elem_type();
+        p.sq = r->sq();
         p.lo = r->lo;
         p.nrows = r->rows;
         p.tkey = r->keyed ? r->table.key : nullptr;
@@ -423,7 +465,8 @@ int knn_passes(qadc_refine* r, int nq, const float* queries, int R, const adc::S
     for (int q0 = 0; q0 < nq; q0 += plan.pass_nq) {
         KnnPass p;
         p.rows = r->data;
-        p.f16 = r->dtype == QADC_REFINE_F16;
+        p.elem = r->elem_type();
+        p.sq = r->sq();
         p.dim = r->dim;
         p.lo = r->lo;
         p.nrows = r->rows;
@@ -450,9 +493,144 @@ int knn_passes(qadc_refine* r, int nq, const float* queries, int R, const adc::S
     return QADC_OK;
 }
 
+// The passes of a read-back: keys in device memory; out and found in device memory (d_side) or in host memory, by way of a stage.
+int get_rows(qadc_refine* r, const uint32_t* d_keys, uint64_t count, float* out, uint8_t* found, bool d_side) {
+    RefinePass p{};
+    p.rows = r->data;
+    p.elem = r->elem_type();
+    p.sq = r->sq();
+    p.lo = r->lo;
+    p.nrows = r->rows;
+    p.tkey = r->keyed ? r->table.key : nullptr;
+    p.trow = r->table.row;
+    p.tbits = r->table.bits;
+    p.dim = r->dim;
+    if (d_side) {
+        HIPCHECK(launch_refine_get(p, d_keys, count, out, found, r->stream));
+        HIPCHECK(hipStreamSynchronize(r->stream));
+        return QADC_OK;
+    }
+    const uint64_t pass = std::max<uint64_t>(1, kStageFloats / (uint64_t)r->dim);
+    HIPCHECK(r->d_get_out.ensure((size_t)(std::min(pass, count) * r->dim)));
+    HIPCHECK(r->d_get_found.ensure((size_t)std::min(pass, count)));
+    for (uint64_t o = 0; o < count; o += pass) {
+        const uint64_t cnt = std::min(pass, count - o);
+        HIPCHECK(launch_refine_get(p, d_keys + o, cnt, r->d_get_out.p, r->d_get_found.p, r->stream));
+        HIPCHECK(hipMemcpyAsync(out + o * r->dim, r->d_get_out.p, (size_t)cnt * r->dim * 4, hipMemcpyDeviceToHost, r->stream));
+        if (found) HIPCHECK(hipMemcpyAsync(found + o, r->d_get_found.p, (size_t)cnt, hipMemcpyDeviceToHost, r->stream));
+        HIPCHECK(hipStreamSynchronize(r->stream));   // (the stage is written again by the next pass)
+    }
+    return QADC_OK;
+}
+
+// The range of `n` vectors, in device memory (d_side) or in host memory, which goes through a stage in passes of whole rows: the
+// extremes of every launch meet in the same two arrays.  On a stream of the call's own.
+int sq_range(const float* vectors, uint64_t n, int dim, bool d_side, float* vmin_out, float* step_out) {
+    std::vector<uint32_t> h(2 * (size_t)dim);
+    const uint64_t pass = std::max<uint64_t>(1, kStageFloats / (uint64_t)dim);
+    Scratch scratch;
+    uint32_t* d_ext = nullptr;
+    float* d_stage = nullptr;
+    HIPCHECK(scratch.alloc(&d_ext, 2 * (size_t)dim * 4));
+    if (!d_side && n) HIPCHECK(scratch.alloc(&d_stage, (size_t)(std::min(pass, n) * dim) * 4));
+    hipStream_t stream = nullptr;
+    HIPCHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    auto run = [&]() -> int {
+        HIPCHECK(hipMemsetAsync(d_ext, 0xFF, (size_t)dim * 4, stream));
+        HIPCHECK(hipMemsetAsync(d_ext + dim, 0, (size_t)dim * 4, stream));
+        if (d_side) {
+            HIPCHECK(launch_refine_sq_range(vectors, n, dim, d_ext, d_ext + dim, stream));
+        } else {
+            for (uint64_t o = 0; o < n; o += pass) {
+                const uint64_t cnt = std::min(pass, n - o);
+                HIPCHECK(hipMemcpyAsync(d_stage, vectors + o * dim, (size_t)cnt * dim * 4, hipMemcpyHostToDevice, stream));
+                HIPCHECK(launch_refine_sq_range(d_stage, cnt, dim, d_ext, d_ext + dim, stream));
+                HIPCHECK(hipStreamSynchronize(stream));   // (the stage is written again by the next pass)
+            }
+        }
+        HIPCHECK(hipMemcpyAsync(h.data(), d_ext, 2 * (size_t)dim * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipStreamSynchronize(stream));
+        return QADC_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(stream);
+    (void)hipStreamDestroy(stream);
+    if (rc != QADC_OK) return rc;
+    sq_range_finish(h.data(), h.data() + dim, dim, vmin_out, step_out);
+    return QADC_OK;
+}
+
+int check_sq_range(const float* vectors, uint64_t n, int dim, const float* vmin_out, const float* step_out) {
+    if (dim < 1 || dim > QADC_REFINE_MAX_DIM) return fail(QADC_E_ARG, "dim is 1 .. " + std::to_string(QADC_REFINE_MAX_DIM));
+    if (!vmin_out || !step_out) return fail(QADC_E_ARG, "vmin_out and step_out must not be null");
+    if (n && !vectors) return fail(QADC_E_ARG, "vectors is null");
+    return QADC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int qadc_refine_create_sq8(qadc_refine** out, int dim, const float* vmin, const float* step, int keyed, int device_id) {
+    if (out) *out = nullptr;
+    if (!vmin || !step) return fail(QADC_E_ARG, "vmin and step must not be null");
+    return create_store(out, dim, QADC_REFINE_SQ8, device_id, keyed != 0, vmin, step);
+}
+
+int qadc_refine_sq_range_device(const float* d_vectors, uint64_t n, int dim, int device_id, float* vmin_out, float* step_out) {
+    if (int rc = check_aligned(d_vectors, 4, "d_vectors")) return rc;
+    if (int rc = check_sq_range(d_vectors, n, dim, vmin_out, step_out)) return rc;
+    DeviceGuard guard;
+    if (int rc = qadc_device_prepare(device_id)) return rc;
+    HIPCHECK(hipSetDevice(device_id));
+    return sq_range(d_vectors, n, dim, true, vmin_out, step_out);
+}
+
+int qadc_refine_sq_range_host(const float* vectors, uint64_t n, int dim, int device_id, float* vmin_out, float* step_out) {
+    if (int rc = check_sq_range(vectors, n, dim, vmin_out, step_out)) return rc;
+    DeviceGuard guard;
+    if (int rc = qadc_device_prepare(device_id)) return rc;
+    HIPCHECK(hipSetDevice(device_id));
+    return sq_range(vectors, n, dim, false, vmin_out, step_out);
+}
+
+int qadc_refine_sq_info(const qadc_refine* r, float* vmin_out, float* step_out, uint64_t* clamped_out) {
+    if (!r) return fail(QADC_E_ARG, "store is null");
+    if (r->dtype != QADC_REFINE_SQ8) return fail(QADC_E_STATE, "qadc_refine_sq_info: the store's rows are not SQ8 (qadc_refine_create_sq8)");
+    if (vmin_out) std::copy(r->sq_vmin.begin(), r->sq_vmin.end(), vmin_out);
+    if (step_out) std::copy(r->sq_step.begin(), r->sq_step.end(), step_out);
+    if (clamped_out) {
+        DeviceGuard guard;
+        HIPCHECK(hipSetDevice(r->device));
+        unsigned long long c = 0;
+        HIPCHECK(hipMemcpyAsync(&c, r->d_clamped, sizeof(c), hipMemcpyDeviceToHost, r->stream));
+        HIPCHECK(hipStreamSynchronize(r->stream));
+        *clamped_out = c;
+    }
+    return QADC_OK;
+}
+
+int qadc_refine_get(qadc_refine* r, const uint32_t* keys, uint64_t count, float* out_vectors, uint8_t* found_out) {
+    if (!r) return fail(QADC_E_ARG, "store is null");
+    if (count == 0) return QADC_OK;
+    if (!keys || !out_vectors) return fail(QADC_E_ARG, "keys and out_vectors must not be null");
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    HIPCHECK(r->d_keys.ensure((size_t)count));
+    HIPCHECK(hipMemcpyAsync(r->d_keys.p, keys, (size_t)count * 4, hipMemcpyHostToDevice, r->stream));
+    return get_rows(r, r->d_keys.p, count, out_vectors, found_out, false);
+}
+
+int qadc_refine_get_device(qadc_refine* r, const uint32_t* d_keys, uint64_t count, float* d_out_vectors, uint8_t* d_found_out) {
+    if (int rc = check_aligned(d_keys, 4, "d_keys")) return rc;
+    if (int rc = check_aligned(d_out_vectors, 4, "d_out_vectors")) return rc;
+    if (!r) return fail(QADC_E_ARG, "store is null");
+    if (count == 0) return QADC_OK;
+    if (!d_keys || !d_out_vectors) return fail(QADC_E_ARG, "d_keys and d_out_vectors must not be null");
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    return get_rows(r, d_keys, count, d_out_vectors, d_found_out, true);
+}
 
 int qadc_refine_create(qadc_refine** out, int dim, int dtype, int device_id) { return create_store(out, dim, dtype, device_id, false); }
 
@@ -502,6 +680,9 @@ int qadc_refine_destroy(qadc_refine* r) {
     if (r->data) (void)hipFree(r->data);
     if (r->row_key) (void)hipFree(r->row_key);
     if (r->free_list) (void)hipFree(r->free_list);
+    if (r->d_sq) (void)hipFree(r->d_sq);
+    if (r->d_clamped) (void)hipFree(r->d_clamped);
+    r->d_get_out.release(); r->d_get_found.release();
     free_table(r->table);
     r->d_cnt.release(); r->d_labels.release(); r->d_slot_of.release(); r->d_dst.release();
     r->d_stage.release(); r->d_words.release(); r->d_missing.release(); r->d_queries.release(); r->d_values.release();

@@ -12,11 +12,25 @@
 namespace qadc {
 namespace refine {
 
+// The element type of a store's rows (= QADC_REFINE_F32 / _F16 / _SQ8, asserted in qadc_refine.cpp)
+enum class Elem : int { kF32 = 0, kF16 = 1, kSQ8 = 2 };
+inline size_t elem_bytes(Elem e) { return e == Elem::kF32 ? 4 : e == Elem::kF16 ? 2 : 1; }
+
+// The parameters of an SQ8 store in device memory: vmin, step and inv = 1 / step (0 where step is 0),
+// [dim] each, and the counter of clamped components.  All null for the other element types.
+struct SqParams {
+    const float* vmin;
+    const float* step;
+    const float* inv;
+    unsigned long long* clamped;
+};
+
 // One re-ranking pass over nq queries (a pass of the plan).  Every pointer is device memory and is touched by kernels only, so
-// memory of another HIP runtime is legal.  rows: the store, `f16` says which element type; counts and values may be null.
+// memory of another HIP runtime is legal.  rows: the store, `elem` says which element type; counts and values may be null.
 struct RefinePass {
     const void* rows;
-    bool f16;
+    Elem elem;
+    SqParams sq;
     uint32_t lo;
     uint64_t nrows;
     const uint32_t* tkey;          // a keyed store: its table's keys and rows [2^tbits] in place of [lo, lo + nrows); else null
@@ -38,8 +52,16 @@ struct RefinePass {
 hipError_t launch_refine_dist(const RefinePass& p, const RefinePlan& plan, hipStream_t stream);
 // refine_select_kernel<N>: sort, dedupe, the first R survivors and the tail of every query of the pass
 hipError_t launch_refine_select(const RefinePass& p, const RefinePlan& plan, hipStream_t stream);
-// refine_convert_kernel<Row>: dst[i] = Row(src[i]) for n floats (Row float: a copy; __half: round to nearest even)
-hipError_t launch_refine_convert(const float* src, void* dst, bool f16, uint64_t n, hipStream_t stream);
+// refine_convert_kernel<Row>: dst[i] = Row(src[i]) for n floats, whole rows of dim (Row float: a copy; __half: round to nearest
+// even; SQ8: sq_encode under component i % dim's parameters, clamped components added to sq.clamped)
+hipError_t launch_refine_convert(const float* src, void* dst, Elem elem, const SqParams& sq, int dim, uint64_t n, hipStream_t stream);
+// refine_get_kernel<Row, Lookup>: out[k] = the row of keys[k] as floats, or dim times 0x7FC00000 where the store does not hold it;
+// found[k] (may be null) = 1 / 0.  p: rows, elem, sq, lo, nrows, the table and dim are read, nothing else.
+hipError_t launch_refine_get(const RefinePass& p, const uint32_t* keys, uint64_t count, float* out, uint8_t* found, hipStream_t stream);
+// refine_sq_range_kernel: lo[i] = min, hi[i] = max over the finite components of column i of vectors [n][dim], as ordered images
+// (host/refine.hpp: sq_ordered); the caller has set lo to 0xFFFFFFFF and hi to 0
+hipError_t launch_refine_sq_range(const float* vectors, uint64_t n, int dim, uint32_t* lo, uint32_t* hi, hipStream_t stream);
+constexpr int kSqRangeRows = 64;                   // rows of a workgroup's tile of refine_sq_range_kernel
 
 // ---- the keyed store.  Every launch takes at most kKeyedPass inputs; labels are device memory read by
 // kernels only. ----
@@ -71,7 +93,8 @@ hipError_t launch_keyed_assign(const uint32_t* labels, uint32_t n, KeyedTable t,
 // win[slot_of[i]] = 0 for every input: what a put that fails between claim and assign leaves behind it
 hipError_t launch_keyed_reset(uint32_t n, KeyedTable t, const uint32_t* slot_of, hipStream_t stream);
 // rows[dst[i]] = the store's element type of src[i] for every input whose dst[i] is a row
-hipError_t launch_keyed_store(const float* src, const uint32_t* dst, uint32_t n, int dim, void* rows, bool f16, hipStream_t stream);
+hipError_t launch_keyed_store(const float* src, const uint32_t* dst, uint32_t n, int dim, void* rows, Elem elem, const SqParams& sq,
+                              hipStream_t stream);
 // Every listed key that is live: its slot's row becomes none (the slot dead), its row free (row_key, the free list from entry
 // free_rows on); cnt[Removed] += 1 each.  A key listed twice frees its row once.
 hipError_t launch_keyed_remove(const uint32_t* labels, uint32_t n, KeyedTable t, uint32_t* row_key, uint32_t* free_list, uint32_t free_rows,
@@ -82,8 +105,9 @@ hipError_t launch_keyed_rebuild(const uint32_t* row_key, uint32_t alloc_rows, Ke
 // ---- exhaustive search (qadc_refine_knn; kernels: csrc/qadc_refine_knn_kernel.hip; geometry:
 // host/refine_knn_plan.hpp).  One pass of the plan over nq queries; every pointer is device memory touched by kernels only. ----
 struct KnnPass {
-    const void* rows;              // the store's rows [nrows][dim], `f16` says which element type
-    bool f16;
+    const void* rows;              // the store's rows [nrows][dim], `elem` says which element type
+    Elem elem;
+    SqParams sq;
     int dim;
     uint32_t lo;                   // a dense store: the key of row r is lo + r
     uint64_t nrows;                // rows to walk (a keyed store: the rows allocated so far)

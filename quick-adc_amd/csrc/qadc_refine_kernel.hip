@@ -3,6 +3,11 @@
 //   refine_dist_kernel<Row>     one candidate per wave: the 64-bit word (image of the L2 distance << 32 | key) of every candidate
 //   refine_select_kernel<N, T>  one workgroup per query: bitonic sort of the words in LDS, equal words kept once, the first R out
 //   refine_convert_kernel<Row>  the append: float -> the store's element type
+//   refine_get_kernel<Row>      the read-back: one key per wave, its row decoded to floats
+//   refine_sq_range_kernel      the range of an SQ8 store: per-dimension min and max of the finite components of a learning set
+// SQ8 rows: a component is vmin[i] + (float)byte * step[i], the product and the sum rounded one by one;
+// the distance kernel stages vmin and step beside the query in LDS, loads a row as one dword per lane and hands the bytes to the
+// lanes that own the components 64 j + l with ds_bpermute, so that the definition's summation order holds.
 // The keyed store: refine_dist_kernel finds a candidate's row through a lookup policy, DenseLookup (the
 // range test) or KeyedLookup (a probe of the table); keyed_*_kernel are the put, the remove and the rebuild.
 #include "qadc_refine.h"
@@ -10,6 +15,7 @@
 #include <hip/hip_fp16.h>
 
 #include <cfloat>
+#include <type_traits>
 
 namespace qadc {
 namespace refine {
@@ -20,8 +26,39 @@ constexpr uint32_t kNanImage = 0x7FC00000u;
 constexpr uint32_t kInfImage = 0x7F800000u;
 constexpr uint64_t kNoWord = ~0ull;
 
-__device__ inline float row_value(const float* x, int i) { return x[i]; }
-__device__ inline float row_value(const __half* x, int i) { return __half2float(x[i]); }
+struct sq8_t {                                        // a component of an SQ8 row
+    uint8_t b;
+};
+
+// component i of a row; vmin and step are component i's parameters of an SQ8 store (unused by the other types)
+__device__ inline float row_value(const float* x, int i, float, float) { return x[i]; }
+__device__ inline float row_value(const __half* x, int i, float, float) { return __half2float(x[i]); }
+__device__ inline float row_value(const sq8_t* x, int i, float vmin, float step) {
+    const float m = (float)x[i].b * step;
+    return vmin + m;
+}
+
+// The wide-load form of an SQ8 row: lane l takes the four bytes of the components b .. b + 3 with one load (the row's end is never
+// passed: a dword that would reach over it is put together from the bytes that exist), and sq_lane_byte hands component
+// 64 s + lane of the 256 the wave holds to its lane: it lies in the dword of lane 16 s + lane / 4, at byte lane % 4.  Every lane
+// of the wave calls both, whatever its own component.
+__device__ inline uint32_t sq_load4(const sq8_t* x, int b, int dim) {
+    uint32_t w = 0;
+    if (b + 4 <= dim) {
+        __builtin_memcpy(&w, x + b, 4);               // (no alignment is promised: dim may be odd)
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (b + k < dim) w |= (uint32_t)x[b + k].b << (8 * k);
+    }
+    return w;
+}
+
+__device__ inline float sq_lane_value(uint32_t w, int s, int lane, float vmin, float step) {
+    const uint32_t v = (uint32_t)__builtin_amdgcn_ds_bpermute((16 * s + (lane >> 2)) << 2, (int)w);
+    const float m = (float)((v >> (8 * (lane & 3))) & 0xFFu) * step;
+    return vmin + m;
+}
 
 // Where a candidate's row lies.  The key is uniform over the wave, so both are uniform code with no per-lane state.
 struct DenseLookup {                                  // the keys [lo, lo + nrows), row = key - lo
@@ -56,16 +93,24 @@ struct KeyedLookup {                                  // linear probing from the
 // strides 32 .. 1 (lane l < s adds lane l + s; what the lanes at and above s compute is never read by a lane below).
 template <typename Row, typename Lookup>
 __global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Row* __restrict__ rows, Lookup look, int dim,
+                                                                        const float* __restrict__ sq_vmin, const float* __restrict__ sq_step,
                                                                         const float* __restrict__ queries, int r_in,
                                                                         const uint32_t* __restrict__ keys, const int32_t* __restrict__ counts,
                                                                         const float* __restrict__ values, int cands_per_wg, int chunks,
                                                                         uint64_t* __restrict__ words, unsigned long long* __restrict__ missing) {
-    extern __shared__ float s_query[];   // [dim]
+    extern __shared__ float s_query[];   // [dim]; SQ8 rows: then vmin [dim] and step [dim]
     __shared__ unsigned s_missing;
+    constexpr bool kSq = std::is_same<Row, sq8_t>::value;
     const int q = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const float* qv = queries + (size_t)q * dim;
-    for (int i = tid; i < dim; i += kRefineWaves * 64) s_query[i] = qv[i];
+    for (int i = tid; i < dim; i += kRefineWaves * 64) {
+        s_query[i] = qv[i];
+        if (kSq) {
+            s_query[dim + i] = sq_vmin[i];
+            s_query[2 * dim + i] = sq_step[i];
+        }
+    }
     if (tid == 0) s_missing = 0;
     __syncthreads();
 
@@ -92,15 +137,37 @@ __global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Ro
                     ++lost;
             }
         }
-        for (int j = lane; j < dim; j += 64) {
-            const float qj = s_query[j];
+        if constexpr (kSq) {
+            for (int b0 = 0; b0 < dim; b0 += 256) {   // 256 components of every row in flight: one dword per lane
+                uint32_t w[kRefineInFlight];
 #pragma unroll
-            for (int c = 0; c < kRefineInFlight; ++c)
-                if (x[c]) {
-                    const float t = qj - row_value(x[c], j);
-                    const float tt = t * t;
-                    p[c] = p[c] + tt;
+                for (int c = 0; c < kRefineInFlight; ++c) w[c] = x[c] ? sq_load4(x[c], b0 + 4 * lane, dim) : 0u;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    if (b0 + 64 * s >= dim) break;    // (uniform)
+                    const int j = b0 + 64 * s + lane;
+                    const bool mine = j < dim;
+                    const float qj = mine ? s_query[j] : 0.0f, vj = mine ? s_query[dim + j] : 0.0f, sj = mine ? s_query[2 * dim + j] : 0.0f;
+#pragma unroll
+                    for (int c = 0; c < kRefineInFlight; ++c)
+                        if (x[c]) {                   // (uniform: the exchange runs with every lane)
+                            const float t = qj - sq_lane_value(w[c], s, lane, vj, sj);
+                            const float tt = t * t;
+                            if (mine) p[c] = p[c] + tt;
+                        }
                 }
+            }
+        } else {
+            for (int j = lane; j < dim; j += 64) {
+                const float qj = s_query[j];
+#pragma unroll
+                for (int c = 0; c < kRefineInFlight; ++c)
+                    if (x[c]) {
+                        const float t = qj - row_value(x[c], j, 0.0f, 0.0f);
+                        const float tt = t * t;
+                        p[c] = p[c] + tt;
+                    }
+            }
         }
 #pragma unroll
         for (int c = 0; c < kRefineInFlight; ++c) {
@@ -185,9 +252,112 @@ __global__ __launch_bounds__(T) void refine_select_kernel(const uint64_t* __rest
 __device__ inline void store_as(float* dst, size_t i, float v) { dst[i] = v; }
 __device__ inline void store_as(__half* dst, size_t i, float v) { dst[i] = __float2half_rn(v); }
 
-template <typename Row>
-__global__ __launch_bounds__(256) void refine_convert_kernel(const float* __restrict__ src, Row* __restrict__ dst, uint64_t n) {
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) store_as(dst, i, src[i]);
+// How a float becomes an element of a row.  PlainEncode: store_as.  SqEncode: sq_encode of host/refine.hpp under the parameters of
+// component `comp`; a component outside the range counts as clamped.
+struct PlainEncode {
+    static constexpr bool kCounts = false;
+    template <typename Row>
+    __device__ inline unsigned put(Row* dst, size_t at, uint32_t, float v) const {
+        store_as(dst, at, v);
+        return 0u;
+    }
+    __device__ inline unsigned long long* counter() const { return nullptr; }
+};
+
+struct SqEncode {
+    static constexpr bool kCounts = true;
+    const float* __restrict__ vmin;
+    const float* __restrict__ step;
+    const float* __restrict__ inv;
+    unsigned long long* clamped;
+    __device__ inline unsigned put(sq8_t* dst, size_t at, uint32_t comp, float x) const {
+        const float lo = vmin[comp], st = step[comp];
+        const float d = x - lo;
+        const float u = d * inv[comp];
+        uint8_t c = 0;
+        if (u > 0.0f) c = u >= 255.0f ? (uint8_t)255 : (uint8_t)rintf(u);   // (rintf: to nearest, ties to even)
+        dst[at].b = c;
+        return (st > 0.0f ? (!(d >= 0.0f) || !(u <= 255.0f)) : !(x == lo)) ? 1u : 0u;
+    }
+    __device__ inline unsigned long long* counter() const { return clamped; }
+};
+
+// every thread of the workgroup arrives: the waves' sums of `mine`, then one add to the 64-bit counter
+__device__ inline void block_count(unsigned mine, unsigned long long* counter) {
+    __shared__ unsigned s_sum;
+    if (threadIdx.x == 0) s_sum = 0;
+    __syncthreads();
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) mine += __shfl_down(mine, s, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_sum, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_sum) atomicAdd(counter, (unsigned long long)s_sum);
+}
+
+// n floats, whole rows of dim: element i is component i % dim of its row
+template <typename Row, typename Enc>
+__global__ __launch_bounds__(256) void refine_convert_kernel(const float* __restrict__ src, Row* __restrict__ dst, uint64_t n, uint32_t dim, Enc enc) {
+    const uint64_t first = (uint64_t)blockIdx.x * 256 + threadIdx.x, stride = (uint64_t)gridDim.x * 256;
+    uint32_t comp = Enc::kCounts ? (uint32_t)(first % dim) : 0u;
+    const uint32_t hop = Enc::kCounts ? (uint32_t)(stride % dim) : 0u;
+    unsigned clamped = 0;
+    for (uint64_t i = first; i < n; i += stride) {
+        clamped += enc.put(dst, i, comp, src[i]);
+        comp += hop;
+        if (comp >= dim) comp -= dim;
+    }
+    if (Enc::kCounts) block_count(clamped, enc.counter());
+}
+
+// One key per wave: the row found as refine_dist_kernel finds it, decoded to floats with coalesced stores
+template <typename Row, typename Lookup>
+__global__ __launch_bounds__(256) void refine_get_kernel(const Row* __restrict__ rows, Lookup look, int dim, const float* __restrict__ sq_vmin,
+                                                         const float* __restrict__ sq_step, const uint32_t* __restrict__ keys, uint64_t count,
+                                                         float* __restrict__ out, uint8_t* __restrict__ found) {
+    constexpr bool kSq = std::is_same<Row, sq8_t>::value;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (uint64_t k = (uint64_t)blockIdx.x * 4 + wave; k < count; k += (uint64_t)gridDim.x * 4) {
+        const uint32_t key = __builtin_amdgcn_readfirstlane(keys[k]);
+        uint64_t row = 0;
+        const bool held = look.row_of(key, &row);
+        const Row* x = rows + row * (uint64_t)dim;
+        float* o = out + k * (uint64_t)dim;
+        for (int j = lane; j < dim; j += 64)
+            o[j] = held ? row_value(x, j, kSq ? sq_vmin[j] : 0.0f, kSq ? sq_step[j] : 0.0f) : __uint_as_float(kNanImage);
+        if (found && lane == 0) found[k] = held ? 1 : 0;
+    }
+}
+
+// A workgroup walks tiles of kSqRangeRows rows with coalesced loads and keeps the columns' extremes in LDS, as ordered images
+// (-0 below +0; a non-finite component takes no part); the workgroups' extremes meet in lo and hi by integer atomics.
+__global__ __launch_bounds__(256) void refine_sq_range_kernel(const float* __restrict__ vectors, uint64_t n, uint32_t dim, uint32_t* __restrict__ lo,
+                                                              uint32_t* __restrict__ hi) {
+    extern __shared__ uint32_t s_ext[];   // lo [dim], hi [dim]
+    uint32_t *s_lo = s_ext, *s_hi = s_ext + dim;
+    for (uint32_t c = threadIdx.x; c < dim; c += 256) {
+        s_lo[c] = 0xFFFFFFFFu;
+        s_hi[c] = 0u;
+    }
+    __syncthreads();
+    const uint64_t tiles = (n + kSqRangeRows - 1) / kSqRangeRows;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint64_t r0 = tile * kSqRangeRows, r1 = min(n, r0 + (uint64_t)kSqRangeRows);
+        const float* v = vectors + r0 * dim;
+        const uint32_t cnt = (uint32_t)(r1 - r0) * dim;
+        for (uint32_t e = threadIdx.x; e < cnt; e += 256) {
+            const uint32_t u = __float_as_uint(v[e]);
+            if ((u & 0x7F800000u) == 0x7F800000u) continue;
+            const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u), c = e % dim;
+            if (o < s_lo[c]) atomicMin(s_lo + c, o);   // (the extremes only move outwards: a stale read costs one atomic at most)
+            if (o > s_hi[c]) atomicMax(s_hi + c, o);
+        }
+    }
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < dim; c += 256)
+        if (s_lo[c] <= s_hi[c]) {
+            atomicMin(lo + c, s_lo[c]);
+            atomicMax(hi + c, s_hi[c]);
+        }
 }
 
 // ---- the keyed store: put (precheck, claim, count, assign, store), remove, rebuild.  One input, row or slot per thread, strided
@@ -282,15 +452,18 @@ __global__ __launch_bounds__(kKeyedThreads) void keyed_reset_kernel(uint32_t n, 
     if (i < n) win[slot_of[i]] = 0u;
 }
 
-// refine_convert_kernel's work with a destination row per input: consecutive threads take consecutive components
-template <typename Row>
+// refine_convert_kernel's work with a destination row per input: consecutive threads take consecutive components.  An input that
+// lost its key to a later one writes nothing and counts nothing.
+template <typename Row, typename Enc>
 __global__ __launch_bounds__(kKeyedThreads) void keyed_store_kernel(const float* __restrict__ src, const uint32_t* __restrict__ dst, uint64_t total,
-                                                                    uint32_t dim, Row* __restrict__ rows) {
+                                                                    uint32_t dim, Row* __restrict__ rows, Enc enc) {
+    unsigned clamped = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * kKeyedThreads + threadIdx.x; e < total; e += (uint64_t)gridDim.x * kKeyedThreads) {
         const uint64_t i = e / dim;
-        const uint32_t r = dst[i];
-        if (r != kKeyedLoser) store_as(rows + (uint64_t)r * dim, (size_t)(e - i * dim), src[e]);
+        const uint32_t r = dst[i], comp = (uint32_t)(e - i * dim);
+        if (r != kKeyedLoser) clamped += enc.put(rows + (uint64_t)r * dim, (size_t)comp, comp, src[e]);
     }
+    if (Enc::kCounts) block_count(clamped, enc.counter());
 }
 
 __global__ __launch_bounds__(kKeyedThreads) void keyed_remove_kernel(const uint32_t* __restrict__ labels, uint32_t n, const uint32_t* __restrict__ tkey,
@@ -340,16 +513,49 @@ hipError_t launch_refine_dist(const RefinePass& p, const RefinePlan& plan, hipSt
     const DenseLookup dense{p.lo, p.nrows};
     const KeyedLookup keyed{p.tkey, p.trow, p.tbits};
 #define QADC_RD(ROW, LOOKUP, look)                                                                                                       \
-    hipLaunchKernelGGL((refine_dist_kernel<ROW, LOOKUP>), grid, block, plan.dist_lds_bytes, stream, static_cast<const ROW*>(p.rows), look, \
-                       p.dim, p.queries, p.r_in, p.keys, p.counts, p.values, plan.cands_per_wg, plan.chunks, p.words, p.missing)
+    hipLaunchKernelGGL((refine_dist_kernel<ROW, LOOKUP>), grid, block, lds, stream, static_cast<const ROW*>(p.rows), look, p.dim, p.sq.vmin, \
+                       p.sq.step, p.queries, p.r_in, p.keys, p.counts, p.values, plan.cands_per_wg, plan.chunks, p.words, p.missing)
+    // (SQ8 rows: vmin and step behind the query, 3 * dim floats <= 48 KiB)
+    const size_t lds = p.elem == Elem::kSQ8 ? 3 * plan.dist_lds_bytes : plan.dist_lds_bytes;
     if (p.tkey) {
-        if (p.f16) QADC_RD(__half, KeyedLookup, keyed);
+        if (p.elem == Elem::kSQ8) QADC_RD(sq8_t, KeyedLookup, keyed);
+        else if (p.elem == Elem::kF16) QADC_RD(__half, KeyedLookup, keyed);
         else QADC_RD(float, KeyedLookup, keyed);
     } else {
-        if (p.f16) QADC_RD(__half, DenseLookup, dense);
+        if (p.elem == Elem::kSQ8) QADC_RD(sq8_t, DenseLookup, dense);
+        else if (p.elem == Elem::kF16) QADC_RD(__half, DenseLookup, dense);
         else QADC_RD(float, DenseLookup, dense);
     }
 #undef QADC_RD
+    return hipGetLastError();
+}
+
+hipError_t launch_refine_get(const RefinePass& p, const uint32_t* keys, uint64_t count, float* out, uint8_t* found, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    const dim3 grid((unsigned)std::min<uint64_t>((count + 3) / 4, 65536)), block(256);
+    const DenseLookup dense{p.lo, p.nrows};
+    const KeyedLookup keyed{p.tkey, p.trow, p.tbits};
+#define QADC_RG(ROW, LOOKUP, look)                                                                                                         \
+    hipLaunchKernelGGL((refine_get_kernel<ROW, LOOKUP>), grid, block, 0, stream, static_cast<const ROW*>(p.rows), look, p.dim, p.sq.vmin, \
+                       p.sq.step, keys, count, out, found)
+    if (p.tkey) {
+        if (p.elem == Elem::kSQ8) QADC_RG(sq8_t, KeyedLookup, keyed);
+        else if (p.elem == Elem::kF16) QADC_RG(__half, KeyedLookup, keyed);
+        else QADC_RG(float, KeyedLookup, keyed);
+    } else {
+        if (p.elem == Elem::kSQ8) QADC_RG(sq8_t, DenseLookup, dense);
+        else if (p.elem == Elem::kF16) QADC_RG(__half, DenseLookup, dense);
+        else QADC_RG(float, DenseLookup, dense);
+    }
+#undef QADC_RG
+    return hipGetLastError();
+}
+
+hipError_t launch_refine_sq_range(const float* vectors, uint64_t n, int dim, uint32_t* lo, uint32_t* hi, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint64_t tiles = (n + kSqRangeRows - 1) / kSqRangeRows;
+    hipLaunchKernelGGL(refine_sq_range_kernel, dim3((unsigned)std::min<uint64_t>(tiles, 2048)), dim3(256), 2 * (size_t)dim * sizeof(uint32_t), stream,
+                       vectors, n, (uint32_t)dim, lo, hi);
     return hipGetLastError();
 }
 
@@ -362,13 +568,18 @@ hipError_t launch_refine_select(const RefinePass& p, const RefinePlan& plan, hip
     }
 }
 
-hipError_t launch_refine_convert(const float* src, void* dst, bool f16, uint64_t n, hipStream_t stream) {
+hipError_t launch_refine_convert(const float* src, void* dst, Elem elem, const SqParams& sq, int dim, uint64_t n, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((unsigned)std::min<uint64_t>((n + 255) / 256, 65536)), block(256);
-    if (f16)
-        hipLaunchKernelGGL(refine_convert_kernel<__half>, grid, block, 0, stream, src, static_cast<__half*>(dst), n);
+    if (elem == Elem::kSQ8)
+        hipLaunchKernelGGL((refine_convert_kernel<sq8_t, SqEncode>), grid, block, 0, stream, src, static_cast<sq8_t*>(dst), n, (uint32_t)dim,
+                           SqEncode{sq.vmin, sq.step, sq.inv, sq.clamped});
+    else if (elem == Elem::kF16)
+        hipLaunchKernelGGL((refine_convert_kernel<__half, PlainEncode>), grid, block, 0, stream, src, static_cast<__half*>(dst), n, (uint32_t)dim,
+                           PlainEncode{});
     else
-        hipLaunchKernelGGL(refine_convert_kernel<float>, grid, block, 0, stream, src, static_cast<float*>(dst), n);
+        hipLaunchKernelGGL((refine_convert_kernel<float, PlainEncode>), grid, block, 0, stream, src, static_cast<float*>(dst), n, (uint32_t)dim,
+                           PlainEncode{});
     return hipGetLastError();
 }
 
@@ -408,15 +619,19 @@ hipError_t launch_keyed_reset(uint32_t n, KeyedTable t, const uint32_t* slot_of,
     return hipGetLastError();
 }
 
-hipError_t launch_keyed_store(const float* src, const uint32_t* dst, uint32_t n, int dim, void* rows, bool f16, hipStream_t stream) {
+hipError_t launch_keyed_store(const float* src, const uint32_t* dst, uint32_t n, int dim, void* rows, Elem elem, const SqParams& sq,
+                              hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const uint64_t total = (uint64_t)n * (uint64_t)dim;
-    if (f16)
-        hipLaunchKernelGGL(keyed_store_kernel<__half>, dim3(keyed_grid(total)), dim3(kKeyedThreads), 0, stream, src, dst, total, (uint32_t)dim,
-                           static_cast<__half*>(rows));
+    if (elem == Elem::kSQ8)
+        hipLaunchKernelGGL((keyed_store_kernel<sq8_t, SqEncode>), dim3(keyed_grid(total)), dim3(kKeyedThreads), 0, stream, src, dst, total,
+                           (uint32_t)dim, static_cast<sq8_t*>(rows), SqEncode{sq.vmin, sq.step, sq.inv, sq.clamped});
+    else if (elem == Elem::kF16)
+        hipLaunchKernelGGL((keyed_store_kernel<__half, PlainEncode>), dim3(keyed_grid(total)), dim3(kKeyedThreads), 0, stream, src, dst, total,
+                           (uint32_t)dim, static_cast<__half*>(rows), PlainEncode{});
     else
-        hipLaunchKernelGGL(keyed_store_kernel<float>, dim3(keyed_grid(total)), dim3(kKeyedThreads), 0, stream, src, dst, total, (uint32_t)dim,
-                           static_cast<float*>(rows));
+        hipLaunchKernelGGL((keyed_store_kernel<float, PlainEncode>), dim3(keyed_grid(total)), dim3(kKeyedThreads), 0, stream, src, dst, total,
+                           (uint32_t)dim, static_cast<float*>(rows), PlainEncode{});
     return hipGetLastError();
 }
 

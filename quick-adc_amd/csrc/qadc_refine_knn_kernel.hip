@@ -8,6 +8,8 @@
 
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
 namespace qadc {
 namespace refine {
 
@@ -17,8 +19,17 @@ constexpr uint32_t kNanImage = 0x7FC00000u;
 constexpr uint32_t kInfImage = 0x7F800000u;
 constexpr uint64_t kNoWord = ~0ull;
 
-__device__ inline float row_value(const float* x, int i) { return x[i]; }
-__device__ inline float row_value(const __half* x, int i) { return __half2float(x[i]); }
+struct sq8_t {                                        // a component of an SQ8 row
+    uint8_t b;
+};
+
+// component i of a row; vmin and step are component i's parameters of an SQ8 store (unused by the other types)
+__device__ inline float row_value(const float* x, int i, float, float) { return x[i]; }
+__device__ inline float row_value(const __half* x, int i, float, float) { return __half2float(x[i]); }
+__device__ inline float row_value(const sq8_t* x, int i, float vmin, float step) {
+    const float m = (float)x[i].b * step;
+    return vmin + m;
+}
 
 // ScanFilter's rule (csrc/qadc_adc_kernels.h): a key is marked where it lies in [lo, lo + last] and its bit is set; EXCLUDE drops
 // the marked keys, ALLOW keeps only them.  The bitmap has one word at least and a key outside the span reads none.
@@ -40,19 +51,32 @@ constexpr int knn_log2(int n) { return n <= 1 ? 0 : 1 + knn_log2(n / 2); }
 // half, as p[l] + p[l - s]: the same two operands, and IEEE addition is commutative (only a NaN's payload can tell, and every NaN
 // becomes 0x7FC00000).  After log2(QT) strides a lane holds one value, that of query lane >> (6 - log2(QT)) of the tile; the
 // remaining strides fold it the plain way and the lanes whose low 6 - log2(QT) bits are zero hold D.
+//
+// SQ8 rows: a register tile keeps vmin and step of the lane's components in registers beside the queries' (2 J more); an LDS tile,
+// which may fill the LDS by itself, reads them from global memory with the row's bytes (coalesced, and the same for every row).
+// The row's bytes are loaded one per lane and component here: the dword-and-exchange form of refine_dist_kernel was measured in this
+// kernel too and is slower in it.
 template <typename Row, int QT, int J>
 __global__ __launch_bounds__(kKnnWaves * 64) void refine_knn_dist_kernel(const Row* __restrict__ rows, uint32_t lo, uint64_t nrows,
                                                                          const uint32_t* __restrict__ row_key, adc::ScanFilter filter, int dim,
+                                                                         const float* __restrict__ sq_vmin, const float* __restrict__ sq_step,
                                                                          const float* __restrict__ queries, int nq, uint64_t chunk_rows,
                                                                          int groups, int slice_rows, int slices, uint64_t launch, uint64_t buf_cap,
                                                                          uint64_t* __restrict__ buf, uint32_t* __restrict__ cnt,
                                                                          const uint64_t* __restrict__ bound) {
     extern __shared__ float s_tile[];   // LDS tile (J == 0): [QT][dim]
     constexpr int kLog = knn_log2(QT), kShift = 6 - kLog, JR = J > 0 ? J : 1;
+    constexpr bool kSq = std::is_same<Row, sq8_t>::value;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int q0 = blockIdx.x * QT, group = blockIdx.y / slices, slice = blockIdx.y % slices;
 
-    float qr[QT][JR];
+    float qr[QT][JR], vr[JR], sr[JR];
+#pragma unroll
+    for (int j = 0; j < JR; ++j) {
+        const int i = 64 * j + lane;
+        vr[j] = (kSq && J > 0 && i < dim) ? sq_vmin[i] : 0.0f;
+        sr[j] = (kSq && J > 0 && i < dim) ? sq_step[i] : 0.0f;
+    }
     if (J > 0) {
 #pragma unroll
         for (int q = 0; q < QT; ++q)
@@ -89,7 +113,7 @@ __global__ __launch_bounds__(kKnnWaves * 64) void refine_knn_dist_kernel(const R
 #pragma unroll
             for (int j = 0; j < JR; ++j) {
                 const int i = 64 * j + lane;
-                const float xv = i < dim ? row_value(x, i) : 0.0f;
+                const float xv = i < dim ? row_value(x, i, vr[j], sr[j]) : 0.0f;
 #pragma unroll
                 for (int q = 0; q < QT; ++q) {
                     const float t = qr[q][j] - xv;
@@ -99,7 +123,7 @@ __global__ __launch_bounds__(kKnnWaves * 64) void refine_knn_dist_kernel(const R
             }
         } else {
             for (int i = lane; i < dim; i += 64) {
-                const float xv = row_value(x, i);
+                const float xv = row_value(x, i, kSq ? sq_vmin[i] : 0.0f, kSq ? sq_step[i] : 0.0f);
 #pragma unroll
                 for (int q = 0; q < QT; ++q) {
                     const float t = s_tile[q * dim + i] - xv;
@@ -213,7 +237,7 @@ template <typename Row, int QT, int J>
 hipError_t launch_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launch, int live, hipStream_t stream) {
     const dim3 grid((unsigned)((p.nq + QT - 1) / QT), (unsigned)(live * plan.slices)), block(kKnnWaves * 64);
     hipLaunchKernelGGL((refine_knn_dist_kernel<Row, QT, J>), grid, block, plan.dist_lds_bytes, stream, static_cast<const Row*>(p.rows), p.lo,
-                       p.nrows, p.row_key, p.filter, p.dim, p.queries, p.nq, plan.chunk_rows, plan.groups, plan.slice_rows, plan.slices, launch,
+                       p.nrows, p.row_key, p.filter, p.dim, p.sq.vmin, p.sq.step, p.queries, p.nq, plan.chunk_rows, plan.groups, plan.slice_rows, plan.slices, launch,
                        plan.buf_cap, p.buf, p.cnt, p.bound);
     return hipGetLastError();
 }
@@ -234,7 +258,8 @@ hipError_t dispatch_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launch,
 hipError_t launch_knn_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream) {
     const int live = knn_launch_groups(p.nrows, plan.chunk_rows, plan.groups, launch);
     if (live == 0 || p.nq == 0) return hipSuccess;
-    return p.f16 ? dispatch_dist<__half>(p, plan, launch, live, stream) : dispatch_dist<float>(p, plan, launch, live, stream);
+    if (p.elem == Elem::kSQ8) return dispatch_dist<sq8_t>(p, plan, launch, live, stream);
+    return p.elem == Elem::kF16 ? dispatch_dist<__half>(p, plan, launch, live, stream) : dispatch_dist<float>(p, plan, launch, live, stream);
 }
 
 hipError_t launch_knn_select(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream) {

@@ -18,19 +18,27 @@
 //
 // Exhaustive search (knn, at the end): the selection above over every key the store holds that passes a
 // key filter — the definition of qadc_refine_knn.
+//
+// SQ8 rows (kSQ8): one byte per component under a per-dimension affine range, vmin[dim] and step[dim], both
+// finite, step >= 0; inv[i] = 1.0f / step[i] where step[i] > 0 (+inf for a subnormal step), else 0, derived once.  sq_encode,
+// sq_decode and sq_range below are the definition; a row's i-th component in D(q, x) is sq_decode of its byte, and `clamped` counts
+// the written components that fell outside the range.  get() reads rows back as floats, decoded by the store's type.
 #pragma once
 #include <algorithm>
+#include <cfenv>
 #include <cfloat>
 #include <cstddef>
 #include <cstdint>
+#include <cmath>
 #include <cstring>
 #include <map>
+#include <stdexcept>
 #include <vector>
 
 namespace qadc {
 namespace refine {
 
-constexpr int kF32 = 0, kF16 = 1;                    // QADC_REFINE_F32, QADC_REFINE_F16
+constexpr int kF32 = 0, kF16 = 1, kSQ8 = 2;          // QADC_REFINE_F32, QADC_REFINE_F16, QADC_REFINE_SQ8
 constexpr int kMaxDim = 4096;
 constexpr int kMaxIn = 8192;                         // QADC_REFINE_MAX_IN
 constexpr uint32_t kNanImage = 0x7FC00000u;          // every NaN distance: behind +inf (0x7F800000)
@@ -105,6 +113,135 @@ QADC_REFINE_NO_CONTRACT inline float distance(const float* q, int dim, RowAt x) 
 
 inline uint32_t image(float d) { return d != d ? kNanImage : float_bits(d); }
 
+// ---- SQ8 rows: IEEE binary32, every operation rounded by itself ----
+
+inline bool sq_finite(float f) { return (float_bits(f) & 0x7F800000u) != 0x7F800000u; }
+
+// The definition is IEEE arithmetic with subnormals.  A thread may run with subnormals flushed to zero (a library built with
+// -ffast-math sets that mode for every thread that loads it); the host-side derivations below — inv, the range's step — run inside
+// an ieee_scope, which puts the thread into the default floating-point environment and gives its own back at the end.  The
+// arithmetic sits in functions that are not inlined, so that none of it moves across the switch.
+struct ieee_scope {
+    std::fenv_t saved;
+    ieee_scope() {
+        std::fegetenv(&saved);
+        std::fesetenv(FE_DFL_ENV);
+    }
+    ~ieee_scope() { std::fesetenv(&saved); }
+    ieee_scope(const ieee_scope&) = delete;
+    ieee_scope& operator=(const ieee_scope&) = delete;
+};
+#if defined(__GNUC__) || defined(__clang__)
+#define QADC_REFINE_NOINLINE __attribute__((noinline))
+#else
+#define QADC_REFINE_NOINLINE
+#endif
+
+// what a store of this type takes: vmin and step finite, step >= 0 (by their bits: -0 is a zero, a negative subnormal is negative)
+inline bool sq_params_ok(const float* vmin, const float* step, int dim) {
+    if (!vmin || !step || dim < 1 || dim > kMaxDim) return false;
+    for (int i = 0; i < dim; ++i) {
+        const uint32_t s = float_bits(step[i]);
+        if (!sq_finite(vmin[i]) || !sq_finite(step[i]) || ((s & 0x80000000u) && (s & 0x7FFFFFFFu))) return false;
+    }
+    return true;
+}
+
+inline float sq_inv(float step) { return step > 0.0f ? 1.0f / step : 0.0f; }
+
+// inv[i] = sq_inv(step[i]) under the default floating-point environment
+QADC_REFINE_NOINLINE inline void sq_inv_rows(const float* step, int dim, float* inv) {
+    for (int i = 0; i < dim; ++i) inv[i] = sq_inv(step[i]);
+}
+inline void sq_derive_inv(const float* step, int dim, float* inv) {
+    ieee_scope ieee;
+    sq_inv_rows(step, dim, inv);
+}
+
+// The byte of component x under (vmin, step, inv = sq_inv(step)): d = x - vmin, u = d * inv; 0 where !(u > 0) (NaN, below the
+// range, a constant dimension), 255 where u >= 255, else u rounded to the nearest integer, ties to even.  *clamped (may be null): the
+// component fell outside the range — step > 0: !(d >= 0) or !(u <= 255); step == 0: x differs in value from vmin (a NaN does).
+inline uint8_t sq_encode(float x, float vmin, float step, float inv, bool* clamped) {
+    const float d = x - vmin;
+    const float u = d * inv;
+    if (clamped) *clamped = step > 0.0f ? (!(d >= 0.0f) || !(u <= 255.0f)) : !(x == vmin);
+    if (!(u > 0.0f)) return 0;
+    if (u >= 255.0f) return 255;
+    return (uint8_t)std::nearbyintf(u);              // (the default rounding mode: to nearest, ties to even)
+}
+
+// vmin + (float)c * step: the product rounded, then the sum
+QADC_REFINE_NO_CONTRACT inline float sq_decode(uint8_t c, float vmin, float step) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float m = (float)c * step;
+    return vmin + m;
+}
+
+// the sign-magnitude order of binary32 as an unsigned integer: -0 below +0
+inline uint32_t sq_ordered(float f) {
+    const uint32_t u = float_bits(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+inline float sq_unordered(uint32_t o) { return bits_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
+
+// vmin and step of the dimensions whose finite components span [lo[i], hi[i]] as ordered images (lo > hi: none, which gives
+// vmin = 0, step = 0)
+QADC_REFINE_NOINLINE inline void sq_range_rows(const uint32_t* lo, const uint32_t* hi, int dim, float* vmin, float* step) {
+    for (int i = 0; i < dim; ++i) {
+        const float a = lo[i] > hi[i] ? 0.0f : sq_unordered(lo[i]), b = lo[i] > hi[i] ? 0.0f : sq_unordered(hi[i]);
+        vmin[i] = a;
+        step[i] = (b - a) / 255.0f;
+    }
+}
+inline void sq_range_finish(const uint32_t* lo, const uint32_t* hi, int dim, float* vmin, float* step) {
+    ieee_scope ieee;
+    sq_range_rows(lo, hi, dim, vmin, step);
+}
+
+// The range of a learning set [n][dim]: per dimension the minimum and maximum over its finite components in the order of
+// sq_ordered; vmin = the minimum, step = (max - min) / 255.0f.  A function of the set alone; step may be +inf where max - min
+// overflows, which no store takes.
+inline void sq_range(const float* vectors, uint64_t n, int dim, float* vmin, float* step) {
+    std::vector<uint32_t> lo((size_t)dim, 0xFFFFFFFFu), hi((size_t)dim, 0u);
+    for (uint64_t r = 0; r < n; ++r)
+        for (int i = 0; i < dim; ++i) {
+            const float x = vectors[(size_t)r * dim + i];
+            if (!sq_finite(x)) continue;
+            const uint32_t o = sq_ordered(x);
+            lo[i] = std::min(lo[i], o);
+            hi[i] = std::max(hi[i], o);
+        }
+    sq_range_finish(lo.data(), hi.data(), dim, vmin, step);
+}
+
+// The parameters of an SQ8 store and its clamp counter
+struct sq_params {
+    std::vector<float> vmin, step, inv;
+    uint64_t clamped = 0;
+    void set(int dim, const float* vmin_, const float* step_) {
+        if (!sq_params_ok(vmin_, step_, dim)) throw std::invalid_argument("SQ8: vmin and step are finite, step >= 0");
+        vmin.assign(vmin_, vmin_ + dim);
+        step.assign(step_, step_ + dim);
+        inv.resize(dim);
+        sq_derive_inv(step.data(), dim, inv.data());
+    }
+    // dst[0 .. dim) = the bytes of v[0 .. dim); counts the clamped components
+    void encode_row(const float* v, uint8_t* dst) {
+        ieee_scope ieee;
+        encode_components(v, dst);
+    }
+    QADC_REFINE_NOINLINE void encode_components(const float* v, uint8_t* dst) {
+        for (size_t i = 0; i < vmin.size(); ++i) {
+            bool c;
+            dst[i] = sq_encode(v[i], vmin[i], step[i], inv[i], &c);
+            clamped += c ? 1 : 0;
+        }
+    }
+};
+
 // The store: dense over the keys [lo, lo + rows), row r the vector of key lo + r.
 struct store {
     int dim = 0, dtype = kF32;
@@ -112,8 +249,13 @@ struct store {
     uint64_t rows = 0;
     std::vector<float> f32;
     std::vector<uint16_t> f16;
+    std::vector<uint8_t> sq8;
+    sq_params sq;                                    // kSQ8 only
 
-    store(int dim_, int dtype_) : dim(dim_), dtype(dtype_) {}
+    store(int dim_, int dtype_) : dim(dim_), dtype(dtype_) {
+        if (dtype_ == kSQ8) throw std::invalid_argument("an SQ8 store needs vmin and step");
+    }
+    store(int dim_, const float* vmin, const float* step) : dim(dim_), dtype(kSQ8) { sq.set(dim_, vmin, step); }
 
     // false: first_key does not continue the store, or lo + rows would pass 2^32 (the store is left as it was)
     bool add(const float* vectors, uint64_t count, uint32_t first_key) {
@@ -125,6 +267,10 @@ struct store {
         if (dtype == kF16) {
             f16.reserve(f16.size() + n);
             for (size_t i = 0; i < n; ++i) f16.push_back(float_to_half(vectors[i]));
+        } else if (dtype == kSQ8) {
+            const size_t at = sq8.size();
+            sq8.resize(at + n);
+            for (uint64_t r = 0; r < count; ++r) sq.encode_row(vectors + (size_t)r * dim, sq8.data() + at + (size_t)r * dim);
         } else {
             f32.insert(f32.end(), vectors, vectors + n);
         }
@@ -141,11 +287,24 @@ struct store {
         return k;
     }
 
+    // component i of the row of a held key, as the distance reads it
+    float value_at(uint32_t key, int i) const {
+        const size_t at = (size_t)(key - lo) * dim + i;
+        if (dtype == kF16) return half_to_float(f16[at]);
+        if (dtype == kSQ8) return sq_decode(sq8[at], sq.vmin[i], sq.step[i]);
+        return f32[at];
+    }
+
     float distance_to(const float* q, uint32_t key) const {
         const size_t base = (size_t)(key - lo) * dim;
         if (dtype == kF16) {
             const uint16_t* x = f16.data() + base;
             return distance(q, dim, [x](int i) { return half_to_float(x[i]); });
+        }
+        if (dtype == kSQ8) {
+            const uint8_t* x = sq8.data() + base;
+            const float *vmin = sq.vmin.data(), *step = sq.step.data();
+            return distance(q, dim, [x, vmin, step](int i) { return sq_decode(x[i], vmin[i], step[i]); });
         }
         const float* x = f32.data() + base;
         return distance(q, dim, [x](int i) { return x[i]; });
@@ -157,21 +316,35 @@ struct store {
 // the call's arguments alone — no slot, row or order of earlier puts can show in it.
 struct keyed_store {
     int dim = 0, dtype = kF32;
-    std::map<uint32_t, std::vector<float>> f32;      // one of the two is in use, by dtype
+    std::map<uint32_t, std::vector<float>> f32;      // one of the three is in use, by dtype
     std::map<uint32_t, std::vector<uint16_t>> f16;
+    std::map<uint32_t, std::vector<uint8_t>> sq8;
+    sq_params sq;                                    // kSQ8 only
 
-    keyed_store(int dim_, int dtype_) : dim(dim_), dtype(dtype_) {}
+    keyed_store(int dim_, int dtype_) : dim(dim_), dtype(dtype_) {
+        if (dtype_ == kSQ8) throw std::invalid_argument("an SQ8 store needs vmin and step");
+    }
+    keyed_store(int dim_, const float* vmin, const float* step) : dim(dim_), dtype(kSQ8) { sq.set(dim_, vmin, step); }
 
-    uint64_t live() const { return dtype == kF16 ? f16.size() : f32.size(); }
+    uint64_t live() const { return dtype == kF16 ? f16.size() : dtype == kSQ8 ? sq8.size() : f32.size(); }
 
     // For i ascending the vector of key labels[i] becomes vectors[i], converted as store::add converts: a key not held becomes
     // held, the last occurrence of a key wins.  false: a label is 0xFFFFFFFF, the filler key of rerank (the map is left as it was).
+    // An SQ8 store writes the last occurrence of a key only, so that only what reaches a row counts as clamped.
     bool put(const float* vectors, const uint32_t* labels, uint64_t count) {
         for (uint64_t i = 0; i < count; ++i)
             if (labels[i] == kNoKey) return false;
+        std::map<uint32_t, uint64_t> last;
+        if (dtype == kSQ8)
+            for (uint64_t i = 0; i < count; ++i) last[labels[i]] = i;
         for (uint64_t i = 0; i < count; ++i) {
             const float* v = vectors + (size_t)i * dim;
-            if (dtype == kF16) {
+            if (dtype == kSQ8) {
+                if (last[labels[i]] != i) continue;
+                std::vector<uint8_t>& row = sq8[labels[i]];
+                row.resize(dim);
+                sq.encode_row(v, row.data());
+            } else if (dtype == kF16) {
                 std::vector<uint16_t>& row = f16[labels[i]];
                 row.resize(dim);
                 for (int j = 0; j < dim; ++j) row[j] = float_to_half(v[j]);
@@ -185,11 +358,14 @@ struct keyed_store {
     // Every listed key that is held leaves; returns how many left (a key listed twice counts once, a key not held is ignored)
     uint64_t remove(const uint32_t* labels, uint64_t count) {
         uint64_t removed = 0;
-        for (uint64_t i = 0; i < count; ++i) removed += dtype == kF16 ? f16.erase(labels[i]) : f32.erase(labels[i]);
+        for (uint64_t i = 0; i < count; ++i)
+            removed += dtype == kF16 ? f16.erase(labels[i]) : dtype == kSQ8 ? sq8.erase(labels[i]) : f32.erase(labels[i]);
         return removed;
     }
 
-    bool holds(uint32_t key) const { return dtype == kF16 ? f16.count(key) != 0 : f32.count(key) != 0; }
+    bool holds(uint32_t key) const {
+        return dtype == kF16 ? f16.count(key) != 0 : dtype == kSQ8 ? sq8.count(key) != 0 : f32.count(key) != 0;
+    }
 
     // every key held, ascending (what knn ranks)
     std::vector<uint32_t> held_keys() const {
@@ -197,9 +373,18 @@ struct keyed_store {
         k.reserve((size_t)live());
         if (dtype == kF16)
             for (const auto& e : f16) k.push_back(e.first);
+        else if (dtype == kSQ8)
+            for (const auto& e : sq8) k.push_back(e.first);
         else
             for (const auto& e : f32) k.push_back(e.first);
         return k;
+    }
+
+    // component i of the row of a held key, as the distance reads it
+    float value_at(uint32_t key, int i) const {
+        if (dtype == kF16) return half_to_float(f16.find(key)->second[i]);
+        if (dtype == kSQ8) return sq_decode(sq8.find(key)->second[i], sq.vmin[i], sq.step[i]);
+        return f32.find(key)->second[i];
     }
 
     float distance_to(const float* q, uint32_t key) const {
@@ -207,10 +392,26 @@ struct keyed_store {
             const uint16_t* x = f16.find(key)->second.data();
             return distance(q, dim, [x](int i) { return half_to_float(x[i]); });
         }
+        if (dtype == kSQ8) {
+            const uint8_t* x = sq8.find(key)->second.data();
+            const float *vmin = sq.vmin.data(), *step = sq.step.data();
+            return distance(q, dim, [x, vmin, step](int i) { return sq_decode(x[i], vmin[i], step[i]); });
+        }
         const float* x = f32.find(key)->second.data();
         return distance(q, dim, [x](int i) { return x[i]; });
     }
 };
+
+// Read-back (qadc_refine_get): out [count][dim] = the rows of the listed keys as floats, decoded by the store's type; a key the
+// store does not hold gives a row of 0x7FC00000 and found 0.  found may be null.
+template <typename Store>
+inline void get(const Store& s, const uint32_t* keys, uint64_t count, float* out, uint8_t* found) {
+    for (uint64_t k = 0; k < count; ++k) {
+        const bool held = s.holds(keys[k]);
+        for (int i = 0; i < s.dim; ++i) out[(size_t)k * s.dim + i] = held ? s.value_at(keys[k], i) : bits_float(kNanImage);
+        if (found) found[k] = held ? 1 : 0;
+    }
+}
 
 // queries [nq][dim], keys [nq][r_in], counts [nq] or null (every count in [0, r_in]), values [nq][r_in] or null ->
 // out_keys [nq][R], out_dist [nq][R], out_sizes [nq]; returns the missing entries of all queries.  Store: store or keyed_store —

@@ -1,4 +1,4 @@
-// refine_store_hip — C++14 RAII mirror of the refine store (qadc_refine_* in include/qadc.h; DESIGN.md sections 11.11 and 11.14): the
+// refine_store_hip — C++14 RAII mirror of the refine store (qadc_refine_* in include/qadc.h; DESIGN.md sections 11.11, 11.14 and 11.20): the
 // original vectors in device memory, dense over the keys [lo, lo + rows) or, with keyed = true, a map from key to vector filled by
 // put() and emptied by remove(); and rerank(), which reorders candidate keys by their exact squared L2 distance to them.  search_refined() composes it with adc_search_engine_hip (host/adc_search_hip.hpp): the engine's search with
 // R = the engine's r as r_in, then the re-ranking of the heaps' keys, the FLT_MAX sentinels left out.  The definition both are held
@@ -29,6 +29,10 @@ struct refine_store_hip {
     refine_store_hip(int dim_, int dtype = QADC_REFINE_F32, int device = 0, bool keyed = false) : dim(dim_) {
         if ((keyed ? qadc_refine_create_keyed(&store, dim_, dtype, device) : qadc_refine_create(&store, dim_, dtype, device)) != QADC_OK)
             die("Cannot create the refine store");
+    }
+    // SQ8 rows (qadc_refine_create_sq8): one byte per component under the range vmin [dim], step [dim]
+    refine_store_hip(int dim_, const float* vmin, const float* step, int device = 0, bool keyed = false) : dim(dim_) {
+        if (qadc_refine_create_sq8(&store, dim_, vmin, step, keyed ? 1 : 0, device) != QADC_OK) die("Cannot create the SQ8 refine store");
     }
     refine_store_hip(const refine_store_hip&) = delete;
     refine_store_hip& operator=(const refine_store_hip&) = delete;
@@ -65,6 +69,23 @@ struct refine_store_hip {
         std::uint64_t n = 0;
         qadc_refine_info(store, nullptr, nullptr, nullptr, &n, nullptr);
         return n;
+    }
+
+    // the rows of keys [count] as floats [count][dim], decoded by the store's type; a key not held gives a row of NaN and found 0
+    std::vector<float> get(const std::uint32_t* keys, std::uint64_t count, std::vector<std::uint8_t>* found = nullptr) {
+        std::vector<float> out((std::size_t)count * dim);
+        if (found) found->resize((std::size_t)count);
+        if (qadc_refine_get(store, keys, count, out.data(), found ? found->data() : nullptr) != QADC_OK) die("get");
+        return out;
+    }
+
+    // an SQ8 store: its range (either may be null) and the components written outside it so far
+    std::uint64_t sq_info(std::vector<float>* vmin = nullptr, std::vector<float>* step = nullptr) const {
+        std::uint64_t clamped = 0;
+        if (vmin) vmin->resize(dim);
+        if (step) step->resize(dim);
+        if (qadc_refine_sq_info(store, vmin ? vmin->data() : nullptr, step ? step->data() : nullptr, &clamped) != QADC_OK) die("sq_info");
+        return clamped;
     }
 
     // queries [nq][dim], keys [nq][r_in], counts [nq] or null, values [nq][r_in] or null -> the first r of every query's candidates

@@ -63,6 +63,8 @@ SYMBOLS = [
     "qadc_refine_create_keyed", "qadc_refine_put", "qadc_refine_put_device", "qadc_refine_remove", "qadc_refine_remove_device",
     "qadc_refine_keyed_info", "qadc_refine_keyed_slot",
     "qadc_refine_knn", "qadc_refine_knn_device", "qadc_refine_set_knn_plan",
+    "qadc_refine_create_sq8", "qadc_refine_sq_range_host", "qadc_refine_sq_range_device", "qadc_refine_sq_info", "qadc_refine_get",
+    "qadc_refine_get_device",
     "qadc_pq_decode_host", "qadc_pq_decode_device", "qadc_adc_index_reconstruct", "qadc_adc_index_reconstruct_device",
     "qadc_adc_index_reconstruct_rows", "qadc_adc_index_reconstruct_rows_device",
     "qadc_adc_range_scan", "qadc_adc_range_scan_device", "qadc_adc_range_search", "qadc_adc_range_search_device",
@@ -326,6 +328,12 @@ def lib():
         L.qadc_refine_knn.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_void_p, u32p, f32p, i32p]
         L.qadc_refine_knn_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qadc_refine_set_knn_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+        L.qadc_refine_create_sq8.argtypes = [C.POINTER(C.c_void_p), C.c_int, f32p, f32p, C.c_int, C.c_int]
+        L.qadc_refine_sq_range_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, f32p, f32p]
+        L.qadc_refine_sq_range_device.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, f32p, f32p]
+        L.qadc_refine_sq_info.argtypes = [C.c_void_p, f32p, f32p, u64p]
+        L.qadc_refine_get.argtypes = [C.c_void_p, u32p, C.c_uint64, f32p, C.POINTER(C.c_uint8)]
+        L.qadc_refine_get_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.qadc_pq_decode_host.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, i32p, C.c_void_p, C.c_uint64, f32p, f32p, f32p,
                                           C.c_int]
         L.qadc_pq_decode_device.argtypes = [C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
@@ -2223,7 +2231,34 @@ class AdcIndex(_RowStoreMixin):
 
 
 QADC_REFINE_F32, QADC_REFINE_F16, QADC_REFINE_MAX_IN = 0, 1, 8192   # include/qadc.h
-_REFINE_DTYPES = {"f32": QADC_REFINE_F32, "f16": QADC_REFINE_F16}
+QADC_REFINE_SQ8 = 2
+_REFINE_DTYPES = {"f32": QADC_REFINE_F32, "f16": QADC_REFINE_F16, "sq8": QADC_REFINE_SQ8}
+_REFINE_DTYPE_NAMES = {v: k for k, v in _REFINE_DTYPES.items()}
+
+
+def refine_sq_range(vectors, device=0):
+    """qadc_refine_sq_range_host: vectors [n][dim] -> (vmin float32 [dim], step float32 [dim]), the range of an SQ8 store
+    (DESIGN.md section 11.20): per dimension the minimum of the finite components and (max - min) / 255"""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2 or v.shape[1] < 1:
+        raise QadcError("vectors has shape %s, expected [n][dim]" % (v.shape,))
+    vmin, step = np.zeros(v.shape[1], np.float32), np.zeros(v.shape[1], np.float32)
+    _check(lib().qadc_refine_sq_range_host(_p(v, f32p) if v.shape[0] else None, v.shape[0], v.shape[1], device, _p(vmin, f32p), _p(step, f32p)))
+    return vmin, step
+
+
+def refine_sq_range_device(vectors):
+    """the same for a contiguous float32 torch tensor [n][dim] in device memory, read where it lies; the results are numpy arrays"""
+    import torch
+    if not isinstance(vectors, torch.Tensor) or vectors.ndim != 2 or vectors.dtype != torch.float32 or vectors.device.type != "cuda":
+        raise TypeError("vectors must be a 2-d float32 torch.Tensor in device memory")
+    if not vectors.is_contiguous():
+        raise QadcError("vectors must be contiguous")
+    n, dim = int(vectors.shape[0]), int(vectors.shape[1])
+    torch.cuda.current_stream(vectors.device).synchronize()
+    vmin, step = np.zeros(dim, np.float32), np.zeros(dim, np.float32)
+    _check(lib().qadc_refine_sq_range_device(vectors.data_ptr() if n else None, n, dim, vectors.device.index, _p(vmin, f32p), _p(step, f32p)))
+    return vmin, step
 
 
 def refine_keyed_slot(key, bits):
@@ -2237,15 +2272,73 @@ class Refine:
     a search's, with a larger R than wanted — by their exact squared L2 distance; AdcIndex.search_refined, .search_refined_device
     and Index.search_refined compose the two.
     keyed=True (qadc_refine_create_keyed; section 11.14): a map from key to vector in place of the dense range, filled by put(),
-    emptied by remove(); add() belongs to the dense kind, put() and remove() to the keyed one (QadcError otherwise)."""
+    emptied by remove(); add() belongs to the dense kind, put() and remove() to the keyed one (QadcError otherwise).
+    dtype="sq8" (qadc_refine_create_sq8; section 11.20): one byte per component under the range vmin=, step= (float32 [dim] each, as
+    refine_sq_range gives them); from_vectors() finds the range, creates and adds in one call."""
 
-    def __init__(self, dim, dtype="f32", device=0, keyed=False):
+    def __init__(self, dim, dtype="f32", device=0, keyed=False, vmin=None, step=None):
         if dtype not in _REFINE_DTYPES:
-            raise ValueError('dtype is "f32" or "f16", not %r' % (dtype,))
+            raise ValueError('dtype is "f32", "f16" or "sq8", not %r' % (dtype,))
         self.dim, self.dtype, self.device, self.keyed = int(dim), dtype, device, bool(keyed)
         self._h = C.c_void_p()
+        if dtype == "sq8":
+            if vmin is None or step is None:
+                raise ValueError('dtype "sq8" needs vmin= and step= (refine_sq_range)')
+            vmin, step = np.ascontiguousarray(vmin, np.float32).reshape(-1), np.ascontiguousarray(step, np.float32).reshape(-1)
+            if vmin.shape[0] != self.dim or step.shape[0] != self.dim:
+                raise ValueError("vmin and step have %d and %d entries for dim %d" % (vmin.shape[0], step.shape[0], self.dim))
+            _check(lib().qadc_refine_create_sq8(C.byref(self._h), self.dim, _p(vmin, f32p), _p(step, f32p), int(self.keyed), device))
+            return
+        if vmin is not None or step is not None:
+            raise ValueError('vmin= and step= belong to dtype "sq8"')
         create = lib().qadc_refine_create_keyed if keyed else lib().qadc_refine_create
         _check(create(C.byref(self._h), int(dim), _REFINE_DTYPES[dtype], device))
+
+    @classmethod
+    def from_vectors(cls, vectors, dtype="f32", device=0, first_key=0):
+        """A dense store holding vectors [n][dim] under the keys first_key ..; an "sq8" store takes the range of these vectors"""
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim != 2:
+            raise QadcError("vectors has shape %s, expected [n][dim]" % (v.shape,))
+        if dtype == "sq8":
+            vmin, step = refine_sq_range(v, device)
+            self = cls(v.shape[1], "sq8", device, vmin=vmin, step=step)
+        else:
+            self = cls(v.shape[1], dtype, device)
+        if v.shape[0]:
+            self.add(v, first_key)
+        return self
+
+    def sq_info(self):
+        """qadc_refine_sq_info -> dict(vmin float32 [dim], step float32 [dim], clamped: components written outside the range)"""
+        vmin, step, clamped = np.zeros(self.dim, np.float32), np.zeros(self.dim, np.float32), C.c_uint64(0)
+        _check(lib().qadc_refine_sq_info(self._h, _p(vmin, f32p), _p(step, f32p), C.byref(clamped)))
+        return dict(vmin=vmin, step=step, clamped=int(clamped.value))
+
+    def get(self, keys):
+        """keys uint32 [n] -> (vectors float32 [n][dim], found bool [n]): the rows as floats, decoded by the store's type; a key the
+        store does not hold gives a row of NaN (0x7FC00000) and found False"""
+        k = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(-1))
+        out, found = np.zeros((k.shape[0], self.dim), np.float32), np.zeros(k.shape[0], np.uint8)
+        _check(lib().qadc_refine_get(self._h, _p(k, u32p), k.shape[0], _p(out, f32p), _p(found, C.POINTER(C.c_uint8))))
+        return out, found.astype(bool)
+
+    def get_device(self, keys, out=None):
+        """get() for an int32 torch tensor [n] of the store's device that carries the keys' uint32 bits -> (vectors float32 [n][dim],
+        found uint8 [n]) on that device.  out: the two tensors to write into."""
+        import torch
+        if getattr(keys, "ndim", 0) != 1:
+            raise TypeError("keys must be a 1-d torch.Tensor")
+        n = int(keys.shape[0])
+        k = self._tensor(keys, "int32", (n,), "keys")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = (torch.zeros((n, self.dim), dtype=torch.float32, device=dev), torch.zeros((n,), dtype=torch.uint8, device=dev))
+        ov = self._tensor(out[0], "float32", (n, self.dim), "out vectors")
+        of = self._tensor(out[1], "uint8", (n,), "out found")
+        self._sync()
+        _check(lib().qadc_refine_get_device(self._h, k.data_ptr(), n, ov.data_ptr(), of.data_ptr()))
+        return ov, of
 
     # ---- the keyed kind ----
     def put(self, vectors, labels):
@@ -2343,10 +2436,10 @@ class Refine:
         _check(lib().qadc_refine_reserve(self._h, int(rows)))
 
     def info(self):
-        """-> dict(dim, dtype "f32" | "f16", lo, rows, bytes: the allocation's)"""
+        """-> dict(dim, dtype "f32" | "f16" | "sq8", lo, rows, bytes: the allocation's)"""
         dim, dtype, lo, rows, nbytes = C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
         _check(lib().qadc_refine_info(self._h, C.byref(dim), C.byref(dtype), C.byref(lo), C.byref(rows), C.byref(nbytes)))
-        return dict(dim=dim.value, dtype="f16" if dtype.value == QADC_REFINE_F16 else "f32", lo=int(lo.value), rows=int(rows.value),
+        return dict(dim=dim.value, dtype=_REFINE_DTYPE_NAMES[dtype.value], lo=int(lo.value), rows=int(rows.value),
                     bytes=int(nbytes.value))
 
     def relocations(self):

@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn,decode] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn,decode,refine_sq] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,opq,seed,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,seed,filter] [--iters N] [--out FILE]
 
@@ -73,6 +73,10 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             float L2 of search() alone and of search_refined_device with r_in = 400 and 1000 over a float and a half store; the time
             of search_refined_device split into search_device and rerank_device; beside it a plain torch gather + (q - x)^2 sum +
             topk on the same candidates, the only yardstick there is.
+  refine_sq SQ8 refine rows (not in the default legs), on the refine leg's shape, for f32, f16 and sq8 stores
+            in the same run: recall@100 of search_refined_device (r_in 400 and 1000), rerank_device ms on the same candidates (three
+            rounds of medians per store, taken in turn: the spread of the f16 figures is the yardstick's own), knn_device ms at 1024,
+            32 and 1 queries, add_device rows/s, sq_range_device ms, the store's bytes and the clamp count.
   keyed     caller-chosen labels (not in the default legs), on the ivf_search / refine shape: rerank_device on a
             keyed store against the dense store holding the same vectors, alternated, at the refine leg's r_in values; put_device and
             remove_device rows/s at 10^6 keys, fresh and overwriting; add_vectors_device(labels=...) against the plain call.
@@ -208,7 +212,7 @@ def search_legs(legs, iters, res):
     part_of, codes = pyqadc.adc_encode(codebooks, vectors, coarse)
     res["adc_encode_1e6_s"] = time.perf_counter() - t0
     print("adc_encode of 10^6 128-d vectors (K = 256, 8x8), host to host: %.2f s" % res["adc_encode_1e6_s"], flush=True)
-    if "refine" not in legs and "keyed" not in legs:
+    if "refine" not in legs and "keyed" not in legs and "refine_sq" not in legs:
         del vectors
     order = np.argsort(part_of, kind="stable")
     bounds = np.searchsorted(part_of[order], np.arange(K + 1))
@@ -251,7 +255,9 @@ def search_legs(legs, iters, res):
         refine_leg(idx, vectors, queries, ma, iters, res)
     if "keyed" in legs:
         keyed_leg(idx, vectors, queries, ma, iters, res, codebooks, coarse)
-    if "refine" in legs or "keyed" in legs:
+    if "refine_sq" in legs:
+        refine_sq_leg(idx, vectors, queries, ma, iters, res)
+    if "refine" in legs or "keyed" in legs or "refine_sq" in legs:
         del vectors
     if "filter" in legs:   # (b): the same search() without a filter and with 10 % of the keys excluded, in turn, under both finishes
         S = rng.permutation(n)[:n // 10].astype(np.uint32)
@@ -461,6 +467,80 @@ def refine_leg(idx, vectors, queries, ma, iters, res):
                   "gather + topk on the same candidates %.3f ms; %.0f MB gathered = %.2f TB/s in the rerank"
                   % (dtype, r_in, R, res[tag + "_recall"], t_search * 1e3, t_rerank * 1e3, t_both * 1e3, t_torch * 1e3,
                      res[tag + "_gather_bytes"] / 1e6, res[tag + "_gather_bytes"] / t_rerank / 1e12), flush=True)
+        st.close()
+
+
+def refine_sq_leg(idx, vectors, queries, ma, iters, res):
+    """SQ8 refine rows beside float and half rows in one run: recall, rerank and knn time, fill rate, bytes"""
+    import torch
+    dev = torch.device("cuda", 0)
+    n, dim = vectors.shape
+    nq = len(queries)
+    tq = torch.from_numpy(queries).to(dev)
+    tx = torch.from_numpy(vectors).to(dev)
+    best_d = torch.full((nq, R), float("inf"), device=dev)
+    best_k = torch.zeros((nq, R), dtype=torch.int64, device=dev)
+    for first in range(0, n, 1 << 17):                                          # ground truth as in refine_leg: float L2
+        x = tx[first:first + (1 << 17)]
+        d = (x * x).sum(1)[None, :] - 2.0 * (tq @ x.T)
+        cd, ck = torch.cat([best_d, d], 1).topk(R, dim=1, largest=False)
+        best_k = torch.cat([best_k, torch.arange(first, first + len(x), device=dev).expand(nq, -1)], 1).gather(1, ck)
+        best_d = cd
+    truth = best_k.cpu().numpy()
+
+    def recall(keys):
+        return float(np.mean([len(set(truth[q].tolist()) & set(np.asarray(keys[q]).tolist())) for q in range(nq)])) / R
+
+    t_range, _ = timed(lambda: pyqadc.refine_sq_range_device(tx), max(5, iters))
+    vmin, step = pyqadc.refine_sq_range_device(tx)
+    res["refine_sq_range_device_ms"] = t_range * 1e3
+    print("sq_range_device of %d x %d floats: %.3f ms = %.2f TB/s" % (n, dim, t_range * 1e3, n * dim * 4 / t_range / 1e12), flush=True)
+    dtypes = ("f32", "f16", "sq8")
+    stores = {}
+    for dtype in dtypes:
+        def fill():
+            st = pyqadc.Refine(dim, dtype, vmin=vmin, step=step) if dtype == "sq8" else pyqadc.Refine(dim, dtype)
+            st.reserve(n)
+            t0 = time.perf_counter()
+            st.add_device(tx)
+            return st, time.perf_counter() - t0
+        fill()[0].close()                                                       # warm-up
+        fills = [fill() for _ in range(3)]
+        for st, _ in fills[1:]:
+            st.close()
+        stores[dtype] = fills[0][0]
+        t_add = float(np.median([t for _, t in fills]))
+        res["refine_sq_%s_add_device_rows_per_s" % dtype] = n / t_add
+        res["refine_sq_%s_bytes" % dtype] = stores[dtype].info()["bytes"]
+        print("%s store: add_device of %d rows %.3f ms = %.1f M rows/s; %d bytes" % (dtype, n, t_add * 1e3, n / t_add / 1e6,
+                                                                                      stores[dtype].info()["bytes"]), flush=True)
+    res["refine_sq_clamped"] = stores["sq8"].sq_info()["clamped"]
+    print("sq8 store: %d of %d components clamped" % (res["refine_sq_clamped"], n * dim), flush=True)
+    for r_in in (400, 1000):
+        ck, cv, _ = idx.search_device(tq, ma, r_in)
+        for dtype in dtypes:
+            keys, _, _, missing = idx.search_refined_device(tq, ma, R, r_in, stores[dtype])
+            assert missing == 0
+            res["refine_sq_%s_rin%d_recall" % (dtype, r_in)] = recall(keys.cpu().numpy().view(np.uint32))
+        rounds = {d: [] for d in dtypes}
+        for _ in range(3):                                                      # rounds in turn: drift shows in every store alike
+            for dtype in dtypes:
+                rounds[dtype].append(timed(lambda: stores[dtype].rerank_device(tq, ck, R, values=cv), max(5, iters))[0] * 1e3)
+        for dtype in dtypes:
+            res["refine_sq_%s_rin%d_rerank_ms_rounds" % (dtype, r_in)] = rounds[dtype]
+            print("%s store, r_in %d: recall@%d %.4f; rerank_device %s ms" % (dtype, r_in, R, res["refine_sq_%s_rin%d_recall" % (dtype, r_in)],
+                                                                             ", ".join("%.3f" % t for t in rounds[dtype])), flush=True)
+    for n_q in (1024, 32, 1):
+        qs = tq[:n_q].contiguous()
+        rounds = {d: [] for d in dtypes}
+        for _ in range(3):
+            for dtype in dtypes:
+                rounds[dtype].append(timed(lambda: stores[dtype].knn_device(qs, R), max(5, iters))[0] * 1e3)
+        for dtype in dtypes:
+            res["refine_sq_%s_knn_device_nq%d_ms_rounds" % (dtype, n_q)] = rounds[dtype]
+        print("knn_device, %d queries over %d rows: %s" % (n_q, n, "; ".join("%s %s ms" % (d, ", ".join("%.3f" % t for t in rounds[d]))
+                                                                              for d in dtypes)), flush=True)
+    for st in stores.values():
         st.close()
 
 
@@ -1698,7 +1778,7 @@ def main():
                 f.write(line + "\n")
         return
     torch = None
-    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs or "decode" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs or "decode" in legs or "refine_sq" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:
             import torch
             torch.zeros(1, device="cuda")
@@ -1787,7 +1867,7 @@ def main():
             print("the same alternated with query_scan_device (tables and heaps stay in device memory): %.2f ms against %.2f ms"
                   % (med_d * 1e3, med_h * 1e3), flush=True)
         idx.close()
-    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs or "range" in legs or "keyed" in legs:
+    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs or "range" in legs or "keyed" in legs or "refine_sq" in legs:
         search_legs(legs, a.iters, res)
     if "filter" in legs:
         filter_leg(8, a.iters, res, torch)

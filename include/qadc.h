@@ -1543,6 +1543,60 @@ int qadc_refine_get(qadc_refine* r, const uint32_t* keys, uint64_t count, float*
  * d_keys and d_out_vectors are checked for 4-byte alignment first. */
 int qadc_refine_get_device(qadc_refine* r, const uint32_t* d_keys, uint64_t count, float* d_out_vectors, uint8_t* d_found_out);
 
+/* ---- exact range search: every row within an exact radius; range results re-ranked by L2 ----
+ * The other query of a refine store, dense or keyed, F32, F16 or SQ8.  A row is KEPT for query q where its key is held by the store,
+ * passes the filter (qadc_adc_filter's rule, as in qadc_refine_knn) and D(q, x) < radius[q] as a binary32 compare, D exactly the
+ * distance above.  A NaN distance or a NaN radius keeps nothing; a radius <= 0 of either sign keeps nothing (D is +0, positive or NaN);
+ * a distance equal to the radius is not kept; radius +inf keeps every finite distance and no +inf one.  Query q's kept rows are ordered
+ * ascending by the 64-bit word (bits(D) << 32) | key.  There is no R, no heap and no cap on a query's rows.  The written definition is
+ * refine::range and refine::rerank_range of quick-adc_amd/host/refine.hpp, to which keys, the distances' bit patterns, lims and the
+ * missing count are held bit for bit; the result is a function of the store's contents and the arguments alone: no region size,
+ * chunk, pass, rerun or arrival order shows in it.
+ *   radius [nq], lims [nq + 1], in_lims [nq + 1]   HOST memory in every form.
+ *   lims                                           out: query q's rows are [lims[q], lims[q + 1]) of the held result; lims[nq] = its rows.
+ * The result stays ON THE STORE, in device memory no other call writes, until the next qadc_refine_range* or _rerank_range* call (which
+ * drops it, also when it fails) or qadc_refine_destroy; qadc_refine_range_collect* copies it out, any number of times, and add, put,
+ * remove, rerank, knn and get calls in between leave it as it is.  Every call is synchronous on the store's stream.  A pass of the
+ * exhaustive form runs once with a region of min(rows, 4096) words per query and, where a region overflowed, a second time with regions
+ * of exactly the counted sizes (counted in qadc_refine_range_reruns).  nq = 0 is a no-op that holds an empty result (lims[0] = 0 where
+ * lims is given); an empty store gives all-zero lims.
+ * QADC_E_ARG before the device is touched: r NULL, nq < 0, a required array NULL with nq > 0, a filter of another device, a device
+ * array that is not 4-byte aligned, an in_lims that does not start at 0 or decreases.  QADC_E_CAPACITY before anything is allocated for
+ * them: the regions of one run of a pass, the candidates of one query, or the rows of the call's whole result exceed
+ * QADC_REFINE_RANGE_MAX_ENTRIES.
+ * Limits: every row is read, whatever the filter and the radius; the held result and a pass's regions are resident in device memory;
+ * a query that keeps more than QADC_REFINE_RANGE_SORT_LDS rows pays the radix passes; L2 only; one device; one filter per call;
+ * synchronous. */
+#define QADC_REFINE_RANGE_MAX_ENTRIES (1ull << 31) /* most words the regions of one run, and most rows a call's result, may hold */
+#define QADC_REFINE_RANGE_SORT_LDS 4096            /* a query's words up to this many are sorted in LDS, more by radix passes */
+/* Exhaustive, host arrays: queries [nq][dim] -> the kept rows of the whole store.  filter may be NULL. */
+int qadc_refine_range(qadc_refine* r, int nq, const float* queries, const float* radius, const qadc_adc_filter* filter, uint64_t* lims);
+/* The same with d_queries in device memory of the store's device (see qadc_refine_add_device), complete before the call and touched
+ * only by kernels. */
+int qadc_refine_range_device(qadc_refine* r, int nq, const float* d_queries, const float* radius, const qadc_adc_filter* filter,
+                             uint64_t* lims);
+/* The same rule restricted to the candidates keys[in_lims[q] .. in_lims[q + 1]) of query q — the CSR result of a range search of an
+ * index, for instance — with no limit on their number.  A key the store does not hold is missing: dropped and counted in *missing_out
+ * (may be NULL); a keyed store never holds key 0xFFFFFFFF; a key listed several times is kept once.  keys is host memory [in_lims[nq]]. */
+int qadc_refine_rerank_range(qadc_refine* r, int nq, const float* queries, const uint64_t* in_lims, const uint32_t* keys, const float* radius,
+                             uint64_t* lims, uint64_t* missing_out);
+/* The same with d_queries and d_keys in device memory of the store's device, as qadc_adc_range_collect_device writes the keys; both
+ * are touched only by kernels.  Only in_lims, lims and the missing count cross the bus. */
+int qadc_refine_rerank_range_device(qadc_refine* r, int nq, const float* d_queries, const uint64_t* in_lims, const uint32_t* d_keys,
+                                    const float* radius, uint64_t* lims, uint64_t* missing_out);
+/* Copies the held result into keys / dist [capacity] (host memory).  QADC_E_CAPACITY when capacity < lims[nq]: nothing is copied and
+ * the result stays held.  QADC_E_STATE when no result is held. */
+int qadc_refine_range_collect(qadc_refine* r, uint64_t capacity, uint32_t* keys, float* dist);
+/* The same into device memory, copied by a kernel (the buffers may belong to another copy of the HIP runtime): exactly lims[nq]
+ * entries of each are written. */
+int qadc_refine_range_collect_device(qadc_refine* r, uint64_t capacity, uint32_t* d_keys, float* d_dist);
+/* A tuning and test knob of the later range calls: the words of a query's region in the first run, the rows of a group per launch
+ * (at most 2^24) and the queries per pass (also of rerank_range); 0 = the plan's default (quick-adc_amd/host/refine_range_plan.hpp).
+ * No value changes a result.  QADC_E_ARG: r NULL, chunk_rows above 2^24, a negative pass_nq. */
+int qadc_refine_set_range_plan(qadc_refine* r, uint64_t region_rows, uint64_t chunk_rows, int pass_nq);
+/* Passes that were run a second time because a region overflowed. */
+uint64_t qadc_refine_range_reruns(const qadc_refine* r);
+
 #ifdef __cplusplus
 }
 #endif

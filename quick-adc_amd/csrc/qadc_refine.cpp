@@ -4,7 +4,9 @@
 // (qadc_device_prepare): it consumes uint32 keys, whoever produced them.  The definition it is held to is host/refine.hpp, the
 // launch geometry host/refine_plan.hpp, the kernels csrc/qadc_refine_kernel.hip.  qadc_refine_knn is the
 // exhaustive form of the same call, every held key of the store against a batch of queries: geometry host/refine_knn_plan.hpp,
-// kernels csrc/qadc_refine_knn_kernel.hip.
+// kernels csrc/qadc_refine_knn_kernel.hip.  qadc_refine_range and qadc_refine_rerank_range are the radius
+// query over the same rows — every row, or the candidates of a range result — whose result stays on the store until it is collected:
+// geometry host/refine_range_plan.hpp, kernels csrc/qadc_refine_range_kernel.hip.
 //
 // Every array of the *_device calls is read and written by kernels only, so memory of another HIP runtime (torch tensors) is
 // legal; for the same reason the library cannot ask which device such a pointer lives on, and does not: as for
@@ -29,6 +31,8 @@ using qadc::host::DeviceGuard;
 static_assert(QADC_REFINE_MAX_IN == qadc::refine::kRefinePlanMaxIn && QADC_REFINE_MAX_IN == qadc::refine::kMaxIn, "one limit on r_in");
 static_assert(QADC_REFINE_MAX_DIM == qadc::refine::kRefinePlanMaxDim && QADC_REFINE_MAX_DIM == qadc::refine::kMaxDim, "one limit on dim");
 static_assert(QADC_REFINE_KNN_MAX_R == qadc::refine::kKnnMaxR, "one limit on the R of knn");
+static_assert(QADC_REFINE_RANGE_MAX_ENTRIES == qadc::refine::kRangeMaxEntries, "one limit on the words of a range pass");
+static_assert(QADC_REFINE_RANGE_SORT_LDS == qadc::refine::kRangeSortLds, "include/qadc.h names the LDS threshold of refine_range_sort_kernel");
 static_assert(QADC_ADC_FILTER_EXCLUDE == qadc::adc::kFilterExclude && QADC_ADC_FILTER_ALLOW == qadc::adc::kFilterAllow &&
                   QADC_ADC_FILTER_EXCLUDE == qadc::refine::kFilterExclude && QADC_ADC_FILTER_ALLOW == qadc::refine::kFilterAllow,
               "the filter modes of the scan, of knn and of its twin");
@@ -70,6 +74,17 @@ struct qadc_refine {
     int knn_pass_nq = 0;
     DevBuf<uint64_t> d_knn_buf, d_knn_bound;        // [pass_nq][groups][buf_cap] / [pass_nq][groups]
     DevBuf<uint32_t> d_knn_cnt;                     // [pass_nq][groups]
+    // exact range search (qadc_refine_range*): the plan's knobs (0: its default), the held result in buffers
+    // no other call writes, and the scratch of a pass
+    uint64_t range_region_rows = 0, range_chunk_rows = 0, range_reruns = 0;
+    int range_pass_nq = 0;
+    std::vector<uint64_t> range_lims;               // [nq + 1] of the last range call; empty: nothing to collect
+    DevBuf<uint32_t> d_rkeys;                       // the held rows' keys
+    DevBuf<float> d_rdist;                          // ... and distances
+    DevBuf<uint64_t> d_rbuf, d_rtmp;                // the regions of a pass and the radix passes' scratch
+    DevBuf<uint64_t> d_rmeta;                       // [5][pass_nq]: limit, base, cap, counters, output offsets
+    DevBuf<uint32_t> d_rkept;                       // [pass_nq]
+    DevBuf<qadc::refine::RangeChunk> d_rchunks;     // the chunk table of a candidate pass
     qadc::refine::Elem elem_type() const { return (qadc::refine::Elem)dtype; }
     size_t elem() const { return qadc::refine::elem_bytes(elem_type()); }
     size_t row_bytes() const { return (size_t)dim * elem(); }
@@ -567,9 +582,305 @@ int check_sq_range(const float* vectors, uint64_t n, int dim, const float* vmin_
     return QADC_OK;
 }
 
+// ---- exact range search ----
+
+RangeStore range_store(const qadc_refine* r, bool candidates) {
+    RangeStore s{};
+    s.rows = r->data;
+    s.elem = r->elem_type();
+    s.sq = r->sq();
+    s.dim = r->dim;
+    s.lo = r->lo;
+    s.nrows = r->rows;
+    s.row_key = r->keyed && !candidates ? r->row_key : nullptr;
+    s.tkey = r->keyed && candidates ? r->table.key : nullptr;
+    s.trow = r->table.row;
+    s.tbits = r->table.bits;
+    return s;
+}
+
+// room for `need` held rows, the first `held` kept: 1.5 x the allocation or `need`, one device-to-device copy each
+template <typename T>
+int grow_held(qadc_refine* r, DevBuf<T>& b, uint64_t held, uint64_t need) {
+    if (need <= b.cap) return QADC_OK;
+    DevBuf<T> n;
+    HIPCHECK(n.ensure((size_t)std::max<uint64_t>(need, b.cap + b.cap / 2)));
+    if (held) {
+        hipError_t e = hipMemcpyAsync(n.p, b.p, (size_t)held * sizeof(T), hipMemcpyDeviceToDevice, r->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+        if (e != hipSuccess) {
+            n.release();
+            return fail(QADC_E_HIP, std::string("moving the held rows: ") + hipGetErrorString(e));
+        }
+    }
+    b.release();
+    b = n;
+    return QADC_OK;
+}
+
+// The five arrays of a pass's meta block, host side and device side
+struct RangeMeta {
+    std::vector<uint64_t> h;       // [5][n]
+    int n = 0;
+    uint64_t* limit() { return h.data(); }
+    uint64_t* base() { return h.data() + n; }
+    uint64_t* cap() { return h.data() + 2 * (size_t)n; }
+    uint64_t* cnt() { return h.data() + 3 * (size_t)n; }
+    uint64_t* off() { return h.data() + 4 * (size_t)n; }
+};
+
+RangeRegions range_regions_of(qadc_refine* r, int n) {
+    RangeRegions g{};
+    g.nq = n;
+    uint64_t* m = r->d_rmeta.p;
+    g.limit = m;
+    g.base = m + n;
+    g.cap = m + 2 * (size_t)n;
+    g.cnt = reinterpret_cast<unsigned long long*>(m + 3 * (size_t)n);
+    g.buf = r->d_rbuf.p;
+    g.tmp = r->d_rtmp.p;
+    return g;
+}
+
+// The end of a pass, both forms: the regions sorted, the survivors counted, summed into lims and written behind the held rows.
+int range_finish_pass(qadc_refine* r, RangeMeta& m, uint64_t entries, std::vector<uint64_t>& lims) {
+    const int n = m.n;
+    uint64_t longest = 0;
+    for (int q = 0; q < n; ++q) longest = std::max(longest, std::min(m.cnt()[q], m.cap()[q]));
+    if (const uint64_t scratch = range_scratch_entries(entries, longest)) HIPCHECK(r->d_rtmp.ensure((size_t)scratch));
+    HIPCHECK(r->d_rkept.ensure((size_t)n));
+    const RangeRegions g = range_regions_of(r, n);
+    std::vector<uint32_t> kept((size_t)n);
+    HIPCHECK(launch_range_sort(g, r->d_rkept.p, r->stream));
+    HIPCHECK(hipMemcpyAsync(kept.data(), r->d_rkept.p, (size_t)n * 4, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    const uint64_t held = lims.back();
+    uint64_t at = held;
+    for (int q = 0; q < n; ++q) {
+        m.off()[q] = at;
+        at += kept[(size_t)q];
+        lims.push_back(at);
+    }
+    if (at == held) return QADC_OK;
+    if (!range_held_fits(held, at - held, kRangeMaxEntries))
+        return fail(QADC_E_CAPACITY, "the range result of this call exceeds QADC_REFINE_RANGE_MAX_ENTRIES rows");
+    if (int rc = grow_held(r, r->d_rkeys, held, at)) return rc;
+    if (int rc = grow_held(r, r->d_rdist, held, at)) return rc;
+    uint64_t* d_off = r->d_rmeta.p + 4 * (size_t)n;
+    HIPCHECK(hipMemcpyAsync(d_off, m.off(), (size_t)n * 8, hipMemcpyHostToDevice, r->stream));
+    HIPCHECK(launch_range_compact(g, d_off, r->d_rkeys.p, r->d_rdist.p, r->stream));
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    return QADC_OK;
+}
+
+// One pass of the exhaustive form over n queries in device memory: the first run with regions of plan.region_rows words, a second
+// with regions of exactly the counted sizes where one overflowed.
+int range_pass(qadc_refine* r, int n, const float* d_queries, const float* radius, const adc::ScanFilter& filter, const RangePlan& plan,
+               std::vector<uint64_t>& lims) {
+    RangeMeta m;
+    m.n = n;
+    m.h.assign(5 * (size_t)n, 0);
+    for (int q = 0; q < n; ++q) {
+        m.limit()[q] = range_limit_word(radius[q]);
+        m.cap()[q] = plan.region_rows;
+    }
+    const RangeStore s = range_store(r, false);
+    uint64_t entries = 0;
+    for (int attempt = 0;; ++attempt) {
+        if (!range_regions(m.cap(), n, kRangeMaxEntries, m.base(), &entries))   // (before anything is allocated for the run)
+            return fail(QADC_E_CAPACITY, "the regions of a range pass exceed QADC_REFINE_RANGE_MAX_ENTRIES words (a smaller radius, or fewer queries per "
+                                         "pass: qadc_refine_set_range_plan)");
+        HIPCHECK(r->d_rmeta.ensure(5 * (size_t)n));
+        HIPCHECK(r->d_rbuf.ensure((size_t)entries));
+        std::fill(m.cnt(), m.cnt() + n, 0);
+        HIPCHECK(hipMemcpyAsync(r->d_rmeta.p, m.h.data(), 4 * (size_t)n * 8, hipMemcpyHostToDevice, r->stream));   // limit, base, cap, zeroed counters
+        const RangeRegions g = range_regions_of(r, n);
+        for (uint64_t l = 0; l < plan.launches; ++l) HIPCHECK(launch_range_dist(s, filter, d_queries, g, plan, l, r->stream));
+        HIPCHECK(hipMemcpyAsync(m.cnt(), g.cnt, (size_t)n * 8, hipMemcpyDeviceToHost, r->stream));
+        HIPCHECK(hipStreamSynchronize(r->stream));
+        if (!range_rerun(m.cap(), m.cnt(), n)) break;
+        if (attempt) return fail(QADC_E_STATE, "a range pass kept more rows in its second run than its first run counted");
+        ++r->range_reruns;
+    }
+    return range_finish_pass(r, m, entries, lims);
+}
+
+int check_range(const qadc_refine* r, int nq, const void* queries, const float* radius, const uint64_t* lims, const qadc_adc_filter* filter,
+                adc::ScanFilter* scan) {
+    if (const char* why = range_refusal(r != nullptr, nq, queries != nullptr, radius != nullptr, lims != nullptr)) return fail(QADC_E_ARG, why);
+    int fdev = -1;
+    adc_filter_view(filter, scan, &fdev);
+    if (filter && fdev != r->device)
+        return fail(QADC_E_ARG, "the filter is on device " + std::to_string(fdev) + " and the store on device " + std::to_string(r->device));
+    return QADC_OK;
+}
+
+// Closes a range call: the result is held and its row offsets go to the caller.
+int publish_range(qadc_refine* r, std::vector<uint64_t>& lims, uint64_t* out) {
+    if (out) std::copy(lims.begin(), lims.end(), out);
+    r->range_lims.swap(lims);
+    return QADC_OK;
+}
+
+// The passes of the exhaustive form on queries in device memory
+int range_call(qadc_refine* r, int nq, const float* d_queries, const float* radius, const adc::ScanFilter& filter, uint64_t* lims_out) {
+    std::vector<uint64_t> lims(1, 0);
+    const uint64_t walk = r->keyed ? (r->live ? r->rows : 0) : r->rows;   // (a keyed store walks the rows allocated so far)
+    if (nq == 0 || walk == 0) {
+        lims.resize((size_t)nq + 1, 0);
+        return publish_range(r, lims, lims_out);
+    }
+    RangePlan plan;
+    if (!range_plan(nq, walk, r->dim, r->range_region_rows, r->range_chunk_rows, r->range_pass_nq, &plan))
+        return fail(QADC_E_ARG, "no launch geometry for this call");
+    for (int q0 = 0; q0 < nq; q0 += plan.pass_nq) {
+        const int n = std::min(plan.pass_nq, nq - q0);
+        if (int rc = range_pass(r, n, d_queries + (size_t)q0 * r->dim, radius + q0, filter, plan, lims)) return rc;
+    }
+    return publish_range(r, lims, lims_out);
+}
+
+// The passes of the candidate form on queries and keys in device memory; in_lims is host memory
+int rerank_range_call(qadc_refine* r, int nq, const float* d_queries, const uint64_t* in_lims, const uint32_t* d_keys, const float* radius,
+                      uint64_t* lims_out, uint64_t* missing_out) {
+    std::vector<uint64_t> lims(1, 0);
+    if (nq == 0) return publish_range(r, lims, lims_out);
+    std::vector<RangeCandPass> passes;
+    if (!range_cand_passes(in_lims, nq, r->range_pass_nq, kRangeMaxEntries, &passes))
+        return fail(QADC_E_CAPACITY, "one query has more than QADC_REFINE_RANGE_MAX_ENTRIES candidates");
+    HIPCHECK(r->d_missing.ensure(1));
+    HIPCHECK(hipMemsetAsync(r->d_missing.p, 0, sizeof(unsigned long long), r->stream));
+    const RangeStore s = range_store(r, true);
+    std::vector<RangeChunk> chunks;
+    for (const RangeCandPass& ps : passes) {
+        const int n = ps.q1 - ps.q0;
+        const uint64_t first = in_lims[ps.q0], entries = in_lims[ps.q1] - first;
+        RangeMeta m;
+        m.n = n;
+        m.h.assign(5 * (size_t)n, 0);
+        for (int q = 0; q < n; ++q) {
+            m.limit()[q] = range_limit_word(radius[ps.q0 + q]);
+            m.base()[q] = in_lims[ps.q0 + q] - first;
+            m.cap()[q] = m.cnt()[q] = in_lims[ps.q0 + q + 1] - in_lims[ps.q0 + q];
+        }
+        range_cand_chunks(in_lims, ps.q0, ps.q1, range_cands_per_wg(in_lims, ps.q0, ps.q1), &chunks);
+        HIPCHECK(r->d_rmeta.ensure(5 * (size_t)n));
+        HIPCHECK(r->d_rbuf.ensure((size_t)entries));
+        HIPCHECK(r->d_rchunks.ensure(chunks.size()));
+        HIPCHECK(hipMemcpyAsync(r->d_rmeta.p, m.h.data(), 4 * (size_t)n * 8, hipMemcpyHostToDevice, r->stream));
+        if (!chunks.empty())
+            HIPCHECK(hipMemcpyAsync(r->d_rchunks.p, chunks.data(), chunks.size() * sizeof(RangeChunk), hipMemcpyHostToDevice, r->stream));
+        const RangeRegions g = range_regions_of(r, n);
+        HIPCHECK(launch_range_cand(s, d_queries + (size_t)ps.q0 * r->dim, d_keys + first, r->d_rchunks.p, (uint32_t)chunks.size(), g, r->d_missing.p,
+                                   r->stream));
+        HIPCHECK(hipStreamSynchronize(r->stream));   // (the chunk table and the meta block leave with this iteration)
+        if (int rc = range_finish_pass(r, m, entries, lims)) return rc;
+    }
+    unsigned long long missing = 0;
+    HIPCHECK(hipMemcpyAsync(&missing, r->d_missing.p, sizeof(missing), hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    if (missing_out) *missing_out = missing;
+    return publish_range(r, lims, lims_out);
+}
+
+// The held result into the caller's buffers: host memory by copies, device memory by a kernel (launch_adc_copy_words).
+int range_collect(qadc_refine* r, uint64_t capacity, uint32_t* keys, float* dist, bool d_side) {
+    if (!r) return fail(QADC_E_ARG, "store is null");
+    if (r->range_lims.empty()) return fail(QADC_E_STATE, "no range result is held: call qadc_refine_range* or qadc_refine_rerank_range* first");
+    const uint64_t n = r->range_lims.back();
+    if (capacity < n)
+        return fail(QADC_E_CAPACITY, "the range result has " + std::to_string(n) + " rows (lims[nq]); the buffers hold " + std::to_string(capacity));
+    if (n == 0) return QADC_OK;
+    if (!keys || !dist) return fail(QADC_E_ARG, "keys and dist are required");
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    if (d_side) {
+        HIPCHECK(adc::launch_adc_copy_words(r->d_rkeys.p, keys, (size_t)n, r->stream));
+        HIPCHECK(adc::launch_adc_copy_words(r->d_rdist.p, dist, (size_t)n, r->stream));
+    } else {
+        HIPCHECK(hipMemcpyAsync(keys, r->d_rkeys.p, (size_t)n * 4, hipMemcpyDeviceToHost, r->stream));
+        HIPCHECK(hipMemcpyAsync(dist, r->d_rdist.p, (size_t)n * 4, hipMemcpyDeviceToHost, r->stream));
+    }
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    return QADC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int qadc_refine_range(qadc_refine* r, int nq, const float* queries, const float* radius, const qadc_adc_filter* filter, uint64_t* lims) {
+    if (r) r->range_lims.clear();   // (the held result is dropped, also when this call fails)
+    adc::ScanFilter scan;
+    if (int rc = check_range(r, nq, queries, radius, lims, filter, &scan)) return rc;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    if (nq) {
+        HIPCHECK(r->d_queries.ensure((size_t)nq * r->dim));
+        HIPCHECK(hipMemcpyAsync(r->d_queries.p, queries, (size_t)nq * r->dim * 4, hipMemcpyHostToDevice, r->stream));
+    }
+    return range_call(r, nq, r->d_queries.p, radius, scan, lims);
+}
+
+int qadc_refine_range_device(qadc_refine* r, int nq, const float* d_queries, const float* radius, const qadc_adc_filter* filter, uint64_t* lims) {
+    if (r) r->range_lims.clear();
+    if (int rc = check_aligned(d_queries, 4, "d_queries")) return rc;
+    adc::ScanFilter scan;
+    if (int rc = check_range(r, nq, d_queries, radius, lims, filter, &scan)) return rc;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    return range_call(r, nq, d_queries, radius, scan, lims);
+}
+
+int qadc_refine_rerank_range(qadc_refine* r, int nq, const float* queries, const uint64_t* in_lims, const uint32_t* keys, const float* radius,
+                             uint64_t* lims, uint64_t* missing_out) {
+    if (r) r->range_lims.clear();
+    if (missing_out) *missing_out = 0;
+    if (const char* why = rerank_range_refusal(r != nullptr, nq, queries != nullptr, in_lims, keys != nullptr, radius != nullptr, lims != nullptr))
+        return fail(QADC_E_ARG, why);
+    const std::vector<uint64_t> in(in_lims ? in_lims : lims, (in_lims ? in_lims : lims) + (nq ? nq + 1 : 0));   // (lims may be in_lims itself)
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    if (nq) {
+        HIPCHECK(r->d_queries.ensure((size_t)nq * r->dim));
+        HIPCHECK(hipMemcpyAsync(r->d_queries.p, queries, (size_t)nq * r->dim * 4, hipMemcpyHostToDevice, r->stream));
+        HIPCHECK(r->d_keys.ensure((size_t)in[nq]));
+        if (in[nq]) HIPCHECK(hipMemcpyAsync(r->d_keys.p, keys, (size_t)in[nq] * 4, hipMemcpyHostToDevice, r->stream));
+    }
+    return rerank_range_call(r, nq, r->d_queries.p, in.data(), r->d_keys.p, radius, lims, missing_out);
+}
+
+int qadc_refine_rerank_range_device(qadc_refine* r, int nq, const float* d_queries, const uint64_t* in_lims, const uint32_t* d_keys,
+                                    const float* radius, uint64_t* lims, uint64_t* missing_out) {
+    if (r) r->range_lims.clear();
+    if (missing_out) *missing_out = 0;
+    if (int rc = check_aligned(d_queries, 4, "d_queries")) return rc;
+    if (int rc = check_aligned(d_keys, 4, "d_keys")) return rc;
+    if (const char* why = rerank_range_refusal(r != nullptr, nq, d_queries != nullptr, in_lims, d_keys != nullptr, radius != nullptr, lims != nullptr))
+        return fail(QADC_E_ARG, why);
+    const std::vector<uint64_t> in(in_lims ? in_lims : lims, (in_lims ? in_lims : lims) + (nq ? nq + 1 : 0));
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    return rerank_range_call(r, nq, d_queries, in.data(), d_keys, radius, lims, missing_out);
+}
+
+int qadc_refine_range_collect(qadc_refine* r, uint64_t capacity, uint32_t* keys, float* dist) { return range_collect(r, capacity, keys, dist, false); }
+
+int qadc_refine_range_collect_device(qadc_refine* r, uint64_t capacity, uint32_t* d_keys, float* d_dist) {
+    if (int rc = check_aligned(d_keys, 4, "d_keys")) return rc;
+    if (int rc = check_aligned(d_dist, 4, "d_dist")) return rc;
+    return range_collect(r, capacity, d_keys, d_dist, true);
+}
+
+int qadc_refine_set_range_plan(qadc_refine* r, uint64_t region_rows, uint64_t chunk_rows, int pass_nq) {
+    if (const char* why = range_plan_refusal(r != nullptr, chunk_rows, pass_nq)) return fail(QADC_E_ARG, why);
+    r->range_region_rows = region_rows;
+    r->range_chunk_rows = chunk_rows;
+    r->range_pass_nq = pass_nq;
+    return QADC_OK;
+}
+
+uint64_t qadc_refine_range_reruns(const qadc_refine* r) { return r ? r->range_reruns : 0; }
 
 int qadc_refine_create_sq8(qadc_refine** out, int dim, const float* vmin, const float* step, int keyed, int device_id) {
     if (out) *out = nullptr;
@@ -688,6 +999,8 @@ int qadc_refine_destroy(qadc_refine* r) {
     r->d_stage.release(); r->d_words.release(); r->d_missing.release(); r->d_queries.release(); r->d_values.release();
     r->d_out_dist.release(); r->d_keys.release(); r->d_out_keys.release(); r->d_counts.release(); r->d_out_sizes.release();
     r->d_knn_buf.release(); r->d_knn_bound.release(); r->d_knn_cnt.release();
+    r->d_rkeys.release(); r->d_rdist.release(); r->d_rbuf.release(); r->d_rtmp.release(); r->d_rmeta.release(); r->d_rkept.release();
+    r->d_rchunks.release();
     delete r;
     return QADC_OK;
 }

@@ -7,6 +7,7 @@
 #include "../host/refine_keyed_plan.hpp"
 #include "../host/refine_knn_plan.hpp"
 #include "../host/refine_plan.hpp"
+#include "../host/refine_range_plan.hpp"
 #include "qadc_adc_kernels.h"   // ScanFilter
 
 namespace qadc {
@@ -128,6 +129,48 @@ hipError_t launch_knn_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launc
 hipError_t launch_knn_select(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream);
 // refine_knn_final_kernel: the groups' lists merged: the first R words, the fillers behind them and the size of every query
 hipError_t launch_knn_final(const KnnPass& p, const KnnPlan& plan, hipStream_t stream);
+
+// ---- exact range search (qadc_refine_range, qadc_refine_rerank_range; kernels:
+// csrc/qadc_refine_range_kernel.hip; geometry: host/refine_range_plan.hpp).  Every pointer is device memory touched by kernels only. ----
+
+// The regions of a pass of nq queries: query q's words are buf[base[q] .. base[q] + min(cnt[q], cap[q])).
+struct RangeRegions {
+    int nq;
+    const uint64_t* limit;         // [nq] a word is kept where it is below limit[q] (range_limit_word; 0: nothing)
+    const uint64_t* base;          // [nq]
+    const uint64_t* cap;           // [nq]
+    unsigned long long* cnt;       // [nq] words appended, counted also beyond cap[q] (exhaustive form: zero before the first launch;
+                                   //      candidate form: the segment sizes)
+    uint64_t* buf;                 // the words
+    uint64_t* tmp;                 // scratch of the radix passes, as large as buf (may be null where no region exceeds kRangeSortLds)
+};
+
+// The store a range kernel reads
+struct RangeStore {
+    const void* rows;
+    Elem elem;
+    SqParams sq;
+    int dim;
+    uint32_t lo;
+    uint64_t nrows;
+    const uint32_t* row_key;       // a keyed store, exhaustive form: a row's key (0xFFFFFFFF: free); else null
+    const uint32_t* tkey;          // a keyed store, candidate form: the table
+    const uint32_t* trow;
+    int tbits;
+};
+
+// refine_range_dist_kernel<Row, QT, J>: the words of launch `launch`'s rows that are below their query's limit, appended to its region
+hipError_t launch_range_dist(const RangeStore& s, const adc::ScanFilter& filter, const float* queries, const RangeRegions& g,
+                             const RangePlan& plan, uint64_t launch, hipStream_t stream);
+// refine_range_cand_kernel<Row, Lookup>: word i of the pass = the word of candidate keys[i] where its key is held and the word is
+// below its query's limit, else ~0; *missing += the candidates whose key is not held.  chunks: the pass's chunk table [nchunks].
+hipError_t launch_range_cand(const RangeStore& s, const float* queries, const uint32_t* keys, const RangeChunk* chunks, uint32_t nchunks,
+                             const RangeRegions& g, unsigned long long* missing, hipStream_t stream);
+// refine_range_sort_kernel: every region sorted ascending where it lies; kept[q] = its words that are not ~0 and differ from the
+// word before them
+hipError_t launch_range_sort(const RangeRegions& g, uint32_t* kept, hipStream_t stream);
+// refine_range_compact_kernel: the kept[q] survivors of query q to out_keys / out_dist [out_off[q] ..)
+hipError_t launch_range_compact(const RangeRegions& g, const uint64_t* out_off, uint32_t* out_keys, float* out_dist, hipStream_t stream);
 
 }  // namespace refine
 }  // namespace qadc

@@ -22,7 +22,8 @@
 // set_query_filters(per_query): one filter per query of the caller's query array on top of it (qadc_adc_search_filtered,
 // qadc_adc_search_candidates_filtered).
 // range_search(...): every row below a radius per query instead of the R best, under the same filters (qadc_adc_range_search;
-// DESIGN.md section 11.13).
+// DESIGN.md section 11.13).  range_search_refined(engine, store, ...) of host/refine_hip.hpp hands its rows to a refine store's
+// rerank_range: the rows of the ADC result within an exact radius (section 11.21).
 #pragma once
 #include <algorithm>
 #include <cstdint>

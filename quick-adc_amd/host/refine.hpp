@@ -19,6 +19,9 @@
 // Exhaustive search (knn, at the end): the selection above over every key the store holds that passes a
 // key filter — the definition of qadc_refine_knn.
 //
+// Exact range search (range and rerank_range, at the end): every held key whose distance is below a radius,
+// over the whole store or over candidate lists of any length — the definition of qadc_refine_range and qadc_refine_rerank_range.
+//
 // SQ8 rows (kSQ8): one byte per component under a per-dimension affine range, vmin[dim] and step[dim], both
 // finite, step >= 0; inv[i] = 1.0f / step[i] where step[i] > 0 (+inf for a subnormal step), else 0, derived once.  sq_encode,
 // sq_decode and sq_range below are the definition; a row's i-th component in D(q, x) is sq_decode of its byte, and `clamped` counts
@@ -476,6 +479,68 @@ inline void knn(const Store& s, int nq, const float* queries, int R, const filte
         }
         rerank(s, 1, queries + (size_t)q * s.dim, n, keys.data(), nullptr, nullptr, R, out_keys + (size_t)q * R, out_dist + (size_t)q * R,
                out_sizes + q);
+    }
+}
+
+// ---- exact range search (qadc_refine_range, qadc_refine_rerank_range) ----
+// A key is KEPT for query q where the store holds it and D(q, x_key) < radius[q] as a binary32 compare: a NaN distance, a NaN
+// radius and a radius <= 0 of either sign keep nothing (D is +0, positive or NaN), a distance equal to the radius is not kept, and
+// radius +inf keeps every finite distance.  A kept key gives the word (bits(D) << 32) | key; a query's words are sorted ascending
+// and equal words kept once.  There is no R and no cap.
+//
+// rerank_range: the rule over the candidates keys[in_lims[q] .. in_lims[q + 1]), in_lims monotone from 0.  A candidate whose key
+// the store does not hold is MISSING: dropped and counted in the return value.  lims gets nq + 1 offsets, out_keys and out_dist the
+// lims[nq] kept rows of all queries one behind the other.
+template <typename Store>
+inline uint64_t rerank_range(const Store& s, int nq, const float* queries, const uint64_t* in_lims, const uint32_t* keys, const float* radius,
+                             std::vector<uint64_t>& lims, std::vector<uint32_t>& out_keys, std::vector<float>& out_dist) {
+    uint64_t missing = 0;
+    std::vector<uint64_t> words;
+    lims.assign(1, 0);
+    out_keys.clear();
+    out_dist.clear();
+    for (int q = 0; q < nq; ++q) {
+        words.clear();
+        for (uint64_t i = in_lims[q]; i < in_lims[q + 1]; ++i) {
+            const uint32_t k = keys[(size_t)i];
+            if (!s.holds(k)) {
+                ++missing;
+                continue;
+            }
+            const float d = s.distance_to(queries + (size_t)q * s.dim, k);
+            if (d < radius[q]) words.push_back(((uint64_t)float_bits(d) << 32) | k);
+        }
+        std::sort(words.begin(), words.end());
+        words.erase(std::unique(words.begin(), words.end()), words.end());
+        for (uint64_t w : words) {
+            out_keys.push_back((uint32_t)w);
+            out_dist.push_back(bits_float((uint32_t)(w >> 32)));
+        }
+        lims.push_back(lims.back() + words.size());
+    }
+    return missing;
+}
+
+// range: the kept rows of the whole store — rerank_range with every query's candidates = every held key that passes `filter`
+// (null: every held key).  Nothing is missing and nothing repeats: a store holds a key once.
+template <typename Store>
+inline void range(const Store& s, int nq, const float* queries, const float* radius, const filter* f, std::vector<uint64_t>& lims,
+                  std::vector<uint32_t>& out_keys, std::vector<float>& out_dist) {
+    std::vector<uint32_t> keys;
+    for (uint32_t k : s.held_keys())
+        if (!f || f->passes(k)) keys.push_back(k);
+    const uint64_t seg[2] = {0, (uint64_t)keys.size()};
+    std::vector<uint64_t> one;
+    std::vector<uint32_t> ok;
+    std::vector<float> od;
+    lims.assign(1, 0);
+    out_keys.clear();
+    out_dist.clear();
+    for (int q = 0; q < nq; ++q) {   // one query at a time: every segment of the rerank_range call is `keys`
+        rerank_range(s, 1, queries + (size_t)q * s.dim, seg, keys.data(), radius + q, one, ok, od);
+        out_keys.insert(out_keys.end(), ok.begin(), ok.end());
+        out_dist.insert(out_dist.end(), od.begin(), od.end());
+        lims.push_back(lims.back() + one[1]);
     }
 }
 

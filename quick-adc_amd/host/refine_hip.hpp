@@ -1,6 +1,7 @@
 // refine_store_hip — C++14 RAII mirror of the refine store (qadc_refine_* in include/qadc.h; DESIGN.md sections 11.11, 11.14 and 11.20): the
 // original vectors in device memory, dense over the keys [lo, lo + rows) or, with keyed = true, a map from key to vector filled by
-// put() and emptied by remove(); and rerank(), which reorders candidate keys by their exact squared L2 distance to them.  search_refined() composes it with adc_search_engine_hip (host/adc_search_hip.hpp): the engine's search with
+// put() and emptied by remove(); rerank(), which reorders candidate keys by their exact squared L2 distance to them; range() and
+// rerank_range(), the exact radius query over the whole store and over a range result (section 11.21).  search_refined() composes it with adc_search_engine_hip (host/adc_search_hip.hpp): the engine's search with
 // R = the engine's r as r_in, then the re-ranking of the heaps' keys, the FLT_MAX sentinels left out.  The definition both are held
 // to is host/refine.hpp.
 #pragma once
@@ -20,6 +21,14 @@ struct refine_result {
     std::vector<float> dist;              // [nq][r]; behind sizes[q]: +inf
     std::vector<std::int32_t> sizes;      // [nq]
     std::uint64_t missing = 0;            // candidates whose key the store does not hold
+};
+
+// An exact range result in CSR form (qadc_refine_range*, qadc_refine_rerank_range*)
+struct refine_range_result {
+    std::vector<std::uint64_t> lims;      // [nq + 1]: query q's rows are [lims[q], lims[q + 1])
+    std::vector<std::uint32_t> keys;      // ascending by (distance, key) within a query
+    std::vector<float> dist;
+    std::uint64_t missing = 0;            // rerank_range: candidates whose key the store does not hold
 };
 
 struct refine_store_hip {
@@ -124,6 +133,42 @@ struct refine_store_hip {
     void set_knn_plan(std::uint64_t chunk_rows, int pass_nq) {
         if (qadc_refine_set_knn_plan(store, chunk_rows, pass_nq) != QADC_OK) die("set_knn_plan");
     }
+
+    // the range result the store holds, copied out (qadc_refine_range_collect); lims: what the range call returned
+    void range_collect(refine_range_result& out) {
+        const std::uint64_t n = out.lims.empty() ? 0 : out.lims.back();
+        out.keys.resize((std::size_t)n);
+        out.dist.resize((std::size_t)n);
+        if (qadc_refine_range_collect(store, n, out.keys.data(), out.dist.data()) != QADC_OK) die("range_collect");
+    }
+
+    // Exact range search (qadc_refine_range): queries [nq][dim], radius [nq] -> per query every key the store
+    // holds that passes `filter` (null: every key) and whose exact distance is < radius[q], by (distance, key)
+    refine_range_result range(int nq, const float* queries, const float* radius, const qadc_adc_filter* filter = nullptr) {
+        refine_range_result out;
+        out.lims.assign((std::size_t)nq + 1, 0);
+        if (qadc_refine_range(store, nq, queries, radius, filter, out.lims.data()) != QADC_OK) die("range");
+        range_collect(out);
+        return out;
+    }
+
+    // The same rule over the candidates keys[in_lims[q] .. in_lims[q + 1]) of query q (qadc_refine_rerank_range): no limit on their
+    // number, a key listed several times kept once, a key not held counted in `missing`
+    refine_range_result rerank_range(int nq, const float* queries, const std::uint64_t* in_lims, const std::uint32_t* keys, const float* radius) {
+        refine_range_result out;
+        out.lims.assign((std::size_t)nq + 1, 0);
+        if (qadc_refine_rerank_range(store, nq, queries, in_lims, keys, radius, out.lims.data(), &out.missing) != QADC_OK) die("rerank_range");
+        range_collect(out);
+        return out;
+    }
+
+    // a tuning and test knob (qadc_refine_set_range_plan): 0 = the plan's default; no value changes a result
+    void set_range_plan(std::uint64_t region_rows, std::uint64_t chunk_rows, int pass_nq) {
+        if (qadc_refine_set_range_plan(store, region_rows, chunk_rows, pass_nq) != QADC_OK) die("set_range_plan");
+    }
+
+    // passes of range() that ran a second time because a query's region overflowed
+    std::uint64_t range_reruns() const { return qadc_refine_range_reruns(store); }
 };
 
 // The engine's search of nq queries with heaps of e.r entries, then their keys re-ranked against `store`: the first r by (exact
@@ -140,6 +185,25 @@ inline refine_result search_refined(adc_search_engine_hip<Db>& e, refine_store_h
     refine_result out = store.rerank(nq, queries, e.r, keys.data(), nullptr, vals.data(), r);
     if (cand_keys) cand_keys->swap(keys);
     if (cand_vals) cand_vals->swap(vals);
+    return out;
+}
+
+// The engine's range search of queries [query_i, query_i + nq) under adc_radius [nq], then its rows re-ranked against `store` under
+// the exact radius [nq]: every key of the ADC result whose exact distance is < radius[q], once, by (distance, key).  adc_lims /
+// adc_keys (may be null) receive the ADC result the re-ranking consumed.  Host arrays throughout; the device chain — range_search_device,
+// range_collect_device, rerank_range_device, nothing but the two lims arrays crossing the bus — is pyqadc's
+// AdcIndex.range_search_refined_device.  tests/cpp/refine_range_search_hip_demo.cpp holds this function to the twin.
+template <typename Db>
+inline refine_range_result range_search_refined(adc_search_engine_hip<Db>& e, refine_store_hip& store, int query_i, const float* queries, int nq,
+                                                const float* adc_radius, const float* radius, std::vector<std::uint64_t>* adc_lims = nullptr,
+                                                std::vector<std::uint32_t>* adc_keys = nullptr) {
+    std::vector<std::uint64_t> lims;
+    std::vector<std::uint32_t> keys;
+    std::vector<float> values;
+    e.range_search(query_i, queries, nq, adc_radius, lims, keys, values);
+    refine_range_result out = store.rerank_range(nq, queries + (std::size_t)query_i * store.dim, lims.data(), keys.data(), radius);
+    if (adc_lims) adc_lims->swap(lims);
+    if (adc_keys) adc_keys->swap(keys);
     return out;
 }
 

@@ -69,6 +69,8 @@ SYMBOLS = [
     "qadc_adc_index_reconstruct_rows", "qadc_adc_index_reconstruct_rows_device",
     "qadc_adc_range_scan", "qadc_adc_range_scan_device", "qadc_adc_range_search", "qadc_adc_range_search_device",
     "qadc_adc_range_collect", "qadc_adc_range_collect_device",
+    "qadc_refine_range", "qadc_refine_range_device", "qadc_refine_rerank_range", "qadc_refine_rerank_range_device",
+    "qadc_refine_range_collect", "qadc_refine_range_collect_device", "qadc_refine_set_range_plan", "qadc_refine_range_reruns",
 ]
 
 
@@ -342,6 +344,15 @@ def lib():
         L.qadc_adc_index_reconstruct_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.qadc_adc_index_reconstruct_rows.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, f32p]
         L.qadc_adc_index_reconstruct_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.qadc_refine_range.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_void_p, u64p]
+        L.qadc_refine_range_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, f32p, C.c_void_p, u64p]
+        L.qadc_refine_rerank_range.argtypes = [C.c_void_p, C.c_int, f32p, u64p, u32p, f32p, u64p, u64p]
+        L.qadc_refine_rerank_range_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, u64p, C.c_void_p, f32p, u64p, u64p]
+        L.qadc_refine_range_collect.argtypes = [C.c_void_p, C.c_uint64, u32p, f32p]
+        L.qadc_refine_range_collect_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.qadc_refine_set_range_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int]
+        L.qadc_refine_range_reruns.argtypes = [C.c_void_p]
+        L.qadc_refine_range_reruns.restype = C.c_uint64
         _lib = L
     return _lib
 
@@ -2229,6 +2240,21 @@ class AdcIndex(_RowStoreMixin):
         keys, vals = self._range_collect_device(lims)
         return lims.astype(np.int64), keys, vals
 
+    def range_search_refined_device(self, queries, ma, adc_radius, radius, store, table_form=2, sum_mode=1, filters=None):
+        """queries: float32 tensor [nq][dim] on the index's device; store: a Refine of that device -> (lims int64 numpy, keys int32
+        tensor carrying the uint32 bits, dist float32 tensor, missing): range_search_device under adc_radius, its rows collected in
+        device memory and handed to store.rerank_range_device under radius — every key of the ADC result whose exact squared L2
+        distance is < radius[q], once, ascending by (distance, key).  Only the two lims arrays and the missing count cross the bus."""
+        lims, keys, _ = self.range_search_device(queries, ma, adc_radius, table_form, sum_mode, filters)
+        return store.rerank_range_device(queries, lims, keys, radius)
+
+    def range_search_refined(self, queries, ma, adc_radius, radius, store, table_form=2, sum_mode=1, filters=None):
+        """the same for host arrays, through range_search and store.rerank_range (the ADC rows cross the bus both ways; the device
+        form keeps them where they are): -> (lims int64, keys uint32, dist float32, missing)"""
+        q = self._queries(queries)
+        lims, keys, _ = self.range_search(q, ma, adc_radius, table_form, sum_mode, filters)
+        return store.rerank_range(q, lims, keys, radius)
+
 
 QADC_REFINE_F32, QADC_REFINE_F16, QADC_REFINE_MAX_IN = 0, 1, 8192   # include/qadc.h
 QADC_REFINE_SQ8 = 2
@@ -2559,3 +2585,122 @@ class Refine:
         """qadc_refine_set_knn_plan: the rows of a group per launch and the queries per pass of the later knn calls (0: the plan's
         default) — a tuning and test knob; no value changes a result"""
         _check(lib().qadc_refine_set_knn_plan(self._h, int(chunk_rows), int(pass_nq)))
+
+    # ---- exact range search (qadc_refine_range*, qadc_refine_rerank_range*; DESIGN.md section 11.21) ----
+    def _queries(self, queries):
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise QadcError("queries has shape %s, expected [nq][%d]" % (q.shape, self.dim))
+        return q
+
+    def range_collect_raw(self, capacity):
+        """The C call as it is: -> (rc, keys [capacity], dist [capacity])"""
+        keys = np.zeros(max(capacity, 1), np.uint32)
+        dist = np.zeros(max(capacity, 1), np.float32)
+        return lib().qadc_refine_range_collect(self._h, capacity, _p(keys, u32p), _p(dist, f32p)), keys, dist
+
+    def range_collect(self, lims=None):
+        """qadc_refine_range_collect: (keys uint32, dist float32) of the range result the store holds, any number of times; lims: the
+        array the range call returned (default: the last one made through this object)."""
+        n = int(lims[-1]) if lims is not None else getattr(self, "_range_rows", 0)
+        rc, keys, dist = self.range_collect_raw(n)
+        _check(rc)
+        return keys[:n], dist[:n]
+
+    def _range_collect_device(self, lims):
+        import torch
+        dev = torch.device("cuda", self.device)
+        n = int(lims[-1])
+        keys = torch.zeros((n,), dtype=torch.int32, device=dev)          # the uint32 keys' bits
+        dist = torch.zeros((n,), dtype=torch.float32, device=dev)
+        self._sync()                                                     # the zero fills are complete before the call
+        _check(lib().qadc_refine_range_collect_device(self._h, n, keys.data_ptr(), dist.data_ptr()))
+        return keys, dist
+
+    def range(self, queries, radius, filter=None):
+        """queries [nq][dim], radius a scalar or [nq] -> (lims int64 [nq+1], keys uint32, dist float32): for query q, rows
+        [lims[q], lims[q+1]) = EVERY key the store holds that passes `filter` (an AdcFilter of the store's device, or None) and whose exact
+        squared L2 distance is < radius[q] (a float compare: NaN keeps nothing), ascending by (distance, key); refine::range."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        r = AdcIndex._radius(radius, nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        _check(lib().qadc_refine_range(self._h, nq, _p(q, f32p), _p(r, f32p), None if filter is None else filter._h, _p(lims, u64p)))
+        self._range_rows = int(lims[-1])
+        keys, dist = self.range_collect(lims)
+        return lims.astype(np.int64), keys, dist
+
+    def range_device(self, queries, radius, filter=None):
+        """range() for a float32 torch tensor [nq][dim] of the store's device -> (lims int64 numpy, keys int32 tensor carrying the
+        uint32 bits, dist float32 tensor): only radius and lims cross the bus."""
+        if getattr(queries, "ndim", 0) != 2:
+            raise TypeError("queries must be a 2-d torch.Tensor")
+        nq = int(queries.shape[0])
+        q = self._tensor(queries, "float32", (nq, self.dim), "queries")
+        r = AdcIndex._radius(radius, nq)
+        lims = np.zeros(nq + 1, np.uint64)
+        self._sync()
+        _check(lib().qadc_refine_range_device(self._h, nq, q.data_ptr(), _p(r, f32p), None if filter is None else filter._h, _p(lims, u64p)))
+        self._range_rows = int(lims[-1])
+        keys, dist = self._range_collect_device(lims)
+        return lims.astype(np.int64), keys, dist
+
+    @staticmethod
+    def _in_lims(lims, nq):
+        a = np.asarray(lims)
+        if a.shape != (nq + 1,) or (a.dtype.kind == "i" and (a < 0).any()):
+            raise ValueError("lims has one entry per query and one more (%d), none negative, not shape %s" % (nq + 1, a.shape))
+        return np.ascontiguousarray(a, np.uint64)
+
+    def rerank_range(self, queries, lims, keys, radius):
+        """queries [nq][dim], lims [nq+1] and keys uint32 [lims[nq]] (a range result in CSR form), radius a scalar or [nq] ->
+        (lims int64 [nq+1], keys uint32, dist float32, missing): per query those of its candidates the store holds whose exact squared
+        L2 distance is < radius[q], ascending by (distance, key), every key once; missing = the candidates whose key the store does not
+        hold.  No limit on the candidates of a query; refine::rerank_range."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        il = self._in_lims(lims, nq)
+        k = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(-1))
+        if k.shape[0] < int(il[-1]):
+            raise ValueError("keys has %d entries, lims[nq] is %d" % (k.shape[0], int(il[-1])))
+        r = AdcIndex._radius(radius, nq)
+        out = np.zeros(nq + 1, np.uint64)
+        missing = C.c_uint64(0)
+        _check(lib().qadc_refine_rerank_range(self._h, nq, _p(q, f32p), _p(il, u64p), _p(k, u32p) if k.shape[0] else None, _p(r, f32p),
+                                              _p(out, u64p), C.byref(missing)))
+        self._range_rows = int(out[-1])
+        okeys, dist = self.range_collect(out)
+        return out.astype(np.int64), okeys, dist, int(missing.value)
+
+    def rerank_range_device(self, queries, lims, keys, radius):
+        """rerank_range() on torch tensors of the store's device: queries float32 [nq][dim], keys int32 [n >= lims[nq]] carrying the
+        uint32 bits (as AdcIndex.range_search_device returns them); lims stays a host array -> (lims int64 numpy, keys int32 tensor,
+        dist float32 tensor, missing)."""
+        if getattr(queries, "ndim", 0) != 2 or getattr(keys, "ndim", 0) != 1:
+            raise TypeError("queries must be a 2-d and keys a 1-d torch.Tensor")
+        nq = int(queries.shape[0])
+        q = self._tensor(queries, "float32", (nq, self.dim), "queries")
+        k = self._tensor(keys, "int32", (int(keys.shape[0]),), "keys")
+        il = self._in_lims(lims, nq)
+        if int(k.shape[0]) < int(il[-1]):
+            raise ValueError("keys has %d entries, lims[nq] is %d" % (int(k.shape[0]), int(il[-1])))
+        r = AdcIndex._radius(radius, nq)
+        out = np.zeros(nq + 1, np.uint64)
+        missing = C.c_uint64(0)
+        self._sync()
+        _check(lib().qadc_refine_rerank_range_device(self._h, nq, q.data_ptr(), _p(il, u64p), k.data_ptr() if k.shape[0] else None, _p(r, f32p),
+                                                     _p(out, u64p), C.byref(missing)))
+        self._range_rows = int(out[-1])
+        okeys, dist = self._range_collect_device(out)
+        return out.astype(np.int64), okeys, dist, int(missing.value)
+
+    def set_range_plan(self, region_rows=0, chunk_rows=0, pass_nq=0):
+        """qadc_refine_set_range_plan: the words of a query's region in the first run, the rows of a group per launch and the queries
+        per pass of the later range calls (0: the plan's default) — a tuning and test knob; no value changes a result"""
+        _check(lib().qadc_refine_set_range_plan(self._h, int(region_rows), int(chunk_rows), int(pass_nq)))
+
+    def range_reruns(self):
+        """passes of range() that ran a second time because a query's region overflowed"""
+        return int(lib().qadc_refine_range_reruns(self._h))

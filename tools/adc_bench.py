@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn,decode,refine_sq] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn,decode,refine_sq,refine_range] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,opq,seed,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,seed,filter] [--iters N] [--out FILE]
 
@@ -212,7 +212,7 @@ def search_legs(legs, iters, res):
     part_of, codes = pyqadc.adc_encode(codebooks, vectors, coarse)
     res["adc_encode_1e6_s"] = time.perf_counter() - t0
     print("adc_encode of 10^6 128-d vectors (K = 256, 8x8), host to host: %.2f s" % res["adc_encode_1e6_s"], flush=True)
-    if "refine" not in legs and "keyed" not in legs and "refine_sq" not in legs:
+    if "refine" not in legs and "keyed" not in legs and "refine_sq" not in legs and "refine_range" not in legs:
         del vectors
     order = np.argsort(part_of, kind="stable")
     bounds = np.searchsorted(part_of[order], np.arange(K + 1))
@@ -257,7 +257,9 @@ def search_legs(legs, iters, res):
         keyed_leg(idx, vectors, queries, ma, iters, res, codebooks, coarse)
     if "refine_sq" in legs:
         refine_sq_leg(idx, vectors, queries, ma, iters, res)
-    if "refine" in legs or "keyed" in legs or "refine_sq" in legs:
+    if "refine_range" in legs:
+        refine_range_search_leg(idx, vectors, queries, ma, iters, res)
+    if "refine" in legs or "keyed" in legs or "refine_sq" in legs or "refine_range" in legs:
         del vectors
     if "filter" in legs:   # (b): the same search() without a filter and with 10 % of the keys excluded, in turn, under both finishes
         S = rng.permutation(n)[:n // 10].astype(np.uint32)
@@ -1627,6 +1629,148 @@ def knn_leg(iters, res, torch):
         del held, norms
 
 
+def refine_range_leg(iters, res, torch):
+    """Exact range search over 10^6 rows of dim 128, F32 and F16, in one process:
+    (a) Refine.range_device under radii that keep about 100 and about 10^4 rows per query beside Refine.knn_device(R = 100) at the same
+        shapes — the same distance pass without the mid-selects — three rounds of each, so that knn's own run-to-run spread is on record;
+        and a torch route (|x|^2 - 2 q.x, a compare, nonzero, a sort) as other arithmetic, not a parity target;
+    (b) Refine.rerank_range_device on 1024 x 1000 candidates beside Refine.rerank_device at r_in = 1000, R = 1000."""
+    if torch is None:
+        print("refine_range leg: needs torch on the GPU (the rows are made there)", flush=True)
+        return
+    n, dim, chunk = 1_000_000, 128, 1 << 18
+    gen = torch.Generator(device="cuda").manual_seed(11)
+    x = torch.randn((n, dim), generator=gen, device="cuda", dtype=torch.float32)
+    out = res.setdefault("refine_range", {"rows": n, "dim": dim})
+    for dtype in ("f32", "f16"):
+        st = pyqadc.Refine(dim, dtype)
+        st.add_device(x, 0)
+        held = x if dtype == "f32" else x.half().float()
+        norms = (held * held).sum(1)
+
+        def torch_route(q, radius):
+            r = torch.from_numpy(radius).cuda()
+            qn = (q * q).sum(1)
+            rows = []
+            for first in range(0, n, chunk):
+                d = qn[:, None] + norms[first:first + chunk][None, :] - 2.0 * (q @ held[first:first + chunk].T)
+                hit = torch.nonzero(d < r[:, None])
+                rows.append(torch.stack([hit[:, 0].double(), d[hit[:, 0], hit[:, 1]].double(), (hit[:, 1] + first).double()], 1))
+            rows = torch.cat(rows)
+            order = torch.argsort(rows[:, 1], stable=True)
+            order = order[torch.argsort(rows[order, 0], stable=True)]
+            torch.cuda.synchronize()
+            return rows[order]
+
+        for nq in (1024, 32, 1):
+            q = torch.randn((nq, dim), generator=gen, device="cuda", dtype=torch.float32)
+            its = max(3, iters if nq < 1024 else iters // 2)
+            _, kd, _ = st.knn_device(q, R)
+            r100 = np.nextafter(kd[:, R - 1].cpu().numpy(), np.float32(np.inf))            # keeps the knn's 100 rows (and their ties)
+            sample = held[torch.randint(0, n, (100_000,), generator=gen, device="cuda")]
+            ds = (q * q).sum(1)[:, None] + (sample * sample).sum(1)[None, :] - 2.0 * (q @ sample.T)
+            r1e4 = torch.kthvalue(ds, 1000, dim=1).values.cpu().numpy().astype(np.float32)   # 1 % of a sample: about 10^4 of 10^6 rows
+            entry = {}
+            knn_rounds, rng_rounds = [], []
+            for _ in range(3):
+                mk, mr = alternated(lambda: st.knn_device(q, R), lambda: st.range_device(q, r100), its)
+                knn_rounds.append(mk * 1e3)
+                rng_rounds.append(mr * 1e3)
+            before = st.range_reruns()
+            big, _ = timed(lambda: st.range_device(q, r1e4), its)
+            reruns = st.range_reruns() - before
+            lims100 = st.range_device(q, r100)[0]
+            lims1e4, k1e4, _ = st.range_device(q, r1e4)
+            t_its = 2 if nq == 1024 else its
+            med_t, _ = timed(lambda: torch_route(q, r100), t_its, warmup=1)
+            want = torch_route(q, r1e4)
+            agree = "%d against %d" % (int(want.shape[0]), int(lims1e4[-1]))   # (other arithmetic: rows at the radius may fall either way)
+            entry.update({"knn_device_R100_ms_rounds": knn_rounds, "range_device_keep100_ms_rounds": rng_rounds,
+                          "knn_spread_ms": max(knn_rounds) - min(knn_rounds), "range_minus_knn_ms": float(np.median(rng_rounds) - np.median(knn_rounds)),
+                          "rows_kept_per_query_keep100": float(lims100[-1]) / nq, "range_device_keep1e4_ms": big * 1e3,
+                          "rows_kept_per_query_keep1e4": float(lims1e4[-1]) / nq, "reruns_per_call_keep1e4": reruns / (its + 2),
+                          "torch_route_keep100_ms": med_t * 1e3, "torch_route_rows_against_range_rows_keep1e4": agree})
+            out["%s_nq%d" % (dtype, nq)] = entry
+            print("range %s, 10^6 x 128, nq %4d: knn_device(R=100) %s ms; range_device keeping %.1f rows/query %s ms (range - knn %.3f ms, knn's "
+                  "spread %.3f ms); keeping %.0f rows/query %.3f ms (%.1f re-runs per call); torch route %.3f ms; rows the torch route and range keep: %s"
+                  % (dtype, nq, ["%.3f" % v for v in knn_rounds], entry["rows_kept_per_query_keep100"], ["%.3f" % v for v in rng_rounds],
+                     entry["range_minus_knn_ms"], entry["knn_spread_ms"], entry["rows_kept_per_query_keep1e4"], big * 1e3,
+                     entry["reruns_per_call_keep1e4"], med_t * 1e3, agree), flush=True)
+        # (b) candidates: 1024 x 1000 random keys
+        nq, r_in = 1024, 1000
+        q = torch.randn((nq, dim), generator=gen, device="cuda", dtype=torch.float32)
+        keys = torch.randint(0, n, (nq, r_in), generator=gen, device="cuda", dtype=torch.int32)
+        flat = keys.reshape(-1).contiguous()
+        lims = np.arange(nq + 1, dtype=np.uint64) * r_in
+        rr_rounds, rk_rounds = [], []
+        for _ in range(3):
+            mk, mr = alternated(lambda: st.rerank_device(q, keys, r_in), lambda: st.rerank_range_device(q, lims, flat, np.float32(np.inf)), max(3, iters))
+            rk_rounds.append(mk * 1e3)
+            rr_rounds.append(mr * 1e3)
+        a, b = st.rerank_device(q, keys, r_in), st.rerank_range_device(q, lims, flat, np.float32(np.inf))
+        same = bool(np.array_equal(np.cumsum(a[2].cpu().numpy()), b[0][1:])) and bool(torch.equal(a[0][0, :int(b[0][1])], b[1][:int(b[0][1])]))
+        out["%s_rerank_1024x1000" % dtype] = {"rerank_device_ms_rounds": rk_rounds, "rerank_range_device_ms_rounds": rr_rounds, "results_agree": same}
+        print("rerank %s, 1024 x 1000 candidates: rerank_device(R = r_in) %s ms; rerank_range_device(+inf) %s ms; results agree: %s"
+              % (dtype, ["%.3f" % v for v in rk_rounds], ["%.3f" % v for v in rr_rounds], same), flush=True)
+        st.close()
+        del held, norms
+
+
+def refine_range_search_leg(idx, vectors, queries, ma, iters, res):
+    """AdcIndex.range_search_refined_device on the IVF index of search_legs (10^6 codes, K = 256, ma = 24, 1024 queries) beside the host
+    route it replaces — range_search to the host, every query padded to 8192 candidates (the rest dropped), Refine.rerank with
+    R = r_in, a threshold in numpy — and the range recall against Refine.range as ground truth for adc_radius = c * radius."""
+    import torch
+    nq, dim = queries.shape
+    out = res.setdefault("refine_range", {})
+    st = pyqadc.Refine(dim, "f32")
+    st.add(vectors, 0)
+    dq = torch.from_numpy(queries).cuda()
+    _, kd, _ = st.knn_device(dq, R)
+    radius = np.nextafter(kd[:, R - 1].cpu().numpy(), np.float32(np.inf))                   # the exact radius of each query's 100 nearest rows
+    _, vals, _, _ = idx.search(queries, ma, 1000)
+    adc_radius = vals.max(axis=1).astype(np.float32)                                        # about 1000 ADC rows per query
+    MAXIN = pyqadc.QADC_REFINE_MAX_IN
+
+    def host_route():
+        lims, keys, _ = idx.range_search(queries, ma, adc_radius)
+        padded = np.full((nq, MAXIN), 0xFFFFFFFF, np.uint32)
+        counts = np.minimum(np.diff(lims), MAXIN).astype(np.int32)
+        for i in range(nq):
+            padded[i, :counts[i]] = keys[lims[i]:lims[i] + counts[i]]
+        k, d, s, _ = st.rerank(queries, padded, MAXIN, counts=counts)
+        keep = d < radius[:, None]
+        return k, keep, int((np.diff(lims) > MAXIN).sum())
+
+    dev = lambda: idx.range_search_refined_device(dq, ma, adc_radius, radius, st)
+    lims, keys, dist, missing = dev()
+    hk, keep, truncated = host_route()
+    agree = all(np.array_equal(hk[i][keep[i]], keys[lims[i]:lims[i + 1]].cpu().numpy().view(np.uint32)) for i in range(0, nq, 37))
+    its = max(3, iters // 2)
+    med_d, _ = timed(dev, its)
+    med_h, _ = timed(host_route, 2, warmup=1)
+    out["range_search_refined"] = {"device_chain_ms": med_d * 1e3, "host_route_ms": med_h * 1e3, "queries_the_host_route_truncates": truncated,
+                                   "adc_rows_per_query": float(idx.range_search(queries, ma, adc_radius)[0][-1]) / nq,
+                                   "rows_kept_per_query": float(lims[-1]) / nq, "missing": missing, "sampled_queries_agree": bool(agree)}
+    print("range_search_refined_device, 10^6 codes K=256 ma=%d, %d queries (%.0f ADC rows/query, %.1f kept): %.2f ms; the host route (collect, pad to "
+          "%d, rerank, threshold) %.2f ms, truncating %d queries; sampled queries agree: %s"
+          % (ma, nq, out["range_search_refined"]["adc_rows_per_query"], float(lims[-1]) / nq, med_d * 1e3, MAXIN, med_h * 1e3, truncated, agree), flush=True)
+    # range recall: the rows truly within the radius (Refine.range) that the composition returns under adc_radius = c * radius
+    sub = 128
+    tl, tk, _ = st.range_device(dq[:sub].contiguous(), radius[:sub])
+    tk = tk.cpu().numpy()
+    recall = {}
+    for c in (0.8, 1.0, 1.2, 1.5, 2.0):
+        gl, gk, _, _ = idx.range_search_refined_device(dq[:sub].contiguous(), ma, (radius[:sub] * np.float32(c)).astype(np.float32), radius[:sub], st)
+        gk = gk.cpu().numpy()
+        hit = sum(len(np.intersect1d(tk[tl[i]:tl[i + 1]], gk[gl[i]:gl[i + 1]])) for i in range(sub))
+        recall["%.1f" % c] = hit / max(1, int(tl[-1]))
+    out["range_recall_by_c"] = recall
+    print("range recall of range_search_refined against Refine.range (%d queries, %.1f true rows each), adc_radius = c * radius: %s"
+          % (sub, float(tl[-1]) / sub, recall), flush=True)
+    st.close()
+
+
 VALU_FMA_PER_S = 157.3e12 / 2   # the FP32 vector peak (spec), in fused multiply-adds
 
 
@@ -1778,7 +1922,7 @@ def main():
                 f.write(line + "\n")
         return
     torch = None
-    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs or "decode" in legs or "refine_sq" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs or "decode" in legs or "refine_sq" in legs or "refine_range" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:
             import torch
             torch.zeros(1, device="cuda")
@@ -1867,7 +2011,7 @@ def main():
             print("the same alternated with query_scan_device (tables and heaps stay in device memory): %.2f ms against %.2f ms"
                   % (med_d * 1e3, med_h * 1e3), flush=True)
         idx.close()
-    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs or "range" in legs or "keyed" in legs or "refine_sq" in legs:
+    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs or "range" in legs or "keyed" in legs or "refine_sq" in legs or "refine_range" in legs:
         search_legs(legs, a.iters, res)
     if "filter" in legs:
         filter_leg(8, a.iters, res, torch)
@@ -1883,6 +2027,8 @@ def main():
         seed_leg(8, a.iters, res)
     if "knn" in legs:
         knn_leg(a.iters, res, torch)
+    if "refine_range" in legs:
+        refine_range_leg(a.iters, res, torch)
     if "decode" in legs:
         decode_leg(8, a.iters, res, torch)
     line = json.dumps(res)

@@ -1503,6 +1503,53 @@ int qadc_refine_knn_device(qadc_refine* r, int nq, const float* d_queries, int R
  * negative pass_nq. */
 int qadc_refine_set_knn_plan(qadc_refine* r, uint64_t chunk_rows, int pass_nq);
 
+/* ---- probed exact search: the R nearest rows among the partitions a query probes ----
+ * IVF-Flat (IVF-F16, IVF-SQ8) from the pieces that are resident: the index gives, per partition, its rows' keys; the store maps a
+ * key to a row.  For query q with the probe list assign[q][0 .. ma):
+ *   probes      P_q = the distinct partition numbers of the list; a repeat counts once.
+ *   candidates  every row i of every p in P_q is one entry; its key is the partition's label i on a labelled index, else
+ *               key_base + i — the key the scan gives the row.  A key that fails the index's filter (qadc_adc_index_set_filter) or
+ *               `filter` is no entry: both must pass (EXCLUDE / ALLOW as above).
+ *   result      qadc_refine_rerank fed q's entries with no r_in limit, bit for bit: D, its image and the NaN image as above; an entry
+ *               whose key the store does not hold is missing and counted in *missing_out, per entry; a key that occurs several times
+ *               (labels may repeat, within and across partitions) is kept once; the survivors ascending by (image(D) << 32) | key,
+ *               the first min(R, survivors) returned, behind them key 0xFFFFFFFF and distance +inf; out_sizes[q].
+ * The twin is refine::knn_probed of quick-adc_amd/host/refine.hpp.  The result is a function of the index's rows, the store's
+ * contents and the arguments: no chunk, tile, pass, group or arrival order shows in it.  The index is read as it is at the call.
+ * idx: an owned 8-bit or 16-bit index, or a view of a 4-bit index.  Dense and keyed stores; F32, F16 and SQ8 rows.
+ * 1 <= R <= QADC_REFINE_KNN_MAX_R, 1 <= ma <= the index's partitions.  qadc_refine_set_knn_plan keeps its meaning for these calls
+ * (chunk_rows: the rows a (query, group) buffer is offered between two selects; a query's probes share min(8, 8192 / R, ma) groups,
+ * and chunk_rows below the probes of a group is refused); no value changes a result.
+ * QADC_E_ARG: what qadc_refine_knn refuses; idx NULL; an index of another device than the store's; ma out of range; a view whose
+ * source is sharded or holds borrowed partitions.  QADC_E_STATE: a view whose 4-bit source is not finalized.
+ * Limits: no probed range search; L2 only; R <= 1024; one device; one filter per call; synchronous; the rows are gathered through
+ * the store (there is no partition-ordered copy of them); a single very long partition means many thin launches. */
+/* Host arrays: queries [nq][dim], assign [nq][ma] -> out_keys [nq][R], out_dist [nq][R], out_sizes [nq]; missing_out may be NULL.
+ * An entry of assign outside [0, partitions) is QADC_E_ARG before the device is touched. */
+int qadc_refine_knn_probed(qadc_refine* r, const qadc_adc_index* idx, int nq, const float* queries, int ma, const int32_t* assign, int R,
+                           const qadc_adc_filter* filter, uint32_t* out_keys, float* out_dist, int32_t* out_sizes, uint64_t* missing_out);
+/* The same with every array, d_assign included, in device memory of the store's device, complete before the call and touched by
+ * kernels only; 4-byte alignment of every array is checked first.  An entry of d_assign outside [0, partitions) is skipped.  What
+ * crosses the bus: the nq x ma probe numbers, device to host (the planner inverts them there), the work lists they become, host to
+ * device, and the missing count. */
+int qadc_refine_knn_probed_device(qadc_refine* r, const qadc_adc_index* idx, int nq, const float* d_queries, int ma, const int32_t* d_assign,
+                                  int R, const qadc_adc_filter* filter, uint32_t* d_out_keys, float* d_out_dist, int32_t* d_out_sizes,
+                                  uint64_t* missing_out);
+/* The coarse step of qadc_adc_search alone, with its kernels and refusals: assign_out [nq][ma] = the probe lists qadc_adc_search
+ * reports in its assign_out.  An index without coarse centroids is flat: every probe 0.  A NaN coarse row with ma > 256 is refused. */
+int qadc_adc_index_assign(qadc_adc_index* idx, int nq, const float* queries, int ma, int sum_mode, int32_t* assign_out);
+/* The same with d_queries and d_assign_out in device memory of the index's device (4-byte aligned; written by a kernel). */
+int qadc_adc_index_assign_device(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int sum_mode, int32_t* d_assign_out);
+/* qadc_adc_index_assign, then qadc_refine_knn_probed on its lists: the exact result over the partitions qadc_adc_search would
+ * probe — the ceiling of a re-ranked search at the same ma.  assign_out [nq][ma] may be NULL. */
+int qadc_adc_search_exact(qadc_adc_index* idx, qadc_refine* store, int nq, const float* queries, int ma, int R, int sum_mode,
+                          const qadc_adc_filter* filter, uint32_t* out_keys, float* out_dist, int32_t* out_sizes, uint64_t* missing_out,
+                          int32_t* assign_out);
+/* The same on arrays in device memory (d_assign_out may be NULL); what crosses the bus is what the two device calls let cross. */
+int qadc_adc_search_exact_device(qadc_adc_index* idx, qadc_refine* store, int nq, const float* d_queries, int ma, int R, int sum_mode,
+                                 const qadc_adc_filter* filter, uint32_t* d_out_keys, float* d_out_dist, int32_t* d_out_sizes,
+                                 uint64_t* missing_out, int32_t* d_assign_out);
+
 /* ---- SQ8 rows: one byte per component under a per-dimension range; read-back ----
  * A third element type: a store of dim bytes per row (no padding) with the parameters vmin[dim] and step[dim], both finite,
  * step >= 0.  The store derives inv[i] = 1.0f / step[i] where step[i] > 0 (+inf for a subnormal step), else 0, on the host, once.

@@ -165,6 +165,30 @@ void qadc::host::adc_filter_view(const qadc_adc_filter* f, qadc::adc::ScanFilter
     *device = f ? f->device : -1;
 }
 
+int qadc::host::adc_probe_view(const qadc_adc_index* idx, std::vector<AdcProbePart>* parts, int* device, qadc::adc::ScanFilter* filter) {
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    parts->clear();
+    if (idx->src) {
+        if (!idx->src->finalized) return fail(QADC_E_STATE, "the view's source index is not finalized");
+        if (idx->src->dist) return fail(QADC_E_ARG, "the view's source index takes part in a multi-GPU merge");
+        if (idx->src->parts.size() != idx->parts4.size()) return fail(QADC_E_STATE, "the view's source index has changed its partitions");
+        for (size_t p = 0; p < idx->src->parts.size(); ++p) {
+            const Part& pt = idx->src->parts[p];
+            if (pt.n != pt.global_n || pt.first_pos != 0 || pt.d_starts) return fail(QADC_E_ARG, "the view's source index is sharded");
+            if (!pt.own) return fail(QADC_E_ARG, "partition " + std::to_string(p) + " of the view's source index is borrowed");
+            parts->push_back(AdcProbePart{idx->parts4[p].labels, idx->parts4[p].key_base, idx->sizes[p]});
+        }
+    } else {
+        for (size_t p = 0; p < idx->sizes.size(); ++p) {
+            const uint32_t n = idx->sizes[p];
+            parts->push_back(AdcProbePart{n && idx->labeled == 1 ? idx->store.part_labels(p) : nullptr, 0, n});
+        }
+    }
+    *device = idx->device;
+    *filter = scan_filter(idx->filter);
+    return QADC_OK;
+}
+
 namespace {
 
 // The database as the scan launcher takes it: the owned codes, or the partition table of a view.
@@ -1645,6 +1669,71 @@ int qadc_adc_search_device(qadc_adc_index* idx, int nq, const float* d_queries, 
 int qadc_adc_search_device_filtered(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int R, int table_form, int sum_mode,
                                     uint32_t* d_keys, float* d_values, int32_t* d_sizes, const qadc_adc_filter* const* filters) {
     return search_device_call(idx, nq, d_queries, ma, R, table_form, sum_mode, d_keys, d_values, d_sizes, filters);
+}
+
+// The coarse step of qadc_adc_search alone: resolve_feeders' refusals, enqueue_assign's kernels, wait_assign's NaN refusal.
+static int assign_call(qadc_adc_index* idx, int nq, const float* queries, int ma, int sum_mode, int32_t* assign_out, bool d_side) {
+    if (!assign_out) return fail(QADC_E_ARG, "assign_out is null");
+    if (d_side) {
+        if (int rc = check_aligned(queries, 4, "d_queries")) return rc;
+        if (int rc = check_aligned(assign_out, 4, "d_assign_out")) return rc;
+    }
+    DeviceGuard guard;
+    Feeders f;
+    if (int rc = resolve_feeders(idx, nq, queries, ma, 0, sum_mode, &f)) return rc;
+    if (int rc = enqueue_assign(idx, f, nq, queries, ma, sum_mode, d_side)) return rc;
+    if (int rc = wait_assign(idx, f, ma)) return rc;
+    if (d_side) {
+        HIPCHECK(launch_adc_copy_words(idx->d_assign.p, assign_out, (size_t)nq * ma, idx->stream));
+        HIPCHECK(hipStreamSynchronize(idx->stream));
+    } else {
+        std::memcpy(assign_out, idx->h_assign.p, (size_t)nq * ma * 4);
+    }
+    return QADC_OK;
+}
+
+int qadc_adc_index_assign(qadc_adc_index* idx, int nq, const float* queries, int ma, int sum_mode, int32_t* assign_out) {
+    return assign_call(idx, nq, queries, ma, sum_mode, assign_out, false);
+}
+
+int qadc_adc_index_assign_device(qadc_adc_index* idx, int nq, const float* d_queries, int ma, int sum_mode, int32_t* d_assign_out) {
+    return assign_call(idx, nq, d_queries, ma, sum_mode, d_assign_out, true);
+}
+
+// assign, then probed: the two calls one behind the other, each with its own refusals
+int qadc_adc_search_exact(qadc_adc_index* idx, qadc_refine* store, int nq, const float* queries, int ma, int R, int sum_mode,
+                          const qadc_adc_filter* filter, uint32_t* out_keys, float* out_dist, int32_t* out_sizes, uint64_t* missing_out,
+                          int32_t* assign_out) {
+    if (nq < 1 || ma < 1) return fail(QADC_E_ARG, "need nq >= 1 and ma >= 1");
+    std::vector<int32_t> own;
+    if (!assign_out) {
+        own.resize((size_t)nq * ma);
+        assign_out = own.data();
+    }
+    if (int rc = assign_call(idx, nq, queries, ma, sum_mode, assign_out, false)) return rc;
+    return qadc_refine_knn_probed(store, idx, nq, queries, ma, assign_out, R, filter, out_keys, out_dist, out_sizes, missing_out);
+}
+
+int qadc_adc_search_exact_device(qadc_adc_index* idx, qadc_refine* store, int nq, const float* d_queries, int ma, int R, int sum_mode,
+                                 const qadc_adc_filter* filter, uint32_t* d_out_keys, float* d_out_dist, int32_t* d_out_sizes,
+                                 uint64_t* missing_out, int32_t* d_assign_out) {
+    if (nq < 1 || ma < 1) return fail(QADC_E_ARG, "need nq >= 1 and ma >= 1");
+    if (!idx) return fail(QADC_E_ARG, "index is null");
+    if (d_assign_out) {
+        if (int rc = assign_call(idx, nq, d_queries, ma, sum_mode, d_assign_out, true)) return rc;
+        return qadc_refine_knn_probed_device(store, idx, nq, d_queries, ma, d_assign_out, R, filter, d_out_keys, d_out_dist, d_out_sizes, missing_out);
+    }
+    // no assign_out: the index's own probe lists, which enqueue_assign leaves in idx->d_assign
+    if (int rc = check_aligned(d_queries, 4, "d_queries")) return rc;
+    {
+        DeviceGuard guard;
+        Feeders f;
+        if (int rc = resolve_feeders(idx, nq, d_queries, ma, 0, sum_mode, &f)) return rc;
+        if (int rc = enqueue_assign(idx, f, nq, d_queries, ma, sum_mode, true)) return rc;
+        if (int rc = wait_assign(idx, f, ma)) return rc;
+        HIPCHECK(hipStreamSynchronize(idx->stream));
+    }
+    return qadc_refine_knn_probed_device(store, idx, nq, d_queries, ma, idx->d_assign.p, R, filter, d_out_keys, d_out_dist, d_out_sizes, missing_out);
 }
 
 int qadc_adc_search_candidates(qadc_adc_index* idx, int nq, const float* queries, int ma, int R, int table_form, int sum_mode,

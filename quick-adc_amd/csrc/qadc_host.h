@@ -596,6 +596,17 @@ int flush_shares(qadc_index* idx, uint64_t upto);            // heap-share gathe
 // qadc_adc.cpp: what a key filter (qadc_adc_filter, private to that unit) gives a kernel, and the device it lives on — for the
 // callers outside the float-ADC engine (qadc_refine_knn)
 void adc_filter_view(const qadc_adc_filter* f, adc::ScanFilter* out, int* device);
+// qadc_adc.cpp: the partitions of a float-ADC index (private to that unit) as the scan keys them, for the probed exact search
+// (qadc_refine_knn_probed): per partition the labels in device memory (null: key = key_base + position), key_base and the rows held
+// at the call; the index's device and its set filter (bitmap null: none).  Valid for owned indexes and for views.  Refuses, with the
+// code returned and the message set, an index the search cannot read: a view whose source is no longer finalized, is sharded or
+// holds borrowed partitions.
+struct AdcProbePart {
+    const uint32_t* labels;
+    uint32_t key_base;
+    uint32_t rows;
+};
+int adc_probe_view(const qadc_adc_index* idx, std::vector<AdcProbePart>* parts, int* device, adc::ScanFilter* filter);
 
 }  // namespace host
 }  // namespace qadc

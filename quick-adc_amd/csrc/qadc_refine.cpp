@@ -6,7 +6,9 @@
 // exhaustive form of the same call, every held key of the store against a batch of queries: geometry host/refine_knn_plan.hpp,
 // kernels csrc/qadc_refine_knn_kernel.hip.  qadc_refine_range and qadc_refine_rerank_range are the radius
 // query over the same rows — every row, or the candidates of a range result — whose result stays on the store until it is collected:
-// geometry host/refine_range_plan.hpp, kernels csrc/qadc_refine_range_kernel.hip.
+// geometry host/refine_range_plan.hpp, kernels csrc/qadc_refine_range_kernel.hip.  qadc_refine_knn_probed is
+// knn over the rows of the partitions of a float-ADC index that each query probes, keyed as the scan keys them and gathered through
+// the store: geometry host/refine_probe_plan.hpp, kernels csrc/qadc_refine_probe_kernel.hip; the index is read through adc_probe_view.
 //
 // Every array of the *_device calls is read and written by kernels only, so memory of another HIP runtime (torch tensors) is
 // legal; for the same reason the library cannot ask which device such a pointer lives on, and does not: as for
@@ -74,6 +76,12 @@ struct qadc_refine {
     int knn_pass_nq = 0;
     DevBuf<uint64_t> d_knn_buf, d_knn_bound;        // [pass_nq][groups][buf_cap] / [pass_nq][groups]
     DevBuf<uint32_t> d_knn_cnt;                     // [pass_nq][groups]
+    // probed exact search (qadc_refine_knn_probed): knn's knobs and scratch, and beside them the index's
+    // partition table, a pass's work and the probe lists on their way to the host (device form) or to the device (search_exact)
+    DevBuf<qadc::refine::ProbePart> d_probe_parts;
+    DevBuf<qadc::refine::ProbeItem> d_probe_items;
+    DevBuf<uint32_t> d_probe_slots;
+    DevBuf<int32_t> d_probe_assign;
     // exact range search (qadc_refine_range*): the plan's knobs (0: its default), the held result in buffers
     // no other call writes, and the scratch of a pass
     uint64_t range_region_rows = 0, range_chunk_rows = 0, range_reruns = 0;
@@ -505,6 +513,99 @@ int knn_passes(qadc_refine* r, int nq, const float* queries, int R, const adc::S
         HIPCHECK(launch_knn_final(p, plan, r->stream));
     }
     HIPCHECK(hipStreamSynchronize(r->stream));
+    return QADC_OK;
+}
+
+// What a probed call reads of its index: the partitions and the set filter (qadc_host.h: adc_probe_view)
+struct ProbeIndex {
+    std::vector<qadc::host::AdcProbePart> parts;
+    adc::ScanFilter filter;
+};
+
+int check_probed(const qadc_refine* r, const qadc_adc_index* idx, int nq, const float* queries, int ma, const int32_t* assign, int R,
+                 const qadc_adc_filter* filter, adc::ScanFilter* scan, const uint32_t* out_keys, const float* out_dist, const int32_t* out_sizes,
+                 ProbeIndex* pi) {
+    if (int rc = check_knn(r, nq, queries, R, filter, scan, out_keys, out_dist, out_sizes)) return rc;
+    int idev = -1;
+    if (int rc = qadc::host::adc_probe_view(idx, &pi->parts, &idev, &pi->filter)) return rc;
+    if (idev != r->device)
+        return fail(QADC_E_ARG, "the index is on device " + std::to_string(idev) + " and the store on device " + std::to_string(r->device));
+    if (ma < 1 || (size_t)ma > pi->parts.size())
+        return fail(QADC_E_ARG, "ma is 1 .. the index's partitions (" + std::to_string(pi->parts.size()) + ")");
+    if (nq && !assign) return fail(QADC_E_ARG, "assign must not be null");
+    return QADC_OK;
+}
+
+// The passes of a probed search: every array in device memory but assign [nq][ma], which the planner reads on the host; the stream
+// is drained before the call returns.
+int probed_passes(qadc_refine* r, const ProbeIndex& pi, int nq, const float* queries, int ma, const int32_t* assign, int R,
+                  const adc::ScanFilter& filter, uint32_t* out_keys, float* out_dist, int32_t* out_sizes, uint64_t* missing_out) {
+    ProbePlan plan;
+    if (!probe_plan(nq, ma, r->dim, R, r->knn_chunk_rows, r->knn_pass_nq, &plan))
+        return fail(QADC_E_ARG, "no launch geometry for this call (qadc_refine_set_knn_plan: R + chunk_rows is at most " + std::to_string(kKnnMaxSort) +
+                                    ", and chunk_rows at least the probes of a query that share a group, ceil(ma / groups))");
+    const int parts = (int)pi.parts.size();
+    std::vector<ProbePart> table((size_t)parts);
+    std::vector<uint32_t> part_rows((size_t)parts);
+    for (int p = 0; p < parts; ++p) {
+        table[p] = ProbePart{pi.parts[p].labels, pi.parts[p].key_base, pi.parts[p].rows};
+        part_rows[p] = pi.parts[p].rows;
+    }
+    const size_t slots = (size_t)plan.pass_nq * plan.groups;
+    HIPCHECK(r->d_knn_buf.ensure(slots * (size_t)plan.buf_cap));
+    HIPCHECK(r->d_knn_bound.ensure(slots));
+    HIPCHECK(r->d_knn_cnt.ensure(slots));
+    HIPCHECK(r->d_probe_parts.ensure(std::max<size_t>(parts, 1)));
+    HIPCHECK(r->d_probe_items.ensure((size_t)plan.pass_nq * ma));
+    HIPCHECK(r->d_probe_slots.ensure((size_t)plan.pass_nq * ma));
+    HIPCHECK(r->d_missing.ensure(1));
+    HIPCHECK(hipMemsetAsync(r->d_missing.p, 0, sizeof(unsigned long long), r->stream));
+    if (parts) HIPCHECK(hipMemcpyAsync(r->d_probe_parts.p, table.data(), (size_t)parts * sizeof(ProbePart), hipMemcpyHostToDevice, r->stream));
+    std::vector<ProbeWork> works((size_t)plan.passes);   // (alive until the stream is drained: their arrays are uploaded from where they lie)
+    for (int q0 = 0, pass = 0; q0 < nq; q0 += plan.pass_nq, ++pass) {
+        ProbeWork& w = works[pass];
+        ProbePass p;
+        p.nq = std::min(plan.pass_nq, nq - q0);
+        probe_work(plan, p.nq, ma, assign + (size_t)q0 * ma, part_rows.data(), parts, &w);
+        p.rows = r->data;
+        p.elem = r->elem_type();
+        p.sq = r->sq();
+        p.dim = r->dim;
+        p.lo = r->lo;
+        p.nrows = r->rows;
+        p.tkey = r->keyed ? r->table.key : nullptr;
+        p.trow = r->table.row;
+        p.tbits = r->table.bits;
+        p.parts = r->d_probe_parts.p;
+        p.index_filter = pi.filter;
+        p.filter = filter;
+        p.R = R;
+        p.queries = queries + (size_t)q0 * r->dim;
+        p.items = r->d_probe_items.p;
+        p.slots = r->d_probe_slots.p;
+        p.buf = r->d_knn_buf.p;
+        p.cnt = r->d_knn_cnt.p;
+        p.bound = r->d_knn_bound.p;
+        p.missing = r->d_missing.p;
+        p.out_keys = out_keys + (size_t)q0 * R;
+        p.out_dist = out_dist + (size_t)q0 * R;
+        p.out_sizes = out_sizes + q0;
+        if (!w.items.empty()) {
+            HIPCHECK(hipMemcpyAsync(r->d_probe_items.p, w.items.data(), w.items.size() * sizeof(ProbeItem), hipMemcpyHostToDevice, r->stream));
+            HIPCHECK(hipMemcpyAsync(r->d_probe_slots.p, w.slots.data(), w.slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, r->stream));
+        }
+        HIPCHECK(hipMemsetAsync(p.cnt, 0, slots * sizeof(uint32_t), r->stream));
+        HIPCHECK(hipMemsetAsync(p.bound, 0xFF, slots * sizeof(uint64_t), r->stream));
+        for (uint64_t l = 0; l < w.launches; ++l) {
+            HIPCHECK(launch_probe_dist(p, plan, ProbeLaunch{w.launch_items[(size_t)l], w.launch_slices[(size_t)l], w.slice_rows, l}, r->stream));
+            HIPCHECK(launch_probe_select(p, plan, r->stream));
+        }
+        HIPCHECK(launch_probe_final(p, plan, r->stream));
+    }
+    unsigned long long missing = 0;
+    HIPCHECK(hipMemcpyAsync(&missing, r->d_missing.p, sizeof(missing), hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    if (missing_out) *missing_out = missing;
     return QADC_OK;
 }
 
@@ -999,6 +1100,7 @@ int qadc_refine_destroy(qadc_refine* r) {
     r->d_stage.release(); r->d_words.release(); r->d_missing.release(); r->d_queries.release(); r->d_values.release();
     r->d_out_dist.release(); r->d_keys.release(); r->d_out_keys.release(); r->d_counts.release(); r->d_out_sizes.release();
     r->d_knn_buf.release(); r->d_knn_bound.release(); r->d_knn_cnt.release();
+    r->d_probe_parts.release(); r->d_probe_items.release(); r->d_probe_slots.release(); r->d_probe_assign.release();
     r->d_rkeys.release(); r->d_rdist.release(); r->d_rbuf.release(); r->d_rtmp.release(); r->d_rmeta.release(); r->d_rkept.release();
     r->d_rchunks.release();
     delete r;
@@ -1138,6 +1240,59 @@ int qadc_refine_knn_device(qadc_refine* r, int nq, const float* d_queries, int R
     DeviceGuard guard;
     HIPCHECK(hipSetDevice(r->device));
     return knn_passes(r, nq, d_queries, R, scan, d_out_keys, d_out_dist, d_out_sizes);
+}
+
+int qadc_refine_knn_probed(qadc_refine* r, const qadc_adc_index* idx, int nq, const float* queries, int ma, const int32_t* assign, int R,
+                           const qadc_adc_filter* filter, uint32_t* out_keys, float* out_dist, int32_t* out_sizes, uint64_t* missing_out) {
+    adc::ScanFilter scan;
+    ProbeIndex pi;
+    if (int rc = check_probed(r, idx, nq, queries, ma, assign, R, filter, &scan, out_keys, out_dist, out_sizes, &pi)) return rc;
+    for (size_t i = 0; i < (size_t)nq * ma; ++i)
+        if (assign[i] < 0 || (size_t)assign[i] >= pi.parts.size())
+            return fail(QADC_E_ARG, "assign[" + std::to_string(i) + "] = " + std::to_string(assign[i]) + " is not a partition (" +
+                                        std::to_string(pi.parts.size()) + " partitions)");
+    if (missing_out) *missing_out = 0;
+    if (nq == 0) return QADC_OK;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    const size_t nout = (size_t)nq * R;
+    HIPCHECK(r->d_queries.ensure((size_t)nq * r->dim));
+    HIPCHECK(r->d_out_keys.ensure(nout));
+    HIPCHECK(r->d_out_dist.ensure(nout));
+    HIPCHECK(r->d_out_sizes.ensure(nq));
+    HIPCHECK(hipMemcpyAsync(r->d_queries.p, queries, (size_t)nq * r->dim * 4, hipMemcpyHostToDevice, r->stream));
+    uint64_t missing = 0;
+    if (int rc = probed_passes(r, pi, nq, r->d_queries.p, ma, assign, R, scan, r->d_out_keys.p, r->d_out_dist.p, r->d_out_sizes.p, &missing)) return rc;
+    HIPCHECK(hipMemcpyAsync(out_keys, r->d_out_keys.p, nout * 4, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipMemcpyAsync(out_dist, r->d_out_dist.p, nout * 4, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipMemcpyAsync(out_sizes, r->d_out_sizes.p, (size_t)nq * 4, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    if (missing_out) *missing_out = missing;
+    return QADC_OK;
+}
+
+int qadc_refine_knn_probed_device(qadc_refine* r, const qadc_adc_index* idx, int nq, const float* d_queries, int ma, const int32_t* d_assign, int R,
+                                  const qadc_adc_filter* filter, uint32_t* d_out_keys, float* d_out_dist, int32_t* d_out_sizes,
+                                  uint64_t* missing_out) {
+    const void* const d_ptrs[] = {d_queries, d_assign, d_out_keys, d_out_dist, d_out_sizes};
+    const char* const d_names[] = {"d_queries", "d_assign", "d_out_keys", "d_out_dist", "d_out_sizes"};
+    for (int i = 0; i < 5; ++i)
+        if (int rc = check_aligned(d_ptrs[i], 4, d_names[i])) return rc;
+    adc::ScanFilter scan;
+    ProbeIndex pi;
+    if (int rc = check_probed(r, idx, nq, d_queries, ma, d_assign, R, filter, &scan, d_out_keys, d_out_dist, d_out_sizes, &pi)) return rc;
+    if (missing_out) *missing_out = 0;
+    if (nq == 0) return QADC_OK;
+    DeviceGuard guard;
+    HIPCHECK(hipSetDevice(r->device));
+    // the probe numbers cross the bus: the planner inverts them on the host (a kernel copies them out of the caller's memory first)
+    const size_t n = (size_t)nq * ma;
+    std::vector<int32_t> assign(n);
+    HIPCHECK(r->d_probe_assign.ensure(n));
+    HIPCHECK(adc::launch_adc_copy_words(d_assign, r->d_probe_assign.p, n, r->stream));
+    HIPCHECK(hipMemcpyAsync(assign.data(), r->d_probe_assign.p, n * 4, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(hipStreamSynchronize(r->stream));
+    return probed_passes(r, pi, nq, d_queries, ma, assign.data(), R, scan, d_out_keys, d_out_dist, d_out_sizes, missing_out);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include "../host/refine_keyed_plan.hpp"
 #include "../host/refine_knn_plan.hpp"
 #include "../host/refine_plan.hpp"
+#include "../host/refine_probe_plan.hpp"
 #include "../host/refine_range_plan.hpp"
 #include "qadc_adc_kernels.h"   // ScanFilter
 
@@ -129,6 +130,54 @@ hipError_t launch_knn_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launc
 hipError_t launch_knn_select(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream);
 // refine_knn_final_kernel: the groups' lists merged: the first R words, the fillers behind them and the size of every query
 hipError_t launch_knn_final(const KnnPass& p, const KnnPlan& plan, hipStream_t stream);
+
+// ---- probed exact search (qadc_refine_knn_probed; kernels: csrc/qadc_refine_probe_kernel.hip; geometry:
+// host/refine_probe_plan.hpp).  One pass of the plan over nq queries; every pointer is device memory touched by kernels only. ----
+
+// A partition of the index as the kernel reads it: row i has the key labels[i], or key_base + i where labels is null
+struct ProbePart {
+    const uint32_t* labels;
+    uint32_t key_base;
+    uint32_t rows;
+};
+
+struct ProbePass {
+    const void* rows;              // the store's rows, `elem` says which element type
+    Elem elem;
+    SqParams sq;
+    int dim;
+    uint32_t lo;                   // a dense store: the keys [lo, lo + nrows)
+    uint64_t nrows;
+    const uint32_t* tkey;          // a keyed store: its table [2^tbits]; else null
+    const uint32_t* trow;
+    int tbits;
+    const ProbePart* parts;        // [partitions of the index]
+    adc::ScanFilter index_filter;  // the index's set filter and the call's (bitmap null: none); a key passes both
+    adc::ScanFilter filter;
+    int nq, R;
+    const float* queries;          // [nq][dim]
+    const ProbeItem* items;        // the pass's work (ProbeWork)
+    const uint32_t* slots;
+    uint64_t* buf;                 // scratch [nq][groups][buf_cap] words
+    uint32_t* cnt;                 // scratch [nq][groups] (zero before the first launch)
+    uint64_t* bound;               // scratch [nq][groups] (~0 before the first launch)
+    unsigned long long* missing;   // += the entries of the pass whose key the store does not hold
+    uint32_t* out_keys;            // [nq][R]
+    float* out_dist;               // [nq][R]
+    int32_t* out_sizes;            // [nq]
+};
+// One distance launch of a pass: ProbeWork's launch_items[launch], launch_slices[launch] and slice_rows
+struct ProbeLaunch {
+    uint32_t items, slices;
+    int slice_rows;
+    uint64_t launch;
+};
+// refine_probe_dist_kernel<Row, Lookup, QT, J>: the words of the launch's rows that are <= their (query, group)'s bound, appended
+hipError_t launch_probe_dist(const ProbePass& p, const ProbePlan& plan, const ProbeLaunch& l, hipStream_t stream);
+// refine_probe_select_kernel: every buffer that holds at least R words keeps its first R distinct ones, sorted; bound = the R-th
+hipError_t launch_probe_select(const ProbePass& p, const ProbePlan& plan, hipStream_t stream);
+// refine_probe_final_kernel: the groups' lists merged, equal words once: the first R, the fillers behind them and the size of every query
+hipError_t launch_probe_final(const ProbePass& p, const ProbePlan& plan, hipStream_t stream);
 
 // ---- exact range search (qadc_refine_range, qadc_refine_rerank_range; kernels:
 // csrc/qadc_refine_range_kernel.hip; geometry: host/refine_range_plan.hpp).  Every pointer is device memory touched by kernels only. ----

@@ -10,9 +10,7 @@
 // lanes that own the components 64 j + l with ds_bpermute, so that the definition's summation order holds.
 // The keyed store: refine_dist_kernel finds a candidate's row through a lookup policy, DenseLookup (the
 // range test) or KeyedLookup (a probe of the table); keyed_*_kernel are the put, the remove and the rebuild.
-#include "qadc_refine.h"
-
-#include <hip/hip_fp16.h>
+#include "qadc_refine_dev.h"
 
 #include <cfloat>
 #include <type_traits>
@@ -21,73 +19,6 @@ namespace qadc {
 namespace refine {
 
 namespace {
-
-constexpr uint32_t kNanImage = 0x7FC00000u;
-constexpr uint32_t kInfImage = 0x7F800000u;
-constexpr uint64_t kNoWord = ~0ull;
-
-struct sq8_t {                                        // a component of an SQ8 row
-    uint8_t b;
-};
-
-// component i of a row; vmin and step are component i's parameters of an SQ8 store (unused by the other types)
-__device__ inline float row_value(const float* x, int i, float, float) { return x[i]; }
-__device__ inline float row_value(const __half* x, int i, float, float) { return __half2float(x[i]); }
-__device__ inline float row_value(const sq8_t* x, int i, float vmin, float step) {
-    const float m = (float)x[i].b * step;
-    return vmin + m;
-}
-
-// The wide-load form of an SQ8 row: lane l takes the four bytes of the components b .. b + 3 with one load (the row's end is never
-// passed: a dword that would reach over it is put together from the bytes that exist), and sq_lane_byte hands component
-// 64 s + lane of the 256 the wave holds to its lane: it lies in the dword of lane 16 s + lane / 4, at byte lane % 4.  Every lane
-// of the wave calls both, whatever its own component.
-__device__ inline uint32_t sq_load4(const sq8_t* x, int b, int dim) {
-    uint32_t w = 0;
-    if (b + 4 <= dim) {
-        __builtin_memcpy(&w, x + b, 4);               // (no alignment is promised: dim may be odd)
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            if (b + k < dim) w |= (uint32_t)x[b + k].b << (8 * k);
-    }
-    return w;
-}
-
-__device__ inline float sq_lane_value(uint32_t w, int s, int lane, float vmin, float step) {
-    const uint32_t v = (uint32_t)__builtin_amdgcn_ds_bpermute((16 * s + (lane >> 2)) << 2, (int)w);
-    const float m = (float)((v >> (8 * (lane & 3))) & 0xFFu) * step;
-    return vmin + m;
-}
-
-// Where a candidate's row lies.  The key is uniform over the wave, so both are uniform code with no per-lane state.
-struct DenseLookup {                                  // the keys [lo, lo + nrows), row = key - lo
-    uint32_t lo;
-    uint64_t nrows;
-    __device__ inline bool row_of(uint32_t key, uint64_t* row) const {
-        *row = (uint64_t)key - lo;
-        return key >= lo && *row < nrows;
-    }
-};
-
-struct KeyedLookup {                                  // linear probing from the key's home slot; the table is at most half used
-    const uint32_t* __restrict__ tkey;
-    const uint32_t* __restrict__ trow;
-    int bits;
-    __device__ inline bool row_of(uint32_t key, uint64_t* row) const {
-        if (key == kKeyedEmpty) return false;         // (rerank's filler key: never held)
-        const uint32_t mask = (1u << bits) - 1u;
-        for (uint32_t s = keyed_slot(key, bits);; s = (s + 1u) & mask) {
-            const uint32_t k = tkey[s];
-            if (k == key) {                           // live, or dead: a removed key is missing
-                const uint32_t r = trow[s];
-                *row = r;
-                return r != kKeyedNoRow;
-            }
-            if (k == kKeyedEmpty) return false;
-        }
-    }
-};
 
 // Lane l of a wave owns the partial sum p[l] of the definition: the components 64 j + l, in ascending j, then the tree at the
 // strides 32 .. 1 (lane l < s adds lane l + s; what the lanes at and above s compute is never read by a lane below).

@@ -4,9 +4,7 @@
 //                                       its distance to every query of the tile; the words that pass the bound are appended
 //   refine_knn_select_kernel            one workgroup per (query, group): the buffer's first R words, the bound lowered to the R-th
 //   refine_knn_final_kernel             one workgroup per query: the groups' lists merged, the outputs written
-#include "qadc_refine.h"
-
-#include <hip/hip_fp16.h>
+#include "qadc_refine_dev.h"
 
 #include <type_traits>
 
@@ -14,32 +12,6 @@ namespace qadc {
 namespace refine {
 
 namespace {
-
-constexpr uint32_t kNanImage = 0x7FC00000u;
-constexpr uint32_t kInfImage = 0x7F800000u;
-constexpr uint64_t kNoWord = ~0ull;
-
-struct sq8_t {                                        // a component of an SQ8 row
-    uint8_t b;
-};
-
-// component i of a row; vmin and step are component i's parameters of an SQ8 store (unused by the other types)
-__device__ inline float row_value(const float* x, int i, float, float) { return x[i]; }
-__device__ inline float row_value(const __half* x, int i, float, float) { return __half2float(x[i]); }
-__device__ inline float row_value(const sq8_t* x, int i, float vmin, float step) {
-    const float m = (float)x[i].b * step;
-    return vmin + m;
-}
-
-// ScanFilter's rule (csrc/qadc_adc_kernels.h): a key is marked where it lies in [lo, lo + last] and its bit is set; EXCLUDE drops
-// the marked keys, ALLOW keeps only them.  The bitmap has one word at least and a key outside the span reads none.
-__device__ inline bool knn_passes(const adc::ScanFilter& f, uint32_t key) {
-    const uint32_t d = key - f.lo;
-    const bool marked = d <= f.last && ((f.bitmap[d >> 5] >> (d & 31u)) & 1u);
-    return marked == (f.mode == adc::kFilterAllow);
-}
-
-constexpr int knn_log2(int n) { return n <= 1 ? 0 : 1 + knn_log2(n / 2); }
 
 // Lane l keeps the components 64 j + l of the tile's queries and of the row, so p[q] is lane l's partial sum p[l] of the definition
 // for query q: j ascending, t = q - x, t * t and p + tt each rounded alone.  A component that does not exist is 0 in both (register
@@ -65,7 +37,7 @@ __global__ __launch_bounds__(kKnnWaves * 64) void refine_knn_dist_kernel(const R
                                                                          uint64_t* __restrict__ buf, uint32_t* __restrict__ cnt,
                                                                          const uint64_t* __restrict__ bound) {
     extern __shared__ float s_tile[];   // LDS tile (J == 0): [QT][dim]
-    constexpr int kLog = knn_log2(QT), kShift = 6 - kLog, JR = J > 0 ? J : 1;
+    constexpr int kShift = 6 - knn_log2(QT), JR = J > 0 ? J : 1;
     constexpr bool kSq = std::is_same<Row, sq8_t>::value;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int q0 = blockIdx.x * QT, group = blockIdx.y / slices, slice = blockIdx.y % slices;
@@ -132,23 +104,7 @@ __global__ __launch_bounds__(kKnnWaves * 64) void refine_knn_dist_kernel(const R
                 }
             }
         }
-        // (constant trip counts: every index of p below is a compile-time constant once unrolled, so p stays in registers)
-#pragma unroll
-        for (int k = 0; k < kLog; ++k) {
-            const int h = QT >> (k + 1), s = 32 >> k;
-            const bool up = (lane & s) != 0;
-#pragma unroll
-            for (int i = 0; i < QT / 2; ++i)
-                if (i < h) {
-                    const float a = p[i], b = p[i + h];   // (values first: a conditional over the two elements would be an lvalue,
-                    const float send = up ? a : b;        // and p an array indexed per lane)
-                    const float keep = up ? b : a;
-                    p[i] = keep + __shfl_xor(send, s, 64);
-                }
-        }
-        float v = p[0];
-#pragma unroll
-        for (int s = (1 << kShift) >> 1; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
+        const float v = knn_fold<QT>(p, lane);
         if (emitter) {
             uint32_t img = __float_as_uint(v);
             if (v != v) img = kNanImage;
@@ -159,29 +115,6 @@ __global__ __launch_bounds__(kKnnWaves * 64) void refine_knn_dist_kernel(const R
             }
         }
     }
-}
-
-// s[0 .. n) sorted ascending, n a power of two, by the T threads of the workgroup: refine_select_kernel's bitonic network
-__device__ inline void knn_sort(uint64_t* s, int n, int tid, int T) {
-    for (int k = 2; k <= n; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int t = tid; t < n / 2; t += T) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const uint64_t a = s[i], b = s[l];
-                if ((a > b) == ((i & k) == 0)) {
-                    s[i] = b;
-                    s[l] = a;
-                }
-            }
-        }
-    __syncthreads();
-}
-
-__device__ inline int knn_sort_size(uint32_t n) {
-    int p = 64;
-    while ((uint32_t)p < n) p <<= 1;
-    return p;
 }
 
 // grid (nq, groups of the launch).  A buffer with fewer than R words, or with the R words the last select left, stays as it is.

@@ -19,6 +19,9 @@
 // Exhaustive search (knn, at the end): the selection above over every key the store holds that passes a
 // key filter — the definition of qadc_refine_knn.
 //
+// Probed exact search (knn_probed, behind knn): the selection above over the rows of the partitions of an index
+// that a query probes, keyed as the scan keys them — the definition of qadc_refine_knn_probed.
+//
 // Exact range search (range and rerank_range, at the end): every held key whose distance is below a radius,
 // over the whole store or over candidate lists of any length — the definition of qadc_refine_range and qadc_refine_rerank_range.
 //
@@ -480,6 +483,54 @@ inline void knn(const Store& s, int nq, const float* queries, int R, const filte
         rerank(s, 1, queries + (size_t)q * s.dim, n, keys.data(), nullptr, nullptr, R, out_keys + (size_t)q * R, out_dist + (size_t)q * R,
                out_sizes + q);
     }
+}
+
+// ---- probed exact search (qadc_refine_knn_probed) ----
+// A partition of an index as the search reads it: row i has the key labels[i], or key_base + i where labels is null (the rule of
+// adc::Source in the scan).
+struct probe_part {
+    const uint32_t* labels;
+    uint32_t key_base;
+    uint64_t rows;
+};
+
+// The R nearest rows among the partitions each query probes.  assign [nq][ma]: P_q is the set of distinct partition numbers of
+// query q's list that lie in [0, nparts) — a repeat counts once; a number outside is skipped here (the device form's rule; the
+// host form of the C-ABI refuses it before this is reached).  Every row of every p in P_q, partitions in the order of their first
+// occurrence and rows ascending, contributes one entry, its key, unless the key fails index_filter (the index's set filter) or f
+// (the call's); either may be null.  The result is rerank fed q's entries, with no limit on their number: an entry whose key the
+// store does not hold is missing and counted in the return value, per entry; a key that occurs several times is kept once.
+template <typename Store>
+inline uint64_t knn_probed(const Store& s, const probe_part* parts, int nparts, const filter* index_filter, int nq, const float* queries,
+                           int ma, const int32_t* assign, int R, const filter* f, uint32_t* out_keys, float* out_dist, int32_t* out_sizes) {
+    uint64_t missing = 0;
+    std::vector<uint32_t> keys;
+    std::vector<int32_t> probed;
+    for (int q = 0; q < nq; ++q) {
+        keys.clear();
+        probed.clear();
+        for (int j = 0; j < ma; ++j) {
+            const int32_t p = assign[(size_t)q * ma + j];
+            if (p < 0 || p >= nparts || std::find(probed.begin(), probed.end(), p) != probed.end()) continue;
+            probed.push_back(p);
+            for (uint64_t i = 0; i < parts[p].rows; ++i) {
+                const uint32_t key = parts[p].labels ? parts[p].labels[i] : (uint32_t)(parts[p].key_base + i);
+                if ((index_filter && !index_filter->passes(key)) || (f && !f->passes(key))) continue;
+                keys.push_back(key);
+            }
+        }
+        if (keys.empty()) {              // (rerank takes r_in >= 1)
+            for (int j = 0; j < R; ++j) {
+                out_keys[(size_t)q * R + j] = kNoKey;
+                out_dist[(size_t)q * R + j] = bits_float(kInfImage);
+            }
+            out_sizes[q] = 0;
+            continue;
+        }
+        missing += rerank(s, 1, queries + (size_t)q * s.dim, (int)keys.size(), keys.data(), nullptr, nullptr, R, out_keys + (size_t)q * R,
+                          out_dist + (size_t)q * R, out_sizes + q);
+    }
+    return missing;
 }
 
 // ---- exact range search (qadc_refine_range, qadc_refine_rerank_range) ----

@@ -1,7 +1,8 @@
 // refine_store_hip — C++14 RAII mirror of the refine store (qadc_refine_* in include/qadc.h; DESIGN.md sections 11.11, 11.14 and 11.20): the
 // original vectors in device memory, dense over the keys [lo, lo + rows) or, with keyed = true, a map from key to vector filled by
 // put() and emptied by remove(); rerank(), which reorders candidate keys by their exact squared L2 distance to them; range() and
-// rerank_range(), the exact radius query over the whole store and over a range result (section 11.21).  search_refined() composes it with adc_search_engine_hip (host/adc_search_hip.hpp): the engine's search with
+// rerank_range(), the exact radius query over the whole store and over a range result (section 11.21); knn_probed() and search_exact(),
+// the exact search over the partitions of an index a query probes (section 11.22).  search_refined() composes it with adc_search_engine_hip (host/adc_search_hip.hpp): the engine's search with
 // R = the engine's r as r_in, then the re-ranking of the heaps' keys, the FLT_MAX sentinels left out.  The definition both are held
 // to is host/refine.hpp.
 #pragma once
@@ -129,6 +130,31 @@ struct refine_store_hip {
         if (qadc_refine_knn_device(store, nq, d_queries, r, filter, d_keys, d_dist, d_sizes) != QADC_OK) die("knn_device");
     }
 
+    // Probed exact search (qadc_refine_knn_probed): queries [nq][dim], assign [nq][ma] -> per query the first
+    // r, by (exact distance, key), of the keys of every row of the partitions of `index` its list probes; a key must pass the index's
+    // filter and `filter`, a key not held is counted in `missing`, a key reached through several rows is kept once
+    refine_result knn_probed(const qadc_adc_index* index, int nq, const float* queries, int ma, const std::int32_t* assign, int r,
+                             const qadc_adc_filter* filter = nullptr) {
+        refine_result out;
+        out.r = r;
+        out.keys.resize((std::size_t)nq * r);
+        out.dist.resize((std::size_t)nq * r);
+        out.sizes.resize(nq);
+        if (qadc_refine_knn_probed(store, index, nq, queries, ma, assign, r, filter, out.keys.data(), out.dist.data(), out.sizes.data(),
+                                   &out.missing) != QADC_OK)
+            die("knn_probed");
+        return out;
+    }
+
+    // the same with every array in device memory of the store's device; returns the missing count
+    std::uint64_t knn_probed_device(const qadc_adc_index* index, int nq, const float* d_queries, int ma, const std::int32_t* d_assign, int r,
+                                    const qadc_adc_filter* filter, std::uint32_t* d_keys, float* d_dist, std::int32_t* d_sizes) {
+        std::uint64_t missing = 0;
+        if (qadc_refine_knn_probed_device(store, index, nq, d_queries, ma, d_assign, r, filter, d_keys, d_dist, d_sizes, &missing) != QADC_OK)
+            die("knn_probed_device");
+        return missing;
+    }
+
     // a tuning and test knob (qadc_refine_set_knn_plan): 0 = the plan's default; no value changes a result
     void set_knn_plan(std::uint64_t chunk_rows, int pass_nq) {
         if (qadc_refine_set_knn_plan(store, chunk_rows, pass_nq) != QADC_OK) die("set_knn_plan");
@@ -185,6 +211,25 @@ inline refine_result search_refined(adc_search_engine_hip<Db>& e, refine_store_h
     refine_result out = store.rerank(nq, queries, e.r, keys.data(), nullptr, vals.data(), r);
     if (cand_keys) cand_keys->swap(keys);
     if (cand_vals) cand_vals->swap(vals);
+    return out;
+}
+
+// Exact search over the partitions the engine would probe (qadc_adc_search_exact): the engine's coarse step at
+// its ma, then store.knn_probed on the probe lists — the ceiling of search_refined at the same ma.  assign (may be null) receives the
+// probe lists [nq][e.ma].
+template <typename Db>
+inline refine_result search_exact(adc_search_engine_hip<Db>& e, refine_store_hip& store, int nq, const float* queries, int r,
+                                  const qadc_adc_filter* filter = nullptr, std::vector<std::int32_t>* assign = nullptr) {
+    refine_result out;
+    out.r = r;
+    out.keys.resize((std::size_t)nq * r);
+    out.dist.resize((std::size_t)nq * r);
+    out.sizes.resize(nq);
+    std::vector<std::int32_t> probes((std::size_t)nq * e.ma);
+    if (qadc_adc_search_exact(e.index, store.store, nq, queries, e.ma, r, e.sum_mode, filter, out.keys.data(), out.dist.data(), out.sizes.data(),
+                              &out.missing, probes.data()) != QADC_OK)
+        adc_search_engine_hip<Db>::die("search_exact");
+    if (assign) assign->swap(probes);
     return out;
 }
 

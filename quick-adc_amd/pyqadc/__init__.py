@@ -63,6 +63,8 @@ SYMBOLS = [
     "qadc_refine_create_keyed", "qadc_refine_put", "qadc_refine_put_device", "qadc_refine_remove", "qadc_refine_remove_device",
     "qadc_refine_keyed_info", "qadc_refine_keyed_slot",
     "qadc_refine_knn", "qadc_refine_knn_device", "qadc_refine_set_knn_plan",
+    "qadc_refine_knn_probed", "qadc_refine_knn_probed_device", "qadc_adc_index_assign", "qadc_adc_index_assign_device",
+    "qadc_adc_search_exact", "qadc_adc_search_exact_device",
     "qadc_refine_create_sq8", "qadc_refine_sq_range_host", "qadc_refine_sq_range_device", "qadc_refine_sq_info", "qadc_refine_get",
     "qadc_refine_get_device",
     "qadc_pq_decode_host", "qadc_pq_decode_device", "qadc_adc_index_reconstruct", "qadc_adc_index_reconstruct_device",
@@ -330,6 +332,16 @@ def lib():
         L.qadc_refine_knn.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_void_p, u32p, f32p, i32p]
         L.qadc_refine_knn_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qadc_refine_set_knn_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+        L.qadc_refine_knn_probed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, C.c_int, i32p, C.c_int, C.c_void_p, u32p, f32p, i32p,
+                                             C.POINTER(C.c_uint64)]
+        L.qadc_refine_knn_probed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.qadc_adc_index_assign.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_int, i32p]
+        L.qadc_adc_index_assign_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.qadc_adc_search_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, u32p, f32p, i32p,
+                                            C.POINTER(C.c_uint64), i32p]
+        L.qadc_adc_search_exact_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
         L.qadc_refine_create_sq8.argtypes = [C.POINTER(C.c_void_p), C.c_int, f32p, f32p, C.c_int, C.c_int]
         L.qadc_refine_sq_range_host.argtypes = [f32p, C.c_uint64, C.c_int, C.c_int, f32p, f32p]
         L.qadc_refine_sq_range_device.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, f32p, f32p]
@@ -1568,6 +1580,15 @@ class Index(_RowStoreMixin):
         got = self.search(q, ma, r_in)
         return store.rerank(q, got["keys"], R, counts=got["sizes"])
 
+    def search_exact(self, queries, ma, R, store, sum_mode=1, filter=None):
+        """AdcIndex.search_exact through a view of this (finalized) index: the exact nearest rows of the Refine `store` among the
+        partitions the queries probe -> (keys, dist, sizes, missing, assign)."""
+        view = AdcIndex.view_of(self)
+        try:
+            return view.search_exact(queries, ma, R, store, sum_mode=sum_mode, filter=filter)
+        finally:
+            view.close()
+
     def search_submit(self, slot, queries, ma, R):
         """Asynchronous (slot 0..3) form of search(): enqueue a batch, collect it later (overlaps the host replay of
         one batch with the GPU work of the next)."""
@@ -2005,6 +2026,60 @@ class AdcIndex(_RowStoreMixin):
         uint32 bits, dist float32 [nq][R], sizes int32 [nq]) in device memory out, and the missing count; nothing else crosses the bus."""
         keys, vals, _ = self.search_device(queries, ma, r_in, table_form, sum_mode, filters=filters)
         return store.rerank_device(queries, keys, R, values=vals)
+
+    # ---- the coarse step alone, and exact search over the probed partitions (qadc_adc_index_assign*, qadc_adc_search_exact*;
+    # DESIGN.md section 11.22) ----
+    def assign(self, queries, ma, sum_mode=1):
+        """queries [nq][dim] -> assign int32 [nq][ma]: the probe lists search() reports (all zero on an index without coarse centroids)"""
+        q = self._queries(queries)
+        assign = np.zeros((q.shape[0], ma), np.int32)
+        _check(lib().qadc_adc_index_assign(self._h, q.shape[0], _p(q, f32p), ma, sum_mode, _p(assign, i32p)))
+        return assign
+
+    def assign_device(self, queries, ma, sum_mode=1):
+        """assign() on a float32 tensor [nq][dim] of the index's device -> an int32 tensor [nq][ma] on that device"""
+        import torch
+        if getattr(queries, "ndim", 0) != 2:
+            raise TypeError("queries must be a 2-d torch.Tensor")
+        nq = int(queries.shape[0])
+        q = self._device_tensor(queries, (nq, getattr(self, "dim", int(queries.shape[1]))), "queries")
+        dev = torch.device("cuda", self.device)
+        assign = torch.zeros((nq, int(ma)), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(lib().qadc_adc_index_assign_device(self._h, nq, q.data_ptr(), ma, sum_mode, assign.data_ptr()))
+        return assign
+
+    def search_exact(self, queries, ma, R, store, sum_mode=1, filter=None):
+        """assign(queries, ma), then store.knn_probed on its lists -> (keys uint32 [nq][R], dist float32 [nq][R], sizes [nq], missing,
+        assign [nq][ma]): the exact nearest rows among the partitions search() would probe — the ceiling of search_refined at the same
+        ma.  filter: an AdcFilter or None, on top of set_filter's."""
+        q = self._queries(queries)
+        nq, R = q.shape[0], int(R)
+        ok = np.zeros((nq, R), np.uint32)
+        od = np.zeros((nq, R), np.float32)
+        osz = np.zeros(nq, np.int32)
+        assign = np.zeros((nq, ma), np.int32)
+        missing = C.c_uint64(0)
+        _check(lib().qadc_adc_search_exact(self._h, store._h, nq, _p(q, f32p), ma, R, sum_mode, None if filter is None else filter._h,
+                                           _p(ok, u32p), _p(od, f32p), _p(osz, i32p), C.byref(missing), _p(assign, i32p)))
+        return ok, od, osz, int(missing.value), assign
+
+    def search_exact_device(self, queries, ma, R, store, sum_mode=1, filter=None):
+        """search_exact() on a float32 tensor [nq][dim] of the index's device -> tensors (keys int32 [nq][R] carrying the uint32 bits,
+        dist float32 [nq][R], sizes int32 [nq]), missing (an int) and assign (int32 [nq][ma]) on that device"""
+        import torch
+        if getattr(queries, "ndim", 0) != 2:
+            raise TypeError("queries must be a 2-d torch.Tensor")
+        nq, R = int(queries.shape[0]), int(R)
+        q = self._device_tensor(queries, (nq, getattr(self, "dim", int(queries.shape[1]))), "queries")
+        keys, dist, sizes = self._device_outputs(nq, R)
+        dev = torch.device("cuda", self.device)
+        assign = torch.zeros((nq, int(ma)), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        missing = C.c_uint64(0)
+        _check(lib().qadc_adc_search_exact_device(self._h, store._h, nq, q.data_ptr(), ma, R, sum_mode, None if filter is None else filter._h,
+                                                  keys.data_ptr(), dist.data_ptr(), sizes.data_ptr(), C.byref(missing), assign.data_ptr()))
+        return keys, dist, sizes, int(missing.value), assign
 
     def search_candidates(self, queries, ma, R, table_form=2, sum_mode=1, filters=None):
         """-> (keys, vals, offsets [nq+1], assign [nq][ma]): the ordered candidate stream, as query_scan_candidates returns it"""
@@ -2580,6 +2655,59 @@ class Refine:
         _check(lib().qadc_refine_knn_device(self._h, nq, q.data_ptr(), R, None if filter is None else filter._h, ok.data_ptr(), od.data_ptr(),
                                             osz.data_ptr()))
         return ok, od, osz
+
+    # ---- probed exact search (qadc_refine_knn_probed) ----
+    def knn_probed(self, index, queries, assign, R, filter=None):
+        """index: an AdcIndex (owned, or a view of a 4-bit index) of the store's device; queries [nq][dim], assign int32 [nq][ma] ->
+        (keys uint32 [nq][R], dist float32 [nq][R], sizes int32 [nq], missing): per query the first R, by (exact squared L2 distance,
+        key), of the keys of every row of the partitions its list probes — rerank() fed those keys with no limit on their number,
+        bit for bit.  A key must pass the index's set_filter and `filter`; a key the store does not hold is missing, per entry; a key
+        reached through several rows is kept once.  An entry of assign outside [0, partitions) raises."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise QadcError("queries has shape %s, expected [nq][%d]" % (q.shape, self.dim))
+        a = np.ascontiguousarray(assign, np.int32)
+        if a.ndim == 1:
+            a = a.reshape(q.shape[0], -1)
+        if a.ndim != 2 or a.shape[0] != q.shape[0]:
+            raise QadcError("assign has shape %s, expected [%d][ma]" % (a.shape, q.shape[0]))
+        return self.knn_probed_raw(index, q.shape[0], q, a.shape[1], a, int(R), filter)
+
+    def knn_probed_raw(self, index, nq, queries, ma, assign, R, filter=None, outputs=True):
+        """The C call as it is (index: an AdcIndex or None; queries, assign: arrays or None; filter: an AdcFilter or None)."""
+        ok = np.zeros((max(nq, 0), max(R, 0)), np.uint32) if outputs else None
+        od = np.zeros((max(nq, 0), max(R, 0)), np.float32) if outputs else None
+        osz = np.zeros(max(nq, 0), np.int32) if outputs else None
+        missing = C.c_uint64(0)
+        _check(lib().qadc_refine_knn_probed(self._h, None if index is None else index._h, nq, _p(queries, f32p), ma, _p(assign, i32p), R,
+                                            None if filter is None else filter._h, _p(ok, u32p), _p(od, f32p), _p(osz, i32p), C.byref(missing)))
+        return ok, od, osz, int(missing.value)
+
+    def knn_probed_device(self, index, queries, assign, R, filter=None, out=None):
+        """knn_probed() on torch tensors of the store's device: queries float32 [nq][dim], assign int32 [nq][ma] -> (keys int32 [nq][R]
+        carrying the uint32 bits, dist float32 [nq][R], sizes int32 [nq]) on that device, and missing (an int).  An entry of assign
+        outside [0, partitions) is skipped.  The probe numbers are read back by the planner; nothing else of the arrays crosses the
+        bus.  out: the three tensors to write into."""
+        import torch
+        if getattr(queries, "ndim", 0) != 2 or getattr(assign, "ndim", 0) != 2:
+            raise TypeError("queries and assign must be 2-d torch.Tensors")
+        nq, ma, R = int(queries.shape[0]), int(assign.shape[1]), int(R)
+        q = self._tensor(queries, "float32", (nq, self.dim), "queries")
+        a = self._tensor(assign, "int32", (nq, ma), "assign")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = (torch.zeros((nq, max(R, 0)), dtype=torch.int32, device=dev), torch.zeros((nq, max(R, 0)), dtype=torch.float32, device=dev),
+                   torch.zeros((nq,), dtype=torch.int32, device=dev))
+        ok = self._tensor(out[0], "int32", (nq, max(R, 0)), "out keys")
+        od = self._tensor(out[1], "float32", (nq, max(R, 0)), "out dist")
+        osz = self._tensor(out[2], "int32", (nq,), "out sizes")
+        self._sync()
+        missing = C.c_uint64(0)
+        _check(lib().qadc_refine_knn_probed_device(self._h, index._h, nq, q.data_ptr(), ma, a.data_ptr(), R, None if filter is None else filter._h,
+                                                   ok.data_ptr(), od.data_ptr(), osz.data_ptr(), C.byref(missing)))
+        return ok, od, osz, int(missing.value)
 
     def set_knn_plan(self, chunk_rows=0, pass_nq=0):
         """qadc_refine_set_knn_plan: the rows of a group per launch and the queries per pass of the later knn calls (0: the plan's

@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn,decode,refine_sq,refine_range] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn,decode,refine_sq,refine_range,probe] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,opq,seed,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,seed,filter] [--iters N] [--out FILE]
 
@@ -83,6 +83,10 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
   decode    PQ decode and reconstruction (not in the default legs; also under --bits 4 at 16x4 and --bits 16 at 2x16; DESIGN.md section
             11.19), dim 128, with and without a rotation: pq_decode_device on 10^6 codes, and reconstruct_device on the keys of a
             1024 x 100 search, each alternated with the route it replaces (read_partition, numpy gather and matmul, upload)
+  probe     probed exact search (not in the default legs), on the ivf_search database (10^6 x 128-d rows,
+            K = 256, ma = 24, R = 100) with batches of 1024, 32 and 1 queries, in one process: AdcIndex.search_exact_device beside
+            Refine.knn_device on the same store (the baseline: every row) and search_refined_device at r_in = 1000; recall@100 against
+            knn of the probed exact result (the coarse quantizer's loss alone) and of search_refined at r_in 400 and 1000.
   knn       exhaustive search over a refine store (not in the default legs): Refine.knn_device and Refine.knn
             on 10^6 rows of dim 128, float and half store, nq = 1, 32 and 1024, R = 100, from call to return, as pairs/s and as a share
             of the estimated roof of 2 x 10^11 pairs/s (3 dim component operations a pair at 32 packed non-FMA float operations per
@@ -212,7 +216,7 @@ def search_legs(legs, iters, res):
     part_of, codes = pyqadc.adc_encode(codebooks, vectors, coarse)
     res["adc_encode_1e6_s"] = time.perf_counter() - t0
     print("adc_encode of 10^6 128-d vectors (K = 256, 8x8), host to host: %.2f s" % res["adc_encode_1e6_s"], flush=True)
-    if "refine" not in legs and "keyed" not in legs and "refine_sq" not in legs and "refine_range" not in legs:
+    if "refine" not in legs and "keyed" not in legs and "refine_sq" not in legs and "refine_range" not in legs and "probe" not in legs:
         del vectors
     order = np.argsort(part_of, kind="stable")
     bounds = np.searchsorted(part_of[order], np.arange(K + 1))
@@ -259,7 +263,9 @@ def search_legs(legs, iters, res):
         refine_sq_leg(idx, vectors, queries, ma, iters, res)
     if "refine_range" in legs:
         refine_range_search_leg(idx, vectors, queries, ma, iters, res)
-    if "refine" in legs or "keyed" in legs or "refine_sq" in legs or "refine_range" in legs:
+    if "probe" in legs:
+        probe_leg(idx, vectors, queries, ma, iters, res)
+    if "refine" in legs or "keyed" in legs or "refine_sq" in legs or "refine_range" in legs or "probe" in legs:
         del vectors
     if "filter" in legs:   # (b): the same search() without a filter and with 10 % of the keys excluded, in turn, under both finishes
         S = rng.permutation(n)[:n // 10].astype(np.uint32)
@@ -469,6 +475,46 @@ def refine_leg(idx, vectors, queries, ma, iters, res):
                   "gather + topk on the same candidates %.3f ms; %.0f MB gathered = %.2f TB/s in the rerank"
                   % (dtype, r_in, R, res[tag + "_recall"], t_search * 1e3, t_rerank * 1e3, t_both * 1e3, t_torch * 1e3,
                      res[tag + "_gather_bytes"] / 1e6, res[tag + "_gather_bytes"] / t_rerank / 1e12), flush=True)
+        st.close()
+
+
+def probe_leg(idx, vectors, queries, ma, iters, res):
+    """exact search over the probed partitions beside the exhaustive search and the re-ranked PQ search"""
+    import torch
+    dev = torch.device("cuda", 0)
+    n, dim = vectors.shape
+    tx = torch.from_numpy(vectors).to(dev)
+    out = res.setdefault("probe", {"rows": n, "dim": dim, "K": idx.partition_count(), "ma": ma, "R": R})
+    for dtype in ("f32", "f16"):
+        st = pyqadc.Refine(dim, dtype)
+        st.add_device(tx)
+        for nq in (1024, 32, 1):
+            tq = torch.from_numpy(queries[:nq]).to(dev)
+            truth = st.knn_device(tq, R)[0].cpu().numpy().view(np.uint32)
+
+            def recall(keys):
+                keys = keys.cpu().numpy().view(np.uint32)
+                return float(np.mean([len(set(truth[q].tolist()) & set(keys[q].tolist())) for q in range(nq)])) / R
+            keys, _, _, missing, assign = idx.search_exact_device(tq, ma, R, st)
+            assert missing == 0
+            probed_rows = float(np.mean([sum(idx.partition_size(int(p)) for p in row) for row in assign.cpu().numpy()]))
+            its = max(5, iters)
+            t_exact, best_exact = timed(lambda: idx.search_exact_device(tq, ma, R, st), its)
+            t_knn, best_knn = timed(lambda: st.knn_device(tq, R), its)
+            t_ref, _ = timed(lambda: idx.search_refined_device(tq, ma, R, 1000, st), its)
+            t_assign, _ = timed(lambda: idx.assign_device(tq, ma), its)
+            row = {"search_exact_device_ms": t_exact * 1e3, "search_exact_device_best_ms": best_exact * 1e3, "knn_device_ms": t_knn * 1e3,
+                   "knn_device_best_ms": best_knn * 1e3, "search_refined_device_rin1000_ms": t_ref * 1e3, "assign_device_ms": t_assign * 1e3,
+                   "rows_probed_per_query": probed_rows, "share_of_rows_probed": probed_rows / n, "recall_probed_exact": recall(keys),
+                   "recall_search_refined_rin400": recall(idx.search_refined_device(tq, ma, R, 400, st)[0]),
+                   "recall_search_refined_rin1000": recall(idx.search_refined_device(tq, ma, R, 1000, st)[0])}
+            out["%s_nq%d" % (dtype, nq)] = row
+            print("probe %s, 10^6 x %d, K %d, ma %d, nq %4d, R %d: search_exact_device %.3f ms (best %.3f; assign alone %.3f) over %.1f %% of the "
+                  "rows; knn_device %.3f ms (best %.3f); search_refined_device(r_in 1000) %.3f ms; recall@%d against knn: probed exact %.4f, "
+                  "search_refined r_in 400 %.4f, r_in 1000 %.4f"
+                  % (dtype, dim, out["K"], ma, nq, R, t_exact * 1e3, best_exact * 1e3, t_assign * 1e3, 100 * probed_rows / n, t_knn * 1e3,
+                     best_knn * 1e3, t_ref * 1e3, R, row["recall_probed_exact"], row["recall_search_refined_rin400"],
+                     row["recall_search_refined_rin1000"]), flush=True)
         st.close()
 
 
@@ -1922,7 +1968,7 @@ def main():
                 f.write(line + "\n")
         return
     torch = None
-    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs or "decode" in legs or "refine_sq" in legs or "refine_range" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs or "decode" in legs or "refine_sq" in legs or "refine_range" in legs or "probe" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:
             import torch
             torch.zeros(1, device="cuda")
@@ -2011,7 +2057,7 @@ def main():
             print("the same alternated with query_scan_device (tables and heaps stay in device memory): %.2f ms against %.2f ms"
                   % (med_d * 1e3, med_h * 1e3), flush=True)
         idx.close()
-    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs or "range" in legs or "keyed" in legs or "refine_sq" in legs or "refine_range" in legs:
+    if "ivf_search" in legs or "lone_search" in legs or "filter" in legs or "qfilter" in legs or "refine" in legs or "range" in legs or "keyed" in legs or "refine_sq" in legs or "refine_range" in legs or "probe" in legs:
         search_legs(legs, a.iters, res)
     if "filter" in legs:
         filter_leg(8, a.iters, res, torch)

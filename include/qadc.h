@@ -1403,7 +1403,8 @@ int qadc_adc_range_collect_device(qadc_adc_index* idx, uint64_t capacity, uint32
  *              (distance, key) — a NaN distance behind +inf, returned as 0x7FC00000 — a key listed several times kept once, and the
  *              first min(R, survivors) come out; the slots behind out_sizes[q] hold key 0xFFFFFFFF and distance +inf.
  * The output is a sorted list, not a heap array, and depends only on the set of candidate keys.  Limits: keys dense from lo; rows are
- * neither removed nor overwritten; r_in <= QADC_REFINE_MAX_IN; L2 only; one device; every call is synchronous. */
+ * neither removed nor overwritten; r_in <= QADC_REFINE_MAX_IN; squared L2 unless the store's metric says inner product
+ * (qadc_refine_set_metric, below); one device; every call is synchronous. */
 #define QADC_REFINE_F32 0
 #define QADC_REFINE_F16 1
 #define QADC_REFINE_MAX_IN 8192   /* most candidates per query a rerank call takes */
@@ -1487,7 +1488,8 @@ uint32_t qadc_refine_keyed_slot(uint32_t key, int table_bits);
  * nothing).  The filter need only be alive for the call and no use is counted on it.  An empty store gives sizes 0 and fillers; R
  * above the rows held is legal.  The result is a function of the store's contents and the arguments alone: no chunk, tile, pass or
  * arrival order shows in it.
- * Limits: every row is read whatever the filter says (a filter saves no time); R <= QADC_REFINE_KNN_MAX_R; L2 only; one device; one
+ * Limits: every row is read whatever the filter says (a filter saves no time); R <= QADC_REFINE_KNN_MAX_R; L2 or inner product
+ * (qadc_refine_set_metric); one device; one
  * filter per call; synchronous, on the store's stream. */
 #define QADC_REFINE_KNN_MAX_R 1024
 /* Host arrays: queries [nq][dim] -> out_keys [nq][R], out_dist [nq][R], out_sizes [nq].  nq = 0 is a no-op.  QADC_E_ARG before the
@@ -1522,7 +1524,7 @@ int qadc_refine_set_knn_plan(qadc_refine* r, uint64_t chunk_rows, int pass_nq);
  * and chunk_rows below the probes of a group is refused); no value changes a result.
  * QADC_E_ARG: what qadc_refine_knn refuses; idx NULL; an index of another device than the store's; ma out of range; a view whose
  * source is sharded or holds borrowed partitions.  QADC_E_STATE: a view whose 4-bit source is not finalized.
- * Limits: no probed range search; L2 only; R <= 1024; one device; one filter per call; synchronous; the rows are gathered through
+ * Limits: no probed range search; L2 or inner product (qadc_refine_set_metric; the probes of qadc_adc_search_exact stay L2); R <= 1024; one device; one filter per call; synchronous; the rows are gathered through
  * the store (there is no partition-ordered copy of them); a single very long partition means many thin launches. */
 /* Host arrays: queries [nq][dim], assign [nq][ma] -> out_keys [nq][R], out_dist [nq][R], out_sizes [nq]; missing_out may be NULL.
  * An entry of assign outside [0, partitions) is QADC_E_ARG before the device is touched. */
@@ -1566,7 +1568,8 @@ int qadc_adc_search_exact_device(qadc_adc_index* idx, qadc_refine* store, int nq
  *            sign-magnitude image (-0 below +0); none: 0 and 0.  vmin = the minimum, step = (max - min) / 255.0f, divided on the
  *            host.  A function of the set alone.  step is +inf where max - min overflows: no store takes such a range.
  * Every call above works on such a store unchanged; qadc_refine_info reports dtype 2 and bytes = capacity x dim.
- * Limits: the range is fixed at creation (no re-encoding); uniform steps only; L2 only; one device. */
+ * Limits: the range is fixed at creation (no re-encoding); uniform steps only; L2 or inner product
+ * (qadc_refine_set_metric); one device. */
 #define QADC_REFINE_SQ8 2
 /* An empty SQ8 store on device_id, dense (keyed = 0) or keyed.  qadc_refine_create and _create_keyed refuse dtype 2: the type needs
  * its parameters.  QADC_E_ARG before the device is touched: out, vmin or step NULL, a bad dim, a vmin[i] or step[i] that is not
@@ -1612,7 +1615,8 @@ int qadc_refine_get_device(qadc_refine* r, const uint32_t* d_keys, uint64_t coun
  * them: the regions of one run of a pass, the candidates of one query, or the rows of the call's whole result exceed
  * QADC_REFINE_RANGE_MAX_ENTRIES.
  * Limits: every row is read, whatever the filter and the radius; the held result and a pass's regions are resident in device memory;
- * a query that keeps more than QADC_REFINE_RANGE_SORT_LDS rows pays the radix passes; L2 only; one device; one filter per call;
+ * a query that keeps more than QADC_REFINE_RANGE_SORT_LDS rows pays the radix passes; L2 only (a store whose metric is QADC_REFINE_IP
+ * refuses the four range calls with QADC_E_STATE); one device; one filter per call;
  * synchronous. */
 #define QADC_REFINE_RANGE_MAX_ENTRIES (1ull << 31) /* most words the regions of one run, and most rows a call's result, may hold */
 #define QADC_REFINE_RANGE_SORT_LDS 4096            /* a query's words up to this many are sorted in LDS, more by radix passes */
@@ -1643,6 +1647,39 @@ int qadc_refine_range_collect_device(qadc_refine* r, uint64_t capacity, uint32_t
 int qadc_refine_set_range_plan(qadc_refine* r, uint64_t region_rows, uint64_t chunk_rows, int pass_nq);
 /* Passes that were run a second time because a region overflowed. */
 uint64_t qadc_refine_range_reruns(const qadc_refine* r);
+
+/* ---- the metric of a store: squared L2 or inner product ----
+ * A property of the store handle, host state only: no device call, no effect on the rows, changeable at any time, QADC_REFINE_L2 at
+ * creation.  Under QADC_REFINE_IP qadc_refine_rerank, _rerank_device, _knn, _knn_device, _knn_probed, _knn_probed_device and what is
+ * composed from them (qadc_adc_search_exact*, a search followed by a rerank) rank by the inner product — maximum-inner-product
+ * search; cosine through rows and queries normalised before add.  Held bit for bit to refine::rerank, ::knn and ::knn_probed of
+ * quick-adc_amd/host/refine.hpp with metric kIP:
+ *   score      S(q, x) in binary32, every operation rounded by itself, no fused multiply-add: 64 partial sums p[l] = +0, over the
+ *              components 64 j + l in ascending j (m = q[i] * x[i]; p[l] = p[l] + m), then p[l] = p[l] + p[l + s] for l < s at
+ *              s = 32, 16, 8, 4, 2, 1; S = p[0] — the strips and the tree of D.  A row's component is what D reads: the float of
+ *              the stored half, or the decoded byte of an SQ8 row.  A component that does not exist contributes nothing.  S is
+ *              never -0: a p starts at +0 and an IEEE sum is -0 only where both operands are.
+ *   order      larger S first, ties by ascending key: the word is (img_ip(S) << 32) | key, sorted ascending.  img_ip(S) is
+ *              0xFFC00000 for every NaN; else, with b the bit pattern of S, b where its sign bit is set and ~b & 0x7FFFFFFF where
+ *              it is clear: +inf 0x007FFFFF, +0 0x7FFFFFFF, -0 0x80000000, -inf 0xFF800000, a NaN behind -inf.
+ *   outputs    out_dist[q][i] holds S itself (the inverse of the image; a NaN as 0x7FC00000), descending; the slots behind
+ *              out_sizes[q] hold key 0xFFFFFFFF and score -inf (0xFF800000).
+ * Everything else is the L2 rule word for word: the skip of values == FLT_MAX, missing keys and their count, a key listed several
+ * times kept once, filters, the probed entry rule, the limits on R and r_in.  Setting the metric back to QADC_REFINE_L2 gives the L2
+ * results exactly.
+ * Under QADC_REFINE_IP qadc_refine_range, _range_device, _rerank_range and _rerank_range_device return QADC_E_STATE before the device
+ * is touched and leave a held result as it is (the radius rules assume D >= 0); qadc_refine_range_collect* of a result held from
+ * before still works.
+ * Not covered: range search by inner product; inner-product coarse assignment (qadc_adc_index_assign and with it
+ * qadc_adc_search_exact probe by L2 to the centroids — a caller who wants other probes passes their own lists to
+ * qadc_refine_knn_probed); inner-product tables from qadc_adc_search (a caller's own tables through qadc_adc_query_scan* serve);
+ * cosine as a metric of its own. */
+#define QADC_REFINE_L2 0
+#define QADC_REFINE_IP 1
+/* QADC_E_ARG: r NULL, a metric that is neither QADC_REFINE_L2 nor QADC_REFINE_IP (the store keeps the metric it had). */
+int qadc_refine_set_metric(qadc_refine* r, int metric);
+/* *metric_out = the store's metric.  QADC_E_ARG: r or metric_out NULL. */
+int qadc_refine_metric(const qadc_refine* r, int* metric_out);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,8 @@
 // geometry host/refine_range_plan.hpp, kernels csrc/qadc_refine_range_kernel.hip.  qadc_refine_knn_probed is
 // knn over the rows of the partitions of a float-ADC index that each query probes, keyed as the scan keys them and gathered through
 // the store: geometry host/refine_probe_plan.hpp, kernels csrc/qadc_refine_probe_kernel.hip; the index is read through adc_probe_view.
+// qadc_refine_set_metric is host state of the handle: every pass of rerank, knn and knn_probed carries it to
+// the launchers, which pick the kernels' L2 or inner-product instantiation; the range calls refuse a store whose metric is not L2.
 //
 // Every array of the *_device calls is read and written by kernels only, so memory of another HIP runtime (torch tensors) is
 // legal; for the same reason the library cannot ask which device such a pointer lives on, and does not: as for
@@ -44,8 +46,13 @@ static_assert(QADC_REFINE_F32 == (int)qadc::refine::Elem::kF32 && QADC_REFINE_F1
                   QADC_REFINE_SQ8 == (int)qadc::refine::Elem::kSQ8,
               "the kernels' element types");
 
+static_assert(QADC_REFINE_L2 == qadc::refine::kMetricL2 && QADC_REFINE_IP == qadc::refine::kMetricIP && QADC_REFINE_L2 == qadc::refine::kL2 &&
+                  QADC_REFINE_IP == qadc::refine::kIP,
+              "the kernels' metrics");
+
 struct qadc_refine {
     int dim = 0, dtype = QADC_REFINE_F32, device = 0;
+    int metric = QADC_REFINE_L2;                    // qadc_refine_set_metric: host state, read by every exact call
     uint32_t lo = 0;                                // key of row 0 (fixed by the first add)
     uint64_t rows = 0, cap = 0;                     // rows held / rows the allocation holds
     void* data = nullptr;                           // [cap][dim] floats, halves or bytes
@@ -431,6 +438,7 @@ int rerank_passes(qadc_refine* r, int nq, const float* queries, int r_in, const 
         RefinePass p;
         p.rows = r->data;
         p.elem = r->elem_type();
+        p.metric = r->metric;
         p.sq = r->sq();
         p.lo = r->lo;
         p.nrows = r->rows;
@@ -489,6 +497,7 @@ int knn_passes(qadc_refine* r, int nq, const float* queries, int R, const adc::S
         KnnPass p;
         p.rows = r->data;
         p.elem = r->elem_type();
+        p.metric = r->metric;
         p.sq = r->sq();
         p.dim = r->dim;
         p.lo = r->lo;
@@ -569,6 +578,7 @@ int probed_passes(qadc_refine* r, const ProbeIndex& pi, int nq, const float* que
         probe_work(plan, p.nq, ma, assign + (size_t)q0 * ma, part_rows.data(), parts, &w);
         p.rows = r->data;
         p.elem = r->elem_type();
+        p.metric = r->metric;
         p.sq = r->sq();
         p.dim = r->dim;
         p.lo = r->lo;
@@ -906,11 +916,32 @@ int range_collect(qadc_refine* r, uint64_t capacity, uint32_t* keys, float* dist
     return QADC_OK;
 }
 
+// Range search has no inner-product form: refused before the device or the held result is touched
+int range_metric_refusal(const qadc_refine* r) {
+    if (r && r->metric != QADC_REFINE_L2)
+        return fail(QADC_E_STATE, "range search is L2 only: the store's metric is QADC_REFINE_IP (qadc_refine_set_metric)");
+    return QADC_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
+int qadc_refine_set_metric(qadc_refine* r, int metric) {
+    if (!r) return fail(QADC_E_ARG, "store is null");
+    if (metric != QADC_REFINE_L2 && metric != QADC_REFINE_IP) return fail(QADC_E_ARG, "metric is QADC_REFINE_L2 or QADC_REFINE_IP");
+    r->metric = metric;
+    return QADC_OK;
+}
+
+int qadc_refine_metric(const qadc_refine* r, int* metric_out) {
+    if (!r || !metric_out) return fail(QADC_E_ARG, "store and metric_out must not be null");
+    *metric_out = r->metric;
+    return QADC_OK;
+}
+
 int qadc_refine_range(qadc_refine* r, int nq, const float* queries, const float* radius, const qadc_adc_filter* filter, uint64_t* lims) {
+    if (int rc = range_metric_refusal(r)) return rc;
     if (r) r->range_lims.clear();   // (the held result is dropped, also when this call fails)
     adc::ScanFilter scan;
     if (int rc = check_range(r, nq, queries, radius, lims, filter, &scan)) return rc;
@@ -924,6 +955,7 @@ int qadc_refine_range(qadc_refine* r, int nq, const float* queries, const float*
 }
 
 int qadc_refine_range_device(qadc_refine* r, int nq, const float* d_queries, const float* radius, const qadc_adc_filter* filter, uint64_t* lims) {
+    if (int rc = range_metric_refusal(r)) return rc;
     if (r) r->range_lims.clear();
     if (int rc = check_aligned(d_queries, 4, "d_queries")) return rc;
     adc::ScanFilter scan;
@@ -935,6 +967,7 @@ int qadc_refine_range_device(qadc_refine* r, int nq, const float* d_queries, con
 
 int qadc_refine_rerank_range(qadc_refine* r, int nq, const float* queries, const uint64_t* in_lims, const uint32_t* keys, const float* radius,
                              uint64_t* lims, uint64_t* missing_out) {
+    if (int rc = range_metric_refusal(r)) return rc;
     if (r) r->range_lims.clear();
     if (missing_out) *missing_out = 0;
     if (const char* why = rerank_range_refusal(r != nullptr, nq, queries != nullptr, in_lims, keys != nullptr, radius != nullptr, lims != nullptr))
@@ -953,6 +986,7 @@ int qadc_refine_rerank_range(qadc_refine* r, int nq, const float* queries, const
 
 int qadc_refine_rerank_range_device(qadc_refine* r, int nq, const float* d_queries, const uint64_t* in_lims, const uint32_t* d_keys,
                                     const float* radius, uint64_t* lims, uint64_t* missing_out) {
+    if (int rc = range_metric_refusal(r)) return rc;
     if (r) r->range_lims.clear();
     if (missing_out) *missing_out = 0;
     if (int rc = check_aligned(d_queries, 4, "d_queries")) return rc;

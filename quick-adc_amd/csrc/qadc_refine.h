@@ -18,6 +18,10 @@ namespace refine {
 enum class Elem : int { kF32 = 0, kF16 = 1, kSQ8 = 2 };
 inline size_t elem_bytes(Elem e) { return e == Elem::kF32 ? 4 : e == Elem::kF16 ? 2 : 1; }
 
+// The metric of a pass (= QADC_REFINE_L2 / _IP, asserted in qadc_refine.cpp): which instantiation of the
+// distance, select and final kernels a launch picks (csrc/qadc_refine_dev.h: MetricL2, MetricIP)
+constexpr int kMetricL2 = 0, kMetricIP = 1;
+
 // The parameters of an SQ8 store in device memory: vmin, step and inv = 1 / step (0 where step is 0),
 // [dim] each, and the counter of clamped components.  All null for the other element types.
 struct SqParams {
@@ -32,6 +36,7 @@ struct SqParams {
 struct RefinePass {
     const void* rows;
     Elem elem;
+    int metric;                    // kMetricL2 / kMetricIP
     SqParams sq;
     uint32_t lo;
     uint64_t nrows;
@@ -50,9 +55,9 @@ struct RefinePass {
     int32_t* out_sizes;            // [nq]
 };
 
-// refine_dist_kernel<Row>: the word of every candidate of the pass into p.words
+// refine_dist_kernel<M, Row, Lookup>: the word of every candidate of the pass into p.words (M: p.metric)
 hipError_t launch_refine_dist(const RefinePass& p, const RefinePlan& plan, hipStream_t stream);
-// refine_select_kernel<N>: sort, dedupe, the first R survivors and the tail of every query of the pass
+// refine_select_kernel<M, N, T>: sort, dedupe, the first R survivors and the tail of every query of the pass
 hipError_t launch_refine_select(const RefinePass& p, const RefinePlan& plan, hipStream_t stream);
 // refine_convert_kernel<Row>: dst[i] = Row(src[i]) for n floats, whole rows of dim (Row float: a copy; __half: round to nearest
 // even; SQ8: sq_encode under component i % dim's parameters, clamped components added to sq.clamped)
@@ -109,6 +114,7 @@ hipError_t launch_keyed_rebuild(const uint32_t* row_key, uint32_t alloc_rows, Ke
 struct KnnPass {
     const void* rows;              // the store's rows [nrows][dim], `elem` says which element type
     Elem elem;
+    int metric;                    // kMetricL2 / kMetricIP
     SqParams sq;
     int dim;
     uint32_t lo;                   // a dense store: the key of row r is lo + r
@@ -124,11 +130,11 @@ struct KnnPass {
     float* out_dist;               // [nq][R]
     int32_t* out_sizes;            // [nq]
 };
-// refine_knn_dist_kernel<Row, QT, J>: the words of launch `launch`'s rows that are <= their (query, group)'s bound, appended
+// refine_knn_dist_kernel<M, Row, QT, J>: the words of launch `launch`'s rows that are <= their (query, group)'s bound, appended
 hipError_t launch_knn_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream);
 // refine_knn_select_kernel: every buffer of the launch's groups that holds at least R words keeps its first R, sorted; bound = the R-th
 hipError_t launch_knn_select(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream);
-// refine_knn_final_kernel: the groups' lists merged: the first R words, the fillers behind them and the size of every query
+// refine_knn_final_kernel<M>: the groups' lists merged: the first R words, the fillers behind them and the size of every query
 hipError_t launch_knn_final(const KnnPass& p, const KnnPlan& plan, hipStream_t stream);
 
 // ---- probed exact search (qadc_refine_knn_probed; kernels: csrc/qadc_refine_probe_kernel.hip; geometry:
@@ -144,6 +150,7 @@ struct ProbePart {
 struct ProbePass {
     const void* rows;              // the store's rows, `elem` says which element type
     Elem elem;
+    int metric;                    // kMetricL2 / kMetricIP
     SqParams sq;
     int dim;
     uint32_t lo;                   // a dense store: the keys [lo, lo + nrows)
@@ -172,11 +179,11 @@ struct ProbeLaunch {
     int slice_rows;
     uint64_t launch;
 };
-// refine_probe_dist_kernel<Row, Lookup, QT, J>: the words of the launch's rows that are <= their (query, group)'s bound, appended
+// refine_probe_dist_kernel<M, Row, Lookup, QT, J>: the words of the launch's rows that are <= their (query, group)'s bound, appended
 hipError_t launch_probe_dist(const ProbePass& p, const ProbePlan& plan, const ProbeLaunch& l, hipStream_t stream);
 // refine_probe_select_kernel: every buffer that holds at least R words keeps its first R distinct ones, sorted; bound = the R-th
 hipError_t launch_probe_select(const ProbePass& p, const ProbePlan& plan, hipStream_t stream);
-// refine_probe_final_kernel: the groups' lists merged, equal words once: the first R, the fillers behind them and the size of every query
+// refine_probe_final_kernel<M>: the groups' lists merged, equal words once: the first R, the fillers behind them and the size of every query
 hipError_t launch_probe_final(const ProbePass& p, const ProbePlan& plan, hipStream_t stream);
 
 // ---- exact range search (qadc_refine_range, qadc_refine_rerank_range; kernels:

@@ -1,5 +1,5 @@
 // Device code the refine kernels share (private to csrc/qadc_refine_kernel.hip, csrc/qadc_refine_knn_kernel.hip and
-// csrc/qadc_refine_probe_kernel.hip; the range kernels keep their own restatement): a row's components, the lookups from a key to a
+// csrc/qadc_refine_probe_kernel.hip; the range kernels keep their own restatement): the metric policies, a row's components, the lookups from a key to a
 // row, the key filter, the transposed fold of a tile's partial sums and the bitonic sort of the selects.  Every unit that includes it
 // is built with -ffp-contract=off; the definition all of it is held to is host/refine.hpp.
 #pragma once
@@ -13,6 +13,40 @@ namespace refine {
 constexpr uint32_t kNanImage = 0x7FC00000u;
 constexpr uint32_t kInfImage = 0x7F800000u;
 constexpr uint64_t kNoWord = ~0ull;
+
+// The metric of a store (qadc_refine_set_metric) as a compile-time policy of the distance, select and final
+// kernels: the term a component adds to a lane's partial sum (the product and the sum it enters are rounded one by one: the units
+// are built with -ffp-contract=off), the image of a folded value — the high half of a word, so that ascending words are the
+// metric's order, best first — its inverse, and the bit pattern out_dist holds in the slots behind out_sizes[q].
+struct MetricL2 {                                     // D: smaller first.  D is +0, positive or NaN, so its bits are its order
+    static constexpr uint32_t kFillerBits = kInfImage;
+    __device__ static inline float term(float q, float x) {
+        const float t = q - x;
+        return t * t;
+    }
+    __device__ static inline uint32_t image(float v) {
+        uint32_t img = __float_as_uint(v);
+        if (v != v) img = kNanImage;
+        return img;
+    }
+    __device__ static inline float value(uint32_t img) { return __uint_as_float(img); }
+};
+
+struct MetricIP {                                     // S: larger first.  +inf 0x007FFFFF .. +0 0x7FFFFFFF, -0 0x80000000 .. -inf
+    static constexpr uint32_t kNanImageIP = 0xFFC00000u;   // 0xFF800000, every NaN behind it; all below kNoWord's high half
+    static constexpr uint32_t kFillerBits = 0xFF800000u;   // -inf
+    __device__ static inline float term(float q, float x) { return q * x; }
+    __device__ static inline uint32_t image(float v) {
+        const uint32_t b = __float_as_uint(v);
+        uint32_t img = (b & 0x80000000u) ? b : (~b & 0x7FFFFFFFu);
+        if (v != v) img = kNanImageIP;
+        return img;
+    }
+    __device__ static inline float value(uint32_t img) {
+        const uint32_t b = (img & 0x80000000u) ? img : (~img & 0x7FFFFFFFu);
+        return __uint_as_float(img > 0xFF800000u ? kNanImage : b);   // (a NaN comes out as 0x7FC00000)
+    }
+};
 
 struct sq8_t {                                        // a component of an SQ8 row
     uint8_t b;

@@ -1,7 +1,7 @@
 // Kernels of exact re-ranking (qadc_refine_*), gfx950, built with -ffp-contract=off: every result is held
 // bit for bit to host/refine.hpp.
-//   refine_dist_kernel<Row>     one candidate per wave: the 64-bit word (image of the L2 distance << 32 | key) of every candidate
-//   refine_select_kernel<N, T>  one workgroup per query: bitonic sort of the words in LDS, equal words kept once, the first R out
+//   refine_dist_kernel<M, Row>  one candidate per wave: the 64-bit word (image of the distance or score << 32 | key) of every candidate
+//   refine_select_kernel<M, N, T>  one workgroup per query: bitonic sort of the words in LDS, equal words kept once, the first R out
 //   refine_convert_kernel<Row>  the append: float -> the store's element type
 //   refine_get_kernel<Row>      the read-back: one key per wave, its row decoded to floats
 //   refine_sq_range_kernel      the range of an SQ8 store: per-dimension min and max of the finite components of a learning set
@@ -10,6 +10,8 @@
 // lanes that own the components 64 j + l with ds_bpermute, so that the definition's summation order holds.
 // The keyed store: refine_dist_kernel finds a candidate's row through a lookup policy, DenseLookup (the
 // range test) or KeyedLookup (a probe of the table); keyed_*_kernel are the put, the remove and the rebuild.
+// The metric is the policy M of csrc/qadc_refine_dev.h, MetricL2 or MetricIP: the term of a component, the
+// image of the folded value and, in the select, the image's inverse and the filler of out_dist.
 #include "qadc_refine_dev.h"
 
 #include <cfloat>
@@ -21,8 +23,10 @@ namespace refine {
 namespace {
 
 // Lane l of a wave owns the partial sum p[l] of the definition: the components 64 j + l, in ascending j, then the tree at the
-// strides 32 .. 1 (lane l < s adds lane l + s; what the lanes at and above s compute is never read by a lane below).
-template <typename Row, typename Lookup>
+// strides 32 .. 1 (lane l < s adds lane l + s; what the lanes at and above s compute is never read by a lane below).  A component
+// that does not exist is left out: its lane's p keeps its value.  Under MetricIP a lane's p starts at +0 and IEEE addition gives -0
+// only from two -0 operands, so no partial sum and no score is ever -0.
+template <typename M, typename Row, typename Lookup>
 __global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Row* __restrict__ rows, Lookup look, int dim,
                                                                         const float* __restrict__ sq_vmin, const float* __restrict__ sq_step,
                                                                         const float* __restrict__ queries, int r_in,
@@ -82,8 +86,7 @@ __global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Ro
 #pragma unroll
                     for (int c = 0; c < kRefineInFlight; ++c)
                         if (x[c]) {                   // (uniform: the exchange runs with every lane)
-                            const float t = qj - sq_lane_value(w[c], s, lane, vj, sj);
-                            const float tt = t * t;
+                            const float tt = M::term(qj, sq_lane_value(w[c], s, lane, vj, sj));
                             if (mine) p[c] = p[c] + tt;
                         }
                 }
@@ -94,8 +97,7 @@ __global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Ro
 #pragma unroll
                 for (int c = 0; c < kRefineInFlight; ++c)
                     if (x[c]) {
-                        const float t = qj - row_value(x[c], j, 0.0f, 0.0f);
-                        const float tt = t * t;
+                        const float tt = M::term(qj, row_value(x[c], j, 0.0f, 0.0f));
                         p[c] = p[c] + tt;
                     }
             }
@@ -106,11 +108,7 @@ __global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Ro
 #pragma unroll
             for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s, 64);
             const int i = base + c;
-            if (lane == 0 && i < c1) {
-                uint32_t img = __float_as_uint(v);
-                if (v != v) img = kNanImage;
-                words[list + i] = x[c] ? ((uint64_t)img << 32) | key[c] : kNoWord;
-            }
+            if (lane == 0 && i < c1) words[list + i] = x[c] ? ((uint64_t)M::image(v) << 32) | key[c] : kNoWord;
         }
     }
     if (lane == 0 && lost) atomicAdd(&s_missing, lost);
@@ -120,7 +118,7 @@ __global__ __launch_bounds__(kRefineWaves * 64) void refine_dist_kernel(const Ro
 
 // N words (the list, padded with ~0) sorted ascending by T threads; a word survives where it differs from the one before it and
 // is not ~0; the survivors' ranks come from a prefix sum over the threads' segments of N / T consecutive words.
-template <int N, int T>
+template <typename M, int N, int T>
 __global__ __launch_bounds__(T) void refine_select_kernel(const uint64_t* __restrict__ words, int r_in, int R, uint32_t* __restrict__ out_keys,
                                                           float* __restrict__ out_dist, int32_t* __restrict__ out_sizes) {
     extern __shared__ uint64_t s_words[];             // [N], then uint32 [T]
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(T) void refine_select_kernel(const uint64_t* __rest
         if (w != kNoWord && (first + i == 0 || w != s_words[first + i - 1])) {
             if (rank < (uint32_t)R) {
                 ok[rank] = (uint32_t)w;
-                od[rank] = __uint_as_float((uint32_t)(w >> 32));
+                od[rank] = M::value((uint32_t)(w >> 32));
             }
             ++rank;
         }
@@ -175,7 +173,7 @@ __global__ __launch_bounds__(T) void refine_select_kernel(const uint64_t* __rest
     const uint32_t size = min(total, (uint32_t)R);
     for (uint32_t k = size + tid; k < (uint32_t)R; k += T) {
         ok[k] = 0xFFFFFFFFu;
-        od[k] = __uint_as_float(kInfImage);
+        od[k] = __uint_as_float(M::kFillerBits);
     }
     if (tid == 0) out_sizes[q] = (int32_t)size;
 }
@@ -425,26 +423,25 @@ __global__ __launch_bounds__(kKeyedThreads) void keyed_rebuild_kernel(const uint
     }
 }
 
-template <int N, int T>
+template <typename M, int N, int T>
 hipError_t launch_select(const RefinePass& p, const RefinePlan& plan, hipStream_t stream) {
     if (plan.select_lds_bytes > kRefineLdsDefault) {   // the largest instantiation: above the default limit of dynamic LDS
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&refine_select_kernel<N, T>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&refine_select_kernel<M, N, T>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.select_lds_bytes);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((refine_select_kernel<N, T>), dim3((unsigned)p.nq), dim3(T), plan.select_lds_bytes, stream, p.words, p.r_in, p.R,
+    hipLaunchKernelGGL((refine_select_kernel<M, N, T>), dim3((unsigned)p.nq), dim3(T), plan.select_lds_bytes, stream, p.words, p.r_in, p.R,
                        p.out_keys, p.out_dist, p.out_sizes);
     return hipGetLastError();
 }
 
-}  // namespace
-
-hipError_t launch_refine_dist(const RefinePass& p, const RefinePlan& plan, hipStream_t stream) {
+template <typename M>
+hipError_t launch_dist(const RefinePass& p, const RefinePlan& plan, hipStream_t stream) {
     const dim3 grid((unsigned)((uint64_t)p.nq * plan.chunks)), block(kRefineWaves * 64);
     const DenseLookup dense{p.lo, p.nrows};
     const KeyedLookup keyed{p.tkey, p.trow, p.tbits};
 #define QADC_RD(ROW, LOOKUP, look)                                                                                                       \
-    hipLaunchKernelGGL((refine_dist_kernel<ROW, LOOKUP>), grid, block, lds, stream, static_cast<const ROW*>(p.rows), look, p.dim, p.sq.vmin, \
+    hipLaunchKernelGGL((refine_dist_kernel<M, ROW, LOOKUP>), grid, block, lds, stream, static_cast<const ROW*>(p.rows), look, p.dim, p.sq.vmin, \
                        p.sq.step, p.queries, p.r_in, p.keys, p.counts, p.values, plan.cands_per_wg, plan.chunks, p.words, p.missing)
     // (SQ8 rows: vmin and step behind the query, 3 * dim floats <= 48 KiB)
     const size_t lds = p.elem == Elem::kSQ8 ? 3 * plan.dist_lds_bytes : plan.dist_lds_bytes;
@@ -459,6 +456,22 @@ hipError_t launch_refine_dist(const RefinePass& p, const RefinePlan& plan, hipSt
     }
 #undef QADC_RD
     return hipGetLastError();
+}
+
+template <typename M>
+hipError_t dispatch_select(const RefinePass& p, const RefinePlan& plan, hipStream_t stream) {
+    switch (plan.sort_n) {
+        case 512: return launch_select<M, 512, 256>(p, plan, stream);
+        case 2048: return launch_select<M, 2048, 1024>(p, plan, stream);
+        case 8192: return launch_select<M, 8192, 1024>(p, plan, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_refine_dist(const RefinePass& p, const RefinePlan& plan, hipStream_t stream) {
+    return p.metric == kMetricIP ? launch_dist<MetricIP>(p, plan, stream) : launch_dist<MetricL2>(p, plan, stream);
 }
 
 hipError_t launch_refine_get(const RefinePass& p, const uint32_t* keys, uint64_t count, float* out, uint8_t* found, hipStream_t stream) {
@@ -491,12 +504,7 @@ hipError_t launch_refine_sq_range(const float* vectors, uint64_t n, int dim, uin
 }
 
 hipError_t launch_refine_select(const RefinePass& p, const RefinePlan& plan, hipStream_t stream) {
-    switch (plan.sort_n) {
-        case 512: return launch_select<512, 256>(p, plan, stream);
-        case 2048: return launch_select<2048, 1024>(p, plan, stream);
-        case 8192: return launch_select<8192, 1024>(p, plan, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return p.metric == kMetricIP ? dispatch_select<MetricIP>(p, plan, stream) : dispatch_select<MetricL2>(p, plan, stream);
 }
 
 hipError_t launch_refine_convert(const float* src, void* dst, Elem elem, const SqParams& sq, int dim, uint64_t n, hipStream_t stream) {

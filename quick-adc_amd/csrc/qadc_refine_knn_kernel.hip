@@ -1,9 +1,10 @@
 // Kernels of the exhaustive search over a refine store (qadc_refine_knn), gfx950, built with
 // -ffp-contract=off: every result is held bit for bit to refine::knn of host/refine.hpp.  The geometry is host/refine_knn_plan.hpp.
-//   refine_knn_dist_kernel<Row, QT, J>  a workgroup owns a tile of QT queries and a slice of rows; a wave reads a row once and forms
+//   refine_knn_dist_kernel<M, Row, QT, J>  a workgroup owns a tile of QT queries and a slice of rows; a wave reads a row once and forms
 //                                       its distance to every query of the tile; the words that pass the bound are appended
 //   refine_knn_select_kernel            one workgroup per (query, group): the buffer's first R words, the bound lowered to the R-th
-//   refine_knn_final_kernel             one workgroup per query: the groups' lists merged, the outputs written
+//   refine_knn_final_kernel<M>          one workgroup per query: the groups' lists merged, the outputs written
+// M is the store's metric (csrc/qadc_refine_dev.h: MetricL2, MetricIP).
 #include "qadc_refine_dev.h"
 
 #include <type_traits>
@@ -15,7 +16,9 @@ namespace {
 
 // Lane l keeps the components 64 j + l of the tile's queries and of the row, so p[q] is lane l's partial sum p[l] of the definition
 // for query q: j ascending, t = q - x, t * t and p + tt each rounded alone.  A component that does not exist is 0 in both (register
-// tile) or is left out (LDS tile): p is +0, positive or NaN, and p + (+0) is p.
+// tile) or is left out (LDS tile): p is +0, positive or NaN, and p + (+0) is p.  Under MetricIP the term is q * x rounded alone and p
+// takes either sign; a component that does not exist is 0 * 0 = +0 on the register tile, and p + (+0) is p there too: a lane's p
+// starts at +0 and IEEE addition gives -0 only from two -0 operands, so p is never -0 (nor is any value of the fold).
 //
 // The fold.  The definition's tree is p[l] = p[l] + p[l + s] for l < s at s = 32 .. 1.  Folding QT values one by one costs six
 // shuffles each; instead the wave folds them as a transpose: at stride s the lanes with bit s clear finish the lower half of the
@@ -28,7 +31,7 @@ namespace {
 // which may fill the LDS by itself, reads them from global memory with the row's bytes (coalesced, and the same for every row).
 // The row's bytes are loaded one per lane and component here: the dword-and-exchange form of refine_dist_kernel was measured in this
 // kernel too and is slower in it.
-template <typename Row, int QT, int J>
+template <typename M, typename Row, int QT, int J>
 __global__ __launch_bounds__(kKnnWaves * 64) void refine_knn_dist_kernel(const Row* __restrict__ rows, uint32_t lo, uint64_t nrows,
                                                                          const uint32_t* __restrict__ row_key, adc::ScanFilter filter, int dim,
                                                                          const float* __restrict__ sq_vmin, const float* __restrict__ sq_step,
@@ -88,8 +91,7 @@ __global__ __launch_bounds__(kKnnWaves * 64) void refine_knn_dist_kernel(const R
                 const float xv = i < dim ? row_value(x, i, vr[j], sr[j]) : 0.0f;
 #pragma unroll
                 for (int q = 0; q < QT; ++q) {
-                    const float t = qr[q][j] - xv;
-                    const float tt = t * t;
+                    const float tt = M::term(qr[q][j], xv);
                     p[q] = p[q] + tt;
                 }
             }
@@ -98,17 +100,14 @@ __global__ __launch_bounds__(kKnnWaves * 64) void refine_knn_dist_kernel(const R
                 const float xv = row_value(x, i, kSq ? sq_vmin[i] : 0.0f, kSq ? sq_step[i] : 0.0f);
 #pragma unroll
                 for (int q = 0; q < QT; ++q) {
-                    const float t = s_tile[q * dim + i] - xv;
-                    const float tt = t * t;
+                    const float tt = M::term(s_tile[q * dim + i], xv);
                     p[q] = p[q] + tt;
                 }
             }
         }
         const float v = knn_fold<QT>(p, lane);
         if (emitter) {
-            uint32_t img = __float_as_uint(v);
-            if (v != v) img = kNanImage;
-            const uint64_t word = ((uint64_t)img << 32) | key;
+            const uint64_t word = ((uint64_t)M::image(v) << 32) | key;
             if (word <= my_bound) {
                 const uint32_t pos = atomicAdd(cnt + slot, 1u);
                 if (pos < buf_cap) buf[slot * buf_cap + pos] = word;   // (a launch appends at most chunk_rows words to at most R)
@@ -138,6 +137,7 @@ __global__ __launch_bounds__(1024) void refine_knn_select_kernel(int R, int grou
 }
 
 // grid nq.  Every group's buffer holds at most R words here (the select ran behind every distance launch).
+template <typename M>
 __global__ __launch_bounds__(1024) void refine_knn_final_kernel(int R, int groups, int live_groups, uint64_t buf_cap,
                                                                 const uint64_t* __restrict__ buf, const uint32_t* __restrict__ cnt,
                                                                 uint32_t* __restrict__ out_keys, float* __restrict__ out_dist,
@@ -161,24 +161,24 @@ __global__ __launch_bounds__(1024) void refine_knn_final_kernel(int R, int group
         const bool held = i < size;
         const uint64_t w = held ? s_words[i] : 0ull;
         ok[i] = held ? (uint32_t)w : 0xFFFFFFFFu;
-        od[i] = __uint_as_float(held ? (uint32_t)(w >> 32) : kInfImage);
+        od[i] = held ? M::value((uint32_t)(w >> 32)) : __uint_as_float(M::kFillerBits);
     }
     if (tid == 0) out_sizes[q] = (int32_t)size;
 }
 
-template <typename Row, int QT, int J>
+template <typename M, typename Row, int QT, int J>
 hipError_t launch_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launch, int live, hipStream_t stream) {
     const dim3 grid((unsigned)((p.nq + QT - 1) / QT), (unsigned)(live * plan.slices)), block(kKnnWaves * 64);
-    hipLaunchKernelGGL((refine_knn_dist_kernel<Row, QT, J>), grid, block, plan.dist_lds_bytes, stream, static_cast<const Row*>(p.rows), p.lo,
+    hipLaunchKernelGGL((refine_knn_dist_kernel<M, Row, QT, J>), grid, block, plan.dist_lds_bytes, stream, static_cast<const Row*>(p.rows), p.lo,
                        p.nrows, p.row_key, p.filter, p.dim, p.sq.vmin, p.sq.step, p.queries, p.nq, plan.chunk_rows, plan.groups, plan.slice_rows, plan.slices, launch,
                        plan.buf_cap, p.buf, p.cnt, p.bound);
     return hipGetLastError();
 }
 
-template <typename Row>
+template <typename M, typename Row>
 hipError_t dispatch_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launch, int live, hipStream_t stream) {
 #define QADC_KNN(QT, J) \
-    if (plan.qt == QT && plan.jregs == J) return launch_dist<Row, QT, J>(p, plan, launch, live, stream)
+    if (plan.qt == QT && plan.jregs == J) return launch_dist<M, Row, QT, J>(p, plan, launch, live, stream)
     QADC_KNN(32, 1); QADC_KNN(32, 2); QADC_KNN(16, 3); QADC_KNN(16, 4);
     QADC_KNN(4, 1); QADC_KNN(4, 2); QADC_KNN(4, 3); QADC_KNN(4, 4);
     QADC_KNN(32, 0); QADC_KNN(16, 0); QADC_KNN(8, 0); QADC_KNN(4, 0);
@@ -186,13 +186,25 @@ hipError_t dispatch_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launch,
     return hipErrorInvalidValue;   // (a tile the plan does not make)
 }
 
+template <typename M>
+hipError_t dispatch_rows(const KnnPass& p, const KnnPlan& plan, uint64_t launch, int live, hipStream_t stream) {
+    if (p.elem == Elem::kSQ8) return dispatch_dist<M, sq8_t>(p, plan, launch, live, stream);
+    return p.elem == Elem::kF16 ? dispatch_dist<M, __half>(p, plan, launch, live, stream) : dispatch_dist<M, float>(p, plan, launch, live, stream);
+}
+
+template <typename M>
+hipError_t launch_final(const KnnPass& p, const KnnPlan& plan, int live, hipStream_t stream) {
+    hipLaunchKernelGGL(refine_knn_final_kernel<M>, dim3((unsigned)p.nq), dim3(plan.select_threads), plan.select_lds_bytes, stream, p.R,
+                       plan.groups, live, plan.buf_cap, p.buf, p.cnt, p.out_keys, p.out_dist, p.out_sizes);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_knn_dist(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream) {
     const int live = knn_launch_groups(p.nrows, plan.chunk_rows, plan.groups, launch);
     if (live == 0 || p.nq == 0) return hipSuccess;
-    if (p.elem == Elem::kSQ8) return dispatch_dist<sq8_t>(p, plan, launch, live, stream);
-    return p.elem == Elem::kF16 ? dispatch_dist<__half>(p, plan, launch, live, stream) : dispatch_dist<float>(p, plan, launch, live, stream);
+    return p.metric == kMetricIP ? dispatch_rows<MetricIP>(p, plan, launch, live, stream) : dispatch_rows<MetricL2>(p, plan, launch, live, stream);
 }
 
 hipError_t launch_knn_select(const KnnPass& p, const KnnPlan& plan, uint64_t launch, hipStream_t stream) {
@@ -206,9 +218,7 @@ hipError_t launch_knn_select(const KnnPass& p, const KnnPlan& plan, uint64_t lau
 hipError_t launch_knn_final(const KnnPass& p, const KnnPlan& plan, hipStream_t stream) {
     if (p.nq == 0) return hipSuccess;
     const int live = knn_launch_groups(p.nrows, plan.chunk_rows, plan.groups, 0);
-    hipLaunchKernelGGL(refine_knn_final_kernel, dim3((unsigned)p.nq), dim3(plan.select_threads), plan.select_lds_bytes, stream, p.R,
-                       plan.groups, live, plan.buf_cap, p.buf, p.cnt, p.out_keys, p.out_dist, p.out_sizes);
-    return hipGetLastError();
+    return p.metric == kMetricIP ? launch_final<MetricIP>(p, plan, live, stream) : launch_final<MetricL2>(p, plan, live, stream);
 }
 
 }  // namespace refine

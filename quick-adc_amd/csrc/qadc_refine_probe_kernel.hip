@@ -1,14 +1,16 @@
 // Kernels of the probed exact search over a refine store (qadc_refine_knn_probed), gfx950, built with
 // -ffp-contract=off: every result is held bit for bit to refine::knn_probed of host/refine.hpp.  The geometry is
 // host/refine_probe_plan.hpp.
-//   refine_probe_dist_kernel<Row, Lookup, QT, J>  a workgroup owns an item — a partition of the index and a tile of at most QT of the
+//   refine_probe_dist_kernel<M, Row, Lookup, QT, J>  a workgroup owns an item — a partition of the index and a tile of at most QT of the
 //                                                 queries that probe it — and a slice of the partition's rows; a wave takes a row of
 //                                                 the partition, finds its key's row in the store, reads it once and forms its distance
 //                                                 to every query of the tile; the words that pass the bound are appended
 //   refine_probe_select_kernel                    one workgroup per (query, group): the buffer's first R DISTINCT words, the bound lowered
 //                                                 to the R-th
-//   refine_probe_final_kernel                     one workgroup per query: the groups' lists merged, equal words kept once, the outputs
-// The arithmetic, the fold and the sort are refine_knn_dist_kernel's (csrc/qadc_refine_dev.h).
+//   refine_probe_final_kernel<M>                  one workgroup per query: the groups' lists merged, equal words kept once, the outputs
+// The arithmetic, the fold and the sort are refine_knn_dist_kernel's (csrc/qadc_refine_dev.h), and so is the metric policy M (MetricL2,
+// MetricIP): what that kernel's comment says of the components that do not exist, and of -0 under MetricIP,
+// holds here word for word.
 #include "qadc_refine_dev.h"
 
 #include <type_traits>
@@ -37,7 +39,7 @@ __device__ inline int probe_fetch(const ProbePart& part, uint64_t r, const adc::
 // the operands come from: the tile's queries are gathered by the item's slots (query = slot / groups), the row's key is read from the
 // partition and the row's address is a lookup in the store.  The key, the lookup and with them the address of the row after this
 // one are fetched before the current row is summed, so that the gather's latency lies under the arithmetic.
-template <typename Row, typename Lookup, int QT, int J>
+template <typename M, typename Row, typename Lookup, int QT, int J>
 __global__ __launch_bounds__(kKnnWaves * 64) void refine_probe_dist_kernel(const Row* __restrict__ rows, Lookup look, const ProbePart* __restrict__ parts,
                                                                            adc::ScanFilter index_filter, adc::ScanFilter filter, int dim,
                                                                            const float* __restrict__ sq_vmin, const float* __restrict__ sq_step,
@@ -110,8 +112,7 @@ __global__ __launch_bounds__(kKnnWaves * 64) void refine_probe_dist_kernel(const
                     const float xv = i < dim ? row_value(x, i, vr[j], sr[j]) : 0.0f;
 #pragma unroll
                     for (int q = 0; q < QT; ++q) {
-                        const float t = qr[q][j] - xv;
-                        const float tt = t * t;
+                        const float tt = M::term(qr[q][j], xv);
                         p[q] = p[q] + tt;
                     }
                 }
@@ -120,17 +121,14 @@ __global__ __launch_bounds__(kKnnWaves * 64) void refine_probe_dist_kernel(const
                     const float xv = row_value(x, i, kSq ? sq_vmin[i] : 0.0f, kSq ? sq_step[i] : 0.0f);
 #pragma unroll
                     for (int q = 0; q < QT; ++q) {
-                        const float t = s_tile[q * dim + i] - xv;
-                        const float tt = t * t;
+                        const float tt = M::term(s_tile[q * dim + i], xv);
                         p[q] = p[q] + tt;
                     }
                 }
             }
             const float v = knn_fold<QT>(p, lane);
             if (emitter) {
-                uint32_t img = __float_as_uint(v);
-                if (v != v) img = kNanImage;
-                const uint64_t word = ((uint64_t)img << 32) | key;
+                const uint64_t word = ((uint64_t)M::image(v) << 32) | key;
                 if (word <= my_bound) {
                     const uint32_t pos = atomicAdd(cnt + slot, 1u);
                     if (pos < buf_cap) buf[slot * buf_cap + pos] = word;   // (a launch appends at most chunk_rows words to at most R)
@@ -206,6 +204,7 @@ __global__ __launch_bounds__(1024) void refine_probe_select_kernel(int R, int gr
 
 // grid nq.  Every group's buffer holds at most R words here (the select ran behind every distance launch); a buffer the select left
 // alone may hold a word twice, and two groups may hold the same word.
+template <typename M>
 __global__ __launch_bounds__(1024) void refine_probe_final_kernel(int R, int groups, uint64_t buf_cap, const uint64_t* __restrict__ buf,
                                                                   const uint32_t* __restrict__ cnt, uint32_t* __restrict__ out_keys,
                                                                   float* __restrict__ out_dist, int32_t* __restrict__ out_sizes) {
@@ -226,30 +225,30 @@ __global__ __launch_bounds__(1024) void refine_probe_final_kernel(int R, int gro
     const uint32_t distinct = probe_distinct(s_words, N, tid, T, [=](uint32_t rank, uint64_t w) {
         if (rank < (uint32_t)R) {
             ok[rank] = (uint32_t)w;
-            od[rank] = __uint_as_float((uint32_t)(w >> 32));
+            od[rank] = M::value((uint32_t)(w >> 32));
         }
     });
     const uint32_t size = min(distinct, (uint32_t)R);
     for (uint32_t i = size + tid; i < (uint32_t)R; i += T) {
         ok[i] = 0xFFFFFFFFu;
-        od[i] = __uint_as_float(kInfImage);
+        od[i] = __uint_as_float(M::kFillerBits);
     }
     if (tid == 0) out_sizes[q] = (int32_t)size;
 }
 
-template <typename Row, typename Lookup, int QT, int J>
+template <typename M, typename Row, typename Lookup, int QT, int J>
 hipError_t launch_dist(const ProbePass& p, const ProbePlan& plan, const Lookup& look, const ProbeLaunch& l, hipStream_t stream) {
     const dim3 grid(l.items, l.slices), block(kKnnWaves * 64);
-    hipLaunchKernelGGL((refine_probe_dist_kernel<Row, Lookup, QT, J>), grid, block, plan.dist_lds_bytes, stream, static_cast<const Row*>(p.rows), look,
+    hipLaunchKernelGGL((refine_probe_dist_kernel<M, Row, Lookup, QT, J>), grid, block, plan.dist_lds_bytes, stream, static_cast<const Row*>(p.rows), look,
                        p.parts, p.index_filter, p.filter, p.dim, p.sq.vmin, p.sq.step, p.queries, p.items, p.slots, plan.groups, plan.launch_rows,
                        l.slice_rows, l.launch, plan.buf_cap, p.buf, p.cnt, p.bound, p.missing);
     return hipGetLastError();
 }
 
-template <typename Row, typename Lookup>
+template <typename M, typename Row, typename Lookup>
 hipError_t dispatch_dist(const ProbePass& p, const ProbePlan& plan, const Lookup& look, const ProbeLaunch& l, hipStream_t stream) {
 #define QADC_PROBE(QT, J) \
-    if (plan.qt == QT && plan.jregs == J) return launch_dist<Row, Lookup, QT, J>(p, plan, look, l, stream)
+    if (plan.qt == QT && plan.jregs == J) return launch_dist<M, Row, Lookup, QT, J>(p, plan, look, l, stream)
     QADC_PROBE(32, 1); QADC_PROBE(32, 2); QADC_PROBE(16, 3); QADC_PROBE(16, 4);
     QADC_PROBE(4, 1); QADC_PROBE(4, 2); QADC_PROBE(4, 3); QADC_PROBE(4, 4);
     QADC_PROBE(32, 0); QADC_PROBE(16, 0); QADC_PROBE(8, 0); QADC_PROBE(4, 0);
@@ -257,10 +256,23 @@ hipError_t dispatch_dist(const ProbePass& p, const ProbePlan& plan, const Lookup
     return hipErrorInvalidValue;   // (a tile the plan does not make)
 }
 
-template <typename Lookup>
+template <typename M, typename Lookup>
 hipError_t dispatch_rows(const ProbePass& p, const ProbePlan& plan, const Lookup& look, const ProbeLaunch& l, hipStream_t stream) {
-    if (p.elem == Elem::kSQ8) return dispatch_dist<sq8_t, Lookup>(p, plan, look, l, stream);
-    return p.elem == Elem::kF16 ? dispatch_dist<__half, Lookup>(p, plan, look, l, stream) : dispatch_dist<float, Lookup>(p, plan, look, l, stream);
+    if (p.elem == Elem::kSQ8) return dispatch_dist<M, sq8_t, Lookup>(p, plan, look, l, stream);
+    return p.elem == Elem::kF16 ? dispatch_dist<M, __half, Lookup>(p, plan, look, l, stream) : dispatch_dist<M, float, Lookup>(p, plan, look, l, stream);
+}
+
+template <typename M>
+hipError_t dispatch_lookup(const ProbePass& p, const ProbePlan& plan, const ProbeLaunch& l, hipStream_t stream) {
+    if (p.tkey) return dispatch_rows<M>(p, plan, KeyedLookup{p.tkey, p.trow, p.tbits}, l, stream);
+    return dispatch_rows<M>(p, plan, DenseLookup{p.lo, p.nrows}, l, stream);
+}
+
+template <typename M>
+hipError_t launch_final(const ProbePass& p, const ProbePlan& plan, hipStream_t stream) {
+    hipLaunchKernelGGL(refine_probe_final_kernel<M>, dim3((unsigned)p.nq), dim3(plan.select_threads), plan.select_lds_bytes, stream, p.R,
+                       plan.groups, plan.buf_cap, p.buf, p.cnt, p.out_keys, p.out_dist, p.out_sizes);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -268,8 +280,7 @@ hipError_t dispatch_rows(const ProbePass& p, const ProbePlan& plan, const Lookup
 hipError_t launch_probe_dist(const ProbePass& p, const ProbePlan& plan, const ProbeLaunch& l, hipStream_t stream) {
     if (l.items == 0 || l.slices == 0) return hipSuccess;
     if (l.slices > 65535u) return hipErrorInvalidValue;
-    if (p.tkey) return dispatch_rows(p, plan, KeyedLookup{p.tkey, p.trow, p.tbits}, l, stream);
-    return dispatch_rows(p, plan, DenseLookup{p.lo, p.nrows}, l, stream);
+    return p.metric == kMetricIP ? dispatch_lookup<MetricIP>(p, plan, l, stream) : dispatch_lookup<MetricL2>(p, plan, l, stream);
 }
 
 hipError_t launch_probe_select(const ProbePass& p, const ProbePlan& plan, hipStream_t stream) {
@@ -281,9 +292,7 @@ hipError_t launch_probe_select(const ProbePass& p, const ProbePlan& plan, hipStr
 
 hipError_t launch_probe_final(const ProbePass& p, const ProbePlan& plan, hipStream_t stream) {
     if (p.nq == 0) return hipSuccess;
-    hipLaunchKernelGGL(refine_probe_final_kernel, dim3((unsigned)p.nq), dim3(plan.select_threads), plan.select_lds_bytes, stream, p.R,
-                       plan.groups, plan.buf_cap, p.buf, p.cnt, p.out_keys, p.out_dist, p.out_sizes);
-    return hipGetLastError();
+    return p.metric == kMetricIP ? launch_final<MetricIP>(p, plan, stream) : launch_final<MetricL2>(p, plan, stream);
 }
 
 }  // namespace refine

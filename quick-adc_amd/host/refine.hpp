@@ -25,6 +25,20 @@
 // Exact range search (range and rerank_range, at the end): every held key whose distance is below a radius,
 // over the whole store or over candidate lists of any length — the definition of qadc_refine_range and qadc_refine_rerank_range.
 //
+// Inner product (kIP): rerank, knn and knn_probed take a metric, kL2 (the default: everything above) or kIP.
+// Score.  S(q, x) over dim floats, IEEE binary32, every operation rounded by itself:
+//   p[l] = +0 for l in 0..63;  for i = 64 j + l < dim, j ascending:  m = q[i] * x[i];  p[l] = p[l] + m
+//   for s in 32, 16, 8, 4, 2, 1:  p[l] = p[l] + p[l + s]  for every l < s
+//   S = p[0]
+// — D's strips and D's tree over the products; a row's component is what D reads.  A component that does not exist contributes
+// nothing.  A p starts at +0 and IEEE addition gives -0 only from two -0 operands, so no p and no S is ever -0.
+// Order.  Larger S first, ties by ascending key: the word is (img_ip(S) << 32) | key, sorted ascending like D's words; img_ip(S) is
+// 0xFFC00000 for every NaN, else with b = S's bit pattern b where the sign bit is set and ~b & 0x7FFFFFFF where it is clear:
+// +inf 0x007FFFFF, +0 0x7FFFFFFF, -0 0x80000000, -inf 0xFF800000, NaN behind -inf, and every word below kNoWord.  The output holds S
+// itself, the inverse of the image (a NaN as 0x7FC00000), descending; the slots behind out_sizes[q] hold key 0xFFFFFFFF and -inf.
+// Skips, missing keys, duplicates, filters, the probed entry rule and the limits are the L2 rules word for word.  Range search has
+// no inner-product form.
+//
 // SQ8 rows (kSQ8): one byte per component under a per-dimension affine range, vmin[dim] and step[dim], both
 // finite, step >= 0; inv[i] = 1.0f / step[i] where step[i] > 0 (+inf for a subnormal step), else 0, derived once.  sq_encode,
 // sq_decode and sq_range below are the definition; a row's i-th component in D(q, x) is sq_decode of its byte, and `clamped` counts
@@ -51,6 +65,9 @@ constexpr uint32_t kNanImage = 0x7FC00000u;          // every NaN distance: behi
 constexpr uint32_t kInfImage = 0x7F800000u;
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;             // key of the slots behind out_sizes[q]
 constexpr uint64_t kNoWord = ~0ull;                  // a skipped or missing entry
+constexpr int kL2 = 0, kIP = 1;                      // QADC_REFINE_L2, QADC_REFINE_IP
+constexpr uint32_t kNanImageIP = 0xFFC00000u;        // every NaN score: behind -inf (0xFF800000)
+constexpr uint32_t kNegInfBits = 0xFF800000u;        // the score of the slots behind out_sizes[q] under kIP
 
 inline uint32_t float_bits(float f) {
     uint32_t u;
@@ -118,6 +135,41 @@ QADC_REFINE_NO_CONTRACT inline float distance(const float* q, int dim, RowAt x) 
 }
 
 inline uint32_t image(float d) { return d != d ? kNanImage : float_bits(d); }
+
+// S(q, x): x(i) gives the row's i-th component as a float
+template <typename RowAt>
+QADC_REFINE_NO_CONTRACT inline float score(const float* q, int dim, RowAt x) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    float p[64];
+    for (int l = 0; l < 64; ++l) p[l] = 0.0f;
+    for (int i = 0; i < dim; ++i) {
+        const float m = q[i] * x(i);
+        p[i & 63] = p[i & 63] + m;
+    }
+    for (int s = 32; s >= 1; s >>= 1)
+        for (int l = 0; l < s; ++l) p[l] = p[l] + p[l + s];
+    return p[0];
+}
+
+// the image of a score: ascending images are descending scores, NaN last
+inline uint32_t img_ip(float s) {
+    if (s != s) return kNanImageIP;
+    const uint32_t b = float_bits(s);
+    return (b & 0x80000000u) ? b : (~b & 0x7FFFFFFFu);
+}
+
+// the score of an image (the flip is its own inverse); every image behind -inf's is a NaN's and gives 0x7FC00000
+inline float img_ip_inverse(uint32_t img) {
+    if (img > kNegInfBits) return bits_float(kNanImage);
+    return bits_float((img & 0x80000000u) ? img : (~img & 0x7FFFFFFFu));
+}
+
+// the high half of a word under a metric, its inverse, and the bits of out_dist behind out_sizes[q]
+inline uint32_t image_of(float v, int metric) { return metric == kIP ? img_ip(v) : image(v); }
+inline float value_of(uint32_t img, int metric) { return metric == kIP ? img_ip_inverse(img) : bits_float(img); }
+inline uint32_t filler_bits(int metric) { return metric == kIP ? kNegInfBits : kInfImage; }
 
 // ---- SQ8 rows: IEEE binary32, every operation rounded by itself ----
 
@@ -315,6 +367,21 @@ struct store {
         const float* x = f32.data() + base;
         return distance(q, dim, [x](int i) { return x[i]; });
     }
+
+    float score_to(const float* q, uint32_t key) const {
+        const size_t base = (size_t)(key - lo) * dim;
+        if (dtype == kF16) {
+            const uint16_t* x = f16.data() + base;
+            return score(q, dim, [x](int i) { return half_to_float(x[i]); });
+        }
+        if (dtype == kSQ8) {
+            const uint8_t* x = sq8.data() + base;
+            const float *vmin = sq.vmin.data(), *step = sq.step.data();
+            return score(q, dim, [x, vmin, step](int i) { return sq_decode(x[i], vmin[i], step[i]); });
+        }
+        const float* x = f32.data() + base;
+        return score(q, dim, [x](int i) { return x[i]; });
+    }
 };
 
 // The keyed store (qadc_refine_create_keyed): a map from key to vector in place of a dense range.  holds(key)
@@ -406,6 +473,20 @@ struct keyed_store {
         const float* x = f32.find(key)->second.data();
         return distance(q, dim, [x](int i) { return x[i]; });
     }
+
+    float score_to(const float* q, uint32_t key) const {
+        if (dtype == kF16) {
+            const uint16_t* x = f16.find(key)->second.data();
+            return score(q, dim, [x](int i) { return half_to_float(x[i]); });
+        }
+        if (dtype == kSQ8) {
+            const uint8_t* x = sq8.find(key)->second.data();
+            const float *vmin = sq.vmin.data(), *step = sq.step.data();
+            return score(q, dim, [x, vmin, step](int i) { return sq_decode(x[i], vmin[i], step[i]); });
+        }
+        const float* x = f32.find(key)->second.data();
+        return score(q, dim, [x](int i) { return x[i]; });
+    }
 };
 
 // Read-back (qadc_refine_get): out [count][dim] = the rows of the listed keys as floats, decoded by the store's type; a key the
@@ -421,10 +502,10 @@ inline void get(const Store& s, const uint32_t* keys, uint64_t count, float* out
 
 // queries [nq][dim], keys [nq][r_in], counts [nq] or null (every count in [0, r_in]), values [nq][r_in] or null ->
 // out_keys [nq][R], out_dist [nq][R], out_sizes [nq]; returns the missing entries of all queries.  Store: store or keyed_store —
-// the definition reads a store through dim, holds and distance_to alone.
+// the definition reads a store through dim, holds and distance_to (kIP: score_to) alone.  metric: kL2 or kIP.
 template <typename Store>
 inline uint64_t rerank(const Store& s, int nq, const float* queries, int r_in, const uint32_t* keys, const int32_t* counts,
-                       const float* values, int R, uint32_t* out_keys, float* out_dist, int32_t* out_sizes) {
+                       const float* values, int R, uint32_t* out_keys, float* out_dist, int32_t* out_sizes, int metric = kL2) {
     uint64_t missing = 0;
     std::vector<uint64_t> words;
     for (int q = 0; q < nq; ++q) {
@@ -437,14 +518,16 @@ inline uint64_t rerank(const Store& s, int nq, const float* queries, int r_in, c
                 ++missing;
                 continue;
             }
-            words.push_back(((uint64_t)image(s.distance_to(queries + (size_t)q * s.dim, k[i])) << 32) | k[i]);
+            const float* qv = queries + (size_t)q * s.dim;
+            const float v = metric == kIP ? s.score_to(qv, k[i]) : s.distance_to(qv, k[i]);
+            words.push_back(((uint64_t)image_of(v, metric) << 32) | k[i]);
         }
         std::sort(words.begin(), words.end());
         words.erase(std::unique(words.begin(), words.end()), words.end());
         const int n = (int)std::min<size_t>((size_t)R, words.size());
         for (int j = 0; j < R; ++j) {
             out_keys[(size_t)q * R + j] = j < n ? (uint32_t)words[j] : kNoKey;
-            out_dist[(size_t)q * R + j] = bits_float(j < n ? (uint32_t)(words[j] >> 32) : kInfImage);
+            out_dist[(size_t)q * R + j] = j < n ? value_of((uint32_t)(words[j] >> 32), metric) : bits_float(filler_bits(metric));
         }
         out_sizes[q] = n;
     }
@@ -466,7 +549,7 @@ struct filter {
 // out_dist [nq][R], out_sizes [nq] = min(R, the keys that pass).
 template <typename Store>
 inline void knn(const Store& s, int nq, const float* queries, int R, const filter* f, uint32_t* out_keys, float* out_dist,
-                int32_t* out_sizes) {
+                int32_t* out_sizes, int metric = kL2) {
     std::vector<uint32_t> keys;
     for (uint32_t k : s.held_keys())
         if (!f || f->passes(k)) keys.push_back(k);
@@ -475,13 +558,13 @@ inline void knn(const Store& s, int nq, const float* queries, int R, const filte
         if (n == 0) {                // (rerank takes r_in >= 1)
             for (int j = 0; j < R; ++j) {
                 out_keys[(size_t)q * R + j] = kNoKey;
-                out_dist[(size_t)q * R + j] = bits_float(kInfImage);
+                out_dist[(size_t)q * R + j] = bits_float(filler_bits(metric));
             }
             out_sizes[q] = 0;
             continue;
         }
         rerank(s, 1, queries + (size_t)q * s.dim, n, keys.data(), nullptr, nullptr, R, out_keys + (size_t)q * R, out_dist + (size_t)q * R,
-               out_sizes + q);
+               out_sizes + q, metric);
     }
 }
 
@@ -502,7 +585,8 @@ struct probe_part {
 // store does not hold is missing and counted in the return value, per entry; a key that occurs several times is kept once.
 template <typename Store>
 inline uint64_t knn_probed(const Store& s, const probe_part* parts, int nparts, const filter* index_filter, int nq, const float* queries,
-                           int ma, const int32_t* assign, int R, const filter* f, uint32_t* out_keys, float* out_dist, int32_t* out_sizes) {
+                           int ma, const int32_t* assign, int R, const filter* f, uint32_t* out_keys, float* out_dist, int32_t* out_sizes,
+                           int metric = kL2) {
     uint64_t missing = 0;
     std::vector<uint32_t> keys;
     std::vector<int32_t> probed;
@@ -522,13 +606,13 @@ inline uint64_t knn_probed(const Store& s, const probe_part* parts, int nparts, 
         if (keys.empty()) {              // (rerank takes r_in >= 1)
             for (int j = 0; j < R; ++j) {
                 out_keys[(size_t)q * R + j] = kNoKey;
-                out_dist[(size_t)q * R + j] = bits_float(kInfImage);
+                out_dist[(size_t)q * R + j] = bits_float(filler_bits(metric));
             }
             out_sizes[q] = 0;
             continue;
         }
         missing += rerank(s, 1, queries + (size_t)q * s.dim, (int)keys.size(), keys.data(), nullptr, nullptr, R, out_keys + (size_t)q * R,
-                          out_dist + (size_t)q * R, out_sizes + q);
+                          out_dist + (size_t)q * R, out_sizes + q, metric);
     }
     return missing;
 }

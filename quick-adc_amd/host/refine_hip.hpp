@@ -4,7 +4,8 @@
 // rerank_range(), the exact radius query over the whole store and over a range result (section 11.21); knn_probed() and search_exact(),
 // the exact search over the partitions of an index a query probes (section 11.22).  search_refined() composes it with adc_search_engine_hip (host/adc_search_hip.hpp): the engine's search with
 // R = the engine's r as r_in, then the re-ranking of the heaps' keys, the FLT_MAX sentinels left out.  The definition both are held
-// to is host/refine.hpp.
+// to is host/refine.hpp.  set_metric(QADC_REFINE_IP) (section 11.23) makes rerank(), knn(), knn_probed() and the compositions rank by the
+// inner product, larger first: `dist` then holds the scores, descending, and -inf behind sizes[q]; range() and rerank_range() are L2 only.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -18,8 +19,8 @@ namespace qadc {
 
 struct refine_result {
     int r = 0;                            // slots per query
-    std::vector<std::uint32_t> keys;      // [nq][r], ascending by (distance, key); behind sizes[q]: 0xFFFFFFFF
-    std::vector<float> dist;              // [nq][r]; behind sizes[q]: +inf
+    std::vector<std::uint32_t> keys;      // [nq][r], ascending by (distance, key) — QADC_REFINE_IP: descending score, then key; behind sizes[q]: 0xFFFFFFFF
+    std::vector<float> dist;              // [nq][r]; behind sizes[q]: +inf (QADC_REFINE_IP: the scores, -inf)
     std::vector<std::int32_t> sizes;      // [nq]
     std::uint64_t missing = 0;            // candidates whose key the store does not hold
 };
@@ -51,6 +52,18 @@ struct refine_store_hip {
     static void die(const char* what) {
         std::cerr << what << ": " << qadc_last_error() << std::endl;
         std::exit(1);
+    }
+
+    // the metric of every later rerank, knn and knn_probed call (qadc_refine_set_metric): QADC_REFINE_L2 (the
+    // default) or QADC_REFINE_IP; host state only
+    void set_metric(int metric) {
+        if (qadc_refine_set_metric(store, metric) != QADC_OK) die("set_metric");
+    }
+
+    int metric() const {
+        int m = QADC_REFINE_L2;
+        if (qadc_refine_metric(store, &m) != QADC_OK) die("metric");
+        return m;
     }
 
     void reserve(std::uint64_t rows) {

@@ -73,6 +73,7 @@ SYMBOLS = [
     "qadc_adc_range_collect", "qadc_adc_range_collect_device",
     "qadc_refine_range", "qadc_refine_range_device", "qadc_refine_rerank_range", "qadc_refine_rerank_range_device",
     "qadc_refine_range_collect", "qadc_refine_range_collect_device", "qadc_refine_set_range_plan", "qadc_refine_range_reruns",
+    "qadc_refine_set_metric", "qadc_refine_metric",
 ]
 
 
@@ -332,6 +333,8 @@ def lib():
         L.qadc_refine_knn.argtypes = [C.c_void_p, C.c_int, f32p, C.c_int, C.c_void_p, u32p, f32p, i32p]
         L.qadc_refine_knn_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qadc_refine_set_knn_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+        L.qadc_refine_set_metric.argtypes = [C.c_void_p, C.c_int]
+        L.qadc_refine_metric.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.qadc_refine_knn_probed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, f32p, C.c_int, i32p, C.c_int, C.c_void_p, u32p, f32p, i32p,
                                              C.POINTER(C.c_uint64)]
         L.qadc_refine_knn_probed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -2335,6 +2338,8 @@ QADC_REFINE_F32, QADC_REFINE_F16, QADC_REFINE_MAX_IN = 0, 1, 8192   # include/qa
 QADC_REFINE_SQ8 = 2
 _REFINE_DTYPES = {"f32": QADC_REFINE_F32, "f16": QADC_REFINE_F16, "sq8": QADC_REFINE_SQ8}
 _REFINE_DTYPE_NAMES = {v: k for k, v in _REFINE_DTYPES.items()}
+QADC_REFINE_L2, QADC_REFINE_IP = 0, 1   # include/qadc.h
+_REFINE_METRICS = {"l2": QADC_REFINE_L2, "ip": QADC_REFINE_IP}
 
 
 def refine_sq_range(vectors, device=0):
@@ -2375,11 +2380,16 @@ class Refine:
     keyed=True (qadc_refine_create_keyed; section 11.14): a map from key to vector in place of the dense range, filled by put(),
     emptied by remove(); add() belongs to the dense kind, put() and remove() to the keyed one (QadcError otherwise).
     dtype="sq8" (qadc_refine_create_sq8; section 11.20): one byte per component under the range vmin=, step= (float32 [dim] each, as
-    refine_sq_range gives them); from_vectors() finds the range, creates and adds in one call."""
+    refine_sq_range gives them); from_vectors() finds the range, creates and adds in one call.
+    metric="ip" (qadc_refine_set_metric; section 11.23): rerank, knn, knn_probed and what is composed from them rank by the inner
+    product, larger first — `dist` then holds the scores, descending, and -inf behind sizes[q]; the range calls raise.  set_metric()
+    changes it at any time; the rows are the same under both."""
 
-    def __init__(self, dim, dtype="f32", device=0, keyed=False, vmin=None, step=None):
+    def __init__(self, dim, dtype="f32", device=0, keyed=False, vmin=None, step=None, metric="l2"):
         if dtype not in _REFINE_DTYPES:
             raise ValueError('dtype is "f32", "f16" or "sq8", not %r' % (dtype,))
+        if metric not in _REFINE_METRICS:
+            raise ValueError('metric is "l2" or "ip", not %r' % (metric,))
         self.dim, self.dtype, self.device, self.keyed = int(dim), dtype, device, bool(keyed)
         self._h = C.c_void_p()
         if dtype == "sq8":
@@ -2389,23 +2399,38 @@ class Refine:
             if vmin.shape[0] != self.dim or step.shape[0] != self.dim:
                 raise ValueError("vmin and step have %d and %d entries for dim %d" % (vmin.shape[0], step.shape[0], self.dim))
             _check(lib().qadc_refine_create_sq8(C.byref(self._h), self.dim, _p(vmin, f32p), _p(step, f32p), int(self.keyed), device))
+            self.set_metric(metric)
             return
         if vmin is not None or step is not None:
             raise ValueError('vmin= and step= belong to dtype "sq8"')
         create = lib().qadc_refine_create_keyed if keyed else lib().qadc_refine_create
         _check(create(C.byref(self._h), int(dim), _REFINE_DTYPES[dtype], device))
+        self.set_metric(metric)
+
+    def set_metric(self, metric):
+        """qadc_refine_set_metric: "l2" or "ip" for every later rerank, knn and knn_probed call; host state only"""
+        if metric not in _REFINE_METRICS:
+            raise ValueError('metric is "l2" or "ip", not %r' % (metric,))
+        _check(lib().qadc_refine_set_metric(self._h, _REFINE_METRICS[metric]))
+
+    @property
+    def metric(self):
+        """qadc_refine_metric: "l2" or "ip"."""
+        m = C.c_int(-1)
+        _check(lib().qadc_refine_metric(self._h, C.byref(m)))
+        return {v: k for k, v in _REFINE_METRICS.items()}[m.value]
 
     @classmethod
-    def from_vectors(cls, vectors, dtype="f32", device=0, first_key=0):
+    def from_vectors(cls, vectors, dtype="f32", device=0, first_key=0, metric="l2"):
         """A dense store holding vectors [n][dim] under the keys first_key ..; an "sq8" store takes the range of these vectors"""
         v = np.ascontiguousarray(vectors, np.float32)
         if v.ndim != 2:
             raise QadcError("vectors has shape %s, expected [n][dim]" % (v.shape,))
         if dtype == "sq8":
             vmin, step = refine_sq_range(v, device)
-            self = cls(v.shape[1], "sq8", device, vmin=vmin, step=step)
+            self = cls(v.shape[1], "sq8", device, vmin=vmin, step=step, metric=metric)
         else:
-            self = cls(v.shape[1], dtype, device)
+            self = cls(v.shape[1], dtype, device, metric=metric)
         if v.shape[0]:
             self.add(v, first_key)
         return self

@@ -1,7 +1,7 @@
 """Float-ADC engine for whole-byte PQ codes (pyqadc.AdcIndex, the GPU scanner_simple) on its reference shapes, with the
 single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Prints one line per leg and one JSON line.
 
-  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn,decode,refine_sq,refine_range,probe] [--iters N] [--out FILE]
+  python tools/adc_bench.py [--legs flat1e8,batch32,lone1e6,ivf,cpu,ivf_search,lone_search,add,remove,train,opq,seed,filter,qfilter,refine,range,keyed,knn,decode,refine_sq,refine_range,probe,refine_ip] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 4 [--legs lone,ivf_search,add,remove,train,opq,seed,filter] [--iters N] [--out FILE]
   python tools/adc_bench.py --bits 16 [--legs lone,ivf_search,encode16,add,remove,train,seed,filter] [--iters N] [--out FILE]
 
@@ -87,6 +87,11 @@ single-thread CPU scan_standard<uint8_t, 8> of the same box in the same run.  Pr
             K = 256, ma = 24, R = 100) with batches of 1024, 32 and 1 queries, in one process: AdcIndex.search_exact_device beside
             Refine.knn_device on the same store (the baseline: every row) and search_refined_device at r_in = 1000; recall@100 against
             knn of the probed exact result (the coarse quantizer's loss alone) and of search_refined at r_in 400 and 1000.
+  refine_ip the inner-product metric of a refine store (not in the default legs): 10^6 x 128-d rows, R = 100, f32,
+            f16 and sq8 stores; knn_device at 1024, 32 and 1 queries, rerank_device at r_in 400 and 1000 and search_exact_device at K = 256,
+            ma = 24, each under "ip" and under "l2" on the same store in the same process, 3 + 3 alternated runs; the reference is the L2 call
+            of the same build and the margin its own run-to-run spread; beside them the share of keys knn under "ip" has in common with
+            torch's (q @ x.T).topk (other arithmetic: a sanity figure)
   knn       exhaustive search over a refine store (not in the default legs): Refine.knn_device and Refine.knn
             on 10^6 rows of dim 128, float and half store, nq = 1, 32 and 1024, R = 100, from call to return, as pairs/s and as a share
             of the estimated roof of 2 x 10^11 pairs/s (3 dim component operations a pair at 32 packed non-FMA float operations per
@@ -1675,6 +1680,73 @@ def knn_leg(iters, res, torch):
         del held, norms
 
 
+def refine_ip_leg(res, torch, runs=3):
+    """Every exact call of a refine store under "ip" beside the same call under "l2" — the same store, the same process, `runs` + `runs`
+    alternated runs after one warm-up of each: the L2 call of the same build is the reference and its own spread the margin"""
+    if torch is None:
+        print("refine_ip leg: needs torch on the GPU (the rows are made there)", flush=True)
+        return
+    n, dim, K, ma = 1_000_000, 128, 256, 24
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device="cuda").manual_seed(11)
+    x = torch.randn((n, dim), generator=gen, device="cuda", dtype=torch.float32)
+    q_all = torch.randn((1024, dim), generator=gen, device="cuda", dtype=torch.float32)
+    centroids = x[torch.randperm(n, generator=gen, device="cuda")[:K]].contiguous()
+    part_of = torch.cat([torch.cdist(x[i:i + (1 << 17)], centroids).argmin(1) for i in range(0, n, 1 << 17)]).cpu().numpy()
+    rng = np.random.default_rng(11)
+    labels = [np.nonzero(part_of == k)[0].astype(np.uint32) for k in range(K)]
+    idx = pyqadc.AdcIndex(8, 8)
+    idx.add_partitions([rng.integers(0, 256, (len(l), 8), dtype=np.uint8) for l in labels], labels)   # (codes no call of this leg reads)
+    idx.set_pq(rng.normal(size=(8, 256, dim // 8)).astype(np.float32))
+    idx.set_coarse(centroids.cpu().numpy())
+    cand = {r_in: torch.from_numpy(rng.integers(0, n, (1024, r_in)).astype(np.int32)).to(dev) for r_in in (400, 1000)}
+    out = res.setdefault("refine_ip", {"rows": n, "dim": dim, "R": R, "K": K, "ma": ma, "runs_per_arm": runs})
+
+    def both(st, call):
+        """call() under "ip" and under "l2" in turn -> (times ip, times l2), seconds"""
+        def arm(metric):
+            st.set_metric(metric)
+            t0 = time.perf_counter()
+            call()
+            return time.perf_counter() - t0
+        arm("ip"), arm("l2")
+        t = {"ip": [], "l2": []}
+        for _ in range(runs):
+            for metric in ("ip", "l2"):
+                t[metric].append(arm(metric))
+        return t["ip"], t["l2"]
+
+    for dtype in ("f32", "f16", "sq8"):
+        if dtype == "sq8":
+            vmin, step = pyqadc.refine_sq_range_device(x)
+            st = pyqadc.Refine(dim, "sq8", vmin=vmin, step=step)
+        else:
+            st = pyqadc.Refine(dim, dtype)
+        st.add_device(x, 0)
+        calls = [("knn_device_nq%d" % nq, (lambda tq: lambda: st.knn_device(tq, R))(q_all[:nq].contiguous())) for nq in (1024, 32, 1)]
+        calls += [("rerank_device_rin%d" % r_in, (lambda k: lambda: st.rerank_device(q_all, k, R))(cand[r_in])) for r_in in (400, 1000)]
+        calls.append(("search_exact_device_ma%d" % ma, lambda: idx.search_exact_device(q_all, ma, R, st)))
+        for name, call in calls:
+            t_ip, t_l2 = both(st, call)
+            med_ip, med_l2 = float(np.median(t_ip)), float(np.median(t_l2))
+            spread = max(t_l2) - min(t_l2)
+            verdict = "no slower" if med_ip <= med_l2 + spread else "slower"
+            out["%s_%s" % (dtype, name)] = {"ip_ms": [t * 1e3 for t in t_ip], "l2_ms": [t * 1e3 for t in t_l2], "ip_median_ms": med_ip * 1e3,
+                                            "l2_median_ms": med_l2 * 1e3, "l2_spread_ms": spread * 1e3, "verdict": verdict}
+            print("refine_ip %s %s: ip %.3f ms, l2 %.3f ms (medians of %d alternated runs; l2 ran %.3f .. %.3f): ip is %s than l2 within l2's spread"
+                  % (dtype, name, med_ip * 1e3, med_l2 * 1e3, runs, min(t_l2) * 1e3, max(t_l2) * 1e3, verdict), flush=True)
+        st.set_metric("ip")
+        tq = q_all[:32].contiguous()
+        keys = st.knn_device(tq, R)[0].cpu().numpy().view(np.uint32)
+        want = torch.topk(tq @ x.T, R, dim=1).indices.cpu().numpy()
+        share = float(np.mean([len(set(a.tolist()) & set(b.tolist())) for a, b in zip(keys, want)])) / R
+        out["%s_share_of_keys_in_common_with_torch_topk" % dtype] = share
+        print("refine_ip %s: knn under ip shares %.4f of its keys with torch's (q @ x.T).topk over the float rows (32 queries)" % (dtype, share),
+              flush=True)
+        st.close()
+    idx.close()
+
+
 def refine_range_leg(iters, res, torch):
     """Exact range search over 10^6 rows of dim 128, F32 and F16, in one process:
     (a) Refine.range_device under radii that keep about 100 and about 10^4 rows per query beside Refine.knn_device(R = 100) at the same
@@ -1968,7 +2040,7 @@ def main():
                 f.write(line + "\n")
         return
     torch = None
-    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs or "decode" in legs or "refine_sq" in legs or "refine_range" in legs or "probe" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
+    if "ivf" in legs or "filter" in legs or "refine" in legs or "keyed" in legs or "knn" in legs or "decode" in legs or "refine_sq" in legs or "refine_range" in legs or "probe" in legs or "refine_ip" in legs:   # the device-memory arm hands a torch tensor over; torch's HIP runtime has to come up before the library's
         try:
             import torch
             torch.zeros(1, device="cuda")
@@ -2075,6 +2147,8 @@ def main():
         knn_leg(a.iters, res, torch)
     if "refine_range" in legs:
         refine_range_leg(a.iters, res, torch)
+    if "refine_ip" in legs:
+        refine_ip_leg(res, torch)
     if "decode" in legs:
         decode_leg(8, a.iters, res, torch)
     line = json.dumps(res)
